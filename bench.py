@@ -58,7 +58,74 @@ def parse():
     ap.add_argument("--no-whole-file", action="store_true", help="skip the saveSpz / loadSpz figure (outside the timed region)")
     ap.add_argument("--cpu-sample-points", type=int, default=0, help="0 = the whole per-GPU workload")
     ap.add_argument("--traffic-file", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed on rank 0 to DIR/<name>.npy (float32/"
+                         "float64, finite; a decoded array's infinities, e.g. alphas of bytes 0 and 255, are coded in "
+                         "<name>_nonfinite.npy): the decoded arrays and the stream they were decoded from, for a fixed, "
+                         "seeded sample of the points (all of them up to %d), so that two builds can be compared output "
+                         "for output"
+                         % DUMP_SAMPLE_POINTS)
     return ap.parse_args()
+
+
+# --dump-outputs: at most this many points, i.e. 65536 x (59 floats + their 59 non-finite codes + 65 stream bytes, each
+# stored as float32) = 48 MB for SH3 v3, inside the 64 MB the dump may take
+DUMP_SAMPLE_POINTS = 1 << 16
+SECTION_NAMES = ("positions", "alphas", "colors", "scales", "rotations", "sh")   # abi.SEC_* order
+
+
+def dump_sample_index(count):
+    """The points a dump covers: all of them, or a fixed, seeded, sorted sample of DUMP_SAMPLE_POINTS."""
+    import numpy as np
+    if count <= DUMP_SAMPLE_POINTS:
+        return np.arange(count, dtype=np.int64)
+    return np.sort(np.random.default_rng(20261015).choice(count, DUMP_SAMPLE_POINTS, replace=False))
+
+
+def dump_outputs(path, out, n, deg, stream, stream_layout, stream_points):
+    """Write the decoded cloud `out` (n points) and the byte stream it was decoded from (stream_points points,
+    laid out as stream_layout) as .npy files: float arrays as float32 rows [point][float], stream bytes as float32
+    rows [point][byte] per section, the 16 header bytes, and the sampled point indices as float64.
+
+    Every file holds finite numbers only.  The decode has non-finite results by design (alpha bytes 0 and 255 decode
+    to -inf and +inf, the reference's invSigmoid; tests/golden/tables.npz), so each decoded array <name> is written as
+    two: <name>.npy with those entries set to 0, and <name>_nonfinite.npy coding them (0 finite, 1 +inf, -1 -inf,
+    2 NaN).  Together they are the decoded floats exactly."""
+    import numpy as np
+    import torch
+    from spz_amd import abi
+    from spz_amd.synth import FIELDS, floats_per_point
+    os.makedirs(path, exist_ok=True)
+    files = {}
+
+    def save(name, a):
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        files[name] = int(a.nbytes)
+
+    idx = dump_sample_index(n)
+    idx_t = torch.from_numpy(idx).to(out[FIELDS[0]].device)
+    save("sample_index", idx.astype(np.float64))
+    for k in FIELDS:
+        w = floats_per_point(k, deg)
+        if w:
+            a = out[k][: n * w].view(n, w).index_select(0, idx_t).cpu().numpy().astype(np.float32)
+            code = np.select([np.isposinf(a), np.isneginf(a), np.isnan(a)], [1, -1, 2], 0).astype(np.float32)
+            save(k, np.where(code == 0, a, np.float32(0)))
+            save(f"{k}_nonfinite", code)
+    if stream_points != n:
+        idx = dump_sample_index(stream_points)
+        idx_t = torch.from_numpy(idx).to(stream.device)
+        save("stream_sample_index", idx.astype(np.float64))
+    save("stream_header", stream[:16].cpu().numpy().astype(np.float32))
+    for sec in range(abi.NUM_SECTIONS):
+        w, o = int(stream_layout.bytes_per_point[sec]), int(stream_layout.offset[sec])
+        if w:
+            rows = stream[o:o + stream_points * w].view(stream_points, w).index_select(0, idx_t)
+            save(f"stream_{SECTION_NAMES[sec]}", rows.cpu().numpy().astype(np.float32))
+    return {"dir": path, "points": n, "points_sampled": int(len(dump_sample_index(n))), "bytes": sum(files.values()),
+            "files": sorted(files),
+            "note": "<name>_nonfinite codes the entries of decoded array <name> that are not finite (1 +inf, -1 -inf, "
+                    "2 NaN); <name> holds 0 there"}
 
 
 KERNEL_SOURCES = ("spz_amd/csrc/spz_kernels.hip", "spz_amd/csrc/spz_kernel_params.hpp", "spz_amd/csrc/spz_abi.hip")
@@ -443,8 +510,9 @@ def main():
     except Exception:  # noqa: BLE001  (no roctx in this process: the summary then covers every launch)
         marked = False
     t0 = time.perf_counter()
+    last_b = None
     for k in range(K):
-        step(k, True)
+        last_b = step(k, True)
     fence()
     elapsed = time.perf_counter() - t0
     if marked:
@@ -453,6 +521,17 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    # --dump-outputs: what the last timed step left, before anything below reuses its buffers
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        if route == "ipc":
+            d_stream, d_layout, d_points = views[last_b], plan.layout, plan.num_points
+        elif use_coll:
+            d_stream, d_layout, d_points = global_streams[last_b], plan.layout, plan.num_points
+        else:
+            d_stream, d_layout, d_points = streams[last_b], lay, n
+        dumped = dump_outputs(args.dump_outputs, out, n, deg, d_stream, d_layout, d_points)
 
     # N>1: the same K steps once more WITHOUT the exchange (every rank encodes and decodes its own shard,
     # nothing crosses xGMI), so the line shows what the kernels sustain next to the link-bound headline.
@@ -588,6 +667,8 @@ def main():
             "config4_fused_vs_two_pass": two_pass,
             "placement": placement,
         }
+        if dumped is not None:
+            res["outputs_dumped"] = dumped
         if world == 1 and not args.no_cpu_baseline:
             def gpu_stream_fn(m):
                 sub = {k: cloud[k][: m * floats_per_point(k, deg)] for k in FIELDS}

@@ -93,17 +93,20 @@ def test_self_check_against_zlib_prefix():
     assert spz._compress_gzipped_exact(data, 4, 8, 1 << 30) == want             # prefix = whole input
 
 
-def test_default_save_path_on_a_real_stream_equals_zlib_and_the_reference(reference):
+def test_default_save_path_on_a_real_stream_equals_zlib_and_the_reference(oracle, reference_digests):
     """A 19.5 MB SH3 stream and a 1.3 MB one (above the 1 MiB switch-over of compressGzipped): the default container bytes
-    equal zlib's and the reference's own compressGzipped."""
+    equal zlib's and the reference's own compressGzipped (recorded, tests/golden/reference_digests.json)."""
+    from conftest import digest, digest_cloud
     from spz_amd.synth import make_cloud_numpy
     n = 300_000
     c = make_cloud_numpy(n, 3, 21)
-    stream = reference.pack(c, n, 3, False, 6)
+    assert digest_cloud(c) == reference_digests["exact_gzip/input"], "the input generator changed"
+    stream = oracle.pack(c, n, 3, False, 6)
+    assert digest(stream) == reference_digests["exact_gzip/pack"], "the stream differs from the reference's"
     raw = stream.tobytes()
     got = spz._compress_gzipped(raw)
     assert got == zlib_gzip(raw)
-    assert got == reference.compress_gzipped(stream).tobytes()
+    assert digest(got) == reference_digests["exact_gzip/gzip"], "the member differs from the reference's compressGzipped"
     assert spz._decompress_gzipped(got) == raw
     small = raw[: 16 + 65 * 20000]
     assert spz._compress_gzipped(small) == zlib_gzip(small)

@@ -613,15 +613,18 @@ def test_baseline_config2_1m_sh0_v2(dev, oracle):
         assert_bits_equal(u[k], w[k], f"cfg2 decode {k}")
 
 
-def test_baseline_config1_ply_to_spz_60k(dev, reference, tmp_path):
+def test_baseline_config1_ply_to_spz_60k(dev, reference_digests, tmp_path):
     """BASELINE configs[0]: a 60 k-point SH3 .ply (synthetic stand-in for the absent
     samples/mic_60k.ply) -> .spz with the CLI's options (UNSPECIFIED/UNSPECIFIED).
     The .spz file must be byte-identical to the reference's saveSpz of the same cloud, and load
-    back to the reference's floats."""
+    back to the reference's floats (both recorded, tests/golden/reference_digests.json)."""
     import spz_amd.spz as spz
+    from conftest import digest, digest_cloud
     from spz_amd.synth import make_cloud_numpy
+    ref = reference_digests
     n, deg = 60_000, 3
     c = make_cloud_numpy(n, deg, 60)
+    assert digest_cloud(c) == ref["config1/input"], "the input generator changed"
     src = spz.GaussianCloud()
     src.sh_degree = deg
     for k in FIELDS:
@@ -633,44 +636,44 @@ def test_baseline_config1_ply_to_spz_60k(dev, reference, tmp_path):
         assert np.array_equal(getattr(loaded, k), c[k]), k  # PLY is lossless
     out = str(tmp_path / "mic_60k_standin.spz")
     assert spz.save_spz(loaded, spz.PackOptions(), out) is True
-    want = reference.save_spz(c, n, deg, False, 0)
-    assert open(out, "rb").read() == want.tobytes(), ".spz bytes differ from the reference's saveSpz"
+    assert digest(open(out, "rb").read()) == ref["config1/save"], ".spz bytes differ from the reference's saveSpz"
     back = spz.load_spz(out, spz.UnpackOptions())
-    ref_back = reference.load_spz(want, n, deg, 0)
+    assert back.num_points == ref["config1/load_to0/num_points"] == n
     for k in FIELDS:
-        assert_bits_equal(getattr(back, k), ref_back[k], f"cfg1 load {k}")
+        assert digest(getattr(back, k)) == ref[f"config1/load_to0/{k}"], f"cfg1 load {k}"
 
 
-def test_cli_tools_round_trip(dev, reference, tmp_path):
+def test_cli_tools_round_trip(dev, reference_digests, tmp_path):
     """The reference's three CLI tools (cli_tools/src/*.cpp) rebuilt over the drop-in layer:
     ply_to_spz produces the reference's .spz bytes, spz_to_ply the reference's .ply bytes,
-    spz_info the reference's report."""
+    spz_info the reference's report (all recorded, tests/golden/reference_digests.json)."""
     import subprocess
-    from conftest import ROOT
+    import spz_amd.spz as spz
+    from conftest import ROOT, digest, digest_cloud
     from spz_amd.synth import make_cloud_numpy
     import os
+    ref = reference_digests
     bin_dir = os.path.join(ROOT, "spz_amd", "bin")
     n, deg = 4321, 2
     c = make_cloud_numpy(n, deg, 77)
+    assert digest_cloud(c) == ref["cli/input"], "the input generator changed"
     ply = str(tmp_path / "in.ply")
-    assert reference.save_ply(c, n, deg, 0, ply) == 0          # a .ply written by the reference
+    src = spz.GaussianCloud()
+    src.sh_degree = deg
+    for k in FIELDS:
+        setattr(src, k, c[k])
+    assert spz.save_splat_to_ply(src, spz.PackOptions(), ply) is True
+    assert digest(open(ply, "rb").read()) == ref["cli/ply_in"]  # the very .ply the reference writes for c
     spz_out, ply_out = str(tmp_path / "out.spz"), str(tmp_path / "back.ply")
     r = subprocess.run([os.path.join(bin_dir, "ply_to_spz"), ply, spz_out], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr
-    want = reference.save_spz(c, n, deg, False, 0)
-    assert open(spz_out, "rb").read() == want.tobytes()
+    assert digest(open(spz_out, "rb").read()) == ref["cli/save"]
     r = subprocess.run([os.path.join(bin_dir, "spz_to_ply"), spz_out, ply_out], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr
-    back = reference.load_spz(want, n, deg, 0)
-    ref_ply = str(tmp_path / "ref_back.ply")
-    assert reference.save_ply(back, n, deg, 0, ref_ply) == 0
-    assert open(ply_out, "rb").read() == open(ref_ply, "rb").read()
+    assert digest(open(ply_out, "rb").read()) == ref["cli/ply_back"]
     r = subprocess.run([os.path.join(bin_dir, "spz_info"), spz_out], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and f"Number of points: {n}" in r.stdout and "Bounding box:" in r.stdout
-    p = back["positions"].reshape(-1, 3)
-    import io
-    want_lines = [f"  {a}: {lo:g} to {hi:g}" for a, lo, hi in zip("XYZ", p.min(0), p.max(0))]
-    for line in want_lines:
+    for line in ref["cli/info_lines"]:
         assert line in r.stdout, (line, r.stdout)
     r = subprocess.run([os.path.join(bin_dir, "spz_info")], capture_output=True, text=True, timeout=60)
     assert r.returncode == 1 and "Usage: spz_info" in r.stderr

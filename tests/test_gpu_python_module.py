@@ -455,14 +455,17 @@ def test_median_scale_sum_device_entry_point_10m(cuda):
     assert rc == abi.OK and np.float32(out.item()).tobytes() == np.float32(want).tobytes()
 
 
-def test_whole_file_of_a_large_cloud_equals_the_reference_file(spz, reference):
+def test_whole_file_of_a_large_cloud_equals_the_reference_file(spz, reference_digests):
     """saveSpz of a 120 k-point SH3 cloud (7.8 MB stream: the GPU pack, then the multi-threaded exact gzip
     writer) is the reference's file byte for byte (the reference build's own saveSpz on the same arrays),
     and loadSpz of the reference's file (large enough for the parallel inflater on a many-core host) gives
-    the reference's floats."""
+    the reference's floats (both recorded, tests/golden/reference_digests.json)."""
+    from conftest import digest, digest_cloud
     from spz_amd.synth import make_cloud_numpy
+    ref = reference_digests
     n, deg = 120_000, 3
     c = make_cloud_numpy(n, deg, 77)
+    assert digest_cloud(c) == ref["whole_file/input"], "the input generator changed"
     g = spz.GaussianCloud()
     g.sh_degree = deg
     g.antialiased = True
@@ -470,8 +473,8 @@ def test_whole_file_of_a_large_cloud_equals_the_reference_file(spz, reference):
         setattr(g, k, c[k])
     o = spz.PackOptions()
     o.from_coord = spz.RDF
-    want = reference.save_spz(c, n, deg, True, 6).tobytes()
-    assert spz._save_spz_bytes(g, o) == want
+    want = spz._save_spz_bytes(g, o)
+    assert digest(want) == ref["whole_file/save"], ".spz bytes differ from the reference's saveSpz"
     # the same with the writer's opt-in checks switched on: SPZ_AMD_GZIP_VERIFY=1 inflates the finished member
     # and compares it with the stream, =2 also runs zlib over the whole stream and compares the two members
     for level in ("1", "2"):
@@ -482,11 +485,10 @@ def test_whole_file_of_a_large_cloud_equals_the_reference_file(spz, reference):
             del os.environ["SPZ_AMD_GZIP_VERIFY"]
     u = spz.UnpackOptions()
     u.to_coord = spz.LUF
-    back = spz._load_spz_bytes(want, u)
-    ref = reference.load_spz(np.frombuffer(want, np.uint8), n, deg, 7)
-    assert back.num_points == n and back.antialiased is True
+    back = spz._load_spz_bytes(want, u)                # want is the reference's file (equal digests)
+    assert back.num_points == ref["whole_file/load_to7/num_points"] == n and back.antialiased is True
     for k in FIELDS:
-        assert_bits_equal(getattr(back, k), ref[k], k)
+        assert digest(getattr(back, k)) == ref[f"whole_file/load_to7/{k}"], k
 
 
 def test_file_name_overloads_of_a_file_above_16_mib(spz, tmp_path):

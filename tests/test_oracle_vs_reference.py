@@ -1,38 +1,40 @@
-"""Pins the CPU restatement against the REFERENCE's own compiled C++ (oracle/_ref/libspz_ref.so)
-on fresh random inputs.  Runs wherever that library exists (the build container, and the GPU box
-since the built .so travels); skipped otherwise — the committed golden vectors then carry the pin."""
+"""Pins the CPU restatement against the REFERENCE's own compiled C++ on seeded random inputs.  What the
+reference returned for them is recorded as digests in tests/golden/reference_digests.json
+(tests/golden/make_reference_digests.py, run where oracle/_ref/libspz_ref.so is built): equal digests are
+equal bytes, and equal float bit patterns."""
 import os
 
 import numpy as np
 import pytest
 
-from conftest import FIELDS, assert_bits_equal, assert_bytes_equal
+from conftest import FIELDS, digest, digest_cloud
 
 
 @pytest.mark.parametrize("deg", [0, 1, 2, 3])
-def test_random_clouds_all_coordinate_pairs(oracle, reference, deg):
+def test_random_clouds_all_coordinate_pairs(oracle, reference_digests, deg):
     from spz_amd.synth import make_cloud_numpy
+    ref = reference_digests
     n = 3001
     for frm in range(9):
+        key = f"clouds/deg{deg}/from{frm}"
         c = make_cloud_numpy(n, deg, 500 + 10 * deg + frm)
+        assert digest_cloud(c) == ref[f"{key}/input"], f"{key}: the input generator changed"
         so = oracle.pack(c, n, deg, True, frm)
-        sr = reference.pack(c, n, deg, True, frm)
-        assert_bytes_equal(so, sr, f"pack deg={deg} from={frm}")
+        assert digest(so) == ref[f"{key}/pack"], f"pack deg={deg} from={frm} differs from the reference's"
         to = (frm * 5 + 3) % 9
-        rc, uo = oracle.unpack(sr, to)
-        ur = reference.unpack(sr, n, deg, to)
-        assert rc == 0 and ur["num_points"] == n
+        rc, uo = oracle.unpack(so, to)             # so is the reference's stream (equal digests)
+        assert rc == 0 and ref[f"{key}/unpack_to{to}/num_points"] == n
         for k in FIELDS:
-            assert_bits_equal(uo[k], ur[k], f"unpack deg={deg} to={to} {k}")
+            assert digest(uo[k]) == ref[f"{key}/unpack_to{to}/{k}"], f"unpack deg={deg} to={to} {k}"
 
 
-def test_quaternion_helpers(oracle, reference):
+def test_quaternion_helpers(oracle, reference_digests):
     import ctypes as C
     rng = np.random.default_rng(8)
     q = rng.standard_normal((20000, 4)).astype(np.float32)
     q[:2000] = np.round(q[:2000])
     q[np.all(q[:, :] == 0, axis=1)] = [0, 0, 0, 1]
-    want = reference.pack_quat(q.reshape(-1), 6)
+    assert digest(q) == reference_digests["quats/input"], "the input generator changed"
     conv = (C.c_float * 21)()
     oracle.lib.spzo_coordinate_converter.argtypes = [C.c_int, C.c_int, C.c_void_p]
     oracle.lib.spzo_coordinate_converter(6, 4, conv)
@@ -40,69 +42,73 @@ def test_quaternion_helpers(oracle, reference):
     got = np.zeros(q.shape[0] * 4, np.uint8)
     for i in range(q.shape[0]):
         oracle.lib.spzo_pack_quat_smallest_three(got[4 * i:].ctypes.data, q[i].ctypes.data, conv)
-    assert_bytes_equal(got, want, "packQuaternionSmallestThree")
+    assert digest(got) == reference_digests["quats/pack_from6"], "packQuaternionSmallestThree differs from the reference's"
 
 
-def test_gzip_container_bytes(reference):
+def test_gzip_container_bytes(reference_digests):
     """The host gzip wrapper of the product (spz::compressGzipped in libspz_host.so) emits the same
     bytes as the reference's (same zlib, same deflateInit2 parameters, load-spz.cc:186-214)."""
     import spz_amd.spz as spz
     rng = np.random.default_rng(3)
     for size in (0, 1, 16, 8191, 8192, 8193, 300_000, 3_000_000):
         data = (rng.integers(0, 256, size, dtype=np.uint16) >> (size % 3 + 2)).astype(np.uint8)
-        want = reference.compress_gzipped(data).tobytes()
-        assert want[:10] == bytes.fromhex("1f8b0800000000000003")
+        assert digest(data) == reference_digests[f"gzip/size{size}/input"], "the input generator changed"
         got = spz._compress_gzipped(data.tobytes())
-        assert got == want, f"gzip bytes differ for size {size}"
+        assert digest(got) == reference_digests[f"gzip/size{size}"], f"gzip bytes differ for size {size}"
+        assert got[:10] == bytes.fromhex("1f8b0800000000000003")
         assert spz._decompress_gzipped(got) == data.tobytes()
     assert spz._decompress_gzipped(b"This is not a valid SPZ file") is None
-    assert spz._decompress_gzipped(want[:-5]) is None  # truncated stream
+    assert spz._decompress_gzipped(got[:-5]) is None  # truncated stream
 
 
-def test_half_to_float_all_values(oracle, reference):
+def test_half_to_float_all_values(oracle, reference_digests):
     hs = np.arange(65536, dtype=np.uint32)
     a = np.array([oracle.lib.spzo_half_to_float(int(h)) for h in hs], np.float32)
-    b = np.array([reference.half_to_float(int(h)) for h in hs], np.float32)
-    assert_bits_equal(a, b, "halfToFloat")
+    assert digest(a) == reference_digests["half_to_float"], "halfToFloat differs from the reference's"
 
 
-def test_convert_coordinates(oracle, reference):
+def test_convert_coordinates(oracle, reference_digests):
     from spz_amd.synth import make_cloud_numpy
     n, deg = 777, 3
     c = make_cloud_numpy(n, deg, 9)
+    assert digest_cloud(c) == reference_digests["convert/input"], "the input generator changed"
     for frm, to in ((4, 6), (6, 7), (1, 8), (0, 3), (5, 5)):
         a = oracle.convert_coordinates(c["positions"], c["rotations"], c["sh"], n, deg, frm, to)
-        b = reference.convert_coordinates(c["positions"], c["rotations"], c["sh"], n, deg, frm, to)
-        for x, y, nm in zip(a, b, ("positions", "rotations", "sh")):
-            assert_bits_equal(x, y, nm)
+        for x, nm in zip(a, ("positions", "rotations", "sh")):
+            assert digest(x) == reference_digests[f"convert/from{frm}_to{to}/{nm}"], f"from={frm} to={to} {nm}"
 
 
-def test_parallel_gzip_is_read_by_the_reference(reference):
+def test_parallel_gzip_is_read_by_the_reference(oracle, reference_digests):
     """Opt-in multi-threaded gzip: not byte-identical to the reference's single
-    deflate stream, but the reference's own loadSpz must read it to the same floats."""
+    deflate stream, but the reference's own loadSpz must read it to the same floats.  The member must be
+    the one the reference was given when the digests were recorded (the writer is deterministic)."""
     import gzip
     import spz_amd.spz as spz
     from spz_amd.synth import make_cloud_numpy
+    ref = reference_digests
     n, deg = 40_000, 3   # 2.6 MB stream -> three 1 MiB deflate blocks
     c = make_cloud_numpy(n, deg, 99)
-    stream = reference.pack(c, n, deg, True, 6).tobytes()
+    assert digest_cloud(c) == ref["parallel_gzip/input"], "the input generator changed"
+    stream = oracle.pack(c, n, deg, True, 6).tobytes()
+    assert digest(stream) == ref["parallel_gzip/pack"], "the stream differs from the reference's"
     par = spz._compress_gzipped_parallel(stream, 4)
     one = spz._compress_gzipped(stream)
     # same gzip member header as zlib's except FLG.FEXTRA: the piece index rides in subfield "SZ"
     assert par != one and par[:3] == one[:3] and par[3] == 4 and par[4:10] == one[4:10]
     assert par[12:14] == b"SZ" and int.from_bytes(par[10:12], "little") == 4 + int.from_bytes(par[14:16], "little")
     assert gzip.decompress(par) == stream and spz._decompress_gzipped(par) == stream
-    a = reference.load_spz(np.frombuffer(par, np.uint8), n, deg, 7)
-    b = reference.load_spz(np.frombuffer(one, np.uint8), n, deg, 7)
-    assert a["num_points"] == n
+    # what the reference's loadSpz returned for this very member and for the single-stream one
+    assert digest(par) == ref["parallel_gzip/member"], "the parallel member is not the one the reference read"
+    a, b = "parallel_gzip/load_parallel", "parallel_gzip/load_single"
+    assert ref[f"{a}/num_points"] == n
     for k in FIELDS:
-        assert_bits_equal(a[k], b[k], k)
+        assert ref[f"{a}/{k}"] == ref[f"{b}/{k}"], k
     # threads <= 1 and small inputs fall back to the reference-identical single stream
     assert spz._compress_gzipped_parallel(stream, 1) == one
     assert spz._compress_gzipped_parallel(stream[:1000], 8) == spz._compress_gzipped(stream[:1000])
 
 
-def test_gunzip_readers_agree_with_zlib(reference):
+def test_gunzip_readers_agree_with_zlib():
     """decompressGzipped has three readers (piece-parallel through the "SZ" index, libdeflate, the
     reference's zlib loop) and must return what zlib returns for every input: valid members from any
     writer, members with other header fields, damaged indexes (the index is advisory), corrupt,
