@@ -212,6 +212,51 @@ int spz_amd_decode_gather_device(const uint8_t *d_stream, size_t size, const spz
                                  const uint32_t *d_indices, uint64_t count, int to_coord,
                                  const spz_amd_cloud_out *d_cloud, void *hip_stream);
 
+/* ---- filter: a smaller stream out of a packed one without requantising (spz_filter.hip; DESIGN §8 "filter").  The
+ *      reference has no counterpart (its only route is load -> floats -> save, which re-encodes).  Output point k is
+ *      input point idx[k] with all its bytes; its sh bytes are the first 3*dim(d') of its 3*dim(d) (layout
+ *      [N][coeff][rgb], lower bands first, so lowering the degree drops a suffix of every record).
+ *
+ *      select: the indices of the points whose predicates all hold, in input order: d_mask[i] != 0 (d_mask: NULL or
+ *      num_points bytes of device memory), the box lo[a] <= p[a] <= hi[a] on every axis with p the position as
+ *      decode (to_coord) returns it (a NaN position is never inside), the decoded alpha logit >= min_alpha (byte 0 is
+ *      -inf, byte 255 +inf).  sel == NULL, or no flag set, and no mask: every point.  A NaN bound or threshold is
+ *      SPZ_AMD_ERR_INVALID_ARG.  d_indices: room for hdr->num_points indices; d_workspace:
+ *      spz_amd_filter_workspace_bytes(num_points) bytes of device memory owned by the caller for the call (any
+ *      alignment).  Three launches on hip_stream (select, scan of the tile counts, compaction), then it BLOCKS until
+ *      the count is in *h_count.
+ *      subset: writes the count-point stream (header: count, degree d', the input's version, fractionalBits and
+ *      antialiased bit, reserved 0; then the six sections) into d_out (capacity >= spz_amd_stream_layout(count, d',
+ *      version).total_bytes).  sh_degree: -1 = the input's, 0 .. the input's = lower it; higher is
+ *      SPZ_AMD_ERR_INVALID_ARG.  Indices >= hdr->num_points are clamped to the last point (check them first: the host
+ *      form, spz::filterSpz and spz_amd.device.subset reject them).  Enqueued on hip_stream, no synchronisation. --- */
+typedef struct {
+  int32_t to_coord;        /* UnpackOptions::to of the positions the box is tested on */
+  int32_t use_box;         /* != 0: box_lo / box_hi apply (inclusive) */
+  float box_lo[3], box_hi[3];
+  int32_t use_min_alpha;   /* != 0: min_alpha applies */
+  float min_alpha;
+} spz_amd_selection;
+uint64_t spz_amd_filter_workspace_bytes(uint64_t num_points);
+int spz_amd_select_device(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, const spz_amd_selection *sel,
+                          const uint8_t *d_mask, uint32_t *d_indices, void *d_workspace, uint64_t *h_count,
+                          void *hip_stream);
+int spz_amd_subset_device(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, const uint32_t *d_indices,
+                          uint64_t count, int sh_degree, uint8_t *d_out, size_t capacity, void *hip_stream);
+/* Host form of the pair for a stream already in device memory (spz_amd_inflate_device_data, spz::filterSpz): either
+ * the caller's index list (use_indices != 0; h_indices[0 .. num_indices), each < num_points, else
+ * SPZ_AMD_ERR_INVALID_ARG before anything is copied; sel must then set no predicate and h_mask be NULL) or the
+ * selection of sel / h_mask (host memory, num_points bytes) goes through the two calls above on `device`, on a stream
+ * of the call's own.  Blocking.  The result stays in device memory in *ctx: *h_count points, *h_out_bytes bytes; fetch
+ * copies it out, device_data is its address (valid until close), close frees it.  h_ms (may be NULL): [0] wall-clock
+ * milliseconds of upload + select, [1] of the subset. */
+int spz_amd_filter_open(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, const spz_amd_selection *sel,
+                        const uint8_t *h_mask, int use_indices, const uint32_t *h_indices, uint64_t num_indices,
+                        int sh_degree, int device, void **ctx, uint64_t *h_count, uint64_t *h_out_bytes, float *h_ms);
+int spz_amd_filter_fetch(void *ctx, uint8_t *h_out);
+const uint8_t *spz_amd_filter_device_data(void *ctx);
+void spz_amd_filter_close(void *ctx);
+
 /* ---- device buffers for a resident cloud, placed for speed (spz_place.hip).  Whether an sh3 decode runs
  *      at 0.46 ms or at 0.55 ms is decided by whether the sh float array shares a physical region of HBM with the other
  *      arrays of the launch; that cannot be asked for, but it shows in one launch.  alloc: the five small arrays (and a

@@ -27,6 +27,7 @@
 #include <array>
 #include <cstdint>
 #include <iosfwd>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -259,6 +260,34 @@ const char *deviceInflateLastDecline();
 // saveSpz keeps its transient stream buffer (65 bytes per Gaussian, at most 1 GiB) for the next save, because returning
 // memory that device copies have pinned costs ~80 ms per GB; this drops it.  (The device side: spz_amd_release_device_memory().)
 void releaseHostMemory();
+// Filter (DESIGN §8 "filter"): a smaller .spz out of an existing one without requantising.  The member is inflated
+// (loadSpzPackedDevice, on the device where the device reader takes it), the points are chosen and the K-point stream is
+// cut out of the packed sections in HBM (spz_amd_filter_open: spz_amd_select_device + spz_amd_subset_device), and the
+// stream goes through compressGzipped — with zlib's level-6 bytes, as saveSpz's.  Output point k is input point idx[k]
+// with all its bytes (so the kept points decode to the same floats, bit for bit); its sh bytes are the first 3*dim(d') of
+// its record.  The header keeps the input's version, fractionalBits and antialiased bit (reserved 0).
+// Choosing idx: EITHER `indices` (any order, duplicates allowed, each < numPoints, at most 10 M) OR the selection — the
+// points for which every given predicate holds, in input order: mask[i] != 0 (numPoints bytes); box lo <= p <= hi on
+// every axis (inclusive; p the position loadSpz(…, UnpackOptions{coord}) returns, NaN never inside); decoded alpha (the
+// logit loadSpz returns) >= minAlpha.  No predicate: every point.  shDegree -1 keeps the input's degree, 0 … the
+// input's lowers it.  Keeping every point at the same degree gives back the input's stream byte for byte.
+// false + one "[SPZ ERROR] filterSpz: …" line on a bad argument (lastDeviceStatus() = SPZ_AMD_ERR_INVALID_ARG), an input
+// that does not load, or a device failure.  *kept: K.  SPZ_AMD_FILTER_TIMING=1 prints the stages' times to stderr.
+struct FilterOptions {
+  struct Box {
+    std::array<float, 3> lo{}, hi{};
+  };
+  CoordinateSystem coord = CoordinateSystem::UNSPECIFIED;  // of the positions the box is tested on
+  std::optional<Box> box;
+  std::optional<float> minAlpha;
+  std::optional<std::vector<uint8_t>> mask;
+  std::optional<std::vector<uint32_t>> indices;
+  int32_t shDegree = -1;
+};
+bool filterSpz(const uint8_t *data, int32_t size, const FilterOptions &options, std::vector<uint8_t> *out,
+               int64_t *kept = nullptr);
+bool filterSpz(const std::string &inputFilename, const std::string &outputFilename, const FilterOptions &options,
+               int64_t *kept = nullptr);
 // Status (spz_amd.h codes) of the last device call made by this thread; 0 = ok.
 int lastDeviceStatus();
 void setLastDeviceStatus(int status);

@@ -59,6 +59,8 @@ EXPORTS = (
     "spz_amd_cloud_buffers_alloc", "spz_amd_cloud_buffers_free",
     "spz_amd_zlib_session_open", "spz_amd_zlib_session_feed", "spz_amd_zlib_session_close", "spz_amd_zlib_parse_open_session",
     "spz_amd_encode_host_keep_session", "spz_amd_encode_host_keep_session_tail", "spz_amd_decode_gather_host_from_device",
+    "spz_amd_filter_workspace_bytes", "spz_amd_select_device", "spz_amd_subset_device",
+    "spz_amd_filter_open", "spz_amd_filter_fetch", "spz_amd_filter_device_data", "spz_amd_filter_close",
 )
 
 RCCL_UNIQUE_ID_BYTES = 128
@@ -104,6 +106,12 @@ class Fragments(C.Structure):
     """spz_amd_fragments: the six byte ranges of a point-range shard."""
     _fields_ = [("global_offset", C.c_uint64 * NUM_SECTIONS), ("local_offset", C.c_uint64 * NUM_SECTIONS),
                 ("bytes", C.c_uint64 * NUM_SECTIONS)]
+
+
+class Selection(C.Structure):
+    """spz_amd_selection: the predicates of spz_amd_select_device (box inclusive, alpha on the decoded logit)."""
+    _fields_ = [("to_coord", C.c_int32), ("use_box", C.c_int32), ("box_lo", C.c_float * 3), ("box_hi", C.c_float * 3),
+                ("use_min_alpha", C.c_int32), ("min_alpha", C.c_float)]
 
 
 class SpzAmdError(RuntimeError):
@@ -258,6 +266,21 @@ def bind(L):
     L.spz_amd_zlib_encode_planned.argtypes = [vp, vp, u32, u32, vp, u64]
     L.spz_amd_zlib_encode_finish_ex.restype = i32
     L.spz_amd_zlib_encode_finish_ex.argtypes = [vp, u32, u64, vp, vp, vp]
+    L.spz_amd_filter_workspace_bytes.restype = u64
+    L.spz_amd_filter_workspace_bytes.argtypes = [u64]
+    L.spz_amd_select_device.restype = i32
+    L.spz_amd_select_device.argtypes = [vp, sz, C.POINTER(Header), C.POINTER(Selection), vp, vp, vp, C.POINTER(u64), vp]
+    L.spz_amd_subset_device.restype = i32
+    L.spz_amd_subset_device.argtypes = [vp, sz, C.POINTER(Header), vp, u64, i32, vp, sz, vp]
+    L.spz_amd_filter_open.restype = i32
+    L.spz_amd_filter_open.argtypes = [vp, sz, C.POINTER(Header), C.POINTER(Selection), vp, i32, vp, u64, i32, i32,
+                                      C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), vp]
+    L.spz_amd_filter_fetch.restype = i32
+    L.spz_amd_filter_fetch.argtypes = [vp, vp]
+    L.spz_amd_filter_device_data.restype = vp
+    L.spz_amd_filter_device_data.argtypes = [vp]
+    L.spz_amd_filter_close.restype = None
+    L.spz_amd_filter_close.argtypes = [vp]
     L.spz_amd_zlib_encode_blocks.restype = i32
     L.spz_amd_zlib_encode_blocks.argtypes = [vp, vp, u32, u32, vp, vp, vp, u64, u64, vp, vp]
     return L

@@ -116,6 +116,9 @@ void build_host_tables() {
   g_tables.host_ready = true;
 }
 
+}  // namespace
+
+namespace spz_amd_detail {
 int ensure_tables(int device, const float **dev_tables) {
   if (device < 0 || device >= kMaxDevices) return SPZ_AMD_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lock(g_tables_mutex);
@@ -135,6 +138,9 @@ int ensure_tables(int device, const float **dev_tables) {
   *dev_tables = g_tables.dev[device];
   return SPZ_AMD_OK;
 }
+}  // namespace spz_amd_detail
+
+namespace {
 
 int grid_for(int device, uint32_t total_tiles, uint32_t *grid) {
   uint32_t cap = 0x7fffffffu;  // hipGridDim.x limit; the kernels grid-stride beyond it

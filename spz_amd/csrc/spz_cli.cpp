@@ -1,9 +1,12 @@
 // spz_cli.cpp — the three command-line tools of the reference (cli_tools/src/*.cpp) over the
-// MI355X drop-in layer: ply_to_spz, spz_to_ply, spz_info.  One binary, dispatched on argv[0]
-// (the Makefile installs it under the three names) or on a first argument naming the tool.
+// MI355X drop-in layer: ply_to_spz, spz_to_ply, spz_info; and spz_filter (spz::filterSpz, no
+// counterpart in the reference).  One binary, dispatched on argv[0] (the Makefile installs it under
+// the four names) or on a first argument naming the tool.
 // Same behaviour as the reference mains: default (UNSPECIFIED) pack/unpack options, exit code 0
 // once the arguments are there (the reference ignores the save/load results), usage -> 1.
+// spz_filter exits 1 when the filter fails as well.
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <exception>
 #include <iostream>
@@ -56,10 +59,65 @@ int spzInfo(int argc, char **argv) {
   return 0;
 }
 
+const char *kFilterUsage =
+    "Usage: spz_filter <input.spz> <output.spz> [--sh-degree D] [--min-alpha A] [--box x0 y0 z0 x1 y1 z1] "
+    "[--coord RUB|RDF|LUF|RUF|LDB|RDB|LUB|LDF|UNSPECIFIED]";
+
+bool parseFloat(const char *s, float *v) {
+  char *end = nullptr;
+  *v = std::strtof(s, &end);
+  return end != s && *end == '\0';
+}
+
+int spzFilter(int argc, char **argv) {
+  auto usage = [] {
+    std::cerr << kFilterUsage << std::endl;
+    return 1;
+  };
+  if (argc < 3) return usage();
+  spz::FilterOptions f;
+  for (int i = 3; i < argc; ++i) {
+    const std::string a = argv[i];
+    if (a == "--sh-degree" && i + 1 < argc) {
+      char *end = nullptr;
+      const long d = std::strtol(argv[++i], &end, 10);
+      if (*end != '\0' || d < 0 || d > 3) return usage();
+      f.shDegree = static_cast<int32_t>(d);
+    } else if (a == "--min-alpha" && i + 1 < argc) {
+      float v = 0;
+      if (!parseFloat(argv[++i], &v)) return usage();
+      f.minAlpha = v;
+    } else if (a == "--box" && i + 6 < argc) {
+      spz::FilterOptions::Box b;
+      for (int k = 0; k < 6; ++k) {
+        if (!parseFloat(argv[i + 1 + k], k < 3 ? &b.lo[k] : &b.hi[k - 3])) return usage();
+      }
+      i += 6;
+      f.box = b;
+    } else if (a == "--coord" && i + 1 < argc) {
+      static const char *names[] = {"UNSPECIFIED", "LDB", "RDB", "LUB", "RUB", "LDF", "RDF", "LUF", "RUF"};
+      const std::string c = argv[++i];
+      int found = -1;
+      for (int k = 0; k < 9; ++k) {
+        if (c == names[k]) found = k;
+      }
+      if (found < 0) return usage();
+      f.coord = static_cast<spz::CoordinateSystem>(found);
+    } else {
+      return usage();
+    }
+  }
+  int64_t kept = 0;
+  if (!spz::filterSpz(std::string(argv[1]), std::string(argv[2]), f, &kept)) return 1;
+  std::cout << "Points kept: " << kept << std::endl;
+  return 0;
+}
+
 int dispatch(const std::string &tool, int argc, char **argv) {
   if (tool == "ply_to_spz") return plyToSpz(argc, argv);
   if (tool == "spz_to_ply") return spzToPly(argc, argv);
   if (tool == "spz_info") return spzInfo(argc, argv);
+  if (tool == "spz_filter") return spzFilter(argc, argv);
   return -1;
 }
 
@@ -76,7 +134,7 @@ int main(int argc, char **argv) {
       rc = dispatch(argv[1], argc - 1, argv + 1);
       if (rc >= 0) return rc;
     }
-    std::cerr << "Usage: spz_tool {ply_to_spz|spz_to_ply|spz_info} <args...>" << std::endl;
+    std::cerr << "Usage: spz_tool {ply_to_spz|spz_to_ply|spz_info|spz_filter} <args...>" << std::endl;
     return 1;
   } catch (const std::exception &e) {
     std::cerr << "Error: " << e.what() << std::endl;

@@ -1,6 +1,6 @@
 // spz_common.hpp — pieces shared by the HIP translation units of libspz_amd.so
 // (spz_kernels.hip + spz_abi.hip: pack/unpack/flip kernels and their device entry points; spz_hostpath.hip: the
-// host-pointer entry points; spz_ply_kernels.hip: .ply row shuffles; spz_median.hip; spz_exchange.hip).
+// host-pointer entry points; spz_ply_kernels.hip: .ply row shuffles; spz_median.hip; spz_exchange.hip; spz_filter.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -29,6 +29,36 @@ __device__ __forceinline__ float mul_pm1(float v, uint32_t neg) {
   uint32_t b = __float_as_uint(v);
   uint32_t flipped = b ^ (neg << 31);
   return __uint_as_float(is_nan_bits(b) ? (b | 0x00400000u) : flipped);
+}
+
+// Same product for operands that cannot be NaN (or whose NaN sign cannot reach the output): a
+// plain sign-bit flip.
+__device__ __forceinline__ float xor_sign(float v, uint32_t neg) {
+  return __uint_as_float(__float_as_uint(v) ^ (neg << 31));
+}
+
+// halfToFloat (splat-types.cc:8-27): exact widening; every NaN becomes the positive quiet NaN.
+__device__ __forceinline__ float half_to_float(uint32_t h) {
+  h &= 0xffffu;
+  if ((h & 0x7c00u) == 0x7c00u && (h & 0x3ffu) != 0) return __uint_as_float(0x7fc00000u);
+  _Float16 f;
+  uint16_t hh = (uint16_t)h;
+  __builtin_memcpy(&f, &hh, 2);
+  return (float)f;
+}
+
+// Axis `axis` of point i's position as unpackGaussians returns it (load-spz.cc:496-502: sign-extended 24-bit times
+// 1 / 2^fractionalBits; v1: the float16 halves), with the coordinate flip of bit `axis` of flip_p.  One point at a
+// time: the random-access decode (spz_decode_gather_kernel) and the selection (spz_select_kernel) share it.
+__device__ __forceinline__ float decode_position_axis(const uint8_t *positions, unsigned long long i, uint32_t axis,
+                                                      bool float16, float pos_scale, uint32_t flip_p) {
+  if (float16) {
+    const uint8_t *b = positions + (i * 3u + axis) * 2u;
+    return mul_pm1(half_to_float((uint32_t)b[0] | ((uint32_t)b[1] << 8)), (flip_p >> axis) & 1u);
+  }
+  const uint8_t *b = positions + (i * 3u + axis) * 3u;
+  const uint32_t v = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16);
+  return xor_sign((float)((int32_t)(v << 8) >> 8) * pos_scale, (flip_p >> axis) & 1u);
 }
 
 

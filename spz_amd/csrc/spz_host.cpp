@@ -1745,6 +1745,125 @@ GaussianCloud loadSpz(const uint8_t *data, int32_t size, const UnpackOptions &o)
   return unpackFromStream(stream.data(), stream.size(), o);
 }
 
+// ---- filter ------------------------------------------------------------------------------------------------------
+namespace {
+bool filterRejected(const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  char msg[256];
+  std::vsnprintf(msg, sizeof(msg), fmt, ap);
+  va_end(ap);
+  logLine("[SPZ ERROR] filterSpz: %s", msg);
+  g_last_status = SPZ_AMD_ERR_INVALID_ARG;
+  return false;
+}
+
+struct FilterLaps {
+  bool on = std::getenv("SPZ_AMD_FILTER_TIMING") != nullptr;
+  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+  void lap(const char *what) {
+    const auto now = std::chrono::steady_clock::now();
+    if (on) std::fprintf(stderr, "[filterSpz] %-8s %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
+    t = now;
+  }
+};
+}  // namespace
+
+bool filterSpz(const uint8_t *data, int32_t size, const FilterOptions &f, std::vector<uint8_t> *out, int64_t *kept) {
+  g_last_status = SPZ_AMD_OK;
+  if (kept) *kept = 0;
+  // the arguments first: nothing touches the device before they are known to be good
+  if (out == nullptr) return filterRejected("no output vector");
+  if (f.shDegree < -1 || f.shDegree > 3) return filterRejected("shDegree %d is outside -1 ... 3", f.shDegree);
+  if (f.indices && (f.mask || f.box || f.minAlpha)) return filterRejected("indices cannot be combined with a mask, a box or minAlpha");
+  if (static_cast<int>(f.coord) < 0 || static_cast<int>(f.coord) > 8) return filterRejected("unknown coordinate system %d", static_cast<int>(f.coord));
+  if (f.box) {
+    for (int a = 0; a < 3; ++a) {
+      if (std::isnan(f.box->lo[a]) || std::isnan(f.box->hi[a])) return filterRejected("a box bound is NaN");
+    }
+  }
+  if (f.minAlpha && std::isnan(*f.minAlpha)) return filterRejected("minAlpha is NaN");
+  if (f.indices && f.indices->size() > SPZ_AMD_REFERENCE_MAX_POINTS) {
+    return filterRejected("%zu indices: the reference reads at most %u points", f.indices->size(), SPZ_AMD_REFERENCE_MAX_POINTS);
+  }
+  FilterLaps laps;
+  DevicePackedGaussians d = loadSpzPackedDevice(data, size);
+  if (!d.valid()) {
+    if (g_last_status == SPZ_AMD_OK) logLine("[SPZ ERROR] filterSpz: the input is not a readable .spz");
+    return false;
+  }
+  laps.lap("inflate");
+  const uint32_t n = static_cast<uint32_t>(d.numPoints);
+  if (f.shDegree > d.shDegree) return filterRejected("shDegree %d is above the input's %d", f.shDegree, d.shDegree);
+  if (f.mask && f.mask->size() != n) return filterRejected("the mask has %zu bytes for %u points", f.mask->size(), n);
+  if (f.indices) {
+    for (const uint32_t i : *f.indices) {
+      if (i >= n) return filterRejected("index %u is out of range for %u points", i, n);
+    }
+  }
+  const spz_amd_header hdr = headerOf(d);
+  spz_amd_selection sel = {};
+  sel.to_coord = static_cast<int32_t>(f.coord);
+  if (f.box) {
+    sel.use_box = 1;
+    for (int a = 0; a < 3; ++a) {
+      sel.box_lo[a] = f.box->lo[a];
+      sel.box_hi[a] = f.box->hi[a];
+    }
+  }
+  if (f.minAlpha) {
+    sel.use_min_alpha = 1;
+    sel.min_alpha = *f.minAlpha;
+  }
+  void *ctx = nullptr;
+  uint64_t count = 0, bytes = 0;
+  float ms[2] = {0.0f, 0.0f};
+  int rc = spz_amd_filter_open(d.stream, d.streamBytes, &hdr, &sel, f.mask ? f.mask->data() : nullptr, f.indices ? 1 : 0,
+                               f.indices ? f.indices->data() : nullptr, f.indices ? f.indices->size() : 0, f.shDegree,
+                               d.device, &ctx, &count, &bytes, ms);
+  if (deviceFailed(rc, "filterSpz")) return false;
+  struct Close {
+    void *c;
+    ~Close() { spz_amd_filter_close(c); }
+  } closer{ctx};
+  if (laps.on) std::fprintf(stderr, "[filterSpz] select   %.3f ms\n[filterSpz] subset   %.3f ms\n", ms[0], ms[1]);
+  laps.lap("filter");
+  d.release();  // the input's device memory goes before the container stage takes its own
+  std::vector<uint8_t> stream;
+  detail::resizeUninitialized(&stream, static_cast<size_t>(bytes));
+  rc = spz_amd_filter_fetch(ctx, stream.data());
+  if (deviceFailed(rc, "filterSpz")) return false;
+  laps.lap("download");
+  // the device copy of the stream is this call's (not spz_amd_encode_host_keep's kept buffer): the device writer reads it
+  // instead of uploading the host copy; it lives until `closer` runs
+  if (!compressGzippedWithCopy(stream.data(), stream.size(), out, spz_amd_filter_device_data(ctx))) {
+    logLine("[SPZ ERROR] filterSpz: compressGzipped failed");
+    return false;
+  }
+  laps.lap("gzip");
+  if (kept) *kept = static_cast<int64_t>(count);
+  return true;
+}
+
+bool filterSpz(const std::string &inputFilename, const std::string &outputFilename, const FilterOptions &f, int64_t *kept) {
+  g_last_status = SPZ_AMD_OK;
+  if (kept) *kept = 0;
+  std::vector<uint8_t> data;
+  if (!readFile(inputFilename, &data, /*log=*/true)) return false;
+  if (data.size() > static_cast<size_t>(INT32_MAX)) return filterRejected("%s is larger than 2 GiB", inputFilename.c_str());
+  std::vector<uint8_t> file;
+  int64_t k = 0;
+  if (!filterSpz(data.data(), static_cast<int32_t>(data.size()), f, &file, &k)) return false;
+  FilterLaps laps;
+  if (!writeFile(outputFilename, file)) {
+    logLine("[SPZ ERROR] filterSpz: unable to write %s", outputFilename.c_str());
+    return false;
+  }
+  laps.lap("write");
+  if (kept) *kept = k;
+  return true;
+}
+
 GaussianCloud loadSpz(const std::vector<uint8_t> &data, const UnpackOptions &o) {
   return loadSpz(data.data(), static_cast<int32_t>(data.size()), o);
 }

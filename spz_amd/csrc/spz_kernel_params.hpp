@@ -220,6 +220,9 @@ struct SelfTestParams {
   unsigned long long *mismatches;  // [0] = count, [1] = smallest mismatching index (init ~0), [2] = inputs compared
 };
 
+// The device tables (kTable*) on `device`, made on first use (spz_abi.hip); shared with spz_filter.hip.
+int ensure_tables(int device, const float **dev_tables);
+
 // The kernels (spz_kernels.hip).
 __global__ void spz_selftest_kernel(const SelfTestParams p);
 __global__ void spz_decode_gather_kernel(const GatherParams p);

@@ -88,12 +88,6 @@ __device__ __forceinline__ float fadd_sep(float a, float b) {
   return r;
 }
 
-// Same product for operands that cannot be NaN (or whose NaN sign cannot reach the output): a
-// plain sign-bit flip.
-__device__ __forceinline__ float xor_sign(float v, uint32_t neg) {
-  return __uint_as_float(__float_as_uint(v) ^ (neg << 31));
-}
-
 // std::round: half away from zero, exact (load-spz.cc:74,78,284).
 __device__ __forceinline__ float round_half_away(float x) {
   float t = __builtin_truncf(x);
@@ -384,16 +378,6 @@ __device__ __forceinline__ F32x4 unpack_quat_first_three(uint32_t r3, uint32_t f
   o.z = xor_sign(z, (flip_q >> 2) & 1u);
   o.w = __builtin_sqrtf(m);
   return o;
-}
-
-// halfToFloat (splat-types.cc:8-27): exact widening; every NaN becomes the positive quiet NaN.
-__device__ __forceinline__ float half_to_float(uint32_t h) {
-  h &= 0xffffu;
-  if ((h & 0x7c00u) == 0x7c00u && (h & 0x3ffu) != 0) return __uint_as_float(0x7fc00000u);
-  _Float16 f;
-  uint16_t hh = (uint16_t)h;
-  __builtin_memcpy(&f, &hh, 2);
-  return (float)f;
 }
 
 // Alpha encode: number of thresholds <= a (NaN -> 0), thresholds ascending, thr[255] = NaN.
@@ -935,13 +919,8 @@ __device__ __forceinline__ float gather_element(const GatherParams &p, unsigned 
   const uint32_t o = (uint32_t)(e - g * (unsigned)FPP);
   uint32_t i = p.indices[g];
   i = i < p.num_points ? i : p.num_points - 1u;
-  if constexpr (KIND == KIND_POS24) {
-    const uint8_t *b = p.positions + ((unsigned long long)i * 3u + o) * 3u;
-    const uint32_t v = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16);
-    return xor_sign((float)((int32_t)(v << 8) >> 8) * p.pos_scale, (p.flip_p >> o) & 1u);
-  } else if constexpr (KIND == KIND_POS16) {
-    const uint8_t *b = p.positions + ((unsigned long long)i * 3u + o) * 2u;
-    return mul_pm1(half_to_float((uint32_t)b[0] | ((uint32_t)b[1] << 8)), (p.flip_p >> o) & 1u);
+  if constexpr (KIND == KIND_POS24 || KIND == KIND_POS16) {
+    return decode_position_axis(p.positions, i, o, KIND == KIND_POS16, p.pos_scale, p.flip_p);
   } else if constexpr (KIND == KIND_ALPHA) {
     return p.tables[kTableAlphaDec + p.alphas[i]];
   } else if constexpr (KIND == KIND_COLOR) {

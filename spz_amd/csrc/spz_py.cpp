@@ -12,6 +12,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <cmath>
 #include <cstring>
 #include <sstream>
 #include <memory>
@@ -87,6 +88,87 @@ void raiseIfDeviceUnusable() {
     throw std::runtime_error(std::string("spz_amd: ") + spz_amd_status_string(st) +
                              " (the SPZ hot path runs on the GPU only)");
   }
+}
+
+// filter_spz's arguments as spz::FilterOptions; every problem is a ValueError, raised before any device work.
+spz::FilterOptions filterOptions(const py::object &mask, const py::object &indices, const py::object &box,
+                                 spz::CoordinateSystem coord, const py::object &min_alpha, const py::object &sh_degree) {
+  spz::FilterOptions f;
+  f.coord = coord;
+  if (!sh_degree.is_none()) {
+    if (!py::isinstance<py::int_>(sh_degree) || py::isinstance<py::bool_>(sh_degree)) throw py::value_error("sh_degree must be None or an int in [-1, 3]");
+    const long d = py::cast<long>(sh_degree);
+    if (d < -1 || d > 3) throw py::value_error("sh_degree must be None or an int in [-1, 3], got " + std::to_string(d));
+    f.shDegree = static_cast<int32_t>(d);
+  }
+  if (!indices.is_none() && (!mask.is_none() || !box.is_none() || !min_alpha.is_none())) {
+    throw py::value_error("indices cannot be combined with mask, box or min_alpha");
+  }
+  auto asArray = [](const py::object &o, const char *name) {
+    py::array a;
+    try {
+      a = py::array::ensure(o);
+    } catch (const py::error_already_set &) {
+      PyErr_Clear();
+    }
+    if (!a) throw py::value_error(std::string(name) + " must be a numpy array");
+    return a;
+  };
+  if (!box.is_none()) {
+    py::array a = asArray(box, "box");
+    const char k = a.dtype().kind();
+    if (!(k == 'i' || k == 'u' || k == 'f')) throw py::value_error("box must be numeric");
+    if (a.ndim() != 2 || a.shape(0) != 2 || a.shape(1) != 3) throw py::value_error("box must have shape (2, 3): [[x0, y0, z0], [x1, y1, z1]]");
+    py::array_t<float, py::array::c_style | py::array::forcecast> b(a);
+    spz::FilterOptions::Box bb;
+    for (int i = 0; i < 3; ++i) {
+      bb.lo[i] = b.at(0, i);
+      bb.hi[i] = b.at(1, i);
+      if (std::isnan(bb.lo[i]) || std::isnan(bb.hi[i])) throw py::value_error("box bounds must not be NaN");
+    }
+    f.box = bb;
+  }
+  if (!min_alpha.is_none()) {
+    const float v = py::cast<float>(min_alpha);
+    if (std::isnan(v)) throw py::value_error("min_alpha must not be NaN");
+    f.minAlpha = v;
+  }
+  if (!mask.is_none()) {
+    py::array a = asArray(mask, "mask");
+    const char k = a.dtype().kind();
+    if (!(k == 'b' || k == 'i' || k == 'u')) throw py::value_error("mask must be a bool or integer array");
+    if (a.ndim() != 1) throw py::value_error("mask must be one-dimensional");
+    py::array_t<bool, py::array::c_style | py::array::forcecast> b(a);
+    std::vector<uint8_t> v(static_cast<size_t>(b.size()));
+    const bool *q = b.data();
+    for (size_t i = 0; i < v.size(); ++i) v[i] = q[i] ? 1 : 0;
+    f.mask = std::move(v);
+  }
+  if (!indices.is_none()) {
+    py::array a = asArray(indices, "indices");
+    const char k = a.dtype().kind();
+    if (!(k == 'i' || k == 'u')) throw py::value_error("indices must be an integer array");
+    if (a.ndim() != 1) throw py::value_error("indices must be one-dimensional");
+    if (static_cast<uint64_t>(a.size()) > SPZ_AMD_REFERENCE_MAX_POINTS) throw py::value_error("more than 10 M indices: the reference reads at most 10 M points");
+    std::vector<uint32_t> v(static_cast<size_t>(a.size()));
+    if (k == 'u') {
+      py::array_t<uint64_t, py::array::c_style | py::array::forcecast> b(a);
+      for (size_t i = 0; i < v.size(); ++i) {
+        if (b.data()[i] > 0xffffffffull) throw py::value_error("index " + std::to_string(b.data()[i]) + " does not fit 32 bits");
+        v[i] = static_cast<uint32_t>(b.data()[i]);
+      }
+    } else {
+      py::array_t<int64_t, py::array::c_style | py::array::forcecast> b(a);
+      for (size_t i = 0; i < v.size(); ++i) {
+        const int64_t x = b.data()[i];
+        if (x < 0) throw py::value_error("negative index " + std::to_string(x));
+        if (x > 0xffffffffll) throw py::value_error("index " + std::to_string(x) + " does not fit 32 bits");
+        v[i] = static_cast<uint32_t>(x);
+      }
+    }
+    f.indices = std::move(v);
+  }
+  return f;
 }
 
 }  // namespace
@@ -284,6 +366,31 @@ PYBIND11_MODULE(spz, m) {
           return g;
         },
         py::arg("filename"), py::arg("options") = spz::UnpackOptions(), "Load a *.spz* file and return a GaussianCloud.");
+  m.def("filter_spz",
+        [](const std::string &input, const std::string &output, const py::object &mask, const py::object &indices,
+           const py::object &box, spz::CoordinateSystem coord, const py::object &min_alpha, const py::object &sh_degree) {
+          const spz::FilterOptions f = filterOptions(mask, indices, box, coord, min_alpha, sh_degree);
+          int64_t kept = 0;
+          bool ok;
+          {
+            py::gil_scoped_release release;
+            ok = spz::filterSpz(input, output, f, &kept);
+          }
+          if (!ok) {
+            raiseIfDeviceUnusable();
+            if (spz::lastDeviceStatus() == SPZ_AMD_ERR_INVALID_ARG) {
+              throw py::value_error("filter_spz: invalid argument for this file (see the [SPZ ERROR] line)");
+            }
+            throw std::runtime_error("filter_spz: " + input + " -> " + output + " failed (see the [SPZ ERROR] line)");
+          }
+          return kept;
+        },
+        py::arg("input_filename"), py::arg("output_filename"), py::kw_only(), py::arg("mask") = py::none(),
+        py::arg("indices") = py::none(), py::arg("box") = py::none(), py::arg("coord") = spz::CoordinateSystem::UNSPECIFIED,
+        py::arg("min_alpha") = py::none(), py::arg("sh_degree") = py::none(),
+        "A smaller .spz out of an existing one without requantising (spz::filterSpz): the points `indices`, or those "
+        "selected by mask / box (inclusive, positions in `coord`) / min_alpha (decoded logit), with sh lowered to "
+        "`sh_degree`.  Returns the number of points kept.");
   m.def("save_spz",
         [](const spz::GaussianCloud &g, const spz::PackOptions &o, const std::string &filename) {
           bool ok;

@@ -204,6 +204,78 @@ def decode_gather(stream_t, header, indices, to_coord=0, out=None, stream=None):
     return out
 
 
+def _selection(box, min_alpha, to_coord):
+    import math
+    sel = abi.Selection()
+    sel.to_coord = int(to_coord)
+    if not 0 <= sel.to_coord <= 8:
+        raise ValueError(f"to_coord must be a CoordinateSystem value 0..8, got {to_coord}")
+    if box is not None:
+        rows = [[float(v) for v in row] for row in box]
+        if len(rows) != 2 or any(len(r) != 3 for r in rows):
+            raise ValueError("box must be [[x0, y0, z0], [x1, y1, z1]]")
+        if any(math.isnan(v) for r in rows for v in r):
+            raise ValueError("box bounds must not be NaN")
+        sel.use_box = 1
+        for a in range(3):
+            sel.box_lo[a], sel.box_hi[a] = rows[0][a], rows[1][a]
+    if min_alpha is not None:
+        if math.isnan(float(min_alpha)):
+            raise ValueError("min_alpha must not be NaN")
+        sel.use_min_alpha, sel.min_alpha = 1, float(min_alpha)
+    return sel
+
+
+def select(stream_t, header, *, mask=None, box=None, min_alpha=None, to_coord=0, stream=None):
+    """The indices (int32 CUDA tensor, input order) of the points of a packed device stream whose predicates all hold:
+    mask[i] != 0 (a bool/uint8 CUDA tensor of num_points), the box [[x0, y0, z0], [x1, y1, z1]] (inclusive, positions
+    as decode(to_coord) gives them), the decoded alpha logit >= min_alpha.  None of them: every point.  Blocks until the
+    count is known (spz_amd_select_device)."""
+    L = abi.load_library()
+    sel = _selection(box, min_alpha, to_coord)
+    n, dev = header.num_points, stream_t.device
+    if mask is not None:
+        if mask.dtype not in (torch.bool, torch.uint8) or not mask.is_cuda or not mask.is_contiguous() or mask.numel() != n:
+            raise ValueError(f"mask must be a contiguous bool/uint8 CUDA tensor of {n} elements")
+        if mask.device != dev:
+            raise ValueError(f"mask is on {mask.device}, expected {dev}")
+    out = torch.empty(n, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(L.spz_amd_filter_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+    count = C.c_uint64(0)
+    with torch.cuda.device(dev):
+        rc = L.spz_amd_select_device(stream_t.data_ptr(), stream_t.numel(), C.byref(header), C.byref(sel),
+                                     mask.data_ptr() if mask is not None else None, out.data_ptr() if n else None,
+                                     ws.data_ptr() if n else None, C.byref(count), _stream_handle(stream))
+    abi.check(rc, "spz_amd_select_device")
+    return out[:count.value]
+
+
+def subset(stream_t, header, indices, sh_degree=None, out=None, stream=None):
+    """The stream of the points `indices` (int32/uint32 CUDA tensor; any order, duplicates allowed) of a packed device
+    stream, with sh lowered to `sh_degree` (None: the input's): a uint8 CUDA tensor, no requantising.  An index >=
+    num_points raises ValueError before the launch (the C ABI's device form clamps)."""
+    L = abi.load_library()
+    deg = -1 if sh_degree is None else int(sh_degree)
+    if not -1 <= deg <= header.sh_degree:
+        raise ValueError(f"sh_degree must be None, -1 or 0..{header.sh_degree}, got {sh_degree}")
+    if indices.dtype not in (torch.int32, torch.uint32) or not indices.is_cuda or not indices.is_contiguous():
+        raise ValueError("indices must be a contiguous int32/uint32 CUDA tensor")
+    count, n = indices.numel(), header.num_points
+    if count:
+        wide = indices.view(torch.int32).to(torch.int64) & 0xffffffff
+        if int(wide.max()) >= n or (indices.dtype == torch.int32 and int(indices.min()) < 0):
+            raise ValueError(f"an index is out of range for {n} points")
+    lay = abi.stream_layout(count, header.sh_degree if deg < 0 else deg, header.version)
+    if out is None:
+        out = torch.empty(lay.total_bytes, dtype=torch.uint8, device=stream_t.device)
+    with torch.cuda.device(stream_t.device):
+        rc = L.spz_amd_subset_device(stream_t.data_ptr(), stream_t.numel(), C.byref(header),
+                                     indices.data_ptr() if count else None, count, deg, out.data_ptr(), out.numel(),
+                                     _stream_handle(stream))
+    abi.check(rc, "spz_amd_subset_device")
+    return out[:lay.total_bytes]
+
+
 def convert_coordinates(cloud, num_points, sh_degree, from_coord, to_coord, stream=None):
     """In-place GaussianCloud::convertCoordinates on device tensors (positions, rotations, sh)."""
     L = abi.load_library()
@@ -229,5 +301,6 @@ def to_numpy(cloud_t):
 
 
 __all__ = ["encode", "decode", "encode_shard", "decode_shard", "decode_gather", "peek_header", "convert_coordinates",
+           "select", "subset",
            "alloc_cloud",
            "make_header", "to_device", "to_numpy", "SH_DIM"]

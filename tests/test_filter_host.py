@@ -1,0 +1,151 @@
+"""spz.filter_spz / spz::filterSpz / spz_filter (DESIGN §8 "filter") without a GPU: the argument checks, which must
+raise before any device work, the CLI's usage line, and a numpy restatement of the output stream — point k of the
+output is input point idx[k] with all its bytes, its sh bytes a prefix of its record — checked against the plain-C
+oracle's decode.  tests/test_gpu_filter.py compares the device's output with this restatement."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT, assert_bits_equal, load_golden
+
+SH_DIM = {0: 0, 1: 3, 2: 8, 3: 15}
+MAGIC = 0x5053474E
+
+
+def parse_stream(stream):
+    """Header fields and the six sections of a raw stream, each as an (N, bytes per point) uint8 array."""
+    s = np.frombuffer(bytes(stream), np.uint8)
+    u32 = s[:12].view("<u4")
+    assert int(u32[0]) == MAGIC
+    version, n = int(u32[1]), int(u32[2])
+    deg, fb, flags = int(s[12]), int(s[13]), int(s[14])
+    bpp = [6 if version == 1 else 9, 1, 3, 3, 4 if version >= 3 else 3, 3 * SH_DIM[deg]]
+    secs, off = [], 16
+    for b in bpp:
+        secs.append(s[off:off + n * b].reshape(n, b))
+        off += n * b
+    return dict(version=version, num_points=n, sh_degree=deg, fractional_bits=fb, flags=flags, sections=secs)
+
+
+def expected_stream(stream, idx, sh_degree=None):
+    """The filter's output stream for the points idx of `stream`, restated with numpy."""
+    h = parse_stream(stream)
+    idx = np.asarray(idx, np.int64).reshape(-1)
+    d2 = h["sh_degree"] if sh_degree is None or sh_degree == -1 else int(sh_degree)
+    head = np.zeros(16, np.uint8)
+    head[:12] = np.array([MAGIC, h["version"], idx.size], "<u4").view(np.uint8)
+    head[12], head[13], head[14], head[15] = d2, h["fractional_bits"], h["flags"] & 1, 0
+    parts = [head]
+    for k, sec in enumerate(h["sections"]):
+        rows = sec[idx]
+        if k == 5:
+            rows = rows[:, :3 * SH_DIM[d2]]
+        parts.append(np.ascontiguousarray(rows).reshape(-1))
+    return np.concatenate(parts).tobytes()
+
+
+def golden_streams():
+    cl, lg = load_golden("clouds.npz"), load_golden("legacy.npz")
+    out = {f"v3_sh{d}": cl[f"d{d}_stream_from0"].tobytes() for d in range(4)}
+    out.update(v2=lg["v2_stream"].tobytes(), v1=lg["v1_stream"].tobytes(),
+               fb0=lg["fb0_stream"].tobytes(), fb8=lg["fb8_stream"].tobytes(), fb23=lg["fb23_stream"].tobytes())
+    return out
+
+
+def index_sets(n, seed=5):
+    """A seeded mask's nonzero points (input order), and reversed indices with duplicates."""
+    rng = np.random.default_rng(seed)
+    masked = np.nonzero(rng.random(n) < 0.5)[0]
+    rev = np.arange(n)[::-1]
+    dup = np.concatenate([rev[: n // 3], rev[: n // 5], [0, 0, n - 1]])
+    return {"mask": masked.astype(np.uint32), "reversed_dup": dup.astype(np.uint32)}
+
+
+# ---- the restatement against the oracle's decode -------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(golden_streams()))
+def test_restated_stream_decodes_to_the_input_rows(oracle, name):
+    raw = golden_streams()[name]
+    rc, full = oracle.unpack(np.frombuffer(raw, np.uint8))
+    assert rc == 0
+    n, deg = full["num_points"], full["sh_degree"]
+    per = {"positions": 3, "scales": 3, "rotations": 4, "alphas": 1, "colors": 3}
+    for label, idx in index_sets(n).items():
+        for d2 in range(deg + 1):
+            out = expected_stream(raw, idx, d2)
+            rc, got = oracle.unpack(np.frombuffer(out, np.uint8))
+            assert rc == 0, f"{name} {label} sh{d2}: the oracle rejects the restated stream"
+            assert got["num_points"] == idx.size and got["sh_degree"] == d2
+            for k, w in per.items():
+                assert_bits_equal(got[k], full[k].reshape(n, w)[idx].reshape(-1), f"{name} {label} sh{d2} {k}")
+            sh = full["sh"].reshape(n, SH_DIM[deg], 3)[idx, :SH_DIM[d2], :]
+            assert_bits_equal(got["sh"], sh.reshape(-1), f"{name} {label} sh{d2} sh")
+    # keeping every point at the same degree is the input itself; no point is a 16-byte stream of 0 points
+    assert expected_stream(raw, np.arange(n)) == raw
+    empty = expected_stream(raw, np.zeros(0, np.int64))
+    assert len(empty) == 16 and oracle.unpack(np.frombuffer(empty, np.uint8))[1]["num_points"] == 0
+
+
+# ---- argument checks: ValueError before any device work (no device here) -----------------------------------------
+@pytest.fixture(scope="module")
+def spz():
+    import spz_amd.spz as m
+    return m
+
+
+@pytest.fixture()
+def some_file(tmp_path):
+    p = tmp_path / "in.spz"
+    p.write_bytes(b"not read: the arguments are checked first")
+    return str(p)
+
+
+@pytest.mark.parametrize("kw", [
+    dict(sh_degree=4), dict(sh_degree=-2), dict(sh_degree=1.5),
+    dict(indices=np.array([0], np.uint32), mask=np.ones(3, np.uint8)),
+    dict(indices=np.array([0], np.uint32), box=[[0, 0, 0], [1, 1, 1]]),
+    dict(indices=np.array([0], np.uint32), min_alpha=0.0),
+    dict(box=[[0, 0, float("nan")], [1, 1, 1]]), dict(box=[[0, 0, 0], [1, float("nan"), 1]]),
+    dict(box=[[0, 0, 0]]), dict(box=[[0, 0, 0, 0], [1, 1, 1, 1]]), dict(box=[0, 0, 0, 1, 1, 1]),
+    dict(min_alpha=float("nan")),
+    dict(indices=np.array([3, -1], np.int64)), dict(indices=np.array([2 ** 32], np.uint64)),
+    dict(indices=np.array([2 ** 40], np.int64)), dict(indices=np.array([0.0, 1.0])),
+    dict(indices=np.zeros((2, 2), np.uint32)), dict(mask=np.ones(4, np.float32)),
+], ids=lambda kw: ",".join(f"{k}" for k in kw))
+def test_bad_arguments_raise_value_error_before_device_work(spz, some_file, tmp_path, kw):
+    with pytest.raises(ValueError):
+        spz.filter_spz(some_file, str(tmp_path / "out.spz"), **kw)
+    assert not (tmp_path / "out.spz").exists()
+
+
+def test_device_select_subset_check_their_arguments():
+    torch = pytest.importorskip("torch")
+    from spz_amd import device as D
+    hdr = D.make_header(10, 2)
+    st = torch.zeros(16, dtype=torch.uint8)
+    with pytest.raises(ValueError):
+        D.select(st, hdr, box=[[0, 0, 0], [1, 1, float("nan")]])
+    with pytest.raises(ValueError):
+        D.select(st, hdr, min_alpha=float("nan"))
+    with pytest.raises(ValueError):
+        D.select(st, hdr, to_coord=9)
+    with pytest.raises(ValueError):
+        D.subset(st, hdr, torch.zeros(1, dtype=torch.int32), sh_degree=3)
+    with pytest.raises(ValueError):
+        D.subset(st, hdr, torch.zeros(1, dtype=torch.int64))
+
+
+# ---- the CLI -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("argv", [
+    ["spz_filter"], ["spz_filter", "in.spz"], ["spz_tool", "spz_filter"], ["spz_tool", "spz_filter", "in.spz"],
+    ["spz_filter", "a.spz", "b.spz", "--sh-degree"], ["spz_filter", "a.spz", "b.spz", "--sh-degree", "4"],
+    ["spz_filter", "a.spz", "b.spz", "--box", "0", "0", "0", "1", "1"], ["spz_filter", "a.spz", "b.spz", "--coord", "XYZ"],
+    ["spz_filter", "a.spz", "b.spz", "--min-alpha", "abc"], ["spz_filter", "a.spz", "b.spz", "--bogus"],
+])
+def test_cli_usage(argv, tmp_path):
+    exe = os.path.join(ROOT, "spz_amd", "bin", argv[0])
+    r = subprocess.run([exe] + argv[1:], capture_output=True, text=True, cwd=str(tmp_path), timeout=60)
+    assert r.returncode == 1
+    assert r.stderr.startswith("Usage: spz_filter <input.spz> <output.spz>")
+    assert not (tmp_path / "b.spz").exists()
