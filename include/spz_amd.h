@@ -257,6 +257,55 @@ int spz_amd_filter_fetch(void *ctx, uint8_t *h_out);
 const uint8_t *spz_amd_filter_device_data(void *ctx);
 void spz_amd_filter_close(void *ctx);
 
+/* ---- transform: place a scene, p -> s*R*p + t, on a resident cloud or on a packed stream (spz_transform.hip; DESIGN
+ *      "Transform").  The reference has only the axis flips of convertCoordinates.
+ *
+ *      transform_params (host only, no GPU): rotation q = (x, y, z, w) (NULL: identity; any nonzero finite length),
+ *      translation t (NULL: 0; finite), uniform scale s (finite, > 0, and so in f32), all stated in `coord`; they are
+ *      conjugated into the stored RUB frame in double with the axis flips of coordinateConverter(coord, RUB), and every
+ *      entry of the block is rounded to f32 once.  D1 / D2 / D3 rotate the sh bands 1..3 in the 3DGS real-SH basis with
+ *      its signs (D_l[k][m] = sum_q w_q Y_k(R^T d_q) Y_m(d_q); new c[m] = sum_k D_l[k][m] c[k]).  Entries within 1e-12
+ *      of 0 or +-1 are snapped, so axis-aligned turns give signed permutations.  A bad argument: SPZ_AMD_ERR_INVALID_ARG.
+ *      The flags say which steps run: positions unless the map is the identity, log-scales (+ ln_s) unless s == 1,
+ *      rotations (q' = q_R * q, Hamilton) and sh unless R is the identity.  The default block is a bitwise no-op.
+ *
+ *      Per point, in f32 with every product and sum rounded on its own: p'_i = ((M_i0 x + M_i1 y) + M_i2 z) + t_i;
+ *      l' = l + ln_s; q' = q_R * q (not normalised); c'[m] = sum over k ascending, starting from the k = 0 product.
+ *      Alphas and colours are untouched.
+ *
+ *      transform_cloud_device: in place on device arrays (any pointer may be NULL).  transform_packed_device: any
+ *      version 1/2/3 stream (any fractionalBits) -> a v3 stream of the same points, sh degree and antialiased bit, with
+ *      positions at `fractional_bits` (0..24; saveSpz writes 12), in one pass: every float is the decoder's, every byte
+ *      the encoder's.  d_out: capacity >= spz_amd_stream_layout(n, degree, 3).total_bytes.  d_out_of_range (device
+ *      memory, may be NULL): set to the number of points whose new position is not finite or does not fit the 24-bit
+ *      field at fractional_bits (their bytes wrap, as saveSpz's would).  Both are enqueued on hip_stream, no
+ *      synchronisation.  The host form (open / fetch / device_data / close, shaped like the filter's) takes a stream
+ *      already in device memory, runs on `device` on a stream of its own and blocks; h_ms (may be NULL): [0] wall-clock
+ *      milliseconds of the kernel.  transform_cloud_host: host arrays in place (upload, kernel, download; blocking). */
+typedef struct {
+  float m[9];                 /* s * R, row-major */
+  float t[3];
+  float ln_s;                 /* log(s) */
+  float q[4];                 /* unit q_R, (x, y, z, w) */
+  float d1[9], d2[25], d3[49];  /* D_l[k][m], row-major */
+  int32_t apply_positions, apply_scales, apply_rotation;
+} spz_amd_transform;
+int spz_amd_transform_params(const double rotation[4], const double translation[3], double scale, int coord,
+                             spz_amd_transform *out);
+int spz_amd_transform_cloud_device(float *d_positions, float *d_scales, float *d_rotations, float *d_sh,
+                                   uint64_t num_points, int sh_degree, const spz_amd_transform *xf, void *hip_stream);
+int spz_amd_transform_packed_device(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr,
+                                    const spz_amd_transform *xf, int fractional_bits, uint8_t *d_out, size_t capacity,
+                                    uint64_t *d_out_of_range, void *hip_stream);
+int spz_amd_transform_open(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, const spz_amd_transform *xf,
+                           int fractional_bits, int device, void **ctx, uint64_t *h_out_bytes, uint64_t *h_out_of_range,
+                           float *h_ms);
+int spz_amd_transform_fetch(void *ctx, uint8_t *h_out);
+const uint8_t *spz_amd_transform_device_data(void *ctx);
+void spz_amd_transform_close(void *ctx);
+int spz_amd_transform_cloud_host(float *h_positions, float *h_scales, float *h_rotations, float *h_sh,
+                                 uint64_t num_points, int sh_degree, const spz_amd_transform *xf, int device);
+
 /* ---- device buffers for a resident cloud, placed for speed (spz_place.hip).  Whether an sh3 decode runs
  *      at 0.46 ms or at 0.55 ms is decided by whether the sh float array shares a physical region of HBM with the other
  *      arrays of the launch; that cannot be asked for, but it shows in one launch.  alloc: the five small arrays (and a

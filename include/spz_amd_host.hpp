@@ -288,6 +288,28 @@ bool filterSpz(const uint8_t *data, int32_t size, const FilterOptions &options, 
                int64_t *kept = nullptr);
 bool filterSpz(const std::string &inputFilename, const std::string &outputFilename, const FilterOptions &options,
                int64_t *kept = nullptr);
+// Transform (DESIGN "Transform"): place a scene, p -> scale * R(rotation) * p + translation, stated in `coord`, with the
+// rotation applied to every quaternion and to the sh bands (3DGS real-SH basis) and log(scale) added to every log-scale.
+// rotation (x, y, z, w) need not be unit length (zero or non-finite is a bad argument); scale finite and > 0.  The
+// parameter block and the per-point arithmetic are spz_amd_transform_params' (include/spz_amd.h).
+// transformSpz: the member is inflated (loadSpzPackedDevice), the stream transformed in HBM in one pass
+// (spz_amd_transform_open; any version 1/2/3 input, a v3 output with positions at fractionalBits, 0 ... 24; saveSpz writes
+// 12), and compressed with zlib's level-6 bytes.  A point whose new position does not fit the 24-bit field at
+// fractionalBits is refused (saveSpz would wrap it): the count is named, and no output is written.
+// transformCloud: in place on the cloud's arrays (upload, kernel, download).
+// false + one "[SPZ ERROR] transformSpz: …" (transformCloud: …) line on a bad argument (lastDeviceStatus() =
+// SPZ_AMD_ERR_INVALID_ARG), an input that does not load, points out of range, or a device failure.
+// SPZ_AMD_TRANSFORM_TIMING=1 prints the stages' times to stderr.
+struct TransformOptions {
+  std::array<double, 4> rotation = {0.0, 0.0, 0.0, 1.0};
+  std::array<double, 3> translation = {0.0, 0.0, 0.0};
+  double scale = 1.0;
+  CoordinateSystem coord = CoordinateSystem::UNSPECIFIED;  // of rotation and translation
+  int32_t fractionalBits = 12;                             // of the output positions (transformSpz)
+};
+bool transformSpz(const uint8_t *data, int32_t size, const TransformOptions &options, std::vector<uint8_t> *out);
+bool transformSpz(const std::string &inputFilename, const std::string &outputFilename, const TransformOptions &options);
+bool transformCloud(GaussianCloud &gaussians, const TransformOptions &options);
 // Status (spz_amd.h codes) of the last device call made by this thread; 0 = ok.
 int lastDeviceStatus();
 void setLastDeviceStatus(int status);

@@ -61,6 +61,9 @@ EXPORTS = (
     "spz_amd_encode_host_keep_session", "spz_amd_encode_host_keep_session_tail", "spz_amd_decode_gather_host_from_device",
     "spz_amd_filter_workspace_bytes", "spz_amd_select_device", "spz_amd_subset_device",
     "spz_amd_filter_open", "spz_amd_filter_fetch", "spz_amd_filter_device_data", "spz_amd_filter_close",
+    "spz_amd_transform_params", "spz_amd_transform_cloud_device", "spz_amd_transform_packed_device",
+    "spz_amd_transform_open", "spz_amd_transform_fetch", "spz_amd_transform_device_data", "spz_amd_transform_close",
+    "spz_amd_transform_cloud_host",
 )
 
 RCCL_UNIQUE_ID_BYTES = 128
@@ -112,6 +115,14 @@ class Selection(C.Structure):
     """spz_amd_selection: the predicates of spz_amd_select_device (box inclusive, alpha on the decoded logit)."""
     _fields_ = [("to_coord", C.c_int32), ("use_box", C.c_int32), ("box_lo", C.c_float * 3), ("box_hi", C.c_float * 3),
                 ("use_min_alpha", C.c_int32), ("min_alpha", C.c_float)]
+
+
+class Transform(C.Structure):
+    """spz_amd_transform: the f32 parameter block of spz_amd_transform_params (M = s*R row-major, t, ln_s, unit q_R,
+    the sh band matrices D_l[k][m] row-major, and which steps run)."""
+    _fields_ = [("m", C.c_float * 9), ("t", C.c_float * 3), ("ln_s", C.c_float), ("q", C.c_float * 4),
+                ("d1", C.c_float * 9), ("d2", C.c_float * 25), ("d3", C.c_float * 49),
+                ("apply_positions", C.c_int32), ("apply_scales", C.c_int32), ("apply_rotation", C.c_int32)]
 
 
 class SpzAmdError(RuntimeError):
@@ -281,6 +292,24 @@ def bind(L):
     L.spz_amd_filter_device_data.argtypes = [vp]
     L.spz_amd_filter_close.restype = None
     L.spz_amd_filter_close.argtypes = [vp]
+    d3 = C.POINTER(C.c_double)
+    L.spz_amd_transform_params.restype = i32
+    L.spz_amd_transform_params.argtypes = [d3, d3, C.c_double, i32, C.POINTER(Transform)]
+    L.spz_amd_transform_cloud_device.restype = i32
+    L.spz_amd_transform_cloud_device.argtypes = [vp, vp, vp, vp, u64, i32, C.POINTER(Transform), vp]
+    L.spz_amd_transform_packed_device.restype = i32
+    L.spz_amd_transform_packed_device.argtypes = [vp, sz, C.POINTER(Header), C.POINTER(Transform), i32, vp, sz, vp, vp]
+    L.spz_amd_transform_open.restype = i32
+    L.spz_amd_transform_open.argtypes = [vp, sz, C.POINTER(Header), C.POINTER(Transform), i32, i32, C.POINTER(vp),
+                                         C.POINTER(u64), C.POINTER(u64), vp]
+    L.spz_amd_transform_fetch.restype = i32
+    L.spz_amd_transform_fetch.argtypes = [vp, vp]
+    L.spz_amd_transform_device_data.restype = vp
+    L.spz_amd_transform_device_data.argtypes = [vp]
+    L.spz_amd_transform_close.restype = None
+    L.spz_amd_transform_close.argtypes = [vp]
+    L.spz_amd_transform_cloud_host.restype = i32
+    L.spz_amd_transform_cloud_host.argtypes = [vp, vp, vp, vp, u64, i32, C.POINTER(Transform), i32]
     L.spz_amd_zlib_encode_blocks.restype = i32
     L.spz_amd_zlib_encode_blocks.argtypes = [vp, vp, u32, u32, vp, vp, vp, u64, u64, vp, vp]
     return L
@@ -316,6 +345,31 @@ def peek_header(stream_bytes, max_points=REFERENCE_MAX_POINTS):
     h = Header()
     rc = load_library().spz_amd_peek_header_ex(buf, len(stream_bytes), int(max_points), C.byref(h))
     return rc, (h if rc == OK else None)
+
+
+def transform_params(rotation=None, translation=None, scale=1.0, coord=UNSPECIFIED):
+    """The f32 parameter block of p -> scale * R(rotation) * p + translation stated in `coord` (spz_amd_transform_params,
+    host only).  rotation (x, y, z, w): None = identity; translation: None = 0.  A bad argument raises ValueError."""
+    import math
+    dbl = C.c_double
+    q = t = None
+    if rotation is not None:
+        rotation = [float(v) for v in rotation]
+        if len(rotation) != 4:
+            raise ValueError("rotation must be (x, y, z, w)")
+        q = (dbl * 4)(*rotation)
+    if translation is not None:
+        translation = [float(v) for v in translation]
+        if len(translation) != 3:
+            raise ValueError("translation must be (x, y, z)")
+        t = (dbl * 3)(*translation)
+    if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(scale):
+        raise ValueError("scale must be a finite number > 0")
+    out = Transform()
+    rc = load_library().spz_amd_transform_params(q, t, float(scale), int(coord), C.byref(out))
+    if rc != OK:
+        raise ValueError(f"invalid transform: rotation={rotation} translation={translation} scale={scale} coord={coord}")
+    return out
 
 
 def get_tables():

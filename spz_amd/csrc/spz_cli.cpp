@@ -1,10 +1,10 @@
 // spz_cli.cpp — the three command-line tools of the reference (cli_tools/src/*.cpp) over the
-// MI355X drop-in layer: ply_to_spz, spz_to_ply, spz_info; and spz_filter (spz::filterSpz, no
-// counterpart in the reference).  One binary, dispatched on argv[0] (the Makefile installs it under
-// the four names) or on a first argument naming the tool.
+// MI355X drop-in layer: ply_to_spz, spz_to_ply, spz_info; and spz_filter (spz::filterSpz) and
+// spz_transform (spz::transformSpz), which have no counterpart in the reference.  One binary, dispatched
+// on argv[0] (the Makefile installs it under the five names) or on a first argument naming the tool.
 // Same behaviour as the reference mains: default (UNSPECIFIED) pack/unpack options, exit code 0
 // once the arguments are there (the reference ignores the save/load results), usage -> 1.
-// spz_filter exits 1 when the filter fails as well.
+// spz_filter and spz_transform exit 1 when the filter / transform fails as well.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -113,11 +113,64 @@ int spzFilter(int argc, char **argv) {
   return 0;
 }
 
+const char *kTransformUsage =
+    "Usage: spz_transform <input.spz> <output.spz> [--rotate x y z w] [--translate x y z] [--scale s] "
+    "[--coord RUB|RDF|LUF|RUF|LDB|RDB|LUB|LDF|UNSPECIFIED] [--fractional-bits n]";
+
+bool parseDouble(const char *s, double *v) {
+  char *end = nullptr;
+  *v = std::strtod(s, &end);
+  return end != s && *end == '\0';
+}
+
+int spzTransform(int argc, char **argv) {
+  auto usage = [] {
+    std::cerr << kTransformUsage << std::endl;
+    return 1;
+  };
+  if (argc < 3) return usage();
+  spz::TransformOptions o;
+  for (int i = 3; i < argc; ++i) {
+    const std::string a = argv[i];
+    if (a == "--rotate" && i + 4 < argc) {
+      for (int k = 0; k < 4; ++k) {
+        if (!parseDouble(argv[i + 1 + k], &o.rotation[k])) return usage();
+      }
+      i += 4;
+    } else if (a == "--translate" && i + 3 < argc) {
+      for (int k = 0; k < 3; ++k) {
+        if (!parseDouble(argv[i + 1 + k], &o.translation[k])) return usage();
+      }
+      i += 3;
+    } else if (a == "--scale" && i + 1 < argc) {
+      if (!parseDouble(argv[++i], &o.scale)) return usage();
+    } else if (a == "--coord" && i + 1 < argc) {
+      static const char *names[] = {"UNSPECIFIED", "LDB", "RDB", "LUB", "RUB", "LDF", "RDF", "LUF", "RUF"};
+      const std::string c = argv[++i];
+      int found = -1;
+      for (int k = 0; k < 9; ++k) {
+        if (c == names[k]) found = k;
+      }
+      if (found < 0) return usage();
+      o.coord = static_cast<spz::CoordinateSystem>(found);
+    } else if (a == "--fractional-bits" && i + 1 < argc) {
+      char *end = nullptr;
+      const long d = std::strtol(argv[++i], &end, 10);
+      if (*end != '\0' || d < 0 || d > 24) return usage();
+      o.fractionalBits = static_cast<int32_t>(d);
+    } else {
+      return usage();
+    }
+  }
+  return spz::transformSpz(std::string(argv[1]), std::string(argv[2]), o) ? 0 : 1;
+}
+
 int dispatch(const std::string &tool, int argc, char **argv) {
   if (tool == "ply_to_spz") return plyToSpz(argc, argv);
   if (tool == "spz_to_ply") return spzToPly(argc, argv);
   if (tool == "spz_info") return spzInfo(argc, argv);
   if (tool == "spz_filter") return spzFilter(argc, argv);
+  if (tool == "spz_transform") return spzTransform(argc, argv);
   return -1;
 }
 
@@ -134,7 +187,7 @@ int main(int argc, char **argv) {
       rc = dispatch(argv[1], argc - 1, argv + 1);
       if (rc >= 0) return rc;
     }
-    std::cerr << "Usage: spz_tool {ply_to_spz|spz_to_ply|spz_info|spz_filter} <args...>" << std::endl;
+    std::cerr << "Usage: spz_tool {ply_to_spz|spz_to_ply|spz_info|spz_filter|spz_transform} <args...>" << std::endl;
     return 1;
   } catch (const std::exception &e) {
     std::cerr << "Error: " << e.what() << std::endl;

@@ -1864,6 +1864,113 @@ bool filterSpz(const std::string &inputFilename, const std::string &outputFilena
   return true;
 }
 
+// ---- transform ---------------------------------------------------------------------------------------------------
+namespace {
+bool transformRejected(const char *who, const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  char msg[256];
+  std::vsnprintf(msg, sizeof(msg), fmt, ap);
+  va_end(ap);
+  logLine("[SPZ ERROR] %s: %s", who, msg);
+  g_last_status = SPZ_AMD_ERR_INVALID_ARG;
+  return false;
+}
+
+struct TransformLaps {
+  bool on = std::getenv("SPZ_AMD_TRANSFORM_TIMING") != nullptr;
+  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+  void lap(const char *what) {
+    const auto now = std::chrono::steady_clock::now();
+    if (on) std::fprintf(stderr, "[transformSpz] %-9s %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
+    t = now;
+  }
+};
+
+// The parameter block of `o`, or false + the [SPZ ERROR] line: every check that needs no device.
+bool transformBlock(const char *who, const TransformOptions &o, bool packed, spz_amd_transform *xf) {
+  if (static_cast<int>(o.coord) < 0 || static_cast<int>(o.coord) > 8) return transformRejected(who, "unknown coordinate system %d", static_cast<int>(o.coord));
+  if (packed && (o.fractionalBits < 0 || o.fractionalBits > 24)) return transformRejected(who, "fractionalBits %d is outside 0 ... 24", o.fractionalBits);
+  if (spz_amd_transform_params(o.rotation.data(), o.translation.data(), o.scale, static_cast<int>(o.coord), xf) != SPZ_AMD_OK) {
+    return transformRejected(who, "the rotation must be finite and nonzero, the translation finite, the scale finite and > 0");
+  }
+  return true;
+}
+}  // namespace
+
+bool transformSpz(const uint8_t *data, int32_t size, const TransformOptions &o, std::vector<uint8_t> *out) {
+  g_last_status = SPZ_AMD_OK;
+  // the arguments first: nothing touches the device before they are known to be good
+  if (out == nullptr) return transformRejected("transformSpz", "no output vector");
+  spz_amd_transform xf;
+  if (!transformBlock("transformSpz", o, true, &xf)) return false;
+  TransformLaps laps;
+  DevicePackedGaussians d = loadSpzPackedDevice(data, size);
+  if (!d.valid()) {
+    if (g_last_status == SPZ_AMD_OK) logLine("[SPZ ERROR] transformSpz: the input is not a readable .spz");
+    return false;
+  }
+  laps.lap("inflate");
+  const spz_amd_header hdr = headerOf(d);
+  void *ctx = nullptr;
+  uint64_t bytes = 0, bad = 0;
+  float ms = 0.0f;
+  int rc = spz_amd_transform_open(d.stream, d.streamBytes, &hdr, &xf, o.fractionalBits, d.device, &ctx, &bytes, &bad, &ms);
+  if (deviceFailed(rc, "transformSpz")) return false;
+  struct Close {
+    void *c;
+    ~Close() { spz_amd_transform_close(c); }
+  } closer{ctx};
+  if (laps.on) std::fprintf(stderr, "[transformSpz] kernel    %.3f ms\n", ms);
+  laps.lap("transform");
+  if (bad > 0) {
+    return transformRejected("transformSpz", "%llu of %u points have a position that does not fit 24 bits at %d fractional bits "
+                             "(lower fractionalBits)", static_cast<unsigned long long>(bad), hdr.num_points, o.fractionalBits);
+  }
+  d.release();  // the input's device memory goes before the container stage takes its own
+  std::vector<uint8_t> stream;
+  detail::resizeUninitialized(&stream, static_cast<size_t>(bytes));
+  rc = spz_amd_transform_fetch(ctx, stream.data());
+  if (deviceFailed(rc, "transformSpz")) return false;
+  laps.lap("download");
+  // the device copy of the stream is this call's: the device writer reads it instead of uploading the host copy
+  if (!compressGzippedWithCopy(stream.data(), stream.size(), out, spz_amd_transform_device_data(ctx))) {
+    logLine("[SPZ ERROR] transformSpz: compressGzipped failed");
+    return false;
+  }
+  laps.lap("gzip");
+  return true;
+}
+
+bool transformSpz(const std::string &inputFilename, const std::string &outputFilename, const TransformOptions &o) {
+  g_last_status = SPZ_AMD_OK;
+  spz_amd_transform xf;
+  if (!transformBlock("transformSpz", o, true, &xf)) return false;
+  std::vector<uint8_t> data;
+  if (!readFile(inputFilename, &data, /*log=*/true)) return false;
+  if (data.size() > static_cast<size_t>(INT32_MAX)) return transformRejected("transformSpz", "%s is larger than 2 GiB", inputFilename.c_str());
+  std::vector<uint8_t> file;
+  if (!transformSpz(data.data(), static_cast<int32_t>(data.size()), o, &file)) return false;
+  TransformLaps laps;
+  if (!writeFile(outputFilename, file)) {
+    logLine("[SPZ ERROR] transformSpz: unable to write %s", outputFilename.c_str());
+    return false;
+  }
+  laps.lap("write");
+  return true;
+}
+
+bool transformCloud(GaussianCloud &g, const TransformOptions &o) {
+  g_last_status = SPZ_AMD_OK;
+  spz_amd_transform xf;
+  if (!transformBlock("transformCloud", o, false, &xf)) return false;
+  if (!checkSizes(g)) return transformRejected("transformCloud", "the cloud's arrays do not match numPoints / shDegree");
+  const int rc = spz_amd_transform_cloud_host(g.positions.data(), g.scales.data(), g.rotations.data(),
+                                              g.sh.empty() ? nullptr : g.sh.data(), static_cast<uint64_t>(g.numPoints),
+                                              g.shDegree, &xf, deviceIndex());
+  return !deviceFailed(rc, "transformCloud");
+}
+
 GaussianCloud loadSpz(const std::vector<uint8_t> &data, const UnpackOptions &o) {
   return loadSpz(data.data(), static_cast<int32_t>(data.size()), o);
 }

@@ -12,6 +12,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <sstream>
@@ -169,6 +170,57 @@ spz::FilterOptions filterOptions(const py::object &mask, const py::object &indic
     f.indices = std::move(v);
   }
   return f;
+}
+
+// transform_spz / transform_cloud's arguments as spz::TransformOptions; every problem is a ValueError, raised before any
+// device work (the parameter block is built on the host, spz_amd_transform_params).
+spz::TransformOptions transformOptions(const py::object &rotation, const py::object &translation, const py::object &scale,
+                                       spz::CoordinateSystem coord, const py::object &fractional_bits) {
+  spz::TransformOptions o;
+  o.coord = coord;
+  auto vec = [](const py::object &v, size_t n, const char *name) {
+    const std::string what = std::string(name) + " must be a sequence of " + std::to_string(n) + " finite numbers";
+    py::array a;
+    try {
+      a = py::array::ensure(v);
+    } catch (const py::error_already_set &) {
+      PyErr_Clear();
+    }
+    if (!a) throw py::value_error(what);
+    const char k = a.dtype().kind();
+    if (!(k == 'i' || k == 'u' || k == 'f') || a.ndim() != 1 || static_cast<size_t>(a.size()) != n) throw py::value_error(what);
+    py::array_t<double, py::array::c_style | py::array::forcecast> d(a);
+    std::vector<double> out(d.data(), d.data() + n);
+    for (double x : out) {
+      if (!std::isfinite(x)) throw py::value_error(what);
+    }
+    return out;
+  };
+  if (!rotation.is_none()) {
+    const std::vector<double> q = vec(rotation, 4, "rotation (x, y, z, w)");
+    std::copy(q.begin(), q.end(), o.rotation.begin());
+    if (q[0] == 0.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0) throw py::value_error("rotation must not be zero");
+  }
+  if (!translation.is_none()) {
+    const std::vector<double> t = vec(translation, 3, "translation (x, y, z)");
+    std::copy(t.begin(), t.end(), o.translation.begin());
+  }
+  if (py::isinstance<py::bool_>(scale) || !(py::isinstance<py::int_>(scale) || py::isinstance<py::float_>(scale))) {
+    throw py::value_error("scale must be a number");
+  }
+  o.scale = py::cast<double>(scale);
+  if (!std::isfinite(o.scale) || !(o.scale > 0.0)) throw py::value_error("scale must be finite and > 0");
+  if (!py::isinstance<py::int_>(fractional_bits) || py::isinstance<py::bool_>(fractional_bits)) {
+    throw py::value_error("fractional_bits must be an int in [0, 24]");
+  }
+  const long fb = py::cast<long>(fractional_bits);
+  if (fb < 0 || fb > 24) throw py::value_error("fractional_bits must be an int in [0, 24], got " + std::to_string(fb));
+  o.fractionalBits = static_cast<int32_t>(fb);
+  spz_amd_transform xf;
+  if (spz_amd_transform_params(o.rotation.data(), o.translation.data(), o.scale, static_cast<int>(coord), &xf) != SPZ_AMD_OK) {
+    throw py::value_error("the transform has no f32 parameter block (scale or translation out of the f32 range?)");
+  }
+  return o;
 }
 
 }  // namespace
@@ -391,6 +443,47 @@ PYBIND11_MODULE(spz, m) {
         "A smaller .spz out of an existing one without requantising (spz::filterSpz): the points `indices`, or those "
         "selected by mask / box (inclusive, positions in `coord`) / min_alpha (decoded logit), with sh lowered to "
         "`sh_degree`.  Returns the number of points kept.");
+  m.def("transform_spz",
+        [](const std::string &input, const std::string &output, const py::object &rotation, const py::object &translation,
+           const py::object &scale, spz::CoordinateSystem coord, const py::object &fractional_bits) {
+          const spz::TransformOptions o = transformOptions(rotation, translation, scale, coord, fractional_bits);
+          bool ok;
+          {
+            py::gil_scoped_release release;
+            ok = spz::transformSpz(input, output, o);
+          }
+          if (!ok) {
+            raiseIfDeviceUnusable();
+            if (spz::lastDeviceStatus() == SPZ_AMD_ERR_INVALID_ARG) {
+              throw py::value_error("transform_spz: refused for this file (see the [SPZ ERROR] line)");
+            }
+            throw std::runtime_error("transform_spz: " + input + " -> " + output + " failed (see the [SPZ ERROR] line)");
+          }
+        },
+        py::arg("input_filename"), py::arg("output_filename"), py::kw_only(), py::arg("rotation") = py::none(),
+        py::arg("translation") = py::none(), py::arg("scale") = 1.0, py::arg("coord") = spz::CoordinateSystem::UNSPECIFIED,
+        py::arg("fractional_bits") = 12,
+        "Place a scene (spz::transformSpz): p -> scale * R(rotation) * p + translation, stated in `coord`, with the "
+        "rotation applied to the quaternions and the sh bands; rotation is (x, y, z, w).  The output is a v3 file with "
+        "positions at `fractional_bits`; a position that does not fit is refused (ValueError).");
+  m.def("transform_cloud",
+        [](spz::GaussianCloud &g, const py::object &rotation, const py::object &translation, const py::object &scale,
+           spz::CoordinateSystem coord) {
+          const spz::TransformOptions o = transformOptions(rotation, translation, scale, coord, py::int_(12));
+          bool ok;
+          {
+            py::gil_scoped_release release;
+            ok = spz::transformCloud(g, o);
+          }
+          if (!ok) {
+            raiseIfDeviceUnusable();
+            if (spz::lastDeviceStatus() == SPZ_AMD_ERR_INVALID_ARG) throw py::value_error("transform_cloud: the cloud's arrays do not match");
+            throw std::runtime_error("transform_cloud failed (see the [SPZ ERROR] line)");
+          }
+        },
+        py::arg("cloud"), py::kw_only(), py::arg("rotation") = py::none(), py::arg("translation") = py::none(),
+        py::arg("scale") = 1.0, py::arg("coord") = spz::CoordinateSystem::UNSPECIFIED,
+        "transform_spz's transform in place on a GaussianCloud (spz::transformCloud), in f32 without quantising.");
   m.def("save_spz",
         [](const spz::GaussianCloud &g, const spz::PackOptions &o, const std::string &filename) {
           bool ok;

@@ -276,6 +276,59 @@ def subset(stream_t, header, indices, sh_degree=None, out=None, stream=None):
     return out[:lay.total_bytes]
 
 
+def transform(cloud, num_points, sh_degree, *, rotation=None, translation=None, scale=1.0, coord=0, stream=None):
+    """p -> scale * R(rotation) * p + translation (stated in `coord`) in place on device tensors: positions, log-scales
+    (+ log(scale)), rotations (q_R * q) and the sh bands (spz_amd_transform_cloud_device).  Any of the four may be
+    missing.  A bad argument raises ValueError before the launch."""
+    L = abi.load_library()
+    xf = abi.transform_params(rotation, translation, scale, coord)
+    if int(sh_degree) not in SH_DIM:
+        raise ValueError(f"sh_degree must be 0..3, got {sh_degree}")
+    dev = None
+    ptrs = []
+    for k in ("positions", "scales", "rotations", "sh"):
+        t = cloud.get(k)
+        need = num_points * floats_per_point(k, sh_degree)
+        if t is None or need == 0:
+            ptrs.append(None)
+            continue
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() != need:
+            raise ValueError(f"cloud[{k!r}] must be a contiguous float32 CUDA tensor of {need} elements")
+        if dev is not None and t.device != dev:
+            raise ValueError(f"cloud[{k!r}] is on {t.device}, expected {dev}")
+        dev = t.device
+        ptrs.append(t.data_ptr())
+    if dev is None:
+        return cloud
+    with torch.cuda.device(dev):
+        rc = L.spz_amd_transform_cloud_device(*ptrs, num_points, sh_degree, C.byref(xf), _stream_handle(stream))
+    abi.check(rc, "spz_amd_transform_cloud_device")
+    return cloud
+
+
+def transform_packed(stream_t, header, *, rotation=None, translation=None, scale=1.0, coord=0, fractional_bits=12,
+                     out=None, stream=None):
+    """transform() on a packed device stream (any version) in one pass: returns (v3 stream as a uint8 CUDA tensor with
+    positions at `fractional_bits`, out-of-range count as a 1-element int64 CUDA tensor).  The count is of the points
+    whose new position does not fit the 24-bit field; their bytes wrap (spz_amd_transform_packed_device)."""
+    L = abi.load_library()
+    xf = abi.transform_params(rotation, translation, scale, coord)
+    if isinstance(fractional_bits, bool) or not isinstance(fractional_bits, int) or not 0 <= fractional_bits <= 24:
+        raise ValueError(f"fractional_bits must be an int in [0, 24], got {fractional_bits!r}")
+    if stream_t.dtype != torch.uint8 or not stream_t.is_cuda or not stream_t.is_contiguous():
+        raise ValueError("stream_t must be a contiguous uint8 CUDA tensor")
+    lay = abi.stream_layout(header.num_points, header.sh_degree, 3)
+    if out is None:
+        out = torch.empty(lay.total_bytes, dtype=torch.uint8, device=stream_t.device)
+    bad = torch.empty(1, dtype=torch.int64, device=stream_t.device)
+    with torch.cuda.device(stream_t.device):
+        rc = L.spz_amd_transform_packed_device(stream_t.data_ptr(), stream_t.numel(), C.byref(header), C.byref(xf),
+                                               fractional_bits, out.data_ptr(), out.numel(), bad.data_ptr(),
+                                               _stream_handle(stream))
+    abi.check(rc, "spz_amd_transform_packed_device")
+    return out[:lay.total_bytes], bad
+
+
 def convert_coordinates(cloud, num_points, sh_degree, from_coord, to_coord, stream=None):
     """In-place GaussianCloud::convertCoordinates on device tensors (positions, rotations, sh)."""
     L = abi.load_library()
@@ -301,6 +354,6 @@ def to_numpy(cloud_t):
 
 
 __all__ = ["encode", "decode", "encode_shard", "decode_shard", "decode_gather", "peek_header", "convert_coordinates",
-           "select", "subset",
+           "select", "subset", "transform", "transform_packed",
            "alloc_cloud",
            "make_header", "to_device", "to_numpy", "SH_DIM"]
