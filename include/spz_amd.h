@@ -306,6 +306,49 @@ void spz_amd_transform_close(void *ctx);
 int spz_amd_transform_cloud_host(float *h_positions, float *h_scales, float *h_rotations, float *h_sh,
                                  uint64_t num_points, int sh_degree, const spz_amd_transform *xf, int device);
 
+/* ---- merge: K packed streams -> one version 3 stream (spz_merge.hip; DESIGN "Merge").  The reference has no
+ *      counterpart (its only route is load every file -> concatenate floats -> save, which requantises).
+ *
+ *      Output: input 0's points, then input 1's, ...  Header (merge_resolve, host only, no GPU): num_points = sum n_i
+ *      (above SPZ_AMD_REFERENCE_MAX_POINTS: SPZ_AMD_ERR_TOO_MANY_POINTS); sh_degree d' (-1: the largest input degree;
+ *      0..3); fractionalBits f' (-1: the value every v2/v3 input shares when they agree, else 12 (v1 inputs do not
+ *      vote); 0..24); antialiased (-1: every input must agree, else SPZ_AMD_ERR_INVALID_ARG; 0/1 overrides); reserved
+ *      0.  k == 0, k > SPZ_AMD_MERGE_MAX_INPUTS or a request out of range: SPZ_AMD_ERR_INVALID_ARG.  *out_bytes (may
+ *      be NULL) = spz_amd_stream_layout(sum n_i, d', 3).total_bytes.
+ *
+ *      Per input and section, bytes are copied unless the encoding or the placement forces a change: alphas and
+ *      colours always; scales unless the placement scales (then + ln s per byte); positions when v2/v3 at f' and not
+ *      moved (else the decoder's floats, placed, the encoder's bytes at f'); rotations when v3 and not rotated (else
+ *      decoded, q_R * q, packed smallest-three); sh records unless the placement rotates (then rotated at the input's
+ *      degree and re-quantised), cut to 3*dim(d') bytes or padded with byte 128 (0.0).  Each input's xf (host memory,
+ *      NULL = identity) is a block of spz_amd_transform_params.
+ *
+ *      merge_device: d_out (capacity >= out_bytes), d_workspace (spz_amd_merge_workspace_bytes(k) bytes of device
+ *      memory owned by the caller for the call; the descriptor table is copied into it), d_out_of_range (device
+ *      memory, may be NULL: set to the number of points whose position is not finite or does not fit 24 bits at f'; their
+ *      bytes wrap).  out_hdr is merge_resolve's.  Enqueued on hip_stream, no synchronisation; no host memory is read
+ *      by the device after it returns.  The host form (open / fetch / device_data / close, shaped like the filter's)
+ *      resolves the header, runs on `device` on a stream of its own and blocks; h_ms (may be NULL): [0] wall-clock
+ *      milliseconds of the table upload and the kernel. */
+#define SPZ_AMD_MERGE_MAX_INPUTS 1024u
+typedef struct {
+  const uint8_t *d_stream;       /* device memory: header + sections */
+  size_t size;
+  spz_amd_header hdr;
+  const spz_amd_transform *xf;   /* host memory; NULL: no placement */
+} spz_amd_merge_input;
+int spz_amd_merge_resolve(const spz_amd_header *headers, uint64_t k, int sh_degree, int fractional_bits, int antialiased,
+                          spz_amd_header *out_hdr, uint64_t *out_bytes);
+uint64_t spz_amd_merge_workspace_bytes(uint64_t k);
+int spz_amd_merge_device(const spz_amd_merge_input *inputs, uint64_t k, const spz_amd_header *out_hdr, uint8_t *d_out,
+                         size_t capacity, void *d_workspace, uint64_t *d_out_of_range, void *hip_stream);
+int spz_amd_merge_open(const spz_amd_merge_input *inputs, uint64_t k, int sh_degree, int fractional_bits, int antialiased,
+                       int device, void **ctx, spz_amd_header *out_hdr, uint64_t *h_out_bytes, uint64_t *h_out_of_range,
+                       float *h_ms);
+int spz_amd_merge_fetch(void *ctx, uint8_t *h_out);
+const uint8_t *spz_amd_merge_device_data(void *ctx);
+void spz_amd_merge_close(void *ctx);
+
 /* ---- device buffers for a resident cloud, placed for speed (spz_place.hip).  Whether an sh3 decode runs
  *      at 0.46 ms or at 0.55 ms is decided by whether the sh float array shares a physical region of HBM with the other
  *      arrays of the launch; that cannot be asked for, but it shows in one launch.  alloc: the five small arrays (and a

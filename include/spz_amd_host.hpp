@@ -310,6 +310,27 @@ struct TransformOptions {
 bool transformSpz(const uint8_t *data, int32_t size, const TransformOptions &options, std::vector<uint8_t> *out);
 bool transformSpz(const std::string &inputFilename, const std::string &outputFilename, const TransformOptions &options);
 bool transformCloud(GaussianCloud &gaussians, const TransformOptions &options);
+// Merge (DESIGN "Merge"): one v3 .spz out of K >= 1 (at most SPZ_AMD_MERGE_MAX_INPUTS) inputs of any version, input
+// 0's points first.  Bytes are copied wherever the encoding and the placement allow (so v3 inputs at the output's
+// fractionalBits and degree with no placement merge losslessly, and a lone such file comes back byte for byte);
+// positions, rotations, scales and sh are re-encoded with the transform's arithmetic only where they must be
+// (spz_amd_merge_resolve / spz_amd_merge_device in include/spz_amd.h).  Every input is inflated on the device
+// (loadSpzPackedDevice), one kernel writes the output, the inputs' device memory is released, and the stream is
+// compressed with zlib's level-6 bytes.  A position that does not fit 24 bits at fractionalBits is refused (the count is
+// named, no output is written).  false + one "[SPZ ERROR] mergeSpz: …" line on a bad argument or a conflict
+// (lastDeviceStatus() = SPZ_AMD_ERR_INVALID_ARG), an input that does not load, or a device failure.
+struct MergeOptions {
+  int32_t shDegree = -1;         // -1: the largest input degree; 0 ... 3
+  int32_t fractionalBits = -1;   // -1: the value all v2/v3 inputs share, else 12; 0 ... 24
+  int32_t antialiased = -1;      // -1: the inputs must agree; 0 / 1 overrides
+  // empty, or one entry per input: its placement (nullopt: none).  The entries' fractionalBits field is ignored: the
+  // output's is the merge's.
+  std::vector<std::optional<TransformOptions>> transforms;
+};
+bool mergeSpz(const std::vector<std::vector<uint8_t>> &inputs, const MergeOptions &options, std::vector<uint8_t> *out,
+              int64_t *points = nullptr);
+bool mergeSpz(const std::vector<std::string> &inputFilenames, const std::string &outputFilename,
+              const MergeOptions &options, int64_t *points = nullptr);
 // Status (spz_amd.h codes) of the last device call made by this thread; 0 = ok.
 int lastDeviceStatus();
 void setLastDeviceStatus(int status);

@@ -64,6 +64,8 @@ EXPORTS = (
     "spz_amd_transform_params", "spz_amd_transform_cloud_device", "spz_amd_transform_packed_device",
     "spz_amd_transform_open", "spz_amd_transform_fetch", "spz_amd_transform_device_data", "spz_amd_transform_close",
     "spz_amd_transform_cloud_host",
+    "spz_amd_merge_resolve", "spz_amd_merge_workspace_bytes", "spz_amd_merge_device", "spz_amd_merge_open",
+    "spz_amd_merge_fetch", "spz_amd_merge_device_data", "spz_amd_merge_close",
 )
 
 RCCL_UNIQUE_ID_BYTES = 128
@@ -123,6 +125,14 @@ class Transform(C.Structure):
     _fields_ = [("m", C.c_float * 9), ("t", C.c_float * 3), ("ln_s", C.c_float), ("q", C.c_float * 4),
                 ("d1", C.c_float * 9), ("d2", C.c_float * 25), ("d3", C.c_float * 49),
                 ("apply_positions", C.c_int32), ("apply_scales", C.c_int32), ("apply_rotation", C.c_int32)]
+
+
+MERGE_MAX_INPUTS = 1024   # SPZ_AMD_MERGE_MAX_INPUTS
+
+
+class MergeInput(C.Structure):
+    """spz_amd_merge_input: one input of a merge (device stream, its size and header, NULL or a placement block)."""
+    _fields_ = [("d_stream", C.c_void_p), ("size", C.c_size_t), ("hdr", Header), ("xf", C.POINTER(Transform))]
 
 
 class SpzAmdError(RuntimeError):
@@ -310,6 +320,21 @@ def bind(L):
     L.spz_amd_transform_close.argtypes = [vp]
     L.spz_amd_transform_cloud_host.restype = i32
     L.spz_amd_transform_cloud_host.argtypes = [vp, vp, vp, vp, u64, i32, C.POINTER(Transform), i32]
+    L.spz_amd_merge_resolve.restype = i32
+    L.spz_amd_merge_resolve.argtypes = [C.POINTER(Header), u64, i32, i32, i32, C.POINTER(Header), C.POINTER(u64)]
+    L.spz_amd_merge_workspace_bytes.restype = u64
+    L.spz_amd_merge_workspace_bytes.argtypes = [u64]
+    L.spz_amd_merge_device.restype = i32
+    L.spz_amd_merge_device.argtypes = [C.POINTER(MergeInput), u64, C.POINTER(Header), vp, sz, vp, vp, vp]
+    L.spz_amd_merge_open.restype = i32
+    L.spz_amd_merge_open.argtypes = [C.POINTER(MergeInput), u64, i32, i32, i32, i32, C.POINTER(vp), C.POINTER(Header),
+                                     C.POINTER(u64), C.POINTER(u64), vp]
+    L.spz_amd_merge_fetch.restype = i32
+    L.spz_amd_merge_fetch.argtypes = [vp, vp]
+    L.spz_amd_merge_device_data.restype = vp
+    L.spz_amd_merge_device_data.argtypes = [vp]
+    L.spz_amd_merge_close.restype = None
+    L.spz_amd_merge_close.argtypes = [vp]
     L.spz_amd_zlib_encode_blocks.restype = i32
     L.spz_amd_zlib_encode_blocks.argtypes = [vp, vp, u32, u32, vp, vp, vp, u64, u64, vp, vp]
     return L
@@ -370,6 +395,17 @@ def transform_params(rotation=None, translation=None, scale=1.0, coord=UNSPECIFI
     if rc != OK:
         raise ValueError(f"invalid transform: rotation={rotation} translation={translation} scale={scale} coord={coord}")
     return out
+
+
+def merge_resolve(headers, sh_degree=None, fractional_bits=None, antialiased=None):
+    """The output header and byte count of a merge of streams with these headers (spz_amd_merge_resolve, host only):
+    (status, Header or None, bytes).  None = the default of each request."""
+    hs = list(headers)
+    arr = (Header * max(len(hs), 1))(*hs)
+    out, nbytes = Header(), C.c_uint64(0)
+    req = [-1 if v is None else int(v) for v in (sh_degree, fractional_bits, antialiased)]
+    rc = load_library().spz_amd_merge_resolve(arr, len(hs), *req, C.byref(out), C.byref(nbytes))
+    return rc, (out if rc == OK else None), int(nbytes.value)
 
 
 def get_tables():

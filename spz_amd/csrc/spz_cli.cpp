@@ -1,10 +1,10 @@
 // spz_cli.cpp — the three command-line tools of the reference (cli_tools/src/*.cpp) over the
 // MI355X drop-in layer: ply_to_spz, spz_to_ply, spz_info; and spz_filter (spz::filterSpz) and
-// spz_transform (spz::transformSpz), which have no counterpart in the reference.  One binary, dispatched
-// on argv[0] (the Makefile installs it under the five names) or on a first argument naming the tool.
+// spz_transform (spz::transformSpz) and spz_merge (spz::mergeSpz), which have no counterpart in the reference.  One
+// binary, dispatched on argv[0] (the Makefile installs it under the six names) or on a first argument naming the tool.
 // Same behaviour as the reference mains: default (UNSPECIFIED) pack/unpack options, exit code 0
 // once the arguments are there (the reference ignores the save/load results), usage -> 1.
-// spz_filter and spz_transform exit 1 when the filter / transform fails as well.
+// spz_filter, spz_transform and spz_merge exit 1 when the filter / transform / merge fails as well.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -165,12 +165,54 @@ int spzTransform(int argc, char **argv) {
   return spz::transformSpz(std::string(argv[1]), std::string(argv[2]), o) ? 0 : 1;
 }
 
+const char *kMergeUsage =
+    "Usage: spz_merge <input.spz>... -o <output.spz> [--sh-degree D] [--fractional-bits B] [--antialiased 0|1]";
+
+bool parseInt(const char *s, long lo, long hi, int32_t *v) {
+  char *end = nullptr;
+  const long d = std::strtol(s, &end, 10);
+  if (end == s || *end != '\0' || d < lo || d > hi) return false;
+  *v = static_cast<int32_t>(d);
+  return true;
+}
+
+int spzMerge(int argc, char **argv) {
+  auto usage = [] {
+    std::cerr << kMergeUsage << std::endl;
+    return 1;
+  };
+  spz::MergeOptions o;
+  std::vector<std::string> inputs;
+  std::string output;
+  bool have_output = false;
+  for (int i = 1; i < argc; ++i) {
+    const std::string a = argv[i];
+    if (a == "-o" && i + 1 < argc && !have_output) {
+      output = argv[++i];
+      have_output = true;
+    } else if (a == "--sh-degree" && i + 1 < argc) {
+      if (!parseInt(argv[++i], 0, 3, &o.shDegree)) return usage();
+    } else if (a == "--fractional-bits" && i + 1 < argc) {
+      if (!parseInt(argv[++i], 0, 24, &o.fractionalBits)) return usage();
+    } else if (a == "--antialiased" && i + 1 < argc) {
+      if (!parseInt(argv[++i], 0, 1, &o.antialiased)) return usage();
+    } else if (!a.empty() && a[0] == '-') {
+      return usage();
+    } else {
+      inputs.push_back(a);
+    }
+  }
+  if (inputs.empty() || !have_output || output.empty()) return usage();
+  return spz::mergeSpz(inputs, output, o) ? 0 : 1;
+}
+
 int dispatch(const std::string &tool, int argc, char **argv) {
   if (tool == "ply_to_spz") return plyToSpz(argc, argv);
   if (tool == "spz_to_ply") return spzToPly(argc, argv);
   if (tool == "spz_info") return spzInfo(argc, argv);
   if (tool == "spz_filter") return spzFilter(argc, argv);
   if (tool == "spz_transform") return spzTransform(argc, argv);
+  if (tool == "spz_merge") return spzMerge(argc, argv);
   return -1;
 }
 
@@ -187,7 +229,7 @@ int main(int argc, char **argv) {
       rc = dispatch(argv[1], argc - 1, argv + 1);
       if (rc >= 0) return rc;
     }
-    std::cerr << "Usage: spz_tool {ply_to_spz|spz_to_ply|spz_info|spz_filter|spz_transform} <args...>" << std::endl;
+    std::cerr << "Usage: spz_tool {ply_to_spz|spz_to_ply|spz_info|spz_filter|spz_transform|spz_merge} <args...>" << std::endl;
     return 1;
   } catch (const std::exception &e) {
     std::cerr << "Error: " << e.what() << std::endl;

@@ -1971,6 +1971,127 @@ bool transformCloud(GaussianCloud &g, const TransformOptions &o) {
   return !deviceFailed(rc, "transformCloud");
 }
 
+// ---- merge -------------------------------------------------------------------------------------------------------
+namespace {
+// The placement blocks of `o` for k inputs (nullopt: none), or false + the [SPZ ERROR] line: every check that needs no
+// device and no header.
+bool mergeArguments(size_t k, const MergeOptions &o, std::vector<std::optional<spz_amd_transform>> *xfs) {
+  if (k == 0) return transformRejected("mergeSpz", "no inputs");
+  if (k > SPZ_AMD_MERGE_MAX_INPUTS) return transformRejected("mergeSpz", "%zu inputs: at most %u can be merged", k, SPZ_AMD_MERGE_MAX_INPUTS);
+  if (o.shDegree < -1 || o.shDegree > 3) return transformRejected("mergeSpz", "shDegree %d is outside -1 ... 3", o.shDegree);
+  if (o.fractionalBits < -1 || o.fractionalBits > 24) return transformRejected("mergeSpz", "fractionalBits %d is outside -1 ... 24", o.fractionalBits);
+  if (o.antialiased < -1 || o.antialiased > 1) return transformRejected("mergeSpz", "antialiased %d is not -1, 0 or 1", o.antialiased);
+  if (!o.transforms.empty() && o.transforms.size() != k) {
+    return transformRejected("mergeSpz", "%zu transforms for %zu inputs (give none or one per input)", o.transforms.size(), k);
+  }
+  xfs->assign(k, std::nullopt);
+  for (size_t i = 0; i < o.transforms.size(); ++i) {
+    if (!o.transforms[i]) continue;
+    spz_amd_transform xf;
+    if (!transformBlock("mergeSpz", *o.transforms[i], false, &xf)) return false;
+    (*xfs)[i] = xf;
+  }
+  return true;
+}
+
+// spz_amd_merge_resolve's refusals, each with its reason.
+bool mergeResolved(const std::vector<spz_amd_header> &h, const MergeOptions &o, spz_amd_header *oh) {
+  const int rc = spz_amd_merge_resolve(h.data(), h.size(), o.shDegree, o.fractionalBits, o.antialiased, oh, nullptr);
+  if (rc == SPZ_AMD_OK) return true;
+  uint64_t total = 0;
+  for (const spz_amd_header &x : h) total += x.num_points;
+  if (rc == SPZ_AMD_ERR_TOO_MANY_POINTS) {
+    return transformRejected("mergeSpz", "%llu points in all: the reference reads at most %u", static_cast<unsigned long long>(total),
+                             SPZ_AMD_REFERENCE_MAX_POINTS);
+  }
+  for (size_t i = 1; i < h.size() && o.antialiased < 0; ++i) {
+    if ((h[i].flags & 1) != (h[0].flags & 1)) {
+      return transformRejected("mergeSpz", "input 0 has antialiased = %d and input %zu has antialiased = %d (set antialiased)",
+                               h[0].flags & 1, i, h[i].flags & 1);
+    }
+  }
+  return transformRejected("mergeSpz", "the inputs cannot be merged (%s)", spz_amd_status_string(rc));
+}
+}  // namespace
+
+bool mergeSpz(const std::vector<std::vector<uint8_t>> &inputs, const MergeOptions &o, std::vector<uint8_t> *out, int64_t *points) {
+  g_last_status = SPZ_AMD_OK;
+  if (points) *points = 0;
+  // the arguments first: nothing touches the device before they are known to be good
+  if (out == nullptr) return transformRejected("mergeSpz", "no output vector");
+  std::vector<std::optional<spz_amd_transform>> xfs;
+  if (!mergeArguments(inputs.size(), o, &xfs)) return false;
+  for (size_t i = 0; i < inputs.size(); ++i) {
+    if (inputs[i].size() > static_cast<size_t>(INT32_MAX)) return transformRejected("mergeSpz", "input %zu is larger than 2 GiB", i);
+  }
+  const size_t k = inputs.size();
+  std::vector<DevicePackedGaussians> d(k);
+  std::vector<spz_amd_header> hdrs(k);
+  for (size_t i = 0; i < k; ++i) {
+    d[i] = loadSpzPackedDevice(inputs[i].data(), static_cast<int32_t>(inputs[i].size()));
+    if (!d[i].valid()) {
+      if (g_last_status == SPZ_AMD_OK) logLine("[SPZ ERROR] mergeSpz: input %zu is not a readable .spz", i);
+      return false;
+    }
+    hdrs[i] = headerOf(d[i]);
+  }
+  spz_amd_header oh;
+  if (!mergeResolved(hdrs, o, &oh)) return false;
+  std::vector<spz_amd_merge_input> in(k);
+  for (size_t i = 0; i < k; ++i) {
+    if (d[i].device != d[0].device) return transformRejected("mergeSpz", "the inputs were loaded on different devices");
+    in[i].d_stream = d[i].stream;
+    in[i].size = d[i].streamBytes;
+    in[i].hdr = hdrs[i];
+    in[i].xf = xfs[i] ? &*xfs[i] : nullptr;
+  }
+  void *ctx = nullptr;
+  uint64_t bytes = 0, bad = 0;
+  int rc = spz_amd_merge_open(in.data(), k, o.shDegree, o.fractionalBits, o.antialiased, d[0].device, &ctx, &oh, &bytes, &bad, nullptr);
+  if (deviceFailed(rc, "mergeSpz")) return false;
+  struct Close {
+    void *c;
+    ~Close() { spz_amd_merge_close(c); }
+  } closer{ctx};
+  if (bad > 0) {
+    return transformRejected("mergeSpz", "%llu of %u points have a position that does not fit 24 bits at %d fractional bits "
+                             "(lower fractionalBits)", static_cast<unsigned long long>(bad), oh.num_points, oh.fractional_bits);
+  }
+  d.clear();  // the inputs' device memory goes before the container stage takes its own
+  std::vector<uint8_t> stream;
+  detail::resizeUninitialized(&stream, static_cast<size_t>(bytes));
+  rc = spz_amd_merge_fetch(ctx, stream.data());
+  if (deviceFailed(rc, "mergeSpz")) return false;
+  // the device copy of the stream is this call's: the device writer reads it instead of uploading the host copy
+  if (!compressGzippedWithCopy(stream.data(), stream.size(), out, spz_amd_merge_device_data(ctx))) {
+    logLine("[SPZ ERROR] mergeSpz: compressGzipped failed");
+    return false;
+  }
+  if (points) *points = oh.num_points;
+  return true;
+}
+
+bool mergeSpz(const std::vector<std::string> &inputFilenames, const std::string &outputFilename, const MergeOptions &o,
+              int64_t *points) {
+  g_last_status = SPZ_AMD_OK;
+  if (points) *points = 0;
+  std::vector<std::optional<spz_amd_transform>> xfs;
+  if (!mergeArguments(inputFilenames.size(), o, &xfs)) return false;
+  std::vector<std::vector<uint8_t>> data(inputFilenames.size());
+  for (size_t i = 0; i < inputFilenames.size(); ++i) {
+    if (!readFile(inputFilenames[i], &data[i], /*log=*/true)) return false;
+  }
+  std::vector<uint8_t> file;
+  int64_t n = 0;
+  if (!mergeSpz(data, o, &file, &n)) return false;
+  if (!writeFile(outputFilename, file)) {
+    logLine("[SPZ ERROR] mergeSpz: unable to write %s", outputFilename.c_str());
+    return false;
+  }
+  if (points) *points = n;
+  return true;
+}
+
 GaussianCloud loadSpz(const std::vector<uint8_t> &data, const UnpackOptions &o) {
   return loadSpz(data.data(), static_cast<int32_t>(data.size()), o);
 }

@@ -14,6 +14,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <optional>
 #include <cstring>
 #include <sstream>
 #include <memory>
@@ -219,6 +220,72 @@ spz::TransformOptions transformOptions(const py::object &rotation, const py::obj
   spz_amd_transform xf;
   if (spz_amd_transform_params(o.rotation.data(), o.translation.data(), o.scale, static_cast<int>(coord), &xf) != SPZ_AMD_OK) {
     throw py::value_error("the transform has no f32 parameter block (scale or translation out of the f32 range?)");
+  }
+  return o;
+}
+
+// merge_spz's arguments as spz::MergeOptions; every problem is a ValueError, raised before any device work.  Each
+// transforms entry is None or a dict of rotation / translation / scale / coord, checked by transform_spz's code.
+spz::MergeOptions mergeOptions(size_t k, const py::object &transforms, const py::object &sh_degree,
+                               const py::object &fractional_bits, const py::object &antialiased) {
+  spz::MergeOptions o;
+  auto opt = [](const py::object &v, long lo, long hi, const char *name) -> int32_t {
+    if (v.is_none()) return -1;
+    if (!py::isinstance<py::int_>(v) || py::isinstance<py::bool_>(v)) {
+      throw py::value_error(std::string(name) + " must be None or an int in [" + std::to_string(lo) + ", " + std::to_string(hi) + "]");
+    }
+    const long d = py::cast<long>(v);
+    if (d < lo || d > hi) {
+      throw py::value_error(std::string(name) + " must be None or an int in [" + std::to_string(lo) + ", " + std::to_string(hi) +
+                            "], got " + std::to_string(d));
+    }
+    return static_cast<int32_t>(d);
+  };
+  o.shDegree = opt(sh_degree, 0, 3, "sh_degree");
+  o.fractionalBits = opt(fractional_bits, 0, 24, "fractional_bits");
+  o.antialiased = opt(antialiased, 0, 1, "antialiased");
+  if (k == 0) throw py::value_error("merge_spz: no inputs");
+  if (k > SPZ_AMD_MERGE_MAX_INPUTS) {
+    throw py::value_error("merge_spz: " + std::to_string(k) + " inputs, at most " + std::to_string(SPZ_AMD_MERGE_MAX_INPUTS));
+  }
+  if (transforms.is_none()) return o;
+  if (!py::isinstance<py::sequence>(transforms) || py::isinstance<py::str>(transforms)) {
+    throw py::value_error("transforms must be None or a list with one entry per input");
+  }
+  const py::sequence seq = transforms.cast<py::sequence>();
+  if (static_cast<size_t>(py::len(seq)) != k) {
+    throw py::value_error("transforms has " + std::to_string(py::len(seq)) + " entries for " + std::to_string(k) + " inputs");
+  }
+  for (size_t i = 0; i < k; ++i) {
+    const py::object e = seq[i];
+    if (e.is_none()) {
+      o.transforms.emplace_back(std::nullopt);
+      continue;
+    }
+    if (!py::isinstance<py::dict>(e)) throw py::value_error("transforms[" + std::to_string(i) + "] must be None or a dict");
+    const py::dict d = e.cast<py::dict>();
+    for (const auto &kv : d) {
+      const std::string key = py::str(kv.first);
+      if (key != "rotation" && key != "translation" && key != "scale" && key != "coord") {
+        throw py::value_error("transforms[" + std::to_string(i) + "]: unknown key '" + key + "'");
+      }
+    }
+    spz::CoordinateSystem coord = spz::CoordinateSystem::UNSPECIFIED;
+    if (d.contains("coord")) {
+      const py::object c = d["coord"];
+      if (py::isinstance<spz::CoordinateSystem>(c)) {
+        coord = c.cast<spz::CoordinateSystem>();
+      } else if (py::isinstance<py::int_>(c) && !py::isinstance<py::bool_>(c) && py::cast<long>(c) >= 0 && py::cast<long>(c) <= 8) {
+        coord = static_cast<spz::CoordinateSystem>(py::cast<long>(c));
+      } else {
+        throw py::value_error("transforms[" + std::to_string(i) + "]: coord must be a CoordinateSystem");
+      }
+    }
+    const py::object none = py::none();
+    o.transforms.emplace_back(transformOptions(d.contains("rotation") ? py::object(d["rotation"]) : none,
+                                               d.contains("translation") ? py::object(d["translation"]) : none,
+                                               d.contains("scale") ? py::object(d["scale"]) : py::object(py::float_(1.0)),
+                                               coord, py::int_(12)));
   }
   return o;
 }
@@ -484,6 +551,31 @@ PYBIND11_MODULE(spz, m) {
         py::arg("cloud"), py::kw_only(), py::arg("rotation") = py::none(), py::arg("translation") = py::none(),
         py::arg("scale") = 1.0, py::arg("coord") = spz::CoordinateSystem::UNSPECIFIED,
         "transform_spz's transform in place on a GaussianCloud (spz::transformCloud), in f32 without quantising.");
+  m.def("merge_spz",
+        [](const std::vector<std::string> &inputs, const std::string &output, const py::object &transforms,
+           const py::object &sh_degree, const py::object &fractional_bits, const py::object &antialiased) {
+          const spz::MergeOptions o = mergeOptions(inputs.size(), transforms, sh_degree, fractional_bits, antialiased);
+          bool ok;
+          int64_t points = 0;
+          {
+            py::gil_scoped_release release;
+            ok = spz::mergeSpz(inputs, output, o, &points);
+          }
+          if (!ok) {
+            raiseIfDeviceUnusable();
+            if (spz::lastDeviceStatus() == SPZ_AMD_ERR_INVALID_ARG) {
+              throw py::value_error("merge_spz: refused for these files (see the [SPZ ERROR] line)");
+            }
+            throw std::runtime_error("merge_spz: -> " + output + " failed (see the [SPZ ERROR] line)");
+          }
+          return points;
+        },
+        py::arg("inputs"), py::arg("output_filename"), py::kw_only(), py::arg("transforms") = py::none(),
+        py::arg("sh_degree") = py::none(), py::arg("fractional_bits") = py::none(), py::arg("antialiased") = py::none(),
+        "One v3 .spz out of several (spz::mergeSpz): input 0's points, then input 1's, ...; bytes are copied wherever the "
+        "encoding and the placement allow.  transforms: None or one entry per input, None or a dict of rotation / "
+        "translation / scale / coord (as transform_spz).  sh_degree (None: the largest), fractional_bits (None: the "
+        "inputs' common value, else 12), antialiased (None: the inputs must agree).  Returns the number of points.");
   m.def("save_spz",
         [](const spz::GaussianCloud &g, const spz::PackOptions &o, const std::string &filename) {
           bool ok;

@@ -11,6 +11,7 @@
 //                                records through LDS so that the global loads and stores stay lane-contiguous, and each
 //                                thread rotates one record (sh_from_byte, quantize_sh_f).  Positions whose new value
 //                                does not fit the 24-bit field are counted: a ballot per wave, one atomic per wave.
+// The per-point arithmetic and the packed point cores live in spz_xf.hpp, shared with spz_merge.hip.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -22,6 +23,7 @@
 #include "spz_common.hpp"
 #include "spz_kernel_params.hpp"
 #include "spz_quant.hpp"
+#include "spz_xf.hpp"
 
 #pragma clang fp contract(off)
 
@@ -33,8 +35,6 @@ constexpr uint32_t kCopyUnroll = 4;
 constexpr uint32_t kCopyTileBytes = kXfBlock * kCopyUnroll * 4u;
 constexpr uint32_t kMaxShBytes = 45;               // 3 * 15 at degree 3
 constexpr uint32_t kMagic = 0x5053474eu;           // load-spz.cc:132
-
-typedef uint32_t u32_a1 __attribute__((aligned(1)));
 
 enum XfKind : uint32_t { XF_POS = 0, XF_COPY, XF_SCALE, XF_ROT, XF_SH };
 
@@ -68,51 +68,6 @@ struct CloudXfParams {
   spz_amd_transform xf;
 };
 
-// ---- the per-point arithmetic (every product and sum rounded on its own) ----------------------------------------
-__device__ __forceinline__ void xf_position(const spz_amd_transform &x, float v[3]) {
-  float o[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const float s = fadd_sep(fadd_sep(fmul_sep(x.m[3 * i], v[0]), fmul_sep(x.m[3 * i + 1], v[1])), fmul_sep(x.m[3 * i + 2], v[2]));
-    o[i] = fadd_sep(s, x.t[i]);
-  }
-  v[0] = o[0];
-  v[1] = o[1];
-  v[2] = o[2];
-}
-
-// q_R * q (Hamilton), a = q_R, b = q, (x, y, z, w); each sum left to right.
-__device__ __forceinline__ F32x4 xf_rotation(const spz_amd_transform &x, F32x4 b) {
-  const float ax = x.q[0], ay = x.q[1], az = x.q[2], aw = x.q[3];
-  F32x4 o;
-  o.x = fadd_sep(fadd_sep(fadd_sep(fmul_sep(aw, b.x), fmul_sep(ax, b.w)), fmul_sep(ay, b.z)), -fmul_sep(az, b.y));
-  o.y = fadd_sep(fadd_sep(fadd_sep(fmul_sep(aw, b.y), -fmul_sep(ax, b.z)), fmul_sep(ay, b.w)), fmul_sep(az, b.x));
-  o.z = fadd_sep(fadd_sep(fadd_sep(fmul_sep(aw, b.z), fmul_sep(ax, b.y)), -fmul_sep(ay, b.x)), fmul_sep(az, b.w));
-  o.w = fadd_sep(fadd_sep(fadd_sep(fmul_sep(aw, b.w), -fmul_sep(ax, b.x)), -fmul_sep(ay, b.y)), -fmul_sep(az, b.z));
-  return o;
-}
-
-// One band of one channel: out[m] = sum_k D[k][m] * in[k], k ascending from the k = 0 product.
-template <int N>
-__device__ __forceinline__ void xf_band(const float *D, const float *in, float *out) {
-#pragma unroll
-  for (int m = 0; m < N; ++m) {
-    float acc = fmul_sep(D[m], in[0]);
-#pragma unroll
-    for (int k = 1; k < N; ++k) acc = fadd_sep(acc, fmul_sep(D[k * N + m], in[k]));
-    out[m] = acc;
-  }
-}
-
-// The bands 1..3 present in `dim` coefficients (3, 8 or 15), coefficient-major [coeff][rgb] records.
-__device__ __forceinline__ void xf_sh_channel(const spz_amd_transform &x, uint32_t dim, const float *in, float *out) {
-  xf_band<3>(x.d1, in, out);
-  if (dim >= 8) xf_band<5>(x.d2, in + 3, out + 3);
-  if (dim >= 15) xf_band<7>(x.d3, in + 8, out + 8);
-}
-
-__device__ __forceinline__ bool fits24(float r) { return r >= -8388608.0f && r <= 8388607.0f; }  // NaN: false
-
 // ---- packed tiles ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void copy_tile(const XfSec &q, uint32_t tl, bool scale, float ln_s) {
   const unsigned long long base = (unsigned long long)tl * kCopyTileBytes;
@@ -127,15 +82,7 @@ __device__ __forceinline__ void copy_tile(const XfSec &q, uint32_t tl, bool scal
     } else {
       for (uint32_t j = 0; j < n; ++j) w |= (uint32_t)q.src[b0 + j] << (8u * j);
     }
-    if (scale) {
-      uint32_t o = 0;
-#pragma unroll
-      for (uint32_t j = 0; j < 4; ++j) {
-        const float v = fadd_sep(scale_from_byte((w >> (8u * j)) & 0xffu), ln_s);
-        o |= (uint32_t)scale_to_byte_f(v) << (8u * j);
-      }
-      w = o;
-    }
+    if (scale) w = xf_scale_bytes(w, ln_s);
     if (n == 4u) {
       *reinterpret_cast<u32_a1 *>(q.dst + b0) = w;
     } else {
@@ -146,23 +93,8 @@ __device__ __forceinline__ void copy_tile(const XfSec &q, uint32_t tl, bool scal
 
 __device__ __forceinline__ void position_tile(const PackedXfParams &p, const XfSec &q, uint32_t tl) {
   const unsigned long long i = (unsigned long long)tl * kXfBlock + threadIdx.x;
-  const bool live = i < p.num_points;
-  bool bad = false;
-  if (live) {
-    float v[3];
-#pragma unroll
-    for (uint32_t a = 0; a < 3; ++a) v[a] = decode_position_axis(q.src, i, a, p.version == 1u, p.in_pos_scale, 0u);
-    if (p.xf.apply_positions) xf_position(p.xf, v);
-    uint8_t *d = q.dst + i * 9ull;
-#pragma unroll
-    for (uint32_t a = 0; a < 3; ++a) {
-      bad = bad || !fits24(round_half_away(v[a] * p.out_pos_scale));
-      const uint32_t f = (uint32_t)position_fixed(v[a], p.out_pos_scale) & 0xffffffu;
-      d[3 * a] = (uint8_t)f;
-      d[3 * a + 1] = (uint8_t)(f >> 8);
-      d[3 * a + 2] = (uint8_t)(f >> 16);
-    }
-  }
+  const bool bad = i < p.num_points &&
+                   xf_position_point(q.src, i, p.version == 1u, p.in_pos_scale, &p.xf, p.out_pos_scale, q.dst + i * 9ull);
   const unsigned long long ballot = __ballot(bad);
   if ((threadIdx.x & 63u) == 0u && ballot != 0ull && p.out_of_range != nullptr) {
     atomicAdd(p.out_of_range, (unsigned long long)__popcll(ballot));
@@ -172,15 +104,7 @@ __device__ __forceinline__ void position_tile(const PackedXfParams &p, const XfS
 __device__ __forceinline__ void rotation_tile(const PackedXfParams &p, const XfSec &q, uint32_t tl) {
   const unsigned long long i = (unsigned long long)tl * kXfBlock + threadIdx.x;
   if (i >= p.num_points) return;
-  F32x4 r;
-  if (p.version >= 3u) {
-    r = unpack_quat_smallest_three(*reinterpret_cast<const u32_a1 *>(q.src + i * 4ull), 0u);
-  } else {
-    const uint8_t *b = q.src + i * 3ull;
-    r = unpack_quat_first_three((uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16), 0u);
-  }
-  if (p.xf.apply_rotation) r = xf_rotation(p.xf, r);
-  *reinterpret_cast<u32_a1 *>(q.dst + i * 4ull) = pack_quat_smallest_three(r, 0u);
+  *reinterpret_cast<u32_a1 *>(q.dst + i * 4ull) = xf_rotation_point(q.src, i, p.version, &p.xf);
 }
 
 // 256 records through LDS: coalesced dword loads of the tile's bytes, one record per thread, coalesced dword stores.
@@ -200,25 +124,7 @@ __device__ __forceinline__ void sh_tile(const PackedXfParams &p, const XfSec &q,
     }
   }
   __syncthreads();
-  if (threadIdx.x < pts) {
-    uint8_t *r = lds + threadIdx.x * rec;
-#pragma unroll
-    for (uint32_t c = 0; c < 3; ++c) {
-      float in[15], out[15];
-#pragma unroll
-      for (uint32_t k = 0; k < 15; ++k) in[k] = k < dim ? sh_from_byte(r[3 * k + c]) : 0.0f;
-      if (p.xf.apply_rotation) {
-        xf_sh_channel(p.xf, dim, in, out);
-      } else {
-#pragma unroll
-        for (uint32_t k = 0; k < 15; ++k) out[k] = in[k];
-      }
-#pragma unroll
-      for (uint32_t k = 0; k < 15; ++k) {
-        if (k < dim) r[3 * k + c] = (uint8_t)quantize_sh_f(out[k], k < 3u);  // elements 0..8: the degree-1 bucket
-      }
-    }
-  }
+  if (threadIdx.x < pts) xf_sh_record(lds + threadIdx.x * rec, dim, dim, &p.xf);
   __syncthreads();
   for (uint32_t b = threadIdx.x * 4u; b < bytes; b += kXfBlock * 4u) {
     if (b + 4u <= bytes) {

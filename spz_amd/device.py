@@ -329,6 +329,72 @@ def transform_packed(stream_t, header, *, rotation=None, translation=None, scale
     return out[:lay.total_bytes], bad
 
 
+def merge_packed(streams, headers, *, transforms=None, sh_degree=None, fractional_bits=None, antialiased=None, out=None,
+                 stream=None):
+    """K packed device streams (any version) -> one v3 stream, input 0's points first, in one launch
+    (spz_amd_merge_device): bytes are copied wherever the encoding and the placement allow.  transforms: None or one
+    entry per input, None or a dict of rotation / translation / scale / coord (transform's arguments).  sh_degree (None:
+    the largest input degree), fractional_bits (None: the v2/v3 inputs' common value, else 12), antialiased (None: the
+    inputs must agree).  Returns (uint8 CUDA tensor, output Header, out-of-range count as a 1-element int64 CUDA tensor:
+    the points whose position does not fit 24 bits at the output's fractional_bits; their bytes wrap).  A bad argument
+    or a conflict raises ValueError before any device work."""
+    L = abi.load_library()
+    streams, headers = list(streams), list(headers)
+    k = len(streams)
+    if k == 0 or k > abi.MERGE_MAX_INPUTS:
+        raise ValueError(f"merge_packed takes 1 ... {abi.MERGE_MAX_INPUTS} streams, got {k}")
+    if len(headers) != k:
+        raise ValueError(f"{len(headers)} headers for {k} streams")
+    for name, v, hi in (("sh_degree", sh_degree, 3), ("fractional_bits", fractional_bits, 24), ("antialiased", antialiased, 1)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= hi):
+            raise ValueError(f"{name} must be None or an int in [0, {hi}], got {v!r}")
+    if transforms is not None:
+        transforms = list(transforms)
+        if len(transforms) != k:
+            raise ValueError(f"{len(transforms)} transforms for {k} streams")
+    xfs = []
+    for i in range(k):
+        t = None if transforms is None else transforms[i]
+        if t is None:
+            xfs.append(None)
+            continue
+        if not isinstance(t, dict) or not set(t) <= {"rotation", "translation", "scale", "coord"}:
+            raise ValueError(f"transforms[{i}] must be None or a dict of rotation / translation / scale / coord")
+        xfs.append(abi.transform_params(t.get("rotation"), t.get("translation"), t.get("scale", 1.0),
+                                        int(t.get("coord", abi.UNSPECIFIED))))
+    dev = None
+    for i, st in enumerate(streams):
+        if st.dtype != torch.uint8 or not st.is_cuda or not st.is_contiguous():
+            raise ValueError(f"streams[{i}] must be a contiguous uint8 CUDA tensor")
+        if dev is not None and st.device != dev:
+            raise ValueError(f"streams[{i}] is on {st.device}, expected {dev}")
+        dev = st.device
+    rc, hdr, nbytes = abi.merge_resolve(headers, sh_degree, fractional_bits, antialiased)
+    if rc != abi.OK:
+        aa = [h.flags & 1 for h in headers]
+        if antialiased is None and len(set(aa)) > 1:
+            j = next(i for i, a in enumerate(aa) if a != aa[0])
+            raise ValueError(f"input 0 has antialiased = {aa[0]} and input {j} has antialiased = {aa[j]} (set antialiased)")
+        raise ValueError(f"the streams cannot be merged: {abi.status_string(rc)}")
+    if out is None:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = torch.empty(int(L.spz_amd_merge_workspace_bytes(k)), dtype=torch.uint8, device=dev)
+    bad = torch.empty(1, dtype=torch.int64, device=dev)
+    ins = (abi.MergeInput * k)()
+    for i in range(k):
+        ins[i].d_stream = streams[i].data_ptr()
+        ins[i].size = streams[i].numel()
+        ins[i].hdr = headers[i]
+        ins[i].xf = C.pointer(xfs[i]) if xfs[i] is not None else None
+    with torch.cuda.device(dev):
+        rc = L.spz_amd_merge_device(ins, k, C.byref(hdr), out.data_ptr(), out.numel(), ws.data_ptr(), bad.data_ptr(),
+                                    _stream_handle(stream))
+    abi.check(rc, "spz_amd_merge_device")
+    if stream is not None:  # the workspace was allocated on the current stream; the launch reads it on `stream`
+        ws.record_stream(stream)
+    return out[:nbytes], hdr, bad
+
+
 def convert_coordinates(cloud, num_points, sh_degree, from_coord, to_coord, stream=None):
     """In-place GaussianCloud::convertCoordinates on device tensors (positions, rotations, sh)."""
     L = abi.load_library()
@@ -354,6 +420,6 @@ def to_numpy(cloud_t):
 
 
 __all__ = ["encode", "decode", "encode_shard", "decode_shard", "decode_gather", "peek_header", "convert_coordinates",
-           "select", "subset", "transform", "transform_packed",
+           "select", "subset", "transform", "transform_packed", "merge_packed",
            "alloc_cloud",
            "make_header", "to_device", "to_numpy", "SH_DIM"]
