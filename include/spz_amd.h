@@ -349,6 +349,45 @@ int spz_amd_merge_fetch(void *ctx, uint8_t *h_out);
 const uint8_t *spz_amd_merge_device_data(void *ctx);
 void spz_amd_merge_close(void *ctx);
 
+/* ---- sort: the points of a packed stream in a new order, without requantising (spz_sort.hip; DESIGN §8 "sort").  The
+ *      reference has no counterpart.  The output is the filter's subset(input, order) at the input's degree: point k is
+ *      input point order[k] with all its bytes; the header keeps version, fractionalBits and antialiased (reserved 0).
+ *
+ *      Order: key ascending (descending != 0: descending); ties by input index ascending (stable), so the output is a
+ *      function of the input and the options, and sorting a sorted stream gives the same bytes.
+ *      Morton key (morton_order_device): per axis a (x = 0, y = 1, z = 2) u_a = the stored 24-bit little-endian field
+ *      XOR 0x800000 (orders like the sign-extended value); key bit 3*b + a = bit b of u_a, b = 0..23 (72 bits, the
+ *      stored RUB frame, independent of fractionalBits); descending sorts the complemented key.  Version 1 (float16
+ *      positions): SPZ_AMD_ERR_UNSUPPORTED (transform_packed with the identity writes a v3 copy).
+ *      f32 keys (argsort_f32_device): the order of numpy's argsort(k, kind="stable") (descending: of argsort(-k)): -0 ==
+ *      +0, +-inf sort normally, every NaN last in both directions, in input order.  n < 2^31.
+ *
+ *      sort_workspace_bytes (host only, no GPU): device memory for either device form at n points (any alignment).
+ *      morton_order_device / argsort_f32_device write the n indices into d_order (device memory).  A stable LSD radix
+ *      sort with 8-bit digits (9 passes for Morton keys, 4 for f32), each pass a tile histogram, a scan of the tile
+ *      counts and a scatter.  Enqueued on hip_stream, no synchronisation.  n == 0 launches nothing.
+ *      chunk_bounds_device: for runs of `chunk` (>= 1) consecutive points (the last may be partial), d_bounds[c][0][a] /
+ *      d_bounds[c][1][a] = min / max over the run of the sign-extended stored integer of axis a times
+ *      2^-fractionalBits, in f32 (exact), stored frame; d_bounds holds ceil(n / chunk) * 6 floats.  v1: UNSUPPORTED.
+ *      Every argument error is returned before anything is launched.
+ *      The host form (open / fetch / device_data / close, shaped like the filter's) takes a stream already in device
+ *      memory, orders it by h_keys (host memory, hdr->num_points floats; NULL: the Morton key), then runs
+ *      spz_amd_subset_device, on `device` on a stream of its own, and blocks.  Streams above
+ *      SPZ_AMD_REFERENCE_MAX_POINTS: SPZ_AMD_ERR_TOO_MANY_POINTS.  h_order (may be NULL): the order, num_points
+ *      entries.  h_ms (may be NULL): [0] wall-clock milliseconds of the key upload and the order, [1] of the subset. */
+uint64_t spz_amd_sort_workspace_bytes(uint64_t num_points);
+int spz_amd_morton_order_device(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, int descending,
+                                uint32_t *d_order, void *d_workspace, void *hip_stream);
+int spz_amd_argsort_f32_device(const float *d_keys, uint64_t n, int descending, uint32_t *d_order, void *d_workspace,
+                               void *hip_stream);
+int spz_amd_chunk_bounds_device(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, uint32_t chunk,
+                                float *d_bounds, void *hip_stream);
+int spz_amd_sort_open(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, const float *h_keys,
+                      int descending, int device, void **ctx, uint64_t *h_out_bytes, uint32_t *h_order, float *h_ms);
+int spz_amd_sort_fetch(void *ctx, uint8_t *h_out);
+const uint8_t *spz_amd_sort_device_data(void *ctx);
+void spz_amd_sort_close(void *ctx);
+
 /* ---- device buffers for a resident cloud, placed for speed (spz_place.hip).  Whether an sh3 decode runs
  *      at 0.46 ms or at 0.55 ms is decided by whether the sh float array shares a physical region of HBM with the other
  *      arrays of the launch; that cannot be asked for, but it shows in one launch.  alloc: the five small arrays (and a

@@ -331,6 +331,25 @@ bool mergeSpz(const std::vector<std::vector<uint8_t>> &inputs, const MergeOption
               int64_t *points = nullptr);
 bool mergeSpz(const std::vector<std::string> &inputFilenames, const std::string &outputFilename,
               const MergeOptions &options, int64_t *points = nullptr);
+// Sort (DESIGN §8 "sort"): the same points in a new order, without requantising.  The member is inflated
+// (loadSpzPackedDevice), the order is computed on the device (spz_amd_sort_open: spz_amd_morton_order_device or
+// spz_amd_argsort_f32_device, then spz_amd_subset_device) and the stream is compressed with zlib's level-6 bytes.
+// Output point k is input point order[k] with all its bytes, at the input's degree; the header keeps the input's
+// version, fractionalBits and antialiased bit.  Order: `keys` (one float per point) ascending, or descending, as numpy's
+// argsort(k, kind="stable") (argsort(-k)): -0 == +0, every NaN last in both directions; no keys: the 72-bit Morton key of
+// the stored 24-bit positions (include/spz_amd.h), not available for version 1 files (SPZ_AMD_ERR_UNSUPPORTED;
+// transformSpz with the identity writes a v3 copy).  Ties keep input order, so sorting a sorted file gives the same bytes.
+// *order (may be NULL): order[k].  false + one "[SPZ ERROR] sortSpz: …" line on a bad argument (a key count that is not
+// numPoints: lastDeviceStatus() = SPZ_AMD_ERR_INVALID_ARG), an input that does not load, or a device failure.
+// SPZ_AMD_SORT_TIMING=1 prints the stages' times to stderr.
+struct SortOptions {
+  std::optional<std::vector<float>> keys;
+  bool descending = false;
+};
+bool sortSpz(const uint8_t *data, int32_t size, const SortOptions &options, std::vector<uint8_t> *out,
+             std::vector<uint32_t> *order = nullptr);
+bool sortSpz(const std::string &inputFilename, const std::string &outputFilename, const SortOptions &options,
+             std::vector<uint32_t> *order = nullptr);
 // Status (spz_amd.h codes) of the last device call made by this thread; 0 = ok.
 int lastDeviceStatus();
 void setLastDeviceStatus(int status);

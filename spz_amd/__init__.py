@@ -7,6 +7,7 @@ Layout:
   csrc/spz_filter.hip   point selection + subset of a packed stream (filterSpz: a smaller .spz without requantising)
   csrc/spz_transform.hip  rotation / translation / uniform scale of a cloud or a packed stream (transformSpz)
   csrc/spz_merge.hip    K packed streams -> one v3 stream, bytes copied where possible (mergeSpz)
+  csrc/spz_sort.hip     stable device radix argsort, Morton order of the stored positions, chunk bounds (sortSpz)
   csrc/spz_abi.hip      the C ABI (include/spz_amd.h) over them: device-pointer entry points
   csrc/spz_hostpath.hip host-pointer entry points: device workspace + chunked H2D/kernel/D2H pipeline
   csrc/spz_exchange.hip multi-GPU exchange: native RCCL gatherv/scatterv, IPC-mapped root stream

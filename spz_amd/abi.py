@@ -66,6 +66,9 @@ EXPORTS = (
     "spz_amd_transform_cloud_host",
     "spz_amd_merge_resolve", "spz_amd_merge_workspace_bytes", "spz_amd_merge_device", "spz_amd_merge_open",
     "spz_amd_merge_fetch", "spz_amd_merge_device_data", "spz_amd_merge_close",
+    "spz_amd_sort_workspace_bytes", "spz_amd_morton_order_device", "spz_amd_argsort_f32_device",
+    "spz_amd_chunk_bounds_device", "spz_amd_sort_open", "spz_amd_sort_fetch", "spz_amd_sort_device_data",
+    "spz_amd_sort_close",
 )
 
 RCCL_UNIQUE_ID_BYTES = 128
@@ -335,6 +338,22 @@ def bind(L):
     L.spz_amd_merge_device_data.argtypes = [vp]
     L.spz_amd_merge_close.restype = None
     L.spz_amd_merge_close.argtypes = [vp]
+    L.spz_amd_sort_workspace_bytes.restype = u64
+    L.spz_amd_sort_workspace_bytes.argtypes = [u64]
+    L.spz_amd_morton_order_device.restype = i32
+    L.spz_amd_morton_order_device.argtypes = [vp, sz, C.POINTER(Header), i32, vp, vp, vp]
+    L.spz_amd_argsort_f32_device.restype = i32
+    L.spz_amd_argsort_f32_device.argtypes = [vp, u64, i32, vp, vp, vp]
+    L.spz_amd_chunk_bounds_device.restype = i32
+    L.spz_amd_chunk_bounds_device.argtypes = [vp, sz, C.POINTER(Header), u32, vp, vp]
+    L.spz_amd_sort_open.restype = i32
+    L.spz_amd_sort_open.argtypes = [vp, sz, C.POINTER(Header), vp, i32, i32, C.POINTER(vp), C.POINTER(u64), vp, vp]
+    L.spz_amd_sort_fetch.restype = i32
+    L.spz_amd_sort_fetch.argtypes = [vp, vp]
+    L.spz_amd_sort_device_data.restype = vp
+    L.spz_amd_sort_device_data.argtypes = [vp]
+    L.spz_amd_sort_close.restype = None
+    L.spz_amd_sort_close.argtypes = [vp]
     L.spz_amd_zlib_encode_blocks.restype = i32
     L.spz_amd_zlib_encode_blocks.argtypes = [vp, vp, u32, u32, vp, vp, vp, u64, u64, vp, vp]
     return L

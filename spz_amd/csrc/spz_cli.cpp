@@ -1,16 +1,18 @@
 // spz_cli.cpp — the three command-line tools of the reference (cli_tools/src/*.cpp) over the
-// MI355X drop-in layer: ply_to_spz, spz_to_ply, spz_info; and spz_filter (spz::filterSpz) and
-// spz_transform (spz::transformSpz) and spz_merge (spz::mergeSpz), which have no counterpart in the reference.  One
-// binary, dispatched on argv[0] (the Makefile installs it under the six names) or on a first argument naming the tool.
+// MI355X drop-in layer: ply_to_spz, spz_to_ply, spz_info; and spz_filter (spz::filterSpz),
+// spz_transform (spz::transformSpz), spz_merge (spz::mergeSpz) and spz_sort (spz::sortSpz), which have no counterpart in
+// the reference.  One binary, dispatched on argv[0] (the Makefile installs it under the seven names) or on a first argument naming the tool.
 // Same behaviour as the reference mains: default (UNSPECIFIED) pack/unpack options, exit code 0
 // once the arguments are there (the reference ignores the save/load results), usage -> 1.
-// spz_filter, spz_transform and spz_merge exit 1 when the filter / transform / merge fails as well.
+// spz_filter, spz_transform, spz_merge and spz_sort exit 1 when the filter / transform / merge / sort fails as well.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <fstream>
 #include <iostream>
 #include <string>
+#include <vector>
 
 #include "spz_amd_host.hpp"
 
@@ -206,6 +208,49 @@ int spzMerge(int argc, char **argv) {
   return spz::mergeSpz(inputs, output, o) ? 0 : 1;
 }
 
+const char *kSortUsage = "Usage: spz_sort <input.spz> <output.spz> [--keys <keys.f32>] [--descending]";
+
+int spzSort(int argc, char **argv) {
+  auto usage = [] {
+    std::cerr << kSortUsage << std::endl;
+    return 1;
+  };
+  if (argc < 3 || argv[1][0] == '-' || argv[2][0] == '-') return usage();
+  spz::SortOptions o;
+  const char *keys = nullptr;
+  for (int i = 3; i < argc; ++i) {
+    const std::string a = argv[i];
+    if (a == "--keys" && i + 1 < argc && keys == nullptr) {
+      keys = argv[++i];
+    } else if (a == "--descending" && !o.descending) {
+      o.descending = true;
+    } else {
+      return usage();
+    }
+  }
+  if (keys != nullptr) {
+    // raw little-endian float32, one per point
+    std::ifstream f(keys, std::ios::binary | std::ios::ate);
+    if (!f) {
+      std::cerr << "[SPZ ERROR] spz_sort: unable to read " << keys << std::endl;
+      return 1;
+    }
+    const std::streamoff bytes = f.tellg();
+    if (bytes < 0 || bytes % 4 != 0) {
+      std::cerr << "[SPZ ERROR] spz_sort: " << keys << " is not a whole number of float32 values" << std::endl;
+      return 1;
+    }
+    std::vector<float> k(static_cast<size_t>(bytes / 4));
+    f.seekg(0);
+    if (!k.empty() && !f.read(reinterpret_cast<char *>(k.data()), bytes)) {
+      std::cerr << "[SPZ ERROR] spz_sort: unable to read " << keys << std::endl;
+      return 1;
+    }
+    o.keys = std::move(k);
+  }
+  return spz::sortSpz(std::string(argv[1]), std::string(argv[2]), o) ? 0 : 1;
+}
+
 int dispatch(const std::string &tool, int argc, char **argv) {
   if (tool == "ply_to_spz") return plyToSpz(argc, argv);
   if (tool == "spz_to_ply") return spzToPly(argc, argv);
@@ -213,6 +258,7 @@ int dispatch(const std::string &tool, int argc, char **argv) {
   if (tool == "spz_filter") return spzFilter(argc, argv);
   if (tool == "spz_transform") return spzTransform(argc, argv);
   if (tool == "spz_merge") return spzMerge(argc, argv);
+  if (tool == "spz_sort") return spzSort(argc, argv);
   return -1;
 }
 
@@ -229,7 +275,7 @@ int main(int argc, char **argv) {
       rc = dispatch(argv[1], argc - 1, argv + 1);
       if (rc >= 0) return rc;
     }
-    std::cerr << "Usage: spz_tool {ply_to_spz|spz_to_ply|spz_info|spz_filter|spz_transform|spz_merge} <args...>" << std::endl;
+    std::cerr << "Usage: spz_tool {ply_to_spz|spz_to_ply|spz_info|spz_filter|spz_transform|spz_merge|spz_sort} <args...>" << std::endl;
     return 1;
   } catch (const std::exception &e) {
     std::cerr << "Error: " << e.what() << std::endl;

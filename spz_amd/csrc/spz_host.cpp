@@ -2092,6 +2092,107 @@ bool mergeSpz(const std::vector<std::string> &inputFilenames, const std::string 
   return true;
 }
 
+// ---- sort --------------------------------------------------------------------------------------------------------
+namespace {
+bool sortRejected(int status, const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  char msg[256];
+  std::vsnprintf(msg, sizeof(msg), fmt, ap);
+  va_end(ap);
+  logLine("[SPZ ERROR] sortSpz: %s", msg);
+  g_last_status = status;
+  return false;
+}
+
+struct SortLaps {
+  bool on = std::getenv("SPZ_AMD_SORT_TIMING") != nullptr;
+  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+  void lap(const char *what) {
+    const auto now = std::chrono::steady_clock::now();
+    if (on) std::fprintf(stderr, "[sortSpz] %-8s %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
+    t = now;
+  }
+};
+}  // namespace
+
+bool sortSpz(const uint8_t *data, int32_t size, const SortOptions &o, std::vector<uint8_t> *out,
+             std::vector<uint32_t> *order) {
+  g_last_status = SPZ_AMD_OK;
+  if (order) order->clear();
+  if (out == nullptr) return sortRejected(SPZ_AMD_ERR_INVALID_ARG, "no output vector");
+  if (o.keys && o.keys->size() > SPZ_AMD_REFERENCE_MAX_POINTS) {
+    return sortRejected(SPZ_AMD_ERR_INVALID_ARG, "%zu keys: the reference reads at most %u points", o.keys->size(),
+                        SPZ_AMD_REFERENCE_MAX_POINTS);
+  }
+  SortLaps laps;
+  DevicePackedGaussians d = loadSpzPackedDevice(data, size);
+  if (!d.valid()) {
+    if (g_last_status == SPZ_AMD_OK) logLine("[SPZ ERROR] sortSpz: the input is not a readable .spz");
+    return false;
+  }
+  laps.lap("inflate");
+  const uint64_t n = static_cast<uint64_t>(d.numPoints);
+  if (o.keys && o.keys->size() != n) {
+    return sortRejected(SPZ_AMD_ERR_INVALID_ARG, "%zu keys for %llu points", o.keys->size(), (unsigned long long)n);
+  }
+  if (!o.keys && d.version == 1) {
+    return sortRejected(SPZ_AMD_ERR_UNSUPPORTED,
+                        "a version 1 file has float16 positions and no Morton key; transformSpz with the identity "
+                        "writes a v3 copy");
+  }
+  const spz_amd_header hdr = headerOf(d);
+  std::vector<uint32_t> ord;
+  if (order) detail::resizeUninitialized(&ord, static_cast<size_t>(n));
+  void *ctx = nullptr;
+  uint64_t bytes = 0;
+  float ms[2] = {0.0f, 0.0f};
+  int rc = spz_amd_sort_open(d.stream, d.streamBytes, &hdr, o.keys ? o.keys->data() : nullptr, o.descending ? 1 : 0,
+                             d.device, &ctx, &bytes, order ? ord.data() : nullptr, ms);
+  if (deviceFailed(rc, "sortSpz")) return false;
+  struct Close {
+    void *c;
+    ~Close() { spz_amd_sort_close(c); }
+  } closer{ctx};
+  if (laps.on) std::fprintf(stderr, "[sortSpz] order    %.3f ms\n[sortSpz] subset   %.3f ms\n", ms[0], ms[1]);
+  laps.lap("sort");
+  d.release();  // the input's device memory goes before the container stage takes its own
+  std::vector<uint8_t> stream;
+  detail::resizeUninitialized(&stream, static_cast<size_t>(bytes));
+  rc = spz_amd_sort_fetch(ctx, stream.data());
+  if (deviceFailed(rc, "sortSpz")) return false;
+  laps.lap("download");
+  if (!compressGzippedWithCopy(stream.data(), stream.size(), out, spz_amd_sort_device_data(ctx))) {
+    logLine("[SPZ ERROR] sortSpz: compressGzipped failed");
+    return false;
+  }
+  laps.lap("gzip");
+  if (order) order->swap(ord);
+  return true;
+}
+
+bool sortSpz(const std::string &inputFilename, const std::string &outputFilename, const SortOptions &o,
+             std::vector<uint32_t> *order) {
+  g_last_status = SPZ_AMD_OK;
+  if (order) order->clear();
+  std::vector<uint8_t> data;
+  if (!readFile(inputFilename, &data, /*log=*/true)) return false;
+  if (data.size() > static_cast<size_t>(INT32_MAX)) {
+    return sortRejected(SPZ_AMD_ERR_INVALID_ARG, "%s is larger than 2 GiB", inputFilename.c_str());
+  }
+  std::vector<uint8_t> file;
+  std::vector<uint32_t> ord;
+  if (!sortSpz(data.data(), static_cast<int32_t>(data.size()), o, &file, order ? &ord : nullptr)) return false;
+  SortLaps laps;
+  if (!writeFile(outputFilename, file)) {
+    logLine("[SPZ ERROR] sortSpz: unable to write %s", outputFilename.c_str());
+    return false;
+  }
+  laps.lap("write");
+  if (order) order->swap(ord);
+  return true;
+}
+
 GaussianCloud loadSpz(const std::vector<uint8_t> &data, const UnpackOptions &o) {
   return loadSpz(data.data(), static_cast<int32_t>(data.size()), o);
 }

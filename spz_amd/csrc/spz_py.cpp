@@ -576,6 +576,44 @@ PYBIND11_MODULE(spz, m) {
         "encoding and the placement allow.  transforms: None or one entry per input, None or a dict of rotation / "
         "translation / scale / coord (as transform_spz).  sh_degree (None: the largest), fractional_bits (None: the "
         "inputs' common value, else 12), antialiased (None: the inputs must agree).  Returns the number of points.");
+  m.def("sort_spz",
+        [](const std::string &input, const std::string &output, const py::object &keys, const py::object &descending) {
+          // the arguments first: every problem is a ValueError before any device work
+          spz::SortOptions o;
+          if (!py::isinstance<py::bool_>(descending)) throw py::value_error("descending must be a bool");
+          o.descending = py::cast<bool>(descending);
+          if (!keys.is_none()) {
+            if (!py::isinstance<py::array>(keys)) throw py::value_error("keys must be a 1-D float32 numpy array");
+            py::array a = py::reinterpret_borrow<py::array>(keys);
+            if (!a.dtype().is(py::dtype::of<float>()) || a.ndim() != 1) {
+              throw py::value_error("keys must be a 1-D float32 numpy array");
+            }
+            py::array_t<float, py::array::c_style> k(a);  // a copy only when `a` is strided
+            o.keys = std::vector<float>(k.data(), k.data() + k.size());
+          }
+          std::vector<uint32_t> order;
+          bool ok;
+          {
+            py::gil_scoped_release release;
+            ok = spz::sortSpz(input, output, o, &order);
+          }
+          if (!ok) {
+            raiseIfDeviceUnusable();
+            const int st = spz::lastDeviceStatus();
+            if (st == SPZ_AMD_ERR_INVALID_ARG || st == SPZ_AMD_ERR_UNSUPPORTED) {
+              throw py::value_error("sort_spz: refused for this file (see the [SPZ ERROR] line)");
+            }
+            throw std::runtime_error("sort_spz: " + input + " -> " + output + " failed (see the [SPZ ERROR] line)");
+          }
+          py::array_t<uint32_t> r(static_cast<py::ssize_t>(order.size()));
+          if (!order.empty()) std::memcpy(r.mutable_data(), order.data(), order.size() * sizeof(uint32_t));
+          return r;
+        },
+        py::arg("input_filename"), py::arg("output_filename"), py::kw_only(), py::arg("keys") = py::none(),
+        py::arg("descending") = false,
+        "The same points in a new order without requantising (spz::sortSpz): by `keys` (a 1-D float32 array, one per "
+        "point; numpy's argsort(kind='stable') order, NaN last), or by the Morton key of the stored positions; ties keep "
+        "input order.  Returns the order (uint32): output point k is input point order[k].");
   m.def("save_spz",
         [](const spz::GaussianCloud &g, const spz::PackOptions &o, const std::string &filename) {
           bool ok;

@@ -395,6 +395,81 @@ def merge_packed(streams, headers, *, transforms=None, sh_degree=None, fractiona
     return out[:nbytes], hdr, bad
 
 
+def _check_stream_tensor(stream_t):
+    if stream_t.dtype != torch.uint8 or not stream_t.is_cuda or not stream_t.is_contiguous():
+        raise ValueError("the stream must be a contiguous uint8 CUDA tensor")
+
+
+def _check_descending(descending):
+    if not isinstance(descending, bool):
+        raise ValueError(f"descending must be a bool, got {descending!r}")
+
+
+def morton_order(stream_t, header, descending=False, stream=None):
+    """The point order of a packed device stream by the 72-bit Morton key of its stored 24-bit positions (int32 CUDA
+    tensor of num_points; spz_amd_morton_order_device): key ascending (or descending), ties in input order.  subset(
+    stream_t, header, order) is the sorted stream.  A version 1 stream (float16 positions) raises ValueError."""
+    L = abi.load_library()
+    _check_stream_tensor(stream_t)
+    _check_descending(descending)
+    if header.version == 1:
+        raise ValueError("a version 1 stream has float16 positions and no Morton key (transform_packed writes a v3 copy)")
+    n, dev = header.num_points, stream_t.device
+    out = torch.empty(n, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(L.spz_amd_sort_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.spz_amd_morton_order_device(stream_t.data_ptr(), stream_t.numel(), C.byref(header), 1 if descending else 0,
+                                           out.data_ptr() if n else None, ws.data_ptr() if n else None,
+                                           _stream_handle(stream))
+    abi.check(rc, "spz_amd_morton_order_device")
+    if stream is not None:  # the workspace was allocated on the current stream; the launches use it on `stream`
+        ws.record_stream(stream)
+    return out
+
+
+def argsort(keys_t, descending=False, stream=None):
+    """The stable argsort of a 1-D float32 CUDA tensor (int32 CUDA tensor; spz_amd_argsort_f32_device): the order of
+    numpy's argsort(k, kind="stable"), or of argsort(-k) when descending: -0 == +0, every NaN last in both directions.
+    A resident cloud is reordered with index_select on each array's (num_points, -1) view."""
+    L = abi.load_library()
+    _check_descending(descending)
+    if keys_t.dtype != torch.float32 or not keys_t.is_cuda or keys_t.dim() != 1 or not keys_t.is_contiguous():
+        raise ValueError("keys must be a contiguous 1-D float32 CUDA tensor")
+    n, dev = keys_t.numel(), keys_t.device
+    if n >= 2 ** 31:
+        raise ValueError(f"{n} keys: at most 2^31 - 1")
+    out = torch.empty(n, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(L.spz_amd_sort_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.spz_amd_argsort_f32_device(keys_t.data_ptr() if n else None, n, 1 if descending else 0,
+                                          out.data_ptr() if n else None, ws.data_ptr() if n else None,
+                                          _stream_handle(stream))
+    abi.check(rc, "spz_amd_argsort_f32_device")
+    if stream is not None:
+        ws.record_stream(stream)
+    return out
+
+
+def chunk_bounds(stream_t, header, chunk=256, stream=None):
+    """Per run of `chunk` consecutive points of a packed v2/v3 device stream (the last may be partial), the min and max
+    of the stored positions per axis as float32 (the integer times 2^-fractional_bits, exact; stored RUB frame): a
+    float32 CUDA tensor of shape (ceil(num_points / chunk), 2, 3) (spz_amd_chunk_bounds_device)."""
+    L = abi.load_library()
+    _check_stream_tensor(stream_t)
+    if isinstance(chunk, bool) or not isinstance(chunk, int) or not 1 <= chunk <= 0xffffffff:
+        raise ValueError(f"chunk must be an int >= 1, got {chunk!r}")
+    if header.version == 1:
+        raise ValueError("a version 1 stream has float16 positions (transform_packed writes a v3 copy)")
+    n = header.num_points
+    c = (n + chunk - 1) // chunk
+    out = torch.empty((c, 2, 3), dtype=torch.float32, device=stream_t.device)
+    with torch.cuda.device(stream_t.device):
+        rc = L.spz_amd_chunk_bounds_device(stream_t.data_ptr(), stream_t.numel(), C.byref(header), chunk,
+                                           out.data_ptr() if n else None, _stream_handle(stream))
+    abi.check(rc, "spz_amd_chunk_bounds_device")
+    return out
+
+
 def convert_coordinates(cloud, num_points, sh_degree, from_coord, to_coord, stream=None):
     """In-place GaussianCloud::convertCoordinates on device tensors (positions, rotations, sh)."""
     L = abi.load_library()

@@ -35,6 +35,25 @@ def make_cloud_numpy(n, sh_degree, seed):
     return cloud
 
 
+def make_cloud_clustered(n, sh_degree, seed, clusters=4000, sigma=0.05):
+    """A clustered host cloud in file order that knows nothing of space: `clusters` centres U(-10,10)^3, each point in a
+    uniformly drawn cluster at centre + N(0, sigma^2) per axis (so consecutive points belong to unrelated clusters).
+    The other fields are drawn as in make_cloud_numpy.  Draw order: centres, cluster ids, offsets, then the rest."""
+    rng = np.random.default_rng(seed)
+    centres = rng.uniform(-10.0, 10.0, (clusters, 3))
+    ids = rng.integers(0, clusters, n)
+    pos = centres[ids] + rng.standard_normal((n, 3)) * sigma
+    d = SH_DIM[sh_degree] * 3
+    return {
+        "positions": pos.astype(np.float32).reshape(-1),
+        "scales": rng.uniform(-8.0, 0.0, n * 3).astype(np.float32),
+        "rotations": rng.standard_normal(n * 4).astype(np.float32),
+        "alphas": (rng.standard_normal(n) * 3.0).astype(np.float32),
+        "colors": rng.standard_normal(n * 3).astype(np.float32),
+        "sh": (rng.standard_normal(n * d) * 0.25).astype(np.float32),
+    }
+
+
 def make_cloud_torch(n, sh_degree, seed, device):
     """Device-resident cloud (dict of flat float32 torch tensors) drawn with a seeded
     torch.Generator on `device`; same distributions as make_cloud_numpy (different
