@@ -388,6 +388,55 @@ int spz_amd_sort_fetch(void *ctx, uint8_t *h_out);
 const uint8_t *spz_amd_sort_device_data(void *ctx);
 void spz_amd_sort_close(void *ctx);
 
+/* ---- decimate: one point per occupied octree cell, a coarser version of a packed stream (spz_decimate.hip; DESIGN §8
+ *      "Decimate").  The reference has no counterpart.  Input v2 or v3 (version 1, float16 positions:
+ *      SPZ_AMD_ERR_UNSUPPORTED, as for the sort).  Everything is in the stored RUB frame.
+ *
+ *      Cells: per axis u_a = the stored 24-bit field XOR 0x800000 (the sort's Morton convention); at level L (0..24)
+ *      a point's cell is (u_x >> L, u_y >> L, u_z >> L), its origin (u >> L) << L, its world edge 2^(L - fractionalBits).
+ *      With key_i the Morton keys in sorted order, cells(L) = 1 + #{i >= 1 : msb(key_i ^ key_i-1) >= 3L} (n >= 1).
+ *      Output: a v3 stream of one point per occupied cell in ascending Morton order of the cells; the header keeps
+ *      fractionalBits, shDegree and the antialiased bit (flags bit 0), reserved 0.  parents[i] (optional, n uint32) =
+ *      the output index of input point i's cell.
+ *      A cell of one point: the point's bytes (a v2 rotation re-encoded with the smallest-three encoder), as mergeSpz
+ *      copies it; so a v3 stream with distinct stored positions at L = 0 decimates to its sort_spz bytes.
+ *      A cell of several points: one Gaussian that matches their moments.  alpha_i = alpha_byte / 255, V_i =
+ *      exp(ls_x + ls_y + ls_z), w_i = alpha_i V_i, W = sum w_i (W == 0: w_i = 1 and the output alpha is 0); p_i from
+ *      the cell origin; mu = sum w_i p_i / W; Sigma = sum w_i (R_i diag(s_i^2) R_i^T + (p_i - mu)(p_i - mu)^T) / W (R_i of
+ *      the normalised decoded quaternion; f64 accumulators).  Symmetric eigen-decomposition (cyclic Jacobi, fixed
+ *      sweeps), eigenvalues descending -> x, y, z, each floored at exp(-20); log scale = ln(lambda) / 2 through the
+ *      scale encoder; the eigenvectors with det +1 (third column flipped) as a quaternion through the smallest-three
+ *      encoder.  alpha = min(1, W / exp(sum of the log scales before the encoder's clamp)), byte =
+ *      clamp(round_half_away(255 alpha)).  Colour and every sh coefficient: the w-weighted means of the decoded floats
+ *      through their encoders.  Position: origin + round_half_away(mu in quanta), clamped into the cell.
+ *      Deterministic: no float atomics; every sum runs in an order fixed by n, so a run repeats its bytes.
+ *
+ *      decimate_workspace_bytes (host only, no GPU): device memory for either device form at n points of sh_degree.
+ *      level_counts_device: sorts (spz_amd_morton_order_device + spz_amd_subset_device into the workspace), then writes
+ *      cells(L) for L = 0..24 into d_counts (25 uint64, device memory; all 0 for n == 0).
+ *      decimate_device: sorts, then writes the stream at `level` into d_out (device memory) and, when d_parents (device
+ *      memory, n entries) is not NULL, the parents.  capacity >= spz_amd_stream_layout(cells(level), sh_degree,
+ *      3).total_bytes (cells from level_counts_device); the kernels check the cell count against capacity on the
+ *      device and write nothing to d_out when it does not fit.  capacity < 16: SPZ_AMD_ERR_CAPACITY.  Both enqueue on
+ *      hip_stream without synchronising; every argument error is returned before anything is launched.
+ *      The host form (open / fetch / device_data / close, shaped like the sort's) takes a stream already in device
+ *      memory and exactly one of level (0..24, target_points 0) or target_points (>= 1, level -1: the smallest L with
+ *      cells(L) <= target_points; the level counts are the one value read back), runs on `device` on a stream of its
+ *      own and blocks.  Streams above SPZ_AMD_REFERENCE_MAX_POINTS: SPZ_AMD_ERR_TOO_MANY_POINTS.  *h_level (may be
+ *      NULL): the level used; *h_out_hdr (may be NULL): the output header; h_parents (may be NULL): num_points entries;
+ *      h_ms (may be NULL): [0] wall-clock milliseconds of the sort, [1] of the level counts, [2] of the reduction. */
+uint64_t spz_amd_decimate_workspace_bytes(uint64_t num_points, int sh_degree);
+int spz_amd_decimate_level_counts_device(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr,
+                                         uint64_t *d_counts, void *d_workspace, void *hip_stream);
+int spz_amd_decimate_device(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, int level, uint8_t *d_out,
+                            size_t capacity, uint32_t *d_parents, void *d_workspace, void *hip_stream);
+int spz_amd_decimate_open(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, int level,
+                          uint64_t target_points, int device, void **ctx, uint64_t *h_out_bytes, int *h_level,
+                          spz_amd_header *h_out_hdr, uint32_t *h_parents, float *h_ms);
+int spz_amd_decimate_fetch(void *ctx, uint8_t *h_out);
+const uint8_t *spz_amd_decimate_device_data(void *ctx);
+void spz_amd_decimate_close(void *ctx);
+
 /* ---- device buffers for a resident cloud, placed for speed (spz_place.hip).  Whether an sh3 decode runs
  *      at 0.46 ms or at 0.55 ms is decided by whether the sh float array shares a physical region of HBM with the other
  *      arrays of the launch; that cannot be asked for, but it shows in one launch.  alloc: the five small arrays (and a

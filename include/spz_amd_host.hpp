@@ -350,6 +350,23 @@ bool sortSpz(const uint8_t *data, int32_t size, const SortOptions &options, std:
              std::vector<uint32_t> *order = nullptr);
 bool sortSpz(const std::string &inputFilename, const std::string &outputFilename, const SortOptions &options,
              std::vector<uint32_t> *order = nullptr);
+// Decimate (DESIGN §8 "Decimate"): one point per occupied octree cell of edge 2^L quanta, in Morton order of the cells
+// (include/spz_amd.h states the contract).  The member is inflated (loadSpzPackedDevice), decimated on the device
+// (spz_amd_decimate_open) and the v3 stream is compressed with zlib's level-6 bytes.  Exactly one of `level` (0..24) and
+// `targetPoints` (>= 1: the smallest level with at most that many cells) is set.  A cell of one point keeps its bytes
+// (a v2 rotation is re-encoded); a cell of several is one Gaussian matching their moments.  Version 1 files are refused
+// (SPZ_AMD_ERR_UNSUPPORTED).  *parents (may be NULL): the output index of every input point's cell; *level (may be NULL):
+// the level used; *points (may be NULL): the output's point count.  false + one "[SPZ ERROR] decimateSpz: …" line on a bad argument (lastDeviceStatus() =
+// SPZ_AMD_ERR_INVALID_ARG), an input that does not load, or a device failure.  SPZ_AMD_DECIMATE_TIMING=1 prints the
+// stages' times to stderr.
+struct DecimateOptions {
+  std::optional<int> level;
+  std::optional<uint64_t> targetPoints;
+};
+bool decimateSpz(const uint8_t *data, int32_t size, const DecimateOptions &options, std::vector<uint8_t> *out,
+                 std::vector<uint32_t> *parents = nullptr, int *level = nullptr, int64_t *points = nullptr);
+bool decimateSpz(const std::string &inputFilename, const std::string &outputFilename, const DecimateOptions &options,
+                 std::vector<uint32_t> *parents = nullptr, int *level = nullptr, int64_t *points = nullptr);
 // Status (spz_amd.h codes) of the last device call made by this thread; 0 = ok.
 int lastDeviceStatus();
 void setLastDeviceStatus(int status);

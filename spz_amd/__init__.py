@@ -8,6 +8,7 @@ Layout:
   csrc/spz_transform.hip  rotation / translation / uniform scale of a cloud or a packed stream (transformSpz)
   csrc/spz_merge.hip    K packed streams -> one v3 stream, bytes copied where possible (mergeSpz)
   csrc/spz_sort.hip     stable device radix argsort, Morton order of the stored positions, chunk bounds (sortSpz)
+  csrc/spz_decimate.hip one point per occupied octree cell by moment matching, over the Morton-sorted stream (decimateSpz)
   csrc/spz_abi.hip      the C ABI (include/spz_amd.h) over them: device-pointer entry points
   csrc/spz_hostpath.hip host-pointer entry points: device workspace + chunked H2D/kernel/D2H pipeline
   csrc/spz_exchange.hip multi-GPU exchange: native RCCL gatherv/scatterv, IPC-mapped root stream

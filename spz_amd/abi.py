@@ -69,6 +69,8 @@ EXPORTS = (
     "spz_amd_sort_workspace_bytes", "spz_amd_morton_order_device", "spz_amd_argsort_f32_device",
     "spz_amd_chunk_bounds_device", "spz_amd_sort_open", "spz_amd_sort_fetch", "spz_amd_sort_device_data",
     "spz_amd_sort_close",
+    "spz_amd_decimate_workspace_bytes", "spz_amd_decimate_level_counts_device", "spz_amd_decimate_device",
+    "spz_amd_decimate_open", "spz_amd_decimate_fetch", "spz_amd_decimate_device_data", "spz_amd_decimate_close",
 )
 
 RCCL_UNIQUE_ID_BYTES = 128
@@ -354,6 +356,21 @@ def bind(L):
     L.spz_amd_sort_device_data.argtypes = [vp]
     L.spz_amd_sort_close.restype = None
     L.spz_amd_sort_close.argtypes = [vp]
+    L.spz_amd_decimate_workspace_bytes.restype = u64
+    L.spz_amd_decimate_workspace_bytes.argtypes = [u64, i32]
+    L.spz_amd_decimate_level_counts_device.restype = i32
+    L.spz_amd_decimate_level_counts_device.argtypes = [vp, sz, C.POINTER(Header), vp, vp, vp]
+    L.spz_amd_decimate_device.restype = i32
+    L.spz_amd_decimate_device.argtypes = [vp, sz, C.POINTER(Header), i32, vp, sz, vp, vp, vp]
+    L.spz_amd_decimate_open.restype = i32
+    L.spz_amd_decimate_open.argtypes = [vp, sz, C.POINTER(Header), i32, u64, i32, C.POINTER(vp), C.POINTER(u64),
+                                        C.POINTER(i32), C.POINTER(Header), vp, vp]
+    L.spz_amd_decimate_fetch.restype = i32
+    L.spz_amd_decimate_fetch.argtypes = [vp, vp]
+    L.spz_amd_decimate_device_data.restype = vp
+    L.spz_amd_decimate_device_data.argtypes = [vp]
+    L.spz_amd_decimate_close.restype = None
+    L.spz_amd_decimate_close.argtypes = [vp]
     L.spz_amd_zlib_encode_blocks.restype = i32
     L.spz_amd_zlib_encode_blocks.argtypes = [vp, vp, u32, u32, vp, vp, vp, u64, u64, vp, vp]
     return L

@@ -1,10 +1,12 @@
 // spz_cli.cpp — the three command-line tools of the reference (cli_tools/src/*.cpp) over the
 // MI355X drop-in layer: ply_to_spz, spz_to_ply, spz_info; and spz_filter (spz::filterSpz),
-// spz_transform (spz::transformSpz), spz_merge (spz::mergeSpz) and spz_sort (spz::sortSpz), which have no counterpart in
-// the reference.  One binary, dispatched on argv[0] (the Makefile installs it under the seven names) or on a first argument naming the tool.
+// spz_transform (spz::transformSpz), spz_merge (spz::mergeSpz), spz_sort (spz::sortSpz) and spz_decimate
+// (spz::decimateSpz), which have no counterpart in the reference.  One binary, dispatched on argv[0] (the Makefile
+// installs it under the eight names) or on a first argument naming the tool.
 // Same behaviour as the reference mains: default (UNSPECIFIED) pack/unpack options, exit code 0
 // once the arguments are there (the reference ignores the save/load results), usage -> 1.
-// spz_filter, spz_transform, spz_merge and spz_sort exit 1 when the filter / transform / merge / sort fails as well.
+// spz_filter, spz_transform, spz_merge, spz_sort and spz_decimate exit 1 when the filter / transform / merge / sort /
+// decimation fails as well.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -251,6 +253,29 @@ int spzSort(int argc, char **argv) {
   return spz::sortSpz(std::string(argv[1]), std::string(argv[2]), o) ? 0 : 1;
 }
 
+const char *kDecimateUsage = "Usage: spz_decimate <input.spz> <output.spz> (--level <L> | --target <N>)";
+
+int spzDecimate(int argc, char **argv) {
+  auto usage = [] {
+    std::cerr << kDecimateUsage << std::endl;
+    return 1;
+  };
+  if (argc != 5 || argv[1][0] == '-' || argv[2][0] == '-') return usage();
+  const std::string flag = argv[3], value = argv[4];
+  // a plain decimal number, nothing else
+  if (value.empty() || value.size() > 19 || value.find_first_not_of("0123456789") != std::string::npos) return usage();
+  const unsigned long long v = std::strtoull(value.c_str(), nullptr, 10);
+  spz::DecimateOptions o;
+  if (flag == "--level" && v <= 24) {
+    o.level = static_cast<int>(v);
+  } else if (flag == "--target" && v >= 1) {
+    o.targetPoints = static_cast<uint64_t>(v);
+  } else {
+    return usage();
+  }
+  return spz::decimateSpz(std::string(argv[1]), std::string(argv[2]), o) ? 0 : 1;
+}
+
 int dispatch(const std::string &tool, int argc, char **argv) {
   if (tool == "ply_to_spz") return plyToSpz(argc, argv);
   if (tool == "spz_to_ply") return spzToPly(argc, argv);
@@ -259,6 +284,7 @@ int dispatch(const std::string &tool, int argc, char **argv) {
   if (tool == "spz_transform") return spzTransform(argc, argv);
   if (tool == "spz_merge") return spzMerge(argc, argv);
   if (tool == "spz_sort") return spzSort(argc, argv);
+  if (tool == "spz_decimate") return spzDecimate(argc, argv);
   return -1;
 }
 
@@ -275,7 +301,7 @@ int main(int argc, char **argv) {
       rc = dispatch(argv[1], argc - 1, argv + 1);
       if (rc >= 0) return rc;
     }
-    std::cerr << "Usage: spz_tool {ply_to_spz|spz_to_ply|spz_info|spz_filter|spz_transform|spz_merge|spz_sort} <args...>" << std::endl;
+    std::cerr << "Usage: spz_tool {ply_to_spz|spz_to_ply|spz_info|spz_filter|spz_transform|spz_merge|spz_sort|spz_decimate} <args...>" << std::endl;
     return 1;
   } catch (const std::exception &e) {
     std::cerr << "Error: " << e.what() << std::endl;

@@ -2193,6 +2193,128 @@ bool sortSpz(const std::string &inputFilename, const std::string &outputFilename
   return true;
 }
 
+// ---- decimate ----------------------------------------------------------------------------------------------------
+namespace {
+bool decimateRejected(int status, const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  char msg[256];
+  std::vsnprintf(msg, sizeof(msg), fmt, ap);
+  va_end(ap);
+  logLine("[SPZ ERROR] decimateSpz: %s", msg);
+  g_last_status = status;
+  return false;
+}
+
+struct DecimateLaps {
+  bool on = std::getenv("SPZ_AMD_DECIMATE_TIMING") != nullptr;
+  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+  void lap(const char *what) {
+    const auto now = std::chrono::steady_clock::now();
+    if (on) std::fprintf(stderr, "[decimateSpz] %-8s %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
+    t = now;
+  }
+};
+
+// Exactly one of the two, each in range.
+bool decimateOptionsOk(const DecimateOptions &o) {
+  if (o.level.has_value() == o.targetPoints.has_value()) {
+    return decimateRejected(SPZ_AMD_ERR_INVALID_ARG, "exactly one of level and targetPoints must be set");
+  }
+  if (o.level && (*o.level < 0 || *o.level > 24)) {
+    return decimateRejected(SPZ_AMD_ERR_INVALID_ARG, "level %d is outside 0..24", *o.level);
+  }
+  if (o.targetPoints && *o.targetPoints == 0) return decimateRejected(SPZ_AMD_ERR_INVALID_ARG, "targetPoints must be >= 1");
+  return true;
+}
+}  // namespace
+
+bool decimateSpz(const uint8_t *data, int32_t size, const DecimateOptions &o, std::vector<uint8_t> *out,
+                 std::vector<uint32_t> *parents, int *level, int64_t *points) {
+  g_last_status = SPZ_AMD_OK;
+  if (parents) parents->clear();
+  if (out == nullptr) return decimateRejected(SPZ_AMD_ERR_INVALID_ARG, "no output vector");
+  if (!decimateOptionsOk(o)) return false;
+  DecimateLaps laps;
+  DevicePackedGaussians d = loadSpzPackedDevice(data, size);
+  if (!d.valid()) {
+    if (g_last_status == SPZ_AMD_OK) logLine("[SPZ ERROR] decimateSpz: the input is not a readable .spz");
+    return false;
+  }
+  laps.lap("inflate");
+  if (d.version == 1) {
+    return decimateRejected(SPZ_AMD_ERR_UNSUPPORTED,
+                            "a version 1 file has float16 positions and no integer cell; transformSpz with the "
+                            "identity writes a v3 copy");
+  }
+  const uint64_t n = static_cast<uint64_t>(d.numPoints);
+  const spz_amd_header hdr = headerOf(d);
+  std::vector<uint32_t> par;
+  if (parents) detail::resizeUninitialized(&par, static_cast<size_t>(n));
+  void *ctx = nullptr;
+  uint64_t bytes = 0;
+  int used = -1;
+  spz_amd_header outHdr = {};
+  float ms[3] = {0.0f, 0.0f, 0.0f};
+  int rc = spz_amd_decimate_open(d.stream, d.streamBytes, &hdr, o.level ? *o.level : -1,
+                                 o.targetPoints ? *o.targetPoints : 0, d.device, &ctx, &bytes, &used, &outHdr,
+                                 parents ? par.data() : nullptr, ms);
+  if (deviceFailed(rc, "decimateSpz")) return false;
+  struct Close {
+    void *c;
+    ~Close() { spz_amd_decimate_close(c); }
+  } closer{ctx};
+  if (laps.on) {
+    std::fprintf(stderr, "[decimateSpz] sort     %.3f ms\n[decimateSpz] levels   %.3f ms\n[decimateSpz] reduce   %.3f ms\n",
+                 ms[0], ms[1], ms[2]);
+  }
+  laps.lap("decimate");
+  d.release();  // the input's device memory goes before the container stage takes its own
+  std::vector<uint8_t> stream;
+  detail::resizeUninitialized(&stream, static_cast<size_t>(bytes));
+  rc = spz_amd_decimate_fetch(ctx, stream.data());
+  if (deviceFailed(rc, "decimateSpz")) return false;
+  laps.lap("download");
+  if (!compressGzippedWithCopy(stream.data(), stream.size(), out, spz_amd_decimate_device_data(ctx))) {
+    logLine("[SPZ ERROR] decimateSpz: compressGzipped failed");
+    return false;
+  }
+  laps.lap("gzip");
+  if (parents) parents->swap(par);
+  if (level) *level = used;
+  if (points) *points = outHdr.num_points;
+  return true;
+}
+
+bool decimateSpz(const std::string &inputFilename, const std::string &outputFilename, const DecimateOptions &o,
+                 std::vector<uint32_t> *parents, int *level, int64_t *points) {
+  g_last_status = SPZ_AMD_OK;
+  if (parents) parents->clear();
+  if (!decimateOptionsOk(o)) return false;
+  std::vector<uint8_t> data;
+  if (!readFile(inputFilename, &data, /*log=*/true)) return false;
+  if (data.size() > static_cast<size_t>(INT32_MAX)) {
+    return decimateRejected(SPZ_AMD_ERR_INVALID_ARG, "%s is larger than 2 GiB", inputFilename.c_str());
+  }
+  std::vector<uint8_t> file;
+  std::vector<uint32_t> par;
+  int used = -1;
+  int64_t count = 0;
+  if (!decimateSpz(data.data(), static_cast<int32_t>(data.size()), o, &file, parents ? &par : nullptr, &used, &count)) {
+    return false;
+  }
+  DecimateLaps laps;
+  if (!writeFile(outputFilename, file)) {
+    logLine("[SPZ ERROR] decimateSpz: unable to write %s", outputFilename.c_str());
+    return false;
+  }
+  laps.lap("write");
+  if (parents) parents->swap(par);
+  if (level) *level = used;
+  if (points) *points = count;
+  return true;
+}
+
 GaussianCloud loadSpz(const std::vector<uint8_t> &data, const UnpackOptions &o) {
   return loadSpz(data.data(), static_cast<int32_t>(data.size()), o);
 }

@@ -614,6 +614,53 @@ PYBIND11_MODULE(spz, m) {
         "The same points in a new order without requantising (spz::sortSpz): by `keys` (a 1-D float32 array, one per "
         "point; numpy's argsort(kind='stable') order, NaN last), or by the Morton key of the stored positions; ties keep "
         "input order.  Returns the order (uint32): output point k is input point order[k].");
+  m.def("decimate_spz",
+        [](const std::string &input, const std::string &output, const py::object &level, const py::object &target,
+           const py::object &return_parents) -> py::object {
+          // the arguments first: every problem is a ValueError before any device work
+          auto is_int = [](const py::object &v) { return py::isinstance<py::int_>(v) && !py::isinstance<py::bool_>(v); };
+          if (!py::isinstance<py::bool_>(return_parents)) throw py::value_error("return_parents must be a bool");
+          if (level.is_none() == target.is_none()) throw py::value_error("give exactly one of level and target_points");
+          spz::DecimateOptions o;
+          if (!level.is_none()) {
+            if (!is_int(level)) throw py::value_error("level must be an int in 0..24");
+            const long long v = py::cast<long long>(level);
+            if (v < 0 || v > 24) throw py::value_error("level must be an int in 0..24");
+            o.level = static_cast<int>(v);
+          } else {
+            if (!is_int(target)) throw py::value_error("target_points must be an int >= 1");
+            const py::int_ t = py::reinterpret_borrow<py::int_>(target);
+            if (t < py::int_(1) || t > py::int_(UINT64_MAX)) throw py::value_error("target_points must be an int >= 1");
+            o.targetPoints = py::cast<uint64_t>(t);
+          }
+          const bool want_parents = py::cast<bool>(return_parents);
+          std::vector<uint32_t> parents;
+          int used = -1;
+          int64_t points = 0;
+          bool ok;
+          {
+            py::gil_scoped_release release;
+            ok = spz::decimateSpz(input, output, o, want_parents ? &parents : nullptr, &used, &points);
+          }
+          if (!ok) {
+            raiseIfDeviceUnusable();
+            const int st = spz::lastDeviceStatus();
+            if (st == SPZ_AMD_ERR_INVALID_ARG || st == SPZ_AMD_ERR_UNSUPPORTED) {
+              throw py::value_error("decimate_spz: refused for this file (see the [SPZ ERROR] line)");
+            }
+            throw std::runtime_error("decimate_spz: " + input + " -> " + output + " failed (see the [SPZ ERROR] line)");
+          }
+          if (!want_parents) return py::make_tuple(used, points);
+          py::array_t<uint32_t> r(static_cast<py::ssize_t>(parents.size()));
+          if (!parents.empty()) std::memcpy(r.mutable_data(), parents.data(), parents.size() * sizeof(uint32_t));
+          return py::make_tuple(used, points, r);
+        },
+        py::arg("input_filename"), py::arg("output_filename"), py::kw_only(), py::arg("level") = py::none(),
+        py::arg("target_points") = py::none(), py::arg("return_parents") = false,
+        "A coarser version of a v2/v3 file (spz::decimateSpz): one point per occupied octree cell of edge 2^level "
+        "quanta, in Morton order; a cell of several points becomes one Gaussian matching their moments.  Exactly one "
+        "of level (0..24) and target_points (>= 1: the smallest level with at most that many cells).  Returns (level, "
+        "points), plus parents (uint32: the output index of every input point's cell) when return_parents.");
   m.def("save_spz",
         [](const spz::GaussianCloud &g, const spz::PackOptions &o, const std::string &filename) {
           bool ok;

@@ -470,6 +470,62 @@ def chunk_bounds(stream_t, header, chunk=256, stream=None):
     return out
 
 
+def _check_decimate_stream(stream_t, header):
+    _check_stream_tensor(stream_t)
+    if header.version == 1:
+        raise ValueError("a version 1 stream has float16 positions and no integer cell (transform_packed writes a v3 "
+                         "copy)")
+
+
+def level_counts(stream_t, header, stream=None):
+    """cells(L) for L = 0..24 of a packed v2/v3 device stream (int64 CUDA tensor of 25;
+    spz_amd_decimate_level_counts_device): the number of occupied octree cells of edge 2^L quanta, counted over the
+    Morton-sorted stream."""
+    L = abi.load_library()
+    _check_decimate_stream(stream_t, header)
+    n, dev = header.num_points, stream_t.device
+    out = torch.empty(25, dtype=torch.int64, device=dev)
+    ws = torch.empty(int(L.spz_amd_decimate_workspace_bytes(n, header.sh_degree)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.spz_amd_decimate_level_counts_device(stream_t.data_ptr(), stream_t.numel(), C.byref(header),
+                                                    out.data_ptr(), ws.data_ptr(), _stream_handle(stream))
+    abi.check(rc, "spz_amd_decimate_level_counts_device")
+    if stream is not None:  # the workspace was allocated on the current stream; the launches use it on `stream`
+        ws.record_stream(stream)
+    return out
+
+
+def decimate_packed(stream_t, header, level, stream=None):
+    """One point per occupied octree cell of edge 2^level quanta of a packed v2/v3 device stream
+    (spz_amd_decimate_device; the contract is in include/spz_amd.h).  Returns (stream uint8 CUDA tensor, Header,
+    parents int32 CUDA tensor of num_points: the output index of every input point's cell).  The cell count comes from
+    level_counts first (one small read-back), so the stream is sorted twice."""
+    L = abi.load_library()
+    _check_decimate_stream(stream_t, header)
+    if isinstance(level, bool) or not isinstance(level, int) or not 0 <= level <= 24:
+        raise ValueError(f"level must be an int in 0..24, got {level!r}")
+    n, dev = header.num_points, stream_t.device
+    m = 0
+    if n:
+        counts = level_counts(stream_t, header, stream)
+        if stream is not None:
+            stream.synchronize()
+        m = int(counts[level].item())
+    nbytes = abi.stream_layout(m, header.sh_degree, 3).total_bytes
+    out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    parents = torch.empty(n, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(L.spz_amd_decimate_workspace_bytes(n, header.sh_degree)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.spz_amd_decimate_device(stream_t.data_ptr(), stream_t.numel(), C.byref(header), level, out.data_ptr(),
+                                       nbytes, parents.data_ptr() if n else None, ws.data_ptr(),
+                                       _stream_handle(stream))
+    abi.check(rc, "spz_amd_decimate_device")
+    if stream is not None:
+        ws.record_stream(stream)
+    hdr = make_header(m, header.sh_degree, 3, header.fractional_bits, bool(header.flags & 1))
+    return out, hdr, parents
+
+
 def convert_coordinates(cloud, num_points, sh_degree, from_coord, to_coord, stream=None):
     """In-place GaussianCloud::convertCoordinates on device tensors (positions, rotations, sh)."""
     L = abi.load_library()
