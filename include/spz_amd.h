@@ -437,6 +437,51 @@ int spz_amd_decimate_fetch(void *ctx, uint8_t *h_out);
 const uint8_t *spz_amd_decimate_device_data(void *ctx);
 void spz_amd_decimate_close(void *ctx);
 
+/* ---- clean: floater removal, the statistical (k nearest neighbours) and the radius outlier rules (spz_clean.hip;
+ *      DESIGN §8 "Clean").  The reference has no counterpart.  Input v2 or v3 (version 1, float16 positions:
+ *      SPZ_AMD_ERR_UNSUPPORTED, as for the sort).  Streams above SPZ_AMD_REFERENCE_MAX_POINTS:
+ *      SPZ_AMD_ERR_TOO_MANY_POINTS.
+ *
+ *      Distances: the stored RUB frame, P_i the sign-extended stored 24-bit integers; d2(i, j) = sum_a (P_ia - P_ja)^2,
+ *      exact (< 2^50).  The neighbours of i are the other points by index; duplicates count, at distance 0.
+ *      Statistical rule: k_eff = min(k, n - 1); score_i = (sum_{j=1..k_eff} sqrt(d2_(j))) / k_eff * 2^-fractionalBits in
+ *      f64, d2_(1) <= ... <= d2_(k_eff) the k_eff smallest, summed in ascending order, sqrt correctly rounded.
+ *      thr = mean + std_ratio * std over the n scores, std with the n - 1 divisor, f64 sums in an order fixed by n.
+ *      Keep i iff score_i <= thr.  n == 1: score 0.
+ *      Radius rule: R2 = floor(fl((radius * 2^fractionalBits)^2)) in f64 on the host (clean_radius_r2);
+ *      count_i = min(#{j != i : d2(i, j) <= R2}, min_neighbors).  Keep i iff count_i >= min_neighbors.
+ *      Both rules: a point is kept iff it passes both.  n <= 1: every point is kept.
+ *      Output: spz_amd_subset_device of the kept indices in input order at the input's degree, so the stream is
+ *      byte-identical to the filter's with the keep mask (header: version, fractionalBits and antialiased bit kept).
+ *      Arguments: k 1..64, std_ratio finite, radius finite and > 0, min_neighbors 1..256, at least one rule; a bad one is
+ *      SPZ_AMD_ERR_INVALID_ARG, returned before anything is launched.
+ *
+ *      clean_workspace_bytes (host only, no GPU): device memory for either device form at n points (any alignment).
+ *      clean_radius_r2 (host only): R2 of the radius rule (>= 2^64: UINT64_MAX).
+ *      knn_scores_device: the n scores into d_scores (device memory, f64, input order) and, when d_kth_d2 (device
+ *      memory, n uint64) is not NULL, d2_(k_eff) of every point.  radius_counts_device: the n counts into d_counts
+ *      (device memory, uint32) for a given R2.  Both Morton-sort the positions into the workspace first
+ *      (spz_amd_morton_order_device), enqueue on hip_stream and do not synchronise.
+ *      The host form (open / fetch / device_data / close, shaped like the decimate's) takes a stream already in device
+ *      memory and the rules (k == 0: no statistical rule; min_neighbors == 0: no radius rule, radius ignored), runs the
+ *      scores and / or counts, the threshold, the keep mask, spz_amd_select_device and spz_amd_subset_device on
+ *      `device` on a stream of its own, and blocks.  *h_kept (may be NULL): the kept count; *h_threshold (may be NULL):
+ *      thr (NaN without the statistical rule); h_mask (may be NULL): num_points bytes, 1 = kept; h_scores (may be NULL;
+ *      only with the statistical rule): num_points f64; h_ms (may be NULL): [0] wall-clock milliseconds of the sort,
+ *      [1] of the scores and counts, [2] of the threshold, the mask and the subset. */
+uint64_t spz_amd_clean_workspace_bytes(uint64_t num_points);
+int spz_amd_clean_radius_r2(double radius, int fractional_bits, uint64_t *r2);
+int spz_amd_knn_scores_device(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, int k, double *d_scores,
+                              uint64_t *d_kth_d2, void *d_workspace, void *hip_stream);
+int spz_amd_radius_counts_device(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, uint64_t r2,
+                                 uint32_t min_neighbors, uint32_t *d_counts, void *d_workspace, void *hip_stream);
+int spz_amd_clean_open(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, int k, double std_ratio,
+                       double radius, uint32_t min_neighbors, int device, void **ctx, uint64_t *h_out_bytes,
+                       uint64_t *h_kept, double *h_threshold, uint8_t *h_mask, double *h_scores, float *h_ms);
+int spz_amd_clean_fetch(void *ctx, uint8_t *h_out);
+const uint8_t *spz_amd_clean_device_data(void *ctx);
+void spz_amd_clean_close(void *ctx);
+
 /* ---- device buffers for a resident cloud, placed for speed (spz_place.hip).  Whether an sh3 decode runs
  *      at 0.46 ms or at 0.55 ms is decided by whether the sh float array shares a physical region of HBM with the other
  *      arrays of the launch; that cannot be asked for, but it shows in one launch.  alloc: the five small arrays (and a

@@ -367,6 +367,33 @@ bool decimateSpz(const uint8_t *data, int32_t size, const DecimateOptions &optio
                  std::vector<uint32_t> *parents = nullptr, int *level = nullptr, int64_t *points = nullptr);
 bool decimateSpz(const std::string &inputFilename, const std::string &outputFilename, const DecimateOptions &options,
                  std::vector<uint32_t> *parents = nullptr, int *level = nullptr, int64_t *points = nullptr);
+// Clean (DESIGN §8 "Clean"): floater removal by the statistical (k nearest neighbours) and / or the radius outlier rule
+// (include/spz_amd.h states the contract).  The member is inflated (loadSpzPackedDevice), cleaned on the device
+// (spz_amd_clean_open) and the kept points' bytes are compressed with zlib's level-6 bytes: the stream equals filterSpz's
+// with the keep mask.  At least one rule is set: statistical (k 1..64, stdRatio finite), radius (radius finite > 0,
+// minNeighbors 1..256).  Version 1 files are refused (SPZ_AMD_ERR_UNSUPPORTED).  *kept (may be NULL): the kept count;
+// *keepMask (may be NULL): one byte per input point, 1 = kept; *scores (may be NULL): the statistical scores (empty
+// without that rule); *threshold (may be NULL): the threshold (NaN without that rule).  false + one
+// "[SPZ ERROR] cleanSpz: …" line on a bad argument (lastDeviceStatus() = SPZ_AMD_ERR_INVALID_ARG), an input that does
+// not load, or a device failure.  SPZ_AMD_CLEAN_TIMING=1 prints the stages' times to stderr.
+struct CleanOptions {
+  struct Statistical {
+    int k = 20;
+    double stdRatio = 2.0;
+  };
+  struct Radius {
+    double radius = 0.0;
+    int minNeighbors = 0;
+  };
+  std::optional<Statistical> statistical;
+  std::optional<Radius> radius;
+};
+bool cleanSpz(const uint8_t *data, int32_t size, const CleanOptions &options, std::vector<uint8_t> *out,
+              int64_t *kept = nullptr, std::vector<uint8_t> *keepMask = nullptr, std::vector<double> *scores = nullptr,
+              double *threshold = nullptr);
+bool cleanSpz(const std::string &inputFilename, const std::string &outputFilename, const CleanOptions &options,
+              int64_t *kept = nullptr, std::vector<uint8_t> *keepMask = nullptr, std::vector<double> *scores = nullptr,
+              double *threshold = nullptr);
 // Status (spz_amd.h codes) of the last device call made by this thread; 0 = ok.
 int lastDeviceStatus();
 void setLastDeviceStatus(int status);

@@ -71,6 +71,9 @@ EXPORTS = (
     "spz_amd_sort_close",
     "spz_amd_decimate_workspace_bytes", "spz_amd_decimate_level_counts_device", "spz_amd_decimate_device",
     "spz_amd_decimate_open", "spz_amd_decimate_fetch", "spz_amd_decimate_device_data", "spz_amd_decimate_close",
+    "spz_amd_clean_workspace_bytes", "spz_amd_clean_radius_r2", "spz_amd_knn_scores_device",
+    "spz_amd_radius_counts_device", "spz_amd_clean_open", "spz_amd_clean_fetch", "spz_amd_clean_device_data",
+    "spz_amd_clean_close",
 )
 
 RCCL_UNIQUE_ID_BYTES = 128
@@ -371,6 +374,23 @@ def bind(L):
     L.spz_amd_decimate_device_data.argtypes = [vp]
     L.spz_amd_decimate_close.restype = None
     L.spz_amd_decimate_close.argtypes = [vp]
+    L.spz_amd_clean_workspace_bytes.restype = u64
+    L.spz_amd_clean_workspace_bytes.argtypes = [u64]
+    L.spz_amd_clean_radius_r2.restype = i32
+    L.spz_amd_clean_radius_r2.argtypes = [C.c_double, i32, C.POINTER(u64)]
+    L.spz_amd_knn_scores_device.restype = i32
+    L.spz_amd_knn_scores_device.argtypes = [vp, sz, C.POINTER(Header), i32, vp, vp, vp, vp]
+    L.spz_amd_radius_counts_device.restype = i32
+    L.spz_amd_radius_counts_device.argtypes = [vp, sz, C.POINTER(Header), u64, u32, vp, vp, vp]
+    L.spz_amd_clean_open.restype = i32
+    L.spz_amd_clean_open.argtypes = [vp, sz, C.POINTER(Header), i32, C.c_double, C.c_double, u32, i32, C.POINTER(vp),
+                                     C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_double), vp, vp, vp]
+    L.spz_amd_clean_fetch.restype = i32
+    L.spz_amd_clean_fetch.argtypes = [vp, vp]
+    L.spz_amd_clean_device_data.restype = vp
+    L.spz_amd_clean_device_data.argtypes = [vp]
+    L.spz_amd_clean_close.restype = None
+    L.spz_amd_clean_close.argtypes = [vp]
     L.spz_amd_zlib_encode_blocks.restype = i32
     L.spz_amd_zlib_encode_blocks.argtypes = [vp, vp, u32, u32, vp, vp, vp, u64, u64, vp, vp]
     return L

@@ -1,13 +1,14 @@
 // spz_cli.cpp — the three command-line tools of the reference (cli_tools/src/*.cpp) over the
 // MI355X drop-in layer: ply_to_spz, spz_to_ply, spz_info; and spz_filter (spz::filterSpz),
-// spz_transform (spz::transformSpz), spz_merge (spz::mergeSpz), spz_sort (spz::sortSpz) and spz_decimate
-// (spz::decimateSpz), which have no counterpart in the reference.  One binary, dispatched on argv[0] (the Makefile
-// installs it under the eight names) or on a first argument naming the tool.
+// spz_transform (spz::transformSpz), spz_merge (spz::mergeSpz), spz_sort (spz::sortSpz), spz_decimate
+// (spz::decimateSpz) and spz_clean (spz::cleanSpz), which have no counterpart in the reference.  One binary, dispatched
+// on argv[0] (the Makefile installs it under the nine names) or on a first argument naming the tool.
 // Same behaviour as the reference mains: default (UNSPECIFIED) pack/unpack options, exit code 0
 // once the arguments are there (the reference ignores the save/load results), usage -> 1.
-// spz_filter, spz_transform, spz_merge, spz_sort and spz_decimate exit 1 when the filter / transform / merge / sort /
-// decimation fails as well.
+// spz_filter, spz_transform, spz_merge, spz_sort, spz_decimate and spz_clean exit 1 when the filter / transform / merge /
+// sort / decimation / clean fails as well.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
@@ -276,6 +277,52 @@ int spzDecimate(int argc, char **argv) {
   return spz::decimateSpz(std::string(argv[1]), std::string(argv[2]), o) ? 0 : 1;
 }
 
+const char *kCleanUsage =
+    "Usage: spz_clean <input.spz> <output.spz> [--k <K> [--std-ratio <S>]] [--radius <R> --min-neighbors <M>]";
+
+// a plain decimal integer in lo..hi
+bool parseCount(const char *s, int lo, int hi, int *v) {
+  const std::string t = s;
+  if (t.empty() || t.size() > 4 || t.find_first_not_of("0123456789") != std::string::npos) return false;
+  *v = std::atoi(s);
+  return *v >= lo && *v <= hi;
+}
+
+int spzClean(int argc, char **argv) {
+  auto usage = [] {
+    std::cerr << kCleanUsage << std::endl;
+    return 1;
+  };
+  if (argc < 5 || argv[1][0] == '-' || argv[2][0] == '-' || (argc - 3) % 2 != 0) return usage();
+  bool hasK = false, hasRatio = false, hasRadius = false, hasMin = false;
+  spz::CleanOptions::Statistical st;
+  spz::CleanOptions::Radius rd;
+  for (int i = 3; i < argc; i += 2) {
+    const std::string flag = argv[i];
+    const char *value = argv[i + 1];
+    if (flag == "--k" && !hasK) {
+      if (!parseCount(value, 1, 64, &st.k)) return usage();
+      hasK = true;
+    } else if (flag == "--std-ratio" && !hasRatio) {
+      if (!parseDouble(value, &st.stdRatio) || !std::isfinite(st.stdRatio)) return usage();
+      hasRatio = true;
+    } else if (flag == "--radius" && !hasRadius) {
+      if (!parseDouble(value, &rd.radius) || !std::isfinite(rd.radius) || !(rd.radius > 0.0)) return usage();
+      hasRadius = true;
+    } else if (flag == "--min-neighbors" && !hasMin) {
+      if (!parseCount(value, 1, 256, &rd.minNeighbors)) return usage();
+      hasMin = true;
+    } else {
+      return usage();
+    }
+  }
+  if ((hasRatio && !hasK) || hasRadius != hasMin || (!hasK && !hasRadius)) return usage();
+  spz::CleanOptions o;
+  if (hasK) o.statistical = st;
+  if (hasRadius) o.radius = rd;
+  return spz::cleanSpz(std::string(argv[1]), std::string(argv[2]), o) ? 0 : 1;
+}
+
 int dispatch(const std::string &tool, int argc, char **argv) {
   if (tool == "ply_to_spz") return plyToSpz(argc, argv);
   if (tool == "spz_to_ply") return spzToPly(argc, argv);
@@ -285,6 +332,7 @@ int dispatch(const std::string &tool, int argc, char **argv) {
   if (tool == "spz_merge") return spzMerge(argc, argv);
   if (tool == "spz_sort") return spzSort(argc, argv);
   if (tool == "spz_decimate") return spzDecimate(argc, argv);
+  if (tool == "spz_clean") return spzClean(argc, argv);
   return -1;
 }
 
@@ -301,7 +349,7 @@ int main(int argc, char **argv) {
       rc = dispatch(argv[1], argc - 1, argv + 1);
       if (rc >= 0) return rc;
     }
-    std::cerr << "Usage: spz_tool {ply_to_spz|spz_to_ply|spz_info|spz_filter|spz_transform|spz_merge|spz_sort|spz_decimate} <args...>" << std::endl;
+    std::cerr << "Usage: spz_tool {ply_to_spz|spz_to_ply|spz_info|spz_filter|spz_transform|spz_merge|spz_sort|spz_decimate|spz_clean} <args...>" << std::endl;
     return 1;
   } catch (const std::exception &e) {
     std::cerr << "Error: " << e.what() << std::endl;

@@ -2315,6 +2315,144 @@ bool decimateSpz(const std::string &inputFilename, const std::string &outputFile
   return true;
 }
 
+// ---- clean -------------------------------------------------------------------------------------------------------
+namespace {
+bool cleanRejected(int status, const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  char msg[256];
+  std::vsnprintf(msg, sizeof(msg), fmt, ap);
+  va_end(ap);
+  logLine("[SPZ ERROR] cleanSpz: %s", msg);
+  g_last_status = status;
+  return false;
+}
+
+struct CleanLaps {
+  bool on = std::getenv("SPZ_AMD_CLEAN_TIMING") != nullptr;
+  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+  void lap(const char *what) {
+    const auto now = std::chrono::steady_clock::now();
+    if (on) std::fprintf(stderr, "[cleanSpz] %-8s %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
+    t = now;
+  }
+};
+
+// At least one rule, each in range.
+bool cleanOptionsOk(const CleanOptions &o) {
+  if (!o.statistical && !o.radius) return cleanRejected(SPZ_AMD_ERR_INVALID_ARG, "set statistical, radius or both");
+  if (o.statistical) {
+    if (o.statistical->k < 1 || o.statistical->k > 64) {
+      return cleanRejected(SPZ_AMD_ERR_INVALID_ARG, "k %d is outside 1..64", o.statistical->k);
+    }
+    if (!std::isfinite(o.statistical->stdRatio)) return cleanRejected(SPZ_AMD_ERR_INVALID_ARG, "stdRatio must be finite");
+  }
+  if (o.radius) {
+    if (!std::isfinite(o.radius->radius) || !(o.radius->radius > 0.0)) {
+      return cleanRejected(SPZ_AMD_ERR_INVALID_ARG, "radius must be finite and > 0");
+    }
+    if (o.radius->minNeighbors < 1 || o.radius->minNeighbors > 256) {
+      return cleanRejected(SPZ_AMD_ERR_INVALID_ARG, "minNeighbors %d is outside 1..256", o.radius->minNeighbors);
+    }
+  }
+  return true;
+}
+}  // namespace
+
+bool cleanSpz(const uint8_t *data, int32_t size, const CleanOptions &o, std::vector<uint8_t> *out, int64_t *kept,
+              std::vector<uint8_t> *keepMask, std::vector<double> *scores, double *threshold) {
+  g_last_status = SPZ_AMD_OK;
+  if (keepMask) keepMask->clear();
+  if (scores) scores->clear();
+  if (out == nullptr) return cleanRejected(SPZ_AMD_ERR_INVALID_ARG, "no output vector");
+  if (!cleanOptionsOk(o)) return false;
+  CleanLaps laps;
+  DevicePackedGaussians d = loadSpzPackedDevice(data, size);
+  if (!d.valid()) {
+    if (g_last_status == SPZ_AMD_OK) logLine("[SPZ ERROR] cleanSpz: the input is not a readable .spz");
+    return false;
+  }
+  laps.lap("inflate");
+  if (d.version == 1) {
+    return cleanRejected(SPZ_AMD_ERR_UNSUPPORTED,
+                         "a version 1 file has float16 positions and no integer distances; transformSpz with the "
+                         "identity writes a v3 copy");
+  }
+  const uint64_t n = static_cast<uint64_t>(d.numPoints);
+  const spz_amd_header hdr = headerOf(d);
+  std::vector<uint8_t> mask;
+  std::vector<double> sc;
+  if (keepMask) detail::resizeUninitialized(&mask, static_cast<size_t>(n));
+  if (scores && o.statistical) detail::resizeUninitialized(&sc, static_cast<size_t>(n));
+  void *ctx = nullptr;
+  uint64_t bytes = 0, count = 0;
+  double thr = 0.0;
+  float ms[3] = {0.0f, 0.0f, 0.0f};
+  int rc = spz_amd_clean_open(d.stream, d.streamBytes, &hdr, o.statistical ? o.statistical->k : 0,
+                              o.statistical ? o.statistical->stdRatio : 0.0, o.radius ? o.radius->radius : 0.0,
+                              o.radius ? static_cast<uint32_t>(o.radius->minNeighbors) : 0u, d.device, &ctx, &bytes,
+                              &count, &thr, keepMask ? mask.data() : nullptr,
+                              scores && o.statistical ? sc.data() : nullptr, ms);
+  if (deviceFailed(rc, "cleanSpz")) return false;
+  struct Close {
+    void *c;
+    ~Close() { spz_amd_clean_close(c); }
+  } closer{ctx};
+  if (laps.on) {
+    std::fprintf(stderr, "[cleanSpz] sort     %.3f ms\n[cleanSpz] search   %.3f ms\n[cleanSpz] subset   %.3f ms\n",
+                 ms[0], ms[1], ms[2]);
+  }
+  laps.lap("clean");
+  d.release();  // the input's device memory goes before the container stage takes its own
+  std::vector<uint8_t> stream;
+  detail::resizeUninitialized(&stream, static_cast<size_t>(bytes));
+  rc = spz_amd_clean_fetch(ctx, stream.data());
+  if (deviceFailed(rc, "cleanSpz")) return false;
+  laps.lap("download");
+  if (!compressGzippedWithCopy(stream.data(), stream.size(), out, spz_amd_clean_device_data(ctx))) {
+    logLine("[SPZ ERROR] cleanSpz: compressGzipped failed");
+    return false;
+  }
+  laps.lap("gzip");
+  if (kept) *kept = static_cast<int64_t>(count);
+  if (keepMask) keepMask->swap(mask);
+  if (scores) scores->swap(sc);
+  if (threshold) *threshold = thr;
+  return true;
+}
+
+bool cleanSpz(const std::string &inputFilename, const std::string &outputFilename, const CleanOptions &o,
+              int64_t *kept, std::vector<uint8_t> *keepMask, std::vector<double> *scores, double *threshold) {
+  g_last_status = SPZ_AMD_OK;
+  if (keepMask) keepMask->clear();
+  if (scores) scores->clear();
+  if (!cleanOptionsOk(o)) return false;
+  std::vector<uint8_t> data;
+  if (!readFile(inputFilename, &data, /*log=*/true)) return false;
+  if (data.size() > static_cast<size_t>(INT32_MAX)) {
+    return cleanRejected(SPZ_AMD_ERR_INVALID_ARG, "%s is larger than 2 GiB", inputFilename.c_str());
+  }
+  std::vector<uint8_t> file, mask;
+  std::vector<double> sc;
+  int64_t count = 0;
+  double thr = 0.0;
+  if (!cleanSpz(data.data(), static_cast<int32_t>(data.size()), o, &file, &count, keepMask ? &mask : nullptr,
+                scores ? &sc : nullptr, &thr)) {
+    return false;
+  }
+  CleanLaps laps;
+  if (!writeFile(outputFilename, file)) {
+    logLine("[SPZ ERROR] cleanSpz: unable to write %s", outputFilename.c_str());
+    return false;
+  }
+  laps.lap("write");
+  if (kept) *kept = count;
+  if (keepMask) keepMask->swap(mask);
+  if (scores) scores->swap(sc);
+  if (threshold) *threshold = thr;
+  return true;
+}
+
 GaussianCloud loadSpz(const std::vector<uint8_t> &data, const UnpackOptions &o) {
   return loadSpz(data.data(), static_cast<int32_t>(data.size()), o);
 }

@@ -661,6 +661,78 @@ PYBIND11_MODULE(spz, m) {
         "quanta, in Morton order; a cell of several points becomes one Gaussian matching their moments.  Exactly one "
         "of level (0..24) and target_points (>= 1: the smallest level with at most that many cells).  Returns (level, "
         "points), plus parents (uint32: the output index of every input point's cell) when return_parents.");
+  m.def("clean_spz",
+        [](const std::string &input, const std::string &output, const py::object &k, const py::object &std_ratio,
+           const py::object &radius, const py::object &min_neighbors, const py::object &return_details) -> py::object {
+          // the arguments first: every problem is a ValueError before any device work
+          auto is_int = [](const py::object &v) { return py::isinstance<py::int_>(v) && !py::isinstance<py::bool_>(v); };
+          auto is_real = [](const py::object &v) {
+            return (py::isinstance<py::float_>(v) || py::isinstance<py::int_>(v)) && !py::isinstance<py::bool_>(v);
+          };
+          if (!py::isinstance<py::bool_>(return_details)) throw py::value_error("return_details must be a bool");
+          if (k.is_none() && radius.is_none() && min_neighbors.is_none()) {
+            throw py::value_error("give k, or radius and min_neighbors, or both");
+          }
+          if (radius.is_none() != min_neighbors.is_none()) {
+            throw py::value_error("radius and min_neighbors go together");
+          }
+          spz::CleanOptions o;
+          if (!k.is_none()) {
+            if (!is_int(k)) throw py::value_error("k must be an int in 1..64");
+            const py::int_ kv = py::reinterpret_borrow<py::int_>(k);
+            if (kv < py::int_(1) || kv > py::int_(64)) throw py::value_error("k must be an int in 1..64");
+            if (!is_real(std_ratio)) throw py::value_error("std_ratio must be a finite number");
+            const double s = py::cast<double>(std_ratio);
+            if (!std::isfinite(s)) throw py::value_error("std_ratio must be a finite number");
+            o.statistical = spz::CleanOptions::Statistical{py::cast<int>(kv), s};
+          }
+          if (!radius.is_none()) {
+            if (!is_real(radius)) throw py::value_error("radius must be a finite number > 0");
+            const double r = py::cast<double>(radius);
+            if (!std::isfinite(r) || !(r > 0.0)) throw py::value_error("radius must be a finite number > 0");
+            if (!is_int(min_neighbors)) throw py::value_error("min_neighbors must be an int in 1..256");
+            const py::int_ mv = py::reinterpret_borrow<py::int_>(min_neighbors);
+            if (mv < py::int_(1) || mv > py::int_(256)) throw py::value_error("min_neighbors must be an int in 1..256");
+            o.radius = spz::CleanOptions::Radius{r, py::cast<int>(mv)};
+          }
+          const bool details = py::cast<bool>(return_details);
+          std::vector<uint8_t> mask;
+          std::vector<double> scores;
+          int64_t kept = 0;
+          double thr = 0.0;
+          bool ok;
+          {
+            py::gil_scoped_release release;
+            ok = spz::cleanSpz(input, output, o, &kept, details ? &mask : nullptr, details ? &scores : nullptr, &thr);
+          }
+          if (!ok) {
+            raiseIfDeviceUnusable();
+            const int st = spz::lastDeviceStatus();
+            if (st == SPZ_AMD_ERR_INVALID_ARG || st == SPZ_AMD_ERR_UNSUPPORTED) {
+              throw py::value_error("clean_spz: refused for this file (see the [SPZ ERROR] line)");
+            }
+            throw std::runtime_error("clean_spz: " + input + " -> " + output + " failed (see the [SPZ ERROR] line)");
+          }
+          if (!details) return py::int_(kept);
+          py::array_t<bool> m(static_cast<py::ssize_t>(mask.size()));
+          if (!mask.empty()) std::memcpy(m.mutable_data(), mask.data(), mask.size());
+          py::object sc = py::none(), th = py::none();
+          if (o.statistical) {
+            py::array_t<double> s(static_cast<py::ssize_t>(scores.size()));
+            if (!scores.empty()) std::memcpy(s.mutable_data(), scores.data(), scores.size() * sizeof(double));
+            sc = s;
+            th = py::float_(thr);
+          }
+          return py::make_tuple(kept, m, sc, th);
+        },
+        py::arg("input_filename"), py::arg("output_filename"), py::kw_only(), py::arg("k") = py::none(),
+        py::arg("std_ratio") = 2.0, py::arg("radius") = py::none(), py::arg("min_neighbors") = py::none(),
+        py::arg("return_details") = false,
+        "Remove floaters from a v2/v3 file without requantising (spz::cleanSpz).  Statistical rule (k in 1..64): drop a "
+        "point whose mean distance to its k nearest neighbours is above mean + std_ratio * std of all of them.  Radius "
+        "rule (radius > 0 in world units, min_neighbors in 1..256): drop a point with fewer than min_neighbors others "
+        "within radius.  Both: a point must pass both.  Returns the kept count, or (kept, mask (bool per input point), "
+        "scores (float64, None without k), threshold (None without k)) when return_details.");
   m.def("save_spz",
         [](const spz::GaussianCloud &g, const spz::PackOptions &o, const std::string &filename) {
           bool ok;

@@ -6,6 +6,7 @@ tensors keyed like the reference's GaussianCloud fields (splat-types.h:101-115):
 positions[3N], scales[3N], rotations[4N], alphas[N], colors[3N], sh[N*shDim*3].
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -524,6 +525,61 @@ def decimate_packed(stream_t, header, level, stream=None):
         ws.record_stream(stream)
     hdr = make_header(m, header.sh_degree, 3, header.fractional_bits, bool(header.flags & 1))
     return out, hdr, parents
+
+
+def _check_clean_stream(stream_t, header):
+    _check_stream_tensor(stream_t)
+    if header.version == 1:
+        raise ValueError("a version 1 stream has float16 positions and no integer distances (transform_packed writes a "
+                         "v3 copy)")
+    if header.num_points > abi.REFERENCE_MAX_POINTS:
+        raise ValueError(f"{header.num_points} points is above the reader limit {abi.REFERENCE_MAX_POINTS}")
+
+
+def knn_scores(stream_t, header, k, stream=None):
+    """The statistical outlier scores of a packed v2/v3 device stream (spz_amd_knn_scores_device; the contract is in
+    include/spz_amd.h "clean"): for every point in input order, the mean distance to its k_eff = min(k, n - 1) nearest
+    other points in world units (float64 CUDA tensor), and the k_eff-th squared distance in stored quanta (int64 CUDA
+    tensor).  Exact: the scores equal a brute-force k-NN over the stored integers bit for bit."""
+    L = abi.load_library()
+    _check_clean_stream(stream_t, header)
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 64:
+        raise ValueError(f"k must be an int in 1..64, got {k!r}")
+    n, dev = header.num_points, stream_t.device
+    scores = torch.empty(n, dtype=torch.float64, device=dev)
+    kth = torch.empty(n, dtype=torch.int64, device=dev)
+    ws = torch.empty(int(L.spz_amd_clean_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.spz_amd_knn_scores_device(stream_t.data_ptr(), stream_t.numel(), C.byref(header), k,
+                                         scores.data_ptr(), kth.data_ptr(), ws.data_ptr(), _stream_handle(stream))
+    abi.check(rc, "spz_amd_knn_scores_device")
+    if stream is not None:  # the workspace was allocated on the current stream; the launches use it on `stream`
+        ws.record_stream(stream)
+    return scores, kth
+
+
+def radius_counts(stream_t, header, radius, min_neighbors, stream=None):
+    """The radius-rule counts of a packed v2/v3 device stream (spz_amd_radius_counts_device): for every point in input
+    order, the number of other points within `radius` (world units, > 0), saturated at min_neighbors (1..256); int32
+    CUDA tensor.  counts >= min_neighbors is the keep mask of the radius rule."""
+    L = abi.load_library()
+    _check_clean_stream(stream_t, header)
+    if isinstance(radius, bool) or not isinstance(radius, (int, float)) or not math.isfinite(radius) or not radius > 0:
+        raise ValueError(f"radius must be a finite number > 0, got {radius!r}")
+    if isinstance(min_neighbors, bool) or not isinstance(min_neighbors, int) or not 1 <= min_neighbors <= 256:
+        raise ValueError(f"min_neighbors must be an int in 1..256, got {min_neighbors!r}")
+    r2 = C.c_uint64(0)
+    abi.check(L.spz_amd_clean_radius_r2(float(radius), header.fractional_bits, C.byref(r2)), "spz_amd_clean_radius_r2")
+    n, dev = header.num_points, stream_t.device
+    counts = torch.empty(n, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(L.spz_amd_clean_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.spz_amd_radius_counts_device(stream_t.data_ptr(), stream_t.numel(), C.byref(header), r2.value,
+                                            min_neighbors, counts.data_ptr(), ws.data_ptr(), _stream_handle(stream))
+    abi.check(rc, "spz_amd_radius_counts_device")
+    if stream is not None:
+        ws.record_stream(stream)
+    return counts
 
 
 def convert_coordinates(cloud, num_points, sh_degree, from_coord, to_coord, stream=None):
