@@ -482,6 +482,88 @@ int spz_amd_clean_fetch(void *ctx, uint8_t *h_out);
 const uint8_t *spz_amd_clean_device_data(void *ctx);
 void spz_amd_clean_close(void *ctx);
 
+/* ---- render: a forward 3D Gaussian splat rasteriser (spz_render.hip; DESIGN §8 "Render").  The reference has no
+ *      counterpart.  The image of one pinhole view, computed on the device with no display attached.
+ *
+ *      Input.  The cloud as loadSpz(to = coord) returns it: the packed forms decode every Gaussian with the per-field
+ *      decoders of the decode kernel (positions, scales, quaternions, alpha, colour, sh and the coordinate flips), then
+ *      run the code of the float forms, so a stream and its decoded floats give bit-identical images.  Versions 1, 2
+ *      and 3.  The float forms take the GaussianCloud arrays (spz_amd_cloud_in) as they are; coord is ignored there.
+ *      Camera: OpenCV axes (x right, y down, z forward).  world_to_camera: [R | t] row-major 3x4 in the coord frame;
+ *      R orthonormal to within 1e-4 per entry of R R^T - I, det R > 0.  fx, fy > 0; cx, cy finite; width, height
+ *      1..16384; near_plane > 0 (0.2 by default in the C++ and Python layers); background RGB finite; max_sh_degree
+ *      0..3 (the degree used is min(file's, max_sh_degree)); coord 0..8.  A bad one: SPZ_AMD_ERR_INVALID_ARG.
+ *
+ *      Per Gaussian (3DGS forward pass, Kerbl et al. 2023, with gsplat's general principal point).  The arithmetic
+ *      runs in f64 from the f32 inputs; the record holds f32.  p_c = R p + t; z <= near: invisible.
+ *      mean m = (fx x/z + cx - 0.5, fy y/z + cy - 0.5) in pixel-index units.  Sigma = M M^T, M = R_q diag(exp(log
+ *      scale)), R_q of the normalised quaternion (x, y, z, w).  J of x/z clamped to [-(cx/fx + 0.3 W/fx),
+ *      (W - cx)/fx + 0.3 W/fx] (likewise y with cy, fy, H).  Sigma' = J R Sigma R^T J^T, then + 0.3 on the diagonal.
+ *      Antialiased bit (flags bit 0, or the float forms' argument): opacity *= sqrt(max(0, det_before) / det_after).
+ *      det_after <= 0: invisible.  conic = Sigma'^-1 as (A, B, C).  radius = ceil(3 sqrt(mid + sqrt(max(0.1, mid^2 -
+ *      det)))), mid = (a + c) / 2.  Tiles are 16x16: rect x0 = clamp(floor((m_x - radius) / 16), 0, tiles_x), x1 =
+ *      clamp(floor((m_x + radius + 15) / 16), 0, tiles_x), likewise y; empty: invisible.  rgb = max(0, C0 colour + the
+ *      higher sh bands of 3DGS (constants and band order) at normalize(p - c), c = -R^T t, + 0.5).  opacity =
+ *      sigmoid(alpha).  A non-finite mean, conic or radius: invisible.  An invisible Gaussian's record is all zero
+ *      but for depth = +inf.
+ *      Order: within a tile, ascending (f32 depth z, input index).  Blend per pixel (u, v), d = (u - m_x, v - m_y),
+ *      T = 1, C = 0, in that order: power = -0.5 (A dx^2 + C dy^2) - B dx dy, skip if power > 0; a = min(0.99,
+ *      opacity exp(power)), skip if a < 1/255; T' = T (1 - a), stop if T' < 1e-4; C += T a rgb; T = T'.
+ *      Image: height x width x 4 float32, row-major, RGB = C + T background, alpha = 1 - T, not clamped.
+ *      Deterministic: no float atomics; a run repeats its bits.
+ *
+ *      render_check_params (host only, no GPU): the argument checks above.  render_workspace_bytes (host only): device
+ *      memory for the device forms at n Gaussians and max_entries (tile, Gaussian) entries; the prepare step touches
+ *      only the first render_workspace_bytes(n, 0) bytes, so that prefix may be copied to the front of a larger one.
+ *      prepare_packed_device / prepare_cloud_device: decode + preprocess (records, tile counts, depth keys), the depth
+ *      order (spz_amd_argsort_f32_device, stable) and the scan of the tile counts in that order; *d_total (device
+ *      memory, uint64) = the number of entries; d_records (device memory, may be NULL) gets the n records in input
+ *      order.  render_finish_device: with the same n, params and workspace, and max_entries <= 2^31 - 1: the entries in
+ *      depth order, their stable radix sort by tile id, the tile ranges and the blend into d_image (device memory,
+ *      height x width x 4 floats).  *d_status (device memory, uint32) = 0, or 1 when the total is above max_entries:
+ *      then nothing is written to d_image.  All enqueue on hip_stream and do not synchronise.
+ *      The host forms take a stream already in device memory (render_host) or a cloud in host memory
+ *      (render_cloud_host), run on `device` on a stream of their own, read the total back once, size their own
+ *      workspace and block.  A total above 2^31 - 1: SPZ_AMD_ERR_CAPACITY.  h_rgba: height x width x 4 floats;
+ *      *h_entries (may be NULL): the total; h_ms (may be NULL): [0] wall-clock milliseconds of the preprocess (with
+ *      the depth order and the scan), [1] of the tile entries and their sort, [2] of the blend. */
+typedef struct {
+  float world_to_camera[12];
+  float fx, fy, cx, cy;
+  uint32_t width, height;
+  float near_plane;
+  float background[3];
+  int32_t max_sh_degree;
+  int32_t coord;
+} spz_amd_render_params;
+
+/* One preprocessed Gaussian (48 bytes): rect = tile x0, y0, x1, y1 (half-open). */
+typedef struct {
+  float mean[2];
+  float conic[3];
+  float opacity;
+  float rgb[3];
+  float depth;
+  uint16_t rect[4];
+} spz_amd_render_record;
+
+int spz_amd_render_check_params(const spz_amd_render_params *params);
+uint64_t spz_amd_render_workspace_bytes(uint64_t num_points, uint64_t max_entries);
+int spz_amd_render_prepare_packed_device(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr,
+                                         const spz_amd_render_params *params, uint64_t *d_total,
+                                         spz_amd_render_record *d_records, void *d_workspace, void *hip_stream);
+int spz_amd_render_prepare_cloud_device(const spz_amd_cloud_in *d_cloud, uint64_t num_points, int sh_degree,
+                                        int antialiased, const spz_amd_render_params *params, uint64_t *d_total,
+                                        spz_amd_render_record *d_records, void *d_workspace, void *hip_stream);
+int spz_amd_render_finish_device(uint64_t num_points, const spz_amd_render_params *params, uint64_t max_entries,
+                                 float *d_image, uint32_t *d_status, void *d_workspace, void *hip_stream);
+int spz_amd_render_host(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr,
+                        const spz_amd_render_params *params, int device, float *h_rgba, uint64_t *h_entries,
+                        float *h_ms);
+int spz_amd_render_cloud_host(const spz_amd_cloud_in *h_cloud, uint64_t num_points, int sh_degree, int antialiased,
+                              const spz_amd_render_params *params, int device, float *h_rgba, uint64_t *h_entries,
+                              float *h_ms);
+
 /* ---- device buffers for a resident cloud, placed for speed (spz_place.hip).  Whether an sh3 decode runs
  *      at 0.46 ms or at 0.55 ms is decided by whether the sh float array shares a physical region of HBM with the other
  *      arrays of the launch; that cannot be asked for, but it shows in one launch.  alloc: the five small arrays (and a

@@ -394,6 +394,33 @@ bool cleanSpz(const uint8_t *data, int32_t size, const CleanOptions &options, st
 bool cleanSpz(const std::string &inputFilename, const std::string &outputFilename, const CleanOptions &options,
               int64_t *kept = nullptr, std::vector<uint8_t> *keepMask = nullptr, std::vector<double> *scores = nullptr,
               double *threshold = nullptr);
+// Render (DESIGN §8 "Render"): the image of one pinhole view on the device (include/spz_amd.h "render" states the
+// contract).  worldToCamera: [R | t] row-major, OpenCV axes (x right, y down, z forward), in the `coord` frame: the file
+// is rendered as loadSpz(to = coord) returns it (renderCloud: the cloud as it is; coord is ignored).  *rgba: height x
+// width x 4 floats, RGB + alpha, not clamped.  *entries (may be NULL): the (tile, Gaussian) entry count.  false + one
+// "[SPZ ERROR] renderSpz: …" line on a bad argument (lastDeviceStatus() = SPZ_AMD_ERR_INVALID_ARG), an input that does
+// not load, or a device failure.  renderCloud uploads the cloud and renders it on the device SPZ_AMD_DEVICE names
+// (default 0), like the other host-memory entry points.  SPZ_AMD_RENDER_TIMING=1 prints the stages' times to stderr.
+struct RenderOptions {
+  std::array<float, 12> worldToCamera = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  float fx = 0.0f, fy = 0.0f, cx = 0.0f, cy = 0.0f;
+  int width = 0, height = 0;
+  float nearPlane = 0.2f;
+  std::array<float, 3> background = {0.0f, 0.0f, 0.0f};
+  int maxShDegree = 3;
+  CoordinateSystem coord = CoordinateSystem::UNSPECIFIED;
+};
+bool renderSpz(const std::string &filename, const RenderOptions &options, std::vector<float> *rgba,
+               int64_t *entries = nullptr);
+bool renderSpz(const uint8_t *data, int32_t size, const RenderOptions &options, std::vector<float> *rgba,
+               int64_t *entries = nullptr);
+bool renderCloud(const GaussianCloud &g, const RenderOptions &options, std::vector<float> *rgba,
+                 int64_t *entries = nullptr);
+// The worldToCamera of a camera at `eye` looking at `target`: z = normalize(target - eye), x = normalize(z x up),
+// y = z x x, so that `up` maps to -y (up on the screen).  std::invalid_argument when eye == target, up is zero or
+// parallel to the view direction, or a value is not finite.
+std::array<float, 12> lookAt(const std::array<float, 3> &eye, const std::array<float, 3> &target,
+                             const std::array<float, 3> &up);
 // Status (spz_amd.h codes) of the last device call made by this thread; 0 = ok.
 int lastDeviceStatus();
 void setLastDeviceStatus(int status);

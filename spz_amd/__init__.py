@@ -10,6 +10,7 @@ Layout:
   csrc/spz_sort.hip     stable device radix argsort, Morton order of the stored positions, chunk bounds (sortSpz)
   csrc/spz_decimate.hip one point per occupied octree cell by moment matching, over the Morton-sorted stream (decimateSpz)
   csrc/spz_clean.hip    exact k-NN scores and radius counts over the Morton-sorted positions, floater removal (cleanSpz)
+  csrc/spz_render.hip   a tiled 3D Gaussian splat rasteriser: preprocess, depth and tile order, per-tile blend (renderSpz)
   csrc/spz_abi.hip      the C ABI (include/spz_amd.h) over them: device-pointer entry points
   csrc/spz_hostpath.hip host-pointer entry points: device workspace + chunked H2D/kernel/D2H pipeline
   csrc/spz_exchange.hip multi-GPU exchange: native RCCL gatherv/scatterv, IPC-mapped root stream

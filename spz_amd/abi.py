@@ -74,6 +74,9 @@ EXPORTS = (
     "spz_amd_clean_workspace_bytes", "spz_amd_clean_radius_r2", "spz_amd_knn_scores_device",
     "spz_amd_radius_counts_device", "spz_amd_clean_open", "spz_amd_clean_fetch", "spz_amd_clean_device_data",
     "spz_amd_clean_close",
+    "spz_amd_render_check_params", "spz_amd_render_workspace_bytes", "spz_amd_render_prepare_packed_device",
+    "spz_amd_render_prepare_cloud_device", "spz_amd_render_finish_device", "spz_amd_render_host",
+    "spz_amd_render_cloud_host",
 )
 
 RCCL_UNIQUE_ID_BYTES = 128
@@ -100,6 +103,16 @@ class Layout(C.Structure):
 class CloudPtrs(C.Structure):
     """spz_amd_cloud_in / spz_amd_cloud_out (same layout: six pointers)."""
     _fields_ = [(k, C.c_void_p) for k in ("positions", "scales", "rotations", "alphas", "colors", "sh")]
+
+
+class RenderParams(C.Structure):
+    """spz_amd_render_params: one pinhole view (OpenCV axes; include/spz_amd.h "render")."""
+    _fields_ = [("world_to_camera", C.c_float * 12), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("width", C.c_uint32), ("height", C.c_uint32), ("near_plane", C.c_float),
+                ("background", C.c_float * 3), ("max_sh_degree", C.c_int32), ("coord", C.c_int32)]
+
+
+RENDER_RECORD_BYTES = 48
 
 
 class CloudBuffers(C.Structure):
@@ -391,6 +404,23 @@ def bind(L):
     L.spz_amd_clean_device_data.argtypes = [vp]
     L.spz_amd_clean_close.restype = None
     L.spz_amd_clean_close.argtypes = [vp]
+    L.spz_amd_render_check_params.restype = i32
+    L.spz_amd_render_check_params.argtypes = [C.POINTER(RenderParams)]
+    L.spz_amd_render_workspace_bytes.restype = u64
+    L.spz_amd_render_workspace_bytes.argtypes = [u64, u64]
+    L.spz_amd_render_prepare_packed_device.restype = i32
+    L.spz_amd_render_prepare_packed_device.argtypes = [vp, sz, C.POINTER(Header), C.POINTER(RenderParams), vp, vp, vp,
+                                                       vp]
+    L.spz_amd_render_prepare_cloud_device.restype = i32
+    L.spz_amd_render_prepare_cloud_device.argtypes = [C.POINTER(CloudPtrs), u64, i32, i32, C.POINTER(RenderParams), vp,
+                                                      vp, vp, vp]
+    L.spz_amd_render_finish_device.restype = i32
+    L.spz_amd_render_finish_device.argtypes = [u64, C.POINTER(RenderParams), u64, vp, vp, vp, vp]
+    L.spz_amd_render_host.restype = i32
+    L.spz_amd_render_host.argtypes = [vp, sz, C.POINTER(Header), C.POINTER(RenderParams), i32, vp, C.POINTER(u64), vp]
+    L.spz_amd_render_cloud_host.restype = i32
+    L.spz_amd_render_cloud_host.argtypes = [C.POINTER(CloudPtrs), u64, i32, i32, C.POINTER(RenderParams), i32, vp,
+                                            C.POINTER(u64), vp]
     L.spz_amd_zlib_encode_blocks.restype = i32
     L.spz_amd_zlib_encode_blocks.argtypes = [vp, vp, u32, u32, vp, vp, vp, u64, u64, vp, vp]
     return L
@@ -451,6 +481,36 @@ def transform_params(rotation=None, translation=None, scale=1.0, coord=UNSPECIFI
     if rc != OK:
         raise ValueError(f"invalid transform: rotation={rotation} translation={translation} scale={scale} coord={coord}")
     return out
+
+
+def render_params(world_to_camera, fx, fy, cx, cy, width, height, near=0.2, background=(0.0, 0.0, 0.0),
+                  max_sh_degree=3, coord=UNSPECIFIED):
+    """A RenderParams, checked on the host (spz_amd_render_check_params): ValueError on a bad camera or size."""
+    import numpy as np
+    m = np.asarray(world_to_camera, dtype=np.float64)
+    if m.shape != (3, 4):
+        raise ValueError(f"world_to_camera must be 3x4, got shape {m.shape}")
+    bg = np.asarray(background, dtype=np.float64).reshape(-1)
+    if bg.size != 3:
+        raise ValueError("background must have three values")
+    for name, v in (("width", width), ("height", height), ("max_sh_degree", max_sh_degree), ("coord", coord)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{name} must be an int, got {v!r}")
+    if not (1 <= width <= 16384 and 1 <= height <= 16384):
+        raise ValueError(f"width and height must be in 1..16384, got {width} x {height}")
+    p = RenderParams()
+    for k, v in enumerate(m.reshape(-1)):
+        p.world_to_camera[k] = float(v)
+    p.fx, p.fy, p.cx, p.cy = float(fx), float(fy), float(cx), float(cy)
+    p.width, p.height = width, height
+    p.near_plane = float(near)
+    for k in range(3):
+        p.background[k] = float(bg[k])
+    p.max_sh_degree, p.coord = max_sh_degree, coord
+    if load_library().spz_amd_render_check_params(C.byref(p)) != OK:
+        raise ValueError("bad render parameters: world_to_camera must be [R | t] with R a rotation (to 1e-4), fx, fy > 0, "
+                         "near > 0, everything finite, max_sh_degree 0..3, coord 0..8")
+    return p
 
 
 def merge_resolve(headers, sh_degree=None, fractional_bits=None, antialiased=None):

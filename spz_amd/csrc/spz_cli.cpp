@@ -1,13 +1,16 @@
 // spz_cli.cpp — the three command-line tools of the reference (cli_tools/src/*.cpp) over the
 // MI355X drop-in layer: ply_to_spz, spz_to_ply, spz_info; and spz_filter (spz::filterSpz),
 // spz_transform (spz::transformSpz), spz_merge (spz::mergeSpz), spz_sort (spz::sortSpz), spz_decimate
-// (spz::decimateSpz) and spz_clean (spz::cleanSpz), which have no counterpart in the reference.  One binary, dispatched
-// on argv[0] (the Makefile installs it under the nine names) or on a first argument naming the tool.
+// (spz::decimateSpz), spz_clean (spz::cleanSpz) and spz_render (spz::renderSpz), which have no counterpart in the
+// reference.  One binary, dispatched on argv[0] (the Makefile installs it under the ten names) or on a first argument
+// naming the tool.
 // Same behaviour as the reference mains: default (UNSPECIFIED) pack/unpack options, exit code 0
 // once the arguments are there (the reference ignores the save/load results), usage -> 1.
-// spz_filter, spz_transform, spz_merge, spz_sort, spz_decimate and spz_clean exit 1 when the filter / transform / merge /
-// sort / decimation / clean fails as well.
+// spz_filter, spz_transform, spz_merge, spz_sort, spz_decimate, spz_clean and spz_render exit 1 when the filter /
+// transform / merge / sort / decimation / clean / render fails as well.
 #include <algorithm>
+#include <stdexcept>
+#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -323,6 +326,154 @@ int spzClean(int argc, char **argv) {
   return spz::cleanSpz(std::string(argv[1]), std::string(argv[2]), o) ? 0 : 1;
 }
 
+const char *kRenderUsage =
+    "Usage: spz_render <in.spz> <out.ppm|out.pfm> --size W H (--fov-y DEG | --intrinsics fx fy cx cy) --eye x y z "
+    "--target x y z [--up x y z] [--coord RUB|RDF|LUF|RUF|LDB|RDB|LUB|LDF|UNSPECIFIED] [--background r g b] "
+    "[--sh-degree D] [--near N]";
+
+bool endsWith(const std::string &s, const char *suffix) {
+  const size_t n = std::strlen(suffix);
+  return s.size() >= n && s.compare(s.size() - n, n, suffix) == 0;
+}
+
+// PPM: clamp to [0, 1], round(255 v), rows top to bottom.  PFM: float RGB, little-endian, rows bottom to top.
+bool writeImage(const std::string &path, const std::vector<float> &rgba, int w, int h, bool pfm) {
+  std::ofstream out(path, std::ios::binary);
+  if (!out) return false;
+  if (pfm) {
+    out << "PF\n" << w << " " << h << "\n-1.0\n";
+    std::vector<float> row(static_cast<size_t>(w) * 3);
+    for (int y = h - 1; y >= 0; --y) {
+      for (int x = 0; x < w; ++x) {
+        for (int c = 0; c < 3; ++c) row[x * 3 + c] = rgba[(static_cast<size_t>(y) * w + x) * 4 + c];
+      }
+      out.write(reinterpret_cast<const char *>(row.data()), static_cast<std::streamsize>(row.size() * sizeof(float)));
+    }
+  } else {
+    out << "P6\n" << w << " " << h << "\n255\n";
+    std::vector<unsigned char> row(static_cast<size_t>(w) * 3);
+    for (int y = 0; y < h; ++y) {
+      for (int x = 0; x < w; ++x) {
+        for (int c = 0; c < 3; ++c) {
+          float v = rgba[(static_cast<size_t>(y) * w + x) * 4 + c];
+          v = std::isnan(v) ? 0.0f : std::min(1.0f, std::max(0.0f, v));
+          row[x * 3 + c] = static_cast<unsigned char>(std::lround(255.0f * v));
+        }
+      }
+      out.write(reinterpret_cast<const char *>(row.data()), static_cast<std::streamsize>(row.size()));
+    }
+  }
+  return static_cast<bool>(out);
+}
+
+int spzRender(int argc, char **argv) {
+  auto usage = [] {
+    std::cerr << kRenderUsage << std::endl;
+    return 1;
+  };
+  if (argc < 3 || argv[1][0] == '-' || argv[2][0] == '-') return usage();
+  const std::string outPath = argv[2];
+  const bool pfm = endsWith(outPath, ".pfm");
+  if (!pfm && !endsWith(outPath, ".ppm")) return usage();
+  spz::RenderOptions o;
+  bool hasSize = false, hasFov = false, hasIntr = false, hasEye = false, hasTarget = false, hasUp = false;
+  bool hasBackground = false, hasNear = false, hasShDegree = false, hasCoord = false;
+  float fovY = 0.0f, intr[4] = {0, 0, 0, 0};
+  std::array<float, 3> eye{}, target{}, up{};
+  auto floats = [&](int &i, int k, float *dst) {
+    if (i + k >= argc) return false;
+    for (int j = 0; j < k; ++j) {
+      if (!parseFloat(argv[i + 1 + j], &dst[j]) || !std::isfinite(dst[j])) return false;
+    }
+    i += k;
+    return true;
+  };
+  for (int i = 3; i < argc; ++i) {
+    const std::string a = argv[i];
+    if (a == "--size" && !hasSize && i + 2 < argc) {
+      int v[2];
+      for (int k = 0; k < 2; ++k) {
+        const std::string t = argv[i + 1 + k];
+        if (t.empty() || t.size() > 5 || t.find_first_not_of("0123456789") != std::string::npos) return usage();
+        v[k] = std::atoi(t.c_str());
+        if (v[k] < 1 || v[k] > 16384) return usage();
+      }
+      o.width = v[0];
+      o.height = v[1];
+      i += 2;
+      hasSize = true;
+    } else if (a == "--fov-y" && !hasFov && !hasIntr) {
+      if (!floats(i, 1, &fovY) || !(fovY > 0.0f && fovY < 180.0f)) return usage();
+      hasFov = true;
+    } else if (a == "--intrinsics" && !hasFov && !hasIntr) {
+      if (!floats(i, 4, intr)) return usage();
+      hasIntr = true;
+    } else if (a == "--eye" && !hasEye) {
+      if (!floats(i, 3, eye.data())) return usage();
+      hasEye = true;
+    } else if (a == "--target" && !hasTarget) {
+      if (!floats(i, 3, target.data())) return usage();
+      hasTarget = true;
+    } else if (a == "--up" && !hasUp) {
+      if (!floats(i, 3, up.data())) return usage();
+      hasUp = true;
+    } else if (a == "--background" && !hasBackground) {
+      if (!floats(i, 3, o.background.data())) return usage();
+      hasBackground = true;
+    } else if (a == "--near" && !hasNear) {
+      if (!floats(i, 1, &o.nearPlane) || !(o.nearPlane > 0.0f)) return usage();
+      hasNear = true;
+    } else if (a == "--sh-degree" && !hasShDegree && i + 1 < argc) {
+      const std::string t = argv[++i];
+      if (t.size() != 1 || t[0] < '0' || t[0] > '3') return usage();
+      o.maxShDegree = t[0] - '0';
+      hasShDegree = true;
+    } else if (a == "--coord" && !hasCoord && i + 1 < argc) {
+      hasCoord = true;
+      static const char *names[] = {"UNSPECIFIED", "LDB", "RDB", "LUB", "RUB", "LDF", "RDF", "LUF", "RUF"};
+      const std::string c = argv[++i];
+      int found = -1;
+      for (int k = 0; k < 9; ++k) {
+        if (c == names[k]) found = k;
+      }
+      if (found < 0) return usage();
+      o.coord = static_cast<spz::CoordinateSystem>(found);
+    } else {
+      return usage();
+    }
+  }
+  if (!hasSize || (!hasFov && !hasIntr) || !hasEye || !hasTarget) return usage();
+  if (hasFov) {
+    o.fy = static_cast<float>(0.5 * o.height / std::tan(0.5 * fovY * 3.14159265358979323846 / 180.0));
+    o.fx = o.fy;
+    o.cx = 0.5f * static_cast<float>(o.width);
+    o.cy = 0.5f * static_cast<float>(o.height);
+  } else {
+    o.fx = intr[0];
+    o.fy = intr[1];
+    o.cx = intr[2];
+    o.cy = intr[3];
+    if (!(o.fx > 0.0f) || !(o.fy > 0.0f)) return usage();
+  }
+  if (!hasUp) {  // the frame's U axis (UNSPECIFIED: the stored RUB frame)
+    const int c = static_cast<int>(o.coord) == 0 ? 4 : static_cast<int>(o.coord);
+    const bool yDown = (((c - 1) >> 1) & 1) == 0;  // LDB, RDB, LDF, RDF
+    up = {0.0f, yDown ? -1.0f : 1.0f, 0.0f};
+  }
+  try {
+    o.worldToCamera = spz::lookAt(eye, target, up);
+  } catch (const std::invalid_argument &) {
+    return usage();
+  }
+  std::vector<float> rgba;
+  if (!spz::renderSpz(std::string(argv[1]), o, &rgba)) return 1;
+  if (!writeImage(outPath, rgba, o.width, o.height, pfm)) {
+    std::cerr << "spz_render: unable to write " << outPath << std::endl;
+    return 1;
+  }
+  return 0;
+}
+
 int dispatch(const std::string &tool, int argc, char **argv) {
   if (tool == "ply_to_spz") return plyToSpz(argc, argv);
   if (tool == "spz_to_ply") return spzToPly(argc, argv);
@@ -333,6 +484,7 @@ int dispatch(const std::string &tool, int argc, char **argv) {
   if (tool == "spz_sort") return spzSort(argc, argv);
   if (tool == "spz_decimate") return spzDecimate(argc, argv);
   if (tool == "spz_clean") return spzClean(argc, argv);
+  if (tool == "spz_render") return spzRender(argc, argv);
   return -1;
 }
 
@@ -349,7 +501,7 @@ int main(int argc, char **argv) {
       rc = dispatch(argv[1], argc - 1, argv + 1);
       if (rc >= 0) return rc;
     }
-    std::cerr << "Usage: spz_tool {ply_to_spz|spz_to_ply|spz_info|spz_filter|spz_transform|spz_merge|spz_sort|spz_decimate|spz_clean} <args...>" << std::endl;
+    std::cerr << "Usage: spz_tool {ply_to_spz|spz_to_ply|spz_info|spz_filter|spz_transform|spz_merge|spz_sort|spz_decimate|spz_clean|spz_render} <args...>" << std::endl;
     return 1;
   } catch (const std::exception &e) {
     std::cerr << "Error: " << e.what() << std::endl;

@@ -25,6 +25,7 @@
 #include <istream>
 #include <mutex>
 #include <ostream>
+#include <stdexcept>
 #include <thread>
 
 #include "spz_amd.h"
@@ -2451,6 +2452,150 @@ bool cleanSpz(const std::string &inputFilename, const std::string &outputFilenam
   if (scores) scores->swap(sc);
   if (threshold) *threshold = thr;
   return true;
+}
+
+// ---- render ------------------------------------------------------------------------------------------------------
+namespace {
+bool renderRejected(int status, const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  char msg[256];
+  std::vsnprintf(msg, sizeof(msg), fmt, ap);
+  va_end(ap);
+  logLine("[SPZ ERROR] renderSpz: %s", msg);
+  g_last_status = status;
+  return false;
+}
+
+bool renderParams(const RenderOptions &o, spz_amd_render_params *p) {
+  *p = spz_amd_render_params{};
+  if (o.width < 1 || o.width > 16384 || o.height < 1 || o.height > 16384) {
+    return renderRejected(SPZ_AMD_ERR_INVALID_ARG, "image size %d x %d is outside 1..16384", o.width, o.height);
+  }
+  for (int k = 0; k < 12; ++k) p->world_to_camera[k] = o.worldToCamera[k];
+  p->fx = o.fx;
+  p->fy = o.fy;
+  p->cx = o.cx;
+  p->cy = o.cy;
+  p->width = static_cast<uint32_t>(o.width);
+  p->height = static_cast<uint32_t>(o.height);
+  p->near_plane = o.nearPlane;
+  for (int k = 0; k < 3; ++k) p->background[k] = o.background[k];
+  p->max_sh_degree = o.maxShDegree;
+  p->coord = static_cast<int32_t>(o.coord);
+  if (spz_amd_render_check_params(p) != SPZ_AMD_OK) {
+    return renderRejected(SPZ_AMD_ERR_INVALID_ARG,
+                          "bad camera: R must be a rotation (to 1e-4), fx, fy > 0, nearPlane > 0, values finite, "
+                          "maxShDegree 0..3");
+  }
+  return true;
+}
+
+void renderTiming(const float *ms, uint64_t entries) {
+  if (std::getenv("SPZ_AMD_RENDER_TIMING") == nullptr) return;
+  std::fprintf(stderr, "[renderSpz] preprocess %.3f ms\n[renderSpz] entries    %.3f ms (%llu)\n[renderSpz] blend      %.3f ms\n",
+               ms[0], ms[1], static_cast<unsigned long long>(entries), ms[2]);
+}
+}  // namespace
+
+bool renderSpz(const uint8_t *data, int32_t size, const RenderOptions &o, std::vector<float> *rgba, int64_t *entries) {
+  g_last_status = SPZ_AMD_OK;
+  if (rgba == nullptr) return renderRejected(SPZ_AMD_ERR_INVALID_ARG, "no output vector");
+  spz_amd_render_params p;
+  if (!renderParams(o, &p)) return false;
+  DevicePackedGaussians d = loadSpzPackedDevice(data, size);
+  if (!d.valid()) {
+    if (g_last_status == SPZ_AMD_OK) logLine("[SPZ ERROR] renderSpz: the input is not a readable .spz");
+    return false;
+  }
+  const spz_amd_header hdr = headerOf(d);
+  std::vector<float> img;
+  detail::resizeUninitialized(&img, static_cast<size_t>(o.width) * static_cast<size_t>(o.height) * 4u);
+  uint64_t count = 0;
+  float ms[3] = {0.0f, 0.0f, 0.0f};
+  const int rc = spz_amd_render_host(d.stream, d.streamBytes, &hdr, &p, d.device, img.data(), &count, ms);
+  if (deviceFailed(rc, "renderSpz")) return false;
+  renderTiming(ms, count);
+  rgba->swap(img);
+  if (entries) *entries = static_cast<int64_t>(count);
+  return true;
+}
+
+bool renderSpz(const std::string &filename, const RenderOptions &o, std::vector<float> *rgba, int64_t *entries) {
+  g_last_status = SPZ_AMD_OK;
+  spz_amd_render_params p;
+  if (!renderParams(o, &p)) return false;
+  std::vector<uint8_t> data;
+  if (!readFile(filename, &data, /*log=*/true)) return false;
+  if (data.size() > static_cast<size_t>(INT32_MAX)) {
+    return renderRejected(SPZ_AMD_ERR_INVALID_ARG, "%s is larger than 2 GiB", filename.c_str());
+  }
+  return renderSpz(data.data(), static_cast<int32_t>(data.size()), o, rgba, entries);
+}
+
+bool renderCloud(const GaussianCloud &g, const RenderOptions &o, std::vector<float> *rgba, int64_t *entries) {
+  g_last_status = SPZ_AMD_OK;
+  if (rgba == nullptr) return renderRejected(SPZ_AMD_ERR_INVALID_ARG, "no output vector");
+  spz_amd_render_params p;
+  if (!renderParams(o, &p)) return false;
+  const size_t n = g.numPoints < 0 ? 0 : static_cast<size_t>(g.numPoints);
+  const int sd = g.shDegree == 0 ? 0 : g.shDegree == 1 ? 3 : g.shDegree == 2 ? 8 : g.shDegree == 3 ? 15 : -1;
+  if (g.numPoints < 0 || sd < 0 || g.positions.size() != n * 3 || g.scales.size() != n * 3 ||
+      g.rotations.size() != n * 4 || g.alphas.size() != n || g.colors.size() != n * 3 ||
+      g.sh.size() != n * static_cast<size_t>(sd) * 3) {
+    return renderRejected(SPZ_AMD_ERR_INVALID_ARG, "the cloud's arrays do not match numPoints and shDegree");
+  }
+  spz_amd_cloud_in c = {g.positions.data(), g.scales.data(), g.rotations.data(), g.alphas.data(), g.colors.data(),
+                        sd ? g.sh.data() : nullptr};
+  std::vector<float> img;
+  detail::resizeUninitialized(&img, static_cast<size_t>(o.width) * static_cast<size_t>(o.height) * 4u);
+  uint64_t count = 0;
+  float ms[3] = {0.0f, 0.0f, 0.0f};
+  const int rc =
+      spz_amd_render_cloud_host(&c, n, g.shDegree, g.antialiased ? 1 : 0, &p, deviceIndex(), img.data(), &count, ms);
+  if (deviceFailed(rc, "renderCloud")) return false;
+  renderTiming(ms, count);
+  rgba->swap(img);
+  if (entries) *entries = static_cast<int64_t>(count);
+  return true;
+}
+
+std::array<float, 12> lookAt(const std::array<float, 3> &eye, const std::array<float, 3> &target,
+                             const std::array<float, 3> &up) {
+  double f[3], u[3], e[3];
+  for (int k = 0; k < 3; ++k) {
+    if (!std::isfinite(eye[k]) || !std::isfinite(target[k]) || !std::isfinite(up[k])) {
+      throw std::invalid_argument("lookAt: values must be finite");
+    }
+    e[k] = eye[k];
+    f[k] = static_cast<double>(target[k]) - eye[k];
+    u[k] = up[k];
+  }
+  auto norm = [](double *v) {
+    const double l = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    if (!(l > 0.0)) return false;
+    for (int k = 0; k < 3; ++k) v[k] /= l;
+    return true;
+  };
+  auto cross = [](const double *a, const double *b, double *o) {
+    o[0] = a[1] * b[2] - a[2] * b[1];
+    o[1] = a[2] * b[0] - a[0] * b[2];
+    o[2] = a[0] * b[1] - a[1] * b[0];
+  };
+  if (!norm(f) || !norm(u)) throw std::invalid_argument("lookAt: eye equals target, or up is zero");
+  double x[3], y[3];
+  cross(f, u, x);
+  const double sx = std::sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+  if (!(sx > 1e-6)) throw std::invalid_argument("lookAt: up is parallel to the view direction");
+  norm(x);
+  cross(f, x, y);
+  std::array<float, 12> m;
+  const double *rows[3] = {x, y, f};
+  for (int r = 0; r < 3; ++r) {
+    for (int k = 0; k < 3; ++k) m[r * 4 + k] = static_cast<float>(rows[r][k]);
+    m[r * 4 + 3] = static_cast<float>(-(rows[r][0] * e[0] + rows[r][1] * e[1] + rows[r][2] * e[2]));
+  }
+  return m;
 }
 
 GaussianCloud loadSpz(const std::vector<uint8_t> &data, const UnpackOptions &o) {

@@ -16,6 +16,7 @@
 #include <cmath>
 #include <optional>
 #include <cstring>
+#include <stdexcept>
 #include <sstream>
 #include <memory>
 #include <string>
@@ -90,6 +91,43 @@ void raiseIfDeviceUnusable() {
     throw std::runtime_error(std::string("spz_amd: ") + spz_amd_status_string(st) +
                              " (the SPZ hot path runs on the GPU only)");
   }
+}
+
+// RenderOptions from render_spz / render_cloud's keyword arguments (the camera itself is checked by the C++ layer).
+spz::RenderOptions renderOptions(const py::object &world_to_camera, int width, int height, float fx, float fy, float cx,
+                                 float cy, float near_plane, const py::object &background, int max_sh_degree,
+                                 spz::CoordinateSystem coord) {
+  spz::RenderOptions o;
+  py::array_t<float, py::array::c_style | py::array::forcecast> m(world_to_camera);
+  if (m.ndim() != 2 || m.shape(0) != 3 || m.shape(1) != 4) throw py::value_error("world_to_camera must be 3x4");
+  for (int k = 0; k < 12; ++k) o.worldToCamera[k] = m.data()[k];
+  py::array_t<float, py::array::c_style | py::array::forcecast> bg(background);
+  if (bg.size() != 3) throw py::value_error("background must have three values");
+  for (int k = 0; k < 3; ++k) o.background[k] = bg.data()[k];
+  o.width = width;
+  o.height = height;
+  o.fx = fx;
+  o.fy = fy;
+  o.cx = cx;
+  o.cy = cy;
+  o.nearPlane = near_plane;
+  o.maxShDegree = max_sh_degree;
+  o.coord = coord;
+  return o;
+}
+
+// The (height, width, 4) array of a render, or the exception of its failure.
+py::object renderedImage(bool ok, const std::vector<float> &img, const spz::RenderOptions &o, const char *what) {
+  if (!ok) {
+    raiseIfDeviceUnusable();
+    if (spz::lastDeviceStatus() == SPZ_AMD_ERR_INVALID_ARG) {
+      throw py::value_error(std::string(what) + ": refused (see the [SPZ ERROR] line)");
+    }
+    throw std::runtime_error(std::string(what) + " failed (see the [SPZ ERROR] line)");
+  }
+  py::array_t<float> out({static_cast<py::ssize_t>(o.height), static_cast<py::ssize_t>(o.width), py::ssize_t(4)});
+  std::memcpy(out.mutable_data(), img.data(), img.size() * sizeof(float));
+  return out;
 }
 
 // filter_spz's arguments as spz::FilterOptions; every problem is a ValueError, raised before any device work.
@@ -661,6 +699,67 @@ PYBIND11_MODULE(spz, m) {
         "quanta, in Morton order; a cell of several points becomes one Gaussian matching their moments.  Exactly one "
         "of level (0..24) and target_points (>= 1: the smallest level with at most that many cells).  Returns (level, "
         "points), plus parents (uint32: the output index of every input point's cell) when return_parents.");
+  m.def("render_spz",
+        [](const py::object &input, const py::object &world_to_camera, int width, int height, float fx, float fy,
+           float cx, float cy, float near_plane, const py::object &background, int max_sh_degree,
+           spz::CoordinateSystem coord) -> py::object {
+          // renderSpz checks the camera before it reads the file: a bad one is a ValueError before any device work
+          const spz::RenderOptions o = renderOptions(world_to_camera, width, height, fx, fy, cx, cy, near_plane, background,
+                                                     max_sh_degree, coord);
+          std::vector<float> img;
+          bool ok;
+          if (py::isinstance<py::bytes>(input)) {
+            const std::string b = input.cast<std::string>();
+            if (b.size() > static_cast<size_t>(INT32_MAX)) throw py::value_error("input is larger than 2 GiB");
+            py::gil_scoped_release release;
+            ok = spz::renderSpz(reinterpret_cast<const uint8_t *>(b.data()), static_cast<int32_t>(b.size()), o, &img);
+          } else {
+            const std::string fn = py::str(input).cast<std::string>();
+            py::gil_scoped_release release;
+            ok = spz::renderSpz(fn, o, &img);
+          }
+          return renderedImage(ok, img, o, "render_spz");
+        },
+        py::arg("input"), py::kw_only(), py::arg("world_to_camera"), py::arg("width"), py::arg("height"), py::arg("fx"),
+        py::arg("fy"), py::arg("cx"), py::arg("cy"), py::arg("near") = 0.2f,
+        py::arg("background") = py::make_tuple(0.0f, 0.0f, 0.0f), py::arg("max_sh_degree") = 3,
+        py::arg("coord") = spz::CoordinateSystem::UNSPECIFIED,
+        "Render one pinhole view of a .spz file (a path or the file's bytes) on the device (spz::renderSpz; the "
+        "contract is in include/spz_amd.h \"render\").  world_to_camera: 3x4 [R | t], OpenCV axes (x right, y down, z "
+        "forward), in the frame `coord` (the file as load_spz(to = coord) returns it).  Returns a (height, width, 4) "
+        "float32 array: RGB + alpha, not clamped.");
+  m.def("render_cloud",
+        [](const spz::GaussianCloud &cloud, const py::object &world_to_camera, int width, int height, float fx, float fy,
+           float cx, float cy, float near_plane, const py::object &background, int max_sh_degree) -> py::object {
+          const spz::RenderOptions o = renderOptions(world_to_camera, width, height, fx, fy, cx, cy, near_plane, background,
+                                                     max_sh_degree, spz::CoordinateSystem::UNSPECIFIED);
+          std::vector<float> img;
+          bool ok;
+          {
+            py::gil_scoped_release release;
+            ok = spz::renderCloud(cloud, o, &img);
+          }
+          return renderedImage(ok, img, o, "render_cloud");
+        },
+        py::arg("cloud"), py::kw_only(), py::arg("world_to_camera"), py::arg("width"), py::arg("height"), py::arg("fx"),
+        py::arg("fy"), py::arg("cx"), py::arg("cy"), py::arg("near") = 0.2f,
+        py::arg("background") = py::make_tuple(0.0f, 0.0f, 0.0f), py::arg("max_sh_degree") = 3,
+        "Render one pinhole view of a GaussianCloud in host memory on the device (spz::renderCloud): the cloud is "
+        "uploaded and rendered as it is, in the frame of world_to_camera.  Returns a (height, width, 4) float32 array.");
+  m.def("look_at",
+        [](const std::array<float, 3> &eye, const std::array<float, 3> &target, const std::array<float, 3> &up) {
+          std::array<float, 12> r;
+          try {
+            r = spz::lookAt(eye, target, up);
+          } catch (const std::invalid_argument &e) {
+            throw py::value_error(e.what());
+          }
+          py::array_t<float> out({py::ssize_t(3), py::ssize_t(4)});
+          std::memcpy(out.mutable_data(), r.data(), sizeof(r));
+          return out;
+        },
+        py::arg("eye"), py::arg("target"), py::arg("up"),
+        "The 3x4 world_to_camera (float32) of a camera at eye looking at target, OpenCV axes: up maps to -y.");
   m.def("clean_spz",
         [](const std::string &input, const std::string &output, const py::object &k, const py::object &std_ratio,
            const py::object &radius, const py::object &min_neighbors, const py::object &return_details) -> py::object {

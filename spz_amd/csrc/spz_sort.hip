@@ -20,6 +20,7 @@
 
 #include "spz_amd.h"
 #include "spz_common.hpp"
+#include "spz_sort_internal.hpp"
 
 namespace spz_amd_detail {
 namespace {
@@ -300,16 +301,7 @@ __global__ __launch_bounds__(kBoundsBlock) void spz_chunk_bounds_kernel(const ui
   }
 }
 
-}  // namespace spz_amd_detail
-
-namespace {
-
-using namespace spz_amd_detail;
-
-struct SortLayout {
-  uint64_t tiles, idx_off, planes_off[2][3], counts_off, totals_off, bytes;
-};
-
+// The workspace of one sort of n keys, and the digit passes over it (spz_sort_internal.hpp).
 SortLayout sort_layout(uint64_t n) {
   SortLayout w;
   w.tiles = (n + kSortTile - 1) / kSortTile;
@@ -331,17 +323,6 @@ SortLayout sort_layout(uint64_t n) {
   return w;
 }
 
-int check_stream(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, spz_amd_layout *lay) {
-  if (d_stream == nullptr || hdr == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
-  if (hdr->version < 1 || hdr->version > 3) return SPZ_AMD_ERR_VERSION;
-  if (hdr->sh_degree > 3) return SPZ_AMD_ERR_SH_DEGREE;
-  int rc = spz_amd_stream_layout(hdr->num_points, hdr->sh_degree, (int)hdr->version, lay);
-  if (rc != SPZ_AMD_OK) return rc;
-  if (size < lay->total_bytes) return SPZ_AMD_ERR_SHORT_STREAM;
-  return SPZ_AMD_OK;
-}
-
-// The digit passes over planes already written into set 0 of the workspace; the order lands in d_order.
 int radix_passes(uint32_t n, uint32_t digits, uint32_t *d_order, uint8_t *ws, const SortLayout &wl, hipStream_t st) {
   uint32_t *planes[2][3];
   for (int s = 0; s < 2; ++s) {
@@ -380,6 +361,22 @@ int radix_passes(uint32_t n, uint32_t digits, uint32_t *d_order, uint8_t *ws, co
     hipLaunchKernelGGL(spz_radix_scatter_kernel, dim3(tiles), dim3(kSortBlock), 0, st, p);
     SPZ_HIP_TRY(hipGetLastError());
   }
+  return SPZ_AMD_OK;
+}
+
+}  // namespace spz_amd_detail
+
+namespace {
+
+using namespace spz_amd_detail;
+
+int check_stream(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, spz_amd_layout *lay) {
+  if (d_stream == nullptr || hdr == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
+  if (hdr->version < 1 || hdr->version > 3) return SPZ_AMD_ERR_VERSION;
+  if (hdr->sh_degree > 3) return SPZ_AMD_ERR_SH_DEGREE;
+  int rc = spz_amd_stream_layout(hdr->num_points, hdr->sh_degree, (int)hdr->version, lay);
+  if (rc != SPZ_AMD_OK) return rc;
+  if (size < lay->total_bytes) return SPZ_AMD_ERR_SHORT_STREAM;
   return SPZ_AMD_OK;
 }
 

@@ -582,6 +582,148 @@ def radius_counts(stream_t, header, radius, min_neighbors, stream=None):
     return counts
 
 
+def _cloud_render_args(cloud, num_points, sh_degree):
+    if int(sh_degree) not in SH_DIM:
+        raise ValueError(f"sh_degree must be 0..3, got {sh_degree}")
+    dev = cloud["positions"].device
+    return _ptrs(cloud, sh_degree, num_points, dev), dev
+
+
+def _render_prepare(L, source, params, total, records, ws, st):
+    """Enqueue the prepare step of a packed ("packed", stream_t, header) or float ("cloud", ptrs, n, sh_degree,
+    antialiased) source into ws on the torch stream st."""
+    rec = records.data_ptr() if records is not None else None
+    if source[0] == "packed":
+        _, stream_t, header = source
+        rc = L.spz_amd_render_prepare_packed_device(stream_t.data_ptr(), stream_t.numel(), C.byref(header),
+                                                    C.byref(params), total.data_ptr(), rec, ws.data_ptr(),
+                                                    C.c_void_p(st.cuda_stream))
+    else:
+        _, ptrs, n, sh_degree, aa = source
+        rc = L.spz_amd_render_prepare_cloud_device(C.byref(ptrs), n, sh_degree, 1 if aa else 0, C.byref(params),
+                                                   total.data_ptr(), rec, ws.data_ptr(), C.c_void_p(st.cuda_stream))
+    abi.check(rc, "spz_amd_render_prepare")
+
+
+def _on_stream(dev, stream):
+    """The stream the render runs on: `stream`, made to wait for the current stream first (which produced the inputs),
+    or the current stream.  Every allocation, copy, launch and read-back of a render is enqueued on it."""
+    cur = torch.cuda.current_stream(dev)
+    if stream is None or stream == cur:
+        return cur
+    stream.wait_stream(cur)
+    return stream
+
+
+def _aligned_view(t, nbytes):
+    """The nbytes of uint8 tensor t from its first 256-aligned byte: where the C ABI puts the workspace's base."""
+    off = (-t.data_ptr()) % 256
+    return t[off: off + nbytes]
+
+
+def _render(source, n, params, dev, max_entries, out, return_info, stream):
+    L = abi.load_library()
+    if not isinstance(params, abi.RenderParams):
+        raise ValueError("params must be an abi.RenderParams (abi.render_params)")
+    abi.check(L.spz_amd_render_check_params(C.byref(params)), "spz_amd_render_check_params")
+    if max_entries is not None and (isinstance(max_entries, bool) or not isinstance(max_entries, int)
+                                    or not 0 <= max_entries <= 0x7fffffff):
+        raise ValueError(f"max_entries must be an int in 0..2^31-1, got {max_entries!r}")
+    h, w = params.height, params.width
+    if out is not None and (out.dtype != torch.float32 or out.device != dev or not out.is_contiguous()
+                            or tuple(out.shape) != (h, w, 4)):
+        raise ValueError(f"out must be a contiguous float32 tensor of shape ({h}, {w}, 4) on {dev}")
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        with torch.cuda.stream(st):
+            if out is None:
+                out = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
+            # the prepare step always writes the total, the finish step always writes the status
+            total = torch.empty(1, dtype=torch.int64, device=dev)
+            status = torch.empty(1, dtype=torch.int32, device=dev)
+            if max_entries is None:
+                # the prepare step writes only the first workspace_bytes(n, 0) - 256 bytes from the workspace's aligned
+                # base: prepare, read the total, then move that prefix to the front of a workspace with room for the
+                # entries
+                ws0_bytes = int(L.spz_amd_render_workspace_bytes(n, 0))
+                ws0 = torch.empty(ws0_bytes, dtype=torch.uint8, device=dev)
+                _render_prepare(L, source, params, total, None, ws0, st)
+                m = int(total.cpu()[0])  # on st: waits for the prepare step
+                if m > 0x7fffffff:
+                    raise RuntimeError(f"{m} tile entries is above the sort's limit of 2^31 - 1")
+                ws = torch.empty(int(L.spz_amd_render_workspace_bytes(n, m)), dtype=torch.uint8, device=dev)
+                prefix = ws0_bytes - 256
+                _aligned_view(ws, prefix).copy_(_aligned_view(ws0, prefix))
+            else:
+                m = max_entries
+                ws = torch.empty(int(L.spz_amd_render_workspace_bytes(n, m)), dtype=torch.uint8, device=dev)
+                _render_prepare(L, source, params, total, None, ws, st)
+            rc = L.spz_amd_render_finish_device(n, C.byref(params), m, out.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                                                C.c_void_p(st.cuda_stream))
+    abi.check(rc, "spz_amd_render_finish_device")
+    return (out, total, status) if return_info else out
+
+
+def render(cloud, num_points, sh_degree, params, antialiased=False, max_entries=None, out=None, return_info=False,
+           stream=None):
+    """The image of a float cloud on the device (spz_amd_render_prepare_cloud_device + finish; the contract is in
+    include/spz_amd.h "render"): a (height, width, 4) float32 CUDA tensor, RGB + alpha.  cloud: device tensors keyed like
+    the GaussianCloud fields, already in the frame of the camera `params` (abi.render_params; its coord is ignored).
+    max_entries None: the prepare step's total sizes the workspace (one value is read back); an int: the workspace is
+    sized for it, and when the total is above it nothing is written to the image and the status word is 1.
+    return_info: (image, total (int64 tensor [1]), status (int32 tensor [1])).  stream: a torch stream that first waits
+    for the current one, then takes every allocation, copy, launch and read-back of the render; the results belong to it
+    (synchronise with it before using them on another stream)."""
+    ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
+    return _render(("cloud", ptrs, num_points, int(sh_degree), antialiased), num_points, params, dev, max_entries, out,
+                   return_info, stream)
+
+
+def render_packed(stream_t, header, params, max_entries=None, out=None, return_info=False, stream=None):
+    """The image of a packed device stream (any version), decoded as loadSpz(to = params.coord) would: bit-identical to
+    render() of the decoded floats.  Otherwise as render()."""
+    _check_stream_tensor(stream_t)
+    return _render(("packed", stream_t, header), header.num_points, params, stream_t.device, max_entries, out,
+                   return_info, stream)
+
+
+def _records(rec_t):
+    f = rec_t.view(torch.float32).view(-1, 12)
+    r16 = rec_t.view(torch.int16).view(-1, 24)
+    return {"mean": f[:, 0:2], "conic": f[:, 2:5], "opacity": f[:, 5], "rgb": f[:, 6:9], "depth": f[:, 9],
+            "rect": r16[:, 20:24].to(torch.int32)}
+
+
+def _preprocess(source, n, params, dev, stream):
+    L = abi.load_library()
+    if not isinstance(params, abi.RenderParams):
+        raise ValueError("params must be an abi.RenderParams (abi.render_params)")
+    abi.check(L.spz_amd_render_check_params(C.byref(params)), "spz_amd_render_check_params")
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        with torch.cuda.stream(st):
+            total = torch.empty(1, dtype=torch.int64, device=dev)
+            rec = torch.empty(n * abi.RENDER_RECORD_BYTES, dtype=torch.uint8, device=dev)
+            ws = torch.empty(int(L.spz_amd_render_workspace_bytes(n, 0)), dtype=torch.uint8, device=dev)
+            _render_prepare(L, source, params, total, rec, ws, st)
+            out = _records(rec)  # the rect widening is a launch: on st too
+    out["total"] = total
+    return out
+
+
+def preprocess(cloud, num_points, sh_degree, params, antialiased=False, stream=None):
+    """The per-Gaussian records of render() (input order) as CUDA tensors: mean (n, 2), conic (n, 3: A, B, C), opacity,
+    rgb (n, 3), depth (+inf: invisible), rect (n, 4 int32: tile x0, y0, x1, y1); and total (the entry count)."""
+    ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
+    return _preprocess(("cloud", ptrs, num_points, int(sh_degree), antialiased), num_points, params, dev, stream)
+
+
+def preprocess_packed(stream_t, header, params, stream=None):
+    """The records of render_packed(), as preprocess()."""
+    _check_stream_tensor(stream_t)
+    return _preprocess(("packed", stream_t, header), header.num_points, params, stream_t.device, stream)
+
+
 def convert_coordinates(cloud, num_points, sh_degree, from_coord, to_coord, stream=None):
     """In-place GaussianCloud::convertCoordinates on device tensors (positions, rotations, sh)."""
     L = abi.load_library()
