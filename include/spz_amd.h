@@ -564,6 +564,62 @@ int spz_amd_render_cloud_host(const spz_amd_cloud_in *h_cloud, uint64_t num_poin
                               const spz_amd_render_params *params, int device, float *h_rgba, uint64_t *h_entries,
                               float *h_ms);
 
+/* ---- render scores: per-Gaussian blend weights of one view (spz_render.hip; DESIGN §8 "Prune").  The reference has
+ *      no counterpart.  With the workspace of a prepare step (as for render_finish_device), the blend of the render
+ *      contract runs again, pixel for pixel; for every (pixel i, Gaussian j) pair the blend USES (not skipped for power
+ *      > 0 or a < 1/255, and not the Gaussian whose T' would fall under 1e-4, which ends the pixel unused):
+ *        w_ij = T a in f32, exactly as the blend computes it;  q_ij = rint(w_ij 2^24), an integer: w <= 0.99, so
+ *        q < 2^24, and w >= 1e-4 / 255, so q >= 7 (a Gaussian's sum is 0 exactly when it was never used);
+ *        d_weight_sum[j] += sum_i q_ij (uint64: at most 2^52 per view of <= 2^28 pixels, so 1024 views stay below
+ *        2^62, which torch's int64 holds);  d_weight_max[j] = max(d_weight_max[j], max_i w_ij) (f32, 0 when unused).
+ *      Integer sums and f32 maxima do not depend on the order of the additions: a run repeats its bits, and a stream and
+ *      its decoded floats give the same scores.  No float atomics (vector integer atomics in LDS and global memory).
+ *      sum_j weight_sum_j 2^-24 over a view is the image's alpha sum (sum_i 1 - T_i), to the rounding of q.
+ *      Removing the Gaussians of zero sum keeps every scoring view's image, with one caveat: the Gaussian that ends a
+ *      pixel (T' = T (1 - a) < 1e-4) is not counted there, so when it scores zero everywhere, removing it lets the
+ *      Gaussians behind it into that pixel.  Such a pixel had T < 1e-4 / (1 - a) <= 0.01 (a <= 0.99), so alpha >=
+ *      0.99, and each channel moves by at most T (max |rgb| + |background|).
+ *      render_score_device: the entries, their sort and ranges as render_finish_device, then the scoring blend; the
+ *      caller zeroes d_weight_sum (uint64[n]) and d_weight_max (f32[n]) once and loops over views (prepare, score).
+ *      d_image (may be NULL): the image, bit-identical to render_finish_device's.  *d_status = 0, or 1 when the total
+ *      is above max_entries: then neither the image nor the scores are touched.  Enqueue only; no synchronisation.
+ *
+ * ---- prune: significance pruning over a set of views (spz_prune.hip; DESIGN §8 "Prune").  Versions 1, 2 and 3.
+ *      views: 1..SPZ_AMD_PRUNE_MAX_VIEWS render params, each passing render_check_params, all with one coord (the
+ *      frame the file is decoded to); background and max_sh_degree do not change a weight.  Per view: prepare, the
+ *      total read back, the workspace grown (grow-only), score.  A total above 2^31 - 1: SPZ_AMD_ERR_CAPACITY.
+ *      score_kind: SPZ_AMD_PRUNE_SCORE_SUM (weight_sum) or _MAX (weight_max).  Rank: score descending, then input
+ *      index ascending, exact on the u64 / u32 keys (a stable radix sort).  rule (exactly one):
+ *        KEEP_COUNT K = rule_value, an integer in 0..n;  KEEP_FRACTION f = rule_value in [0, 1], K = min(n, ceil(f n))
+ *        in f64 (spz_amd_prune_keep_count, host only, computes K);  MIN_SCORE s = rule_value, finite: keep j iff
+ *        score_j >= s, the sum compared as q 2^-24 (pixel units) in f64.
+ *      Output: spz_amd_select_device + spz_amd_subset_device of the kept indices at the input's degree, so the stream
+ *      is byte-identical to the filter's with the keep mask.  A bad argument is SPZ_AMD_ERR_INVALID_ARG before anything
+ *      is launched.  open (shaped like clean's) runs on `device` on a stream of its own and blocks.  *h_kept (may be
+ *      NULL): the kept count; h_mask (may be NULL): n bytes, 1 = kept; h_weight_sum / h_weight_max (may be NULL): n
+ *      uint64 / f32; h_ms (may be NULL): [0] wall-clock milliseconds of the views' scores, [1] of the rank and mask,
+ *      [2] of the subset; *h_bad_view (may be NULL): the index of the view a failure concerns (a bad view, a
+ *      different coord, the entry cap), else -1. */
+enum {
+  SPZ_AMD_PRUNE_MAX_VIEWS = 1024,
+  SPZ_AMD_PRUNE_SCORE_SUM = 0,
+  SPZ_AMD_PRUNE_SCORE_MAX = 1,
+  SPZ_AMD_PRUNE_KEEP_COUNT = 0,
+  SPZ_AMD_PRUNE_KEEP_FRACTION = 1,
+  SPZ_AMD_PRUNE_MIN_SCORE = 2
+};
+int spz_amd_render_score_device(uint64_t num_points, const spz_amd_render_params *params, uint64_t max_entries,
+                                float *d_image, uint64_t *d_weight_sum, float *d_weight_max, uint32_t *d_status,
+                                void *d_workspace, void *hip_stream);
+int spz_amd_prune_keep_count(uint64_t num_points, int rule, double rule_value, uint64_t *k);
+int spz_amd_prune_open(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr,
+                       const spz_amd_render_params *views, int num_views, int score_kind, int rule, double rule_value,
+                       int device, void **ctx, uint64_t *h_out_bytes, uint64_t *h_kept, uint8_t *h_mask,
+                       uint64_t *h_weight_sum, float *h_weight_max, float *h_ms, int32_t *h_bad_view);
+int spz_amd_prune_fetch(void *ctx, uint8_t *h_out);
+const uint8_t *spz_amd_prune_device_data(void *ctx);
+void spz_amd_prune_close(void *ctx);
+
 /* ---- device buffers for a resident cloud, placed for speed (spz_place.hip).  Whether an sh3 decode runs
  *      at 0.46 ms or at 0.55 ms is decided by whether the sh float array shares a physical region of HBM with the other
  *      arrays of the launch; that cannot be asked for, but it shows in one launch.  alloc: the five small arrays (and a

@@ -421,6 +421,51 @@ bool renderCloud(const GaussianCloud &g, const RenderOptions &options, std::vect
 // parallel to the view direction, or a value is not finite.
 std::array<float, 12> lookAt(const std::array<float, 3> &eye, const std::array<float, 3> &target,
                              const std::array<float, 3> &up);
+// Prune (DESIGN §8 "Prune"): significance pruning (include/spz_amd.h "render scores" and "prune" state the contract).
+// Every Gaussian's blend weight T a is summed (and maximised) over the views on the device, the points are ranked by
+// score (descending, then input index) and the kept ones are written as filterSpz would with the keep mask.  views:
+// 1..1024 pinhole cameras (the camera fields of RenderOptions), all in the `coord` frame.  Exactly one rule: keepCount
+// (0..n), keepFraction ([0, 1], K = min(n, ceil(f n))) or minScore (finite; the sum in pixel units, q 2^-24).  *kept
+// (may be NULL): the kept count; *keepMask: one byte per input point, 1 = kept; *weightSum: the u64 sums q (pixel
+// units times 2^24); *weightMax: the f32 maxima.  false + one "[SPZ ERROR] pruneSpz: …" line on a bad argument
+// (lastDeviceStatus() = SPZ_AMD_ERR_INVALID_ARG; a bad view is named by its index), an input that does not load, or a
+// device failure.  SPZ_AMD_PRUNE_TIMING=1 prints the stages' times to stderr.
+struct PruneOptions {
+  struct View {
+    std::array<float, 12> worldToCamera = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    float fx = 0.0f, fy = 0.0f, cx = 0.0f, cy = 0.0f;
+    int width = 0, height = 0;
+  };
+  enum Score { Sum = 0, Max = 1 };
+  std::vector<View> views;
+  CoordinateSystem coord = CoordinateSystem::UNSPECIFIED;
+  float nearPlane = 0.2f;
+  Score score = Sum;
+  std::optional<int64_t> keepCount;
+  std::optional<double> keepFraction;
+  std::optional<double> minScore;
+};
+bool pruneSpz(const uint8_t *data, int32_t size, const PruneOptions &options, std::vector<uint8_t> *out,
+              int64_t *kept = nullptr, std::vector<uint8_t> *keepMask = nullptr,
+              std::vector<uint64_t> *weightSum = nullptr, std::vector<float> *weightMax = nullptr);
+bool pruneSpz(const std::string &inputFilename, const std::string &outputFilename, const PruneOptions &options,
+              int64_t *kept = nullptr, std::vector<uint8_t> *keepMask = nullptr,
+              std::vector<uint64_t> *weightSum = nullptr, std::vector<float> *weightMax = nullptr);
+// n cameras (1..1024) on a Fibonacci sphere around `center` at distance distanceFactor * radius, each looking at the
+// centre (lookAt), fx = fy = height / 2 / tan(fovY / 2), cx, cy = width / 2, height / 2.  up is +y, or +z for a view
+// direction within 2.6 degrees of +-y, so no view is degenerate.  Callers without a centre and radius take them from the
+// axis-aligned box of the decoded positions (centre and half diagonal); floaters inflate that box, so clean first or
+// pass both.  std::invalid_argument on n outside 1..1024, a size outside 1..16384, fovY outside (0, 180), radius or
+// distanceFactor not finite and > 0, or a centre that is not finite.
+std::vector<PruneOptions::View> orbitViews(int n, const std::array<float, 3> &center, float radius, int width,
+                                           int height, float fovY, float distanceFactor = 2.5f);
+// The centre and half diagonal of the axis-aligned box of the finite positions (x, y, z triples) — orbitViews' defaults
+// (the radius is at least 1e-6).  false when no position is finite.
+bool boundingSphere(const std::vector<float> &positions, std::array<float, 3> *center, float *radius);
+// A plain-text views file: one view per line, "width height fx fy cx cy r00 r01 r02 t0 r10 r11 r12 t1 r20 r21 r22 t2",
+// blank lines and text after '#' ignored.  std::invalid_argument naming the line on a line that does not parse, a file
+// that does not open or holds no view.  The cameras themselves are checked by pruneSpz.
+std::vector<PruneOptions::View> loadViewsFile(const std::string &filename);
 // Status (spz_amd.h codes) of the last device call made by this thread; 0 = ok.
 int lastDeviceStatus();
 void setLastDeviceStatus(int status);

@@ -11,6 +11,7 @@ Layout:
   csrc/spz_decimate.hip one point per occupied octree cell by moment matching, over the Morton-sorted stream (decimateSpz)
   csrc/spz_clean.hip    exact k-NN scores and radius counts over the Morton-sorted positions, floater removal (cleanSpz)
   csrc/spz_render.hip   a tiled 3D Gaussian splat rasteriser: preprocess, depth and tile order, per-tile blend (renderSpz)
+  csrc/spz_prune.hip    per-Gaussian blend weights over views, exact rank, the filter's subset of the kept (pruneSpz)
   csrc/spz_abi.hip      the C ABI (include/spz_amd.h) over them: device-pointer entry points
   csrc/spz_hostpath.hip host-pointer entry points: device workspace + chunked H2D/kernel/D2H pipeline
   csrc/spz_exchange.hip multi-GPU exchange: native RCCL gatherv/scatterv, IPC-mapped root stream
@@ -27,6 +28,7 @@ Layout:
   device.py             device-resident encode/decode on torch-owned HBM
   shard.py              point-range sharding across GPUs + gatherv of the byte stream
   synth.py              seeded synthetic clouds
+  cameras.py            readers of camera sets (3DGS cameras.json) for prune_spz
 
 Nothing here falls back to the CPU: without libspz_amd.so or a HIP device, calls raise.
 """

@@ -76,7 +76,8 @@ EXPORTS = (
     "spz_amd_clean_close",
     "spz_amd_render_check_params", "spz_amd_render_workspace_bytes", "spz_amd_render_prepare_packed_device",
     "spz_amd_render_prepare_cloud_device", "spz_amd_render_finish_device", "spz_amd_render_host",
-    "spz_amd_render_cloud_host",
+    "spz_amd_render_cloud_host", "spz_amd_render_score_device", "spz_amd_prune_keep_count", "spz_amd_prune_open",
+    "spz_amd_prune_fetch", "spz_amd_prune_device_data", "spz_amd_prune_close",
 )
 
 RCCL_UNIQUE_ID_BYTES = 128
@@ -113,6 +114,9 @@ class RenderParams(C.Structure):
 
 
 RENDER_RECORD_BYTES = 48
+PRUNE_MAX_VIEWS = 1024
+PRUNE_SCORE_SUM, PRUNE_SCORE_MAX = 0, 1
+PRUNE_KEEP_COUNT, PRUNE_KEEP_FRACTION, PRUNE_MIN_SCORE = 0, 1, 2
 
 
 class CloudBuffers(C.Structure):
@@ -421,6 +425,20 @@ def bind(L):
     L.spz_amd_render_cloud_host.restype = i32
     L.spz_amd_render_cloud_host.argtypes = [C.POINTER(CloudPtrs), u64, i32, i32, C.POINTER(RenderParams), i32, vp,
                                             C.POINTER(u64), vp]
+    L.spz_amd_render_score_device.restype = i32
+    L.spz_amd_render_score_device.argtypes = [u64, C.POINTER(RenderParams), u64, vp, vp, vp, vp, vp, vp]
+    L.spz_amd_prune_keep_count.restype = i32
+    L.spz_amd_prune_keep_count.argtypes = [u64, i32, C.c_double, C.POINTER(u64)]
+    L.spz_amd_prune_open.restype = i32
+    L.spz_amd_prune_open.argtypes = [vp, sz, C.POINTER(Header), C.POINTER(RenderParams), i32, i32, i32, C.c_double, i32,
+                                     C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), vp, vp, vp, vp,
+                                     C.POINTER(C.c_int32)]
+    L.spz_amd_prune_fetch.restype = i32
+    L.spz_amd_prune_fetch.argtypes = [vp, vp]
+    L.spz_amd_prune_device_data.restype = vp
+    L.spz_amd_prune_device_data.argtypes = [vp]
+    L.spz_amd_prune_close.restype = None
+    L.spz_amd_prune_close.argtypes = [vp]
     L.spz_amd_zlib_encode_blocks.restype = i32
     L.spz_amd_zlib_encode_blocks.argtypes = [vp, vp, u32, u32, vp, vp, vp, u64, u64, vp, vp]
     return L

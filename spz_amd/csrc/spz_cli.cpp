@@ -1,13 +1,13 @@
 // spz_cli.cpp — the three command-line tools of the reference (cli_tools/src/*.cpp) over the
 // MI355X drop-in layer: ply_to_spz, spz_to_ply, spz_info; and spz_filter (spz::filterSpz),
 // spz_transform (spz::transformSpz), spz_merge (spz::mergeSpz), spz_sort (spz::sortSpz), spz_decimate
-// (spz::decimateSpz), spz_clean (spz::cleanSpz) and spz_render (spz::renderSpz), which have no counterpart in the
-// reference.  One binary, dispatched on argv[0] (the Makefile installs it under the ten names) or on a first argument
-// naming the tool.
+// (spz::decimateSpz), spz_clean (spz::cleanSpz), spz_render (spz::renderSpz) and spz_prune (spz::pruneSpz), which have
+// no counterpart in the reference.  One binary, dispatched on argv[0] (the Makefile installs it under the eleven names)
+// or on a first argument naming the tool.
 // Same behaviour as the reference mains: default (UNSPECIFIED) pack/unpack options, exit code 0
 // once the arguments are there (the reference ignores the save/load results), usage -> 1.
-// spz_filter, spz_transform, spz_merge, spz_sort, spz_decimate, spz_clean and spz_render exit 1 when the filter /
-// transform / merge / sort / decimation / clean / render fails as well.
+// spz_filter, spz_transform, spz_merge, spz_sort, spz_decimate, spz_clean, spz_render and spz_prune exit 1 when the
+// filter / transform / merge / sort / decimation / clean / render / prune fails as well.
 #include <algorithm>
 #include <stdexcept>
 #include <array>
@@ -474,6 +474,132 @@ int spzRender(int argc, char **argv) {
   return 0;
 }
 
+const char *kPruneUsage =
+    "Usage: spz_prune <in.spz> <out.spz> (--views FILE | --orbit N --size W H --fov-y DEG [--center x y z --radius R] "
+    "[--distance K]) (--keep N | --keep-fraction F | --min-score S) [--score sum|max] "
+    "[--coord RUB|RDF|LUF|RUF|LDB|RDB|LUB|LDF|UNSPECIFIED]";
+
+int spzPrune(int argc, char **argv) {
+  auto usage = [] {
+    std::cerr << kPruneUsage << std::endl;
+    return 1;
+  };
+  if (argc < 3 || argv[1][0] == '-' || argv[2][0] == '-') return usage();
+  spz::PruneOptions o;
+  std::string viewsFile;
+  int orbit = 0, size[2] = {0, 0};
+  float fovY = 0.0f, radius = 0.0f, distance = 2.5f;
+  std::array<float, 3> center{};
+  bool hasViews = false, hasOrbit = false, hasSize = false, hasFov = false, hasCenter = false, hasRadius = false;
+  bool hasDistance = false, hasScore = false, hasCoord = false;
+  auto floats = [&](int &i, int k, float *dst) {
+    if (i + k >= argc) return false;
+    for (int j = 0; j < k; ++j) {
+      if (!parseFloat(argv[i + 1 + j], &dst[j]) || !std::isfinite(dst[j])) return false;
+    }
+    i += k;
+    return true;
+  };
+  auto integer = [](const char *s, int lo, int hi, int *v) {
+    const std::string t = s;
+    if (t.empty() || t.size() > 10 || t.find_first_not_of("0123456789") != std::string::npos) return false;
+    const long long x = std::atoll(s);
+    if (x < lo || x > hi) return false;
+    *v = static_cast<int>(x);
+    return true;
+  };
+  for (int i = 3; i < argc; ++i) {
+    const std::string a = argv[i];
+    const bool more = i + 1 < argc;
+    if (a == "--views" && !hasViews && more) {
+      viewsFile = argv[++i];
+      hasViews = true;
+    } else if (a == "--orbit" && !hasOrbit && more) {
+      if (!integer(argv[++i], 1, 1024, &orbit)) return usage();
+      hasOrbit = true;
+    } else if (a == "--size" && !hasSize && i + 2 < argc) {
+      for (int k = 0; k < 2; ++k) {
+        if (!integer(argv[i + 1 + k], 1, 16384, &size[k])) return usage();
+      }
+      i += 2;
+      hasSize = true;
+    } else if (a == "--fov-y" && !hasFov) {
+      if (!floats(i, 1, &fovY) || !(fovY > 0.0f && fovY < 180.0f)) return usage();
+      hasFov = true;
+    } else if (a == "--center" && !hasCenter) {
+      if (!floats(i, 3, center.data())) return usage();
+      hasCenter = true;
+    } else if (a == "--radius" && !hasRadius) {
+      if (!floats(i, 1, &radius) || !(radius > 0.0f)) return usage();
+      hasRadius = true;
+    } else if (a == "--distance" && !hasDistance) {
+      if (!floats(i, 1, &distance) || !(distance > 0.0f)) return usage();
+      hasDistance = true;
+    } else if (a == "--keep" && !o.keepCount && more) {
+      int k = 0;
+      if (!integer(argv[++i], 0, 0x7fffffff, &k)) return usage();
+      o.keepCount = k;
+    } else if (a == "--keep-fraction" && !o.keepFraction && more) {
+      double f = 0.0;
+      if (!parseDouble(argv[++i], &f) || !(f >= 0.0 && f <= 1.0)) return usage();
+      o.keepFraction = f;
+    } else if (a == "--min-score" && !o.minScore && more) {
+      double s = 0.0;
+      if (!parseDouble(argv[++i], &s) || !std::isfinite(s)) return usage();
+      o.minScore = s;
+    } else if (a == "--score" && !hasScore && more) {
+      const std::string v = argv[++i];
+      if (v == "sum") {
+        o.score = spz::PruneOptions::Sum;
+      } else if (v == "max") {
+        o.score = spz::PruneOptions::Max;
+      } else {
+        return usage();
+      }
+      hasScore = true;
+    } else if (a == "--coord" && !hasCoord && more) {
+      hasCoord = true;
+      static const char *names[] = {"UNSPECIFIED", "LDB", "RDB", "LUB", "RUB", "LDF", "RDF", "LUF", "RUF"};
+      const std::string c = argv[++i];
+      int found = -1;
+      for (int k = 0; k < 9; ++k) {
+        if (c == names[k]) found = k;
+      }
+      if (found < 0) return usage();
+      o.coord = static_cast<spz::CoordinateSystem>(found);
+    } else {
+      return usage();
+    }
+  }
+  const int rules = (o.keepCount ? 1 : 0) + (o.keepFraction ? 1 : 0) + (o.minScore ? 1 : 0);
+  if (rules != 1 || hasViews == hasOrbit) return usage();
+  if (hasViews && (hasSize || hasFov || hasCenter || hasRadius || hasDistance)) return usage();
+  if (hasOrbit && (!hasSize || !hasFov || hasCenter != hasRadius)) return usage();
+  try {
+    if (hasViews) {
+      o.views = spz::loadViewsFile(viewsFile);
+    } else {
+      if (!hasCenter) {  // the box of the decoded positions
+        spz::UnpackOptions u;
+        u.to = o.coord;
+        const spz::GaussianCloud g = spz::loadSpz(std::string(argv[1]), u);
+        if (g.numPoints <= 0 || !spz::boundingSphere(g.positions, &center, &radius)) {
+          std::cerr << "spz_prune: " << argv[1] << " has no points to take a centre and radius from" << std::endl;
+          return 1;
+        }
+      }
+      o.views = spz::orbitViews(orbit, center, radius, size[0], size[1], fovY, distance);
+    }
+  } catch (const std::invalid_argument &e) {
+    std::cerr << e.what() << std::endl;
+    return usage();
+  }
+  int64_t kept = 0;
+  if (!spz::pruneSpz(std::string(argv[1]), std::string(argv[2]), o, &kept)) return 1;
+  std::cout << "kept " << kept << std::endl;
+  return 0;
+}
+
 int dispatch(const std::string &tool, int argc, char **argv) {
   if (tool == "ply_to_spz") return plyToSpz(argc, argv);
   if (tool == "spz_to_ply") return spzToPly(argc, argv);
@@ -485,6 +611,7 @@ int dispatch(const std::string &tool, int argc, char **argv) {
   if (tool == "spz_decimate") return spzDecimate(argc, argv);
   if (tool == "spz_clean") return spzClean(argc, argv);
   if (tool == "spz_render") return spzRender(argc, argv);
+  if (tool == "spz_prune") return spzPrune(argc, argv);
   return -1;
 }
 
@@ -501,7 +628,7 @@ int main(int argc, char **argv) {
       rc = dispatch(argv[1], argc - 1, argv + 1);
       if (rc >= 0) return rc;
     }
-    std::cerr << "Usage: spz_tool {ply_to_spz|spz_to_ply|spz_info|spz_filter|spz_transform|spz_merge|spz_sort|spz_decimate|spz_clean|spz_render} <args...>" << std::endl;
+    std::cerr << "Usage: spz_tool {ply_to_spz|spz_to_ply|spz_info|spz_filter|spz_transform|spz_merge|spz_sort|spz_decimate|spz_clean|spz_render|spz_prune} <args...>" << std::endl;
     return 1;
   } catch (const std::exception &e) {
     std::cerr << "Error: " << e.what() << std::endl;

@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <sstream>
 #include <istream>
 #include <mutex>
 #include <ostream>
@@ -2596,6 +2597,284 @@ std::array<float, 12> lookAt(const std::array<float, 3> &eye, const std::array<f
     m[r * 4 + 3] = static_cast<float>(-(rows[r][0] * e[0] + rows[r][1] * e[1] + rows[r][2] * e[2]));
   }
   return m;
+}
+
+// ---- prune -------------------------------------------------------------------------------------------------------
+namespace {
+bool pruneRejected(int status, const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  char msg[256];
+  std::vsnprintf(msg, sizeof(msg), fmt, ap);
+  va_end(ap);
+  logLine("[SPZ ERROR] pruneSpz: %s", msg);
+  g_last_status = status;
+  return false;
+}
+
+struct PruneLaps {
+  bool on = std::getenv("SPZ_AMD_PRUNE_TIMING") != nullptr;
+  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+  void lap(const char *what) {
+    const auto now = std::chrono::steady_clock::now();
+    if (on) std::fprintf(stderr, "[pruneSpz] %-8s %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
+    t = now;
+  }
+};
+
+// The views as render params, and exactly one rule in range (keepCount's upper bound needs n: checked later).
+bool pruneOptionsOk(const PruneOptions &o, std::vector<spz_amd_render_params> *params) {
+  const int rules = (o.keepCount ? 1 : 0) + (o.keepFraction ? 1 : 0) + (o.minScore ? 1 : 0);
+  if (rules != 1) return pruneRejected(SPZ_AMD_ERR_INVALID_ARG, "set exactly one of keepCount, keepFraction, minScore");
+  if (o.keepCount && *o.keepCount < 0) {
+    return pruneRejected(SPZ_AMD_ERR_INVALID_ARG, "keepCount %lld is negative", static_cast<long long>(*o.keepCount));
+  }
+  if (o.keepFraction && !(*o.keepFraction >= 0.0 && *o.keepFraction <= 1.0)) {
+    return pruneRejected(SPZ_AMD_ERR_INVALID_ARG, "keepFraction must be in [0, 1]");
+  }
+  if (o.minScore && !std::isfinite(*o.minScore)) return pruneRejected(SPZ_AMD_ERR_INVALID_ARG, "minScore must be finite");
+  if (o.score != PruneOptions::Sum && o.score != PruneOptions::Max) {
+    return pruneRejected(SPZ_AMD_ERR_INVALID_ARG, "score must be Sum or Max");
+  }
+  if (o.views.empty() || o.views.size() > SPZ_AMD_PRUNE_MAX_VIEWS) {
+    return pruneRejected(SPZ_AMD_ERR_INVALID_ARG, "%zu views: give 1..%d", o.views.size(), SPZ_AMD_PRUNE_MAX_VIEWS);
+  }
+  params->assign(o.views.size(), spz_amd_render_params{});
+  for (size_t v = 0; v < o.views.size(); ++v) {
+    const PruneOptions::View &w = o.views[v];
+    spz_amd_render_params &p = (*params)[v];
+    if (w.width < 1 || w.width > 16384 || w.height < 1 || w.height > 16384) {
+      return pruneRejected(SPZ_AMD_ERR_INVALID_ARG, "view %zu: image size %d x %d is outside 1..16384", v, w.width,
+                           w.height);
+    }
+    for (int k = 0; k < 12; ++k) p.world_to_camera[k] = w.worldToCamera[k];
+    p.fx = w.fx;
+    p.fy = w.fy;
+    p.cx = w.cx;
+    p.cy = w.cy;
+    p.width = static_cast<uint32_t>(w.width);
+    p.height = static_cast<uint32_t>(w.height);
+    p.near_plane = o.nearPlane;
+    p.max_sh_degree = 0;  // colours do not change a weight
+    p.coord = static_cast<int32_t>(o.coord);
+    if (spz_amd_render_check_params(&p) != SPZ_AMD_OK) {
+      return pruneRejected(SPZ_AMD_ERR_INVALID_ARG,
+                           "view %zu: bad camera: R must be a rotation (to 1e-4), fx, fy > 0, nearPlane > 0, values "
+                           "finite, coord valid", v);
+    }
+  }
+  return true;
+}
+}  // namespace
+
+bool pruneSpz(const uint8_t *data, int32_t size, const PruneOptions &o, std::vector<uint8_t> *out, int64_t *kept,
+              std::vector<uint8_t> *keepMask, std::vector<uint64_t> *weightSum, std::vector<float> *weightMax) {
+  g_last_status = SPZ_AMD_OK;
+  if (keepMask) keepMask->clear();
+  if (weightSum) weightSum->clear();
+  if (weightMax) weightMax->clear();
+  if (out == nullptr) return pruneRejected(SPZ_AMD_ERR_INVALID_ARG, "no output vector");
+  std::vector<spz_amd_render_params> params;
+  if (!pruneOptionsOk(o, &params)) return false;
+  PruneLaps laps;
+  DevicePackedGaussians d = loadSpzPackedDevice(data, size);
+  if (!d.valid()) {
+    if (g_last_status == SPZ_AMD_OK) logLine("[SPZ ERROR] pruneSpz: the input is not a readable .spz");
+    return false;
+  }
+  laps.lap("inflate");
+  const uint64_t n = static_cast<uint64_t>(d.numPoints);
+  if (o.keepCount && static_cast<uint64_t>(*o.keepCount) > n) {
+    return pruneRejected(SPZ_AMD_ERR_INVALID_ARG, "keepCount %lld is above the %llu points",
+                         static_cast<long long>(*o.keepCount), static_cast<unsigned long long>(n));
+  }
+  const spz_amd_header hdr = headerOf(d);
+  std::vector<uint8_t> mask;
+  std::vector<uint64_t> sums;
+  std::vector<float> maxima;
+  if (keepMask) detail::resizeUninitialized(&mask, static_cast<size_t>(n));
+  if (weightSum) detail::resizeUninitialized(&sums, static_cast<size_t>(n));
+  if (weightMax) detail::resizeUninitialized(&maxima, static_cast<size_t>(n));
+  const int rule = o.keepCount ? SPZ_AMD_PRUNE_KEEP_COUNT : o.keepFraction ? SPZ_AMD_PRUNE_KEEP_FRACTION
+                                                                           : SPZ_AMD_PRUNE_MIN_SCORE;
+  const double value = o.keepCount ? static_cast<double>(*o.keepCount) : o.keepFraction ? *o.keepFraction : *o.minScore;
+  void *ctx = nullptr;
+  uint64_t bytes = 0, count = 0;
+  float ms[3] = {0.0f, 0.0f, 0.0f};
+  int32_t bad = -1;
+  int rc = spz_amd_prune_open(d.stream, d.streamBytes, &hdr, params.data(), static_cast<int>(params.size()),
+                              static_cast<int>(o.score), rule, value, d.device, &ctx, &bytes, &count,
+                              keepMask ? mask.data() : nullptr, weightSum ? sums.data() : nullptr,
+                              weightMax ? maxima.data() : nullptr, ms, &bad);
+  if (rc == SPZ_AMD_ERR_CAPACITY && bad >= 0) {
+    return pruneRejected(rc, "view %d: more than 2^31 - 1 tile entries", bad);
+  }
+  if (rc != SPZ_AMD_OK && bad >= 0) logLine("[SPZ ERROR] pruneSpz: view %d failed", bad);
+  if (deviceFailed(rc, "pruneSpz")) return false;
+  struct Close {
+    void *c;
+    ~Close() { spz_amd_prune_close(c); }
+  } closer{ctx};
+  if (laps.on) {
+    std::fprintf(stderr, "[pruneSpz] score    %.3f ms (%zu views)\n[pruneSpz] rank     %.3f ms\n[pruneSpz] subset   %.3f ms\n",
+                 ms[0], params.size(), ms[1], ms[2]);
+  }
+  laps.lap("prune");
+  d.release();  // the input's device memory goes before the container stage takes its own
+  std::vector<uint8_t> stream;
+  detail::resizeUninitialized(&stream, static_cast<size_t>(bytes));
+  rc = spz_amd_prune_fetch(ctx, stream.data());
+  if (deviceFailed(rc, "pruneSpz")) return false;
+  laps.lap("download");
+  if (!compressGzippedWithCopy(stream.data(), stream.size(), out, spz_amd_prune_device_data(ctx))) {
+    logLine("[SPZ ERROR] pruneSpz: compressGzipped failed");
+    return false;
+  }
+  laps.lap("gzip");
+  if (kept) *kept = static_cast<int64_t>(count);
+  if (keepMask) keepMask->swap(mask);
+  if (weightSum) weightSum->swap(sums);
+  if (weightMax) weightMax->swap(maxima);
+  return true;
+}
+
+bool pruneSpz(const std::string &inputFilename, const std::string &outputFilename, const PruneOptions &o,
+              int64_t *kept, std::vector<uint8_t> *keepMask, std::vector<uint64_t> *weightSum,
+              std::vector<float> *weightMax) {
+  g_last_status = SPZ_AMD_OK;
+  if (keepMask) keepMask->clear();
+  if (weightSum) weightSum->clear();
+  if (weightMax) weightMax->clear();
+  std::vector<spz_amd_render_params> params;
+  if (!pruneOptionsOk(o, &params)) return false;
+  std::vector<uint8_t> data;
+  if (!readFile(inputFilename, &data, /*log=*/true)) return false;
+  if (data.size() > static_cast<size_t>(INT32_MAX)) {
+    return pruneRejected(SPZ_AMD_ERR_INVALID_ARG, "%s is larger than 2 GiB", inputFilename.c_str());
+  }
+  std::vector<uint8_t> file, mask;
+  std::vector<uint64_t> sums;
+  std::vector<float> maxima;
+  int64_t count = 0;
+  if (!pruneSpz(data.data(), static_cast<int32_t>(data.size()), o, &file, &count, keepMask ? &mask : nullptr,
+                weightSum ? &sums : nullptr, weightMax ? &maxima : nullptr)) {
+    return false;
+  }
+  PruneLaps laps;
+  if (!writeFile(outputFilename, file)) {
+    logLine("[SPZ ERROR] pruneSpz: unable to write %s", outputFilename.c_str());
+    return false;
+  }
+  laps.lap("write");
+  if (kept) *kept = count;
+  if (keepMask) keepMask->swap(mask);
+  if (weightSum) weightSum->swap(sums);
+  if (weightMax) weightMax->swap(maxima);
+  return true;
+}
+
+std::vector<PruneOptions::View> orbitViews(int n, const std::array<float, 3> &center, float radius, int width,
+                                           int height, float fovY, float distanceFactor) {
+  if (n < 1 || n > SPZ_AMD_PRUNE_MAX_VIEWS) throw std::invalid_argument("orbitViews: n must be in 1..1024");
+  if (width < 1 || width > 16384 || height < 1 || height > 16384) {
+    throw std::invalid_argument("orbitViews: width and height must be in 1..16384");
+  }
+  if (!(fovY > 0.0f && fovY < 180.0f)) throw std::invalid_argument("orbitViews: fovY must be in (0, 180) degrees");
+  if (!std::isfinite(radius) || !(radius > 0.0f) || !std::isfinite(distanceFactor) || !(distanceFactor > 0.0f)) {
+    throw std::invalid_argument("orbitViews: radius and distanceFactor must be finite and > 0");
+  }
+  for (int k = 0; k < 3; ++k) {
+    if (!std::isfinite(center[k])) throw std::invalid_argument("orbitViews: center must be finite");
+  }
+  const double pi = 3.14159265358979323846;
+  const double golden = pi * (3.0 - std::sqrt(5.0));
+  const double dist = static_cast<double>(radius) * distanceFactor;
+  const double f = 0.5 * height / std::tan(0.5 * fovY * pi / 180.0);
+  std::vector<PruneOptions::View> out(static_cast<size_t>(n));
+  for (int i = 0; i < n; ++i) {
+    const double y = 1.0 - 2.0 * (i + 0.5) / n;
+    const double r = std::sqrt(std::max(0.0, 1.0 - y * y));
+    const double phi = golden * i;
+    const double dir[3] = {r * std::cos(phi), y, r * std::sin(phi)};
+    std::array<float, 3> eye;
+    for (int k = 0; k < 3; ++k) eye[k] = static_cast<float>(center[k] + dist * dir[k]);
+    const std::array<float, 3> up = std::fabs(y) > 0.999 ? std::array<float, 3>{0.0f, 0.0f, 1.0f}
+                                                         : std::array<float, 3>{0.0f, 1.0f, 0.0f};
+    PruneOptions::View &v = out[static_cast<size_t>(i)];
+    v.worldToCamera = lookAt(eye, center, up);
+    v.fx = v.fy = static_cast<float>(f);
+    v.cx = 0.5f * width;
+    v.cy = 0.5f * height;
+    v.width = width;
+    v.height = height;
+  }
+  return out;
+}
+
+bool boundingSphere(const std::vector<float> &positions, std::array<float, 3> *center, float *radius) {
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (size_t i = 0; i + 2 < positions.size(); i += 3) {
+    if (!std::isfinite(positions[i]) || !std::isfinite(positions[i + 1]) || !std::isfinite(positions[i + 2])) continue;
+    for (int k = 0; k < 3; ++k) {
+      lo[k] = std::min(lo[k], static_cast<double>(positions[i + k]));
+      hi[k] = std::max(hi[k], static_cast<double>(positions[i + k]));
+    }
+  }
+  if (!(lo[0] <= hi[0])) return false;
+  double d2 = 0.0;
+  for (int k = 0; k < 3; ++k) {
+    (*center)[k] = static_cast<float>(0.5 * (lo[k] + hi[k]));
+    d2 += (hi[k] - lo[k]) * (hi[k] - lo[k]);
+  }
+  *radius = static_cast<float>(std::max(0.5 * std::sqrt(d2), 1e-6));
+  return true;
+}
+
+std::vector<PruneOptions::View> loadViewsFile(const std::string &filename) {
+  std::ifstream in(filename);
+  if (!in) throw std::invalid_argument("loadViewsFile: unable to open " + filename);
+  std::vector<PruneOptions::View> views;
+  std::string line;
+  int lineNo = 0;
+  while (std::getline(in, line)) {
+    ++lineNo;
+    const size_t hash = line.find('#');
+    if (hash != std::string::npos) line.resize(hash);
+    std::istringstream ss(line);
+    std::vector<std::string> tok;
+    std::string t;
+    while (ss >> t) tok.push_back(t);
+    if (tok.empty()) continue;
+    const std::string at = "loadViewsFile: " + filename + " line " + std::to_string(lineNo) + ": ";
+    if (tok.size() != 18) {
+      throw std::invalid_argument(at + "expected 18 values (width height fx fy cx cy and the 3x4 [R | t]), got " +
+                                  std::to_string(tok.size()));
+    }
+    double v[18];
+    for (int k = 0; k < 18; ++k) {
+      char *end = nullptr;
+      v[k] = std::strtod(tok[k].c_str(), &end);
+      if (end == tok[k].c_str() || *end != '\0' || !std::isfinite(v[k])) {
+        throw std::invalid_argument(at + "'" + tok[k] + "' is not a finite number");
+      }
+    }
+    PruneOptions::View w;
+    for (int k = 0; k < 2; ++k) {
+      if (v[k] != std::floor(v[k]) || v[k] < 1.0 || v[k] > 16384.0) {
+        throw std::invalid_argument(at + "width and height must be integers in 1..16384");
+      }
+    }
+    w.width = static_cast<int>(v[0]);
+    w.height = static_cast<int>(v[1]);
+    w.fx = static_cast<float>(v[2]);
+    w.fy = static_cast<float>(v[3]);
+    w.cx = static_cast<float>(v[4]);
+    w.cy = static_cast<float>(v[5]);
+    for (int k = 0; k < 12; ++k) w.worldToCamera[k] = static_cast<float>(v[6 + k]);
+    views.push_back(w);
+  }
+  if (views.empty()) throw std::invalid_argument("loadViewsFile: " + filename + " holds no view");
+  return views;
 }
 
 GaussianCloud loadSpz(const std::vector<uint8_t> &data, const UnpackOptions &o) {

@@ -130,6 +130,63 @@ py::object renderedImage(bool ok, const std::vector<float> &img, const spz::Rend
   return out;
 }
 
+// A prune view from a mapping with world_to_camera (3x4), fx, fy, cx, cy, width, height (what orbit_views and
+// load_3dgs_cameras return); every problem is a ValueError that names the view.
+spz::PruneOptions::View pruneView(const py::handle &h, size_t k, spz::CoordinateSystem coord, float near_plane) {
+  const std::string at = "view " + std::to_string(k) + ": ";
+  if (!py::isinstance<py::dict>(h)) throw py::value_error(at + "must be a dict (world_to_camera, fx, fy, cx, cy, width, height)");
+  const py::dict d = py::reinterpret_borrow<py::dict>(h);
+  for (const char *key : {"world_to_camera", "fx", "fy", "cx", "cy", "width", "height"}) {
+    if (!d.contains(key)) throw py::value_error(at + "has no " + key);
+  }
+  if (d.contains("coord") && !d["coord"].is_none() && d["coord"].cast<spz::CoordinateSystem>() != coord) {
+    throw py::value_error(at + "its coord differs from the prune's coord (every view is in one frame)");
+  }
+  spz::PruneOptions::View v;
+  py::array_t<float, py::array::c_style | py::array::forcecast> m(d["world_to_camera"]);
+  if (m.ndim() != 2 || m.shape(0) != 3 || m.shape(1) != 4) throw py::value_error(at + "world_to_camera must be 3x4");
+  for (int i = 0; i < 12; ++i) v.worldToCamera[i] = m.data()[i];
+  try {
+    v.fx = d["fx"].cast<float>();
+    v.fy = d["fy"].cast<float>();
+    v.cx = d["cx"].cast<float>();
+    v.cy = d["cy"].cast<float>();
+    v.width = d["width"].cast<int>();
+    v.height = d["height"].cast<int>();
+  } catch (const py::cast_error &) {
+    throw py::value_error(at + "fx, fy, cx, cy must be numbers and width, height ints");
+  }
+  spz_amd_render_params p = {};
+  for (int i = 0; i < 12; ++i) p.world_to_camera[i] = v.worldToCamera[i];
+  p.fx = v.fx;
+  p.fy = v.fy;
+  p.cx = v.cx;
+  p.cy = v.cy;
+  p.width = static_cast<uint32_t>(v.width < 0 ? 0 : v.width);
+  p.height = static_cast<uint32_t>(v.height < 0 ? 0 : v.height);
+  p.near_plane = near_plane;
+  p.coord = static_cast<int32_t>(coord);
+  if (spz_amd_render_check_params(&p) != SPZ_AMD_OK) {
+    throw py::value_error(at + "bad camera: world_to_camera must be [R | t] with R a rotation (to 1e-4), fx, fy > 0, "
+                               "width and height in 1..16384, near_plane > 0, values finite");
+  }
+  return v;
+}
+
+py::dict viewDict(const spz::PruneOptions::View &v) {
+  py::dict d;
+  py::array_t<float> m({py::ssize_t(3), py::ssize_t(4)});
+  std::memcpy(m.mutable_data(), v.worldToCamera.data(), sizeof(float) * 12);
+  d["world_to_camera"] = m;
+  d["fx"] = v.fx;
+  d["fy"] = v.fy;
+  d["cx"] = v.cx;
+  d["cy"] = v.cy;
+  d["width"] = v.width;
+  d["height"] = v.height;
+  return d;
+}
+
 // filter_spz's arguments as spz::FilterOptions; every problem is a ValueError, raised before any device work.
 spz::FilterOptions filterOptions(const py::object &mask, const py::object &indices, const py::object &box,
                                  spz::CoordinateSystem coord, const py::object &min_alpha, const py::object &sh_degree) {
@@ -760,6 +817,161 @@ PYBIND11_MODULE(spz, m) {
         },
         py::arg("eye"), py::arg("target"), py::arg("up"),
         "The 3x4 world_to_camera (float32) of a camera at eye looking at target, OpenCV axes: up maps to -y.");
+  m.def("prune_spz",
+        [](const std::string &input, const std::string &output, const py::object &views, const py::object &keep,
+           const py::object &keep_fraction, const py::object &min_score, const std::string &score,
+           spz::CoordinateSystem coord, float near_plane, const py::object &return_scores) -> py::object {
+          // the arguments first: every problem is a ValueError before any device work
+          auto is_int = [](const py::object &v) { return py::isinstance<py::int_>(v) && !py::isinstance<py::bool_>(v); };
+          auto is_real = [](const py::object &v) {
+            return (py::isinstance<py::float_>(v) || py::isinstance<py::int_>(v)) && !py::isinstance<py::bool_>(v);
+          };
+          if (!py::isinstance<py::bool_>(return_scores)) throw py::value_error("return_scores must be a bool");
+          const int rules = (keep.is_none() ? 0 : 1) + (keep_fraction.is_none() ? 0 : 1) + (min_score.is_none() ? 0 : 1);
+          if (rules != 1) throw py::value_error("give exactly one of keep, keep_fraction, min_score");
+          spz::PruneOptions o;
+          if (!keep.is_none()) {
+            if (!is_int(keep) || py::reinterpret_borrow<py::int_>(keep) < py::int_(0) ||
+                py::reinterpret_borrow<py::int_>(keep) > py::int_(0x7fffffff)) {
+              throw py::value_error("keep must be an int in 0..n");
+            }
+            o.keepCount = py::cast<int64_t>(keep);
+          }
+          if (!keep_fraction.is_none()) {
+            const double f = is_real(keep_fraction) ? py::cast<double>(keep_fraction) : -1.0;
+            if (!(f >= 0.0 && f <= 1.0)) throw py::value_error("keep_fraction must be a number in [0, 1]");
+            o.keepFraction = f;
+          }
+          if (!min_score.is_none()) {
+            const double v = is_real(min_score) ? py::cast<double>(min_score) : __builtin_nan("");
+            if (!std::isfinite(v)) throw py::value_error("min_score must be a finite number");
+            o.minScore = v;
+          }
+          if (score == "sum") {
+            o.score = spz::PruneOptions::Sum;
+          } else if (score == "max") {
+            o.score = spz::PruneOptions::Max;
+          } else {
+            throw py::value_error("score must be 'sum' or 'max'");
+          }
+          if (!std::isfinite(near_plane) || !(near_plane > 0.0f)) throw py::value_error("near_plane must be > 0");
+          o.coord = coord;
+          o.nearPlane = near_plane;
+          if (py::isinstance<py::dict>(views) || py::isinstance<py::str>(views) || !py::isinstance<py::sequence>(views)) {
+            throw py::value_error("views must be a sequence of view dicts (orbit_views, load_3dgs_cameras)");
+          }
+          const py::sequence seq = py::reinterpret_borrow<py::sequence>(views);
+          if (seq.size() < 1 || seq.size() > SPZ_AMD_PRUNE_MAX_VIEWS) {
+            throw py::value_error("give 1..1024 views, got " + std::to_string(seq.size()));
+          }
+          for (size_t k = 0; k < seq.size(); ++k) o.views.push_back(pruneView(seq[k], k, coord, near_plane));
+          const bool details = py::cast<bool>(return_scores);
+          std::vector<uint8_t> mask;
+          std::vector<uint64_t> sums;
+          std::vector<float> maxima;
+          int64_t kept = 0;
+          bool ok;
+          {
+            py::gil_scoped_release release;
+            ok = spz::pruneSpz(input, output, o, &kept, details ? &mask : nullptr, details ? &sums : nullptr,
+                               details ? &maxima : nullptr);
+          }
+          if (!ok) {
+            raiseIfDeviceUnusable();
+            if (spz::lastDeviceStatus() == SPZ_AMD_ERR_INVALID_ARG) {
+              throw py::value_error("prune_spz: refused for this file (see the [SPZ ERROR] line)");
+            }
+            throw std::runtime_error("prune_spz: " + input + " -> " + output + " failed (see the [SPZ ERROR] line)");
+          }
+          if (!details) return py::int_(kept);
+          py::array_t<bool> m(static_cast<py::ssize_t>(mask.size()));
+          if (!mask.empty()) std::memcpy(m.mutable_data(), mask.data(), mask.size());
+          py::array_t<uint64_t> ws(static_cast<py::ssize_t>(sums.size()));
+          if (!sums.empty()) std::memcpy(ws.mutable_data(), sums.data(), sums.size() * 8u);
+          py::array_t<float> wm(static_cast<py::ssize_t>(maxima.size()));
+          if (!maxima.empty()) std::memcpy(wm.mutable_data(), maxima.data(), maxima.size() * 4u);
+          return py::make_tuple(kept, m, ws, wm);
+        },
+        py::arg("input_filename"), py::arg("output_filename"), py::arg("views"), py::kw_only(),
+        py::arg("keep") = py::none(), py::arg("keep_fraction") = py::none(), py::arg("min_score") = py::none(),
+        py::arg("score") = "sum", py::arg("coord") = spz::CoordinateSystem::UNSPECIFIED, py::arg("near_plane") = 0.2f,
+        py::arg("return_scores") = false,
+        "Drop the splats that contribute least to a set of views, without requantising (spz::pruneSpz; the contract is "
+        "in include/spz_amd.h \"prune\").  views: 1..1024 dicts with world_to_camera (3x4, OpenCV axes, in the frame "
+        "`coord`), fx, fy, cx, cy, width, height (orbit_views, load_3dgs_cameras).  score 'sum': the blend weight T a "
+        "summed over every pixel of every view (pixel units); 'max': its maximum.  Exactly one rule: keep (a count), "
+        "keep_fraction (K = ceil(f n)) or min_score (keep score >= s).  Ties go by input index.  Returns the kept count, "
+        "or (kept, mask (bool per input point), weight_sum (uint64, pixel units times 2^24), weight_max (float32)) when "
+        "return_scores.  The output equals filter_spz's with the mask.");
+  m.def("orbit_views",
+        [](int n, int width, int height, float fov_y, const py::object &center, const py::object &radius,
+           float distance, const py::object &scene, spz::CoordinateSystem coord) -> py::list {
+          std::array<float, 3> c = {0.0f, 0.0f, 0.0f};
+          float r = 0.0f;
+          if (center.is_none() || radius.is_none()) {
+            if (scene.is_none()) throw py::value_error("give center and radius, or a scene to take them from");
+            std::vector<float> pos;
+            if (py::isinstance<spz::GaussianCloud>(scene)) {
+              pos = scene.cast<const spz::GaussianCloud &>().positions;
+            } else {
+              spz::UnpackOptions u;
+              u.to = coord;
+              spz::GaussianCloud g;
+              if (py::isinstance<py::bytes>(scene)) {
+                const std::string b = scene.cast<std::string>();
+                py::gil_scoped_release release;
+                g = spz::loadSpz(reinterpret_cast<const uint8_t *>(b.data()), static_cast<int32_t>(b.size()), u);
+              } else {
+                const std::string fn = py::str(scene).cast<std::string>();
+                py::gil_scoped_release release;
+                g = spz::loadSpz(fn, u);
+              }
+              if (g.numPoints <= 0) {
+                raiseIfDeviceUnusable();
+                throw py::value_error("orbit_views: the scene has no points, or does not load");
+              }
+              pos.swap(g.positions);
+            }
+            if (!spz::boundingSphere(pos, &c, &r)) throw py::value_error("orbit_views: the scene has no finite positions");
+          }
+          if (!center.is_none()) {
+            const auto cc = center.cast<std::vector<float>>();
+            if (cc.size() != 3) throw py::value_error("center must have three values");
+            for (int k = 0; k < 3; ++k) c[k] = cc[k];
+          }
+          if (!radius.is_none()) r = radius.cast<float>();
+          std::vector<spz::PruneOptions::View> v;
+          try {
+            v = spz::orbitViews(n, c, r, width, height, fov_y, distance);
+          } catch (const std::invalid_argument &e) {
+            throw py::value_error(e.what());
+          }
+          py::list out;
+          for (const auto &x : v) out.append(viewDict(x));
+          return out;
+        },
+        py::arg("n"), py::kw_only(), py::arg("width"), py::arg("height"), py::arg("fov_y"),
+        py::arg("center") = py::none(), py::arg("radius") = py::none(), py::arg("distance") = 2.5f,
+        py::arg("scene") = py::none(), py::arg("coord") = spz::CoordinateSystem::UNSPECIFIED,
+        "n view dicts (prune_spz's form) on a Fibonacci sphere around center at distance * radius, each looking at the "
+        "centre, fov_y in degrees (spz::orbitViews).  Without center or radius they come from the axis-aligned box of "
+        "`scene` (a .spz path, its bytes or a GaussianCloud; files are decoded to `coord`): its centre and half "
+        "diagonal.  Floaters inflate that box: clean first, or pass both.");
+  m.def("load_views_file",
+        [](const std::string &filename) {
+          std::vector<spz::PruneOptions::View> v;
+          try {
+            v = spz::loadViewsFile(filename);
+          } catch (const std::invalid_argument &e) {
+            throw py::value_error(e.what());
+          }
+          py::list out;
+          for (const auto &x : v) out.append(viewDict(x));
+          return out;
+        },
+        py::arg("filename"),
+        "The views of a plain-text views file (spz_prune --views; spz::loadViewsFile) as prune_spz's view dicts: one "
+        "view per line, 'width height fx fy cx cy r00 r01 r02 t0 r10 r11 r12 t1 r20 r21 r22 t2', '#' starts a comment.");
   m.def("clean_spz",
         [](const std::string &input, const std::string &output, const py::object &k, const py::object &std_ratio,
            const py::object &radius, const py::object &min_neighbors, const py::object &return_details) -> py::object {
@@ -1042,4 +1254,6 @@ PYBIND11_MODULE(spz, m) {
           return ok;
         },
         py::arg("gaussians"), py::arg("options"), py::arg("filename"), "Write GaussianCloud data to a *.ply* file.");
+  // the reader of 3DGS's cameras.json is plain Python (spz_amd/cameras.py)
+  m.attr("load_3dgs_cameras") = py::module_::import("spz_amd.cameras").attr("load_3dgs_cameras");
 }

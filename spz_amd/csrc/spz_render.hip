@@ -17,6 +17,8 @@
 //   spz_render_blend_kernel            one 256-lane workgroup per 16x16 tile, one pixel per lane: the tile's records
 //                                      staged in LDS 256 at a time, read by every lane at the same address (a
 //                                      broadcast); the workgroup stops once every lane has stopped.
+//   spz_render_score_kernel            the blend again, pixel for pixel, adding each used pair's weight T a into the
+//                                      Gaussian's u64 sum (as rint(w 2^24)) and f32 max (spz_prune.hip uses it).
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -484,6 +486,130 @@ __global__ __launch_bounds__(kBlendThreads) void spz_render_blend_kernel(const B
   }
 }
 
+namespace {
+
+// Sum and max of a u32 over the 64 lanes of a wave (every lane active): within each row of 16 by DPP (quad xor 1, quad
+// xor 2, half-row mirror, row mirror), then the four rows' values by readlane.  The results are wave-uniform.
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xb1, 0xf, 0xf, false);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4e, 0xf, 0xf, false);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xf, 0xf, false);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xf, 0xf, false);
+  return (uint32_t)__builtin_amdgcn_readlane((int)v, 0) + (uint32_t)__builtin_amdgcn_readlane((int)v, 16) +
+         (uint32_t)__builtin_amdgcn_readlane((int)v, 32) + (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
+}
+
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xb1, 0xf, 0xf, false));
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4e, 0xf, 0xf, false));
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xf, 0xf, false));
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xf, 0xf, false));
+  const uint32_t a = max((uint32_t)__builtin_amdgcn_readlane((int)v, 0), (uint32_t)__builtin_amdgcn_readlane((int)v, 16));
+  const uint32_t b = max((uint32_t)__builtin_amdgcn_readlane((int)v, 32), (uint32_t)__builtin_amdgcn_readlane((int)v, 48));
+  return max(a, b);
+}
+
+}  // namespace
+
+struct ScoreParams {
+  const spz_amd_render_record *rec;
+  const uint32_t *sorted_gid;
+  const uint2 *ranges;
+  const unsigned long long *total;
+  float *image;  // may be null
+  unsigned long long *weight_sum;
+  uint32_t *weight_max;  // the f32 bit patterns (non-negative, so they order as u32)
+  unsigned long long max_entries;
+  uint32_t width, height, tiles_x;
+  float bg[3];
+};
+
+// The blend of spz_render_blend_kernel, pixel for pixel, plus each used (pixel, Gaussian) pair's weight w = T a.  The
+// loop over a batch runs in step across the wave (a stopped lane takes no more pairs) so that each record's
+// q = rint(w 2^24) and w are reduced over the wave by DPP; one lane per wave adds them into the batch's LDS slots
+// (integer LDS atomics), and each slot that was used goes to the Gaussian's u64 sum and u32 max by one global integer
+// atomic each.  Integer sums and maxima do not depend on the order, so the scores repeat their bits.
+__global__ __launch_bounds__(kBlendThreads) void spz_render_score_kernel(const ScoreParams p) {
+  __shared__ float2 s_xy[kBlendThreads];
+  __shared__ float4 s_co[kBlendThreads];   // conic A, B, C, opacity
+  __shared__ float4 s_rgb[kBlendThreads];
+  __shared__ uint32_t s_sum[kBlendThreads], s_max[kBlendThreads];
+  const unsigned long long total = *p.total;
+  if (total > p.max_entries) return;
+  const uint32_t t = threadIdx.x;
+  const uint32_t u = blockIdx.x * kTile + (t % kTile), v = blockIdx.y * kTile + (t / kTile);
+  const bool inside = u < p.width && v < p.height;
+  uint32_t begin = 0, end = 0;
+  if (total != 0ull) {
+    const uint2 r = p.ranges[blockIdx.y * p.tiles_x + blockIdx.x];
+    begin = r.x;
+    end = r.y;
+  }
+  const float fu = (float)u, fv = (float)v;
+  float T = 1.0f, c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
+  bool done = !inside;
+  for (uint32_t base = begin; base < end; base += kBlendThreads) {
+    // also the barrier between the previous batch's reads and this batch's writes
+    if (__syncthreads_count(done ? 1 : 0) == (int)kBlendThreads) break;
+    const uint32_t j = base + t;
+    uint32_t gid = 0;
+    if (j < end) {
+      gid = p.sorted_gid[j];
+      const spz_amd_render_record &q = p.rec[gid];
+      s_xy[t] = make_float2(q.mean[0], q.mean[1]);
+      s_co[t] = make_float4(q.conic[0], q.conic[1], q.conic[2], q.opacity);
+      s_rgb[t] = make_float4(q.rgb[0], q.rgb[1], q.rgb[2], 0.0f);
+    }
+    s_sum[t] = 0u;
+    s_max[t] = 0u;
+    __syncthreads();
+    const uint32_t cnt = (end - base) < kBlendThreads ? end - base : kBlendThreads;
+    for (uint32_t k = 0; k < cnt; ++k) {
+      if (__ballot(!done) == 0ull) break;  // wave-uniform: every lane of the wave has stopped
+      const float2 xy = s_xy[k];
+      const float4 co = s_co[k];
+      const float dx = fu - xy.x, dy = fv - xy.y;
+      const float power = -0.5f * (co.x * dx * dx + co.z * dy * dy) - co.y * dx * dy;
+      const float a = fminf(0.99f, co.w * expf(power));
+      const float Tn = T * (1.0f - a);
+      bool use = !done && !(power > 0.0f) && !(a < 1.0f / 255.0f);
+      if (use && Tn < 1e-4f) {
+        done = true;
+        use = false;
+      }
+      const float w = T * a;
+      if (use) {
+        const float4 rgb = s_rgb[k];
+        c0 = c0 + w * rgb.x;
+        c1 = c1 + w * rgb.y;
+        c2 = c2 + w * rgb.z;
+        T = Tn;
+      }
+      if (__ballot(use) != 0ull) {  // wave-uniform
+        const uint32_t qv = use ? (uint32_t)rintf(w * 16777216.0f) : 0u;
+        const uint32_t wb = use ? __float_as_uint(w) : 0u;
+        const uint32_t sq = wave_sum_u32(qv), mw = wave_max_u32(wb);
+        if ((t & 63u) == 0u) {
+          atomicAdd(&s_sum[k], sq);
+          atomicMax(&s_max[k], mw);
+        }
+      }
+    }
+    __syncthreads();
+    if (j < end && s_sum[t] != 0u) {
+      atomicAdd(p.weight_sum + gid, (unsigned long long)s_sum[t]);
+      atomicMax(p.weight_max + gid, s_max[t]);
+    }
+  }
+  if (inside && p.image) {
+    float *o = p.image + ((unsigned long long)v * p.width + u) * 4u;
+    o[0] = c0 + T * p.bg[0];
+    o[1] = c1 + T * p.bg[1];
+    o[2] = c2 + T * p.bg[2];
+    o[3] = 1.0f - T;
+  }
+}
+
 }  // namespace spz_amd_detail
 
 namespace {
@@ -696,6 +822,28 @@ int blend_impl(uint64_t n, const spz_amd_render_params *params, uint64_t m, floa
   return SPZ_AMD_OK;
 }
 
+int score_impl(uint64_t n, const spz_amd_render_params *params, uint64_t m, float *d_image, uint64_t *d_weight_sum,
+               float *d_weight_max, uint8_t *base, uint8_t *ent, hipStream_t st) {
+  const RenderLayout wl = render_layout(n, m);
+  ScoreParams b = {};
+  b.rec = reinterpret_cast<const spz_amd_render_record *>(base + wl.rec);
+  b.sorted_gid = m ? reinterpret_cast<const uint32_t *>(ent + wl.sorted_gid) : nullptr;
+  b.ranges = m ? reinterpret_cast<const uint2 *>(ent + wl.ranges) : nullptr;  // read only when the total is > 0
+  b.total = reinterpret_cast<const unsigned long long *>(base + wl.total);
+  b.image = d_image;
+  b.weight_sum = reinterpret_cast<unsigned long long *>(d_weight_sum);
+  b.weight_max = reinterpret_cast<uint32_t *>(d_weight_max);
+  b.max_entries = m;
+  b.width = params->width;
+  b.height = params->height;
+  b.tiles_x = (params->width + kTile - 1) / kTile;
+  for (int k = 0; k < 3; ++k) b.bg[k] = params->background[k];
+  const dim3 grid(b.tiles_x, (params->height + kTile - 1) / kTile);
+  hipLaunchKernelGGL(spz_render_score_kernel, grid, dim3(kBlendThreads), 0, st, b);
+  SPZ_HIP_TRY(hipGetLastError());
+  return SPZ_AMD_OK;
+}
+
 int packed_source(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, int coord, PackedSrc *src) {
   if (d_stream == nullptr || hdr == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
   if (hdr->version < 1 || hdr->version > 3) return SPZ_AMD_ERR_VERSION;
@@ -860,6 +1008,25 @@ int spz_amd_render_finish_device(uint64_t num_points, const spz_amd_render_param
   rc = entries_impl(num_points, params, max_entries, d_status, base, ent, st);
   if (rc != SPZ_AMD_OK) return rc;
   return blend_impl(num_points, params, max_entries, d_image, base, ent, st);
+}
+
+int spz_amd_render_score_device(uint64_t num_points, const spz_amd_render_params *params, uint64_t max_entries,
+                                float *d_image, uint64_t *d_weight_sum, float *d_weight_max, uint32_t *d_status,
+                                void *d_workspace, void *hip_stream) {
+  int rc = check_params(params);
+  if (rc != SPZ_AMD_OK) return rc;
+  if (num_points > kMaxEntries || max_entries > kMaxEntries) return SPZ_AMD_ERR_INVALID_ARG;
+  if (d_status == nullptr || d_workspace == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
+  if (num_points && (d_weight_sum == nullptr || d_weight_max == nullptr)) return SPZ_AMD_ERR_INVALID_ARG;
+  int device = 0;
+  rc = current_device(&device);
+  if (rc != SPZ_AMD_OK) return rc;
+  const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  uint8_t *base = align256(d_workspace);
+  uint8_t *ent = base + render_layout(num_points, 0).prefix;
+  rc = entries_impl(num_points, params, max_entries, d_status, base, ent, st);
+  if (rc != SPZ_AMD_OK) return rc;
+  return score_impl(num_points, params, max_entries, d_image, d_weight_sum, d_weight_max, base, ent, st);
 }
 
 int spz_amd_render_host(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr,

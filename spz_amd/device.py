@@ -687,6 +687,88 @@ def render_packed(stream_t, header, params, max_entries=None, out=None, return_i
                    return_info, stream)
 
 
+def _score(source, n, views, dev, max_entries, images, return_status, stream):
+    L = abi.load_library()
+    views = list(views)
+    if not 1 <= len(views) <= abi.PRUNE_MAX_VIEWS:
+        raise ValueError(f"give 1..{abi.PRUNE_MAX_VIEWS} views, got {len(views)}")
+    for k, p in enumerate(views):
+        if not isinstance(p, abi.RenderParams):
+            raise ValueError(f"view {k}: must be an abi.RenderParams (abi.render_params)")
+        if L.spz_amd_render_check_params(C.byref(p)) != abi.OK:
+            raise ValueError(f"view {k}: bad render parameters")
+        if p.coord != views[0].coord:
+            raise ValueError(f"view {k}: coord {p.coord} differs from view 0's {views[0].coord}")
+    if max_entries is not None and (isinstance(max_entries, bool) or not isinstance(max_entries, int)
+                                    or not 0 <= max_entries <= 0x7fffffff):
+        raise ValueError(f"max_entries must be an int in 0..2^31-1, got {max_entries!r}")
+    imgs = []
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        with torch.cuda.stream(st):
+            wsum = torch.zeros(n, dtype=torch.int64, device=dev)
+            wmax = torch.zeros(n, dtype=torch.float32, device=dev)
+            total = torch.empty(1, dtype=torch.int64, device=dev)
+            status = torch.empty(len(views), dtype=torch.int32, device=dev)
+            ws = None
+            prefix = int(L.spz_amd_render_workspace_bytes(n, 0)) - 256
+            for k, p in enumerate(views):
+                if max_entries is None:
+                    # prepare into the current workspace (its prefix is the prepare part), read the total, grow
+                    if ws is None:
+                        ws = torch.empty(prefix + 256, dtype=torch.uint8, device=dev)
+                    _render_prepare(L, source, p, total, None, ws, st)
+                    m = int(total.cpu()[0])  # on st: waits for the prepare step
+                    if m > 0x7fffffff:
+                        raise RuntimeError(f"view {k}: {m} tile entries is above the sort's limit of 2^31 - 1")
+                    need = int(L.spz_amd_render_workspace_bytes(n, m))
+                    if need > ws.numel():
+                        bigger = torch.empty(need, dtype=torch.uint8, device=dev)
+                        _aligned_view(bigger, prefix).copy_(_aligned_view(ws, prefix))
+                        ws = bigger
+                else:
+                    m = max_entries
+                    if ws is None:
+                        ws = torch.empty(int(L.spz_amd_render_workspace_bytes(n, m)), dtype=torch.uint8, device=dev)
+                    _render_prepare(L, source, p, total, None, ws, st)
+                img = None
+                if images:
+                    img = torch.empty((p.height, p.width, 4), dtype=torch.float32, device=dev)
+                    imgs.append(img)
+                rc = L.spz_amd_render_score_device(n, C.byref(p), m, img.data_ptr() if img is not None else None,
+                                                   wsum.data_ptr(), wmax.data_ptr(), status[k:].data_ptr(),
+                                                   ws.data_ptr(), C.c_void_p(st.cuda_stream))
+                abi.check(rc, "spz_amd_render_score_device")
+    out = (wsum, wmax)
+    if images:
+        out += (imgs,)
+    if return_status:
+        out += (status,)
+    return out
+
+
+def score(cloud, num_points, sh_degree, views, antialiased=False, max_entries=None, images=False, return_status=False,
+          stream=None):
+    """Per-Gaussian blend weights of a float cloud over views (spz_amd_render_prepare_cloud_device +
+    spz_amd_render_score_device per view; include/spz_amd.h "render scores"): (weight_sum, weight_max), an int64 tensor
+    (the u64 sums of rint(T a 2^24); below 2^62) and a float32 tensor of n on the device.  views: abi.RenderParams, one
+    coord.  max_entries None: each view's total sizes the workspace (one value read back per view); an int: the
+    workspace is sized for it, and a view whose total is above it adds nothing and gets status 1.  images: also the
+    list of the views' images (bit-identical to render()).  return_status: also the int32 status word of every view.
+    stream: as render()."""
+    ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
+    return _score(("cloud", ptrs, num_points, int(sh_degree), antialiased), num_points, views, dev, max_entries, images,
+                  return_status, stream)
+
+
+def score_packed(stream_t, header, views, max_entries=None, images=False, return_status=False, stream=None):
+    """The scores of a packed device stream (any version), decoded as loadSpz(to = coord) would: bit-identical to
+    score() of the decoded floats.  Otherwise as score()."""
+    _check_stream_tensor(stream_t)
+    return _score(("packed", stream_t, header), header.num_points, views, stream_t.device, max_entries, images,
+                  return_status, stream)
+
+
 def _records(rec_t):
     f = rec_t.view(torch.float32).view(-1, 12)
     r16 = rec_t.view(torch.int16).view(-1, 24)
