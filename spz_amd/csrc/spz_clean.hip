@@ -553,30 +553,6 @@ int cl_threshold(uint32_t n, double std_ratio, const double *d_scores, uint8_t *
   return SPZ_AMD_OK;
 }
 
-struct ClCtx {
-  int device = 0;
-  uint8_t *ws = nullptr;      // workspace, scores, counts, mask, indices, the filter's workspace
-  uint8_t *out = nullptr;
-  uint64_t out_bytes = 0;
-  hipStream_t st = nullptr;
-};
-
-void cl_free(ClCtx *c) {
-  if (c == nullptr) return;
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  (void)hipSetDevice(c->device);
-  if (c->st) (void)hipStreamDestroy(c->st);
-  if (c->ws) (void)hipFree(c->ws);
-  if (c->out) (void)hipFree(c->out);
-  if (prev >= 0) (void)hipSetDevice(prev);
-  delete c;
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 }  // namespace
 
 extern "C" {
@@ -650,12 +626,9 @@ int spz_amd_clean_open(const uint8_t *d_stream, size_t size, const spz_amd_heade
   rc = guard.enter(device);
   if (rc != SPZ_AMD_OK) return rc;
   const auto t0 = std::chrono::steady_clock::now();
-  ClCtx *c = new ClCtx;
-  c->device = device;
-  struct Free {
-    ClCtx *c;
-    ~Free() { cl_free(c); }
-  } on_error{c};
+  PackedResultPtr c;
+  rc = packed_result_open(device, &c);
+  if (rc != SPZ_AMD_OK) return rc;
   const ClLayout wl = cl_layout(n);
   uint64_t off = wl.bytes;
   auto put = [&off](uint64_t bytes) {
@@ -665,10 +638,9 @@ int spz_amd_clean_open(const uint8_t *d_stream, size_t size, const spz_amd_heade
   };
   const uint64_t o_scores = put(n * 8u), o_counts = put(n * 4u), o_mask = put(n), o_idx = put(n * 4u),
                  o_fws = put(spz_amd_filter_workspace_bytes(n));
-  SPZ_HIP_TRY(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
-  SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->ws), off));
-  uint8_t *ws = align_ws(c->ws);
-  uint8_t *raw = c->ws;  // the extra sections are placed from the unaligned base (each is 256-aligned by hipMalloc)
+  SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->block), off));
+  uint8_t *ws = align_ws(c->block);
+  uint8_t *raw = c->block;  // the extra sections are placed from the unaligned base (each is 256-aligned by hipMalloc)
   double *d_scores = stat ? reinterpret_cast<double *>(raw + o_scores) : nullptr;
   uint32_t *d_counts = rad ? reinterpret_cast<uint32_t *>(raw + o_counts) : nullptr;
   uint8_t *d_mask = raw + o_mask;
@@ -702,14 +674,7 @@ int spz_amd_clean_open(const uint8_t *d_stream, size_t size, const spz_amd_heade
     }
   }
   uint64_t kept = 0;
-  rc = spz_amd_select_device(d_stream, size, hdr, nullptr, n ? d_mask : nullptr, d_idx, raw + o_fws, &kept, c->st);
-  if (rc != SPZ_AMD_OK) return rc;
-  spz_amd_layout ol;
-  rc = spz_amd_stream_layout(kept, hdr->sh_degree, (int)hdr->version, &ol);
-  if (rc != SPZ_AMD_OK) return rc;
-  c->out_bytes = ol.total_bytes;
-  SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->out), c->out_bytes));
-  rc = spz_amd_subset_device(d_stream, size, hdr, d_idx, kept, -1, c->out, c->out_bytes, c->st);
+  rc = select_subset_masked(d_stream, size, hdr, d_mask, d_idx, raw + o_fws, c.get(), &kept);
   if (rc != SPZ_AMD_OK) return rc;
   if (h_mask && n) SPZ_HIP_TRY(hipMemcpyAsync(h_mask, d_mask, n, hipMemcpyDeviceToHost, c->st));
   if (h_scores && n) SPZ_HIP_TRY(hipMemcpyAsync(h_scores, d_scores, n * 8u, hipMemcpyDeviceToHost, c->st));
@@ -722,24 +687,14 @@ int spz_amd_clean_open(const uint8_t *d_stream, size_t size, const spz_amd_heade
   if (h_kept) *h_kept = kept;
   if (h_threshold) *h_threshold = stat ? stats.thr : __builtin_nan("");
   *h_out_bytes = c->out_bytes;
-  *ctx = c;
-  on_error.c = nullptr;
+  *ctx = c.release();
   return SPZ_AMD_OK;
 }
 
-int spz_amd_clean_fetch(void *ctx, uint8_t *h_out) {
-  ClCtx *c = static_cast<ClCtx *>(ctx);
-  if (c == nullptr || h_out == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
-  DeviceGuard guard;
-  int rc = guard.enter(c->device);
-  if (rc != SPZ_AMD_OK) return rc;
-  SPZ_HIP_TRY(hipMemcpyAsync(h_out, c->out, c->out_bytes, hipMemcpyDeviceToHost, c->st));
-  SPZ_HIP_TRY(hipStreamSynchronize(c->st));
-  return SPZ_AMD_OK;
-}
+int spz_amd_clean_fetch(void *ctx, uint8_t *h_out) { return packed_result_fetch(ctx, h_out); }
 
-const uint8_t *spz_amd_clean_device_data(void *ctx) { return ctx ? static_cast<ClCtx *>(ctx)->out : nullptr; }
+const uint8_t *spz_amd_clean_device_data(void *ctx) { return packed_result_device_data(ctx); }
 
-void spz_amd_clean_close(void *ctx) { cl_free(static_cast<ClCtx *>(ctx)); }
+void spz_amd_clean_close(void *ctx) { packed_result_close(ctx); }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // spz_common.hpp — pieces shared by the HIP translation units of libspz_amd.so
 // (spz_kernels.hip + spz_abi.hip: pack/unpack/flip kernels and their device entry points; spz_hostpath.hip: the
-// host-pointer entry points; spz_ply_kernels.hip: .ply row shuffles; spz_median.hip; spz_exchange.hip; spz_filter.hip).
+// host-pointer entry points; spz_ply_kernels.hip: .ply row shuffles; spz_median.hip; spz_exchange.hip; the packed
+// operations spz_filter.hip ... spz_prune.hip and their host forms' result).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,6 +12,7 @@
 #include <cstdlib>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <mutex>
 
 #include "spz_amd.h"
@@ -300,6 +302,78 @@ struct DeviceGuard {
     if (active && prev >= 0) (void)hipSetDevice(prev);
   }
 };
+
+inline double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// An operation's output stream in HBM until its close: the ctx of every spz_amd_<op>_open / _fetch / _device_data /
+// _close host form (filter, transform, merge, sort, decimate, clean, prune).  `out` points into one of the allocations.
+struct PackedResult {
+  int device = 0;
+  hipStream_t st = nullptr;
+  uint8_t *block = nullptr;      // the operation's workspace (filter, transform, merge, sort: the output stream too)
+  uint8_t *scratch = nullptr;    // a second workspace (prune: the render's)
+  uint8_t *out_block = nullptr;  // the output stream in an allocation of its own (decimate, clean, prune)
+  uint8_t *out = nullptr;
+  uint64_t out_bytes = 0;
+};
+
+// Synchronise the stream (a failed open may leave work in flight), destroy it, free the allocations, restore the
+// previous device.
+inline void packed_result_free(PackedResult *r) {
+  if (r == nullptr) return;
+  int prev = -1;
+  (void)hipGetDevice(&prev);
+  (void)hipSetDevice(r->device);
+  if (r->st) {
+    (void)hipStreamSynchronize(r->st);
+    (void)hipStreamDestroy(r->st);
+  }
+  for (uint8_t *p : {r->block, r->scratch, r->out_block}) {
+    if (p) (void)hipFree(p);
+  }
+  if (prev >= 0) (void)hipSetDevice(prev);
+  delete r;
+}
+
+struct PackedResultFree {
+  void operator()(PackedResult *r) const { packed_result_free(r); }
+};
+using PackedResultPtr = std::unique_ptr<PackedResult, PackedResultFree>;
+
+// A new result on `device` (the current device) with a non-blocking stream of its own.  An open holds it in `*r` until
+// it succeeds (r->release() becomes the ctx): every error return frees it.
+inline int packed_result_open(int device, PackedResultPtr *r) {
+  r->reset(new PackedResult);
+  (*r)->device = device;
+  SPZ_HIP_TRY(hipStreamCreateWithFlags(&(*r)->st, hipStreamNonBlocking));
+  return SPZ_AMD_OK;
+}
+
+inline int packed_result_fetch(void *ctx, uint8_t *h_out) {
+  PackedResult *r = static_cast<PackedResult *>(ctx);
+  if (r == nullptr || h_out == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
+  DeviceGuard guard;
+  int rc = guard.enter(r->device);
+  if (rc != SPZ_AMD_OK) return rc;
+  SPZ_HIP_TRY(hipMemcpyAsync(h_out, r->out, r->out_bytes, hipMemcpyDeviceToHost, r->st));
+  SPZ_HIP_TRY(hipStreamSynchronize(r->st));
+  return SPZ_AMD_OK;
+}
+
+inline const uint8_t *packed_result_device_data(void *ctx) {
+  return ctx ? static_cast<PackedResult *>(ctx)->out : nullptr;
+}
+
+inline void packed_result_close(void *ctx) { packed_result_free(static_cast<PackedResult *>(ctx)); }
+
+// The points of a packed stream whose d_mask byte is set (clean, prune; d_mask is not read when the stream has no
+// points): their indices into d_idx (n u32) through the filter's selection (d_fws: spz_amd_filter_workspace_bytes(n)),
+// then their subset at the input's degree into r->out_block, a new allocation that becomes r->out.  Enqueues on r->st
+// and waits for the count.  spz_filter.hip.
+int select_subset_masked(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, const uint8_t *d_mask,
+                         uint32_t *d_idx, void *d_fws, PackedResult *r, uint64_t *kept);
 
 
 }  // namespace spz_amd_detail

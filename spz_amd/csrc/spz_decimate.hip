@@ -814,30 +814,6 @@ int dec_run(const spz_amd_header *hdr, int level, uint8_t *ws, const DecLayout &
   }
 }
 
-struct DecCtx {
-  int device = 0;
-  uint8_t *ws = nullptr;      // workspace + the level counts' host copy target
-  uint8_t *out = nullptr;
-  uint64_t out_bytes = 0;
-  hipStream_t st = nullptr;
-};
-
-void dec_free(DecCtx *c) {
-  if (c == nullptr) return;
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  (void)hipSetDevice(c->device);
-  if (c->st) (void)hipStreamDestroy(c->st);
-  if (c->ws) (void)hipFree(c->ws);
-  if (c->out) (void)hipFree(c->out);
-  if (prev >= 0) (void)hipSetDevice(prev);
-  delete c;
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 }  // namespace
 
 extern "C" {
@@ -904,16 +880,12 @@ int spz_amd_decimate_open(const uint8_t *d_stream, size_t size, const spz_amd_he
   rc = guard.enter(device);
   if (rc != SPZ_AMD_OK) return rc;
   const auto t0 = std::chrono::steady_clock::now();
-  DecCtx *c = new DecCtx;
-  c->device = device;
-  struct Free {
-    DecCtx *c;
-    ~Free() { dec_free(c); }
-  } on_error{c};
+  PackedResultPtr c;
+  rc = packed_result_open(device, &c);
+  if (rc != SPZ_AMD_OK) return rc;
   const DecLayout wl = dec_layout(n, hdr->sh_degree);
-  SPZ_HIP_TRY(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
-  SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->ws), wl.bytes));
-  uint8_t *ws = align_ws(c->ws);
+  SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->block), wl.bytes));
+  uint8_t *ws = align_ws(c->block);
   if (n) {
     rc = dec_sort(d_stream, size, hdr, ws, wl, lay, c->st);
     if (rc != SPZ_AMD_OK) return rc;
@@ -940,7 +912,8 @@ int spz_amd_decimate_open(const uint8_t *d_stream, size_t size, const spz_amd_he
   const uint64_t m = counts[L];
   const uint32_t dim = (uint32_t)sh_dim_for_degree(hdr->sh_degree);
   c->out_bytes = out_layout(m, dim).total;
-  SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->out), c->out_bytes));
+  SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->out_block), c->out_bytes));
+  c->out = c->out_block;
   uint32_t *d_parents = h_parents && n ? reinterpret_cast<uint32_t *>(ws + wl.sort_ws) : nullptr;  // the sort is done
   rc = dec_run(hdr, L, ws, wl, lay, c->out, c->out_bytes, d_parents, c->st);
   if (rc != SPZ_AMD_OK) return rc;
@@ -961,24 +934,14 @@ int spz_amd_decimate_open(const uint8_t *d_stream, size_t size, const spz_amd_he
     h_out_hdr->reserved = 0;
   }
   *h_out_bytes = c->out_bytes;
-  *ctx = c;
-  on_error.c = nullptr;
+  *ctx = c.release();
   return SPZ_AMD_OK;
 }
 
-int spz_amd_decimate_fetch(void *ctx, uint8_t *h_out) {
-  DecCtx *c = static_cast<DecCtx *>(ctx);
-  if (c == nullptr || h_out == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
-  DeviceGuard guard;
-  int rc = guard.enter(c->device);
-  if (rc != SPZ_AMD_OK) return rc;
-  SPZ_HIP_TRY(hipMemcpyAsync(h_out, c->out, c->out_bytes, hipMemcpyDeviceToHost, c->st));
-  SPZ_HIP_TRY(hipStreamSynchronize(c->st));
-  return SPZ_AMD_OK;
-}
+int spz_amd_decimate_fetch(void *ctx, uint8_t *h_out) { return packed_result_fetch(ctx, h_out); }
 
-const uint8_t *spz_amd_decimate_device_data(void *ctx) { return ctx ? static_cast<DecCtx *>(ctx)->out : nullptr; }
+const uint8_t *spz_amd_decimate_device_data(void *ctx) { return packed_result_device_data(ctx); }
 
-void spz_amd_decimate_close(void *ctx) { dec_free(static_cast<DecCtx *>(ctx)); }
+void spz_amd_decimate_close(void *ctx) { packed_result_close(ctx); }
 
 }  // extern "C"

@@ -362,30 +362,22 @@ int subset_impl(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr,
   return SPZ_AMD_OK;
 }
 
-struct FilterCtx {
-  int device = 0;
-  uint8_t *block = nullptr;   // one allocation: mask or index list, workspace, output stream
-  uint8_t *out = nullptr;
-  uint64_t out_bytes = 0;
-  hipStream_t st = nullptr;
-};
-
-void filter_free(FilterCtx *c) {
-  if (c == nullptr) return;
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  (void)hipSetDevice(c->device);
-  if (c->st) (void)hipStreamDestroy(c->st);
-  if (c->block) (void)hipFree(c->block);
-  if (prev >= 0) (void)hipSetDevice(prev);
-  delete c;
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 }  // namespace
+
+int spz_amd_detail::select_subset_masked(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr,
+                                         const uint8_t *d_mask, uint32_t *d_idx, void *d_fws, PackedResult *r,
+                                         uint64_t *kept) {
+  *kept = 0;
+  int rc = select_impl(d_stream, size, hdr, nullptr, hdr->num_points ? d_mask : nullptr, d_idx, d_fws, kept, r->st);
+  if (rc != SPZ_AMD_OK) return rc;
+  spz_amd_layout ol;
+  rc = spz_amd_stream_layout(*kept, hdr->sh_degree, (int)hdr->version, &ol);
+  if (rc != SPZ_AMD_OK) return rc;
+  r->out_bytes = ol.total_bytes;
+  SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&r->out_block), r->out_bytes));
+  r->out = r->out_block;
+  return subset_impl(d_stream, size, hdr, d_idx, *kept, -1, r->out, r->out_bytes, r->st);
+}
 
 extern "C" {
 
@@ -428,12 +420,9 @@ int spz_amd_filter_open(const uint8_t *d_stream, size_t size, const spz_amd_head
   rc = guard.enter(device);
   if (rc != SPZ_AMD_OK) return rc;
   const auto t0 = std::chrono::steady_clock::now();
-  FilterCtx *c = new FilterCtx;
-  c->device = device;
-  struct Free {
-    FilterCtx *c;
-    ~Free() { filter_free(c); }
-  } on_error{c};
+  PackedResultPtr c;
+  rc = packed_result_open(device, &c);
+  if (rc != SPZ_AMD_OK) return rc;
   const uint64_t idx_cap = use_indices ? num_indices : n;
   const WorkspaceLayout wl = workspace_layout(n);
   const uint64_t mask_bytes = (!use_indices && h_mask != nullptr) ? n : 0;
@@ -443,7 +432,6 @@ int spz_amd_filter_open(const uint8_t *d_stream, size_t size, const spz_amd_head
   if (rc != SPZ_AMD_OK) return rc;
   const size_t total = Workspace::aligned(idx_cap * 4u) + Workspace::aligned(mask_bytes) +
                        (use_indices ? 0 : Workspace::aligned(wl.bytes)) + Workspace::aligned(most.total_bytes);
-  SPZ_HIP_TRY(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
   SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->block), total));
   uint8_t *q = c->block;
   uint32_t *d_idx = reinterpret_cast<uint32_t *>(q);
@@ -477,26 +465,14 @@ int spz_amd_filter_open(const uint8_t *d_stream, size_t size, const spz_amd_head
   c->out_bytes = out.total_bytes;
   *h_count = count;
   *h_out_bytes = out.total_bytes;
-  *ctx = c;
-  on_error.c = nullptr;
+  *ctx = c.release();
   return SPZ_AMD_OK;
 }
 
-int spz_amd_filter_fetch(void *ctx, uint8_t *h_out) {
-  FilterCtx *c = static_cast<FilterCtx *>(ctx);
-  if (c == nullptr || h_out == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
-  DeviceGuard guard;
-  int rc = guard.enter(c->device);
-  if (rc != SPZ_AMD_OK) return rc;
-  SPZ_HIP_TRY(hipMemcpyAsync(h_out, c->out, c->out_bytes, hipMemcpyDeviceToHost, c->st));
-  SPZ_HIP_TRY(hipStreamSynchronize(c->st));
-  return SPZ_AMD_OK;
-}
+int spz_amd_filter_fetch(void *ctx, uint8_t *h_out) { return packed_result_fetch(ctx, h_out); }
 
-const uint8_t *spz_amd_filter_device_data(void *ctx) {
-  return ctx ? static_cast<FilterCtx *>(ctx)->out : nullptr;
-}
+const uint8_t *spz_amd_filter_device_data(void *ctx) { return packed_result_device_data(ctx); }
 
-void spz_amd_filter_close(void *ctx) { filter_free(static_cast<FilterCtx *>(ctx)); }
+void spz_amd_filter_close(void *ctx) { packed_result_close(ctx); }
 
 }  // extern "C"

@@ -1747,60 +1747,158 @@ GaussianCloud loadSpz(const uint8_t *data, int32_t size, const UnpackOptions &o)
   return unpackFromStream(stream.data(), stream.size(), o);
 }
 
-// ---- filter ------------------------------------------------------------------------------------------------------
+// ---- the packed operations' shared steps -----------------------------------------------------------------------
+// filter, transform, merge, sort, decimate, clean and prune: the input loaded onto the device, spz_amd_<op>_open, the
+// input's device memory released, the result fetched and gzipped from its device copy, closed.  Their file-name forms
+// read the input, call the buffer form and write its file image.
 namespace {
-bool filterRejected(const char *fmt, ...) {
+// The "[SPZ ERROR] <who>: ..." line of a refused call, with `status` left for lastDeviceStatus(); false.
+bool opRejected(const char *who, int status, const char *fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
   char msg[256];
   std::vsnprintf(msg, sizeof(msg), fmt, ap);
   va_end(ap);
-  logLine("[SPZ ERROR] filterSpz: %s", msg);
-  g_last_status = SPZ_AMD_ERR_INVALID_ARG;
+  logLine("[SPZ ERROR] %s: %s", who, msg);
+  g_last_status = status;
   return false;
 }
 
-struct FilterLaps {
-  bool on = std::getenv("SPZ_AMD_FILTER_TIMING") != nullptr;
-  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+// Stage times on stderr while the environment variable `env` is set: "[<who>] <stage> <x> ms".
+class Laps {
+ public:
+  Laps(const char *who, const char *env) : who_(who), on_(std::getenv(env) != nullptr) {}
+  // The time since the last lap (or since construction) as stage `what`.
   void lap(const char *what) {
     const auto now = std::chrono::steady_clock::now();
-    if (on) std::fprintf(stderr, "[filterSpz] %-8s %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
-    t = now;
+    stage(what, std::chrono::duration<double, std::milli>(now - t_).count());
+    t_ = now;
   }
+  // A stage the device timed (an open's h_ms), `note` after the unit.
+  void stage(const char *what, double ms, const char *note = "") const {
+    if (on_) std::fprintf(stderr, "[%s] %-8s %.3f ms%s\n", who_, what, ms, note);
+  }
+
+ private:
+  const char *who_;
+  bool on_;
+  std::chrono::steady_clock::time_point t_ = std::chrono::steady_clock::now();
 };
+
+// The input on the device, or false with "<who>: the input is not a readable .spz" where the load logged no reason.
+bool loadInput(const char *who, const uint8_t *data, int32_t size, DevicePackedGaussians *d) {
+  *d = loadSpzPackedDevice(data, size);
+  if (d->valid()) return true;
+  if (g_last_status == SPZ_AMD_OK) logLine("[SPZ ERROR] %s: the input is not a readable .spz", who);
+  return false;
+}
+
+// The ctx of an operation's spz_amd_<op>_open with the operation's fetch, device_data and close; closed when this goes.
+class OpenResult {
+ public:
+  OpenResult(int (*fetch)(void *, uint8_t *), const uint8_t *(*deviceData)(void *), void (*close)(void *))
+      : fetch_(fetch), deviceData_(deviceData), close_(close) {}
+  OpenResult(const OpenResult &) = delete;
+  OpenResult &operator=(const OpenResult &) = delete;
+  ~OpenResult() { close_(ctx); }
+
+  // The result's `bytes` of stream as a .spz file image in *out, then closed.  The device writer reads the result's own
+  // device copy instead of uploading the host one.  The caller has released the input's device memory by now: the
+  // container stage takes its own.
+  bool finish(const char *who, uint64_t bytes, Laps *laps, std::vector<uint8_t> *out) {
+    std::vector<uint8_t> stream;
+    detail::resizeUninitialized(&stream, static_cast<size_t>(bytes));
+    if (deviceFailed(fetch_(ctx, stream.data()), who)) return false;
+    if (laps) laps->lap("download");
+    if (!compressGzippedWithCopy(stream.data(), stream.size(), out, deviceData_(ctx))) {
+      logLine("[SPZ ERROR] %s: compressGzipped failed", who);
+      return false;
+    }
+    if (laps) laps->lap("gzip");
+    close_(ctx);
+    ctx = nullptr;
+    return true;
+  }
+
+  void *ctx = nullptr;
+
+ private:
+  int (*fetch_)(void *, uint8_t *);
+  const uint8_t *(*deviceData_)(void *);
+  void (*close_)(void *);
+};
+
+// The input file of a file-name form, or false with the reader's line or "<who>: <name> is larger than 2 GiB".
+bool readInput(const char *who, const std::string &filename, std::vector<uint8_t> *data) {
+  if (!readFile(filename, data, /*log=*/true)) return false;
+  if (data->size() > static_cast<size_t>(INT32_MAX)) {
+    return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "%s is larger than 2 GiB", filename.c_str());
+  }
+  return true;
+}
+
+// The file image written, or false with "<who>: unable to write <name>".
+bool writeOutput(const char *who, const std::string &filename, const std::vector<uint8_t> &file) {
+  if (writeFile(filename, file)) return true;
+  logLine("[SPZ ERROR] %s: unable to write %s", who, filename.c_str());
+  return false;
+}
+
+// The file-name form of an operation whose options the caller has checked: the input read, `run` (the buffer form, its
+// results into the caller's temporaries) on its bytes, the file image written as the "write" lap under `env`.  The
+// caller sets its out-parameters from the temporaries only when this returns true.
+template <class Run>
+bool fileToFile(const char *who, const char *env, const std::string &input, const std::string &output, Run run) {
+  std::vector<uint8_t> data;
+  if (!readInput(who, input, &data)) return false;
+  std::vector<uint8_t> file;
+  if (!run(data.data(), static_cast<int32_t>(data.size()), &file)) return false;
+  Laps laps(who, env);
+  if (!writeOutput(who, output, file)) return false;
+  laps.lap("write");
+  return true;
+}
+}  // namespace
+
+// ---- filter ------------------------------------------------------------------------------------------------------
+namespace {
+// Every check that needs no input.
+bool filterOptionsOk(const FilterOptions &f) {
+  const char *who = "filterSpz";
+  const int invalid = SPZ_AMD_ERR_INVALID_ARG;
+  if (f.shDegree < -1 || f.shDegree > 3) return opRejected(who, invalid, "shDegree %d is outside -1 ... 3", f.shDegree);
+  if (f.indices && (f.mask || f.box || f.minAlpha)) return opRejected(who, invalid, "indices cannot be combined with a mask, a box or minAlpha");
+  if (static_cast<int>(f.coord) < 0 || static_cast<int>(f.coord) > 8) return opRejected(who, invalid, "unknown coordinate system %d", static_cast<int>(f.coord));
+  if (f.box) {
+    for (int a = 0; a < 3; ++a) {
+      if (std::isnan(f.box->lo[a]) || std::isnan(f.box->hi[a])) return opRejected(who, invalid, "a box bound is NaN");
+    }
+  }
+  if (f.minAlpha && std::isnan(*f.minAlpha)) return opRejected(who, invalid, "minAlpha is NaN");
+  if (f.indices && f.indices->size() > SPZ_AMD_REFERENCE_MAX_POINTS) {
+    return opRejected(who, invalid, "%zu indices: the reference reads at most %u points", f.indices->size(), SPZ_AMD_REFERENCE_MAX_POINTS);
+  }
+  return true;
+}
 }  // namespace
 
 bool filterSpz(const uint8_t *data, int32_t size, const FilterOptions &f, std::vector<uint8_t> *out, int64_t *kept) {
+  const char *who = "filterSpz";
   g_last_status = SPZ_AMD_OK;
   if (kept) *kept = 0;
   // the arguments first: nothing touches the device before they are known to be good
-  if (out == nullptr) return filterRejected("no output vector");
-  if (f.shDegree < -1 || f.shDegree > 3) return filterRejected("shDegree %d is outside -1 ... 3", f.shDegree);
-  if (f.indices && (f.mask || f.box || f.minAlpha)) return filterRejected("indices cannot be combined with a mask, a box or minAlpha");
-  if (static_cast<int>(f.coord) < 0 || static_cast<int>(f.coord) > 8) return filterRejected("unknown coordinate system %d", static_cast<int>(f.coord));
-  if (f.box) {
-    for (int a = 0; a < 3; ++a) {
-      if (std::isnan(f.box->lo[a]) || std::isnan(f.box->hi[a])) return filterRejected("a box bound is NaN");
-    }
-  }
-  if (f.minAlpha && std::isnan(*f.minAlpha)) return filterRejected("minAlpha is NaN");
-  if (f.indices && f.indices->size() > SPZ_AMD_REFERENCE_MAX_POINTS) {
-    return filterRejected("%zu indices: the reference reads at most %u points", f.indices->size(), SPZ_AMD_REFERENCE_MAX_POINTS);
-  }
-  FilterLaps laps;
-  DevicePackedGaussians d = loadSpzPackedDevice(data, size);
-  if (!d.valid()) {
-    if (g_last_status == SPZ_AMD_OK) logLine("[SPZ ERROR] filterSpz: the input is not a readable .spz");
-    return false;
-  }
+  if (out == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no output vector");
+  if (!filterOptionsOk(f)) return false;
+  Laps laps(who, "SPZ_AMD_FILTER_TIMING");
+  DevicePackedGaussians d;
+  if (!loadInput(who, data, size, &d)) return false;
   laps.lap("inflate");
   const uint32_t n = static_cast<uint32_t>(d.numPoints);
-  if (f.shDegree > d.shDegree) return filterRejected("shDegree %d is above the input's %d", f.shDegree, d.shDegree);
-  if (f.mask && f.mask->size() != n) return filterRejected("the mask has %zu bytes for %u points", f.mask->size(), n);
+  if (f.shDegree > d.shDegree) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "shDegree %d is above the input's %d", f.shDegree, d.shDegree);
+  if (f.mask && f.mask->size() != n) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "the mask has %zu bytes for %u points", f.mask->size(), n);
   if (f.indices) {
     for (const uint32_t i : *f.indices) {
-      if (i >= n) return filterRejected("index %u is out of range for %u points", i, n);
+      if (i >= n) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "index %u is out of range for %u points", i, n);
     }
   }
   const spz_amd_header hdr = headerOf(d);
@@ -1817,32 +1915,18 @@ bool filterSpz(const uint8_t *data, int32_t size, const FilterOptions &f, std::v
     sel.use_min_alpha = 1;
     sel.min_alpha = *f.minAlpha;
   }
-  void *ctx = nullptr;
+  OpenResult r(spz_amd_filter_fetch, spz_amd_filter_device_data, spz_amd_filter_close);
   uint64_t count = 0, bytes = 0;
   float ms[2] = {0.0f, 0.0f};
-  int rc = spz_amd_filter_open(d.stream, d.streamBytes, &hdr, &sel, f.mask ? f.mask->data() : nullptr, f.indices ? 1 : 0,
-                               f.indices ? f.indices->data() : nullptr, f.indices ? f.indices->size() : 0, f.shDegree,
-                               d.device, &ctx, &count, &bytes, ms);
-  if (deviceFailed(rc, "filterSpz")) return false;
-  struct Close {
-    void *c;
-    ~Close() { spz_amd_filter_close(c); }
-  } closer{ctx};
-  if (laps.on) std::fprintf(stderr, "[filterSpz] select   %.3f ms\n[filterSpz] subset   %.3f ms\n", ms[0], ms[1]);
+  const int rc = spz_amd_filter_open(d.stream, d.streamBytes, &hdr, &sel, f.mask ? f.mask->data() : nullptr, f.indices ? 1 : 0,
+                                     f.indices ? f.indices->data() : nullptr, f.indices ? f.indices->size() : 0, f.shDegree,
+                                     d.device, &r.ctx, &count, &bytes, ms);
+  if (deviceFailed(rc, who)) return false;
+  laps.stage("select", ms[0]);
+  laps.stage("subset", ms[1]);
   laps.lap("filter");
-  d.release();  // the input's device memory goes before the container stage takes its own
-  std::vector<uint8_t> stream;
-  detail::resizeUninitialized(&stream, static_cast<size_t>(bytes));
-  rc = spz_amd_filter_fetch(ctx, stream.data());
-  if (deviceFailed(rc, "filterSpz")) return false;
-  laps.lap("download");
-  // the device copy of the stream is this call's (not spz_amd_encode_host_keep's kept buffer): the device writer reads it
-  // instead of uploading the host copy; it lives until `closer` runs
-  if (!compressGzippedWithCopy(stream.data(), stream.size(), out, spz_amd_filter_device_data(ctx))) {
-    logLine("[SPZ ERROR] filterSpz: compressGzipped failed");
-    return false;
-  }
-  laps.lap("gzip");
+  d.release();
+  if (!r.finish(who, bytes, &laps, out)) return false;
   if (kept) *kept = static_cast<int64_t>(count);
   return true;
 }
@@ -1850,123 +1934,73 @@ bool filterSpz(const uint8_t *data, int32_t size, const FilterOptions &f, std::v
 bool filterSpz(const std::string &inputFilename, const std::string &outputFilename, const FilterOptions &f, int64_t *kept) {
   g_last_status = SPZ_AMD_OK;
   if (kept) *kept = 0;
-  std::vector<uint8_t> data;
-  if (!readFile(inputFilename, &data, /*log=*/true)) return false;
-  if (data.size() > static_cast<size_t>(INT32_MAX)) return filterRejected("%s is larger than 2 GiB", inputFilename.c_str());
-  std::vector<uint8_t> file;
+  if (!filterOptionsOk(f)) return false;
   int64_t k = 0;
-  if (!filterSpz(data.data(), static_cast<int32_t>(data.size()), f, &file, &k)) return false;
-  FilterLaps laps;
-  if (!writeFile(outputFilename, file)) {
-    logLine("[SPZ ERROR] filterSpz: unable to write %s", outputFilename.c_str());
+  if (!fileToFile("filterSpz", "SPZ_AMD_FILTER_TIMING", inputFilename, outputFilename,
+                  [&](const uint8_t *data, int32_t size, std::vector<uint8_t> *file) { return filterSpz(data, size, f, file, &k); })) {
     return false;
   }
-  laps.lap("write");
   if (kept) *kept = k;
   return true;
 }
 
 // ---- transform ---------------------------------------------------------------------------------------------------
 namespace {
-bool transformRejected(const char *who, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  char msg[256];
-  std::vsnprintf(msg, sizeof(msg), fmt, ap);
-  va_end(ap);
-  logLine("[SPZ ERROR] %s: %s", who, msg);
-  g_last_status = SPZ_AMD_ERR_INVALID_ARG;
-  return false;
-}
-
-struct TransformLaps {
-  bool on = std::getenv("SPZ_AMD_TRANSFORM_TIMING") != nullptr;
-  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-  void lap(const char *what) {
-    const auto now = std::chrono::steady_clock::now();
-    if (on) std::fprintf(stderr, "[transformSpz] %-9s %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
-    t = now;
-  }
-};
-
 // The parameter block of `o`, or false + the [SPZ ERROR] line: every check that needs no device.
 bool transformBlock(const char *who, const TransformOptions &o, bool packed, spz_amd_transform *xf) {
-  if (static_cast<int>(o.coord) < 0 || static_cast<int>(o.coord) > 8) return transformRejected(who, "unknown coordinate system %d", static_cast<int>(o.coord));
-  if (packed && (o.fractionalBits < 0 || o.fractionalBits > 24)) return transformRejected(who, "fractionalBits %d is outside 0 ... 24", o.fractionalBits);
+  const int invalid = SPZ_AMD_ERR_INVALID_ARG;
+  if (static_cast<int>(o.coord) < 0 || static_cast<int>(o.coord) > 8) return opRejected(who, invalid, "unknown coordinate system %d", static_cast<int>(o.coord));
+  if (packed && (o.fractionalBits < 0 || o.fractionalBits > 24)) return opRejected(who, invalid, "fractionalBits %d is outside 0 ... 24", o.fractionalBits);
   if (spz_amd_transform_params(o.rotation.data(), o.translation.data(), o.scale, static_cast<int>(o.coord), xf) != SPZ_AMD_OK) {
-    return transformRejected(who, "the rotation must be finite and nonzero, the translation finite, the scale finite and > 0");
+    return opRejected(who, invalid, "the rotation must be finite and nonzero, the translation finite, the scale finite and > 0");
   }
   return true;
+}
+
+// A placement's positions that did not fit 24 bits: refused.
+bool outOfRange(const char *who, uint64_t bad, uint32_t points, int fractionalBits) {
+  return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "%llu of %u points have a position that does not fit 24 bits at %d fractional bits "
+                    "(lower fractionalBits)", static_cast<unsigned long long>(bad), points, fractionalBits);
 }
 }  // namespace
 
 bool transformSpz(const uint8_t *data, int32_t size, const TransformOptions &o, std::vector<uint8_t> *out) {
+  const char *who = "transformSpz";
   g_last_status = SPZ_AMD_OK;
   // the arguments first: nothing touches the device before they are known to be good
-  if (out == nullptr) return transformRejected("transformSpz", "no output vector");
+  if (out == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no output vector");
   spz_amd_transform xf;
-  if (!transformBlock("transformSpz", o, true, &xf)) return false;
-  TransformLaps laps;
-  DevicePackedGaussians d = loadSpzPackedDevice(data, size);
-  if (!d.valid()) {
-    if (g_last_status == SPZ_AMD_OK) logLine("[SPZ ERROR] transformSpz: the input is not a readable .spz");
-    return false;
-  }
+  if (!transformBlock(who, o, true, &xf)) return false;
+  Laps laps(who, "SPZ_AMD_TRANSFORM_TIMING");
+  DevicePackedGaussians d;
+  if (!loadInput(who, data, size, &d)) return false;
   laps.lap("inflate");
   const spz_amd_header hdr = headerOf(d);
-  void *ctx = nullptr;
+  OpenResult r(spz_amd_transform_fetch, spz_amd_transform_device_data, spz_amd_transform_close);
   uint64_t bytes = 0, bad = 0;
   float ms = 0.0f;
-  int rc = spz_amd_transform_open(d.stream, d.streamBytes, &hdr, &xf, o.fractionalBits, d.device, &ctx, &bytes, &bad, &ms);
-  if (deviceFailed(rc, "transformSpz")) return false;
-  struct Close {
-    void *c;
-    ~Close() { spz_amd_transform_close(c); }
-  } closer{ctx};
-  if (laps.on) std::fprintf(stderr, "[transformSpz] kernel    %.3f ms\n", ms);
+  const int rc = spz_amd_transform_open(d.stream, d.streamBytes, &hdr, &xf, o.fractionalBits, d.device, &r.ctx, &bytes, &bad, &ms);
+  if (deviceFailed(rc, who)) return false;
+  laps.stage("kernel", ms);
   laps.lap("transform");
-  if (bad > 0) {
-    return transformRejected("transformSpz", "%llu of %u points have a position that does not fit 24 bits at %d fractional bits "
-                             "(lower fractionalBits)", static_cast<unsigned long long>(bad), hdr.num_points, o.fractionalBits);
-  }
-  d.release();  // the input's device memory goes before the container stage takes its own
-  std::vector<uint8_t> stream;
-  detail::resizeUninitialized(&stream, static_cast<size_t>(bytes));
-  rc = spz_amd_transform_fetch(ctx, stream.data());
-  if (deviceFailed(rc, "transformSpz")) return false;
-  laps.lap("download");
-  // the device copy of the stream is this call's: the device writer reads it instead of uploading the host copy
-  if (!compressGzippedWithCopy(stream.data(), stream.size(), out, spz_amd_transform_device_data(ctx))) {
-    logLine("[SPZ ERROR] transformSpz: compressGzipped failed");
-    return false;
-  }
-  laps.lap("gzip");
-  return true;
+  if (bad > 0) return outOfRange(who, bad, hdr.num_points, o.fractionalBits);
+  d.release();
+  return r.finish(who, bytes, &laps, out);
 }
 
 bool transformSpz(const std::string &inputFilename, const std::string &outputFilename, const TransformOptions &o) {
   g_last_status = SPZ_AMD_OK;
   spz_amd_transform xf;
   if (!transformBlock("transformSpz", o, true, &xf)) return false;
-  std::vector<uint8_t> data;
-  if (!readFile(inputFilename, &data, /*log=*/true)) return false;
-  if (data.size() > static_cast<size_t>(INT32_MAX)) return transformRejected("transformSpz", "%s is larger than 2 GiB", inputFilename.c_str());
-  std::vector<uint8_t> file;
-  if (!transformSpz(data.data(), static_cast<int32_t>(data.size()), o, &file)) return false;
-  TransformLaps laps;
-  if (!writeFile(outputFilename, file)) {
-    logLine("[SPZ ERROR] transformSpz: unable to write %s", outputFilename.c_str());
-    return false;
-  }
-  laps.lap("write");
-  return true;
+  return fileToFile("transformSpz", "SPZ_AMD_TRANSFORM_TIMING", inputFilename, outputFilename,
+                    [&](const uint8_t *data, int32_t size, std::vector<uint8_t> *file) { return transformSpz(data, size, o, file); });
 }
 
 bool transformCloud(GaussianCloud &g, const TransformOptions &o) {
   g_last_status = SPZ_AMD_OK;
   spz_amd_transform xf;
   if (!transformBlock("transformCloud", o, false, &xf)) return false;
-  if (!checkSizes(g)) return transformRejected("transformCloud", "the cloud's arrays do not match numPoints / shDegree");
+  if (!checkSizes(g)) return opRejected("transformCloud", SPZ_AMD_ERR_INVALID_ARG, "the cloud's arrays do not match numPoints / shDegree");
   const int rc = spz_amd_transform_cloud_host(g.positions.data(), g.scales.data(), g.rotations.data(),
                                               g.sh.empty() ? nullptr : g.sh.data(), static_cast<uint64_t>(g.numPoints),
                                               g.shDegree, &xf, deviceIndex());
@@ -1978,19 +2012,21 @@ namespace {
 // The placement blocks of `o` for k inputs (nullopt: none), or false + the [SPZ ERROR] line: every check that needs no
 // device and no header.
 bool mergeArguments(size_t k, const MergeOptions &o, std::vector<std::optional<spz_amd_transform>> *xfs) {
-  if (k == 0) return transformRejected("mergeSpz", "no inputs");
-  if (k > SPZ_AMD_MERGE_MAX_INPUTS) return transformRejected("mergeSpz", "%zu inputs: at most %u can be merged", k, SPZ_AMD_MERGE_MAX_INPUTS);
-  if (o.shDegree < -1 || o.shDegree > 3) return transformRejected("mergeSpz", "shDegree %d is outside -1 ... 3", o.shDegree);
-  if (o.fractionalBits < -1 || o.fractionalBits > 24) return transformRejected("mergeSpz", "fractionalBits %d is outside -1 ... 24", o.fractionalBits);
-  if (o.antialiased < -1 || o.antialiased > 1) return transformRejected("mergeSpz", "antialiased %d is not -1, 0 or 1", o.antialiased);
+  const char *who = "mergeSpz";
+  const int invalid = SPZ_AMD_ERR_INVALID_ARG;
+  if (k == 0) return opRejected(who, invalid, "no inputs");
+  if (k > SPZ_AMD_MERGE_MAX_INPUTS) return opRejected(who, invalid, "%zu inputs: at most %u can be merged", k, SPZ_AMD_MERGE_MAX_INPUTS);
+  if (o.shDegree < -1 || o.shDegree > 3) return opRejected(who, invalid, "shDegree %d is outside -1 ... 3", o.shDegree);
+  if (o.fractionalBits < -1 || o.fractionalBits > 24) return opRejected(who, invalid, "fractionalBits %d is outside -1 ... 24", o.fractionalBits);
+  if (o.antialiased < -1 || o.antialiased > 1) return opRejected(who, invalid, "antialiased %d is not -1, 0 or 1", o.antialiased);
   if (!o.transforms.empty() && o.transforms.size() != k) {
-    return transformRejected("mergeSpz", "%zu transforms for %zu inputs (give none or one per input)", o.transforms.size(), k);
+    return opRejected(who, invalid, "%zu transforms for %zu inputs (give none or one per input)", o.transforms.size(), k);
   }
   xfs->assign(k, std::nullopt);
   for (size_t i = 0; i < o.transforms.size(); ++i) {
     if (!o.transforms[i]) continue;
     spz_amd_transform xf;
-    if (!transformBlock("mergeSpz", *o.transforms[i], false, &xf)) return false;
+    if (!transformBlock(who, *o.transforms[i], false, &xf)) return false;
     (*xfs)[i] = xf;
   }
   return true;
@@ -1998,33 +2034,36 @@ bool mergeArguments(size_t k, const MergeOptions &o, std::vector<std::optional<s
 
 // spz_amd_merge_resolve's refusals, each with its reason.
 bool mergeResolved(const std::vector<spz_amd_header> &h, const MergeOptions &o, spz_amd_header *oh) {
+  const char *who = "mergeSpz";
+  const int invalid = SPZ_AMD_ERR_INVALID_ARG;
   const int rc = spz_amd_merge_resolve(h.data(), h.size(), o.shDegree, o.fractionalBits, o.antialiased, oh, nullptr);
   if (rc == SPZ_AMD_OK) return true;
   uint64_t total = 0;
   for (const spz_amd_header &x : h) total += x.num_points;
   if (rc == SPZ_AMD_ERR_TOO_MANY_POINTS) {
-    return transformRejected("mergeSpz", "%llu points in all: the reference reads at most %u", static_cast<unsigned long long>(total),
-                             SPZ_AMD_REFERENCE_MAX_POINTS);
+    return opRejected(who, invalid, "%llu points in all: the reference reads at most %u", static_cast<unsigned long long>(total),
+                      SPZ_AMD_REFERENCE_MAX_POINTS);
   }
   for (size_t i = 1; i < h.size() && o.antialiased < 0; ++i) {
     if ((h[i].flags & 1) != (h[0].flags & 1)) {
-      return transformRejected("mergeSpz", "input 0 has antialiased = %d and input %zu has antialiased = %d (set antialiased)",
-                               h[0].flags & 1, i, h[i].flags & 1);
+      return opRejected(who, invalid, "input 0 has antialiased = %d and input %zu has antialiased = %d (set antialiased)",
+                        h[0].flags & 1, i, h[i].flags & 1);
     }
   }
-  return transformRejected("mergeSpz", "the inputs cannot be merged (%s)", spz_amd_status_string(rc));
+  return opRejected(who, invalid, "the inputs cannot be merged (%s)", spz_amd_status_string(rc));
 }
 }  // namespace
 
 bool mergeSpz(const std::vector<std::vector<uint8_t>> &inputs, const MergeOptions &o, std::vector<uint8_t> *out, int64_t *points) {
+  const char *who = "mergeSpz";
   g_last_status = SPZ_AMD_OK;
   if (points) *points = 0;
   // the arguments first: nothing touches the device before they are known to be good
-  if (out == nullptr) return transformRejected("mergeSpz", "no output vector");
+  if (out == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no output vector");
   std::vector<std::optional<spz_amd_transform>> xfs;
   if (!mergeArguments(inputs.size(), o, &xfs)) return false;
   for (size_t i = 0; i < inputs.size(); ++i) {
-    if (inputs[i].size() > static_cast<size_t>(INT32_MAX)) return transformRejected("mergeSpz", "input %zu is larger than 2 GiB", i);
+    if (inputs[i].size() > static_cast<size_t>(INT32_MAX)) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "input %zu is larger than 2 GiB", i);
   }
   const size_t k = inputs.size();
   std::vector<DevicePackedGaussians> d(k);
@@ -2041,34 +2080,19 @@ bool mergeSpz(const std::vector<std::vector<uint8_t>> &inputs, const MergeOption
   if (!mergeResolved(hdrs, o, &oh)) return false;
   std::vector<spz_amd_merge_input> in(k);
   for (size_t i = 0; i < k; ++i) {
-    if (d[i].device != d[0].device) return transformRejected("mergeSpz", "the inputs were loaded on different devices");
+    if (d[i].device != d[0].device) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "the inputs were loaded on different devices");
     in[i].d_stream = d[i].stream;
     in[i].size = d[i].streamBytes;
     in[i].hdr = hdrs[i];
     in[i].xf = xfs[i] ? &*xfs[i] : nullptr;
   }
-  void *ctx = nullptr;
+  OpenResult r(spz_amd_merge_fetch, spz_amd_merge_device_data, spz_amd_merge_close);
   uint64_t bytes = 0, bad = 0;
-  int rc = spz_amd_merge_open(in.data(), k, o.shDegree, o.fractionalBits, o.antialiased, d[0].device, &ctx, &oh, &bytes, &bad, nullptr);
-  if (deviceFailed(rc, "mergeSpz")) return false;
-  struct Close {
-    void *c;
-    ~Close() { spz_amd_merge_close(c); }
-  } closer{ctx};
-  if (bad > 0) {
-    return transformRejected("mergeSpz", "%llu of %u points have a position that does not fit 24 bits at %d fractional bits "
-                             "(lower fractionalBits)", static_cast<unsigned long long>(bad), oh.num_points, oh.fractional_bits);
-  }
-  d.clear();  // the inputs' device memory goes before the container stage takes its own
-  std::vector<uint8_t> stream;
-  detail::resizeUninitialized(&stream, static_cast<size_t>(bytes));
-  rc = spz_amd_merge_fetch(ctx, stream.data());
-  if (deviceFailed(rc, "mergeSpz")) return false;
-  // the device copy of the stream is this call's: the device writer reads it instead of uploading the host copy
-  if (!compressGzippedWithCopy(stream.data(), stream.size(), out, spz_amd_merge_device_data(ctx))) {
-    logLine("[SPZ ERROR] mergeSpz: compressGzipped failed");
-    return false;
-  }
+  const int rc = spz_amd_merge_open(in.data(), k, o.shDegree, o.fractionalBits, o.antialiased, d[0].device, &r.ctx, &oh, &bytes, &bad, nullptr);
+  if (deviceFailed(rc, who)) return false;
+  if (bad > 0) return outOfRange(who, bad, oh.num_points, oh.fractional_bits);
+  d.clear();
+  if (!r.finish(who, bytes, nullptr, out)) return false;
   if (points) *points = oh.num_points;
   return true;
 }
@@ -2085,90 +2109,56 @@ bool mergeSpz(const std::vector<std::string> &inputFilenames, const std::string 
   }
   std::vector<uint8_t> file;
   int64_t n = 0;
-  if (!mergeSpz(data, o, &file, &n)) return false;
-  if (!writeFile(outputFilename, file)) {
-    logLine("[SPZ ERROR] mergeSpz: unable to write %s", outputFilename.c_str());
-    return false;
-  }
+  if (!mergeSpz(data, o, &file, &n) || !writeOutput("mergeSpz", outputFilename, file)) return false;
   if (points) *points = n;
   return true;
 }
 
 // ---- sort --------------------------------------------------------------------------------------------------------
 namespace {
-bool sortRejected(int status, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  char msg[256];
-  std::vsnprintf(msg, sizeof(msg), fmt, ap);
-  va_end(ap);
-  logLine("[SPZ ERROR] sortSpz: %s", msg);
-  g_last_status = status;
-  return false;
-}
-
-struct SortLaps {
-  bool on = std::getenv("SPZ_AMD_SORT_TIMING") != nullptr;
-  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-  void lap(const char *what) {
-    const auto now = std::chrono::steady_clock::now();
-    if (on) std::fprintf(stderr, "[sortSpz] %-8s %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
-    t = now;
+bool sortOptionsOk(const SortOptions &o) {
+  if (o.keys && o.keys->size() > SPZ_AMD_REFERENCE_MAX_POINTS) {
+    return opRejected("sortSpz", SPZ_AMD_ERR_INVALID_ARG, "%zu keys: the reference reads at most %u points", o.keys->size(),
+                      SPZ_AMD_REFERENCE_MAX_POINTS);
   }
-};
+  return true;
+}
 }  // namespace
 
 bool sortSpz(const uint8_t *data, int32_t size, const SortOptions &o, std::vector<uint8_t> *out,
              std::vector<uint32_t> *order) {
+  const char *who = "sortSpz";
   g_last_status = SPZ_AMD_OK;
   if (order) order->clear();
-  if (out == nullptr) return sortRejected(SPZ_AMD_ERR_INVALID_ARG, "no output vector");
-  if (o.keys && o.keys->size() > SPZ_AMD_REFERENCE_MAX_POINTS) {
-    return sortRejected(SPZ_AMD_ERR_INVALID_ARG, "%zu keys: the reference reads at most %u points", o.keys->size(),
-                        SPZ_AMD_REFERENCE_MAX_POINTS);
-  }
-  SortLaps laps;
-  DevicePackedGaussians d = loadSpzPackedDevice(data, size);
-  if (!d.valid()) {
-    if (g_last_status == SPZ_AMD_OK) logLine("[SPZ ERROR] sortSpz: the input is not a readable .spz");
-    return false;
-  }
+  if (out == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no output vector");
+  if (!sortOptionsOk(o)) return false;
+  Laps laps(who, "SPZ_AMD_SORT_TIMING");
+  DevicePackedGaussians d;
+  if (!loadInput(who, data, size, &d)) return false;
   laps.lap("inflate");
   const uint64_t n = static_cast<uint64_t>(d.numPoints);
   if (o.keys && o.keys->size() != n) {
-    return sortRejected(SPZ_AMD_ERR_INVALID_ARG, "%zu keys for %llu points", o.keys->size(), (unsigned long long)n);
+    return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "%zu keys for %llu points", o.keys->size(), (unsigned long long)n);
   }
   if (!o.keys && d.version == 1) {
-    return sortRejected(SPZ_AMD_ERR_UNSUPPORTED,
-                        "a version 1 file has float16 positions and no Morton key; transformSpz with the identity "
-                        "writes a v3 copy");
+    return opRejected(who, SPZ_AMD_ERR_UNSUPPORTED,
+                      "a version 1 file has float16 positions and no Morton key; transformSpz with the identity "
+                      "writes a v3 copy");
   }
   const spz_amd_header hdr = headerOf(d);
   std::vector<uint32_t> ord;
   if (order) detail::resizeUninitialized(&ord, static_cast<size_t>(n));
-  void *ctx = nullptr;
+  OpenResult r(spz_amd_sort_fetch, spz_amd_sort_device_data, spz_amd_sort_close);
   uint64_t bytes = 0;
   float ms[2] = {0.0f, 0.0f};
-  int rc = spz_amd_sort_open(d.stream, d.streamBytes, &hdr, o.keys ? o.keys->data() : nullptr, o.descending ? 1 : 0,
-                             d.device, &ctx, &bytes, order ? ord.data() : nullptr, ms);
-  if (deviceFailed(rc, "sortSpz")) return false;
-  struct Close {
-    void *c;
-    ~Close() { spz_amd_sort_close(c); }
-  } closer{ctx};
-  if (laps.on) std::fprintf(stderr, "[sortSpz] order    %.3f ms\n[sortSpz] subset   %.3f ms\n", ms[0], ms[1]);
+  const int rc = spz_amd_sort_open(d.stream, d.streamBytes, &hdr, o.keys ? o.keys->data() : nullptr, o.descending ? 1 : 0,
+                                   d.device, &r.ctx, &bytes, order ? ord.data() : nullptr, ms);
+  if (deviceFailed(rc, who)) return false;
+  laps.stage("order", ms[0]);
+  laps.stage("subset", ms[1]);
   laps.lap("sort");
-  d.release();  // the input's device memory goes before the container stage takes its own
-  std::vector<uint8_t> stream;
-  detail::resizeUninitialized(&stream, static_cast<size_t>(bytes));
-  rc = spz_amd_sort_fetch(ctx, stream.data());
-  if (deviceFailed(rc, "sortSpz")) return false;
-  laps.lap("download");
-  if (!compressGzippedWithCopy(stream.data(), stream.size(), out, spz_amd_sort_device_data(ctx))) {
-    logLine("[SPZ ERROR] sortSpz: compressGzipped failed");
-    return false;
-  }
-  laps.lap("gzip");
+  d.release();
+  if (!r.finish(who, bytes, &laps, out)) return false;
   if (order) order->swap(ord);
   return true;
 }
@@ -2177,111 +2167,68 @@ bool sortSpz(const std::string &inputFilename, const std::string &outputFilename
              std::vector<uint32_t> *order) {
   g_last_status = SPZ_AMD_OK;
   if (order) order->clear();
-  std::vector<uint8_t> data;
-  if (!readFile(inputFilename, &data, /*log=*/true)) return false;
-  if (data.size() > static_cast<size_t>(INT32_MAX)) {
-    return sortRejected(SPZ_AMD_ERR_INVALID_ARG, "%s is larger than 2 GiB", inputFilename.c_str());
-  }
-  std::vector<uint8_t> file;
+  if (!sortOptionsOk(o)) return false;
   std::vector<uint32_t> ord;
-  if (!sortSpz(data.data(), static_cast<int32_t>(data.size()), o, &file, order ? &ord : nullptr)) return false;
-  SortLaps laps;
-  if (!writeFile(outputFilename, file)) {
-    logLine("[SPZ ERROR] sortSpz: unable to write %s", outputFilename.c_str());
+  if (!fileToFile("sortSpz", "SPZ_AMD_SORT_TIMING", inputFilename, outputFilename,
+                  [&](const uint8_t *data, int32_t size, std::vector<uint8_t> *file) {
+                    return sortSpz(data, size, o, file, order ? &ord : nullptr);
+                  })) {
     return false;
   }
-  laps.lap("write");
   if (order) order->swap(ord);
   return true;
 }
 
 // ---- decimate ----------------------------------------------------------------------------------------------------
 namespace {
-bool decimateRejected(int status, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  char msg[256];
-  std::vsnprintf(msg, sizeof(msg), fmt, ap);
-  va_end(ap);
-  logLine("[SPZ ERROR] decimateSpz: %s", msg);
-  g_last_status = status;
-  return false;
-}
-
-struct DecimateLaps {
-  bool on = std::getenv("SPZ_AMD_DECIMATE_TIMING") != nullptr;
-  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-  void lap(const char *what) {
-    const auto now = std::chrono::steady_clock::now();
-    if (on) std::fprintf(stderr, "[decimateSpz] %-8s %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
-    t = now;
-  }
-};
-
 // Exactly one of the two, each in range.
 bool decimateOptionsOk(const DecimateOptions &o) {
+  const char *who = "decimateSpz";
+  const int invalid = SPZ_AMD_ERR_INVALID_ARG;
   if (o.level.has_value() == o.targetPoints.has_value()) {
-    return decimateRejected(SPZ_AMD_ERR_INVALID_ARG, "exactly one of level and targetPoints must be set");
+    return opRejected(who, invalid, "exactly one of level and targetPoints must be set");
   }
-  if (o.level && (*o.level < 0 || *o.level > 24)) {
-    return decimateRejected(SPZ_AMD_ERR_INVALID_ARG, "level %d is outside 0..24", *o.level);
-  }
-  if (o.targetPoints && *o.targetPoints == 0) return decimateRejected(SPZ_AMD_ERR_INVALID_ARG, "targetPoints must be >= 1");
+  if (o.level && (*o.level < 0 || *o.level > 24)) return opRejected(who, invalid, "level %d is outside 0..24", *o.level);
+  if (o.targetPoints && *o.targetPoints == 0) return opRejected(who, invalid, "targetPoints must be >= 1");
   return true;
 }
 }  // namespace
 
 bool decimateSpz(const uint8_t *data, int32_t size, const DecimateOptions &o, std::vector<uint8_t> *out,
                  std::vector<uint32_t> *parents, int *level, int64_t *points) {
+  const char *who = "decimateSpz";
   g_last_status = SPZ_AMD_OK;
   if (parents) parents->clear();
-  if (out == nullptr) return decimateRejected(SPZ_AMD_ERR_INVALID_ARG, "no output vector");
+  if (out == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no output vector");
   if (!decimateOptionsOk(o)) return false;
-  DecimateLaps laps;
-  DevicePackedGaussians d = loadSpzPackedDevice(data, size);
-  if (!d.valid()) {
-    if (g_last_status == SPZ_AMD_OK) logLine("[SPZ ERROR] decimateSpz: the input is not a readable .spz");
-    return false;
-  }
+  Laps laps(who, "SPZ_AMD_DECIMATE_TIMING");
+  DevicePackedGaussians d;
+  if (!loadInput(who, data, size, &d)) return false;
   laps.lap("inflate");
   if (d.version == 1) {
-    return decimateRejected(SPZ_AMD_ERR_UNSUPPORTED,
-                            "a version 1 file has float16 positions and no integer cell; transformSpz with the "
-                            "identity writes a v3 copy");
+    return opRejected(who, SPZ_AMD_ERR_UNSUPPORTED,
+                      "a version 1 file has float16 positions and no integer cell; transformSpz with the "
+                      "identity writes a v3 copy");
   }
   const uint64_t n = static_cast<uint64_t>(d.numPoints);
   const spz_amd_header hdr = headerOf(d);
   std::vector<uint32_t> par;
   if (parents) detail::resizeUninitialized(&par, static_cast<size_t>(n));
-  void *ctx = nullptr;
+  OpenResult r(spz_amd_decimate_fetch, spz_amd_decimate_device_data, spz_amd_decimate_close);
   uint64_t bytes = 0;
   int used = -1;
   spz_amd_header outHdr = {};
   float ms[3] = {0.0f, 0.0f, 0.0f};
-  int rc = spz_amd_decimate_open(d.stream, d.streamBytes, &hdr, o.level ? *o.level : -1,
-                                 o.targetPoints ? *o.targetPoints : 0, d.device, &ctx, &bytes, &used, &outHdr,
-                                 parents ? par.data() : nullptr, ms);
-  if (deviceFailed(rc, "decimateSpz")) return false;
-  struct Close {
-    void *c;
-    ~Close() { spz_amd_decimate_close(c); }
-  } closer{ctx};
-  if (laps.on) {
-    std::fprintf(stderr, "[decimateSpz] sort     %.3f ms\n[decimateSpz] levels   %.3f ms\n[decimateSpz] reduce   %.3f ms\n",
-                 ms[0], ms[1], ms[2]);
-  }
+  const int rc = spz_amd_decimate_open(d.stream, d.streamBytes, &hdr, o.level ? *o.level : -1,
+                                       o.targetPoints ? *o.targetPoints : 0, d.device, &r.ctx, &bytes, &used, &outHdr,
+                                       parents ? par.data() : nullptr, ms);
+  if (deviceFailed(rc, who)) return false;
+  laps.stage("sort", ms[0]);
+  laps.stage("levels", ms[1]);
+  laps.stage("reduce", ms[2]);
   laps.lap("decimate");
-  d.release();  // the input's device memory goes before the container stage takes its own
-  std::vector<uint8_t> stream;
-  detail::resizeUninitialized(&stream, static_cast<size_t>(bytes));
-  rc = spz_amd_decimate_fetch(ctx, stream.data());
-  if (deviceFailed(rc, "decimateSpz")) return false;
-  laps.lap("download");
-  if (!compressGzippedWithCopy(stream.data(), stream.size(), out, spz_amd_decimate_device_data(ctx))) {
-    logLine("[SPZ ERROR] decimateSpz: compressGzipped failed");
-    return false;
-  }
-  laps.lap("gzip");
+  d.release();
+  if (!r.finish(who, bytes, &laps, out)) return false;
   if (parents) parents->swap(par);
   if (level) *level = used;
   if (points) *points = outHdr.num_points;
@@ -2293,24 +2240,15 @@ bool decimateSpz(const std::string &inputFilename, const std::string &outputFile
   g_last_status = SPZ_AMD_OK;
   if (parents) parents->clear();
   if (!decimateOptionsOk(o)) return false;
-  std::vector<uint8_t> data;
-  if (!readFile(inputFilename, &data, /*log=*/true)) return false;
-  if (data.size() > static_cast<size_t>(INT32_MAX)) {
-    return decimateRejected(SPZ_AMD_ERR_INVALID_ARG, "%s is larger than 2 GiB", inputFilename.c_str());
-  }
-  std::vector<uint8_t> file;
   std::vector<uint32_t> par;
   int used = -1;
   int64_t count = 0;
-  if (!decimateSpz(data.data(), static_cast<int32_t>(data.size()), o, &file, parents ? &par : nullptr, &used, &count)) {
+  if (!fileToFile("decimateSpz", "SPZ_AMD_DECIMATE_TIMING", inputFilename, outputFilename,
+                  [&](const uint8_t *data, int32_t size, std::vector<uint8_t> *file) {
+                    return decimateSpz(data, size, o, file, parents ? &par : nullptr, &used, &count);
+                  })) {
     return false;
   }
-  DecimateLaps laps;
-  if (!writeFile(outputFilename, file)) {
-    logLine("[SPZ ERROR] decimateSpz: unable to write %s", outputFilename.c_str());
-    return false;
-  }
-  laps.lap("write");
   if (parents) parents->swap(par);
   if (level) *level = used;
   if (points) *points = count;
@@ -2319,42 +2257,19 @@ bool decimateSpz(const std::string &inputFilename, const std::string &outputFile
 
 // ---- clean -------------------------------------------------------------------------------------------------------
 namespace {
-bool cleanRejected(int status, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  char msg[256];
-  std::vsnprintf(msg, sizeof(msg), fmt, ap);
-  va_end(ap);
-  logLine("[SPZ ERROR] cleanSpz: %s", msg);
-  g_last_status = status;
-  return false;
-}
-
-struct CleanLaps {
-  bool on = std::getenv("SPZ_AMD_CLEAN_TIMING") != nullptr;
-  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-  void lap(const char *what) {
-    const auto now = std::chrono::steady_clock::now();
-    if (on) std::fprintf(stderr, "[cleanSpz] %-8s %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
-    t = now;
-  }
-};
-
 // At least one rule, each in range.
 bool cleanOptionsOk(const CleanOptions &o) {
-  if (!o.statistical && !o.radius) return cleanRejected(SPZ_AMD_ERR_INVALID_ARG, "set statistical, radius or both");
+  const char *who = "cleanSpz";
+  const int invalid = SPZ_AMD_ERR_INVALID_ARG;
+  if (!o.statistical && !o.radius) return opRejected(who, invalid, "set statistical, radius or both");
   if (o.statistical) {
-    if (o.statistical->k < 1 || o.statistical->k > 64) {
-      return cleanRejected(SPZ_AMD_ERR_INVALID_ARG, "k %d is outside 1..64", o.statistical->k);
-    }
-    if (!std::isfinite(o.statistical->stdRatio)) return cleanRejected(SPZ_AMD_ERR_INVALID_ARG, "stdRatio must be finite");
+    if (o.statistical->k < 1 || o.statistical->k > 64) return opRejected(who, invalid, "k %d is outside 1..64", o.statistical->k);
+    if (!std::isfinite(o.statistical->stdRatio)) return opRejected(who, invalid, "stdRatio must be finite");
   }
   if (o.radius) {
-    if (!std::isfinite(o.radius->radius) || !(o.radius->radius > 0.0)) {
-      return cleanRejected(SPZ_AMD_ERR_INVALID_ARG, "radius must be finite and > 0");
-    }
+    if (!std::isfinite(o.radius->radius) || !(o.radius->radius > 0.0)) return opRejected(who, invalid, "radius must be finite and > 0");
     if (o.radius->minNeighbors < 1 || o.radius->minNeighbors > 256) {
-      return cleanRejected(SPZ_AMD_ERR_INVALID_ARG, "minNeighbors %d is outside 1..256", o.radius->minNeighbors);
+      return opRejected(who, invalid, "minNeighbors %d is outside 1..256", o.radius->minNeighbors);
     }
   }
   return true;
@@ -2363,22 +2278,20 @@ bool cleanOptionsOk(const CleanOptions &o) {
 
 bool cleanSpz(const uint8_t *data, int32_t size, const CleanOptions &o, std::vector<uint8_t> *out, int64_t *kept,
               std::vector<uint8_t> *keepMask, std::vector<double> *scores, double *threshold) {
+  const char *who = "cleanSpz";
   g_last_status = SPZ_AMD_OK;
   if (keepMask) keepMask->clear();
   if (scores) scores->clear();
-  if (out == nullptr) return cleanRejected(SPZ_AMD_ERR_INVALID_ARG, "no output vector");
+  if (out == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no output vector");
   if (!cleanOptionsOk(o)) return false;
-  CleanLaps laps;
-  DevicePackedGaussians d = loadSpzPackedDevice(data, size);
-  if (!d.valid()) {
-    if (g_last_status == SPZ_AMD_OK) logLine("[SPZ ERROR] cleanSpz: the input is not a readable .spz");
-    return false;
-  }
+  Laps laps(who, "SPZ_AMD_CLEAN_TIMING");
+  DevicePackedGaussians d;
+  if (!loadInput(who, data, size, &d)) return false;
   laps.lap("inflate");
   if (d.version == 1) {
-    return cleanRejected(SPZ_AMD_ERR_UNSUPPORTED,
-                         "a version 1 file has float16 positions and no integer distances; transformSpz with the "
-                         "identity writes a v3 copy");
+    return opRejected(who, SPZ_AMD_ERR_UNSUPPORTED,
+                      "a version 1 file has float16 positions and no integer distances; transformSpz with the "
+                      "identity writes a v3 copy");
   }
   const uint64_t n = static_cast<uint64_t>(d.numPoints);
   const spz_amd_header hdr = headerOf(d);
@@ -2386,36 +2299,22 @@ bool cleanSpz(const uint8_t *data, int32_t size, const CleanOptions &o, std::vec
   std::vector<double> sc;
   if (keepMask) detail::resizeUninitialized(&mask, static_cast<size_t>(n));
   if (scores && o.statistical) detail::resizeUninitialized(&sc, static_cast<size_t>(n));
-  void *ctx = nullptr;
+  OpenResult r(spz_amd_clean_fetch, spz_amd_clean_device_data, spz_amd_clean_close);
   uint64_t bytes = 0, count = 0;
   double thr = 0.0;
   float ms[3] = {0.0f, 0.0f, 0.0f};
-  int rc = spz_amd_clean_open(d.stream, d.streamBytes, &hdr, o.statistical ? o.statistical->k : 0,
-                              o.statistical ? o.statistical->stdRatio : 0.0, o.radius ? o.radius->radius : 0.0,
-                              o.radius ? static_cast<uint32_t>(o.radius->minNeighbors) : 0u, d.device, &ctx, &bytes,
-                              &count, &thr, keepMask ? mask.data() : nullptr,
-                              scores && o.statistical ? sc.data() : nullptr, ms);
-  if (deviceFailed(rc, "cleanSpz")) return false;
-  struct Close {
-    void *c;
-    ~Close() { spz_amd_clean_close(c); }
-  } closer{ctx};
-  if (laps.on) {
-    std::fprintf(stderr, "[cleanSpz] sort     %.3f ms\n[cleanSpz] search   %.3f ms\n[cleanSpz] subset   %.3f ms\n",
-                 ms[0], ms[1], ms[2]);
-  }
+  const int rc = spz_amd_clean_open(d.stream, d.streamBytes, &hdr, o.statistical ? o.statistical->k : 0,
+                                    o.statistical ? o.statistical->stdRatio : 0.0, o.radius ? o.radius->radius : 0.0,
+                                    o.radius ? static_cast<uint32_t>(o.radius->minNeighbors) : 0u, d.device, &r.ctx, &bytes,
+                                    &count, &thr, keepMask ? mask.data() : nullptr,
+                                    scores && o.statistical ? sc.data() : nullptr, ms);
+  if (deviceFailed(rc, who)) return false;
+  laps.stage("sort", ms[0]);
+  laps.stage("search", ms[1]);
+  laps.stage("subset", ms[2]);
   laps.lap("clean");
-  d.release();  // the input's device memory goes before the container stage takes its own
-  std::vector<uint8_t> stream;
-  detail::resizeUninitialized(&stream, static_cast<size_t>(bytes));
-  rc = spz_amd_clean_fetch(ctx, stream.data());
-  if (deviceFailed(rc, "cleanSpz")) return false;
-  laps.lap("download");
-  if (!compressGzippedWithCopy(stream.data(), stream.size(), out, spz_amd_clean_device_data(ctx))) {
-    logLine("[SPZ ERROR] cleanSpz: compressGzipped failed");
-    return false;
-  }
-  laps.lap("gzip");
+  d.release();
+  if (!r.finish(who, bytes, &laps, out)) return false;
   if (kept) *kept = static_cast<int64_t>(count);
   if (keepMask) keepMask->swap(mask);
   if (scores) scores->swap(sc);
@@ -2429,25 +2328,16 @@ bool cleanSpz(const std::string &inputFilename, const std::string &outputFilenam
   if (keepMask) keepMask->clear();
   if (scores) scores->clear();
   if (!cleanOptionsOk(o)) return false;
-  std::vector<uint8_t> data;
-  if (!readFile(inputFilename, &data, /*log=*/true)) return false;
-  if (data.size() > static_cast<size_t>(INT32_MAX)) {
-    return cleanRejected(SPZ_AMD_ERR_INVALID_ARG, "%s is larger than 2 GiB", inputFilename.c_str());
-  }
-  std::vector<uint8_t> file, mask;
+  std::vector<uint8_t> mask;
   std::vector<double> sc;
   int64_t count = 0;
   double thr = 0.0;
-  if (!cleanSpz(data.data(), static_cast<int32_t>(data.size()), o, &file, &count, keepMask ? &mask : nullptr,
-                scores ? &sc : nullptr, &thr)) {
+  if (!fileToFile("cleanSpz", "SPZ_AMD_CLEAN_TIMING", inputFilename, outputFilename,
+                  [&](const uint8_t *data, int32_t size, std::vector<uint8_t> *file) {
+                    return cleanSpz(data, size, o, file, &count, keepMask ? &mask : nullptr, scores ? &sc : nullptr, &thr);
+                  })) {
     return false;
   }
-  CleanLaps laps;
-  if (!writeFile(outputFilename, file)) {
-    logLine("[SPZ ERROR] cleanSpz: unable to write %s", outputFilename.c_str());
-    return false;
-  }
-  laps.lap("write");
   if (kept) *kept = count;
   if (keepMask) keepMask->swap(mask);
   if (scores) scores->swap(sc);
@@ -2457,21 +2347,10 @@ bool cleanSpz(const std::string &inputFilename, const std::string &outputFilenam
 
 // ---- render ------------------------------------------------------------------------------------------------------
 namespace {
-bool renderRejected(int status, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  char msg[256];
-  std::vsnprintf(msg, sizeof(msg), fmt, ap);
-  va_end(ap);
-  logLine("[SPZ ERROR] renderSpz: %s", msg);
-  g_last_status = status;
-  return false;
-}
-
 bool renderParams(const RenderOptions &o, spz_amd_render_params *p) {
   *p = spz_amd_render_params{};
   if (o.width < 1 || o.width > 16384 || o.height < 1 || o.height > 16384) {
-    return renderRejected(SPZ_AMD_ERR_INVALID_ARG, "image size %d x %d is outside 1..16384", o.width, o.height);
+    return opRejected("renderSpz", SPZ_AMD_ERR_INVALID_ARG, "image size %d x %d is outside 1..16384", o.width, o.height);
   }
   for (int k = 0; k < 12; ++k) p->world_to_camera[k] = o.worldToCamera[k];
   p->fx = o.fx;
@@ -2485,30 +2364,28 @@ bool renderParams(const RenderOptions &o, spz_amd_render_params *p) {
   p->max_sh_degree = o.maxShDegree;
   p->coord = static_cast<int32_t>(o.coord);
   if (spz_amd_render_check_params(p) != SPZ_AMD_OK) {
-    return renderRejected(SPZ_AMD_ERR_INVALID_ARG,
-                          "bad camera: R must be a rotation (to 1e-4), fx, fy > 0, nearPlane > 0, values finite, "
-                          "maxShDegree 0..3");
+    return opRejected("renderSpz", SPZ_AMD_ERR_INVALID_ARG,
+                      "bad camera: R must be a rotation (to 1e-4), fx, fy > 0, nearPlane > 0, values finite, "
+                      "maxShDegree 0..3");
   }
   return true;
 }
 
 void renderTiming(const float *ms, uint64_t entries) {
-  if (std::getenv("SPZ_AMD_RENDER_TIMING") == nullptr) return;
-  std::fprintf(stderr, "[renderSpz] preprocess %.3f ms\n[renderSpz] entries    %.3f ms (%llu)\n[renderSpz] blend      %.3f ms\n",
-               ms[0], ms[1], static_cast<unsigned long long>(entries), ms[2]);
+  const Laps laps("renderSpz", "SPZ_AMD_RENDER_TIMING");
+  laps.stage("preprocess", ms[0]);
+  laps.stage("entries", ms[1], (" (" + std::to_string(entries) + ")").c_str());
+  laps.stage("blend", ms[2]);
 }
 }  // namespace
 
 bool renderSpz(const uint8_t *data, int32_t size, const RenderOptions &o, std::vector<float> *rgba, int64_t *entries) {
   g_last_status = SPZ_AMD_OK;
-  if (rgba == nullptr) return renderRejected(SPZ_AMD_ERR_INVALID_ARG, "no output vector");
+  if (rgba == nullptr) return opRejected("renderSpz", SPZ_AMD_ERR_INVALID_ARG, "no output vector");
   spz_amd_render_params p;
   if (!renderParams(o, &p)) return false;
-  DevicePackedGaussians d = loadSpzPackedDevice(data, size);
-  if (!d.valid()) {
-    if (g_last_status == SPZ_AMD_OK) logLine("[SPZ ERROR] renderSpz: the input is not a readable .spz");
-    return false;
-  }
+  DevicePackedGaussians d;
+  if (!loadInput("renderSpz", data, size, &d)) return false;
   const spz_amd_header hdr = headerOf(d);
   std::vector<float> img;
   detail::resizeUninitialized(&img, static_cast<size_t>(o.width) * static_cast<size_t>(o.height) * 4u);
@@ -2527,16 +2404,13 @@ bool renderSpz(const std::string &filename, const RenderOptions &o, std::vector<
   spz_amd_render_params p;
   if (!renderParams(o, &p)) return false;
   std::vector<uint8_t> data;
-  if (!readFile(filename, &data, /*log=*/true)) return false;
-  if (data.size() > static_cast<size_t>(INT32_MAX)) {
-    return renderRejected(SPZ_AMD_ERR_INVALID_ARG, "%s is larger than 2 GiB", filename.c_str());
-  }
+  if (!readInput("renderSpz", filename, &data)) return false;
   return renderSpz(data.data(), static_cast<int32_t>(data.size()), o, rgba, entries);
 }
 
 bool renderCloud(const GaussianCloud &g, const RenderOptions &o, std::vector<float> *rgba, int64_t *entries) {
   g_last_status = SPZ_AMD_OK;
-  if (rgba == nullptr) return renderRejected(SPZ_AMD_ERR_INVALID_ARG, "no output vector");
+  if (rgba == nullptr) return opRejected("renderSpz", SPZ_AMD_ERR_INVALID_ARG, "no output vector");
   spz_amd_render_params p;
   if (!renderParams(o, &p)) return false;
   const size_t n = g.numPoints < 0 ? 0 : static_cast<size_t>(g.numPoints);
@@ -2544,7 +2418,7 @@ bool renderCloud(const GaussianCloud &g, const RenderOptions &o, std::vector<flo
   if (g.numPoints < 0 || sd < 0 || g.positions.size() != n * 3 || g.scales.size() != n * 3 ||
       g.rotations.size() != n * 4 || g.alphas.size() != n || g.colors.size() != n * 3 ||
       g.sh.size() != n * static_cast<size_t>(sd) * 3) {
-    return renderRejected(SPZ_AMD_ERR_INVALID_ARG, "the cloud's arrays do not match numPoints and shDegree");
+    return opRejected("renderSpz", SPZ_AMD_ERR_INVALID_ARG, "the cloud's arrays do not match numPoints and shDegree");
   }
   spz_amd_cloud_in c = {g.positions.data(), g.scales.data(), g.rotations.data(), g.alphas.data(), g.colors.data(),
                         sd ? g.sh.data() : nullptr};
@@ -2601,51 +2475,29 @@ std::array<float, 12> lookAt(const std::array<float, 3> &eye, const std::array<f
 
 // ---- prune -------------------------------------------------------------------------------------------------------
 namespace {
-bool pruneRejected(int status, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  char msg[256];
-  std::vsnprintf(msg, sizeof(msg), fmt, ap);
-  va_end(ap);
-  logLine("[SPZ ERROR] pruneSpz: %s", msg);
-  g_last_status = status;
-  return false;
-}
-
-struct PruneLaps {
-  bool on = std::getenv("SPZ_AMD_PRUNE_TIMING") != nullptr;
-  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-  void lap(const char *what) {
-    const auto now = std::chrono::steady_clock::now();
-    if (on) std::fprintf(stderr, "[pruneSpz] %-8s %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
-    t = now;
-  }
-};
-
 // The views as render params, and exactly one rule in range (keepCount's upper bound needs n: checked later).
 bool pruneOptionsOk(const PruneOptions &o, std::vector<spz_amd_render_params> *params) {
+  const char *who = "pruneSpz";
+  const int invalid = SPZ_AMD_ERR_INVALID_ARG;
   const int rules = (o.keepCount ? 1 : 0) + (o.keepFraction ? 1 : 0) + (o.minScore ? 1 : 0);
-  if (rules != 1) return pruneRejected(SPZ_AMD_ERR_INVALID_ARG, "set exactly one of keepCount, keepFraction, minScore");
+  if (rules != 1) return opRejected(who, invalid, "set exactly one of keepCount, keepFraction, minScore");
   if (o.keepCount && *o.keepCount < 0) {
-    return pruneRejected(SPZ_AMD_ERR_INVALID_ARG, "keepCount %lld is negative", static_cast<long long>(*o.keepCount));
+    return opRejected(who, invalid, "keepCount %lld is negative", static_cast<long long>(*o.keepCount));
   }
   if (o.keepFraction && !(*o.keepFraction >= 0.0 && *o.keepFraction <= 1.0)) {
-    return pruneRejected(SPZ_AMD_ERR_INVALID_ARG, "keepFraction must be in [0, 1]");
+    return opRejected(who, invalid, "keepFraction must be in [0, 1]");
   }
-  if (o.minScore && !std::isfinite(*o.minScore)) return pruneRejected(SPZ_AMD_ERR_INVALID_ARG, "minScore must be finite");
-  if (o.score != PruneOptions::Sum && o.score != PruneOptions::Max) {
-    return pruneRejected(SPZ_AMD_ERR_INVALID_ARG, "score must be Sum or Max");
-  }
+  if (o.minScore && !std::isfinite(*o.minScore)) return opRejected(who, invalid, "minScore must be finite");
+  if (o.score != PruneOptions::Sum && o.score != PruneOptions::Max) return opRejected(who, invalid, "score must be Sum or Max");
   if (o.views.empty() || o.views.size() > SPZ_AMD_PRUNE_MAX_VIEWS) {
-    return pruneRejected(SPZ_AMD_ERR_INVALID_ARG, "%zu views: give 1..%d", o.views.size(), SPZ_AMD_PRUNE_MAX_VIEWS);
+    return opRejected(who, invalid, "%zu views: give 1..%d", o.views.size(), SPZ_AMD_PRUNE_MAX_VIEWS);
   }
   params->assign(o.views.size(), spz_amd_render_params{});
   for (size_t v = 0; v < o.views.size(); ++v) {
     const PruneOptions::View &w = o.views[v];
     spz_amd_render_params &p = (*params)[v];
     if (w.width < 1 || w.width > 16384 || w.height < 1 || w.height > 16384) {
-      return pruneRejected(SPZ_AMD_ERR_INVALID_ARG, "view %zu: image size %d x %d is outside 1..16384", v, w.width,
-                           w.height);
+      return opRejected(who, invalid, "view %zu: image size %d x %d is outside 1..16384", v, w.width, w.height);
     }
     for (int k = 0; k < 12; ++k) p.world_to_camera[k] = w.worldToCamera[k];
     p.fx = w.fx;
@@ -2658,9 +2510,9 @@ bool pruneOptionsOk(const PruneOptions &o, std::vector<spz_amd_render_params> *p
     p.max_sh_degree = 0;  // colours do not change a weight
     p.coord = static_cast<int32_t>(o.coord);
     if (spz_amd_render_check_params(&p) != SPZ_AMD_OK) {
-      return pruneRejected(SPZ_AMD_ERR_INVALID_ARG,
-                           "view %zu: bad camera: R must be a rotation (to 1e-4), fx, fy > 0, nearPlane > 0, values "
-                           "finite, coord valid", v);
+      return opRejected(who, invalid,
+                        "view %zu: bad camera: R must be a rotation (to 1e-4), fx, fy > 0, nearPlane > 0, values "
+                        "finite, coord valid", v);
     }
   }
   return true;
@@ -2669,24 +2521,22 @@ bool pruneOptionsOk(const PruneOptions &o, std::vector<spz_amd_render_params> *p
 
 bool pruneSpz(const uint8_t *data, int32_t size, const PruneOptions &o, std::vector<uint8_t> *out, int64_t *kept,
               std::vector<uint8_t> *keepMask, std::vector<uint64_t> *weightSum, std::vector<float> *weightMax) {
+  const char *who = "pruneSpz";
   g_last_status = SPZ_AMD_OK;
   if (keepMask) keepMask->clear();
   if (weightSum) weightSum->clear();
   if (weightMax) weightMax->clear();
-  if (out == nullptr) return pruneRejected(SPZ_AMD_ERR_INVALID_ARG, "no output vector");
+  if (out == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no output vector");
   std::vector<spz_amd_render_params> params;
   if (!pruneOptionsOk(o, &params)) return false;
-  PruneLaps laps;
-  DevicePackedGaussians d = loadSpzPackedDevice(data, size);
-  if (!d.valid()) {
-    if (g_last_status == SPZ_AMD_OK) logLine("[SPZ ERROR] pruneSpz: the input is not a readable .spz");
-    return false;
-  }
+  Laps laps(who, "SPZ_AMD_PRUNE_TIMING");
+  DevicePackedGaussians d;
+  if (!loadInput(who, data, size, &d)) return false;
   laps.lap("inflate");
   const uint64_t n = static_cast<uint64_t>(d.numPoints);
   if (o.keepCount && static_cast<uint64_t>(*o.keepCount) > n) {
-    return pruneRejected(SPZ_AMD_ERR_INVALID_ARG, "keepCount %lld is above the %llu points",
-                         static_cast<long long>(*o.keepCount), static_cast<unsigned long long>(n));
+    return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "keepCount %lld is above the %llu points",
+                      static_cast<long long>(*o.keepCount), static_cast<unsigned long long>(n));
   }
   const spz_amd_header hdr = headerOf(d);
   std::vector<uint8_t> mask;
@@ -2698,39 +2548,23 @@ bool pruneSpz(const uint8_t *data, int32_t size, const PruneOptions &o, std::vec
   const int rule = o.keepCount ? SPZ_AMD_PRUNE_KEEP_COUNT : o.keepFraction ? SPZ_AMD_PRUNE_KEEP_FRACTION
                                                                            : SPZ_AMD_PRUNE_MIN_SCORE;
   const double value = o.keepCount ? static_cast<double>(*o.keepCount) : o.keepFraction ? *o.keepFraction : *o.minScore;
-  void *ctx = nullptr;
+  OpenResult r(spz_amd_prune_fetch, spz_amd_prune_device_data, spz_amd_prune_close);
   uint64_t bytes = 0, count = 0;
   float ms[3] = {0.0f, 0.0f, 0.0f};
   int32_t bad = -1;
-  int rc = spz_amd_prune_open(d.stream, d.streamBytes, &hdr, params.data(), static_cast<int>(params.size()),
-                              static_cast<int>(o.score), rule, value, d.device, &ctx, &bytes, &count,
-                              keepMask ? mask.data() : nullptr, weightSum ? sums.data() : nullptr,
-                              weightMax ? maxima.data() : nullptr, ms, &bad);
-  if (rc == SPZ_AMD_ERR_CAPACITY && bad >= 0) {
-    return pruneRejected(rc, "view %d: more than 2^31 - 1 tile entries", bad);
-  }
+  const int rc = spz_amd_prune_open(d.stream, d.streamBytes, &hdr, params.data(), static_cast<int>(params.size()),
+                                    static_cast<int>(o.score), rule, value, d.device, &r.ctx, &bytes, &count,
+                                    keepMask ? mask.data() : nullptr, weightSum ? sums.data() : nullptr,
+                                    weightMax ? maxima.data() : nullptr, ms, &bad);
+  if (rc == SPZ_AMD_ERR_CAPACITY && bad >= 0) return opRejected(who, rc, "view %d: more than 2^31 - 1 tile entries", bad);
   if (rc != SPZ_AMD_OK && bad >= 0) logLine("[SPZ ERROR] pruneSpz: view %d failed", bad);
-  if (deviceFailed(rc, "pruneSpz")) return false;
-  struct Close {
-    void *c;
-    ~Close() { spz_amd_prune_close(c); }
-  } closer{ctx};
-  if (laps.on) {
-    std::fprintf(stderr, "[pruneSpz] score    %.3f ms (%zu views)\n[pruneSpz] rank     %.3f ms\n[pruneSpz] subset   %.3f ms\n",
-                 ms[0], params.size(), ms[1], ms[2]);
-  }
+  if (deviceFailed(rc, who)) return false;
+  laps.stage("score", ms[0], (" (" + std::to_string(params.size()) + " views)").c_str());
+  laps.stage("rank", ms[1]);
+  laps.stage("subset", ms[2]);
   laps.lap("prune");
-  d.release();  // the input's device memory goes before the container stage takes its own
-  std::vector<uint8_t> stream;
-  detail::resizeUninitialized(&stream, static_cast<size_t>(bytes));
-  rc = spz_amd_prune_fetch(ctx, stream.data());
-  if (deviceFailed(rc, "pruneSpz")) return false;
-  laps.lap("download");
-  if (!compressGzippedWithCopy(stream.data(), stream.size(), out, spz_amd_prune_device_data(ctx))) {
-    logLine("[SPZ ERROR] pruneSpz: compressGzipped failed");
-    return false;
-  }
-  laps.lap("gzip");
+  d.release();
+  if (!r.finish(who, bytes, &laps, out)) return false;
   if (kept) *kept = static_cast<int64_t>(count);
   if (keepMask) keepMask->swap(mask);
   if (weightSum) weightSum->swap(sums);
@@ -2747,25 +2581,17 @@ bool pruneSpz(const std::string &inputFilename, const std::string &outputFilenam
   if (weightMax) weightMax->clear();
   std::vector<spz_amd_render_params> params;
   if (!pruneOptionsOk(o, &params)) return false;
-  std::vector<uint8_t> data;
-  if (!readFile(inputFilename, &data, /*log=*/true)) return false;
-  if (data.size() > static_cast<size_t>(INT32_MAX)) {
-    return pruneRejected(SPZ_AMD_ERR_INVALID_ARG, "%s is larger than 2 GiB", inputFilename.c_str());
-  }
-  std::vector<uint8_t> file, mask;
+  std::vector<uint8_t> mask;
   std::vector<uint64_t> sums;
   std::vector<float> maxima;
   int64_t count = 0;
-  if (!pruneSpz(data.data(), static_cast<int32_t>(data.size()), o, &file, &count, keepMask ? &mask : nullptr,
-                weightSum ? &sums : nullptr, weightMax ? &maxima : nullptr)) {
+  if (!fileToFile("pruneSpz", "SPZ_AMD_PRUNE_TIMING", inputFilename, outputFilename,
+                  [&](const uint8_t *data, int32_t size, std::vector<uint8_t> *file) {
+                    return pruneSpz(data, size, o, file, &count, keepMask ? &mask : nullptr, weightSum ? &sums : nullptr,
+                                    weightMax ? &maxima : nullptr);
+                  })) {
     return false;
   }
-  PruneLaps laps;
-  if (!writeFile(outputFilename, file)) {
-    logLine("[SPZ ERROR] pruneSpz: unable to write %s", outputFilename.c_str());
-    return false;
-  }
-  laps.lap("write");
   if (kept) *kept = count;
   if (keepMask) keepMask->swap(mask);
   if (weightSum) weightSum->swap(sums);

@@ -399,26 +399,6 @@ int merge_impl(const spz_amd_merge_input *inputs, uint64_t k, const spz_amd_head
   return SPZ_AMD_OK;
 }
 
-struct MergeCtx {
-  int device = 0;
-  uint8_t *block = nullptr;   // the output stream, the table, then the out-of-range count
-  uint8_t *out = nullptr;
-  uint64_t out_bytes = 0;
-  hipStream_t st = nullptr;
-};
-
-void merge_free(MergeCtx *c) {
-  if (c == nullptr) return;
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  (void)hipSetDevice(c->device);
-  if (c->st) (void)hipStreamSynchronize(c->st);   // a failed open may leave the table copy in flight
-  if (c->st) (void)hipStreamDestroy(c->st);
-  if (c->block) (void)hipFree(c->block);
-  if (prev >= 0) (void)hipSetDevice(prev);
-  delete c;
-}
-
 }  // namespace
 
 extern "C" {
@@ -456,15 +436,11 @@ int spz_amd_merge_open(const spz_amd_merge_input *inputs, uint64_t k, int sh_deg
   DeviceGuard guard;
   rc = guard.enter(device);
   if (rc != SPZ_AMD_OK) return rc;
-  MergeCtx *c = new MergeCtx;
-  c->device = device;
-  struct Free {
-    MergeCtx *c;
-    ~Free() { merge_free(c); }
-  } on_error{c};
+  PackedResultPtr c;
+  rc = packed_result_open(device, &c);
+  if (rc != SPZ_AMD_OK) return rc;
   const size_t stream_bytes = Workspace::aligned(bytes);
   const size_t table_bytes = Workspace::aligned(table_layout(k).bytes);
-  SPZ_HIP_TRY(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
   SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->block), stream_bytes + table_bytes + 256));
   c->out = c->block;
   uint64_t *d_count = reinterpret_cast<uint64_t *>(c->block + stream_bytes + table_bytes);
@@ -474,29 +450,19 @@ int spz_amd_merge_open(const spz_amd_merge_input *inputs, uint64_t k, int sh_deg
   uint64_t h = 0;
   SPZ_HIP_TRY(hipMemcpyAsync(&h, d_count, sizeof(h), hipMemcpyDeviceToHost, c->st));
   SPZ_HIP_TRY(hipStreamSynchronize(c->st));
-  if (h_ms) h_ms[0] = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (h_ms) h_ms[0] = (float)ms_since(t0);
   c->out_bytes = bytes;
   *out_hdr = oh;
   *h_out_bytes = bytes;
   *h_out_of_range = h;
-  *ctx = c;
-  on_error.c = nullptr;
+  *ctx = c.release();
   return SPZ_AMD_OK;
 }
 
-int spz_amd_merge_fetch(void *ctx, uint8_t *h_out) {
-  MergeCtx *c = static_cast<MergeCtx *>(ctx);
-  if (c == nullptr || h_out == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
-  DeviceGuard guard;
-  int rc = guard.enter(c->device);
-  if (rc != SPZ_AMD_OK) return rc;
-  SPZ_HIP_TRY(hipMemcpyAsync(h_out, c->out, c->out_bytes, hipMemcpyDeviceToHost, c->st));
-  SPZ_HIP_TRY(hipStreamSynchronize(c->st));
-  return SPZ_AMD_OK;
-}
+int spz_amd_merge_fetch(void *ctx, uint8_t *h_out) { return packed_result_fetch(ctx, h_out); }
 
-const uint8_t *spz_amd_merge_device_data(void *ctx) { return ctx ? static_cast<MergeCtx *>(ctx)->out : nullptr; }
+const uint8_t *spz_amd_merge_device_data(void *ctx) { return packed_result_device_data(ctx); }
 
-void spz_amd_merge_close(void *ctx) { merge_free(static_cast<MergeCtx *>(ctx)); }
+void spz_amd_merge_close(void *ctx) { packed_result_close(ctx); }
 
 }  // extern "C"

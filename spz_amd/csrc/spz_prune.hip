@@ -11,7 +11,8 @@
 //                                  sort (spz_sort_internal.hpp) ranks by score descending, then input index.
 //   spz_prune_top_kernel           mask[order[r]] = 1 for the first K ranks.
 //   spz_prune_threshold_kernel     min_score: mask[j] = score_j >= s, the sum as q 2^-24 in f64.
-//   (subset)                       spz_amd_select_device + spz_amd_subset_device at the input's degree.
+//   (subset)                       select_subset_masked (spz_filter.hip): the filter's select and subset at the
+//                                  input's degree.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -59,35 +60,8 @@ __global__ __launch_bounds__(kPrBlock) void spz_prune_threshold_kernel(const uns
 
 namespace {
 
-struct PrCtx {
-  int device = 0;
-  uint8_t *block = nullptr;  // scores, mask, indices, order, the sort's and the filter's workspaces
-  uint8_t *ws = nullptr;     // the render's workspace (grow-only)
-  uint8_t *out = nullptr;
-  uint64_t out_bytes = 0;
-  hipStream_t st = nullptr;
-};
-
-void pr_free(PrCtx *c) {
-  if (c == nullptr) return;
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  (void)hipSetDevice(c->device);
-  if (c->st) (void)hipStreamSynchronize(c->st);
-  if (c->st) (void)hipStreamDestroy(c->st);
-  if (c->block) (void)hipFree(c->block);
-  if (c->ws) (void)hipFree(c->ws);
-  if (c->out) (void)hipFree(c->out);
-  if (prev >= 0) (void)hipSetDevice(prev);
-  delete c;
-}
-
 uint8_t *align256(void *p) {
   return reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(p) + 255u) & ~uintptr_t(255));
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 }  // namespace
@@ -150,12 +124,9 @@ int spz_amd_prune_open(const uint8_t *d_stream, size_t size, const spz_amd_heade
   rc = guard.enter(device);
   if (rc != SPZ_AMD_OK) return rc;
   const auto t0 = std::chrono::steady_clock::now();
-  PrCtx *c = new PrCtx;
-  c->device = device;
-  struct Free {
-    PrCtx *c;
-    ~Free() { pr_free(c); }
-  } on_error{c};
+  PackedResultPtr c;
+  rc = packed_result_open(device, &c);
+  if (rc != SPZ_AMD_OK) return rc;
   const SortLayout sl = sort_layout(n);
   uint64_t off = 0;
   auto put = [&off](uint64_t bytes) {
@@ -165,7 +136,6 @@ int spz_amd_prune_open(const uint8_t *d_stream, size_t size, const spz_amd_heade
   };
   const uint64_t o_sum = put(n * 8u), o_max = put(n * 4u), o_small = put(16u), o_mask = put(n), o_idx = put(n * 4u),
                  o_order = put(n * 4u), o_sort = put(n ? sl.bytes : 0u), o_fws = put(spz_amd_filter_workspace_bytes(n));
-  SPZ_HIP_TRY(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
   SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->block), off));
   uint8_t *raw = c->block;  // every section is 256-aligned from hipMalloc's base
   auto *d_sum = reinterpret_cast<uint64_t *>(raw + o_sum);
@@ -186,9 +156,9 @@ int spz_amd_prune_open(const uint8_t *d_stream, size_t size, const spz_amd_heade
     const spz_amd_render_params &p = views[v];
     if (cap < prefix + 256u) {
       cap = prefix + 256u;
-      SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->ws), cap));
+      SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->scratch), cap));
     }
-    rc = spz_amd_render_prepare_packed_device(d_stream, size, hdr, &p, d_total, nullptr, c->ws, c->st);
+    rc = spz_amd_render_prepare_packed_device(d_stream, size, hdr, &p, d_total, nullptr, c->scratch, c->st);
     if (rc != SPZ_AMD_OK) {
       if (h_bad_view) *h_bad_view = v;
       return rc;
@@ -205,7 +175,7 @@ int spz_amd_prune_open(const uint8_t *d_stream, size_t size, const spz_amd_heade
       uint8_t *bigger = nullptr;
       SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&bigger), need));
       if (prefix) {
-        const hipError_t e = hipMemcpyAsync(align256(bigger), align256(c->ws), prefix, hipMemcpyDeviceToDevice, c->st);
+        const hipError_t e = hipMemcpyAsync(align256(bigger), align256(c->scratch), prefix, hipMemcpyDeviceToDevice, c->st);
         if (e == hipSuccess) (void)hipStreamSynchronize(c->st);
         if (e != hipSuccess) {
           (void)hipFree(bigger);
@@ -213,11 +183,11 @@ int spz_amd_prune_open(const uint8_t *d_stream, size_t size, const spz_amd_heade
           return SPZ_AMD_ERR_HIP;
         }
       }
-      SPZ_HIP_TRY(hipFree(c->ws));
-      c->ws = bigger;
+      SPZ_HIP_TRY(hipFree(c->scratch));
+      c->scratch = bigger;
       cap = need;
     }
-    rc = spz_amd_render_score_device(n, &p, total, nullptr, d_sum, d_max, d_status, c->ws, c->st);
+    rc = spz_amd_render_score_device(n, &p, total, nullptr, d_sum, d_max, d_status, c->scratch, c->st);
     if (rc != SPZ_AMD_OK) {
       if (h_bad_view) *h_bad_view = v;
       return rc;
@@ -255,14 +225,7 @@ int spz_amd_prune_open(const uint8_t *d_stream, size_t size, const spz_amd_heade
   SPZ_HIP_TRY(hipStreamSynchronize(c->st));
   const double rank_ms = ms_since(t0) - score_ms;
   uint64_t kept = 0;
-  rc = spz_amd_select_device(d_stream, size, hdr, nullptr, n ? d_mask : nullptr, d_idx, raw + o_fws, &kept, c->st);
-  if (rc != SPZ_AMD_OK) return rc;
-  spz_amd_layout ol;
-  rc = spz_amd_stream_layout(kept, hdr->sh_degree, (int)hdr->version, &ol);
-  if (rc != SPZ_AMD_OK) return rc;
-  c->out_bytes = ol.total_bytes;
-  SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->out), c->out_bytes));
-  rc = spz_amd_subset_device(d_stream, size, hdr, d_idx, kept, -1, c->out, c->out_bytes, c->st);
+  rc = select_subset_masked(d_stream, size, hdr, d_mask, d_idx, raw + o_fws, c.get(), &kept);
   if (rc != SPZ_AMD_OK) return rc;
   if (h_mask && n) SPZ_HIP_TRY(hipMemcpyAsync(h_mask, d_mask, n, hipMemcpyDeviceToHost, c->st));
   if (h_weight_sum && n) SPZ_HIP_TRY(hipMemcpyAsync(h_weight_sum, d_sum, n * 8u, hipMemcpyDeviceToHost, c->st));
@@ -276,26 +239,16 @@ int spz_amd_prune_open(const uint8_t *d_stream, size_t size, const spz_amd_heade
   if (h_kept) *h_kept = kept;
   *h_out_bytes = c->out_bytes;
   // the render's workspace is not needed by fetch: free it now
-  SPZ_HIP_TRY(hipFree(c->ws));
-  c->ws = nullptr;
-  *ctx = c;
-  on_error.c = nullptr;
+  SPZ_HIP_TRY(hipFree(c->scratch));
+  c->scratch = nullptr;
+  *ctx = c.release();
   return SPZ_AMD_OK;
 }
 
-int spz_amd_prune_fetch(void *ctx, uint8_t *h_out) {
-  PrCtx *c = static_cast<PrCtx *>(ctx);
-  if (c == nullptr || h_out == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
-  DeviceGuard guard;
-  int rc = guard.enter(c->device);
-  if (rc != SPZ_AMD_OK) return rc;
-  SPZ_HIP_TRY(hipMemcpyAsync(h_out, c->out, c->out_bytes, hipMemcpyDeviceToHost, c->st));
-  SPZ_HIP_TRY(hipStreamSynchronize(c->st));
-  return SPZ_AMD_OK;
-}
+int spz_amd_prune_fetch(void *ctx, uint8_t *h_out) { return packed_result_fetch(ctx, h_out); }
 
-const uint8_t *spz_amd_prune_device_data(void *ctx) { return ctx ? static_cast<PrCtx *>(ctx)->out : nullptr; }
+const uint8_t *spz_amd_prune_device_data(void *ctx) { return packed_result_device_data(ctx); }
 
-void spz_amd_prune_close(void *ctx) { pr_free(static_cast<PrCtx *>(ctx)); }
+void spz_amd_prune_close(void *ctx) { packed_result_close(ctx); }
 
 }  // extern "C"

@@ -69,10 +69,12 @@ std::vector<float> toFloatVector(const py::object &obj, const char *prop) {
   return out;
 }
 
-// New owning float32 1-D copy (spz.cc:47-79).
-py::array_t<float> toArray(const std::vector<float> &v) {
-  py::array_t<float> a(static_cast<py::ssize_t>(v.size()));
-  if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(float));
+// New owning 1-D copy (spz.cc:47-79), of element type E (a mask's bytes: bool).
+template <class T, class E = T>
+py::array_t<E> toArray(const std::vector<T> &v) {
+  static_assert(sizeof(E) == sizeof(T), "a copy of the elements' bytes");
+  py::array_t<E> a(static_cast<py::ssize_t>(v.size()));
+  if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(T));
   return a;
 }
 
@@ -116,14 +118,20 @@ spz::RenderOptions renderOptions(const py::object &world_to_camera, int width, i
   return o;
 }
 
+// The exception of a failed call: the unusable device's RuntimeError; a ValueError `refused` when the call refused its
+// arguments (SPZ_AMD_ERR_INVALID_ARG, and SPZ_AMD_ERR_UNSUPPORTED where `unsupportedRefused`); else a RuntimeError `failed`.
+[[noreturn]] void raiseFailure(const std::string &refused, const std::string &failed, bool unsupportedRefused = false) {
+  raiseIfDeviceUnusable();
+  const int st = spz::lastDeviceStatus();
+  if (st == SPZ_AMD_ERR_INVALID_ARG || (unsupportedRefused && st == SPZ_AMD_ERR_UNSUPPORTED)) throw py::value_error(refused);
+  throw std::runtime_error(failed);
+}
+
 // The (height, width, 4) array of a render, or the exception of its failure.
 py::object renderedImage(bool ok, const std::vector<float> &img, const spz::RenderOptions &o, const char *what) {
   if (!ok) {
-    raiseIfDeviceUnusable();
-    if (spz::lastDeviceStatus() == SPZ_AMD_ERR_INVALID_ARG) {
-      throw py::value_error(std::string(what) + ": refused (see the [SPZ ERROR] line)");
-    }
-    throw std::runtime_error(std::string(what) + " failed (see the [SPZ ERROR] line)");
+    raiseFailure(std::string(what) + ": refused (see the [SPZ ERROR] line)",
+                 std::string(what) + " failed (see the [SPZ ERROR] line)");
   }
   py::array_t<float> out({static_cast<py::ssize_t>(o.height), static_cast<py::ssize_t>(o.width), py::ssize_t(4)});
   std::memcpy(out.mutable_data(), img.data(), img.size() * sizeof(float));
@@ -591,11 +599,8 @@ PYBIND11_MODULE(spz, m) {
             ok = spz::filterSpz(input, output, f, &kept);
           }
           if (!ok) {
-            raiseIfDeviceUnusable();
-            if (spz::lastDeviceStatus() == SPZ_AMD_ERR_INVALID_ARG) {
-              throw py::value_error("filter_spz: invalid argument for this file (see the [SPZ ERROR] line)");
-            }
-            throw std::runtime_error("filter_spz: " + input + " -> " + output + " failed (see the [SPZ ERROR] line)");
+            raiseFailure("filter_spz: invalid argument for this file (see the [SPZ ERROR] line)",
+                         "filter_spz: " + input + " -> " + output + " failed (see the [SPZ ERROR] line)");
           }
           return kept;
         },
@@ -615,11 +620,8 @@ PYBIND11_MODULE(spz, m) {
             ok = spz::transformSpz(input, output, o);
           }
           if (!ok) {
-            raiseIfDeviceUnusable();
-            if (spz::lastDeviceStatus() == SPZ_AMD_ERR_INVALID_ARG) {
-              throw py::value_error("transform_spz: refused for this file (see the [SPZ ERROR] line)");
-            }
-            throw std::runtime_error("transform_spz: " + input + " -> " + output + " failed (see the [SPZ ERROR] line)");
+            raiseFailure("transform_spz: refused for this file (see the [SPZ ERROR] line)",
+                         "transform_spz: " + input + " -> " + output + " failed (see the [SPZ ERROR] line)");
           }
         },
         py::arg("input_filename"), py::arg("output_filename"), py::kw_only(), py::arg("rotation") = py::none(),
@@ -637,11 +639,7 @@ PYBIND11_MODULE(spz, m) {
             py::gil_scoped_release release;
             ok = spz::transformCloud(g, o);
           }
-          if (!ok) {
-            raiseIfDeviceUnusable();
-            if (spz::lastDeviceStatus() == SPZ_AMD_ERR_INVALID_ARG) throw py::value_error("transform_cloud: the cloud's arrays do not match");
-            throw std::runtime_error("transform_cloud failed (see the [SPZ ERROR] line)");
-          }
+          if (!ok) raiseFailure("transform_cloud: the cloud's arrays do not match", "transform_cloud failed (see the [SPZ ERROR] line)");
         },
         py::arg("cloud"), py::kw_only(), py::arg("rotation") = py::none(), py::arg("translation") = py::none(),
         py::arg("scale") = 1.0, py::arg("coord") = spz::CoordinateSystem::UNSPECIFIED,
@@ -657,11 +655,8 @@ PYBIND11_MODULE(spz, m) {
             ok = spz::mergeSpz(inputs, output, o, &points);
           }
           if (!ok) {
-            raiseIfDeviceUnusable();
-            if (spz::lastDeviceStatus() == SPZ_AMD_ERR_INVALID_ARG) {
-              throw py::value_error("merge_spz: refused for these files (see the [SPZ ERROR] line)");
-            }
-            throw std::runtime_error("merge_spz: -> " + output + " failed (see the [SPZ ERROR] line)");
+            raiseFailure("merge_spz: refused for these files (see the [SPZ ERROR] line)",
+                         "merge_spz: -> " + output + " failed (see the [SPZ ERROR] line)");
           }
           return points;
         },
@@ -693,16 +688,10 @@ PYBIND11_MODULE(spz, m) {
             ok = spz::sortSpz(input, output, o, &order);
           }
           if (!ok) {
-            raiseIfDeviceUnusable();
-            const int st = spz::lastDeviceStatus();
-            if (st == SPZ_AMD_ERR_INVALID_ARG || st == SPZ_AMD_ERR_UNSUPPORTED) {
-              throw py::value_error("sort_spz: refused for this file (see the [SPZ ERROR] line)");
-            }
-            throw std::runtime_error("sort_spz: " + input + " -> " + output + " failed (see the [SPZ ERROR] line)");
+            raiseFailure("sort_spz: refused for this file (see the [SPZ ERROR] line)",
+                         "sort_spz: " + input + " -> " + output + " failed (see the [SPZ ERROR] line)", true);
           }
-          py::array_t<uint32_t> r(static_cast<py::ssize_t>(order.size()));
-          if (!order.empty()) std::memcpy(r.mutable_data(), order.data(), order.size() * sizeof(uint32_t));
-          return r;
+          return toArray(order);
         },
         py::arg("input_filename"), py::arg("output_filename"), py::kw_only(), py::arg("keys") = py::none(),
         py::arg("descending") = false,
@@ -738,17 +727,11 @@ PYBIND11_MODULE(spz, m) {
             ok = spz::decimateSpz(input, output, o, want_parents ? &parents : nullptr, &used, &points);
           }
           if (!ok) {
-            raiseIfDeviceUnusable();
-            const int st = spz::lastDeviceStatus();
-            if (st == SPZ_AMD_ERR_INVALID_ARG || st == SPZ_AMD_ERR_UNSUPPORTED) {
-              throw py::value_error("decimate_spz: refused for this file (see the [SPZ ERROR] line)");
-            }
-            throw std::runtime_error("decimate_spz: " + input + " -> " + output + " failed (see the [SPZ ERROR] line)");
+            raiseFailure("decimate_spz: refused for this file (see the [SPZ ERROR] line)",
+                         "decimate_spz: " + input + " -> " + output + " failed (see the [SPZ ERROR] line)", true);
           }
           if (!want_parents) return py::make_tuple(used, points);
-          py::array_t<uint32_t> r(static_cast<py::ssize_t>(parents.size()));
-          if (!parents.empty()) std::memcpy(r.mutable_data(), parents.data(), parents.size() * sizeof(uint32_t));
-          return py::make_tuple(used, points, r);
+          return py::make_tuple(used, points, toArray(parents));
         },
         py::arg("input_filename"), py::arg("output_filename"), py::kw_only(), py::arg("level") = py::none(),
         py::arg("target_points") = py::none(), py::arg("return_parents") = false,
@@ -877,20 +860,11 @@ PYBIND11_MODULE(spz, m) {
                                details ? &maxima : nullptr);
           }
           if (!ok) {
-            raiseIfDeviceUnusable();
-            if (spz::lastDeviceStatus() == SPZ_AMD_ERR_INVALID_ARG) {
-              throw py::value_error("prune_spz: refused for this file (see the [SPZ ERROR] line)");
-            }
-            throw std::runtime_error("prune_spz: " + input + " -> " + output + " failed (see the [SPZ ERROR] line)");
+            raiseFailure("prune_spz: refused for this file (see the [SPZ ERROR] line)",
+                         "prune_spz: " + input + " -> " + output + " failed (see the [SPZ ERROR] line)");
           }
           if (!details) return py::int_(kept);
-          py::array_t<bool> m(static_cast<py::ssize_t>(mask.size()));
-          if (!mask.empty()) std::memcpy(m.mutable_data(), mask.data(), mask.size());
-          py::array_t<uint64_t> ws(static_cast<py::ssize_t>(sums.size()));
-          if (!sums.empty()) std::memcpy(ws.mutable_data(), sums.data(), sums.size() * 8u);
-          py::array_t<float> wm(static_cast<py::ssize_t>(maxima.size()));
-          if (!maxima.empty()) std::memcpy(wm.mutable_data(), maxima.data(), maxima.size() * 4u);
-          return py::make_tuple(kept, m, ws, wm);
+          return py::make_tuple(kept, toArray<uint8_t, bool>(mask), toArray(sums), toArray(maxima));
         },
         py::arg("input_filename"), py::arg("output_filename"), py::arg("views"), py::kw_only(),
         py::arg("keep") = py::none(), py::arg("keep_fraction") = py::none(), py::arg("min_score") = py::none(),
@@ -1017,24 +991,16 @@ PYBIND11_MODULE(spz, m) {
             ok = spz::cleanSpz(input, output, o, &kept, details ? &mask : nullptr, details ? &scores : nullptr, &thr);
           }
           if (!ok) {
-            raiseIfDeviceUnusable();
-            const int st = spz::lastDeviceStatus();
-            if (st == SPZ_AMD_ERR_INVALID_ARG || st == SPZ_AMD_ERR_UNSUPPORTED) {
-              throw py::value_error("clean_spz: refused for this file (see the [SPZ ERROR] line)");
-            }
-            throw std::runtime_error("clean_spz: " + input + " -> " + output + " failed (see the [SPZ ERROR] line)");
+            raiseFailure("clean_spz: refused for this file (see the [SPZ ERROR] line)",
+                         "clean_spz: " + input + " -> " + output + " failed (see the [SPZ ERROR] line)", true);
           }
           if (!details) return py::int_(kept);
-          py::array_t<bool> m(static_cast<py::ssize_t>(mask.size()));
-          if (!mask.empty()) std::memcpy(m.mutable_data(), mask.data(), mask.size());
           py::object sc = py::none(), th = py::none();
           if (o.statistical) {
-            py::array_t<double> s(static_cast<py::ssize_t>(scores.size()));
-            if (!scores.empty()) std::memcpy(s.mutable_data(), scores.data(), scores.size() * sizeof(double));
-            sc = s;
+            sc = toArray(scores);
             th = py::float_(thr);
           }
-          return py::make_tuple(kept, m, sc, th);
+          return py::make_tuple(kept, toArray<uint8_t, bool>(mask), sc, th);
         },
         py::arg("input_filename"), py::arg("output_filename"), py::kw_only(), py::arg("k") = py::none(),
         py::arg("std_ratio") = 2.0, py::arg("radius") = py::none(), py::arg("min_neighbors") = py::none(),

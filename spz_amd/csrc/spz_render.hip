@@ -884,10 +884,6 @@ int cloud_source(const spz_amd_cloud_in *cl, uint64_t n, int sh_degree, FloatSrc
   return SPZ_AMD_OK;
 }
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // The host forms: prepare into a block of their own, read the total, then the entries and the blend into a second.
 template <class Prepare>
 int render_host_impl(uint64_t n, const spz_amd_render_params *params, int device, float *h_rgba, uint64_t *h_entries,

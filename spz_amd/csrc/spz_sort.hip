@@ -424,29 +424,6 @@ int argsort_impl(const float *d_keys, uint64_t n, int descending, uint32_t *d_or
   return radix_passes((uint32_t)n, kFloatDigits, d_order, ws, wl, st);
 }
 
-struct SortCtx {
-  int device = 0;
-  uint8_t *block = nullptr;   // one allocation: keys, order, workspace, output stream
-  uint8_t *out = nullptr;
-  uint64_t out_bytes = 0;
-  hipStream_t st = nullptr;
-};
-
-void sort_free(SortCtx *c) {
-  if (c == nullptr) return;
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  (void)hipSetDevice(c->device);
-  if (c->st) (void)hipStreamDestroy(c->st);
-  if (c->block) (void)hipFree(c->block);
-  if (prev >= 0) (void)hipSetDevice(prev);
-  delete c;
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 }  // namespace
 
 extern "C" {
@@ -502,16 +479,12 @@ int spz_amd_sort_open(const uint8_t *d_stream, size_t size, const spz_amd_header
   rc = guard.enter(device);
   if (rc != SPZ_AMD_OK) return rc;
   const auto t0 = std::chrono::steady_clock::now();
-  SortCtx *c = new SortCtx;
-  c->device = device;
-  struct Free {
-    SortCtx *c;
-    ~Free() { sort_free(c); }
-  } on_error{c};
+  PackedResultPtr c;
+  rc = packed_result_open(device, &c);
+  if (rc != SPZ_AMD_OK) return rc;
   const uint64_t key_bytes = h_keys ? Workspace::aligned(n * 4u) : 0;
   const uint64_t ws_bytes = Workspace::aligned(sort_layout(n).bytes);
   const size_t total = key_bytes + Workspace::aligned(n * 4u) + ws_bytes + Workspace::aligned(in.total_bytes);
-  SPZ_HIP_TRY(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
   SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->block), total));
   uint8_t *q = c->block;
   float *d_keys = reinterpret_cast<float *>(q);
@@ -540,24 +513,14 @@ int spz_amd_sort_open(const uint8_t *d_stream, size_t size, const spz_amd_header
   }
   c->out_bytes = in.total_bytes;
   *h_out_bytes = in.total_bytes;
-  *ctx = c;
-  on_error.c = nullptr;
+  *ctx = c.release();
   return SPZ_AMD_OK;
 }
 
-int spz_amd_sort_fetch(void *ctx, uint8_t *h_out) {
-  SortCtx *c = static_cast<SortCtx *>(ctx);
-  if (c == nullptr || h_out == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
-  DeviceGuard guard;
-  int rc = guard.enter(c->device);
-  if (rc != SPZ_AMD_OK) return rc;
-  SPZ_HIP_TRY(hipMemcpyAsync(h_out, c->out, c->out_bytes, hipMemcpyDeviceToHost, c->st));
-  SPZ_HIP_TRY(hipStreamSynchronize(c->st));
-  return SPZ_AMD_OK;
-}
+int spz_amd_sort_fetch(void *ctx, uint8_t *h_out) { return packed_result_fetch(ctx, h_out); }
 
-const uint8_t *spz_amd_sort_device_data(void *ctx) { return ctx ? static_cast<SortCtx *>(ctx)->out : nullptr; }
+const uint8_t *spz_amd_sort_device_data(void *ctx) { return packed_result_device_data(ctx); }
 
-void spz_amd_sort_close(void *ctx) { sort_free(static_cast<SortCtx *>(ctx)); }
+void spz_amd_sort_close(void *ctx) { packed_result_close(ctx); }
 
 }  // extern "C"

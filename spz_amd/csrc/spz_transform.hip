@@ -401,25 +401,6 @@ int cloud_impl(float *pos, float *scales, float *rot, float *sh, uint64_t n, int
   return SPZ_AMD_OK;
 }
 
-struct TransformCtx {
-  int device = 0;
-  uint8_t *block = nullptr;   // the output stream, then the out-of-range count
-  uint8_t *out = nullptr;
-  uint64_t out_bytes = 0;
-  hipStream_t st = nullptr;
-};
-
-void transform_free(TransformCtx *c) {
-  if (c == nullptr) return;
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  (void)hipSetDevice(c->device);
-  if (c->st) (void)hipStreamDestroy(c->st);
-  if (c->block) (void)hipFree(c->block);
-  if (prev >= 0) (void)hipSetDevice(prev);
-  delete c;
-}
-
 }  // namespace
 
 extern "C" {
@@ -458,14 +439,10 @@ int spz_amd_transform_open(const uint8_t *d_stream, size_t size, const spz_amd_h
   DeviceGuard guard;
   rc = guard.enter(device);
   if (rc != SPZ_AMD_OK) return rc;
-  TransformCtx *c = new TransformCtx;
-  c->device = device;
-  struct Free {
-    TransformCtx *c;
-    ~Free() { transform_free(c); }
-  } on_error{c};
+  PackedResultPtr c;
+  rc = packed_result_open(device, &c);
+  if (rc != SPZ_AMD_OK) return rc;
   const size_t stream_bytes = Workspace::aligned(out.total_bytes);
-  SPZ_HIP_TRY(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
   SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->block), stream_bytes + 256));
   c->out = c->block;
   uint64_t *d_count = reinterpret_cast<uint64_t *>(c->block + stream_bytes);
@@ -475,31 +452,19 @@ int spz_amd_transform_open(const uint8_t *d_stream, size_t size, const spz_amd_h
   uint64_t h = 0;
   SPZ_HIP_TRY(hipMemcpyAsync(&h, d_count, sizeof(h), hipMemcpyDeviceToHost, c->st));
   SPZ_HIP_TRY(hipStreamSynchronize(c->st));
-  if (h_ms) h_ms[0] = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (h_ms) h_ms[0] = (float)ms_since(t0);
   c->out_bytes = out.total_bytes;
   *h_out_bytes = out.total_bytes;
   *h_out_of_range = h;
-  *ctx = c;
-  on_error.c = nullptr;
+  *ctx = c.release();
   return SPZ_AMD_OK;
 }
 
-int spz_amd_transform_fetch(void *ctx, uint8_t *h_out) {
-  TransformCtx *c = static_cast<TransformCtx *>(ctx);
-  if (c == nullptr || h_out == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
-  DeviceGuard guard;
-  int rc = guard.enter(c->device);
-  if (rc != SPZ_AMD_OK) return rc;
-  SPZ_HIP_TRY(hipMemcpyAsync(h_out, c->out, c->out_bytes, hipMemcpyDeviceToHost, c->st));
-  SPZ_HIP_TRY(hipStreamSynchronize(c->st));
-  return SPZ_AMD_OK;
-}
+int spz_amd_transform_fetch(void *ctx, uint8_t *h_out) { return packed_result_fetch(ctx, h_out); }
 
-const uint8_t *spz_amd_transform_device_data(void *ctx) {
-  return ctx ? static_cast<TransformCtx *>(ctx)->out : nullptr;
-}
+const uint8_t *spz_amd_transform_device_data(void *ctx) { return packed_result_device_data(ctx); }
 
-void spz_amd_transform_close(void *ctx) { transform_free(static_cast<TransformCtx *>(ctx)); }
+void spz_amd_transform_close(void *ctx) { packed_result_close(ctx); }
 
 int spz_amd_transform_cloud_host(float *h_positions, float *h_scales, float *h_rotations, float *h_sh,
                                  uint64_t num_points, int sh_degree, const spz_amd_transform *xf, int device) {
