@@ -8,15 +8,22 @@
 // once the arguments are there (the reference ignores the save/load results), usage -> 1.
 // spz_filter, spz_transform, spz_merge, spz_sort, spz_decimate, spz_clean, spz_render and spz_prune exit 1 when the
 // filter / transform / merge / sort / decimation / clean / render / prune fails as well.
+// Those eight read their arguments with one reader (Args): <input> <output> come first and may not start with '-'
+// (spz_merge takes its inputs anywhere, and -o); each option may be given once; an integer is decimal digits only,
+// leading zeros allowed, no sign or space, range-checked; a real is all of its argument, by strtof for a float field
+// and strtod for a double field.  Anything else prints the tool's usage line.
 #include <algorithm>
 #include <stdexcept>
 #include <array>
 #include <cmath>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
 #include <fstream>
 #include <iostream>
+#include <iterator>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -67,53 +74,110 @@ int spzInfo(int argc, char **argv) {
   return 0;
 }
 
-const char *kFilterUsage =
-    "Usage: spz_filter <input.spz> <output.spz> [--sh-degree D] [--min-alpha A] [--box x0 y0 z0 x1 y1 z1] "
-    "[--coord RUB|RDF|LUF|RUF|LDB|RDB|LUB|LDF|UNSPECIFIED]";
+// The --coord names: as the usage lines list them, and in spz::CoordinateSystem's order.
+#define SPZ_COORD_NAMES "RUB|RDF|LUF|RUF|LDB|RDB|LUB|LDF|UNSPECIFIED"
+const char *const kCoordNames[] = {"UNSPECIFIED", "LDB", "RDB", "LUB", "RUB", "LDF", "RDF", "LUF", "RUF"};
 
-bool parseFloat(const char *s, float *v) {
-  char *end = nullptr;
-  *v = std::strtof(s, &end);
-  return end != s && *end == '\0';
+// One tool's arguments, read in the tool's own loop: next() steps to an argument, is() names it, and the value
+// readers take the option's values after it.  A value reader returns false when fewer values are left than it needs or
+// one is malformed; the tool then returns usage().
+class Args {
+ public:
+  Args(int argc, char **argv, const char *usage) : argc_(argc), argv_(argv), usage_(usage) {}
+
+  int usage() const {
+    std::cerr << usage_ << std::endl;
+    return 1;
+  }
+  // <input> <output>: both there, neither starting with '-'.  The options follow them.
+  bool files() {
+    at_ = 3;
+    return argc_ >= 3 && argv_[1][0] != '-' && argv_[2][0] != '-';
+  }
+  bool next() {
+    if (at_ >= argc_) return false;
+    arg_ = argv_[at_++];
+    repeat_ = !given_.insert(arg_).second;
+    return true;
+  }
+  const char *arg() const { return arg_; }
+  // Whether the argument is `option`, given for the first time: a repeated option is no option at all.
+  bool is(const char *option) const { return !repeat_ && std::strcmp(arg_, option) == 0; }
+  bool given(const char *option) const { return given_.count(option) != 0; }
+
+  bool text(std::string *v) {
+    char **s = values(1);
+    if (s) *v = s[0];
+    return s != nullptr;
+  }
+  bool coord(spz::CoordinateSystem *c) {
+    std::string name;
+    if (!text(&name)) return false;
+    const auto *n = std::find(std::begin(kCoordNames), std::end(kCoordNames), name);
+    if (n == std::end(kCoordNames)) return false;
+    *c = static_cast<spz::CoordinateSystem>(n - std::begin(kCoordNames));
+    return true;
+  }
+  template <class T>
+  bool integer(T *v, uint64_t lo, uint64_t hi, int k = 1) {
+    char **s = values(k);
+    for (int j = 0; s && j < k; ++j) {
+      const char *c = s[j];
+      uint64_t x = 0;
+      for (; *c >= '0' && *c <= '9' && x <= (UINT64_MAX - (*c - '0')) / 10; ++c) x = 10 * x + (*c - '0');
+      if (c == s[j] || *c != '\0' || x < lo || x > hi) return false;
+      v[j] = static_cast<T>(x);
+    }
+    return s != nullptr;
+  }
+  bool real(float *v, int k = 1) { return reals(v, k, std::strtof); }
+  bool real(double *v, int k = 1) { return reals(v, k, std::strtod); }
+
+ private:
+  char **values(int k) {
+    if (at_ + k > argc_) return nullptr;
+    at_ += k;
+    return argv_ + at_ - k;
+  }
+  template <class T>
+  bool reals(T *v, int k, T (*convert)(const char *, char **)) {
+    char **s = values(k);
+    for (int j = 0; s && j < k; ++j) {
+      char *end = nullptr;
+      v[j] = convert(s[j], &end);
+      if (end == s[j] || *end != '\0') return false;
+    }
+    return s != nullptr;
+  }
+
+  int argc_;
+  char **argv_;
+  const char *usage_;
+  int at_ = 1;
+  const char *arg_ = "";
+  bool repeat_ = false;
+  std::set<std::string> given_;
+};
+
+bool allFinite(const float *v, int k) {
+  return std::all_of(v, v + k, [](float x) { return std::isfinite(x); });
 }
 
+const char *kFilterUsage =
+    "Usage: spz_filter <input.spz> <output.spz> [--sh-degree D] [--min-alpha A] [--box x0 y0 z0 x1 y1 z1] "
+    "[--coord " SPZ_COORD_NAMES "]";
+
 int spzFilter(int argc, char **argv) {
-  auto usage = [] {
-    std::cerr << kFilterUsage << std::endl;
-    return 1;
-  };
-  if (argc < 3) return usage();
+  Args a(argc, argv, kFilterUsage);
+  if (!a.files()) return a.usage();
   spz::FilterOptions f;
-  for (int i = 3; i < argc; ++i) {
-    const std::string a = argv[i];
-    if (a == "--sh-degree" && i + 1 < argc) {
-      char *end = nullptr;
-      const long d = std::strtol(argv[++i], &end, 10);
-      if (*end != '\0' || d < 0 || d > 3) return usage();
-      f.shDegree = static_cast<int32_t>(d);
-    } else if (a == "--min-alpha" && i + 1 < argc) {
-      float v = 0;
-      if (!parseFloat(argv[++i], &v)) return usage();
-      f.minAlpha = v;
-    } else if (a == "--box" && i + 6 < argc) {
-      spz::FilterOptions::Box b;
-      for (int k = 0; k < 6; ++k) {
-        if (!parseFloat(argv[i + 1 + k], k < 3 ? &b.lo[k] : &b.hi[k - 3])) return usage();
-      }
-      i += 6;
-      f.box = b;
-    } else if (a == "--coord" && i + 1 < argc) {
-      static const char *names[] = {"UNSPECIFIED", "LDB", "RDB", "LUB", "RUB", "LDF", "RDF", "LUF", "RUF"};
-      const std::string c = argv[++i];
-      int found = -1;
-      for (int k = 0; k < 9; ++k) {
-        if (c == names[k]) found = k;
-      }
-      if (found < 0) return usage();
-      f.coord = static_cast<spz::CoordinateSystem>(found);
-    } else {
-      return usage();
-    }
+  while (a.next()) {
+    bool good = false;
+    if (a.is("--sh-degree")) good = a.integer(&f.shDegree, 0, 3);
+    else if (a.is("--min-alpha")) good = a.real(&f.minAlpha.emplace());
+    else if (a.is("--box")) good = a.real(f.box.emplace().lo.data(), 3) && a.real(f.box->hi.data(), 3);
+    else if (a.is("--coord")) good = a.coord(&f.coord);
+    if (!good) return a.usage();
   }
   int64_t kept = 0;
   if (!spz::filterSpz(std::string(argv[1]), std::string(argv[2]), f, &kept)) return 1;
@@ -123,52 +187,20 @@ int spzFilter(int argc, char **argv) {
 
 const char *kTransformUsage =
     "Usage: spz_transform <input.spz> <output.spz> [--rotate x y z w] [--translate x y z] [--scale s] "
-    "[--coord RUB|RDF|LUF|RUF|LDB|RDB|LUB|LDF|UNSPECIFIED] [--fractional-bits n]";
-
-bool parseDouble(const char *s, double *v) {
-  char *end = nullptr;
-  *v = std::strtod(s, &end);
-  return end != s && *end == '\0';
-}
+    "[--coord " SPZ_COORD_NAMES "] [--fractional-bits n]";
 
 int spzTransform(int argc, char **argv) {
-  auto usage = [] {
-    std::cerr << kTransformUsage << std::endl;
-    return 1;
-  };
-  if (argc < 3) return usage();
+  Args a(argc, argv, kTransformUsage);
+  if (!a.files()) return a.usage();
   spz::TransformOptions o;
-  for (int i = 3; i < argc; ++i) {
-    const std::string a = argv[i];
-    if (a == "--rotate" && i + 4 < argc) {
-      for (int k = 0; k < 4; ++k) {
-        if (!parseDouble(argv[i + 1 + k], &o.rotation[k])) return usage();
-      }
-      i += 4;
-    } else if (a == "--translate" && i + 3 < argc) {
-      for (int k = 0; k < 3; ++k) {
-        if (!parseDouble(argv[i + 1 + k], &o.translation[k])) return usage();
-      }
-      i += 3;
-    } else if (a == "--scale" && i + 1 < argc) {
-      if (!parseDouble(argv[++i], &o.scale)) return usage();
-    } else if (a == "--coord" && i + 1 < argc) {
-      static const char *names[] = {"UNSPECIFIED", "LDB", "RDB", "LUB", "RUB", "LDF", "RDF", "LUF", "RUF"};
-      const std::string c = argv[++i];
-      int found = -1;
-      for (int k = 0; k < 9; ++k) {
-        if (c == names[k]) found = k;
-      }
-      if (found < 0) return usage();
-      o.coord = static_cast<spz::CoordinateSystem>(found);
-    } else if (a == "--fractional-bits" && i + 1 < argc) {
-      char *end = nullptr;
-      const long d = std::strtol(argv[++i], &end, 10);
-      if (*end != '\0' || d < 0 || d > 24) return usage();
-      o.fractionalBits = static_cast<int32_t>(d);
-    } else {
-      return usage();
-    }
+  while (a.next()) {
+    bool good = false;
+    if (a.is("--rotate")) good = a.real(o.rotation.data(), 4);
+    else if (a.is("--translate")) good = a.real(o.translation.data(), 3);
+    else if (a.is("--scale")) good = a.real(&o.scale);
+    else if (a.is("--coord")) good = a.coord(&o.coord);
+    else if (a.is("--fractional-bits")) good = a.integer(&o.fractionalBits, 0, 24);
+    if (!good) return a.usage();
   }
   return spz::transformSpz(std::string(argv[1]), std::string(argv[2]), o) ? 0 : 1;
 }
@@ -176,65 +208,41 @@ int spzTransform(int argc, char **argv) {
 const char *kMergeUsage =
     "Usage: spz_merge <input.spz>... -o <output.spz> [--sh-degree D] [--fractional-bits B] [--antialiased 0|1]";
 
-bool parseInt(const char *s, long lo, long hi, int32_t *v) {
-  char *end = nullptr;
-  const long d = std::strtol(s, &end, 10);
-  if (end == s || *end != '\0' || d < lo || d > hi) return false;
-  *v = static_cast<int32_t>(d);
-  return true;
-}
-
 int spzMerge(int argc, char **argv) {
-  auto usage = [] {
-    std::cerr << kMergeUsage << std::endl;
-    return 1;
-  };
+  Args a(argc, argv, kMergeUsage);
   spz::MergeOptions o;
   std::vector<std::string> inputs;
   std::string output;
-  bool have_output = false;
-  for (int i = 1; i < argc; ++i) {
-    const std::string a = argv[i];
-    if (a == "-o" && i + 1 < argc && !have_output) {
-      output = argv[++i];
-      have_output = true;
-    } else if (a == "--sh-degree" && i + 1 < argc) {
-      if (!parseInt(argv[++i], 0, 3, &o.shDegree)) return usage();
-    } else if (a == "--fractional-bits" && i + 1 < argc) {
-      if (!parseInt(argv[++i], 0, 24, &o.fractionalBits)) return usage();
-    } else if (a == "--antialiased" && i + 1 < argc) {
-      if (!parseInt(argv[++i], 0, 1, &o.antialiased)) return usage();
-    } else if (!a.empty() && a[0] == '-') {
-      return usage();
-    } else {
-      inputs.push_back(a);
+  while (a.next()) {
+    if (a.arg()[0] != '-') {
+      inputs.push_back(a.arg());
+      continue;
     }
+    bool good = false;
+    if (a.is("-o")) good = a.text(&output);
+    else if (a.is("--sh-degree")) good = a.integer(&o.shDegree, 0, 3);
+    else if (a.is("--fractional-bits")) good = a.integer(&o.fractionalBits, 0, 24);
+    else if (a.is("--antialiased")) good = a.integer(&o.antialiased, 0, 1);
+    if (!good) return a.usage();
   }
-  if (inputs.empty() || !have_output || output.empty()) return usage();
+  if (inputs.empty() || output.empty()) return a.usage();
   return spz::mergeSpz(inputs, output, o) ? 0 : 1;
 }
 
 const char *kSortUsage = "Usage: spz_sort <input.spz> <output.spz> [--keys <keys.f32>] [--descending]";
 
 int spzSort(int argc, char **argv) {
-  auto usage = [] {
-    std::cerr << kSortUsage << std::endl;
-    return 1;
-  };
-  if (argc < 3 || argv[1][0] == '-' || argv[2][0] == '-') return usage();
+  Args a(argc, argv, kSortUsage);
+  if (!a.files()) return a.usage();
   spz::SortOptions o;
-  const char *keys = nullptr;
-  for (int i = 3; i < argc; ++i) {
-    const std::string a = argv[i];
-    if (a == "--keys" && i + 1 < argc && keys == nullptr) {
-      keys = argv[++i];
-    } else if (a == "--descending" && !o.descending) {
-      o.descending = true;
-    } else {
-      return usage();
-    }
+  std::string keys;
+  while (a.next()) {
+    bool good = false;
+    if (a.is("--keys")) good = a.text(&keys);
+    else if (a.is("--descending")) good = o.descending = true;
+    if (!good) return a.usage();
   }
-  if (keys != nullptr) {
+  if (a.given("--keys")) {
     // raw little-endian float32, one per point
     std::ifstream f(keys, std::ios::binary | std::ios::ate);
     if (!f) {
@@ -260,66 +268,40 @@ int spzSort(int argc, char **argv) {
 const char *kDecimateUsage = "Usage: spz_decimate <input.spz> <output.spz> (--level <L> | --target <N>)";
 
 int spzDecimate(int argc, char **argv) {
-  auto usage = [] {
-    std::cerr << kDecimateUsage << std::endl;
-    return 1;
-  };
-  if (argc != 5 || argv[1][0] == '-' || argv[2][0] == '-') return usage();
-  const std::string flag = argv[3], value = argv[4];
-  // a plain decimal number, nothing else
-  if (value.empty() || value.size() > 19 || value.find_first_not_of("0123456789") != std::string::npos) return usage();
-  const unsigned long long v = std::strtoull(value.c_str(), nullptr, 10);
+  Args a(argc, argv, kDecimateUsage);
+  if (!a.files()) return a.usage();
   spz::DecimateOptions o;
-  if (flag == "--level" && v <= 24) {
-    o.level = static_cast<int>(v);
-  } else if (flag == "--target" && v >= 1) {
-    o.targetPoints = static_cast<uint64_t>(v);
-  } else {
-    return usage();
+  const uint64_t maxTarget = 9999999999999999999ull;  // the largest --target spz_decimate has taken
+  while (a.next()) {
+    bool good = false;
+    if (a.is("--level")) good = a.integer(&o.level.emplace(), 0, 24);
+    else if (a.is("--target")) good = a.integer(&o.targetPoints.emplace(), 1, maxTarget);
+    if (!good) return a.usage();
   }
+  if (o.level.has_value() == o.targetPoints.has_value()) return a.usage();
   return spz::decimateSpz(std::string(argv[1]), std::string(argv[2]), o) ? 0 : 1;
 }
 
 const char *kCleanUsage =
     "Usage: spz_clean <input.spz> <output.spz> [--k <K> [--std-ratio <S>]] [--radius <R> --min-neighbors <M>]";
 
-// a plain decimal integer in lo..hi
-bool parseCount(const char *s, int lo, int hi, int *v) {
-  const std::string t = s;
-  if (t.empty() || t.size() > 4 || t.find_first_not_of("0123456789") != std::string::npos) return false;
-  *v = std::atoi(s);
-  return *v >= lo && *v <= hi;
-}
-
 int spzClean(int argc, char **argv) {
-  auto usage = [] {
-    std::cerr << kCleanUsage << std::endl;
-    return 1;
-  };
-  if (argc < 5 || argv[1][0] == '-' || argv[2][0] == '-' || (argc - 3) % 2 != 0) return usage();
-  bool hasK = false, hasRatio = false, hasRadius = false, hasMin = false;
+  Args a(argc, argv, kCleanUsage);
+  if (!a.files()) return a.usage();
   spz::CleanOptions::Statistical st;
   spz::CleanOptions::Radius rd;
-  for (int i = 3; i < argc; i += 2) {
-    const std::string flag = argv[i];
-    const char *value = argv[i + 1];
-    if (flag == "--k" && !hasK) {
-      if (!parseCount(value, 1, 64, &st.k)) return usage();
-      hasK = true;
-    } else if (flag == "--std-ratio" && !hasRatio) {
-      if (!parseDouble(value, &st.stdRatio) || !std::isfinite(st.stdRatio)) return usage();
-      hasRatio = true;
-    } else if (flag == "--radius" && !hasRadius) {
-      if (!parseDouble(value, &rd.radius) || !std::isfinite(rd.radius) || !(rd.radius > 0.0)) return usage();
-      hasRadius = true;
-    } else if (flag == "--min-neighbors" && !hasMin) {
-      if (!parseCount(value, 1, 256, &rd.minNeighbors)) return usage();
-      hasMin = true;
-    } else {
-      return usage();
-    }
+  while (a.next()) {
+    bool good = false;
+    if (a.is("--k")) good = a.integer(&st.k, 1, 64);
+    else if (a.is("--std-ratio")) good = a.real(&st.stdRatio) && std::isfinite(st.stdRatio);
+    else if (a.is("--radius")) good = a.real(&rd.radius) && std::isfinite(rd.radius) && rd.radius > 0.0;
+    else if (a.is("--min-neighbors")) good = a.integer(&rd.minNeighbors, 1, 256);
+    if (!good) return a.usage();
   }
-  if ((hasRatio && !hasK) || hasRadius != hasMin || (!hasK && !hasRadius)) return usage();
+  const bool hasK = a.given("--k"), hasRadius = a.given("--radius");
+  if ((a.given("--std-ratio") && !hasK) || hasRadius != a.given("--min-neighbors") || (!hasK && !hasRadius)) {
+    return a.usage();
+  }
   spz::CleanOptions o;
   if (hasK) o.statistical = st;
   if (hasRadius) o.radius = rd;
@@ -328,7 +310,7 @@ int spzClean(int argc, char **argv) {
 
 const char *kRenderUsage =
     "Usage: spz_render <in.spz> <out.ppm|out.pfm> --size W H (--fov-y DEG | --intrinsics fx fy cx cy) --eye x y z "
-    "--target x y z [--up x y z] [--coord RUB|RDF|LUF|RUF|LDB|RDB|LUB|LDF|UNSPECIFIED] [--background r g b] "
+    "--target x y z [--up x y z] [--coord " SPZ_COORD_NAMES "] [--background r g b] "
     "[--sh-degree D] [--near N]";
 
 bool endsWith(const std::string &s, const char *suffix) {
@@ -367,82 +349,35 @@ bool writeImage(const std::string &path, const std::vector<float> &rgba, int w, 
 }
 
 int spzRender(int argc, char **argv) {
-  auto usage = [] {
-    std::cerr << kRenderUsage << std::endl;
-    return 1;
-  };
-  if (argc < 3 || argv[1][0] == '-' || argv[2][0] == '-') return usage();
+  Args a(argc, argv, kRenderUsage);
+  if (!a.files()) return a.usage();
   const std::string outPath = argv[2];
   const bool pfm = endsWith(outPath, ".pfm");
-  if (!pfm && !endsWith(outPath, ".ppm")) return usage();
+  if (!pfm && !endsWith(outPath, ".ppm")) return a.usage();
   spz::RenderOptions o;
-  bool hasSize = false, hasFov = false, hasIntr = false, hasEye = false, hasTarget = false, hasUp = false;
-  bool hasBackground = false, hasNear = false, hasShDegree = false, hasCoord = false;
+  int size[2] = {0, 0};
   float fovY = 0.0f, intr[4] = {0, 0, 0, 0};
   std::array<float, 3> eye{}, target{}, up{};
-  auto floats = [&](int &i, int k, float *dst) {
-    if (i + k >= argc) return false;
-    for (int j = 0; j < k; ++j) {
-      if (!parseFloat(argv[i + 1 + j], &dst[j]) || !std::isfinite(dst[j])) return false;
-    }
-    i += k;
-    return true;
-  };
-  for (int i = 3; i < argc; ++i) {
-    const std::string a = argv[i];
-    if (a == "--size" && !hasSize && i + 2 < argc) {
-      int v[2];
-      for (int k = 0; k < 2; ++k) {
-        const std::string t = argv[i + 1 + k];
-        if (t.empty() || t.size() > 5 || t.find_first_not_of("0123456789") != std::string::npos) return usage();
-        v[k] = std::atoi(t.c_str());
-        if (v[k] < 1 || v[k] > 16384) return usage();
-      }
-      o.width = v[0];
-      o.height = v[1];
-      i += 2;
-      hasSize = true;
-    } else if (a == "--fov-y" && !hasFov && !hasIntr) {
-      if (!floats(i, 1, &fovY) || !(fovY > 0.0f && fovY < 180.0f)) return usage();
-      hasFov = true;
-    } else if (a == "--intrinsics" && !hasFov && !hasIntr) {
-      if (!floats(i, 4, intr)) return usage();
-      hasIntr = true;
-    } else if (a == "--eye" && !hasEye) {
-      if (!floats(i, 3, eye.data())) return usage();
-      hasEye = true;
-    } else if (a == "--target" && !hasTarget) {
-      if (!floats(i, 3, target.data())) return usage();
-      hasTarget = true;
-    } else if (a == "--up" && !hasUp) {
-      if (!floats(i, 3, up.data())) return usage();
-      hasUp = true;
-    } else if (a == "--background" && !hasBackground) {
-      if (!floats(i, 3, o.background.data())) return usage();
-      hasBackground = true;
-    } else if (a == "--near" && !hasNear) {
-      if (!floats(i, 1, &o.nearPlane) || !(o.nearPlane > 0.0f)) return usage();
-      hasNear = true;
-    } else if (a == "--sh-degree" && !hasShDegree && i + 1 < argc) {
-      const std::string t = argv[++i];
-      if (t.size() != 1 || t[0] < '0' || t[0] > '3') return usage();
-      o.maxShDegree = t[0] - '0';
-      hasShDegree = true;
-    } else if (a == "--coord" && !hasCoord && i + 1 < argc) {
-      hasCoord = true;
-      static const char *names[] = {"UNSPECIFIED", "LDB", "RDB", "LUB", "RUB", "LDF", "RDF", "LUF", "RUF"};
-      const std::string c = argv[++i];
-      int found = -1;
-      for (int k = 0; k < 9; ++k) {
-        if (c == names[k]) found = k;
-      }
-      if (found < 0) return usage();
-      o.coord = static_cast<spz::CoordinateSystem>(found);
-    } else {
-      return usage();
-    }
+  while (a.next()) {
+    bool good = false;
+    if (a.is("--size")) good = a.integer(size, 1, 16384, 2);
+    else if (a.is("--fov-y")) good = a.real(&fovY) && fovY > 0.0f && fovY < 180.0f;
+    else if (a.is("--intrinsics")) good = a.real(intr, 4) && allFinite(intr, 4);
+    else if (a.is("--eye")) good = a.real(eye.data(), 3) && allFinite(eye.data(), 3);
+    else if (a.is("--target")) good = a.real(target.data(), 3) && allFinite(target.data(), 3);
+    else if (a.is("--up")) good = a.real(up.data(), 3) && allFinite(up.data(), 3);
+    else if (a.is("--background")) good = a.real(o.background.data(), 3) && allFinite(o.background.data(), 3);
+    else if (a.is("--near")) good = a.real(&o.nearPlane) && std::isfinite(o.nearPlane) && o.nearPlane > 0.0f;
+    else if (a.is("--sh-degree")) good = a.integer(&o.maxShDegree, 0, 3);
+    else if (a.is("--coord")) good = a.coord(&o.coord);
+    if (!good) return a.usage();
   }
-  if (!hasSize || (!hasFov && !hasIntr) || !hasEye || !hasTarget) return usage();
+  const bool hasFov = a.given("--fov-y");
+  if (!a.given("--size") || hasFov == a.given("--intrinsics") || !a.given("--eye") || !a.given("--target")) {
+    return a.usage();
+  }
+  o.width = size[0];
+  o.height = size[1];
   if (hasFov) {
     o.fy = static_cast<float>(0.5 * o.height / std::tan(0.5 * fovY * 3.14159265358979323846 / 180.0));
     o.fx = o.fy;
@@ -453,9 +388,9 @@ int spzRender(int argc, char **argv) {
     o.fy = intr[1];
     o.cx = intr[2];
     o.cy = intr[3];
-    if (!(o.fx > 0.0f) || !(o.fy > 0.0f)) return usage();
+    if (!(o.fx > 0.0f) || !(o.fy > 0.0f)) return a.usage();
   }
-  if (!hasUp) {  // the frame's U axis (UNSPECIFIED: the stored RUB frame)
+  if (!a.given("--up")) {  // the frame's U axis (UNSPECIFIED: the stored RUB frame)
     const int c = static_cast<int>(o.coord) == 0 ? 4 : static_cast<int>(o.coord);
     const bool yDown = (((c - 1) >> 1) & 1) == 0;  // LDB, RDB, LDF, RDF
     up = {0.0f, yDown ? -1.0f : 1.0f, 0.0f};
@@ -463,7 +398,7 @@ int spzRender(int argc, char **argv) {
   try {
     o.worldToCamera = spz::lookAt(eye, target, up);
   } catch (const std::invalid_argument &) {
-    return usage();
+    return a.usage();
   }
   std::vector<float> rgba;
   if (!spz::renderSpz(std::string(argv[1]), o, &rgba)) return 1;
@@ -477,104 +412,40 @@ int spzRender(int argc, char **argv) {
 const char *kPruneUsage =
     "Usage: spz_prune <in.spz> <out.spz> (--views FILE | --orbit N --size W H --fov-y DEG [--center x y z --radius R] "
     "[--distance K]) (--keep N | --keep-fraction F | --min-score S) [--score sum|max] "
-    "[--coord RUB|RDF|LUF|RUF|LDB|RDB|LUB|LDF|UNSPECIFIED]";
+    "[--coord " SPZ_COORD_NAMES "]";
 
 int spzPrune(int argc, char **argv) {
-  auto usage = [] {
-    std::cerr << kPruneUsage << std::endl;
-    return 1;
-  };
-  if (argc < 3 || argv[1][0] == '-' || argv[2][0] == '-') return usage();
+  Args a(argc, argv, kPruneUsage);
+  if (!a.files()) return a.usage();
   spz::PruneOptions o;
-  std::string viewsFile;
+  std::string viewsFile, score;
   int orbit = 0, size[2] = {0, 0};
   float fovY = 0.0f, radius = 0.0f, distance = 2.5f;
   std::array<float, 3> center{};
-  bool hasViews = false, hasOrbit = false, hasSize = false, hasFov = false, hasCenter = false, hasRadius = false;
-  bool hasDistance = false, hasScore = false, hasCoord = false;
-  auto floats = [&](int &i, int k, float *dst) {
-    if (i + k >= argc) return false;
-    for (int j = 0; j < k; ++j) {
-      if (!parseFloat(argv[i + 1 + j], &dst[j]) || !std::isfinite(dst[j])) return false;
-    }
-    i += k;
-    return true;
-  };
-  auto integer = [](const char *s, int lo, int hi, int *v) {
-    const std::string t = s;
-    if (t.empty() || t.size() > 10 || t.find_first_not_of("0123456789") != std::string::npos) return false;
-    const long long x = std::atoll(s);
-    if (x < lo || x > hi) return false;
-    *v = static_cast<int>(x);
-    return true;
-  };
-  for (int i = 3; i < argc; ++i) {
-    const std::string a = argv[i];
-    const bool more = i + 1 < argc;
-    if (a == "--views" && !hasViews && more) {
-      viewsFile = argv[++i];
-      hasViews = true;
-    } else if (a == "--orbit" && !hasOrbit && more) {
-      if (!integer(argv[++i], 1, 1024, &orbit)) return usage();
-      hasOrbit = true;
-    } else if (a == "--size" && !hasSize && i + 2 < argc) {
-      for (int k = 0; k < 2; ++k) {
-        if (!integer(argv[i + 1 + k], 1, 16384, &size[k])) return usage();
-      }
-      i += 2;
-      hasSize = true;
-    } else if (a == "--fov-y" && !hasFov) {
-      if (!floats(i, 1, &fovY) || !(fovY > 0.0f && fovY < 180.0f)) return usage();
-      hasFov = true;
-    } else if (a == "--center" && !hasCenter) {
-      if (!floats(i, 3, center.data())) return usage();
-      hasCenter = true;
-    } else if (a == "--radius" && !hasRadius) {
-      if (!floats(i, 1, &radius) || !(radius > 0.0f)) return usage();
-      hasRadius = true;
-    } else if (a == "--distance" && !hasDistance) {
-      if (!floats(i, 1, &distance) || !(distance > 0.0f)) return usage();
-      hasDistance = true;
-    } else if (a == "--keep" && !o.keepCount && more) {
-      int k = 0;
-      if (!integer(argv[++i], 0, 0x7fffffff, &k)) return usage();
-      o.keepCount = k;
-    } else if (a == "--keep-fraction" && !o.keepFraction && more) {
-      double f = 0.0;
-      if (!parseDouble(argv[++i], &f) || !(f >= 0.0 && f <= 1.0)) return usage();
-      o.keepFraction = f;
-    } else if (a == "--min-score" && !o.minScore && more) {
-      double s = 0.0;
-      if (!parseDouble(argv[++i], &s) || !std::isfinite(s)) return usage();
-      o.minScore = s;
-    } else if (a == "--score" && !hasScore && more) {
-      const std::string v = argv[++i];
-      if (v == "sum") {
-        o.score = spz::PruneOptions::Sum;
-      } else if (v == "max") {
-        o.score = spz::PruneOptions::Max;
-      } else {
-        return usage();
-      }
-      hasScore = true;
-    } else if (a == "--coord" && !hasCoord && more) {
-      hasCoord = true;
-      static const char *names[] = {"UNSPECIFIED", "LDB", "RDB", "LUB", "RUB", "LDF", "RDF", "LUF", "RUF"};
-      const std::string c = argv[++i];
-      int found = -1;
-      for (int k = 0; k < 9; ++k) {
-        if (c == names[k]) found = k;
-      }
-      if (found < 0) return usage();
-      o.coord = static_cast<spz::CoordinateSystem>(found);
-    } else {
-      return usage();
-    }
+  while (a.next()) {
+    bool good = false;
+    if (a.is("--views")) good = a.text(&viewsFile);
+    else if (a.is("--orbit")) good = a.integer(&orbit, 1, 1024);
+    else if (a.is("--size")) good = a.integer(size, 1, 16384, 2);
+    else if (a.is("--fov-y")) good = a.real(&fovY) && fovY > 0.0f && fovY < 180.0f;
+    else if (a.is("--center")) good = a.real(center.data(), 3) && allFinite(center.data(), 3);
+    else if (a.is("--radius")) good = a.real(&radius) && std::isfinite(radius) && radius > 0.0f;
+    else if (a.is("--distance")) good = a.real(&distance) && std::isfinite(distance) && distance > 0.0f;
+    else if (a.is("--keep")) good = a.integer(&o.keepCount.emplace(), 0, 0x7fffffff);
+    else if (a.is("--keep-fraction")) good = a.real(&o.keepFraction.emplace()) && *o.keepFraction >= 0.0 &&
+                                             *o.keepFraction <= 1.0;
+    else if (a.is("--min-score")) good = a.real(&o.minScore.emplace()) && std::isfinite(*o.minScore);
+    else if (a.is("--score")) good = a.text(&score) && (score == "sum" || score == "max");
+    else if (a.is("--coord")) good = a.coord(&o.coord);
+    if (!good) return a.usage();
   }
-  const int rules = (o.keepCount ? 1 : 0) + (o.keepFraction ? 1 : 0) + (o.minScore ? 1 : 0);
-  if (rules != 1 || hasViews == hasOrbit) return usage();
-  if (hasViews && (hasSize || hasFov || hasCenter || hasRadius || hasDistance)) return usage();
-  if (hasOrbit && (!hasSize || !hasFov || hasCenter != hasRadius)) return usage();
+  if (score == "max") o.score = spz::PruneOptions::Max;
+  const bool hasViews = a.given("--views"), hasOrbit = a.given("--orbit"), hasCenter = a.given("--center");
+  const int rules = a.given("--keep") + a.given("--keep-fraction") + a.given("--min-score");
+  if (rules != 1 || hasViews == hasOrbit) return a.usage();
+  const bool hasSize = a.given("--size"), hasFov = a.given("--fov-y"), hasRadius = a.given("--radius");
+  if (hasViews && (hasSize || hasFov || hasCenter || hasRadius || a.given("--distance"))) return a.usage();
+  if (hasOrbit && (!hasSize || !hasFov || hasCenter != hasRadius)) return a.usage();
   try {
     if (hasViews) {
       o.views = spz::loadViewsFile(viewsFile);
@@ -592,7 +463,7 @@ int spzPrune(int argc, char **argv) {
     }
   } catch (const std::invalid_argument &e) {
     std::cerr << e.what() << std::endl;
-    return usage();
+    return a.usage();
   }
   int64_t kept = 0;
   if (!spz::pruneSpz(std::string(argv[1]), std::string(argv[2]), o, &kept)) return 1;
@@ -600,18 +471,18 @@ int spzPrune(int argc, char **argv) {
   return 0;
 }
 
+const struct {
+  const char *name;
+  int (*run)(int, char **);
+} kTools[] = {{"ply_to_spz", plyToSpz},     {"spz_to_ply", spzToPly},         {"spz_info", spzInfo},
+              {"spz_filter", spzFilter},    {"spz_transform", spzTransform},  {"spz_merge", spzMerge},
+              {"spz_sort", spzSort},        {"spz_decimate", spzDecimate},    {"spz_clean", spzClean},
+              {"spz_render", spzRender},    {"spz_prune", spzPrune}};
+
 int dispatch(const std::string &tool, int argc, char **argv) {
-  if (tool == "ply_to_spz") return plyToSpz(argc, argv);
-  if (tool == "spz_to_ply") return spzToPly(argc, argv);
-  if (tool == "spz_info") return spzInfo(argc, argv);
-  if (tool == "spz_filter") return spzFilter(argc, argv);
-  if (tool == "spz_transform") return spzTransform(argc, argv);
-  if (tool == "spz_merge") return spzMerge(argc, argv);
-  if (tool == "spz_sort") return spzSort(argc, argv);
-  if (tool == "spz_decimate") return spzDecimate(argc, argv);
-  if (tool == "spz_clean") return spzClean(argc, argv);
-  if (tool == "spz_render") return spzRender(argc, argv);
-  if (tool == "spz_prune") return spzPrune(argc, argv);
+  for (const auto &t : kTools) {
+    if (tool == t.name) return t.run(argc, argv);
+  }
   return -1;
 }
 
@@ -628,7 +499,9 @@ int main(int argc, char **argv) {
       rc = dispatch(argv[1], argc - 1, argv + 1);
       if (rc >= 0) return rc;
     }
-    std::cerr << "Usage: spz_tool {ply_to_spz|spz_to_ply|spz_info|spz_filter|spz_transform|spz_merge|spz_sort|spz_decimate|spz_clean|spz_render|spz_prune} <args...>" << std::endl;
+    std::cerr << "Usage: spz_tool {";
+    for (const auto &t : kTools) std::cerr << (&t == kTools ? "" : "|") << t.name;
+    std::cerr << "} <args...>" << std::endl;
     return 1;
   } catch (const std::exception &e) {
     std::cerr << "Error: " << e.what() << std::endl;

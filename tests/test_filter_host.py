@@ -142,6 +142,11 @@ def test_device_select_subset_check_their_arguments():
     ["spz_filter", "a.spz", "b.spz", "--sh-degree"], ["spz_filter", "a.spz", "b.spz", "--sh-degree", "4"],
     ["spz_filter", "a.spz", "b.spz", "--box", "0", "0", "0", "1", "1"], ["spz_filter", "a.spz", "b.spz", "--coord", "XYZ"],
     ["spz_filter", "a.spz", "b.spz", "--min-alpha", "abc"], ["spz_filter", "a.spz", "b.spz", "--bogus"],
+    ["spz_filter", "a.spz", "b.spz", "--sh-degree", ""], ["spz_filter", "a.spz", "b.spz", "--sh-degree", "+2"],
+    ["spz_filter", "a.spz", "b.spz", "--sh-degree", " 2"], ["spz_filter", "a.spz", "b.spz", "--sh-degree", "-0"],
+    ["spz_filter", "a.spz", "b.spz", "--min-alpha", "0.5", "--min-alpha", "0.5"],
+    ["spz_filter", "a.spz", "b.spz", "--sh-degree", "1", "--sh-degree", "2"],
+    ["spz_filter", "-a.spz", "b.spz"], ["spz_filter", "a.spz", "-b.spz"],
 ])
 def test_cli_usage(argv, tmp_path):
     exe = os.path.join(ROOT, "spz_amd", "bin", argv[0])

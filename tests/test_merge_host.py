@@ -258,6 +258,10 @@ def test_device_merge_checks_its_arguments():
     ["spz_merge", "a.spz", "-o", "b.spz", "--fractional-bits", "25"], ["spz_merge", "a.spz", "-o", "b.spz", "--antialiased", "2"],
     ["spz_merge", "a.spz", "-o", "b.spz", "--antialiased", "x"], ["spz_merge", "a.spz", "-o", "b.spz", "--bogus"],
     ["spz_merge", "a.spz", "-o", "b.spz", "--rotate", "0", "0", "0", "1"],
+    ["spz_merge", "a.spz", "-o", "b.spz", "--sh-degree", "+2"], ["spz_merge", "a.spz", "-o", "b.spz", "--sh-degree", " 2"],
+    ["spz_merge", "a.spz", "-o", "b.spz", "--fractional-bits", "-0"], ["spz_merge", "a.spz", "-o", "b.spz", "--antialiased", "+1"],
+    ["spz_merge", "a.spz", "-o", "b.spz", "--sh-degree", "1", "--sh-degree", "2"],
+    ["spz_merge", "a.spz", "-o", "b.spz", "--antialiased", "0", "--antialiased", "0"],
 ])
 def test_cli_usage(argv, tmp_path):
     exe = os.path.join(ROOT, "spz_amd", "bin", argv[0])

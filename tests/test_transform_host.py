@@ -310,6 +310,11 @@ def test_device_transform_checks_its_arguments():
     ["spz_transform", "a.spz", "b.spz", "--scale", "x"], ["spz_transform", "a.spz", "b.spz", "--translate", "1", "2"],
     ["spz_transform", "a.spz", "b.spz", "--coord", "XYZ"], ["spz_transform", "a.spz", "b.spz", "--fractional-bits", "25"],
     ["spz_transform", "a.spz", "b.spz", "--bogus"],
+    ["spz_transform", "a.spz", "b.spz", "--fractional-bits", ""], ["spz_transform", "a.spz", "b.spz", "--fractional-bits", "+2"],
+    ["spz_transform", "a.spz", "b.spz", "--fractional-bits", " 2"], ["spz_transform", "a.spz", "b.spz", "--fractional-bits", "-0"],
+    ["spz_transform", "a.spz", "b.spz", "--scale", "2", "--scale", "2"],
+    ["spz_transform", "a.spz", "b.spz", "--coord", "RUB", "--coord", "RDF"],
+    ["spz_transform", "-a.spz", "b.spz"], ["spz_transform", "a.spz", "-b.spz"],
 ])
 def test_cli_usage(argv, tmp_path):
     exe = os.path.join(ROOT, "spz_amd", "bin", argv[0])
