@@ -620,6 +620,63 @@ int spz_amd_prune_fetch(void *ctx, uint8_t *h_out);
 const uint8_t *spz_amd_prune_device_data(void *ctx);
 void spz_amd_prune_close(void *ctx);
 
+/* ---- image metrics: PSNR, MSE, L1, max error and SSIM of two images (spz_metrics.hip; DESIGN §8 "Compare").  The
+ *      reference has no counterpart.  The convention of the 3DGS evaluation code (Kerbl et al. 2023, loss_utils.ssim and
+ *      image_utils.psnr), so the numbers compare with published tables.
+ *
+ *      Inputs.  Two images a, b, each height x width x C float32, row-major and contiguous, C in {3, 4}; the two may
+ *      have different C (a render's RGBA against a photo's RGB).  Only the first three channels are used.  Each used
+ *      value is clamped first: v = fminf(fmaxf(v, 0), 1), so NaN becomes 0, +inf 1 and -inf 0 (a render's images are
+ *      not clamped).  width, height 1..16384.
+ *      Per pixel, with d = a - b on the clamped values (f64):  mse = sum d^2 / (3 H W);  psnr = 10 log10(1 / mse), or +inf
+ *      when mse == 0;  l1 = sum |d| / (3 H W);  max_abs = max |d|.
+ *      SSIM, per channel.  Window g: the 11x11 Gaussian, the outer product of w_k = exp(-(k - 5)^2 / (2 1.5^2)) / sum_j
+ *      exp(-(j - 5)^2 / (2 1.5^2)), k = 0..10.  Convolution: "same" size with zero padding (pixels outside the image
+ *      count as 0 and stay in the window's weight, as conv2d(padding = 5)), separable: along rows, then along columns,
+ *      taps in k order, in f64.  mu_a = g*a, mu_b = g*b, s_a = g*a^2 - mu_a^2, s_b = g*b^2 - mu_b^2, s_ab = g*(ab) -
+ *      mu_a mu_b;  S = ((2 mu_a mu_b + C1)(2 s_ab + C2)) / ((mu_a^2 + mu_b^2 + C1)(s_a + s_b + C2)), C1 = 0.01^2,
+ *      C2 = 0.03^2.  ssim = the mean of S over all 3 H W values.  The SSIM map (optional): height x width float32, the
+ *      mean of S over the three channels at each pixel.
+ *      Precision against a float64 restatement: mse, l1 and max_abs within 1e-12 relative, ssim within 1e-7 absolute,
+ *      each map value within 1e-6.  Deterministic: no float atomics; each workgroup writes its partial sums to a slab in
+ *      a fixed order and one pass reduces the slab in a fixed order (max_abs through the u64 bit pattern of the f64
+ *      |d|).  A run repeats its bits, and swapping a and b gives bit-identical results (every expression is symmetric).
+ *
+ *      image_metrics_check (host only, no GPU): SPZ_AMD_ERR_INVALID_ARG when a side is outside 1..16384 or a channel
+ *      count is not 3 or 4.  image_metrics_workspace_bytes (host only): device memory for the device form (0 for a bad
+ *      size).  image_metrics_device: enqueues on hip_stream, no synchronisation; *d_out (device memory, 8-aligned) gets
+ *      the five results; d_ssim_map (device memory, may be NULL); d_workspace 8-aligned.  image_metrics_host: host
+ *      images in, *h_out and h_ssim_map (may be NULL) out, on `device`, blocking.
+ *
+ * ---- compare: two packed streams rendered from a set of views, and the metrics above of each view's two images
+ *      (spz_metrics.hip; DESIGN §8 "Compare").  Versions 1, 2 and 3; the two streams may differ in point count, SH degree
+ *      and version.  views: 1..SPZ_AMD_COMPARE_MAX_VIEWS render params, each passing render_check_params, all with one
+ *      coord (a bad one: SPZ_AMD_ERR_INVALID_ARG before anything is launched, the view in *h_bad_view).  Per view: A
+ *      rendered, B rendered (render_prepare_packed_device, the total read back, render_finish_device: the images are
+ *      bit-identical to render_host's), then image_metrics_device of the two RGBA images.  The render workspace and
+ *      the two images are grow-only and reused across views.  A 0-point input renders as render_host renders it (the
+ *      background, alpha 0).  A total above 2^31 - 1: SPZ_AMD_ERR_CAPACITY, the view in *h_bad_view.  Runs on `device`
+ *      on a stream of its own and blocks.  h_metrics: num_views results; h_ssim_maps (may be NULL): sum_i W_i H_i floats,
+ *      view after view; h_entries (may be NULL): 2 num_views totals, A then B per view; h_ms (may be NULL): [0]
+ *      wall-clock milliseconds of the renders, [1] of the metrics; *h_bad_view (may be NULL): the view a failure
+ *      concerns, else -1. */
+enum { SPZ_AMD_COMPARE_MAX_VIEWS = 1024 };
+typedef struct {
+  double mse, psnr, ssim, l1, max_abs;
+} spz_amd_image_metrics;
+int spz_amd_image_metrics_check(int width, int height, int channels_a, int channels_b);
+uint64_t spz_amd_image_metrics_workspace_bytes(int width, int height);
+int spz_amd_image_metrics_device(const float *d_a, int channels_a, const float *d_b, int channels_b, int width,
+                                 int height, spz_amd_image_metrics *d_out, float *d_ssim_map, void *d_workspace,
+                                 void *hip_stream);
+int spz_amd_image_metrics_host(const float *h_a, int channels_a, const float *h_b, int channels_b, int width,
+                               int height, int device, spz_amd_image_metrics *h_out, float *h_ssim_map);
+int spz_amd_compare_host(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
+                         const uint8_t *d_stream_b, size_t size_b, const spz_amd_header *hdr_b,
+                         const spz_amd_render_params *views, int num_views, int device,
+                         spz_amd_image_metrics *h_metrics, float *h_ssim_maps, uint64_t *h_entries, float *h_ms,
+                         int32_t *h_bad_view);
+
 /* ---- device buffers for a resident cloud, placed for speed (spz_place.hip).  Whether an sh3 decode runs
  *      at 0.46 ms or at 0.55 ms is decided by whether the sh float array shares a physical region of HBM with the other
  *      arrays of the launch; that cannot be asked for, but it shows in one launch.  alloc: the five small arrays (and a

@@ -466,6 +466,33 @@ bool boundingSphere(const std::vector<float> &positions, std::array<float, 3> *c
 // blank lines and text after '#' ignored.  std::invalid_argument naming the line on a line that does not parse, a file
 // that does not open or holds no view.  The cameras themselves are checked by pruneSpz.
 std::vector<PruneOptions::View> loadViewsFile(const std::string &filename);
+// Compare (DESIGN §8 "Compare"): PSNR, MSE, L1, max error and SSIM of two images on the device, in the convention of the
+// 3DGS evaluation code (include/spz_amd.h "image metrics" states the contract: values clamped to [0, 1], NaN -> 0; the
+// first three channels; an 11x11 Gaussian window of sigma 1.5 with zero padding).  compareSpz renders both files from
+// every view (as renderSpz would, in the `coord` frame) and compares the two images of each view; the files may differ
+// in point count, SH degree and version.  views: 1..1024 pinhole cameras (orbitViews, loadViewsFile).  *metrics: one
+// result per view; *ssimMaps (may be NULL): per view the height x width map of S averaged over the channels.
+// compareImages: two height x width x channels float32 images in host memory (channels 3 or 4 each), compared on the
+// device SPZ_AMD_DEVICE names (default 0).  false + one "[SPZ ERROR] compareSpz: …" (compareImages: …) line on a bad
+// argument (lastDeviceStatus() = SPZ_AMD_ERR_INVALID_ARG; a bad view is named by its index), an input that does not
+// load, or a device failure.  SPZ_AMD_COMPARE_TIMING=1 prints the stages' times to stderr.
+struct ImageMetrics {
+  double mse = 0.0, psnr = 0.0, ssim = 0.0, l1 = 0.0, maxAbs = 0.0;
+};
+struct CompareOptions {
+  std::vector<PruneOptions::View> views;
+  CoordinateSystem coord = CoordinateSystem::UNSPECIFIED;
+  float nearPlane = 0.2f;
+  std::array<float, 3> background = {0.0f, 0.0f, 0.0f};
+  int maxShDegree = 3;
+};
+bool compareSpz(const std::string &fileA, const std::string &fileB, const CompareOptions &options,
+                std::vector<ImageMetrics> *metrics, std::vector<std::vector<float>> *ssimMaps = nullptr);
+bool compareSpz(const uint8_t *dataA, int32_t sizeA, const uint8_t *dataB, int32_t sizeB,
+                const CompareOptions &options, std::vector<ImageMetrics> *metrics,
+                std::vector<std::vector<float>> *ssimMaps = nullptr);
+bool compareImages(const float *a, int channelsA, const float *b, int channelsB, int width, int height,
+                   ImageMetrics *metrics, std::vector<float> *ssimMap = nullptr);
 // Status (spz_amd.h codes) of the last device call made by this thread; 0 = ok.
 int lastDeviceStatus();
 void setLastDeviceStatus(int status);

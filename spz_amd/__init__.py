@@ -12,6 +12,7 @@ Layout:
   csrc/spz_clean.hip    exact k-NN scores and radius counts over the Morton-sorted positions, floater removal (cleanSpz)
   csrc/spz_render.hip   a tiled 3D Gaussian splat rasteriser: preprocess, depth and tile order, per-tile blend (renderSpz)
   csrc/spz_prune.hip    per-Gaussian blend weights over views, exact rank, the filter's subset of the kept (pruneSpz)
+  csrc/spz_metrics.hip  PSNR / MSE / L1 / max error / SSIM of two images, and two files over views (compareSpz)
   csrc/spz_abi.hip      the C ABI (include/spz_amd.h) over them: device-pointer entry points
   csrc/spz_hostpath.hip host-pointer entry points: device workspace + chunked H2D/kernel/D2H pipeline
   csrc/spz_exchange.hip multi-GPU exchange: native RCCL gatherv/scatterv, IPC-mapped root stream

@@ -78,6 +78,8 @@ EXPORTS = (
     "spz_amd_render_prepare_cloud_device", "spz_amd_render_finish_device", "spz_amd_render_host",
     "spz_amd_render_cloud_host", "spz_amd_render_score_device", "spz_amd_prune_keep_count", "spz_amd_prune_open",
     "spz_amd_prune_fetch", "spz_amd_prune_device_data", "spz_amd_prune_close",
+    "spz_amd_image_metrics_check", "spz_amd_image_metrics_workspace_bytes", "spz_amd_image_metrics_device",
+    "spz_amd_image_metrics_host", "spz_amd_compare_host",
 )
 
 RCCL_UNIQUE_ID_BYTES = 128
@@ -117,6 +119,13 @@ RENDER_RECORD_BYTES = 48
 PRUNE_MAX_VIEWS = 1024
 PRUNE_SCORE_SUM, PRUNE_SCORE_MAX = 0, 1
 PRUNE_KEEP_COUNT, PRUNE_KEEP_FRACTION, PRUNE_MIN_SCORE = 0, 1, 2
+COMPARE_MAX_VIEWS = 1024
+
+
+class ImageMetrics(C.Structure):
+    """spz_amd_image_metrics: the five results of one image pair (include/spz_amd.h "image metrics")."""
+    _fields_ = [("mse", C.c_double), ("psnr", C.c_double), ("ssim", C.c_double), ("l1", C.c_double),
+                ("max_abs", C.c_double)]
 
 
 class CloudBuffers(C.Structure):
@@ -439,6 +448,17 @@ def bind(L):
     L.spz_amd_prune_device_data.argtypes = [vp]
     L.spz_amd_prune_close.restype = None
     L.spz_amd_prune_close.argtypes = [vp]
+    L.spz_amd_image_metrics_check.restype = i32
+    L.spz_amd_image_metrics_check.argtypes = [i32, i32, i32, i32]
+    L.spz_amd_image_metrics_workspace_bytes.restype = u64
+    L.spz_amd_image_metrics_workspace_bytes.argtypes = [i32, i32]
+    L.spz_amd_image_metrics_device.restype = i32
+    L.spz_amd_image_metrics_device.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp]
+    L.spz_amd_image_metrics_host.restype = i32
+    L.spz_amd_image_metrics_host.argtypes = [vp, i32, vp, i32, i32, i32, i32, C.POINTER(ImageMetrics), vp]
+    L.spz_amd_compare_host.restype = i32
+    L.spz_amd_compare_host.argtypes = [vp, sz, C.POINTER(Header), vp, sz, C.POINTER(Header), C.POINTER(RenderParams),
+                                       i32, i32, C.POINTER(ImageMetrics), vp, vp, vp, C.POINTER(C.c_int32)]
     L.spz_amd_zlib_encode_blocks.restype = i32
     L.spz_amd_zlib_encode_blocks.argtypes = [vp, vp, u32, u32, vp, vp, vp, u64, u64, vp, vp]
     return L

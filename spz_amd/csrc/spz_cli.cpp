@@ -1,9 +1,10 @@
 // spz_cli.cpp — the three command-line tools of the reference (cli_tools/src/*.cpp) over the
 // MI355X drop-in layer: ply_to_spz, spz_to_ply, spz_info; and spz_filter (spz::filterSpz),
 // spz_transform (spz::transformSpz), spz_merge (spz::mergeSpz), spz_sort (spz::sortSpz), spz_decimate
-// (spz::decimateSpz), spz_clean (spz::cleanSpz), spz_render (spz::renderSpz) and spz_prune (spz::pruneSpz), which have
-// no counterpart in the reference.  One binary, dispatched on argv[0] (the Makefile installs it under the eleven names)
-// or on a first argument naming the tool.
+// (spz::decimateSpz), spz_clean (spz::cleanSpz), spz_render (spz::renderSpz), spz_prune (spz::pruneSpz) and spz_compare
+// (spz::compareSpz), which have no counterpart in the reference.  One binary, dispatched on argv[0] (the Makefile
+// installs it under the twelve names) or on a first argument naming the tool.
+// spz_compare exits 0 on success, 1 on a failure and 2 when a view misses --min-psnr or --min-ssim.
 // Same behaviour as the reference mains: default (UNSPECIFIED) pack/unpack options, exit code 0
 // once the arguments are there (the reference ignores the save/load results), usage -> 1.
 // spz_filter, spz_transform, spz_merge, spz_sort, spz_decimate, spz_clean, spz_render and spz_prune exit 1 when the
@@ -17,6 +18,7 @@
 #include <array>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
@@ -471,13 +473,114 @@ int spzPrune(int argc, char **argv) {
   return 0;
 }
 
+const char *kCompareUsage =
+    "Usage: spz_compare <a.spz> <b.spz> (--views FILE | --orbit N --size W H --fov-y DEG [--center x y z --radius R] "
+    "[--distance K]) [--coord " SPZ_COORD_NAMES "] [--background r g b] [--max-sh-degree D] [--near Z] "
+    "[--ssim-maps PREFIX] [--min-psnr DB] [--min-ssim S]";
+
+// A greyscale PFM ("Pf"): little-endian floats, rows bottom to top.
+bool writeMap(const std::string &path, const std::vector<float> &map, int w, int h) {
+  std::ofstream out(path, std::ios::binary);
+  if (!out) return false;
+  out << "Pf\n" << w << " " << h << "\n-1.0\n";
+  for (int y = h - 1; y >= 0; --y) {
+    out.write(reinterpret_cast<const char *>(map.data() + static_cast<size_t>(y) * w),
+              static_cast<std::streamsize>(static_cast<size_t>(w) * sizeof(float)));
+  }
+  return static_cast<bool>(out);
+}
+
+// One line per view, then the mean PSNR and SSIM over the views and the worst view of each.  Exit 2 when a view misses
+// --min-psnr or --min-ssim.
+int spzCompare(int argc, char **argv) {
+  Args a(argc, argv, kCompareUsage);
+  if (!a.files()) return a.usage();
+  spz::CompareOptions o;
+  std::string viewsFile, mapPrefix;
+  int orbit = 0, size[2] = {0, 0};
+  float fovY = 0.0f, radius = 0.0f, distance = 2.5f;
+  double minPsnr = 0.0, minSsim = 0.0;
+  std::array<float, 3> center{};
+  while (a.next()) {
+    bool good = false;
+    if (a.is("--views")) good = a.text(&viewsFile);
+    else if (a.is("--orbit")) good = a.integer(&orbit, 1, 1024);
+    else if (a.is("--size")) good = a.integer(size, 1, 16384, 2);
+    else if (a.is("--fov-y")) good = a.real(&fovY) && fovY > 0.0f && fovY < 180.0f;
+    else if (a.is("--center")) good = a.real(center.data(), 3) && allFinite(center.data(), 3);
+    else if (a.is("--radius")) good = a.real(&radius) && std::isfinite(radius) && radius > 0.0f;
+    else if (a.is("--distance")) good = a.real(&distance) && std::isfinite(distance) && distance > 0.0f;
+    else if (a.is("--coord")) good = a.coord(&o.coord);
+    else if (a.is("--background")) good = a.real(o.background.data(), 3) && allFinite(o.background.data(), 3);
+    else if (a.is("--max-sh-degree")) good = a.integer(&o.maxShDegree, 0, 3);
+    else if (a.is("--near")) good = a.real(&o.nearPlane) && std::isfinite(o.nearPlane) && o.nearPlane > 0.0f;
+    else if (a.is("--ssim-maps")) good = a.text(&mapPrefix) && !mapPrefix.empty();
+    else if (a.is("--min-psnr")) good = a.real(&minPsnr) && !std::isnan(minPsnr);
+    else if (a.is("--min-ssim")) good = a.real(&minSsim) && !std::isnan(minSsim);
+    if (!good) return a.usage();
+  }
+  const bool hasViews = a.given("--views"), hasOrbit = a.given("--orbit"), hasCenter = a.given("--center");
+  if (hasViews == hasOrbit) return a.usage();
+  const bool hasSize = a.given("--size"), hasFov = a.given("--fov-y"), hasRadius = a.given("--radius");
+  if (hasViews && (hasSize || hasFov || hasCenter || hasRadius || a.given("--distance"))) return a.usage();
+  if (hasOrbit && (!hasSize || !hasFov || hasCenter != hasRadius)) return a.usage();
+  try {
+    if (hasViews) {
+      o.views = spz::loadViewsFile(viewsFile);
+    } else {
+      if (!hasCenter) {  // the box of file a's decoded positions
+        spz::UnpackOptions u;
+        u.to = o.coord;
+        const spz::GaussianCloud g = spz::loadSpz(std::string(argv[1]), u);
+        if (g.numPoints <= 0 || !spz::boundingSphere(g.positions, &center, &radius)) {
+          std::cerr << "spz_compare: " << argv[1] << " has no points to take a centre and radius from" << std::endl;
+          return 1;
+        }
+      }
+      o.views = spz::orbitViews(orbit, center, radius, size[0], size[1], fovY, distance);
+    }
+  } catch (const std::invalid_argument &e) {
+    std::cerr << e.what() << std::endl;
+    return a.usage();
+  }
+  std::vector<spz::ImageMetrics> m;
+  std::vector<std::vector<float>> maps;
+  if (!spz::compareSpz(std::string(argv[1]), std::string(argv[2]), o, &m, mapPrefix.empty() ? nullptr : &maps)) {
+    return 1;
+  }
+  double psnrSum = 0.0, ssimSum = 0.0;
+  size_t worstPsnr = 0, worstSsim = 0;
+  bool missed = false;
+  for (size_t v = 0; v < m.size(); ++v) {
+    std::printf("view %zu psnr %.17g ssim %.17g mse %.17g l1 %.17g max_abs %.17g\n", v, m[v].psnr, m[v].ssim, m[v].mse,
+                m[v].l1, m[v].maxAbs);
+    psnrSum += m[v].psnr;
+    ssimSum += m[v].ssim;
+    if (m[v].psnr < m[worstPsnr].psnr) worstPsnr = v;
+    if (m[v].ssim < m[worstSsim].ssim) worstSsim = v;
+    if ((a.given("--min-psnr") && m[v].psnr < minPsnr) || (a.given("--min-ssim") && m[v].ssim < minSsim)) missed = true;
+    if (!mapPrefix.empty()) {
+      const std::string path = mapPrefix + "_" + std::to_string(v) + ".pfm";
+      if (!writeMap(path, maps[v], o.views[v].width, o.views[v].height)) {
+        std::cerr << "spz_compare: unable to write " << path << std::endl;
+        return 1;
+      }
+    }
+  }
+  const double n = static_cast<double>(m.size());
+  std::printf("mean psnr %.17g ssim %.17g worst psnr %.17g view %zu worst ssim %.17g view %zu\n", psnrSum / n,
+              ssimSum / n, m[worstPsnr].psnr, worstPsnr, m[worstSsim].ssim, worstSsim);
+  std::fflush(stdout);
+  return missed ? 2 : 0;
+}
+
 const struct {
   const char *name;
   int (*run)(int, char **);
 } kTools[] = {{"ply_to_spz", plyToSpz},     {"spz_to_ply", spzToPly},         {"spz_info", spzInfo},
               {"spz_filter", spzFilter},    {"spz_transform", spzTransform},  {"spz_merge", spzMerge},
               {"spz_sort", spzSort},        {"spz_decimate", spzDecimate},    {"spz_clean", spzClean},
-              {"spz_render", spzRender},    {"spz_prune", spzPrune}};
+              {"spz_render", spzRender},    {"spz_prune", spzPrune},          {"spz_compare", spzCompare}};
 
 int dispatch(const std::string &tool, int argc, char **argv) {
   for (const auto &t : kTools) {

@@ -2703,6 +2703,147 @@ std::vector<PruneOptions::View> loadViewsFile(const std::string &filename) {
   return views;
 }
 
+// ---- compare -----------------------------------------------------------------------------------------------------
+namespace {
+// The views as render params with the options' frame, near plane, background and degree.
+bool compareOptionsOk(const CompareOptions &o, std::vector<spz_amd_render_params> *params) {
+  const char *who = "compareSpz";
+  const int invalid = SPZ_AMD_ERR_INVALID_ARG;
+  if (o.views.empty() || o.views.size() > SPZ_AMD_COMPARE_MAX_VIEWS) {
+    return opRejected(who, invalid, "%zu views: give 1..%d", o.views.size(), SPZ_AMD_COMPARE_MAX_VIEWS);
+  }
+  params->assign(o.views.size(), spz_amd_render_params{});
+  for (size_t v = 0; v < o.views.size(); ++v) {
+    const PruneOptions::View &w = o.views[v];
+    spz_amd_render_params &p = (*params)[v];
+    if (w.width < 1 || w.width > 16384 || w.height < 1 || w.height > 16384) {
+      return opRejected(who, invalid, "view %zu: image size %d x %d is outside 1..16384", v, w.width, w.height);
+    }
+    for (int k = 0; k < 12; ++k) p.world_to_camera[k] = w.worldToCamera[k];
+    p.fx = w.fx;
+    p.fy = w.fy;
+    p.cx = w.cx;
+    p.cy = w.cy;
+    p.width = static_cast<uint32_t>(w.width);
+    p.height = static_cast<uint32_t>(w.height);
+    p.near_plane = o.nearPlane;
+    for (int k = 0; k < 3; ++k) p.background[k] = o.background[k];
+    p.max_sh_degree = o.maxShDegree;
+    p.coord = static_cast<int32_t>(o.coord);
+    if (spz_amd_render_check_params(&p) != SPZ_AMD_OK) {
+      return opRejected(who, invalid,
+                        "view %zu: bad camera: R must be a rotation (to 1e-4), fx, fy > 0, nearPlane > 0, values "
+                        "finite, maxShDegree 0..3, coord valid", v);
+    }
+  }
+  return true;
+}
+
+ImageMetrics toMetrics(const spz_amd_image_metrics &m) {
+  ImageMetrics r;
+  r.mse = m.mse;
+  r.psnr = m.psnr;
+  r.ssim = m.ssim;
+  r.l1 = m.l1;
+  r.maxAbs = m.max_abs;
+  return r;
+}
+}  // namespace
+
+bool compareSpz(const uint8_t *dataA, int32_t sizeA, const uint8_t *dataB, int32_t sizeB, const CompareOptions &o,
+                std::vector<ImageMetrics> *metrics, std::vector<std::vector<float>> *ssimMaps) {
+  const char *who = "compareSpz";
+  g_last_status = SPZ_AMD_OK;
+  if (ssimMaps) ssimMaps->clear();
+  if (metrics == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no output vector");
+  metrics->clear();
+  std::vector<spz_amd_render_params> params;
+  if (!compareOptionsOk(o, &params)) return false;
+  Laps laps(who, "SPZ_AMD_COMPARE_TIMING");
+  DevicePackedGaussians da, db;
+  if (!loadInput(who, dataA, sizeA, &da) || !loadInput(who, dataB, sizeB, &db)) return false;
+  laps.lap("inflate");
+  if (da.device != db.device) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "the inputs were loaded on different devices");
+  const spz_amd_header ha = headerOf(da), hb = headerOf(db);
+  const size_t nv = params.size();
+  std::vector<spz_amd_image_metrics> m(nv);
+  std::vector<float> maps;
+  if (ssimMaps) {
+    size_t floats = 0;
+    for (const spz_amd_render_params &p : params) floats += static_cast<size_t>(p.width) * p.height;
+    detail::resizeUninitialized(&maps, floats);
+  }
+  std::vector<uint64_t> entries(2 * nv);
+  float ms[2] = {0.0f, 0.0f};
+  int32_t bad = -1;
+  const int rc = spz_amd_compare_host(da.stream, da.streamBytes, &ha, db.stream, db.streamBytes, &hb, params.data(),
+                                      static_cast<int>(nv), da.device, m.data(), ssimMaps ? maps.data() : nullptr,
+                                      entries.data(), ms, &bad);
+  if (rc == SPZ_AMD_ERR_CAPACITY && bad >= 0) return opRejected(who, rc, "view %d: more than 2^31 - 1 tile entries", bad);
+  if (rc != SPZ_AMD_OK && bad >= 0) logLine("[SPZ ERROR] compareSpz: view %d failed", bad);
+  if (deviceFailed(rc, who)) return false;
+  uint64_t ea = 0, eb = 0;
+  for (size_t v = 0; v < nv; ++v) {
+    ea += entries[2 * v];
+    eb += entries[2 * v + 1];
+  }
+  laps.stage("render", ms[0], (" (" + std::to_string(nv) + " views; entries " + std::to_string(ea) + " + " +
+                               std::to_string(eb) + ")").c_str());
+  laps.stage("metrics", ms[1]);
+  laps.lap("compare");
+  metrics->resize(nv);
+  for (size_t v = 0; v < nv; ++v) (*metrics)[v] = toMetrics(m[v]);
+  if (ssimMaps) {
+    ssimMaps->resize(nv);
+    size_t at = 0;
+    for (size_t v = 0; v < nv; ++v) {
+      const size_t px = static_cast<size_t>(params[v].width) * params[v].height;
+      (*ssimMaps)[v].assign(maps.begin() + static_cast<std::ptrdiff_t>(at),
+                            maps.begin() + static_cast<std::ptrdiff_t>(at + px));
+      at += px;
+    }
+  }
+  return true;
+}
+
+bool compareSpz(const std::string &fileA, const std::string &fileB, const CompareOptions &o,
+                std::vector<ImageMetrics> *metrics, std::vector<std::vector<float>> *ssimMaps) {
+  const char *who = "compareSpz";
+  g_last_status = SPZ_AMD_OK;
+  if (ssimMaps) ssimMaps->clear();
+  if (metrics == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no output vector");
+  metrics->clear();
+  std::vector<spz_amd_render_params> params;
+  if (!compareOptionsOk(o, &params)) return false;
+  std::vector<uint8_t> a, b;
+  if (!readInput(who, fileA, &a) || !readInput(who, fileB, &b)) return false;
+  return compareSpz(a.data(), static_cast<int32_t>(a.size()), b.data(), static_cast<int32_t>(b.size()), o, metrics,
+                    ssimMaps);
+}
+
+bool compareImages(const float *a, int channelsA, const float *b, int channelsB, int width, int height,
+                   ImageMetrics *metrics, std::vector<float> *ssimMap) {
+  const char *who = "compareImages";
+  g_last_status = SPZ_AMD_OK;
+  if (ssimMap) ssimMap->clear();
+  if (a == nullptr || b == nullptr || metrics == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no image or no output");
+  if (spz_amd_image_metrics_check(width, height, channelsA, channelsB) != SPZ_AMD_OK) {
+    return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "%d x %d with %d and %d channels: sides 1..16384, channels 3 or 4",
+                      width, height, channelsA, channelsB);
+  }
+  Laps laps(who, "SPZ_AMD_COMPARE_TIMING");
+  std::vector<float> map;
+  if (ssimMap) detail::resizeUninitialized(&map, static_cast<size_t>(width) * static_cast<size_t>(height));
+  spz_amd_image_metrics m = {};
+  const int rc = spz_amd_image_metrics_host(a, channelsA, b, channelsB, width, height, deviceIndex(), &m,
+                                            ssimMap ? map.data() : nullptr);
+  if (deviceFailed(rc, who)) return false;
+  laps.lap("metrics");
+  *metrics = toMetrics(m);
+  if (ssimMap) ssimMap->swap(map);
+  return true;
+}
+
 GaussianCloud loadSpz(const std::vector<uint8_t> &data, const UnpackOptions &o) {
   return loadSpz(data.data(), static_cast<int32_t>(data.size()), o);
 }

@@ -195,6 +195,23 @@ py::dict viewDict(const spz::PruneOptions::View &v) {
   return d;
 }
 
+// compare_spz / compare_images' result of one image pair.
+py::dict metricsDict(const spz::ImageMetrics &m) {
+  py::dict d;
+  d["mse"] = m.mse;
+  d["psnr"] = m.psnr;
+  d["ssim"] = m.ssim;
+  d["l1"] = m.l1;
+  d["max_abs"] = m.maxAbs;
+  return d;
+}
+
+py::array_t<float> mapArray(const std::vector<float> &map, int height, int width) {
+  py::array_t<float> out({static_cast<py::ssize_t>(height), static_cast<py::ssize_t>(width)});
+  if (!map.empty()) std::memcpy(out.mutable_data(), map.data(), map.size() * sizeof(float));
+  return out;
+}
+
 // filter_spz's arguments as spz::FilterOptions; every problem is a ValueError, raised before any device work.
 spz::FilterOptions filterOptions(const py::object &mask, const py::object &indices, const py::object &box,
                                  spz::CoordinateSystem coord, const py::object &min_alpha, const py::object &sh_degree) {
@@ -946,6 +963,115 @@ PYBIND11_MODULE(spz, m) {
         py::arg("filename"),
         "The views of a plain-text views file (spz_prune --views; spz::loadViewsFile) as prune_spz's view dicts: one "
         "view per line, 'width height fx fy cx cy r00 r01 r02 t0 r10 r11 r12 t1 r20 r21 r22 t2', '#' starts a comment.");
+  m.def("compare_spz",
+        [](const py::object &a, const py::object &b, const py::object &views, spz::CoordinateSystem coord,
+           const py::object &background, int max_sh_degree, float near_plane, const py::object &return_maps) {
+          // the arguments first: every problem is a ValueError before any device work
+          if (!py::isinstance<py::bool_>(return_maps)) throw py::value_error("return_maps must be a bool");
+          if (!std::isfinite(near_plane) || !(near_plane > 0.0f)) throw py::value_error("near must be > 0");
+          if (max_sh_degree < 0 || max_sh_degree > 3) throw py::value_error("max_sh_degree must be 0..3");
+          spz::CompareOptions o;
+          py::array_t<float, py::array::c_style | py::array::forcecast> bg(background);
+          if (bg.size() != 3) throw py::value_error("background must have three values");
+          for (int k = 0; k < 3; ++k) {
+            o.background[k] = bg.data()[k];
+            if (!std::isfinite(o.background[k])) throw py::value_error("background must be finite");
+          }
+          o.coord = coord;
+          o.nearPlane = near_plane;
+          o.maxShDegree = max_sh_degree;
+          if (py::isinstance<py::dict>(views) || py::isinstance<py::str>(views) || !py::isinstance<py::sequence>(views)) {
+            throw py::value_error("views must be a sequence of view dicts (orbit_views, load_3dgs_cameras)");
+          }
+          const py::sequence seq = py::reinterpret_borrow<py::sequence>(views);
+          if (seq.size() < 1 || seq.size() > SPZ_AMD_COMPARE_MAX_VIEWS) {
+            throw py::value_error("give 1..1024 views, got " + std::to_string(seq.size()));
+          }
+          for (size_t k = 0; k < seq.size(); ++k) o.views.push_back(pruneView(seq[k], k, coord, near_plane));
+          const bool maps = py::cast<bool>(return_maps);
+          std::vector<spz::ImageMetrics> got;
+          std::vector<std::vector<float>> ssim;
+          bool ok;
+          if (py::isinstance<py::bytes>(a) != py::isinstance<py::bytes>(b)) {
+            throw py::value_error("give a and b both as paths or both as bytes");
+          }
+          if (py::isinstance<py::bytes>(a)) {
+            const std::string ba = a.cast<std::string>(), bb = b.cast<std::string>();
+            if (ba.size() > static_cast<size_t>(INT32_MAX) || bb.size() > static_cast<size_t>(INT32_MAX)) {
+              throw py::value_error("an input is larger than 2 GiB");
+            }
+            py::gil_scoped_release release;
+            ok = spz::compareSpz(reinterpret_cast<const uint8_t *>(ba.data()), static_cast<int32_t>(ba.size()),
+                                 reinterpret_cast<const uint8_t *>(bb.data()), static_cast<int32_t>(bb.size()), o, &got,
+                                 maps ? &ssim : nullptr);
+          } else {
+            const std::string fa = py::str(a).cast<std::string>(), fb = py::str(b).cast<std::string>();
+            py::gil_scoped_release release;
+            ok = spz::compareSpz(fa, fb, o, &got, maps ? &ssim : nullptr);
+          }
+          if (!ok) {
+            raiseFailure("compare_spz: refused (see the [SPZ ERROR] line)",
+                         "compare_spz failed (see the [SPZ ERROR] line)");
+          }
+          py::list out;
+          for (size_t v = 0; v < got.size(); ++v) {
+            py::dict d = metricsDict(got[v]);
+            if (maps) d["ssim_map"] = mapArray(ssim[v], o.views[v].height, o.views[v].width);
+            out.append(d);
+          }
+          return out;
+        },
+        py::arg("a"), py::arg("b"), py::arg("views"), py::kw_only(),
+        py::arg("coord") = spz::CoordinateSystem::UNSPECIFIED,
+        py::arg("background") = py::make_tuple(0.0f, 0.0f, 0.0f), py::arg("max_sh_degree") = 3,
+        py::arg("near") = 0.2f, py::arg("return_maps") = false,
+        "Render two .spz files (paths, or both files' bytes) from every view on the device and compare each view's two "
+        "images (spz::compareSpz; the contract is in include/spz_amd.h \"image metrics\" and \"compare\").  views: "
+        "1..1024 dicts as orbit_views, load_views_file and load_3dgs_cameras return them, in the frame `coord`.  Returns "
+        "one dict per view: mse, psnr (dB; inf when the images are equal), ssim, l1, max_abs; with return_maps also "
+        "ssim_map, a (height, width) float32 array of S averaged over the channels.");
+  m.def("compare_images",
+        [](const py::object &a, const py::object &b, const py::object &return_map) {
+          if (!py::isinstance<py::bool_>(return_map)) throw py::value_error("return_map must be a bool");
+          auto image = [](const py::object &o, const char *name) {
+            if (!py::isinstance<py::array>(o)) throw py::value_error(std::string(name) + " must be a numpy array");
+            const py::array arr = py::reinterpret_borrow<py::array>(o);
+            if (!arr.dtype().is(py::dtype::of<float>())) throw py::value_error(std::string(name) + " must be float32");
+            if (arr.ndim() != 3 || (arr.shape(2) != 3 && arr.shape(2) != 4)) {
+              throw py::value_error(std::string(name) + " must be height x width x 3 or 4");
+            }
+            return py::array_t<float, py::array::c_style | py::array::forcecast>(arr);
+          };
+          const auto fa = image(a, "a"), fb = image(b, "b");
+          if (fa.shape(0) != fb.shape(0) || fa.shape(1) != fb.shape(1)) {
+            throw py::value_error("a and b must have the same height and width");
+          }
+          if (fa.shape(0) < 1 || fa.shape(0) > 16384 || fa.shape(1) < 1 || fa.shape(1) > 16384) {
+            throw py::value_error("height and width must be in 1..16384");
+          }
+          const int h = static_cast<int>(fa.shape(0)), w = static_cast<int>(fa.shape(1));
+          const int ca = static_cast<int>(fa.shape(2)), cb = static_cast<int>(fb.shape(2));
+          const bool want = py::cast<bool>(return_map);
+          spz::ImageMetrics m;
+          std::vector<float> map;
+          bool ok;
+          {
+            py::gil_scoped_release release;
+            ok = spz::compareImages(fa.data(), ca, fb.data(), cb, w, h, &m, want ? &map : nullptr);
+          }
+          if (!ok) {
+            raiseFailure("compare_images: refused (see the [SPZ ERROR] line)",
+                         "compare_images failed (see the [SPZ ERROR] line)");
+          }
+          py::dict d = metricsDict(m);
+          if (want) d["ssim_map"] = mapArray(map, h, w);
+          return d;
+        },
+        py::arg("a"), py::arg("b"), py::kw_only(), py::arg("return_map") = false,
+        "PSNR, MSE, L1, max error and SSIM of two (height, width, 3 or 4) float32 images on the device "
+        "(spz::compareImages; include/spz_amd.h \"image metrics\"): values clamped to [0, 1] (NaN -> 0), the first three "
+        "channels, an 11x11 Gaussian window of sigma 1.5 with zero padding.  Returns a dict: mse, psnr, ssim, l1, "
+        "max_abs; with return_map also ssim_map, (height, width) float32.");
   m.def("clean_spz",
         [](const std::string &input, const std::string &output, const py::object &k, const py::object &std_ratio,
            const py::object &radius, const py::object &min_neighbors, const py::object &return_details) -> py::object {

@@ -806,6 +806,37 @@ def preprocess_packed(stream_t, header, params, stream=None):
     return _preprocess(("packed", stream_t, header), header.num_points, params, stream_t.device, stream)
 
 
+def image_metrics(a_t, b_t, ssim_map=None, stream=None):
+    """PSNR, MSE, L1, max error and SSIM of two (height, width, 3 or 4) float32 CUDA tensors on one device
+    (spz_amd_image_metrics_device; the contract is in include/spz_amd.h "image metrics"): a float64 tensor [mse, psnr,
+    ssim, l1, max_abs] on the device, not synchronised, so it can follow render() in a loop.  ssim_map: a contiguous
+    (height, width) float32 tensor that gets the map.  stream: as render()."""
+    L = abi.load_library()
+    for name, t in (("a", a_t), ("b", b_t)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() \
+                or t.dim() != 3 or t.shape[2] not in (3, 4):
+            raise ValueError(f"{name} must be a contiguous float32 CUDA tensor of shape (height, width, 3 or 4)")
+    dev = a_t.device
+    if b_t.device != dev or tuple(a_t.shape[:2]) != tuple(b_t.shape[:2]):
+        raise ValueError("a and b must have the same height and width, on one device")
+    h, w = int(a_t.shape[0]), int(a_t.shape[1])
+    abi.check(L.spz_amd_image_metrics_check(w, h, int(a_t.shape[2]), int(b_t.shape[2])), "spz_amd_image_metrics_check")
+    if ssim_map is not None and (not isinstance(ssim_map, torch.Tensor) or ssim_map.dtype != torch.float32
+                                 or ssim_map.device != dev or not ssim_map.is_contiguous()
+                                 or tuple(ssim_map.shape) != (h, w)):
+        raise ValueError(f"ssim_map must be a contiguous float32 tensor of shape ({h}, {w}) on {dev}")
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        with torch.cuda.stream(st):
+            out = torch.empty(5, dtype=torch.float64, device=dev)
+            ws = torch.empty(max(8, int(L.spz_amd_image_metrics_workspace_bytes(w, h))), dtype=torch.uint8, device=dev)
+            rc = L.spz_amd_image_metrics_device(a_t.data_ptr(), int(a_t.shape[2]), b_t.data_ptr(), int(b_t.shape[2]), w,
+                                                h, out.data_ptr(), ssim_map.data_ptr() if ssim_map is not None else None,
+                                                ws.data_ptr(), C.c_void_p(st.cuda_stream))
+    abi.check(rc, "spz_amd_image_metrics_device")
+    return out
+
+
 def convert_coordinates(cloud, num_points, sh_degree, from_coord, to_coord, stream=None):
     """In-place GaussianCloud::convertCoordinates on device tensors (positions, rotations, sh)."""
     L = abi.load_library()
