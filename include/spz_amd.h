@@ -437,6 +437,96 @@ int spz_amd_decimate_fetch(void *ctx, uint8_t *h_out);
 const uint8_t *spz_amd_decimate_device_data(void *ctx);
 void spz_amd_decimate_close(void *ctx);
 
+/* ---- tile: an octree of LOD tiles over a packed stream (spz_tile.hip; DESIGN §8 "Tile").  The reference has no
+ *      counterpart.  Input v2 or v3 (version 1: SPZ_AMD_ERR_UNSUPPORTED, as sort and decimate); above
+ *      SPZ_AMD_REFERENCE_MAX_POINTS: SPZ_AMD_ERR_TOO_MANY_POINTS.  Everything is in the stored RUB frame and in the
+ *      sort's and the decimate's conventions (u_a, cell = u >> L, cells(L), Morton order of the cells).
+ *
+ *      With the points in Morton order (spz_amd_morton_order_device, stable) and cap = max_points >= 1:
+ *      A node (L, c) is an occupied cell c at level L (0..24); count(L, c) its number of points, a contiguous range
+ *      [s, e) of the sorted order; cells_l(node) the number of occupied level-l cells inside it (l <= L; cells_L = 1,
+ *      cells_0 = distinct stored positions).
+ *      The root is the cell at the smallest L with cells(L) == 1.  A node is a leaf iff count <= cap or L == 0 (a pile
+ *      of more than cap points on one lattice position is a leaf above the cap: the one exception to the cap).  Any
+ *      other node is interior; its children are its occupied level L - 1 cells.  An interior node with exactly one
+ *      occupied child is not emitted: the child takes its place, so every emitted interior tile has >= 2 children and
+ *      there are at most 2 leaves - 1 tiles.
+ *      Leaf content: points [s, e) of the sorted stream with all their bytes, i.e. spz_amd_subset_device(stream,
+ *      order[s..e)) at the input's degree (the header keeps version, fractionalBits and the antialiased bit).
+ *      content_level = -1, content_begin = s, geometric_error = 0.
+ *      Interior content: content_level l = the smallest l in 0..L with cells_l(node) <= cap; the content is the index
+ *      range [content_begin, content_begin + num_points) of spz_amd_decimate_device(stream, level = l) whose cells lie
+ *      in the node, byte for byte (a v3 stream, the decimate's header).  geometric_error = 2^(l - fractionalBits), the
+ *      cell edge in world units.  So num_points = cells_l(node) <= cap, cells_(l-1)(node) > cap when l > 0, and a
+ *      child's content_level never exceeds its parent's (the child's cells are a subset of the parent's at every level).
+ *      Order and ids: pre-order, i.e. ascending range start, the larger L first; id = the position in that order, so
+ *      an interior tile's first child is id + 1 and a parent's children are in ascending Morton order.  A function of
+ *      the input and cap only.
+ *      Bounds, over a tile's content points: min / max per axis of the sign-extended stored integers times
+ *      2^-fractionalBits (exact in f32, as spz_amd_chunk_bounds_device), and max_radius = 3 exp(scale) in f32 of the
+ *      largest scale byte of the content (exp in f64 of the f32 log scale byte / 16 - 10, rounded to f32, from a table
+ *      the host's libm fills).  A tile without points: NaN boxes, max_radius 0.
+ *      Arena: the tiles' streams in id order, each at `offset` (a multiple of 16) and `bytes` long, zeros between them.
+ *      Deterministic: no float atomics; integer atomics and fixed-order scans only: a run repeats its table and bytes.
+ *      Arguments: max_points 1..SPZ_AMD_REFERENCE_MAX_POINTS, max_tiles 1..2^31 - 1; a bad one is
+ *      SPZ_AMD_ERR_INVALID_ARG before anything is launched.  n == 0: one empty leaf (level 0, 16 bytes).
+ *
+ *      tile_workspace_bytes (host only, no GPU): device memory for tile_tree_device.
+ *      tile_tree_device: sorts, then writes the summary and, when the tree has at most max_tiles tiles (summary.ok),
+ *      the table rows (d_table: min(max_tiles, max(1, 2 n - 1)) rows) with every integer field, the arena layout and the
+ *      leaves' bounds; interior boxes are NaN and their max_radius 0.  Enqueue-only; nothing is read back.
+ *      tile_content_device: for the num_tiles rows whose content_level is `content_level` (-1: the leaves), with
+ *      d_source the stream their content is cut from (the sorted stream; the decimate's output at that level; its
+ *      header is read on the device): the bounds into the table and, when d_arena is not NULL, header + six sections
+ *      of every such tile into the arena at the table's offsets.  One launch per source, work items of 1024 points; a
+ *      row whose range does not lie in the source or the arena is left alone.  Enqueue-only.
+ *      The host form takes a stream already in device memory, runs on `device` on a stream of its own and blocks: the
+ *      tree, one readback of the summary and the table (more than max_tiles tiles: SPZ_AMD_ERR_CAPACITY, before any
+ *      content is produced), then per distinct content_level one spz_amd_decimate_device into a reused buffer and its
+ *      tile_content_device, then the leaves', all enqueued without readbacks; the finished table is read once at the
+ *      end.  h_ms (may be NULL): wall-clock milliseconds of [0] the sort, [1] the tree, [2] the decimates, [3] bounds
+ *      and emit.  tile_table: the rows; tile_fetch / tile_device_data: one tile's stream; tile_fetch_arena: all. */
+typedef struct {
+  uint32_t id;
+  int32_t parent;          /* -1: the root */
+  int32_t first_child;     /* id + 1, or -1 for a leaf */
+  uint32_t child_count;
+  int32_t level;           /* L */
+  uint32_t cell[3];        /* u_a >> L of the tile's points */
+  uint32_t range_begin, range_end;   /* [s, e) of the sorted order */
+  int32_t content_level;   /* -1: a leaf */
+  uint32_t num_points;     /* of the content */
+  uint32_t content_begin;  /* first index of the content in its source stream */
+  uint32_t reserved;
+  uint64_t offset, bytes;  /* of the tile's stream in the arena */
+  float box_min[3], box_max[3];
+  float max_radius;
+  float geometric_error;
+} spz_amd_tile_info;       /* 104 bytes */
+typedef struct {
+  uint64_t num_tiles;
+  uint64_t arena_bytes;
+  uint32_t ok;             /* num_tiles <= max_tiles: the table is written */
+  uint32_t root_level;
+  uint64_t cells[25];      /* cells(L) of the whole stream */
+} spz_amd_tile_summary;
+uint64_t spz_amd_tile_workspace_bytes(uint64_t num_points, int sh_degree, uint64_t max_tiles);
+uint64_t spz_amd_tile_content_workspace_bytes(uint64_t num_tiles);
+int spz_amd_tile_tree_device(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, uint32_t max_points,
+                             uint32_t max_tiles, spz_amd_tile_info *d_table, spz_amd_tile_summary *d_summary,
+                             void *d_workspace, void *hip_stream);
+int spz_amd_tile_content_device(spz_amd_tile_info *d_table, uint32_t num_tiles, int content_level,
+                                const uint8_t *d_source, size_t source_size, uint8_t *d_arena, uint64_t arena_bytes,
+                                void *d_workspace, void *hip_stream);
+int spz_amd_tile_open(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, uint32_t max_points,
+                      uint32_t max_tiles, int device, void **ctx, uint64_t *h_num_tiles, uint64_t *h_arena_bytes,
+                      float *h_ms);
+int spz_amd_tile_table(void *ctx, spz_amd_tile_info *h_table);
+int spz_amd_tile_fetch(void *ctx, uint32_t id, uint8_t *h_out);
+int spz_amd_tile_fetch_arena(void *ctx, uint8_t *h_out);
+const uint8_t *spz_amd_tile_device_data(void *ctx, uint32_t id);
+void spz_amd_tile_close(void *ctx);
+
 /* ---- clean: floater removal, the statistical (k nearest neighbours) and the radius outlier rules (spz_clean.hip;
  *      DESIGN §8 "Clean").  The reference has no counterpart.  Input v2 or v3 (version 1, float16 positions:
  *      SPZ_AMD_ERR_UNSUPPORTED, as for the sort).  Streams above SPZ_AMD_REFERENCE_MAX_POINTS:

@@ -497,4 +497,48 @@ bool compareImages(const float *a, int channelsA, const float *b, int channelsB,
 int lastDeviceStatus();
 void setLastDeviceStatus(int status);
 
+// Tile (DESIGN §8 "Tile"): a file cut into an octree of level-of-detail tiles for streaming (include/spz_amd.h, "tile",
+// states the contract).  The member is inflated (loadSpzPackedDevice), tiled on the device (spz_amd_tile_open), and every
+// tile's stream is written as outDir/tile_%06u.spz with zlib's level-6 bytes (members under 1 MiB by zlib on at most 16
+// threads, larger ones through compressGzipped), with outDir/tileset.json beside them.  outDir must be absent (it is
+// created) or an empty directory; nothing is written when the arguments, the input or the tree (more than maxTiles tiles)
+// are refused.  coord only flips the boxes' axes as coordinateConverter(RUB, coord) does; the tiles' bytes stay in the
+// stored frame.  false + one "[SPZ ERROR] tileSpz: …" line on failure.  SPZ_AMD_TILE_TIMING=1 prints the stages' times.
+struct TileOptions {
+  uint32_t maxPoints = 65536;
+  uint32_t maxTiles = 65536;
+  CoordinateSystem coord = CoordinateSystem::RUB;
+};
+struct Tile {
+  uint32_t id = 0;
+  std::string file;
+  int32_t parent = -1;
+  std::vector<uint32_t> children;   // ascending Morton order
+  int32_t level = 0;
+  std::array<uint32_t, 3> cell = {0, 0, 0};
+  int32_t contentLevel = -1;        // -1: a leaf
+  uint32_t numPoints = 0;
+  float geometricError = 0.0f;
+  std::array<float, 3> boxMin = {0, 0, 0}, boxMax = {0, 0, 0};   // NaN for a tile without points
+  float maxRadius = 0.0f;
+};
+struct Tileset {
+  CoordinateSystem coord = CoordinateSystem::RUB;
+  uint64_t numPoints = 0;
+  int shDegree = 0, fractionalBits = 0;
+  uint32_t maxPoints = 0;
+  std::vector<Tile> tiles;          // tiles[i].id == i
+};
+bool tileSpz(const std::string &inputFilename, const std::string &outDir, const TileOptions &options,
+             Tileset *tileset = nullptr);
+// tileset.json written / read: floats are written so that they read back to the same f32 (NaN as null).
+bool saveTileset(const Tileset &tileset, const std::string &path);
+bool loadTileset(const std::string &path, Tileset *tileset);
+// The screen-space-error cut, host only, float64.  A tile's sphere: the centre and half-diagonal of its box plus
+// maxRadius; d = max(|centre - eye| - radius, nearPlane), eye = -R^T t of view.worldToCamera (in the tileset's coord
+// frame); sse = geometricError max(fx, fy) / d.  Descends while sse > maxPixelError and the tile has children, else
+// takes it.  Tile ids in tile order; every leaf has exactly one ancestor-or-self in the result.
+std::vector<uint32_t> selectTiles(const Tileset &tileset, const PruneOptions::View &view, double maxPixelError,
+                                  double nearPlane = 0.2);
+
 }  // namespace spz

@@ -9,6 +9,7 @@ Layout:
   csrc/spz_merge.hip    K packed streams -> one v3 stream, bytes copied where possible (mergeSpz)
   csrc/spz_sort.hip     stable device radix argsort, Morton order of the stored positions, chunk bounds (sortSpz)
   csrc/spz_decimate.hip one point per occupied octree cell by moment matching, over the Morton-sorted stream (decimateSpz)
+  csrc/spz_tile.hip     an octree of LOD tiles over the Morton-sorted stream: tree, level choice, bounds, batched emit
   csrc/spz_clean.hip    exact k-NN scores and radius counts over the Morton-sorted positions, floater removal (cleanSpz)
   csrc/spz_render.hip   a tiled 3D Gaussian splat rasteriser: preprocess, depth and tile order, per-tile blend (renderSpz)
   csrc/spz_prune.hip    per-Gaussian blend weights over views, exact rank, the filter's subset of the kept (pruneSpz)

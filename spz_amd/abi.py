@@ -71,6 +71,9 @@ EXPORTS = (
     "spz_amd_sort_close",
     "spz_amd_decimate_workspace_bytes", "spz_amd_decimate_level_counts_device", "spz_amd_decimate_device",
     "spz_amd_decimate_open", "spz_amd_decimate_fetch", "spz_amd_decimate_device_data", "spz_amd_decimate_close",
+    "spz_amd_tile_workspace_bytes", "spz_amd_tile_content_workspace_bytes", "spz_amd_tile_tree_device",
+    "spz_amd_tile_content_device", "spz_amd_tile_open", "spz_amd_tile_table", "spz_amd_tile_fetch",
+    "spz_amd_tile_fetch_arena", "spz_amd_tile_device_data", "spz_amd_tile_close",
     "spz_amd_clean_workspace_bytes", "spz_amd_clean_radius_r2", "spz_amd_knn_scores_device",
     "spz_amd_radius_counts_device", "spz_amd_clean_open", "spz_amd_clean_fetch", "spz_amd_clean_device_data",
     "spz_amd_clean_close",
@@ -126,6 +129,24 @@ class ImageMetrics(C.Structure):
     """spz_amd_image_metrics: the five results of one image pair (include/spz_amd.h "image metrics")."""
     _fields_ = [("mse", C.c_double), ("psnr", C.c_double), ("ssim", C.c_double), ("l1", C.c_double),
                 ("max_abs", C.c_double)]
+
+
+class TileInfo(C.Structure):
+    """spz_amd_tile_info: one row of a tile table (include/spz_amd.h "tile"); 104 bytes."""
+    _fields_ = [("id", C.c_uint32), ("parent", C.c_int32), ("first_child", C.c_int32), ("child_count", C.c_uint32),
+                ("level", C.c_int32), ("cell", C.c_uint32 * 3), ("range_begin", C.c_uint32), ("range_end", C.c_uint32),
+                ("content_level", C.c_int32), ("num_points", C.c_uint32), ("content_begin", C.c_uint32),
+                ("reserved", C.c_uint32), ("offset", C.c_uint64), ("bytes", C.c_uint64), ("box_min", C.c_float * 3),
+                ("box_max", C.c_float * 3), ("max_radius", C.c_float), ("geometric_error", C.c_float)]
+
+
+class TileSummary(C.Structure):
+    """spz_amd_tile_summary: what spz_amd_tile_tree_device leaves beside the table."""
+    _fields_ = [("num_tiles", C.c_uint64), ("arena_bytes", C.c_uint64), ("ok", C.c_uint32), ("root_level", C.c_uint32),
+                ("cells", C.c_uint64 * 25)]
+
+
+TILE_DEFAULT_MAX_TILES = 65536
 
 
 class CloudBuffers(C.Structure):
@@ -400,6 +421,27 @@ def bind(L):
     L.spz_amd_decimate_device_data.argtypes = [vp]
     L.spz_amd_decimate_close.restype = None
     L.spz_amd_decimate_close.argtypes = [vp]
+    L.spz_amd_tile_workspace_bytes.restype = u64
+    L.spz_amd_tile_workspace_bytes.argtypes = [u64, i32, u64]
+    L.spz_amd_tile_content_workspace_bytes.restype = u64
+    L.spz_amd_tile_content_workspace_bytes.argtypes = [u64]
+    L.spz_amd_tile_tree_device.restype = i32
+    L.spz_amd_tile_tree_device.argtypes = [vp, sz, C.POINTER(Header), C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    L.spz_amd_tile_content_device.restype = i32
+    L.spz_amd_tile_content_device.argtypes = [vp, C.c_uint32, i32, vp, sz, vp, u64, vp, vp]
+    L.spz_amd_tile_open.restype = i32
+    L.spz_amd_tile_open.argtypes = [vp, sz, C.POINTER(Header), C.c_uint32, C.c_uint32, i32, C.POINTER(vp),
+                                    C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_float)]
+    L.spz_amd_tile_table.restype = i32
+    L.spz_amd_tile_table.argtypes = [vp, vp]
+    L.spz_amd_tile_fetch.restype = i32
+    L.spz_amd_tile_fetch.argtypes = [vp, C.c_uint32, vp]
+    L.spz_amd_tile_fetch_arena.restype = i32
+    L.spz_amd_tile_fetch_arena.argtypes = [vp, vp]
+    L.spz_amd_tile_device_data.restype = vp
+    L.spz_amd_tile_device_data.argtypes = [vp, C.c_uint32]
+    L.spz_amd_tile_close.restype = None
+    L.spz_amd_tile_close.argtypes = [vp]
     L.spz_amd_clean_workspace_bytes.restype = u64
     L.spz_amd_clean_workspace_bytes.argtypes = [u64]
     L.spz_amd_clean_radius_r2.restype = i32

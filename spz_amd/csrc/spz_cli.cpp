@@ -1,9 +1,9 @@
 // spz_cli.cpp — the three command-line tools of the reference (cli_tools/src/*.cpp) over the
 // MI355X drop-in layer: ply_to_spz, spz_to_ply, spz_info; and spz_filter (spz::filterSpz),
 // spz_transform (spz::transformSpz), spz_merge (spz::mergeSpz), spz_sort (spz::sortSpz), spz_decimate
-// (spz::decimateSpz), spz_clean (spz::cleanSpz), spz_render (spz::renderSpz), spz_prune (spz::pruneSpz) and spz_compare
+// (spz::decimateSpz), spz_tile (spz::tileSpz), spz_clean (spz::cleanSpz), spz_render (spz::renderSpz), spz_prune (spz::pruneSpz) and spz_compare
 // (spz::compareSpz), which have no counterpart in the reference.  One binary, dispatched on argv[0] (the Makefile
-// installs it under the twelve names) or on a first argument naming the tool.
+// installs it under the thirteen names) or on a first argument naming the tool.
 // spz_compare exits 0 on success, 1 on a failure and 2 when a view misses --min-psnr or --min-ssim.
 // Same behaviour as the reference mains: default (UNSPECIFIED) pack/unpack options, exit code 0
 // once the arguments are there (the reference ignores the save/load results), usage -> 1.
@@ -282,6 +282,24 @@ int spzDecimate(int argc, char **argv) {
   }
   if (o.level.has_value() == o.targetPoints.has_value()) return a.usage();
   return spz::decimateSpz(std::string(argv[1]), std::string(argv[2]), o) ? 0 : 1;
+}
+
+const char *kTileUsage =
+    "Usage: spz_tile <input.spz> <outdir> --max-points <N> [--max-tiles <M>] [--coord " SPZ_COORD_NAMES "]";
+
+int spzTile(int argc, char **argv) {
+  Args a(argc, argv, kTileUsage);
+  if (!a.files()) return a.usage();
+  spz::TileOptions o;
+  while (a.next()) {
+    bool good = false;
+    if (a.is("--max-points")) good = a.integer(&o.maxPoints, 1, 10000000);
+    else if (a.is("--max-tiles")) good = a.integer(&o.maxTiles, 1, 2147483647);
+    else if (a.is("--coord")) good = a.coord(&o.coord);
+    if (!good) return a.usage();
+  }
+  if (!a.given("--max-points")) return a.usage();
+  return spz::tileSpz(std::string(argv[1]), std::string(argv[2]), o) ? 0 : 1;
 }
 
 const char *kCleanUsage =
@@ -580,7 +598,8 @@ const struct {
 } kTools[] = {{"ply_to_spz", plyToSpz},     {"spz_to_ply", spzToPly},         {"spz_info", spzInfo},
               {"spz_filter", spzFilter},    {"spz_transform", spzTransform},  {"spz_merge", spzMerge},
               {"spz_sort", spzSort},        {"spz_decimate", spzDecimate},    {"spz_clean", spzClean},
-              {"spz_render", spzRender},    {"spz_prune", spzPrune},          {"spz_compare", spzCompare}};
+              {"spz_render", spzRender},    {"spz_prune", spzPrune},          {"spz_compare", spzCompare},
+              {"spz_tile", spzTile}};
 
 int dispatch(const std::string &tool, int argc, char **argv) {
   for (const auto &t : kTools) {

@@ -308,13 +308,14 @@ inline double ms_since(std::chrono::steady_clock::time_point t0) {
 }
 
 // An operation's output stream in HBM until its close: the ctx of every spz_amd_<op>_open / _fetch / _device_data /
-// _close host form (filter, transform, merge, sort, decimate, clean, prune).  `out` points into one of the allocations.
+// _close host form (filter, transform, merge, sort, decimate, clean, prune, tile).  `out` points into one of the allocations.
 struct PackedResult {
   int device = 0;
   hipStream_t st = nullptr;
   uint8_t *block = nullptr;      // the operation's workspace (filter, transform, merge, sort: the output stream too)
   uint8_t *scratch = nullptr;    // a second workspace (prune: the render's)
-  uint8_t *out_block = nullptr;  // the output stream in an allocation of its own (decimate, clean, prune)
+  uint8_t *out_block = nullptr;  // the output stream in an allocation of its own (decimate, clean, prune; tile: the arena)
+  uint8_t *extra = nullptr;      // a fourth allocation (tile: the decimate output its coarse tiles are cut from)
   uint8_t *out = nullptr;
   uint64_t out_bytes = 0;
 };
@@ -330,7 +331,7 @@ inline void packed_result_free(PackedResult *r) {
     (void)hipStreamSynchronize(r->st);
     (void)hipStreamDestroy(r->st);
   }
-  for (uint8_t *p : {r->block, r->scratch, r->out_block}) {
+  for (uint8_t *p : {r->block, r->scratch, r->out_block, r->extra}) {
     if (p) (void)hipFree(p);
   }
   if (prev >= 0) (void)hipSetDevice(prev);

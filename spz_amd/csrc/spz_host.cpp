@@ -10,6 +10,7 @@
 #include <unistd.h>
 #include <fcntl.h>
 #include <sys/stat.h>
+#include <dirent.h>
 #include <cerrno>
 #include <zlib.h>
 
@@ -2853,6 +2854,367 @@ GaussianCloud loadSpz(const std::string &filename, const UnpackOptions &o) {
   std::vector<uint8_t> data;
   if (!readFile(filename, &data, /*log=*/true)) return {};
   return loadSpz(data, o);
+}
+
+// ---- tile --------------------------------------------------------------------------------------------------------
+namespace {
+const char *const kCoordNames[9] = {"UNSPECIFIED", "LDB", "RDB", "LUB", "RUB", "LDF", "RDF", "LUF", "RUF"};
+
+// Axis a of the stored RUB frame is negated in `coord` (enum - 1: bit 0 = R, bit 1 = U, bit 2 = F; UNSPECIFIED: none).
+bool axisFlipped(CoordinateSystem coord, int a) {
+  const int c = static_cast<int>(coord) - 1;
+  if (c < 0) return false;
+  return ((c >> a) & 1) != (((static_cast<int>(CoordinateSystem::RUB) - 1) >> a) & 1);
+}
+
+void jsonFloat(std::string *o, float v) {
+  if (std::isnan(v)) {
+    *o += "null";
+    return;
+  }
+  char b[40];
+  std::snprintf(b, sizeof(b), "%.9g", static_cast<double>(v));
+  *o += b;
+}
+
+// A reader for the JSON tileset.json holds: objects, arrays, numbers, strings without escapes, null.
+struct JsonIn {
+  const char *p, *e;
+  bool ok = true;
+  void ws() {
+    while (p < e && (*p == ' ' || *p == '\n' || *p == '\r' || *p == '\t')) ++p;
+  }
+  bool eat(char c) {
+    ws();
+    if (p < e && *p == c) {
+      ++p;
+      return true;
+    }
+    return false;
+  }
+  bool need(char c) {
+    if (!eat(c)) ok = false;
+    return ok;
+  }
+  std::string str() {
+    std::string r;
+    if (!need('"')) return r;
+    while (p < e && *p != '"') r += *p++;
+    need('"');
+    return r;
+  }
+  double num() {   // null: NaN
+    ws();
+    if (e - p >= 4 && std::strncmp(p, "null", 4) == 0) {
+      p += 4;
+      return std::nan("");
+    }
+    char *end = nullptr;
+    const std::string t(p, std::min<size_t>(static_cast<size_t>(e - p), 64));
+    const double v = std::strtod(t.c_str(), &end);
+    if (end == t.c_str()) ok = false;
+    p += end - t.c_str();
+    return v;
+  }
+  template <class F>
+  void array(F each) {
+    if (!need('[')) return;
+    if (eat(']')) return;
+    do each(); while (ok && eat(','));
+    need(']');
+  }
+  template <class F>
+  void object(F field) {   // field(key): reads the value
+    if (!need('{')) return;
+    if (eat('}')) return;
+    do {
+      const std::string k = str();
+      if (!need(':')) return;
+      field(k);
+    } while (ok && eat(','));
+    need('}');
+  }
+};
+}  // namespace
+
+bool saveTileset(const Tileset &t, const std::string &path) {
+  std::string o = "{\"format\": \"spz-tileset\", \"version\": 1, \"coord\": \"";
+  const int c = static_cast<int>(t.coord);
+  o += kCoordNames[c < 0 || c > 8 ? 0 : c];
+  o += "\", \"num_points\": " + std::to_string(t.numPoints) + ", \"sh_degree\": " + std::to_string(t.shDegree) +
+       ", \"fractional_bits\": " + std::to_string(t.fractionalBits) + ", \"max_points\": " + std::to_string(t.maxPoints) +
+       ", \"tiles\": [";
+  for (size_t i = 0; i < t.tiles.size(); ++i) {
+    const Tile &k = t.tiles[i];
+    o += i ? ",\n  {" : "\n  {";
+    o += "\"id\": " + std::to_string(k.id) + ", \"file\": \"" + k.file + "\", \"parent\": " + std::to_string(k.parent) +
+         ", \"children\": [";
+    for (size_t j = 0; j < k.children.size(); ++j) o += (j ? ", " : "") + std::to_string(k.children[j]);
+    o += "], \"level\": " + std::to_string(k.level) + ", \"cell\": [" + std::to_string(k.cell[0]) + ", " +
+         std::to_string(k.cell[1]) + ", " + std::to_string(k.cell[2]) + "], \"content_level\": " +
+         std::to_string(k.contentLevel) + ", \"num_points\": " + std::to_string(k.numPoints) + ", \"geometric_error\": ";
+    jsonFloat(&o, k.geometricError);
+    o += ", \"box\": [[";
+    for (int a = 0; a < 3; ++a) {
+      if (a) o += ", ";
+      jsonFloat(&o, k.boxMin[a]);
+    }
+    o += "], [";
+    for (int a = 0; a < 3; ++a) {
+      if (a) o += ", ";
+      jsonFloat(&o, k.boxMax[a]);
+    }
+    o += "]], \"max_radius\": ";
+    jsonFloat(&o, k.maxRadius);
+    o += "}";
+  }
+  o += "\n]}\n";
+  return writeFile(path, std::vector<uint8_t>(o.begin(), o.end()));
+}
+
+bool loadTileset(const std::string &path, Tileset *out) {
+  const char *who = "loadTileset";
+  g_last_status = SPZ_AMD_OK;
+  if (out == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no tileset to fill");
+  std::vector<uint8_t> data;
+  if (!readFile(path, &data, /*log=*/true)) return false;
+  Tileset t;
+  std::string format;
+  int version = 0;
+  bool coordOk = false;
+  JsonIn in{reinterpret_cast<const char *>(data.data()), reinterpret_cast<const char *>(data.data()) + data.size()};
+  in.object([&](const std::string &k) {
+    if (k == "format") format = in.str();
+    else if (k == "version") version = static_cast<int>(in.num());
+    else if (k == "coord") {
+      const std::string c = in.str();
+      for (int i = 0; i < 9; ++i) {
+        if (c == kCoordNames[i]) {
+          t.coord = static_cast<CoordinateSystem>(i);
+          coordOk = true;
+        }
+      }
+    } else if (k == "num_points") t.numPoints = static_cast<uint64_t>(in.num());
+    else if (k == "sh_degree") t.shDegree = static_cast<int>(in.num());
+    else if (k == "fractional_bits") t.fractionalBits = static_cast<int>(in.num());
+    else if (k == "max_points") t.maxPoints = static_cast<uint32_t>(in.num());
+    else if (k == "tiles") {
+      in.array([&] {
+        Tile tile;
+        in.object([&](const std::string &f) {
+          if (f == "id") tile.id = static_cast<uint32_t>(in.num());
+          else if (f == "file") tile.file = in.str();
+          else if (f == "parent") tile.parent = static_cast<int32_t>(in.num());
+          else if (f == "children") in.array([&] { tile.children.push_back(static_cast<uint32_t>(in.num())); });
+          else if (f == "level") tile.level = static_cast<int32_t>(in.num());
+          else if (f == "cell") {
+            int a = 0;
+            in.array([&] {
+              const double v = in.num();
+              if (a < 3) tile.cell[a++] = static_cast<uint32_t>(v);
+            });
+          } else if (f == "content_level") tile.contentLevel = static_cast<int32_t>(in.num());
+          else if (f == "num_points") tile.numPoints = static_cast<uint32_t>(in.num());
+          else if (f == "geometric_error") tile.geometricError = static_cast<float>(in.num());
+          else if (f == "box") {
+            int row = 0;
+            in.array([&] {
+              int a = 0;
+              in.array([&] {
+                const float v = static_cast<float>(in.num());
+                if (row < 2 && a < 3) (row ? tile.boxMax : tile.boxMin)[a] = v;
+                ++a;
+              });
+              ++row;
+            });
+          } else if (f == "max_radius") tile.maxRadius = static_cast<float>(in.num());
+          else in.ok = false;
+        });
+        t.tiles.push_back(std::move(tile));
+      });
+    } else in.ok = false;
+  });
+  in.ws();
+  bool ok = in.ok && in.p == in.e && format == "spz-tileset" && version == 1 && coordOk && !t.tiles.empty();
+  for (size_t i = 0; ok && i < t.tiles.size(); ++i) {
+    const Tile &k = t.tiles[i];
+    ok = k.id == i && k.parent >= -1 && k.parent < static_cast<int32_t>(i);
+    for (const uint32_t c : k.children) ok = ok && c > i && c < t.tiles.size();
+  }
+  if (!ok) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "%s is not a version 1 spz-tileset", path.c_str());
+  *out = std::move(t);
+  return true;
+}
+
+std::vector<uint32_t> selectTiles(const Tileset &t, const PruneOptions::View &view, double maxPixelError,
+                                  double nearPlane) {
+  std::vector<uint32_t> out;
+  if (t.tiles.empty()) return out;
+  const auto &m = view.worldToCamera;   // eye = -R^T t
+  double eye[3];
+  for (int a = 0; a < 3; ++a) {
+    eye[a] = -(static_cast<double>(m[a]) * m[3] + static_cast<double>(m[4 + a]) * m[7] + static_cast<double>(m[8 + a]) * m[11]);
+  }
+  const double focal = std::max(static_cast<double>(view.fx), static_cast<double>(view.fy));
+  std::vector<uint32_t> stack = {0};
+  while (!stack.empty()) {
+    const uint32_t i = stack.back();
+    stack.pop_back();
+    const Tile &k = t.tiles[i];
+    if (!k.children.empty()) {
+      double d2 = 0.0, diag2 = 0.0;
+      for (int a = 0; a < 3; ++a) {
+        const double lo = k.boxMin[a], hi = k.boxMax[a];
+        const double c = (lo + hi) / 2.0 - eye[a];
+        d2 += c * c;
+        diag2 += (hi - lo) * (hi - lo);
+      }
+      const double radius = std::sqrt(diag2) / 2.0 + static_cast<double>(k.maxRadius);
+      const double d = std::max(std::sqrt(d2) - radius, nearPlane);
+      if (static_cast<double>(k.geometricError) * focal / d > maxPixelError) {
+        for (size_t j = k.children.size(); j-- > 0;) stack.push_back(k.children[j]);
+        continue;
+      }
+    }
+    out.push_back(i);
+  }
+  std::sort(out.begin(), out.end());
+  return out;
+}
+
+bool tileSpz(const std::string &inputFilename, const std::string &outDir, const TileOptions &o, Tileset *tileset) {
+  const char *who = "tileSpz";
+  const int invalid = SPZ_AMD_ERR_INVALID_ARG;
+  g_last_status = SPZ_AMD_OK;
+  if (o.maxPoints < 1 || o.maxPoints > SPZ_AMD_REFERENCE_MAX_POINTS) {
+    return opRejected(who, invalid, "maxPoints %u is outside 1..%u", o.maxPoints, SPZ_AMD_REFERENCE_MAX_POINTS);
+  }
+  if (o.maxTiles < 1 || o.maxTiles > 0x7fffffffu) return opRejected(who, invalid, "maxTiles %u is outside 1..2^31 - 1", o.maxTiles);
+  if (static_cast<int>(o.coord) < 0 || static_cast<int>(o.coord) > 8) return opRejected(who, invalid, "unknown coordinate system %d", static_cast<int>(o.coord));
+  if (outDir.empty()) return opRejected(who, invalid, "no output directory");
+  struct stat sb;
+  const bool exists = ::stat(outDir.c_str(), &sb) == 0;
+  if (exists) {
+    if (!S_ISDIR(sb.st_mode)) return opRejected(who, invalid, "%s is not a directory", outDir.c_str());
+    bool empty = true;
+    if (DIR *dir = ::opendir(outDir.c_str())) {
+      while (const dirent *e = ::readdir(dir)) {
+        if (std::strcmp(e->d_name, ".") != 0 && std::strcmp(e->d_name, "..") != 0) empty = false;
+      }
+      ::closedir(dir);
+    } else {
+      empty = false;
+    }
+    if (!empty) return opRejected(who, invalid, "%s is not empty", outDir.c_str());
+  }
+  Laps laps(who, "SPZ_AMD_TILE_TIMING");
+  std::vector<uint8_t> data;
+  if (!readInput(who, inputFilename, &data)) return false;
+  DevicePackedGaussians d;
+  if (!loadInput(who, data.data(), static_cast<int32_t>(data.size()), &d)) return false;
+  laps.lap("inflate");
+  if (d.version == 1) {
+    return opRejected(who, SPZ_AMD_ERR_UNSUPPORTED,
+                      "a version 1 file has float16 positions and no integer cell; transformSpz with the "
+                      "identity writes a v3 copy");
+  }
+  const spz_amd_header hdr = headerOf(d);
+  void *ctx = nullptr;
+  struct Closer {
+    void **c;
+    ~Closer() { spz_amd_tile_close(*c); }
+  } closer{&ctx};
+  uint64_t count = 0, arenaBytes = 0;
+  float ms[4] = {0, 0, 0, 0};
+  const int rc = spz_amd_tile_open(d.stream, d.streamBytes, &hdr, o.maxPoints, o.maxTiles, d.device, &ctx, &count,
+                                   &arenaBytes, ms);
+  if (rc == SPZ_AMD_ERR_CAPACITY) return opRejected(who, rc, "the tree has more than maxTiles = %u tiles", o.maxTiles);
+  if (deviceFailed(rc, who)) return false;
+  laps.stage("sort", ms[0]);
+  laps.stage("tree", ms[1]);
+  laps.stage("decimate", ms[2]);
+  laps.stage("emit", ms[3]);
+  laps.lap("tile");
+  d.release();
+  std::vector<spz_amd_tile_info> table(static_cast<size_t>(count));
+  std::vector<uint8_t> arena;
+  detail::resizeUninitialized(&arena, static_cast<size_t>(arenaBytes));
+  if (deviceFailed(spz_amd_tile_table(ctx, table.data()), who)) return false;
+  if (deviceFailed(spz_amd_tile_fetch_arena(ctx, arena.data()), who)) return false;
+  spz_amd_tile_close(ctx);
+  ctx = nullptr;
+  laps.lap("download");
+  Tileset t;
+  t.coord = o.coord;
+  t.numPoints = static_cast<uint64_t>(hdr.num_points);
+  t.shDegree = hdr.sh_degree;
+  t.fractionalBits = hdr.fractional_bits;
+  t.maxPoints = o.maxPoints;
+  t.tiles.resize(table.size());
+  for (size_t i = 0; i < table.size(); ++i) {
+    const spz_amd_tile_info &r = table[i];
+    Tile &k = t.tiles[i];
+    char name[32];
+    std::snprintf(name, sizeof(name), "tile_%06u.spz", r.id);
+    k.id = r.id;
+    k.file = name;
+    k.parent = r.parent;
+    if (r.parent >= 0) t.tiles[static_cast<size_t>(r.parent)].children.push_back(r.id);
+    k.level = r.level;
+    k.cell = {r.cell[0], r.cell[1], r.cell[2]};
+    k.contentLevel = r.content_level;
+    k.numPoints = r.num_points;
+    k.geometricError = r.geometric_error;
+    k.maxRadius = r.max_radius;
+    for (int a = 0; a < 3; ++a) {
+      const bool f = axisFlipped(o.coord, a);
+      k.boxMin[a] = f ? -r.box_max[a] : r.box_min[a];
+      k.boxMax[a] = f ? -r.box_min[a] : r.box_max[a];
+    }
+  }
+  // the container stage: thousands of small members must not pay the device writer's floor one after another, so
+  // members under 1 MiB go to zlib on at most 16 threads; the few larger ones take compressGzipped's routes after them
+  constexpr uint64_t kSmall = uint64_t(1) << 20;
+  std::vector<std::vector<uint8_t>> files(table.size());
+  std::atomic<size_t> next{0};
+  std::atomic<bool> failed{false};
+  const unsigned hw = std::thread::hardware_concurrency();
+  size_t most = 16;   // SPZ_AMD_TILE_GZIP_THREADS = 1..16 lowers it (measurements)
+  if (const char *e = std::getenv("SPZ_AMD_TILE_GZIP_THREADS")) {
+    const int v = std::atoi(e);
+    if (v >= 1 && v <= 16) most = static_cast<size_t>(v);
+  }
+  const size_t workers = std::max<size_t>(1, std::min<size_t>({most, hw ? hw : 1, table.size()}));
+  auto work = [&] {
+    for (size_t i = next.fetch_add(1); i < table.size(); i = next.fetch_add(1)) {
+      if (table[i].bytes >= kSmall) continue;
+      if (!compressGzippedZlib(arena.data() + table[i].offset, static_cast<size_t>(table[i].bytes), &files[i])) failed = true;
+    }
+  };
+  std::vector<std::thread> pool;
+  for (size_t w = 1; w < workers; ++w) pool.emplace_back(work);
+  work();
+  for (std::thread &th : pool) th.join();
+  for (size_t i = 0; i < table.size() && !failed; ++i) {
+    if (table[i].bytes < kSmall) continue;
+    if (!compressGzipped(arena.data() + table[i].offset, static_cast<size_t>(table[i].bytes), &files[i])) failed = true;
+  }
+  if (failed) {
+    logLine("[SPZ ERROR] %s: compressGzipped failed", who);
+    return false;
+  }
+  laps.lap("gzip");
+  if (!exists && ::mkdir(outDir.c_str(), 0777) != 0) return opRejected(who, invalid, "unable to create %s", outDir.c_str());
+  for (size_t i = 0; i < table.size(); ++i) {
+    if (!writeOutput(who, outDir + "/" + t.tiles[i].file, files[i])) return false;
+  }
+  if (!saveTileset(t, outDir + "/tileset.json")) {
+    logLine("[SPZ ERROR] %s: unable to write %s/tileset.json", who, outDir.c_str());
+    return false;
+  }
+  laps.lap("write");
+  if (tileset) *tileset = std::move(t);
+  return true;
 }
 
 }  // namespace spz

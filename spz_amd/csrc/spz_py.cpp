@@ -412,6 +412,81 @@ spz::MergeOptions mergeOptions(size_t k, const py::object &transforms, const py:
 
 }  // namespace
 
+namespace {
+py::dict tilesetToDict(const spz::Tileset &t) {
+  py::dict d;
+  d["format"] = "spz-tileset";
+  d["version"] = 1;
+  d["coord"] = t.coord;
+  d["num_points"] = t.numPoints;
+  d["sh_degree"] = t.shDegree;
+  d["fractional_bits"] = t.fractionalBits;
+  d["max_points"] = t.maxPoints;
+  py::list tiles;
+  for (const spz::Tile &k : t.tiles) {
+    py::dict e;
+    e["id"] = k.id;
+    e["file"] = k.file;
+    e["parent"] = k.parent;
+    e["children"] = k.children;
+    e["level"] = k.level;
+    e["cell"] = py::make_tuple(k.cell[0], k.cell[1], k.cell[2]);
+    e["content_level"] = k.contentLevel;
+    e["num_points"] = k.numPoints;
+    e["geometric_error"] = k.geometricError;
+    e["box"] = py::make_tuple(py::make_tuple(k.boxMin[0], k.boxMin[1], k.boxMin[2]),
+                              py::make_tuple(k.boxMax[0], k.boxMax[1], k.boxMax[2]));
+    e["max_radius"] = k.maxRadius;
+    tiles.append(e);
+  }
+  d["tiles"] = tiles;
+  return d;
+}
+
+spz::Tileset tilesetFromDict(const py::dict &d) {
+  spz::Tileset t;
+  try {
+    t.coord = py::cast<spz::CoordinateSystem>(d["coord"]);
+    t.numPoints = py::cast<uint64_t>(d["num_points"]);
+    t.shDegree = py::cast<int>(d["sh_degree"]);
+    t.fractionalBits = py::cast<int>(d["fractional_bits"]);
+    t.maxPoints = py::cast<uint32_t>(d["max_points"]);
+    for (const py::handle &h : py::cast<py::list>(d["tiles"])) {
+      const py::dict e = py::cast<py::dict>(h);
+      spz::Tile k;
+      k.id = py::cast<uint32_t>(e["id"]);
+      k.file = py::cast<std::string>(e["file"]);
+      k.parent = py::cast<int32_t>(e["parent"]);
+      k.children = py::cast<std::vector<uint32_t>>(e["children"]);
+      k.level = py::cast<int32_t>(e["level"]);
+      k.cell = py::cast<std::array<uint32_t, 3>>(e["cell"]);
+      k.contentLevel = py::cast<int32_t>(e["content_level"]);
+      k.numPoints = py::cast<uint32_t>(e["num_points"]);
+      k.geometricError = py::cast<float>(e["geometric_error"]);
+      const auto box = py::cast<std::array<std::array<float, 3>, 2>>(e["box"]);
+      k.boxMin = box[0];
+      k.boxMax = box[1];
+      k.maxRadius = py::cast<float>(e["max_radius"]);
+      if (k.id != t.tiles.size()) throw py::value_error("tile ids must count from 0");
+      for (const uint32_t c : k.children) {
+        if (c <= k.id) throw py::value_error("a child's id must be above its parent's");
+      }
+      t.tiles.push_back(std::move(k));
+    }
+    for (const spz::Tile &k : t.tiles) {
+      for (const uint32_t c : k.children) {
+        if (c >= t.tiles.size()) throw py::value_error("a child id is out of range");
+      }
+    }
+  } catch (const py::cast_error &) {
+    throw py::value_error("not a tileset dict (see load_tileset)");
+  } catch (const py::error_already_set &) {
+    throw py::value_error("not a tileset dict (see load_tileset)");
+  }
+  return t;
+}
+}  // namespace
+
 PYBIND11_MODULE(spz, m) {
   m.doc() = "MI355X-native drop-in for the `spz` Python bindings (Gaussian splat .spz codec).";
 
@@ -756,6 +831,66 @@ PYBIND11_MODULE(spz, m) {
         "quanta, in Morton order; a cell of several points becomes one Gaussian matching their moments.  Exactly one "
         "of level (0..24) and target_points (>= 1: the smallest level with at most that many cells).  Returns (level, "
         "points), plus parents (uint32: the output index of every input point's cell) when return_parents.");
+  m.def("tile_spz",
+        [](const std::string &input, const std::string &out_dir, const py::object &max_points, const py::object &max_tiles,
+           spz::CoordinateSystem coord) -> py::object {
+          auto is_int = [](const py::object &v) { return py::isinstance<py::int_>(v) && !py::isinstance<py::bool_>(v); };
+          if (!is_int(max_points) || py::int_(max_points) < py::int_(1) || py::int_(max_points) > py::int_(10000000)) {
+            throw py::value_error("max_points must be an int in 1..10000000");
+          }
+          if (!is_int(max_tiles) || py::int_(max_tiles) < py::int_(1) || py::int_(max_tiles) > py::int_(2147483647)) {
+            throw py::value_error("max_tiles must be an int in 1..2^31 - 1");
+          }
+          spz::TileOptions o;
+          o.maxPoints = py::cast<uint32_t>(max_points);
+          o.maxTiles = py::cast<uint32_t>(max_tiles);
+          o.coord = coord;
+          spz::Tileset t;
+          bool ok;
+          {
+            py::gil_scoped_release release;
+            ok = spz::tileSpz(input, out_dir, o, &t);
+          }
+          if (!ok) {
+            raiseFailure("tile_spz: refused (see the [SPZ ERROR] line)",
+                         "tile_spz: " + input + " -> " + out_dir + " failed (see the [SPZ ERROR] line)", true);
+          }
+          return tilesetToDict(t);
+        },
+        py::arg("input_filename"), py::arg("out_dir"), py::kw_only(), py::arg("max_points"),
+        py::arg("max_tiles") = 65536, py::arg("coord") = spz::CoordinateSystem::RUB,
+        "Cut a v2/v3 file into an octree of level-of-detail tiles (spz::tileSpz): out_dir/tile_%06u.spz per tile and "
+        "out_dir/tileset.json; out_dir must be absent or empty.  Returns the tileset as load_tileset does.");
+  m.def("load_tileset",
+        [](const std::string &path) -> py::object {
+          spz::Tileset t;
+          if (!spz::loadTileset(path, &t)) throw py::value_error("load_tileset: " + path + " is not a readable tileset.json");
+          return tilesetToDict(t);
+        },
+        py::arg("path"), "A tileset.json as a dict: format fields and `tiles`, a list of dicts (spz::loadTileset).");
+  m.def("save_tileset",
+        [](const py::dict &tileset, const std::string &path) {
+          if (!spz::saveTileset(tilesetFromDict(tileset), path)) throw std::runtime_error("save_tileset: unable to write " + path);
+        },
+        py::arg("tileset"), py::arg("path"), "Write a tileset dict as tileset.json (spz::saveTileset).");
+  m.def("select_tiles",
+        [](const py::dict &tileset, const py::object &world_to_camera, float fx, float fy, double max_pixel_error,
+           double near_plane) -> py::object {
+          const std::vector<float> m = py::cast<std::vector<float>>(
+              py::module_::import("numpy").attr("asarray")(world_to_camera).attr("reshape")(-1).attr("tolist")());
+          if (m.size() != 12) throw py::value_error("world_to_camera must hold 12 values ([R | t] row-major)");
+          if (!(max_pixel_error >= 0.0) || !(near_plane > 0.0) || !(fx > 0.0f) || !(fy > 0.0f)) {
+            throw py::value_error("max_pixel_error must be >= 0, near_plane, fx and fy > 0");
+          }
+          spz::PruneOptions::View v;
+          for (int i = 0; i < 12; ++i) v.worldToCamera[i] = m[i];
+          v.fx = fx;
+          v.fy = fy;
+          return py::cast(spz::selectTiles(tilesetFromDict(tileset), v, max_pixel_error, near_plane));
+        },
+        py::arg("tileset"), py::arg("world_to_camera"), py::arg("fx"), py::arg("fy"), py::arg("max_pixel_error"),
+        py::arg("near_plane") = 0.2,
+        "The screen-space-error cut through a tileset (spz::selectTiles, float64): the tile ids to draw, in tile order.");
   m.def("render_spz",
         [](const py::object &input, const py::object &world_to_camera, int width, int height, float fx, float fy,
            float cx, float cy, float near_plane, const py::object &background, int max_sh_degree,

@@ -527,6 +527,94 @@ def decimate_packed(stream_t, header, level, stream=None):
     return out, hdr, parents
 
 
+def _check_tile_args(stream_t, header, max_points, max_tiles):
+    if isinstance(max_points, bool) or not isinstance(max_points, int) or not 1 <= max_points <= abi.REFERENCE_MAX_POINTS:
+        raise ValueError(f"max_points must be an int in 1..{abi.REFERENCE_MAX_POINTS}, got {max_points!r}")
+    if isinstance(max_tiles, bool) or not isinstance(max_tiles, int) or not 1 <= max_tiles <= 2 ** 31 - 1:
+        raise ValueError(f"max_tiles must be an int in 1..2^31 - 1, got {max_tiles!r}")
+    _check_decimate_stream(stream_t, header)
+    if header.num_points > abi.REFERENCE_MAX_POINTS:
+        raise ValueError(f"{header.num_points} points is above the reader limit {abi.REFERENCE_MAX_POINTS}")
+
+
+def tile_table_numpy(table_t, count):
+    """The first `count` rows of a device tile table as a numpy structured array (abi.TileInfo's fields)."""
+    import numpy as np
+    raw = table_t[:count].cpu().numpy().reshape(-1)
+    return np.frombuffer(raw.tobytes(), dtype=np.dtype(abi.TileInfo), count=count)
+
+
+def _tile_tree_on(L, stream_t, header, max_points, max_tiles, st):
+    """tile_tree's allocations, fills and launches, all on the current stream `st`."""
+    n, dev = header.num_points, stream_t.device
+    rows = min(max_tiles, max(1, 2 * n - 1))
+    table = torch.zeros((rows, C.sizeof(abi.TileInfo)), dtype=torch.uint8, device=dev)
+    summary = torch.zeros(C.sizeof(abi.TileSummary), dtype=torch.uint8, device=dev)
+    ws = torch.empty(int(L.spz_amd_tile_workspace_bytes(n, header.sh_degree, max_tiles)), dtype=torch.uint8, device=dev)
+    rc = L.spz_amd_tile_tree_device(stream_t.data_ptr(), stream_t.numel(), C.byref(header), max_points, max_tiles,
+                                    table.data_ptr(), summary.data_ptr(), ws.data_ptr(), C.c_void_p(st.cuda_stream))
+    abi.check(rc, "spz_amd_tile_tree_device")
+    return table, summary
+
+
+def tile_tree(stream_t, header, max_points, max_tiles=abi.TILE_DEFAULT_MAX_TILES, stream=None):
+    """The octree of LOD tiles of a packed v2/v3 device stream (spz_amd_tile_tree_device; the contract is in
+    include/spz_amd.h, "tile").  Returns (table, summary): a uint8 CUDA tensor of (rows, 104) tile rows and one of
+    sizeof(abi.TileSummary) bytes.  Nothing is read back: the tile count is in the summary (tile_summary reads it), and
+    the rows are written only when it is at most max_tiles.  Interior boxes are NaN until tile_packed fills them.
+    Every allocation, fill and launch is enqueued on `stream` (after the current stream's work), or the current one."""
+    L = abi.load_library()
+    _check_tile_args(stream_t, header, max_points, max_tiles)
+    dev = stream_t.device
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        with torch.cuda.stream(st):
+            return _tile_tree_on(L, stream_t, header, max_points, max_tiles, st)
+
+
+def tile_summary(summary_t):
+    """The summary of tile_tree on the host (an abi.TileSummary; one small read-back on the current stream)."""
+    return abi.TileSummary.from_buffer_copy(summary_t.cpu().numpy().tobytes())
+
+
+def tile_packed(stream_t, header, max_points, max_tiles=abi.TILE_DEFAULT_MAX_TILES, stream=None):
+    """The tileset of a packed v2/v3 device stream, all in device memory: tile_tree, one read-back of the summary and
+    the table, then per distinct content level one decimate_packed and one spz_amd_tile_content_device (bounds + the
+    batched emit), then the leaves' from the sorted stream.  Returns (table: numpy structured array of the finished
+    rows, tiles: a list of uint8 CUDA tensors, views of `arena`, one stream per tile in id order, arena).  More than
+    max_tiles tiles raises abi.SpzAmdError(SPZ_AMD_ERR_CAPACITY) before any content is produced.  Everything is
+    enqueued on `stream` (after the current stream's work), or the current one; the call waits for it."""
+    L = abi.load_library()
+    _check_tile_args(stream_t, header, max_points, max_tiles)
+    dev = stream_t.device
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        with torch.cuda.stream(st):
+            table_t, summary_t = _tile_tree_on(L, stream_t, header, max_points, max_tiles, st)
+            s = tile_summary(summary_t)
+            if not s.ok:
+                raise abi.SpzAmdError(abi.ERR_CAPACITY, f"tile_packed: {s.num_tiles} tiles, max_tiles {max_tiles}")
+            count = int(s.num_tiles)
+            rows = tile_table_numpy(table_t, count)
+            arena = torch.zeros(int(s.arena_bytes), dtype=torch.uint8, device=dev)
+            ws = torch.empty(int(L.spz_amd_tile_content_workspace_bytes(count)), dtype=torch.uint8, device=dev)
+            for level in sorted(set(int(l) for l in rows["content_level"])):
+                if level >= 0:
+                    source = decimate_packed(stream_t, header, level)[0]
+                elif header.num_points:
+                    source = subset(stream_t, header, morton_order(stream_t, header))
+                else:
+                    source = stream_t
+                rc = L.spz_amd_tile_content_device(table_t.data_ptr(), count, level, source.data_ptr(), source.numel(),
+                                                   arena.data_ptr(), arena.numel(), ws.data_ptr(),
+                                                   C.c_void_p(st.cuda_stream))
+                abi.check(rc, "spz_amd_tile_content_device")
+            rows = tile_table_numpy(table_t, count)   # a blocking copy on st: everything above is done
+            st.synchronize()
+    tiles = [arena[int(r["offset"]):int(r["offset"]) + int(r["bytes"])] for r in rows]
+    return rows, tiles, arena
+
+
 def _check_clean_stream(stream_t, header):
     _check_stream_tensor(stream_t)
     if header.version == 1:
