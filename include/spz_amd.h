@@ -572,6 +572,113 @@ int spz_amd_clean_fetch(void *ctx, uint8_t *h_out);
 const uint8_t *spz_amd_clean_device_data(void *ctx);
 void spz_amd_clean_close(void *ctx);
 
+/* ---- align: the similarity that places a source stream on a target stream, by a point-to-point, trimmed ICP with an
+ *      optional scale (spz_align.hip; DESIGN §8 "Align").  The reference has no counterpart.  The convention of Open3D's
+ *      registration_icp(TransformationEstimationPointToPoint(with_scaling)) with the trimming of Chetverikov's TrICP.
+ *      Source S (n_s points, fractionalBits f_s) and target T (n_t >= 1 points, f_t; n_t == 0: SPZ_AMD_ERR_INVALID_ARG),
+ *      both v2 or v3 (version 1, float16 positions: SPZ_AMD_ERR_UNSUPPORTED, as for sort and clean), both at most
+ *      SPZ_AMD_REFERENCE_MAX_POINTS (SPZ_AMD_ERR_TOO_MANY_POINTS).  All geometry is in the stored RUB frame; align_host
+ *      conjugates the options' placement into it and the result out of it with the axis flips of
+ *      spz_amd_transform_params (R = F R_c F, t = F t_c), in f64.
+ *
+ *      One step for a map (map[0..9) = M = s R row-major, map[9..12) = t, f64):
+ *      1. x_i = P_i 2^-f_s, P_i the sign-extended stored integers (exact).  Only i with i % stride == 0 take part.
+ *      2. y_a = ((M_a0 x + M_a1 y) + M_a2 z) + t_a in f64, every product and sum rounded on its own (no fused
+ *         multiply-add).  Query Q_i = rint(y_i 2^f_t) (ties to even), each component saturated to [-2^26, 2^26]; a
+ *         non-finite y_i makes i invalid.
+ *      3. j(i) = the target point with the smallest d2(i, j) = sum_a (Q_ia - P^T_ja)^2, an exact integer below 2^56
+ *         (uint64); ties go to the smallest target input index.
+ *      4. With a limit R2 (spz_amd_clean_radius_r2(max_distance, f_t); UINT64_MAX: none) i is a candidate iff
+ *         d2 <= R2; without one every valid i is.  With overlap f in (0, 1], K = min(c, ceil(f c)) in f64 over the c
+ *         candidates, and the inliers are the K candidates smallest by (d2, source index): an exact rank on integer
+ *         keys (a stable radix sort).
+ *      5. Moments over the inliers, a = x_i, b = P^T_j(i) 2^-f_t, in f64: sum a, sum b, sum a b^T (sum_ab[3 r + c] =
+ *         sum a_r b_c), sum |a|^2, sum |b|^2 (|v|^2 = (x x + y y) + z z), and as integers the count K and sum d2
+ *         (sum_d2_hi 2^64 + sum_d2_lo).  No float atomics: per tile of 2048 source points a pairwise sum in a fixed
+ *         tree, then one workgroup over the tiles, so the order depends on n_s alone and a run repeats its bits; every
+ *         f64 sum is within (ceil(log2 n_s) + 2) 2^-53 sum |term| of the exact one.
+ *      6. align_solve (host only, no GPU, f64; a 3x3 one-sided Jacobi SVD): ma = sum a / K, mb = sum b / K,
+ *         H = sum_ab^T / K - mb ma^T = U D V^T, S = diag(1, 1, sign(det U det V)), R = U S V^T, s = tr(D S) / var_a
+ *         (var_a = sum |a|^2 / K - |ma|^2) when estimate_scale, else scale_in; t = mb - s R ma.  *degenerate = 1 (and
+ *         map_out untouched) when K < 3, var_a is not > 0 or D_1 <= 1e-12 D_0 (a line or a point: no rotation).
+ *      fitness = K / (number of source points taking part); inlier_rmse = sqrt(sum d2 / K) 2^-f_t (0 for K == 0).
+ *
+ *      The run (align_host; blocking, on `device`, on a stream of its own; both streams already in device memory): from
+ *      the options' rotation (x, y, z, w; any nonzero finite length), translation and scale, stated in coord (with
+ *      init_centroids the translation is first replaced so that the centroid of the taking-part source points lands on
+ *      the target's centroid), step and solve until max_iterations steps ran or, after a step, both |fitness -
+ *      previous| <= relative_fitness max(fitness, previous) and |rmse - previous| <= relative_rmse max(rmse, previous)
+ *      (converged = 1).  A degenerate solve ends the run (degenerate = 1, converged = 0).  The result is the map USED BY
+ *      THE LAST STEP with that step's fitness, rmse and inlier count: map in the stored frame; rotation (unit, w >= 0),
+ *      translation and scale stated in coord, ready for spz_amd_transform_params.  history (may be NULL): one entry per
+ *      step, up to capacity.  h_ms (may be NULL): [0] wall-clock milliseconds of the preparation, [1] of the queries,
+ *      [2] of the selections, moments and solves.  The two clouds are put in Morton order once per run.
+ *      align_check (host only, no GPU): stride >= 1; overlap in (0, 1]; max_distance (when has_max_distance) finite and
+ *      > 0; max_iterations 1..1000; tolerances finite and >= 0; rotation of nonzero finite length, translation finite,
+ *      scale finite and > 0; coord 0..8.  A bad one is SPZ_AMD_ERR_INVALID_ARG before anything is launched.
+ *      align_default_options: identity, overlap 1, no max_distance, stride 1, 30 iterations, tolerances 1e-6.
+ *
+ *      Device forms (enqueue on hip_stream, no synchronisation; d_workspace: align_workspace_bytes(n_s, n_t) bytes of
+ *      device memory, any alignment, the same for every call on one pair).  align_prepare_device: the Morton order and
+ *      the sorted positions of both clouds.  nearest_device: steps 1-3 for a prepared pair, results in source input
+ *      order (d_index: n_s uint32, d_d2: n_s uint64); 0xFFFFFFFF / UINT64_MAX for points not taking part, invalid, or
+ *      without a neighbour within r2.  align_step_device: steps 1-5 (d_index, d_d2 and d_inlier, n_s bytes, may be
+ *      NULL: kept in the workspace) into *d_out (device memory). */
+typedef struct {
+  const uint8_t *d_stream;       /* device memory: header + sections */
+  size_t size;
+  spz_amd_header hdr;
+} spz_amd_align_cloud;
+typedef struct {
+  double rotation[4];            /* (x, y, z, w), in coord */
+  double translation[3];
+  double scale;
+  int32_t coord;
+  int32_t estimate_scale;
+  double overlap;
+  double max_distance;           /* world units; read when has_max_distance */
+  int32_t has_max_distance;
+  uint32_t stride;
+  uint32_t max_iterations;
+  int32_t init_centroids;
+  double relative_fitness, relative_rmse;
+} spz_amd_align_options;
+typedef struct {
+  uint64_t count;                /* K */
+  uint64_t taking_part;
+  uint64_t candidates;           /* c */
+  uint64_t sum_d2_lo, sum_d2_hi;
+  double sum_a[3], sum_b[3], sum_ab[9], sum_aa, sum_bb;
+} spz_amd_align_moments;
+typedef struct {
+  double fitness, inlier_rmse;
+  uint64_t inliers;
+} spz_amd_align_history;
+typedef struct {
+  double rotation[4], translation[3], scale;   /* in coord */
+  double map[12];                               /* stored frame */
+  double fitness, inlier_rmse;
+  uint64_t inliers;
+  uint32_t iterations;
+  int32_t converged, degenerate;
+} spz_amd_align_result;
+int spz_amd_align_default_options(spz_amd_align_options *options);
+int spz_amd_align_check(const spz_amd_align_options *options);
+uint64_t spz_amd_align_workspace_bytes(uint64_t num_source, uint64_t num_target);
+int spz_amd_align_prepare_device(const spz_amd_align_cloud *source, const spz_amd_align_cloud *target, void *d_workspace,
+                                 void *hip_stream);
+int spz_amd_nearest_device(const spz_amd_align_cloud *source, const spz_amd_align_cloud *target, uint32_t stride,
+                           const double map[12], uint64_t r2, uint32_t *d_index, uint64_t *d_d2, void *d_workspace,
+                           void *hip_stream);
+int spz_amd_align_step_device(const spz_amd_align_cloud *source, const spz_amd_align_cloud *target, uint32_t stride,
+                              const double map[12], uint64_t r2, double overlap, uint32_t *d_index, uint64_t *d_d2,
+                              uint8_t *d_inlier, spz_amd_align_moments *d_out, void *d_workspace, void *hip_stream);
+int spz_amd_align_solve(const spz_amd_align_moments *moments, int estimate_scale, double scale_in, double map_out[12],
+                        double *scale_out, int *degenerate);
+int spz_amd_align_host(const spz_amd_align_cloud *source, const spz_amd_align_cloud *target,
+                       const spz_amd_align_options *options, int device, spz_amd_align_result *result,
+                       spz_amd_align_history *history, uint32_t capacity, float *h_ms);
+
 /* ---- render: a forward 3D Gaussian splat rasteriser (spz_render.hip; DESIGN §8 "Render").  The reference has no
  *      counterpart.  The image of one pinhole view, computed on the device with no display attached.
  *

@@ -394,6 +394,46 @@ bool cleanSpz(const uint8_t *data, int32_t size, const CleanOptions &options, st
 bool cleanSpz(const std::string &inputFilename, const std::string &outputFilename, const CleanOptions &options,
               int64_t *kept = nullptr, std::vector<uint8_t> *keepMask = nullptr, std::vector<double> *scores = nullptr,
               double *threshold = nullptr);
+// Align (DESIGN §8 "Align"): the similarity that places a source .spz on a target .spz, by a point-to-point, trimmed ICP
+// with an optional scale on the stored integers of both files (include/spz_amd.h "align" states the contract).  Both
+// members are inflated (loadSpzPackedDevice) and the run happens on the device (spz_amd_align_host).  rotation,
+// translation and scale are the initial placement, stated in `coord`; the result's are stated in `coord` too, ready for
+// TransformOptions or a merge placement.  Version 1 files are refused (SPZ_AMD_ERR_UNSUPPORTED), and so is a target
+// without points.  A run that ends degenerate (fewer than three inliers, or source points on one line) returns true with
+// degenerate set and converged false.  false + one "[SPZ ERROR] alignSpz: …" line on a bad argument (lastDeviceStatus()
+// = SPZ_AMD_ERR_INVALID_ARG), an input that does not load, or a device failure.  SPZ_AMD_ALIGN_TIMING=1 prints the
+// stages' times to stderr.
+struct AlignOptions {
+  std::array<double, 4> rotation = {0.0, 0.0, 0.0, 1.0};
+  std::array<double, 3> translation = {0.0, 0.0, 0.0};
+  double scale = 1.0;
+  CoordinateSystem coord = CoordinateSystem::UNSPECIFIED;
+  bool estimateScale = false;
+  double overlap = 1.0;                 // (0, 1]: the fraction of the candidates kept, nearest first
+  std::optional<double> maxDistance;    // world units
+  uint32_t stride = 1;                  // source points i with i % stride == 0 take part
+  uint32_t maxIterations = 30;          // 1 ... 1000
+  double relativeFitness = 1e-6, relativeRmse = 1e-6;
+  bool initCentroids = false;
+};
+struct AlignResult {
+  std::array<double, 4> rotation = {0.0, 0.0, 0.0, 1.0};
+  std::array<double, 3> translation = {0.0, 0.0, 0.0};
+  double scale = 1.0;
+  double fitness = 0.0, inlierRmse = 0.0;
+  uint64_t inliers = 0;
+  uint32_t iterations = 0;
+  bool converged = false, degenerate = false;
+  struct Step {
+    double fitness, inlierRmse;
+    uint64_t inliers;
+  };
+  std::vector<Step> history;
+};
+bool alignSpz(const uint8_t *source, int32_t sourceSize, const uint8_t *target, int32_t targetSize,
+              const AlignOptions &options, AlignResult *result);
+bool alignSpz(const std::string &sourceFilename, const std::string &targetFilename, const AlignOptions &options,
+              AlignResult *result);
 // Render (DESIGN §8 "Render"): the image of one pinhole view on the device (include/spz_amd.h "render" states the
 // contract).  worldToCamera: [R | t] row-major, OpenCV axes (x right, y down, z forward), in the `coord` frame: the file
 // is rendered as loadSpz(to = coord) returns it (renderCloud: the cloud as it is; coord is ignored).  *rgba: height x

@@ -77,6 +77,9 @@ EXPORTS = (
     "spz_amd_clean_workspace_bytes", "spz_amd_clean_radius_r2", "spz_amd_knn_scores_device",
     "spz_amd_radius_counts_device", "spz_amd_clean_open", "spz_amd_clean_fetch", "spz_amd_clean_device_data",
     "spz_amd_clean_close",
+    "spz_amd_align_default_options", "spz_amd_align_check", "spz_amd_align_workspace_bytes",
+    "spz_amd_align_prepare_device", "spz_amd_nearest_device", "spz_amd_align_step_device", "spz_amd_align_solve",
+    "spz_amd_align_host",
     "spz_amd_render_check_params", "spz_amd_render_workspace_bytes", "spz_amd_render_prepare_packed_device",
     "spz_amd_render_prepare_cloud_device", "spz_amd_render_finish_device", "spz_amd_render_host",
     "spz_amd_render_cloud_host", "spz_amd_render_score_device", "spz_amd_prune_keep_count", "spz_amd_prune_open",
@@ -123,6 +126,44 @@ PRUNE_MAX_VIEWS = 1024
 PRUNE_SCORE_SUM, PRUNE_SCORE_MAX = 0, 1
 PRUNE_KEEP_COUNT, PRUNE_KEEP_FRACTION, PRUNE_MIN_SCORE = 0, 1, 2
 COMPARE_MAX_VIEWS = 1024
+
+
+class AlignCloud(C.Structure):
+    """spz_amd_align_cloud: one cloud of an alignment (device stream, its size and header)."""
+    _fields_ = [("d_stream", C.c_void_p), ("size", C.c_size_t), ("hdr", Header)]
+
+
+class AlignOptions(C.Structure):
+    """spz_amd_align_options (include/spz_amd.h "align"); spz_amd_align_default_options fills the defaults."""
+    _fields_ = [("rotation", C.c_double * 4), ("translation", C.c_double * 3), ("scale", C.c_double),
+                ("coord", C.c_int32), ("estimate_scale", C.c_int32), ("overlap", C.c_double),
+                ("max_distance", C.c_double), ("has_max_distance", C.c_int32), ("stride", C.c_uint32),
+                ("max_iterations", C.c_uint32), ("init_centroids", C.c_int32), ("relative_fitness", C.c_double),
+                ("relative_rmse", C.c_double)]
+
+
+class AlignMoments(C.Structure):
+    """spz_amd_align_moments: the sums of one step over its inliers (sum d2 = sum_d2_hi 2^64 + sum_d2_lo)."""
+    _fields_ = [("count", C.c_uint64), ("taking_part", C.c_uint64), ("candidates", C.c_uint64),
+                ("sum_d2_lo", C.c_uint64), ("sum_d2_hi", C.c_uint64), ("sum_a", C.c_double * 3),
+                ("sum_b", C.c_double * 3), ("sum_ab", C.c_double * 9), ("sum_aa", C.c_double), ("sum_bb", C.c_double)]
+
+
+class AlignHistory(C.Structure):
+    _fields_ = [("fitness", C.c_double), ("inlier_rmse", C.c_double), ("inliers", C.c_uint64)]
+
+
+class AlignResult(C.Structure):
+    """spz_amd_align_result: the map used by the last step (rotation, translation, scale in coord; map in the stored
+    frame) with that step's fitness, rmse and inlier count."""
+    _fields_ = [("rotation", C.c_double * 4), ("translation", C.c_double * 3), ("scale", C.c_double),
+                ("map", C.c_double * 12), ("fitness", C.c_double), ("inlier_rmse", C.c_double),
+                ("inliers", C.c_uint64), ("iterations", C.c_uint32), ("converged", C.c_int32),
+                ("degenerate", C.c_int32)]
+
+
+NO_NEIGHBOUR = 0xFFFFFFFF      # spz_amd_nearest_device's index of a point without one
+NO_LIMIT_R2 = (1 << 64) - 1    # its r2 for "no distance limit"
 
 
 class ImageMetrics(C.Structure):
@@ -459,6 +500,25 @@ def bind(L):
     L.spz_amd_clean_device_data.argtypes = [vp]
     L.spz_amd_clean_close.restype = None
     L.spz_amd_clean_close.argtypes = [vp]
+    ac = C.POINTER(AlignCloud)
+    L.spz_amd_align_default_options.restype = i32
+    L.spz_amd_align_default_options.argtypes = [C.POINTER(AlignOptions)]
+    L.spz_amd_align_check.restype = i32
+    L.spz_amd_align_check.argtypes = [C.POINTER(AlignOptions)]
+    L.spz_amd_align_workspace_bytes.restype = u64
+    L.spz_amd_align_workspace_bytes.argtypes = [u64, u64]
+    L.spz_amd_align_prepare_device.restype = i32
+    L.spz_amd_align_prepare_device.argtypes = [ac, ac, vp, vp]
+    L.spz_amd_nearest_device.restype = i32
+    L.spz_amd_nearest_device.argtypes = [ac, ac, u32, C.POINTER(C.c_double), u64, vp, vp, vp, vp]
+    L.spz_amd_align_step_device.restype = i32
+    L.spz_amd_align_step_device.argtypes = [ac, ac, u32, C.POINTER(C.c_double), u64, C.c_double, vp, vp, vp, vp, vp, vp]
+    L.spz_amd_align_solve.restype = i32
+    L.spz_amd_align_solve.argtypes = [C.POINTER(AlignMoments), i32, C.c_double, C.POINTER(C.c_double),
+                                      C.POINTER(C.c_double), C.POINTER(i32)]
+    L.spz_amd_align_host.restype = i32
+    L.spz_amd_align_host.argtypes = [ac, ac, C.POINTER(AlignOptions), i32, C.POINTER(AlignResult),
+                                     C.POINTER(AlignHistory), u32, C.POINTER(C.c_float)]
     L.spz_amd_render_check_params.restype = i32
     L.spz_amd_render_check_params.argtypes = [C.POINTER(RenderParams)]
     L.spz_amd_render_workspace_bytes.restype = u64

@@ -1,9 +1,12 @@
 // spz_cli.cpp — the three command-line tools of the reference (cli_tools/src/*.cpp) over the
 // MI355X drop-in layer: ply_to_spz, spz_to_ply, spz_info; and spz_filter (spz::filterSpz),
 // spz_transform (spz::transformSpz), spz_merge (spz::mergeSpz), spz_sort (spz::sortSpz), spz_decimate
-// (spz::decimateSpz), spz_tile (spz::tileSpz), spz_clean (spz::cleanSpz), spz_render (spz::renderSpz), spz_prune (spz::pruneSpz) and spz_compare
-// (spz::compareSpz), which have no counterpart in the reference.  One binary, dispatched on argv[0] (the Makefile
-// installs it under the thirteen names) or on a first argument naming the tool.
+// (spz::decimateSpz), spz_tile (spz::tileSpz), spz_clean (spz::cleanSpz), spz_render (spz::renderSpz), spz_prune
+// (spz::pruneSpz), spz_compare (spz::compareSpz) and spz_align (spz::alignSpz), which have no counterpart in the
+// reference.  One binary, dispatched on argv[0] (the Makefile installs it under the fourteen names) or on a first
+// argument naming the tool.
+// spz_align exits 0 on success, 1 on a failure and 2 when the run ends degenerate; its --output is written by
+// transformSpz, at --fractional-bits (12 unless given, as for spz_transform).
 // spz_compare exits 0 on success, 1 on a failure and 2 when a view misses --min-psnr or --min-ssim.
 // Same behaviour as the reference mains: default (UNSPECIFIED) pack/unpack options, exit code 0
 // once the arguments are there (the reference ignores the save/load results), usage -> 1.
@@ -592,6 +595,59 @@ int spzCompare(int argc, char **argv) {
   return missed ? 2 : 0;
 }
 
+const char *kAlignUsage =
+    "Usage: spz_align <source.spz> <target.spz> [--output aligned.spz] [--scale] [--overlap F] [--max-distance D] "
+    "[--stride K] [--iterations N] [--init-centroids] [--rotate x y z w] [--translate x y z] [--init-scale S] "
+    "[--coord " SPZ_COORD_NAMES "] [--fractional-bits n]";
+
+// Prints the placement in spz_transform's own spelling, then fitness, rmse and iterations; exit 2 when the run ends
+// degenerate.
+int spzAlign(int argc, char **argv) {
+  Args a(argc, argv, kAlignUsage);
+  if (!a.files()) return a.usage();
+  spz::AlignOptions o;
+  std::string output;
+  int32_t fractionalBits = 12;
+  while (a.next()) {
+    bool good = false;
+    if (a.is("--output")) good = a.text(&output);
+    else if (a.is("--scale")) good = o.estimateScale = true;
+    else if (a.is("--overlap")) good = a.real(&o.overlap);
+    else if (a.is("--max-distance")) good = a.real(&o.maxDistance.emplace());
+    else if (a.is("--stride")) good = a.integer(&o.stride, 1, UINT32_MAX);
+    else if (a.is("--iterations")) good = a.integer(&o.maxIterations, 1, 1000);
+    else if (a.is("--init-centroids")) good = o.initCentroids = true;
+    else if (a.is("--rotate")) good = a.real(o.rotation.data(), 4);
+    else if (a.is("--translate")) good = a.real(o.translation.data(), 3);
+    else if (a.is("--init-scale")) good = a.real(&o.scale);
+    else if (a.is("--coord")) good = a.coord(&o.coord);
+    else if (a.is("--fractional-bits")) good = a.integer(&fractionalBits, 0, 24);
+    if (!good) return a.usage();
+  }
+  spz::AlignResult r;
+  if (!spz::alignSpz(std::string(argv[1]), std::string(argv[2]), o, &r)) return 1;
+  std::printf("--rotate %.17g %.17g %.17g %.17g --translate %.17g %.17g %.17g --scale %.17g --coord %s\n", r.rotation[0],
+              r.rotation[1], r.rotation[2], r.rotation[3], r.translation[0], r.translation[1], r.translation[2], r.scale,
+              kCoordNames[static_cast<int>(o.coord)]);
+  std::printf("fitness %.17g rmse %.17g inliers %llu iterations %u converged %d\n", r.fitness, r.inlierRmse,
+              static_cast<unsigned long long>(r.inliers), r.iterations, r.converged ? 1 : 0);
+  std::fflush(stdout);
+  if (r.degenerate) {
+    std::cerr << "spz_align: the correspondences do not determine a rotation (fewer than three, or on one line)" << std::endl;
+    return 2;
+  }
+  if (!output.empty()) {
+    spz::TransformOptions t;
+    t.rotation = r.rotation;
+    t.translation = r.translation;
+    t.scale = r.scale;
+    t.coord = o.coord;
+    t.fractionalBits = fractionalBits;
+    if (!spz::transformSpz(std::string(argv[1]), output, t)) return 1;
+  }
+  return 0;
+}
+
 const struct {
   const char *name;
   int (*run)(int, char **);
@@ -599,7 +655,7 @@ const struct {
               {"spz_filter", spzFilter},    {"spz_transform", spzTransform},  {"spz_merge", spzMerge},
               {"spz_sort", spzSort},        {"spz_decimate", spzDecimate},    {"spz_clean", spzClean},
               {"spz_render", spzRender},    {"spz_prune", spzPrune},          {"spz_compare", spzCompare},
-              {"spz_tile", spzTile}};
+              {"spz_tile", spzTile},        {"spz_align", spzAlign}};
 
 int dispatch(const std::string &tool, int argc, char **argv) {
   for (const auto &t : kTools) {

@@ -2822,6 +2822,85 @@ bool compareSpz(const std::string &fileA, const std::string &fileB, const Compar
                     ssimMaps);
 }
 
+// ---- align -------------------------------------------------------------------------------------------------------
+namespace {
+bool alignOptionsOk(const AlignOptions &o, spz_amd_align_options *c) {
+  spz_amd_align_default_options(c);
+  for (int k = 0; k < 4; ++k) c->rotation[k] = o.rotation[k];
+  for (int k = 0; k < 3; ++k) c->translation[k] = o.translation[k];
+  c->scale = o.scale;
+  c->coord = static_cast<int32_t>(o.coord);
+  c->estimate_scale = o.estimateScale ? 1 : 0;
+  c->overlap = o.overlap;
+  c->has_max_distance = o.maxDistance ? 1 : 0;
+  c->max_distance = o.maxDistance ? *o.maxDistance : 0.0;
+  c->stride = o.stride;
+  c->max_iterations = o.maxIterations;
+  c->init_centroids = o.initCentroids ? 1 : 0;
+  c->relative_fitness = o.relativeFitness;
+  c->relative_rmse = o.relativeRmse;
+  if (spz_amd_align_check(c) == SPZ_AMD_OK) return true;
+  return opRejected("alignSpz", SPZ_AMD_ERR_INVALID_ARG,
+                    "bad options: stride >= 1, overlap in (0, 1], maxDistance > 0, maxIterations 1..1000, tolerances "
+                    ">= 0, a nonzero rotation, scale > 0, coord valid, all finite");
+}
+}  // namespace
+
+bool alignSpz(const uint8_t *source, int32_t sourceSize, const uint8_t *target, int32_t targetSize,
+              const AlignOptions &o, AlignResult *result) {
+  const char *who = "alignSpz";
+  g_last_status = SPZ_AMD_OK;
+  if (result == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no result");
+  *result = AlignResult{};
+  spz_amd_align_options c;
+  if (!alignOptionsOk(o, &c)) return false;
+  Laps laps(who, "SPZ_AMD_ALIGN_TIMING");
+  DevicePackedGaussians ds, dt;
+  if (!loadInput(who, source, sourceSize, &ds) || !loadInput(who, target, targetSize, &dt)) return false;
+  laps.lap("inflate");
+  if (ds.device != dt.device) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "the inputs were loaded on different devices");
+  const spz_amd_align_cloud cs = {ds.stream, ds.streamBytes, headerOf(ds)}, ct = {dt.stream, dt.streamBytes, headerOf(dt)};
+  if (cs.hdr.version == 1 || ct.hdr.version == 1) {
+    return opRejected(who, SPZ_AMD_ERR_UNSUPPORTED, "a version 1 file has float16 positions (transformSpz with the identity writes a v3 copy)");
+  }
+  if (ct.hdr.num_points == 0) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "the target has no points");
+  spz_amd_align_result r;
+  std::vector<spz_amd_align_history> hist(c.max_iterations);
+  float ms[3] = {0.0f, 0.0f, 0.0f};
+  const int rc = spz_amd_align_host(&cs, &ct, &c, ds.device, &r, hist.data(), c.max_iterations, ms);
+  if (deviceFailed(rc, who)) return false;
+  laps.stage("prepare", ms[0]);
+  laps.stage("query", ms[1], (" (" + std::to_string(r.iterations) + " steps)").c_str());
+  laps.stage("solve", ms[2]);
+  laps.lap("align");
+  for (int k = 0; k < 4; ++k) result->rotation[k] = r.rotation[k];
+  for (int k = 0; k < 3; ++k) result->translation[k] = r.translation[k];
+  result->scale = r.scale;
+  result->fitness = r.fitness;
+  result->inlierRmse = r.inlier_rmse;
+  result->inliers = r.inliers;
+  result->iterations = r.iterations;
+  result->converged = r.converged != 0;
+  result->degenerate = r.degenerate != 0;
+  for (uint32_t k = 0; k < r.iterations; ++k) {
+    result->history.push_back({hist[k].fitness, hist[k].inlier_rmse, hist[k].inliers});
+  }
+  return true;
+}
+
+bool alignSpz(const std::string &sourceFilename, const std::string &targetFilename, const AlignOptions &o,
+              AlignResult *result) {
+  const char *who = "alignSpz";
+  g_last_status = SPZ_AMD_OK;
+  if (result == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no result");
+  *result = AlignResult{};
+  spz_amd_align_options c;
+  if (!alignOptionsOk(o, &c)) return false;
+  std::vector<uint8_t> a, b;
+  if (!readInput(who, sourceFilename, &a) || !readInput(who, targetFilename, &b)) return false;
+  return alignSpz(a.data(), static_cast<int32_t>(a.size()), b.data(), static_cast<int32_t>(b.size()), o, result);
+}
+
 bool compareImages(const float *a, int channelsA, const float *b, int channelsB, int width, int height,
                    ImageMetrics *metrics, std::vector<float> *ssimMap) {
   const char *who = "compareImages";

@@ -1098,6 +1098,95 @@ PYBIND11_MODULE(spz, m) {
         py::arg("filename"),
         "The views of a plain-text views file (spz_prune --views; spz::loadViewsFile) as prune_spz's view dicts: one "
         "view per line, 'width height fx fy cx cy r00 r01 r02 t0 r10 r11 r12 t1 r20 r21 r22 t2', '#' starts a comment.");
+  m.def("align_spz",
+        [](const py::object &source, const py::object &target, const py::object &rotation, const py::object &translation,
+           double scale, spz::CoordinateSystem coord, bool estimate_scale, double overlap, const py::object &max_distance,
+           const py::object &stride, const py::object &max_iterations, double relative_fitness, double relative_rmse,
+           bool init_centroids) {
+          // the arguments first: every problem is a ValueError before any device work
+          spz::AlignOptions o;
+          if (!rotation.is_none()) {
+            py::array_t<double, py::array::c_style | py::array::forcecast> q(rotation);
+            if (q.size() != 4) throw py::value_error("rotation must be (x, y, z, w)");
+            for (int k = 0; k < 4; ++k) o.rotation[k] = q.data()[k];
+          }
+          if (!translation.is_none()) {
+            py::array_t<double, py::array::c_style | py::array::forcecast> t(translation);
+            if (t.size() != 3) throw py::value_error("translation must be (x, y, z)");
+            for (int k = 0; k < 3; ++k) o.translation[k] = t.data()[k];
+          }
+          auto count = [](const py::object &v, const char *name, long long hi) {
+            if (py::isinstance<py::bool_>(v) || !py::isinstance<py::int_>(v)) {
+              throw py::value_error(std::string(name) + " must be an int");
+            }
+            const long long x = v.cast<long long>();
+            if (x < 1 || x > hi) throw py::value_error(std::string(name) + " must be in 1.." + std::to_string(hi));
+            return static_cast<uint32_t>(x);
+          };
+          o.stride = count(stride, "stride", 0xffffffffll);
+          o.maxIterations = count(max_iterations, "max_iterations", 1000);
+          o.scale = scale;
+          o.coord = coord;
+          o.estimateScale = estimate_scale;
+          o.overlap = overlap;
+          if (!max_distance.is_none()) o.maxDistance = max_distance.cast<double>();
+          o.relativeFitness = relative_fitness;
+          o.relativeRmse = relative_rmse;
+          o.initCentroids = init_centroids;
+          if (!(overlap > 0.0) || !(overlap <= 1.0)) throw py::value_error("overlap must be in (0, 1]");
+          if (o.maxDistance && (!std::isfinite(*o.maxDistance) || !(*o.maxDistance > 0.0))) {
+            throw py::value_error("max_distance must be None or a finite number > 0");
+          }
+          if (!std::isfinite(scale) || !(scale > 0.0)) throw py::value_error("scale must be a finite number > 0");
+          if (py::isinstance<py::bytes>(source) != py::isinstance<py::bytes>(target)) {
+            throw py::value_error("give source and target both as paths or both as bytes");
+          }
+          spz::AlignResult r;
+          bool ok;
+          if (py::isinstance<py::bytes>(source)) {
+            const std::string a = source.cast<std::string>(), b = target.cast<std::string>();
+            if (a.size() > static_cast<size_t>(INT32_MAX) || b.size() > static_cast<size_t>(INT32_MAX)) {
+              throw py::value_error("an input is larger than 2 GiB");
+            }
+            py::gil_scoped_release release;
+            ok = spz::alignSpz(reinterpret_cast<const uint8_t *>(a.data()), static_cast<int32_t>(a.size()),
+                               reinterpret_cast<const uint8_t *>(b.data()), static_cast<int32_t>(b.size()), o, &r);
+          } else {
+            const std::string fa = py::str(source).cast<std::string>(), fb = py::str(target).cast<std::string>();
+            py::gil_scoped_release release;
+            ok = spz::alignSpz(fa, fb, o, &r);
+          }
+          if (!ok) {
+            raiseFailure("align_spz: refused (see the [SPZ ERROR] line)", "align_spz failed (see the [SPZ ERROR] line)",
+                         /*unsupportedRefused=*/true);
+          }
+          py::dict d;
+          d["rotation"] = py::make_tuple(r.rotation[0], r.rotation[1], r.rotation[2], r.rotation[3]);
+          d["translation"] = py::make_tuple(r.translation[0], r.translation[1], r.translation[2]);
+          d["scale"] = r.scale;
+          d["fitness"] = r.fitness;
+          d["inlier_rmse"] = r.inlierRmse;
+          d["inliers"] = r.inliers;
+          d["iterations"] = r.iterations;
+          d["converged"] = r.converged;
+          d["degenerate"] = r.degenerate;
+          py::list h;
+          for (const auto &s : r.history) h.append(py::make_tuple(s.fitness, s.inlierRmse, s.inliers));
+          d["history"] = h;
+          return d;
+        },
+        py::arg("source"), py::arg("target"), py::kw_only(), py::arg("rotation") = py::none(),
+        py::arg("translation") = py::none(), py::arg("scale") = 1.0,
+        py::arg("coord") = spz::CoordinateSystem::UNSPECIFIED, py::arg("estimate_scale") = false,
+        py::arg("overlap") = 1.0, py::arg("max_distance") = py::none(), py::arg("stride") = 1,
+        py::arg("max_iterations") = 30, py::arg("relative_fitness") = 1e-6, py::arg("relative_rmse") = 1e-6,
+        py::arg("init_centroids") = false,
+        "The similarity that places the source .spz on the target .spz (paths, or both files' bytes), by a trimmed "
+        "point-to-point ICP with an optional scale on the device (spz::alignSpz; the contract is in include/spz_amd.h "
+        "\"align\").  rotation (x, y, z, w), translation and scale are the initial placement in the frame `coord`.  "
+        "Returns a dict: rotation, translation, scale (in `coord`, ready for transform_spz or a merge placement), "
+        "fitness, inlier_rmse, inliers, iterations, converged, degenerate and history, a list of (fitness, "
+        "inlier_rmse, inliers) per step.");
   m.def("compare_spz",
         [](const py::object &a, const py::object &b, const py::object &views, spz::CoordinateSystem coord,
            const py::object &background, int max_sh_degree, float near_plane, const py::object &return_maps) {

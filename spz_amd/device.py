@@ -670,6 +670,151 @@ def radius_counts(stream_t, header, radius, min_neighbors, stream=None):
     return counts
 
 
+def _align_pair(source_t, source_hdr, target_t, target_hdr):
+    _check_clean_stream(source_t, source_hdr)
+    _check_clean_stream(target_t, target_hdr)
+    if source_t.device != target_t.device:
+        raise ValueError("the source and the target are on different devices")
+    if target_hdr.num_points == 0:
+        raise ValueError("the target has no points")
+    return (abi.AlignCloud(source_t.data_ptr(), source_t.numel(), source_hdr),
+            abi.AlignCloud(target_t.data_ptr(), target_t.numel(), target_hdr))
+
+
+def _align_map(map):
+    m = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0] if map is None else [float(v) for v in map]
+    if len(m) != 12 or not all(math.isfinite(v) for v in m):
+        raise ValueError("map must be twelve finite numbers: M = s R row-major, then t")
+    return (C.c_double * 12)(*m)
+
+
+def _align_stride(stride):
+    if isinstance(stride, bool) or not isinstance(stride, int) or stride < 1:
+        raise ValueError(f"stride must be an int >= 1, got {stride!r}")
+    return stride
+
+
+def _align_r2(max_distance, fractional_bits):
+    if max_distance is None:
+        return abi.NO_LIMIT_R2
+    if isinstance(max_distance, bool) or not isinstance(max_distance, (int, float)) or \
+            not math.isfinite(max_distance) or not max_distance > 0:
+        raise ValueError(f"max_distance must be None or a finite number > 0, got {max_distance!r}")
+    r2 = C.c_uint64(0)
+    abi.check(abi.load_library().spz_amd_clean_radius_r2(float(max_distance), fractional_bits, C.byref(r2)),
+              "spz_amd_clean_radius_r2")
+    return r2.value
+
+
+def nearest_packed(source_t, source_hdr, target_t, target_hdr, map=None, stride=1, max_distance=None, stream=None):
+    """The nearest target point of every source point of two packed v2/v3 device streams under a map (twelve floats:
+    M = s R row-major, then t, in the stored RUB frame; None: the identity), exact on the stored integers (include/
+    spz_amd.h "align", steps 1-3): (index, d2), an int64 and a uint64-valued int64 CUDA tensor in source input order.
+    index is -1 (and d2 -1) for points not taking part (i % stride != 0), mapped to a non-finite place, or without a
+    target point within max_distance (world units)."""
+    L = abi.load_library()
+    src, tgt = _align_pair(source_t, source_hdr, target_t, target_hdr)
+    m = _align_map(map)
+    stride = _align_stride(stride)
+    r2 = _align_r2(max_distance, target_hdr.fractional_bits)
+    ns, dev = source_hdr.num_points, source_t.device
+    index = torch.empty(ns, dtype=torch.int32, device=dev)
+    d2 = torch.empty(ns, dtype=torch.int64, device=dev)
+    ws = torch.empty(int(L.spz_amd_align_workspace_bytes(ns, target_hdr.num_points)), dtype=torch.uint8, device=dev)
+    st = _stream_handle(stream)
+    with torch.cuda.device(dev):
+        abi.check(L.spz_amd_align_prepare_device(C.byref(src), C.byref(tgt), ws.data_ptr(), st),
+                  "spz_amd_align_prepare_device")
+        abi.check(L.spz_amd_nearest_device(C.byref(src), C.byref(tgt), stride, m, r2, index.data_ptr(), d2.data_ptr(),
+                                           ws.data_ptr(), st), "spz_amd_nearest_device")
+    if stream is not None:
+        ws.record_stream(stream)
+    return index.to(torch.int64), d2   # 0xFFFFFFFF -> -1, UINT64_MAX -> -1
+
+
+def align_step_packed(source_t, source_hdr, target_t, target_hdr, map=None, stride=1, max_distance=None, overlap=1.0,
+                      stream=None):
+    """One step of the alignment (include/spz_amd.h "align", steps 1-5) under a map: (index, d2, inlier mask as a bool
+    CUDA tensor, abi.AlignMoments).  Synchronises to read the moments."""
+    L = abi.load_library()
+    src, tgt = _align_pair(source_t, source_hdr, target_t, target_hdr)
+    m = _align_map(map)
+    stride = _align_stride(stride)
+    r2 = _align_r2(max_distance, target_hdr.fractional_bits)
+    if isinstance(overlap, bool) or not isinstance(overlap, (int, float)) or not 0 < overlap <= 1:
+        raise ValueError(f"overlap must be in (0, 1], got {overlap!r}")
+    ns, dev = source_hdr.num_points, source_t.device
+    index = torch.empty(ns, dtype=torch.int32, device=dev)
+    d2 = torch.empty(ns, dtype=torch.int64, device=dev)
+    inlier = torch.empty(ns, dtype=torch.uint8, device=dev)
+    mom_t = torch.empty(C.sizeof(abi.AlignMoments), dtype=torch.uint8, device=dev)
+    ws = torch.empty(int(L.spz_amd_align_workspace_bytes(ns, target_hdr.num_points)), dtype=torch.uint8, device=dev)
+    st = _stream_handle(stream)
+    with torch.cuda.device(dev):
+        abi.check(L.spz_amd_align_prepare_device(C.byref(src), C.byref(tgt), ws.data_ptr(), st),
+                  "spz_amd_align_prepare_device")
+        abi.check(L.spz_amd_align_step_device(C.byref(src), C.byref(tgt), stride, m, r2, float(overlap),
+                                              index.data_ptr(), d2.data_ptr(), inlier.data_ptr(), mom_t.data_ptr(),
+                                              ws.data_ptr(), st), "spz_amd_align_step_device")
+        (stream or torch.cuda.current_stream(dev)).synchronize()
+    mom = abi.AlignMoments.from_buffer_copy(mom_t.cpu().numpy().tobytes())
+    return index.to(torch.int64), d2, inlier.bool(), mom
+
+
+def align_packed(source_t, source_hdr, target_t, target_hdr, *, rotation=None, translation=None, scale=1.0, coord=0,
+                 estimate_scale=False, overlap=1.0, max_distance=None, stride=1, max_iterations=30,
+                 relative_fitness=1e-6, relative_rmse=1e-6, init_centroids=False):
+    """The similarity that places the source stream on the target stream (spz_amd_align_host; include/spz_amd.h
+    "align"): a dict with rotation (x, y, z, w), translation and scale stated in `coord` (ready for transform_packed or
+    a merge placement), map (twelve floats, stored frame), fitness, inlier_rmse, inliers, iterations, converged,
+    degenerate, history (a list of (fitness, inlier_rmse, inliers) per step) and ms (prepare, queries, the rest).
+    Blocking; runs on a stream of its own."""
+    L = abi.load_library()
+    src, tgt = _align_pair(source_t, source_hdr, target_t, target_hdr)
+    o = abi.AlignOptions()
+    abi.check(L.spz_amd_align_default_options(C.byref(o)), "spz_amd_align_default_options")
+    if rotation is not None:
+        rotation = [float(v) for v in rotation]
+        if len(rotation) != 4:
+            raise ValueError("rotation must be (x, y, z, w)")
+        o.rotation[:] = rotation
+    if translation is not None:
+        translation = [float(v) for v in translation]
+        if len(translation) != 3:
+            raise ValueError("translation must be (x, y, z)")
+        o.translation[:] = translation
+    for name, v in (("stride", stride), ("max_iterations", max_iterations)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 2 ** 32:
+            raise ValueError(f"{name} must be a non-negative int, got {v!r}")
+    o.scale = float(scale)
+    o.coord = int(coord)
+    o.estimate_scale = 1 if estimate_scale else 0
+    o.overlap = float(overlap)
+    o.has_max_distance = 0 if max_distance is None else 1
+    o.max_distance = 0.0 if max_distance is None else float(max_distance)
+    o.stride = stride
+    o.max_iterations = max_iterations
+    o.init_centroids = 1 if init_centroids else 0
+    o.relative_fitness = float(relative_fitness)
+    o.relative_rmse = float(relative_rmse)
+    if L.spz_amd_align_check(C.byref(o)) != abi.OK:
+        raise ValueError("invalid align options: stride >= 1, overlap in (0, 1], max_distance > 0, max_iterations "
+                         "1..1000, tolerances >= 0, a nonzero rotation, scale > 0, coord 0..8, all finite")
+    res = abi.AlignResult()
+    hist = (abi.AlignHistory * max_iterations)()
+    ms = (C.c_float * 3)()
+    dev = source_t.device
+    torch.cuda.current_stream(dev).synchronize()   # the streams' producers: the run uses a stream of its own
+    rc = L.spz_amd_align_host(C.byref(src), C.byref(tgt), C.byref(o), dev.index or 0, C.byref(res), hist,
+                              max_iterations, ms)
+    abi.check(rc, "spz_amd_align_host")
+    return dict(rotation=tuple(res.rotation), translation=tuple(res.translation), scale=res.scale, map=tuple(res.map),
+                fitness=res.fitness, inlier_rmse=res.inlier_rmse, inliers=int(res.inliers),
+                iterations=int(res.iterations), converged=bool(res.converged), degenerate=bool(res.degenerate),
+                history=[(h.fitness, h.inlier_rmse, int(h.inliers)) for h in hist[:res.iterations]],
+                ms=tuple(ms))
+
+
 def _cloud_render_args(cloud, num_points, sh_degree):
     if int(sh_degree) not in SH_DIM:
         raise ValueError(f"sh_degree must be 0..3, got {sh_degree}")
