@@ -1,21 +1,18 @@
 // spz_align.hip — registration of two packed streams (DESIGN §8 "Align"; the contract is in include/spz_amd.h): a
 // point-to-point, trimmed ICP with an optional scale, on the stored 24-bit integers of both clouds.
 //
-//   spz_align_gather_kernel      sorted (u_x, u_y, u_z, input index), 16 B per point, for either cloud (u = the stored
-//                                field XOR 0x800000, as in spz_clean.hip).  Both clouds are put in Morton order once per
-//                                run (spz_amd_morton_order_device).
-//   spz_align_query_kernel       one wave per 64 consecutive source points of the source's own Morton order.  Every lane
-//                                maps its point (f64, no fused multiply-add), rounds it to the target's grid and
-//                                saturates it; its start level comes from the target's occupancy at the query's cell (one
-//                                binary search for the query's place in the sorted target: the two points beside that
-//                                place share the longest Morton prefix with it).  Then the walk of spz_clean.hip: lanes
-//                                that share a level and a cell form a group, 54 lanes find the 3x3x3 block's ranges, the
-//                                block's points stream through in coalesced chunks of 64 broadcast by readlane, and a
-//                                query whose best d2 is not below its gap to the block's faces retries one level up.  A
-//                                query outside the target's cube is located by its projection onto the cube (no target
-//                                point is nearer to the query than to that projection); its distances are its own.
-//                                k = 1 with (d2, target input index) as the key; distances are uint64 (< 2^56, beyond
-//                                f64's exact range).  With a distance limit the level whose cell side covers it is final.
+//   spz_align_query_kernel       one wave per 64 consecutive source points of the source's own Morton order (both clouds
+//                                are sorted once per run: spz_sort.hip's morton_sorted_points).  Every lane maps its
+//                                point (f64, no fused multiply-add), rounds it to the target's grid and saturates it;
+//                                its start level comes from the target's occupancy at the query's cell (one binary
+//                                search for the query's place in the sorted target: the two points beside that place
+//                                share the longest Morton prefix with it).  Then the walk of spz_morton_walk.hpp, which
+//                                describes the traversal; a query whose best d2 is not below its gap to the block's
+//                                faces retries one level up.  A query outside the target's cube is located by its
+//                                projection onto the cube (no target point is nearer to the query than to that
+//                                projection); its distances are its own.  k = 1 with (d2, target input index) as the
+//                                key; distances are uint64 (< 2^56, beyond f64's exact range).  With a distance limit
+//                                the level whose cell side covers it is final.
 //   spz_align_key_kernel /       trimming: d2 as two u32 key planes for the stable radix sort (spz_sort_internal.hpp),
 //   spz_align_select_kernel      ties in input order; the first K = min(c, ceil(overlap c)) ranks are the inliers.
 //   spz_align_moment_kernel /    the moments of the inliers: per tile of 2048 source points a pairwise sum in a fixed
@@ -31,7 +28,9 @@
 #include <cstring>
 
 #include "spz_amd.h"
+#include "spz_block_ops.hpp"
 #include "spz_common.hpp"
+#include "spz_morton_walk.hpp"
 #include "spz_sort_internal.hpp"
 
 #pragma clang fp contract(off)
@@ -41,6 +40,7 @@ namespace {
 
 constexpr uint32_t kAlBlock = 256;
 constexpr uint32_t kAlWaves = kAlBlock / 64u;
+static_assert(kAlBlock == kOpsBlock, "block_sum is over 256 threads");
 constexpr uint32_t kAlItems = 8;                      // source points per thread of the moment sums
 constexpr uint32_t kAlTile = kAlBlock * kAlItems;     // 2048
 constexpr uint32_t kAlSums = 17;                      // f64 sums: a (3), b (3), a b^T (9), |a|^2, |b|^2
@@ -72,55 +72,6 @@ struct MomentParams {
   unsigned long long *partials;  // tiles x kAlPartial words
 };
 
-__device__ __forceinline__ uint32_t al_load_u(const uint8_t *pos, unsigned long long i, uint32_t a) {
-  const uint8_t *b = pos + i * 9ull + 3u * a;
-  return ((uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16)) ^ 0x800000u;
-}
-
-__device__ __forceinline__ bool al_msb_less(uint32_t p, uint32_t q) { return p < q && p < (p ^ q); }
-
-// Morton order of two cells at one level (spz_clean.hip's cell_cmp): z outranks y outranks x at equal bits.
-__device__ __forceinline__ int al_cell_cmp(uint32_t a0, uint32_t a1, uint32_t a2, uint32_t b0, uint32_t b1, uint32_t b2) {
-  uint32_t best = a2 ^ b2, x = a2, y = b2;
-  if (al_msb_less(best, a1 ^ b1)) {
-    best = a1 ^ b1;
-    x = a1;
-    y = b1;
-  }
-  if (al_msb_less(best, a0 ^ b0)) {
-    best = a0 ^ b0;
-    x = a0;
-    y = b0;
-  }
-  if (best == 0) return 0;
-  return x < y ? -1 : 1;
-}
-
-// The first sorted point whose cell at level L is >= c (upper: > c) in Morton order.
-__device__ uint32_t al_cell_bound(const uint4 *pts, uint32_t n, uint32_t L, uint32_t c0, uint32_t c1, uint32_t c2,
-                                  bool upper) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    const uint4 p = pts[mid];
-    const int r = al_cell_cmp(p.x >> L, p.y >> L, p.z >> L, c0, c1, c2);
-    if (r < 0 || (upper && r == 0)) {
-      lo = mid + 1;
-    } else {
-      hi = mid;
-    }
-  }
-  return lo;
-}
-
-// Cell q of the 3x3x3 block in scan order: q = 0 is the centre, then the other 26.
-__device__ __forceinline__ void al_block_offset(uint32_t q, int *o) {
-  const uint32_t t = q == 0 ? 13u : (q == 13 ? 0u : q);
-  o[0] = (int)(t % 3u) - 1;
-  o[1] = (int)((t / 3u) % 3u) - 1;
-  o[2] = (int)(t / 9u) - 1;
-}
-
 __device__ __forceinline__ unsigned long long al_sq(int32_t d) {
   const uint32_t a = (uint32_t)(d < 0 ? -d : d);  // |d| < 2^27
   return (unsigned long long)a * a;
@@ -142,39 +93,40 @@ __device__ __forceinline__ unsigned long long al_pair_d2(const int32_t q[3], uin
   return al_sq(q[0] - (int32_t)x) + al_sq(q[1] - (int32_t)y) + al_sq(q[2] - (int32_t)z);  // < 3 * 2^54
 }
 
-// The smallest Morton cell holding sorted points f and l (and so every point between them): [lo, hi] per axis.
-__device__ __forceinline__ void al_common_cell(uint32_t f0, uint32_t f1, uint32_t f2, uint32_t l0, uint32_t l1,
-                                               uint32_t l2, uint32_t lo[3], uint32_t hi[3]) {
-  const uint32_t x = (f0 ^ l0) | (f1 ^ l1) | (f2 ^ l2);
-  const uint32_t lv = x ? 32u - (uint32_t)__clz(x) : 0u;
-  const uint32_t mask = lv >= 32u ? 0xffffffffu : ((1u << lv) - 1u);
-  lo[0] = f0 & ~mask;
-  lo[1] = f1 & ~mask;
-  lo[2] = f2 & ~mask;
-  hi[0] = lo[0] | mask;
-  hi[1] = lo[1] | mask;
-  hi[2] = lo[2] | mask;
-}
+// The nearest-neighbour side of the walk: the minimum of (d2, target input index) within the limit.
+struct NearestPolicy {
+  static constexpr bool kSaturates = false;
+  const QueryParams &p;
+  int32_t q[3];        // the query, biased; may lie outside the cube
+  uint32_t c[3], orig; // q clamped to the cube
+  unsigned long long best;
+  uint32_t bidx;
 
-__device__ __forceinline__ uint32_t al_rl(uint32_t v, uint32_t lane) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)lane);
-}
-
-// The smallest level at which c and p lie in one cell.
-__device__ __forceinline__ uint32_t al_join_level(const uint32_t c[3], const uint4 p) {
-  const uint32_t d = (c[0] ^ p.x) | (c[1] ^ p.y) | (c[2] ^ p.z);
-  return d ? 32u - (uint32_t)__clz(d) : 0u;
-}
+  __device__ __forceinline__ void start() {}
+  __device__ __forceinline__ bool more() const { return true; }
+  // <=: a point at the best distance with a smaller input index replaces the best
+  __device__ __forceinline__ bool near(const uint32_t lo[3], const uint32_t hi[3]) const {
+    return al_box_d2(q, lo, hi) <= (best < p.limit ? best : p.limit);
+  }
+  __device__ __forceinline__ void visit(bool mine, uint32_t x, uint32_t y, uint32_t z, uint32_t w, uint32_t) {
+    const unsigned long long d2 = al_pair_d2(q, x, y, z);
+    if (mine && d2 <= p.limit && (d2 < best || (d2 == best && w < bidx))) {
+      best = d2;
+      bidx = w;
+    }
+  }
+  // settled when every point outside the block is farther than the best: the gap to the block's faces, strictly (a
+  // point at the same distance outside the block could have the smaller index)
+  __device__ __forceinline__ bool settle(uint32_t Lg) {
+    const long long g = face_gap(q, c, Lg);
+    if (Lg < 24u && Lg < p.limit_level && g >= 0 && !(best < (unsigned long long)g * (unsigned long long)g)) return false;
+    p.index[orig] = bidx;
+    p.d2[orig] = bidx == kAlNone ? kAlNoLimit : best;
+    return true;
+  }
+};
 
 }  // namespace
-
-__global__ __launch_bounds__(kAlBlock) void spz_align_gather_kernel(const uint8_t *pos, const uint32_t *order,
-                                                                    uint32_t n, uint4 *pts) {
-  const unsigned long long i = (unsigned long long)blockIdx.x * kAlBlock + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t s = order[i];
-  pts[i] = make_uint4(al_load_u(pos, s, 0), al_load_u(pos, s, 1), al_load_u(pos, s, 2), s);
-}
 
 // One wave per 64 sorted source points.  See the file comment.
 __global__ __launch_bounds__(kAlBlock) void spz_align_query_kernel(const QueryParams p) {
@@ -183,13 +135,13 @@ __global__ __launch_bounds__(kAlBlock) void spz_align_query_kernel(const QueryPa
   if (base_i >= p.ns) return;  // the whole wave
   const uint32_t i = (uint32_t)base_i + lane;
   const bool in_range = i < p.ns;
-  int32_t q[3] = {0, 0, 0};
-  uint32_t c[3] = {0, 0, 0}, orig = 0, L = 0;
+  NearestPolicy pol = {p, {0, 0, 0}, {0, 0, 0}, 0, kAlNoLimit, kAlNone};
+  uint32_t L = 0;
   bool valid = false;
   if (in_range) {
     const uint4 me = p.spts[i];
-    orig = me.w;
-    if (orig % p.stride == 0u) {
+    pol.orig = me.w;
+    if (pol.orig % p.stride == 0u) {
       const double x = (double)((int32_t)me.x - kAlBias) * p.src_scale;
       const double y = (double)((int32_t)me.y - kAlBias) * p.src_scale;
       const double z = (double)((int32_t)me.z - kAlBias) * p.src_scale;
@@ -199,94 +151,18 @@ __global__ __launch_bounds__(kAlBlock) void spz_align_query_kernel(const QueryPa
         const double v = ((p.m[3 * a] * x + p.m[3 * a + 1] * y) + p.m[3 * a + 2] * z) + p.m[9 + a];
         valid = valid && __builtin_isfinite(v);
         const double r = fmax(-67108864.0, fmin(67108864.0, __builtin_rint(v * p.tgt_scale)));  // +-2^26
-        q[a] = (valid ? (int32_t)r : 0) + kAlBias;
-        c[a] = (uint32_t)min(max(q[a], 0), 0xffffff);
+        pol.q[a] = (valid ? (int32_t)r : 0) + kAlBias;
+        pol.c[a] = (uint32_t)min(max(pol.q[a], 0), 0xffffff);
       }
     }
   }
-  if (valid) {
-    // the query's place in the sorted target: its neighbours there share the longest Morton prefix with it
-    const uint32_t at = al_cell_bound(p.tpts, p.nt, 0u, c[0], c[1], c[2], false);
-    uint32_t l0 = 24u;
-    if (at < p.nt) l0 = min(l0, al_join_level(c, p.tpts[at]));
-    if (at > 0u) l0 = min(l0, al_join_level(c, p.tpts[at - 1u]));
-    L = min(l0, p.limit_level);
-  }
-  unsigned long long best = kAlNoLimit;
-  uint32_t bidx = kAlNone;
-  unsigned long long pending = __ballot(valid);
-  while (pending) {
-    const uint32_t leader = (uint32_t)__builtin_ctzll(pending);
-    const uint32_t Lg = al_rl(L, leader);
-    const uint32_t c0 = al_rl(c[0] >> Lg, leader), c1 = al_rl(c[1] >> Lg, leader), c2 = al_rl(c[2] >> Lg, leader);
-    const bool in_g = ((pending >> lane) & 1ull) && L == Lg && (c[0] >> Lg) == c0 && (c[1] >> Lg) == c1 &&
-                      (c[2] >> Lg) == c2;
-    // the block's cell ranges: lane t < 27 the first point of cell t, lane 27 + t the end
-    uint32_t bound = 0;
-    if (lane < 54u) {
-      const uint32_t t = lane % 27u;
-      int o[3];
-      al_block_offset(t, o);
-      const long long cells = 1ll << (24 - Lg);
-      const long long x = (long long)c0 + o[0], y = (long long)c1 + o[1], z = (long long)c2 + o[2];
-      if (x >= 0 && y >= 0 && z >= 0 && x < cells && y < cells && z < cells) {
-        bound = al_cell_bound(p.tpts, p.nt, Lg, (uint32_t)x, (uint32_t)y, (uint32_t)z, lane >= 27u);
-      }
-    }
-    for (uint32_t t = 0; t < 27u; ++t) {
-      const uint32_t s = al_rl(bound, t), e = al_rl(bound, t + 27u);
-      for (uint32_t b0 = s; b0 < e; b0 += 64u) {
-        const uint32_t cnt = min(64u, e - b0);
-        uint4 cand = make_uint4(0, 0, 0, 0);
-        if (lane < cnt) cand = p.tpts[b0 + lane];
-        uint32_t lo[3], hi[3];
-        al_common_cell(al_rl(cand.x, 0), al_rl(cand.y, 0), al_rl(cand.z, 0), al_rl(cand.x, cnt - 1),
-                       al_rl(cand.y, cnt - 1), al_rl(cand.z, cnt - 1), lo, hi);
-        // <=: a point at the best distance with a smaller input index replaces the best
-        if (!__ballot(in_g && al_box_d2(q, lo, hi) <= (best < p.limit ? best : p.limit))) continue;
-        for (uint32_t k = 0; k < cnt; ++k) {
-          const unsigned long long d2 = al_pair_d2(q, al_rl(cand.x, k), al_rl(cand.y, k), al_rl(cand.z, k));
-          const uint32_t w = al_rl(cand.w, k);
-          if (in_g && d2 <= p.limit && (d2 < best || (d2 == best && w < bidx))) {
-            best = d2;
-            bidx = w;
-          }
-        }
-      }
-    }
-    // resolved when every point outside the block is farther than the best: the gap to the block's faces, strictly
-    // (a point at the same distance outside the block could have the smaller index)
-    bool done = false;
-    if (in_g) {
-      const uint32_t last = (1u << (24u - Lg)) - 1u;
-      long long g = -1;
-#pragma unroll
-      for (uint32_t a = 0; a < 3; ++a) {
-        const uint32_t cc = c[a] >> Lg;
-        if (cc > 1u) {
-          const long long v = (long long)q[a] - (long long)((unsigned long long)(cc - 1u) << Lg) + 1;
-          g = g < 0 || v < g ? v : g;
-        }
-        if (cc + 1u < last) {
-          const long long v = (long long)((unsigned long long)(cc + 2u) << Lg) - (long long)q[a];
-          g = g < 0 || v < g ? v : g;
-        }
-      }
-      done = Lg >= 24u || Lg >= p.limit_level || g < 0 || best < (unsigned long long)g * (unsigned long long)g;
-      if (done) {
-        p.index[orig] = bidx;
-        p.d2[orig] = bidx == kAlNone ? kAlNoLimit : best;
-      } else {
-        L = Lg + 1u;
-      }
-    }
-    pending &= ~__ballot(in_g && done);
-  }
+  if (valid) L = min(occupied_level(p.tpts, p.nt, pol.c), p.limit_level);
+  morton_walk(p.tpts, p.nt, lane, valid, pol.c, L, pol);
   if (in_range && !valid) {
-    p.index[orig] = kAlNone;
-    p.d2[orig] = kAlNoLimit;
+    p.index[pol.orig] = kAlNone;
+    p.d2[pol.orig] = kAlNoLimit;
   }
-  const unsigned long long found = __ballot(valid && bidx != kAlNone);
+  const unsigned long long found = __ballot(valid && pol.bidx != kAlNone);
   if (lane == 0 && found) atomicAdd(p.counter, (uint32_t)__popcll(found));
 }
 
@@ -317,36 +193,6 @@ __global__ __launch_bounds__(kAlBlock) void spz_align_select_kernel(const uint32
   inlier[order[r]] = r < K ? 1u : 0u;
 }
 
-namespace {
-
-__device__ __forceinline__ double al_block_sum(double v, double *s) {
-  const uint32_t tid = threadIdx.x;
-  s[tid] = v;
-  __syncthreads();
-  for (uint32_t off = kAlBlock / 2u; off > 0; off >>= 1) {
-    if (tid < off) s[tid] = s[tid] + s[tid + off];
-    __syncthreads();
-  }
-  const double r = s[0];
-  __syncthreads();
-  return r;
-}
-
-__device__ __forceinline__ unsigned long long al_block_sum_u64(unsigned long long v, unsigned long long *s) {
-  const uint32_t tid = threadIdx.x;
-  s[tid] = v;
-  __syncthreads();
-  for (uint32_t off = kAlBlock / 2u; off > 0; off >>= 1) {
-    if (tid < off) s[tid] = s[tid] + s[tid + off];
-    __syncthreads();
-  }
-  const unsigned long long r = s[0];
-  __syncthreads();
-  return r;
-}
-
-}  // namespace
-
 // The moments of one tile of 2048 source points (input order).  A thread's eight terms are added pairwise, then the
 // workgroup's 256 sums in a binary tree: depth 11 for the tile.
 __global__ __launch_bounds__(kAlBlock) void spz_align_moment_kernel(const MomentParams p) {
@@ -364,14 +210,14 @@ __global__ __launch_bounds__(kAlBlock) void spz_align_moment_kernel(const Moment
     if (in) {
       double a[3], b[3];
 #pragma unroll
-      for (uint32_t k = 0; k < 3; ++k) a[k] = (double)((int32_t)al_load_u(p.spos, i, k) - kAlBias) * p.src_scale;
+      for (uint32_t k = 0; k < 3; ++k) a[k] = (double)((int32_t)load_u(p.spos, i, k) - kAlBias) * p.src_scale;
       if (p.self) {
 #pragma unroll
         for (uint32_t k = 0; k < 3; ++k) b[k] = a[k];
       } else {
         const uint32_t j = p.index[i];
 #pragma unroll
-        for (uint32_t k = 0; k < 3; ++k) b[k] = (double)((int32_t)al_load_u(p.tpos, j, k) - kAlBias) * p.tgt_scale;
+        for (uint32_t k = 0; k < 3; ++k) b[k] = (double)((int32_t)load_u(p.tpos, j, k) - kAlBias) * p.tgt_scale;
         const unsigned long long d = p.d2[i];
         dlo += d & 0xffffffffull;
         dhi += d >> 32;
@@ -409,10 +255,10 @@ __global__ __launch_bounds__(kAlBlock) void spz_align_moment_kernel(const Moment
   unsigned long long *out = p.partials + (unsigned long long)blockIdx.x * kAlPartial;
 #pragma unroll
   for (uint32_t k = 0; k < kAlSums; ++k) {
-    const double v = al_block_sum(l2[k], reinterpret_cast<double *>(s));
+    const double v = block_sum(l2[k], reinterpret_cast<double *>(s));
     if (threadIdx.x == 0) out[k] = (unsigned long long)__double_as_longlong(v);
   }
-  const unsigned long long c = al_block_sum_u64(count, s), lo = al_block_sum_u64(dlo, s), hi = al_block_sum_u64(dhi, s);
+  const unsigned long long c = block_sum(count, s), lo = block_sum(dlo, s), hi = block_sum(dhi, s);
   if (threadIdx.x == 0) {
     out[kAlSums] = c;
     out[kAlSums + 1] = lo;
@@ -441,7 +287,7 @@ __global__ __launch_bounds__(kAlBlock) void spz_align_reduce_kernel(const unsign
 #pragma unroll
       for (uint32_t r = 0; r < kAlReduceItems; r += 2u * w) v[r] = v[r] + v[r + w];
     }
-    const double total = al_block_sum(v[0], reinterpret_cast<double *>(s));
+    const double total = block_sum(v[0], reinterpret_cast<double *>(s));
     if (threadIdx.x == 0) sums[k] = total;
   }
   unsigned long long ints[3];
@@ -449,7 +295,7 @@ __global__ __launch_bounds__(kAlBlock) void spz_align_reduce_kernel(const unsign
   for (uint32_t k = 0; k < 3; ++k) {
     unsigned long long v = 0;
     for (uint32_t t = threadIdx.x; t < tiles; t += kAlBlock) v += partials[(unsigned long long)t * kAlPartial + kAlSums + k];
-    ints[k] = al_block_sum_u64(v, s);
+    ints[k] = block_sum(v, s);
   }
   if (threadIdx.x != 0) return;
   out->count = ints[0];
@@ -476,36 +322,25 @@ AlLayout al_layout(uint64_t ns, uint64_t nt) {
   AlLayout w;
   w.tiles = (ns + kAlTile - 1) / kAlTile;
   const uint64_t nmax = ns > nt ? ns : nt;
-  uint64_t off = 0;
-  auto put = [&off](uint64_t *at, uint64_t bytes) {
-    *at = off;
-    off += Workspace::aligned(bytes);
-  };
-  put(&w.sort_ws, spz_amd_sort_workspace_bytes(nmax));
-  put(&w.order, nmax * 4u);
-  put(&w.tpts, nt * 16u);
-  put(&w.spts, ns * 16u);
-  put(&w.index, ns * 4u);
-  put(&w.d2, ns * 8u);
-  put(&w.inlier, ns);
-  put(&w.partials, ((nmax + kAlTile - 1) / kAlTile + 1) * kAlPartial * 8u);  // the target's centroid uses it too
-  put(&w.counter, 256u);
-  w.bytes = off + 256;  // room to align a caller's pointer up to 256
+  WorkspaceOffsets o;
+  o.put(&w.sort_ws, spz_amd_sort_workspace_bytes(nmax));
+  o.put(&w.order, nmax * 4u);
+  o.put(&w.tpts, nt * 16u);
+  o.put(&w.spts, ns * 16u);
+  o.put(&w.index, ns * 4u);
+  o.put(&w.d2, ns * 8u);
+  o.put(&w.inlier, ns);
+  o.put(&w.partials, ((nmax + kAlTile - 1) / kAlTile + 1) * kAlPartial * 8u);  // the target's centroid uses it too
+  o.put(&w.counter, 256u);
+  w.bytes = o.bytes();
   return w;
 }
 
-uint8_t *al_align_ws(void *d_workspace) {
-  return reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(d_workspace) + 255u) & ~uintptr_t(255));
-}
-
 int al_check_cloud(const spz_amd_align_cloud *c, spz_amd_layout *lay) {
-  if (c == nullptr || c->d_stream == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
+  if (c == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
   const spz_amd_header *hdr = &c->hdr;
-  if (hdr->version < 1 || hdr->version > 3) return SPZ_AMD_ERR_VERSION;
-  if (hdr->sh_degree > 3) return SPZ_AMD_ERR_SH_DEGREE;
-  int rc = spz_amd_stream_layout(hdr->num_points, hdr->sh_degree, (int)hdr->version, lay);
+  const int rc = check_packed_stream(c->d_stream, c->size, hdr, lay);
   if (rc != SPZ_AMD_OK) return rc;
-  if (c->size < lay->total_bytes) return SPZ_AMD_ERR_SHORT_STREAM;
   if (hdr->version == 1) return SPZ_AMD_ERR_UNSUPPORTED;  // float16 positions: no integer distances
   if (hdr->num_points > SPZ_AMD_REFERENCE_MAX_POINTS) return SPZ_AMD_ERR_TOO_MANY_POINTS;
   if (hdr->fractional_bits > 24) return SPZ_AMD_ERR_INVALID_ARG;
@@ -535,15 +370,8 @@ bool al_bad_overlap(double f) { return !(f > 0.0) || !(f <= 1.0); }
 
 int al_sort_one(const spz_amd_align_cloud *c, const spz_amd_layout &lay, uint8_t *ws, const AlLayout &wl, uint64_t pts_off,
                 hipStream_t st) {
-  const uint32_t n = c->hdr.num_points;
-  if (n == 0) return SPZ_AMD_OK;
-  uint32_t *order = reinterpret_cast<uint32_t *>(ws + wl.order);
-  int rc = spz_amd_morton_order_device(c->d_stream, c->size, &c->hdr, 0, order, ws + wl.sort_ws, st);
-  if (rc != SPZ_AMD_OK) return rc;
-  hipLaunchKernelGGL(spz_align_gather_kernel, dim3((n + kAlBlock - 1) / kAlBlock), dim3(kAlBlock), 0, st,
-                     c->d_stream + lay.offset[SPZ_AMD_SEC_POSITIONS], order, n, reinterpret_cast<uint4 *>(ws + pts_off));
-  SPZ_HIP_TRY(hipGetLastError());
-  return SPZ_AMD_OK;
+  return morton_sorted_points(c->d_stream, c->size, &c->hdr, lay, reinterpret_cast<uint32_t *>(ws + wl.order),
+                              reinterpret_cast<uint4 *>(ws + pts_off), ws + wl.sort_ws, st);
 }
 
 int al_prepare(const spz_amd_align_cloud *source, const spz_amd_layout &sl, const spz_amd_align_cloud *target,
@@ -824,7 +652,7 @@ int spz_amd_align_prepare_device(const spz_amd_align_cloud *source, const spz_am
   rc = current_device(&device);
   if (rc != SPZ_AMD_OK) return rc;
   const AlLayout wl = al_layout(source->hdr.num_points, target->hdr.num_points);
-  return al_prepare(source, sl, target, tl, al_align_ws(d_workspace), wl, static_cast<hipStream_t>(hip_stream));
+  return al_prepare(source, sl, target, tl, align_ws(d_workspace), wl, static_cast<hipStream_t>(hip_stream));
 }
 
 int spz_amd_nearest_device(const spz_amd_align_cloud *source, const spz_amd_align_cloud *target, uint32_t stride,
@@ -839,7 +667,7 @@ int spz_amd_nearest_device(const spz_amd_align_cloud *source, const spz_amd_alig
   rc = current_device(&device);
   if (rc != SPZ_AMD_OK) return rc;
   const AlLayout wl = al_layout(source->hdr.num_points, target->hdr.num_points);
-  return al_query(source, target, stride, map, r2, d_index, d_d2, al_align_ws(d_workspace), wl,
+  return al_query(source, target, stride, map, r2, d_index, d_d2, align_ws(d_workspace), wl,
                   static_cast<hipStream_t>(hip_stream));
 }
 
@@ -857,7 +685,7 @@ int spz_amd_align_step_device(const spz_amd_align_cloud *source, const spz_amd_a
   if (rc != SPZ_AMD_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   const AlLayout wl = al_layout(source->hdr.num_points, target->hdr.num_points);
-  uint8_t *ws = al_align_ws(d_workspace);
+  uint8_t *ws = align_ws(d_workspace);
   if (d_index == nullptr) d_index = reinterpret_cast<uint32_t *>(ws + wl.index);
   if (d_d2 == nullptr) d_d2 = reinterpret_cast<uint64_t *>(ws + wl.d2);
   if (d_inlier == nullptr) d_inlier = ws + wl.inlier;
@@ -931,7 +759,7 @@ int spz_amd_align_host(const spz_amd_align_cloud *source, const spz_amd_align_cl
   if (rc != SPZ_AMD_OK) return rc;
   const AlLayout wl = al_layout(source->hdr.num_points, target->hdr.num_points);
   SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->block), wl.bytes + 256));
-  uint8_t *ws = al_align_ws(c->block);
+  uint8_t *ws = align_ws(c->block);
   auto *d_mom = reinterpret_cast<spz_amd_align_moments *>(c->block + wl.bytes);
   static_assert(sizeof(spz_amd_align_moments) <= 256, "the moments follow the workspace");
   rc = al_prepare(source, sl, target, tl, ws, wl, c->st);

@@ -1,20 +1,16 @@
 // spz_clean.hip — floater removal on a packed stream (DESIGN §8 "Clean"): the exact k nearest neighbours of every point
 // (statistical outlier removal) and the count of neighbours within a radius, on the stored 24-bit integers, then the
-// filter's subset of the kept points.  The input is put in Morton order first (spz_sort.hip's
-// spz_amd_morton_order_device, then a gather of the positions), so every octree cell at every level is a contiguous
-// range of the sorted points, found by binary search.
+// filter's subset of the kept points.  The input is put in Morton order first (spz_sort.hip's morton_sorted_points:
+// sorted (u_x, u_y, u_z, input index), 16 B per point), and both searches are the walk of spz_morton_walk.hpp, which
+// describes the traversal; this file holds what the two searches do with a candidate.
 //
-//   spz_clean_gather_kernel      sorted (u_x, u_y, u_z, input index), 16 B per point.
 //   spz_clean_level_kernel       per sorted point, the start level of the k-NN search: the smallest L at which its
 //                                own cell holds at least k_eff + 1 points (sliding max / min over the level at which
 //                                consecutive points part, in LDS).
-//   spz_clean_search_kernel<K>   one wave per 64 consecutive sorted points.  Lanes that share a level and a cell form a
-//                                group; 54 lanes find the 3x3x3 block's cell ranges, then the wave streams the block's
-//                                points in chunks of 64 (one coalesced load, each candidate broadcast with readlane)
-//                                and every lane of the group keeps a sorted top-K of d2 in registers (fully unrolled,
-//                                no runtime index).  A chunk whose common Morton cell is no nearer than every group
-//                                lane's k-th distance is skipped.  A point whose k-th d2 is above its gap to the
-//                                block's faces retries one level up; level 24 covers all of space.
+//   spz_clean_search_kernel<K>   one wave per 64 consecutive sorted points; every lane keeps a sorted top-K of d2 in
+//                                registers (fully unrolled, no runtime index).  A chunk whose common Morton cell is no
+//                                nearer than every group lane's k-th distance is skipped.  A point whose k-th d2 is
+//                                above its gap to the block's faces retries one level up.
 //   spz_clean_radius_kernel      the same walk at one level (4^L >= R2), counting d2 <= R2 up to min_neighbors.
 //   spz_clean_sum_kernel /       the threshold: per tile of 2048 scores a sum in a fixed tree, then one workgroup
 //   spz_clean_stats_kernel       over the tiles; two passes (mean, then the squared deviations).
@@ -29,7 +25,10 @@
 #include <cstring>
 
 #include "spz_amd.h"
+#include "spz_block_ops.hpp"
 #include "spz_common.hpp"
+#include "spz_morton_walk.hpp"
+#include "spz_sort_internal.hpp"
 
 #pragma clang fp contract(off)
 
@@ -38,6 +37,7 @@ namespace {
 
 constexpr uint32_t kClBlock = 256;
 constexpr uint32_t kClWaves = kClBlock / 64u;
+static_assert(kClBlock == kOpsBlock, "block_sum is over 256 threads");
 constexpr uint32_t kClItems = 8;                        // scores per thread of the threshold sums
 constexpr uint32_t kClTile = kClBlock * kClItems;       // 2048
 constexpr uint32_t kClMaxK = 64;
@@ -47,57 +47,6 @@ constexpr double kClR2Cap = 1125899906842624.0;         // 2^50 > every d2 (< 3 
 struct CleanStats {
   double sum, mean, sq, std, thr;
 };
-
-__device__ __forceinline__ uint32_t load_u(const uint8_t *pos, unsigned long long i, uint32_t a) {
-  const uint8_t *b = pos + i * 9ull + 3u * a;
-  return ((uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16)) ^ 0x800000u;
-}
-
-// msb(p) < msb(q) (msb(0) = -1)
-__device__ __forceinline__ bool msb_less(uint32_t p, uint32_t q) { return p < q && p < (p ^ q); }
-
-// Morton order of two cells at one level: the axis of the highest differing bit decides; at equal bits z outranks y
-// outranks x (key bit 3b + a).
-__device__ __forceinline__ int cell_cmp(uint32_t a0, uint32_t a1, uint32_t a2, uint32_t b0, uint32_t b1, uint32_t b2) {
-  uint32_t best = a2 ^ b2, x = a2, y = b2;
-  if (msb_less(best, a1 ^ b1)) {
-    best = a1 ^ b1;
-    x = a1;
-    y = b1;
-  }
-  if (msb_less(best, a0 ^ b0)) {
-    best = a0 ^ b0;
-    x = a0;
-    y = b0;
-  }
-  if (best == 0) return 0;
-  return x < y ? -1 : 1;
-}
-
-// The first sorted point whose cell at level L is >= c (upper: > c) in Morton order.
-__device__ uint32_t cell_bound(const uint4 *pts, uint32_t n, uint32_t L, uint32_t c0, uint32_t c1, uint32_t c2,
-                               bool upper) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    const uint4 p = pts[mid];
-    const int r = cell_cmp(p.x >> L, p.y >> L, p.z >> L, c0, c1, c2);
-    if (r < 0 || (upper && r == 0)) {
-      lo = mid + 1;
-    } else {
-      hi = mid;
-    }
-  }
-  return lo;
-}
-
-// Cell q of the 3x3x3 block in scan order: q = 0 is the centre, then the other 26.
-__device__ __forceinline__ void block_offset(uint32_t q, int *o) {
-  const uint32_t t = q == 0 ? 13u : (q == 13 ? 0u : q);
-  o[0] = (int)(t % 3u) - 1;
-  o[1] = (int)((t / 3u) % 3u) - 1;
-  o[2] = (int)(t / 9u) - 1;
-}
 
 // The smallest distance from u to a point of the closed box [lo, hi], squared, in f64 (exact).
 __device__ __forceinline__ double box_d2(const uint32_t u[3], const uint32_t lo[3], const uint32_t hi[3]) {
@@ -118,30 +67,12 @@ __device__ __forceinline__ double pair_d2(const uint32_t u[3], uint32_t x, uint3
   return dx * dx + dy * dy + dz * dz;  // every term and partial sum is an integer < 2^50: exact
 }
 
-// The smallest Morton cell holding sorted points f and l (and so every point between them): [lo, hi] per axis.
-__device__ __forceinline__ void common_cell(uint32_t f0, uint32_t f1, uint32_t f2, uint32_t l0, uint32_t l1, uint32_t l2,
-                                            uint32_t lo[3], uint32_t hi[3]) {
-  const uint32_t x = (f0 ^ l0) | (f1 ^ l1) | (f2 ^ l2);
-  const uint32_t lv = x ? 32u - (uint32_t)__clz(x) : 0u;  // the level of the common cell
-  const uint32_t mask = lv >= 32u ? 0xffffffffu : ((1u << lv) - 1u);
-  lo[0] = f0 & ~mask;
-  lo[1] = f1 & ~mask;
-  lo[2] = f2 & ~mask;
-  hi[0] = lo[0] | mask;
-  hi[1] = lo[1] | mask;
-  hi[2] = lo[2] | mask;
-}
-
 // Sorted ascending list t[0..K), insertion of d with the last entry dropped; compile-time indices only.
 template <int K>
 __device__ __forceinline__ void topk_insert(double (&t)[K], double d) {
 #pragma unroll
   for (int j = K - 1; j >= 1; --j) t[j] = fmax(fmin(t[j], d), t[j - 1]);
   t[0] = fmin(t[0], d);
-}
-
-__device__ __forceinline__ uint32_t rl(uint32_t v, uint32_t lane) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)lane);
 }
 
 struct SearchParams {
@@ -155,14 +86,6 @@ struct SearchParams {
 };
 
 }  // namespace
-
-__global__ __launch_bounds__(kClBlock) void spz_clean_gather_kernel(const uint8_t *pos, const uint32_t *order,
-                                                                    uint32_t n, uint4 *pts) {
-  const unsigned long long i = (unsigned long long)blockIdx.x * kClBlock + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t s = order[i];
-  pts[i] = make_uint4(load_u(pos, s, 0), load_u(pos, s, 1), load_u(pos, s, 2), s);
-}
 
 // b_t (t >= 1): the level at which sorted points t - 1 and t part, max_a msb(u_a ^ u'_a), -1 when equal.  Window j
 // (points j .. j + keff) lies in one cell at level L iff M_j = max(b_j+1 .. b_j+keff) < L; point i's start level is
@@ -202,166 +125,103 @@ __global__ __launch_bounds__(kClBlock) void spz_clean_level_kernel(const uint4 *
   lvl[i] = (uint8_t)min(best + 1, 24);
 }
 
-// One wave per 64 sorted points.  See the file comment.
+namespace {
+
+// The k-NN search's side of the walk: a sorted top-K of d2 in registers (fully unrolled, no runtime index).
+template <int K>
+struct KnnPolicy {
+  static constexpr bool kSaturates = true;
+  const SearchParams &p;
+  uint32_t u[3], self, orig;
+  double t[K];
+
+  __device__ __forceinline__ void start() {
+#pragma unroll
+    for (int j = 0; j < K; ++j) t[j] = (j < K - (int)p.keff) ? -__builtin_inf() : __builtin_inf();
+  }
+  __device__ __forceinline__ bool more() const { return t[K - 1] > 0.0; }  // else k zero distances: final
+  __device__ __forceinline__ bool near(const uint32_t lo[3], const uint32_t hi[3]) const {
+    return box_d2(u, lo, hi) < t[K - 1];
+  }
+  __device__ __forceinline__ void visit(bool mine, uint32_t x, uint32_t y, uint32_t z, uint32_t, uint32_t at) {
+    const double d2 = pair_d2(u, x, y, z);
+    if (mine && d2 < t[K - 1] && at != self) topk_insert<K>(t, d2);
+  }
+  // settled when no point outside the block can be nearer than the k-th: its gap to the block's faces
+  __device__ __forceinline__ bool settle(uint32_t Lg) {
+    const int32_t q[3] = {(int32_t)u[0], (int32_t)u[1], (int32_t)u[2]};
+    const long long g = face_gap(q, u, Lg);
+    const bool done = Lg >= 24u || g < 0 || t[K - 1] <= (double)g * (double)g;  // g < 2^25: exact in f64
+    if (done) {
+      double sum = 0.0;
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        if (j >= K - (int)p.keff) sum = sum + __builtin_sqrt(t[j]);  // ascending
+      }
+      p.scores[orig] = sum / (double)p.keff * p.scale;
+      if (p.kth) p.kth[orig] = (unsigned long long)t[K - 1];
+    }
+    return done;
+  }
+};
+
+// The radius counts' side: other points with d2 <= r2, up to min_neighbors; one level settles every query.
+struct RadiusPolicy {
+  static constexpr bool kSaturates = true;
+  const SearchParams &p;
+  uint32_t u[3], self, orig, count;
+
+  __device__ __forceinline__ void start() {}
+  __device__ __forceinline__ bool more() const { return count < p.min_neighbors; }
+  __device__ __forceinline__ bool near(const uint32_t lo[3], const uint32_t hi[3]) const {
+    return more() && box_d2(u, lo, hi) <= p.r2;
+  }
+  __device__ __forceinline__ void visit(bool mine, uint32_t x, uint32_t y, uint32_t z, uint32_t, uint32_t at) {
+    count += (mine && pair_d2(u, x, y, z) <= p.r2 && at != self) ? 1u : 0u;
+  }
+  __device__ __forceinline__ bool settle(uint32_t) {
+    p.counts[orig] = min(count, p.min_neighbors);
+    return true;
+  }
+};
+
+// This lane's sorted point of the wave's 64 into the policy; false for the lanes past the end.  *whole_wave: the wave
+// has no point at all.
+template <class Policy>
+__device__ __forceinline__ bool load_query(const SearchParams &p, Policy &pol, bool *whole_wave) {
+  const unsigned long long base_i = ((unsigned long long)blockIdx.x * kClWaves + (threadIdx.x >> 6)) * 64ull;
+  *whole_wave = base_i >= p.n;
+  pol.self = (uint32_t)base_i + (threadIdx.x & 63u);
+  pol.u[0] = pol.u[1] = pol.u[2] = pol.orig = 0;
+  if (pol.self >= p.n) return false;
+  const uint4 me = p.pts[pol.self];
+  pol.u[0] = me.x;
+  pol.u[1] = me.y;
+  pol.u[2] = me.z;
+  pol.orig = me.w;
+  return true;
+}
+
+}  // namespace
+
+// One wave per 64 sorted points, each from its start level.  See the file comment.
 template <int K>
 __global__ __launch_bounds__(kClBlock) void spz_clean_search_kernel(const SearchParams p) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const unsigned long long base_i = ((unsigned long long)blockIdx.x * kClWaves + (threadIdx.x >> 6)) * 64ull;
-  if (base_i >= p.n) return;  // the whole wave
-  const uint32_t i = (uint32_t)base_i + lane;
-  const bool valid = i < p.n;
-  uint32_t u[3] = {0, 0, 0}, orig = 0, L = 0;
-  if (valid) {
-    const uint4 me = p.pts[i];
-    u[0] = me.x;
-    u[1] = me.y;
-    u[2] = me.z;
-    orig = me.w;
-    L = p.lvl[i];
-  }
-  const double inf = __builtin_inf();
-  double t[K];
-  unsigned long long pending = __ballot(valid);
-  while (pending) {
-    const uint32_t leader = (uint32_t)__builtin_ctzll(pending);
-    const uint32_t Lg = rl(L, leader);
-    const uint32_t c0 = rl(u[0] >> Lg, leader), c1 = rl(u[1] >> Lg, leader), c2 = rl(u[2] >> Lg, leader);
-    const bool in_g = ((pending >> lane) & 1ull) && L == Lg && (u[0] >> Lg) == c0 && (u[1] >> Lg) == c1 &&
-                      (u[2] >> Lg) == c2;
-    // the block's cell ranges: lane q < 27 the first point of cell q, lane 27 + q the end
-    uint32_t bound = 0;
-    if (lane < 54u) {
-      const uint32_t q = lane % 27u;
-      int o[3];
-      block_offset(q, o);
-      const long long cells = 1ll << (24 - Lg);
-      const long long x = (long long)c0 + o[0], y = (long long)c1 + o[1], z = (long long)c2 + o[2];
-      if (x >= 0 && y >= 0 && z >= 0 && x < cells && y < cells && z < cells) {
-        bound = cell_bound(p.pts, p.n, Lg, (uint32_t)x, (uint32_t)y, (uint32_t)z, lane >= 27u);
-      }
-    }
-    const double init_lo = -inf;
-#pragma unroll
-    for (int j = 0; j < K; ++j) t[j] = (j < K - (int)p.keff) ? init_lo : inf;
-    bool stop = false;
-    for (uint32_t q = 0; q < 27u && !stop; ++q) {
-      const uint32_t s = rl(bound, q), e = rl(bound, q + 27u);
-      for (uint32_t b0 = s; b0 < e; b0 += 64u) {
-        if (!__ballot(in_g && t[K - 1] > 0.0)) {  // k zero distances everywhere: final
-          stop = true;
-          break;
-        }
-        const uint32_t cnt = min(64u, e - b0);
-        uint4 cand = make_uint4(0, 0, 0, 0);
-        if (lane < cnt) cand = p.pts[b0 + lane];
-        uint32_t lo[3], hi[3];
-        common_cell(rl(cand.x, 0), rl(cand.y, 0), rl(cand.z, 0), rl(cand.x, cnt - 1), rl(cand.y, cnt - 1),
-                    rl(cand.z, cnt - 1), lo, hi);
-        if (!__ballot(in_g && box_d2(u, lo, hi) < t[K - 1])) continue;
-        for (uint32_t c = 0; c < cnt; ++c) {
-          const double d2 = pair_d2(u, rl(cand.x, c), rl(cand.y, c), rl(cand.z, c));
-          if (in_g && d2 < t[K - 1] && b0 + c != i) topk_insert<K>(t, d2);
-        }
-      }
-    }
-    // resolved when no point outside the block can be nearer than the k-th: its gap to the block's faces
-    bool done = false;
-    if (in_g) {
-      const uint32_t last = (1u << (24 - Lg)) - 1u;
-      double g = inf;
-#pragma unroll
-      for (uint32_t a = 0; a < 3; ++a) {
-        const uint32_t c = u[a] >> Lg;
-        if (c > 1u) g = fmin(g, (double)(u[a] - ((c - 1u) << Lg) + 1u));
-        if (c + 1u < last) g = fmin(g, (double)(((unsigned long long)(c + 2u) << Lg) - u[a]));
-      }
-      done = Lg >= 24u || t[K - 1] <= g * g;
-      if (done) {
-        double sum = 0.0;
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-          if (j >= K - (int)p.keff) sum = sum + __builtin_sqrt(t[j]);  // ascending
-        }
-        p.scores[orig] = sum / (double)p.keff * p.scale;
-        if (p.kth) p.kth[orig] = (unsigned long long)t[K - 1];
-      } else {
-        L = Lg + 1u;
-      }
-    }
-    pending &= ~__ballot(in_g && done);
-  }
+  KnnPolicy<K> pol = {p};
+  bool none;
+  const bool valid = load_query(p, pol, &none);
+  if (none) return;
+  morton_walk(p.pts, p.n, threadIdx.x & 63u, valid, pol.u, valid ? (uint32_t)p.lvl[pol.self] : 0u, pol);
 }
 
 // The radius counts: every point at radius_level, counting other points with d2 <= r2 up to min_neighbors.
 __global__ __launch_bounds__(kClBlock) void spz_clean_radius_kernel(const SearchParams p) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const unsigned long long base_i = ((unsigned long long)blockIdx.x * kClWaves + (threadIdx.x >> 6)) * 64ull;
-  if (base_i >= p.n) return;
-  const uint32_t i = (uint32_t)base_i + lane;
-  const bool valid = i < p.n;
-  const uint32_t L = p.radius_level, m = p.min_neighbors;
-  uint32_t u[3] = {0, 0, 0}, orig = 0;
-  if (valid) {
-    const uint4 me = p.pts[i];
-    u[0] = me.x;
-    u[1] = me.y;
-    u[2] = me.z;
-    orig = me.w;
-  }
-  uint32_t count = 0;
-  unsigned long long pending = __ballot(valid);
-  while (pending) {
-    const uint32_t leader = (uint32_t)__builtin_ctzll(pending);
-    const uint32_t c0 = rl(u[0] >> L, leader), c1 = rl(u[1] >> L, leader), c2 = rl(u[2] >> L, leader);
-    const bool in_g = ((pending >> lane) & 1ull) && (u[0] >> L) == c0 && (u[1] >> L) == c1 && (u[2] >> L) == c2;
-    uint32_t bound = 0;
-    if (lane < 54u) {
-      const uint32_t q = lane % 27u;
-      int o[3];
-      block_offset(q, o);
-      const long long cells = 1ll << (24 - L);
-      const long long x = (long long)c0 + o[0], y = (long long)c1 + o[1], z = (long long)c2 + o[2];
-      if (x >= 0 && y >= 0 && z >= 0 && x < cells && y < cells && z < cells) {
-        bound = cell_bound(p.pts, p.n, L, (uint32_t)x, (uint32_t)y, (uint32_t)z, lane >= 27u);
-      }
-    }
-    bool stop = false;
-    for (uint32_t q = 0; q < 27u && !stop; ++q) {
-      const uint32_t s = rl(bound, q), e = rl(bound, q + 27u);
-      for (uint32_t b0 = s; b0 < e; b0 += 64u) {
-        if (!__ballot(in_g && count < m)) {  // every count saturated
-          stop = true;
-          break;
-        }
-        const uint32_t cnt = min(64u, e - b0);
-        uint4 cand = make_uint4(0, 0, 0, 0);
-        if (lane < cnt) cand = p.pts[b0 + lane];
-        uint32_t lo[3], hi[3];
-        common_cell(rl(cand.x, 0), rl(cand.y, 0), rl(cand.z, 0), rl(cand.x, cnt - 1), rl(cand.y, cnt - 1),
-                    rl(cand.z, cnt - 1), lo, hi);
-        if (!__ballot(in_g && count < m && box_d2(u, lo, hi) <= p.r2)) continue;
-        for (uint32_t c = 0; c < cnt; ++c) {
-          const double d2 = pair_d2(u, rl(cand.x, c), rl(cand.y, c), rl(cand.z, c));
-          count += (in_g && d2 <= p.r2 && b0 + c != i) ? 1u : 0u;
-        }
-      }
-    }
-    if (in_g) p.counts[orig] = min(count, m);
-    pending &= ~__ballot(in_g);
-  }
-}
-
-__device__ __forceinline__ double block_sum(double v, double *s) {
-  const uint32_t tid = threadIdx.x;
-  s[tid] = v;
-  __syncthreads();
-  for (uint32_t off = kClBlock / 2u; off > 0; off >>= 1) {
-    if (tid < off) s[tid] = s[tid] + s[tid + off];
-    __syncthreads();
-  }
-  const double r = s[0];
-  __syncthreads();
-  return r;
+  RadiusPolicy pol = {p};
+  bool none;
+  const bool valid = load_query(p, pol, &none);
+  if (none) return;
+  pol.count = 0;
+  morton_walk(p.pts, p.n, threadIdx.x & 63u, valid, pol.u, p.radius_level, pol);
 }
 
 // pass 0: the sum of the scores of each tile; pass 1: of their squared deviations from the mean.
@@ -431,32 +291,20 @@ struct ClLayout {
 ClLayout cl_layout(uint64_t n) {
   ClLayout w;
   w.tiles = (n + kClTile - 1) / kClTile;
-  uint64_t off = 0;
-  auto put = [&off](uint64_t *at, uint64_t bytes) {
-    *at = off;
-    off += Workspace::aligned(bytes);
-  };
-  put(&w.sort_ws, spz_amd_sort_workspace_bytes(n));
-  put(&w.order, n * 4u);
-  put(&w.pts, n * 16u);
-  put(&w.lvl, n);
-  put(&w.partials, (w.tiles ? w.tiles : 1) * 8u);
-  put(&w.stats, sizeof(CleanStats));
-  w.bytes = off + 256;  // room to align a caller's pointer up to 256
+  WorkspaceOffsets o;
+  o.put(&w.sort_ws, spz_amd_sort_workspace_bytes(n));
+  o.put(&w.order, n * 4u);
+  o.put(&w.pts, n * 16u);
+  o.put(&w.lvl, n);
+  o.put(&w.partials, (w.tiles ? w.tiles : 1) * 8u);
+  o.put(&w.stats, sizeof(CleanStats));
+  w.bytes = o.bytes();
   return w;
 }
 
-uint8_t *align_ws(void *d_workspace) {
-  return reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(d_workspace) + 255u) & ~uintptr_t(255));
-}
-
 int check_input(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, spz_amd_layout *lay) {
-  if (d_stream == nullptr || hdr == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
-  if (hdr->version < 1 || hdr->version > 3) return SPZ_AMD_ERR_VERSION;
-  if (hdr->sh_degree > 3) return SPZ_AMD_ERR_SH_DEGREE;
-  int rc = spz_amd_stream_layout(hdr->num_points, hdr->sh_degree, (int)hdr->version, lay);
+  const int rc = check_packed_stream(d_stream, size, hdr, lay);
   if (rc != SPZ_AMD_OK) return rc;
-  if (size < lay->total_bytes) return SPZ_AMD_ERR_SHORT_STREAM;
   if (hdr->version == 1) return SPZ_AMD_ERR_UNSUPPORTED;  // float16 positions: no integer distances
   if (hdr->num_points > SPZ_AMD_REFERENCE_MAX_POINTS) return SPZ_AMD_ERR_TOO_MANY_POINTS;
   return SPZ_AMD_OK;
@@ -468,15 +316,8 @@ bool bad_min_neighbors(uint32_t m) { return m < 1 || m > kClMaxMinNeighbors; }
 // Morton order, then the sorted positions with their input index.
 int cl_prepare(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, const spz_amd_layout &lay, uint8_t *ws,
                const ClLayout &wl, hipStream_t st) {
-  const uint32_t n = hdr->num_points;
-  if (n == 0) return SPZ_AMD_OK;
-  uint32_t *order = reinterpret_cast<uint32_t *>(ws + wl.order);
-  int rc = spz_amd_morton_order_device(d_stream, size, hdr, 0, order, ws + wl.sort_ws, st);
-  if (rc != SPZ_AMD_OK) return rc;
-  hipLaunchKernelGGL(spz_clean_gather_kernel, dim3((n + kClBlock - 1) / kClBlock), dim3(kClBlock), 0, st,
-                     d_stream + lay.offset[SPZ_AMD_SEC_POSITIONS], order, n, reinterpret_cast<uint4 *>(ws + wl.pts));
-  SPZ_HIP_TRY(hipGetLastError());
-  return SPZ_AMD_OK;
+  return morton_sorted_points(d_stream, size, hdr, lay, reinterpret_cast<uint32_t *>(ws + wl.order),
+                              reinterpret_cast<uint4 *>(ws + wl.pts), ws + wl.sort_ws, st);
 }
 
 uint32_t search_blocks(uint32_t n) { return (n + kClBlock - 1) / kClBlock; }
@@ -630,15 +471,10 @@ int spz_amd_clean_open(const uint8_t *d_stream, size_t size, const spz_amd_heade
   rc = packed_result_open(device, &c);
   if (rc != SPZ_AMD_OK) return rc;
   const ClLayout wl = cl_layout(n);
-  uint64_t off = wl.bytes;
-  auto put = [&off](uint64_t bytes) {
-    const uint64_t at = off;
-    off += Workspace::aligned(bytes);
-    return at;
-  };
-  const uint64_t o_scores = put(n * 8u), o_counts = put(n * 4u), o_mask = put(n), o_idx = put(n * 4u),
-                 o_fws = put(spz_amd_filter_workspace_bytes(n));
-  SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->block), off));
+  WorkspaceOffsets o = {wl.bytes};
+  const uint64_t o_scores = o.put(n * 8u), o_counts = o.put(n * 4u), o_mask = o.put(n), o_idx = o.put(n * 4u),
+                 o_fws = o.put(spz_amd_filter_workspace_bytes(n));
+  SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->block), o.off));
   uint8_t *ws = align_ws(c->block);
   uint8_t *raw = c->block;  // the extra sections are placed from the unaligned base (each is 256-aligned by hipMalloc)
   double *d_scores = stat ? reinterpret_cast<double *>(raw + o_scores) : nullptr;

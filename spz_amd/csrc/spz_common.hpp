@@ -181,6 +181,38 @@ class Workspace {
   bool open_ = false;
 };
 
+// A caller's workspace pointer rounded up to 256 (every *_workspace_bytes leaves room for it).
+inline uint8_t *align_ws(void *d_workspace) {
+  return reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(d_workspace) + 255u) & ~uintptr_t(255));
+}
+
+// The byte offsets of an operation's workspace sections, each 256-aligned, laid out one after the other from `off`.
+struct WorkspaceOffsets {
+  uint64_t off = 0;
+  void put(uint64_t *at, uint64_t bytes) {
+    *at = off;
+    off += Workspace::aligned(bytes);
+  }
+  uint64_t put(uint64_t bytes) {
+    uint64_t at;
+    put(&at, bytes);
+    return at;
+  }
+  uint64_t bytes() const { return off + 256; }  // with room to align a caller's pointer up to 256
+};
+
+// What every packed operation refuses first, in this order: null pointers, a version outside 1..3, a degree above 3,
+// a point count the layout refuses, a stream shorter than its layout.  The layout into *lay.
+inline int check_packed_stream(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, spz_amd_layout *lay) {
+  if (d_stream == nullptr || hdr == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
+  if (hdr->version < 1 || hdr->version > 3) return SPZ_AMD_ERR_VERSION;
+  if (hdr->sh_degree > 3) return SPZ_AMD_ERR_SH_DEGREE;
+  const int rc = spz_amd_stream_layout(hdr->num_points, hdr->sh_degree, (int)hdr->version, lay);
+  if (rc != SPZ_AMD_OK) return rc;
+  if (size < lay->total_bytes) return SPZ_AMD_ERR_SHORT_STREAM;
+  return SPZ_AMD_OK;
+}
+
 // A stream of its own for a stage: level +1 = in front of the others when both have work for the chip (the pipeline
 // whose copies the link waits for), -1 = behind them (kernels that fill idle CUs beside it), 0 = the default.
 // SPZ_AMD_STREAM_PRIORITIES=0 makes them all equal (measurements).

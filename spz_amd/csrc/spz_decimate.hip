@@ -26,6 +26,7 @@
 #include <cstring>
 
 #include "spz_amd.h"
+#include "spz_block_ops.hpp"
 #include "spz_common.hpp"
 #include "spz_kernel_params.hpp"
 #include "spz_quant.hpp"
@@ -36,7 +37,7 @@
 namespace spz_amd_detail {
 namespace {
 
-constexpr uint32_t kDecBlock = 256;
+constexpr uint32_t kDecBlock = kOpsBlock;  // 256
 constexpr uint32_t kDecItems = 8;                          // contiguous points per thread of the integer passes
 constexpr uint32_t kDecTile = kDecBlock * kDecItems;       // 2048 points per tile
 constexpr uint32_t kDecLevels = 25;                        // L = 0..24
@@ -105,21 +106,6 @@ __device__ __host__ __forceinline__ OutLayout out_layout(unsigned long long m, u
   o.sh = o.rot + 4ull * m;
   o.total = o.sh + 3ull * dim * m;
   return o;
-}
-
-__device__ __forceinline__ unsigned long long block_exclusive_scan64(unsigned long long v, unsigned long long *s) {
-  const uint32_t t = threadIdx.x;
-  s[t] = v;
-  __syncthreads();
-  for (uint32_t off = 1; off < kDecBlock; off <<= 1) {
-    const unsigned long long u = t >= off ? s[t - off] : 0ull;
-    __syncthreads();
-    s[t] += u;
-    __syncthreads();
-  }
-  const unsigned long long r = s[t] - v;
-  __syncthreads();
-  return r;
 }
 
 // ---- the per-point moments ---------------------------------------------------------------------------------------
@@ -688,39 +674,27 @@ DecLayout dec_layout(uint64_t n, int sh_degree) {
   w.wave_tiles = (n + kWaveTile - 1) / kWaveTile;
   spz_amd_layout sl;
   if (spz_amd_stream_layout(n, sh_degree, 3, &sl) != SPZ_AMD_OK) sl.total_bytes = 16 + 64 * n;
-  uint64_t off = 0;
-  auto put = [&off](uint64_t *at, uint64_t bytes) {
-    *at = off;
-    off += Workspace::aligned(bytes);
-  };
-  put(&w.sort_ws, spz_amd_sort_workspace_bytes(n));
-  put(&w.order, n * 4u);
-  put(&w.sorted, sl.total_bytes);
-  put(&w.seg, n * 4u);
-  put(&w.start, (n + 1) * 4u);
-  put(&w.nz_start, (n + 1) * 4u);
-  put(&w.tile_sums, w.tiles * 8u);
-  put(&w.hist, w.tiles * kDecLevels * 4u);
-  put(&w.counts, kDecLevels * 8u);
-  put(&w.plan, sizeof(DecPlan));
-  put(&w.head, w.wave_tiles * sizeof(MomentSlot));
-  put(&w.tail, w.wave_tiles * sizeof(MomentSlot));
-  put(&w.tail_cell, w.wave_tiles * 4u);
-  w.bytes = off + 256;  // room to align a caller's pointer up to 256
+  WorkspaceOffsets o;
+  o.put(&w.sort_ws, spz_amd_sort_workspace_bytes(n));
+  o.put(&w.order, n * 4u);
+  o.put(&w.sorted, sl.total_bytes);
+  o.put(&w.seg, n * 4u);
+  o.put(&w.start, (n + 1) * 4u);
+  o.put(&w.nz_start, (n + 1) * 4u);
+  o.put(&w.tile_sums, w.tiles * 8u);
+  o.put(&w.hist, w.tiles * kDecLevels * 4u);
+  o.put(&w.counts, kDecLevels * 8u);
+  o.put(&w.plan, sizeof(DecPlan));
+  o.put(&w.head, w.wave_tiles * sizeof(MomentSlot));
+  o.put(&w.tail, w.wave_tiles * sizeof(MomentSlot));
+  o.put(&w.tail_cell, w.wave_tiles * 4u);
+  w.bytes = o.bytes();
   return w;
 }
 
-uint8_t *align_ws(void *d_workspace) {
-  return reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(d_workspace) + 255u) & ~uintptr_t(255));
-}
-
 int check_input(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, spz_amd_layout *lay) {
-  if (d_stream == nullptr || hdr == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
-  if (hdr->version < 1 || hdr->version > 3) return SPZ_AMD_ERR_VERSION;
-  if (hdr->sh_degree > 3) return SPZ_AMD_ERR_SH_DEGREE;
-  int rc = spz_amd_stream_layout(hdr->num_points, hdr->sh_degree, (int)hdr->version, lay);
+  const int rc = check_packed_stream(d_stream, size, hdr, lay);
   if (rc != SPZ_AMD_OK) return rc;
-  if (size < lay->total_bytes) return SPZ_AMD_ERR_SHORT_STREAM;
   if (hdr->version == 1) return SPZ_AMD_ERR_UNSUPPORTED;  // float16 positions: no integer cell
   if (hdr->num_points > 0x7fffffffu) return SPZ_AMD_ERR_INVALID_ARG;
   return SPZ_AMD_OK;

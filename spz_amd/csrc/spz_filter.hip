@@ -244,22 +244,12 @@ bool sh_prefix_degree(int sh_degree, int in_degree, int *out_degree) {
   return true;
 }
 
-int check_stream(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, spz_amd_layout *lay) {
-  if (d_stream == nullptr || hdr == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
-  if (hdr->version < 1 || hdr->version > 3) return SPZ_AMD_ERR_VERSION;
-  if (hdr->sh_degree > 3) return SPZ_AMD_ERR_SH_DEGREE;
-  int rc = spz_amd_stream_layout(hdr->num_points, hdr->sh_degree, (int)hdr->version, lay);
-  if (rc != SPZ_AMD_OK) return rc;
-  if (size < lay->total_bytes) return SPZ_AMD_ERR_SHORT_STREAM;
-  return SPZ_AMD_OK;
-}
-
 int select_impl(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, const spz_amd_selection *sel,
                 const uint8_t *d_mask, uint32_t *d_indices, void *d_workspace, uint64_t *h_count, void *hip_stream) {
   if (h_count == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
   *h_count = 0;
   spz_amd_layout lay;
-  int rc = check_stream(d_stream, size, hdr, &lay);
+  int rc = check_packed_stream(d_stream, size, hdr, &lay);
   if (rc != SPZ_AMD_OK) return rc;
   SelectParams p = {};
   if (sel != nullptr) {
@@ -287,7 +277,7 @@ int select_impl(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr,
   rc = ensure_tables(device, &p.tables);
   if (rc != SPZ_AMD_OK) return rc;
   const WorkspaceLayout wl = workspace_layout(n);
-  uint8_t *ws = reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(d_workspace) + 255u) & ~uintptr_t(255));
+  uint8_t *ws = align_ws(d_workspace);
   p.positions = d_stream + lay.offset[SPZ_AMD_SEC_POSITIONS];
   p.alphas = d_stream + lay.offset[SPZ_AMD_SEC_ALPHAS];
   p.mask = d_mask;
@@ -317,7 +307,7 @@ int select_impl(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr,
 int subset_impl(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, const uint32_t *d_indices,
                 uint64_t count, int sh_degree, uint8_t *d_out, size_t capacity, void *hip_stream) {
   spz_amd_layout in;
-  int rc = check_stream(d_stream, size, hdr, &in);
+  int rc = check_packed_stream(d_stream, size, hdr, &in);
   if (rc != SPZ_AMD_OK) return rc;
   int out_degree = 0;
   if (!sh_prefix_degree(sh_degree, hdr->sh_degree, &out_degree)) return SPZ_AMD_ERR_INVALID_ARG;
@@ -402,7 +392,7 @@ int spz_amd_filter_open(const uint8_t *d_stream, size_t size, const spz_amd_head
   *h_count = 0;
   *h_out_bytes = 0;
   spz_amd_layout in;
-  int rc = check_stream(d_stream, size, hdr, &in);
+  int rc = check_packed_stream(d_stream, size, hdr, &in);
   if (rc != SPZ_AMD_OK) return rc;
   int out_degree = 0;
   if (!sh_prefix_degree(sh_degree, hdr->sh_degree, &out_degree)) return SPZ_AMD_ERR_INVALID_ARG;

@@ -262,10 +262,6 @@ int compare_input_ok(const uint8_t *d_stream, size_t size, const spz_amd_header 
   return size < lay.total_bytes ? SPZ_AMD_ERR_SHORT_STREAM : SPZ_AMD_OK;
 }
 
-uint8_t *align256(void *p) {
-  return reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(p) + 255u) & ~uintptr_t(255));
-}
-
 // The device blocks of one compare call, grow-only, freed (after the stream) when it returns.
 struct CompareBlocks {
   hipStream_t st = nullptr;
@@ -326,7 +322,7 @@ int compare_render(CompareBlocks *k, const uint8_t *d_stream, size_t size, const
     uint8_t *bigger = nullptr;
     SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&bigger), need));
     const hipError_t e =
-        hipMemcpyAsync(align256(bigger), align256(k->ws), ws0 - 256u, hipMemcpyDeviceToDevice, k->st);
+        hipMemcpyAsync(align_ws(bigger), align_ws(k->ws), ws0 - 256u, hipMemcpyDeviceToDevice, k->st);
     if (e == hipSuccess) (void)hipStreamSynchronize(k->st);
     if (e != hipSuccess) {
       (void)hipFree(bigger);

@@ -58,13 +58,6 @@ __global__ __launch_bounds__(kPrBlock) void spz_prune_threshold_kernel(const uns
   mask[i] = v >= s ? 1u : 0u;
 }
 
-namespace {
-
-uint8_t *align256(void *p) {
-  return reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(p) + 255u) & ~uintptr_t(255));
-}
-
-}  // namespace
 }  // namespace spz_amd_detail
 
 using namespace spz_amd_detail;
@@ -128,15 +121,11 @@ int spz_amd_prune_open(const uint8_t *d_stream, size_t size, const spz_amd_heade
   rc = packed_result_open(device, &c);
   if (rc != SPZ_AMD_OK) return rc;
   const SortLayout sl = sort_layout(n);
-  uint64_t off = 0;
-  auto put = [&off](uint64_t bytes) {
-    const uint64_t at = off;
-    off += Workspace::aligned(bytes);
-    return at;
-  };
-  const uint64_t o_sum = put(n * 8u), o_max = put(n * 4u), o_small = put(16u), o_mask = put(n), o_idx = put(n * 4u),
-                 o_order = put(n * 4u), o_sort = put(n ? sl.bytes : 0u), o_fws = put(spz_amd_filter_workspace_bytes(n));
-  SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->block), off));
+  WorkspaceOffsets o;
+  const uint64_t o_sum = o.put(n * 8u), o_max = o.put(n * 4u), o_small = o.put(16u), o_mask = o.put(n),
+                 o_idx = o.put(n * 4u), o_order = o.put(n * 4u), o_sort = o.put(n ? sl.bytes : 0u),
+                 o_fws = o.put(spz_amd_filter_workspace_bytes(n));
+  SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->block), o.off));
   uint8_t *raw = c->block;  // every section is 256-aligned from hipMalloc's base
   auto *d_sum = reinterpret_cast<uint64_t *>(raw + o_sum);
   auto *d_max = reinterpret_cast<float *>(raw + o_max);
@@ -175,7 +164,7 @@ int spz_amd_prune_open(const uint8_t *d_stream, size_t size, const spz_amd_heade
       uint8_t *bigger = nullptr;
       SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&bigger), need));
       if (prefix) {
-        const hipError_t e = hipMemcpyAsync(align256(bigger), align256(c->scratch), prefix, hipMemcpyDeviceToDevice, c->st);
+        const hipError_t e = hipMemcpyAsync(align_ws(bigger), align_ws(c->scratch), prefix, hipMemcpyDeviceToDevice, c->st);
         if (e == hipSuccess) (void)hipStreamSynchronize(c->st);
         if (e != hipSuccess) {
           (void)hipFree(bigger);
@@ -207,7 +196,7 @@ int spz_amd_prune_open(const uint8_t *d_stream, size_t size, const spz_amd_heade
     } else if (keep == 0 || keep == n) {
       SPZ_HIP_TRY(hipMemsetAsync(d_mask, keep ? 1 : 0, n, c->st));
     } else {
-      uint8_t *sws = align256(raw + o_sort);
+      uint8_t *sws = align_ws(raw + o_sort);
       auto *k0 = reinterpret_cast<uint32_t *>(sws + sl.planes_off[0][0]);
       auto *k1 = reinterpret_cast<uint32_t *>(sws + sl.planes_off[0][1]);
       hipLaunchKernelGGL(spz_prune_key_kernel, dim3(blocks), dim3(kPrBlock), 0, c->st,

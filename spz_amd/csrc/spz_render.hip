@@ -666,10 +666,6 @@ RenderLayout render_layout(uint64_t n, uint64_t m) {
   return w;
 }
 
-uint8_t *align256(void *p) {
-  return reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(p) + 255u) & ~uintptr_t(255));
-}
-
 bool finite3(const float *v, int k) {
   for (int i = 0; i < k; ++i) {
     if (!std::isfinite(v[i])) return false;
@@ -845,13 +841,9 @@ int score_impl(uint64_t n, const spz_amd_render_params *params, uint64_t m, floa
 }
 
 int packed_source(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, int coord, PackedSrc *src) {
-  if (d_stream == nullptr || hdr == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
-  if (hdr->version < 1 || hdr->version > 3) return SPZ_AMD_ERR_VERSION;
-  if (hdr->sh_degree > 3) return SPZ_AMD_ERR_SH_DEGREE;
   spz_amd_layout lay;
-  int rc = spz_amd_stream_layout(hdr->num_points, hdr->sh_degree, (int)hdr->version, &lay);
+  const int rc = check_packed_stream(d_stream, size, hdr, &lay);
   if (rc != SPZ_AMD_OK) return rc;
-  if (size < lay.total_bytes) return SPZ_AMD_ERR_SHORT_STREAM;
   if (hdr->num_points > kMaxEntries) return SPZ_AMD_ERR_TOO_MANY_POINTS;
   *src = PackedSrc{};
   src->positions = d_stream + lay.offset[SPZ_AMD_SEC_POSITIONS];
@@ -906,7 +898,7 @@ int render_host_impl(uint64_t n, const spz_amd_render_params *params, int device
   const RenderLayout wp = render_layout(n, 0);
   const uint64_t small = 256;  // total (8) + status (4)
   SPZ_HIP_TRY(hipMalloc(&k.a, wp.bytes + small + al(upload_bytes)));
-  uint8_t *base = align256(k.a);
+  uint8_t *base = align_ws(k.a);
   uint8_t *tail = base + wp.prefix;
   auto *d_total = reinterpret_cast<uint64_t *>(tail);
   auto *d_status = reinterpret_cast<uint32_t *>(tail + 8);
@@ -922,7 +914,7 @@ int render_host_impl(uint64_t n, const spz_amd_render_params *params, int device
   const RenderLayout wf = render_layout(n, total);
   const uint64_t image_bytes = (uint64_t)params->width * params->height * 16u;
   SPZ_HIP_TRY(hipMalloc(&k.b, wf.entries + al(image_bytes) + 256));
-  uint8_t *ent = align256(k.b);
+  uint8_t *ent = align_ws(k.b);
   float *d_image = reinterpret_cast<float *>(ent + wf.entries);
   const auto t1 = std::chrono::steady_clock::now();
   rc = entries_impl(n, params, total, d_status, base, ent, k.st);
@@ -970,7 +962,7 @@ int spz_amd_render_prepare_packed_device(const uint8_t *d_stream, size_t size, c
   rc = ensure_tables(device, &src.tables);
   if (rc != SPZ_AMD_OK) return rc;
   return prepare_impl(src, hdr->num_points, hdr->sh_degree, hdr->flags & 1, params, d_total, d_records,
-                      align256(d_workspace), static_cast<hipStream_t>(hip_stream));
+                      align_ws(d_workspace), static_cast<hipStream_t>(hip_stream));
 }
 
 int spz_amd_render_prepare_cloud_device(const spz_amd_cloud_in *d_cloud, uint64_t num_points, int sh_degree,
@@ -985,7 +977,7 @@ int spz_amd_render_prepare_cloud_device(const spz_amd_cloud_in *d_cloud, uint64_
   int device = 0;
   rc = current_device(&device);
   if (rc != SPZ_AMD_OK) return rc;
-  return prepare_impl(src, num_points, sh_degree, antialiased, params, d_total, d_records, align256(d_workspace),
+  return prepare_impl(src, num_points, sh_degree, antialiased, params, d_total, d_records, align_ws(d_workspace),
                       static_cast<hipStream_t>(hip_stream));
 }
 
@@ -999,7 +991,7 @@ int spz_amd_render_finish_device(uint64_t num_points, const spz_amd_render_param
   rc = current_device(&device);
   if (rc != SPZ_AMD_OK) return rc;
   const hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  uint8_t *base = align256(d_workspace);
+  uint8_t *base = align_ws(d_workspace);
   uint8_t *ent = base + render_layout(num_points, 0).prefix;
   rc = entries_impl(num_points, params, max_entries, d_status, base, ent, st);
   if (rc != SPZ_AMD_OK) return rc;
@@ -1018,7 +1010,7 @@ int spz_amd_render_score_device(uint64_t num_points, const spz_amd_render_params
   rc = current_device(&device);
   if (rc != SPZ_AMD_OK) return rc;
   const hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  uint8_t *base = align256(d_workspace);
+  uint8_t *base = align_ws(d_workspace);
   uint8_t *ent = base + render_layout(num_points, 0).prefix;
   rc = entries_impl(num_points, params, max_entries, d_status, base, ent, st);
   if (rc != SPZ_AMD_OK) return rc;

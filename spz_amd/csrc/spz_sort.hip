@@ -10,6 +10,8 @@
 //   spz_radix_scatter_kernel  stable in-tile rank (wave64 __ballot match masks + a prefix over (round, wave) in LDS),
 //                             the tile staged in LDS in digit order, then each digit's run written contiguously at
 //                             digit base + tile offset.  Reduce-then-scan: no inter-workgroup flags, no global atomics.
+//   spz_morton_gather_kernel  the positions in an order: sorted (u_x, u_y, u_z, input index), 16 B per point, for the
+//                             neighbour searches (spz_morton_walk.hpp).
 //   spz_chunk_bounds_kernel   one wave per run of `chunk` points: min / max of the sign-extended stored integers.
 #include <hip/hip_runtime.h>
 
@@ -20,6 +22,7 @@
 
 #include "spz_amd.h"
 #include "spz_common.hpp"
+#include "spz_morton_walk.hpp"
 #include "spz_sort_internal.hpp"
 
 namespace spz_amd_detail {
@@ -116,6 +119,14 @@ __global__ __launch_bounds__(kSortBlock) void spz_morton_key_kernel(const uint8_
   k0[i] = w0;
   k1[i] = w1;
   k2[i] = w2;
+}
+
+__global__ __launch_bounds__(kSortBlock) void spz_morton_gather_kernel(const uint8_t *pos, const uint32_t *order,
+                                                                       uint32_t n, uint4 *pts) {
+  const unsigned long long i = (unsigned long long)blockIdx.x * kSortBlock + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t s = order[i];
+  pts[i] = make_uint4(load_u(pos, s, 0), load_u(pos, s, 1), load_u(pos, s, 2), s);
 }
 
 __global__ __launch_bounds__(kSortBlock) void spz_float_key_kernel(const float *keys, uint32_t n, uint32_t descending,
@@ -370,24 +381,10 @@ namespace {
 
 using namespace spz_amd_detail;
 
-int check_stream(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, spz_amd_layout *lay) {
-  if (d_stream == nullptr || hdr == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
-  if (hdr->version < 1 || hdr->version > 3) return SPZ_AMD_ERR_VERSION;
-  if (hdr->sh_degree > 3) return SPZ_AMD_ERR_SH_DEGREE;
-  int rc = spz_amd_stream_layout(hdr->num_points, hdr->sh_degree, (int)hdr->version, lay);
-  if (rc != SPZ_AMD_OK) return rc;
-  if (size < lay->total_bytes) return SPZ_AMD_ERR_SHORT_STREAM;
-  return SPZ_AMD_OK;
-}
-
-uint8_t *align_ws(void *d_workspace) {
-  return reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(d_workspace) + 255u) & ~uintptr_t(255));
-}
-
 int morton_impl(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, int descending, uint32_t *d_order,
                 void *d_workspace, hipStream_t st) {
   spz_amd_layout lay;
-  int rc = check_stream(d_stream, size, hdr, &lay);
+  int rc = check_packed_stream(d_stream, size, hdr, &lay);
   if (rc != SPZ_AMD_OK) return rc;
   if (hdr->version == 1) return SPZ_AMD_ERR_UNSUPPORTED;  // float16 positions: no stored integers
   const uint64_t n = hdr->num_points;
@@ -426,6 +423,22 @@ int argsort_impl(const float *d_keys, uint64_t n, int descending, uint32_t *d_or
 
 }  // namespace
 
+namespace spz_amd_detail {
+
+int morton_sorted_points(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, const spz_amd_layout &lay,
+                         uint32_t *d_order, uint4 *d_pts, void *d_sort_ws, hipStream_t st) {
+  const uint32_t n = hdr->num_points;
+  if (n == 0) return SPZ_AMD_OK;
+  const int rc = morton_impl(d_stream, size, hdr, 0, d_order, d_sort_ws, st);
+  if (rc != SPZ_AMD_OK) return rc;
+  hipLaunchKernelGGL(spz_morton_gather_kernel, dim3((n + kSortBlock - 1) / kSortBlock), dim3(kSortBlock), 0, st,
+                     d_stream + lay.offset[SPZ_AMD_SEC_POSITIONS], d_order, n, d_pts);
+  SPZ_HIP_TRY(hipGetLastError());
+  return SPZ_AMD_OK;
+}
+
+}  // namespace spz_amd_detail
+
 extern "C" {
 
 uint64_t spz_amd_sort_workspace_bytes(uint64_t n) { return sort_layout(n).bytes; }
@@ -443,7 +456,7 @@ int spz_amd_argsort_f32_device(const float *d_keys, uint64_t n, int descending, 
 int spz_amd_chunk_bounds_device(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, uint32_t chunk,
                                 float *d_bounds, void *hip_stream) {
   spz_amd_layout lay;
-  int rc = check_stream(d_stream, size, hdr, &lay);
+  int rc = check_packed_stream(d_stream, size, hdr, &lay);
   if (rc != SPZ_AMD_OK) return rc;
   if (hdr->version == 1) return SPZ_AMD_ERR_UNSUPPORTED;
   if (chunk == 0) return SPZ_AMD_ERR_INVALID_ARG;
@@ -470,7 +483,7 @@ int spz_amd_sort_open(const uint8_t *d_stream, size_t size, const spz_amd_header
   *ctx = nullptr;
   *h_out_bytes = 0;
   spz_amd_layout in;
-  int rc = check_stream(d_stream, size, hdr, &in);
+  int rc = check_packed_stream(d_stream, size, hdr, &in);
   if (rc != SPZ_AMD_OK) return rc;
   if (h_keys == nullptr && hdr->version == 1) return SPZ_AMD_ERR_UNSUPPORTED;
   const uint64_t n = hdr->num_points;

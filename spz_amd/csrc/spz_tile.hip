@@ -33,12 +33,13 @@
 #include <vector>
 
 #include "spz_amd.h"
+#include "spz_block_ops.hpp"
 #include "spz_common.hpp"
 
 namespace spz_amd_detail {
 namespace {
 
-constexpr uint32_t kBlock = 256;
+constexpr uint32_t kBlock = kOpsBlock;  // 256
 constexpr uint32_t kScanItems = 8;
 constexpr uint32_t kScanTile = kBlock * kScanItems;   // positions per workgroup of the id scan
 constexpr uint32_t kHistRun = 1024;                   // positions per row of the dd histogram
@@ -143,21 +144,6 @@ __device__ __forceinline__ uint32_t block_exclusive_scan32(uint32_t v, uint32_t 
     __syncthreads();
   }
   const uint32_t r = s[t] - v;
-  __syncthreads();
-  return r;
-}
-
-__device__ __forceinline__ unsigned long long block_exclusive_scan64(unsigned long long v, unsigned long long *s) {
-  const uint32_t t = threadIdx.x;
-  s[t] = v;
-  __syncthreads();
-  for (uint32_t off = 1; off < kBlock; off <<= 1) {
-    const unsigned long long u = t >= off ? s[t - off] : 0ull;
-    __syncthreads();
-    s[t] += u;
-    __syncthreads();
-  }
-  const unsigned long long r = s[t] - v;
   __syncthreads();
   return r;
 }
@@ -739,43 +725,31 @@ TileLayout tile_layout(uint64_t n, int sh_degree, uint64_t max_tiles) {
   w.table_rows = table_rows_for(n, max_tiles);
   spz_amd_layout sl;
   if (spz_amd_stream_layout(n, sh_degree, 3, &sl) != SPZ_AMD_OK) sl.total_bytes = 16 + 64 * n;
-  uint64_t off = 0;
-  auto put = [&off](uint64_t *at, uint64_t bytes) {
-    *at = off;
-    off += Workspace::aligned(bytes);
-  };
-  put(&w.sort_ws, spz_amd_sort_workspace_bytes(n));
-  put(&w.order, n * 4u);
-  put(&w.sorted, sl.total_bytes);
+  WorkspaceOffsets o;
+  o.put(&w.sort_ws, spz_amd_sort_workspace_bytes(n));
+  o.put(&w.order, n * 4u);
+  o.put(&w.sorted, sl.total_bytes);
   uint64_t size = n ? n : 1;
   w.pyr_levels = 0;
   for (;;) {
     w.pyr_size[w.pyr_levels] = (uint32_t)size;
-    put(&w.dd[w.pyr_levels], size);
+    o.put(&w.dd[w.pyr_levels], size);
     ++w.pyr_levels;
     if (size <= 64 || w.pyr_levels == kPyrMax) break;
     size = (size + 63) / 64;
   }
-  put(&w.mask, n * 4u);
-  put(&w.toff, n * 4u);
-  put(&w.sums, (w.scan_tiles + 1) * 4u);
-  put(&w.rows, (w.hist_runs + 1) * kLevels * 4u);
-  put(&w.prefix, (w.table_rows + 1) * 4u);
-  w.bytes = off + 256;  // room to align a caller's pointer up to 256
+  o.put(&w.mask, n * 4u);
+  o.put(&w.toff, n * 4u);
+  o.put(&w.sums, (w.scan_tiles + 1) * 4u);
+  o.put(&w.rows, (w.hist_runs + 1) * kLevels * 4u);
+  o.put(&w.prefix, (w.table_rows + 1) * 4u);
+  w.bytes = o.bytes();
   return w;
 }
 
-uint8_t *align_ws(void *d_workspace) {
-  return reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(d_workspace) + 255u) & ~uintptr_t(255));
-}
-
 int check_input(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, spz_amd_layout *lay) {
-  if (d_stream == nullptr || hdr == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
-  if (hdr->version < 1 || hdr->version > 3) return SPZ_AMD_ERR_VERSION;
-  if (hdr->sh_degree > 3) return SPZ_AMD_ERR_SH_DEGREE;
-  int rc = spz_amd_stream_layout(hdr->num_points, hdr->sh_degree, (int)hdr->version, lay);
+  const int rc = check_packed_stream(d_stream, size, hdr, lay);
   if (rc != SPZ_AMD_OK) return rc;
-  if (size < lay->total_bytes) return SPZ_AMD_ERR_SHORT_STREAM;
   if (hdr->version == 1) return SPZ_AMD_ERR_UNSUPPORTED;  // float16 positions: no integer cell
   if (hdr->num_points > SPZ_AMD_REFERENCE_MAX_POINTS) return SPZ_AMD_ERR_TOO_MANY_POINTS;
   return SPZ_AMD_OK;

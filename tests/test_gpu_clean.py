@@ -155,6 +155,38 @@ def test_resident_forms_determinism_and_the_file_form(spz, tmp_path, cuda):
     assert out.cpu().numpy().tobytes() == zlib.decompress(got, 31)
 
 
+def walk_cloud(seed=33):
+    """4097 stored position fields whose nearest-neighbour distances span several octree levels: a dense and a loose
+    cluster, uniform points over the whole cube and four points repeated fifty times each; shuffled."""
+    rng = np.random.default_rng(seed)
+    dense = 0x800000 + rng.integers(0, 1 << 10, (1500, 3))
+    loose = 0x300000 + rng.integers(0, 1 << 16, (1400, 3))
+    spread = rng.integers(0, 1 << 24, (997, 3))
+    fields = np.concatenate([dense, loose, spread, np.repeat(dense[:4], 50, axis=0)])
+    return fields[rng.permutation(fields.shape[0])]
+
+
+def test_radius_counts_agree_with_the_nearest_neighbour(cuda):
+    """The two searches of the shared walk against each other: a point has a neighbour within the radius exactly where
+    its nearest neighbour's squared distance is <= R2.  The radius is the median nearest-neighbour distance of the CPU
+    reference, so both outcomes are common."""
+    import torch
+    from spz_amd import abi, device as D
+    raw = stream_of(walk_cloud(), deg=0, seed=33)
+    assert parse_stream(raw)["num_points"] == 4097
+    nearest = knn_d2(stored_positions(raw), 1)[:, -1]
+    radius = float(np.sqrt(np.median(nearest))) * 2.0 ** -12
+    r2 = C.c_uint64(0)
+    assert abi.load_library().spz_amd_clean_radius_r2(radius, 12, C.byref(r2)) == 0
+    st, hdr = on_device(raw)
+    _, kth = D.knn_scores(st, hdr, 1)
+    counts = D.radius_counts(st, hdr, radius, 1)
+    torch.cuda.synchronize()
+    within = kth.cpu().numpy() <= r2.value
+    assert np.array_equal(counts.cpu().numpy() >= 1, within)
+    assert 0.1 <= within.mean() <= 0.9, "each outcome for at least a tenth of the points"
+
+
 def test_c_abi_host_form(cuda):
     import torch
     from spz_amd import abi

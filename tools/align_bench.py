@@ -93,7 +93,7 @@ def cpu_route(spz, src, tgt, steps):
     return rmse
 
 
-PREFIXES = ("spz_align_", "spz_clean_search", "spz_clean_level", "spz_clean_gather", "spz_morton", "spz_radix")
+PREFIXES = ("spz_align_", "spz_clean_search", "spz_clean_level", "spz_morton", "spz_radix")
 
 
 def trace_rows(path):

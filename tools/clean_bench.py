@@ -92,8 +92,8 @@ def bench_cloud(spz, label, cloud, deg, reps, tmp, skip_cpu=False):
 
 
 PREFIXES = ("spz_clean_", "spz_morton", "spz_radix", "spz_subset", "spz_select", "spz_compact")
-STAGES = (("sort (Morton key + 9 radix passes)", ("spz_morton", "spz_radix")),
-          ("gather + start levels", ("spz_clean_gather", "spz_clean_level")),
+STAGES = (("sort (Morton key + 9 radix passes)", ("spz_morton_key", "spz_radix")),
+          ("gather + start levels", ("spz_morton_gather", "spz_clean_level")),
           ("k-NN search", ("spz_clean_search",)), ("radius search", ("spz_clean_radius",)),
           ("threshold + mask", ("spz_clean_sum", "spz_clean_stats", "spz_clean_mask")),
           ("select + subset", ("spz_select", "spz_compact", "spz_subset")))
