@@ -817,6 +817,36 @@ int spz_amd_prune_fetch(void *ctx, uint8_t *h_out);
 const uint8_t *spz_amd_prune_device_data(void *ctx);
 void spz_amd_prune_close(void *ctx);
 
+/* ---- render depth: expected depth, median depth and the median Gaussian of one view (spz_render.hip; DESIGN §8
+ *      "Render").  The reference has no counterpart.  With the workspace of a prepare step (as for
+ *      render_finish_device), the blend of the render contract runs again, pixel for pixel: the same skips, the same
+ *      stop, the same f32 operations in the same order.  For every pair the blend USES (as "render scores" defines it),
+ *      with z the record's f32 depth and g the Gaussian's input index, D = 0 at first:
+ *        D = D + (T a) z in f32: w = T a, then w z, then the add, not contracted;
+ *        after T' = T (1 - a): when no median has been taken and T' < 0.5f, median depth = z and median index = g.
+ *      d_depth: height x width x 2 f32.  Channel 0 = D, un-normalised (0 where nothing was blended); channel 1 = the
+ *      median depth, +inf when T never fell below 0.5.  d_index (may be NULL): height x width u32, the median
+ *      Gaussian's input index, 0xffffffff without a median.  d_image (may be NULL): the image, bit-identical to
+ *      render_finish_device's.  The normalised expected depth is D / alpha in f32 where alpha = 1 - T > 0, +inf
+ *      elsewhere: the layers above derive it, the kernel does not.  No atomics: a run repeats its bits, and a stream and
+ *      its decoded floats give the same bits.
+ *      render_depth_device: the entries, their sort and ranges as render_finish_device, then the depth blend.
+ *      *d_status = 0, or 1 when the total is above max_entries: then nothing is written to the three outputs.  A NULL
+ *      d_depth, d_status or d_workspace or bad params: SPZ_AMD_ERR_INVALID_ARG; max_entries above 2^31 - 1:
+ *      SPZ_AMD_ERR_CAPACITY; both before anything is launched.  Enqueue only; no synchronisation.
+ *      render_depth_host / render_depth_cloud_host: as render_host / render_cloud_host.  h_rgba (may be NULL): height x
+ *      width x 4 floats; h_depth: height x width x 2 floats; h_index (may be NULL): height x width u32; h_ms[2]: the
+ *      depth blend.  A total above 2^31 - 1: SPZ_AMD_ERR_CAPACITY. */
+int spz_amd_render_depth_device(uint64_t num_points, const spz_amd_render_params *params, uint64_t max_entries,
+                                float *d_image, float *d_depth, uint32_t *d_index, uint32_t *d_status,
+                                void *d_workspace, void *hip_stream);
+int spz_amd_render_depth_host(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr,
+                              const spz_amd_render_params *params, int device, float *h_rgba, float *h_depth,
+                              uint32_t *h_index, uint64_t *h_entries, float *h_ms);
+int spz_amd_render_depth_cloud_host(const spz_amd_cloud_in *h_cloud, uint64_t num_points, int sh_degree,
+                                    int antialiased, const spz_amd_render_params *params, int device, float *h_rgba,
+                                    float *h_depth, uint32_t *h_index, uint64_t *h_entries, float *h_ms);
+
 /* ---- image metrics: PSNR, MSE, L1, max error and SSIM of two images (spz_metrics.hip; DESIGN §8 "Compare").  The
  *      reference has no counterpart.  The convention of the 3DGS evaluation code (Kerbl et al. 2023, loss_utils.ssim and
  *      image_utils.psnr), so the numbers compare with published tables.

@@ -456,6 +456,21 @@ bool renderSpz(const uint8_t *data, int32_t size, const RenderOptions &options, 
                int64_t *entries = nullptr);
 bool renderCloud(const GaussianCloud &g, const RenderOptions &options, std::vector<float> *rgba,
                  int64_t *entries = nullptr);
+// Depth maps (DESIGN §8 "Render"; include/spz_amd.h "render depth" states the contract): the view of renderSpz again,
+// with per pixel the blend's depth sum `accumulated` = sum (T a) z, `alpha` = 1 - T, `expected` = accumulated / alpha in
+// f32 (+inf where alpha == 0), `median` = the depth of the first Gaussian after which T < 0.5 (+inf: none) and `index`
+// = that Gaussian's input index (0xffffffff: none), each height x width, row-major.  *rgba (may be NULL): the image,
+// bit-identical to renderSpz's.  Errors as renderSpz's, the line naming renderSpzDepth.
+struct DepthMaps {
+  std::vector<float> expected, median, accumulated, alpha;
+  std::vector<uint32_t> index;
+};
+bool renderSpzDepth(const std::string &filename, const RenderOptions &options, DepthMaps *maps,
+                    std::vector<float> *rgba = nullptr, int64_t *entries = nullptr);
+bool renderSpzDepth(const uint8_t *data, int32_t size, const RenderOptions &options, DepthMaps *maps,
+                    std::vector<float> *rgba = nullptr, int64_t *entries = nullptr);
+bool renderCloudDepth(const GaussianCloud &g, const RenderOptions &options, DepthMaps *maps,
+                      std::vector<float> *rgba = nullptr, int64_t *entries = nullptr);
 // The worldToCamera of a camera at `eye` looking at `target`: z = normalize(target - eye), x = normalize(z x up),
 // y = z x x, so that `up` maps to -y (up on the screen).  std::invalid_argument when eye == target, up is zero or
 // parallel to the view direction, or a value is not finite.

@@ -84,6 +84,7 @@ EXPORTS = (
     "spz_amd_render_prepare_cloud_device", "spz_amd_render_finish_device", "spz_amd_render_host",
     "spz_amd_render_cloud_host", "spz_amd_render_score_device", "spz_amd_prune_keep_count", "spz_amd_prune_open",
     "spz_amd_prune_fetch", "spz_amd_prune_device_data", "spz_amd_prune_close",
+    "spz_amd_render_depth_device", "spz_amd_render_depth_host", "spz_amd_render_depth_cloud_host",
     "spz_amd_image_metrics_check", "spz_amd_image_metrics_workspace_bytes", "spz_amd_image_metrics_device",
     "spz_amd_image_metrics_host", "spz_amd_compare_host",
 )
@@ -538,6 +539,14 @@ def bind(L):
                                             C.POINTER(u64), vp]
     L.spz_amd_render_score_device.restype = i32
     L.spz_amd_render_score_device.argtypes = [u64, C.POINTER(RenderParams), u64, vp, vp, vp, vp, vp, vp]
+    L.spz_amd_render_depth_device.restype = i32
+    L.spz_amd_render_depth_device.argtypes = [u64, C.POINTER(RenderParams), u64, vp, vp, vp, vp, vp, vp]
+    L.spz_amd_render_depth_host.restype = i32
+    L.spz_amd_render_depth_host.argtypes = [vp, sz, C.POINTER(Header), C.POINTER(RenderParams), i32, vp, vp, vp,
+                                            C.POINTER(u64), vp]
+    L.spz_amd_render_depth_cloud_host.restype = i32
+    L.spz_amd_render_depth_cloud_host.argtypes = [C.POINTER(CloudPtrs), u64, i32, i32, C.POINTER(RenderParams), i32, vp,
+                                                  vp, vp, C.POINTER(u64), vp]
     L.spz_amd_prune_keep_count.restype = i32
     L.spz_amd_prune_keep_count.argtypes = [u64, i32, C.c_double, C.POINTER(u64)]
     L.spz_amd_prune_open.restype = i32

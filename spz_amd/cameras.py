@@ -1,4 +1,5 @@
-"""Readers of camera sets for prune_spz (DESIGN §8 "Prune"): plain Python, no device work."""
+"""Readers of camera sets for prune_spz (DESIGN §8 "Prune") and the back-projection of depth maps (DESIGN §8 "Render"):
+plain Python, no device work."""
 import json
 
 import numpy as np
@@ -32,3 +33,22 @@ def load_3dgs_cameras(path):
         views.append({"world_to_camera": m, "fx": float(e["fx"]), "fy": float(e["fy"]), "cx": width / 2.0,
                       "cy": height / 2.0, "width": width, "height": height})
     return views
+
+
+def unproject_depth(depth, world_to_camera, fx, fy, cx, cy):
+    """The world points of a depth map (render_depth_spz's expected or median): (K, 3) float64, one per finite pixel in
+    row-major order, in the frame of world_to_camera (the render's `coord` frame).
+
+    depth: (height, width), the camera-space z of each pixel.  Pixel (u, v) is centred at (u + 0.5, v + 0.5), as in the
+    render contract, so its ray is ((u + 0.5 - cx) / fx, (v + 0.5 - cy) / fy, 1) and the point is R^T (z ray - t).
+    ValueError when depth is not two-dimensional or world_to_camera is not 3x4."""
+    d = np.asarray(depth, dtype=np.float64)
+    m = np.asarray(world_to_camera, dtype=np.float64)
+    if d.ndim != 2:
+        raise ValueError(f"depth must be (height, width), got shape {d.shape}")
+    if m.shape != (3, 4):
+        raise ValueError(f"world_to_camera must be 3x4, got shape {m.shape}")
+    v, u = np.nonzero(np.isfinite(d))
+    z = d[v, u]
+    cam = np.stack([(u + 0.5 - cx) / fx * z, (v + 0.5 - cy) / fy * z, z], axis=1)
+    return (cam - m[:, 3]) @ m[:, :3]

@@ -334,7 +334,11 @@ int spzClean(int argc, char **argv) {
 const char *kRenderUsage =
     "Usage: spz_render <in.spz> <out.ppm|out.pfm> --size W H (--fov-y DEG | --intrinsics fx fy cx cy) --eye x y z "
     "--target x y z [--up x y z] [--coord " SPZ_COORD_NAMES "] [--background r g b] "
-    "[--sh-degree D] [--near N]";
+    "[--sh-degree D] [--near N] [--depth FILE.pfm [--depth-kind expected|median]] [--ids FILE.bin] [--pick X Y]...\n"
+    "  --depth  the depth map as a one-channel PFM (rows bottom to top; +inf where there is none): expected = the blend's\n"
+    "           depth sum over alpha, median = the depth at which the transmittance falls below 0.5\n"
+    "  --ids    the median splat's index per pixel: raw little-endian uint32, rows top to bottom, 4294967295 for none\n"
+    "  --pick   print `index depth` of the median splat at pixel X Y, or `none` (one line per --pick, in order)";
 
 bool endsWith(const std::string &s, const char *suffix) {
   const size_t n = std::strlen(suffix);
@@ -371,6 +375,25 @@ bool writeImage(const std::string &path, const std::vector<float> &rgba, int w, 
   return static_cast<bool>(out);
 }
 
+// One-channel PFM ("Pf"): little-endian floats, rows bottom to top, non-finite values kept.
+bool writeDepthPfm(const std::string &path, const std::vector<float> &depth, int w, int h) {
+  std::ofstream out(path, std::ios::binary);
+  if (!out) return false;
+  out << "Pf\n" << w << " " << h << "\n-1.0\n";
+  for (int y = h - 1; y >= 0; --y) {
+    out.write(reinterpret_cast<const char *>(depth.data() + static_cast<size_t>(y) * w),
+              static_cast<std::streamsize>(static_cast<size_t>(w) * sizeof(float)));
+  }
+  return static_cast<bool>(out);
+}
+
+bool writeIds(const std::string &path, const std::vector<uint32_t> &index) {
+  std::ofstream out(path, std::ios::binary);
+  if (!out) return false;
+  out.write(reinterpret_cast<const char *>(index.data()), static_cast<std::streamsize>(index.size() * sizeof(uint32_t)));
+  return static_cast<bool>(out);
+}
+
 int spzRender(int argc, char **argv) {
   Args a(argc, argv, kRenderUsage);
   if (!a.files()) return a.usage();
@@ -381,9 +404,17 @@ int spzRender(int argc, char **argv) {
   int size[2] = {0, 0};
   float fovY = 0.0f, intr[4] = {0, 0, 0, 0};
   std::array<float, 3> eye{}, target{}, up{};
+  std::string depthPath, depthKind = "expected", idsPath;
+  std::vector<std::array<int, 2>> picks;
   while (a.next()) {
     bool good = false;
-    if (a.is("--size")) good = a.integer(size, 1, 16384, 2);
+    if (std::strcmp(a.arg(), "--pick") == 0) {  // the one option that may be repeated
+      picks.emplace_back();
+      good = a.integer(picks.back().data(), 0, 16383, 2);
+    } else if (a.is("--depth")) good = a.text(&depthPath) && endsWith(depthPath, ".pfm");
+    else if (a.is("--depth-kind")) good = a.text(&depthKind) && (depthKind == "expected" || depthKind == "median");
+    else if (a.is("--ids")) good = a.text(&idsPath) && !idsPath.empty();
+    else if (a.is("--size")) good = a.integer(size, 1, 16384, 2);
     else if (a.is("--fov-y")) good = a.real(&fovY) && fovY > 0.0f && fovY < 180.0f;
     else if (a.is("--intrinsics")) good = a.real(intr, 4) && allFinite(intr, 4);
     else if (a.is("--eye")) good = a.real(eye.data(), 3) && allFinite(eye.data(), 3);
@@ -401,6 +432,10 @@ int spzRender(int argc, char **argv) {
   }
   o.width = size[0];
   o.height = size[1];
+  if (a.given("--depth-kind") && !a.given("--depth")) return a.usage();
+  for (const auto &px : picks) {
+    if (px[0] >= o.width || px[1] >= o.height) return a.usage();
+  }
   if (hasFov) {
     o.fy = static_cast<float>(0.5 * o.height / std::tan(0.5 * fovY * 3.14159265358979323846 / 180.0));
     o.fx = o.fy;
@@ -424,10 +459,32 @@ int spzRender(int argc, char **argv) {
     return a.usage();
   }
   std::vector<float> rgba;
-  if (!spz::renderSpz(std::string(argv[1]), o, &rgba)) return 1;
+  spz::DepthMaps maps;
+  const bool wantDepth = a.given("--depth") || a.given("--ids") || !picks.empty();
+  if (!(wantDepth ? spz::renderSpzDepth(std::string(argv[1]), o, &maps, &rgba) : spz::renderSpz(std::string(argv[1]), o, &rgba))) {
+    return 1;
+  }
   if (!writeImage(outPath, rgba, o.width, o.height, pfm)) {
     std::cerr << "spz_render: unable to write " << outPath << std::endl;
     return 1;
+  }
+  if (a.given("--depth") && !writeDepthPfm(depthPath, depthKind == "median" ? maps.median : maps.expected, o.width, o.height)) {
+    std::cerr << "spz_render: unable to write " << depthPath << std::endl;
+    return 1;
+  }
+  if (a.given("--ids") && !writeIds(idsPath, maps.index)) {
+    std::cerr << "spz_render: unable to write " << idsPath << std::endl;
+    return 1;
+  }
+  for (const auto &px : picks) {
+    const size_t at = static_cast<size_t>(px[1]) * o.width + px[0];
+    if (maps.index[at] == 0xffffffffu) {
+      std::cout << "none" << std::endl;
+    } else {
+      char line[64];
+      std::snprintf(line, sizeof line, "%u %.9g", maps.index[at], static_cast<double>(maps.median[at]));
+      std::cout << line << std::endl;
+    }
   }
   return 0;
 }

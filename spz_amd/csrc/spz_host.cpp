@@ -25,6 +25,7 @@
 #include <fstream>
 #include <sstream>
 #include <istream>
+#include <limits>
 #include <mutex>
 #include <ostream>
 #include <stdexcept>
@@ -2348,10 +2349,10 @@ bool cleanSpz(const std::string &inputFilename, const std::string &outputFilenam
 
 // ---- render ------------------------------------------------------------------------------------------------------
 namespace {
-bool renderParams(const RenderOptions &o, spz_amd_render_params *p) {
+bool renderParams(const RenderOptions &o, spz_amd_render_params *p, const char *op = "renderSpz") {
   *p = spz_amd_render_params{};
   if (o.width < 1 || o.width > 16384 || o.height < 1 || o.height > 16384) {
-    return opRejected("renderSpz", SPZ_AMD_ERR_INVALID_ARG, "image size %d x %d is outside 1..16384", o.width, o.height);
+    return opRejected(op, SPZ_AMD_ERR_INVALID_ARG, "image size %d x %d is outside 1..16384", o.width, o.height);
   }
   for (int k = 0; k < 12; ++k) p->world_to_camera[k] = o.worldToCamera[k];
   p->fx = o.fx;
@@ -2365,19 +2366,63 @@ bool renderParams(const RenderOptions &o, spz_amd_render_params *p) {
   p->max_sh_degree = o.maxShDegree;
   p->coord = static_cast<int32_t>(o.coord);
   if (spz_amd_render_check_params(p) != SPZ_AMD_OK) {
-    return opRejected("renderSpz", SPZ_AMD_ERR_INVALID_ARG,
+    return opRejected(op, SPZ_AMD_ERR_INVALID_ARG,
                       "bad camera: R must be a rotation (to 1e-4), fx, fy > 0, nearPlane > 0, values finite, "
                       "maxShDegree 0..3");
   }
   return true;
 }
 
-void renderTiming(const float *ms, uint64_t entries) {
-  const Laps laps("renderSpz", "SPZ_AMD_RENDER_TIMING");
+void renderTiming(const float *ms, uint64_t entries, const char *op = "renderSpz") {
+  const Laps laps(op, "SPZ_AMD_RENDER_TIMING");
   laps.stage("preprocess", ms[0]);
   laps.stage("entries", ms[1], (" (" + std::to_string(entries) + ")").c_str());
   laps.stage("blend", ms[2]);
 }
+
+// The cloud's arrays as the C ABI takes them; false when they do not match numPoints and shDegree.
+bool cloudArrays(const GaussianCloud &g, spz_amd_cloud_in *c, size_t *n) {
+  *n = g.numPoints < 0 ? 0 : static_cast<size_t>(g.numPoints);
+  const int sd = g.shDegree == 0 ? 0 : g.shDegree == 1 ? 3 : g.shDegree == 2 ? 8 : g.shDegree == 3 ? 15 : -1;
+  if (g.numPoints < 0 || sd < 0 || g.positions.size() != *n * 3 || g.scales.size() != *n * 3 ||
+      g.rotations.size() != *n * 4 || g.alphas.size() != *n || g.colors.size() != *n * 3 ||
+      g.sh.size() != *n * static_cast<size_t>(sd) * 3) {
+    return false;
+  }
+  *c = {g.positions.data(), g.scales.data(), g.rotations.data(), g.alphas.data(), g.colors.data(),
+        sd ? g.sh.data() : nullptr};
+  return true;
+}
+
+// The buffers a depth call fills, and the maps derived from them once it has succeeded.
+struct DepthBuffers {
+  std::vector<float> img, depth;
+  std::vector<uint32_t> index;
+  explicit DepthBuffers(const RenderOptions &o) {
+    const size_t px = static_cast<size_t>(o.width) * static_cast<size_t>(o.height);
+    detail::resizeUninitialized(&img, px * 4u);
+    detail::resizeUninitialized(&depth, px * 2u);
+    index.resize(px);
+  }
+  void finish(DepthMaps *maps, std::vector<float> *rgba) {
+    const size_t px = index.size();
+    DepthMaps m;
+    m.expected.resize(px);
+    m.median.resize(px);
+    m.accumulated.resize(px);
+    m.alpha.resize(px);
+    for (size_t i = 0; i < px; ++i) {
+      const float acc = depth[i * 2], alpha = img[i * 4 + 3];
+      m.accumulated[i] = acc;
+      m.median[i] = depth[i * 2 + 1];
+      m.alpha[i] = alpha;
+      m.expected[i] = alpha > 0.0f ? acc / alpha : std::numeric_limits<float>::infinity();
+    }
+    m.index.swap(index);
+    *maps = std::move(m);
+    if (rgba) rgba->swap(img);
+  }
+};
 }  // namespace
 
 bool renderSpz(const uint8_t *data, int32_t size, const RenderOptions &o, std::vector<float> *rgba, int64_t *entries) {
@@ -2414,15 +2459,11 @@ bool renderCloud(const GaussianCloud &g, const RenderOptions &o, std::vector<flo
   if (rgba == nullptr) return opRejected("renderSpz", SPZ_AMD_ERR_INVALID_ARG, "no output vector");
   spz_amd_render_params p;
   if (!renderParams(o, &p)) return false;
-  const size_t n = g.numPoints < 0 ? 0 : static_cast<size_t>(g.numPoints);
-  const int sd = g.shDegree == 0 ? 0 : g.shDegree == 1 ? 3 : g.shDegree == 2 ? 8 : g.shDegree == 3 ? 15 : -1;
-  if (g.numPoints < 0 || sd < 0 || g.positions.size() != n * 3 || g.scales.size() != n * 3 ||
-      g.rotations.size() != n * 4 || g.alphas.size() != n || g.colors.size() != n * 3 ||
-      g.sh.size() != n * static_cast<size_t>(sd) * 3) {
+  spz_amd_cloud_in c;
+  size_t n = 0;
+  if (!cloudArrays(g, &c, &n)) {
     return opRejected("renderSpz", SPZ_AMD_ERR_INVALID_ARG, "the cloud's arrays do not match numPoints and shDegree");
   }
-  spz_amd_cloud_in c = {g.positions.data(), g.scales.data(), g.rotations.data(), g.alphas.data(), g.colors.data(),
-                        sd ? g.sh.data() : nullptr};
   std::vector<float> img;
   detail::resizeUninitialized(&img, static_cast<size_t>(o.width) * static_cast<size_t>(o.height) * 4u);
   uint64_t count = 0;
@@ -2432,6 +2473,61 @@ bool renderCloud(const GaussianCloud &g, const RenderOptions &o, std::vector<flo
   if (deviceFailed(rc, "renderCloud")) return false;
   renderTiming(ms, count);
   rgba->swap(img);
+  if (entries) *entries = static_cast<int64_t>(count);
+  return true;
+}
+
+bool renderSpzDepth(const uint8_t *data, int32_t size, const RenderOptions &o, DepthMaps *maps, std::vector<float> *rgba,
+                    int64_t *entries) {
+  g_last_status = SPZ_AMD_OK;
+  if (maps == nullptr) return opRejected("renderSpzDepth", SPZ_AMD_ERR_INVALID_ARG, "no output maps");
+  spz_amd_render_params p;
+  if (!renderParams(o, &p, "renderSpzDepth")) return false;
+  DevicePackedGaussians d;
+  if (!loadInput("renderSpzDepth", data, size, &d)) return false;
+  const spz_amd_header hdr = headerOf(d);
+  DepthBuffers b(o);
+  uint64_t count = 0;
+  float ms[3] = {0.0f, 0.0f, 0.0f};
+  const int rc = spz_amd_render_depth_host(d.stream, d.streamBytes, &hdr, &p, d.device, b.img.data(), b.depth.data(),
+                                           b.index.data(), &count, ms);
+  if (deviceFailed(rc, "renderSpzDepth")) return false;
+  renderTiming(ms, count, "renderSpzDepth");
+  b.finish(maps, rgba);
+  if (entries) *entries = static_cast<int64_t>(count);
+  return true;
+}
+
+bool renderSpzDepth(const std::string &filename, const RenderOptions &o, DepthMaps *maps, std::vector<float> *rgba,
+                    int64_t *entries) {
+  g_last_status = SPZ_AMD_OK;
+  if (maps == nullptr) return opRejected("renderSpzDepth", SPZ_AMD_ERR_INVALID_ARG, "no output maps");
+  spz_amd_render_params p;
+  if (!renderParams(o, &p, "renderSpzDepth")) return false;
+  std::vector<uint8_t> data;
+  if (!readInput("renderSpzDepth", filename, &data)) return false;
+  return renderSpzDepth(data.data(), static_cast<int32_t>(data.size()), o, maps, rgba, entries);
+}
+
+bool renderCloudDepth(const GaussianCloud &g, const RenderOptions &o, DepthMaps *maps, std::vector<float> *rgba,
+                      int64_t *entries) {
+  g_last_status = SPZ_AMD_OK;
+  if (maps == nullptr) return opRejected("renderSpzDepth", SPZ_AMD_ERR_INVALID_ARG, "no output maps");
+  spz_amd_render_params p;
+  if (!renderParams(o, &p, "renderSpzDepth")) return false;
+  spz_amd_cloud_in c;
+  size_t n = 0;
+  if (!cloudArrays(g, &c, &n)) {
+    return opRejected("renderSpzDepth", SPZ_AMD_ERR_INVALID_ARG, "the cloud's arrays do not match numPoints and shDegree");
+  }
+  DepthBuffers b(o);
+  uint64_t count = 0;
+  float ms[3] = {0.0f, 0.0f, 0.0f};
+  const int rc = spz_amd_render_depth_cloud_host(&c, n, g.shDegree, g.antialiased ? 1 : 0, &p, deviceIndex(),
+                                                 b.img.data(), b.depth.data(), b.index.data(), &count, ms);
+  if (deviceFailed(rc, "renderSpzDepth")) return false;
+  renderTiming(ms, count, "renderSpzDepth");
+  b.finish(maps, rgba);
   if (entries) *entries = static_cast<int64_t>(count);
   return true;
 }

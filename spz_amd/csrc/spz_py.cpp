@@ -138,6 +138,27 @@ py::object renderedImage(bool ok, const std::vector<float> &img, const spz::Rend
   return out;
 }
 
+// The dict of a depth render (each map (height, width); index int32 with -1 for none), or the exception of its failure.
+py::object renderedDepth(bool ok, spz::DepthMaps &maps, const spz::RenderOptions &o, const char *what) {
+  if (!ok) {
+    raiseFailure(std::string(what) + ": refused (see the [SPZ ERROR] line)",
+                 std::string(what) + " failed (see the [SPZ ERROR] line)");
+  }
+  const std::vector<py::ssize_t> shape = {static_cast<py::ssize_t>(o.height), static_cast<py::ssize_t>(o.width)};
+  py::dict d;
+  const std::pair<const char *, const std::vector<float> *> maps_f[] = {
+      {"expected", &maps.expected}, {"median", &maps.median}, {"accumulated", &maps.accumulated}, {"alpha", &maps.alpha}};
+  for (const auto &kv : maps_f) {
+    py::array_t<float> a(shape);
+    std::memcpy(a.mutable_data(), kv.second->data(), kv.second->size() * sizeof(float));
+    d[kv.first] = a;
+  }
+  py::array_t<int32_t> idx(shape);
+  std::memcpy(idx.mutable_data(), maps.index.data(), maps.index.size() * sizeof(uint32_t));  // 0xffffffff reads as -1
+  d["index"] = idx;
+  return d;
+}
+
 // A prune view from a mapping with world_to_camera (3x4), fx, fy, cx, cy, width, height (what orbit_views and
 // load_3dgs_cameras return); every problem is a ValueError that names the view.
 spz::PruneOptions::View pruneView(const py::handle &h, size_t k, spz::CoordinateSystem coord, float near_plane) {
@@ -938,6 +959,53 @@ PYBIND11_MODULE(spz, m) {
         py::arg("background") = py::make_tuple(0.0f, 0.0f, 0.0f), py::arg("max_sh_degree") = 3,
         "Render one pinhole view of a GaussianCloud in host memory on the device (spz::renderCloud): the cloud is "
         "uploaded and rendered as it is, in the frame of world_to_camera.  Returns a (height, width, 4) float32 array.");
+  m.def("render_depth_spz",
+        [](const py::object &input, const py::object &world_to_camera, int width, int height, float fx, float fy,
+           float cx, float cy, float near_plane, const py::object &background, int max_sh_degree,
+           spz::CoordinateSystem coord) -> py::object {
+          const spz::RenderOptions o = renderOptions(world_to_camera, width, height, fx, fy, cx, cy, near_plane, background,
+                                                     max_sh_degree, coord);
+          spz::DepthMaps maps;
+          bool ok;
+          if (py::isinstance<py::bytes>(input)) {
+            const std::string b = input.cast<std::string>();
+            if (b.size() > static_cast<size_t>(INT32_MAX)) throw py::value_error("input is larger than 2 GiB");
+            py::gil_scoped_release release;
+            ok = spz::renderSpzDepth(reinterpret_cast<const uint8_t *>(b.data()), static_cast<int32_t>(b.size()), o, &maps);
+          } else {
+            const std::string fn = py::str(input).cast<std::string>();
+            py::gil_scoped_release release;
+            ok = spz::renderSpzDepth(fn, o, &maps);
+          }
+          return renderedDepth(ok, maps, o, "render_depth_spz");
+        },
+        py::arg("input"), py::kw_only(), py::arg("world_to_camera"), py::arg("width"), py::arg("height"), py::arg("fx"),
+        py::arg("fy"), py::arg("cx"), py::arg("cy"), py::arg("near") = 0.2f,
+        py::arg("background") = py::make_tuple(0.0f, 0.0f, 0.0f), py::arg("max_sh_degree") = 3,
+        py::arg("coord") = spz::CoordinateSystem::UNSPECIFIED,
+        "The depth maps of one pinhole view of a .spz file (a path or the file's bytes) on the device "
+        "(spz::renderSpzDepth; the contract is in include/spz_amd.h \"render depth\"); the arguments are render_spz's.  "
+        "Returns a dict of (height, width) arrays: expected (float32: accumulated / alpha, +inf where alpha is 0), median "
+        "(float32: the depth at which the transmittance falls below 0.5, +inf for none), alpha (float32), index (int32: "
+        "the median Gaussian's index in the file, -1 for none) and accumulated (float32: the sum of (T a) z).");
+  m.def("render_depth_cloud",
+        [](const spz::GaussianCloud &cloud, const py::object &world_to_camera, int width, int height, float fx, float fy,
+           float cx, float cy, float near_plane, const py::object &background, int max_sh_degree) -> py::object {
+          const spz::RenderOptions o = renderOptions(world_to_camera, width, height, fx, fy, cx, cy, near_plane, background,
+                                                     max_sh_degree, spz::CoordinateSystem::UNSPECIFIED);
+          spz::DepthMaps maps;
+          bool ok;
+          {
+            py::gil_scoped_release release;
+            ok = spz::renderCloudDepth(cloud, o, &maps);
+          }
+          return renderedDepth(ok, maps, o, "render_depth_cloud");
+        },
+        py::arg("cloud"), py::kw_only(), py::arg("world_to_camera"), py::arg("width"), py::arg("height"), py::arg("fx"),
+        py::arg("fy"), py::arg("cx"), py::arg("cy"), py::arg("near") = 0.2f,
+        py::arg("background") = py::make_tuple(0.0f, 0.0f, 0.0f), py::arg("max_sh_degree") = 3,
+        "The depth maps of one pinhole view of a GaussianCloud in host memory (spz::renderCloudDepth): the dict of "
+        "render_depth_spz, the cloud uploaded and taken as it is, in the frame of world_to_camera.");
   m.def("look_at",
         [](const std::array<float, 3> &eye, const std::array<float, 3> &target, const std::array<float, 3> &up) {
           std::array<float, 12> r;
@@ -1572,4 +1640,5 @@ PYBIND11_MODULE(spz, m) {
         py::arg("gaussians"), py::arg("options"), py::arg("filename"), "Write GaussianCloud data to a *.ply* file.");
   // the reader of 3DGS's cameras.json is plain Python (spz_amd/cameras.py)
   m.attr("load_3dgs_cameras") = py::module_::import("spz_amd.cameras").attr("load_3dgs_cameras");
+  m.attr("unproject_depth") = py::module_::import("spz_amd.cameras").attr("unproject_depth");
 }

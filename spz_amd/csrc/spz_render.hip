@@ -19,6 +19,8 @@
 //                                      broadcast); the workgroup stops once every lane has stopped.
 //   spz_render_score_kernel            the blend again, pixel for pixel, adding each used pair's weight T a into the
 //                                      Gaussian's u64 sum (as rint(w 2^24)) and f32 max (spz_prune.hip uses it).
+//   spz_render_depth_kernel            the blend again, pixel for pixel, adding each used pair's (T a) z into the pixel's
+//                                      depth sum and taking the first Gaussian after which T < 0.5 as its median.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -610,6 +612,110 @@ __global__ __launch_bounds__(kBlendThreads) void spz_render_score_kernel(const S
   }
 }
 
+struct DepthParams {
+  const spz_amd_render_record *rec;
+  const uint32_t *sorted_gid;
+  const uint2 *ranges;
+  const unsigned long long *total;
+  float *image;     // may be null
+  float *depth;     // height x width x 2: accumulated depth, median depth
+  uint32_t *index;  // may be null: the median Gaussian
+  unsigned long long max_entries;
+  uint32_t width, height, tiles_x;
+  float bg[3];
+};
+
+namespace {
+
+constexpr uint32_t kNoIndex = 0xffffffffu;
+
+// One pixel's state in the depth blend: the blend kernel's T and colour, the depth sum D and the median taken so far.
+struct DepthPixel {
+  float T = 1.0f, c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, D = 0.0f, median = __builtin_huge_valf();
+  uint32_t index = kNoIndex;
+  // A used pair: weight w = T a, the colour and depth sums, T = Tn, and the first Gaussian to bring T under 0.5.
+  __device__ __forceinline__ void use(float a, float Tn, const float4 &rgbz, uint32_t gid) {
+    const float w = T * a;
+    c0 = c0 + w * rgbz.x;
+    c1 = c1 + w * rgbz.y;
+    c2 = c2 + w * rgbz.z;
+    D = D + w * rgbz.w;
+    T = Tn;
+    if (index == kNoIndex && Tn < 0.5f) {
+      median = rgbz.w;
+      index = gid;
+    }
+  }
+};
+
+}  // namespace
+
+// The blend of spz_render_blend_kernel, pixel for pixel, plus each used pair's depth: s_rgb[k].w carries the record's
+// depth z and s_gid[k] its Gaussian.  D += (T a) z; the first used Gaussian after which T < 0.5 is the pixel's median.
+__global__ __launch_bounds__(kBlendThreads) void spz_render_depth_kernel(const DepthParams p) {
+  __shared__ float2 s_xy[kBlendThreads];
+  __shared__ float4 s_co[kBlendThreads];   // conic A, B, C, opacity
+  __shared__ float4 s_rgb[kBlendThreads];  // rgb, depth
+  __shared__ uint32_t s_gid[kBlendThreads];
+  const unsigned long long total = *p.total;
+  if (total > p.max_entries) return;
+  const uint32_t t = threadIdx.x;
+  const uint32_t u = blockIdx.x * kTile + (t % kTile), v = blockIdx.y * kTile + (t / kTile);
+  const bool inside = u < p.width && v < p.height;
+  uint32_t begin = 0, end = 0;
+  if (total != 0ull) {
+    const uint2 r = p.ranges[blockIdx.y * p.tiles_x + blockIdx.x];
+    begin = r.x;
+    end = r.y;
+  }
+  const float fu = (float)u, fv = (float)v;
+  DepthPixel px;
+  bool done = !inside;
+  for (uint32_t base = begin; base < end; base += kBlendThreads) {
+    // also the barrier between the previous batch's reads and this batch's writes
+    if (__syncthreads_count(done ? 1 : 0) == (int)kBlendThreads) break;
+    const uint32_t j = base + t;
+    if (j < end) {
+      const uint32_t gid = p.sorted_gid[j];
+      const spz_amd_render_record &q = p.rec[gid];
+      s_xy[t] = make_float2(q.mean[0], q.mean[1]);
+      s_co[t] = make_float4(q.conic[0], q.conic[1], q.conic[2], q.opacity);
+      s_rgb[t] = make_float4(q.rgb[0], q.rgb[1], q.rgb[2], q.depth);
+      s_gid[t] = gid;
+    }
+    __syncthreads();
+    const uint32_t cnt = (end - base) < kBlendThreads ? end - base : kBlendThreads;
+    for (uint32_t k = 0; k < cnt && !done; ++k) {
+      const float2 xy = s_xy[k];
+      const float4 co = s_co[k];
+      const float dx = fu - xy.x, dy = fv - xy.y;
+      const float power = -0.5f * (co.x * dx * dx + co.z * dy * dy) - co.y * dx * dy;
+      if (power > 0.0f) continue;
+      const float a = fminf(0.99f, co.w * expf(power));
+      if (a < 1.0f / 255.0f) continue;
+      const float Tn = px.T * (1.0f - a);
+      if (Tn < 1e-4f) {
+        done = true;
+        break;
+      }
+      px.use(a, Tn, s_rgb[k], s_gid[k]);
+    }
+  }
+  if (inside) {
+    const unsigned long long at = (unsigned long long)v * p.width + u;
+    p.depth[at * 2u] = px.D;
+    p.depth[at * 2u + 1u] = px.median;
+    if (p.index) p.index[at] = px.index;
+    if (p.image) {
+      float *o = p.image + at * 4u;
+      o[0] = px.c0 + px.T * p.bg[0];
+      o[1] = px.c1 + px.T * p.bg[1];
+      o[2] = px.c2 + px.T * p.bg[2];
+      o[3] = 1.0f - px.T;
+    }
+  }
+}
+
 }  // namespace spz_amd_detail
 
 namespace {
@@ -840,6 +946,28 @@ int score_impl(uint64_t n, const spz_amd_render_params *params, uint64_t m, floa
   return SPZ_AMD_OK;
 }
 
+int depth_impl(uint64_t n, const spz_amd_render_params *params, uint64_t m, float *d_image, float *d_depth,
+               uint32_t *d_index, uint8_t *base, uint8_t *ent, hipStream_t st) {
+  const RenderLayout wl = render_layout(n, m);
+  DepthParams b = {};
+  b.rec = reinterpret_cast<const spz_amd_render_record *>(base + wl.rec);
+  b.sorted_gid = m ? reinterpret_cast<const uint32_t *>(ent + wl.sorted_gid) : nullptr;
+  b.ranges = m ? reinterpret_cast<const uint2 *>(ent + wl.ranges) : nullptr;  // read only when the total is > 0
+  b.total = reinterpret_cast<const unsigned long long *>(base + wl.total);
+  b.image = d_image;
+  b.depth = d_depth;
+  b.index = d_index;
+  b.max_entries = m;
+  b.width = params->width;
+  b.height = params->height;
+  b.tiles_x = (params->width + kTile - 1) / kTile;
+  for (int k = 0; k < 3; ++k) b.bg[k] = params->background[k];
+  const dim3 grid(b.tiles_x, (params->height + kTile - 1) / kTile);
+  hipLaunchKernelGGL(spz_render_depth_kernel, grid, dim3(kBlendThreads), 0, st, b);
+  SPZ_HIP_TRY(hipGetLastError());
+  return SPZ_AMD_OK;
+}
+
 int packed_source(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, int coord, PackedSrc *src) {
   spz_amd_layout lay;
   const int rc = check_packed_stream(d_stream, size, hdr, &lay);
@@ -876,9 +1004,17 @@ int cloud_source(const spz_amd_cloud_in *cl, uint64_t n, int sh_degree, FloatSrc
   return SPZ_AMD_OK;
 }
 
+// What a host form returns: the image alone (the blend kernel), or depth maps with an optional index and image (the
+// depth kernel).
+struct HostOut {
+  float *rgba = nullptr;
+  float *depth = nullptr;
+  uint32_t *index = nullptr;
+};
+
 // The host forms: prepare into a block of their own, read the total, then the entries and the blend into a second.
 template <class Prepare>
-int render_host_impl(uint64_t n, const spz_amd_render_params *params, int device, float *h_rgba, uint64_t *h_entries,
+int render_host_impl(uint64_t n, const spz_amd_render_params *params, int device, const HostOut &out, uint64_t *h_entries,
                      float *h_ms, uint64_t upload_bytes, const Prepare &prepare) {
   struct Blocks {
     hipStream_t st = nullptr;
@@ -912,21 +1048,28 @@ int render_host_impl(uint64_t n, const spz_amd_render_params *params, int device
   const double t_pre = ms_since(t0);
   if (total > kMaxEntries) return SPZ_AMD_ERR_CAPACITY;
   const RenderLayout wf = render_layout(n, total);
-  const uint64_t image_bytes = (uint64_t)params->width * params->height * 16u;
-  SPZ_HIP_TRY(hipMalloc(&k.b, wf.entries + al(image_bytes) + 256));
+  const uint64_t pixels = (uint64_t)params->width * params->height;
+  const uint64_t image_bytes = out.rgba ? pixels * 16u : 0u, depth_bytes = out.depth ? pixels * 8u : 0u, index_bytes = out.index ? pixels * 4u : 0u;
+  SPZ_HIP_TRY(hipMalloc(&k.b, wf.entries + al(image_bytes) + al(depth_bytes) + al(index_bytes) + 256));
   uint8_t *ent = align_ws(k.b);
   float *d_image = reinterpret_cast<float *>(ent + wf.entries);
+  float *d_depth = reinterpret_cast<float *>(ent + wf.entries + al(image_bytes));
+  uint32_t *d_index = reinterpret_cast<uint32_t *>(ent + wf.entries + al(image_bytes) + al(depth_bytes));
   const auto t1 = std::chrono::steady_clock::now();
   rc = entries_impl(n, params, total, d_status, base, ent, k.st);
   if (rc != SPZ_AMD_OK) return rc;
   SPZ_HIP_TRY(hipStreamSynchronize(k.st));
   const double t_ent = ms_since(t1);
   const auto t2 = std::chrono::steady_clock::now();
-  rc = blend_impl(n, params, total, d_image, base, ent, k.st);
+  rc = out.depth ? depth_impl(n, params, total, out.rgba ? d_image : nullptr, d_depth, out.index ? d_index : nullptr,
+                              base, ent, k.st)
+                 : blend_impl(n, params, total, d_image, base, ent, k.st);
   if (rc != SPZ_AMD_OK) return rc;
   SPZ_HIP_TRY(hipStreamSynchronize(k.st));
   const double t_blend = ms_since(t2);
-  SPZ_HIP_TRY(hipMemcpyAsync(h_rgba, d_image, image_bytes, hipMemcpyDeviceToHost, k.st));
+  if (out.rgba) SPZ_HIP_TRY(hipMemcpyAsync(out.rgba, d_image, image_bytes, hipMemcpyDeviceToHost, k.st));
+  if (out.depth) SPZ_HIP_TRY(hipMemcpyAsync(out.depth, d_depth, depth_bytes, hipMemcpyDeviceToHost, k.st));
+  if (out.index) SPZ_HIP_TRY(hipMemcpyAsync(out.index, d_index, index_bytes, hipMemcpyDeviceToHost, k.st));
   SPZ_HIP_TRY(hipStreamSynchronize(k.st));
   if (h_entries) *h_entries = total;
   if (h_ms) {
@@ -935,6 +1078,58 @@ int render_host_impl(uint64_t n, const spz_amd_render_params *params, int device
     h_ms[2] = (float)t_blend;
   }
   return SPZ_AMD_OK;
+}
+
+// render_host and render_depth_host: a stream in device memory.  has_output: the form's required output is there.
+int packed_host(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, const spz_amd_render_params *params,
+                int device, const HostOut &out, bool has_output, uint64_t *h_entries, float *h_ms) {
+  int rc = check_params(params);
+  if (rc != SPZ_AMD_OK) return rc;
+  PackedSrc src;
+  rc = packed_source(d_stream, size, hdr, params->coord, &src);
+  if (rc != SPZ_AMD_OK) return rc;
+  if (!has_output) return SPZ_AMD_ERR_INVALID_ARG;
+  return render_host_impl(hdr->num_points, params, device, out, h_entries, h_ms, 0,
+                          [&](uint8_t *base, uint64_t *d_total, uint8_t *, hipStream_t st,
+                              std::chrono::steady_clock::time_point *) -> int {
+                            int r = ensure_tables(device, &src.tables);
+                            if (r != SPZ_AMD_OK) return r;
+                            return prepare_impl(src, hdr->num_points, hdr->sh_degree, hdr->flags & 1, params, d_total,
+                                                nullptr, base, st);
+                          });
+}
+
+// render_cloud_host and render_depth_cloud_host: a cloud in host memory, uploaded first.
+int cloud_host(const spz_amd_cloud_in *h_cloud, uint64_t num_points, int sh_degree, int antialiased,
+               const spz_amd_render_params *params, int device, const HostOut &out, bool has_output,
+               uint64_t *h_entries, float *h_ms) {
+  int rc = check_params(params);
+  if (rc != SPZ_AMD_OK) return rc;
+  FloatSrc hs;
+  rc = cloud_source(h_cloud, num_points, sh_degree, &hs);
+  if (rc != SPZ_AMD_OK) return rc;
+  if (!has_output) return SPZ_AMD_ERR_INVALID_ARG;
+  const uint64_t fpp[6] = {3, 3, 4, 1, 3, (uint64_t)hs.sh_dim * 3u};
+  uint64_t upload = 0;
+  for (int f = 0; f < 6; ++f) upload += al(num_points * fpp[f] * 4u);
+  return render_host_impl(num_points, params, device, out, h_entries, h_ms, upload,
+                          [&](uint8_t *base, uint64_t *d_total, uint8_t *up, hipStream_t st,
+                              std::chrono::steady_clock::time_point *t0) -> int {
+                            const float *hp[6] = {hs.positions, hs.scales, hs.rotations, hs.alphas, hs.colors, hs.sh};
+                            float *dp[6];
+                            uint8_t *q = up;
+                            for (int f = 0; f < 6; ++f) {
+                              dp[f] = reinterpret_cast<float *>(q);
+                              const uint64_t bytes = num_points * fpp[f] * 4u;
+                              if (bytes) SPZ_HIP_TRY(hipMemcpyAsync(dp[f], hp[f], bytes, hipMemcpyHostToDevice, st));
+                              q += al(bytes);
+                            }
+                            SPZ_HIP_TRY(hipStreamSynchronize(st));
+                            *t0 = std::chrono::steady_clock::now();
+                            const FloatSrc ds{dp[0], dp[1], dp[2], dp[3], dp[4], dp[5], hs.sh_dim};
+                            return prepare_impl(ds, num_points, sh_degree, antialiased, params, d_total, nullptr,
+                                                base, st);
+                          });
 }
 
 }  // namespace
@@ -1020,52 +1215,57 @@ int spz_amd_render_score_device(uint64_t num_points, const spz_amd_render_params
 int spz_amd_render_host(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr,
                         const spz_amd_render_params *params, int device, float *h_rgba, uint64_t *h_entries,
                         float *h_ms) {
-  int rc = check_params(params);
-  if (rc != SPZ_AMD_OK) return rc;
-  PackedSrc src;
-  rc = packed_source(d_stream, size, hdr, params->coord, &src);
-  if (rc != SPZ_AMD_OK) return rc;
-  if (h_rgba == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
-  return render_host_impl(hdr->num_points, params, device, h_rgba, h_entries, h_ms, 0,
-                          [&](uint8_t *base, uint64_t *d_total, uint8_t *, hipStream_t st,
-                              std::chrono::steady_clock::time_point *) -> int {
-                            int r = ensure_tables(device, &src.tables);
-                            if (r != SPZ_AMD_OK) return r;
-                            return prepare_impl(src, hdr->num_points, hdr->sh_degree, hdr->flags & 1, params, d_total,
-                                                nullptr, base, st);
-                          });
+  HostOut out;
+  out.rgba = h_rgba;
+  return packed_host(d_stream, size, hdr, params, device, out, h_rgba != nullptr, h_entries, h_ms);
 }
 
 int spz_amd_render_cloud_host(const spz_amd_cloud_in *h_cloud, uint64_t num_points, int sh_degree, int antialiased,
                               const spz_amd_render_params *params, int device, float *h_rgba, uint64_t *h_entries,
                               float *h_ms) {
+  HostOut out;
+  out.rgba = h_rgba;
+  return cloud_host(h_cloud, num_points, sh_degree, antialiased, params, device, out, h_rgba != nullptr, h_entries, h_ms);
+}
+
+int spz_amd_render_depth_device(uint64_t num_points, const spz_amd_render_params *params, uint64_t max_entries,
+                                float *d_image, float *d_depth, uint32_t *d_index, uint32_t *d_status,
+                                void *d_workspace, void *hip_stream) {
   int rc = check_params(params);
   if (rc != SPZ_AMD_OK) return rc;
-  FloatSrc hs;
-  rc = cloud_source(h_cloud, num_points, sh_degree, &hs);
+  if (num_points > kMaxEntries) return SPZ_AMD_ERR_INVALID_ARG;
+  if (d_depth == nullptr || d_status == nullptr || d_workspace == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
+  if (max_entries > kMaxEntries) return SPZ_AMD_ERR_CAPACITY;
+  int device = 0;
+  rc = current_device(&device);
   if (rc != SPZ_AMD_OK) return rc;
-  if (h_rgba == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
-  const uint64_t fpp[6] = {3, 3, 4, 1, 3, (uint64_t)hs.sh_dim * 3u};
-  uint64_t upload = 0;
-  for (int f = 0; f < 6; ++f) upload += al(num_points * fpp[f] * 4u);
-  return render_host_impl(num_points, params, device, h_rgba, h_entries, h_ms, upload,
-                          [&](uint8_t *base, uint64_t *d_total, uint8_t *up, hipStream_t st,
-                              std::chrono::steady_clock::time_point *t0) -> int {
-                            const float *hp[6] = {hs.positions, hs.scales, hs.rotations, hs.alphas, hs.colors, hs.sh};
-                            float *dp[6];
-                            uint8_t *q = up;
-                            for (int f = 0; f < 6; ++f) {
-                              dp[f] = reinterpret_cast<float *>(q);
-                              const uint64_t bytes = num_points * fpp[f] * 4u;
-                              if (bytes) SPZ_HIP_TRY(hipMemcpyAsync(dp[f], hp[f], bytes, hipMemcpyHostToDevice, st));
-                              q += al(bytes);
-                            }
-                            SPZ_HIP_TRY(hipStreamSynchronize(st));
-                            *t0 = std::chrono::steady_clock::now();
-                            const FloatSrc ds{dp[0], dp[1], dp[2], dp[3], dp[4], dp[5], hs.sh_dim};
-                            return prepare_impl(ds, num_points, sh_degree, antialiased, params, d_total, nullptr,
-                                                base, st);
-                          });
+  const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  uint8_t *base = align_ws(d_workspace);
+  uint8_t *ent = base + render_layout(num_points, 0).prefix;
+  rc = entries_impl(num_points, params, max_entries, d_status, base, ent, st);
+  if (rc != SPZ_AMD_OK) return rc;
+  return depth_impl(num_points, params, max_entries, d_image, d_depth, d_index, base, ent, st);
+}
+
+int spz_amd_render_depth_host(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr,
+                              const spz_amd_render_params *params, int device, float *h_rgba, float *h_depth,
+                              uint32_t *h_index, uint64_t *h_entries, float *h_ms) {
+  HostOut out;
+  out.rgba = h_rgba;
+  out.depth = h_depth;
+  out.index = h_index;
+  return packed_host(d_stream, size, hdr, params, device, out, h_depth != nullptr, h_entries, h_ms);
+}
+
+int spz_amd_render_depth_cloud_host(const spz_amd_cloud_in *h_cloud, uint64_t num_points, int sh_degree,
+                                    int antialiased, const spz_amd_render_params *params, int device, float *h_rgba,
+                                    float *h_depth, uint32_t *h_index, uint64_t *h_entries, float *h_ms) {
+  HostOut out;
+  out.rgba = h_rgba;
+  out.depth = h_depth;
+  out.index = h_index;
+  return cloud_host(h_cloud, num_points, sh_degree, antialiased, params, device, out, h_depth != nullptr, h_entries,
+                    h_ms);
 }
 
 }  // extern "C"

@@ -854,14 +854,46 @@ def _aligned_view(t, nbytes):
     return t[off: off + nbytes]
 
 
-def _render(source, n, params, dev, max_entries, out, return_info, stream):
-    L = abi.load_library()
+def _check_render_args(L, params, max_entries):
     if not isinstance(params, abi.RenderParams):
         raise ValueError("params must be an abi.RenderParams (abi.render_params)")
     abi.check(L.spz_amd_render_check_params(C.byref(params)), "spz_amd_render_check_params")
     if max_entries is not None and (isinstance(max_entries, bool) or not isinstance(max_entries, int)
                                     or not 0 <= max_entries <= 0x7fffffff):
         raise ValueError(f"max_entries must be an int in 0..2^31-1, got {max_entries!r}")
+
+
+def _prepared_workspace(L, source, n, params, dev, max_entries, total, st):
+    """Enqueue the prepare step on st and return (workspace, m): the workspace holds the prepare part and has room for m
+    entries, m = max_entries or, when that is None, the total read back."""
+    if max_entries is None:
+        # the prepare step writes only the first workspace_bytes(n, 0) - 256 bytes from the workspace's aligned
+        # base: prepare, read the total, then move that prefix to the front of a workspace with room for the
+        # entries
+        ws0_bytes = int(L.spz_amd_render_workspace_bytes(n, 0))
+        ws0 = torch.empty(ws0_bytes, dtype=torch.uint8, device=dev)
+        _render_prepare(L, source, params, total, None, ws0, st)
+        m = int(total.cpu()[0])  # on st: waits for the prepare step
+        if m > 0x7fffffff:
+            raise RuntimeError(f"{m} tile entries is above the sort's limit of 2^31 - 1")
+        ws = torch.empty(int(L.spz_amd_render_workspace_bytes(n, m)), dtype=torch.uint8, device=dev)
+        prefix = ws0_bytes - 256
+        _aligned_view(ws, prefix).copy_(_aligned_view(ws0, prefix))
+    else:
+        m = max_entries
+        ws = torch.empty(int(L.spz_amd_render_workspace_bytes(n, m)), dtype=torch.uint8, device=dev)
+        _render_prepare(L, source, params, total, None, ws, st)
+    return ws, m
+
+
+def _check_out(name, t, shape, dtype, dev):
+    if t is not None and (t.dtype != dtype or t.device != dev or not t.is_contiguous() or tuple(t.shape) != shape):
+        raise ValueError(f"{name} must be a contiguous {str(dtype).split('.')[-1]} tensor of shape {shape} on {dev}")
+
+
+def _render(source, n, params, dev, max_entries, out, return_info, stream):
+    L = abi.load_library()
+    _check_render_args(L, params, max_entries)
     h, w = params.height, params.width
     if out is not None and (out.dtype != torch.float32 or out.device != dev or not out.is_contiguous()
                             or tuple(out.shape) != (h, w, 4)):
@@ -874,27 +906,50 @@ def _render(source, n, params, dev, max_entries, out, return_info, stream):
             # the prepare step always writes the total, the finish step always writes the status
             total = torch.empty(1, dtype=torch.int64, device=dev)
             status = torch.empty(1, dtype=torch.int32, device=dev)
-            if max_entries is None:
-                # the prepare step writes only the first workspace_bytes(n, 0) - 256 bytes from the workspace's aligned
-                # base: prepare, read the total, then move that prefix to the front of a workspace with room for the
-                # entries
-                ws0_bytes = int(L.spz_amd_render_workspace_bytes(n, 0))
-                ws0 = torch.empty(ws0_bytes, dtype=torch.uint8, device=dev)
-                _render_prepare(L, source, params, total, None, ws0, st)
-                m = int(total.cpu()[0])  # on st: waits for the prepare step
-                if m > 0x7fffffff:
-                    raise RuntimeError(f"{m} tile entries is above the sort's limit of 2^31 - 1")
-                ws = torch.empty(int(L.spz_amd_render_workspace_bytes(n, m)), dtype=torch.uint8, device=dev)
-                prefix = ws0_bytes - 256
-                _aligned_view(ws, prefix).copy_(_aligned_view(ws0, prefix))
-            else:
-                m = max_entries
-                ws = torch.empty(int(L.spz_amd_render_workspace_bytes(n, m)), dtype=torch.uint8, device=dev)
-                _render_prepare(L, source, params, total, None, ws, st)
+            ws, m = _prepared_workspace(L, source, n, params, dev, max_entries, total, st)
             rc = L.spz_amd_render_finish_device(n, C.byref(params), m, out.data_ptr(), status.data_ptr(), ws.data_ptr(),
                                                 C.c_void_p(st.cuda_stream))
     abi.check(rc, "spz_amd_render_finish_device")
     return (out, total, status) if return_info else out
+
+
+def _render_depth(source, n, params, dev, max_entries, return_image, return_index, out, return_info, stream):
+    L = abi.load_library()
+    _check_render_args(L, params, max_entries)
+    h, w = params.height, params.width
+    out = dict(out or {})
+    if set(out) - {"depth", "index", "image"}:
+        raise ValueError("out may hold depth, index and image")
+    _check_out("out['depth']", out.get("depth"), (h, w, 2), torch.float32, dev)
+    _check_out("out['index']", out.get("index"), (h, w), torch.int32, dev)
+    _check_out("out['image']", out.get("image"), (h, w, 4), torch.float32, dev)
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        with torch.cuda.stream(st):
+            depth = out.get("depth")
+            if depth is None:
+                depth = torch.empty((h, w, 2), dtype=torch.float32, device=dev)
+            index = out.get("index")
+            if index is None and return_index:
+                index = torch.empty((h, w), dtype=torch.int32, device=dev)
+            image = out.get("image")
+            if image is None and return_image:
+                image = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
+            total = torch.empty(1, dtype=torch.int64, device=dev)
+            status = torch.empty(1, dtype=torch.int32, device=dev)
+            ws, m = _prepared_workspace(L, source, n, params, dev, max_entries, total, st)
+            rc = L.spz_amd_render_depth_device(n, C.byref(params), m, image.data_ptr() if image is not None else None,
+                                               depth.data_ptr(), index.data_ptr() if index is not None else None,
+                                               status.data_ptr(), ws.data_ptr(), C.c_void_p(st.cuda_stream))
+    abi.check(rc, "spz_amd_render_depth_device")
+    res = (depth,)
+    if index is not None:
+        res += (index,)
+    if image is not None:
+        res += (image,)
+    if return_info:
+        res += (total, status)
+    return res[0] if len(res) == 1 else res
 
 
 def render(cloud, num_points, sh_degree, params, antialiased=False, max_entries=None, out=None, return_info=False,
@@ -918,6 +973,37 @@ def render_packed(stream_t, header, params, max_entries=None, out=None, return_i
     _check_stream_tensor(stream_t)
     return _render(("packed", stream_t, header), header.num_points, params, stream_t.device, max_entries, out,
                    return_info, stream)
+
+
+def render_depth(cloud, num_points, sh_degree, params, antialiased=False, max_entries=None, return_image=False,
+                 return_index=True, out=None, return_info=False, stream=None):
+    """The depth maps of a float cloud on the device (spz_amd_render_prepare_cloud_device + spz_amd_render_depth_device;
+    the contract is in include/spz_amd.h "render depth"): (depth, index, image), without index when return_index is
+    False and without image unless return_image.  depth: (height, width, 2) float32, channel 0 the accumulated depth
+    sum (T a) z, un-normalised, channel 1 the median depth (+inf: none).  index: (height, width) int32, the median
+    Gaussian's input index or -1 for none (the C ABI's uint32 0xffffffff: torch has no uint32 arithmetic).  image: as
+    render(), bit for bit.  expected_depth() normalises channel 0.  out: a dict of tensors to write into (depth, index,
+    image; a given one is also returned).  cloud, max_entries, return_info (appends total and status) and stream: as
+    render(); with status 1 no output is written."""
+    ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
+    return _render_depth(("cloud", ptrs, num_points, int(sh_degree), antialiased), num_points, params, dev, max_entries,
+                         return_image, return_index, out, return_info, stream)
+
+
+def render_depth_packed(stream_t, header, params, max_entries=None, return_image=False, return_index=True, out=None,
+                        return_info=False, stream=None):
+    """The depth maps of a packed device stream (any version), decoded as loadSpz(to = params.coord) would:
+    bit-identical to render_depth() of the decoded floats.  Otherwise as render_depth()."""
+    _check_stream_tensor(stream_t)
+    return _render_depth(("packed", stream_t, header), header.num_points, params, stream_t.device, max_entries,
+                         return_image, return_index, out, return_info, stream)
+
+
+def expected_depth(depth, alpha):
+    """The normalised expected depth of render_depth(): depth[..., 0] / alpha in float32 where alpha > 0 (the image's
+    alpha channel, 1 - T), +inf elsewhere."""
+    acc = depth[..., 0]
+    return torch.where(alpha > 0, acc / alpha, torch.full_like(acc, float("inf")))
 
 
 def _score(source, n, views, dev, max_entries, images, return_status, stream):
