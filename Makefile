@@ -76,7 +76,7 @@ clean:
 	rm -rf $(LIBDIR) $(ROOT)build $(ROOT)spz_amd/spz*.so $(ROOT)spz_amd/bin
 	$(MAKE) -C $(ROOT)oracle clean
 
-.PHONY: fuzz gzip-campaign all device host python cli oracle asm clean
+.PHONY: fuzz fuzz-foreign gzip-campaign all device host python cli oracle asm clean
 
 # The byte-identity of the multi-threaded gzip writer against zlib 1.2.11 on ~9 300 randomized inputs (host
 # only, about twenty minutes on 8 cores); the result line goes to profiles/.
@@ -92,3 +92,14 @@ fuzz: $(LIBDIR)/libspz_amd.so
 	    $(ROOT)tools/fuzz/$$t.cpp $(CSRC)/spz_host.cpp $(CSRC)/spz_ply.cpp $(CSRC)/spz_deflate.cpp $(CSRC)/spz_lz77_model.cpp $(CSRC)/spz_inflate.cpp -L$(LIBDIR) -lspz_amd -lz -ldl -lpthread \
 	    -Wl,-rpath,$(abspath $(LIBDIR)) && ASAN_OPTIONS=detect_leaks=0 $(ROOT)build/$$t || exit 1; \
 	done
+
+# The decoder source both inflate readers share, under ASan + UBSan, over the crafted members of tests/deflate_craft.py
+# (valid deflate no zlib writes, and members invalid in one chosen way), at the device reader's size and the host reader's.
+fuzz-foreign:
+	mkdir -p $(ROOT)build/foreign_small $(ROOT)build/foreign_large
+	$(CXX) -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -std=gnu++17 -I$(INC) -o $(ROOT)build/inflate_foreign \
+	    $(ROOT)tools/fuzz/inflate_foreign.cpp $(CSRC)/spz_inflate.cpp -lz -lpthread
+	$(PYTHON) $(ROOT)tests/deflate_craft.py $(ROOT)build/foreign_small 1150000
+	$(PYTHON) $(ROOT)tests/deflate_craft.py $(ROOT)build/foreign_large
+	ASAN_OPTIONS=detect_leaks=0 $(ROOT)build/inflate_foreign $(ROOT)build/foreign_small/*.gz
+	ASAN_OPTIONS=detect_leaks=0 $(ROOT)build/inflate_foreign $(ROOT)build/foreign_large/*.gz

@@ -87,7 +87,9 @@ struct HuffT {
   int ncodes;
   static constexpr int fastbits = FAST;
 
-  // returns false for an over-subscribed set, or an incomplete one that is not a single code
+  // returns false for an over-subscribed set, or an incomplete one that is not a single code of one bit (zlib's rule,
+  // inftrees.c: "left > 0 && max != 1" is an incomplete set; a single code of two bits and more was taken here until
+  // a member with one — tests/deflate_craft.py, one-dist-code-of-two-bits — came out as bytes where zlib gives an error)
   SPZ_INF_HD bool build(const uint8_t *lens, int n) {
     SPZ_INF_NO_UNROLL
     for (int i = 0; i < 16; ++i) count[i] = 0;
@@ -102,7 +104,7 @@ struct HuffT {
       left -= count[len];
       if (left < 0) return false;
     }
-    if (left > 0 && ncodes != 1 && ncodes != 0) return false;
+    if (left > 0 && ncodes != 0 && !(ncodes == 1 && count[1] == 1)) return false;
     offs[0] = 0;
     offs[1] = 0;
     SPZ_INF_NO_UNROLL
@@ -202,10 +204,14 @@ SPZ_INF_HD void buildStatic(HL *lit, HD *dist, uint8_t *lens /* 316 bytes of the
   for (int i = 280; i < 288; ++i) l[i] = 8;
   lit->build(l, 288);
   lit->pack(false);
+  // All 32 five-bit codes: 30 of them are an incomplete set, which build() refuses BEFORE it fills a table — until the
+  // members of tests/deflate_craft.py every fixed block's matches were read with whatever the tables held before (the
+  // previous block's code, or nothing at all: pack() then indexed ent[] with it), and the CRC check sent the member to
+  // the serial readers.  Codes 30 and 31 are ENT_INVALID through pack().
   uint8_t *d = lens;
   SPZ_INF_NO_UNROLL
-  for (int i = 0; i < 30; ++i) d[i] = 5;
-  dist->build(d, 30);
+  for (int i = 0; i < 32; ++i) d[i] = 5;
+  dist->build(d, 32);
   dist->pack(true);
 }
 
@@ -220,7 +226,7 @@ struct HeaderWork {
   uint32_t walked;  // code-length symbols the last header check decoded (statistics of the device's search)
 };
 
-// Same acceptance rule as HuffT::build(): not over-subscribed, and complete unless it has at most one code.
+// Same acceptance rule as HuffT::build(): not over-subscribed, and complete unless it has no code or a single one of one bit.
 SPZ_INF_HD bool completeCode(const uint8_t *lens, int n, int *ncodes, uint16_t *count) {
   SPZ_INF_NO_UNROLL
   for (int i = 0; i < 16; ++i) count[i] = 0;
@@ -235,7 +241,7 @@ SPZ_INF_HD bool completeCode(const uint8_t *lens, int n, int *ncodes, uint16_t *
     if (left < 0) return false;
   }
   *ncodes = codes;
-  return !(left > 0 && codes != 1 && codes != 0);
+  return !(left > 0 && codes != 0 && !(codes == 1 && count[1] == 1));
 }
 
 // Reads a dynamic block's code lengths (after the 3 header bits): lens[0 .. hlit) literal/length, lens[hlit .. hlit + hdist)
@@ -263,7 +269,7 @@ SPZ_INF_HD bool readCodeLengths(const In &in, uint64_t *at, HeaderWork *w, int *
   }
   pos += 3 * static_cast<uint64_t>(hclen);
   if (!clh.build(cl, 19)) return false;
-  if (clh.ncodes < 1) return false;
+  if (clh.ncodes < 2) return false;  // the code-length code must be complete (zlib: "invalid code lengths set")
   int n = 0;
   const int total = hlit + hdist;
   // (lens[] is not cleared: every entry below hlit + hdist is written before it is read — a repeat code reads the one
@@ -552,8 +558,9 @@ SPZ_INF_HD bool hasValidDynamicHeader(const In &in, uint64_t p, HeaderWork *w) {
   }
   if (bad) return false;
   if (pos > in.nbits || !eob_has_code) return false;
-  // complete, unless it has at most one code (HuffT::build()'s rule); two literal / length codes at least
-  const bool lit_ok = kraft_lit == 32768u || codes_lit <= 1, dist_ok = kraft_dist == 32768u || codes_dist <= 1;
+  // complete, unless it has no code or a single one of one bit (HuffT::build()'s rule); two literal / length codes at least
+  const bool lit_ok = kraft_lit == 32768u || codes_lit <= 1,
+             dist_ok = kraft_dist == 32768u || codes_dist == 0 || (codes_dist == 1 && kraft_dist == 16384u);
   return lit_ok && dist_ok && codes_lit >= 2;
 }
 

@@ -19,8 +19,10 @@
 // Runs of stored blocks (incompressible sections) have no dynamic header to find: their blocks are found by their own
 // pattern (00 LEN ~LEN at a byte boundary, leading to another header).  Raw bytes now and then read like a block header: the chunk before such a look-alike does not end on it, so the
 // look-alike is dropped and the chunk resumes, from the block that ran past it, towards the next start.
-// Anything else irregular (a reference where there is no predecessor, a chunk that expands more than 8x, data
-// that opens with a stored block) declines: the caller's host readers take over.
+// Data that opens with a stored block is decoded like any other (chunk 0 starts at bit 0 whatever the block type).
+// Anything else irregular (a reference where there is no predecessor, a chunk that expands more than 8x, no dynamic
+// block to start a second chunk at, bytes carried through more than 2048 chunks) declines: the caller's host readers
+// take over.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

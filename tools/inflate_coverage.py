@@ -7,6 +7,11 @@ readers give the same bytes), so it never shows in a test — this campaign coun
 the device inflated and the reason for every one it did not (spz_amd_inflate_last_decline).
 
   python tools/inflate_coverage.py [--per-cell 6] > profiles/r03_inflate_coverage.json
+
+--foreign walks the members no zlib writes instead (the case table of tests/deflate_craft.py, at the sizes of
+tests/test_gpu_inflate_foreign.py): per case the verdict, who gave it and the member's and the output's size.
+
+  python tools/inflate_coverage.py --foreign > profiles/inflate_foreign_coverage.json
 """
 import argparse
 import json
@@ -50,11 +55,33 @@ def spz_stream(n_points, deg, seed):
     return spz._pack_to_stream(g, spz.PackOptions())
 
 
+def foreign():
+    import deflate_craft as dc
+    import spz_amd.spz as spz
+    from test_gpu_inflate_foreign import CHAIN_SIZE, NAMES, SIZE
+    rows = []
+    for name in NAMES:
+        kind, gz, want = dc.build(name, CHAIN_SIZE.get(name, SIZE))
+        before = spz._device_inflate_count()
+        out = spz._decompress_gzipped(gz)
+        took = spz._device_inflate_count() == before + 1
+        # (a member with FHCRC or a reserved flag goes to zlib before the device reader is asked: no reason of its own)
+        asked = name not in ("headers-fhcrc", "bad-fhcrc", "bad-reserved-flg")
+        rows.append({"case": name, "kind": kind, "member_bytes": len(gz), "output_bytes": None if want is None else len(want),
+                     "verdict_is_zlibs": out == want,
+                     "result": "device" if took else (asked and spz._device_inflate_last_decline()) or "not-asked"})
+    print(json.dumps({"cases": len(rows), "all_verdicts_zlibs": all(r["verdict_is_zlibs"] for r in rows), "table": rows}, indent=1))
+    sys.exit(0 if all(r["verdict_is_zlibs"] for r in rows) else 1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--per-cell", type=int, default=4)
+    ap.add_argument("--foreign", action="store_true")
     a = ap.parse_args()
     os.environ["SPZ_AMD_GUNZIP_DEVICE"] = "1"
+    if a.foreign:
+        return foreign()
     import spz_amd.spz as spz
     rng = np.random.default_rng(2025)
     writers = [("zlib-1", 1, 9), ("zlib-6", 6, 9), ("zlib-9", 9, 9), ("zlib-6-mem8", 6, 8), ("zlib-1-mem8", 1, 8)]
