@@ -707,7 +707,8 @@ int spz_amd_align_host(const spz_amd_align_cloud *source, const spz_amd_align_cl
  *      T = 1, C = 0, in that order: power = -0.5 (A dx^2 + C dy^2) - B dx dy, skip if power > 0; a = min(0.99,
  *      opacity exp(power)), skip if a < 1/255; T' = T (1 - a), stop if T' < 1e-4; C += T a rgb; T = T'.
  *      Image: height x width x 4 float32, row-major, RGB = C + T background, alpha = 1 - T, not clamped.
- *      Deterministic: no float atomics; a run repeats its bits.
+ *      Deterministic: no float atomics; a run repeats its bits.  (That is the forward's promise alone: "render backward"
+ *      below sums with f32 atomic adds and need not repeat its bits.)
  *
  *      render_check_params (host only, no GPU): the argument checks above.  render_workspace_bytes (host only): device
  *      memory for the device forms at n Gaussians and max_entries (tile, Gaussian) entries; the prepare step touches
@@ -760,6 +761,52 @@ int spz_amd_render_host(const uint8_t *d_stream, size_t size, const spz_amd_head
 int spz_amd_render_cloud_host(const spz_amd_cloud_in *h_cloud, uint64_t num_points, int sh_degree, int antialiased,
                               const spz_amd_render_params *params, int device, float *h_rgba, uint64_t *h_entries,
                               float *h_ms);
+
+/* ---- render backward: the gradients of one view to a float cloud (spz_render_backward.hip; DESIGN §8 "Render
+ *      backward").  The reference has no counterpart.  Given G (height x width x 4 float32), the gradient of a scalar
+ *      loss to the image of render_finish_device, it produces that loss's gradient to the six arrays of the float cloud
+ *      the image was prepared from: positions, log scales, rotations (xyzw, unnormalised), alphas (pre-sigmoid), colours
+ *      and sh, in the shapes and order of spz_amd_cloud_in.  The packed streams have no backward.
+ *
+ *      It is the exact derivative of the forward as "render" words it, with every discrete decision held constant:
+ *      visibility, radius, tile rectangle, depth order, "skip if power > 0", "skip if a < 1/255" and "stop if T' < 1e-4".
+ *      Skipped pairs, the stopping pair and everything after it contribute nothing.  a = min(0.99, .) passes no gradient
+ *      where it clamps (the pair's rgb still gets its own).  max(0, rgb) passes none where it clamps: not to colour and
+ *      sh, and not to the position through the view direction.  The clamp of x/z and y/z in J passes none through the
+ *      clamped quotient where it clamps (J still depends on z there); where it does not clamp, J's dependence on the
+ *      position is differentiated.  The position gets gradient through the mean, through J and through the normalised
+ *      view direction of the sh bands; the quaternion through its normalisation to the raw xyzw.  With the antialiased
+ *      flag sqrt(max(0, det_before) / det_after) is differentiated, and is zero where det_before <= 0.  The background
+ *      term T_final background and the alpha channel 1 - T_final are part of the image and are differentiated.  Sh
+ *      coefficients above min(file degree, max_sh_degree) get exactly 0; an invisible Gaussian gets exactly 0 in every
+ *      array.  Every element of the six arrays is written (not accumulated into).
+ *      Arithmetic.  The blend's part re-evaluates power, a, T' and the three tests with the forward blend's f32
+ *      expressions, so it uses the pairs the image used, and forms each used pair's gradient to the record's nine floats
+ *      (mean 2, conic 3, opacity 1, rgb 3) in f32.  They are summed per Gaussian with f32 atomic adds, in an order that
+ *      is not fixed: a run need not repeat its bits.  The per-Gaussian chain from those nine values to the six arrays
+ *      runs in f64 from the f32 inputs, like the forward's preprocess, and uses no atomics.
+ *
+ *      render_backward_workspace_bytes (host only): device memory for the n x 9 record gradients.
+ *      render_backward_device: d_cloud, num_points, sh_degree, antialiased, params and max_entries as given to
+ *      prepare_cloud_device and render_finish_device; d_render_workspace exactly as render_finish_device left it (the
+ *      records, the sorted entries, the tile ranges and the total are read; nothing is sorted again and nothing in it is
+ *      written).  d_image: the image render_finish_device wrote, or NULL; it is not read, because alpha = 1 - T_final
+ *      keeps T_final only to 2^-24 absolute: each pixel's final colour sum and T are blended again instead.
+ *      d_grad_image: G.  d_grads: six device pointers (sh may be NULL iff sh_degree == 0).  d_record_grads (may be NULL):
+ *      n x 9 floats out, the record gradients in input order.  *d_status (device memory, uint32) = 0, or 1 when the
+ *      total is above max_entries: then no gradient is written.  Arguments are checked on the host before any launch
+ *      (a bad one: SPZ_AMD_ERR_INVALID_ARG; no device: SPZ_AMD_ERR_NO_DEVICE).  Enqueues on hip_stream and does not
+ *      synchronise. */
+typedef struct {
+  float *positions, *scales, *rotations, *alphas, *colors, *sh;
+} spz_amd_cloud_grads;
+
+uint64_t spz_amd_render_backward_workspace_bytes(uint64_t num_points);
+int spz_amd_render_backward_device(const spz_amd_cloud_in *d_cloud, uint64_t num_points, int sh_degree, int antialiased,
+                                   const spz_amd_render_params *params, uint64_t max_entries, const float *d_image,
+                                   const float *d_grad_image, const spz_amd_cloud_grads *d_grads, float *d_record_grads,
+                                   uint32_t *d_status, const void *d_render_workspace, void *d_backward_workspace,
+                                   void *hip_stream);
 
 /* ---- render scores: per-Gaussian blend weights of one view (spz_render.hip; DESIGN §8 "Prune").  The reference has
  *      no counterpart.  With the workspace of a prepare step (as for render_finish_device), the blend of the render

@@ -85,6 +85,7 @@ EXPORTS = (
     "spz_amd_render_cloud_host", "spz_amd_render_score_device", "spz_amd_prune_keep_count", "spz_amd_prune_open",
     "spz_amd_prune_fetch", "spz_amd_prune_device_data", "spz_amd_prune_close",
     "spz_amd_render_depth_device", "spz_amd_render_depth_host", "spz_amd_render_depth_cloud_host",
+    "spz_amd_render_backward_workspace_bytes", "spz_amd_render_backward_device",
     "spz_amd_image_metrics_check", "spz_amd_image_metrics_workspace_bytes", "spz_amd_image_metrics_device",
     "spz_amd_image_metrics_host", "spz_amd_compare_host",
 )
@@ -111,7 +112,7 @@ class Layout(C.Structure):
 
 
 class CloudPtrs(C.Structure):
-    """spz_amd_cloud_in / spz_amd_cloud_out (same layout: six pointers)."""
+    """spz_amd_cloud_in / spz_amd_cloud_out / spz_amd_cloud_grads (same layout: six pointers)."""
     _fields_ = [(k, C.c_void_p) for k in ("positions", "scales", "rotations", "alphas", "colors", "sh")]
 
 
@@ -541,6 +542,11 @@ def bind(L):
     L.spz_amd_render_score_device.argtypes = [u64, C.POINTER(RenderParams), u64, vp, vp, vp, vp, vp, vp]
     L.spz_amd_render_depth_device.restype = i32
     L.spz_amd_render_depth_device.argtypes = [u64, C.POINTER(RenderParams), u64, vp, vp, vp, vp, vp, vp]
+    L.spz_amd_render_backward_workspace_bytes.restype = u64
+    L.spz_amd_render_backward_workspace_bytes.argtypes = [u64]
+    L.spz_amd_render_backward_device.restype = i32
+    L.spz_amd_render_backward_device.argtypes = [C.POINTER(CloudPtrs), u64, i32, i32, C.POINTER(RenderParams), u64, vp, vp,
+                                                 C.POINTER(CloudPtrs), vp, vp, vp, vp, vp]
     L.spz_amd_render_depth_host.restype = i32
     L.spz_amd_render_depth_host.argtypes = [vp, sz, C.POINTER(Header), C.POINTER(RenderParams), i32, vp, vp, vp,
                                             C.POINTER(u64), vp]

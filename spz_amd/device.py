@@ -967,6 +967,120 @@ def render(cloud, num_points, sh_degree, params, antialiased=False, max_entries=
                    return_info, stream)
 
 
+def _rendered_workspace(L, source, n, params, dev, max_entries, st):
+    """Prepare + finish on st, keeping the workspace: (image, workspace, m).  Raises when the total is above
+    max_entries (one word is read back)."""
+    h, w = params.height, params.width
+    image = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws, m = _prepared_workspace(L, source, n, params, dev, max_entries, total, st)
+    rc = L.spz_amd_render_finish_device(n, C.byref(params), m, image.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                                        C.c_void_p(st.cuda_stream))
+    abi.check(rc, "spz_amd_render_finish_device")
+    if max_entries is not None and int(status.cpu()[0]) != 0:  # on st: waits for the finish step
+        raise RuntimeError(f"{int(total.cpu()[0])} tile entries is above max_entries = {max_entries}")
+    return image, ws, m
+
+
+def _render_backward(L, ptrs, n, sh_degree, antialiased, params, m, image, grad_image, ws, dev, want_records, st):
+    """Enqueue spz_amd_render_backward_device on st over the workspace ws of a finished render: (grads, record_grads)."""
+    grads = alloc_cloud(n, sh_degree, dev)
+    gp = abi.CloudPtrs(*[grads[k].data_ptr() if grads[k].numel() else None for k in FIELDS])
+    rec = torch.empty((n, 9), dtype=torch.float32, device=dev) if want_records else None
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    bws = torch.empty(int(L.spz_amd_render_backward_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+    rc = L.spz_amd_render_backward_device(C.byref(ptrs), n, sh_degree, 1 if antialiased else 0, C.byref(params), m,
+                                          image.data_ptr(), grad_image.data_ptr(), C.byref(gp),
+                                          rec.data_ptr() if rec is not None and n else None, status.data_ptr(),
+                                          ws.data_ptr(), bws.data_ptr(), C.c_void_p(st.cuda_stream))
+    abi.check(rc, "spz_amd_render_backward_device")
+    return grads, rec
+
+
+def _check_grad_image(grad_image, params, dev):
+    shape = (params.height, params.width, 4)
+    if (not isinstance(grad_image, torch.Tensor) or grad_image.dtype != torch.float32 or grad_image.device != dev
+            or tuple(grad_image.shape) != shape):
+        raise ValueError(f"grad_image must be a float32 tensor of shape {shape} on {dev}")
+    return grad_image.contiguous()
+
+
+def render_backward(cloud, num_points, sh_degree, params, grad_image, *, antialiased=False, max_entries=None,
+                    return_record_grads=False, stream=None):
+    """The gradients of a scalar loss to a float cloud, given grad_image = its gradient to the image of render() (a
+    (height, width, 4) float32 CUDA tensor): renders (prepare + finish), then spz_amd_render_backward_device over the
+    same workspace (include/spz_amd.h "render backward").  Returns a dict of six flat float32 CUDA tensors keyed and
+    shaped like the cloud; with return_record_grads also "records", (n, 9): the gradients to each Gaussian's mean 2,
+    conic 3, opacity 1 and rgb 3.  Sums with f32 atomic adds: two runs may differ in the last bits.  max_entries: as
+    render(), but a total above it raises RuntimeError.  stream: as render()."""
+    ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
+    L = abi.load_library()
+    _check_render_args(L, params, max_entries)
+    grad_image = _check_grad_image(grad_image, params, dev)
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        with torch.cuda.stream(st):
+            source = ("cloud", ptrs, num_points, int(sh_degree), antialiased)
+            image, ws, m = _rendered_workspace(L, source, num_points, params, dev, max_entries, st)
+            grads, rec = _render_backward(L, ptrs, num_points, int(sh_degree), antialiased, params, m, image, grad_image,
+                                          ws, dev, return_record_grads, st)
+    if return_record_grads:
+        grads["records"] = rec
+    return grads
+
+
+class _RenderFunction(torch.autograd.Function):
+    """render() with a backward: the forward keeps its workspace (a tensor of this call alone, never reused), the
+    backward runs spz_amd_render_backward_device over it on the current stream.  The six arrays are saved with
+    save_for_backward, so changing one in place before the backward raises torch's usual error."""
+
+    @staticmethod
+    def forward(ctx, num_points, sh_degree, params, antialiased, max_entries, *arrays):
+        cloud = dict(zip(FIELDS, (a.detach() for a in arrays)))
+        ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
+        L = abi.load_library()
+        _check_render_args(L, params, max_entries)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev)
+            source = ("cloud", ptrs, num_points, int(sh_degree), antialiased)
+            image, ws, m = _rendered_workspace(L, source, num_points, params, dev, max_entries, st)
+        ctx.save_for_backward(image, ws, *arrays)
+        ctx.args = (num_points, int(sh_degree), params, bool(antialiased), m)
+        return image
+
+    @staticmethod
+    def backward(ctx, grad_image):
+        image, ws = ctx.saved_tensors[:2]
+        arrays = ctx.saved_tensors[2:]
+        num_points, sh_degree, params, antialiased, m = ctx.args
+        cloud = dict(zip(FIELDS, (a.detach() for a in arrays)))
+        ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
+        L = abi.load_library()
+        grad_image = _check_grad_image(grad_image, params, dev)
+        with torch.cuda.device(dev):
+            grads, _ = _render_backward(L, ptrs, num_points, sh_degree, antialiased, params, m, image, grad_image, ws,
+                                        dev, False, torch.cuda.current_stream(dev))
+        out = tuple(grads[k].view_as(a) if need else None
+                    for k, a, need in zip(FIELDS, arrays, ctx.needs_input_grad[5:]))
+        return (None,) * 5 + out
+
+
+def render_autograd(cloud, num_points, sh_degree, params, antialiased=False, max_entries=None):
+    """render() as a differentiable torch operation: the (height, width, 4) image, bit-identical to render()'s, whose
+    backward() gives the six arrays of cloud their gradients (those that require grad; the others get None).  Runs on
+    the current stream.  The backward is the exact derivative of the forward with its discrete decisions held constant
+    (include/spz_amd.h "render backward") and sums with f32 atomic adds.  A total above max_entries raises
+    RuntimeError.  A cloud without sh (degree 0) may leave "sh" out."""
+    arrays = []
+    for k in FIELDS:
+        t = cloud.get(k)
+        if t is None:
+            t = torch.empty(0, dtype=torch.float32, device=cloud["positions"].device)
+        arrays.append(t)
+    return _RenderFunction.apply(num_points, sh_degree, params, antialiased, max_entries, *arrays)
+
+
 def render_packed(stream_t, header, params, max_entries=None, out=None, return_info=False, stream=None):
     """The image of a packed device stream (any version), decoded as loadSpz(to = params.coord) would: bit-identical to
     render() of the decoded floats.  Otherwise as render()."""
