@@ -951,6 +951,115 @@ int spz_amd_compare_host(const uint8_t *d_stream_a, size_t size_a, const spz_amd
                          spz_amd_image_metrics *h_metrics, float *h_ssim_maps, uint64_t *h_entries, float *h_ms,
                          int32_t *h_bad_view);
 
+/* ---- image loss: the 3DGS training loss of a render against a target, and its gradient to the render
+ *      (spz_metrics.hip; DESIGN §8 "Refine").  The reference has no counterpart.
+ *        L = (1 - lambda) l1 + lambda (1 - ssim)           (Kerbl et al. 2023, loss_utils)
+ *      with l1 and ssim exactly the quantities of "image metrics" above: the first three channels, each value clamped to
+ *      [0, 1] first (NaN -> 0), the 11x11 window with zero padding, means over 3 H W, in f64.  lambda in [0, 1].
+ *      Inputs.  a (the render) and b (the target): height x width x C float32, C in {3, 4}, independently; width,
+ *      height 1..16384 (image_metrics_check).  d_loss (device memory, 8-aligned): three doubles, L, l1 and ssim; l1 and
+ *      ssim carry the bits image_metrics_device gives for the same pair.  d_grad (device memory): dL/da, height x width
+ *      x C_a float32; with C_a = 4 it is the d_grad_image of render_backward_device.
+ *      Gradient.  Every element of d_grad is written.  A fourth channel gets exactly 0.  The clamp passes gradient where
+ *      0 <= a <= 1, both ends included (as torch.clamp: a render over a black background is exactly 0 over much of the
+ *      image), and nothing elsewhere or for NaN.  The L1 part is sign(a - b) / (3 H W) on the clamped values, sign(0) =
+ *      0.  The SSIM part, per channel and window q with A1 = 2 mu_a mu_b + C1, A2 = 2 s_ab + C2, B1 = mu_a^2 + mu_b^2 +
+ *      C1, B2 = s_a + s_b + C2, S = A1 A2 / (B1 B2):  P = 2 A1 / (B1 B2) (to g*(ab)), Q = -S / B2 (to g*a^2), M =
+ *      2 mu_b (A2 - A1) / (B1 B2) - 2 mu_a S (1 / B1 - 1 / B2) (to mu_a, in total);  d ssim / d a(p) = ((g*M)(p) +
+ *      2 a(p) (g*Q)(p) + b(p) (g*P)(p)) / (3 H W), the same zero-padded "same" convolutions, the maps zero outside the
+ *      image.  dL/da = (1 - lambda) dl1/da - lambda dssim/da.
+ *      Arithmetic.  Two passes: the metrics' tile pass, which also stores M, Q and P of each channel as nine f64 planes,
+ *      and a tile pass that filters them.  Everything is f64 up to the one rounding of each gradient value to f32.  No
+ *      float atomics; the partial sums go through the metrics' slab in its fixed order: a run repeats its bits.
+ *      image_loss_workspace_bytes (host only): device memory for the device form, 72 H W bytes and the slab (0 for a bad
+ *      size).  image_loss_device: arguments checked on the host before any launch (SPZ_AMD_ERR_INVALID_ARG; no device:
+ *      SPZ_AMD_ERR_NO_DEVICE); enqueues on hip_stream and does not synchronise.
+ *
+ * ---- adam step: one Adam update of the trained arrays of a float cloud (spz_refine.hip; DESIGN §8 "Refine").  The
+ *      reference has no counterpart.  d_params, d_grads, d_m, d_v: the six arrays (as spz_amd_cloud_in orders and shapes
+ *      them), their gradients and their first and second moments.  train_mask: bit 0 positions, 1 scales, 2 rotations,
+ *      3 alphas, 4 colours, 5 sh; non-zero.  An array whose bit is clear is neither read nor written, and its four
+ *      pointers may be NULL; sh may be NULL when sh_degree == 0 as well.
+ *      Scalars (spz_amd_adam_scalars_of, host only, computes them in f64 for step t >= 1 and rounds each to f32):
+ *      beta1, c1 = 1 - beta1, beta2, c2 = 1 - beta2, eps, r = sqrt(1 - beta2^t), and per array s = lr / (1 - beta1^t).
+ *      Per element, in f32, each operation rounded once and none contracted (torch's form of Adam):
+ *        m' = beta1 m + c1 g;  v' = beta2 v + (c2 g) g;  den = sqrt(v') / r + eps;  p' = p - s (m' / den).
+ *      An element whose p or g is not finite is left untouched, moments included (the decoded alphas of bytes 0 and 255
+ *      are -inf and +inf and stay so), and counted: *d_skipped (device memory, uint32, zeroed by the caller) grows by
+ *      their number, with one vector integer atomic per workgroup that has any.  One launch; 16-byte accesses from the
+ *      first 16-aligned parameter address of each array, scalar elements before and after.  Arguments checked on the
+ *      host before the launch; enqueues on hip_stream and does not synchronise.
+ *
+ * ---- refine: a packed stream fitted to a target stream over a set of views (spz_refine.hip; DESIGN §8 "Refine").
+ *      A (the stream to improve) and B (the target), both in device memory with their headers; they may differ in point
+ *      count, SH degree and version, as in compare.  views: 1..SPZ_AMD_REFINE_MAX_VIEWS render params, each passing
+ *      render_check_params, all with one coord (a bad one: SPZ_AMD_ERR_INVALID_ARG before anything is launched, the view
+ *      in *h_bad_view).  options: iterations >= 0; lambda_dssim in [0, 1]; lr[6] >= 0 in the train_mask's order; beta1,
+ *      beta2 in [0, 1); eps >= 0; train_mask non-zero (refine_check, host only; refine_default_options: 3DGS's published
+ *      arguments, every array trained, lr[0] = 1.6e-4 for a scene of unit extent).
+ *      Run.  Every view of B rendered once with the packed path and kept (16 W H bytes per view, beside four float
+ *      clouds of A's size and 104 W H bytes for the largest view); the "before" metrics (image_metrics_device) of A's
+ *      packed render against it.  A decoded once to a float cloud in the views' coord, the moments zeroed.  Iteration i
+ *      uses view i mod V: render_prepare_cloud_device with A's antialiased flag, the total read back, the workspace
+ *      grown (grow-only), render_finish_device; image_loss_device against the kept target; render_backward_device;
+ *      adam_step_device with t = i + 1.  A total above 2^31 - 1: SPZ_AMD_ERR_CAPACITY, the view in *h_bad_view.
+ *      h_history[i] (iterations doubles) = L before step i.
+ *      Output: a stream with A's header (version, fractional bits, sh degree, antialiased flag, point count).  The
+ *      sections of trained arrays are encoded from the floats with the encode kernel, from the views' coord back to the
+ *      file's; the sections of untrained arrays are A's bytes: refine does not requantise what it does not train.  With
+ *      iterations == 0 the output is A's bytes and after equals before.  The encode kernel writes versions 2 and 3 and
+ *      positions at 12 fractional bits: a version 1 input, or trained positions at another precision, with iterations
+ *      > 0: SPZ_AMD_ERR_UNSUPPORTED.  h_after: the metrics of the OUTPUT STREAM, rendered with the packed path, against
+ *      the kept targets: the claim is about the file, quantisation included.
+ *      The backward sums with f32 atomic adds, so a refine need not repeat its bits; with at least one iteration
+ *      h_history[0] does, because it comes before any step.
+ *      open (shaped like prune's) runs on `device` on a stream of its own and blocks.  h_before, h_after (may be NULL):
+ *      num_views results each; *h_skipped (may be NULL): the non-finite elements the steps left alone, summed over the
+ *      steps; h_ms (may be NULL): [0] wall-clock milliseconds of the targets and "before" metrics, [1] of the
+ *      iterations and the encode, [2] of the "after" metrics; *h_bad_view (may be NULL): the view a failure concerns,
+ *      else -1. */
+enum {
+  SPZ_AMD_REFINE_MAX_VIEWS = 1024,
+  SPZ_AMD_TRAIN_POSITIONS = 1,
+  SPZ_AMD_TRAIN_SCALES = 2,
+  SPZ_AMD_TRAIN_ROTATIONS = 4,
+  SPZ_AMD_TRAIN_ALPHAS = 8,
+  SPZ_AMD_TRAIN_COLORS = 16,
+  SPZ_AMD_TRAIN_SH = 32,
+  SPZ_AMD_TRAIN_ALL = 63
+};
+typedef struct {
+  float beta1, c1, beta2, c2, eps, r;
+  float s[6];
+} spz_amd_adam_scalars;
+typedef struct {
+  int32_t iterations;
+  uint32_t train_mask;
+  double lambda_dssim;
+  double lr[6];
+  double beta1, beta2, eps;
+} spz_amd_refine_options;
+uint64_t spz_amd_image_loss_workspace_bytes(int width, int height);
+int spz_amd_image_loss_device(const float *d_a, int channels_a, const float *d_b, int channels_b, int width, int height,
+                              double lambda_dssim, double *d_loss, float *d_grad, void *d_workspace, void *hip_stream);
+int spz_amd_adam_scalars_of(int t, const double lr[6], double beta1, double beta2, double eps,
+                            spz_amd_adam_scalars *out);
+int spz_amd_adam_step_device(const spz_amd_cloud_grads *d_params, const spz_amd_cloud_grads *d_grads,
+                             const spz_amd_cloud_grads *d_m, const spz_amd_cloud_grads *d_v, uint64_t num_points,
+                             int sh_degree, unsigned train_mask, spz_amd_adam_scalars scalars, uint32_t *d_skipped,
+                             void *hip_stream);
+int spz_amd_refine_default_options(spz_amd_refine_options *options);
+int spz_amd_refine_check(const spz_amd_refine_options *options);
+int spz_amd_refine_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
+                        const uint8_t *d_stream_b, size_t size_b, const spz_amd_header *hdr_b,
+                        const spz_amd_render_params *views, int num_views, const spz_amd_refine_options *options,
+                        int device, void **ctx, uint64_t *h_out_bytes, double *h_history,
+                        spz_amd_image_metrics *h_before, spz_amd_image_metrics *h_after, uint64_t *h_skipped, float *h_ms,
+                        int32_t *h_bad_view);
+int spz_amd_refine_fetch(void *ctx, uint8_t *h_out);
+const uint8_t *spz_amd_refine_device_data(void *ctx);
+void spz_amd_refine_close(void *ctx);
+
 /* ---- device buffers for a resident cloud, placed for speed (spz_place.hip).  Whether an sh3 decode runs
  *      at 0.46 ms or at 0.55 ms is decided by whether the sh float array shares a physical region of HBM with the other
  *      arrays of the launch; that cannot be asked for, but it shows in one launch.  alloc: the five small arrays (and a

@@ -548,6 +548,44 @@ bool compareSpz(const uint8_t *dataA, int32_t sizeA, const uint8_t *dataB, int32
                 std::vector<std::vector<float>> *ssimMaps = nullptr);
 bool compareImages(const float *a, int channelsA, const float *b, int channelsB, int width, int height,
                    ImageMetrics *metrics, std::vector<float> *ssimMap = nullptr);
+// Refine (DESIGN §8 "Refine"): a file fitted to a target file over views, closed-loop: the lossy edits (decimateSpz,
+// pruneSpz, filterSpz to a lower degree, the coarse tiles of tileSpz) write a smaller file, compareSpz says what that
+// cost, and refineSpz gives some of it back (include/spz_amd.h "image loss", "adam step" and "refine" state the
+// contract).  The target is rendered once from every view; then `iterations` steps of Adam on the 3DGS loss
+// (1 - lambdaDssim) l1 + lambdaDssim (1 - ssim), view i mod V at step i, over the arrays `train` names; then the trained
+// sections are encoded again under the input's header, and the sections of untrained arrays keep the input's bytes.
+// The defaults are 3DGS's published arguments; positionLr unset: 1.6e-4 times the radius of boundingSphere of the
+// target's positions.  The report's "after" metrics are of the written stream, quantisation included.  The backward sums
+// with f32 atomics, so two runs may differ in the last bits.  false + one "[SPZ ERROR] refineSpz: …" line on a bad
+// argument (lastDeviceStatus() = SPZ_AMD_ERR_INVALID_ARG; a bad view is named by its index), an input that does not load,
+// a version 1 input (SPZ_AMD_ERR_UNSUPPORTED), or a device failure.  SPZ_AMD_REFINE_TIMING=1 prints the stages' times.
+struct RefineOptions {
+  enum Train { Positions = 1, Scales = 2, Rotations = 4, Alphas = 8, Colors = 16, Sh = 32, All = 63 };
+  std::vector<PruneOptions::View> views;
+  CoordinateSystem coord = CoordinateSystem::UNSPECIFIED;
+  float nearPlane = 0.2f;
+  std::array<float, 3> background = {0.0f, 0.0f, 0.0f};
+  int maxShDegree = 3;
+  int iterations = 200;
+  double lambdaDssim = 0.2;
+  std::optional<double> positionLr;
+  double scaleLr = 5e-3, rotationLr = 1e-3, alphaLr = 5e-2, colorLr = 2.5e-3, shLr = 2.5e-3 / 20.0;
+  double beta1 = 0.9, beta2 = 0.999, eps = 1e-15;
+  unsigned train = All;
+};
+struct RefineReport {
+  std::vector<double> history;               // the loss before each step
+  std::vector<ImageMetrics> before, after;   // per view, against the target's render
+  uint64_t skipped = 0;                      // non-finite elements the steps left alone, summed over the steps
+  double positionLr = 0.0;                   // the rate used
+  float ms[3] = {0.0f, 0.0f, 0.0f};          // targets + before, iterations + encode, after
+};
+bool refineSpz(const uint8_t *data, int32_t size, const uint8_t *target, int32_t targetSize, const RefineOptions &options,
+               std::vector<uint8_t> *out, RefineReport *report = nullptr);
+bool refineSpz(const std::vector<uint8_t> &data, const std::vector<uint8_t> &target, const RefineOptions &options,
+               std::vector<uint8_t> *out, RefineReport *report = nullptr);
+bool refineSpz(const std::string &inputFilename, const std::string &targetFilename, const std::string &outputFilename,
+               const RefineOptions &options, RefineReport *report = nullptr);
 // Status (spz_amd.h codes) of the last device call made by this thread; 0 = ok.
 int lastDeviceStatus();
 void setLastDeviceStatus(int status);

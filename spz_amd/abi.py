@@ -88,6 +88,9 @@ EXPORTS = (
     "spz_amd_render_backward_workspace_bytes", "spz_amd_render_backward_device",
     "spz_amd_image_metrics_check", "spz_amd_image_metrics_workspace_bytes", "spz_amd_image_metrics_device",
     "spz_amd_image_metrics_host", "spz_amd_compare_host",
+    "spz_amd_image_loss_workspace_bytes", "spz_amd_image_loss_device", "spz_amd_adam_scalars_of",
+    "spz_amd_adam_step_device", "spz_amd_refine_default_options", "spz_amd_refine_check", "spz_amd_refine_open",
+    "spz_amd_refine_fetch", "spz_amd_refine_device_data", "spz_amd_refine_close",
 )
 
 RCCL_UNIQUE_ID_BYTES = 128
@@ -172,6 +175,23 @@ class ImageMetrics(C.Structure):
     """spz_amd_image_metrics: the five results of one image pair (include/spz_amd.h "image metrics")."""
     _fields_ = [("mse", C.c_double), ("psnr", C.c_double), ("ssim", C.c_double), ("l1", C.c_double),
                 ("max_abs", C.c_double)]
+
+
+REFINE_MAX_VIEWS = 1024
+TRAIN_ARRAYS = ("positions", "scales", "rotations", "alphas", "colors", "sh")   # bit k of a train_mask
+TRAIN_ALL = 63
+
+
+class AdamScalars(C.Structure):
+    """spz_amd_adam_scalars: the f32 scalars of one Adam step (include/spz_amd.h "adam step")."""
+    _fields_ = [("beta1", C.c_float), ("c1", C.c_float), ("beta2", C.c_float), ("c2", C.c_float), ("eps", C.c_float),
+                ("r", C.c_float), ("s", C.c_float * 6)]
+
+
+class RefineOptions(C.Structure):
+    """spz_amd_refine_options (include/spz_amd.h "refine")."""
+    _fields_ = [("iterations", C.c_int32), ("train_mask", C.c_uint32), ("lambda_dssim", C.c_double),
+                ("lr", C.c_double * 6), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
 
 
 class TileInfo(C.Structure):
@@ -578,6 +598,31 @@ def bind(L):
                                        i32, i32, C.POINTER(ImageMetrics), vp, vp, vp, C.POINTER(C.c_int32)]
     L.spz_amd_zlib_encode_blocks.restype = i32
     L.spz_amd_zlib_encode_blocks.argtypes = [vp, vp, u32, u32, vp, vp, vp, u64, u64, vp, vp]
+    L.spz_amd_image_loss_workspace_bytes.restype = u64
+    L.spz_amd_image_loss_workspace_bytes.argtypes = [i32, i32]
+    L.spz_amd_image_loss_device.restype = i32
+    L.spz_amd_image_loss_device.argtypes = [vp, i32, vp, i32, i32, i32, C.c_double, vp, vp, vp, vp]
+    L.spz_amd_adam_scalars_of.restype = i32
+    L.spz_amd_adam_scalars_of.argtypes = [i32, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double,
+                                          C.POINTER(AdamScalars)]
+    L.spz_amd_adam_step_device.restype = i32
+    L.spz_amd_adam_step_device.argtypes = [C.POINTER(CloudPtrs), C.POINTER(CloudPtrs), C.POINTER(CloudPtrs),
+                                           C.POINTER(CloudPtrs), u64, i32, u32, AdamScalars, vp, vp]
+    L.spz_amd_refine_default_options.restype = i32
+    L.spz_amd_refine_default_options.argtypes = [C.POINTER(RefineOptions)]
+    L.spz_amd_refine_check.restype = i32
+    L.spz_amd_refine_check.argtypes = [C.POINTER(RefineOptions)]
+    L.spz_amd_refine_open.restype = i32
+    L.spz_amd_refine_open.argtypes = [vp, sz, C.POINTER(Header), vp, sz, C.POINTER(Header), C.POINTER(RenderParams), i32,
+                                      C.POINTER(RefineOptions), i32, C.POINTER(vp), C.POINTER(u64), vp,
+                                      C.POINTER(ImageMetrics), C.POINTER(ImageMetrics), C.POINTER(u64), vp,
+                                      C.POINTER(C.c_int32)]
+    L.spz_amd_refine_fetch.restype = i32
+    L.spz_amd_refine_fetch.argtypes = [vp, vp]
+    L.spz_amd_refine_device_data.restype = vp
+    L.spz_amd_refine_device_data.argtypes = [vp]
+    L.spz_amd_refine_close.restype = None
+    L.spz_amd_refine_close.argtypes = [vp]
     return L
 
 
@@ -666,6 +711,53 @@ def render_params(world_to_camera, fx, fy, cx, cy, width, height, near=0.2, back
         raise ValueError("bad render parameters: world_to_camera must be [R | t] with R a rotation (to 1e-4), fx, fy > 0, "
                          "near > 0, everything finite, max_sh_degree 0..3, coord 0..8")
     return p
+
+
+def train_mask(arrays):
+    """The six-bit mask of an iterable of array names (TRAIN_ARRAYS), or an int that already is one."""
+    if isinstance(arrays, int) and not isinstance(arrays, bool):
+        mask = arrays
+    else:
+        mask = 0
+        for k in arrays:
+            if k not in TRAIN_ARRAYS:
+                raise ValueError(f"train: unknown array {k!r} (one of {', '.join(TRAIN_ARRAYS)})")
+            mask |= 1 << TRAIN_ARRAYS.index(k)
+    if not 0 < mask <= TRAIN_ALL:
+        raise ValueError("train: at least one array, and only the six")
+    return mask
+
+
+def adam_scalars(t, lrs, beta1=0.9, beta2=0.999, eps=1e-15):
+    """The f32 scalars of Adam step t >= 1 (spz_amd_adam_scalars_of): lrs, six learning rates in TRAIN_ARRAYS' order."""
+    out = AdamScalars()
+    check(load_library().spz_amd_adam_scalars_of(int(t), (C.c_double * 6)(*[float(x) for x in lrs]), float(beta1),
+                                                 float(beta2), float(eps), C.byref(out)), "spz_amd_adam_scalars_of")
+    return out
+
+
+def refine_options(iterations, *, lambda_dssim=None, lrs=None, beta1=None, beta2=None, eps=None, train=None):
+    """spz_amd_refine_default_options with the given fields replaced.  lrs: a dict by array name or six numbers."""
+    o = RefineOptions()
+    check(load_library().spz_amd_refine_default_options(C.byref(o)), "spz_amd_refine_default_options")
+    if isinstance(iterations, bool) or not isinstance(iterations, int):
+        raise ValueError(f"iterations must be an int, got {iterations!r}")
+    o.iterations = iterations
+    if lambda_dssim is not None:
+        o.lambda_dssim = float(lambda_dssim)
+    if lrs is not None:
+        if isinstance(lrs, dict):
+            for k, x in lrs.items():
+                o.lr[TRAIN_ARRAYS.index(k)] = float(x)
+        else:
+            for k, x in enumerate(lrs):
+                o.lr[k] = float(x)
+    for name, x in (("beta1", beta1), ("beta2", beta2), ("eps", eps)):
+        if x is not None:
+            setattr(o, name, float(x))
+    if train is not None:
+        o.train_mask = train_mask(train)
+    return o
 
 
 def merge_resolve(headers, sh_degree=None, fractional_bits=None, antialiased=None):

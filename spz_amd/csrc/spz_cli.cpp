@@ -2,9 +2,10 @@
 // MI355X drop-in layer: ply_to_spz, spz_to_ply, spz_info; and spz_filter (spz::filterSpz),
 // spz_transform (spz::transformSpz), spz_merge (spz::mergeSpz), spz_sort (spz::sortSpz), spz_decimate
 // (spz::decimateSpz), spz_tile (spz::tileSpz), spz_clean (spz::cleanSpz), spz_render (spz::renderSpz), spz_prune
-// (spz::pruneSpz), spz_compare (spz::compareSpz) and spz_align (spz::alignSpz), which have no counterpart in the
-// reference.  One binary, dispatched on argv[0] (the Makefile installs it under the fourteen names) or on a first
-// argument naming the tool.
+// (spz::pruneSpz), spz_compare (spz::compareSpz), spz_align (spz::alignSpz) and spz_refine (spz::refineSpz), which
+// have no counterpart in the reference.  One binary, dispatched on argv[0] (the Makefile installs it under the fifteen
+// names) or on a first argument naming the tool.
+// spz_refine exits 0 on success and 1 on a failure.
 // spz_align exits 0 on success, 1 on a failure and 2 when the run ends degenerate; its --output is written by
 // transformSpz, at --fractional-bits (12 unless given, as for spz_transform).
 // spz_compare exits 0 on success, 1 on a failure and 2 when a view misses --min-psnr or --min-ssim.
@@ -94,10 +95,14 @@ class Args {
     std::cerr << usage_ << std::endl;
     return 1;
   }
-  // <input> <output>: both there, neither starting with '-'.  The options follow them.
-  bool files() {
-    at_ = 3;
-    return argc_ >= 3 && argv_[1][0] != '-' && argv_[2][0] != '-';
+  // <input> <output> (spz_refine: three files): all there, none starting with '-'.  The options follow them.
+  bool files(int count = 2) {
+    at_ = count + 1;
+    if (argc_ <= count) return false;
+    for (int k = 1; k <= count; ++k) {
+      if (argv_[k][0] == '-') return false;
+    }
+    return true;
   }
   bool next() {
     if (at_ >= argc_) return false;
@@ -489,6 +494,61 @@ int spzRender(int argc, char **argv) {
   return 0;
 }
 
+// The view arguments spz_prune, spz_compare and spz_refine share: --views FILE, or --orbit N --size W H --fov-y DEG
+// [--center x y z --radius R] [--distance K].
+struct ViewArgs {
+  std::string viewsFile;
+  int orbit = 0, size[2] = {0, 0};
+  float fovY = 0.0f, radius = 0.0f, distance = 2.5f;
+  std::array<float, 3> center{};
+
+  // Whether the current argument is one of these; *good: whether its values parsed.
+  bool take(Args &a, bool *good) {
+    if (a.is("--views")) *good = a.text(&viewsFile);
+    else if (a.is("--orbit")) *good = a.integer(&orbit, 1, 1024);
+    else if (a.is("--size")) *good = a.integer(size, 1, 16384, 2);
+    else if (a.is("--fov-y")) *good = a.real(&fovY) && fovY > 0.0f && fovY < 180.0f;
+    else if (a.is("--center")) *good = a.real(center.data(), 3) && allFinite(center.data(), 3);
+    else if (a.is("--radius")) *good = a.real(&radius) && std::isfinite(radius) && radius > 0.0f;
+    else if (a.is("--distance")) *good = a.real(&distance) && std::isfinite(distance) && distance > 0.0f;
+    else return false;
+    return true;
+  }
+  // Exactly one of the two forms, each with what it needs and nothing of the other.
+  bool consistent(const Args &a) const {
+    const bool hasViews = a.given("--views"), hasOrbit = a.given("--orbit"), hasCenter = a.given("--center");
+    if (hasViews == hasOrbit) return false;
+    const bool hasSize = a.given("--size"), hasFov = a.given("--fov-y"), hasRadius = a.given("--radius");
+    if (hasViews && (hasSize || hasFov || hasCenter || hasRadius || a.given("--distance"))) return false;
+    return !hasOrbit || (hasSize && hasFov && hasCenter == hasRadius);
+  }
+  // The views; an orbit without --center takes the box of `file`'s decoded positions.  0, 1 (failed, said why) or 2
+  // (usage).
+  int resolve(const Args &a, const char *tool, const char *file, spz::CoordinateSystem coord,
+              std::vector<spz::PruneOptions::View> *views) {
+    try {
+      if (a.given("--views")) {
+        *views = spz::loadViewsFile(viewsFile);
+      } else {
+        if (!a.given("--center")) {
+          spz::UnpackOptions u;
+          u.to = coord;
+          const spz::GaussianCloud g = spz::loadSpz(std::string(file), u);
+          if (g.numPoints <= 0 || !spz::boundingSphere(g.positions, &center, &radius)) {
+            std::cerr << tool << ": " << file << " has no points to take a centre and radius from" << std::endl;
+            return 1;
+          }
+        }
+        *views = spz::orbitViews(orbit, center, radius, size[0], size[1], fovY, distance);
+      }
+    } catch (const std::invalid_argument &e) {
+      std::cerr << e.what() << std::endl;
+      return 2;
+    }
+    return 0;
+  }
+};
+
 const char *kPruneUsage =
     "Usage: spz_prune <in.spz> <out.spz> (--views FILE | --orbit N --size W H --fov-y DEG [--center x y z --radius R] "
     "[--distance K]) (--keep N | --keep-fraction F | --min-score S) [--score sum|max] "
@@ -498,19 +558,11 @@ int spzPrune(int argc, char **argv) {
   Args a(argc, argv, kPruneUsage);
   if (!a.files()) return a.usage();
   spz::PruneOptions o;
-  std::string viewsFile, score;
-  int orbit = 0, size[2] = {0, 0};
-  float fovY = 0.0f, radius = 0.0f, distance = 2.5f;
-  std::array<float, 3> center{};
+  ViewArgs va;
+  std::string score;
   while (a.next()) {
     bool good = false;
-    if (a.is("--views")) good = a.text(&viewsFile);
-    else if (a.is("--orbit")) good = a.integer(&orbit, 1, 1024);
-    else if (a.is("--size")) good = a.integer(size, 1, 16384, 2);
-    else if (a.is("--fov-y")) good = a.real(&fovY) && fovY > 0.0f && fovY < 180.0f;
-    else if (a.is("--center")) good = a.real(center.data(), 3) && allFinite(center.data(), 3);
-    else if (a.is("--radius")) good = a.real(&radius) && std::isfinite(radius) && radius > 0.0f;
-    else if (a.is("--distance")) good = a.real(&distance) && std::isfinite(distance) && distance > 0.0f;
+    if (va.take(a, &good)) {}
     else if (a.is("--keep")) good = a.integer(&o.keepCount.emplace(), 0, 0x7fffffff);
     else if (a.is("--keep-fraction")) good = a.real(&o.keepFraction.emplace()) && *o.keepFraction >= 0.0 &&
                                              *o.keepFraction <= 1.0;
@@ -520,31 +572,10 @@ int spzPrune(int argc, char **argv) {
     if (!good) return a.usage();
   }
   if (score == "max") o.score = spz::PruneOptions::Max;
-  const bool hasViews = a.given("--views"), hasOrbit = a.given("--orbit"), hasCenter = a.given("--center");
   const int rules = a.given("--keep") + a.given("--keep-fraction") + a.given("--min-score");
-  if (rules != 1 || hasViews == hasOrbit) return a.usage();
-  const bool hasSize = a.given("--size"), hasFov = a.given("--fov-y"), hasRadius = a.given("--radius");
-  if (hasViews && (hasSize || hasFov || hasCenter || hasRadius || a.given("--distance"))) return a.usage();
-  if (hasOrbit && (!hasSize || !hasFov || hasCenter != hasRadius)) return a.usage();
-  try {
-    if (hasViews) {
-      o.views = spz::loadViewsFile(viewsFile);
-    } else {
-      if (!hasCenter) {  // the box of the decoded positions
-        spz::UnpackOptions u;
-        u.to = o.coord;
-        const spz::GaussianCloud g = spz::loadSpz(std::string(argv[1]), u);
-        if (g.numPoints <= 0 || !spz::boundingSphere(g.positions, &center, &radius)) {
-          std::cerr << "spz_prune: " << argv[1] << " has no points to take a centre and radius from" << std::endl;
-          return 1;
-        }
-      }
-      o.views = spz::orbitViews(orbit, center, radius, size[0], size[1], fovY, distance);
-    }
-  } catch (const std::invalid_argument &e) {
-    std::cerr << e.what() << std::endl;
-    return a.usage();
-  }
+  if (rules != 1 || !va.consistent(a)) return a.usage();
+  const int vr = va.resolve(a, "spz_prune", argv[1], o.coord, &o.views);
+  if (vr != 0) return vr == 2 ? a.usage() : 1;
   int64_t kept = 0;
   if (!spz::pruneSpz(std::string(argv[1]), std::string(argv[2]), o, &kept)) return 1;
   std::cout << "kept " << kept << std::endl;
@@ -574,20 +605,12 @@ int spzCompare(int argc, char **argv) {
   Args a(argc, argv, kCompareUsage);
   if (!a.files()) return a.usage();
   spz::CompareOptions o;
-  std::string viewsFile, mapPrefix;
-  int orbit = 0, size[2] = {0, 0};
-  float fovY = 0.0f, radius = 0.0f, distance = 2.5f;
+  ViewArgs va;
+  std::string mapPrefix;
   double minPsnr = 0.0, minSsim = 0.0;
-  std::array<float, 3> center{};
   while (a.next()) {
     bool good = false;
-    if (a.is("--views")) good = a.text(&viewsFile);
-    else if (a.is("--orbit")) good = a.integer(&orbit, 1, 1024);
-    else if (a.is("--size")) good = a.integer(size, 1, 16384, 2);
-    else if (a.is("--fov-y")) good = a.real(&fovY) && fovY > 0.0f && fovY < 180.0f;
-    else if (a.is("--center")) good = a.real(center.data(), 3) && allFinite(center.data(), 3);
-    else if (a.is("--radius")) good = a.real(&radius) && std::isfinite(radius) && radius > 0.0f;
-    else if (a.is("--distance")) good = a.real(&distance) && std::isfinite(distance) && distance > 0.0f;
+    if (va.take(a, &good)) {}
     else if (a.is("--coord")) good = a.coord(&o.coord);
     else if (a.is("--background")) good = a.real(o.background.data(), 3) && allFinite(o.background.data(), 3);
     else if (a.is("--max-sh-degree")) good = a.integer(&o.maxShDegree, 0, 3);
@@ -597,30 +620,9 @@ int spzCompare(int argc, char **argv) {
     else if (a.is("--min-ssim")) good = a.real(&minSsim) && !std::isnan(minSsim);
     if (!good) return a.usage();
   }
-  const bool hasViews = a.given("--views"), hasOrbit = a.given("--orbit"), hasCenter = a.given("--center");
-  if (hasViews == hasOrbit) return a.usage();
-  const bool hasSize = a.given("--size"), hasFov = a.given("--fov-y"), hasRadius = a.given("--radius");
-  if (hasViews && (hasSize || hasFov || hasCenter || hasRadius || a.given("--distance"))) return a.usage();
-  if (hasOrbit && (!hasSize || !hasFov || hasCenter != hasRadius)) return a.usage();
-  try {
-    if (hasViews) {
-      o.views = spz::loadViewsFile(viewsFile);
-    } else {
-      if (!hasCenter) {  // the box of file a's decoded positions
-        spz::UnpackOptions u;
-        u.to = o.coord;
-        const spz::GaussianCloud g = spz::loadSpz(std::string(argv[1]), u);
-        if (g.numPoints <= 0 || !spz::boundingSphere(g.positions, &center, &radius)) {
-          std::cerr << "spz_compare: " << argv[1] << " has no points to take a centre and radius from" << std::endl;
-          return 1;
-        }
-      }
-      o.views = spz::orbitViews(orbit, center, radius, size[0], size[1], fovY, distance);
-    }
-  } catch (const std::invalid_argument &e) {
-    std::cerr << e.what() << std::endl;
-    return a.usage();
-  }
+  if (!va.consistent(a)) return a.usage();
+  const int vr = va.resolve(a, "spz_compare", argv[1], o.coord, &o.views);
+  if (vr != 0) return vr == 2 ? a.usage() : 1;
   std::vector<spz::ImageMetrics> m;
   std::vector<std::vector<float>> maps;
   if (!spz::compareSpz(std::string(argv[1]), std::string(argv[2]), o, &m, mapPrefix.empty() ? nullptr : &maps)) {
@@ -650,6 +652,76 @@ int spzCompare(int argc, char **argv) {
               ssimSum / n, m[worstPsnr].psnr, worstPsnr, m[worstSsim].ssim, worstSsim);
   std::fflush(stdout);
   return missed ? 2 : 0;
+}
+
+const char *kRefineUsage =
+    "Usage: spz_refine <in.spz> <target.spz> <out.spz> (--views FILE | --orbit N --size W H --fov-y DEG [--center x y z "
+    "--radius R] [--distance K]) [--iters N] [--lambda-dssim L] [--lr-positions X] [--lr-scales X] [--lr-rotations X] "
+    "[--lr-alphas X] [--lr-colors X] [--lr-sh X] [--train positions,scales,rotations,alphas,colors,sh] "
+    "[--coord " SPZ_COORD_NAMES "] [--background r g b] [--max-sh-degree D] [--near Z]";
+
+// One line per view with its PSNR and SSIM before and after, then their means.  An orbit without --center is taken
+// around the target.
+int spzRefine(int argc, char **argv) {
+  Args a(argc, argv, kRefineUsage);
+  if (!a.files(3)) return a.usage();
+  spz::RefineOptions o;
+  ViewArgs va;
+  std::string train;
+  auto rate = [&](double *x) { return a.real(x) && std::isfinite(*x) && *x >= 0.0; };
+  while (a.next()) {
+    bool good = false;
+    if (va.take(a, &good)) {}
+    else if (a.is("--iters")) good = a.integer(&o.iterations, 0, 0x7fffffff);
+    else if (a.is("--lambda-dssim")) good = a.real(&o.lambdaDssim) && o.lambdaDssim >= 0.0 && o.lambdaDssim <= 1.0;
+    else if (a.is("--lr-positions")) good = rate(&o.positionLr.emplace());
+    else if (a.is("--lr-scales")) good = rate(&o.scaleLr);
+    else if (a.is("--lr-rotations")) good = rate(&o.rotationLr);
+    else if (a.is("--lr-alphas")) good = rate(&o.alphaLr);
+    else if (a.is("--lr-colors")) good = rate(&o.colorLr);
+    else if (a.is("--lr-sh")) good = rate(&o.shLr);
+    else if (a.is("--train")) good = a.text(&train) && !train.empty();
+    else if (a.is("--coord")) good = a.coord(&o.coord);
+    else if (a.is("--background")) good = a.real(o.background.data(), 3) && allFinite(o.background.data(), 3);
+    else if (a.is("--max-sh-degree")) good = a.integer(&o.maxShDegree, 0, 3);
+    else if (a.is("--near")) good = a.real(&o.nearPlane) && std::isfinite(o.nearPlane) && o.nearPlane > 0.0f;
+    if (!good) return a.usage();
+  }
+  if (!va.consistent(a)) return a.usage();
+  if (a.given("--train")) {
+    static const char *const kArrays[6] = {"positions", "scales", "rotations", "alphas", "colors", "sh"};
+    o.train = 0;
+    size_t at = 0;
+    while (at <= train.size()) {
+      const size_t comma = std::min(train.find(',', at), train.size());
+      const std::string name = train.substr(at, comma - at);
+      const auto *n = std::find(std::begin(kArrays), std::end(kArrays), name);
+      if (n == std::end(kArrays)) return a.usage();
+      o.train |= 1u << (n - std::begin(kArrays));
+      at = comma + 1;
+    }
+  }
+  const int vr = va.resolve(a, "spz_refine", argv[2], o.coord, &o.views);
+  if (vr != 0) return vr == 2 ? a.usage() : 1;
+  spz::RefineReport r;
+  if (!spz::refineSpz(std::string(argv[1]), std::string(argv[2]), std::string(argv[3]), o, &r)) return 1;
+  double sums[4] = {0.0, 0.0, 0.0, 0.0};
+  for (size_t v = 0; v < r.before.size(); ++v) {
+    std::printf("view %zu psnr %.17g -> %.17g ssim %.17g -> %.17g\n", v, r.before[v].psnr, r.after[v].psnr,
+                r.before[v].ssim, r.after[v].ssim);
+    sums[0] += r.before[v].psnr;
+    sums[1] += r.after[v].psnr;
+    sums[2] += r.before[v].ssim;
+    sums[3] += r.after[v].ssim;
+  }
+  const double n = static_cast<double>(r.before.size());
+  std::printf("mean psnr %.17g -> %.17g ssim %.17g -> %.17g\n", sums[0] / n, sums[1] / n, sums[2] / n, sums[3] / n);
+  if (!r.history.empty()) {
+    std::printf("loss %.17g -> %.17g over %zu iterations, %llu non-finite elements skipped\n", r.history.front(),
+                r.history.back(), r.history.size(), static_cast<unsigned long long>(r.skipped));
+  }
+  std::fflush(stdout);
+  return 0;
 }
 
 const char *kAlignUsage =
@@ -712,7 +784,7 @@ const struct {
               {"spz_filter", spzFilter},    {"spz_transform", spzTransform},  {"spz_merge", spzMerge},
               {"spz_sort", spzSort},        {"spz_decimate", spzDecimate},    {"spz_clean", spzClean},
               {"spz_render", spzRender},    {"spz_prune", spzPrune},          {"spz_compare", spzCompare},
-              {"spz_tile", spzTile},        {"spz_align", spzAlign}};
+              {"spz_tile", spzTile},        {"spz_align", spzAlign},          {"spz_refine", spzRefine}};
 
 int dispatch(const std::string &tool, int argc, char **argv) {
   for (const auto &t : kTools) {

@@ -340,13 +340,14 @@ inline double ms_since(std::chrono::steady_clock::time_point t0) {
 }
 
 // An operation's output stream in HBM until its close: the ctx of every spz_amd_<op>_open / _fetch / _device_data /
-// _close host form (filter, transform, merge, sort, decimate, clean, prune, tile).  `out` points into one of the allocations.
+// _close host form (filter, transform, merge, sort, decimate, clean, prune, tile, refine).  `out` points into one of the
+// allocations.
 struct PackedResult {
   int device = 0;
   hipStream_t st = nullptr;
   uint8_t *block = nullptr;      // the operation's workspace (filter, transform, merge, sort: the output stream too)
-  uint8_t *scratch = nullptr;    // a second workspace (prune: the render's)
-  uint8_t *out_block = nullptr;  // the output stream in an allocation of its own (decimate, clean, prune; tile: the arena)
+  uint8_t *scratch = nullptr;    // a second workspace (prune, refine: the render's)
+  uint8_t *out_block = nullptr;  // the output stream in an allocation of its own (decimate, clean, prune, refine; tile: the arena)
   uint8_t *extra = nullptr;      // a fourth allocation (tile: the decimate output its coarse tiles are cut from)
   uint8_t *out = nullptr;
   uint64_t out_bytes = 0;

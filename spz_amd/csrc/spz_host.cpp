@@ -2918,6 +2918,157 @@ bool compareSpz(const std::string &fileA, const std::string &fileB, const Compar
                     ssimMaps);
 }
 
+// ---- refine ------------------------------------------------------------------------------------------------------
+namespace {
+// The views as render params, and the options but the position rate as the C ABI's.
+bool refineOptionsOk(const RefineOptions &o, std::vector<spz_amd_render_params> *params, spz_amd_refine_options *c) {
+  const char *who = "refineSpz";
+  const int invalid = SPZ_AMD_ERR_INVALID_ARG;
+  if (o.iterations < 0) return opRejected(who, invalid, "iterations %d is negative", o.iterations);
+  if (!(o.lambdaDssim >= 0.0 && o.lambdaDssim <= 1.0)) return opRejected(who, invalid, "lambdaDssim must be in [0, 1]");
+  if (o.train == 0 || o.train > RefineOptions::All) return opRejected(who, invalid, "train must name at least one array");
+  spz_amd_refine_default_options(c);
+  c->iterations = o.iterations;
+  c->train_mask = o.train;
+  c->lambda_dssim = o.lambdaDssim;
+  c->lr[0] = o.positionLr ? *o.positionLr : 0.0;
+  c->lr[1] = o.scaleLr;
+  c->lr[2] = o.rotationLr;
+  c->lr[3] = o.alphaLr;
+  c->lr[4] = o.colorLr;
+  c->lr[5] = o.shLr;
+  c->beta1 = o.beta1;
+  c->beta2 = o.beta2;
+  c->eps = o.eps;
+  if (spz_amd_refine_check(c) != SPZ_AMD_OK) {
+    return opRejected(who, invalid, "learning rates must be finite and >= 0, beta1 and beta2 in [0, 1), eps finite and >= 0");
+  }
+  if (o.views.empty() || o.views.size() > SPZ_AMD_REFINE_MAX_VIEWS) {
+    return opRejected(who, invalid, "%zu views: give 1..%d", o.views.size(), SPZ_AMD_REFINE_MAX_VIEWS);
+  }
+  params->assign(o.views.size(), spz_amd_render_params{});
+  for (size_t v = 0; v < o.views.size(); ++v) {
+    const PruneOptions::View &w = o.views[v];
+    spz_amd_render_params &p = (*params)[v];
+    if (w.width < 1 || w.width > 16384 || w.height < 1 || w.height > 16384) {
+      return opRejected(who, invalid, "view %zu: image size %d x %d is outside 1..16384", v, w.width, w.height);
+    }
+    for (int k = 0; k < 12; ++k) p.world_to_camera[k] = w.worldToCamera[k];
+    p.fx = w.fx;
+    p.fy = w.fy;
+    p.cx = w.cx;
+    p.cy = w.cy;
+    p.width = static_cast<uint32_t>(w.width);
+    p.height = static_cast<uint32_t>(w.height);
+    p.near_plane = o.nearPlane;
+    for (int k = 0; k < 3; ++k) p.background[k] = o.background[k];
+    p.max_sh_degree = o.maxShDegree;
+    p.coord = static_cast<int32_t>(o.coord);
+    if (spz_amd_render_check_params(&p) != SPZ_AMD_OK) {
+      return opRejected(who, invalid,
+                        "view %zu: bad camera: R must be a rotation (to 1e-4), fx, fy > 0, nearPlane > 0, values "
+                        "finite, maxShDegree 0..3, coord valid", v);
+    }
+  }
+  return true;
+}
+}  // namespace
+
+bool refineSpz(const uint8_t *data, int32_t size, const uint8_t *target, int32_t targetSize, const RefineOptions &o,
+               std::vector<uint8_t> *out, RefineReport *report) {
+  const char *who = "refineSpz";
+  g_last_status = SPZ_AMD_OK;
+  if (report) *report = RefineReport{};
+  if (out == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no output vector");
+  std::vector<spz_amd_render_params> params;
+  spz_amd_refine_options c;
+  if (!refineOptionsOk(o, &params, &c)) return false;
+  Laps laps(who, "SPZ_AMD_REFINE_TIMING");
+  DevicePackedGaussians da, db;
+  if (!loadInput(who, data, size, &da) || !loadInput(who, target, targetSize, &db)) return false;
+  laps.lap("inflate");
+  if (da.device != db.device) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "the inputs were loaded on different devices");
+  if (!o.positionLr) {  // 3DGS scales the position rate by the scene's extent
+    UnpackOptions u;
+    u.to = o.coord;
+    const GaussianCloud t = db.unpack(u);
+    std::array<float, 3> centre;
+    float radius = 1.0f;
+    if (!boundingSphere(t.positions, &centre, &radius)) radius = 1.0f;
+    c.lr[0] = 1.6e-4 * static_cast<double>(radius);
+    laps.lap("extent");
+  }
+  const spz_amd_header ha = headerOf(da), hb = headerOf(db);
+  const size_t nv = params.size();
+  std::vector<spz_amd_image_metrics> before(nv), after(nv);
+  std::vector<double> history(static_cast<size_t>(o.iterations) + 1);
+  OpenResult r(spz_amd_refine_fetch, spz_amd_refine_device_data, spz_amd_refine_close);
+  uint64_t bytes = 0, skipped = 0;
+  float ms[3] = {0.0f, 0.0f, 0.0f};
+  int32_t bad = -1;
+  const int rc = spz_amd_refine_open(da.stream, da.streamBytes, &ha, db.stream, db.streamBytes, &hb, params.data(),
+                                     static_cast<int>(nv), &c, da.device, &r.ctx, &bytes, history.data(), before.data(),
+                                     after.data(), &skipped, ms, &bad);
+  if (rc == SPZ_AMD_ERR_CAPACITY && bad >= 0) return opRejected(who, rc, "view %d: more than 2^31 - 1 tile entries", bad);
+  if (rc == SPZ_AMD_ERR_UNSUPPORTED) {
+    return opRejected(who, rc, "the encoder writes versions 2 and 3 and positions at 12 fractional bits: the input has "
+                      "version %u and %u", ha.version, static_cast<unsigned>(ha.fractional_bits));
+  }
+  if (rc != SPZ_AMD_OK && bad >= 0) logLine("[SPZ ERROR] refineSpz: view %d failed", bad);
+  if (deviceFailed(rc, who)) return false;
+  laps.stage("targets", ms[0], (" (" + std::to_string(nv) + " views)").c_str());
+  laps.stage("iterations", ms[1], (" (" + std::to_string(o.iterations) + ")").c_str());
+  laps.stage("after", ms[2]);
+  laps.lap("refine");
+  da.release();
+  db.release();
+  if (!r.finish(who, bytes, &laps, out)) return false;
+  if (report) {
+    history.resize(static_cast<size_t>(o.iterations));
+    report->history.swap(history);
+    report->before.resize(nv);
+    report->after.resize(nv);
+    for (size_t v = 0; v < nv; ++v) {
+      report->before[v] = toMetrics(before[v]);
+      report->after[v] = toMetrics(after[v]);
+    }
+    report->skipped = skipped;
+    report->positionLr = c.lr[0];
+    for (int k = 0; k < 3; ++k) report->ms[k] = ms[k];
+  }
+  return true;
+}
+
+bool refineSpz(const std::vector<uint8_t> &data, const std::vector<uint8_t> &target, const RefineOptions &o,
+               std::vector<uint8_t> *out, RefineReport *report) {
+  if (data.size() > static_cast<size_t>(INT32_MAX) || target.size() > static_cast<size_t>(INT32_MAX)) {
+    return opRejected("refineSpz", SPZ_AMD_ERR_INVALID_ARG, "an input is larger than 2 GiB");
+  }
+  return refineSpz(data.data(), static_cast<int32_t>(data.size()), target.data(), static_cast<int32_t>(target.size()), o,
+                   out, report);
+}
+
+bool refineSpz(const std::string &inputFilename, const std::string &targetFilename, const std::string &outputFilename,
+               const RefineOptions &o, RefineReport *report) {
+  const char *who = "refineSpz";
+  g_last_status = SPZ_AMD_OK;
+  if (report) *report = RefineReport{};
+  std::vector<spz_amd_render_params> params;
+  spz_amd_refine_options c;
+  if (!refineOptionsOk(o, &params, &c)) return false;
+  std::vector<uint8_t> target;
+  if (!readInput(who, targetFilename, &target)) return false;
+  RefineReport rep;
+  if (!fileToFile(who, "SPZ_AMD_REFINE_TIMING", inputFilename, outputFilename,
+                  [&](const uint8_t *data, int32_t size, std::vector<uint8_t> *file) {
+                    return refineSpz(data, size, target.data(), static_cast<int32_t>(target.size()), o, file, &rep);
+                  })) {
+    return false;
+  }
+  if (report) *report = std::move(rep);
+  return true;
+}
+
 // ---- align -------------------------------------------------------------------------------------------------------
 namespace {
 bool alignOptionsOk(const AlignOptions &o, spz_amd_align_options *c) {

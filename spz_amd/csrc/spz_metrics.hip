@@ -8,6 +8,12 @@
 //                                  and max |d| on the way.  The map (mean S over the channels) when asked; the tile's
 //                                  partial sums to a slab, reduced across the workgroup in a fixed order.
 //   spz_metrics_reduce_kernel      one workgroup: the slab in a fixed order, then the five results.  No float atomics.
+//   spz_loss_tile_kernel           the same tile body (metrics_tile_body<true>): beside the partial sums, the three
+//                                  derivative maps of S per channel (to the window mean of a, of a^2 and of ab) as nine
+//                                  f64 planes.
+//   spz_loss_reduce_kernel         the slab in the metrics' order, then L = (1 - lambda) l1 + lambda (1 - ssim), l1, ssim.
+//   spz_loss_grad_kernel           one workgroup per 32x16 tile: each plane's tile and halo into LDS (zeros outside the
+//                                  image), the same two 11-tap passes, then dL/da per pixel through the clamp's mask.
 //   compare                        per view: render A, render B (spz_amd_render_prepare_packed_device + _finish_device
 //                                  into grow-only buffers), then the two kernels above.
 #include <hip/hip_runtime.h>
@@ -82,14 +88,27 @@ __device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
   return v;
 }
 
-}  // namespace
+// The derivatives of one pixel's S (image loss): to the window mean of ab (P), of a^2 (Q), and the total one to the
+// window mean of a (M), the variances' dependence on it included.
+__device__ __forceinline__ void ssim_derivatives(double ma, double mb, double maa, double mbb, double mab, double s,
+                                                 double *p, double *q, double *m) {
+  const double mu_ab = ma * mb, mu_aa = ma * ma, mu_bb = mb * mb;
+  const double sa = maa - mu_aa, sb = mbb - mu_bb, sab = mab - mu_ab;
+  const double a1 = 2.0 * mu_ab + kC1, a2 = 2.0 * sab + kC2, b1 = mu_aa + mu_bb + kC1, b2 = sa + sb + kC2;
+  const double b12 = b1 * b2;
+  *p = (2.0 * a1) / b12;
+  *q = -s / b2;
+  *m = (2.0 * mb * (a2 - a1)) / b12 - (2.0 * ma * s) * (1.0 / b1 - 1.0 / b2);
+}
 
-// slab: 4 planes of `tiles` 8-byte words: sum d^2, sum |d|, sum S (all f64), max |d| (the u64 bits of the f64).
-__global__ __launch_bounds__(kMtThreads) void spz_metrics_tile_kernel(const float *__restrict__ a, uint32_t ca,
-                                                                      const float *__restrict__ b, uint32_t cb,
-                                                                      uint32_t width, uint32_t height, uint32_t tiles_x,
-                                                                      uint32_t tiles, MetricsWindow win,
-                                                                      float *__restrict__ map, double *__restrict__ slab) {
+// The tile pass of the metrics and of the image loss.  slab: 4 planes of `tiles` 8-byte words: sum d^2, sum |d|, sum S
+// (all f64), max |d| (the u64 bits of the f64).  kLoss: dmaps gets nine planes of height x width f64, plane 3 c + {0: M,
+// 1: Q, 2: P} of channel c; map is not used.
+template <bool kLoss>
+__device__ __forceinline__ void metrics_tile_body(const float *__restrict__ a, uint32_t ca, const float *__restrict__ b,
+                                                  uint32_t cb, uint32_t width, uint32_t height, uint32_t tiles_x,
+                                                  uint32_t tiles, const MetricsWindow &win, float *__restrict__ map,
+                                                  double *__restrict__ dmaps, double *__restrict__ slab) {
   __shared__ float la[kMtInH][kMtInW];
   __shared__ float lb[kMtInH][kMtInW];
   __shared__ double hs[5][kMtInH][kMtW];
@@ -150,14 +169,25 @@ __global__ __launch_bounds__(kMtThreads) void spz_metrics_tile_kernel(const floa
           mbb += wk * hs[3][py + k][px];
           mab += wk * hs[4][py + k][px];
         }
-        s_px[j] += ssim_of(ma, mb, maa, mbb, mab);
+        const double s_one = ssim_of(ma, mb, maa, mbb, mab);
+        s_px[j] += s_one;
+        if constexpr (kLoss) {
+          double dp, dq, dm;
+          ssim_derivatives(ma, mb, maa, mbb, mab, s_one, &dp, &dq, &dm);
+          const size_t plane = (size_t)width * height, at = (size_t)gy * width + (size_t)gx;
+          dmaps[(3u * c + 0u) * plane + at] = dm;
+          dmaps[(3u * c + 1u) * plane + at] = dq;
+          dmaps[(3u * c + 2u) * plane + at] = dp;
+        }
         const double d = (double)la[py + kMtR][px + kMtR] - (double)lb[py + kMtR][px + kMtR];
         const double ad = fabs(d);
         sum_d2 += d * d;
         sum_d1 += ad;
         const unsigned long long bits = (unsigned long long)__double_as_longlong(ad);
         max_d = bits > max_d ? bits : max_d;
-        if (map != nullptr && c == 2) map[(size_t)gy * width + (size_t)gx] = (float)(s_px[j] / 3.0);
+        if constexpr (!kLoss) {
+          if (map != nullptr && c == 2) map[(size_t)gy * width + (size_t)gx] = (float)(s_px[j] / 3.0);
+        }
       }
     }
     __syncthreads();  // the next channel overwrites la, lb and hs
@@ -191,9 +221,30 @@ __global__ __launch_bounds__(kMtThreads) void spz_metrics_tile_kernel(const floa
   }
 }
 
-__global__ __launch_bounds__(kMtRedThreads) void spz_metrics_reduce_kernel(const double *__restrict__ slab,
-                                                                           uint32_t tiles, double count,
-                                                                           spz_amd_image_metrics *__restrict__ out) {
+}  // namespace
+
+__global__ __launch_bounds__(kMtThreads) void spz_metrics_tile_kernel(const float *__restrict__ a, uint32_t ca,
+                                                                      const float *__restrict__ b, uint32_t cb,
+                                                                      uint32_t width, uint32_t height, uint32_t tiles_x,
+                                                                      uint32_t tiles, MetricsWindow win,
+                                                                      float *__restrict__ map, double *__restrict__ slab) {
+  metrics_tile_body<false>(a, ca, b, cb, width, height, tiles_x, tiles, win, map, nullptr, slab);
+}
+
+__global__ __launch_bounds__(kMtThreads) void spz_loss_tile_kernel(const float *__restrict__ a, uint32_t ca,
+                                                                   const float *__restrict__ b, uint32_t cb,
+                                                                   uint32_t width, uint32_t height, uint32_t tiles_x,
+                                                                   uint32_t tiles, MetricsWindow win,
+                                                                   double *__restrict__ dmaps, double *__restrict__ slab) {
+  metrics_tile_body<true>(a, ca, b, cb, width, height, tiles_x, tiles, win, nullptr, dmaps, slab);
+}
+
+namespace {
+
+// The slab's three sums and its maximum, in a fixed order: each lane its strided entries, then a tree over the lanes.
+// Lane 0 returns with the results.
+__device__ __forceinline__ void reduce_slab(const double *__restrict__ slab, uint32_t tiles, double *sum_d2,
+                                            double *sum_d1, double *sum_s, unsigned long long *max_d) {
   __shared__ double r0[kMtRedThreads], r1[kMtRedThreads], r2[kMtRedThreads];
   __shared__ unsigned long long rm[kMtRedThreads];
   const uint32_t tid = threadIdx.x;
@@ -220,13 +271,125 @@ __global__ __launch_bounds__(kMtRedThreads) void spz_metrics_reduce_kernel(const
     }
     __syncthreads();
   }
-  if (tid == 0) {
-    const double mse = r0[0] / count;
+  *sum_d2 = r0[0];
+  *sum_d1 = r1[0];
+  *sum_s = r2[0];
+  *max_d = rm[0];
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kMtRedThreads) void spz_metrics_reduce_kernel(const double *__restrict__ slab,
+                                                                           uint32_t tiles, double count,
+                                                                           spz_amd_image_metrics *__restrict__ out) {
+  double d2, d1, ss;
+  unsigned long long md;
+  reduce_slab(slab, tiles, &d2, &d1, &ss, &md);
+  if (threadIdx.x == 0) {
+    const double mse = d2 / count;
     out->mse = mse;
     out->psnr = mse == 0.0 ? __longlong_as_double(0x7ff0000000000000ll) : 10.0 * log10(1.0 / mse);
-    out->ssim = r2[0] / count;
-    out->l1 = r1[0] / count;
-    out->max_abs = __longlong_as_double((long long)rm[0]);
+    out->ssim = ss / count;
+    out->l1 = d1 / count;
+    out->max_abs = __longlong_as_double((long long)md);
+  }
+}
+
+// out[0] = L = (1 - lambda) l1 + lambda (1 - ssim), out[1] = l1, out[2] = ssim; l1 and ssim as the metrics give them.
+__global__ __launch_bounds__(kMtRedThreads) void spz_loss_reduce_kernel(const double *__restrict__ slab, uint32_t tiles,
+                                                                        double count, double lambda,
+                                                                        double *__restrict__ out) {
+  double d2, d1, ss;
+  unsigned long long md;
+  reduce_slab(slab, tiles, &d2, &d1, &ss, &md);
+  if (threadIdx.x == 0) {
+    const double l1 = d1 / count, ssim = ss / count;
+    out[0] = (1.0 - lambda) * l1 + lambda * (1.0 - ssim);
+    out[1] = l1;
+    out[2] = ssim;
+  }
+}
+
+// dL/da of one 32x16 tile.  Per channel, the three planes (M, Q, P) one after the other: the tile and its halo into LDS
+// (zeros outside the image), the 11 taps along rows, then along columns at this lane's two pixels:
+//   d ssim / d a = (g*M + 2 a g*Q + b g*P) / count on the clamped a, b;  the L1 part: sign(a - b) / count;
+//   dL/da = ((1 - lambda) sign - lambda (g*M + 2 a g*Q + b g*P)) / count where 0 <= a <= 1 (the raw value), else 0.
+// Every element of grad is written; a fourth channel gets 0.
+__global__ __launch_bounds__(kMtThreads) void spz_loss_grad_kernel(const float *__restrict__ a, uint32_t ca,
+                                                                   const float *__restrict__ b, uint32_t cb,
+                                                                   uint32_t width, uint32_t height, uint32_t tiles_x,
+                                                                   MetricsWindow win, const double *__restrict__ dmaps,
+                                                                   double lambda, double count,
+                                                                   float *__restrict__ grad) {
+  __shared__ double lm[kMtInH][kMtInW];
+  __shared__ double hs[kMtInH][kMtW];
+  const uint32_t tid = threadIdx.x;
+  const int x0 = (int)((blockIdx.x % tiles_x) * kMtW), y0 = (int)((blockIdx.x / tiles_x) * kMtH);
+  const int W = (int)width, H = (int)height;
+  const int px = (int)(tid % kMtW), py0 = (int)(tid / kMtW);  // this lane's pixels: (px, py0) and (px, py0 + 8)
+  const size_t plane = (size_t)width * height;
+  float g_out[2][3];
+  for (uint32_t c = 0; c < 3; ++c) {
+    double acc[2] = {0.0, 0.0};
+    double va[2] = {0.0, 0.0}, vb[2] = {0.0, 0.0};
+    bool pass[2] = {false, false};
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int gx = x0 + px, gy = y0 + py0 + 8 * j;
+      if (gx < W && gy < H) {
+        const size_t p = (size_t)gy * width + (size_t)gx;
+        const float ra = a[p * ca + c];
+        pass[j] = ra >= 0.0f && ra <= 1.0f;  // false for NaN
+        va[j] = (double)clamp01(ra);
+        vb[j] = (double)clamp01(b[p * cb + c]);
+      }
+    }
+    for (uint32_t m = 0; m < 3; ++m) {
+      const double *__restrict__ src = dmaps + (3u * c + m) * plane;
+      for (int i = (int)tid; i < kMtInH * kMtInW; i += kMtThreads) {
+        const int r = i / kMtInW, q = i % kMtInW;
+        const int gy = y0 - kMtR + r, gx = x0 - kMtR + q;
+        lm[r][q] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? src[(size_t)gy * width + (size_t)gx] : 0.0;
+      }
+      __syncthreads();
+      for (int i = (int)tid; i < kMtInH * kMtW; i += kMtThreads) {
+        const int r = i / kMtW, q = i % kMtW;
+        double t = 0.0;
+#pragma unroll
+        for (int k = 0; k <= 2 * kMtR; ++k) t += win.w[k] * lm[r][q + k];
+        hs[r][q] = t;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int py = py0 + 8 * j;
+        double t = 0.0;
+#pragma unroll
+        for (int k = 0; k <= 2 * kMtR; ++k) t += win.w[k] * hs[py + k][px];
+        acc[j] += m == 0 ? t : (m == 1 ? (2.0 * va[j]) * t : vb[j] * t);
+      }
+      __syncthreads();  // the next plane overwrites lm and hs
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const double d = va[j] - vb[j];
+      const double sign = d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : 0.0);
+      g_out[j][c] = pass[j] ? (float)(((1.0 - lambda) * sign - lambda * acc[j]) / count) : 0.0f;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int gx = x0 + px, gy = y0 + py0 + 8 * j;
+    if (gx < W && gy < H) {
+      const size_t p = (size_t)gy * width + (size_t)gx;
+      if (ca == 4) {
+        *reinterpret_cast<F32x4 *>(grad + p * 4u) = F32x4{g_out[j][0], g_out[j][1], g_out[j][2], 0.0f};
+      } else {
+        grad[p * 3u] = g_out[j][0];
+        grad[p * 3u + 1u] = g_out[j][1];
+        grad[p * 3u + 2u] = g_out[j][2];
+      }
+    }
   }
 }
 
@@ -244,6 +407,30 @@ int metrics_enqueue(const float *d_a, int channels_a, const float *d_b, int chan
   SPZ_HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(spz_metrics_reduce_kernel, dim3(1), dim3(kMtRedThreads), 0, st, slab, tiles,
                      3.0 * (double)w * (double)h, d_out);
+  SPZ_HIP_TRY(hipGetLastError());
+  return SPZ_AMD_OK;
+}
+
+// The image loss's workspace: the slab, then the nine f64 planes.
+uint64_t loss_slab_bytes(uint32_t w, uint32_t h) { return Workspace::aligned((uint64_t)metrics_tiles(w, h) * 32u); }
+
+int loss_enqueue(const float *d_a, int channels_a, const float *d_b, int channels_b, int width, int height,
+                 double lambda, double *d_loss, float *d_grad, void *d_workspace, hipStream_t st) {
+  const uint32_t w = (uint32_t)width, h = (uint32_t)height;
+  const uint32_t tiles_x = (w + kMtW - 1) / kMtW;
+  const uint32_t tiles = metrics_tiles(w, h);
+  static const MetricsWindow win = metrics_window();
+  uint8_t *base = align_ws(d_workspace);
+  auto *slab = reinterpret_cast<double *>(base);
+  auto *dmaps = reinterpret_cast<double *>(base + loss_slab_bytes(w, h));
+  const double count = 3.0 * (double)w * (double)h;
+  hipLaunchKernelGGL(spz_loss_tile_kernel, dim3(tiles), dim3(kMtThreads), 0, st, d_a, (uint32_t)channels_a, d_b,
+                     (uint32_t)channels_b, w, h, tiles_x, tiles, win, dmaps, slab);
+  SPZ_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(spz_loss_reduce_kernel, dim3(1), dim3(kMtRedThreads), 0, st, slab, tiles, count, lambda, d_loss);
+  SPZ_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(spz_loss_grad_kernel, dim3(tiles), dim3(kMtThreads), 0, st, d_a, (uint32_t)channels_a, d_b,
+                     (uint32_t)channels_b, w, h, tiles_x, win, dmaps, lambda, count, d_grad);
   SPZ_HIP_TRY(hipGetLastError());
   return SPZ_AMD_OK;
 }
@@ -371,6 +558,29 @@ int spz_amd_image_metrics_device(const float *d_a, int channels_a, const float *
   if (rc != SPZ_AMD_OK) return rc;
   return metrics_enqueue(d_a, channels_a, d_b, channels_b, width, height, d_out, d_ssim_map, d_workspace,
                          static_cast<hipStream_t>(hip_stream));
+}
+
+uint64_t spz_amd_image_loss_workspace_bytes(int width, int height) {
+  if (width < 1 || height < 1 || (uint32_t)width > kMtMaxSide || (uint32_t)height > kMtMaxSide) return 0;
+  return loss_slab_bytes((uint32_t)width, (uint32_t)height) + 9u * 8u * (uint64_t)width * (uint64_t)height + 256u;
+}
+
+int spz_amd_image_loss_device(const float *d_a, int channels_a, const float *d_b, int channels_b, int width, int height,
+                              double lambda_dssim, double *d_loss, float *d_grad, void *d_workspace, void *hip_stream) {
+  int rc = spz_amd_image_metrics_check(width, height, channels_a, channels_b);
+  if (rc != SPZ_AMD_OK) return rc;
+  if (!(lambda_dssim >= 0.0) || !(lambda_dssim <= 1.0)) return SPZ_AMD_ERR_INVALID_ARG;
+  if (d_a == nullptr || d_b == nullptr || d_loss == nullptr || d_grad == nullptr || d_workspace == nullptr) {
+    return SPZ_AMD_ERR_INVALID_ARG;
+  }
+  if (!aligned_to(d_a, 4) || !aligned_to(d_b, 4) || !aligned_to(d_loss, 8) || !aligned_to(d_grad, 4)) {
+    return SPZ_AMD_ERR_INVALID_ARG;
+  }
+  int device = 0;
+  rc = current_device(&device);
+  if (rc != SPZ_AMD_OK) return rc;
+  return loss_enqueue(d_a, channels_a, d_b, channels_b, width, height, lambda_dssim, d_loss, d_grad, d_workspace,
+                      static_cast<hipStream_t>(hip_stream));
 }
 
 int spz_amd_image_metrics_host(const float *h_a, int channels_a, const float *h_b, int channels_b, int width,

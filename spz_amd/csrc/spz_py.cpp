@@ -1322,6 +1322,124 @@ PYBIND11_MODULE(spz, m) {
         "1..1024 dicts as orbit_views, load_views_file and load_3dgs_cameras return them, in the frame `coord`.  Returns "
         "one dict per view: mse, psnr (dB; inf when the images are equal), ssim, l1, max_abs; with return_maps also "
         "ssim_map, a (height, width) float32 array of S averaged over the channels.");
+  m.def("refine_spz",
+        [](const py::object &input, const py::object &target, const py::object &output, const py::object &views,
+           int iterations, spz::CoordinateSystem coord, const py::object &background, int max_sh_degree,
+           float near_plane, double lambda_dssim, const py::object &lrs, double beta1, double beta2, double eps,
+           const py::object &train) {
+          // the arguments first: every problem is a ValueError before any device work
+          static const char *const kArrays[6] = {"positions", "scales", "rotations", "alphas", "colors", "sh"};
+          if (iterations < 0) throw py::value_error("iterations must be >= 0");
+          if (!std::isfinite(near_plane) || !(near_plane > 0.0f)) throw py::value_error("near must be > 0");
+          if (max_sh_degree < 0 || max_sh_degree > 3) throw py::value_error("max_sh_degree must be 0..3");
+          if (!(lambda_dssim >= 0.0 && lambda_dssim <= 1.0)) throw py::value_error("lambda_dssim must be in [0, 1]");
+          if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) {
+            throw py::value_error("beta1 and beta2 must be in [0, 1)");
+          }
+          if (!std::isfinite(eps) || eps < 0.0) throw py::value_error("eps must be finite and >= 0");
+          spz::RefineOptions o;
+          py::array_t<float, py::array::c_style | py::array::forcecast> bg(background);
+          if (bg.size() != 3) throw py::value_error("background must have three values");
+          for (int k = 0; k < 3; ++k) {
+            o.background[k] = bg.data()[k];
+            if (!std::isfinite(o.background[k])) throw py::value_error("background must be finite");
+          }
+          o.coord = coord;
+          o.nearPlane = near_plane;
+          o.maxShDegree = max_sh_degree;
+          o.iterations = iterations;
+          o.lambdaDssim = lambda_dssim;
+          o.beta1 = beta1;
+          o.beta2 = beta2;
+          o.eps = eps;
+          if (!lrs.is_none()) {
+            if (!py::isinstance<py::dict>(lrs)) throw py::value_error("lrs must be a dict by array name");
+            double *const slot[6] = {nullptr, &o.scaleLr, &o.rotationLr, &o.alphaLr, &o.colorLr, &o.shLr};
+            for (auto item : py::reinterpret_borrow<py::dict>(lrs)) {
+              const std::string name = py::str(item.first).cast<std::string>();
+              const double x = py::cast<double>(item.second);
+              if (!std::isfinite(x) || x < 0.0) throw py::value_error("lrs[" + name + "] must be finite and >= 0");
+              int k = 0;
+              while (k < 6 && name != kArrays[k]) ++k;
+              if (k == 6) throw py::value_error("lrs: unknown array '" + name + "'");
+              if (k == 0) o.positionLr = x; else *slot[k] = x;
+            }
+          }
+          if (!train.is_none()) {
+            if (py::isinstance<py::str>(train) || !py::isinstance<py::sequence>(train)) {
+              throw py::value_error("train must be a sequence of array names");
+            }
+            o.train = 0;
+            for (auto item : py::reinterpret_borrow<py::sequence>(train)) {
+              const std::string name = py::str(item).cast<std::string>();
+              int k = 0;
+              while (k < 6 && name != kArrays[k]) ++k;
+              if (k == 6) throw py::value_error("train: unknown array '" + name + "'");
+              o.train |= 1u << k;
+            }
+            if (o.train == 0) throw py::value_error("train must name at least one array");
+          }
+          if (py::isinstance<py::dict>(views) || py::isinstance<py::str>(views) || !py::isinstance<py::sequence>(views)) {
+            throw py::value_error("views must be a sequence of view dicts (orbit_views, load_3dgs_cameras)");
+          }
+          const py::sequence seq = py::reinterpret_borrow<py::sequence>(views);
+          if (seq.size() < 1 || seq.size() > SPZ_AMD_REFINE_MAX_VIEWS) {
+            throw py::value_error("give 1..1024 views, got " + std::to_string(seq.size()));
+          }
+          for (size_t k = 0; k < seq.size(); ++k) o.views.push_back(pruneView(seq[k], k, coord, near_plane));
+          if (py::isinstance<py::bytes>(input) != py::isinstance<py::bytes>(target)) {
+            throw py::value_error("give input and target both as paths or both as bytes");
+          }
+          spz::RefineReport rep;
+          std::vector<uint8_t> bytes;
+          bool ok;
+          const bool fromBytes = py::isinstance<py::bytes>(input);
+          if (fromBytes) {
+            if (!output.is_none()) throw py::value_error("with bytes in, output must be None: the bytes are returned");
+            const std::string ba = input.cast<std::string>(), bb = target.cast<std::string>();
+            if (ba.size() > static_cast<size_t>(INT32_MAX) || bb.size() > static_cast<size_t>(INT32_MAX)) {
+              throw py::value_error("an input is larger than 2 GiB");
+            }
+            py::gil_scoped_release release;
+            ok = spz::refineSpz(reinterpret_cast<const uint8_t *>(ba.data()), static_cast<int32_t>(ba.size()),
+                                reinterpret_cast<const uint8_t *>(bb.data()), static_cast<int32_t>(bb.size()), o, &bytes,
+                                &rep);
+          } else {
+            if (output.is_none()) throw py::value_error("with paths in, give the output path");
+            const std::string fi = py::str(input).cast<std::string>(), ft = py::str(target).cast<std::string>(),
+                              fo = py::str(output).cast<std::string>();
+            py::gil_scoped_release release;
+            ok = spz::refineSpz(fi, ft, fo, o, &rep);
+          }
+          if (!ok) {
+            raiseFailure("refine_spz: refused (see the [SPZ ERROR] line)", "refine_spz failed (see the [SPZ ERROR] line)");
+          }
+          py::dict d;
+          d["history"] = rep.history;
+          py::list before, after;
+          for (const spz::ImageMetrics &x : rep.before) before.append(metricsDict(x));
+          for (const spz::ImageMetrics &x : rep.after) after.append(metricsDict(x));
+          d["before"] = before;
+          d["after"] = after;
+          d["skipped"] = rep.skipped;
+          d["position_lr"] = rep.positionLr;
+          d["ms"] = py::make_tuple(rep.ms[0], rep.ms[1], rep.ms[2]);
+          if (fromBytes) d["data"] = py::bytes(reinterpret_cast<const char *>(bytes.data()), bytes.size());
+          return d;
+        },
+        py::arg("input"), py::arg("target"), py::arg("output"), py::arg("views"), py::kw_only(),
+        py::arg("iterations") = 200, py::arg("coord") = spz::CoordinateSystem::UNSPECIFIED,
+        py::arg("background") = py::make_tuple(0.0f, 0.0f, 0.0f), py::arg("max_sh_degree") = 3, py::arg("near") = 0.2f,
+        py::arg("lambda_dssim") = 0.2, py::arg("lrs") = py::none(), py::arg("beta1") = 0.9, py::arg("beta2") = 0.999,
+        py::arg("eps") = 1e-15, py::arg("train") = py::none(),
+        "Fit the .spz file `input` to the file `target` over `views` on the device and write `output` (spz::refineSpz; "
+        "the contract is in include/spz_amd.h \"refine\"): the target is rendered once per view, then `iterations` Adam "
+        "steps on the 3DGS loss (1 - lambda_dssim) l1 + lambda_dssim (1 - ssim), view i mod V at step i, over the "
+        "arrays `train` names (default: all six of positions, scales, rotations, alphas, colors, sh); sections of "
+        "untrained arrays keep the input's bytes.  lrs: a dict by array name replacing 3DGS's published rates (the "
+        "position rate defaults to 1.6e-4 times the target's bounding-sphere radius).  Paths in: `output` is written; "
+        "bytes in (output None): the dict carries \"data\".  Returns a dict: history (the loss before each step), "
+        "before and after (one metrics dict per view, the latter of the written stream), skipped, position_lr, ms.");
   m.def("compare_images",
         [](const py::object &a, const py::object &b, const py::object &return_map) {
           if (!py::isinstance<py::bool_>(return_map)) throw py::value_error("return_map must be a bool");

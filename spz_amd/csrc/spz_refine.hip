@@ -1,0 +1,538 @@
+// spz_refine.hip — fitting a packed stream to a target over views (DESIGN §8 "Refine"; the contract is in
+// include/spz_amd.h): the Adam step over a float cloud and the loop from a stream to a stream.  The image loss and its
+// gradient are beside the metrics kernels (spz_metrics.hip), whose window and tile pass they share.
+//
+//   spz_adam_step_kernel           one launch for all trained arrays.  Every array is cut into 16-byte units from the
+//                                  first 16-aligned parameter address, with up to three scalar elements before and
+//                                  after; a workgroup belongs to one array (a table of first workgroups in the kernel
+//                                  arguments), a lane takes one unit: g, m, v, p in, m', v', p' out, in f32, one
+//                                  rounding per operation.  Non-finite p or g: the element is left alone and counted
+//                                  (one vector integer atomic per workgroup that has any).
+//   refine                         decode A; per view the target (B rendered) and the "before" metrics; per iteration
+//                                  prepare, the total read back, the workspace grown, finish, spz_amd_image_loss_device,
+//                                  spz_amd_render_backward_device, the Adam step; then the trained sections encoded over
+//                                  a copy of A's bytes and the "after" metrics of that stream.
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "spz_amd.h"
+#include "spz_common.hpp"
+
+namespace spz_amd_detail {
+namespace {
+
+constexpr uint32_t kAdBlock = 256;
+constexpr uint64_t kRfMaxEntries = 0x7fffffffull;  // the render's sort limit
+
+// One trained array of the launch: n4 16-byte units from element `head`, then the elements after them; the array's
+// workgroups begin at `first_block`.
+struct AdamSegment {
+  float *p, *m, *v;
+  const float *g;
+  unsigned long long count;  // elements
+  unsigned long long n4;     // 16-byte units
+  uint32_t head;             // scalar elements in front of the units, 0..3
+  uint32_t first_block;
+  float s;                   // lr / (1 - beta1^t)
+  uint32_t pad;
+};
+
+struct AdamLaunch {
+  AdamSegment seg[6];
+  uint32_t n_seg;
+  float beta1, c1, beta2, c2, eps, r;
+};
+
+__device__ __forceinline__ bool finite_bits(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+
+// torch's form of Adam on one element; false (and nothing changed) when p or g is not finite.
+__device__ __forceinline__ bool adam_one(float &p, float g, float &m, float &v, const AdamLaunch &a, float s) {
+  if (!finite_bits(p) || !finite_bits(g)) return false;
+  const float m1 = a.beta1 * m + a.c1 * g;
+  const float v1 = a.beta2 * v + (a.c2 * g) * g;
+  const float den = sqrtf(v1) / a.r + a.eps;
+  p = p - s * (m1 / den);
+  m = m1;
+  v = v1;
+  return true;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kAdBlock) void spz_adam_step_kernel(AdamLaunch a, uint32_t *__restrict__ skipped) {
+  __shared__ uint32_t part[kAdBlock / 64];
+  uint32_t k = 0;
+  while (k + 1 < a.n_seg && blockIdx.x >= a.seg[k + 1].first_block) ++k;  // uniform: a workgroup has one array
+  const AdamSegment &sg = a.seg[k];
+  const unsigned long long u = (unsigned long long)(blockIdx.x - sg.first_block) * kAdBlock + threadIdx.x;
+  const unsigned long long n_scalar = sg.count - 4ull * sg.n4;  // head + tail, at most 6
+  uint32_t bad = 0;
+  if (u < sg.n4) {
+    const unsigned long long e = sg.head + 4ull * u;
+    F32x4 p = *reinterpret_cast<const F32x4 *>(sg.p + e);
+    const F32x4 g = *reinterpret_cast<const F32x4 *>(sg.g + e);
+    F32x4 m = *reinterpret_cast<const F32x4 *>(sg.m + e);
+    F32x4 v = *reinterpret_cast<const F32x4 *>(sg.v + e);
+    bad += adam_one(p.x, g.x, m.x, v.x, a, sg.s) ? 0u : 1u;
+    bad += adam_one(p.y, g.y, m.y, v.y, a, sg.s) ? 0u : 1u;
+    bad += adam_one(p.z, g.z, m.z, v.z, a, sg.s) ? 0u : 1u;
+    bad += adam_one(p.w, g.w, m.w, v.w, a, sg.s) ? 0u : 1u;
+    if (bad != 4u) {  // (untouched elements are written back with the bits that were read)
+      *reinterpret_cast<F32x4 *>(sg.p + e) = p;
+      *reinterpret_cast<F32x4 *>(sg.m + e) = m;
+      *reinterpret_cast<F32x4 *>(sg.v + e) = v;
+    }
+  } else if (u - sg.n4 < n_scalar) {
+    const unsigned long long s = u - sg.n4;
+    const unsigned long long e = s < sg.head ? s : 4ull * sg.n4 + s;
+    float p = sg.p[e], m = sg.m[e], v = sg.v[e];
+    if (adam_one(p, sg.g[e], m, v, a, sg.s)) {
+      sg.p[e] = p;
+      sg.m[e] = m;
+      sg.v[e] = v;
+    } else {
+      bad = 1u;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o);
+  if ((threadIdx.x & 63u) == 0) part[threadIdx.x / 64] = bad;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t t = 0;
+    for (uint32_t w = 0; w < kAdBlock / 64; ++w) t += part[w];
+    if (t) atomicAdd(skipped, t);
+  }
+}
+
+namespace {
+
+bool finite_f(float x) { return std::isfinite(x); }
+
+int adam_check_scalars(const spz_amd_adam_scalars &s) {
+  if (!finite_f(s.beta1) || !finite_f(s.c1) || !finite_f(s.beta2) || !finite_f(s.c2) || !finite_f(s.eps) ||
+      !finite_f(s.r) || !(s.r > 0.0f) || !(s.eps >= 0.0f)) {
+    return SPZ_AMD_ERR_INVALID_ARG;
+  }
+  for (int k = 0; k < 6; ++k) {
+    if (!finite_f(s.s[k])) return SPZ_AMD_ERR_INVALID_ARG;
+  }
+  return SPZ_AMD_OK;
+}
+
+// The element counts of the six arrays in the order of spz_amd_cloud_in.
+void cloud_counts(uint64_t n, int sh_degree, uint64_t count[6]) {
+  const uint64_t sd = (uint64_t)sh_dim_for_degree(sh_degree);
+  const uint64_t c[6] = {3u * n, 3u * n, 4u * n, n, 3u * n, n * sd * 3u};
+  for (int k = 0; k < 6; ++k) count[k] = c[k];
+}
+
+float *grads_field(const spz_amd_cloud_grads *c, int k) {
+  float *const f[6] = {c->positions, c->scales, c->rotations, c->alphas, c->colors, c->sh};
+  return f[k];
+}
+
+int adam_enqueue(const spz_amd_cloud_grads *d_params, const spz_amd_cloud_grads *d_grads, const spz_amd_cloud_grads *d_m,
+                 const spz_amd_cloud_grads *d_v, uint64_t num_points, int sh_degree, unsigned train_mask,
+                 const spz_amd_adam_scalars &sc, uint32_t *d_skipped, hipStream_t st) {
+  uint64_t count[6];
+  cloud_counts(num_points, sh_degree, count);
+  AdamLaunch a = {};
+  a.beta1 = sc.beta1;
+  a.c1 = sc.c1;
+  a.beta2 = sc.beta2;
+  a.c2 = sc.c2;
+  a.eps = sc.eps;
+  a.r = sc.r;
+  uint64_t blocks = 0;
+  for (int k = 0; k < 6; ++k) {
+    if (((train_mask >> k) & 1u) == 0u || count[k] == 0) continue;
+    AdamSegment &sg = a.seg[a.n_seg++];
+    sg.p = grads_field(d_params, k);
+    sg.g = grads_field(d_grads, k);
+    sg.m = grads_field(d_m, k);
+    sg.v = grads_field(d_v, k);
+    sg.count = count[k];
+    const uint64_t to16 = ((16u - (reinterpret_cast<uintptr_t>(sg.p) & 15u)) & 15u) / 4u;
+    sg.head = (uint32_t)(to16 < count[k] ? to16 : count[k]);
+    sg.n4 = (count[k] - sg.head) / 4u;
+    sg.first_block = (uint32_t)blocks;
+    sg.s = sc.s[k];
+    const uint64_t units = sg.n4 + (count[k] - 4u * sg.n4);
+    blocks += (units + kAdBlock - 1) / kAdBlock;
+  }
+  if (a.n_seg == 0) return SPZ_AMD_OK;
+  if (blocks > 0x7fffffffull) return SPZ_AMD_ERR_TOO_MANY_POINTS;
+  hipLaunchKernelGGL(spz_adam_step_kernel, dim3((unsigned)blocks), dim3(kAdBlock), 0, st, a, d_skipped);
+  SPZ_HIP_TRY(hipGetLastError());
+  return SPZ_AMD_OK;
+}
+
+bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+int adam_check_args(const spz_amd_cloud_grads *d_params, const spz_amd_cloud_grads *d_grads, const spz_amd_cloud_grads *d_m,
+                    const spz_amd_cloud_grads *d_v, uint64_t num_points, int sh_degree, unsigned train_mask,
+                    const spz_amd_adam_scalars &sc, const uint32_t *d_skipped) {
+  if (d_params == nullptr || d_grads == nullptr || d_m == nullptr || d_v == nullptr || d_skipped == nullptr) {
+    return SPZ_AMD_ERR_INVALID_ARG;
+  }
+  if (sh_degree < 0 || sh_degree > 3) return SPZ_AMD_ERR_SH_DEGREE;
+  if (train_mask == 0u || train_mask > SPZ_AMD_TRAIN_ALL || !aligned4(d_skipped)) return SPZ_AMD_ERR_INVALID_ARG;
+  if (num_points > kRfMaxEntries) return SPZ_AMD_ERR_TOO_MANY_POINTS;
+  int rc = adam_check_scalars(sc);
+  if (rc != SPZ_AMD_OK) return rc;
+  uint64_t count[6];
+  cloud_counts(num_points, sh_degree, count);
+  for (int k = 0; k < 6; ++k) {
+    if (((train_mask >> k) & 1u) == 0u || count[k] == 0) continue;
+    for (const spz_amd_cloud_grads *c : {d_params, d_grads, d_m, d_v}) {
+      const float *f = grads_field(c, k);
+      if (f == nullptr || !aligned4(f)) return SPZ_AMD_ERR_INVALID_ARG;
+    }
+  }
+  return SPZ_AMD_OK;
+}
+
+// The float cloud, its gradients and moments: four times the six arrays, each array 256-aligned in one allocation.
+struct CloudSet {
+  spz_amd_cloud_grads p, g, m, v;
+  uint64_t moments_off = 0, moments_bytes = 0;  // m and v are contiguous: one memset
+};
+
+spz_amd_cloud_grads cloud_at(uint8_t *base, const uint64_t off[6], const uint64_t count[6]) {
+  auto f = [&](int k) { return count[k] ? reinterpret_cast<float *>(base + off[k]) : nullptr; };
+  return spz_amd_cloud_grads{f(0), f(1), f(2), f(3), f(4), f(5)};
+}
+
+// One view of a packed stream or of the float cloud into d_image, the render workspace (r->scratch) grown as the
+// prune loop grows it.  *cap: its size.  A total above the sort's limit: SPZ_AMD_ERR_CAPACITY.
+struct RenderSource {
+  const uint8_t *d_stream = nullptr;  // packed
+  size_t size = 0;
+  const spz_amd_header *hdr = nullptr;
+  const spz_amd_cloud_in *cloud = nullptr;  // float
+  uint64_t n = 0;
+  int sh_degree = 0, antialiased = 0;
+};
+
+int refine_render(PackedResult *r, uint64_t *cap, const RenderSource &src, const spz_amd_render_params *p,
+                  uint64_t *d_total, uint32_t *d_status, float *d_image, uint64_t *h_total) {
+  const uint64_t n = src.n;
+  const uint64_t prefix = spz_amd_render_workspace_bytes(n, 0) - 256u;
+  if (*cap < prefix + 256u) {
+    SPZ_HIP_TRY(hipStreamSynchronize(r->st));  // an earlier view's blend may still read it
+    if (r->scratch) SPZ_HIP_TRY(hipFree(r->scratch));
+    r->scratch = nullptr;
+    *cap = 0;
+    SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&r->scratch), prefix + 256u));
+    *cap = prefix + 256u;
+  }
+  int rc = src.cloud ? spz_amd_render_prepare_cloud_device(src.cloud, n, src.sh_degree, src.antialiased, p, d_total,
+                                                            nullptr, r->scratch, r->st)
+                     : spz_amd_render_prepare_packed_device(src.d_stream, src.size, src.hdr, p, d_total, nullptr,
+                                                            r->scratch, r->st);
+  if (rc != SPZ_AMD_OK) return rc;
+  uint64_t total = 0;
+  SPZ_HIP_TRY(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, r->st));
+  SPZ_HIP_TRY(hipStreamSynchronize(r->st));
+  *h_total = total;
+  if (total > kRfMaxEntries) return SPZ_AMD_ERR_CAPACITY;
+  const uint64_t need = spz_amd_render_workspace_bytes(n, total);
+  if (need > *cap) {
+    uint8_t *bigger = nullptr;
+    SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&bigger), need));
+    if (prefix) {
+      const hipError_t e = hipMemcpyAsync(align_ws(bigger), align_ws(r->scratch), prefix, hipMemcpyDeviceToDevice, r->st);
+      if (e == hipSuccess) (void)hipStreamSynchronize(r->st);
+      if (e != hipSuccess) {
+        (void)hipFree(bigger);
+        g_last_hip_error = (int)e;
+        return SPZ_AMD_ERR_HIP;
+      }
+    }
+    SPZ_HIP_TRY(hipFree(r->scratch));
+    r->scratch = bigger;
+    *cap = need;
+  }
+  return spz_amd_render_finish_device(n, p, total, d_image, d_status, r->scratch, r->st);
+}
+
+}  // namespace
+}  // namespace spz_amd_detail
+
+using namespace spz_amd_detail;
+
+extern "C" {
+
+int spz_amd_adam_scalars_of(int t, const double lr[6], double beta1, double beta2, double eps,
+                            spz_amd_adam_scalars *out) {
+  if (out == nullptr || lr == nullptr || t < 1) return SPZ_AMD_ERR_INVALID_ARG;
+  if (!(beta1 >= 0.0) || !(beta1 < 1.0) || !(beta2 >= 0.0) || !(beta2 < 1.0) || !(eps >= 0.0) || !std::isfinite(eps)) {
+    return SPZ_AMD_ERR_INVALID_ARG;
+  }
+  for (int k = 0; k < 6; ++k) {
+    if (!std::isfinite(lr[k]) || lr[k] < 0.0) return SPZ_AMD_ERR_INVALID_ARG;
+  }
+  const double bc1 = 1.0 - std::pow(beta1, (double)t), bc2 = 1.0 - std::pow(beta2, (double)t);
+  out->beta1 = (float)beta1;
+  out->c1 = (float)(1.0 - beta1);
+  out->beta2 = (float)beta2;
+  out->c2 = (float)(1.0 - beta2);
+  out->eps = (float)eps;
+  out->r = (float)std::sqrt(bc2);
+  for (int k = 0; k < 6; ++k) out->s[k] = (float)(lr[k] / bc1);
+  return adam_check_scalars(*out);
+}
+
+int spz_amd_adam_step_device(const spz_amd_cloud_grads *d_params, const spz_amd_cloud_grads *d_grads,
+                             const spz_amd_cloud_grads *d_m, const spz_amd_cloud_grads *d_v, uint64_t num_points,
+                             int sh_degree, unsigned train_mask, spz_amd_adam_scalars scalars, uint32_t *d_skipped,
+                             void *hip_stream) {
+  int rc = adam_check_args(d_params, d_grads, d_m, d_v, num_points, sh_degree, train_mask, scalars, d_skipped);
+  if (rc != SPZ_AMD_OK) return rc;
+  int device = 0;
+  rc = current_device(&device);
+  if (rc != SPZ_AMD_OK) return rc;
+  return adam_enqueue(d_params, d_grads, d_m, d_v, num_points, sh_degree, train_mask, scalars, d_skipped,
+                      static_cast<hipStream_t>(hip_stream));
+}
+
+int spz_amd_refine_default_options(spz_amd_refine_options *options) {
+  if (options == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
+  std::memset(options, 0, sizeof(*options));
+  options->iterations = 0;
+  options->train_mask = SPZ_AMD_TRAIN_ALL;
+  options->lambda_dssim = 0.2;
+  options->lr[0] = 1.6e-4;  // times the scene's extent: the layers above scale it
+  options->lr[1] = 5e-3;
+  options->lr[2] = 1e-3;
+  options->lr[3] = 5e-2;
+  options->lr[4] = 2.5e-3;
+  options->lr[5] = 2.5e-3 / 20.0;
+  options->beta1 = 0.9;
+  options->beta2 = 0.999;
+  options->eps = 1e-15;
+  return SPZ_AMD_OK;
+}
+
+int spz_amd_refine_check(const spz_amd_refine_options *o) {
+  if (o == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
+  if (o->iterations < 0 || o->train_mask == 0u || o->train_mask > SPZ_AMD_TRAIN_ALL) return SPZ_AMD_ERR_INVALID_ARG;
+  if (!(o->lambda_dssim >= 0.0) || !(o->lambda_dssim <= 1.0)) return SPZ_AMD_ERR_INVALID_ARG;
+  spz_amd_adam_scalars sc;
+  return spz_amd_adam_scalars_of(1, o->lr, o->beta1, o->beta2, o->eps, &sc);
+}
+
+int spz_amd_refine_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
+                        const uint8_t *d_stream_b, size_t size_b, const spz_amd_header *hdr_b,
+                        const spz_amd_render_params *views, int num_views, const spz_amd_refine_options *options,
+                        int device, void **ctx, uint64_t *h_out_bytes, double *h_history,
+                        spz_amd_image_metrics *h_before, spz_amd_image_metrics *h_after, uint64_t *h_skipped, float *h_ms,
+                        int32_t *h_bad_view) {
+  if (h_bad_view) *h_bad_view = -1;
+  if (ctx == nullptr || h_out_bytes == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
+  *ctx = nullptr;
+  *h_out_bytes = 0;
+  if (views == nullptr || num_views < 1 || num_views > SPZ_AMD_REFINE_MAX_VIEWS) return SPZ_AMD_ERR_INVALID_ARG;
+  int rc = spz_amd_refine_check(options);
+  if (rc != SPZ_AMD_OK) return rc;
+  if (options->iterations > 0 && h_history == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
+  for (int v = 0; v < num_views; ++v) {
+    if (spz_amd_render_check_params(&views[v]) != SPZ_AMD_OK || views[v].coord != views[0].coord) {
+      if (h_bad_view) *h_bad_view = v;
+      return SPZ_AMD_ERR_INVALID_ARG;
+    }
+  }
+  spz_amd_layout lay_a, lay_b;
+  rc = check_packed_stream(d_stream_a, size_a, hdr_a, &lay_a);
+  if (rc != SPZ_AMD_OK) return rc;
+  rc = check_packed_stream(d_stream_b, size_b, hdr_b, &lay_b);
+  if (rc != SPZ_AMD_OK) return rc;
+  if (hdr_a->num_points > kRfMaxEntries || hdr_b->num_points > kRfMaxEntries) return SPZ_AMD_ERR_TOO_MANY_POINTS;
+  const uint64_t n = hdr_a->num_points;
+  const int deg = hdr_a->sh_degree, aa = hdr_a->flags & 1, coord = views[0].coord;
+  const int iters = options->iterations;
+  unsigned mask = options->train_mask;
+  if (deg == 0) mask &= ~32u;  // nothing to train there
+  // what the encode kernel writes: versions 2 and 3, positions at 12 fractional bits
+  if (iters > 0 && (hdr_a->version == 1 || ((mask & 1u) && hdr_a->fractional_bits != 12))) return SPZ_AMD_ERR_UNSUPPORTED;
+  DeviceGuard guard;
+  rc = guard.enter(device);
+  if (rc != SPZ_AMD_OK) return rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  PackedResultPtr c;
+  rc = packed_result_open(device, &c);
+  if (rc != SPZ_AMD_OK) return rc;
+
+  // the block: four clouds, the targets, the image and its gradient, the two small workspaces, the results
+  uint64_t count[6];
+  cloud_counts(n, deg, count);
+  uint64_t max_px = 0, loss_ws = 0, metrics_ws = 0;
+  std::vector<uint64_t> target_off((size_t)num_views);
+  for (int v = 0; v < num_views; ++v) {
+    const uint64_t px = (uint64_t)views[v].width * views[v].height;
+    max_px = px > max_px ? px : max_px;
+    const uint64_t lw = spz_amd_image_loss_workspace_bytes((int)views[v].width, (int)views[v].height);
+    const uint64_t mw = spz_amd_image_metrics_workspace_bytes((int)views[v].width, (int)views[v].height);
+    loss_ws = lw > loss_ws ? lw : loss_ws;
+    metrics_ws = mw > metrics_ws ? mw : metrics_ws;
+  }
+  WorkspaceOffsets o;
+  uint64_t off[4][6];
+  for (int s = 0; s < 4; ++s) {
+    for (int k = 0; k < 6; ++k) off[s][k] = o.put(count[k] * 4u);
+  }
+  for (int v = 0; v < num_views; ++v) target_off[(size_t)v] = o.put(16u * (uint64_t)views[v].width * views[v].height);
+  const uint64_t o_image = o.put(16u * max_px), o_grad = o.put(16u * max_px), o_lws = o.put(iters ? loss_ws : 0u),
+                 o_mws = o.put(metrics_ws), o_small = o.put(16u), o_loss = o.put(24u * (uint64_t)iters),
+                 o_metrics = o.put(2u * (uint64_t)num_views * sizeof(spz_amd_image_metrics)),
+                 o_bws = o.put(iters ? spz_amd_render_backward_workspace_bytes(n) : 0u);
+  SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->block), o.off));
+  uint8_t *raw = c->block;  // every section is 256-aligned from hipMalloc's base
+  CloudSet cs;
+  cs.p = cloud_at(raw, off[0], count);
+  cs.g = cloud_at(raw, off[1], count);
+  cs.m = cloud_at(raw, off[2], count);
+  cs.v = cloud_at(raw, off[3], count);
+  cs.moments_off = off[2][0];
+  cs.moments_bytes = target_off[0] - off[2][0];
+  auto *d_image = reinterpret_cast<float *>(raw + o_image);
+  auto *d_grad = reinterpret_cast<float *>(raw + o_grad);
+  auto *d_total = reinterpret_cast<uint64_t *>(raw + o_small);
+  auto *d_status = reinterpret_cast<uint32_t *>(raw + o_small + 8u);
+  auto *d_skipped = reinterpret_cast<uint32_t *>(raw + o_small + 12u);
+  auto *d_loss = reinterpret_cast<double *>(raw + o_loss);
+  auto *d_metrics = reinterpret_cast<spz_amd_image_metrics *>(raw + o_metrics);
+  auto target = [&](int v) { return reinterpret_cast<float *>(raw + target_off[(size_t)v]); };
+  auto fail = [&](int v, int r) {
+    if (h_bad_view) *h_bad_view = v;
+    return r;
+  };
+  SPZ_HIP_TRY(hipMemsetAsync(d_skipped, 0, 4, c->st));
+
+  // the output begins as A's bytes
+  SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->out_block), lay_a.total_bytes));
+  SPZ_HIP_TRY(hipMemcpyAsync(c->out_block, d_stream_a, lay_a.total_bytes, hipMemcpyDeviceToDevice, c->st));
+  c->out = c->out_block;
+  c->out_bytes = lay_a.total_bytes;
+
+  // targets and the "before" metrics
+  uint64_t cap = 0, total = 0;
+  RenderSource src_a, src_b;
+  src_a.d_stream = d_stream_a;
+  src_a.size = size_a;
+  src_a.hdr = hdr_a;
+  src_a.n = n;
+  src_b.d_stream = d_stream_b;
+  src_b.size = size_b;
+  src_b.hdr = hdr_b;
+  src_b.n = hdr_b->num_points;
+  for (int v = 0; v < num_views; ++v) {
+    const spz_amd_render_params &p = views[v];
+    rc = refine_render(c.get(), &cap, src_b, &p, d_total, d_status, target(v), &total);
+    if (rc != SPZ_AMD_OK) return fail(v, rc);
+    rc = refine_render(c.get(), &cap, src_a, &p, d_total, d_status, d_image, &total);
+    if (rc != SPZ_AMD_OK) return fail(v, rc);
+    rc = spz_amd_image_metrics_device(d_image, 4, target(v), 4, (int)p.width, (int)p.height, d_metrics + v, nullptr,
+                                      raw + o_mws, c->st);
+    if (rc != SPZ_AMD_OK) return fail(v, rc);
+  }
+  SPZ_HIP_TRY(hipStreamSynchronize(c->st));
+  const double before_ms = ms_since(t0);
+
+  // the iterations
+  if (iters > 0) {
+    const spz_amd_cloud_out dec = {cs.p.positions, cs.p.scales, cs.p.rotations, cs.p.alphas, cs.p.colors, cs.p.sh};
+    rc = spz_amd_decode_device(d_stream_a, size_a, hdr_a, coord, &dec, c->st);
+    if (rc != SPZ_AMD_OK) return rc;
+    if (cs.moments_bytes) SPZ_HIP_TRY(hipMemsetAsync(raw + cs.moments_off, 0, cs.moments_bytes, c->st));
+    const spz_amd_cloud_in cloud = {cs.p.positions, cs.p.scales, cs.p.rotations, cs.p.alphas, cs.p.colors, cs.p.sh};
+    RenderSource src_f;
+    src_f.cloud = &cloud;
+    src_f.n = n;
+    src_f.sh_degree = deg;
+    src_f.antialiased = aa;
+    for (int i = 0; i < iters; ++i) {
+      const int v = i % num_views;
+      const spz_amd_render_params &p = views[v];
+      rc = refine_render(c.get(), &cap, src_f, &p, d_total, d_status, d_image, &total);
+      if (rc != SPZ_AMD_OK) return fail(v, rc);
+      rc = spz_amd_image_loss_device(d_image, 4, target(v), 4, (int)p.width, (int)p.height, options->lambda_dssim,
+                                     d_loss + 3 * (size_t)i, d_grad, raw + o_lws, c->st);
+      if (rc != SPZ_AMD_OK) return fail(v, rc);
+      rc = spz_amd_render_backward_device(&cloud, n, deg, aa, &p, total, d_image, d_grad, &cs.g, nullptr, d_status,
+                                          c->scratch, raw + o_bws, c->st);
+      if (rc != SPZ_AMD_OK) return fail(v, rc);
+      if (n) {
+        spz_amd_adam_scalars sc;
+        rc = spz_amd_adam_scalars_of(i + 1, options->lr, options->beta1, options->beta2, options->eps, &sc);
+        if (rc != SPZ_AMD_OK) return rc;
+        rc = adam_enqueue(&cs.p, &cs.g, &cs.m, &cs.v, n, deg, mask, sc, d_skipped, c->st);
+        if (rc != SPZ_AMD_OK) return rc;
+      }
+    }
+    // the trained sections over the copy of A's bytes, from the views' frame back to the file's
+    const unsigned sec_of[6] = {1u << SPZ_AMD_SEC_POSITIONS, 1u << SPZ_AMD_SEC_SCALES, 1u << SPZ_AMD_SEC_ROTATIONS,
+                                1u << SPZ_AMD_SEC_ALPHAS,    1u << SPZ_AMD_SEC_COLORS, 1u << SPZ_AMD_SEC_SH};
+    unsigned sections = 0;
+    for (int k = 0; k < 6; ++k) sections |= ((mask >> k) & 1u) ? sec_of[k] : 0u;
+    if (n && sections) {
+      rc = spz_amd_encode_shard_sections_device(&cloud, 0, n, n, deg, aa, coord, (int)hdr_a->version, 0, sections,
+                                                c->out_block, lay_a.total_bytes, c->st);
+      if (rc != SPZ_AMD_OK) return rc;
+    }
+  }
+  SPZ_HIP_TRY(hipStreamSynchronize(c->st));
+  const double loop_ms = ms_since(t0) - before_ms;
+
+  // the "after" metrics: of the output stream
+  RenderSource src_o = src_a;
+  src_o.d_stream = c->out_block;
+  src_o.size = lay_a.total_bytes;
+  for (int v = 0; v < num_views; ++v) {
+    const spz_amd_render_params &p = views[v];
+    if (iters == 0) break;
+    rc = refine_render(c.get(), &cap, src_o, &p, d_total, d_status, d_image, &total);
+    if (rc != SPZ_AMD_OK) return fail(v, rc);
+    rc = spz_amd_image_metrics_device(d_image, 4, target(v), 4, (int)p.width, (int)p.height, d_metrics + num_views + v,
+                                      nullptr, raw + o_mws, c->st);
+    if (rc != SPZ_AMD_OK) return fail(v, rc);
+  }
+  const size_t mbytes = (size_t)num_views * sizeof(spz_amd_image_metrics);
+  if (h_before) SPZ_HIP_TRY(hipMemcpyAsync(h_before, d_metrics, mbytes, hipMemcpyDeviceToHost, c->st));
+  if (h_after) {
+    SPZ_HIP_TRY(hipMemcpyAsync(h_after, iters ? d_metrics + num_views : d_metrics, mbytes, hipMemcpyDeviceToHost, c->st));
+  }
+  std::vector<double> loss3(3u * (size_t)iters);
+  if (iters) SPZ_HIP_TRY(hipMemcpyAsync(loss3.data(), d_loss, 24u * (size_t)iters, hipMemcpyDeviceToHost, c->st));
+  uint32_t skipped = 0;
+  SPZ_HIP_TRY(hipMemcpyAsync(&skipped, d_skipped, 4, hipMemcpyDeviceToHost, c->st));
+  SPZ_HIP_TRY(hipStreamSynchronize(c->st));
+  for (int i = 0; i < iters; ++i) h_history[i] = loss3[3u * (size_t)i];
+  if (h_skipped) *h_skipped = skipped;
+  if (h_ms) {
+    h_ms[0] = (float)before_ms;
+    h_ms[1] = (float)loop_ms;
+    h_ms[2] = (float)(ms_since(t0) - before_ms - loop_ms);
+  }
+  *h_out_bytes = c->out_bytes;
+  // fetch needs the output alone
+  SPZ_HIP_TRY(hipFree(c->scratch));
+  c->scratch = nullptr;
+  SPZ_HIP_TRY(hipFree(c->block));
+  c->block = nullptr;
+  *ctx = c.release();
+  return SPZ_AMD_OK;
+}
+
+int spz_amd_refine_fetch(void *ctx, uint8_t *h_out) { return packed_result_fetch(ctx, h_out); }
+
+const uint8_t *spz_amd_refine_device_data(void *ctx) { return packed_result_device_data(ctx); }
+
+void spz_amd_refine_close(void *ctx) { packed_result_close(ctx); }
+
+}  // extern "C"

@@ -1270,6 +1270,174 @@ def image_metrics(a_t, b_t, ssim_map=None, stream=None):
     return out
 
 
+def _check_image(name, t):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() \
+            or t.dim() != 3 or t.shape[2] not in (3, 4):
+        raise ValueError(f"{name} must be a contiguous float32 CUDA tensor of shape (height, width, 3 or 4)")
+
+
+def image_loss(a_t, b_t, lambda_dssim, grad=None, stream=None):
+    """The 3DGS training loss L = (1 - lambda) l1 + lambda (1 - ssim) of a render a_t against a target b_t, two (height,
+    width, 3 or 4) float32 CUDA tensors on one device, and its gradient to a_t (spz_amd_image_loss_device; the contract
+    is in include/spz_amd.h "image loss"): (loss_t, grad_t).  loss_t: a float64 tensor [L, l1, ssim] on the device, not
+    synchronised.  grad_t: float32, shaped like a_t (with four channels it is render_backward()'s grad_image); `grad`: a
+    tensor to write it into.  stream: as render()."""
+    L = abi.load_library()
+    _check_image("a", a_t)
+    _check_image("b", b_t)
+    dev = a_t.device
+    if b_t.device != dev or tuple(a_t.shape[:2]) != tuple(b_t.shape[:2]):
+        raise ValueError("a and b must have the same height and width, on one device")
+    h, w, ca, cb = int(a_t.shape[0]), int(a_t.shape[1]), int(a_t.shape[2]), int(b_t.shape[2])
+    abi.check(L.spz_amd_image_metrics_check(w, h, ca, cb), "spz_amd_image_metrics_check")
+    lam = float(lambda_dssim)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"lambda_dssim must be in [0, 1], got {lambda_dssim!r}")
+    _check_out("grad", grad, (h, w, ca), torch.float32, dev)
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        with torch.cuda.stream(st):
+            loss = torch.empty(3, dtype=torch.float64, device=dev)
+            if grad is None:
+                grad = torch.empty((h, w, ca), dtype=torch.float32, device=dev)
+            ws = torch.empty(int(L.spz_amd_image_loss_workspace_bytes(w, h)), dtype=torch.uint8, device=dev)
+            rc = L.spz_amd_image_loss_device(a_t.data_ptr(), ca, b_t.data_ptr(), cb, w, h, lam, loss.data_ptr(),
+                                             grad.data_ptr(), ws.data_ptr(), C.c_void_p(st.cuda_stream))
+    abi.check(rc, "spz_amd_image_loss_device")
+    return loss, grad
+
+
+def _train_ptrs(cloud, sh_degree, n, device, mask):
+    """CloudPtrs of the arrays a train mask names (checked like _ptrs); the others NULL."""
+    p = abi.CloudPtrs()
+    for i, k in enumerate(abi.TRAIN_ARRAYS):
+        need = n * floats_per_point(k, sh_degree)
+        if need == 0 or not (mask >> i) & 1:
+            setattr(p, k, None)
+            continue
+        t = cloud.get(k)
+        if t is None or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() != need \
+                or t.device != device:
+            raise ValueError(f"[{k!r}] must be a contiguous float32 tensor of {need} elements on {device}")
+        setattr(p, k, t.data_ptr())
+    return p
+
+
+def adam_step(cloud, grads, m, v, num_points, sh_degree, t, lrs, beta1=0.9, beta2=0.999, eps=1e-15, train=abi.TRAIN_ALL,
+              skipped=None, stream=None):
+    """One Adam step, in place, over the trained arrays of a float cloud (spz_amd_adam_step_device; the contract is in
+    include/spz_amd.h "adam step").  cloud, grads, m, v: dicts of flat float32 CUDA tensors keyed and shaped like the
+    cloud (m and v zero before step 1); the arrays `train` (names, or a mask) leaves out may be missing.  t: the step,
+    from 1.  lrs: six learning rates in abi.TRAIN_ARRAYS' order, or a dict by name.  Elements whose parameter or
+    gradient is not finite are left alone and counted into `skipped`, an int32 CUDA tensor [1] (a zeroed one is made
+    when None) that is returned, not synchronised.  stream: as render()."""
+    L = abi.load_library()
+    if int(sh_degree) not in SH_DIM:
+        raise ValueError(f"sh_degree must be 0..3, got {sh_degree}")
+    mask = abi.train_mask(train)
+    if isinstance(lrs, dict):
+        lrs = [float(lrs.get(k, 0.0)) for k in abi.TRAIN_ARRAYS]
+    sc = abi.adam_scalars(t, lrs, beta1, beta2, eps)
+    first = next(x for x in cloud.values() if x is not None)
+    dev = first.device
+    n = int(num_points)
+    ptrs = [_train_ptrs(c, sh_degree, n, dev, mask) for c in (cloud, grads, m, v)]
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        with torch.cuda.stream(st):
+            if skipped is None:
+                skipped = torch.zeros(1, dtype=torch.int32, device=dev)
+            _check_out("skipped", skipped, (1,), torch.int32, dev)
+            rc = L.spz_amd_adam_step_device(C.byref(ptrs[0]), C.byref(ptrs[1]), C.byref(ptrs[2]), C.byref(ptrs[3]), n,
+                                            int(sh_degree), mask, sc, skipped.data_ptr(), C.c_void_p(st.cuda_stream))
+    abi.check(rc, "spz_amd_adam_step_device")
+    return skipped
+
+
+def _metrics_dict(m):
+    return {"mse": m.mse, "psnr": m.psnr, "ssim": m.ssim, "l1": m.l1, "max_abs": m.max_abs}
+
+
+class RefineResult:
+    """The output of refine_packed(): `report` (history, before, after, skipped, ms, out_bytes) and the output stream
+    in device memory until close().  tensor(): a uint8 CUDA view of it (not valid after close()); fetch(): its bytes as
+    a numpy array.  After close() both raise."""
+
+    def __init__(self, ctx, out_bytes, device, report):
+        self._ctx, self.out_bytes, self.device, self.report = ctx, int(out_bytes), device, report
+
+    def _open(self):
+        if self._ctx is None:
+            raise RuntimeError("the refine result is closed")
+        return self._ctx
+
+    def tensor(self):
+        ptr = abi.load_library().spz_amd_refine_device_data(self._open())
+        return torch.as_tensor(_DeviceArray(ptr, self.out_bytes, "|u1", self), device=self.device)
+
+    def fetch(self):
+        import numpy as np
+        out = np.empty(self.out_bytes, dtype=np.uint8)
+        abi.check(abi.load_library().spz_amd_refine_fetch(self._open(), out.ctypes.data), "spz_amd_refine_fetch")
+        return out
+
+    def close(self):
+        if self._ctx is not None:
+            ctx, self._ctx = self._ctx, None
+            abi.load_library().spz_amd_refine_close(ctx)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001  (interpreter shutdown)
+            pass
+
+
+def refine_packed(stream_a, header_a, stream_b, header_b, views, iterations, *, lambda_dssim=None, lrs=None, beta1=None,
+                  beta2=None, eps=None, train=None):
+    """Fit the resident packed stream A to the target B over `views` (a sequence of abi.RenderParams, one coord):
+    spz_amd_refine_open (include/spz_amd.h "refine").  Options left None take spz_amd_refine_default_options' values
+    (lrs[0], the position rate, is for a scene of unit extent: scale it by the scene's).  Blocks; runs on a stream of
+    the library's own after the current stream has drained.  Returns a RefineResult; a bad view raises
+    abi.SpzAmdError whose `view` attribute names it."""
+    L = abi.load_library()
+    _check_stream_tensor(stream_a)
+    _check_stream_tensor(stream_b)
+    dev = stream_a.device
+    if stream_b.device != dev:
+        raise ValueError("the two streams must be on one device")
+    views = list(views)
+    if not 1 <= len(views) <= abi.REFINE_MAX_VIEWS or not all(isinstance(p, abi.RenderParams) for p in views):
+        raise ValueError(f"views must be 1..{abi.REFINE_MAX_VIEWS} abi.RenderParams")
+    opts = abi.refine_options(iterations, lambda_dssim=lambda_dssim, lrs=lrs, beta1=beta1, beta2=beta2, eps=eps,
+                              train=train)
+    arr = (abi.RenderParams * len(views))(*views)
+    ctx, out_bytes, skipped, bad = C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_int32(-1)
+    history = (C.c_double * max(1, opts.iterations))()
+    before = (abi.ImageMetrics * len(views))()
+    after = (abi.ImageMetrics * len(views))()
+    ms = (C.c_float * 3)()
+    torch.cuda.current_stream(dev).synchronize()  # the streams' producers
+    rc = L.spz_amd_refine_open(stream_a.data_ptr(), stream_a.numel(), C.byref(header_a), stream_b.data_ptr(),
+                               stream_b.numel(), C.byref(header_b), arr, len(views), C.byref(opts),
+                               dev.index if dev.index is not None else torch.cuda.current_device(), C.byref(ctx),
+                               C.byref(out_bytes), history, before, after, C.byref(skipped), ms, C.byref(bad))
+    if rc != abi.OK:
+        err = abi.SpzAmdError(rc, "spz_amd_refine_open" + (f" (view {bad.value})" if bad.value >= 0 else ""))
+        err.view = bad.value
+        raise err
+    report = {"history": [history[i] for i in range(max(0, opts.iterations))],
+              "before": [_metrics_dict(x) for x in before], "after": [_metrics_dict(x) for x in after],
+              "skipped": int(skipped.value), "ms": tuple(ms), "out_bytes": int(out_bytes.value)}
+    return RefineResult(ctx, out_bytes.value, dev, report)
+
+
 def convert_coordinates(cloud, num_points, sh_degree, from_coord, to_coord, stream=None):
     """In-place GaussianCloud::convertCoordinates on device tensors (positions, rotations, sh)."""
     L = abi.load_library()
@@ -1296,5 +1464,5 @@ def to_numpy(cloud_t):
 
 __all__ = ["encode", "decode", "encode_shard", "decode_shard", "decode_gather", "peek_header", "convert_coordinates",
            "select", "subset", "transform", "transform_packed", "merge_packed",
-           "alloc_cloud",
+           "alloc_cloud", "image_loss", "adam_step", "refine_packed",
            "make_header", "to_device", "to_numpy", "SH_DIM"]
