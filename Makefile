@@ -32,7 +32,7 @@ python: $(ROOT)spz_amd/spz$(PYEXT)
 cli:    $(ROOT)spz_amd/bin/spz_tool $(ROOT)spz_amd/bin/dropin_user_test $(ROOT)spz_amd/bin/host_bench
 
 DEVICE_SRCS := $(CSRC)/spz_kernels.hip $(CSRC)/spz_abi.hip $(CSRC)/spz_hostpath.hip $(CSRC)/spz_ply_kernels.hip $(CSRC)/spz_median.hip $(CSRC)/spz_exchange.hip $(CSRC)/spz_lz77.hip $(CSRC)/spz_inflate_dev.hip $(CSRC)/spz_place.hip $(CSRC)/spz_filter.hip $(CSRC)/spz_transform.hip $(CSRC)/spz_merge.hip $(CSRC)/spz_sort.hip $(CSRC)/spz_decimate.hip $(CSRC)/spz_tile.hip $(CSRC)/spz_clean.hip $(CSRC)/spz_align.hip $(CSRC)/spz_render.hip $(CSRC)/spz_render_backward.hip $(CSRC)/spz_prune.hip $(CSRC)/spz_metrics.hip $(CSRC)/spz_refine.hip
-$(LIBDIR)/libspz_amd.so: $(DEVICE_SRCS) $(CSRC)/spz_common.hpp $(CSRC)/spz_kernel_params.hpp $(CSRC)/spz_quant.hpp $(CSRC)/spz_sort_internal.hpp $(CSRC)/spz_render_internal.hpp $(CSRC)/spz_morton_walk.hpp $(CSRC)/spz_block_ops.hpp $(CSRC)/spz_xf.hpp $(CSRC)/spz_lz77_core.hpp $(CSRC)/spz_huff_core.hpp $(CSRC)/spz_inflate_core.hpp $(INC)/spz_amd.h
+$(LIBDIR)/libspz_amd.so: $(DEVICE_SRCS) $(CSRC)/spz_common.hpp $(CSRC)/spz_kernel_params.hpp $(CSRC)/spz_quant.hpp $(CSRC)/spz_sort_internal.hpp $(CSRC)/spz_render_internal.hpp $(CSRC)/spz_view_pass.hpp $(CSRC)/spz_morton_walk.hpp $(CSRC)/spz_block_ops.hpp $(CSRC)/spz_xf.hpp $(CSRC)/spz_lz77_core.hpp $(CSRC)/spz_huff_core.hpp $(CSRC)/spz_inflate_core.hpp $(INC)/spz_amd.h
 	mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(DEVICE_SRCS) -ldl
 

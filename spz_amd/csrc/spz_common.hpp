@@ -213,6 +213,9 @@ inline int check_packed_stream(const uint8_t *d_stream, size_t size, const spz_a
   return SPZ_AMD_OK;
 }
 
+// The most points, and the most (tile, Gaussian) entries of one view, the rasteriser takes: the radix sort's limit.
+constexpr uint64_t kMaxEntries = 0x7fffffffull;
+
 // A stream of its own for a stage: level +1 = in front of the others when both have work for the chip (the pipeline
 // whose copies the link waits for), -1 = behind them (kernels that fill idle CUs beside it), 0 = the default.
 // SPZ_AMD_STREAM_PRIORITIES=0 makes them all equal (measurements).

@@ -2349,28 +2349,73 @@ bool cleanSpz(const std::string &inputFilename, const std::string &outputFilenam
 
 // ---- render ------------------------------------------------------------------------------------------------------
 namespace {
-bool renderParams(const RenderOptions &o, spz_amd_render_params *p, const char *op = "renderSpz") {
+// What a view is rendered with beside its camera: the option fields that vary between the callers, and how their
+// "bad camera" line ends.
+struct ViewFrame {
+  float nearPlane;
+  CoordinateSystem coord;
+  const std::array<float, 3> *background;  // NULL: black
+  int maxShDegree;
+  const char *alsoChecked;  // what the caller's "bad camera" line names after "values finite" (the texts differ)
+};
+
+// One view as render params, checked; `label` ("view 3: " or "") leads the line of a refused one.
+bool viewParams(const char *who, const char *label, const PruneOptions::View &w, const ViewFrame &f,
+                spz_amd_render_params *p) {
   *p = spz_amd_render_params{};
-  if (o.width < 1 || o.width > 16384 || o.height < 1 || o.height > 16384) {
-    return opRejected(op, SPZ_AMD_ERR_INVALID_ARG, "image size %d x %d is outside 1..16384", o.width, o.height);
+  if (w.width < 1 || w.width > 16384 || w.height < 1 || w.height > 16384) {
+    return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "%simage size %d x %d is outside 1..16384", label, w.width, w.height);
   }
-  for (int k = 0; k < 12; ++k) p->world_to_camera[k] = o.worldToCamera[k];
-  p->fx = o.fx;
-  p->fy = o.fy;
-  p->cx = o.cx;
-  p->cy = o.cy;
-  p->width = static_cast<uint32_t>(o.width);
-  p->height = static_cast<uint32_t>(o.height);
-  p->near_plane = o.nearPlane;
-  for (int k = 0; k < 3; ++k) p->background[k] = o.background[k];
-  p->max_sh_degree = o.maxShDegree;
-  p->coord = static_cast<int32_t>(o.coord);
+  for (int k = 0; k < 12; ++k) p->world_to_camera[k] = w.worldToCamera[k];
+  p->fx = w.fx;
+  p->fy = w.fy;
+  p->cx = w.cx;
+  p->cy = w.cy;
+  p->width = static_cast<uint32_t>(w.width);
+  p->height = static_cast<uint32_t>(w.height);
+  p->near_plane = f.nearPlane;
+  for (int k = 0; k < 3; ++k) p->background[k] = f.background ? (*f.background)[k] : 0.0f;
+  p->max_sh_degree = f.maxShDegree;
+  p->coord = static_cast<int32_t>(f.coord);
   if (spz_amd_render_check_params(p) != SPZ_AMD_OK) {
-    return opRejected(op, SPZ_AMD_ERR_INVALID_ARG,
-                      "bad camera: R must be a rotation (to 1e-4), fx, fy > 0, nearPlane > 0, values finite, "
-                      "maxShDegree 0..3");
+    return opRejected(who, SPZ_AMD_ERR_INVALID_ARG,
+                      "%sbad camera: R must be a rotation (to 1e-4), fx, fy > 0, nearPlane > 0, values finite%s", label,
+                      f.alsoChecked);
   }
   return true;
+}
+
+// The views of prune, compare and refine as render params: 1..maxViews of them, each checked and named by its index.
+bool viewListParams(const char *who, const std::vector<PruneOptions::View> &views, int maxViews, const ViewFrame &f,
+                    std::vector<spz_amd_render_params> *params) {
+  if (views.empty() || views.size() > static_cast<size_t>(maxViews)) {
+    return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "%zu views: give 1..%d", views.size(), maxViews);
+  }
+  params->assign(views.size(), spz_amd_render_params{});
+  for (size_t v = 0; v < views.size(); ++v) {
+    const std::string label = "view " + std::to_string(v) + ": ";
+    if (!viewParams(who, label.c_str(), views[v], f, &(*params)[v])) return false;
+  }
+  return true;
+}
+
+// After a multi-view device call: true when it failed, with the view the device named in the line.
+bool viewsFailed(const char *who, int rc, int32_t bad) {
+  if (rc == SPZ_AMD_ERR_CAPACITY && bad >= 0) return !opRejected(who, rc, "view %d: more than 2^31 - 1 tile entries", bad);
+  if (rc != SPZ_AMD_OK && bad >= 0) logLine("[SPZ ERROR] %s: view %d failed", who, bad);
+  return deviceFailed(rc, who);
+}
+
+bool renderParams(const RenderOptions &o, spz_amd_render_params *p, const char *op) {
+  PruneOptions::View w;
+  w.worldToCamera = o.worldToCamera;
+  w.fx = o.fx;
+  w.fy = o.fy;
+  w.cx = o.cx;
+  w.cy = o.cy;
+  w.width = o.width;
+  w.height = o.height;
+  return viewParams(op, "", w, {o.nearPlane, o.coord, &o.background, o.maxShDegree, ", maxShDegree 0..3"}, p);
 }
 
 void renderTiming(const float *ms, uint64_t entries, const char *op = "renderSpz") {
@@ -2425,77 +2470,78 @@ struct DepthBuffers {
 };
 }  // namespace
 
-bool renderSpz(const uint8_t *data, int32_t size, const RenderOptions &o, std::vector<float> *rgba, int64_t *entries) {
+namespace {
+// The four render entry points: a packed input (`data`) or a cloud (`g`), into the image alone or (wantMaps) into
+// depth maps with an optional image.  `op` names the call in its rejections and timings, `deviceOp` in a device failure.
+bool renderAny(const char *op, const char *deviceOp, const uint8_t *data, int32_t size, const GaussianCloud *g,
+               const RenderOptions &o, DepthMaps *maps, bool wantMaps, std::vector<float> *rgba, int64_t *entries) {
   g_last_status = SPZ_AMD_OK;
-  if (rgba == nullptr) return opRejected("renderSpz", SPZ_AMD_ERR_INVALID_ARG, "no output vector");
+  if (wantMaps && maps == nullptr) return opRejected(op, SPZ_AMD_ERR_INVALID_ARG, "no output maps");
+  if (!wantMaps && rgba == nullptr) return opRejected(op, SPZ_AMD_ERR_INVALID_ARG, "no output vector");
   spz_amd_render_params p;
-  if (!renderParams(o, &p)) return false;
+  if (!renderParams(o, &p, op)) return false;
   DevicePackedGaussians d;
-  if (!loadInput("renderSpz", data, size, &d)) return false;
-  const spz_amd_header hdr = headerOf(d);
+  spz_amd_header hdr = {};
+  spz_amd_cloud_in c = {};
+  size_t n = 0;
+  if (g == nullptr) {
+    if (!loadInput(op, data, size, &d)) return false;
+    hdr = headerOf(d);
+  } else if (!cloudArrays(*g, &c, &n)) {
+    return opRejected(op, SPZ_AMD_ERR_INVALID_ARG, "the cloud's arrays do not match numPoints and shDegree");
+  }
+  const int aa = g && g->antialiased ? 1 : 0, device = g ? deviceIndex() : d.device;
   std::vector<float> img;
-  detail::resizeUninitialized(&img, static_cast<size_t>(o.width) * static_cast<size_t>(o.height) * 4u);
+  std::optional<DepthBuffers> b;
+  if (wantMaps) {
+    b.emplace(o);
+  } else {
+    detail::resizeUninitialized(&img, static_cast<size_t>(o.width) * static_cast<size_t>(o.height) * 4u);
+  }
   uint64_t count = 0;
   float ms[3] = {0.0f, 0.0f, 0.0f};
-  const int rc = spz_amd_render_host(d.stream, d.streamBytes, &hdr, &p, d.device, img.data(), &count, ms);
-  if (deviceFailed(rc, "renderSpz")) return false;
-  renderTiming(ms, count);
-  rgba->swap(img);
+  int rc;
+  if (wantMaps) {
+    rc = g ? spz_amd_render_depth_cloud_host(&c, n, g->shDegree, aa, &p, device, b->img.data(), b->depth.data(),
+                                             b->index.data(), &count, ms)
+           : spz_amd_render_depth_host(d.stream, d.streamBytes, &hdr, &p, device, b->img.data(), b->depth.data(),
+                                       b->index.data(), &count, ms);
+  } else {
+    rc = g ? spz_amd_render_cloud_host(&c, n, g->shDegree, aa, &p, device, img.data(), &count, ms)
+           : spz_amd_render_host(d.stream, d.streamBytes, &hdr, &p, device, img.data(), &count, ms);
+  }
+  if (deviceFailed(rc, deviceOp)) return false;
+  renderTiming(ms, count, op);
+  if (wantMaps) {
+    b->finish(maps, rgba);
+  } else {
+    rgba->swap(img);
+  }
   if (entries) *entries = static_cast<int64_t>(count);
   return true;
+}
+}  // namespace
+
+bool renderSpz(const uint8_t *data, int32_t size, const RenderOptions &o, std::vector<float> *rgba, int64_t *entries) {
+  return renderAny("renderSpz", "renderSpz", data, size, nullptr, o, nullptr, false, rgba, entries);
 }
 
 bool renderSpz(const std::string &filename, const RenderOptions &o, std::vector<float> *rgba, int64_t *entries) {
   g_last_status = SPZ_AMD_OK;
   spz_amd_render_params p;
-  if (!renderParams(o, &p)) return false;
+  if (!renderParams(o, &p, "renderSpz")) return false;
   std::vector<uint8_t> data;
   if (!readInput("renderSpz", filename, &data)) return false;
   return renderSpz(data.data(), static_cast<int32_t>(data.size()), o, rgba, entries);
 }
 
 bool renderCloud(const GaussianCloud &g, const RenderOptions &o, std::vector<float> *rgba, int64_t *entries) {
-  g_last_status = SPZ_AMD_OK;
-  if (rgba == nullptr) return opRejected("renderSpz", SPZ_AMD_ERR_INVALID_ARG, "no output vector");
-  spz_amd_render_params p;
-  if (!renderParams(o, &p)) return false;
-  spz_amd_cloud_in c;
-  size_t n = 0;
-  if (!cloudArrays(g, &c, &n)) {
-    return opRejected("renderSpz", SPZ_AMD_ERR_INVALID_ARG, "the cloud's arrays do not match numPoints and shDegree");
-  }
-  std::vector<float> img;
-  detail::resizeUninitialized(&img, static_cast<size_t>(o.width) * static_cast<size_t>(o.height) * 4u);
-  uint64_t count = 0;
-  float ms[3] = {0.0f, 0.0f, 0.0f};
-  const int rc =
-      spz_amd_render_cloud_host(&c, n, g.shDegree, g.antialiased ? 1 : 0, &p, deviceIndex(), img.data(), &count, ms);
-  if (deviceFailed(rc, "renderCloud")) return false;
-  renderTiming(ms, count);
-  rgba->swap(img);
-  if (entries) *entries = static_cast<int64_t>(count);
-  return true;
+  return renderAny("renderSpz", "renderCloud", nullptr, 0, &g, o, nullptr, false, rgba, entries);
 }
 
 bool renderSpzDepth(const uint8_t *data, int32_t size, const RenderOptions &o, DepthMaps *maps, std::vector<float> *rgba,
                     int64_t *entries) {
-  g_last_status = SPZ_AMD_OK;
-  if (maps == nullptr) return opRejected("renderSpzDepth", SPZ_AMD_ERR_INVALID_ARG, "no output maps");
-  spz_amd_render_params p;
-  if (!renderParams(o, &p, "renderSpzDepth")) return false;
-  DevicePackedGaussians d;
-  if (!loadInput("renderSpzDepth", data, size, &d)) return false;
-  const spz_amd_header hdr = headerOf(d);
-  DepthBuffers b(o);
-  uint64_t count = 0;
-  float ms[3] = {0.0f, 0.0f, 0.0f};
-  const int rc = spz_amd_render_depth_host(d.stream, d.streamBytes, &hdr, &p, d.device, b.img.data(), b.depth.data(),
-                                           b.index.data(), &count, ms);
-  if (deviceFailed(rc, "renderSpzDepth")) return false;
-  renderTiming(ms, count, "renderSpzDepth");
-  b.finish(maps, rgba);
-  if (entries) *entries = static_cast<int64_t>(count);
-  return true;
+  return renderAny("renderSpzDepth", "renderSpzDepth", data, size, nullptr, o, maps, true, rgba, entries);
 }
 
 bool renderSpzDepth(const std::string &filename, const RenderOptions &o, DepthMaps *maps, std::vector<float> *rgba,
@@ -2511,25 +2557,7 @@ bool renderSpzDepth(const std::string &filename, const RenderOptions &o, DepthMa
 
 bool renderCloudDepth(const GaussianCloud &g, const RenderOptions &o, DepthMaps *maps, std::vector<float> *rgba,
                       int64_t *entries) {
-  g_last_status = SPZ_AMD_OK;
-  if (maps == nullptr) return opRejected("renderSpzDepth", SPZ_AMD_ERR_INVALID_ARG, "no output maps");
-  spz_amd_render_params p;
-  if (!renderParams(o, &p, "renderSpzDepth")) return false;
-  spz_amd_cloud_in c;
-  size_t n = 0;
-  if (!cloudArrays(g, &c, &n)) {
-    return opRejected("renderSpzDepth", SPZ_AMD_ERR_INVALID_ARG, "the cloud's arrays do not match numPoints and shDegree");
-  }
-  DepthBuffers b(o);
-  uint64_t count = 0;
-  float ms[3] = {0.0f, 0.0f, 0.0f};
-  const int rc = spz_amd_render_depth_cloud_host(&c, n, g.shDegree, g.antialiased ? 1 : 0, &p, deviceIndex(),
-                                                 b.img.data(), b.depth.data(), b.index.data(), &count, ms);
-  if (deviceFailed(rc, "renderSpzDepth")) return false;
-  renderTiming(ms, count, "renderSpzDepth");
-  b.finish(maps, rgba);
-  if (entries) *entries = static_cast<int64_t>(count);
-  return true;
+  return renderAny("renderSpzDepth", "renderSpzDepth", nullptr, 0, &g, o, maps, true, rgba, entries);
 }
 
 std::array<float, 12> lookAt(const std::array<float, 3> &eye, const std::array<float, 3> &target,
@@ -2586,33 +2614,8 @@ bool pruneOptionsOk(const PruneOptions &o, std::vector<spz_amd_render_params> *p
   }
   if (o.minScore && !std::isfinite(*o.minScore)) return opRejected(who, invalid, "minScore must be finite");
   if (o.score != PruneOptions::Sum && o.score != PruneOptions::Max) return opRejected(who, invalid, "score must be Sum or Max");
-  if (o.views.empty() || o.views.size() > SPZ_AMD_PRUNE_MAX_VIEWS) {
-    return opRejected(who, invalid, "%zu views: give 1..%d", o.views.size(), SPZ_AMD_PRUNE_MAX_VIEWS);
-  }
-  params->assign(o.views.size(), spz_amd_render_params{});
-  for (size_t v = 0; v < o.views.size(); ++v) {
-    const PruneOptions::View &w = o.views[v];
-    spz_amd_render_params &p = (*params)[v];
-    if (w.width < 1 || w.width > 16384 || w.height < 1 || w.height > 16384) {
-      return opRejected(who, invalid, "view %zu: image size %d x %d is outside 1..16384", v, w.width, w.height);
-    }
-    for (int k = 0; k < 12; ++k) p.world_to_camera[k] = w.worldToCamera[k];
-    p.fx = w.fx;
-    p.fy = w.fy;
-    p.cx = w.cx;
-    p.cy = w.cy;
-    p.width = static_cast<uint32_t>(w.width);
-    p.height = static_cast<uint32_t>(w.height);
-    p.near_plane = o.nearPlane;
-    p.max_sh_degree = 0;  // colours do not change a weight
-    p.coord = static_cast<int32_t>(o.coord);
-    if (spz_amd_render_check_params(&p) != SPZ_AMD_OK) {
-      return opRejected(who, invalid,
-                        "view %zu: bad camera: R must be a rotation (to 1e-4), fx, fy > 0, nearPlane > 0, values "
-                        "finite, coord valid", v);
-    }
-  }
-  return true;
+  // max SH degree 0: colours do not change a weight
+  return viewListParams(who, o.views, SPZ_AMD_PRUNE_MAX_VIEWS, {o.nearPlane, o.coord, nullptr, 0, ", coord valid"}, params);
 }
 }  // namespace
 
@@ -2653,9 +2656,7 @@ bool pruneSpz(const uint8_t *data, int32_t size, const PruneOptions &o, std::vec
                                     static_cast<int>(o.score), rule, value, d.device, &r.ctx, &bytes, &count,
                                     keepMask ? mask.data() : nullptr, weightSum ? sums.data() : nullptr,
                                     weightMax ? maxima.data() : nullptr, ms, &bad);
-  if (rc == SPZ_AMD_ERR_CAPACITY && bad >= 0) return opRejected(who, rc, "view %d: more than 2^31 - 1 tile entries", bad);
-  if (rc != SPZ_AMD_OK && bad >= 0) logLine("[SPZ ERROR] pruneSpz: view %d failed", bad);
-  if (deviceFailed(rc, who)) return false;
+  if (viewsFailed(who, rc, bad)) return false;
   laps.stage("score", ms[0], (" (" + std::to_string(params.size()) + " views)").c_str());
   laps.stage("rank", ms[1]);
   laps.stage("subset", ms[2]);
@@ -2804,36 +2805,8 @@ std::vector<PruneOptions::View> loadViewsFile(const std::string &filename) {
 namespace {
 // The views as render params with the options' frame, near plane, background and degree.
 bool compareOptionsOk(const CompareOptions &o, std::vector<spz_amd_render_params> *params) {
-  const char *who = "compareSpz";
-  const int invalid = SPZ_AMD_ERR_INVALID_ARG;
-  if (o.views.empty() || o.views.size() > SPZ_AMD_COMPARE_MAX_VIEWS) {
-    return opRejected(who, invalid, "%zu views: give 1..%d", o.views.size(), SPZ_AMD_COMPARE_MAX_VIEWS);
-  }
-  params->assign(o.views.size(), spz_amd_render_params{});
-  for (size_t v = 0; v < o.views.size(); ++v) {
-    const PruneOptions::View &w = o.views[v];
-    spz_amd_render_params &p = (*params)[v];
-    if (w.width < 1 || w.width > 16384 || w.height < 1 || w.height > 16384) {
-      return opRejected(who, invalid, "view %zu: image size %d x %d is outside 1..16384", v, w.width, w.height);
-    }
-    for (int k = 0; k < 12; ++k) p.world_to_camera[k] = w.worldToCamera[k];
-    p.fx = w.fx;
-    p.fy = w.fy;
-    p.cx = w.cx;
-    p.cy = w.cy;
-    p.width = static_cast<uint32_t>(w.width);
-    p.height = static_cast<uint32_t>(w.height);
-    p.near_plane = o.nearPlane;
-    for (int k = 0; k < 3; ++k) p.background[k] = o.background[k];
-    p.max_sh_degree = o.maxShDegree;
-    p.coord = static_cast<int32_t>(o.coord);
-    if (spz_amd_render_check_params(&p) != SPZ_AMD_OK) {
-      return opRejected(who, invalid,
-                        "view %zu: bad camera: R must be a rotation (to 1e-4), fx, fy > 0, nearPlane > 0, values "
-                        "finite, maxShDegree 0..3, coord valid", v);
-    }
-  }
-  return true;
+  return viewListParams("compareSpz", o.views, SPZ_AMD_COMPARE_MAX_VIEWS,
+                        {o.nearPlane, o.coord, &o.background, o.maxShDegree, ", maxShDegree 0..3, coord valid"}, params);
 }
 
 ImageMetrics toMetrics(const spz_amd_image_metrics &m) {
@@ -2876,9 +2849,7 @@ bool compareSpz(const uint8_t *dataA, int32_t sizeA, const uint8_t *dataB, int32
   const int rc = spz_amd_compare_host(da.stream, da.streamBytes, &ha, db.stream, db.streamBytes, &hb, params.data(),
                                       static_cast<int>(nv), da.device, m.data(), ssimMaps ? maps.data() : nullptr,
                                       entries.data(), ms, &bad);
-  if (rc == SPZ_AMD_ERR_CAPACITY && bad >= 0) return opRejected(who, rc, "view %d: more than 2^31 - 1 tile entries", bad);
-  if (rc != SPZ_AMD_OK && bad >= 0) logLine("[SPZ ERROR] compareSpz: view %d failed", bad);
-  if (deviceFailed(rc, who)) return false;
+  if (viewsFailed(who, rc, bad)) return false;
   uint64_t ea = 0, eb = 0;
   for (size_t v = 0; v < nv; ++v) {
     ea += entries[2 * v];
@@ -2943,34 +2914,8 @@ bool refineOptionsOk(const RefineOptions &o, std::vector<spz_amd_render_params> 
   if (spz_amd_refine_check(c) != SPZ_AMD_OK) {
     return opRejected(who, invalid, "learning rates must be finite and >= 0, beta1 and beta2 in [0, 1), eps finite and >= 0");
   }
-  if (o.views.empty() || o.views.size() > SPZ_AMD_REFINE_MAX_VIEWS) {
-    return opRejected(who, invalid, "%zu views: give 1..%d", o.views.size(), SPZ_AMD_REFINE_MAX_VIEWS);
-  }
-  params->assign(o.views.size(), spz_amd_render_params{});
-  for (size_t v = 0; v < o.views.size(); ++v) {
-    const PruneOptions::View &w = o.views[v];
-    spz_amd_render_params &p = (*params)[v];
-    if (w.width < 1 || w.width > 16384 || w.height < 1 || w.height > 16384) {
-      return opRejected(who, invalid, "view %zu: image size %d x %d is outside 1..16384", v, w.width, w.height);
-    }
-    for (int k = 0; k < 12; ++k) p.world_to_camera[k] = w.worldToCamera[k];
-    p.fx = w.fx;
-    p.fy = w.fy;
-    p.cx = w.cx;
-    p.cy = w.cy;
-    p.width = static_cast<uint32_t>(w.width);
-    p.height = static_cast<uint32_t>(w.height);
-    p.near_plane = o.nearPlane;
-    for (int k = 0; k < 3; ++k) p.background[k] = o.background[k];
-    p.max_sh_degree = o.maxShDegree;
-    p.coord = static_cast<int32_t>(o.coord);
-    if (spz_amd_render_check_params(&p) != SPZ_AMD_OK) {
-      return opRejected(who, invalid,
-                        "view %zu: bad camera: R must be a rotation (to 1e-4), fx, fy > 0, nearPlane > 0, values "
-                        "finite, maxShDegree 0..3, coord valid", v);
-    }
-  }
-  return true;
+  return viewListParams(who, o.views, SPZ_AMD_REFINE_MAX_VIEWS,
+                        {o.nearPlane, o.coord, &o.background, o.maxShDegree, ", maxShDegree 0..3, coord valid"}, params);
 }
 }  // namespace
 
@@ -3009,13 +2954,11 @@ bool refineSpz(const uint8_t *data, int32_t size, const uint8_t *target, int32_t
   const int rc = spz_amd_refine_open(da.stream, da.streamBytes, &ha, db.stream, db.streamBytes, &hb, params.data(),
                                      static_cast<int>(nv), &c, da.device, &r.ctx, &bytes, history.data(), before.data(),
                                      after.data(), &skipped, ms, &bad);
-  if (rc == SPZ_AMD_ERR_CAPACITY && bad >= 0) return opRejected(who, rc, "view %d: more than 2^31 - 1 tile entries", bad);
   if (rc == SPZ_AMD_ERR_UNSUPPORTED) {
     return opRejected(who, rc, "the encoder writes versions 2 and 3 and positions at 12 fractional bits: the input has "
                       "version %u and %u", ha.version, static_cast<unsigned>(ha.fractional_bits));
   }
-  if (rc != SPZ_AMD_OK && bad >= 0) logLine("[SPZ ERROR] refineSpz: view %d failed", bad);
-  if (deviceFailed(rc, who)) return false;
+  if (viewsFailed(who, rc, bad)) return false;
   laps.stage("targets", ms[0], (" (" + std::to_string(nv) + " views)").c_str());
   laps.stage("iterations", ms[1], (" (" + std::to_string(o.iterations) + ")").c_str());
   laps.stage("after", ms[2]);

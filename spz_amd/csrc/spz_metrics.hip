@@ -14,8 +14,8 @@
 //   spz_loss_reduce_kernel         the slab in the metrics' order, then L = (1 - lambda) l1 + lambda (1 - ssim), l1, ssim.
 //   spz_loss_grad_kernel           one workgroup per 32x16 tile: each plane's tile and halo into LDS (zeros outside the
 //                                  image), the same two 11-tap passes, then dL/da per pixel through the clamp's mask.
-//   compare                        per view: render A, render B (spz_amd_render_prepare_packed_device + _finish_device
-//                                  into grow-only buffers), then the two kernels above.
+//   compare                        per view: render A, render B (render_view of spz_view_pass.hpp into grow-only
+//                                  buffers), then the two kernels above.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -25,6 +25,7 @@
 
 #include "spz_amd.h"
 #include "spz_common.hpp"
+#include "spz_view_pass.hpp"
 
 namespace spz_amd_detail {
 namespace {
@@ -37,7 +38,6 @@ constexpr int kMtInH = kMtH + 2 * kMtR;  // 26
 constexpr uint32_t kMtThreads = 256;
 constexpr uint32_t kMtRedThreads = 256;
 constexpr uint32_t kMtMaxSide = 16384;
-constexpr uint64_t kMtMaxEntries = 0x7fffffffull;  // the render's sort limit
 constexpr double kC1 = 0.01 * 0.01;
 constexpr double kC2 = 0.03 * 0.03;
 
@@ -437,18 +437,6 @@ int loss_enqueue(const float *d_a, int channels_a, const float *d_b, int channel
 
 bool aligned_to(const void *p, uintptr_t k) { return (reinterpret_cast<uintptr_t>(p) & (k - 1)) == 0; }
 
-// A packed input of compare: the header and size checks of the render's prepare step, before anything is launched.
-int compare_input_ok(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr) {
-  if (d_stream == nullptr || hdr == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
-  if (hdr->version < 1 || hdr->version > 3) return SPZ_AMD_ERR_VERSION;
-  if (hdr->sh_degree > 3) return SPZ_AMD_ERR_SH_DEGREE;
-  if (hdr->num_points > kMtMaxEntries) return SPZ_AMD_ERR_TOO_MANY_POINTS;
-  spz_amd_layout lay;
-  const int rc = spz_amd_stream_layout(hdr->num_points, hdr->sh_degree, (int)hdr->version, &lay);
-  if (rc != SPZ_AMD_OK) return rc;
-  return size < lay.total_bytes ? SPZ_AMD_ERR_SHORT_STREAM : SPZ_AMD_OK;
-}
-
 // The device blocks of one compare call, grow-only, freed (after the stream) when it returns.
 struct CompareBlocks {
   hipStream_t st = nullptr;
@@ -479,48 +467,6 @@ int grow(T **p, uint64_t *cap, uint64_t need, uint64_t elem) {
   SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(p), need * elem));
   *cap = need;
   return SPZ_AMD_OK;
-}
-
-// One render of view p into d_image, the workspace grown as it needs (its prepare part copied to the front of a new
-// one).  *entries: the total.
-int compare_render(CompareBlocks *k, const uint8_t *d_stream, size_t size, const spz_amd_header *hdr,
-                   const spz_amd_render_params *p, float *d_image, uint64_t *entries) {
-  const uint64_t n = hdr->num_points;
-  const uint64_t ws0 = spz_amd_render_workspace_bytes(n, 0);
-  auto *d_total = reinterpret_cast<uint64_t *>(k->small);
-  auto *d_status = reinterpret_cast<uint32_t *>(k->small + 8);
-  if (k->ws_cap < ws0) {
-    SPZ_HIP_TRY(hipStreamSynchronize(k->st));  // the other file's blend may still read it
-    if (k->ws) SPZ_HIP_TRY(hipFree(k->ws));
-    k->ws = nullptr;
-    k->ws_cap = 0;
-    SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&k->ws), ws0));
-    k->ws_cap = ws0;
-  }
-  int rc = spz_amd_render_prepare_packed_device(d_stream, size, hdr, p, d_total, nullptr, k->ws, k->st);
-  if (rc != SPZ_AMD_OK) return rc;
-  uint64_t total = 0;
-  SPZ_HIP_TRY(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, k->st));
-  SPZ_HIP_TRY(hipStreamSynchronize(k->st));
-  *entries = total;
-  if (total > kMtMaxEntries) return SPZ_AMD_ERR_CAPACITY;
-  const uint64_t need = spz_amd_render_workspace_bytes(n, total);
-  if (need > k->ws_cap) {
-    uint8_t *bigger = nullptr;
-    SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&bigger), need));
-    const hipError_t e =
-        hipMemcpyAsync(align_ws(bigger), align_ws(k->ws), ws0 - 256u, hipMemcpyDeviceToDevice, k->st);
-    if (e == hipSuccess) (void)hipStreamSynchronize(k->st);
-    if (e != hipSuccess) {
-      (void)hipFree(bigger);
-      g_last_hip_error = (int)e;
-      return SPZ_AMD_ERR_HIP;
-    }
-    SPZ_HIP_TRY(hipFree(k->ws));
-    k->ws = bigger;
-    k->ws_cap = need;
-  }
-  return spz_amd_render_finish_device(n, p, total, d_image, d_status, k->ws, k->st);
 }
 
 }  // namespace
@@ -621,16 +567,11 @@ int spz_amd_compare_host(const uint8_t *d_stream_a, size_t size_a, const spz_amd
                          int32_t *h_bad_view) {
   if (h_bad_view) *h_bad_view = -1;
   if (h_metrics == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
-  if (views == nullptr || num_views < 1 || num_views > SPZ_AMD_COMPARE_MAX_VIEWS) return SPZ_AMD_ERR_INVALID_ARG;
-  for (int v = 0; v < num_views; ++v) {
-    if (spz_amd_render_check_params(&views[v]) != SPZ_AMD_OK || views[v].coord != views[0].coord) {
-      if (h_bad_view) *h_bad_view = v;
-      return SPZ_AMD_ERR_INVALID_ARG;
-    }
-  }
-  int rc = compare_input_ok(d_stream_a, size_a, hdr_a);
+  int rc = check_views(views, num_views, SPZ_AMD_COMPARE_MAX_VIEWS, h_bad_view);
   if (rc != SPZ_AMD_OK) return rc;
-  rc = compare_input_ok(d_stream_b, size_b, hdr_b);
+  rc = check_render_input(d_stream_a, size_a, hdr_a);
+  if (rc != SPZ_AMD_OK) return rc;
+  rc = check_render_input(d_stream_b, size_b, hdr_b);
   if (rc != SPZ_AMD_OK) return rc;
   DeviceGuard guard;
   rc = guard.enter(device);
@@ -638,7 +579,11 @@ int spz_amd_compare_host(const uint8_t *d_stream_a, size_t size_a, const spz_amd
   CompareBlocks k;
   SPZ_HIP_TRY(hipStreamCreateWithFlags(&k.st, hipStreamNonBlocking));
   SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&k.small), 256u + (uint64_t)num_views * sizeof(spz_amd_image_metrics)));
+  auto *d_total = reinterpret_cast<uint64_t *>(k.small);
+  auto *d_status = reinterpret_cast<uint32_t *>(k.small + 8);
   auto *d_metrics = reinterpret_cast<spz_amd_image_metrics *>(k.small + 256u);
+  const RenderSource src_a = packed_render_source(d_stream_a, size_a, hdr_a);
+  const RenderSource src_b = packed_render_source(d_stream_b, size_b, hdr_b);
   double render_ms = 0.0, metrics_ms = 0.0;
   uint64_t map_off = 0;
   for (int v = 0; v < num_views; ++v) {
@@ -659,9 +604,9 @@ int spz_amd_compare_host(const uint8_t *d_stream_a, size_t size_a, const spz_amd
     float *img_a = k.img, *img_b = k.img + 4u * px;
     const auto t0 = std::chrono::steady_clock::now();
     uint64_t ea = 0, eb = 0;
-    rc = compare_render(&k, d_stream_a, size_a, hdr_a, &p, img_a, &ea);
+    rc = render_view(&k.ws, &k.ws_cap, src_a, &p, d_total, d_status, img_a, k.st, &ea);
     if (rc != SPZ_AMD_OK) return fail(rc);
-    rc = compare_render(&k, d_stream_b, size_b, hdr_b, &p, img_b, &eb);
+    rc = render_view(&k.ws, &k.ws_cap, src_b, &p, d_total, d_status, img_b, k.st, &eb);
     if (rc != SPZ_AMD_OK) return fail(rc);
     SPZ_HIP_TRY(hipStreamSynchronize(k.st));
     const auto t1 = std::chrono::steady_clock::now();

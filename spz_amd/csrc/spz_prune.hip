@@ -2,10 +2,9 @@
 // every Gaussian's blend weight summed (and maximised) over a set of views, the least significant dropped, the rest
 // written as the filter's subset.
 //
-//   per view                       spz_amd_render_prepare_packed_device, the total read back, the workspace grown
-//                                  (grow-only, the prepare part copied to the front of the new one), then
-//                                  spz_amd_render_score_device (spz_render.hip's spz_render_score_kernel) adding into
-//                                  the u64 sums and f32 maxima.
+//   per view                       prepare_view (spz_view_pass.hpp: prepare, the total read back, the workspace
+//                                  grown), then spz_amd_render_score_device (spz_render.hip's spz_render_score_kernel)
+//                                  adding into the u64 sums and f32 maxima.
 //   spz_prune_key_kernel           keep_count / keep_fraction: the complement of the score as radix keys (u64 sum: two
 //                                  planes, 8 digits; the f32 max's bits: one plane, 4 digits), so the stable ascending
 //                                  sort (spz_sort_internal.hpp) ranks by score descending, then input index.
@@ -23,12 +22,12 @@
 #include "spz_amd.h"
 #include "spz_common.hpp"
 #include "spz_sort_internal.hpp"
+#include "spz_view_pass.hpp"
 
 namespace spz_amd_detail {
 namespace {
 
 constexpr uint32_t kPrBlock = 256;
-constexpr uint64_t kPrMaxEntries = 0x7fffffffull;  // the radix sort's limit, as in the render
 
 }  // namespace
 
@@ -90,22 +89,12 @@ int spz_amd_prune_open(const uint8_t *d_stream, size_t size, const spz_amd_heade
   if (ctx == nullptr || h_out_bytes == nullptr || d_stream == nullptr || hdr == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
   *ctx = nullptr;
   *h_out_bytes = 0;
-  if (views == nullptr || num_views < 1 || num_views > SPZ_AMD_PRUNE_MAX_VIEWS) return SPZ_AMD_ERR_INVALID_ARG;
-  for (int v = 0; v < num_views; ++v) {
-    if (spz_amd_render_check_params(&views[v]) != SPZ_AMD_OK || views[v].coord != views[0].coord) {
-      if (h_bad_view) *h_bad_view = v;
-      return SPZ_AMD_ERR_INVALID_ARG;
-    }
-  }
-  if (score_kind != SPZ_AMD_PRUNE_SCORE_SUM && score_kind != SPZ_AMD_PRUNE_SCORE_MAX) return SPZ_AMD_ERR_INVALID_ARG;
-  if (hdr->version < 1 || hdr->version > 3) return SPZ_AMD_ERR_VERSION;
-  if (hdr->sh_degree > 3) return SPZ_AMD_ERR_SH_DEGREE;
-  const uint64_t n = hdr->num_points;
-  if (n > kPrMaxEntries) return SPZ_AMD_ERR_TOO_MANY_POINTS;
-  spz_amd_layout lay;
-  int rc = spz_amd_stream_layout(n, hdr->sh_degree, (int)hdr->version, &lay);
+  int rc = check_views(views, num_views, SPZ_AMD_PRUNE_MAX_VIEWS, h_bad_view);
   if (rc != SPZ_AMD_OK) return rc;
-  if (size < lay.total_bytes) return SPZ_AMD_ERR_SHORT_STREAM;
+  if (score_kind != SPZ_AMD_PRUNE_SCORE_SUM && score_kind != SPZ_AMD_PRUNE_SCORE_MAX) return SPZ_AMD_ERR_INVALID_ARG;
+  rc = check_render_input(d_stream, size, hdr);
+  if (rc != SPZ_AMD_OK) return rc;
+  const uint64_t n = hdr->num_points;
   uint64_t keep = 0;
   if (rule == SPZ_AMD_PRUNE_MIN_SCORE) {
     if (!std::isfinite(rule_value)) return SPZ_AMD_ERR_INVALID_ARG;
@@ -139,44 +128,13 @@ int spz_amd_prune_open(const uint8_t *d_stream, size_t size, const spz_amd_heade
     SPZ_HIP_TRY(hipMemsetAsync(d_max, 0, n * 4u, c->st));
   }
   // the views: prepare, the total, the workspace, the score
-  const uint64_t prefix = spz_amd_render_workspace_bytes(n, 0) - 256u;
-  uint64_t cap = 0;
+  const RenderSource src = packed_render_source(d_stream, size, hdr);
+  uint64_t cap = 0, total = 0;
   for (int v = 0; v < num_views; ++v) {
-    const spz_amd_render_params &p = views[v];
-    if (cap < prefix + 256u) {
-      cap = prefix + 256u;
-      SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->scratch), cap));
+    rc = prepare_view(&c->scratch, &cap, src, &views[v], d_total, c->st, &total);
+    if (rc == SPZ_AMD_OK) {
+      rc = spz_amd_render_score_device(n, &views[v], total, nullptr, d_sum, d_max, d_status, c->scratch, c->st);
     }
-    rc = spz_amd_render_prepare_packed_device(d_stream, size, hdr, &p, d_total, nullptr, c->scratch, c->st);
-    if (rc != SPZ_AMD_OK) {
-      if (h_bad_view) *h_bad_view = v;
-      return rc;
-    }
-    uint64_t total = 0;
-    SPZ_HIP_TRY(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, c->st));
-    SPZ_HIP_TRY(hipStreamSynchronize(c->st));
-    if (total > kPrMaxEntries) {
-      if (h_bad_view) *h_bad_view = v;
-      return SPZ_AMD_ERR_CAPACITY;
-    }
-    const uint64_t need = spz_amd_render_workspace_bytes(n, total);
-    if (need > cap) {
-      uint8_t *bigger = nullptr;
-      SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&bigger), need));
-      if (prefix) {
-        const hipError_t e = hipMemcpyAsync(align_ws(bigger), align_ws(c->scratch), prefix, hipMemcpyDeviceToDevice, c->st);
-        if (e == hipSuccess) (void)hipStreamSynchronize(c->st);
-        if (e != hipSuccess) {
-          (void)hipFree(bigger);
-          g_last_hip_error = (int)e;
-          return SPZ_AMD_ERR_HIP;
-        }
-      }
-      SPZ_HIP_TRY(hipFree(c->scratch));
-      c->scratch = bigger;
-      cap = need;
-    }
-    rc = spz_amd_render_score_device(n, &p, total, nullptr, d_sum, d_max, d_status, c->scratch, c->st);
     if (rc != SPZ_AMD_OK) {
       if (h_bad_view) *h_bad_view = v;
       return rc;

@@ -9,9 +9,10 @@
 //                                  rounding per operation.  Non-finite p or g: the element is left alone and counted
 //                                  (one vector integer atomic per workgroup that has any).
 //   refine                         decode A; per view the target (B rendered) and the "before" metrics; per iteration
-//                                  prepare, the total read back, the workspace grown, finish, spz_amd_image_loss_device,
-//                                  spz_amd_render_backward_device, the Adam step; then the trained sections encoded over
-//                                  a copy of A's bytes and the "after" metrics of that stream.
+//                                  render_view (spz_view_pass.hpp), spz_amd_image_loss_device,
+//                                  spz_amd_render_backward_device on the same workspace and total, the Adam step; then
+//                                  the trained sections encoded over a copy of A's bytes and the "after" metrics of
+//                                  that stream.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -22,12 +23,12 @@
 
 #include "spz_amd.h"
 #include "spz_common.hpp"
+#include "spz_view_pass.hpp"
 
 namespace spz_amd_detail {
 namespace {
 
 constexpr uint32_t kAdBlock = 256;
-constexpr uint64_t kRfMaxEntries = 0x7fffffffull;  // the render's sort limit
 
 // One trained array of the launch: n4 16-byte units from element `head`, then the elements after them; the array's
 // workgroups begin at `first_block`.
@@ -182,7 +183,7 @@ int adam_check_args(const spz_amd_cloud_grads *d_params, const spz_amd_cloud_gra
   }
   if (sh_degree < 0 || sh_degree > 3) return SPZ_AMD_ERR_SH_DEGREE;
   if (train_mask == 0u || train_mask > SPZ_AMD_TRAIN_ALL || !aligned4(d_skipped)) return SPZ_AMD_ERR_INVALID_ARG;
-  if (num_points > kRfMaxEntries) return SPZ_AMD_ERR_TOO_MANY_POINTS;
+  if (num_points > kMaxEntries) return SPZ_AMD_ERR_TOO_MANY_POINTS;
   int rc = adam_check_scalars(sc);
   if (rc != SPZ_AMD_OK) return rc;
   uint64_t count[6];
@@ -206,59 +207,6 @@ struct CloudSet {
 spz_amd_cloud_grads cloud_at(uint8_t *base, const uint64_t off[6], const uint64_t count[6]) {
   auto f = [&](int k) { return count[k] ? reinterpret_cast<float *>(base + off[k]) : nullptr; };
   return spz_amd_cloud_grads{f(0), f(1), f(2), f(3), f(4), f(5)};
-}
-
-// One view of a packed stream or of the float cloud into d_image, the render workspace (r->scratch) grown as the
-// prune loop grows it.  *cap: its size.  A total above the sort's limit: SPZ_AMD_ERR_CAPACITY.
-struct RenderSource {
-  const uint8_t *d_stream = nullptr;  // packed
-  size_t size = 0;
-  const spz_amd_header *hdr = nullptr;
-  const spz_amd_cloud_in *cloud = nullptr;  // float
-  uint64_t n = 0;
-  int sh_degree = 0, antialiased = 0;
-};
-
-int refine_render(PackedResult *r, uint64_t *cap, const RenderSource &src, const spz_amd_render_params *p,
-                  uint64_t *d_total, uint32_t *d_status, float *d_image, uint64_t *h_total) {
-  const uint64_t n = src.n;
-  const uint64_t prefix = spz_amd_render_workspace_bytes(n, 0) - 256u;
-  if (*cap < prefix + 256u) {
-    SPZ_HIP_TRY(hipStreamSynchronize(r->st));  // an earlier view's blend may still read it
-    if (r->scratch) SPZ_HIP_TRY(hipFree(r->scratch));
-    r->scratch = nullptr;
-    *cap = 0;
-    SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&r->scratch), prefix + 256u));
-    *cap = prefix + 256u;
-  }
-  int rc = src.cloud ? spz_amd_render_prepare_cloud_device(src.cloud, n, src.sh_degree, src.antialiased, p, d_total,
-                                                            nullptr, r->scratch, r->st)
-                     : spz_amd_render_prepare_packed_device(src.d_stream, src.size, src.hdr, p, d_total, nullptr,
-                                                            r->scratch, r->st);
-  if (rc != SPZ_AMD_OK) return rc;
-  uint64_t total = 0;
-  SPZ_HIP_TRY(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, r->st));
-  SPZ_HIP_TRY(hipStreamSynchronize(r->st));
-  *h_total = total;
-  if (total > kRfMaxEntries) return SPZ_AMD_ERR_CAPACITY;
-  const uint64_t need = spz_amd_render_workspace_bytes(n, total);
-  if (need > *cap) {
-    uint8_t *bigger = nullptr;
-    SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&bigger), need));
-    if (prefix) {
-      const hipError_t e = hipMemcpyAsync(align_ws(bigger), align_ws(r->scratch), prefix, hipMemcpyDeviceToDevice, r->st);
-      if (e == hipSuccess) (void)hipStreamSynchronize(r->st);
-      if (e != hipSuccess) {
-        (void)hipFree(bigger);
-        g_last_hip_error = (int)e;
-        return SPZ_AMD_ERR_HIP;
-      }
-    }
-    SPZ_HIP_TRY(hipFree(r->scratch));
-    r->scratch = bigger;
-    *cap = need;
-  }
-  return spz_amd_render_finish_device(n, p, total, d_image, d_status, r->scratch, r->st);
 }
 
 }  // namespace
@@ -337,22 +285,17 @@ int spz_amd_refine_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_
   if (ctx == nullptr || h_out_bytes == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
   *ctx = nullptr;
   *h_out_bytes = 0;
-  if (views == nullptr || num_views < 1 || num_views > SPZ_AMD_REFINE_MAX_VIEWS) return SPZ_AMD_ERR_INVALID_ARG;
   int rc = spz_amd_refine_check(options);
   if (rc != SPZ_AMD_OK) return rc;
   if (options->iterations > 0 && h_history == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
-  for (int v = 0; v < num_views; ++v) {
-    if (spz_amd_render_check_params(&views[v]) != SPZ_AMD_OK || views[v].coord != views[0].coord) {
-      if (h_bad_view) *h_bad_view = v;
-      return SPZ_AMD_ERR_INVALID_ARG;
-    }
-  }
+  rc = check_views(views, num_views, SPZ_AMD_REFINE_MAX_VIEWS, h_bad_view);
+  if (rc != SPZ_AMD_OK) return rc;
   spz_amd_layout lay_a, lay_b;
   rc = check_packed_stream(d_stream_a, size_a, hdr_a, &lay_a);
   if (rc != SPZ_AMD_OK) return rc;
   rc = check_packed_stream(d_stream_b, size_b, hdr_b, &lay_b);
   if (rc != SPZ_AMD_OK) return rc;
-  if (hdr_a->num_points > kRfMaxEntries || hdr_b->num_points > kRfMaxEntries) return SPZ_AMD_ERR_TOO_MANY_POINTS;
+  if (hdr_a->num_points > kMaxEntries || hdr_b->num_points > kMaxEntries) return SPZ_AMD_ERR_TOO_MANY_POINTS;
   const uint64_t n = hdr_a->num_points;
   const int deg = hdr_a->sh_degree, aa = hdr_a->flags & 1, coord = views[0].coord;
   const int iters = options->iterations;
@@ -422,20 +365,16 @@ int spz_amd_refine_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_
 
   // targets and the "before" metrics
   uint64_t cap = 0, total = 0;
-  RenderSource src_a, src_b;
-  src_a.d_stream = d_stream_a;
-  src_a.size = size_a;
-  src_a.hdr = hdr_a;
-  src_a.n = n;
-  src_b.d_stream = d_stream_b;
-  src_b.size = size_b;
-  src_b.hdr = hdr_b;
-  src_b.n = hdr_b->num_points;
+  const RenderSource src_a = packed_render_source(d_stream_a, size_a, hdr_a);
+  const RenderSource src_b = packed_render_source(d_stream_b, size_b, hdr_b);
+  auto render = [&](const RenderSource &src, const spz_amd_render_params *p, float *d_out) {
+    return render_view(&c->scratch, &cap, src, p, d_total, d_status, d_out, c->st, &total);
+  };
   for (int v = 0; v < num_views; ++v) {
     const spz_amd_render_params &p = views[v];
-    rc = refine_render(c.get(), &cap, src_b, &p, d_total, d_status, target(v), &total);
+    rc = render(src_b, &p, target(v));
     if (rc != SPZ_AMD_OK) return fail(v, rc);
-    rc = refine_render(c.get(), &cap, src_a, &p, d_total, d_status, d_image, &total);
+    rc = render(src_a, &p, d_image);
     if (rc != SPZ_AMD_OK) return fail(v, rc);
     rc = spz_amd_image_metrics_device(d_image, 4, target(v), 4, (int)p.width, (int)p.height, d_metrics + v, nullptr,
                                       raw + o_mws, c->st);
@@ -459,7 +398,7 @@ int spz_amd_refine_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_
     for (int i = 0; i < iters; ++i) {
       const int v = i % num_views;
       const spz_amd_render_params &p = views[v];
-      rc = refine_render(c.get(), &cap, src_f, &p, d_total, d_status, d_image, &total);
+      rc = render(src_f, &p, d_image);
       if (rc != SPZ_AMD_OK) return fail(v, rc);
       rc = spz_amd_image_loss_device(d_image, 4, target(v), 4, (int)p.width, (int)p.height, options->lambda_dssim,
                                      d_loss + 3 * (size_t)i, d_grad, raw + o_lws, c->st);
@@ -496,7 +435,7 @@ int spz_amd_refine_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_
   for (int v = 0; v < num_views; ++v) {
     const spz_amd_render_params &p = views[v];
     if (iters == 0) break;
-    rc = refine_render(c.get(), &cap, src_o, &p, d_total, d_status, d_image, &total);
+    rc = render(src_o, &p, d_image);
     if (rc != SPZ_AMD_OK) return fail(v, rc);
     rc = spz_amd_image_metrics_device(d_image, 4, target(v), 4, (int)p.width, (int)p.height, d_metrics + num_views + v,
                                       nullptr, raw + o_mws, c->st);

@@ -25,7 +25,6 @@ constexpr uint32_t kPreBlock = 256;
 constexpr uint32_t kScanBlock = 256;
 constexpr uint32_t kScanPer = 4;
 constexpr uint32_t kScanItems = kScanBlock * kScanPer;  // depth-ordered Gaussians per run of the count scan
-constexpr uint64_t kMaxEntries = 0x7fffffffull;         // the radix sort's limit
 
 // The camera, in f64 (every value is the f32 argument widened, or computed from them on the host).
 struct RenderCam {

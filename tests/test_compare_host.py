@@ -126,11 +126,11 @@ def test_c_abi_compare_checks_the_views_first():
     buf = (C.c_uint8 * 4096)()
     good = abi.render_params(RR.look_at([0, 0, -5], [0, 0, 0], [0, 1, 0]), 50, 50, 32, 24, 64, 48, coord=abi.RUB)
 
-    def call(views):
+    def call(views, a=buf, b=buf, ha=h, hb=h):
         arr = (abi.RenderParams * max(1, len(views)))(*views)
         out = (abi.ImageMetrics * max(1, len(views)))()
         bad = C.c_int32(7)
-        rc = L.spz_amd_compare_host(buf, 4096, C.byref(h), buf, 4096, C.byref(h), arr, len(views), 0, out, None, None,
+        rc = L.spz_amd_compare_host(a, 4096, C.byref(ha), b, 4096, C.byref(hb), arr, len(views), 0, out, None, None,
                                     None, C.byref(bad))
         return rc, bad.value
 
@@ -139,9 +139,25 @@ def test_c_abi_compare_checks_the_views_first():
     worse = abi.RenderParams.from_buffer_copy(good)
     worse.near_plane = 0.0
     assert call([good, good, worse]) == (abi.ERR_INVALID_ARG, 2)
+    assert call([worse, good, good]) == (abi.ERR_INVALID_ARG, 0)
     other = abi.RenderParams.from_buffer_copy(good)
     other.coord = abi.RDF
     assert call([good, other]) == (abi.ERR_INVALID_ARG, 1)
+    # the views before the inputs: no streams, a header the render refuses
+    assert call([good, other], a=None, b=None) == (abi.ERR_INVALID_ARG, 1)
+    assert call([good], a=None) == (abi.ERR_INVALID_ARG, -1) and call([good], b=None) == (abi.ERR_INVALID_ARG, -1)
+    big = abi.Header.from_buffer_copy(h)
+    big.num_points = 0x80000000
+    assert call([good, good, worse], ha=big) == (abi.ERR_INVALID_ARG, 2)
+    # an input: the version, the degree, the point count, the stream's length, in this order; A before B
+    assert call([good], ha=big)[0] == abi.ERR_TOO_MANY_POINTS and call([good], hb=big)[0] == abi.ERR_TOO_MANY_POINTS
+    big.sh_degree = 4
+    assert call([good], hb=big)[0] == abi.ERR_SH_DEGREE
+    big.version = 0
+    assert call([good], hb=big)[0] == abi.ERR_VERSION
+    long = abi.Header.from_buffer_copy(h)
+    long.num_points = 1000
+    assert call([good], ha=long, hb=big)[0] == abi.ERR_SHORT_STREAM
 
 
 def test_compare_spz_arguments_are_checked_first(spz, tmp_path):

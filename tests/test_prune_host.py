@@ -148,10 +148,10 @@ def test_c_abi_checks_the_views_before_any_device_work():
     buf = (C.c_uint8 * 4096)()
     good = abi.render_params(RR.look_at([0, 0, -5], [0, 0, 0], [0, 1, 0]), 50, 50, 32, 24, 64, 48, coord=abi.RUB)
 
-    def call(views, rule=abi.PRUNE_KEEP_COUNT, value=1.0, kind=abi.PRUNE_SCORE_SUM):
+    def call(views, rule=abi.PRUNE_KEEP_COUNT, value=1.0, kind=abi.PRUNE_SCORE_SUM, stream=buf, hdr=h):
         arr = (abi.RenderParams * max(1, len(views)))(*views)
         ctx, nbytes, bad = C.c_void_p(), C.c_uint64(), C.c_int32(7)
-        rc = L.spz_amd_prune_open(buf, 4096, C.byref(h), arr, len(views), kind, rule, value, 0, C.byref(ctx),
+        rc = L.spz_amd_prune_open(stream, 4096, C.byref(hdr), arr, len(views), kind, rule, value, 0, C.byref(ctx),
                                   C.byref(nbytes), None, None, None, None, None, C.byref(bad))
         assert not ctx.value
         return rc, bad.value
@@ -161,9 +161,20 @@ def test_c_abi_checks_the_views_before_any_device_work():
     worse = abi.RenderParams.from_buffer_copy(good)
     worse.fx = -1.0
     assert call([good, good, worse]) == (abi.ERR_INVALID_ARG, 2)
+    assert call([worse, good, good]) == (abi.ERR_INVALID_ARG, 0)
     other = abi.RenderParams.from_buffer_copy(good)
     other.coord = abi.RDF
     assert call([good, other]) == (abi.ERR_INVALID_ARG, 1)
+    assert call([good, other], stream=None) == (abi.ERR_INVALID_ARG, -1)    # no stream: before the views
+    assert call([good, other], kind=2) == (abi.ERR_INVALID_ARG, 1)          # the views: before the score kind,
+    big = abi.Header.from_buffer_copy(h)
+    big.num_points = 0x80000000
+    assert call([good, other], hdr=big) == (abi.ERR_INVALID_ARG, 1)         # and before the input;
+    assert call([good], hdr=big)[0] == abi.ERR_TOO_MANY_POINTS              # the point count before the short stream
+    big.sh_degree = 4
+    assert call([good], hdr=big)[0] == abi.ERR_SH_DEGREE
+    big.version = 4
+    assert call([good], hdr=big)[0] == abi.ERR_VERSION
     assert call([good], kind=2)[0] == abi.ERR_INVALID_ARG
     assert call([good], rule=3)[0] == abi.ERR_INVALID_ARG
     assert call([good], value=11.0)[0] == abi.ERR_INVALID_ARG       # K above n

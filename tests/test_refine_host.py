@@ -222,11 +222,11 @@ def test_refine_open_refuses_bad_arguments_and_no_device_is_an_error():
     good = good_view()
     history = (C.c_double * 8)()
 
-    def call(views, a=buf, b=buf, ha=h, hb=h, size_a=4096, hist=history, **kw):
+    def call(views, a=buf, b=buf, ha=h, hb=h, size_a=4096, size_b=4096, hist=history, **kw):
         o = abi.refine_options(kw.pop("iterations", 4), **kw) if "options" not in kw else kw["options"]
         arr = (abi.RenderParams * max(1, len(views)))(*views)
         ctx, nbytes, bad = C.c_void_p(), C.c_uint64(), C.c_int32(7)
-        rc = L.spz_amd_refine_open(a, size_a, C.byref(ha) if ha is not None else None, b, 4096,
+        rc = L.spz_amd_refine_open(a, size_a, C.byref(ha) if ha is not None else None, b, size_b,
                                    C.byref(hb) if hb is not None else None, arr, len(views),
                                    C.byref(o) if o is not None else None, 0, C.byref(ctx), C.byref(nbytes), hist, None,
                                    None, None, None, C.byref(bad))
@@ -238,7 +238,18 @@ def test_refine_open_refuses_bad_arguments_and_no_device_is_an_error():
     worse = abi.RenderParams.from_buffer_copy(good)
     worse.fx = -1.0
     assert call([good, good, worse]) == (abi.ERR_INVALID_ARG, 2)
+    assert call([worse, good, good]) == (abi.ERR_INVALID_ARG, 0)
     assert call([good, good_view(coord=6)]) == (abi.ERR_INVALID_ARG, 1)      # mixed coords
+    # the options before the views, the views before the streams
+    assert call([worse, good], options=None) == (abi.ERR_INVALID_ARG, -1)
+    assert call([], options=None) == (abi.ERR_INVALID_ARG, -1)
+    assert call([good, good, worse], a=None, b=None, ha=None, hb=None) == (abi.ERR_INVALID_ARG, 2)
+    big = abi.Header.from_buffer_copy(h)
+    big.num_points = 0x80000000
+    assert call([good, good_view(coord=6)], ha=big) == (abi.ERR_INVALID_ARG, 1)
+    assert call([good], ha=big)[0] == abi.ERR_SHORT_STREAM                   # here the stream's length comes first,
+    assert call([good], hb=big)[0] == abi.ERR_SHORT_STREAM
+    assert call([good], hb=big, size_b=2 ** 36)[0] == abi.ERR_TOO_MANY_POINTS  # then the point count (B never read)
     assert call([good], options=None) == (abi.ERR_INVALID_ARG, -1)
     assert call([good], a=None)[0] == abi.ERR_INVALID_ARG
     assert call([good], b=None)[0] == abi.ERR_INVALID_ARG
