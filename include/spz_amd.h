@@ -1060,6 +1060,126 @@ int spz_amd_refine_fetch(void *ctx, uint8_t *h_out);
 const uint8_t *spz_amd_refine_device_data(void *ctx);
 void spz_amd_refine_close(void *ctx);
 
+/* ---- densify: 3DGS's adaptive density control over a float cloud and its Adam moments (spz_densify.hip; DESIGN §8
+ *      "Densify").  The reference has no counterpart.  Gaussians whose screen-space position gradient stays high are
+ *      cloned (small ones) or split in two (large ones), transparent ones are culled, opacities can be reset.  No float
+ *      atomics anywhere: given the same inputs every entry repeats its bits.  Arguments are checked on the host before
+ *      any launch; the device entries enqueue on hip_stream and do not synchronise, unless stated.
+ *
+ *      Options (densify_default_options: 3DGS's published values; interval and opacity_reset_interval are 0 = off, as
+ *      every layer above has densify off unless asked; 3DGS runs them at 100 and 3000).  densify_check (host only)
+ *      refuses negative values, until_iter < from_iter, NaN or infinities, min_opacity outside (0, 1), and percent_dense
+ *      <= 0 when interval > 0.
+ *      Thresholds (densify_thresholds, host only, f64 then rounded to f32): extent = options->extent, or when that is 0
+ *      3DGS's 1.1 max_v |c_v - mean c| over the views' camera centres c = -R^T t (a result of 0, or no views:
+ *      SPZ_AMD_ERR_INVALID_ARG); log_dense = log(percent_dense extent); alpha_min = log(min_opacity / (1 -
+ *      min_opacity)); log_max_scale = log(max_scale), use_max_scale = 0 when max_scale is 0.  The kernels compare floats
+ *      and never evaluate exp or a sigmoid.
+ *
+ *      accumulate: one thread per Gaussian.  d_records: the n records of the view's prepare step (the front of the
+ *      render workspace); d_record_grads: the n x 9 record gradients of render_backward_device, mean first, in pixels.
+ *      For a record of finite depth (the forward's "visible"): d_accum[i] += sqrt((gx 0.5 W)^2 + (gy 0.5 H)^2), in f32,
+ *      each operation rounded once and none contracted, the square root correctly rounded; a non-finite norm adds 0;
+ *      d_denom[i] += 1 (uint32) either way.  The scaling puts the gradient in 3DGS's NDC units.
+ *
+ *      plan: d_action[n] (uint8: 0 keep, 1 clone, 2 split, 3 cull), then the output lists d_parent[n'] (uint32: the
+ *      input index) and d_child[n'] (uint8: 0 the Gaussian itself, 1 a clone's copy, 2 and 3 a split's children), and
+ *      d_counts[5] (uint64, device memory: n', cloned, split, culled, refused).  Per Gaussian, with ms = the largest of
+ *      its three log scales (NaN ignored): cull if alpha < alpha_min (-inf is culled, NaN is not) or, with use_max_scale,
+ *      ms > log_max_scale; else a candidate if g >= grad_threshold, g = denom > 0 ? accum / denom : 0, NaN as 0; a
+ *      candidate is a split if ms > log_dense, else a clone.  Every candidate adds one point; the budget is max(0,
+ *      max_points - (n - culled)); candidates are granted in descending g, ties to the lower index (argsort_f32_device,
+ *      stable): rank r is granted iff r < budget; a refused candidate is a keep and is counted.  Output order is input
+ *      order, each Gaussian replaced in place by its outputs: keep -> itself; clone -> itself, then the copy; split ->
+ *      child 2, child 3; cull -> nothing.  Offsets: an exclusive scan per 256 Gaussians and one of the workgroups' sums.
+ *      list_capacity (entries of d_parent and d_child) must be at least min(2 n, max(max_points, n)), which bounds n'.
+ *      densify_plan_workspace_bytes (host only): device memory for n Gaussians.  densify_plan_host: the same, then
+ *      blocks and copies the five counts to h_counts.  n < 2^31.
+ *
+ *      apply: one launch, a gather through d_parent (entries clamped to n_src - 1) of the six arrays of the parameters
+ *      and both moments into destination sets that do not overlap the sources.  keep and a clone's child 0: parameters
+ *      and moments copied; child 1: parameters copied, moments 0; children 2 and 3: moments 0, log scales - (float)log
+ *      1.6 in f32 (3DGS's / (0.8 * 2)), position p + R(q / |q|) (exp(ls) (.) z_k) in f64 from the f32 inputs, rounded
+ *      once (R as the render's preprocess forms it from xyzw); a child whose position is not finite takes the parent's;
+ *      everything else copied.  z_2, z_3: standard normals from counters, with sm = splitmix64 (x += 0x9E3779B97F4A7C15;
+ *      x = (x ^ x >> 30) 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) 0x94D049BB133111EB; x ^ x >> 31): key = sm(sm(seed ^
+ *      round) + i), i the parent's index; for j = 0..2: a = sm(key + 2 j + 1), b = sm(key + 2 j + 2), u1 = ((a >> 11) +
+ *      1) 2^-53, u2 = (b >> 11) 2^-53, r = sqrt(-2 ln u1), z_2[j] = r cos(2 pi u2), z_3[j] = r sin(2 pi u2).  n_new
+ *      above dst_capacity (points): SPZ_AMD_ERR_CAPACITY.  sh may be NULL when sh_degree == 0.
+ *      reset_opacity: alpha = min(alpha, (float)logit(0.01)), NaN left alone; the alphas' two moments zeroed.
+ *
+ *      refine_densify_open: spz_amd_refine_open with densify.  densify NULL or interval == 0: exactly refine_open
+ *      (*h_num_points = A's count, no rounds).  Else positions and scales must be in the train mask, and alphas when
+ *      opacity_reset_interval > 0 (SPZ_AMD_ERR_INVALID_ARG); max_points (0: B's count) below A's count:
+ *      SPZ_AMD_ERR_INVALID_ARG, above 2^31 - 1: SPZ_AMD_ERR_TOO_MANY_POINTS.  After the backward of each iteration i in
+ *      [from_iter, until_iter): accumulate.  After the Adam step of such an i with (i + 1) % interval == 0: plan_host,
+ *      apply, the sets swapped, accum and denom zeroed.  After the Adam step of any i with (i + 1) %
+ *      opacity_reset_interval == 0: reset.  Adam's t stays i + 1 for everyone.  Every buffer is allocated once at
+ *      capacity max_points: seven float clouds (parameters, gradients, two moments, and the apply's three destinations)
+ *      beside 9 + 2 floats, 14 bytes of lists and origin maps and the plan's workspace per point: about 7 x 4 x (14 + 3
+ *      sh_dim) + 58 bytes + densify_plan_workspace_bytes(max_points) / max_points per point of max_points.  apply's
+ *      `round` is the count of rounds so far, from 0.
+ *      Output: A's header with num_points =
+ *      n'; sections of trained arrays encoded from the floats; sections of untrained arrays A's bytes gathered through
+ *      the origin map (the index in A of each output point, carried through every round) with subset_device.  h_rounds
+ *      (may be NULL): the first rounds_capacity rounds; *h_num_rounds (may be NULL): how many ran.  h_origin (may be
+ *      NULL): max_points entries of room, n' written. */
+typedef struct {
+  int32_t interval;               /* a round every `interval` iterations; 0 = off */
+  int32_t from_iter, until_iter;  /* rounds and accumulation run for iterations in [from_iter, until_iter) */
+  int32_t opacity_reset_interval; /* 0 = off */
+  double grad_threshold;          /* 2e-4 */
+  double percent_dense;           /* 0.01 */
+  double extent;                  /* 0 = derive from the views */
+  double min_opacity;             /* 0.005 */
+  double max_scale;               /* 0 = off */
+  uint64_t max_points;            /* 0 = the target's count */
+  uint64_t seed;
+} spz_amd_densify_options;
+typedef struct {
+  float grad_threshold, log_dense, alpha_min, log_max_scale;
+  int32_t use_max_scale;
+  int32_t reserved;
+  double extent;
+} spz_amd_densify_limits;
+typedef struct {
+  int32_t iteration;
+  int32_t reserved;
+  uint64_t cloned, split, culled, refused, num_points;
+} spz_amd_densify_round;
+int spz_amd_densify_default_options(spz_amd_densify_options *options);
+int spz_amd_densify_check(const spz_amd_densify_options *options);
+int spz_amd_densify_thresholds(const spz_amd_densify_options *options, const spz_amd_render_params *views,
+                               int num_views, spz_amd_densify_limits *limits);
+int spz_amd_densify_accumulate_device(const spz_amd_render_record *d_records, const float *d_record_grads,
+                                      uint64_t num_points, uint32_t width, uint32_t height, float *d_accum,
+                                      uint32_t *d_denom, void *hip_stream);
+uint64_t spz_amd_densify_plan_workspace_bytes(uint64_t num_points);
+int spz_amd_densify_plan_device(const float *d_accum, const uint32_t *d_denom, const float *d_scales,
+                                const float *d_alphas, uint64_t num_points, const spz_amd_densify_limits *limits,
+                                uint64_t max_points, uint64_t list_capacity, uint8_t *d_action, uint32_t *d_parent,
+                                uint8_t *d_child, uint64_t *d_counts, void *d_workspace, void *hip_stream);
+int spz_amd_densify_plan_host(const float *d_accum, const uint32_t *d_denom, const float *d_scales,
+                              const float *d_alphas, uint64_t num_points, const spz_amd_densify_limits *limits,
+                              uint64_t max_points, uint64_t list_capacity, uint8_t *d_action, uint32_t *d_parent,
+                              uint8_t *d_child, uint64_t *d_counts, void *d_workspace, uint64_t *h_counts,
+                              void *hip_stream);
+int spz_amd_densify_apply_device(const spz_amd_cloud_grads *d_src_params, const spz_amd_cloud_grads *d_src_m,
+                                 const spz_amd_cloud_grads *d_src_v, const spz_amd_cloud_grads *d_dst_params,
+                                 const spz_amd_cloud_grads *d_dst_m, const spz_amd_cloud_grads *d_dst_v,
+                                 const uint32_t *d_parent, const uint8_t *d_child, uint64_t n_src, uint64_t n_new,
+                                 uint64_t dst_capacity, int sh_degree, uint64_t seed, uint32_t round, void *hip_stream);
+int spz_amd_densify_reset_opacity_device(float *d_alphas, float *d_alphas_m, float *d_alphas_v, uint64_t num_points,
+                                         void *hip_stream);
+int spz_amd_refine_densify_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
+                                const uint8_t *d_stream_b, size_t size_b, const spz_amd_header *hdr_b,
+                                const spz_amd_render_params *views, int num_views, const spz_amd_refine_options *options,
+                                const spz_amd_densify_options *densify, int device, void **ctx, uint64_t *h_out_bytes,
+                                double *h_history, spz_amd_image_metrics *h_before, spz_amd_image_metrics *h_after,
+                                uint64_t *h_skipped, float *h_ms, int32_t *h_bad_view, uint64_t *h_num_points,
+                                spz_amd_densify_round *h_rounds, int rounds_capacity, int *h_num_rounds,
+                                uint32_t *h_origin);
+
 /* ---- device buffers for a resident cloud, placed for speed (spz_place.hip).  Whether an sh3 decode runs
  *      at 0.46 ms or at 0.55 ms is decided by whether the sh float array shares a physical region of HBM with the other
  *      arrays of the launch; that cannot be asked for, but it shows in one launch.  alloc: the five small arrays (and a

@@ -559,6 +559,25 @@ bool compareImages(const float *a, int channelsA, const float *b, int channelsB,
 // with f32 atomics, so two runs may differ in the last bits.  false + one "[SPZ ERROR] refineSpz: …" line on a bad
 // argument (lastDeviceStatus() = SPZ_AMD_ERR_INVALID_ARG; a bad view is named by its index), an input that does not load,
 // a version 1 input (SPZ_AMD_ERR_UNSUPPORTED), or a device failure.  SPZ_AMD_REFINE_TIMING=1 prints the stages' times.
+// Densify (DESIGN §8 "Densify"; include/spz_amd.h "densify"): with interval > 0 refineSpz runs 3DGS's adaptive density
+// control while it fits: after every `interval` iterations in [fromIter, untilIter) the Gaussians whose mean screen-space
+// position gradient is at least gradThreshold are cloned (largest scale <= percentDense * extent) or split in two, and
+// those with opacity under minOpacity (or a scale above maxScale, when set) are culled, never growing past maxPoints (0:
+// the target's count).  extent 0: derived from the views' camera centres, as 3DGS does; one view cannot give one.
+// Positions and scales must be trained, and alphas when opacityResetInterval > 0.  The output's header carries the new
+// count; untrained sections keep the input's bytes, gathered from the point each output point descends from.
+struct DensifyOptions {
+  int interval = 0;  // 0 = off
+  int fromIter = 500, untilIter = 15000;
+  int opacityResetInterval = 0;  // 0 = off
+  double gradThreshold = 2e-4, percentDense = 0.01, extent = 0.0, minOpacity = 0.005, maxScale = 0.0;
+  uint64_t maxPoints = 0;
+  uint64_t seed = 0;
+};
+struct DensifyRound {
+  int iteration = 0;
+  uint64_t cloned = 0, split = 0, culled = 0, refused = 0, numPoints = 0;
+};
 struct RefineOptions {
   enum Train { Positions = 1, Scales = 2, Rotations = 4, Alphas = 8, Colors = 16, Sh = 32, All = 63 };
   std::vector<PruneOptions::View> views;
@@ -572,6 +591,7 @@ struct RefineOptions {
   double scaleLr = 5e-3, rotationLr = 1e-3, alphaLr = 5e-2, colorLr = 2.5e-3, shLr = 2.5e-3 / 20.0;
   double beta1 = 0.9, beta2 = 0.999, eps = 1e-15;
   unsigned train = All;
+  DensifyOptions densify;  // off by default
 };
 struct RefineReport {
   std::vector<double> history;               // the loss before each step
@@ -579,6 +599,8 @@ struct RefineReport {
   uint64_t skipped = 0;                      // non-finite elements the steps left alone, summed over the steps
   double positionLr = 0.0;                   // the rate used
   float ms[3] = {0.0f, 0.0f, 0.0f};          // targets + before, iterations + encode, after
+  uint64_t numPoints = 0;                    // of the output (the input's, without densify)
+  std::vector<DensifyRound> rounds;          // what each densify round did
 };
 bool refineSpz(const uint8_t *data, int32_t size, const uint8_t *target, int32_t targetSize, const RefineOptions &options,
                std::vector<uint8_t> *out, RefineReport *report = nullptr);

@@ -91,6 +91,10 @@ EXPORTS = (
     "spz_amd_image_loss_workspace_bytes", "spz_amd_image_loss_device", "spz_amd_adam_scalars_of",
     "spz_amd_adam_step_device", "spz_amd_refine_default_options", "spz_amd_refine_check", "spz_amd_refine_open",
     "spz_amd_refine_fetch", "spz_amd_refine_device_data", "spz_amd_refine_close",
+    "spz_amd_densify_default_options", "spz_amd_densify_check", "spz_amd_densify_thresholds",
+    "spz_amd_densify_accumulate_device", "spz_amd_densify_plan_workspace_bytes", "spz_amd_densify_plan_device",
+    "spz_amd_densify_plan_host", "spz_amd_densify_apply_device", "spz_amd_densify_reset_opacity_device",
+    "spz_amd_refine_densify_open",
 )
 
 RCCL_UNIQUE_ID_BYTES = 128
@@ -192,6 +196,32 @@ class RefineOptions(C.Structure):
     """spz_amd_refine_options (include/spz_amd.h "refine")."""
     _fields_ = [("iterations", C.c_int32), ("train_mask", C.c_uint32), ("lambda_dssim", C.c_double),
                 ("lr", C.c_double * 6), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
+
+
+class DensifyOptions(C.Structure):
+    """spz_amd_densify_options (include/spz_amd.h "densify"); interval 0 = off."""
+    _fields_ = [("interval", C.c_int32), ("from_iter", C.c_int32), ("until_iter", C.c_int32),
+                ("opacity_reset_interval", C.c_int32), ("grad_threshold", C.c_double), ("percent_dense", C.c_double),
+                ("extent", C.c_double), ("min_opacity", C.c_double), ("max_scale", C.c_double),
+                ("max_points", C.c_uint64), ("seed", C.c_uint64)]
+
+
+class DensifyLimits(C.Structure):
+    """spz_amd_densify_limits: the f32 thresholds the plan kernel compares against, and the extent they came from."""
+    _fields_ = [("grad_threshold", C.c_float), ("log_dense", C.c_float), ("alpha_min", C.c_float),
+                ("log_max_scale", C.c_float), ("use_max_scale", C.c_int32), ("reserved", C.c_int32),
+                ("extent", C.c_double)]
+
+
+class DensifyRound(C.Structure):
+    """spz_amd_densify_round: what one round of refine's densify did."""
+    _fields_ = [("iteration", C.c_int32), ("reserved", C.c_int32), ("cloned", C.c_uint64), ("split", C.c_uint64),
+                ("culled", C.c_uint64), ("refused", C.c_uint64), ("num_points", C.c_uint64)]
+
+
+DENSIFY_KEEP, DENSIFY_CLONE, DENSIFY_SPLIT, DENSIFY_CULL = 0, 1, 2, 3   # d_action's values
+DENSIFY_FIELDS = ("interval", "from_iter", "until_iter", "opacity_reset_interval", "grad_threshold", "percent_dense",
+                  "extent", "min_opacity", "max_scale", "max_points", "seed")
 
 
 class TileInfo(C.Structure):
@@ -623,6 +653,34 @@ def bind(L):
     L.spz_amd_refine_device_data.argtypes = [vp]
     L.spz_amd_refine_close.restype = None
     L.spz_amd_refine_close.argtypes = [vp]
+    L.spz_amd_densify_default_options.restype = i32
+    L.spz_amd_densify_default_options.argtypes = [C.POINTER(DensifyOptions)]
+    L.spz_amd_densify_check.restype = i32
+    L.spz_amd_densify_check.argtypes = [C.POINTER(DensifyOptions)]
+    L.spz_amd_densify_thresholds.restype = i32
+    L.spz_amd_densify_thresholds.argtypes = [C.POINTER(DensifyOptions), C.POINTER(RenderParams), i32,
+                                             C.POINTER(DensifyLimits)]
+    L.spz_amd_densify_accumulate_device.restype = i32
+    L.spz_amd_densify_accumulate_device.argtypes = [vp, vp, u64, u32, u32, vp, vp, vp]
+    L.spz_amd_densify_plan_workspace_bytes.restype = u64
+    L.spz_amd_densify_plan_workspace_bytes.argtypes = [u64]
+    L.spz_amd_densify_plan_device.restype = i32
+    L.spz_amd_densify_plan_device.argtypes = [vp, vp, vp, vp, u64, C.POINTER(DensifyLimits), u64, u64, vp, vp, vp, vp,
+                                              vp, vp]
+    L.spz_amd_densify_plan_host.restype = i32
+    L.spz_amd_densify_plan_host.argtypes = [vp, vp, vp, vp, u64, C.POINTER(DensifyLimits), u64, u64, vp, vp, vp, vp, vp,
+                                            C.POINTER(u64), vp]
+    L.spz_amd_densify_apply_device.restype = i32
+    L.spz_amd_densify_apply_device.argtypes = [C.POINTER(CloudPtrs)] * 6 + [vp, vp, u64, u64, u64, i32, u64, u32, vp]
+    L.spz_amd_densify_reset_opacity_device.restype = i32
+    L.spz_amd_densify_reset_opacity_device.argtypes = [vp, vp, vp, u64, vp]
+    L.spz_amd_refine_densify_open.restype = i32
+    L.spz_amd_refine_densify_open.argtypes = [vp, sz, C.POINTER(Header), vp, sz, C.POINTER(Header),
+                                              C.POINTER(RenderParams), i32, C.POINTER(RefineOptions),
+                                              C.POINTER(DensifyOptions), i32, C.POINTER(vp), C.POINTER(u64), vp,
+                                              C.POINTER(ImageMetrics), C.POINTER(ImageMetrics), C.POINTER(u64), vp,
+                                              C.POINTER(C.c_int32), C.POINTER(u64), C.POINTER(DensifyRound), i32,
+                                              C.POINTER(C.c_int32), vp]
     return L
 
 
@@ -758,6 +816,45 @@ def refine_options(iterations, *, lambda_dssim=None, lrs=None, beta1=None, beta2
     if train is not None:
         o.train_mask = train_mask(train)
     return o
+
+
+def densify_options(options=None, **fields):
+    """spz_amd_densify_default_options with the given fields replaced (a dict, a DensifyOptions to copy, or keywords:
+    DENSIFY_FIELDS), checked by spz_amd_densify_check: ValueError on an unknown field or a refused value."""
+    L = load_library()
+    o = DensifyOptions()
+    check(L.spz_amd_densify_default_options(C.byref(o)), "spz_amd_densify_default_options")
+    if isinstance(options, DensifyOptions):
+        o = DensifyOptions.from_buffer_copy(options)
+    elif options is not None:
+        if not isinstance(options, dict):
+            raise ValueError("densify must be a dict or an abi.DensifyOptions")
+        fields = {**options, **fields}
+    for k, x in fields.items():
+        if k not in DENSIFY_FIELDS:
+            raise ValueError(f"densify: unknown field {k!r} (one of {', '.join(DENSIFY_FIELDS)})")
+        if isinstance(getattr(o, k), int):
+            if isinstance(x, bool) or not isinstance(x, int) or x < 0 or (k not in ("max_points", "seed") and x > 2**31 - 1) \
+                    or x > 2**64 - 1:
+                raise ValueError(f"densify: {k} must be a non-negative int, got {x!r}")
+            setattr(o, k, x)
+        else:
+            setattr(o, k, float(x))
+    if L.spz_amd_densify_check(C.byref(o)) != OK:
+        raise ValueError("densify: refused options (values >= 0 and finite, until_iter >= from_iter, min_opacity in "
+                         "(0, 1), percent_dense > 0 when interval > 0)")
+    return o
+
+
+def densify_thresholds(options, views=()):
+    """The f32 thresholds of `options` over `views` (spz_amd_densify_thresholds, host only): a DensifyLimits.  With
+    extent == 0 it is derived from the views' camera centres; when that gives 0, SpzAmdError (invalid argument)."""
+    views = list(views)
+    arr = (RenderParams * max(1, len(views)))(*views)
+    out = DensifyLimits()
+    check(load_library().spz_amd_densify_thresholds(C.byref(options), arr if views else None, len(views), C.byref(out)),
+          "spz_amd_densify_thresholds")
+    return out
 
 
 def merge_resolve(headers, sh_degree=None, fractional_bits=None, antialiased=None):

@@ -658,16 +658,20 @@ const char *kRefineUsage =
     "Usage: spz_refine <in.spz> <target.spz> <out.spz> (--views FILE | --orbit N --size W H --fov-y DEG [--center x y z "
     "--radius R] [--distance K]) [--iters N] [--lambda-dssim L] [--lr-positions X] [--lr-scales X] [--lr-rotations X] "
     "[--lr-alphas X] [--lr-colors X] [--lr-sh X] [--train positions,scales,rotations,alphas,colors,sh] "
-    "[--coord " SPZ_COORD_NAMES "] [--background r g b] [--max-sh-degree D] [--near Z]";
+    "[--coord " SPZ_COORD_NAMES "] [--background r g b] [--max-sh-degree D] [--near Z] [--densify-interval N "
+    "[--densify-from I] [--densify-until I] [--grad-threshold X] [--percent-dense X] [--extent X] [--min-opacity X] "
+    "[--max-scale X] [--max-points N] [--opacity-reset-interval N] [--seed S]]";
 
 // One line per view with its PSNR and SSIM before and after, then their means.  An orbit without --center is taken
-// around the target.
+// around the target.  With --densify-interval N (alone: from = N, until = iterations / 2) one line per densify round
+// and the final count follow.
 int spzRefine(int argc, char **argv) {
   Args a(argc, argv, kRefineUsage);
   if (!a.files(3)) return a.usage();
   spz::RefineOptions o;
   ViewArgs va;
   std::string train;
+  spz::DensifyOptions &dn = o.densify;
   auto rate = [&](double *x) { return a.real(x) && std::isfinite(*x) && *x >= 0.0; };
   while (a.next()) {
     bool good = false;
@@ -685,9 +689,31 @@ int spzRefine(int argc, char **argv) {
     else if (a.is("--background")) good = a.real(o.background.data(), 3) && allFinite(o.background.data(), 3);
     else if (a.is("--max-sh-degree")) good = a.integer(&o.maxShDegree, 0, 3);
     else if (a.is("--near")) good = a.real(&o.nearPlane) && std::isfinite(o.nearPlane) && o.nearPlane > 0.0f;
+    else if (a.is("--densify-interval")) good = a.integer(&dn.interval, 0, 0x7fffffff);
+    else if (a.is("--densify-from")) good = a.integer(&dn.fromIter, 0, 0x7fffffff);
+    else if (a.is("--densify-until")) good = a.integer(&dn.untilIter, 0, 0x7fffffff);
+    else if (a.is("--opacity-reset-interval")) good = a.integer(&dn.opacityResetInterval, 0, 0x7fffffff);
+    else if (a.is("--grad-threshold")) good = rate(&dn.gradThreshold);
+    else if (a.is("--percent-dense")) good = rate(&dn.percentDense) && dn.percentDense > 0.0;
+    else if (a.is("--extent")) good = rate(&dn.extent);
+    else if (a.is("--min-opacity")) good = rate(&dn.minOpacity) && dn.minOpacity > 0.0 && dn.minOpacity < 1.0;
+    else if (a.is("--max-scale")) good = rate(&dn.maxScale);
+    else if (a.is("--max-points")) good = a.integer(&dn.maxPoints, 0, 0x7fffffff);
+    else if (a.is("--seed")) good = a.integer(&dn.seed, 0, UINT64_MAX);
     if (!good) return a.usage();
   }
   if (!va.consistent(a)) return a.usage();
+  static const char *const kDensifyOnly[] = {"--densify-from", "--densify-until", "--grad-threshold", "--percent-dense",
+                                             "--extent", "--min-opacity", "--max-scale", "--max-points",
+                                             "--opacity-reset-interval", "--seed"};
+  for (const char *name : kDensifyOnly) {
+    if (a.given(name) && !a.given("--densify-interval")) return a.usage();
+  }
+  if (dn.interval > 0) {
+    if (!a.given("--densify-from")) dn.fromIter = dn.interval;
+    if (!a.given("--densify-until")) dn.untilIter = std::max(dn.fromIter, o.iterations / 2);
+    if (dn.untilIter < dn.fromIter) return a.usage();
+  }
   if (a.given("--train")) {
     static const char *const kArrays[6] = {"positions", "scales", "rotations", "alphas", "colors", "sh"};
     o.train = 0;
@@ -719,6 +745,15 @@ int spzRefine(int argc, char **argv) {
   if (!r.history.empty()) {
     std::printf("loss %.17g -> %.17g over %zu iterations, %llu non-finite elements skipped\n", r.history.front(),
                 r.history.back(), r.history.size(), static_cast<unsigned long long>(r.skipped));
+  }
+  if (dn.interval > 0) {
+    for (const spz::DensifyRound &x : r.rounds) {
+      std::printf("densify iteration %d cloned %llu split %llu culled %llu refused %llu points %llu\n", x.iteration,
+                  static_cast<unsigned long long>(x.cloned), static_cast<unsigned long long>(x.split),
+                  static_cast<unsigned long long>(x.culled), static_cast<unsigned long long>(x.refused),
+                  static_cast<unsigned long long>(x.numPoints));
+    }
+    std::printf("points %llu\n", static_cast<unsigned long long>(r.numPoints));
   }
   std::fflush(stdout);
   return 0;

@@ -2892,7 +2892,8 @@ bool compareSpz(const std::string &fileA, const std::string &fileB, const Compar
 // ---- refine ------------------------------------------------------------------------------------------------------
 namespace {
 // The views as render params, and the options but the position rate as the C ABI's.
-bool refineOptionsOk(const RefineOptions &o, std::vector<spz_amd_render_params> *params, spz_amd_refine_options *c) {
+bool refineOptionsOk(const RefineOptions &o, std::vector<spz_amd_render_params> *params, spz_amd_refine_options *c,
+                     spz_amd_densify_options *d) {
   const char *who = "refineSpz";
   const int invalid = SPZ_AMD_ERR_INVALID_ARG;
   if (o.iterations < 0) return opRejected(who, invalid, "iterations %d is negative", o.iterations);
@@ -2914,6 +2915,29 @@ bool refineOptionsOk(const RefineOptions &o, std::vector<spz_amd_render_params> 
   if (spz_amd_refine_check(c) != SPZ_AMD_OK) {
     return opRejected(who, invalid, "learning rates must be finite and >= 0, beta1 and beta2 in [0, 1), eps finite and >= 0");
   }
+  spz_amd_densify_default_options(d);
+  const DensifyOptions &dn = o.densify;
+  d->interval = dn.interval;
+  d->from_iter = dn.fromIter;
+  d->until_iter = dn.untilIter;
+  d->opacity_reset_interval = dn.opacityResetInterval;
+  d->grad_threshold = dn.gradThreshold;
+  d->percent_dense = dn.percentDense;
+  d->extent = dn.extent;
+  d->min_opacity = dn.minOpacity;
+  d->max_scale = dn.maxScale;
+  d->max_points = dn.maxPoints;
+  d->seed = dn.seed;
+  if (spz_amd_densify_check(d) != SPZ_AMD_OK) {
+    return opRejected(who, invalid, "densify: values must be finite and >= 0, untilIter >= fromIter, minOpacity in (0, 1), "
+                      "percentDense > 0 when interval > 0");
+  }
+  if (dn.interval > 0) {
+    if ((o.train & 3u) != 3u) return opRejected(who, invalid, "densify needs positions and scales among the trained arrays");
+    if (dn.opacityResetInterval > 0 && (o.train & 8u) == 0u) {
+      return opRejected(who, invalid, "the opacity reset needs alphas among the trained arrays");
+    }
+  }
   return viewListParams(who, o.views, SPZ_AMD_REFINE_MAX_VIEWS,
                         {o.nearPlane, o.coord, &o.background, o.maxShDegree, ", maxShDegree 0..3, coord valid"}, params);
 }
@@ -2927,7 +2951,8 @@ bool refineSpz(const uint8_t *data, int32_t size, const uint8_t *target, int32_t
   if (out == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no output vector");
   std::vector<spz_amd_render_params> params;
   spz_amd_refine_options c;
-  if (!refineOptionsOk(o, &params, &c)) return false;
+  spz_amd_densify_options d;
+  if (!refineOptionsOk(o, &params, &c, &d)) return false;
   Laps laps(who, "SPZ_AMD_REFINE_TIMING");
   DevicePackedGaussians da, db;
   if (!loadInput(who, data, size, &da) || !loadInput(who, target, targetSize, &db)) return false;
@@ -2951,9 +2976,30 @@ bool refineSpz(const uint8_t *data, int32_t size, const uint8_t *target, int32_t
   uint64_t bytes = 0, skipped = 0;
   float ms[3] = {0.0f, 0.0f, 0.0f};
   int32_t bad = -1;
-  const int rc = spz_amd_refine_open(da.stream, da.streamBytes, &ha, db.stream, db.streamBytes, &hb, params.data(),
-                                     static_cast<int>(nv), &c, da.device, &r.ctx, &bytes, history.data(), before.data(),
-                                     after.data(), &skipped, ms, &bad);
+  const bool densify = d.interval > 0;
+  if (densify) {
+    spz_amd_densify_limits lim;
+    if (spz_amd_densify_thresholds(&d, params.data(), static_cast<int>(nv), &lim) != SPZ_AMD_OK) {
+      return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "densify: the views' camera centres coincide, so they give no "
+                        "extent: set densify.extent");
+    }
+    const uint64_t cap = d.max_points ? d.max_points : hb.num_points;
+    if (cap < ha.num_points) {
+      return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "densify: maxPoints %llu is below the input's %u points",
+                        static_cast<unsigned long long>(cap), ha.num_points);
+    }
+  }
+  uint64_t numPoints = ha.num_points;
+  int numRounds = 0;
+  std::vector<spz_amd_densify_round> rounds(densify ? static_cast<size_t>(o.iterations / d.interval) + 1 : 0);
+  const int rc = densify
+      ? spz_amd_refine_densify_open(da.stream, da.streamBytes, &ha, db.stream, db.streamBytes, &hb, params.data(),
+                                    static_cast<int>(nv), &c, &d, da.device, &r.ctx, &bytes, history.data(),
+                                    before.data(), after.data(), &skipped, ms, &bad, &numPoints, rounds.data(),
+                                    static_cast<int>(rounds.size()), &numRounds, nullptr)
+      : spz_amd_refine_open(da.stream, da.streamBytes, &ha, db.stream, db.streamBytes, &hb, params.data(),
+                            static_cast<int>(nv), &c, da.device, &r.ctx, &bytes, history.data(), before.data(),
+                            after.data(), &skipped, ms, &bad);
   if (rc == SPZ_AMD_ERR_UNSUPPORTED) {
     return opRejected(who, rc, "the encoder writes versions 2 and 3 and positions at 12 fractional bits: the input has "
                       "version %u and %u", ha.version, static_cast<unsigned>(ha.fractional_bits));
@@ -2978,6 +3024,11 @@ bool refineSpz(const uint8_t *data, int32_t size, const uint8_t *target, int32_t
     report->skipped = skipped;
     report->positionLr = c.lr[0];
     for (int k = 0; k < 3; ++k) report->ms[k] = ms[k];
+    report->numPoints = numPoints;
+    for (int k = 0; k < numRounds && static_cast<size_t>(k) < rounds.size(); ++k) {
+      const spz_amd_densify_round &x = rounds[static_cast<size_t>(k)];
+      report->rounds.push_back(DensifyRound{x.iteration, x.cloned, x.split, x.culled, x.refused, x.num_points});
+    }
   }
   return true;
 }
@@ -2998,7 +3049,8 @@ bool refineSpz(const std::string &inputFilename, const std::string &targetFilena
   if (report) *report = RefineReport{};
   std::vector<spz_amd_render_params> params;
   spz_amd_refine_options c;
-  if (!refineOptionsOk(o, &params, &c)) return false;
+  spz_amd_densify_options d;
+  if (!refineOptionsOk(o, &params, &c, &d)) return false;
   std::vector<uint8_t> target;
   if (!readInput(who, targetFilename, &target)) return false;
   RefineReport rep;

@@ -1326,7 +1326,7 @@ PYBIND11_MODULE(spz, m) {
         [](const py::object &input, const py::object &target, const py::object &output, const py::object &views,
            int iterations, spz::CoordinateSystem coord, const py::object &background, int max_sh_degree,
            float near_plane, double lambda_dssim, const py::object &lrs, double beta1, double beta2, double eps,
-           const py::object &train) {
+           const py::object &train, const py::object &densify) {
           // the arguments first: every problem is a ValueError before any device work
           static const char *const kArrays[6] = {"positions", "scales", "rotations", "alphas", "colors", "sh"};
           if (iterations < 0) throw py::value_error("iterations must be >= 0");
@@ -1379,6 +1379,67 @@ PYBIND11_MODULE(spz, m) {
             }
             if (o.train == 0) throw py::value_error("train must name at least one array");
           }
+          if (!densify.is_none()) {
+            // a dict, or an options object with the same names (spz_amd.abi.DensifyOptions)
+            static const char *const kInts[4] = {"interval", "from_iter", "until_iter", "opacity_reset_interval"};
+            static const char *const kReals[5] = {"grad_threshold", "percent_dense", "extent", "min_opacity", "max_scale"};
+            static const char *const kCounts[2] = {"max_points", "seed"};
+            spz::DensifyOptions &dn = o.densify;
+            int *const ints[4] = {&dn.interval, &dn.fromIter, &dn.untilIter, &dn.opacityResetInterval};
+            double *const reals[5] = {&dn.gradThreshold, &dn.percentDense, &dn.extent, &dn.minOpacity, &dn.maxScale};
+            uint64_t *const counts[2] = {&dn.maxPoints, &dn.seed};
+            const bool isDict = py::isinstance<py::dict>(densify);
+            size_t known = 0;
+            auto field = [&](const char *name) -> py::object {
+              if (isDict) {
+                const py::dict dd = py::reinterpret_borrow<py::dict>(densify);
+                if (!dd.contains(name)) return py::none();
+                ++known;
+                return dd[name];
+              }
+              if (!py::hasattr(densify, name)) throw py::value_error("densify must be a dict or a densify options object");
+              return densify.attr(name);
+            };
+            try {
+              for (int k = 0; k < 4; ++k) {
+                const py::object x = field(kInts[k]);
+                if (x.is_none()) continue;
+                if (!py::isinstance<py::int_>(x) || py::isinstance<py::bool_>(x)) throw py::cast_error();
+                const long long v = x.cast<long long>();
+                if (v < 0 || v > 0x7fffffffLL) throw py::cast_error();
+                *ints[k] = static_cast<int>(v);
+              }
+              for (int k = 0; k < 5; ++k) {
+                const py::object x = field(kReals[k]);
+                if (!x.is_none()) *reals[k] = x.cast<double>();
+              }
+              for (int k = 0; k < 2; ++k) {
+                const py::object x = field(kCounts[k]);
+                if (x.is_none()) continue;
+                if (!py::isinstance<py::int_>(x) || py::isinstance<py::bool_>(x)) throw py::cast_error();
+                *counts[k] = x.cast<uint64_t>();
+              }
+            } catch (const py::cast_error &) {
+              throw py::value_error("densify: a field has the wrong type or is out of range");
+            }
+            if (isDict && known != py::reinterpret_borrow<py::dict>(densify).size()) {
+              throw py::value_error("densify: unknown field (interval, from_iter, until_iter, opacity_reset_interval, "
+                                    "grad_threshold, percent_dense, extent, min_opacity, max_scale, max_points, seed)");
+            }
+            const double realsNow[5] = {dn.gradThreshold, dn.percentDense, dn.extent, dn.minOpacity, dn.maxScale};
+            for (double x : realsNow) {
+              if (!std::isfinite(x) || x < 0.0) throw py::value_error("densify: values must be finite and >= 0");
+            }
+            if (dn.untilIter < dn.fromIter) throw py::value_error("densify: until_iter is below from_iter");
+            if (!(dn.minOpacity > 0.0 && dn.minOpacity < 1.0)) throw py::value_error("densify: min_opacity must be in (0, 1)");
+            if (dn.interval > 0 && !(dn.percentDense > 0.0)) throw py::value_error("densify: percent_dense must be > 0");
+            if (dn.interval > 0 && (o.train & 3u) != 3u) {
+              throw py::value_error("densify needs positions and scales among the trained arrays");
+            }
+            if (dn.interval > 0 && dn.opacityResetInterval > 0 && (o.train & 8u) == 0u) {
+              throw py::value_error("densify: the opacity reset needs alphas among the trained arrays");
+            }
+          }
           if (py::isinstance<py::dict>(views) || py::isinstance<py::str>(views) || !py::isinstance<py::sequence>(views)) {
             throw py::value_error("views must be a sequence of view dicts (orbit_views, load_3dgs_cameras)");
           }
@@ -1424,6 +1485,19 @@ PYBIND11_MODULE(spz, m) {
           d["skipped"] = rep.skipped;
           d["position_lr"] = rep.positionLr;
           d["ms"] = py::make_tuple(rep.ms[0], rep.ms[1], rep.ms[2]);
+          d["num_points"] = rep.numPoints;
+          py::list rounds;
+          for (const spz::DensifyRound &x : rep.rounds) {
+            py::dict r;
+            r["iteration"] = x.iteration;
+            r["cloned"] = x.cloned;
+            r["split"] = x.split;
+            r["culled"] = x.culled;
+            r["refused"] = x.refused;
+            r["num_points"] = x.numPoints;
+            rounds.append(r);
+          }
+          d["rounds"] = rounds;
           if (fromBytes) d["data"] = py::bytes(reinterpret_cast<const char *>(bytes.data()), bytes.size());
           return d;
         },
@@ -1431,7 +1505,7 @@ PYBIND11_MODULE(spz, m) {
         py::arg("iterations") = 200, py::arg("coord") = spz::CoordinateSystem::UNSPECIFIED,
         py::arg("background") = py::make_tuple(0.0f, 0.0f, 0.0f), py::arg("max_sh_degree") = 3, py::arg("near") = 0.2f,
         py::arg("lambda_dssim") = 0.2, py::arg("lrs") = py::none(), py::arg("beta1") = 0.9, py::arg("beta2") = 0.999,
-        py::arg("eps") = 1e-15, py::arg("train") = py::none(),
+        py::arg("eps") = 1e-15, py::arg("train") = py::none(), py::arg("densify") = py::none(),
         "Fit the .spz file `input` to the file `target` over `views` on the device and write `output` (spz::refineSpz; "
         "the contract is in include/spz_amd.h \"refine\"): the target is rendered once per view, then `iterations` Adam "
         "steps on the 3DGS loss (1 - lambda_dssim) l1 + lambda_dssim (1 - ssim), view i mod V at step i, over the "
@@ -1439,7 +1513,11 @@ PYBIND11_MODULE(spz, m) {
         "untrained arrays keep the input's bytes.  lrs: a dict by array name replacing 3DGS's published rates (the "
         "position rate defaults to 1.6e-4 times the target's bounding-sphere radius).  Paths in: `output` is written; "
         "bytes in (output None): the dict carries \"data\".  Returns a dict: history (the loss before each step), "
-        "before and after (one metrics dict per view, the latter of the written stream), skipped, position_lr, ms.");
+        "before and after (one metrics dict per view, the latter of the written stream), skipped, position_lr, ms, "
+        "num_points and rounds.  densify: None, or a dict (or spz_amd.abi.DensifyOptions) of interval, from_iter, "
+        "until_iter, grad_threshold, percent_dense, extent, min_opacity, max_scale, max_points, opacity_reset_interval, "
+        "seed: with interval > 0 Gaussians are cloned, split and culled every `interval` iterations (include/spz_amd.h "
+        "\"densify\"), the output's count is num_points and rounds has one dict per round.");
   m.def("compare_images",
         [](const py::object &a, const py::object &b, const py::object &return_map) {
           if (!py::isinstance<py::bool_>(return_map)) throw py::value_error("return_map must be a bool");

@@ -23,6 +23,7 @@
 
 #include "spz_amd.h"
 #include "spz_common.hpp"
+#include "spz_densify_internal.hpp"
 #include "spz_view_pass.hpp"
 
 namespace spz_amd_detail {
@@ -275,13 +276,28 @@ int spz_amd_refine_check(const spz_amd_refine_options *o) {
   return spz_amd_adam_scalars_of(1, o->lr, o->beta1, o->beta2, o->eps, &sc);
 }
 
-int spz_amd_refine_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
-                        const uint8_t *d_stream_b, size_t size_b, const spz_amd_header *hdr_b,
-                        const spz_amd_render_params *views, int num_views, const spz_amd_refine_options *options,
-                        int device, void **ctx, uint64_t *h_out_bytes, double *h_history,
-                        spz_amd_image_metrics *h_before, spz_amd_image_metrics *h_after, uint64_t *h_skipped, float *h_ms,
-                        int32_t *h_bad_view) {
+}  // extern "C"
+
+namespace {
+
+// What the densify entry reports beside refine_open's results.
+struct DensifyReport {
+  uint64_t *h_num_points;
+  spz_amd_densify_round *h_rounds;
+  int rounds_capacity;
+  int *h_num_rounds;
+  uint32_t *h_origin;
+};
+
+// The loop of both entries: spz_amd_refine_open (densify == nullptr) and spz_amd_refine_densify_open.
+int refine_run(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a, const uint8_t *d_stream_b,
+               size_t size_b, const spz_amd_header *hdr_b, const spz_amd_render_params *views, int num_views,
+               const spz_amd_refine_options *options, const spz_amd_densify_options *densify, int device, void **ctx,
+               uint64_t *h_out_bytes, double *h_history, spz_amd_image_metrics *h_before, spz_amd_image_metrics *h_after,
+               uint64_t *h_skipped, float *h_ms, int32_t *h_bad_view, const DensifyReport &rep) {
   if (h_bad_view) *h_bad_view = -1;
+  if (rep.h_num_points) *rep.h_num_points = 0;
+  if (rep.h_num_rounds) *rep.h_num_rounds = 0;
   if (ctx == nullptr || h_out_bytes == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
   *ctx = nullptr;
   *h_out_bytes = 0;
@@ -303,6 +319,24 @@ int spz_amd_refine_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_
   if (deg == 0) mask &= ~32u;  // nothing to train there
   // what the encode kernel writes: versions 2 and 3, positions at 12 fractional bits
   if (iters > 0 && (hdr_a->version == 1 || ((mask & 1u) && hdr_a->fractional_bits != 12))) return SPZ_AMD_ERR_UNSUPPORTED;
+  // densify: the thresholds once, every buffer at the capacity the cloud may grow to
+  spz_amd_densify_limits lim = {};
+  uint64_t cap_n = n;
+  bool dn = false;
+  if (densify != nullptr) {
+    rc = spz_amd_densify_check(densify);
+    if (rc != SPZ_AMD_OK) return rc;
+    if (densify->interval > 0) {
+      rc = spz_amd_densify_thresholds(densify, views, num_views, &lim);
+      if (rc != SPZ_AMD_OK) return rc;
+      if ((mask & 3u) != 3u || (densify->opacity_reset_interval > 0 && (mask & 8u) == 0u)) return SPZ_AMD_ERR_INVALID_ARG;
+      const uint64_t mp = densify->max_points ? densify->max_points : hdr_b->num_points;
+      if (mp > kMaxEntries) return SPZ_AMD_ERR_TOO_MANY_POINTS;
+      if (mp < n) return SPZ_AMD_ERR_INVALID_ARG;
+      dn = iters > 0;
+      if (dn) cap_n = mp;
+    }
+  }
   DeviceGuard guard;
   rc = guard.enter(device);
   if (rc != SPZ_AMD_OK) return rc;
@@ -313,7 +347,7 @@ int spz_amd_refine_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_
 
   // the block: four clouds, the targets, the image and its gradient, the two small workspaces, the results
   uint64_t count[6];
-  cloud_counts(n, deg, count);
+  cloud_counts(cap_n, deg, count);
   uint64_t max_px = 0, loss_ws = 0, metrics_ws = 0;
   std::vector<uint64_t> target_off((size_t)num_views);
   for (int v = 0; v < num_views; ++v) {
@@ -333,7 +367,16 @@ int spz_amd_refine_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_
   const uint64_t o_image = o.put(16u * max_px), o_grad = o.put(16u * max_px), o_lws = o.put(iters ? loss_ws : 0u),
                  o_mws = o.put(metrics_ws), o_small = o.put(16u), o_loss = o.put(24u * (uint64_t)iters),
                  o_metrics = o.put(2u * (uint64_t)num_views * sizeof(spz_amd_image_metrics)),
-                 o_bws = o.put(iters ? spz_amd_render_backward_workspace_bytes(n) : 0u);
+                 o_bws = o.put(iters ? spz_amd_render_backward_workspace_bytes(cap_n) : 0u);
+  uint64_t off_alt[3][6] = {};
+  for (int s = 0; s < 3; ++s) {
+    for (int k = 0; k < 6; ++k) off_alt[s][k] = o.put(dn ? count[k] * 4u : 0u);
+  }
+  const uint64_t o_accum = o.put(dn ? cap_n * 4u : 0u), o_denom = o.put(dn ? cap_n * 4u : 0u),
+                 o_action = o.put(dn ? cap_n : 0u), o_parent = o.put(dn ? cap_n * 4u : 0u),
+                 o_child = o.put(dn ? cap_n : 0u), o_origin0 = o.put(dn ? cap_n * 4u : 0u),
+                 o_origin1 = o.put(dn ? cap_n * 4u : 0u), o_rg = o.put(dn ? cap_n * 36u : 0u),
+                 o_counts = o.put(dn ? 64u : 0u), o_pws = o.put(dn ? spz_amd_densify_plan_workspace_bytes(cap_n) : 0u);
   SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->block), o.off));
   uint8_t *raw = c->block;  // every section is 256-aligned from hipMalloc's base
   CloudSet cs;
@@ -343,6 +386,21 @@ int spz_amd_refine_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_
   cs.v = cloud_at(raw, off[3], count);
   cs.moments_off = off[2][0];
   cs.moments_bytes = target_off[0] - off[2][0];
+  CloudSet alt;  // the apply's destinations: parameters and both moments
+  if (dn) {
+    alt.p = cloud_at(raw, off_alt[0], count);
+    alt.m = cloud_at(raw, off_alt[1], count);
+    alt.v = cloud_at(raw, off_alt[2], count);
+  }
+  auto *d_accum = reinterpret_cast<float *>(raw + o_accum);
+  auto *d_denom = reinterpret_cast<uint32_t *>(raw + o_denom);
+  auto *d_parent = reinterpret_cast<uint32_t *>(raw + o_parent);
+  uint32_t *d_origin[2] = {reinterpret_cast<uint32_t *>(raw + o_origin0), reinterpret_cast<uint32_t *>(raw + o_origin1)};
+  const uint32_t *origin_cur = nullptr;  // nullptr: no round yet, the identity
+  auto *d_rg = reinterpret_cast<float *>(raw + o_rg);
+  auto *d_counts = reinterpret_cast<uint64_t *>(raw + o_counts);
+  uint64_t n_cur = n;
+  std::vector<spz_amd_densify_round> rounds;
   auto *d_image = reinterpret_cast<float *>(raw + o_image);
   auto *d_grad = reinterpret_cast<float *>(raw + o_grad);
   auto *d_total = reinterpret_cast<uint64_t *>(raw + o_small);
@@ -389,7 +447,8 @@ int spz_amd_refine_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_
     rc = spz_amd_decode_device(d_stream_a, size_a, hdr_a, coord, &dec, c->st);
     if (rc != SPZ_AMD_OK) return rc;
     if (cs.moments_bytes) SPZ_HIP_TRY(hipMemsetAsync(raw + cs.moments_off, 0, cs.moments_bytes, c->st));
-    const spz_amd_cloud_in cloud = {cs.p.positions, cs.p.scales, cs.p.rotations, cs.p.alphas, cs.p.colors, cs.p.sh};
+    spz_amd_cloud_in cloud = {cs.p.positions, cs.p.scales, cs.p.rotations, cs.p.alphas, cs.p.colors, cs.p.sh};
+    if (dn && cap_n) SPZ_HIP_TRY(hipMemsetAsync(raw + o_accum, 0, o_action - o_accum, c->st));  // accum and denom
     RenderSource src_f;
     src_f.cloud = &cloud;
     src_f.n = n;
@@ -403,14 +462,66 @@ int spz_amd_refine_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_
       rc = spz_amd_image_loss_device(d_image, 4, target(v), 4, (int)p.width, (int)p.height, options->lambda_dssim,
                                      d_loss + 3 * (size_t)i, d_grad, raw + o_lws, c->st);
       if (rc != SPZ_AMD_OK) return fail(v, rc);
-      rc = spz_amd_render_backward_device(&cloud, n, deg, aa, &p, total, d_image, d_grad, &cs.g, nullptr, d_status,
-                                          c->scratch, raw + o_bws, c->st);
+      const bool gather_stats = dn && i >= densify->from_iter && i < densify->until_iter;
+      rc = spz_amd_render_backward_device(&cloud, n_cur, deg, aa, &p, total, d_image, d_grad, &cs.g,
+                                          gather_stats && n_cur ? d_rg : nullptr, d_status, c->scratch, raw + o_bws,
+                                          c->st);
       if (rc != SPZ_AMD_OK) return fail(v, rc);
-      if (n) {
+      if (gather_stats && n_cur) {  // the records are the front of the render workspace
+        rc = spz_amd_densify_accumulate_device(reinterpret_cast<const spz_amd_render_record *>(align_ws(c->scratch)),
+                                               d_rg, n_cur, p.width, p.height, d_accum, d_denom, c->st);
+        if (rc != SPZ_AMD_OK) return rc;
+      }
+      if (n_cur) {
         spz_amd_adam_scalars sc;
         rc = spz_amd_adam_scalars_of(i + 1, options->lr, options->beta1, options->beta2, options->eps, &sc);
         if (rc != SPZ_AMD_OK) return rc;
-        rc = adam_enqueue(&cs.p, &cs.g, &cs.m, &cs.v, n, deg, mask, sc, d_skipped, c->st);
+        rc = adam_enqueue(&cs.p, &cs.g, &cs.m, &cs.v, n_cur, deg, mask, sc, d_skipped, c->st);
+        if (rc != SPZ_AMD_OK) return rc;
+      }
+      if (gather_stats && (i + 1) % densify->interval == 0) {
+        uint64_t counts[5] = {};
+        rc = spz_amd_densify_plan_host(d_accum, d_denom, cs.p.scales, cs.p.alphas, n_cur, &lim, cap_n, cap_n,
+                                       raw + o_action, d_parent, raw + o_child, d_counts, raw + o_pws, counts, c->st);
+        if (rc != SPZ_AMD_OK) return rc;
+        const uint64_t n_new = counts[0];
+        if (n_new > cap_n) return SPZ_AMD_ERR_CAPACITY;  // (the plan's bound says it cannot be)
+        rc = spz_amd_densify_apply_device(&cs.p, &cs.m, &cs.v, &alt.p, &alt.m, &alt.v, d_parent, raw + o_child, n_cur,
+                                          n_new, cap_n, deg, densify->seed, (uint32_t)rounds.size(), c->st);
+        if (rc != SPZ_AMD_OK) return rc;
+        uint32_t *origin_next = d_origin[origin_cur == d_origin[0] ? 1 : 0];
+        rc = densify_gather_u32(origin_cur, d_parent, n_cur, n_new, origin_next, c->st);
+        if (rc != SPZ_AMD_OK) return rc;
+        origin_cur = origin_next;
+        std::swap(cs.p, alt.p);
+        std::swap(cs.m, alt.m);
+        std::swap(cs.v, alt.v);
+        cloud = spz_amd_cloud_in{cs.p.positions, cs.p.scales, cs.p.rotations, cs.p.alphas, cs.p.colors, cs.p.sh};
+        if (cap_n) SPZ_HIP_TRY(hipMemsetAsync(raw + o_accum, 0, o_action - o_accum, c->st));
+        rounds.push_back(spz_amd_densify_round{i, 0, counts[1], counts[2], counts[3], counts[4], n_new});
+        n_cur = n_new;
+        src_f.n = n_cur;
+      }
+      if (dn && densify->opacity_reset_interval > 0 && (i + 1) % densify->opacity_reset_interval == 0) {
+        rc = spz_amd_densify_reset_opacity_device(cs.p.alphas, cs.m.alphas, cs.v.alphas, n_cur, c->st);
+        if (rc != SPZ_AMD_OK) return rc;
+      }
+    }
+    if (dn) {
+      // the output at the new count: A's bytes gathered through the origin map, the header's count replaced
+      spz_amd_layout lay_o;
+      rc = spz_amd_stream_layout(n_cur, deg, (int)hdr_a->version, &lay_o);
+      if (rc != SPZ_AMD_OK) return rc;
+      if (origin_cur != nullptr) {
+        SPZ_HIP_TRY(hipStreamSynchronize(c->st));
+        SPZ_HIP_TRY(hipFree(c->out_block));
+        c->out_block = nullptr;
+        c->out = nullptr;
+        SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->out_block), lay_o.total_bytes));
+        c->out = c->out_block;
+        c->out_bytes = lay_o.total_bytes;
+        rc = spz_amd_subset_device(d_stream_a, size_a, hdr_a, origin_cur, n_cur, -1, c->out_block, lay_o.total_bytes,
+                                   c->st);
         if (rc != SPZ_AMD_OK) return rc;
       }
     }
@@ -419,9 +530,9 @@ int spz_amd_refine_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_
                                 1u << SPZ_AMD_SEC_ALPHAS,    1u << SPZ_AMD_SEC_COLORS, 1u << SPZ_AMD_SEC_SH};
     unsigned sections = 0;
     for (int k = 0; k < 6; ++k) sections |= ((mask >> k) & 1u) ? sec_of[k] : 0u;
-    if (n && sections) {
-      rc = spz_amd_encode_shard_sections_device(&cloud, 0, n, n, deg, aa, coord, (int)hdr_a->version, 0, sections,
-                                                c->out_block, lay_a.total_bytes, c->st);
+    if (n_cur && sections) {
+      rc = spz_amd_encode_shard_sections_device(&cloud, 0, n_cur, n_cur, deg, aa, coord, (int)hdr_a->version, 0, sections,
+                                                c->out_block, c->out_bytes, c->st);
       if (rc != SPZ_AMD_OK) return rc;
     }
   }
@@ -429,9 +540,9 @@ int spz_amd_refine_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_
   const double loop_ms = ms_since(t0) - before_ms;
 
   // the "after" metrics: of the output stream
-  RenderSource src_o = src_a;
-  src_o.d_stream = c->out_block;
-  src_o.size = lay_a.total_bytes;
+  spz_amd_header hdr_o = *hdr_a;
+  hdr_o.num_points = (uint32_t)n_cur;
+  RenderSource src_o = packed_render_source(c->out_block, c->out_bytes, &hdr_o);
   for (int v = 0; v < num_views; ++v) {
     const spz_amd_render_params &p = views[v];
     if (iters == 0) break;
@@ -450,7 +561,16 @@ int spz_amd_refine_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_
   if (iters) SPZ_HIP_TRY(hipMemcpyAsync(loss3.data(), d_loss, 24u * (size_t)iters, hipMemcpyDeviceToHost, c->st));
   uint32_t skipped = 0;
   SPZ_HIP_TRY(hipMemcpyAsync(&skipped, d_skipped, 4, hipMemcpyDeviceToHost, c->st));
+  if (rep.h_origin && origin_cur && n_cur) {
+    SPZ_HIP_TRY(hipMemcpyAsync(rep.h_origin, origin_cur, 4u * n_cur, hipMemcpyDeviceToHost, c->st));
+  }
   SPZ_HIP_TRY(hipStreamSynchronize(c->st));
+  if (rep.h_origin && !origin_cur) {
+    for (uint64_t k = 0; k < n_cur; ++k) rep.h_origin[k] = (uint32_t)k;
+  }
+  if (rep.h_num_points) *rep.h_num_points = n_cur;
+  if (rep.h_num_rounds) *rep.h_num_rounds = (int)rounds.size();
+  for (size_t k = 0; rep.h_rounds && k < rounds.size() && (int)k < rep.rounds_capacity; ++k) rep.h_rounds[k] = rounds[k];
   for (int i = 0; i < iters; ++i) h_history[i] = loss3[3u * (size_t)i];
   if (h_skipped) *h_skipped = skipped;
   if (h_ms) {
@@ -466,6 +586,40 @@ int spz_amd_refine_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_
   c->block = nullptr;
   *ctx = c.release();
   return SPZ_AMD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int spz_amd_refine_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
+                        const uint8_t *d_stream_b, size_t size_b, const spz_amd_header *hdr_b,
+                        const spz_amd_render_params *views, int num_views, const spz_amd_refine_options *options,
+                        int device, void **ctx, uint64_t *h_out_bytes, double *h_history,
+                        spz_amd_image_metrics *h_before, spz_amd_image_metrics *h_after, uint64_t *h_skipped, float *h_ms,
+                        int32_t *h_bad_view) {
+  return refine_run(d_stream_a, size_a, hdr_a, d_stream_b, size_b, hdr_b, views, num_views, options, nullptr, device,
+                    ctx, h_out_bytes, h_history, h_before, h_after, h_skipped, h_ms, h_bad_view,
+                    DensifyReport{nullptr, nullptr, 0, nullptr, nullptr});
+}
+
+int spz_amd_refine_densify_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
+                                const uint8_t *d_stream_b, size_t size_b, const spz_amd_header *hdr_b,
+                                const spz_amd_render_params *views, int num_views, const spz_amd_refine_options *options,
+                                const spz_amd_densify_options *densify, int device, void **ctx, uint64_t *h_out_bytes,
+                                double *h_history, spz_amd_image_metrics *h_before, spz_amd_image_metrics *h_after,
+                                uint64_t *h_skipped, float *h_ms, int32_t *h_bad_view, uint64_t *h_num_points,
+                                spz_amd_densify_round *h_rounds, int rounds_capacity, int *h_num_rounds,
+                                uint32_t *h_origin) {
+  if (rounds_capacity < 0 || (rounds_capacity > 0 && h_rounds == nullptr)) {
+    if (h_bad_view) *h_bad_view = -1;
+    if (ctx) *ctx = nullptr;
+    if (h_out_bytes) *h_out_bytes = 0;
+    return SPZ_AMD_ERR_INVALID_ARG;
+  }
+  return refine_run(d_stream_a, size_a, hdr_a, d_stream_b, size_b, hdr_b, views, num_views, options, densify, device,
+                    ctx, h_out_bytes, h_history, h_before, h_after, h_skipped, h_ms, h_bad_view,
+                    DensifyReport{h_num_points, h_rounds, rounds_capacity, h_num_rounds, h_origin});
 }
 
 int spz_amd_refine_fetch(void *ctx, uint8_t *h_out) { return packed_result_fetch(ctx, h_out); }

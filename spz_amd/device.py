@@ -1399,13 +1399,124 @@ class RefineResult:
             pass
 
 
+def _flat(name, t, dtype, count, dev):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous() \
+            or t.numel() != count or (dev is not None and t.device != dev):
+        raise ValueError(f"{name} must be a contiguous {dtype} CUDA tensor of {count} elements"
+                         + (f" on {dev}" if dev is not None else ""))
+    return t
+
+
+def densify_accumulate(records, record_grads, width, height, accum, denom, stream=None):
+    """Add one view's screen-space position gradient norms to accum (float32 [n]) and count the view in denom (int32
+    [n]) for every visible Gaussian (spz_amd_densify_accumulate_device; include/spz_amd.h "densify").  records: the
+    view's n raw 48-byte render records, a uint8 CUDA tensor of 48 n bytes (the front of a render workspace, 256-aligned);
+    record_grads: render_backward(..., return_record_grads=True)["records"], (n, 9) float32.  In place; returns None."""
+    L = abi.load_library()
+    n = int(accum.numel()) if isinstance(accum, torch.Tensor) else -1
+    dev = accum.device if isinstance(accum, torch.Tensor) else None
+    _flat("accum", accum, torch.float32, n, None)
+    _flat("denom", denom, torch.int32, n, dev)
+    _flat("records", records, torch.uint8, n * abi.RENDER_RECORD_BYTES, dev)
+    _flat("record_grads", record_grads, torch.float32, n * 9, dev)
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        rc = L.spz_amd_densify_accumulate_device(records.data_ptr(), record_grads.data_ptr(), n, int(width), int(height),
+                                                 accum.data_ptr(), denom.data_ptr(), C.c_void_p(st.cuda_stream))
+    abi.check(rc, "spz_amd_densify_accumulate_device")
+
+
+def densify_plan(accum, denom, scales, alphas, limits, max_points, stream=None):
+    """Decide one densify round (spz_amd_densify_plan_host; include/spz_amd.h "densify"): accum (float32 [n]), denom
+    (int32 [n]), the cloud's flat log scales [3 n] and alpha logits [n], limits (abi.densify_thresholds) and the cap
+    max_points.  Blocks for the counts.  Returns a dict: action (uint8 [n]: abi.DENSIFY_KEEP / CLONE / SPLIT / CULL),
+    parent (int32 [n']) and child (uint8 [n']) for densify_apply, and num_points, cloned, split, culled, refused."""
+    L = abi.load_library()
+    if not isinstance(limits, abi.DensifyLimits):
+        raise ValueError("limits must be an abi.DensifyLimits (abi.densify_thresholds)")
+    if isinstance(max_points, bool) or not isinstance(max_points, int) or max_points < 0:
+        raise ValueError(f"max_points must be a non-negative int, got {max_points!r}")
+    n = int(accum.numel()) if isinstance(accum, torch.Tensor) else -1
+    dev = accum.device if isinstance(accum, torch.Tensor) else None
+    _flat("accum", accum, torch.float32, n, None)
+    _flat("denom", denom, torch.int32, n, dev)
+    _flat("scales", scales, torch.float32, 3 * n, dev)
+    _flat("alphas", alphas, torch.float32, n, dev)
+    cap = min(2 * n, max(max_points, n))
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        with torch.cuda.stream(st):
+            action = torch.empty(n, dtype=torch.uint8, device=dev)
+            parent = torch.empty(cap, dtype=torch.int32, device=dev)
+            child = torch.empty(cap, dtype=torch.uint8, device=dev)
+            counts = torch.empty(5, dtype=torch.int64, device=dev)
+            ws = torch.empty(max(8, int(L.spz_amd_densify_plan_workspace_bytes(n))), dtype=torch.uint8, device=dev)
+            h = (C.c_uint64 * 5)()
+            rc = L.spz_amd_densify_plan_host(accum.data_ptr(), denom.data_ptr(), scales.data_ptr(), alphas.data_ptr(), n,
+                                             C.byref(limits), max_points, cap, action.data_ptr(), parent.data_ptr(),
+                                             child.data_ptr(), counts.data_ptr(), ws.data_ptr(), h,
+                                             C.c_void_p(st.cuda_stream))
+    abi.check(rc, "spz_amd_densify_plan_host")
+    m = int(h[0])
+    return {"action": action, "parent": parent[:m], "child": child[:m], "num_points": m, "cloned": int(h[1]),
+            "split": int(h[2]), "culled": int(h[3]), "refused": int(h[4])}
+
+
+def densify_apply(cloud, m, v, num_points, sh_degree, parent, child, seed=0, round=0, stream=None):
+    """Rewrite a float cloud and its two Adam moments at a plan's new count (spz_amd_densify_apply_device; include/
+    spz_amd.h "densify"): one launch gathering all 18 arrays through parent.  cloud, m, v: dicts of flat float32 CUDA
+    tensors of num_points Gaussians (sh may be missing at degree 0).  Returns (cloud', m', v') as new dicts."""
+    L = abi.load_library()
+    if int(sh_degree) not in SH_DIM:
+        raise ValueError(f"sh_degree must be 0..3, got {sh_degree}")
+    n = int(num_points)
+    dev = cloud["positions"].device
+    n_new = int(parent.numel()) if isinstance(parent, torch.Tensor) else -1
+    _flat("parent", parent, torch.int32, n_new, dev)
+    _flat("child", child, torch.uint8, n_new, dev)
+    src = [_ptrs(c, sh_degree, n, dev) for c in (cloud, m, v)]
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        with torch.cuda.stream(st):
+            out = [alloc_cloud(n_new, sh_degree, dev) for _ in range(3)]
+            dst = [_ptrs(c, sh_degree, n_new, dev) for c in out]
+            rc = L.spz_amd_densify_apply_device(C.byref(src[0]), C.byref(src[1]), C.byref(src[2]), C.byref(dst[0]),
+                                                C.byref(dst[1]), C.byref(dst[2]), parent.data_ptr(), child.data_ptr(), n,
+                                                n_new, n_new, int(sh_degree), int(seed), int(round),
+                                                C.c_void_p(st.cuda_stream))
+    abi.check(rc, "spz_amd_densify_apply_device")
+    return tuple(out)
+
+
+def reset_opacity(alphas, m=None, v=None, stream=None):
+    """3DGS's opacity reset, in place (spz_amd_densify_reset_opacity_device): alphas = min(alphas, logit(0.01)), NaN
+    left alone; the alphas' Adam moments m and v (float32 [n], or None) zeroed."""
+    L = abi.load_library()
+    n = int(alphas.numel()) if isinstance(alphas, torch.Tensor) else -1
+    dev = alphas.device if isinstance(alphas, torch.Tensor) else None
+    _flat("alphas", alphas, torch.float32, n, None)
+    for name, t in (("m", m), ("v", v)):
+        if t is not None:
+            _flat(name, t, torch.float32, n, dev)
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        rc = L.spz_amd_densify_reset_opacity_device(alphas.data_ptr(), m.data_ptr() if m is not None else None,
+                                                    v.data_ptr() if v is not None else None, n,
+                                                    C.c_void_p(st.cuda_stream))
+    abi.check(rc, "spz_amd_densify_reset_opacity_device")
+
+
 def refine_packed(stream_a, header_a, stream_b, header_b, views, iterations, *, lambda_dssim=None, lrs=None, beta1=None,
-                  beta2=None, eps=None, train=None):
+                  beta2=None, eps=None, train=None, densify=None):
     """Fit the resident packed stream A to the target B over `views` (a sequence of abi.RenderParams, one coord):
     spz_amd_refine_open (include/spz_amd.h "refine").  Options left None take spz_amd_refine_default_options' values
     (lrs[0], the position rate, is for a scene of unit extent: scale it by the scene's).  Blocks; runs on a stream of
     the library's own after the current stream has drained.  Returns a RefineResult; a bad view raises
-    abi.SpzAmdError whose `view` attribute names it."""
+    abi.SpzAmdError whose `view` attribute names it.
+    densify: None, or a dict / abi.DensifyOptions (abi.densify_options) for spz_amd_refine_densify_open: Gaussians are
+    cloned, split and culled while fitting, up to max_points (0: B's count).  The report's num_points is the output's
+    count, rounds one dict per round (iteration, cloned, split, culled, refused, num_points), and origin the index in A
+    of every output point (a numpy uint32 array)."""
     L = abi.load_library()
     _check_stream_tensor(stream_a)
     _check_stream_tensor(stream_b)
@@ -1423,18 +1534,43 @@ def refine_packed(stream_a, header_a, stream_b, header_b, views, iterations, *, 
     before = (abi.ImageMetrics * len(views))()
     after = (abi.ImageMetrics * len(views))()
     ms = (C.c_float * 3)()
+    dopts = abi.densify_options(densify) if densify is not None else None
     torch.cuda.current_stream(dev).synchronize()  # the streams' producers
-    rc = L.spz_amd_refine_open(stream_a.data_ptr(), stream_a.numel(), C.byref(header_a), stream_b.data_ptr(),
-                               stream_b.numel(), C.byref(header_b), arr, len(views), C.byref(opts),
-                               dev.index if dev.index is not None else torch.cuda.current_device(), C.byref(ctx),
-                               C.byref(out_bytes), history, before, after, C.byref(skipped), ms, C.byref(bad))
+    device_index = dev.index if dev.index is not None else torch.cuda.current_device()
+    num_points, rounds, origin = int(header_a.num_points), [], None
+    if dopts is None:
+        entry = "spz_amd_refine_open"
+        rc = L.spz_amd_refine_open(stream_a.data_ptr(), stream_a.numel(), C.byref(header_a), stream_b.data_ptr(),
+                                   stream_b.numel(), C.byref(header_b), arr, len(views), C.byref(opts), device_index,
+                                   C.byref(ctx), C.byref(out_bytes), history, before, after, C.byref(skipped), ms,
+                                   C.byref(bad))
+    else:
+        import numpy as np
+        entry = "spz_amd_refine_densify_open"
+        room = max(1, opts.iterations // max(1, dopts.interval))
+        h_rounds, n_rounds, n_out = (abi.DensifyRound * room)(), C.c_int32(), C.c_uint64()
+        cap = max(int(dopts.max_points) or int(header_b.num_points), int(header_a.num_points), 1)
+        origin = np.empty(cap, dtype=np.uint32)
+        rc = L.spz_amd_refine_densify_open(stream_a.data_ptr(), stream_a.numel(), C.byref(header_a), stream_b.data_ptr(),
+                                           stream_b.numel(), C.byref(header_b), arr, len(views), C.byref(opts),
+                                           C.byref(dopts), device_index, C.byref(ctx), C.byref(out_bytes), history,
+                                           before, after, C.byref(skipped), ms, C.byref(bad), C.byref(n_out), h_rounds,
+                                           room, C.byref(n_rounds), origin.ctypes.data)
+        if rc == abi.OK:
+            num_points = int(n_out.value)
+            origin = origin[:num_points].copy()
+            rounds = [{k: int(getattr(r, k)) for k in ("iteration", "cloned", "split", "culled", "refused", "num_points")}
+                      for r in h_rounds[:min(room, n_rounds.value)]]
     if rc != abi.OK:
-        err = abi.SpzAmdError(rc, "spz_amd_refine_open" + (f" (view {bad.value})" if bad.value >= 0 else ""))
+        err = abi.SpzAmdError(rc, entry + (f" (view {bad.value})" if bad.value >= 0 else ""))
         err.view = bad.value
         raise err
     report = {"history": [history[i] for i in range(max(0, opts.iterations))],
               "before": [_metrics_dict(x) for x in before], "after": [_metrics_dict(x) for x in after],
-              "skipped": int(skipped.value), "ms": tuple(ms), "out_bytes": int(out_bytes.value)}
+              "skipped": int(skipped.value), "ms": tuple(ms), "out_bytes": int(out_bytes.value),
+              "num_points": num_points, "rounds": rounds}
+    if origin is not None:
+        report["origin"] = origin
     return RefineResult(ctx, out_bytes.value, dev, report)
 
 
@@ -1465,4 +1601,5 @@ def to_numpy(cloud_t):
 __all__ = ["encode", "decode", "encode_shard", "decode_shard", "decode_gather", "peek_header", "convert_coordinates",
            "select", "subset", "transform", "transform_packed", "merge_packed",
            "alloc_cloud", "image_loss", "adam_step", "refine_packed",
+           "densify_accumulate", "densify_plan", "densify_apply", "reset_opacity",
            "make_header", "to_device", "to_numpy", "SH_DIM"]

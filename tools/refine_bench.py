@@ -20,6 +20,13 @@ The C ABI enqueues a call's kernels together, so the kernels' own times come fro
                and the copy refined against the original over 8 orbit views of --width x --height for --iters
                iterations; wall clock of the tool, and its report's mean PSNR and SSIM before and after.
   --collect F... --out O   merge the JSON lines of several runs into one document: medians and ranges.
+  --densify    instead: the densify round (DESIGN §8 "Densify") at --points SH3 Gaussians with planted statistics (about
+               a fifth cloned, a fifth split, a few culled): spz_amd_densify_apply_device (one launch for the 18 arrays
+               of parameters and both moments) against torch.index_select over the same 18 arrays with the same parent
+               list, the route a Python user would otherwise take (it copies moments where apply writes zeros, and
+               leaves the children where the parents are); one whole round (plan, the read-back of the count, apply) by
+               the wall clock; and one refine iteration at the same size beside it.
+  --collect-densify F... --out O   the --densify lines of several sizes as one document (profiles/densify_bench.json).
 Prints one JSON line (--out: also writes it)."""
 import argparse
 import ctypes as C
@@ -251,6 +258,114 @@ def events(a):
     return out
 
 
+def densify(a):
+    import numpy as np
+    import torch
+    from spz_amd import abi, device as D
+    from spz_amd.synth import FIELDS, floats_per_point, make_cloud_clustered
+
+    dev = torch.device("cuda:0")
+    L = abi.load_library()
+    n, deg = a.points, 3
+    cloud = D.to_device(make_cloud_clustered(n, deg, 1234), dev)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(9)
+    m = {k: torch.empty_like(t).normal_(0.0, 0.1, generator=gen) for k, t in cloud.items()}
+    v = {k: torch.empty_like(t).uniform_(0.0, 0.01, generator=gen) for k, t in cloud.items()}
+    # planted statistics: g uniform in [0, 2.5 thr), so 60 % are candidates; the budget grants 40 % of n
+    lim = abi.densify_thresholds(abi.densify_options(interval=1, extent=1.0, grad_threshold=2.0 ** -12))
+    med = float(cloud["scales"].view(-1, 3).max(dim=1).values.median())
+    lim.log_dense = med  # half of the candidates split
+    denom = torch.randint(1, 5, (n,), generator=gen, device=dev, dtype=torch.int32)
+    accum = torch.empty(n, device=dev).uniform_(0.0, 2.5 * 2.0 ** -12, generator=gen) * denom
+    max_points = int(1.4 * n)
+    st = torch.cuda.current_stream(dev)
+    sp = C.c_void_p(st.cuda_stream)
+    plan = D.densify_plan(accum, denom, cloud["scales"], cloud["alphas"], lim, max_points)
+    n_new = plan["num_points"]
+    parent, child = plan["parent"].contiguous(), plan["child"].contiguous()
+    dst = [D.alloc_cloud(n_new, deg, dev) for _ in range(3)]
+    src_p = [D._ptrs(c, deg, n, dev) for c in (cloud, m, v)]
+    dst_p = [D._ptrs(c, deg, n_new, dev) for c in dst]
+    apply_ms, select_ms, round_ms = [], [], []
+    for r in range(a.reps + 1):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        abi.check(L.spz_amd_densify_apply_device(C.byref(src_p[0]), C.byref(src_p[1]), C.byref(src_p[2]),
+                                                 C.byref(dst_p[0]), C.byref(dst_p[1]), C.byref(dst_p[2]),
+                                                 parent.data_ptr(), child.data_ptr(), n, n_new, n_new, deg, 7, r, sp),
+                  "spz_amd_densify_apply_device")
+        e1.record(st)
+        torch.cuda.synchronize()
+        if r:
+            apply_ms.append(e0.elapsed_time(e1))
+    index = parent.to(torch.int64)
+    for r in range(a.reps + 1):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        for c, d in zip((cloud, m, v), dst):
+            for k in FIELDS:
+                w = floats_per_point(k, deg)
+                torch.index_select(c[k].view(-1, w), 0, index, out=d[k].view(-1, w))
+        e1.record(st)
+        torch.cuda.synchronize()
+        if r:
+            select_ms.append(e0.elapsed_time(e1))
+    # one whole round by the wall clock: plan (with its read-back of the counts), then apply
+    cap = min(2 * n, max(max_points, n))
+    action = torch.empty(n, dtype=torch.uint8, device=dev)
+    par = torch.empty(cap, dtype=torch.int32, device=dev)
+    chi = torch.empty(cap, dtype=torch.uint8, device=dev)
+    counts = torch.empty(5, dtype=torch.int64, device=dev)
+    ws = torch.empty(int(L.spz_amd_densify_plan_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+    h = (C.c_uint64 * 5)()
+    for r in range(a.reps + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        abi.check(L.spz_amd_densify_plan_host(accum.data_ptr(), denom.data_ptr(), cloud["scales"].data_ptr(),
+                                              cloud["alphas"].data_ptr(), n, C.byref(lim), max_points, cap,
+                                              action.data_ptr(), par.data_ptr(), chi.data_ptr(), counts.data_ptr(),
+                                              ws.data_ptr(), h, sp), "spz_amd_densify_plan_host")
+        abi.check(L.spz_amd_densify_apply_device(C.byref(src_p[0]), C.byref(src_p[1]), C.byref(src_p[2]),
+                                                 C.byref(dst_p[0]), C.byref(dst_p[1]), C.byref(dst_p[2]), par.data_ptr(),
+                                                 chi.data_ptr(), n, int(h[0]), n_new, deg, 7, r, sp),
+                  "spz_amd_densify_apply_device")
+        torch.cuda.synchronize()
+        if r:
+            round_ms.append(1e3 * (time.perf_counter() - t0))
+    assert int(h[0]) == n_new
+    floats = sum(floats_per_point(k, deg) for k in FIELDS)
+    # every output float of the 18 arrays read and written: an upper bound, zeroed moments are not read
+    moved = 2 * 3 * 4 * floats * n_new
+    out = {"tool": "refine_bench", "mode": "densify", "points": n, "sh_degree": deg, "reps": a.reps,
+           "new_points": n_new, "cloned": plan["cloned"], "split": plan["split"], "culled": plan["culled"],
+           "refused": plan["refused"], "apply_ms": spread(apply_ms), "index_select_18_arrays_ms": spread(select_ms),
+           "apply_bytes_upper_bound": moved,
+           "apply_tb_per_s": spread([moved / (ms * 1e-3) / 1e12 for ms in apply_ms]),
+           "index_select_tb_per_s": spread([moved / (ms * 1e-3) / 1e12 for ms in select_ms]),
+           "index_select_over_apply": round(statistics.median(select_ms) / statistics.median(apply_ms), 3),
+           "round_wall_ms": spread(round_ms), "device": torch.cuda.get_device_name(0)}
+    del cloud, m, v, dst, accum, denom, parent, child, index, par, chi, ws, action
+    torch.cuda.empty_cache()
+    a.no_baseline = True
+    it = events(a)
+    out["iteration_ms"] = it["iteration_ms"]
+    out["iteration_view"] = [it["width"], it["height"]]
+    out["round_over_iteration"] = round(out["round_wall_ms"]["median"] / it["iteration_ms"]["median"], 3)
+    return out
+
+
+def collect_densify(paths):
+    sizes = {}
+    for p in paths:
+        for line in open(p):
+            line = line.strip()
+            if line.startswith("{") and json.loads(line).get("mode") == "densify":
+                d = json.loads(line)
+                sizes[str(d["points"])] = {k: v for k, v in d.items() if k not in ("tool", "mode", "points")}
+    return {"tool": "refine_bench", "mode": "densify", "copy_ceiling_tb_per_s": COPY_CEILING_TBS, "sizes": sizes}
+
+
 def e2e(a):
     import spz_amd.spz as spz
     from spz_amd.synth import make_cloud_clustered
@@ -302,6 +417,8 @@ def main():
     ap.add_argument("--tolerance", action="store_true")
     ap.add_argument("--e2e", action="store_true")
     ap.add_argument("--collect", nargs="+", default=None)
+    ap.add_argument("--densify", action="store_true")
+    ap.add_argument("--collect-densify", nargs="+", default=None)
     a = ap.parse_args()
     if a.trace:
         out = trace_summary(a.trace)
@@ -312,6 +429,10 @@ def main():
         out = e2e(a)
     elif a.collect:
         out = collect(a.collect)
+    elif a.collect_densify:
+        out = collect_densify(a.collect_densify)
+    elif a.densify:
+        out = densify(a)
     else:
         out = events(a)
     line = json.dumps(out)
