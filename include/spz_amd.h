@@ -1180,6 +1180,116 @@ int spz_amd_refine_densify_open(const uint8_t *d_stream_a, size_t size_a, const 
                                 spz_amd_densify_round *h_rounds, int rounds_capacity, int *h_num_rounds,
                                 uint32_t *h_origin);
 
+/* ---- render view backward: the gradient of one view to its camera (spz_render_view_backward.hip; DESIGN §8
+ *      "Locate").  The reference has no counterpart.  Given the n x 9 record gradients of a view (mean 2, conic 3,
+ *      opacity 1, rgb 3, as "render backward" forms them), it produces the gradient of the same scalar loss to the 12
+ *      entries of world_to_camera = [R | t], taken as independent: it is not projected onto the rotation group, just as
+ *      the raw quaternion gets its gradient.  Intrinsics get none.
+ *
+ *      It is the exact derivative of the forward as "render" words it, with the discrete decisions "render backward"
+ *      holds constant: visibility, radius, tile rectangle and depth order; the three blend tests; the clamp of x/z and
+ *      y/z in J, which passes nothing through the clamped quotient; max(0, rgb), which passes nothing where it clamps;
+ *      the antialiased factor, which is zero where det_before <= 0.  The camera enters three times and all three are
+ *      differentiated: p_c = R p + t, which feeds the mean and J; R in Sigma' = J R Sigma R^T J^T; and the camera
+ *      centre c = -R^T t in the view direction normalize(p - c) of the sh bands.  The record's depth carries no
+ *      gradient (the colour image does not read it).  An invisible Gaussian contributes exactly 0.
+ *      Arithmetic.  One lane per Gaussian runs the chain in f64 from the f32 inputs and forms its 12 contributions.
+ *      They are summed without atomics: over the wave by a fixed tree of 64-lane shuffles, over the workgroup's waves
+ *      through LDS in wave order, one row of 12 doubles per workgroup; a second launch of one workgroup adds the rows
+ *      in a fixed order.  Given the same record gradients a run repeats its bits.  The record gradients come from f32
+ *      atomic adds, so the whole chain from G need not.
+ *
+ *      render_records_backward_device: the blend half of render_backward_device on its own, for a caller that needs
+ *      no gradients to the six cloud arrays.  d_render_workspace exactly as render_finish_device left it; d_grad_image:
+ *      G, height x width x 4 floats; d_record_grads: n x 9 floats out (written, not accumulated into; may be NULL iff
+ *      num_points == 0).  *d_status = 0, or 1 when the total is above max_entries: then nothing is written.
+ *      render_view_backward_workspace_bytes (host only): device memory for the workgroups' rows.
+ *      render_view_backward_device: d_cloud, num_points, sh_degree, antialiased, params and max_entries as given to
+ *      prepare_cloud_device and render_finish_device; d_record_grads: n x 9 floats in; d_render_workspace as
+ *      render_finish_device left it (the records and the total are read; nothing in it is written).  d_view_grad
+ *      (device memory, 8-aligned): 12 doubles out, row-major 3 x 4.  *d_status (device memory, uint32) = 0, or 1 when
+ *      the total is above max_entries: then d_view_grad is not written.  num_points == 0 or nothing visible: twelve
+ *      zeros.
+ *      Both check their arguments on the host before any launch (a bad one: SPZ_AMD_ERR_INVALID_ARG; more than 2^31 - 1
+ *      points: SPZ_AMD_ERR_TOO_MANY_POINTS; no device: SPZ_AMD_ERR_NO_DEVICE), enqueue on hip_stream and do not
+ *      synchronise. */
+int spz_amd_render_records_backward_device(uint64_t num_points, const spz_amd_render_params *params,
+                                           uint64_t max_entries, const float *d_grad_image, float *d_record_grads,
+                                           uint32_t *d_status, const void *d_render_workspace, void *hip_stream);
+uint64_t spz_amd_render_view_backward_workspace_bytes(uint64_t num_points);
+int spz_amd_render_view_backward_device(const spz_amd_cloud_in *d_cloud, uint64_t num_points, int sh_degree,
+                                        int antialiased, const spz_amd_render_params *params, uint64_t max_entries,
+                                        const float *d_record_grads, double *d_view_grad, uint32_t *d_status,
+                                        const void *d_render_workspace, void *d_workspace, void *hip_stream);
+
+/* ---- locate: the pose of a camera in a scene, fitted to a picture (spz_locate.hip; DESIGN §8 "Locate").  The
+ *      reference has no counterpart.  Given a scene, a view with a rough pose and the picture taken from the true one,
+ *      it moves the pose down the gradient of the 3DGS loss ("image loss") of the scene's render against the picture.
+ *      No search: the initial pose must be close enough for the two images to overlap.
+ *      options: iterations >= 0; levels 1..SPZ_AMD_LOCATE_MAX_LEVELS; lambda_dssim in [0, 1]; lr_rotation (radians) and
+ *      lr_translation (scene units) >= 0; lr_final_factor in (0, 1]; beta1, beta2 in [0, 1); eps >= 0 (locate_check,
+ *      host only; locate_default_options: 300 iterations, 1 level, lambda 0.2, both step sizes 2e-3 — the translation's
+ *      for a camera at unit distance, the layers above scale it — final factor 0.1, 0.9, 0.999, 1e-15).
+ *      target: height x width x C float32 in device memory, C in {3, 4}, the size of params.
+ *      Run.  The "before" metrics (image_metrics_device) of the input's render (the packed path for a stream) at the
+ *      initial pose.  A stream is decoded once to a float cloud in params.coord.  One iteration: render_prepare_cloud_
+ *      device, the total read back, the workspace grown (grow-only), render_finish_device; image_loss_device against
+ *      the target; render_records_backward_device; render_view_backward_device; the 12 doubles read back.  A total
+ *      above 2^31 - 1: SPZ_AMD_ERR_CAPACITY.
+ *      Update, in f64 on the host; the pose is kept in f64 and rounded to f32 only into the params.  With G = [G_R |
+ *      G_t] and A = G_R R^T + G_t t^T, the gradient to the twist (w, v) of L(Exp(w) R, Exp(w) t + v) at 0 is g_w = (A21 -
+ *      A12, A02 - A20, A10 - A01), g_v = G_t (locate_twist_gradient, host only).  Adam over the six values with bias
+ *      correction, t = i + 1: m = beta1 m + (1 - beta1) g; v = beta2 v + (1 - beta2) g^2; d = -lr f_i (m / (1 -
+ *      beta1^t)) / (sqrt(v / (1 - beta2^t)) + eps), 0 where m is 0; lr = lr_rotation for w and lr_translation for v;
+ *      f_i = lr_final_factor^(i / iterations).  Then R <- Exp(d_w) R, t <- Exp(d_w) t + d_v, Exp by Rodrigues' formula,
+ *      below |d_w| = 1e-4 with the series 1 - x/6 and 1/2 - x/24 in x = |d_w|^2 (locate_pose_step, host only: one
+ *      update of pose, m and v in place for iteration i in 0..iterations - 1).  A gradient with a non-finite entry stops
+ *      the run at the last pose; *h_iterations says how many steps were taken.
+ *      Coarse to fine.  Level k runs from levels - 1 down to 0 at (width / 2^k) x (height / 2^k) with fx, fy, cx, cy
+ *      divided by 2^k (locate_level_params, host only): the exact pinhole of the box-averaged image under m = f x/z + c -
+ *      0.5.  Its target is the k-fold 2 x 2 box mean of the target (image_halve_device: f32, ((top left + top right) +
+ *      (bottom left + bottom right)) / 4, channels kept, width and height even).  Width and height must be divisible
+ *      by 2^(levels - 1): otherwise SPZ_AMD_ERR_INVALID_ARG.  iterations / levels iterations per level, the remainder
+ *      to level 0; Adam's state and f_i run through all levels.
+ *      The host forms run on `device` on a stream of their own and block; every argument is checked before the first
+ *      HIP call.  locate_host: a packed stream; locate_image_host: the same with the target in host memory, uploaded
+ *      once; locate_cloud_host: a float cloud in device memory, rendered as it is (params.coord is ignored).  h_world_to_camera: the final pose, 12 floats.  h_history (iterations doubles; may be NULL iff
+ *      iterations == 0): [i] = L before step i, 0 from *h_iterations on.  h_before, h_after (may be NULL): the metrics
+ *      at the initial and the final pose; equal when no step was taken.  h_ms (may be NULL): [0] wall-clock
+ *      milliseconds of the "before" metrics, [1] of the iterations, [2] of the "after" metrics.
+ *      The record gradients come from f32 atomic adds, so a run need not repeat its bits; h_history[0] and h_before
+ *      do. */
+enum { SPZ_AMD_LOCATE_MAX_LEVELS = 8 };
+typedef struct {
+  int32_t iterations;
+  int32_t levels;
+  double lambda_dssim;
+  double lr_rotation, lr_translation, lr_final_factor;
+  double beta1, beta2, eps;
+} spz_amd_locate_options;
+int spz_amd_locate_default_options(spz_amd_locate_options *options);
+int spz_amd_locate_check(const spz_amd_locate_options *options);
+int spz_amd_locate_level_params(const spz_amd_render_params *params, int level, spz_amd_render_params *out);
+int spz_amd_locate_twist_gradient(const double pose[12], const double view_grad[12], double twist_grad[6]);
+int spz_amd_locate_pose_step(const spz_amd_locate_options *options, int iteration, const double twist_grad[6],
+                             double m[6], double v[6], double pose[12]);
+int spz_amd_image_halve_device(const float *d_in, int channels, int width, int height, float *d_out, void *hip_stream);
+int spz_amd_locate_host(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr,
+                        const spz_amd_render_params *params, const float *d_target, int channels,
+                        const spz_amd_locate_options *options, int device, float *h_world_to_camera, double *h_history,
+                        spz_amd_image_metrics *h_before, spz_amd_image_metrics *h_after, int32_t *h_iterations,
+                        float *h_ms);
+int spz_amd_locate_image_host(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr,
+                              const spz_amd_render_params *params, const float *h_target, int channels,
+                              const spz_amd_locate_options *options, int device, float *h_world_to_camera,
+                              double *h_history, spz_amd_image_metrics *h_before, spz_amd_image_metrics *h_after,
+                              int32_t *h_iterations, float *h_ms);
+int spz_amd_locate_cloud_host(const spz_amd_cloud_in *d_cloud, uint64_t num_points, int sh_degree, int antialiased,
+                              const spz_amd_render_params *params, const float *d_target, int channels,
+                              const spz_amd_locate_options *options, int device, float *h_world_to_camera,
+                              double *h_history, spz_amd_image_metrics *h_before, spz_amd_image_metrics *h_after,
+                              int32_t *h_iterations, float *h_ms);
+
 /* ---- device buffers for a resident cloud, placed for speed (spz_place.hip).  Whether an sh3 decode runs
  *      at 0.46 ms or at 0.55 ms is decided by whether the sh float array shares a physical region of HBM with the other
  *      arrays of the launch; that cannot be asked for, but it shows in one launch.  alloc: the five small arrays (and a

@@ -608,6 +608,49 @@ bool refineSpz(const std::vector<uint8_t> &data, const std::vector<uint8_t> &tar
                std::vector<uint8_t> *out, RefineReport *report = nullptr);
 bool refineSpz(const std::string &inputFilename, const std::string &targetFilename, const std::string &outputFilename,
                const RefineOptions &options, RefineReport *report = nullptr);
+// Locate (DESIGN §8 "Locate"): the pose of the camera that took a picture of the scene in a file, from a rough guess
+// (include/spz_amd.h "render view backward" and "locate" state the contract).  initial: the view with the rough pose, in
+// the `coord` frame; image: height x width x channels float32 (channels 3 or 4), the picture, in the render's
+// convention (rows top to bottom, values in [0, 1]).  `iterations` steps of Adam on the six values of a twist move the
+// pose down the gradient of the 3DGS loss of the file's render against the picture; with levels > 1 the first steps run
+// on 2 x 2 box means of the picture (width and height divisible by 2^(levels - 1)).  rotationLr: radians per step.
+// translationLr unset: rotationLr times the distance from the initial camera centre to the centre of boundingSphere of
+// the file's positions, and at least rotationLr times that sphere's radius.  The report's view is `initial` with its
+// matrix replaced.  No search: the guess must be close enough for the two images to overlap.  The backward sums with
+// f32 atomics, so two runs may differ in the last bits.  false + one "[SPZ ERROR] locateSpz: …" line on a bad argument
+// (lastDeviceStatus() = SPZ_AMD_ERR_INVALID_ARG), an input that does not load, or a device failure.
+// SPZ_AMD_LOCATE_TIMING=1 prints the stages' times.
+struct LocateOptions {
+  CoordinateSystem coord = CoordinateSystem::UNSPECIFIED;
+  float nearPlane = 0.2f;
+  std::array<float, 3> background = {0.0f, 0.0f, 0.0f};
+  int maxShDegree = 3;
+  int iterations = 300;
+  int levels = 1;
+  double lambdaDssim = 0.2;
+  double rotationLr = 2e-3;
+  std::optional<double> translationLr;
+  double lrFinalFactor = 0.1;
+  double beta1 = 0.9, beta2 = 0.999, eps = 1e-15;
+};
+struct LocateReport {
+  PruneOptions::View view;             // the initial view at the fitted pose
+  std::vector<double> history;         // the loss before each step taken
+  ImageMetrics before, after;          // the file's render against the picture at the initial and the fitted pose
+  int iterations = 0;                  // steps taken (fewer than asked for: a gradient was not finite)
+  double translationLr = 0.0;          // the rate used
+  float ms[3] = {0.0f, 0.0f, 0.0f};    // before, iterations, after
+};
+bool locateSpz(const uint8_t *data, int32_t size, const PruneOptions::View &initial, const float *image, int channels,
+               const LocateOptions &options, LocateReport *report);
+bool locateSpz(const std::vector<uint8_t> &data, const PruneOptions::View &initial, const float *image, int channels,
+               const LocateOptions &options, LocateReport *report);
+bool locateSpz(const std::string &filename, const PruneOptions::View &initial, const float *image, int channels,
+               const LocateOptions &options, LocateReport *report);
+// A picture as spz_render writes it, as locateSpz takes it: a binary PPM ("P6", maxval 255: v / 255) or a colour PFM
+// ("PF", either byte order, rows bottom to top in the file), three channels, rows top to bottom in *pixels.
+// std::invalid_argument naming the file when it does not open or is neither.
+void loadImageFile(const std::string &filename, std::vector<float> *pixels, int *width, int *height);
 // Status (spz_amd.h codes) of the last device call made by this thread; 0 = ok.
 int lastDeviceStatus();
 void setLastDeviceStatus(int status);

@@ -95,6 +95,11 @@ EXPORTS = (
     "spz_amd_densify_accumulate_device", "spz_amd_densify_plan_workspace_bytes", "spz_amd_densify_plan_device",
     "spz_amd_densify_plan_host", "spz_amd_densify_apply_device", "spz_amd_densify_reset_opacity_device",
     "spz_amd_refine_densify_open",
+    "spz_amd_render_records_backward_device", "spz_amd_render_view_backward_workspace_bytes",
+    "spz_amd_render_view_backward_device",
+    "spz_amd_locate_default_options", "spz_amd_locate_check", "spz_amd_locate_level_params",
+    "spz_amd_locate_twist_gradient", "spz_amd_locate_pose_step", "spz_amd_image_halve_device", "spz_amd_locate_host",
+    "spz_amd_locate_image_host", "spz_amd_locate_cloud_host",
 )
 
 RCCL_UNIQUE_ID_BYTES = 128
@@ -196,6 +201,16 @@ class RefineOptions(C.Structure):
     """spz_amd_refine_options (include/spz_amd.h "refine")."""
     _fields_ = [("iterations", C.c_int32), ("train_mask", C.c_uint32), ("lambda_dssim", C.c_double),
                 ("lr", C.c_double * 6), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
+
+
+LOCATE_MAX_LEVELS = 8
+
+
+class LocateOptions(C.Structure):
+    """spz_amd_locate_options (include/spz_amd.h "locate")."""
+    _fields_ = [("iterations", C.c_int32), ("levels", C.c_int32), ("lambda_dssim", C.c_double),
+                ("lr_rotation", C.c_double), ("lr_translation", C.c_double), ("lr_final_factor", C.c_double),
+                ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
 
 
 class DensifyOptions(C.Structure):
@@ -681,6 +696,35 @@ def bind(L):
                                               C.POINTER(ImageMetrics), C.POINTER(ImageMetrics), C.POINTER(u64), vp,
                                               C.POINTER(C.c_int32), C.POINTER(u64), C.POINTER(DensifyRound), i32,
                                               C.POINTER(C.c_int32), vp]
+    L.spz_amd_render_records_backward_device.restype = i32
+    L.spz_amd_render_records_backward_device.argtypes = [u64, C.POINTER(RenderParams), u64, vp, vp, vp, vp, vp]
+    L.spz_amd_render_view_backward_workspace_bytes.restype = u64
+    L.spz_amd_render_view_backward_workspace_bytes.argtypes = [u64]
+    L.spz_amd_render_view_backward_device.restype = i32
+    L.spz_amd_render_view_backward_device.argtypes = [C.POINTER(CloudPtrs), u64, i32, i32, C.POINTER(RenderParams), u64,
+                                                      vp, vp, vp, vp, vp, vp]
+    L.spz_amd_locate_default_options.restype = i32
+    L.spz_amd_locate_default_options.argtypes = [C.POINTER(LocateOptions)]
+    L.spz_amd_locate_check.restype = i32
+    L.spz_amd_locate_check.argtypes = [C.POINTER(LocateOptions)]
+    L.spz_amd_locate_level_params.restype = i32
+    L.spz_amd_locate_level_params.argtypes = [C.POINTER(RenderParams), i32, C.POINTER(RenderParams)]
+    L.spz_amd_locate_twist_gradient.restype = i32
+    L.spz_amd_locate_twist_gradient.argtypes = [C.POINTER(C.c_double)] * 3
+    L.spz_amd_locate_pose_step.restype = i32
+    L.spz_amd_locate_pose_step.argtypes = [C.POINTER(LocateOptions), i32] + [C.POINTER(C.c_double)] * 4
+    L.spz_amd_image_halve_device.restype = i32
+    L.spz_amd_image_halve_device.argtypes = [vp, i32, i32, i32, vp, vp]
+    L.spz_amd_locate_host.restype = i32
+    L.spz_amd_locate_host.argtypes = [vp, sz, C.POINTER(Header), C.POINTER(RenderParams), vp, i32,
+                                      C.POINTER(LocateOptions), i32, vp, vp, C.POINTER(ImageMetrics),
+                                      C.POINTER(ImageMetrics), C.POINTER(C.c_int32), vp]
+    L.spz_amd_locate_image_host.restype = i32
+    L.spz_amd_locate_image_host.argtypes = L.spz_amd_locate_host.argtypes
+    L.spz_amd_locate_cloud_host.restype = i32
+    L.spz_amd_locate_cloud_host.argtypes = [C.POINTER(CloudPtrs), u64, i32, i32, C.POINTER(RenderParams), vp, i32,
+                                            C.POINTER(LocateOptions), i32, vp, vp, C.POINTER(ImageMetrics),
+                                            C.POINTER(ImageMetrics), C.POINTER(C.c_int32), vp]
     return L
 
 
@@ -816,6 +860,42 @@ def refine_options(iterations, *, lambda_dssim=None, lrs=None, beta1=None, beta2
     if train is not None:
         o.train_mask = train_mask(train)
     return o
+
+
+LOCATE_FIELDS = ("iterations", "levels", "lambda_dssim", "lr_rotation", "lr_translation", "lr_final_factor", "beta1",
+                 "beta2", "eps")
+
+
+def locate_options(**fields):
+    """spz_amd_locate_default_options with the given fields (LOCATE_FIELDS) replaced, checked by spz_amd_locate_check:
+    ValueError on an unknown field or a refused value."""
+    L = load_library()
+    o = LocateOptions()
+    check(L.spz_amd_locate_default_options(C.byref(o)), "spz_amd_locate_default_options")
+    for k, x in fields.items():
+        if k not in LOCATE_FIELDS:
+            raise ValueError(f"locate: unknown option {k!r} (one of {', '.join(LOCATE_FIELDS)})")
+        if x is None:
+            continue
+        if k in ("iterations", "levels"):
+            if isinstance(x, bool) or not isinstance(x, int):
+                raise ValueError(f"{k} must be an int, got {x!r}")
+            setattr(o, k, x)
+        else:
+            setattr(o, k, float(x))
+    if L.spz_amd_locate_check(C.byref(o)) != OK:
+        raise ValueError("bad locate options: iterations >= 0, levels 1..8, lambda_dssim in [0, 1], step sizes >= 0, "
+                         "lr_final_factor in (0, 1], beta1, beta2 in [0, 1), eps >= 0")
+    return o
+
+
+def locate_level_params(params, level):
+    """The view of coarse-to-fine level `level` (spz_amd_locate_level_params): the size and fx, fy, cx, cy divided by
+    2^level.  ValueError when the size is not divisible."""
+    out = RenderParams()
+    if load_library().spz_amd_locate_level_params(C.byref(params), int(level), C.byref(out)) != OK:
+        raise ValueError(f"level {level}: width and height must be divisible by 2^level (level 0..7)")
+    return out
 
 
 def densify_options(options=None, **fields):

@@ -2,10 +2,10 @@
 // MI355X drop-in layer: ply_to_spz, spz_to_ply, spz_info; and spz_filter (spz::filterSpz),
 // spz_transform (spz::transformSpz), spz_merge (spz::mergeSpz), spz_sort (spz::sortSpz), spz_decimate
 // (spz::decimateSpz), spz_tile (spz::tileSpz), spz_clean (spz::cleanSpz), spz_render (spz::renderSpz), spz_prune
-// (spz::pruneSpz), spz_compare (spz::compareSpz), spz_align (spz::alignSpz) and spz_refine (spz::refineSpz), which
-// have no counterpart in the reference.  One binary, dispatched on argv[0] (the Makefile installs it under the fifteen
-// names) or on a first argument naming the tool.
-// spz_refine exits 0 on success and 1 on a failure.
+// (spz::pruneSpz), spz_compare (spz::compareSpz), spz_align (spz::alignSpz), spz_refine (spz::refineSpz) and
+// spz_locate (spz::locateSpz), which have no counterpart in the reference.  One binary, dispatched on argv[0] (the
+// Makefile installs it under the sixteen names) or on a first argument naming the tool.
+// spz_refine and spz_locate exit 0 on success and 1 on a failure.
 // spz_align exits 0 on success, 1 on a failure and 2 when the run ends degenerate; its --output is written by
 // transformSpz, at --fractional-bits (12 unless given, as for spz_transform).
 // spz_compare exits 0 on success, 1 on a failure and 2 when a view misses --min-psnr or --min-ssim.
@@ -812,6 +812,98 @@ int spzAlign(int argc, char **argv) {
   return 0;
 }
 
+const char *kLocateUsage =
+    "Usage: spz_locate <scene.spz> --views FILE --images a.pfm|a.ppm [b ...] [--out FILE] [--iterations N] "
+    "[--lr-rotation R] [--lr-translation T] [--lambda L] [--levels K] [--coord " SPZ_COORD_NAMES "] "
+    "[--background r g b] [--max-sh-degree D] [--near Z]";
+
+// View i of the views file is fitted to image i.  Writes the fitted views in the views file's own spelling (to --out,
+// or to stdout), so they feed spz_prune, spz_compare and spz_refine --views: per view a '#' comment line with its PSNR
+// before and after, then the view's line.  With --out the PSNR lines also go to stdout.
+int spzLocate(int argc, char **argv) {
+  Args a(argc, argv, kLocateUsage);
+  if (!a.files(1)) return a.usage();
+  spz::LocateOptions o;
+  std::string viewsFile, outFile;
+  std::vector<std::string> images;
+  bool inImages = false;
+  while (a.next()) {
+    if (inImages && a.arg()[0] != '-') {  // the rest of --images' list
+      images.push_back(a.arg());
+      continue;
+    }
+    inImages = false;
+    bool good = false;
+    if (a.is("--views")) good = a.text(&viewsFile);
+    else if (a.is("--images")) good = inImages = a.text(&images.emplace_back());
+    else if (a.is("--out")) good = a.text(&outFile);
+    else if (a.is("--iterations")) good = a.integer(&o.iterations, 0, 0x7fffffff);
+    else if (a.is("--lr-rotation")) good = a.real(&o.rotationLr) && std::isfinite(o.rotationLr) && o.rotationLr >= 0.0;
+    else if (a.is("--lr-translation")) {
+      good = a.real(&o.translationLr.emplace()) && std::isfinite(*o.translationLr) && *o.translationLr >= 0.0;
+    }
+    else if (a.is("--lambda")) good = a.real(&o.lambdaDssim) && o.lambdaDssim >= 0.0 && o.lambdaDssim <= 1.0;
+    else if (a.is("--levels")) good = a.integer(&o.levels, 1, 8);
+    else if (a.is("--coord")) good = a.coord(&o.coord);
+    else if (a.is("--background")) good = a.real(o.background.data(), 3) && allFinite(o.background.data(), 3);
+    else if (a.is("--max-sh-degree")) good = a.integer(&o.maxShDegree, 0, 3);
+    else if (a.is("--near")) good = a.real(&o.nearPlane) && std::isfinite(o.nearPlane) && o.nearPlane > 0.0f;
+    if (!good) return a.usage();
+  }
+  if (!a.given("--views") || !a.given("--images")) return a.usage();
+  std::vector<spz::PruneOptions::View> views;
+  try {
+    views = spz::loadViewsFile(viewsFile);
+  } catch (const std::invalid_argument &e) {
+    std::cerr << "[SPZ ERROR] spz_locate: " << e.what() << std::endl;
+    return 1;
+  }
+  if (views.size() != images.size()) {
+    std::cerr << "[SPZ ERROR] spz_locate: " << views.size() << " views but " << images.size() << " images" << std::endl;
+    return 1;
+  }
+  std::vector<std::string> lines, notes;
+  for (size_t v = 0; v < views.size(); ++v) {
+    std::vector<float> pixels;
+    int w = 0, h = 0;
+    try {
+      spz::loadImageFile(images[v], &pixels, &w, &h);
+    } catch (const std::invalid_argument &e) {
+      std::cerr << "[SPZ ERROR] spz_locate: " << e.what() << std::endl;
+      return 1;
+    }
+    if (w != views[v].width || h != views[v].height) {
+      std::cerr << "[SPZ ERROR] spz_locate: view " << v << " is " << views[v].width << " x " << views[v].height << " but "
+                << images[v] << " is " << w << " x " << h << std::endl;
+      return 1;
+    }
+    spz::LocateReport r;
+    if (!spz::locateSpz(std::string(argv[1]), views[v], pixels.data(), 3, o, &r)) return 1;
+    char buf[1024];
+    const std::array<float, 12> &m = r.view.worldToCamera;
+    std::snprintf(buf, sizeof(buf), "%d %d %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g",
+                  r.view.width, r.view.height, r.view.fx, r.view.fy, r.view.cx, r.view.cy, m[0], m[1], m[2], m[3], m[4], m[5],
+                  m[6], m[7], m[8], m[9], m[10], m[11]);
+    lines.push_back(buf);
+    std::snprintf(buf, sizeof(buf), "view %zu psnr %.17g -> %.17g after %d iterations", v, r.before.psnr, r.after.psnr,
+                  r.iterations);
+    notes.push_back(buf);
+  }
+  if (!outFile.empty()) {
+    std::ofstream out(outFile);
+    for (size_t v = 0; v < lines.size(); ++v) out << "# " << notes[v] << "\n" << lines[v] << "\n";
+    out.flush();
+    if (!out) {
+      std::cerr << "[SPZ ERROR] spz_locate: unable to write " << outFile << std::endl;
+      return 1;
+    }
+    for (const std::string &n : notes) std::cout << n << std::endl;
+  } else {
+    for (size_t v = 0; v < lines.size(); ++v) std::cout << "# " << notes[v] << "\n" << lines[v] << std::endl;
+  }
+  return 0;
+}
+
 const struct {
   const char *name;
   int (*run)(int, char **);
@@ -819,7 +911,8 @@ const struct {
               {"spz_filter", spzFilter},    {"spz_transform", spzTransform},  {"spz_merge", spzMerge},
               {"spz_sort", spzSort},        {"spz_decimate", spzDecimate},    {"spz_clean", spzClean},
               {"spz_render", spzRender},    {"spz_prune", spzPrune},          {"spz_compare", spzCompare},
-              {"spz_tile", spzTile},        {"spz_align", spzAlign},          {"spz_refine", spzRefine}};
+              {"spz_tile", spzTile},        {"spz_align", spzAlign},          {"spz_refine", spzRefine},
+              {"spz_locate", spzLocate}};
 
 int dispatch(const std::string &tool, int argc, char **argv) {
   for (const auto &t : kTools) {

@@ -16,6 +16,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cctype>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -3062,6 +3063,183 @@ bool refineSpz(const std::string &inputFilename, const std::string &targetFilena
   }
   if (report) *report = std::move(rep);
   return true;
+}
+
+// ---- locate ------------------------------------------------------------------------------------------------------
+namespace {
+// The initial view as render params, and the options but the translation's rate as the C ABI's.
+bool locateOptionsOk(const PruneOptions::View &initial, const float *image, int channels, const LocateOptions &o,
+                     spz_amd_render_params *p, spz_amd_locate_options *c) {
+  const char *who = "locateSpz";
+  const int invalid = SPZ_AMD_ERR_INVALID_ARG;
+  if (image == nullptr) return opRejected(who, invalid, "no image");
+  if (channels != 3 && channels != 4) return opRejected(who, invalid, "channels %d: give 3 or 4", channels);
+  if (o.iterations < 0) return opRejected(who, invalid, "iterations %d is negative", o.iterations);
+  if (o.levels < 1 || o.levels > SPZ_AMD_LOCATE_MAX_LEVELS) {
+    return opRejected(who, invalid, "levels %d is outside 1..%d", o.levels, SPZ_AMD_LOCATE_MAX_LEVELS);
+  }
+  if (!(o.lambdaDssim >= 0.0 && o.lambdaDssim <= 1.0)) return opRejected(who, invalid, "lambdaDssim must be in [0, 1]");
+  spz_amd_locate_default_options(c);
+  c->iterations = o.iterations;
+  c->levels = o.levels;
+  c->lambda_dssim = o.lambdaDssim;
+  c->lr_rotation = o.rotationLr;
+  c->lr_translation = o.translationLr ? *o.translationLr : 0.0;
+  c->lr_final_factor = o.lrFinalFactor;
+  c->beta1 = o.beta1;
+  c->beta2 = o.beta2;
+  c->eps = o.eps;
+  if (spz_amd_locate_check(c) != SPZ_AMD_OK) {
+    return opRejected(who, invalid, "step sizes must be finite and >= 0, lrFinalFactor in (0, 1], beta1 and beta2 in "
+                      "[0, 1), eps finite and >= 0");
+  }
+  if (!viewParams(who, "", initial, {o.nearPlane, o.coord, &o.background, o.maxShDegree, ", maxShDegree 0..3, coord valid"},
+                  p)) {
+    return false;
+  }
+  const int f = 1 << (o.levels - 1);
+  if (initial.width % f != 0 || initial.height % f != 0) {
+    return opRejected(who, invalid, "image size %d x %d is not divisible by %d (levels %d)", initial.width, initial.height,
+                      f, o.levels);
+  }
+  return true;
+}
+}  // namespace
+
+bool locateSpz(const uint8_t *data, int32_t size, const PruneOptions::View &initial, const float *image, int channels,
+               const LocateOptions &o, LocateReport *report) {
+  const char *who = "locateSpz";
+  g_last_status = SPZ_AMD_OK;
+  if (report == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no report");
+  *report = LocateReport{};
+  spz_amd_render_params p;
+  spz_amd_locate_options c;
+  if (!locateOptionsOk(initial, image, channels, o, &p, &c)) return false;
+  Laps laps(who, "SPZ_AMD_LOCATE_TIMING");
+  DevicePackedGaussians d;
+  if (!loadInput(who, data, size, &d)) return false;
+  laps.lap("inflate");
+  if (!o.translationLr) {  // a step of the rotation's size, seen from the scene's centre
+    UnpackOptions u;
+    u.to = o.coord;
+    const GaussianCloud g = d.unpack(u);
+    std::array<float, 3> centre = {0.0f, 0.0f, 0.0f};
+    float radius = 1.0f;
+    if (!boundingSphere(g.positions, &centre, &radius)) radius = 1.0f;
+    const float *m = p.world_to_camera;
+    double dist2 = 0.0;
+    for (int k = 0; k < 3; ++k) {  // the camera centre is -R^T t
+      const double eye = -(static_cast<double>(m[k]) * m[3] + static_cast<double>(m[4 + k]) * m[7] +
+                           static_cast<double>(m[8 + k]) * m[11]);
+      dist2 += (eye - centre[static_cast<size_t>(k)]) * (eye - centre[static_cast<size_t>(k)]);
+    }
+    c.lr_translation = o.rotationLr * std::max(std::sqrt(dist2), static_cast<double>(radius));
+    laps.lap("extent");
+  }
+  const spz_amd_header h = headerOf(d);
+  std::vector<double> history(static_cast<size_t>(o.iterations) + 1);
+  spz_amd_image_metrics before, after;
+  std::array<float, 12> pose{};
+  int32_t ran = 0;
+  float ms[3] = {0.0f, 0.0f, 0.0f};
+  const int rc = spz_amd_locate_image_host(d.stream, d.streamBytes, &h, &p, image, channels, &c, d.device, pose.data(),
+                                           history.data(), &before, &after, &ran, ms);
+  if (rc == SPZ_AMD_ERR_CAPACITY) return opRejected(who, rc, "more than 2^31 - 1 tile entries");
+  if (deviceFailed(rc, who)) return false;
+  laps.stage("before", ms[0]);
+  laps.stage("iterations", ms[1], (" (" + std::to_string(ran) + ")").c_str());
+  laps.stage("after", ms[2]);
+  laps.lap("locate");
+  report->view = initial;
+  report->view.worldToCamera = pose;
+  history.resize(static_cast<size_t>(ran));
+  report->history.swap(history);
+  report->before = toMetrics(before);
+  report->after = toMetrics(after);
+  report->iterations = ran;
+  report->translationLr = c.lr_translation;
+  for (int k = 0; k < 3; ++k) report->ms[k] = ms[k];
+  return true;
+}
+
+bool locateSpz(const std::vector<uint8_t> &data, const PruneOptions::View &initial, const float *image, int channels,
+               const LocateOptions &o, LocateReport *report) {
+  if (data.size() > static_cast<size_t>(INT32_MAX)) {
+    return opRejected("locateSpz", SPZ_AMD_ERR_INVALID_ARG, "the input is larger than 2 GiB");
+  }
+  return locateSpz(data.data(), static_cast<int32_t>(data.size()), initial, image, channels, o, report);
+}
+
+bool locateSpz(const std::string &filename, const PruneOptions::View &initial, const float *image, int channels,
+               const LocateOptions &o, LocateReport *report) {
+  const char *who = "locateSpz";
+  g_last_status = SPZ_AMD_OK;
+  if (report == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no report");
+  *report = LocateReport{};
+  spz_amd_render_params p;
+  spz_amd_locate_options c;
+  if (!locateOptionsOk(initial, image, channels, o, &p, &c)) return false;
+  std::vector<uint8_t> data;
+  if (!readInput(who, filename, &data)) return false;
+  return locateSpz(data, initial, image, channels, o, report);
+}
+
+void loadImageFile(const std::string &filename, std::vector<float> *pixels, int *width, int *height) {
+  auto bad = [&](const char *why) { return std::invalid_argument("loadImageFile: " + filename + ": " + why); };
+  if (pixels == nullptr || width == nullptr || height == nullptr) throw bad("no output");
+  std::ifstream f(filename, std::ios::binary);
+  if (!f) throw bad("unable to open");
+  // the header: a magic, then width, height and maxval (PPM) or scale (PFM), separated by white space, '#' comments
+  auto token = [&]() {
+    std::string t;
+    int ch = f.get();
+    while (ch != EOF) {
+      if (ch == '#') {
+        while (ch != EOF && ch != '\n') ch = f.get();
+      } else if (!std::isspace(ch)) {
+        break;
+      }
+      ch = f.get();
+    }
+    for (; ch != EOF && !std::isspace(ch); ch = f.get()) t.push_back(static_cast<char>(ch));
+    return t;  // the one white-space character after the token is consumed
+  };
+  const std::string magic = token();
+  if (magic != "P6" && magic != "PF") throw bad("neither a binary PPM (P6) nor a colour PFM (PF)");
+  char *end = nullptr;
+  const std::string ws = token(), hs = token(), last = token();
+  const long w = std::strtol(ws.c_str(), &end, 10);
+  if (ws.empty() || *end != '\0' || w < 1 || w > 16384) throw bad("bad width");
+  const long h = std::strtol(hs.c_str(), &end, 10);
+  if (hs.empty() || *end != '\0' || h < 1 || h > 16384) throw bad("bad height");
+  const size_t count = static_cast<size_t>(w) * static_cast<size_t>(h) * 3u;
+  pixels->assign(count, 0.0f);
+  if (magic == "P6") {
+    if (last != "255") throw bad("maxval must be 255");
+    std::vector<uint8_t> raw(count);
+    if (!f.read(reinterpret_cast<char *>(raw.data()), static_cast<std::streamsize>(count))) throw bad("short file");
+    for (size_t k = 0; k < count; ++k) (*pixels)[k] = static_cast<float>(raw[k]) / 255.0f;
+  } else {
+    const double scale = std::strtod(last.c_str(), &end);
+    if (last.empty() || *end != '\0' || !std::isfinite(scale) || scale == 0.0) throw bad("bad scale");
+    std::vector<uint8_t> raw(count * 4u);
+    if (!f.read(reinterpret_cast<char *>(raw.data()), static_cast<std::streamsize>(raw.size()))) throw bad("short file");
+    const bool little = scale < 0.0;
+    const size_t row = static_cast<size_t>(w) * 3u;
+    for (size_t y = 0; y < static_cast<size_t>(h); ++y) {
+      const uint8_t *src = raw.data() + (static_cast<size_t>(h) - 1u - y) * row * 4u;  // the file's rows run bottom to top
+      for (size_t k = 0; k < row; ++k) {
+        const uint8_t *b = src + 4u * k;
+        const uint32_t bits = little ? (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24)
+                                     : (uint32_t)b[3] | ((uint32_t)b[2] << 8) | ((uint32_t)b[1] << 16) | ((uint32_t)b[0] << 24);
+        float v;
+        std::memcpy(&v, &bits, 4);
+        (*pixels)[y * row + k] = v;
+      }
+    }
+  }
+  *width = static_cast<int>(w);
+  *height = static_cast<int>(h);
 }
 
 // ---- align -------------------------------------------------------------------------------------------------------

@@ -1518,6 +1518,113 @@ PYBIND11_MODULE(spz, m) {
         "until_iter, grad_threshold, percent_dense, extent, min_opacity, max_scale, max_points, opacity_reset_interval, "
         "seed: with interval > 0 Gaussians are cloned, split and culled every `interval` iterations (include/spz_amd.h "
         "\"densify\"), the output's count is num_points and rounds has one dict per round.");
+  m.def("locate_spz",
+        [](const py::object &input, const py::object &view, const py::object &image, int iterations, int levels,
+           spz::CoordinateSystem coord, const py::object &background, int max_sh_degree, float near_plane,
+           double lambda_dssim, double lr_rotation, const py::object &lr_translation, double lr_final_factor, double beta1,
+           double beta2, double eps) {
+          // the arguments first: every problem is a ValueError before any device work
+          if (iterations < 0) throw py::value_error("iterations must be >= 0");
+          if (levels < 1 || levels > SPZ_AMD_LOCATE_MAX_LEVELS) throw py::value_error("levels must be 1..8");
+          if (!std::isfinite(near_plane) || !(near_plane > 0.0f)) throw py::value_error("near must be > 0");
+          if (max_sh_degree < 0 || max_sh_degree > 3) throw py::value_error("max_sh_degree must be 0..3");
+          if (!(lambda_dssim >= 0.0 && lambda_dssim <= 1.0)) throw py::value_error("lambda_dssim must be in [0, 1]");
+          if (!std::isfinite(lr_rotation) || lr_rotation < 0.0) throw py::value_error("lr_rotation must be finite and >= 0");
+          if (!(lr_final_factor > 0.0 && lr_final_factor <= 1.0)) throw py::value_error("lr_final_factor must be in (0, 1]");
+          if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) {
+            throw py::value_error("beta1 and beta2 must be in [0, 1)");
+          }
+          if (!std::isfinite(eps) || eps < 0.0) throw py::value_error("eps must be finite and >= 0");
+          spz::LocateOptions o;
+          py::array_t<float, py::array::c_style | py::array::forcecast> bg(background);
+          if (bg.size() != 3) throw py::value_error("background must have three values");
+          for (int k = 0; k < 3; ++k) {
+            o.background[k] = bg.data()[k];
+            if (!std::isfinite(o.background[k])) throw py::value_error("background must be finite");
+          }
+          o.coord = coord;
+          o.nearPlane = near_plane;
+          o.maxShDegree = max_sh_degree;
+          o.iterations = iterations;
+          o.levels = levels;
+          o.lambdaDssim = lambda_dssim;
+          o.rotationLr = lr_rotation;
+          if (!lr_translation.is_none()) {
+            const double x = py::cast<double>(lr_translation);
+            if (!std::isfinite(x) || x < 0.0) throw py::value_error("lr_translation must be finite and >= 0");
+            o.translationLr = x;
+          }
+          o.lrFinalFactor = lr_final_factor;
+          o.beta1 = beta1;
+          o.beta2 = beta2;
+          o.eps = eps;
+          const spz::PruneOptions::View v = pruneView(view, 0, coord, near_plane);
+          if (!py::isinstance<py::array>(image)) throw py::value_error("image must be a numpy array");
+          const py::array arr = py::reinterpret_borrow<py::array>(image);
+          if (!arr.dtype().is(py::dtype::of<float>())) throw py::value_error("image must be float32");
+          if (arr.ndim() != 3 || (arr.shape(2) != 3 && arr.shape(2) != 4) || arr.shape(0) != v.height ||
+              arr.shape(1) != v.width) {
+            throw py::value_error("image must be the view's height x width x 3 or 4");
+          }
+          if (v.width % (1 << (levels - 1)) != 0 || v.height % (1 << (levels - 1)) != 0) {
+            throw py::value_error("width and height must be divisible by 2^(levels - 1)");
+          }
+          const py::array_t<float, py::array::c_style | py::array::forcecast> pixels(arr);
+          const int channels = static_cast<int>(arr.shape(2));
+          spz::LocateReport rep;
+          bool ok;
+          if (py::isinstance<py::bytes>(input)) {
+            const std::string b = input.cast<std::string>();
+            if (b.size() > static_cast<size_t>(INT32_MAX)) throw py::value_error("the input is larger than 2 GiB");
+            py::gil_scoped_release release;
+            ok = spz::locateSpz(reinterpret_cast<const uint8_t *>(b.data()), static_cast<int32_t>(b.size()), v,
+                                pixels.data(), channels, o, &rep);
+          } else {
+            const std::string f = py::str(input).cast<std::string>();
+            py::gil_scoped_release release;
+            ok = spz::locateSpz(f, v, pixels.data(), channels, o, &rep);
+          }
+          if (!ok) {
+            raiseFailure("locate_spz: refused (see the [SPZ ERROR] line)", "locate_spz failed (see the [SPZ ERROR] line)");
+          }
+          py::dict d;
+          d["history"] = rep.history;
+          d["before"] = metricsDict(rep.before);
+          d["after"] = metricsDict(rep.after);
+          d["iterations"] = rep.iterations;
+          d["lr_translation"] = rep.translationLr;
+          d["ms"] = py::make_tuple(rep.ms[0], rep.ms[1], rep.ms[2]);
+          return py::make_tuple(viewDict(rep.view), d);
+        },
+        py::arg("input"), py::arg("view"), py::arg("image"), py::kw_only(), py::arg("iterations") = 300,
+        py::arg("levels") = 1, py::arg("coord") = spz::CoordinateSystem::UNSPECIFIED,
+        py::arg("background") = py::make_tuple(0.0f, 0.0f, 0.0f), py::arg("max_sh_degree") = 3, py::arg("near") = 0.2f,
+        py::arg("lambda_dssim") = 0.2, py::arg("lr_rotation") = 2e-3, py::arg("lr_translation") = py::none(),
+        py::arg("lr_final_factor") = 0.1, py::arg("beta1") = 0.9, py::arg("beta2") = 0.999, py::arg("eps") = 1e-15,
+        "Fit the pose of `view` (a view dict with a rough world_to_camera) so that the .spz file `input` (a path, or the "
+        "file's bytes) renders as `image`, a (height, width, 3 or 4) float32 array (spz::locateSpz; the contract is in "
+        "include/spz_amd.h \"locate\"): `iterations` Adam steps on the six values of a twist, down the gradient of the "
+        "3DGS loss; with levels > 1 the first steps run on 2 x 2 box means of the image.  lr_translation None: "
+        "lr_rotation times the distance from the camera to the scene's centre.  Returns (view, report): the view with "
+        "its matrix replaced, and a dict of history (the loss before each step taken), before and after (metrics "
+        "dicts), iterations, lr_translation and ms.");
+  m.def("load_image",
+        [](const std::string &path) {
+          std::vector<float> pixels;
+          int w = 0, h = 0;
+          try {
+            spz::loadImageFile(path, &pixels, &w, &h);
+          } catch (const std::invalid_argument &e) {
+            throw py::value_error(e.what());
+          }
+          py::array_t<float> out({static_cast<py::ssize_t>(h), static_cast<py::ssize_t>(w), py::ssize_t(3)});
+          std::memcpy(out.mutable_data(), pixels.data(), pixels.size() * sizeof(float));
+          return out;
+        },
+        py::arg("path"),
+        "A picture as spz_render writes it, as locate_spz takes it: a binary PPM (P6, maxval 255) or a colour PFM (PF, "
+        "either byte order) as a (height, width, 3) float32 array, rows top to bottom.  ValueError when the file does "
+        "not open or is neither.");
   m.def("compare_images",
         [](const py::object &a, const py::object &b, const py::object &return_map) {
           if (!py::isinstance<py::bool_>(return_map)) throw py::value_error("return_map must be a bool");

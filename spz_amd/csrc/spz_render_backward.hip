@@ -539,3 +539,69 @@ int spz_amd_render_backward_device(const spz_amd_cloud_in *d_cloud, uint64_t num
 }
 
 }  // extern "C"
+
+// ---- the blend half on its own ("render view backward": the pose fit needs no gradients to the cloud)
+namespace spz_amd_detail {
+
+// Zeroes the caller's n x 9 record gradients for the blend backward to add into; with the total above max_entries it
+// sets the status instead and writes nothing, as the blend backward then adds nothing.
+__global__ __launch_bounds__(kPreBlock) void spz_render_records_clear_kernel(float *__restrict__ rec_grad,
+                                                                             unsigned long long count,
+                                                                             const unsigned long long *total,
+                                                                             unsigned long long max_entries,
+                                                                             uint32_t *status) {
+  const unsigned long long j = (unsigned long long)blockIdx.x * kPreBlock + threadIdx.x;
+  if (*total > max_entries) {
+    if (j == 0ull) *status = 1u;
+    return;
+  }
+  if (j < count) rec_grad[j] = 0.0f;
+}
+
+}  // namespace spz_amd_detail
+
+extern "C" {
+
+int spz_amd_render_records_backward_device(uint64_t num_points, const spz_amd_render_params *params,
+                                           uint64_t max_entries, const float *d_grad_image, float *d_record_grads,
+                                           uint32_t *d_status, const void *d_render_workspace, void *hip_stream) {
+  int rc = check_params(params);
+  if (rc != SPZ_AMD_OK) return rc;
+  if (num_points > kMaxEntries) return SPZ_AMD_ERR_TOO_MANY_POINTS;
+  if (max_entries > kMaxEntries) return SPZ_AMD_ERR_INVALID_ARG;
+  if (d_grad_image == nullptr || d_status == nullptr || d_render_workspace == nullptr ||
+      (num_points && d_record_grads == nullptr)) {
+    return SPZ_AMD_ERR_INVALID_ARG;
+  }
+  int device = 0;
+  rc = current_device(&device);
+  if (rc != SPZ_AMD_OK) return rc;
+  const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  SPZ_HIP_TRY(hipMemsetAsync(d_status, 0, sizeof(uint32_t), st));
+  if (num_points == 0) return SPZ_AMD_OK;  // the total is 0 and there is nothing to write
+  const RenderLayout wl = render_layout(num_points, max_entries);
+  const uint8_t *base = align_ws(const_cast<void *>(d_render_workspace));
+  const uint8_t *ent = base + wl.prefix;
+  BlendBackwardParams b = {};
+  b.rec = reinterpret_cast<const spz_amd_render_record *>(base + wl.rec);
+  b.sorted_gid = max_entries ? reinterpret_cast<const uint32_t *>(ent + wl.sorted_gid) : nullptr;
+  b.ranges = max_entries ? reinterpret_cast<const uint2 *>(ent + wl.ranges) : nullptr;  // read only when the total is > 0
+  b.total = reinterpret_cast<const unsigned long long *>(base + wl.total);
+  b.grad_image = d_grad_image;
+  b.rec_grad = d_record_grads;
+  b.max_entries = max_entries;
+  b.width = params->width;
+  b.height = params->height;
+  b.tiles_x = (params->width + kTile - 1) / kTile;
+  for (int k = 0; k < 3; ++k) b.bg[k] = params->background[k];
+  const unsigned long long count = (unsigned long long)num_points * kRecGrads;
+  hipLaunchKernelGGL(spz_render_records_clear_kernel, dim3((unsigned)((count + kPreBlock - 1) / kPreBlock)),
+                     dim3(kPreBlock), 0, st, d_record_grads, count, b.total, max_entries, d_status);
+  SPZ_HIP_TRY(hipGetLastError());
+  const dim3 grid(b.tiles_x, (params->height + kTile - 1) / kTile);
+  hipLaunchKernelGGL(spz_render_blend_backward_kernel, grid, dim3(kBlendThreads), 0, st, b);
+  SPZ_HIP_TRY(hipGetLastError());
+  return SPZ_AMD_OK;
+}
+
+}  // extern "C"

@@ -1066,18 +1066,132 @@ class _RenderFunction(torch.autograd.Function):
         return (None,) * 5 + out
 
 
-def render_autograd(cloud, num_points, sh_degree, params, antialiased=False, max_entries=None):
+def _records_backward(L, n, params, m, grad_image, ws, dev, st):
+    """Enqueue spz_amd_render_records_backward_device on st over the workspace ws of a finished render: (n, 9)."""
+    rec = torch.empty((n, 9), dtype=torch.float32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    rc = L.spz_amd_render_records_backward_device(n, C.byref(params), m, grad_image.data_ptr(),
+                                                  rec.data_ptr() if n else None, status.data_ptr(), ws.data_ptr(),
+                                                  C.c_void_p(st.cuda_stream))
+    abi.check(rc, "spz_amd_render_records_backward_device")
+    return rec
+
+
+def _view_backward(L, ptrs, n, sh_degree, antialiased, params, m, rec, ws, dev, st):
+    """Enqueue spz_amd_render_view_backward_device on st: the (3, 4) float64 gradient to [R | t]."""
+    out = torch.empty((3, 4), dtype=torch.float64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    vws = torch.empty(int(L.spz_amd_render_view_backward_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+    rc = L.spz_amd_render_view_backward_device(C.byref(ptrs), n, sh_degree, 1 if antialiased else 0, C.byref(params), m,
+                                               rec.data_ptr() if n else None, out.data_ptr(), status.data_ptr(),
+                                               ws.data_ptr(), vws.data_ptr(), C.c_void_p(st.cuda_stream))
+    abi.check(rc, "spz_amd_render_view_backward_device")
+    return out
+
+
+def render_view_backward(cloud, num_points, sh_degree, params, grad_image, *, antialiased=False, max_entries=None,
+                         record_grads=None, return_record_grads=False, stream=None):
+    """The gradient of a scalar loss to the camera [R | t] of params, given grad_image = its gradient to the image of
+    render(): a (3, 4) float64 CUDA tensor, the 12 entries taken as independent (include/spz_amd.h "render view
+    backward").  Renders (prepare + finish), then the blend half of the backward
+    (spz_amd_render_records_backward_device) and spz_amd_render_view_backward_device over the same workspace.
+    record_grads: an (n, 9) float32 CUDA tensor to use instead of the blend half's (grad_image may then be None): the
+    sum over the Gaussians uses no atomics, so the same record gradients give the same bits.  return_record_grads:
+    (view_grad, record_grads).  max_entries and stream: as render_backward()."""
+    ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
+    L = abi.load_library()
+    _check_render_args(L, params, max_entries)
+    if record_grads is None:
+        grad_image = _check_grad_image(grad_image, params, dev)
+    elif (not isinstance(record_grads, torch.Tensor) or record_grads.dtype != torch.float32
+          or record_grads.device != dev or tuple(record_grads.shape) != (num_points, 9)):
+        raise ValueError(f"record_grads must be a float32 tensor of shape ({num_points}, 9) on {dev}")
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        with torch.cuda.stream(st):
+            source = ("cloud", ptrs, num_points, int(sh_degree), antialiased)
+            image, ws, m = _rendered_workspace(L, source, num_points, params, dev, max_entries, st)
+            if record_grads is None:
+                rec = _records_backward(L, num_points, params, m, grad_image, ws, dev, st)
+            else:
+                rec = record_grads.contiguous()
+            out = _view_backward(L, ptrs, num_points, int(sh_degree), antialiased, params, m, rec, ws, dev, st)
+    return (out, rec) if return_record_grads else out
+
+
+def _params_with_pose(params, world_to_camera):
+    """A copy of params with its matrix replaced by the (3, 4) tensor world_to_camera, rounded to float32."""
+    if not isinstance(world_to_camera, torch.Tensor) or tuple(world_to_camera.shape) != (3, 4) \
+            or not world_to_camera.is_floating_point():
+        raise ValueError("world_to_camera must be a floating-point tensor of shape (3, 4)")
+    p = abi.RenderParams.from_buffer_copy(params)
+    for k, x in enumerate(world_to_camera.detach().to(torch.float32).cpu().reshape(-1).tolist()):
+        p.world_to_camera[k] = x
+    return p
+
+
+class _RenderPoseFunction(torch.autograd.Function):
+    """_RenderFunction with the camera's [R | t] as one more differentiable input: the forward renders params with the
+    matrix replaced, the backward also runs spz_amd_render_view_backward_device over the kept workspace."""
+
+    @staticmethod
+    def forward(ctx, num_points, sh_degree, params, antialiased, max_entries, world_to_camera, *arrays):
+        params = _params_with_pose(params, world_to_camera)
+        cloud = dict(zip(FIELDS, (a.detach() for a in arrays)))
+        ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
+        L = abi.load_library()
+        _check_render_args(L, params, max_entries)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev)
+            source = ("cloud", ptrs, num_points, int(sh_degree), antialiased)
+            image, ws, m = _rendered_workspace(L, source, num_points, params, dev, max_entries, st)
+        ctx.save_for_backward(image, ws, world_to_camera, *arrays)
+        ctx.args = (num_points, int(sh_degree), params, bool(antialiased), m)
+        return image
+
+    @staticmethod
+    def backward(ctx, grad_image):
+        image, ws, world_to_camera = ctx.saved_tensors[:3]
+        arrays = ctx.saved_tensors[3:]
+        num_points, sh_degree, params, antialiased, m = ctx.args
+        cloud = dict(zip(FIELDS, (a.detach() for a in arrays)))
+        ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
+        L = abi.load_library()
+        grad_image = _check_grad_image(grad_image, params, dev)
+        need_pose, need = ctx.needs_input_grad[5], ctx.needs_input_grad[6:]
+        grads, rec, pose = None, None, None
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev)
+            if any(need):
+                grads, rec = _render_backward(L, ptrs, num_points, sh_degree, antialiased, params, m, image, grad_image,
+                                              ws, dev, need_pose, st)
+            elif need_pose:
+                rec = _records_backward(L, num_points, params, m, grad_image, ws, dev, st)
+            if need_pose:
+                pose = _view_backward(L, ptrs, num_points, sh_degree, antialiased, params, m, rec, ws, dev, st)
+                pose = pose.to(device=world_to_camera.device, dtype=world_to_camera.dtype)
+        out = tuple(grads[k].view_as(a) if n else None for k, a, n in zip(FIELDS, arrays, need))
+        return (None,) * 5 + (pose,) + out
+
+
+def render_autograd(cloud, num_points, sh_degree, params, antialiased=False, max_entries=None, world_to_camera=None):
     """render() as a differentiable torch operation: the (height, width, 4) image, bit-identical to render()'s, whose
     backward() gives the six arrays of cloud their gradients (those that require grad; the others get None).  Runs on
     the current stream.  The backward is the exact derivative of the forward with its discrete decisions held constant
     (include/spz_amd.h "render backward") and sums with f32 atomic adds.  A total above max_entries raises
-    RuntimeError.  A cloud without sh (degree 0) may leave "sh" out."""
+    RuntimeError.  A cloud without sh (degree 0) may leave "sh" out.
+    world_to_camera: a (3, 4) floating-point tensor that replaces the matrix of params (rounded to float32; it must
+    still pass the render's checks) and, when it requires grad, receives the gradient to its 12 entries taken as
+    independent (include/spz_amd.h "render view backward").  None: params as they are."""
     arrays = []
     for k in FIELDS:
         t = cloud.get(k)
         if t is None:
             t = torch.empty(0, dtype=torch.float32, device=cloud["positions"].device)
         arrays.append(t)
+    if world_to_camera is not None:
+        return _RenderPoseFunction.apply(num_points, sh_degree, params, antialiased, max_entries, world_to_camera,
+                                         *arrays)
     return _RenderFunction.apply(num_points, sh_degree, params, antialiased, max_entries, *arrays)
 
 
@@ -1574,6 +1688,77 @@ def refine_packed(stream_a, header_a, stream_b, header_b, views, iterations, *, 
     return RefineResult(ctx, out_bytes.value, dev, report)
 
 
+def image_halve(image_t, stream=None):
+    """The 2 x 2 box mean of a (height, width, 3 or 4) float32 CUDA image with even sides
+    (spz_amd_image_halve_device): ((top left + top right) + (bottom left + bottom right)) / 4 in f32, channels kept.
+    The target of the next coarser level of locate().  stream: as render()."""
+    L = abi.load_library()
+    _check_image("image", image_t)
+    h, w, ch = (int(x) for x in image_t.shape)
+    if h % 2 or w % 2:
+        raise ValueError(f"width and height must be even, got {w} x {h}")
+    dev = image_t.device
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        with torch.cuda.stream(st):
+            out = torch.empty((h // 2, w // 2, ch), dtype=torch.float32, device=dev)
+            rc = L.spz_amd_image_halve_device(image_t.data_ptr(), ch, w, h, out.data_ptr(), C.c_void_p(st.cuda_stream))
+    abi.check(rc, "spz_amd_image_halve_device")
+    return out
+
+
+def _locate(entry, call, params, target, options):
+    import numpy as np
+    if not isinstance(params, abi.RenderParams):
+        raise ValueError("params must be an abi.RenderParams (abi.render_params)")
+    _check_image("target", target)
+    if tuple(target.shape[:2]) != (params.height, params.width):
+        raise ValueError(f"target must be ({params.height}, {params.width}, 3 or 4)")
+    opts = abi.locate_options(**options)
+    pose = (C.c_float * 12)()
+    history = (C.c_double * max(1, opts.iterations))()
+    before, after = abi.ImageMetrics(), abi.ImageMetrics()
+    ran = C.c_int32()
+    ms = (C.c_float * 3)()
+    dev = target.device
+    torch.cuda.current_stream(dev).synchronize()  # the inputs' producers
+    device_index = dev.index if dev.index is not None else torch.cuda.current_device()
+    rc = call(C.byref(params), target.data_ptr(), int(target.shape[2]), C.byref(opts), device_index, pose, history,
+              C.byref(before), C.byref(after), C.byref(ran), ms)
+    abi.check(rc, entry)
+    return {"world_to_camera": np.array(list(pose), dtype=np.float32).reshape(3, 4),
+            "history": [history[i] for i in range(ran.value)], "iterations": int(ran.value),
+            "before": _metrics_dict(before), "after": _metrics_dict(after), "ms": tuple(ms)}
+
+
+def locate(cloud, num_points, sh_degree, params, target, *, antialiased=False, **options):
+    """The pose of the camera that took `target` in the scene `cloud` (device tensors, as render() takes them), from
+    the rough pose in params (spz_amd_locate_cloud_host; the contract is in include/spz_amd.h "locate").  target: a
+    (height, width, 3 or 4) float32 CUDA tensor of params' size.  options: abi.LOCATE_FIELDS (iterations, levels,
+    lambda_dssim, lr_rotation, lr_translation, lr_final_factor, beta1, beta2, eps).  Blocks.  Returns a dict:
+    world_to_camera (a (3, 4) float32 numpy array), history (the loss before each step taken), iterations (steps
+    taken), before and after (the metrics of the render against the target at the initial and the final pose), ms."""
+    ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
+    L = abi.load_library()
+    if isinstance(target, torch.Tensor) and target.device != dev:
+        raise ValueError("the cloud and the target must be on one device")
+    return _locate("spz_amd_locate_cloud_host",
+                   lambda *a: L.spz_amd_locate_cloud_host(C.byref(ptrs), num_points, int(sh_degree),
+                                                          1 if antialiased else 0, *a), params, target, options)
+
+
+def locate_packed(stream_t, header, params, target, **options):
+    """locate() of a packed device stream (any version), decoded once as loadSpz(to = params.coord) would
+    (spz_amd_locate_host); before and after are the metrics of the packed render."""
+    _check_stream_tensor(stream_t)
+    L = abi.load_library()
+    if isinstance(target, torch.Tensor) and target.device != stream_t.device:
+        raise ValueError("the stream and the target must be on one device")
+    return _locate("spz_amd_locate_host",
+                   lambda *a: L.spz_amd_locate_host(stream_t.data_ptr(), stream_t.numel(), C.byref(header), *a), params,
+                   target, options)
+
+
 def convert_coordinates(cloud, num_points, sh_degree, from_coord, to_coord, stream=None):
     """In-place GaussianCloud::convertCoordinates on device tensors (positions, rotations, sh)."""
     L = abi.load_library()
@@ -1602,4 +1787,5 @@ __all__ = ["encode", "decode", "encode_shard", "decode_shard", "decode_gather", 
            "select", "subset", "transform", "transform_packed", "merge_packed",
            "alloc_cloud", "image_loss", "adam_step", "refine_packed",
            "densify_accumulate", "densify_plan", "densify_apply", "reset_opacity",
+           "render_view_backward", "image_halve", "locate", "locate_packed",
            "make_header", "to_device", "to_numpy", "SH_DIM"]
