@@ -40,7 +40,7 @@ $(LIBDIR)/libspz_host.so: $(CSRC)/spz_host.cpp $(CSRC)/spz_ply.cpp $(CSRC)/spz_d
 	$(CXX) $(CXXFLAGS) -shared -o $@ $(CSRC)/spz_host.cpp $(CSRC)/spz_ply.cpp $(CSRC)/spz_deflate.cpp $(CSRC)/spz_lz77_model.cpp $(CSRC)/spz_inflate.cpp -L$(LIBDIR) -lspz_amd -lz -ldl -lpthread \
 	    -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,/opt/rocm/lib
 
-$(ROOT)spz_amd/spz$(PYEXT): $(CSRC)/spz_py.cpp $(INC)/spz_amd_host.hpp $(LIBDIR)/libspz_host.so
+$(ROOT)spz_amd/spz$(PYEXT): $(CSRC)/spz_py.cpp $(CSRC)/spz_py_args.hpp $(INC)/spz_amd_host.hpp $(LIBDIR)/libspz_host.so
 	$(CXX) $(CXXFLAGS) $(PYINC) -fvisibility=hidden -shared -o $@ $(CSRC)/spz_py.cpp \
 	    -L$(LIBDIR) -lspz_host -lspz_amd -Wl,-rpath,'$$ORIGIN/lib' -Wl,-rpath,/opt/rocm/lib
 

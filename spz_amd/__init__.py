@@ -26,6 +26,7 @@ Layout:
   csrc/spz_deflate.cpp  multi-threaded gzip writer with zlib's exact bytes (the default container stage)
   csrc/spz_inflate.cpp  multi-threaded, CRC-verified inflate of ordinary single-stream members
   csrc/spz_py.cpp       Python module `spz_amd.spz` with the reference nanobind shim's surface
+  csrc/spz_py_args.hpp  ... how it reads arguments and shapes results, each rule defined once
   abi.py                ctypes binding of the C ABI
   device.py             device-resident encode/decode on torch-owned HBM
   shard.py              point-range sharding across GPUs + gatherv of the byte stream
