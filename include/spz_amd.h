@@ -894,6 +894,113 @@ int spz_amd_render_depth_cloud_host(const spz_amd_cloud_in *h_cloud, uint64_t nu
                                     int antialiased, const spz_amd_render_params *params, int device, float *h_rgba,
                                     float *h_depth, uint32_t *h_index, uint64_t *h_entries, float *h_ms);
 
+/* ---- mesh: a triangle mesh of a scene (spz_mesh.hip; DESIGN §8 "Mesh").  The reference has no counterpart.  Depth
+ *      maps of a set of views are fused into a truncated signed distance volume (TSDF), and the zero level set of the
+ *      volume is extracted by marching tetrahedra: vertices, per-vertex colours and triangles.
+ *
+ *      The volume.  A lattice of nx x ny x nz sample points at lo + (i, j, k) s in the views' coord frame (dims = nx,
+ *      ny, nz; s = voxel_size).  Each dimension 2..2048, nx ny nz <= 2^28, s and truncation finite and > 0, lo finite.
+ *      The grid is five f32 planes of nx ny nz values each, in this order: W (weight), S (sum of truncated distances),
+ *      Cr, Cg, Cb (colour sums); the linear index of a point is (k ny + j) nx + i.  A new grid is all zero.
+ *      tsdf_check, tsdf_bytes (20 nx ny nz; 0 for a bad volume) and tsdf_volume_from_box are host only.
+ *      volume_from_box: lo = (float)lo, dims_a = floor((hi_a - lo_a) / s) + 2 in f64 (the lattice reaches past hi),
+ *      hi_a >= lo_a; a dimension above 2048 or a lattice above 2^28: SPZ_AMD_ERR_INVALID_ARG.
+ *
+ *      Fuse (tsdf_integrate_device): one view into the grid.  d_depth (H x W x 2) and d_image (H x W x 4) exactly as
+ *      render_depth_device writes them; depth_kind SPZ_AMD_MESH_DEPTH_MEDIAN or _EXPECTED; min_alpha in [0, 1].  Per
+ *      lattice point, every operation rounded on its own (no contraction):
+ *        p = lo + (i, j, k) s in f64 from the f32 fields;  p_c = R p + t in f64, each row ((R0 px + R1 py) + R2 pz) + t;
+ *        z = p_c.z; skip unless z > near_plane.  u = floor(fx (x / z) + cx), v = floor(fy (y / z) + cy) (the render's
+ *        pixel centre is at index + 0.5); skip unless 0 <= u < W and 0 <= v < H.
+ *        MEDIAN: D = depth[v][u][1].  EXPECTED: a = image[v][u][3], skip unless a >= min_alpha, D = depth[v][u][0] / a
+ *        in f32.  Skip unless D is finite and > 0.  sdf = (double)D - z; skip if sdf < -truncation;
+ *        d = (float)min(1.0, sdf / truncation).  Then, with f32 adds: W += 1, S += d, C += image[v][u][0..2] (unclamped).
+ *      A skipped point is not written.  No atomics; views are fused one call after another, so a run repeats its bits,
+ *      and a stream and its decoded floats give the same grid.  background and max_sh_degree of params are not read.
+ *      Projective fusion marks up to `truncation` behind a surface seen at a grazing angle as inside: a known artefact
+ *      of the method, which opens the mesh at the limbs of a view set.
+ *
+ *      Extract (mesh_count_device, mesh_emit_device).  f = S / W (f32 division) at a lattice point; inside iff f < 0.
+ *      A cube is the 8 points (i..i+1, j..j+1, k..k+1); it is valid iff all 8 have W >= min_weight (finite, > 0); only
+ *      valid cubes emit.  Corners are numbered dx + 2 dy + 4 dz.  Each cube splits into the six Kuhn tetrahedra around
+ *      the diagonal from corner 0 to corner 7: for the axis permutations p in lexicographic order (xyz, xzy, yxz, yzx,
+ *      zxy, zyx) v0 = corner 0, v1 = v0 + e_p0, v2 = v1 + e_p1, v3 = corner 7.  Cubes that share a face split it along
+ *      the same diagonal, so the surface is watertight across cubes.
+ *      Every tet edge runs from a lattice point a to a + delta, delta in {0,1}^3 \ {0}; its id is 7 lin(a) + (dx + 2 dy
+ *      + 4 dz - 1).  One vertex per edge that at least one emitted triangle uses.  t = f_a / (f_a - f_b) in f64;
+ *      position = lo + (idx_a + t delta) s per axis in f64, rounded to f32; colour = c_a + t (c_b - c_a) with c = C / W
+ *      (f32 division), in f64, rounded to f32.
+ *      Tet edges are numbered by vertex pairs (0,1), (0,2), (0,3), (1,2), (1,3), (2,3).  One vertex i alone on its
+ *      side: one triangle, the three edges at i in ascending number.  A 2-2 split {0, j} | {k, l}, k < l: the quad q =
+ *      (0k, 0l, jl, jk) as (q0, q1, q2) and (q0, q2, q3).  A triangle's last two indices are swapped where needed so
+ *      that (b - a) x (c - a) points from the centroid of the tet's inside vertices to that of its outside vertices,
+ *      judged with the edge midpoints as positions.  The table is generated from this rule (mesh_tet_table, host only:
+ *      corners[tet][4], num_triangles[tet][mask], edges[tet][mask][6], mask bit v = tet vertex v inside).
+ *      Order: vertices in ascending edge id; triangles by ascending cube (linear index of corner 0), then tet, then
+ *      the case's order.  No atomic decides an order: a run repeats its bits.  Where f == 0 exactly at a lattice point
+ *      the triangles around it have zero area; they are kept, because the topology stays manifold.
+ *      mesh_workspace_bytes (host only; 0 for a bad volume): 33 bytes per lattice point (a dense edge map) and the
+ *      scans' block sums.  mesh_count_device: the classification and the two scans; d_counts (device memory, 2 uint64)
+ *      = the number of vertices, of triangles.  The caller reads them back once, then mesh_emit_device with the same
+ *      volume, grid and workspace writes d_positions and d_colors (num_vertices x 3 f32) and d_triangles
+ *      (num_triangles x 3 u32).  A capacity below its count: SPZ_AMD_ERR_CAPACITY, nothing written.  The host form
+ *      refuses more than 2^32 - 1 vertices the same way.
+ *      All device forms check their arguments on the host before any launch (a bad one: SPZ_AMD_ERR_INVALID_ARG; no
+ *      device: SPZ_AMD_ERR_NO_DEVICE), enqueue on hip_stream and do not synchronise.
+ *
+ *      The host form (mesh_open / _fetch / _close, shaped like prune's) takes a stream already in device memory.
+ *      views: 1..SPZ_AMD_MESH_MAX_VIEWS, each passing render_check_params, all with one coord.  options (mesh_check,
+ *      host only): has_box and box = lo xyz, hi xyz with hi > lo; exactly one of voxel_size (> 0) and resolution
+ *      (1..2046 lattice cells along the longest side of the box; mesh_default_options sets 256) non-zero; truncation
+ *      (0: 4 voxel_size); depth_kind; min_alpha; min_weight.  Without a box: the exact bounding box of the file's
+ *      finite decoded positions in coord, computed on the device (no finite position: SPZ_AMD_ERR_INVALID_ARG); a
+ *      file with floaters wants a clean first, or a box.  Per view: prepare, render_depth_device, the fuse; then the
+ *      extraction.  It runs on `device` on a stream of its own and blocks.  h_counts[2]: vertices, triangles;
+ *      *h_volume (may be NULL): the volume used; h_ms (may be NULL): [0] wall-clock milliseconds of the views' renders,
+ *      [1] of the fuses, [2] of the extraction; *h_bad_view (may be NULL): the view a failure concerns, else -1.  An
+ *      entry total above 2^31 - 1: SPZ_AMD_ERR_CAPACITY.  mesh_fetch: the three arrays into host memory. */
+enum { SPZ_AMD_MESH_MAX_VIEWS = 1024, SPZ_AMD_MESH_DEPTH_MEDIAN = 0, SPZ_AMD_MESH_DEPTH_EXPECTED = 1 };
+typedef struct {
+  float lo[3];
+  float voxel_size;
+  uint32_t dims[3];
+  float truncation;
+} spz_amd_tsdf_volume;
+typedef struct {
+  double box[6];
+  double voxel_size;
+  double truncation;
+  int32_t has_box;
+  int32_t resolution;
+  int32_t depth_kind;
+  float min_alpha;
+  float min_weight;
+  int32_t reserved;
+} spz_amd_mesh_options;
+
+int spz_amd_tsdf_check(const spz_amd_tsdf_volume *volume);
+uint64_t spz_amd_tsdf_bytes(const spz_amd_tsdf_volume *volume);
+int spz_amd_tsdf_volume_from_box(const double lo[3], const double hi[3], double voxel_size, double truncation,
+                                 spz_amd_tsdf_volume *out);
+int spz_amd_tsdf_integrate_device(const spz_amd_tsdf_volume *volume, float *d_grid, const spz_amd_render_params *params,
+                                  const float *d_depth, const float *d_image, int depth_kind, float min_alpha,
+                                  void *hip_stream);
+int spz_amd_mesh_tet_table(uint8_t corners[24], uint8_t num_triangles[96], uint8_t edges[576]);
+uint64_t spz_amd_mesh_workspace_bytes(const spz_amd_tsdf_volume *volume);
+int spz_amd_mesh_count_device(const spz_amd_tsdf_volume *volume, const float *d_grid, float min_weight,
+                              uint64_t *d_counts, void *d_workspace, void *hip_stream);
+int spz_amd_mesh_emit_device(const spz_amd_tsdf_volume *volume, const float *d_grid, uint64_t num_vertices,
+                             uint64_t num_triangles, uint64_t vertex_capacity, uint64_t triangle_capacity,
+                             float *d_positions, float *d_colors, uint32_t *d_triangles, const void *d_workspace,
+                             void *hip_stream);
+int spz_amd_mesh_default_options(spz_amd_mesh_options *options);
+int spz_amd_mesh_check(const spz_amd_mesh_options *options);
+int spz_amd_mesh_open(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, const spz_amd_render_params *views,
+                      int num_views, const spz_amd_mesh_options *options, int device, void **ctx, uint64_t *h_counts,
+                      spz_amd_tsdf_volume *h_volume, float *h_ms, int32_t *h_bad_view);
+int spz_amd_mesh_fetch(void *ctx, float *h_positions, float *h_colors, uint32_t *h_triangles);
+void spz_amd_mesh_close(void *ctx);
+
 /* ---- image metrics: PSNR, MSE, L1, max error and SSIM of two images (spz_metrics.hip; DESIGN §8 "Compare").  The
  *      reference has no counterpart.  The convention of the 3DGS evaluation code (Kerbl et al. 2023, loss_utils.ssim and
  *      image_utils.psnr), so the numbers compare with published tables.

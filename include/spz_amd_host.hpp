@@ -651,6 +651,48 @@ bool locateSpz(const std::string &filename, const PruneOptions::View &initial, c
 // ("PF", either byte order, rows bottom to top in the file), three channels, rows top to bottom in *pixels.
 // std::invalid_argument naming the file when it does not open or is neither.
 void loadImageFile(const std::string &filename, std::vector<float> *pixels, int *width, int *height);
+// Mesh (DESIGN §8 "Mesh"): a triangle mesh of a file, for software that does not speak Gaussians (include/spz_amd.h
+// "mesh" states the contract).  The file's depth maps over the views (renderSpzDepth's, median depth by default) are
+// fused on the device into a truncated signed distance volume, and its zero level set is extracted by marching
+// tetrahedra: vertices, per-vertex colours (not clamped) and triangles, in a fixed order; a run repeats its bytes.
+// views: 1..1024 pinhole cameras (orbitViews, loadViewsFile), all in the `coord` frame.  box: x0 y0 z0 x1 y1 z1 in
+// `coord`; unset: the exact bounding box of the file's finite decoded positions, which floaters inflate (cleanSpz first,
+// or pass a box).  Exactly one of voxelSize and resolution (lattice cells along the longest side of the box); neither:
+// resolution 256.  truncation unset: 4 voxelSize.  Projective fusion marks up to `truncation` behind a surface seen at
+// a grazing angle as inside, so the mesh of a closed object may open at the limbs of the view set.  false + one
+// "[SPZ ERROR] meshSpz: …" line on a bad argument (lastDeviceStatus() = SPZ_AMD_ERR_INVALID_ARG; a bad view is named by
+// its index), an input that does not load, or a device failure.  SPZ_AMD_MESH_TIMING=1 prints the stages' times.
+struct MeshOptions {
+  enum Depth { Median = 0, Expected = 1 };
+  std::vector<PruneOptions::View> views;
+  CoordinateSystem coord = CoordinateSystem::UNSPECIFIED;
+  float nearPlane = 0.2f;
+  std::optional<std::array<double, 6>> box;
+  std::optional<double> voxelSize;
+  std::optional<int> resolution;
+  std::optional<double> truncation;
+  Depth depth = Median;
+  float minAlpha = 0.5f;   // Expected: pixels of less alpha are not fused
+  float minWeight = 1.0f;  // a cube emits when all 8 corners were seen by at least this many views
+};
+struct TriangleMesh {
+  std::vector<float> vertices;      // x y z per vertex
+  std::vector<float> colors;        // r g b per vertex, not clamped
+  std::vector<uint32_t> triangles;  // three vertex numbers per triangle
+  std::array<float, 3> lo = {0, 0, 0};  // the volume used: lattice points at lo + (i, j, k) voxelSize
+  float voxelSize = 0.0f, truncation = 0.0f;
+  std::array<uint32_t, 3> dims = {0, 0, 0};
+  float ms[3] = {0.0f, 0.0f, 0.0f};  // renders, fuses, extraction
+};
+bool meshSpz(const uint8_t *data, int32_t size, const MeshOptions &options, TriangleMesh *mesh);
+bool meshSpz(const std::string &filename, const MeshOptions &options, TriangleMesh *mesh);
+// A binary little-endian PLY: vertex properties x y z (float) and red green blue (uchar, rint(255 clamp(c, 0, 1)), NaN as
+// 0), faces as "list uchar uint vertex_indices".  false + one "[SPZ ERROR] saveMeshPly: …" line when the arrays' sizes
+// do not match (3 numVertices floats each, 3 numTriangles indices, every index below numVertices) or the file cannot be
+// written.
+bool saveMeshPly(const std::string &filename, const float *vertices, const float *colors, size_t numVertices,
+                 const uint32_t *triangles, size_t numTriangles);
+bool saveMeshPly(const std::string &filename, const TriangleMesh &mesh);
 // Status (spz_amd.h codes) of the last device call made by this thread; 0 = ok.
 int lastDeviceStatus();
 void setLastDeviceStatus(int status);

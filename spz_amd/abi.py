@@ -100,6 +100,10 @@ EXPORTS = (
     "spz_amd_locate_default_options", "spz_amd_locate_check", "spz_amd_locate_level_params",
     "spz_amd_locate_twist_gradient", "spz_amd_locate_pose_step", "spz_amd_image_halve_device", "spz_amd_locate_host",
     "spz_amd_locate_image_host", "spz_amd_locate_cloud_host",
+    "spz_amd_tsdf_check", "spz_amd_tsdf_bytes", "spz_amd_tsdf_volume_from_box", "spz_amd_tsdf_integrate_device",
+    "spz_amd_mesh_tet_table", "spz_amd_mesh_workspace_bytes", "spz_amd_mesh_count_device", "spz_amd_mesh_emit_device",
+    "spz_amd_mesh_default_options", "spz_amd_mesh_check", "spz_amd_mesh_open", "spz_amd_mesh_fetch",
+    "spz_amd_mesh_close",
 )
 
 RCCL_UNIQUE_ID_BYTES = 128
@@ -211,6 +215,23 @@ class LocateOptions(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("levels", C.c_int32), ("lambda_dssim", C.c_double),
                 ("lr_rotation", C.c_double), ("lr_translation", C.c_double), ("lr_final_factor", C.c_double),
                 ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
+
+
+MESH_MAX_VIEWS = 1024
+MESH_DEPTH_MEDIAN, MESH_DEPTH_EXPECTED = 0, 1
+MESH_DEPTH_KINDS = {"median": MESH_DEPTH_MEDIAN, "expected": MESH_DEPTH_EXPECTED}
+
+
+class TsdfVolume(C.Structure):
+    """spz_amd_tsdf_volume: a lattice of dims sample points at lo + (i, j, k) voxel_size (include/spz_amd.h "mesh")."""
+    _fields_ = [("lo", C.c_float * 3), ("voxel_size", C.c_float), ("dims", C.c_uint32 * 3), ("truncation", C.c_float)]
+
+
+class MeshOptions(C.Structure):
+    """spz_amd_mesh_options (include/spz_amd.h "mesh"); spz_amd_mesh_default_options fills the defaults."""
+    _fields_ = [("box", C.c_double * 6), ("voxel_size", C.c_double), ("truncation", C.c_double),
+                ("has_box", C.c_int32), ("resolution", C.c_int32), ("depth_kind", C.c_int32),
+                ("min_alpha", C.c_float), ("min_weight", C.c_float), ("reserved", C.c_int32)]
 
 
 class DensifyOptions(C.Structure):
@@ -725,6 +746,35 @@ def bind(L):
     L.spz_amd_locate_cloud_host.argtypes = [C.POINTER(CloudPtrs), u64, i32, i32, C.POINTER(RenderParams), vp, i32,
                                             C.POINTER(LocateOptions), i32, vp, vp, C.POINTER(ImageMetrics),
                                             C.POINTER(ImageMetrics), C.POINTER(C.c_int32), vp]
+    L.spz_amd_tsdf_check.restype = i32
+    L.spz_amd_tsdf_check.argtypes = [C.POINTER(TsdfVolume)]
+    L.spz_amd_tsdf_bytes.restype = u64
+    L.spz_amd_tsdf_bytes.argtypes = [C.POINTER(TsdfVolume)]
+    L.spz_amd_tsdf_volume_from_box.restype = i32
+    L.spz_amd_tsdf_volume_from_box.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_double,
+                                               C.POINTER(TsdfVolume)]
+    L.spz_amd_tsdf_integrate_device.restype = i32
+    L.spz_amd_tsdf_integrate_device.argtypes = [C.POINTER(TsdfVolume), vp, C.POINTER(RenderParams), vp, vp, i32,
+                                                C.c_float, vp]
+    L.spz_amd_mesh_tet_table.restype = i32
+    L.spz_amd_mesh_tet_table.argtypes = [vp, vp, vp]
+    L.spz_amd_mesh_workspace_bytes.restype = u64
+    L.spz_amd_mesh_workspace_bytes.argtypes = [C.POINTER(TsdfVolume)]
+    L.spz_amd_mesh_count_device.restype = i32
+    L.spz_amd_mesh_count_device.argtypes = [C.POINTER(TsdfVolume), vp, C.c_float, vp, vp, vp]
+    L.spz_amd_mesh_emit_device.restype = i32
+    L.spz_amd_mesh_emit_device.argtypes = [C.POINTER(TsdfVolume), vp, u64, u64, u64, u64, vp, vp, vp, vp, vp]
+    L.spz_amd_mesh_default_options.restype = i32
+    L.spz_amd_mesh_default_options.argtypes = [C.POINTER(MeshOptions)]
+    L.spz_amd_mesh_check.restype = i32
+    L.spz_amd_mesh_check.argtypes = [C.POINTER(MeshOptions)]
+    L.spz_amd_mesh_open.restype = i32
+    L.spz_amd_mesh_open.argtypes = [vp, sz, C.POINTER(Header), C.POINTER(RenderParams), i32, C.POINTER(MeshOptions), i32,
+                                    C.POINTER(vp), C.POINTER(u64), C.POINTER(TsdfVolume), vp, C.POINTER(C.c_int32)]
+    L.spz_amd_mesh_fetch.restype = i32
+    L.spz_amd_mesh_fetch.argtypes = [vp, vp, vp, vp]
+    L.spz_amd_mesh_close.restype = None
+    L.spz_amd_mesh_close.argtypes = [vp]
     return L
 
 
@@ -896,6 +946,95 @@ def locate_level_params(params, level):
     if load_library().spz_amd_locate_level_params(C.byref(params), int(level), C.byref(out)) != OK:
         raise ValueError(f"level {level}: width and height must be divisible by 2^level (level 0..7)")
     return out
+
+
+def tsdf_volume(lo, dims, voxel_size, truncation=None):
+    """A TsdfVolume, checked on the host (spz_amd_tsdf_check): ValueError when refused.  truncation: None = 4 voxels."""
+    v = TsdfVolume()
+    lo, dims = [float(x) for x in lo], [int(x) for x in dims]
+    if len(lo) != 3 or len(dims) != 3 or min(dims) < 0 or max(dims) > 2**32 - 1:
+        raise ValueError("lo and dims must have three values each")
+    for a in range(3):
+        v.lo[a], v.dims[a] = lo[a], dims[a]
+    v.voxel_size = float(voxel_size)
+    v.truncation = 4.0 * float(voxel_size) if truncation is None else float(truncation)
+    if load_library().spz_amd_tsdf_check(C.byref(v)) != OK:
+        raise ValueError("bad volume: each dimension 2..2048, at most 2^28 lattice points, voxel_size and truncation "
+                         "finite and > 0, lo finite")
+    return v
+
+
+def tsdf_volume_from_box(lo, hi, voxel_size, truncation=None):
+    """The TsdfVolume that covers the box lo..hi at `voxel_size` (spz_amd_tsdf_volume_from_box): dims_a =
+    floor((hi_a - lo_a) / voxel_size) + 2.  ValueError when refused."""
+    lo, hi = [float(x) for x in lo], [float(x) for x in hi]
+    if len(lo) != 3 or len(hi) != 3:
+        raise ValueError("lo and hi must have three values each")
+    v = TsdfVolume()
+    t = 4.0 * float(voxel_size) if truncation is None else float(truncation)
+    if load_library().spz_amd_tsdf_volume_from_box((C.c_double * 3)(*lo), (C.c_double * 3)(*hi), float(voxel_size), t,
+                                                   C.byref(v)) != OK:
+        raise ValueError("bad box or voxel size: hi >= lo, everything finite, voxel_size and truncation > 0, each "
+                         "dimension at most 2048 and at most 2^28 lattice points")
+    return v
+
+
+def mesh_tet_table():
+    """The generated marching-tetrahedra table (spz_amd_mesh_tet_table, host only): corners (6, 4), num_triangles
+    (6, 16) and edges (6, 16, 6) as uint8 arrays."""
+    import numpy as np
+    c, n, e = np.zeros((6, 4), np.uint8), np.zeros((6, 16), np.uint8), np.zeros((6, 16, 6), np.uint8)
+    check(load_library().spz_amd_mesh_tet_table(c.ctypes.data, n.ctypes.data, e.ctypes.data), "spz_amd_mesh_tet_table")
+    return c, n, e
+
+
+MESH_FIELDS = ("box", "voxel_size", "resolution", "truncation", "depth", "min_alpha", "min_weight")
+
+
+def mesh_options(**fields):
+    """spz_amd_mesh_default_options with the given fields (MESH_FIELDS) replaced, checked by spz_amd_mesh_check:
+    ValueError on an unknown field or a refused value.  voxel_size and resolution exclude each other; with neither,
+    resolution = 256."""
+    L = load_library()
+    o = MeshOptions()
+    check(L.spz_amd_mesh_default_options(C.byref(o)), "spz_amd_mesh_default_options")
+    for k in fields:
+        if k not in MESH_FIELDS:
+            raise ValueError(f"mesh: unknown option {k!r} (one of {', '.join(MESH_FIELDS)})")
+    f = {k: x for k, x in fields.items() if x is not None}
+    if "voxel_size" in f and "resolution" in f:
+        raise ValueError("mesh: voxel_size and resolution exclude each other")
+    if "box" in f:
+        box = [float(x) for x in f["box"]]
+        if len(box) != 6:
+            raise ValueError("mesh: box must be (x0, y0, z0, x1, y1, z1)")
+        o.has_box = 1
+        for a in range(6):
+            o.box[a] = box[a]
+    if "voxel_size" in f:
+        o.voxel_size, o.resolution = float(f["voxel_size"]), 0
+        if o.voxel_size == 0.0:
+            raise ValueError("mesh: voxel_size must be > 0")
+    if "resolution" in f:
+        x = f["resolution"]
+        if isinstance(x, bool) or not isinstance(x, int) or not 1 <= x <= 2046:
+            raise ValueError(f"mesh: resolution must be an int in 1..2046, got {x!r}")
+        o.resolution = x
+    if "truncation" in f:
+        o.truncation = float(f["truncation"])
+        if o.truncation == 0.0:
+            raise ValueError("mesh: truncation must be > 0")
+    if "depth" in f:
+        if f["depth"] not in MESH_DEPTH_KINDS:
+            raise ValueError(f"mesh: depth must be 'median' or 'expected', got {f['depth']!r}")
+        o.depth_kind = MESH_DEPTH_KINDS[f["depth"]]
+    for k in ("min_alpha", "min_weight"):
+        if k in f:
+            setattr(o, k, float(f[k]))
+    if L.spz_amd_mesh_check(C.byref(o)) != OK:
+        raise ValueError("mesh: refused options (box hi > lo and finite, voxel_size > 0 or resolution 1..2046, "
+                         "truncation > 0, min_alpha in [0, 1], min_weight > 0)")
+    return o
 
 
 def densify_options(options=None, **fields):

@@ -2,10 +2,10 @@
 // MI355X drop-in layer: ply_to_spz, spz_to_ply, spz_info; and spz_filter (spz::filterSpz),
 // spz_transform (spz::transformSpz), spz_merge (spz::mergeSpz), spz_sort (spz::sortSpz), spz_decimate
 // (spz::decimateSpz), spz_tile (spz::tileSpz), spz_clean (spz::cleanSpz), spz_render (spz::renderSpz), spz_prune
-// (spz::pruneSpz), spz_compare (spz::compareSpz), spz_align (spz::alignSpz), spz_refine (spz::refineSpz) and
-// spz_locate (spz::locateSpz), which have no counterpart in the reference.  One binary, dispatched on argv[0] (the
-// Makefile installs it under the sixteen names) or on a first argument naming the tool.
-// spz_refine and spz_locate exit 0 on success and 1 on a failure.
+// (spz::pruneSpz), spz_compare (spz::compareSpz), spz_align (spz::alignSpz), spz_refine (spz::refineSpz),
+// spz_locate (spz::locateSpz) and spz_mesh (spz::meshSpz), which have no counterpart in the reference.  One binary,
+// dispatched on argv[0] (the Makefile installs it under the seventeen names) or on a first argument naming the tool.
+// spz_refine, spz_locate and spz_mesh exit 0 on success and 1 on a failure.
 // spz_align exits 0 on success, 1 on a failure and 2 when the run ends degenerate; its --output is written by
 // transformSpz, at --fractional-bits (12 unless given, as for spz_transform).
 // spz_compare exits 0 on success, 1 on a failure and 2 when a view misses --min-psnr or --min-ssim.
@@ -904,15 +904,58 @@ int spzLocate(int argc, char **argv) {
   return 0;
 }
 
+const char *kMeshUsage =
+    "Usage: spz_mesh <in.spz> <out.ply> (--views FILE | --orbit N --size W H --fov-y DEG [--center x y z --radius R] "
+    "[--distance K]) [--voxel S | --resolution N] [--box x0 y0 z0 x1 y1 z1] [--truncation T] [--depth median|expected] "
+    "[--min-alpha A] [--min-weight W] [--near Z] [--coord " SPZ_COORD_NAMES "]";
+
+// The file's triangle mesh (spz::meshSpz) as a binary PLY; prints the vertex and triangle counts and the volume.
+int spzMesh(int argc, char **argv) {
+  Args a(argc, argv, kMeshUsage);
+  if (!a.files()) return a.usage();
+  spz::MeshOptions o;
+  ViewArgs va;
+  std::string depth;
+  while (a.next()) {
+    bool good = false;
+    if (va.take(a, &good)) {}
+    else if (a.is("--voxel")) good = a.real(&o.voxelSize.emplace()) && std::isfinite(*o.voxelSize) && *o.voxelSize > 0.0;
+    else if (a.is("--resolution")) good = a.integer(&o.resolution.emplace(), 1, 2046);
+    else if (a.is("--box")) {
+      std::array<double, 6> &b = o.box.emplace();
+      good = a.real(b.data(), 6) && std::all_of(b.begin(), b.end(), [](double v) { return std::isfinite(v); }) &&
+             b[3] > b[0] && b[4] > b[1] && b[5] > b[2];
+    }
+    else if (a.is("--truncation")) good = a.real(&o.truncation.emplace()) && std::isfinite(*o.truncation) && *o.truncation > 0.0;
+    else if (a.is("--depth")) good = a.text(&depth) && (depth == "median" || depth == "expected");
+    else if (a.is("--min-alpha")) good = a.real(&o.minAlpha) && o.minAlpha >= 0.0f && o.minAlpha <= 1.0f;
+    else if (a.is("--min-weight")) good = a.real(&o.minWeight) && std::isfinite(o.minWeight) && o.minWeight > 0.0f;
+    else if (a.is("--near")) good = a.real(&o.nearPlane) && std::isfinite(o.nearPlane) && o.nearPlane > 0.0f;
+    else if (a.is("--coord")) good = a.coord(&o.coord);
+    if (!good) return a.usage();
+  }
+  if (depth == "expected") o.depth = spz::MeshOptions::Expected;
+  if ((a.given("--voxel") && a.given("--resolution")) || !va.consistent(a)) return a.usage();
+  const int vr = va.resolve(a, "spz_mesh", argv[1], o.coord, &o.views);
+  if (vr != 0) return vr == 2 ? a.usage() : 1;
+  spz::TriangleMesh mesh;
+  if (!spz::meshSpz(std::string(argv[1]), o, &mesh)) return 1;
+  if (!spz::saveMeshPly(std::string(argv[2]), mesh)) return 1;
+  std::cout << mesh.vertices.size() / 3 << " vertices, " << mesh.triangles.size() / 3 << " triangles; lattice "
+            << mesh.dims[0] << " x " << mesh.dims[1] << " x " << mesh.dims[2] << " at " << mesh.voxelSize << " from ("
+            << mesh.lo[0] << ", " << mesh.lo[1] << ", " << mesh.lo[2] << "), truncation " << mesh.truncation << std::endl;
+  return 0;
+}
+
 const struct {
   const char *name;
   int (*run)(int, char **);
 } kTools[] = {{"ply_to_spz", plyToSpz},     {"spz_to_ply", spzToPly},         {"spz_info", spzInfo},
               {"spz_filter", spzFilter},    {"spz_transform", spzTransform},  {"spz_merge", spzMerge},
               {"spz_sort", spzSort},        {"spz_decimate", spzDecimate},    {"spz_clean", spzClean},
-              {"spz_render", spzRender},    {"spz_prune", spzPrune},          {"spz_compare", spzCompare},
-              {"spz_tile", spzTile},        {"spz_align", spzAlign},          {"spz_refine", spzRefine},
-              {"spz_locate", spzLocate}};
+              {"spz_render", spzRender},    {"spz_mesh", spzMesh},            {"spz_prune", spzPrune},
+              {"spz_compare", spzCompare},  {"spz_tile", spzTile},            {"spz_align", spzAlign},
+              {"spz_refine", spzRefine},    {"spz_locate", spzLocate}};
 
 int dispatch(const std::string &tool, int argc, char **argv) {
   for (const auto &t : kTools) {

@@ -3242,6 +3242,146 @@ void loadImageFile(const std::string &filename, std::vector<float> *pixels, int 
   *height = static_cast<int>(h);
 }
 
+// ---- mesh --------------------------------------------------------------------------------------------------------
+namespace {
+bool meshOptionsOk(const MeshOptions &o, spz_amd_mesh_options *c, std::vector<spz_amd_render_params> *params) {
+  const char *who = "meshSpz";
+  const int invalid = SPZ_AMD_ERR_INVALID_ARG;
+  spz_amd_mesh_default_options(c);
+  if (o.voxelSize && o.resolution) return opRejected(who, invalid, "set at most one of voxelSize and resolution");
+  if (o.voxelSize) {
+    if (!(*o.voxelSize > 0.0) || !std::isfinite(*o.voxelSize)) return opRejected(who, invalid, "voxelSize must be finite and > 0");
+    c->voxel_size = *o.voxelSize;
+    c->resolution = 0;
+  }
+  if (o.resolution) {
+    if (*o.resolution < 1 || *o.resolution > 2046) return opRejected(who, invalid, "resolution %d is outside 1..2046", *o.resolution);
+    c->resolution = *o.resolution;
+  }
+  if (o.truncation) {
+    if (!(*o.truncation > 0.0) || !std::isfinite(*o.truncation)) return opRejected(who, invalid, "truncation must be finite and > 0");
+    c->truncation = *o.truncation;
+  }
+  if (o.box) {
+    c->has_box = 1;
+    for (int k = 0; k < 6; ++k) c->box[k] = (*o.box)[k];
+  }
+  c->depth_kind = static_cast<int32_t>(o.depth);
+  c->min_alpha = o.minAlpha;
+  c->min_weight = o.minWeight;
+  if (spz_amd_mesh_check(c) != SPZ_AMD_OK) {
+    return opRejected(who, invalid,
+                      "bad options: box finite with x1 > x0, y1 > y0, z1 > z0; depth Median or Expected; minAlpha in [0, 1]; "
+                      "minWeight finite and > 0");
+  }
+  return viewListParams(who, o.views, SPZ_AMD_MESH_MAX_VIEWS, {o.nearPlane, o.coord, nullptr, 3, ", coord valid"}, params);
+}
+}  // namespace
+
+bool meshSpz(const uint8_t *data, int32_t size, const MeshOptions &o, TriangleMesh *mesh) {
+  const char *who = "meshSpz";
+  g_last_status = SPZ_AMD_OK;
+  if (mesh == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no output mesh");
+  spz_amd_mesh_options c;
+  std::vector<spz_amd_render_params> params;
+  if (!meshOptionsOk(o, &c, &params)) return false;
+  Laps laps(who, "SPZ_AMD_MESH_TIMING");
+  DevicePackedGaussians d;
+  if (!loadInput(who, data, size, &d)) return false;
+  laps.lap("inflate");
+  const spz_amd_header hdr = headerOf(d);
+  void *ctx = nullptr;
+  uint64_t counts[2] = {0, 0};
+  spz_amd_tsdf_volume vol = {};
+  float ms[3] = {0.0f, 0.0f, 0.0f};
+  int32_t bad = -1;
+  const int rc = spz_amd_mesh_open(d.stream, d.streamBytes, &hdr, params.data(), static_cast<int>(params.size()), &c,
+                                   d.device, &ctx, counts, &vol, ms, &bad);
+  if (rc == SPZ_AMD_ERR_INVALID_ARG && bad < 0) {
+    return opRejected(who, rc, "no volume: the file has no finite position, the box is empty, or the lattice would "
+                               "have a side above 2048 points or more than 2^28 points");
+  }
+  if (viewsFailed(who, rc, bad)) return false;
+  laps.stage("render", ms[0], (" (" + std::to_string(params.size()) + " views)").c_str());
+  laps.stage("fuse", ms[1]);
+  laps.stage("extract", ms[2]);
+  d.release();
+  TriangleMesh m;
+  detail::resizeUninitialized(&m.vertices, static_cast<size_t>(counts[0]) * 3u);
+  detail::resizeUninitialized(&m.colors, static_cast<size_t>(counts[0]) * 3u);
+  m.triangles.resize(static_cast<size_t>(counts[1]) * 3u);
+  const int frc = spz_amd_mesh_fetch(ctx, m.vertices.data(), m.colors.data(), m.triangles.data());
+  spz_amd_mesh_close(ctx);
+  if (deviceFailed(frc, who)) return false;
+  laps.lap("fetch");
+  for (int k = 0; k < 3; ++k) {
+    m.lo[k] = vol.lo[k];
+    m.dims[k] = vol.dims[k];
+    m.ms[k] = ms[k];
+  }
+  m.voxelSize = vol.voxel_size;
+  m.truncation = vol.truncation;
+  *mesh = std::move(m);
+  return true;
+}
+
+bool meshSpz(const std::string &filename, const MeshOptions &o, TriangleMesh *mesh) {
+  g_last_status = SPZ_AMD_OK;
+  if (mesh == nullptr) return opRejected("meshSpz", SPZ_AMD_ERR_INVALID_ARG, "no output mesh");
+  spz_amd_mesh_options c;
+  std::vector<spz_amd_render_params> params;
+  if (!meshOptionsOk(o, &c, &params)) return false;
+  std::vector<uint8_t> data;
+  if (!readInput("meshSpz", filename, &data)) return false;
+  return meshSpz(data.data(), static_cast<int32_t>(data.size()), o, mesh);
+}
+
+bool saveMeshPly(const std::string &filename, const float *vertices, const float *colors, size_t numVertices,
+                 const uint32_t *triangles, size_t numTriangles) {
+  const char *who = "saveMeshPly";
+  g_last_status = SPZ_AMD_OK;
+  if ((numVertices && (vertices == nullptr || colors == nullptr)) || (numTriangles && triangles == nullptr)) {
+    return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "an array is missing");
+  }
+  if (numVertices > 0xffffffffull) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "more than 2^32 - 1 vertices");
+  for (size_t k = 0; k < numTriangles * 3u; ++k) {
+    if (triangles[k] >= numVertices) {
+      return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "triangle %zu names vertex %u of %zu", k / 3u, triangles[k], numVertices);
+    }
+  }
+  const std::string head = "ply\nformat binary_little_endian 1.0\nelement vertex " + std::to_string(numVertices) +
+                           "\nproperty float x\nproperty float y\nproperty float z\nproperty uchar red\nproperty uchar green\n"
+                           "property uchar blue\nelement face " + std::to_string(numTriangles) +
+                           "\nproperty list uchar uint vertex_indices\nend_header\n";
+  std::vector<uint8_t> bytes(head.size() + numVertices * 15u + numTriangles * 13u);
+  std::memcpy(bytes.data(), head.data(), head.size());
+  uint8_t *at = bytes.data() + head.size();
+  for (size_t v = 0; v < numVertices; ++v) {
+    std::memcpy(at, vertices + 3u * v, 12);  // little-endian hosts only, like the .ply writer of the clouds
+    for (int k = 0; k < 3; ++k) {
+      const float c = colors[3u * v + static_cast<size_t>(k)];
+      const float clamped = c >= 0.0f ? (c <= 1.0f ? c : 1.0f) : 0.0f;  // NaN -> 0
+      at[12 + k] = static_cast<uint8_t>(std::rint(255.0f * clamped));
+    }
+    at += 15;
+  }
+  for (size_t t = 0; t < numTriangles; ++t) {
+    *at = 3;
+    std::memcpy(at + 1, triangles + 3u * t, 12);
+    at += 13;
+  }
+  return writeOutput(who, filename, bytes);
+}
+
+bool saveMeshPly(const std::string &filename, const TriangleMesh &m) {
+  if (m.vertices.size() % 3u != 0 || m.colors.size() != m.vertices.size() || m.triangles.size() % 3u != 0) {
+    g_last_status = SPZ_AMD_OK;
+    return opRejected("saveMeshPly", SPZ_AMD_ERR_INVALID_ARG, "the mesh's arrays do not match");
+  }
+  return saveMeshPly(filename, m.vertices.data(), m.colors.data(), m.vertices.size() / 3u, m.triangles.data(),
+                     m.triangles.size() / 3u);
+}
+
 // ---- align -------------------------------------------------------------------------------------------------------
 namespace {
 bool alignOptionsOk(const AlignOptions &o, spz_amd_align_options *c) {

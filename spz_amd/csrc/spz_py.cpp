@@ -624,6 +624,46 @@ PYBIND11_MODULE(spz, m) {
         "(spz::compareImages; include/spz_amd.h \"image metrics\"): values clamped to [0, 1] (NaN -> 0), the first three "
         "channels, an 11x11 Gaussian window of sigma 1.5 with zero padding.  Returns a dict: mse, psnr, ssim, l1, "
         "max_abs; with return_map also ssim_map, (height, width) float32.");
+  m.def("mesh_spz",
+        [](const py::object &input, const py::object &views, const py::object &box, const py::object &voxel_size,
+           const py::object &resolution, const py::object &truncation, const std::string &depth,
+           const py::object &min_alpha, const py::object &min_weight, float near_plane, spz::CoordinateSystem coord) {
+          const spz::MeshOptions o = meshOptions(views, box, voxel_size, resolution, truncation, depth, min_alpha,
+                                                 min_weight, near_plane, coord);
+          spz::TriangleMesh mesh;
+          if (!callOn(Input(input), [&](auto... file) { return spz::meshSpz(file..., o, &mesh); })) {
+            raiseFailure("mesh_spz");
+          }
+          return meshResult(mesh);
+        },
+        py::arg("input"), py::arg("views"), py::kw_only(), py::arg("box") = py::none(),
+        py::arg("voxel_size") = py::none(), py::arg("resolution") = py::none(), py::arg("truncation") = py::none(),
+        py::arg("depth") = "median", py::arg("min_alpha") = 0.5, py::arg("min_weight") = 1.0, py::arg("near") = 0.2f,
+        py::arg("coord") = spz::CoordinateSystem::UNSPECIFIED,
+        "The triangle mesh of a .spz file (a path or the file's bytes) on the device (spz::meshSpz; the contract is in "
+        "include/spz_amd.h \"mesh\"): the depth maps of `views` (1..1024 dicts as orbit_views returns them, in the frame "
+        "`coord`) fused into a truncated signed distance volume, its zero level set by marching tetrahedra.  box (x0, y0, "
+        "z0, x1, y1, z1): None = the bounding box of the file's positions (floaters inflate it: clean_spz first, or pass "
+        "one).  voxel_size or resolution (cells along the longest side; neither: 256); truncation: None = 4 voxels; "
+        "depth 'median' or 'expected' (then pixels under min_alpha are not fused); min_weight: the views that must have "
+        "seen every corner of a cube.  Returns a dict: vertices (n, 3) float32, colors (n, 3) float32 (not clamped), "
+        "triangles (m, 3) uint32, volume (lo, voxel_size, dims, truncation) and ms (renders, fuses, extraction).");
+  m.def("save_mesh_ply",
+        [](const std::string &path, const py::object &vertices, const py::object &colors, const py::object &triangles) {
+          const FloatArray v = meshFloats(vertices, "vertices"), c = meshFloats(colors, "colors");
+          if (c.shape(0) != v.shape(0)) throw py::value_error("colors must have one row per vertex");
+          const IndexArray t = meshIndices(triangles);
+          if (!unlocked([&] {
+                return spz::saveMeshPly(path, v.data(), c.data(), static_cast<size_t>(v.shape(0)), t.data(),
+                                        static_cast<size_t>(t.shape(0)));
+              })) {
+            raiseFailure("save_mesh_ply", "", path);
+          }
+        },
+        py::arg("path"), py::arg("vertices"), py::arg("colors"), py::arg("triangles"),
+        "Write a triangle mesh as a binary little-endian PLY (spz::saveMeshPly): x y z float, red green blue uchar "
+        "(rint(255 clamp(c, 0, 1))), faces as list uchar uint vertex_indices.  ValueError when an index is not below "
+        "the vertex count.");
   m.def("clean_spz",
         [](const std::string &input, const std::string &output, const py::object &k, const py::object &std_ratio,
            const py::object &radius, const py::object &min_neighbors, const py::object &return_details) -> py::object {

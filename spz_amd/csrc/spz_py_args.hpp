@@ -816,6 +816,82 @@ spz::AlignOptions alignOptions(const py::object &rotation, const py::object &tra
   return o;
 }
 
+// ---- mesh ----------------------------------------------------------------------------------------------------------
+// MeshOptions from mesh_spz's keyword arguments.
+spz::MeshOptions meshOptions(const py::object &views, const py::object &box, const py::object &voxel_size,
+                             const py::object &resolution, const py::object &truncation, const std::string &depth,
+                             const py::object &min_alpha, const py::object &min_weight, float near_plane,
+                             spz::CoordinateSystem coord) {
+  spz::MeshOptions o;
+  finite(near_plane, Bound::Positive, "near must be > 0");
+  o.coord = coord;
+  o.nearPlane = near_plane;
+  if (!voxel_size.is_none() && !resolution.is_none()) throw py::value_error("give voxel_size or resolution, not both");
+  if (!voxel_size.is_none()) o.voxelSize = finiteReal(voxel_size, Bound::Positive, "voxel_size must be a finite number > 0");
+  if (!resolution.is_none()) o.resolution = intIn<int>(resolution, 1, 2046, "resolution must be an int in 1..2046");
+  if (!truncation.is_none()) o.truncation = finiteReal(truncation, Bound::Positive, "truncation must be a finite number > 0");
+  if (depth == "median") {
+    o.depth = spz::MeshOptions::Median;
+  } else if (depth == "expected") {
+    o.depth = spz::MeshOptions::Expected;
+  } else {
+    throw py::value_error("depth must be 'median' or 'expected'");
+  }
+  const double a = finiteReal(min_alpha, Bound::NonNegative, "min_alpha must be a number in [0, 1]");
+  if (a > 1.0) throw py::value_error("min_alpha must be a number in [0, 1]");
+  o.minAlpha = static_cast<float>(a);
+  o.minWeight = static_cast<float>(finiteReal(min_weight, Bound::Positive, "min_weight must be a finite number > 0"));
+  if (!box.is_none()) {
+    const char *what = "box must be six finite numbers x0, y0, z0, x1, y1, z1 with x1 > x0, y1 > y0, z1 > z0";
+    if (py::isinstance<py::str>(box) || !py::isinstance<py::sequence>(box)) throw py::value_error(what);
+    const py::sequence seq = py::reinterpret_borrow<py::sequence>(box);
+    if (seq.size() != 6) throw py::value_error(what);
+    std::array<double, 6> b;
+    for (size_t k = 0; k < 6; ++k) b[k] = finiteReal(seq[k], Bound::Any, what);
+    for (size_t k = 0; k < 3; ++k) {
+      if (!(b[3 + k] > b[k])) throw py::value_error(what);
+    }
+    o.box = b;
+  }
+  o.views = viewList(views, SPZ_AMD_MESH_MAX_VIEWS, coord, near_plane);
+  return o;
+}
+
+// The (n, 3) arrays of a triangle mesh argument: float32 vertices and colours of one length, uint32 triangles below it.
+using IndexArray = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>;
+FloatArray meshFloats(const py::object &o, const char *name) {
+  if (!py::isinstance<py::array>(o)) throw py::value_error(std::string(name) + " must be a numpy array of shape (n, 3)");
+  FloatArray a(o);
+  if (a.ndim() != 2 || a.shape(1) != 3) throw py::value_error(std::string(name) + " must be a numpy array of shape (n, 3)");
+  return a;
+}
+IndexArray meshIndices(const py::object &o) {
+  const char *what = "triangles must be an integer numpy array of shape (n, 3)";
+  if (!py::isinstance<py::array>(o)) throw py::value_error(what);
+  const py::array raw = py::reinterpret_borrow<py::array>(o);
+  if (raw.ndim() != 2 || raw.shape(1) != 3 || (raw.dtype().kind() != 'i' && raw.dtype().kind() != 'u')) {
+    throw py::value_error(what);
+  }
+  return IndexArray(o);
+}
+
+py::dict meshResult(const spz::TriangleMesh &m) {
+  const py::ssize_t nv = static_cast<py::ssize_t>(m.vertices.size() / 3u), nt = static_cast<py::ssize_t>(m.triangles.size() / 3u);
+  py::dict d, vol;
+  d["vertices"] = toArray(m.vertices, {nv, 3});
+  d["colors"] = toArray(m.colors, {nv, 3});
+  py::array_t<uint32_t> tri(std::vector<py::ssize_t>{nt, 3});
+  if (nt) std::memcpy(tri.mutable_data(), m.triangles.data(), m.triangles.size() * sizeof(uint32_t));
+  d["triangles"] = tri;
+  vol["lo"] = py::make_tuple(m.lo[0], m.lo[1], m.lo[2]);
+  vol["voxel_size"] = m.voxelSize;
+  vol["dims"] = py::make_tuple(m.dims[0], m.dims[1], m.dims[2]);
+  vol["truncation"] = m.truncation;
+  d["volume"] = vol;
+  d["ms"] = py::make_tuple(m.ms[0], m.ms[1], m.ms[2]);
+  return d;
+}
+
 // The index of a GaussianCloud array's name among positions, scales, rotations, alphas, colors, sh; `list` ("lrs",
 // "train") names the argument in the ValueError.
 int cloudArrayIndex(const std::string &name, const char *list) {

@@ -1759,6 +1759,121 @@ def locate_packed(stream_t, header, params, target, **options):
                    target, options)
 
 
+def _check_volume(volume):
+    if not isinstance(volume, abi.TsdfVolume):
+        raise ValueError("volume must be an abi.TsdfVolume (abi.tsdf_volume, abi.tsdf_volume_from_box)")
+    abi.check(abi.load_library().spz_amd_tsdf_check(C.byref(volume)), "spz_amd_tsdf_check")
+    return tuple(int(d) for d in volume.dims)
+
+
+def _check_grid(grid, volume):
+    nx, ny, nz = _check_volume(volume)
+    if not isinstance(grid, torch.Tensor) or not grid.is_cuda or grid.dtype != torch.float32 \
+            or not grid.is_contiguous() or tuple(grid.shape) != (5, nz, ny, nx):
+        raise ValueError(f"grid must be a contiguous float32 CUDA tensor of shape (5, {nz}, {ny}, {nx})")
+    return grid.device
+
+
+def tsdf_alloc(volume, device):
+    """A new, all-zero grid of `volume` (an abi.TsdfVolume) on `device`: a (5, nz, ny, nx) float32 tensor, the planes
+    W, S, Cr, Cg, Cb of include/spz_amd.h "mesh"."""
+    nx, ny, nz = _check_volume(volume)
+    return torch.zeros((5, nz, ny, nx), dtype=torch.float32, device=device)
+
+
+def tsdf_integrate(grid, volume, params, depth, image, depth_kind="median", min_alpha=0.5, stream=None):
+    """Fuse one view into `grid` in place (spz_amd_tsdf_integrate_device; the contract is in include/spz_amd.h "mesh").
+    depth (height, width, 2) and image (height, width, 4): float32 CUDA tensors as render_depth(return_image=True)
+    returns them.  depth_kind: "median" or "expected".  Enqueues; returns grid."""
+    L = abi.load_library()
+    dev = _check_grid(grid, volume)
+    _check_render_args(L, params, None)
+    h, w = params.height, params.width
+    for name, t, ch in (("depth", depth, 2), ("image", image, 4)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() \
+                or tuple(t.shape) != (h, w, ch):
+            raise ValueError(f"{name} must be a contiguous float32 tensor of shape ({h}, {w}, {ch}) on {dev}")
+    if depth_kind not in abi.MESH_DEPTH_KINDS:
+        raise ValueError(f"depth_kind must be 'median' or 'expected', got {depth_kind!r}")
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        rc = L.spz_amd_tsdf_integrate_device(C.byref(volume), grid.data_ptr(), C.byref(params), depth.data_ptr(),
+                                             image.data_ptr(), abi.MESH_DEPTH_KINDS[depth_kind], float(min_alpha),
+                                             C.c_void_p(st.cuda_stream))
+    abi.check(rc, "spz_amd_tsdf_integrate_device")
+    return grid
+
+
+def tsdf_extract(grid, volume, min_weight=1.0, stream=None):
+    """The zero level set of `grid` by marching tetrahedra (spz_amd_mesh_count_device, the two counts read back,
+    spz_amd_mesh_emit_device): (vertices (n_v, 3) float32, colors (n_v, 3) float32, triangles (n_t, 3) int32 holding
+    the uint32 vertex numbers) as CUDA tensors, in the fixed order of include/spz_amd.h "mesh"."""
+    L = abi.load_library()
+    dev = _check_grid(grid, volume)
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        with torch.cuda.stream(st):
+            ws = torch.empty(int(L.spz_amd_mesh_workspace_bytes(C.byref(volume))), dtype=torch.uint8, device=dev)
+            counts = torch.empty(2, dtype=torch.int64, device=dev)
+            rc = L.spz_amd_mesh_count_device(C.byref(volume), grid.data_ptr(), float(min_weight), counts.data_ptr(),
+                                             ws.data_ptr(), C.c_void_p(st.cuda_stream))
+            abi.check(rc, "spz_amd_mesh_count_device")
+            nv, nt = (int(x) for x in counts.cpu())  # on st: waits for the scans
+            if nv > 0xffffffff:
+                raise RuntimeError(f"{nv} vertices is above the limit of 2^32 - 1")
+            vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+            colors = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+            triangles = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+            rc = L.spz_amd_mesh_emit_device(C.byref(volume), grid.data_ptr(), nv, nt, nv, nt, vertices.data_ptr(),
+                                            colors.data_ptr(), triangles.data_ptr(), ws.data_ptr(),
+                                            C.c_void_p(st.cuda_stream))
+            abi.check(rc, "spz_amd_mesh_emit_device")
+    return vertices, colors, triangles
+
+
+def volume_dict(volume):
+    """An abi.TsdfVolume as plain values: lo, voxel_size, dims, truncation."""
+    return {"lo": tuple(float(x) for x in volume.lo), "voxel_size": float(volume.voxel_size),
+            "dims": tuple(int(x) for x in volume.dims), "truncation": float(volume.truncation)}
+
+
+def mesh_packed(stream_t, header, views, **options):
+    """The triangle mesh of a packed device stream over `views` (a sequence of abi.RenderParams, one coord):
+    spz_amd_mesh_open (include/spz_amd.h "mesh").  options: abi.MESH_FIELDS (box, voxel_size or resolution, truncation,
+    depth, min_alpha, min_weight).  Blocks; runs on a stream of the library's own after the current stream has
+    drained.  Returns a dict: vertices (n_v, 3) float32, colors (n_v, 3) float32 and triangles (n_t, 3) uint32 numpy
+    arrays, volume (volume_dict) and ms (renders, fuses, extraction).  A bad view raises abi.SpzAmdError whose `view`
+    attribute names it."""
+    import numpy as np
+    L = abi.load_library()
+    _check_stream_tensor(stream_t)
+    dev = stream_t.device
+    views = list(views)
+    if not 1 <= len(views) <= abi.MESH_MAX_VIEWS or not all(isinstance(p, abi.RenderParams) for p in views):
+        raise ValueError(f"views must be 1..{abi.MESH_MAX_VIEWS} abi.RenderParams")
+    opts = abi.mesh_options(**options)
+    arr = (abi.RenderParams * len(views))(*views)
+    ctx, bad, vol = C.c_void_p(), C.c_int32(-1), abi.TsdfVolume()
+    counts, ms = (C.c_uint64 * 2)(), (C.c_float * 3)()
+    torch.cuda.current_stream(dev).synchronize()  # the stream's producers
+    device_index = dev.index if dev.index is not None else torch.cuda.current_device()
+    rc = L.spz_amd_mesh_open(stream_t.data_ptr(), stream_t.numel(), C.byref(header), arr, len(views), C.byref(opts),
+                             device_index, C.byref(ctx), counts, C.byref(vol), ms, C.byref(bad))
+    if rc != abi.OK:
+        err = abi.SpzAmdError(rc, "spz_amd_mesh_open" + (f" (view {bad.value})" if bad.value >= 0 else ""))
+        err.view = bad.value
+        raise err
+    try:
+        vertices = np.empty((counts[0], 3), np.float32)
+        colors = np.empty((counts[0], 3), np.float32)
+        triangles = np.empty((counts[1], 3), np.uint32)
+        abi.check(L.spz_amd_mesh_fetch(ctx, vertices.ctypes.data, colors.ctypes.data, triangles.ctypes.data),
+                  "spz_amd_mesh_fetch")
+    finally:
+        L.spz_amd_mesh_close(ctx)
+    return {"vertices": vertices, "colors": colors, "triangles": triangles, "volume": volume_dict(vol), "ms": tuple(ms)}
+
+
 def convert_coordinates(cloud, num_points, sh_degree, from_coord, to_coord, stream=None):
     """In-place GaussianCloud::convertCoordinates on device tensors (positions, rotations, sh)."""
     L = abi.load_library()
@@ -1788,4 +1903,5 @@ __all__ = ["encode", "decode", "encode_shard", "decode_shard", "decode_gather", 
            "alloc_cloud", "image_loss", "adam_step", "refine_packed",
            "densify_accumulate", "densify_plan", "densify_apply", "reset_opacity",
            "render_view_backward", "image_halve", "locate", "locate_packed",
+           "tsdf_alloc", "tsdf_integrate", "tsdf_extract", "mesh_packed",
            "make_header", "to_device", "to_numpy", "SH_DIM"]
