@@ -1287,6 +1287,97 @@ int spz_amd_refine_densify_open(const uint8_t *d_stream_a, size_t size_a, const 
                                 spz_amd_densify_round *h_rounds, int rounds_capacity, int *h_num_rounds,
                                 uint32_t *h_origin);
 
+/* ---- photo loss: the image loss of a render against a photograph, with per-pixel weights and a per-image exposure of
+ *      the render (spz_photo.hip; DESIGN §8 "Fit").  The reference has no counterpart.  Everything "image loss" says
+ *      holds unless this says otherwise; a, b, d_loss and d_grad are its arguments.
+ *      Exposure.  h_exposure (host memory): 12 doubles, row-major [M | o], 3DGS's 3 x 4 colour transform of one image;
+ *      every value finite.  NULL: the identity, and nothing is multiplied.  The exposed render of a pixel is t_c =
+ *      ((o_c + M_c0 a_0) + M_c1 a_1) + M_c2 a_2 in f64 from the f32 values; a' = t clamped to [0, 1], NaN -> 0; the gate
+ *      of (pixel, channel) is open where 0 <= t <= 1, both ends included, and closed elsewhere and for NaN.
+ *      Weights.  d_weight (device memory): height x width float32, NULL: every weight 1.  Each is clamped to [0, 1],
+ *      NaN -> 0.  W = sum_p w_p in f64.
+ *      Loss.  L = (1 - lambda) l1 + lambda (1 - ssim), l1 = sum_p w_p sum_c |a'_pc - b_pc| / (3 W), ssim = sum_p w_p
+ *      sum_c S_pc / (3 W), S the per-pixel, per-channel SSIM of "image metrics" over the UNWEIGHTED 11 x 11 zero-padded
+ *      windows of a' and the clamped b.  W == 0: L = l1 = 0, ssim = 1, and every gradient is exactly 0.
+ *      Gradient to the exposed render: image loss's formulas with w_p / (3 W) for 1 / (3 H W) in the L1 part, and the
+ *      maps M, Q, P multiplied by w_q before they are filtered, then divided by 3 W.  A pixel of weight 0 still gets
+ *      gradient from the windows centred on weighted neighbours: that is the derivative.
+ *      d_grad = dL/da = M^T (gate . dL/da') in the rgb channels, each value summed in f64 over the open gates in channel
+ *      order and rounded once to f32; without an exposure gate . dL/da' itself.  A fourth channel gets exactly 0; every
+ *      element is written.  d_exposure_grad (device memory, 8-aligned, 12 doubles, row-major as h_exposure; required
+ *      with h_exposure, else it may be NULL): dL/dM_ck = sum_p gate_pc dL/da'_pc a_pk, dL/do_c = sum_p gate_pc
+ *      dL/da'_pc.  A (pixel, channel) whose gate is closed is skipped, not multiplied by zero (its a may be infinite: a
+ *      non-finite a_k makes every t_c of its pixel infinite or NaN, which closes all three gates); a term whose a_pk is
+ *      not finite is skipped as well, which matters without an exposure, where the gate of channel c is that of a_c
+ *      alone.
+ *      Arithmetic.  The image loss's two passes with the products above, every one an f64 product, then a reduction of
+ *      the 12 sums: per tile over the wave, the waves in order, one row of `tiles` per value, summed by one workgroup in
+ *      a fixed order.  No float atomics: a run repeats its bits.  With d_weight == NULL and h_exposure == NULL every
+ *      product is by 1.0, W = H W exactly, and d_loss and d_grad carry exactly the bits of image_loss_device.  The
+ *      exposure path reads a's three channels for each channel it forms: a is read once more than the loss reads it.
+ *      photo_loss_workspace_bytes (host only; 0 for a bad size): 72 H W bytes, the slab, and 96 bytes per tile.
+ *      photo_loss_device: arguments checked on the host before any launch (SPZ_AMD_ERR_INVALID_ARG; no device:
+ *      SPZ_AMD_ERR_NO_DEVICE); enqueues on hip_stream and does not synchronise.
+ *      image_exposure_device: out_c = ((o_c + M_c0 a_0) + M_c1 a_1) + M_c2 a_2, unclamped, in f32 with the 12 values
+ *      rounded to f32 first, each operation rounded once in that order, none contracted.  channels in {3, 4}; a fourth
+ *      channel is copied; d_out == d_in is allowed.  h_exposure NULL or not finite: SPZ_AMD_ERR_INVALID_ARG.
+ *
+ * ---- refine images: a packed stream fitted to photographs (spz_refine.hip; DESIGN §8 "Fit").  "refine" and "densify"
+ *      with the targets given instead of rendered: there is no stream B.  d_targets: a host array of num_views device
+ *      pointers, target v height_v x width_v x channels float32 of view v's size, channels in {3, 4}; d_weights: NULL, or
+ *      a host array of num_views device pointers to height_v x width_v float32, any of them NULL (photo loss's weights).
+ *      A NULL or misaligned target, a misaligned weight map, or a view larger than image_metrics_check allows:
+ *      SPZ_AMD_ERR_INVALID_ARG with the view in *h_bad_view; channels outside {3, 4}: SPZ_AMD_ERR_INVALID_ARG.  The
+ *      targets are used in place and must stay until the call returns; the block no longer holds 16 W H bytes per view.
+ *      photo (photo_default_options: fit_exposure 0, lr_exposure 0.01, 3DGS's exposure_lr_init; photo_check, host only:
+ *      fit_exposure 0 or 1, lr_exposure >= 0 and finite).  densify: NULL, or as refine_densify_open; with interval > 0
+ *      max_points == 0 is refused (SPZ_AMD_ERR_INVALID_ARG): there is no target count to default to.
+ *      Run.  Iteration i uses view v = i mod V: the render; photo_loss with view v's weights and, with fit_exposure,
+ *      view v's exposure read from device memory; render_backward_device with that d_grad; then everything refine does.
+ *      With fit_exposure view v's 12 values then take one Adam step in f64 on the device (one workgroup; m' = beta1 m +
+ *      (1 - beta1) g, v' = beta2 v + ((1 - beta2) g) g, e' = e - lr_exposure / (1 - beta1^t) (m' / (sqrt(v') / sqrt(1 -
+ *      beta2^t) + eps)), with options' betas and eps and t the number of visits of that view, from 1; a non-finite
+ *      gradient value leaves its element alone): the loop gains no host synchronisation.  Exposures start at the
+ *      identity and are never written into the file.  Without fit_exposure no exposure is applied anywhere.
+ *      h_history[i] = L before step i.  h_before: image_metrics_device of A's packed render against the target,
+ *      unweighted, identity exposure.  h_after: the OUTPUT STREAM's packed render, passed through that view's fitted
+ *      exposure with image_exposure_device when fit_exposure is set, against the target, unweighted.  h_exposures (may
+ *      be NULL): 12 doubles per view, exactly the identity without fit_exposure.  The other outputs are
+ *      refine_densify_open's; the result is fetched and closed with refine_fetch, refine_device_data, refine_close.
+ *      refine_images_host_open: the same with the images and weight maps in host memory (h_targets, h_weights, shaped
+ *      as above): views, options and photo are checked first, then the images are copied to `device` and kept there
+ *      until the call returns. */
+typedef struct {
+  int32_t fit_exposure; /* 0 or 1 */
+  int32_t reserved;
+  double lr_exposure;   /* 0.01 */
+} spz_amd_photo_options;
+uint64_t spz_amd_photo_loss_workspace_bytes(int width, int height);
+int spz_amd_photo_loss_device(const float *d_a, int channels_a, const float *d_b, int channels_b, const float *d_weight,
+                              const double *h_exposure, int width, int height, double lambda_dssim, double *d_loss,
+                              float *d_grad, double *d_exposure_grad, void *d_workspace, void *hip_stream);
+int spz_amd_image_exposure_device(const float *d_in, int channels, const double *h_exposure, int width, int height,
+                                  float *d_out, void *hip_stream);
+int spz_amd_photo_default_options(spz_amd_photo_options *options);
+int spz_amd_photo_check(const spz_amd_photo_options *options);
+int spz_amd_refine_images_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
+                               const spz_amd_render_params *views, int num_views, const float *const *d_targets,
+                               int channels, const float *const *d_weights, const spz_amd_refine_options *options,
+                               const spz_amd_photo_options *photo, const spz_amd_densify_options *densify, int device,
+                               void **ctx, uint64_t *h_out_bytes, double *h_history, spz_amd_image_metrics *h_before,
+                               spz_amd_image_metrics *h_after, uint64_t *h_skipped, float *h_ms, int32_t *h_bad_view,
+                               uint64_t *h_num_points, spz_amd_densify_round *h_rounds, int rounds_capacity,
+                               int *h_num_rounds, uint32_t *h_origin, double *h_exposures);
+int spz_amd_refine_images_host_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
+                                    const spz_amd_render_params *views, int num_views, const float *const *h_targets,
+                                    int channels, const float *const *h_weights, const spz_amd_refine_options *options,
+                                    const spz_amd_photo_options *photo, const spz_amd_densify_options *densify,
+                                    int device, void **ctx, uint64_t *h_out_bytes, double *h_history,
+                                    spz_amd_image_metrics *h_before, spz_amd_image_metrics *h_after, uint64_t *h_skipped,
+                                    float *h_ms, int32_t *h_bad_view, uint64_t *h_num_points,
+                                    spz_amd_densify_round *h_rounds, int rounds_capacity, int *h_num_rounds,
+                                    uint32_t *h_origin, double *h_exposures);
+
 /* ---- render view backward: the gradient of one view to its camera (spz_render_view_backward.hip; DESIGN §8
  *      "Locate").  The reference has no counterpart.  Given the n x 9 record gradients of a view (mean 2, conic 3,
  *      opacity 1, rgb 3, as "render backward" forms them), it produces the gradient of the same scalar loss to the 12

@@ -608,6 +608,38 @@ bool refineSpz(const std::vector<uint8_t> &data, const std::vector<uint8_t> &tar
                std::vector<uint8_t> *out, RefineReport *report = nullptr);
 bool refineSpz(const std::string &inputFilename, const std::string &targetFilename, const std::string &outputFilename,
                const RefineOptions &options, RefineReport *report = nullptr);
+// Fit (DESIGN §8 "Fit"): refineSpz against photographs instead of a target file (include/spz_amd.h "photo loss" and
+// "refine images" state the contract).  images: one per view of `options.views`, of the view's size: pixels height x
+// width x channels float32 (channels 3 or 4, the same for all), rows top to bottom, values in [0, 1] (loadImageFile);
+// weights: null, or height x width float32 in [0, 1], what each pixel counts in the loss (an object mask, the sky, the
+// rim of an undistorted frame).  fitExposure: a 3 x 4 colour transform [M | o] per image is fitted beside the cloud, as
+// 3DGS does for auto-exposure and white balance, at rate exposureLr; the exposures start at the identity, come back in
+// the report, and are never written into the file.  Every option of RefineOptions holds as in refineSpz; positionLr
+// unset: 1.6e-4 times the radius of boundingSphere of the INPUT's positions; densify needs maxPoints (there is no
+// target count).  The report's "before" is the input's render against the images, "after" the written stream's render,
+// passed through that image's fitted exposure when fitExposure is set, against the images, both unweighted.  false + one
+// "[SPZ ERROR] refineSpzToImages: …" line as refineSpz; an image whose size is not its view's names the view and both
+// sizes.  SPZ_AMD_REFINE_TIMING=1 prints the stages' times.
+struct PhotoImage {
+  const float *pixels = nullptr;
+  int width = 0, height = 0, channels = 3;
+  const float *weights = nullptr;
+};
+struct PhotoOptions {
+  std::vector<PhotoImage> images;
+  bool fitExposure = false;
+  double exposureLr = 0.01;  // 3DGS's exposure_lr_init
+};
+struct PhotoReport {
+  RefineReport refine;
+  std::vector<std::array<double, 12>> exposures;  // per view, row-major [M | o]
+};
+bool refineSpzToImages(const uint8_t *data, int32_t size, const RefineOptions &options, const PhotoOptions &photo,
+                       std::vector<uint8_t> *out, PhotoReport *report = nullptr);
+bool refineSpzToImages(const std::vector<uint8_t> &data, const RefineOptions &options, const PhotoOptions &photo,
+                       std::vector<uint8_t> *out, PhotoReport *report = nullptr);
+bool refineSpzToImages(const std::string &inputFilename, const std::string &outputFilename, const RefineOptions &options,
+                       const PhotoOptions &photo, PhotoReport *report = nullptr);
 // Locate (DESIGN §8 "Locate"): the pose of the camera that took a picture of the scene in a file, from a rough guess
 // (include/spz_amd.h "render view backward" and "locate" state the contract).  initial: the view with the rough pose, in
 // the `coord` frame; image: height x width x channels float32 (channels 3 or 4), the picture, in the render's

@@ -95,6 +95,9 @@ EXPORTS = (
     "spz_amd_densify_accumulate_device", "spz_amd_densify_plan_workspace_bytes", "spz_amd_densify_plan_device",
     "spz_amd_densify_plan_host", "spz_amd_densify_apply_device", "spz_amd_densify_reset_opacity_device",
     "spz_amd_refine_densify_open",
+    "spz_amd_photo_loss_workspace_bytes", "spz_amd_photo_loss_device", "spz_amd_image_exposure_device",
+    "spz_amd_photo_default_options", "spz_amd_photo_check", "spz_amd_refine_images_open",
+    "spz_amd_refine_images_host_open",
     "spz_amd_render_records_backward_device", "spz_amd_render_view_backward_workspace_bytes",
     "spz_amd_render_view_backward_device",
     "spz_amd_locate_default_options", "spz_amd_locate_check", "spz_amd_locate_level_params",
@@ -206,6 +209,13 @@ class RefineOptions(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("train_mask", C.c_uint32), ("lambda_dssim", C.c_double),
                 ("lr", C.c_double * 6), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
 
+
+class PhotoOptions(C.Structure):
+    """spz_amd_photo_options (include/spz_amd.h "refine images")."""
+    _fields_ = [("fit_exposure", C.c_int32), ("reserved", C.c_int32), ("lr_exposure", C.c_double)]
+
+
+EXPOSURE_IDENTITY = (1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0)   # row-major [M | o]
 
 LOCATE_MAX_LEVELS = 8
 
@@ -717,6 +727,26 @@ def bind(L):
                                               C.POINTER(ImageMetrics), C.POINTER(ImageMetrics), C.POINTER(u64), vp,
                                               C.POINTER(C.c_int32), C.POINTER(u64), C.POINTER(DensifyRound), i32,
                                               C.POINTER(C.c_int32), vp]
+    L.spz_amd_photo_loss_workspace_bytes.restype = u64
+    L.spz_amd_photo_loss_workspace_bytes.argtypes = [i32, i32]
+    L.spz_amd_photo_loss_device.restype = i32
+    L.spz_amd_photo_loss_device.argtypes = [vp, i32, vp, i32, vp, C.POINTER(C.c_double), i32, i32, C.c_double, vp, vp,
+                                            vp, vp, vp]
+    L.spz_amd_image_exposure_device.restype = i32
+    L.spz_amd_image_exposure_device.argtypes = [vp, i32, C.POINTER(C.c_double), i32, i32, vp, vp]
+    L.spz_amd_photo_default_options.restype = i32
+    L.spz_amd_photo_default_options.argtypes = [C.POINTER(PhotoOptions)]
+    L.spz_amd_photo_check.restype = i32
+    L.spz_amd_photo_check.argtypes = [C.POINTER(PhotoOptions)]
+    L.spz_amd_refine_images_open.restype = i32
+    L.spz_amd_refine_images_open.argtypes = [vp, sz, C.POINTER(Header), C.POINTER(RenderParams), i32,
+                                             C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(RefineOptions),
+                                             C.POINTER(PhotoOptions), C.POINTER(DensifyOptions), i32, C.POINTER(vp),
+                                             C.POINTER(u64), vp, C.POINTER(ImageMetrics), C.POINTER(ImageMetrics),
+                                             C.POINTER(u64), vp, C.POINTER(C.c_int32), C.POINTER(u64),
+                                             C.POINTER(DensifyRound), i32, C.POINTER(C.c_int32), vp, vp]
+    L.spz_amd_refine_images_host_open.restype = i32
+    L.spz_amd_refine_images_host_open.argtypes = L.spz_amd_refine_images_open.argtypes
     L.spz_amd_render_records_backward_device.restype = i32
     L.spz_amd_render_records_backward_device.argtypes = [u64, C.POINTER(RenderParams), u64, vp, vp, vp, vp, vp]
     L.spz_amd_render_view_backward_workspace_bytes.restype = u64
@@ -910,6 +940,32 @@ def refine_options(iterations, *, lambda_dssim=None, lrs=None, beta1=None, beta2
     if train is not None:
         o.train_mask = train_mask(train)
     return o
+
+
+def photo_options(fit_exposure=False, lr_exposure=None):
+    """spz_amd_photo_default_options with the given fields replaced, checked by spz_amd_photo_check: ValueError on a
+    refused value."""
+    L = load_library()
+    o = PhotoOptions()
+    check(L.spz_amd_photo_default_options(C.byref(o)), "spz_amd_photo_default_options")
+    if not isinstance(fit_exposure, (bool, int)):
+        raise ValueError(f"fit_exposure must be a bool, got {fit_exposure!r}")
+    o.fit_exposure = 1 if fit_exposure else 0
+    if lr_exposure is not None:
+        o.lr_exposure = float(lr_exposure)
+    if L.spz_amd_photo_check(C.byref(o)) != OK:
+        raise ValueError(f"lr_exposure must be a finite number >= 0, got {lr_exposure!r}")
+    return o
+
+
+def exposure_values(exposure):
+    """The 12 doubles [M | o], row-major, of a (3, 4) array-like (or 12 numbers) as a ctypes array: ValueError when
+    it has another size or a value is not finite."""
+    import numpy as np
+    e = np.asarray(exposure, dtype=np.float64).reshape(-1)
+    if e.size != 12 or not np.isfinite(e).all():
+        raise ValueError("exposure must be 12 finite numbers, a row-major 3 x 4 [M | o]")
+    return (C.c_double * 12)(*e.tolist())
 
 
 LOCATE_FIELDS = ("iterations", "levels", "lambda_dssim", "lr_rotation", "lr_translation", "lr_final_factor", "beta1",

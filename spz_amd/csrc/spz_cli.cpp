@@ -654,29 +654,28 @@ int spzCompare(int argc, char **argv) {
   return missed ? 2 : 0;
 }
 
+// The options spz_refine and spz_fit share, as their usage lines spell them.
+#define SPZ_REFINE_OPTION_NAMES                                                                                         \
+  "[--iters N] [--lambda-dssim L] [--lr-positions X] [--lr-scales X] [--lr-rotations X] "                              \
+  "[--lr-alphas X] [--lr-colors X] [--lr-sh X] [--train positions,scales,rotations,alphas,colors,sh] "                  \
+  "[--coord " SPZ_COORD_NAMES "] [--background r g b] [--max-sh-degree D] [--near Z] [--densify-interval N "            \
+  "[--densify-from I] [--densify-until I] [--grad-threshold X] [--percent-dense X] [--extent X] [--min-opacity X] "     \
+  "[--max-scale X] [--max-points N] [--opacity-reset-interval N] [--seed S]]"
+
 const char *kRefineUsage =
     "Usage: spz_refine <in.spz> <target.spz> <out.spz> (--views FILE | --orbit N --size W H --fov-y DEG [--center x y z "
-    "--radius R] [--distance K]) [--iters N] [--lambda-dssim L] [--lr-positions X] [--lr-scales X] [--lr-rotations X] "
-    "[--lr-alphas X] [--lr-colors X] [--lr-sh X] [--train positions,scales,rotations,alphas,colors,sh] "
-    "[--coord " SPZ_COORD_NAMES "] [--background r g b] [--max-sh-degree D] [--near Z] [--densify-interval N "
-    "[--densify-from I] [--densify-until I] [--grad-threshold X] [--percent-dense X] [--extent X] [--min-opacity X] "
-    "[--max-scale X] [--max-points N] [--opacity-reset-interval N] [--seed S]]";
+    "--radius R] [--distance K]) " SPZ_REFINE_OPTION_NAMES;
 
-// One line per view with its PSNR and SSIM before and after, then their means.  An orbit without --center is taken
-// around the target.  With --densify-interval N (alone: from = N, until = iterations / 2) one line per densify round
-// and the final count follow.
-int spzRefine(int argc, char **argv) {
-  Args a(argc, argv, kRefineUsage);
-  if (!a.files(3)) return a.usage();
-  spz::RefineOptions o;
-  ViewArgs va;
+// Those options' parsing: take() reads the current one into `o` (false: it is not one of them), finish() settles the
+// densify defaults and --train once all are read (false: a usage error).
+struct RefineArgs {
   std::string train;
-  spz::DensifyOptions &dn = o.densify;
-  auto rate = [&](double *x) { return a.real(x) && std::isfinite(*x) && *x >= 0.0; };
-  while (a.next()) {
+
+  bool take(Args &a, spz::RefineOptions &o, bool *ok) {
+    spz::DensifyOptions &dn = o.densify;
+    auto rate = [&](double *x) { return a.real(x) && std::isfinite(*x) && *x >= 0.0; };
     bool good = false;
-    if (va.take(a, &good)) {}
-    else if (a.is("--iters")) good = a.integer(&o.iterations, 0, 0x7fffffff);
+    if (a.is("--iters")) good = a.integer(&o.iterations, 0, 0x7fffffff);
     else if (a.is("--lambda-dssim")) good = a.real(&o.lambdaDssim) && o.lambdaDssim >= 0.0 && o.lambdaDssim <= 1.0;
     else if (a.is("--lr-positions")) good = rate(&o.positionLr.emplace());
     else if (a.is("--lr-scales")) good = rate(&o.scaleLr);
@@ -700,37 +699,44 @@ int spzRefine(int argc, char **argv) {
     else if (a.is("--max-scale")) good = rate(&dn.maxScale);
     else if (a.is("--max-points")) good = a.integer(&dn.maxPoints, 0, 0x7fffffff);
     else if (a.is("--seed")) good = a.integer(&dn.seed, 0, UINT64_MAX);
-    if (!good) return a.usage();
+    else return false;
+    *ok = good;
+    return true;
   }
-  if (!va.consistent(a)) return a.usage();
-  static const char *const kDensifyOnly[] = {"--densify-from", "--densify-until", "--grad-threshold", "--percent-dense",
-                                             "--extent", "--min-opacity", "--max-scale", "--max-points",
-                                             "--opacity-reset-interval", "--seed"};
-  for (const char *name : kDensifyOnly) {
-    if (a.given(name) && !a.given("--densify-interval")) return a.usage();
-  }
-  if (dn.interval > 0) {
-    if (!a.given("--densify-from")) dn.fromIter = dn.interval;
-    if (!a.given("--densify-until")) dn.untilIter = std::max(dn.fromIter, o.iterations / 2);
-    if (dn.untilIter < dn.fromIter) return a.usage();
-  }
-  if (a.given("--train")) {
-    static const char *const kArrays[6] = {"positions", "scales", "rotations", "alphas", "colors", "sh"};
-    o.train = 0;
-    size_t at = 0;
-    while (at <= train.size()) {
-      const size_t comma = std::min(train.find(',', at), train.size());
-      const std::string name = train.substr(at, comma - at);
-      const auto *n = std::find(std::begin(kArrays), std::end(kArrays), name);
-      if (n == std::end(kArrays)) return a.usage();
-      o.train |= 1u << (n - std::begin(kArrays));
-      at = comma + 1;
+
+  bool finish(Args &a, spz::RefineOptions &o) {
+    spz::DensifyOptions &dn = o.densify;
+    static const char *const kDensifyOnly[] = {"--densify-from", "--densify-until", "--grad-threshold", "--percent-dense",
+                                               "--extent", "--min-opacity", "--max-scale", "--max-points",
+                                               "--opacity-reset-interval", "--seed"};
+    for (const char *name : kDensifyOnly) {
+      if (a.given(name) && !a.given("--densify-interval")) return false;
     }
+    if (dn.interval > 0) {
+      if (!a.given("--densify-from")) dn.fromIter = dn.interval;
+      if (!a.given("--densify-until")) dn.untilIter = std::max(dn.fromIter, o.iterations / 2);
+      if (dn.untilIter < dn.fromIter) return false;
+    }
+    if (a.given("--train")) {
+      static const char *const kArrays[6] = {"positions", "scales", "rotations", "alphas", "colors", "sh"};
+      o.train = 0;
+      size_t at = 0;
+      while (at <= train.size()) {
+        const size_t comma = std::min(train.find(',', at), train.size());
+        const std::string name = train.substr(at, comma - at);
+        const auto *n = std::find(std::begin(kArrays), std::end(kArrays), name);
+        if (n == std::end(kArrays)) return false;
+        o.train |= 1u << (n - std::begin(kArrays));
+        at = comma + 1;
+      }
+    }
+    return true;
   }
-  const int vr = va.resolve(a, "spz_refine", argv[2], o.coord, &o.views);
-  if (vr != 0) return vr == 2 ? a.usage() : 1;
-  spz::RefineReport r;
-  if (!spz::refineSpz(std::string(argv[1]), std::string(argv[2]), std::string(argv[3]), o, &r)) return 1;
+};
+
+// spz_refine's and spz_fit's lines: one per view with its PSNR and SSIM before and after, then their means and the
+// loss; with densify one line per round and the final count.
+void printRefineReport(const spz::RefineReport &r, const spz::DensifyOptions &dn) {
   double sums[4] = {0.0, 0.0, 0.0, 0.0};
   for (size_t v = 0; v < r.before.size(); ++v) {
     std::printf("view %zu psnr %.17g -> %.17g ssim %.17g -> %.17g\n", v, r.before[v].psnr, r.after[v].psnr,
@@ -756,6 +762,123 @@ int spzRefine(int argc, char **argv) {
     std::printf("points %llu\n", static_cast<unsigned long long>(r.numPoints));
   }
   std::fflush(stdout);
+}
+
+// One line per view with its PSNR and SSIM before and after, then their means.  An orbit without --center is taken
+// around the target.  With --densify-interval N (alone: from = N, until = iterations / 2) one line per densify round
+// and the final count follow.
+int spzRefine(int argc, char **argv) {
+  Args a(argc, argv, kRefineUsage);
+  if (!a.files(3)) return a.usage();
+  spz::RefineOptions o;
+  ViewArgs va;
+  RefineArgs ra;
+  while (a.next()) {
+    bool good = false;
+    if (va.take(a, &good)) {}
+    else if (ra.take(a, o, &good)) {}
+    if (!good) return a.usage();
+  }
+  if (!va.consistent(a) || !ra.finish(a, o)) return a.usage();
+  const int vr = va.resolve(a, "spz_refine", argv[2], o.coord, &o.views);
+  if (vr != 0) return vr == 2 ? a.usage() : 1;
+  spz::RefineReport r;
+  if (!spz::refineSpz(std::string(argv[1]), std::string(argv[2]), std::string(argv[3]), o, &r)) return 1;
+  printRefineReport(r, o.densify);
+  return 0;
+}
+
+const char *kFitUsage =
+    "Usage: spz_fit <in.spz> <out.spz> --views FILE --images a.ppm|a.pfm [b ...] [--masks m.ppm|m.pfm [n ...]] "
+    "[--fit-exposure [--lr-exposure X] [--exposures-out FILE]] " SPZ_REFINE_OPTION_NAMES;
+
+// spz_refine against photographs: image i (and mask i, whose first channel is the weight) belongs to view i of the
+// views file, as spz_locate writes it.  Prints spz_refine's lines; --exposures-out writes one line of 12 numbers
+// [M | o], row-major, per view.
+int spzFit(int argc, char **argv) {
+  Args a(argc, argv, kFitUsage);
+  if (!a.files(2)) return a.usage();
+  spz::RefineOptions o;
+  spz::PhotoOptions p;
+  RefineArgs ra;
+  std::string viewsFile, exposuresOut;
+  std::vector<std::string> images, masks;
+  std::vector<std::string> *list = nullptr;  // the list a bare argument continues
+  while (a.next()) {
+    if (list != nullptr && a.arg()[0] != '-') {
+      list->push_back(a.arg());
+      continue;
+    }
+    list = nullptr;
+    bool good = false;
+    if (a.is("--views")) good = a.text(&viewsFile);
+    else if (a.is("--images")) good = a.text(&images.emplace_back()) && (list = &images) != nullptr;
+    else if (a.is("--masks")) good = a.text(&masks.emplace_back()) && (list = &masks) != nullptr;
+    else if (a.is("--fit-exposure")) good = p.fitExposure = true;
+    else if (a.is("--lr-exposure")) good = a.real(&p.exposureLr) && std::isfinite(p.exposureLr) && p.exposureLr >= 0.0;
+    else if (a.is("--exposures-out")) good = a.text(&exposuresOut);
+    else if (ra.take(a, o, &good)) {}
+    if (!good) return a.usage();
+  }
+  if (!a.given("--views") || !a.given("--images") || !ra.finish(a, o)) return a.usage();
+  if ((a.given("--lr-exposure") || a.given("--exposures-out")) && !p.fitExposure) return a.usage();
+  try {
+    o.views = spz::loadViewsFile(viewsFile);
+  } catch (const std::invalid_argument &e) {
+    std::cerr << "[SPZ ERROR] spz_fit: " << e.what() << std::endl;
+    return 1;
+  }
+  if (o.views.size() != images.size() || (!masks.empty() && masks.size() != images.size())) {
+    std::cerr << "[SPZ ERROR] spz_fit: " << o.views.size() << " views but " << images.size() << " images"
+              << (masks.empty() ? std::string() : " and " + std::to_string(masks.size()) + " masks") << std::endl;
+    return a.usage();
+  }
+  std::vector<std::vector<float>> pixels(images.size()), weights(masks.size());
+  for (size_t v = 0; v < images.size(); ++v) {
+    for (int kind = 0; kind < (masks.empty() ? 1 : 2); ++kind) {
+      const std::string &file = kind == 0 ? images[v] : masks[v];
+      std::vector<float> rgb;
+      int w = 0, h = 0;
+      try {
+        spz::loadImageFile(file, &rgb, &w, &h);
+      } catch (const std::invalid_argument &e) {
+        std::cerr << "[SPZ ERROR] spz_fit: " << e.what() << std::endl;
+        return 1;
+      }
+      if (w != o.views[v].width || h != o.views[v].height) {
+        std::cerr << "[SPZ ERROR] spz_fit: view " << v << " is " << o.views[v].width << " x " << o.views[v].height
+                  << " but " << file << " is " << w << " x " << h << std::endl;
+        return 1;
+      }
+      if (kind == 0) {
+        pixels[v].swap(rgb);
+      } else {  // the first channel
+        weights[v].resize(static_cast<size_t>(w) * static_cast<size_t>(h));
+        for (size_t k = 0; k < weights[v].size(); ++k) weights[v][k] = rgb[3 * k];
+      }
+    }
+    p.images.push_back(spz::PhotoImage{pixels[v].data(), o.views[v].width, o.views[v].height, 3,
+                                       masks.empty() ? nullptr : weights[v].data()});
+  }
+  spz::PhotoReport r;
+  if (!spz::refineSpzToImages(std::string(argv[1]), std::string(argv[2]), o, p, &r)) return 1;
+  printRefineReport(r.refine, o.densify);
+  if (!exposuresOut.empty()) {
+    std::ofstream out(exposuresOut);
+    char buf[64];
+    for (const std::array<double, 12> &e : r.exposures) {
+      for (size_t k = 0; k < 12; ++k) {
+        std::snprintf(buf, sizeof(buf), "%.17g", e[k]);
+        out << (k ? " " : "") << buf;
+      }
+      out << "\n";
+    }
+    out.flush();
+    if (!out) {
+      std::cerr << "[SPZ ERROR] spz_fit: unable to write " << exposuresOut << std::endl;
+      return 1;
+    }
+  }
   return 0;
 }
 
@@ -955,7 +1078,7 @@ const struct {
               {"spz_sort", spzSort},        {"spz_decimate", spzDecimate},    {"spz_clean", spzClean},
               {"spz_render", spzRender},    {"spz_mesh", spzMesh},            {"spz_prune", spzPrune},
               {"spz_compare", spzCompare},  {"spz_tile", spzTile},            {"spz_align", spzAlign},
-              {"spz_refine", spzRefine},    {"spz_locate", spzLocate}};
+              {"spz_refine", spzRefine},    {"spz_fit", spzFit},              {"spz_locate", spzLocate}};
 
 int dispatch(const std::string &tool, int argc, char **argv) {
   for (const auto &t : kTools) {

@@ -2894,8 +2894,7 @@ bool compareSpz(const std::string &fileA, const std::string &fileB, const Compar
 namespace {
 // The views as render params, and the options but the position rate as the C ABI's.
 bool refineOptionsOk(const RefineOptions &o, std::vector<spz_amd_render_params> *params, spz_amd_refine_options *c,
-                     spz_amd_densify_options *d) {
-  const char *who = "refineSpz";
+                     spz_amd_densify_options *d, const char *who = "refineSpz") {
   const int invalid = SPZ_AMD_ERR_INVALID_ARG;
   if (o.iterations < 0) return opRejected(who, invalid, "iterations %d is negative", o.iterations);
   if (!(o.lambdaDssim >= 0.0 && o.lambdaDssim <= 1.0)) return opRejected(who, invalid, "lambdaDssim must be in [0, 1]");
@@ -3058,6 +3057,160 @@ bool refineSpz(const std::string &inputFilename, const std::string &targetFilena
   if (!fileToFile(who, "SPZ_AMD_REFINE_TIMING", inputFilename, outputFilename,
                   [&](const uint8_t *data, int32_t size, std::vector<uint8_t> *file) {
                     return refineSpz(data, size, target.data(), static_cast<int32_t>(target.size()), o, file, &rep);
+                  })) {
+    return false;
+  }
+  if (report) *report = std::move(rep);
+  return true;
+}
+
+// ---- fit ---------------------------------------------------------------------------------------------------------
+namespace {
+// One image per view, each of its view's size, one channel count; the options as the C ABI's.
+bool photoOptionsOk(const char *who, const RefineOptions &o, const PhotoOptions &p, spz_amd_photo_options *c) {
+  const int invalid = SPZ_AMD_ERR_INVALID_ARG;
+  if (p.images.size() != o.views.size()) {
+    return opRejected(who, invalid, "%zu views but %zu images", o.views.size(), p.images.size());
+  }
+  for (size_t v = 0; v < p.images.size(); ++v) {
+    const PhotoImage &im = p.images[v];
+    if (im.pixels == nullptr) return opRejected(who, invalid, "image %zu has no pixels", v);
+    if (im.channels != 3 && im.channels != 4) return opRejected(who, invalid, "image %zu has %d channels: 3 or 4", v, im.channels);
+    if (im.channels != p.images[0].channels) {
+      return opRejected(who, invalid, "image %zu has %d channels but image 0 has %d", v, im.channels, p.images[0].channels);
+    }
+    if (im.width != o.views[v].width || im.height != o.views[v].height) {
+      return opRejected(who, invalid, "view %zu is %d x %d but its image is %d x %d", v, o.views[v].width,
+                        o.views[v].height, im.width, im.height);
+    }
+  }
+  spz_amd_photo_default_options(c);
+  c->fit_exposure = p.fitExposure ? 1 : 0;
+  c->lr_exposure = p.exposureLr;
+  if (spz_amd_photo_check(c) != SPZ_AMD_OK) return opRejected(who, invalid, "exposureLr must be finite and >= 0");
+  return true;
+}
+}  // namespace
+
+bool refineSpzToImages(const uint8_t *data, int32_t size, const RefineOptions &o, const PhotoOptions &p,
+                       std::vector<uint8_t> *out, PhotoReport *report) {
+  const char *who = "refineSpzToImages";
+  g_last_status = SPZ_AMD_OK;
+  if (report) *report = PhotoReport{};
+  if (out == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no output vector");
+  std::vector<spz_amd_render_params> params;
+  spz_amd_refine_options c;
+  spz_amd_densify_options d;
+  spz_amd_photo_options pc;
+  if (!refineOptionsOk(o, &params, &c, &d, who) || !photoOptionsOk(who, o, p, &pc)) return false;
+  const bool densify = d.interval > 0;
+  if (densify && d.max_points == 0) {
+    return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "densify: there is no target to take a count from: set densify.maxPoints");
+  }
+  Laps laps(who, "SPZ_AMD_REFINE_TIMING");
+  DevicePackedGaussians da;
+  if (!loadInput(who, data, size, &da)) return false;
+  laps.lap("inflate");
+  if (!o.positionLr) {  // 3DGS scales the position rate by the scene's extent
+    UnpackOptions u;
+    u.to = o.coord;
+    const GaussianCloud t = da.unpack(u);
+    std::array<float, 3> centre;
+    float radius = 1.0f;
+    if (!boundingSphere(t.positions, &centre, &radius)) radius = 1.0f;
+    c.lr[0] = 1.6e-4 * static_cast<double>(radius);
+    laps.lap("extent");
+  }
+  const spz_amd_header ha = headerOf(da);
+  const size_t nv = params.size();
+  if (densify) {
+    spz_amd_densify_limits lim;
+    if (spz_amd_densify_thresholds(&d, params.data(), static_cast<int>(nv), &lim) != SPZ_AMD_OK) {
+      return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "densify: the views' camera centres coincide, so they give no "
+                        "extent: set densify.extent");
+    }
+    if (d.max_points < ha.num_points) {
+      return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "densify: maxPoints %llu is below the input's %u points",
+                        static_cast<unsigned long long>(d.max_points), ha.num_points);
+    }
+  }
+  std::vector<const float *> targets(nv), weights(nv);
+  bool anyWeights = false;
+  for (size_t v = 0; v < nv; ++v) {
+    targets[v] = p.images[v].pixels;
+    weights[v] = p.images[v].weights;
+    anyWeights = anyWeights || weights[v] != nullptr;
+  }
+  std::vector<spz_amd_image_metrics> before(nv), after(nv);
+  std::vector<double> history(static_cast<size_t>(o.iterations) + 1), exposures(12 * nv);
+  OpenResult r(spz_amd_refine_fetch, spz_amd_refine_device_data, spz_amd_refine_close);
+  uint64_t bytes = 0, skipped = 0, numPoints = ha.num_points;
+  float ms[3] = {0.0f, 0.0f, 0.0f};
+  int32_t bad = -1;
+  int numRounds = 0;
+  std::vector<spz_amd_densify_round> rounds(densify ? static_cast<size_t>(o.iterations / d.interval) + 1 : 0);
+  const int rc = spz_amd_refine_images_host_open(
+      da.stream, da.streamBytes, &ha, params.data(), static_cast<int>(nv), targets.data(), p.images[0].channels,
+      anyWeights ? weights.data() : nullptr, &c, &pc, densify ? &d : nullptr, da.device, &r.ctx, &bytes, history.data(),
+      before.data(), after.data(), &skipped, ms, &bad, &numPoints, rounds.data(), static_cast<int>(rounds.size()),
+      &numRounds, nullptr, exposures.data());
+  if (rc == SPZ_AMD_ERR_UNSUPPORTED) {
+    return opRejected(who, rc, "the encoder writes versions 2 and 3 and positions at 12 fractional bits: the input has "
+                      "version %u and %u", ha.version, static_cast<unsigned>(ha.fractional_bits));
+  }
+  if (viewsFailed(who, rc, bad)) return false;
+  laps.stage("before", ms[0], (" (" + std::to_string(nv) + " views)").c_str());
+  laps.stage("iterations", ms[1], (" (" + std::to_string(o.iterations) + ")").c_str());
+  laps.stage("after", ms[2]);
+  laps.lap("refine");
+  da.release();
+  if (!r.finish(who, bytes, &laps, out)) return false;
+  if (report) {
+    RefineReport &rr = report->refine;
+    history.resize(static_cast<size_t>(o.iterations));
+    rr.history.swap(history);
+    rr.before.resize(nv);
+    rr.after.resize(nv);
+    report->exposures.resize(nv);
+    for (size_t v = 0; v < nv; ++v) {
+      rr.before[v] = toMetrics(before[v]);
+      rr.after[v] = toMetrics(after[v]);
+      std::copy(exposures.begin() + 12 * v, exposures.begin() + 12 * (v + 1), report->exposures[v].begin());
+    }
+    rr.skipped = skipped;
+    rr.positionLr = c.lr[0];
+    for (int k = 0; k < 3; ++k) rr.ms[k] = ms[k];
+    rr.numPoints = numPoints;
+    for (int k = 0; k < numRounds && static_cast<size_t>(k) < rounds.size(); ++k) {
+      const spz_amd_densify_round &x = rounds[static_cast<size_t>(k)];
+      rr.rounds.push_back(DensifyRound{x.iteration, x.cloned, x.split, x.culled, x.refused, x.num_points});
+    }
+  }
+  return true;
+}
+
+bool refineSpzToImages(const std::vector<uint8_t> &data, const RefineOptions &o, const PhotoOptions &p,
+                       std::vector<uint8_t> *out, PhotoReport *report) {
+  if (data.size() > static_cast<size_t>(INT32_MAX)) {
+    return opRejected("refineSpzToImages", SPZ_AMD_ERR_INVALID_ARG, "the input is larger than 2 GiB");
+  }
+  return refineSpzToImages(data.data(), static_cast<int32_t>(data.size()), o, p, out, report);
+}
+
+bool refineSpzToImages(const std::string &inputFilename, const std::string &outputFilename, const RefineOptions &o,
+                       const PhotoOptions &p, PhotoReport *report) {
+  const char *who = "refineSpzToImages";
+  g_last_status = SPZ_AMD_OK;
+  if (report) *report = PhotoReport{};
+  std::vector<spz_amd_render_params> params;
+  spz_amd_refine_options c;
+  spz_amd_densify_options d;
+  spz_amd_photo_options pc;
+  if (!refineOptionsOk(o, &params, &c, &d, who) || !photoOptionsOk(who, o, p, &pc)) return false;
+  PhotoReport rep;
+  if (!fileToFile(who, "SPZ_AMD_REFINE_TIMING", inputFilename, outputFilename,
+                  [&](const uint8_t *data, int32_t size, std::vector<uint8_t> *file) {
+                    return refineSpzToImages(data, size, o, p, file, &rep);
                   })) {
     return false;
   }

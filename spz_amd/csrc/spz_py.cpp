@@ -553,6 +553,55 @@ PYBIND11_MODULE(spz, m) {
         "until_iter, grad_threshold, percent_dense, extent, min_opacity, max_scale, max_points, opacity_reset_interval, "
         "seed: with interval > 0 Gaussians are cloned, split and culled every `interval` iterations (include/spz_amd.h "
         "\"densify\"), the output's count is num_points and rounds has one dict per round.");
+  m.def("refine_spz_to_images",
+        [](const py::object &input, const py::object &output, const py::object &views, const py::object &images,
+           const py::object &weights, const py::object &fit_exposure, double lr_exposure, int iterations,
+           spz::CoordinateSystem coord, const py::object &background, int max_sh_degree, float near_plane,
+           double lambda_dssim, const py::object &lrs, double beta1, double beta2, double eps, const py::object &train,
+           const py::object &densify) {
+          const spz::RefineOptions o = refineOptions(views, iterations, coord, background, max_sh_degree, near_plane,
+                                                     lambda_dssim, lrs, beta1, beta2, eps, train, densify);
+          std::vector<FloatArray> keep;
+          const spz::PhotoOptions p = photoOptions(images, weights, fit_exposure, lr_exposure, o.views, &keep);
+          const Input in(input);
+          if (in.bytes && !output.is_none()) {
+            throw py::value_error("with bytes in, output must be None: the bytes are returned");
+          }
+          if (!in.bytes && output.is_none()) throw py::value_error("with a path in, give the output path");
+          const std::string out = output.is_none() ? std::string() : py::str(output).cast<std::string>();
+          spz::PhotoReport rep;
+          std::vector<uint8_t> data;
+          if (!callOn(in, [&](auto... file) {
+                if constexpr (sizeof...(file) == 2) {
+                  return spz::refineSpzToImages(file..., o, p, &data, &rep);
+                } else {
+                  return spz::refineSpzToImages(file..., out, o, p, &rep);
+                }
+              })) {
+            raiseFailure("refine_spz_to_images");
+          }
+          py::dict d = refineDict(rep.refine, in.bytes ? &data : nullptr);
+          py::array_t<double> ex(std::vector<py::ssize_t>{static_cast<py::ssize_t>(rep.exposures.size()), 3, 4});
+          for (size_t v = 0; v < rep.exposures.size(); ++v) {
+            std::copy(rep.exposures[v].begin(), rep.exposures[v].end(), ex.mutable_data() + 12 * v);
+          }
+          d["exposures"] = ex;
+          return d;
+        },
+        py::arg("input"), py::arg("output"), py::arg("views"), py::arg("images"), py::arg("weights") = py::none(),
+        py::arg("fit_exposure") = false, py::arg("lr_exposure") = 0.01, py::kw_only(), py::arg("iterations") = 200,
+        py::arg("coord") = spz::CoordinateSystem::UNSPECIFIED, py::arg("background") = py::make_tuple(0.0f, 0.0f, 0.0f),
+        py::arg("max_sh_degree") = 3, py::arg("near") = 0.2f, py::arg("lambda_dssim") = 0.2, py::arg("lrs") = py::none(),
+        py::arg("beta1") = 0.9, py::arg("beta2") = 0.999, py::arg("eps") = 1e-15, py::arg("train") = py::none(),
+        py::arg("densify") = py::none(),
+        "refine_spz against photographs (spz::refineSpzToImages; the contract is in include/spz_amd.h \"photo loss\" and "
+        "\"refine images\"): fit the .spz file `input` (a path, or the file's bytes with output None) to `images`, one "
+        "(height, width, 3 or 4) float32 array per view of `views`, of the view's size, values in [0, 1] (load_image).  "
+        "weights: None, or one entry per view, each None or a (height, width) float32 array in [0, 1]: what each pixel "
+        "counts in the loss.  fit_exposure: fit a 3 x 4 colour transform per image beside the cloud, at rate lr_exposure.  "
+        "The other keywords are refine_spz's (the position rate defaults to 1.6e-4 times the input's bounding-sphere "
+        "radius; densify needs max_points).  Returns refine_spz's dict and \"exposures\", a (views, 3, 4) float64 array "
+        "[M | o], the identity without fit_exposure; \"after\" is of the written stream through the fitted exposure.");
   m.def("locate_spz",
         [](const py::object &input, const py::object &view, const py::object &image, int iterations, int levels,
            spz::CoordinateSystem coord, const py::object &background, int max_sh_degree, float near_plane,

@@ -994,6 +994,64 @@ spz::RefineOptions refineOptions(const py::object &views, int iterations, spz::C
   return o;
 }
 
+// refine_spz_to_images' images, weights and exposure arguments as spz::PhotoOptions; `keep` holds the arrays the
+// options point into.
+spz::PhotoOptions photoOptions(const py::object &images, const py::object &weights, const py::object &fit_exposure,
+                               double lr_exposure, const std::vector<View> &views, std::vector<FloatArray> *keep) {
+  spz::PhotoOptions p;
+  p.fitExposure = flag(fit_exposure, "fit_exposure");
+  p.exposureLr = finite(lr_exposure, Bound::NonNegative, "lr_exposure must be finite and >= 0");
+  if (py::isinstance<py::str>(images) || py::isinstance<py::array>(images) || !py::isinstance<py::sequence>(images)) {
+    throw py::value_error("images must be a sequence of numpy arrays, one per view");
+  }
+  const py::sequence ims = py::reinterpret_borrow<py::sequence>(images);
+  if (ims.size() != views.size()) {
+    throw py::value_error("images must have one array per view: " + std::to_string(views.size()) + " views, " +
+                          std::to_string(ims.size()) + " images");
+  }
+  py::sequence wts;
+  if (!weights.is_none()) {
+    if (py::isinstance<py::str>(weights) || py::isinstance<py::array>(weights) || !py::isinstance<py::sequence>(weights)) {
+      throw py::value_error("weights must be None or a sequence of numpy arrays or None, one per view");
+    }
+    wts = py::reinterpret_borrow<py::sequence>(weights);
+    if (wts.size() != views.size()) {
+      throw py::value_error("weights must have one entry per view: " + std::to_string(views.size()) + " views, " +
+                            std::to_string(wts.size()) + " weights");
+    }
+  }
+  keep->reserve(2 * views.size());
+  for (size_t k = 0; k < views.size(); ++k) {
+    const std::string name = "images[" + std::to_string(k) + "]";
+    keep->push_back(imageArray(py::reinterpret_borrow<py::object>(ims[k]), name.c_str(), &views[k]));
+    const FloatArray &im = keep->back();
+    spz::PhotoImage pi;
+    pi.pixels = im.data();
+    pi.width = views[k].width;
+    pi.height = views[k].height;
+    pi.channels = static_cast<int>(im.shape(2));
+    if (pi.channels != static_cast<int>((*keep)[0].shape(2))) {
+      throw py::value_error(name + " has " + std::to_string(pi.channels) + " channels but images[0] has " +
+                            std::to_string((*keep)[0].shape(2)));
+    }
+    p.images.push_back(pi);
+  }
+  for (size_t k = 0; !weights.is_none() && k < views.size(); ++k) {
+    const py::object w = py::reinterpret_borrow<py::object>(wts[k]);
+    if (w.is_none()) continue;
+    const std::string bad = "weights[" + std::to_string(k) + "] must be a float32 array of the view's height x width";
+    if (!py::isinstance<py::array>(w)) throw py::value_error(bad);
+    const py::array arr = py::reinterpret_borrow<py::array>(w);
+    if (!arr.dtype().is(py::dtype::of<float>()) || arr.ndim() != 2 || arr.shape(0) != views[k].height ||
+        arr.shape(1) != views[k].width) {
+      throw py::value_error(bad);
+    }
+    keep->push_back(FloatArray(arr));
+    p.images[k].weights = keep->back().data();
+  }
+  return p;
+}
+
 // locate_spz's arguments as spz::LocateOptions.
 spz::LocateOptions locateOptions(int iterations, int levels, spz::CoordinateSystem coord, const py::object &background,
                                  int max_sh_degree, float near_plane, double lambda_dssim, double lr_rotation,

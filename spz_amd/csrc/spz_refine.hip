@@ -13,6 +13,10 @@
 //                                  spz_amd_render_backward_device on the same workspace and total, the Adam step; then
 //                                  the trained sections encoded over a copy of A's bytes and the "after" metrics of
 //                                  that stream.
+//   refine images                  (DESIGN §8 "Fit") the same loop with the targets given, not rendered: the photo loss
+//                                  of spz_photo.hip with each view's weights and, when they are fitted, its exposure
+//                                  read from device memory, and that exposure's own Adam step on the device; "after"
+//                                  through the fitted exposure.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -24,6 +28,7 @@
 #include "spz_amd.h"
 #include "spz_common.hpp"
 #include "spz_densify_internal.hpp"
+#include "spz_photo_internal.hpp"
 #include "spz_view_pass.hpp"
 
 namespace spz_amd_detail {
@@ -289,12 +294,23 @@ struct DensifyReport {
   uint32_t *h_origin;
 };
 
-// The loop of both entries: spz_amd_refine_open (densify == nullptr) and spz_amd_refine_densify_open.
+// The targets of spz_amd_refine_images_open: given, not rendered.  Every pointer is the caller's.
+struct PhotoTargets {
+  const float *const *d_targets;  // num_views images of `channels` floats per pixel
+  const float *const *d_weights;  // NULL, or num_views weight maps, any of them NULL
+  int channels;
+  const spz_amd_photo_options *options;
+  double *h_exposures;            // may be NULL: 12 doubles per view out
+};
+
+// The loop of the three entries: spz_amd_refine_open (densify == nullptr), spz_amd_refine_densify_open, and
+// spz_amd_refine_images_open (photo != nullptr: there is no stream B, the targets are the caller's images).
 int refine_run(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a, const uint8_t *d_stream_b,
                size_t size_b, const spz_amd_header *hdr_b, const spz_amd_render_params *views, int num_views,
                const spz_amd_refine_options *options, const spz_amd_densify_options *densify, int device, void **ctx,
                uint64_t *h_out_bytes, double *h_history, spz_amd_image_metrics *h_before, spz_amd_image_metrics *h_after,
-               uint64_t *h_skipped, float *h_ms, int32_t *h_bad_view, const DensifyReport &rep) {
+               uint64_t *h_skipped, float *h_ms, int32_t *h_bad_view, const DensifyReport &rep,
+               const PhotoTargets *photo = nullptr) {
   if (h_bad_view) *h_bad_view = -1;
   if (rep.h_num_points) *rep.h_num_points = 0;
   if (rep.h_num_rounds) *rep.h_num_rounds = 0;
@@ -309,8 +325,27 @@ int refine_run(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *h
   spz_amd_layout lay_a, lay_b;
   rc = check_packed_stream(d_stream_a, size_a, hdr_a, &lay_a);
   if (rc != SPZ_AMD_OK) return rc;
-  rc = check_packed_stream(d_stream_b, size_b, hdr_b, &lay_b);
-  if (rc != SPZ_AMD_OK) return rc;
+  const int tch = photo ? photo->channels : 4;  // the targets' channels
+  bool fit = false;
+  if (photo != nullptr) {
+    rc = spz_amd_photo_check(photo->options);
+    if (rc != SPZ_AMD_OK) return rc;
+    if (photo->d_targets == nullptr || (tch != 3 && tch != 4)) return SPZ_AMD_ERR_INVALID_ARG;
+    for (int v = 0; v < num_views; ++v) {
+      const float *w = photo->d_weights ? photo->d_weights[v] : nullptr;
+      if (photo->d_targets[v] == nullptr || (reinterpret_cast<uintptr_t>(photo->d_targets[v]) & 3u) != 0 ||
+          (reinterpret_cast<uintptr_t>(w) & 3u) != 0 ||
+          spz_amd_image_metrics_check((int)views[v].width, (int)views[v].height, 4, tch) != SPZ_AMD_OK) {
+        if (h_bad_view) *h_bad_view = v;
+        return SPZ_AMD_ERR_INVALID_ARG;
+      }
+    }
+    fit = photo->options->fit_exposure != 0 && options->iterations > 0;
+    hdr_b = hdr_a;  // (only its count is read below)
+  } else {
+    rc = check_packed_stream(d_stream_b, size_b, hdr_b, &lay_b);
+    if (rc != SPZ_AMD_OK) return rc;
+  }
   if (hdr_a->num_points > kMaxEntries || hdr_b->num_points > kMaxEntries) return SPZ_AMD_ERR_TOO_MANY_POINTS;
   const uint64_t n = hdr_a->num_points;
   const int deg = hdr_a->sh_degree, aa = hdr_a->flags & 1, coord = views[0].coord;
@@ -330,6 +365,7 @@ int refine_run(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *h
       rc = spz_amd_densify_thresholds(densify, views, num_views, &lim);
       if (rc != SPZ_AMD_OK) return rc;
       if ((mask & 3u) != 3u || (densify->opacity_reset_interval > 0 && (mask & 8u) == 0u)) return SPZ_AMD_ERR_INVALID_ARG;
+      if (photo != nullptr && densify->max_points == 0) return SPZ_AMD_ERR_INVALID_ARG;  // no target count to take
       const uint64_t mp = densify->max_points ? densify->max_points : hdr_b->num_points;
       if (mp > kMaxEntries) return SPZ_AMD_ERR_TOO_MANY_POINTS;
       if (mp < n) return SPZ_AMD_ERR_INVALID_ARG;
@@ -353,7 +389,8 @@ int refine_run(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *h
   for (int v = 0; v < num_views; ++v) {
     const uint64_t px = (uint64_t)views[v].width * views[v].height;
     max_px = px > max_px ? px : max_px;
-    const uint64_t lw = spz_amd_image_loss_workspace_bytes((int)views[v].width, (int)views[v].height);
+    const uint64_t lw = photo ? spz_amd_photo_loss_workspace_bytes((int)views[v].width, (int)views[v].height)
+                              : spz_amd_image_loss_workspace_bytes((int)views[v].width, (int)views[v].height);
     const uint64_t mw = spz_amd_image_metrics_workspace_bytes((int)views[v].width, (int)views[v].height);
     loss_ws = lw > loss_ws ? lw : loss_ws;
     metrics_ws = mw > metrics_ws ? mw : metrics_ws;
@@ -363,7 +400,11 @@ int refine_run(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *h
   for (int s = 0; s < 4; ++s) {
     for (int k = 0; k < 6; ++k) off[s][k] = o.put(count[k] * 4u);
   }
-  for (int v = 0; v < num_views; ++v) target_off[(size_t)v] = o.put(16u * (uint64_t)views[v].width * views[v].height);
+  for (int v = 0; v < num_views; ++v) {  // (given targets are used in place)
+    target_off[(size_t)v] = o.put(photo ? 0u : 16u * (uint64_t)views[v].width * views[v].height);
+  }
+  // a fitted exposure per view: 12 values and their two moments, each kind contiguous; then one gradient
+  const uint64_t o_exposure = o.put(fit ? 3u * 96u * (uint64_t)num_views + 96u : 0u);
   const uint64_t o_image = o.put(16u * max_px), o_grad = o.put(16u * max_px), o_lws = o.put(iters ? loss_ws : 0u),
                  o_mws = o.put(metrics_ws), o_small = o.put(16u), o_loss = o.put(24u * (uint64_t)iters),
                  o_metrics = o.put(2u * (uint64_t)num_views * sizeof(spz_amd_image_metrics)),
@@ -408,7 +449,16 @@ int refine_run(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *h
   auto *d_skipped = reinterpret_cast<uint32_t *>(raw + o_small + 12u);
   auto *d_loss = reinterpret_cast<double *>(raw + o_loss);
   auto *d_metrics = reinterpret_cast<spz_amd_image_metrics *>(raw + o_metrics);
-  auto target = [&](int v) { return reinterpret_cast<float *>(raw + target_off[(size_t)v]); };
+  auto target = [&](int v) {
+    return photo ? photo->d_targets[v] : reinterpret_cast<const float *>(raw + target_off[(size_t)v]);
+  };
+  auto weight = [&](int v) { return photo && photo->d_weights ? photo->d_weights[v] : nullptr; };
+  // view v's exposure at d_exposure + 12 v, its moments 12 V and 24 V doubles on, the gradient after them all
+  auto *d_exposure = reinterpret_cast<double *>(raw + o_exposure);
+  double *d_exposure_grad = d_exposure + 36u * (size_t)num_views;
+  std::vector<double> exposures(12u * (size_t)num_views, 0.0);
+  for (int v = 0; v < num_views; ++v) exposures[12u * (size_t)v] = exposures[12u * (size_t)v + 5u] = exposures[12u * (size_t)v + 10u] = 1.0;
+  std::vector<int> visits((size_t)num_views, 0);
   auto fail = [&](int v, int r) {
     if (h_bad_view) *h_bad_view = v;
     return r;
@@ -424,19 +474,25 @@ int refine_run(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *h
   // targets and the "before" metrics
   uint64_t cap = 0, total = 0;
   const RenderSource src_a = packed_render_source(d_stream_a, size_a, hdr_a);
-  const RenderSource src_b = packed_render_source(d_stream_b, size_b, hdr_b);
   auto render = [&](const RenderSource &src, const spz_amd_render_params *p, float *d_out) {
     return render_view(&c->scratch, &cap, src, p, d_total, d_status, d_out, c->st, &total);
   };
   for (int v = 0; v < num_views; ++v) {
     const spz_amd_render_params &p = views[v];
-    rc = render(src_b, &p, target(v));
-    if (rc != SPZ_AMD_OK) return fail(v, rc);
+    if (photo == nullptr) {
+      const RenderSource src_b = packed_render_source(d_stream_b, size_b, hdr_b);
+      rc = render(src_b, &p, reinterpret_cast<float *>(raw + target_off[(size_t)v]));
+      if (rc != SPZ_AMD_OK) return fail(v, rc);
+    }
     rc = render(src_a, &p, d_image);
     if (rc != SPZ_AMD_OK) return fail(v, rc);
-    rc = spz_amd_image_metrics_device(d_image, 4, target(v), 4, (int)p.width, (int)p.height, d_metrics + v, nullptr,
+    rc = spz_amd_image_metrics_device(d_image, 4, target(v), tch, (int)p.width, (int)p.height, d_metrics + v, nullptr,
                                       raw + o_mws, c->st);
     if (rc != SPZ_AMD_OK) return fail(v, rc);
+  }
+  if (fit) {
+    SPZ_HIP_TRY(hipMemsetAsync(d_exposure, 0, 3u * 96u * (size_t)num_views + 96u, c->st));
+    SPZ_HIP_TRY(hipMemcpyAsync(d_exposure, exposures.data(), 96u * (size_t)num_views, hipMemcpyHostToDevice, c->st));
   }
   SPZ_HIP_TRY(hipStreamSynchronize(c->st));
   const double before_ms = ms_since(t0);
@@ -459,9 +515,22 @@ int refine_run(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *h
       const spz_amd_render_params &p = views[v];
       rc = render(src_f, &p, d_image);
       if (rc != SPZ_AMD_OK) return fail(v, rc);
-      rc = spz_amd_image_loss_device(d_image, 4, target(v), 4, (int)p.width, (int)p.height, options->lambda_dssim,
-                                     d_loss + 3 * (size_t)i, d_grad, raw + o_lws, c->st);
+      if (photo != nullptr) {
+        rc = photo_loss_enqueue(d_image, 4, target(v), tch, weight(v), fit ? d_exposure + 12u * (size_t)v : nullptr,
+                                (int)p.width, (int)p.height, options->lambda_dssim, d_loss + 3 * (size_t)i, d_grad,
+                                fit ? d_exposure_grad : nullptr, raw + o_lws, c->st);
+      } else {
+        rc = spz_amd_image_loss_device(d_image, 4, target(v), 4, (int)p.width, (int)p.height, options->lambda_dssim,
+                                       d_loss + 3 * (size_t)i, d_grad, raw + o_lws, c->st);
+      }
       if (rc != SPZ_AMD_OK) return fail(v, rc);
+      if (fit) {  // the exposure's own step: the image gradient above was formed with the values before it
+        double *e = d_exposure + 12u * (size_t)v;
+        rc = photo_exposure_adam_enqueue(e, d_exposure_grad, e + 12u * (size_t)num_views, e + 24u * (size_t)num_views,
+                                         ++visits[(size_t)v], photo->options->lr_exposure, options->beta1,
+                                         options->beta2, options->eps, c->st);
+        if (rc != SPZ_AMD_OK) return rc;
+      }
       const bool gather_stats = dn && i >= densify->from_iter && i < densify->until_iter;
       rc = spz_amd_render_backward_device(&cloud, n_cur, deg, aa, &p, total, d_image, d_grad, &cs.g,
                                           gather_stats && n_cur ? d_rg : nullptr, d_status, c->scratch, raw + o_bws,
@@ -536,6 +605,9 @@ int refine_run(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *h
       if (rc != SPZ_AMD_OK) return rc;
     }
   }
+  if (fit) {
+    SPZ_HIP_TRY(hipMemcpyAsync(exposures.data(), d_exposure, 96u * (size_t)num_views, hipMemcpyDeviceToHost, c->st));
+  }
   SPZ_HIP_TRY(hipStreamSynchronize(c->st));
   const double loop_ms = ms_since(t0) - before_ms;
 
@@ -548,9 +620,17 @@ int refine_run(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *h
     if (iters == 0) break;
     rc = render(src_o, &p, d_image);
     if (rc != SPZ_AMD_OK) return fail(v, rc);
-    rc = spz_amd_image_metrics_device(d_image, 4, target(v), 4, (int)p.width, (int)p.height, d_metrics + num_views + v,
-                                      nullptr, raw + o_mws, c->st);
+    if (fit) {  // the file is judged through the exposure fitted for this photograph
+      rc = spz_amd_image_exposure_device(d_image, 4, exposures.data() + 12u * (size_t)v, (int)p.width, (int)p.height,
+                                         d_image, c->st);
+      if (rc != SPZ_AMD_OK) return fail(v, rc);
+    }
+    rc = spz_amd_image_metrics_device(d_image, 4, target(v), tch, (int)p.width, (int)p.height,
+                                      d_metrics + num_views + v, nullptr, raw + o_mws, c->st);
     if (rc != SPZ_AMD_OK) return fail(v, rc);
+  }
+  if (photo != nullptr && photo->h_exposures != nullptr) {
+    std::memcpy(photo->h_exposures, exposures.data(), 96u * (size_t)num_views);
   }
   const size_t mbytes = (size_t)num_views * sizeof(spz_amd_image_metrics);
   if (h_before) SPZ_HIP_TRY(hipMemcpyAsync(h_before, d_metrics, mbytes, hipMemcpyDeviceToHost, c->st));
@@ -620,6 +700,86 @@ int spz_amd_refine_densify_open(const uint8_t *d_stream_a, size_t size_a, const 
   return refine_run(d_stream_a, size_a, hdr_a, d_stream_b, size_b, hdr_b, views, num_views, options, densify, device,
                     ctx, h_out_bytes, h_history, h_before, h_after, h_skipped, h_ms, h_bad_view,
                     DensifyReport{h_num_points, h_rounds, rounds_capacity, h_num_rounds, h_origin});
+}
+
+int spz_amd_refine_images_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
+                               const spz_amd_render_params *views, int num_views, const float *const *d_targets,
+                               int channels, const float *const *d_weights, const spz_amd_refine_options *options,
+                               const spz_amd_photo_options *photo, const spz_amd_densify_options *densify, int device,
+                               void **ctx, uint64_t *h_out_bytes, double *h_history, spz_amd_image_metrics *h_before,
+                               spz_amd_image_metrics *h_after, uint64_t *h_skipped, float *h_ms, int32_t *h_bad_view,
+                               uint64_t *h_num_points, spz_amd_densify_round *h_rounds, int rounds_capacity,
+                               int *h_num_rounds, uint32_t *h_origin, double *h_exposures) {
+  if (rounds_capacity < 0 || (rounds_capacity > 0 && h_rounds == nullptr)) {
+    if (h_bad_view) *h_bad_view = -1;
+    if (ctx) *ctx = nullptr;
+    if (h_out_bytes) *h_out_bytes = 0;
+    return SPZ_AMD_ERR_INVALID_ARG;
+  }
+  const PhotoTargets targets = {d_targets, d_weights, channels, photo, h_exposures};
+  return refine_run(d_stream_a, size_a, hdr_a, nullptr, 0, nullptr, views, num_views, options, densify, device, ctx,
+                    h_out_bytes, h_history, h_before, h_after, h_skipped, h_ms, h_bad_view,
+                    DensifyReport{h_num_points, h_rounds, rounds_capacity, h_num_rounds, h_origin}, &targets);
+}
+
+int spz_amd_refine_images_host_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
+                                    const spz_amd_render_params *views, int num_views, const float *const *h_targets,
+                                    int channels, const float *const *h_weights, const spz_amd_refine_options *options,
+                                    const spz_amd_photo_options *photo, const spz_amd_densify_options *densify,
+                                    int device, void **ctx, uint64_t *h_out_bytes, double *h_history,
+                                    spz_amd_image_metrics *h_before, spz_amd_image_metrics *h_after, uint64_t *h_skipped,
+                                    float *h_ms, int32_t *h_bad_view, uint64_t *h_num_points,
+                                    spz_amd_densify_round *h_rounds, int rounds_capacity, int *h_num_rounds,
+                                    uint32_t *h_origin, double *h_exposures) {
+  if (h_bad_view) *h_bad_view = -1;
+  if (ctx) *ctx = nullptr;
+  if (h_out_bytes) *h_out_bytes = 0;
+  int rc = check_views(views, num_views, SPZ_AMD_REFINE_MAX_VIEWS, h_bad_view);
+  if (rc != SPZ_AMD_OK) return rc;
+  if (h_targets == nullptr || (channels != 3 && channels != 4)) return SPZ_AMD_ERR_INVALID_ARG;
+  if (spz_amd_refine_check(options) != SPZ_AMD_OK || spz_amd_photo_check(photo) != SPZ_AMD_OK || rounds_capacity < 0 ||
+      (rounds_capacity > 0 && h_rounds == nullptr)) {
+    return SPZ_AMD_ERR_INVALID_ARG;  // before anything is uploaded
+  }
+  spz_amd_layout lay_a;
+  rc = check_packed_stream(d_stream_a, size_a, hdr_a, &lay_a);
+  if (rc != SPZ_AMD_OK) return rc;
+  WorkspaceOffsets o;
+  std::vector<uint64_t> t_off((size_t)num_views), w_off((size_t)num_views);
+  for (int v = 0; v < num_views; ++v) {
+    if (h_targets[v] == nullptr) {
+      if (h_bad_view) *h_bad_view = v;
+      return SPZ_AMD_ERR_INVALID_ARG;
+    }
+    const uint64_t px = (uint64_t)views[v].width * views[v].height;
+    t_off[(size_t)v] = o.put(4u * (uint64_t)channels * px);
+    w_off[(size_t)v] = o.put(h_weights && h_weights[v] ? 4u * px : 0u);
+  }
+  DeviceGuard guard;
+  rc = guard.enter(device);
+  if (rc != SPZ_AMD_OK) return rc;
+  struct Block {
+    uint8_t *p = nullptr;
+    ~Block() {
+      if (p) (void)hipFree(p);
+    }
+  } block;
+  SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&block.p), o.off ? o.off : 256u));
+  std::vector<const float *> d_targets((size_t)num_views), d_weights((size_t)num_views, nullptr);
+  for (int v = 0; v < num_views; ++v) {
+    const uint64_t px = (uint64_t)views[v].width * views[v].height;
+    d_targets[(size_t)v] = reinterpret_cast<const float *>(block.p + t_off[(size_t)v]);
+    SPZ_HIP_TRY(hipMemcpy(block.p + t_off[(size_t)v], h_targets[v], 4u * (uint64_t)channels * px, hipMemcpyHostToDevice));
+    if (h_weights && h_weights[v]) {
+      d_weights[(size_t)v] = reinterpret_cast<const float *>(block.p + w_off[(size_t)v]);
+      SPZ_HIP_TRY(hipMemcpy(block.p + w_off[(size_t)v], h_weights[v], 4u * px, hipMemcpyHostToDevice));
+    }
+  }
+  // (the loop blocks, so the images outlive it)
+  return spz_amd_refine_images_open(d_stream_a, size_a, hdr_a, views, num_views, d_targets.data(), channels,
+                                    h_weights ? d_weights.data() : nullptr, options, photo, densify, device, ctx,
+                                    h_out_bytes, h_history, h_before, h_after, h_skipped, h_ms, h_bad_view, h_num_points,
+                                    h_rounds, rounds_capacity, h_num_rounds, h_origin, h_exposures);
 }
 
 int spz_amd_refine_fetch(void *ctx, uint8_t *h_out) { return packed_result_fetch(ctx, h_out); }

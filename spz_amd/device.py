@@ -1421,6 +1421,68 @@ def image_loss(a_t, b_t, lambda_dssim, grad=None, stream=None):
     return loss, grad
 
 
+def photo_loss(a_t, b_t, lambda_dssim, weight=None, exposure=None, grad=None, stream=None):
+    """image_loss() of a render a_t against a photograph b_t with per-pixel weights and an exposure of the render
+    (spz_amd_photo_loss_device; the contract is in include/spz_amd.h "photo loss"): (loss_t, grad_t, exposure_grad_t).
+    weight: None, or a contiguous (height, width) float32 CUDA tensor, clamped to [0, 1].  exposure: None (the
+    identity), or a (3, 4) array-like [M | o] of finite numbers on the host.  exposure_grad_t: a float64 CUDA tensor
+    (3, 4), dL/d[M | o], or None without an exposure.  With neither, loss_t and grad_t carry image_loss()'s bits.
+    Not synchronised.  stream: as render()."""
+    L = abi.load_library()
+    _check_image("a", a_t)
+    _check_image("b", b_t)
+    dev = a_t.device
+    if b_t.device != dev or tuple(a_t.shape[:2]) != tuple(b_t.shape[:2]):
+        raise ValueError("a and b must have the same height and width, on one device")
+    h, w, ca, cb = int(a_t.shape[0]), int(a_t.shape[1]), int(a_t.shape[2]), int(b_t.shape[2])
+    abi.check(L.spz_amd_image_metrics_check(w, h, ca, cb), "spz_amd_image_metrics_check")
+    lam = float(lambda_dssim)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"lambda_dssim must be in [0, 1], got {lambda_dssim!r}")
+    if weight is not None and (not isinstance(weight, torch.Tensor) or weight.dtype != torch.float32
+                               or weight.device != dev or not weight.is_contiguous() or tuple(weight.shape) != (h, w)):
+        raise ValueError(f"weight must be a contiguous float32 tensor of shape ({h}, {w}) on {dev}")
+    ex = abi.exposure_values(exposure) if exposure is not None else None
+    _check_out("grad", grad, (h, w, ca), torch.float32, dev)
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        with torch.cuda.stream(st):
+            loss = torch.empty(3, dtype=torch.float64, device=dev)
+            if grad is None:
+                grad = torch.empty((h, w, ca), dtype=torch.float32, device=dev)
+            egrad = torch.empty((3, 4), dtype=torch.float64, device=dev) if ex is not None else None
+            ws = torch.empty(int(L.spz_amd_photo_loss_workspace_bytes(w, h)), dtype=torch.uint8, device=dev)
+            rc = L.spz_amd_photo_loss_device(a_t.data_ptr(), ca, b_t.data_ptr(), cb,
+                                             weight.data_ptr() if weight is not None else None, ex, w, h, lam,
+                                             loss.data_ptr(), grad.data_ptr(),
+                                             egrad.data_ptr() if egrad is not None else None, ws.data_ptr(),
+                                             C.c_void_p(st.cuda_stream))
+    abi.check(rc, "spz_amd_photo_loss_device")
+    return loss, grad, egrad
+
+
+def image_exposure(image_t, exposure, out=None, stream=None):
+    """out = M a + o over the rgb channels of a (height, width, 3 or 4) float32 CUDA image, unclamped, in f32
+    (spz_amd_image_exposure_device): exposure a (3, 4) array-like [M | o]; a fourth channel is copied.  out: None (a
+    new tensor), or a tensor shaped like the image, which may be the image itself.  stream: as render()."""
+    L = abi.load_library()
+    _check_image("image", image_t)
+    dev = image_t.device
+    h, w, ch = (int(x) for x in image_t.shape)
+    abi.check(L.spz_amd_image_metrics_check(w, h, ch, ch), "spz_amd_image_metrics_check")
+    ex = abi.exposure_values(exposure)
+    _check_out("out", out, (h, w, ch), torch.float32, dev)
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        with torch.cuda.stream(st):
+            if out is None:
+                out = torch.empty_like(image_t)
+            rc = L.spz_amd_image_exposure_device(image_t.data_ptr(), ch, ex, w, h, out.data_ptr(),
+                                                 C.c_void_p(st.cuda_stream))
+    abi.check(rc, "spz_amd_image_exposure_device")
+    return out
+
+
 def _train_ptrs(cloud, sh_degree, n, device, mask):
     """CloudPtrs of the arrays a train mask names (checked like _ptrs); the others NULL."""
     p = abi.CloudPtrs()
@@ -1685,6 +1747,84 @@ def refine_packed(stream_a, header_a, stream_b, header_b, views, iterations, *, 
               "num_points": num_points, "rounds": rounds}
     if origin is not None:
         report["origin"] = origin
+    return RefineResult(ctx, out_bytes.value, dev, report)
+
+
+def refine_packed_images(stream_a, header_a, views, images, iterations, *, weights=None, fit_exposure=False,
+                         lr_exposure=None, lambda_dssim=None, lrs=None, beta1=None, beta2=None, eps=None, train=None,
+                         densify=None):
+    """refine_packed() against photographs: spz_amd_refine_images_open (include/spz_amd.h "refine images").  images: one
+    contiguous (height, width, C) float32 CUDA tensor per view, of the view's size, C in {3, 4} and the same for all;
+    they are used in place.  weights: None, or one entry per view, each None or a contiguous (height, width) float32
+    CUDA tensor.  fit_exposure: fit a 3 x 4 exposure per view beside the cloud, at rate lr_exposure (None: 0.01).
+    densify: as refine_packed(), but max_points must be given.  Returns a RefineResult whose report also has
+    `exposures`, a float64 numpy array (views, 3, 4): the identity without fit_exposure."""
+    import numpy as np
+    L = abi.load_library()
+    _check_stream_tensor(stream_a)
+    dev = stream_a.device
+    views = list(views)
+    if not 1 <= len(views) <= abi.REFINE_MAX_VIEWS or not all(isinstance(p, abi.RenderParams) for p in views):
+        raise ValueError(f"views must be 1..{abi.REFINE_MAX_VIEWS} abi.RenderParams")
+    images = list(images)
+    if len(images) != len(views):
+        raise ValueError(f"images must have one entry per view: {len(images)} images, {len(views)} views")
+    weights = [None] * len(views) if weights is None else list(weights)
+    if len(weights) != len(views):
+        raise ValueError(f"weights must have one entry per view: {len(weights)} weights, {len(views)} views")
+    channels = None
+    for k, (p, img, wt) in enumerate(zip(views, images, weights)):
+        _check_image(f"images[{k}]", img)
+        shape = (int(p.height), int(p.width))
+        if img.device != dev or tuple(img.shape[:2]) != shape:
+            raise ValueError(f"images[{k}] must be {shape[0]} x {shape[1]} (view {k}'s size) on {dev}, got "
+                             f"{tuple(img.shape[:2])} on {img.device}")
+        if channels is None:
+            channels = int(img.shape[2])
+        if int(img.shape[2]) != channels:
+            raise ValueError(f"every image must have {channels} channels, images[{k}] has {int(img.shape[2])}")
+        if wt is not None and (not isinstance(wt, torch.Tensor) or wt.dtype != torch.float32 or wt.device != dev
+                               or not wt.is_contiguous() or tuple(wt.shape) != shape):
+            raise ValueError(f"weights[{k}] must be a contiguous float32 tensor of shape {shape} on {dev}")
+    opts = abi.refine_options(iterations, lambda_dssim=lambda_dssim, lrs=lrs, beta1=beta1, beta2=beta2, eps=eps,
+                              train=train)
+    popts = abi.photo_options(fit_exposure, lr_exposure)
+    dopts = abi.densify_options(densify) if densify is not None else None
+    nv = len(views)
+    arr = (abi.RenderParams * nv)(*views)
+    targets = (C.c_void_p * nv)(*[img.data_ptr() for img in images])
+    wptrs = (C.c_void_p * nv)(*[wt.data_ptr() if wt is not None else None for wt in weights])
+    ctx, out_bytes, skipped, bad = C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_int32(-1)
+    history = (C.c_double * max(1, opts.iterations))()
+    before = (abi.ImageMetrics * nv)()
+    after = (abi.ImageMetrics * nv)()
+    ms = (C.c_float * 3)()
+    room = max(1, opts.iterations // max(1, dopts.interval)) if dopts is not None else 0
+    h_rounds = (abi.DensifyRound * max(1, room))()
+    n_rounds, n_out = C.c_int32(), C.c_uint64()
+    origin = np.empty(max(int(dopts.max_points) if dopts is not None else 0, int(header_a.num_points), 1), dtype=np.uint32)
+    exposures = np.zeros((nv, 3, 4), dtype=np.float64)
+    torch.cuda.current_stream(dev).synchronize()  # the stream's and the images' producers
+    device_index = dev.index if dev.index is not None else torch.cuda.current_device()
+    rc = L.spz_amd_refine_images_open(stream_a.data_ptr(), stream_a.numel(), C.byref(header_a), arr, nv, targets,
+                                      channels, wptrs if any(wt is not None for wt in weights) else None,
+                                      C.byref(opts), C.byref(popts), C.byref(dopts) if dopts is not None else None,
+                                      device_index, C.byref(ctx), C.byref(out_bytes), history, before, after,
+                                      C.byref(skipped), ms, C.byref(bad), C.byref(n_out), h_rounds, room,
+                                      C.byref(n_rounds), origin.ctypes.data, exposures.ctypes.data)
+    if rc != abi.OK:
+        err = abi.SpzAmdError(rc, "spz_amd_refine_images_open" + (f" (view {bad.value})" if bad.value >= 0 else ""))
+        err.view = bad.value
+        raise err
+    num_points = int(n_out.value)
+    report = {"history": [history[i] for i in range(max(0, opts.iterations))],
+              "before": [_metrics_dict(x) for x in before], "after": [_metrics_dict(x) for x in after],
+              "skipped": int(skipped.value), "ms": tuple(ms), "out_bytes": int(out_bytes.value),
+              "num_points": num_points, "exposures": exposures,
+              "rounds": [{k: int(getattr(r, k)) for k in ("iteration", "cloned", "split", "culled", "refused",
+                                                          "num_points")} for r in h_rounds[:min(room, n_rounds.value)]]}
+    if dopts is not None:
+        report["origin"] = origin[:num_points].copy()
     return RefineResult(ctx, out_bytes.value, dev, report)
 
 
