@@ -808,6 +808,38 @@ int spz_amd_render_backward_device(const spz_amd_cloud_in *d_cloud, uint64_t num
                                    uint32_t *d_status, const void *d_render_workspace, void *d_backward_workspace,
                                    void *hip_stream);
 
+/* ---- render depth backward: the gradients of one view's image AND accumulated depth to a float cloud
+ *      (spz_render_backward.hip; DESIGN §8 "Depth fit").  The reference has no counterpart.  "render backward" with
+ *      the depth sum of "render depth" in it: given G (height x width x 4 float32, or NULL for all zero), the gradient
+ *      of a scalar loss to the image, and G_D (height x width float32), its gradient to channel 0 of d_depth (the
+ *      un-normalised sum D of (T a) z over the used pairs, z the record's f32 depth), it produces that loss's gradient
+ *      to the six arrays.  The median channel and the index are discrete and carry no gradient.
+ *      Everything "render backward" holds constant is held constant here, and depth adds no decision.  Per used pair
+ *      i, with T the transmittance before it, w = T a, C_i and D_i the prefixes that include it, C_f, D_f and T_f the
+ *      pixel's finals and tail = T_f (g_rgb . bg - g_alpha):
+ *        dL/drgb_i = w g_rgb;  dL/dz_i = w g_D;
+ *        dL/da_i = T (g_rgb . rgb_i + g_D z_i) - (g_rgb . (C_f - C_i) + g_D (D_f - D_i) + tail) / (1 - a),
+ *      and dL/da reaches opacity and power only where a = min(0.99, .) does not clamp.  The ten values per Gaussian are
+ *      summed with f32 atomic adds (a run need not repeat its bits).  The chain is that of "render backward" with one
+ *      more term: z = (R p + t)_z is computed in f64 and rounded to f32, straight through, so dL/dp += R[2, :] dL/dz
+ *      in f64.
+ *
+ *      render_depth_backward_workspace_bytes (host only): device memory for the n x 9 record gradients and the n
+ *      depth gradients.  render_depth_backward_device: as render_backward_device, with d_render_workspace as
+ *      render_finish_device OR render_depth_device left it (both leave the same records, entries, ranges and total).
+ *      d_grad_image: G, may be NULL.  d_grad_depth: G_D.  d_record_grads (may be NULL): n x 9 floats out;
+ *      d_depth_grads (may be NULL): n floats out, dL/dz per Gaussian in input order.  *d_status = 0, or 1 when the
+ *      total is above max_entries: then no gradient is written.  Every element of the six arrays is written; an
+ *      invisible Gaussian gets exact zeros.  Arguments are checked on the host before any launch, with
+ *      render_backward_device's codes.  Enqueues on hip_stream and does not synchronise. */
+uint64_t spz_amd_render_depth_backward_workspace_bytes(uint64_t num_points);
+int spz_amd_render_depth_backward_device(const spz_amd_cloud_in *d_cloud, uint64_t num_points, int sh_degree,
+                                         int antialiased, const spz_amd_render_params *params, uint64_t max_entries,
+                                         const float *d_grad_image, const float *d_grad_depth,
+                                         const spz_amd_cloud_grads *d_grads, float *d_record_grads, float *d_depth_grads,
+                                         uint32_t *d_status, const void *d_render_workspace, void *d_backward_workspace,
+                                         void *hip_stream);
+
 /* ---- render scores: per-Gaussian blend weights of one view (spz_render.hip; DESIGN §8 "Prune").  The reference has
  *      no counterpart.  With the workspace of a prepare step (as for render_finish_device), the blend of the render
  *      contract runs again, pixel for pixel; for every (pixel i, Gaussian j) pair the blend USES (not skipped for power
@@ -1377,6 +1409,84 @@ int spz_amd_refine_images_host_open(const uint8_t *d_stream_a, size_t size_a, co
                                     float *h_ms, int32_t *h_bad_view, uint64_t *h_num_points,
                                     spz_amd_densify_round *h_rounds, int rounds_capacity, int *h_num_rounds,
                                     uint32_t *h_origin, double *h_exposures);
+
+/* ---- depth loss: the loss of a depth render against a measured depth map, and its gradient to the render
+ *      (spz_depth_loss.hip; DESIGN §8 "Depth fit").  The reference has no counterpart.
+ *      d_depth: height x width x 2 float32 as render_depth_device writes it; only channel 0, D, is read.  d_image:
+ *      height x width x 4; only channel 3, alpha, is read.  d_target: height x width float32, metric depth along the
+ *      camera's z in scene units.  d_weight: NULL (every weight 1), or height x width float32, each clamped to [0, 1],
+ *      NaN -> 0: the photo loss's rule.  kind: SPZ_AMD_DEPTH_L1 or SPZ_AMD_DEPTH_INVERSE_L1.  min_alpha in (0, 1].
+ *      scale >= 0 and finite: the weight of this term in the caller's total loss; it scales the gradients, not L.
+ *      A pixel is valid iff w_p > 0, the target is finite and > 0, alpha >= min_alpha (both f32) and D is finite and
+ *      > 0.  In f64 from the f32 values: e = D / alpha - t (L1) or alpha / D - 1 / t (inverse); W_v = sum_valid w_p;
+ *      L = sum_valid w_p |e_p| / W_v.  W_v == 0: L = 0 and every gradient is exactly 0.
+ *      Gradients, the validity held constant, with s = scale sign(e) w_p / W_v and sign(0) = 0.  L1: g_D = s / alpha,
+ *      g_alpha = -s D / alpha^2.  Inverse: g_D = -s alpha / D^2, g_alpha = s / D.  Each is rounded once to f32.
+ *      d_loss (device memory, 8-aligned): two doubles, L (not scaled) and W_v.  d_grad_depth: height x width float32,
+ *      every element written, exact 0 where the pixel is invalid; it is the d_grad_depth of
+ *      render_depth_backward_device.  d_grad_image (may be NULL): height x width x 4; channel 3 gets += g_alpha, one
+ *      lane per pixel, the other channels are not touched: run it after the photo loss, which writes an exact 0 there.
+ *      Arithmetic.  Per-workgroup partial sums in a fixed tree, summed by one workgroup in a fixed order; the gradient
+ *      pass reads W_v from d_loss.  No float atomics and no host synchronisation: a run repeats its bits.
+ *      depth_loss_workspace_bytes (host only; 0 for a bad size): 16 bytes per 256 pixels.  depth_loss_device: arguments
+ *      checked on the host before any launch (sizes as image_metrics_check, 4-byte alignment, kind, min_alpha, scale:
+ *      SPZ_AMD_ERR_INVALID_ARG; no device: SPZ_AMD_ERR_NO_DEVICE); enqueues on hip_stream and does not synchronise. */
+enum { SPZ_AMD_DEPTH_L1 = 0, SPZ_AMD_DEPTH_INVERSE_L1 = 1 };
+uint64_t spz_amd_depth_loss_workspace_bytes(int width, int height);
+int spz_amd_depth_loss_device(const float *d_depth, const float *d_image, const float *d_target, const float *d_weight,
+                              int width, int height, int kind, float min_alpha, double scale, double *d_loss,
+                              float *d_grad_depth, float *d_grad_image, void *d_workspace, void *hip_stream);
+
+/* ---- refine images with depth: "refine images" with a measured depth map for some or all of the views
+ *      (spz_refine.hip; DESIGN §8 "Depth fit").  The two entries are refine_images_open and refine_images_host_open
+ *      with, after the weights, d_depth_targets (h_depth_targets for the host form): NULL, or a host array of num_views
+ *      pointers, any of them NULL, to height_v x width_v float32 maps as "depth loss" takes them (a value that is not
+ *      finite or not > 0 means no measurement there); and depth (depth_default_options: weight 1.0, min_alpha 0.5,
+ *      SPZ_AMD_DEPTH_L1; depth_check, host only: weight >= 0 and finite, min_alpha in (0, 1], a known kind).  A
+ *      misaligned map: SPZ_AMD_ERR_INVALID_ARG with the view in *h_bad_view.  The maps are used in place.
+ *      Run.  An iteration whose view has a map, with weight > 0: prepare; render_depth_device (its image is
+ *      render_finish_device's, bit for bit); the photo loss; depth_loss_device with view v's weights and scale = weight,
+ *      adding its gradient to alpha into the photo loss's d_grad; render_depth_backward_device with both gradients;
+ *      then Adam, the exposure step and densify as "refine images" has them.  Densify's screen-space accumulator reads
+ *      the record gradients of that backward, so it sees the depth term's mean gradient too.  A view without a map, or
+ *      weight == 0, takes the path of "refine images" unchanged; with no map at all h_history and h_before carry
+ *      exactly the bits refine_images_open gives.
+ *      h_history[i] = L_photo + weight L_depth before step i.  h_depth_history (may be NULL): iterations doubles,
+ *      L_depth before step i, 0 for a view without a map or with weight == 0.  h_depth_error (may be NULL): 2 doubles
+ *      per view; [2 v] is the depth loss (view v's weights, the options' kind and min_alpha) of A's packed depth render
+ *      against the map, [2 v + 1] that of the OUTPUT STREAM's packed depth render (with iterations == 0: the same
+ *      value); -1 for a view without a map.
+ *      Memory grows by 12 W H bytes for the depth render and its gradient and by the depth loss's workspace, all for
+ *      the largest view, and the backward workspace by 4 bytes per Gaussian. */
+typedef struct {
+  double weight;   /* 1.0: the depth term's weight in the loss */
+  float min_alpha; /* 0.5 */
+  int32_t kind;    /* SPZ_AMD_DEPTH_L1 */
+} spz_amd_depth_options;
+int spz_amd_depth_default_options(spz_amd_depth_options *options);
+int spz_amd_depth_check(const spz_amd_depth_options *options);
+int spz_amd_refine_images_depth_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
+                                     const spz_amd_render_params *views, int num_views, const float *const *d_targets,
+                                     int channels, const float *const *d_weights, const float *const *d_depth_targets,
+                                     const spz_amd_depth_options *depth, const spz_amd_refine_options *options,
+                                     const spz_amd_photo_options *photo, const spz_amd_densify_options *densify,
+                                     int device, void **ctx, uint64_t *h_out_bytes, double *h_history,
+                                     spz_amd_image_metrics *h_before, spz_amd_image_metrics *h_after,
+                                     uint64_t *h_skipped, float *h_ms, int32_t *h_bad_view, uint64_t *h_num_points,
+                                     spz_amd_densify_round *h_rounds, int rounds_capacity, int *h_num_rounds,
+                                     uint32_t *h_origin, double *h_exposures, double *h_depth_history,
+                                     double *h_depth_error);
+int spz_amd_refine_images_depth_host_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
+                                          const spz_amd_render_params *views, int num_views,
+                                          const float *const *h_targets, int channels, const float *const *h_weights,
+                                          const float *const *h_depth_targets, const spz_amd_depth_options *depth,
+                                          const spz_amd_refine_options *options, const spz_amd_photo_options *photo,
+                                          const spz_amd_densify_options *densify, int device, void **ctx,
+                                          uint64_t *h_out_bytes, double *h_history, spz_amd_image_metrics *h_before,
+                                          spz_amd_image_metrics *h_after, uint64_t *h_skipped, float *h_ms,
+                                          int32_t *h_bad_view, uint64_t *h_num_points, spz_amd_densify_round *h_rounds,
+                                          int rounds_capacity, int *h_num_rounds, uint32_t *h_origin,
+                                          double *h_exposures, double *h_depth_history, double *h_depth_error);
 
 /* ---- render view backward: the gradient of one view to its camera (spz_render_view_backward.hip; DESIGN §8
  *      "Locate").  The reference has no counterpart.  Given the n x 9 record gradients of a view (mean 2, conic 3,

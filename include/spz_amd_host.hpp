@@ -620,19 +620,34 @@ bool refineSpz(const std::string &inputFilename, const std::string &targetFilena
 // passed through that image's fitted exposure when fitExposure is set, against the images, both unweighted.  false + one
 // "[SPZ ERROR] refineSpzToImages: …" line as refineSpz; an image whose size is not its view's names the view and both
 // sizes.  SPZ_AMD_REFINE_TIMING=1 prints the stages' times.
+// Depth (DESIGN §8 "Depth fit"; include/spz_amd.h "depth loss" and "refine images with depth"): an image may carry a
+// measured depth map, height x width float32 of metric depth along the camera's z in scene units (LiDAR, an RGB-D rig,
+// MVS, a render of a mesh; loadDepthFile), a value that is not finite or not > 0 meaning "no measurement".  The loss of
+// an iteration on such a view gains depthWeight times the depth loss: the mean over the pixels with a measurement and
+// an alpha of at least depthMinAlpha, weighted by the image's weights, of |expected depth - measured| (L1) or of the
+// difference of their reciprocals (InverseL1, which counts near errors more).  With no image carrying a depth
+// everything is as without these fields.  The report's depthHistory is the depth loss before each step (0 for a view
+// without a map), depthError per view that of the input's and of the written stream's depth render against the map
+// (-1 for a view without one); both are empty when no image carries a depth.
 struct PhotoImage {
   const float *pixels = nullptr;
   int width = 0, height = 0, channels = 3;
   const float *weights = nullptr;
+  const float *depth = nullptr;  // height x width, metric z
 };
 struct PhotoOptions {
   std::vector<PhotoImage> images;
   bool fitExposure = false;
   double exposureLr = 0.01;  // 3DGS's exposure_lr_init
+  double depthWeight = 1.0;
+  enum DepthKind { L1, InverseL1 } depthKind = L1;
+  float depthMinAlpha = 0.5f;
 };
 struct PhotoReport {
   RefineReport refine;
   std::vector<std::array<double, 12>> exposures;  // per view, row-major [M | o]
+  std::vector<double> depthHistory;
+  std::vector<std::array<double, 2>> depthError;  // per view: before, after
 };
 bool refineSpzToImages(const uint8_t *data, int32_t size, const RefineOptions &options, const PhotoOptions &photo,
                        std::vector<uint8_t> *out, PhotoReport *report = nullptr);
@@ -683,6 +698,11 @@ bool locateSpz(const std::string &filename, const PruneOptions::View &initial, c
 // ("PF", either byte order, rows bottom to top in the file), three channels, rows top to bottom in *pixels.
 // std::invalid_argument naming the file when it does not open or is neither.
 void loadImageFile(const std::string &filename, std::vector<float> *pixels, int *width, int *height);
+// A depth map as spz_render --depth writes it, as PhotoImage::depth takes it: a one-channel PFM ("Pf"), or the first
+// channel of a colour PFM ("PF"); either byte order, rows bottom to top in the file and top to bottom in *pixels, the
+// floats' bits kept (+inf stays +inf: no measurement).  std::invalid_argument naming the file when it does not open or
+// is neither.
+void loadDepthFile(const std::string &filename, std::vector<float> *pixels, int *width, int *height);
 // Mesh (DESIGN §8 "Mesh"): a triangle mesh of a file, for software that does not speak Gaussians (include/spz_amd.h
 // "mesh" states the contract).  The file's depth maps over the views (renderSpzDepth's, median depth by default) are
 // fused on the device into a truncated signed distance volume, and its zero level set is extracted by marching

@@ -86,6 +86,9 @@ EXPORTS = (
     "spz_amd_prune_fetch", "spz_amd_prune_device_data", "spz_amd_prune_close",
     "spz_amd_render_depth_device", "spz_amd_render_depth_host", "spz_amd_render_depth_cloud_host",
     "spz_amd_render_backward_workspace_bytes", "spz_amd_render_backward_device",
+    "spz_amd_render_depth_backward_workspace_bytes", "spz_amd_render_depth_backward_device",
+    "spz_amd_depth_loss_workspace_bytes", "spz_amd_depth_loss_device", "spz_amd_depth_default_options",
+    "spz_amd_depth_check", "spz_amd_refine_images_depth_open", "spz_amd_refine_images_depth_host_open",
     "spz_amd_image_metrics_check", "spz_amd_image_metrics_workspace_bytes", "spz_amd_image_metrics_device",
     "spz_amd_image_metrics_host", "spz_amd_compare_host",
     "spz_amd_image_loss_workspace_bytes", "spz_amd_image_loss_device", "spz_amd_adam_scalars_of",
@@ -196,6 +199,7 @@ class ImageMetrics(C.Structure):
 REFINE_MAX_VIEWS = 1024
 TRAIN_ARRAYS = ("positions", "scales", "rotations", "alphas", "colors", "sh")   # bit k of a train_mask
 TRAIN_ALL = 63
+DEPTH_L1, DEPTH_INVERSE_L1 = 0, 1  # the depth loss's kinds
 
 
 class AdamScalars(C.Structure):
@@ -213,6 +217,11 @@ class RefineOptions(C.Structure):
 class PhotoOptions(C.Structure):
     """spz_amd_photo_options (include/spz_amd.h "refine images")."""
     _fields_ = [("fit_exposure", C.c_int32), ("reserved", C.c_int32), ("lr_exposure", C.c_double)]
+
+
+class DepthOptions(C.Structure):
+    """spz_amd_depth_options (include/spz_amd.h "refine images with depth")."""
+    _fields_ = [("weight", C.c_double), ("min_alpha", C.c_float), ("kind", C.c_int32)]
 
 
 EXPOSURE_IDENTITY = (1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0)   # row-major [M | o]
@@ -643,6 +652,15 @@ def bind(L):
     L.spz_amd_render_backward_device.restype = i32
     L.spz_amd_render_backward_device.argtypes = [C.POINTER(CloudPtrs), u64, i32, i32, C.POINTER(RenderParams), u64, vp, vp,
                                                  C.POINTER(CloudPtrs), vp, vp, vp, vp, vp]
+    L.spz_amd_render_depth_backward_workspace_bytes.restype = u64
+    L.spz_amd_render_depth_backward_workspace_bytes.argtypes = [u64]
+    L.spz_amd_render_depth_backward_device.restype = i32
+    L.spz_amd_render_depth_backward_device.argtypes = [C.POINTER(CloudPtrs), u64, i32, i32, C.POINTER(RenderParams), u64,
+                                                       vp, vp, C.POINTER(CloudPtrs), vp, vp, vp, vp, vp, vp]
+    L.spz_amd_depth_loss_workspace_bytes.restype = u64
+    L.spz_amd_depth_loss_workspace_bytes.argtypes = [i32, i32]
+    L.spz_amd_depth_loss_device.restype = i32
+    L.spz_amd_depth_loss_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.c_float, C.c_double, vp, vp, vp, vp, vp]
     L.spz_amd_render_depth_host.restype = i32
     L.spz_amd_render_depth_host.argtypes = [vp, sz, C.POINTER(Header), C.POINTER(RenderParams), i32, vp, vp, vp,
                                             C.POINTER(u64), vp]
@@ -747,6 +765,15 @@ def bind(L):
                                              C.POINTER(DensifyRound), i32, C.POINTER(C.c_int32), vp, vp]
     L.spz_amd_refine_images_host_open.restype = i32
     L.spz_amd_refine_images_host_open.argtypes = L.spz_amd_refine_images_open.argtypes
+    L.spz_amd_depth_default_options.restype = i32
+    L.spz_amd_depth_default_options.argtypes = [C.POINTER(DepthOptions)]
+    L.spz_amd_depth_check.restype = i32
+    L.spz_amd_depth_check.argtypes = [C.POINTER(DepthOptions)]
+    base = L.spz_amd_refine_images_open.argtypes  # two more after the weights, two more at the end
+    L.spz_amd_refine_images_depth_open.restype = i32
+    L.spz_amd_refine_images_depth_open.argtypes = base[:8] + [C.POINTER(vp), C.POINTER(DepthOptions)] + base[8:] + [vp, vp]
+    L.spz_amd_refine_images_depth_host_open.restype = i32
+    L.spz_amd_refine_images_depth_host_open.argtypes = L.spz_amd_refine_images_depth_open.argtypes
     L.spz_amd_render_records_backward_device.restype = i32
     L.spz_amd_render_records_backward_device.argtypes = [u64, C.POINTER(RenderParams), u64, vp, vp, vp, vp, vp]
     L.spz_amd_render_view_backward_workspace_bytes.restype = u64
@@ -955,6 +982,26 @@ def photo_options(fit_exposure=False, lr_exposure=None):
         o.lr_exposure = float(lr_exposure)
     if L.spz_amd_photo_check(C.byref(o)) != OK:
         raise ValueError(f"lr_exposure must be a finite number >= 0, got {lr_exposure!r}")
+    return o
+
+
+def depth_options(weight=None, kind=None, min_alpha=None):
+    """spz_amd_depth_default_options with the given fields replaced (kind: "l1" or "inverse"), checked by
+    spz_amd_depth_check: ValueError on a refused value."""
+    L = load_library()
+    o = DepthOptions()
+    check(L.spz_amd_depth_default_options(C.byref(o)), "spz_amd_depth_default_options")
+    if weight is not None:
+        o.weight = float(weight)
+    if kind is not None:
+        if kind not in ("l1", "inverse"):
+            raise ValueError(f"depth_kind must be 'l1' or 'inverse', got {kind!r}")
+        o.kind = DEPTH_L1 if kind == "l1" else DEPTH_INVERSE_L1
+    if min_alpha is not None:
+        o.min_alpha = float(min_alpha)
+    if L.spz_amd_depth_check(C.byref(o)) != OK:
+        raise ValueError(f"depth_weight must be finite and >= 0 and depth_min_alpha in (0, 1], got {weight!r} and "
+                         f"{min_alpha!r}")
     return o
 
 

@@ -790,11 +790,13 @@ int spzRefine(int argc, char **argv) {
 
 const char *kFitUsage =
     "Usage: spz_fit <in.spz> <out.spz> --views FILE --images a.ppm|a.pfm [b ...] [--masks m.ppm|m.pfm [n ...]] "
-    "[--fit-exposure [--lr-exposure X] [--exposures-out FILE]] " SPZ_REFINE_OPTION_NAMES;
+    "[--fit-exposure [--lr-exposure X] [--exposures-out FILE]] [--depths d0.pfm|none [d1 ...] [--depth-weight W] "
+    "[--depth-kind l1|inverse] [--depth-min-alpha A]] " SPZ_REFINE_OPTION_NAMES;
 
 // spz_refine against photographs: image i (and mask i, whose first channel is the weight) belongs to view i of the
 // views file, as spz_locate writes it.  Prints spz_refine's lines; --exposures-out writes one line of 12 numbers
-// [M | o], row-major, per view.
+// [M | o], row-major, per view.  --depths: depth map i (a PFM as spz_render --depth writes it, or "none") belongs to
+// view i; the depth error before -> after is printed per view that has a map.
 int spzFit(int argc, char **argv) {
   Args a(argc, argv, kFitUsage);
   if (!a.files(2)) return a.usage();
@@ -802,7 +804,9 @@ int spzFit(int argc, char **argv) {
   spz::PhotoOptions p;
   RefineArgs ra;
   std::string viewsFile, exposuresOut;
-  std::vector<std::string> images, masks;
+  std::vector<std::string> images, masks, depths;
+  std::string depthKind;
+  double depthMinAlpha = 0.5;
   std::vector<std::string> *list = nullptr;  // the list a bare argument continues
   while (a.next()) {
     if (list != nullptr && a.arg()[0] != '-') {
@@ -817,11 +821,20 @@ int spzFit(int argc, char **argv) {
     else if (a.is("--fit-exposure")) good = p.fitExposure = true;
     else if (a.is("--lr-exposure")) good = a.real(&p.exposureLr) && std::isfinite(p.exposureLr) && p.exposureLr >= 0.0;
     else if (a.is("--exposures-out")) good = a.text(&exposuresOut);
+    else if (a.is("--depths")) good = a.text(&depths.emplace_back()) && (list = &depths) != nullptr;
+    else if (a.is("--depth-weight")) good = a.real(&p.depthWeight) && std::isfinite(p.depthWeight) && p.depthWeight >= 0.0;
+    else if (a.is("--depth-kind")) good = a.text(&depthKind) && (depthKind == "l1" || depthKind == "inverse");
+    else if (a.is("--depth-min-alpha")) good = a.real(&depthMinAlpha) && depthMinAlpha > 0.0 && depthMinAlpha <= 1.0;
     else if (ra.take(a, o, &good)) {}
     if (!good) return a.usage();
   }
   if (!a.given("--views") || !a.given("--images") || !ra.finish(a, o)) return a.usage();
   if ((a.given("--lr-exposure") || a.given("--exposures-out")) && !p.fitExposure) return a.usage();
+  if ((a.given("--depth-weight") || a.given("--depth-kind") || a.given("--depth-min-alpha")) && !a.given("--depths")) {
+    return a.usage();
+  }
+  p.depthKind = depthKind == "inverse" ? spz::PhotoOptions::InverseL1 : spz::PhotoOptions::L1;
+  p.depthMinAlpha = static_cast<float>(depthMinAlpha);
   try {
     o.views = spz::loadViewsFile(viewsFile);
   } catch (const std::invalid_argument &e) {
@@ -833,6 +846,11 @@ int spzFit(int argc, char **argv) {
               << (masks.empty() ? std::string() : " and " + std::to_string(masks.size()) + " masks") << std::endl;
     return a.usage();
   }
+  if (!depths.empty() && depths.size() != images.size()) {
+    std::cerr << "[SPZ ERROR] spz_fit: " << o.views.size() << " views but " << depths.size() << " depths" << std::endl;
+    return a.usage();
+  }
+  std::vector<std::vector<float>> zmaps(depths.size());
   std::vector<std::vector<float>> pixels(images.size()), weights(masks.size());
   for (size_t v = 0; v < images.size(); ++v) {
     for (int kind = 0; kind < (masks.empty() ? 1 : 2); ++kind) {
@@ -859,10 +877,30 @@ int spzFit(int argc, char **argv) {
     }
     p.images.push_back(spz::PhotoImage{pixels[v].data(), o.views[v].width, o.views[v].height, 3,
                                        masks.empty() ? nullptr : weights[v].data()});
+    if (!depths.empty() && depths[v] != "none") {
+      int w = 0, h = 0;
+      try {
+        spz::loadDepthFile(depths[v], &zmaps[v], &w, &h);
+      } catch (const std::invalid_argument &e) {
+        std::cerr << "[SPZ ERROR] spz_fit: " << e.what() << std::endl;
+        return 1;
+      }
+      if (w != o.views[v].width || h != o.views[v].height) {
+        std::cerr << "[SPZ ERROR] spz_fit: view " << v << " is " << o.views[v].width << " x " << o.views[v].height
+                  << " but " << depths[v] << " is " << w << " x " << h << std::endl;
+        return 1;
+      }
+      p.images.back().depth = zmaps[v].data();
+    }
   }
   spz::PhotoReport r;
   if (!spz::refineSpzToImages(std::string(argv[1]), std::string(argv[2]), o, p, &r)) return 1;
   printRefineReport(r.refine, o.densify);
+  for (size_t v = 0; v < r.depthError.size(); ++v) {
+    if (r.depthError[v][0] < 0.0) continue;  // no map
+    std::printf("view %zu depth error %.17g -> %.17g\n", v, r.depthError[v][0], r.depthError[v][1]);
+  }
+  std::fflush(stdout);
   if (!exposuresOut.empty()) {
     std::ofstream out(exposuresOut);
     char buf[64];

@@ -3067,7 +3067,8 @@ bool refineSpz(const std::string &inputFilename, const std::string &targetFilena
 // ---- fit ---------------------------------------------------------------------------------------------------------
 namespace {
 // One image per view, each of its view's size, one channel count; the options as the C ABI's.
-bool photoOptionsOk(const char *who, const RefineOptions &o, const PhotoOptions &p, spz_amd_photo_options *c) {
+bool photoOptionsOk(const char *who, const RefineOptions &o, const PhotoOptions &p, spz_amd_photo_options *c,
+                    spz_amd_depth_options *z) {
   const int invalid = SPZ_AMD_ERR_INVALID_ARG;
   if (p.images.size() != o.views.size()) {
     return opRejected(who, invalid, "%zu views but %zu images", o.views.size(), p.images.size());
@@ -3088,6 +3089,16 @@ bool photoOptionsOk(const char *who, const RefineOptions &o, const PhotoOptions 
   c->fit_exposure = p.fitExposure ? 1 : 0;
   c->lr_exposure = p.exposureLr;
   if (spz_amd_photo_check(c) != SPZ_AMD_OK) return opRejected(who, invalid, "exposureLr must be finite and >= 0");
+  spz_amd_depth_default_options(z);
+  z->weight = p.depthWeight;
+  z->min_alpha = p.depthMinAlpha;
+  z->kind = p.depthKind == PhotoOptions::InverseL1 ? SPZ_AMD_DEPTH_INVERSE_L1 : SPZ_AMD_DEPTH_L1;
+  if (p.depthKind != PhotoOptions::L1 && p.depthKind != PhotoOptions::InverseL1) {
+    return opRejected(who, invalid, "depthKind must be L1 or InverseL1");
+  }
+  if (spz_amd_depth_check(z) != SPZ_AMD_OK) {
+    return opRejected(who, invalid, "depthWeight must be finite and >= 0 and depthMinAlpha in (0, 1]");
+  }
   return true;
 }
 }  // namespace
@@ -3102,7 +3113,8 @@ bool refineSpzToImages(const uint8_t *data, int32_t size, const RefineOptions &o
   spz_amd_refine_options c;
   spz_amd_densify_options d;
   spz_amd_photo_options pc;
-  if (!refineOptionsOk(o, &params, &c, &d, who) || !photoOptionsOk(who, o, p, &pc)) return false;
+  spz_amd_depth_options zc;
+  if (!refineOptionsOk(o, &params, &c, &d, who) || !photoOptionsOk(who, o, p, &pc, &zc)) return false;
   const bool densify = d.interval > 0;
   if (densify && d.max_points == 0) {
     return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "densify: there is no target to take a count from: set densify.maxPoints");
@@ -3134,13 +3146,16 @@ bool refineSpzToImages(const uint8_t *data, int32_t size, const RefineOptions &o
                         static_cast<unsigned long long>(d.max_points), ha.num_points);
     }
   }
-  std::vector<const float *> targets(nv), weights(nv);
-  bool anyWeights = false;
+  std::vector<const float *> targets(nv), weights(nv), depths(nv);
+  bool anyWeights = false, anyDepth = false;
   for (size_t v = 0; v < nv; ++v) {
     targets[v] = p.images[v].pixels;
     weights[v] = p.images[v].weights;
+    depths[v] = p.images[v].depth;
     anyWeights = anyWeights || weights[v] != nullptr;
+    anyDepth = anyDepth || depths[v] != nullptr;
   }
+  std::vector<double> depthHistory(anyDepth ? static_cast<size_t>(o.iterations) + 1 : 0), depthError(anyDepth ? 2 * nv : 0);
   std::vector<spz_amd_image_metrics> before(nv), after(nv);
   std::vector<double> history(static_cast<size_t>(o.iterations) + 1), exposures(12 * nv);
   OpenResult r(spz_amd_refine_fetch, spz_amd_refine_device_data, spz_amd_refine_close);
@@ -3149,11 +3164,18 @@ bool refineSpzToImages(const uint8_t *data, int32_t size, const RefineOptions &o
   int32_t bad = -1;
   int numRounds = 0;
   std::vector<spz_amd_densify_round> rounds(densify ? static_cast<size_t>(o.iterations / d.interval) + 1 : 0);
-  const int rc = spz_amd_refine_images_host_open(
-      da.stream, da.streamBytes, &ha, params.data(), static_cast<int>(nv), targets.data(), p.images[0].channels,
-      anyWeights ? weights.data() : nullptr, &c, &pc, densify ? &d : nullptr, da.device, &r.ctx, &bytes, history.data(),
-      before.data(), after.data(), &skipped, ms, &bad, &numPoints, rounds.data(), static_cast<int>(rounds.size()),
-      &numRounds, nullptr, exposures.data());
+  const int rc =
+      anyDepth ? spz_amd_refine_images_depth_host_open(
+                     da.stream, da.streamBytes, &ha, params.data(), static_cast<int>(nv), targets.data(),
+                     p.images[0].channels, anyWeights ? weights.data() : nullptr, depths.data(), &zc, &c, &pc,
+                     densify ? &d : nullptr, da.device, &r.ctx, &bytes, history.data(), before.data(), after.data(),
+                     &skipped, ms, &bad, &numPoints, rounds.data(), static_cast<int>(rounds.size()), &numRounds, nullptr,
+                     exposures.data(), depthHistory.data(), depthError.data())
+               : spz_amd_refine_images_host_open(
+                     da.stream, da.streamBytes, &ha, params.data(), static_cast<int>(nv), targets.data(),
+                     p.images[0].channels, anyWeights ? weights.data() : nullptr, &c, &pc, densify ? &d : nullptr,
+                     da.device, &r.ctx, &bytes, history.data(), before.data(), after.data(), &skipped, ms, &bad,
+                     &numPoints, rounds.data(), static_cast<int>(rounds.size()), &numRounds, nullptr, exposures.data());
   if (rc == SPZ_AMD_ERR_UNSUPPORTED) {
     return opRejected(who, rc, "the encoder writes versions 2 and 3 and positions at 12 fractional bits: the input has "
                       "version %u and %u", ha.version, static_cast<unsigned>(ha.fractional_bits));
@@ -3185,6 +3207,12 @@ bool refineSpzToImages(const uint8_t *data, int32_t size, const RefineOptions &o
       const spz_amd_densify_round &x = rounds[static_cast<size_t>(k)];
       rr.rounds.push_back(DensifyRound{x.iteration, x.cloned, x.split, x.culled, x.refused, x.num_points});
     }
+    if (anyDepth) {
+      depthHistory.resize(static_cast<size_t>(o.iterations));
+      report->depthHistory.swap(depthHistory);
+      report->depthError.resize(nv);
+      for (size_t v = 0; v < nv; ++v) report->depthError[v] = {depthError[2 * v], depthError[2 * v + 1]};
+    }
   }
   return true;
 }
@@ -3206,7 +3234,8 @@ bool refineSpzToImages(const std::string &inputFilename, const std::string &outp
   spz_amd_refine_options c;
   spz_amd_densify_options d;
   spz_amd_photo_options pc;
-  if (!refineOptionsOk(o, &params, &c, &d, who) || !photoOptionsOk(who, o, p, &pc)) return false;
+  spz_amd_depth_options zc;
+  if (!refineOptionsOk(o, &params, &c, &d, who) || !photoOptionsOk(who, o, p, &pc, &zc)) return false;
   PhotoReport rep;
   if (!fileToFile(who, "SPZ_AMD_REFINE_TIMING", inputFilename, outputFilename,
                   [&](const uint8_t *data, int32_t size, std::vector<uint8_t> *file) {
@@ -3337,8 +3366,12 @@ bool locateSpz(const std::string &filename, const PruneOptions::View &initial, c
   return locateSpz(data, initial, image, channels, o, report);
 }
 
-void loadImageFile(const std::string &filename, std::vector<float> *pixels, int *width, int *height) {
-  auto bad = [&](const char *why) { return std::invalid_argument("loadImageFile: " + filename + ": " + why); };
+namespace {
+// loadImageFile (depth false: P6 or PF, three channels out) and loadDepthFile (depth true: Pf, or the first channel of a
+// PF; one channel out).
+void loadPixelFile(const char *who, bool depth, const std::string &filename, std::vector<float> *pixels, int *width,
+                   int *height) {
+  auto bad = [&](const char *why) { return std::invalid_argument(std::string(who) + ": " + filename + ": " + why); };
   if (pixels == nullptr || width == nullptr || height == nullptr) throw bad("no output");
   std::ifstream f(filename, std::ios::binary);
   if (!f) throw bad("unable to open");
@@ -3358,15 +3391,20 @@ void loadImageFile(const std::string &filename, std::vector<float> *pixels, int 
     return t;  // the one white-space character after the token is consumed
   };
   const std::string magic = token();
-  if (magic != "P6" && magic != "PF") throw bad("neither a binary PPM (P6) nor a colour PFM (PF)");
+  if (depth) {
+    if (magic != "Pf" && magic != "PF") throw bad("neither a one-channel PFM (Pf) nor a colour PFM (PF)");
+  } else if (magic != "P6" && magic != "PF") {
+    throw bad("neither a binary PPM (P6) nor a colour PFM (PF)");
+  }
+  const size_t in_ch = magic == "Pf" ? 1u : 3u, out_ch = depth ? 1u : 3u;  // of a PF a depth map is the first channel
   char *end = nullptr;
   const std::string ws = token(), hs = token(), last = token();
   const long w = std::strtol(ws.c_str(), &end, 10);
   if (ws.empty() || *end != '\0' || w < 1 || w > 16384) throw bad("bad width");
   const long h = std::strtol(hs.c_str(), &end, 10);
   if (hs.empty() || *end != '\0' || h < 1 || h > 16384) throw bad("bad height");
-  const size_t count = static_cast<size_t>(w) * static_cast<size_t>(h) * 3u;
-  pixels->assign(count, 0.0f);
+  const size_t count = static_cast<size_t>(w) * static_cast<size_t>(h) * in_ch;
+  pixels->assign(static_cast<size_t>(w) * static_cast<size_t>(h) * out_ch, 0.0f);
   if (magic == "P6") {
     if (last != "255") throw bad("maxval must be 255");
     std::vector<uint8_t> raw(count);
@@ -3378,11 +3416,12 @@ void loadImageFile(const std::string &filename, std::vector<float> *pixels, int 
     std::vector<uint8_t> raw(count * 4u);
     if (!f.read(reinterpret_cast<char *>(raw.data()), static_cast<std::streamsize>(raw.size()))) throw bad("short file");
     const bool little = scale < 0.0;
-    const size_t row = static_cast<size_t>(w) * 3u;
+    const size_t row = static_cast<size_t>(w) * out_ch;
     for (size_t y = 0; y < static_cast<size_t>(h); ++y) {
-      const uint8_t *src = raw.data() + (static_cast<size_t>(h) - 1u - y) * row * 4u;  // the file's rows run bottom to top
+      // the file's rows run bottom to top
+      const uint8_t *src = raw.data() + (static_cast<size_t>(h) - 1u - y) * static_cast<size_t>(w) * in_ch * 4u;
       for (size_t k = 0; k < row; ++k) {
-        const uint8_t *b = src + 4u * k;
+        const uint8_t *b = src + 4u * (k / out_ch * in_ch + k % out_ch);
         const uint32_t bits = little ? (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24)
                                      : (uint32_t)b[3] | ((uint32_t)b[2] << 8) | ((uint32_t)b[1] << 16) | ((uint32_t)b[0] << 24);
         float v;
@@ -3393,6 +3432,15 @@ void loadImageFile(const std::string &filename, std::vector<float> *pixels, int 
   }
   *width = static_cast<int>(w);
   *height = static_cast<int>(h);
+}
+}  // namespace
+
+void loadImageFile(const std::string &filename, std::vector<float> *pixels, int *width, int *height) {
+  loadPixelFile("loadImageFile", false, filename, pixels, width, height);
+}
+
+void loadDepthFile(const std::string &filename, std::vector<float> *pixels, int *width, int *height) {
+  loadPixelFile("loadDepthFile", true, filename, pixels, width, height);
 }
 
 // ---- mesh --------------------------------------------------------------------------------------------------------

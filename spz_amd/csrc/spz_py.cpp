@@ -558,11 +558,13 @@ PYBIND11_MODULE(spz, m) {
            const py::object &weights, const py::object &fit_exposure, double lr_exposure, int iterations,
            spz::CoordinateSystem coord, const py::object &background, int max_sh_degree, float near_plane,
            double lambda_dssim, const py::object &lrs, double beta1, double beta2, double eps, const py::object &train,
-           const py::object &densify) {
+           const py::object &densify, const py::object &depths, double depth_weight, const py::object &depth_kind,
+           double depth_min_alpha) {
           const spz::RefineOptions o = refineOptions(views, iterations, coord, background, max_sh_degree, near_plane,
                                                      lambda_dssim, lrs, beta1, beta2, eps, train, densify);
           std::vector<FloatArray> keep;
-          const spz::PhotoOptions p = photoOptions(images, weights, fit_exposure, lr_exposure, o.views, &keep);
+          spz::PhotoOptions p = photoOptions(images, weights, fit_exposure, lr_exposure, o.views, &keep);
+          depthOptionsInto(p, depths, depth_weight, depth_kind, depth_min_alpha, o.views, &keep);
           const Input in(input);
           if (in.bytes && !output.is_none()) {
             throw py::value_error("with bytes in, output must be None: the bytes are returned");
@@ -586,6 +588,14 @@ PYBIND11_MODULE(spz, m) {
             std::copy(rep.exposures[v].begin(), rep.exposures[v].end(), ex.mutable_data() + 12 * v);
           }
           d["exposures"] = ex;
+          if (!rep.depthError.empty()) {
+            d["depth_history"] = rep.depthHistory;
+            py::array_t<double> de(std::vector<py::ssize_t>{static_cast<py::ssize_t>(rep.depthError.size()), 2});
+            for (size_t v = 0; v < rep.depthError.size(); ++v) {
+              std::copy(rep.depthError[v].begin(), rep.depthError[v].end(), de.mutable_data() + 2 * v);
+            }
+            d["depth_error"] = de;
+          }
           return d;
         },
         py::arg("input"), py::arg("output"), py::arg("views"), py::arg("images"), py::arg("weights") = py::none(),
@@ -593,7 +603,8 @@ PYBIND11_MODULE(spz, m) {
         py::arg("coord") = spz::CoordinateSystem::UNSPECIFIED, py::arg("background") = py::make_tuple(0.0f, 0.0f, 0.0f),
         py::arg("max_sh_degree") = 3, py::arg("near") = 0.2f, py::arg("lambda_dssim") = 0.2, py::arg("lrs") = py::none(),
         py::arg("beta1") = 0.9, py::arg("beta2") = 0.999, py::arg("eps") = 1e-15, py::arg("train") = py::none(),
-        py::arg("densify") = py::none(),
+        py::arg("densify") = py::none(), py::arg("depths") = py::none(), py::arg("depth_weight") = 1.0,
+        py::arg("depth_kind") = "l1", py::arg("depth_min_alpha") = 0.5,
         "refine_spz against photographs (spz::refineSpzToImages; the contract is in include/spz_amd.h \"photo loss\" and "
         "\"refine images\"): fit the .spz file `input` (a path, or the file's bytes with output None) to `images`, one "
         "(height, width, 3 or 4) float32 array per view of `views`, of the view's size, values in [0, 1] (load_image).  "
@@ -601,7 +612,12 @@ PYBIND11_MODULE(spz, m) {
         "counts in the loss.  fit_exposure: fit a 3 x 4 colour transform per image beside the cloud, at rate lr_exposure.  "
         "The other keywords are refine_spz's (the position rate defaults to 1.6e-4 times the input's bounding-sphere "
         "radius; densify needs max_points).  Returns refine_spz's dict and \"exposures\", a (views, 3, 4) float64 array "
-        "[M | o], the identity without fit_exposure; \"after\" is of the written stream through the fitted exposure.");
+        "[M | o], the identity without fit_exposure; \"after\" is of the written stream through the fitted exposure.  "
+        "depths: None, or one entry per view, each None or a (height, width) float32 array of metric depth along the "
+        "camera's z (load_depth; not finite or <= 0: no measurement): the loss gains depth_weight times the depth loss "
+        "(include/spz_amd.h \"depth loss\"), depth_kind \"l1\" or \"inverse\", over the pixels of alpha >= "
+        "depth_min_alpha; the dict then also has \"depth_history\" and \"depth_error\", a (views, 2) float64 array: "
+        "the depth loss of the input and of the written stream against each map, -1 for a view without one.");
   m.def("locate_spz",
         [](const py::object &input, const py::object &view, const py::object &image, int iterations, int levels,
            spz::CoordinateSystem coord, const py::object &background, int max_sh_degree, float near_plane,
@@ -649,6 +665,21 @@ PYBIND11_MODULE(spz, m) {
         "A picture as spz_render writes it, as locate_spz takes it: a binary PPM (P6, maxval 255) or a colour PFM (PF, "
         "either byte order) as a (height, width, 3) float32 array, rows top to bottom.  ValueError when the file does "
         "not open or is neither.");
+  m.def("load_depth",
+        [](const std::string &path) {
+          std::vector<float> pixels;
+          int w = 0, h = 0;
+          try {
+            spz::loadDepthFile(path, &pixels, &w, &h);
+          } catch (const std::invalid_argument &e) {
+            throw py::value_error(e.what());
+          }
+          return toArray(pixels, {h, w});
+        },
+        py::arg("path"),
+        "A depth map as spz_render --depth writes it, as refine_spz_to_images takes it: a one-channel PFM (Pf), or the "
+        "first channel of a colour PFM (PF), either byte order, as a (height, width) float32 array, rows top to bottom, "
+        "the floats' bits kept.  ValueError when the file does not open or is neither.");
   m.def("compare_images",
         [](const py::object &a, const py::object &b, const py::object &return_map) {
           const bool want = flag(return_map, "return_map");

@@ -1052,6 +1052,39 @@ spz::PhotoOptions photoOptions(const py::object &images, const py::object &weigh
   return p;
 }
 
+// refine_spz_to_images' depths and depth_* arguments into p (after photoOptions: its checks come first).
+void depthOptionsInto(spz::PhotoOptions &p, const py::object &depths, double depth_weight, const py::object &depth_kind,
+                      double depth_min_alpha, const std::vector<View> &views, std::vector<FloatArray> *keep) {
+  p.depthWeight = finite(depth_weight, Bound::NonNegative, "depth_weight must be finite and >= 0");
+  if (!(depth_min_alpha > 0.0 && depth_min_alpha <= 1.0)) throw py::value_error("depth_min_alpha must be in (0, 1]");
+  p.depthMinAlpha = static_cast<float>(depth_min_alpha);
+  const std::string kind = py::isinstance<py::str>(depth_kind) ? depth_kind.cast<std::string>() : std::string();
+  if (kind != "l1" && kind != "inverse") throw py::value_error("depth_kind must be 'l1' or 'inverse'");
+  p.depthKind = kind == "l1" ? spz::PhotoOptions::L1 : spz::PhotoOptions::InverseL1;
+  if (depths.is_none()) return;
+  if (py::isinstance<py::str>(depths) || py::isinstance<py::array>(depths) || !py::isinstance<py::sequence>(depths)) {
+    throw py::value_error("depths must be None or a sequence of numpy arrays or None, one per view");
+  }
+  const py::sequence ds = py::reinterpret_borrow<py::sequence>(depths);
+  if (ds.size() != views.size()) {
+    throw py::value_error("depths must have one entry per view: " + std::to_string(views.size()) + " views, " +
+                          std::to_string(ds.size()) + " depths");
+  }
+  for (size_t k = 0; k < views.size(); ++k) {
+    const py::object d = py::reinterpret_borrow<py::object>(ds[k]);
+    if (d.is_none()) continue;
+    const std::string bad = "depths[" + std::to_string(k) + "] must be a float32 array of the view's height x width";
+    if (!py::isinstance<py::array>(d)) throw py::value_error(bad);
+    const py::array arr = py::reinterpret_borrow<py::array>(d);
+    if (!arr.dtype().is(py::dtype::of<float>()) || arr.ndim() != 2 || arr.shape(0) != views[k].height ||
+        arr.shape(1) != views[k].width) {
+      throw py::value_error(bad);
+    }
+    keep->push_back(FloatArray(arr));
+    p.images[k].depth = keep->back().data();
+  }
+}
+
 // locate_spz's arguments as spz::LocateOptions.
 spz::LocateOptions locateOptions(int iterations, int levels, spz::CoordinateSystem coord, const py::object &background,
                                  int max_sh_degree, float near_plane, double lambda_dssim, double lr_rotation,

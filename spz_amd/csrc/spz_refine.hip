@@ -17,6 +17,9 @@
 //                                  of spz_photo.hip with each view's weights and, when they are fitted, its exposure
 //                                  read from device memory, and that exposure's own Adam step on the device; "after"
 //                                  through the fitted exposure.
+//   refine images with depth       (DESIGN §8 "Depth fit") a view with a depth map: spz_amd_render_depth_device for the
+//                                  finish, the photo loss, spz_amd_depth_loss_device adding into its gradient, and
+//                                  spz_amd_render_depth_backward_device; the depth error of A and of the output.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -301,6 +304,11 @@ struct PhotoTargets {
   int channels;
   const spz_amd_photo_options *options;
   double *h_exposures;            // may be NULL: 12 doubles per view out
+  // "refine images with depth": all NULL for spz_amd_refine_images_open
+  const float *const *d_depths = nullptr;        // NULL, or num_views depth maps, any of them NULL
+  const spz_amd_depth_options *depth = nullptr;  // required with the depth entries
+  double *h_depth_history = nullptr;             // may be NULL: iterations doubles out
+  double *h_depth_error = nullptr;               // may be NULL: 2 doubles per view out
 };
 
 // The loop of the three entries: spz_amd_refine_open (densify == nullptr), spz_amd_refine_densify_open, and
@@ -327,14 +335,23 @@ int refine_run(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *h
   if (rc != SPZ_AMD_OK) return rc;
   const int tch = photo ? photo->channels : 4;  // the targets' channels
   bool fit = false;
+  bool any_depth = false;  // some view has a depth map
   if (photo != nullptr) {
     rc = spz_amd_photo_check(photo->options);
     if (rc != SPZ_AMD_OK) return rc;
+    if (photo->depth != nullptr) {
+      rc = spz_amd_depth_check(photo->depth);
+      if (rc != SPZ_AMD_OK) return rc;
+    } else if (photo->d_depths != nullptr) {
+      return SPZ_AMD_ERR_INVALID_ARG;
+    }
     if (photo->d_targets == nullptr || (tch != 3 && tch != 4)) return SPZ_AMD_ERR_INVALID_ARG;
     for (int v = 0; v < num_views; ++v) {
       const float *w = photo->d_weights ? photo->d_weights[v] : nullptr;
+      const float *dm = photo->d_depths ? photo->d_depths[v] : nullptr;
+      any_depth = any_depth || dm != nullptr;
       if (photo->d_targets[v] == nullptr || (reinterpret_cast<uintptr_t>(photo->d_targets[v]) & 3u) != 0 ||
-          (reinterpret_cast<uintptr_t>(w) & 3u) != 0 ||
+          (reinterpret_cast<uintptr_t>(w) & 3u) != 0 || (reinterpret_cast<uintptr_t>(dm) & 3u) != 0 ||
           spz_amd_image_metrics_check((int)views[v].width, (int)views[v].height, 4, tch) != SPZ_AMD_OK) {
         if (h_bad_view) *h_bad_view = v;
         return SPZ_AMD_ERR_INVALID_ARG;
@@ -384,7 +401,7 @@ int refine_run(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *h
   // the block: four clouds, the targets, the image and its gradient, the two small workspaces, the results
   uint64_t count[6];
   cloud_counts(cap_n, deg, count);
-  uint64_t max_px = 0, loss_ws = 0, metrics_ws = 0;
+  uint64_t max_px = 0, loss_ws = 0, metrics_ws = 0, depth_ws = 0;
   std::vector<uint64_t> target_off((size_t)num_views);
   for (int v = 0; v < num_views; ++v) {
     const uint64_t px = (uint64_t)views[v].width * views[v].height;
@@ -392,8 +409,10 @@ int refine_run(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *h
     const uint64_t lw = photo ? spz_amd_photo_loss_workspace_bytes((int)views[v].width, (int)views[v].height)
                               : spz_amd_image_loss_workspace_bytes((int)views[v].width, (int)views[v].height);
     const uint64_t mw = spz_amd_image_metrics_workspace_bytes((int)views[v].width, (int)views[v].height);
+    const uint64_t dw = any_depth ? spz_amd_depth_loss_workspace_bytes((int)views[v].width, (int)views[v].height) : 0u;
     loss_ws = lw > loss_ws ? lw : loss_ws;
     metrics_ws = mw > metrics_ws ? mw : metrics_ws;
+    depth_ws = dw > depth_ws ? dw : depth_ws;
   }
   WorkspaceOffsets o;
   uint64_t off[4][6];
@@ -408,7 +427,14 @@ int refine_run(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *h
   const uint64_t o_image = o.put(16u * max_px), o_grad = o.put(16u * max_px), o_lws = o.put(iters ? loss_ws : 0u),
                  o_mws = o.put(metrics_ws), o_small = o.put(16u), o_loss = o.put(24u * (uint64_t)iters),
                  o_metrics = o.put(2u * (uint64_t)num_views * sizeof(spz_amd_image_metrics)),
-                 o_bws = o.put(iters ? spz_amd_render_backward_workspace_bytes(cap_n) : 0u);
+                 o_bws = o.put(!iters       ? 0u
+                               : any_depth ? spz_amd_render_depth_backward_workspace_bytes(cap_n)
+                                           : spz_amd_render_backward_workspace_bytes(cap_n));
+  // with depth maps: the depth render, the gradient to its channel 0, the depth loss's workspace, L_depth and W_v per
+  // iteration, and per view the two depth errors (each L and W_v)
+  const uint64_t o_depth = o.put(any_depth ? 8u * max_px : 0u), o_gdepth = o.put(any_depth ? 4u * max_px : 0u),
+                 o_dws = o.put(depth_ws), o_dloss = o.put(any_depth ? 16u * (uint64_t)iters : 0u),
+                 o_derr = o.put(any_depth ? 32u * (uint64_t)num_views : 0u);
   uint64_t off_alt[3][6] = {};
   for (int s = 0; s < 3; ++s) {
     for (int k = 0; k < 6; ++k) off_alt[s][k] = o.put(dn ? count[k] * 4u : 0u);
@@ -453,6 +479,11 @@ int refine_run(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *h
     return photo ? photo->d_targets[v] : reinterpret_cast<const float *>(raw + target_off[(size_t)v]);
   };
   auto weight = [&](int v) { return photo && photo->d_weights ? photo->d_weights[v] : nullptr; };
+  auto depth_map = [&](int v) { return any_depth ? photo->d_depths[v] : nullptr; };
+  auto *d_depth = reinterpret_cast<float *>(raw + o_depth);
+  auto *d_gdepth = reinterpret_cast<float *>(raw + o_gdepth);
+  auto *d_dloss = reinterpret_cast<double *>(raw + o_dloss);
+  auto *d_derr = reinterpret_cast<double *>(raw + o_derr);
   // view v's exposure at d_exposure + 12 v, its moments 12 V and 24 V doubles on, the gradient after them all
   auto *d_exposure = reinterpret_cast<double *>(raw + o_exposure);
   double *d_exposure_grad = d_exposure + 36u * (size_t)num_views;
@@ -477,6 +508,21 @@ int refine_run(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *h
   auto render = [&](const RenderSource &src, const spz_amd_render_params *p, float *d_out) {
     return render_view(&c->scratch, &cap, src, p, d_total, d_status, d_out, c->st, &total);
   };
+  // render_view with the depth blend for the second stage: the same image, and d_depth
+  auto render_with_depth = [&](const RenderSource &src, const spz_amd_render_params *p, float *d_out) {
+    const int r = prepare_view(&c->scratch, &cap, src, p, d_total, c->st, &total);
+    if (r != SPZ_AMD_OK) return r;
+    return spz_amd_render_depth_device(src.n, p, total, d_out, d_depth, nullptr, d_status, c->scratch, c->st);
+  };
+  // view v's depth error (L and W_v, scale 1) of the depth render in d_image and d_depth, into slot `which` (0: A, 1:
+  // the output stream)
+  auto depth_error = [&](int v, int which) {
+    const spz_amd_render_params &p = views[v];
+    return spz_amd_depth_loss_device(d_depth, d_image, depth_map(v), weight(v), (int)p.width, (int)p.height,
+                                     photo->depth->kind, photo->depth->min_alpha, 1.0,
+                                     d_derr + 2u * (2u * (size_t)v + (size_t)which), d_gdepth, nullptr, raw + o_dws,
+                                     c->st);
+  };
   for (int v = 0; v < num_views; ++v) {
     const spz_amd_render_params &p = views[v];
     if (photo == nullptr) {
@@ -484,11 +530,15 @@ int refine_run(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *h
       rc = render(src_b, &p, reinterpret_cast<float *>(raw + target_off[(size_t)v]));
       if (rc != SPZ_AMD_OK) return fail(v, rc);
     }
-    rc = render(src_a, &p, d_image);
+    rc = depth_map(v) ? render_with_depth(src_a, &p, d_image) : render(src_a, &p, d_image);
     if (rc != SPZ_AMD_OK) return fail(v, rc);
     rc = spz_amd_image_metrics_device(d_image, 4, target(v), tch, (int)p.width, (int)p.height, d_metrics + v, nullptr,
                                       raw + o_mws, c->st);
     if (rc != SPZ_AMD_OK) return fail(v, rc);
+    if (depth_map(v)) {
+      rc = depth_error(v, 0);
+      if (rc != SPZ_AMD_OK) return fail(v, rc);
+    }
   }
   if (fit) {
     SPZ_HIP_TRY(hipMemsetAsync(d_exposure, 0, 3u * 96u * (size_t)num_views + 96u, c->st));
@@ -513,7 +563,8 @@ int refine_run(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *h
     for (int i = 0; i < iters; ++i) {
       const int v = i % num_views;
       const spz_amd_render_params &p = views[v];
-      rc = render(src_f, &p, d_image);
+      const bool with_depth = depth_map(v) != nullptr && photo->depth->weight > 0.0;
+      rc = with_depth ? render_with_depth(src_f, &p, d_image) : render(src_f, &p, d_image);
       if (rc != SPZ_AMD_OK) return fail(v, rc);
       if (photo != nullptr) {
         rc = photo_loss_enqueue(d_image, 4, target(v), tch, weight(v), fit ? d_exposure + 12u * (size_t)v : nullptr,
@@ -532,9 +583,19 @@ int refine_run(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *h
         if (rc != SPZ_AMD_OK) return rc;
       }
       const bool gather_stats = dn && i >= densify->from_iter && i < densify->until_iter;
-      rc = spz_amd_render_backward_device(&cloud, n_cur, deg, aa, &p, total, d_image, d_grad, &cs.g,
-                                          gather_stats && n_cur ? d_rg : nullptr, d_status, c->scratch, raw + o_bws,
-                                          c->st);
+      if (with_depth) {  // the depth term: its gradient to alpha joins the photo loss's d_grad
+        rc = spz_amd_depth_loss_device(d_depth, d_image, depth_map(v), weight(v), (int)p.width, (int)p.height,
+                                       photo->depth->kind, photo->depth->min_alpha, photo->depth->weight,
+                                       d_dloss + 2 * (size_t)i, d_gdepth, d_grad, raw + o_dws, c->st);
+        if (rc != SPZ_AMD_OK) return fail(v, rc);
+        rc = spz_amd_render_depth_backward_device(&cloud, n_cur, deg, aa, &p, total, d_grad, d_gdepth, &cs.g,
+                                                  gather_stats && n_cur ? d_rg : nullptr, nullptr, d_status, c->scratch,
+                                                  raw + o_bws, c->st);
+      } else {
+        rc = spz_amd_render_backward_device(&cloud, n_cur, deg, aa, &p, total, d_image, d_grad, &cs.g,
+                                            gather_stats && n_cur ? d_rg : nullptr, d_status, c->scratch, raw + o_bws,
+                                            c->st);
+      }
       if (rc != SPZ_AMD_OK) return fail(v, rc);
       if (gather_stats && n_cur) {  // the records are the front of the render workspace
         rc = spz_amd_densify_accumulate_device(reinterpret_cast<const spz_amd_render_record *>(align_ws(c->scratch)),
@@ -618,8 +679,12 @@ int refine_run(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *h
   for (int v = 0; v < num_views; ++v) {
     const spz_amd_render_params &p = views[v];
     if (iters == 0) break;
-    rc = render(src_o, &p, d_image);
+    rc = depth_map(v) ? render_with_depth(src_o, &p, d_image) : render(src_o, &p, d_image);
     if (rc != SPZ_AMD_OK) return fail(v, rc);
+    if (depth_map(v)) {
+      rc = depth_error(v, 1);
+      if (rc != SPZ_AMD_OK) return fail(v, rc);
+    }
     if (fit) {  // the file is judged through the exposure fitted for this photograph
       rc = spz_amd_image_exposure_device(d_image, 4, exposures.data() + 12u * (size_t)v, (int)p.width, (int)p.height,
                                          d_image, c->st);
@@ -639,6 +704,11 @@ int refine_run(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *h
   }
   std::vector<double> loss3(3u * (size_t)iters);
   if (iters) SPZ_HIP_TRY(hipMemcpyAsync(loss3.data(), d_loss, 24u * (size_t)iters, hipMemcpyDeviceToHost, c->st));
+  std::vector<double> dloss2(any_depth ? 2u * (size_t)iters : 0u), derr4(any_depth ? 4u * (size_t)num_views : 0u);
+  if (any_depth) {
+    if (iters) SPZ_HIP_TRY(hipMemcpyAsync(dloss2.data(), d_dloss, 16u * (size_t)iters, hipMemcpyDeviceToHost, c->st));
+    SPZ_HIP_TRY(hipMemcpyAsync(derr4.data(), d_derr, 32u * (size_t)num_views, hipMemcpyDeviceToHost, c->st));
+  }
   uint32_t skipped = 0;
   SPZ_HIP_TRY(hipMemcpyAsync(&skipped, d_skipped, 4, hipMemcpyDeviceToHost, c->st));
   if (rep.h_origin && origin_cur && n_cur) {
@@ -651,7 +721,17 @@ int refine_run(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *h
   if (rep.h_num_points) *rep.h_num_points = n_cur;
   if (rep.h_num_rounds) *rep.h_num_rounds = (int)rounds.size();
   for (size_t k = 0; rep.h_rounds && k < rounds.size() && (int)k < rep.rounds_capacity; ++k) rep.h_rounds[k] = rounds[k];
-  for (int i = 0; i < iters; ++i) h_history[i] = loss3[3u * (size_t)i];
+  for (int i = 0; i < iters; ++i) {
+    const bool with_depth = depth_map(i % num_views) != nullptr && photo->depth->weight > 0.0;
+    const double l_depth = with_depth ? dloss2[2u * (size_t)i] : 0.0;
+    h_history[i] = with_depth ? loss3[3u * (size_t)i] + photo->depth->weight * l_depth : loss3[3u * (size_t)i];
+    if (photo && photo->h_depth_history) photo->h_depth_history[i] = l_depth;
+  }
+  for (int v = 0; photo && photo->h_depth_error && v < num_views; ++v) {
+    const bool has = depth_map(v) != nullptr;
+    photo->h_depth_error[2 * v] = has ? derr4[4u * (size_t)v] : -1.0;
+    photo->h_depth_error[2 * v + 1] = has ? derr4[4u * (size_t)v + (iters ? 2u : 0u)] : -1.0;
+  }
   if (h_skipped) *h_skipped = skipped;
   if (h_ms) {
     h_ms[0] = (float)before_ms;
@@ -702,6 +782,33 @@ int spz_amd_refine_densify_open(const uint8_t *d_stream_a, size_t size_a, const 
                     DensifyReport{h_num_points, h_rounds, rounds_capacity, h_num_rounds, h_origin});
 }
 
+int spz_amd_refine_images_depth_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
+                                     const spz_amd_render_params *views, int num_views, const float *const *d_targets,
+                                     int channels, const float *const *d_weights, const float *const *d_depth_targets,
+                                     const spz_amd_depth_options *depth, const spz_amd_refine_options *options,
+                                     const spz_amd_photo_options *photo, const spz_amd_densify_options *densify,
+                                     int device, void **ctx, uint64_t *h_out_bytes, double *h_history,
+                                     spz_amd_image_metrics *h_before, spz_amd_image_metrics *h_after,
+                                     uint64_t *h_skipped, float *h_ms, int32_t *h_bad_view, uint64_t *h_num_points,
+                                     spz_amd_densify_round *h_rounds, int rounds_capacity, int *h_num_rounds,
+                                     uint32_t *h_origin, double *h_exposures, double *h_depth_history,
+                                     double *h_depth_error) {
+  if (rounds_capacity < 0 || (rounds_capacity > 0 && h_rounds == nullptr) || depth == nullptr) {
+    if (h_bad_view) *h_bad_view = -1;
+    if (ctx) *ctx = nullptr;
+    if (h_out_bytes) *h_out_bytes = 0;
+    return SPZ_AMD_ERR_INVALID_ARG;
+  }
+  PhotoTargets targets = {d_targets, d_weights, channels, photo, h_exposures};
+  targets.d_depths = d_depth_targets;
+  targets.depth = depth;
+  targets.h_depth_history = h_depth_history;
+  targets.h_depth_error = h_depth_error;
+  return refine_run(d_stream_a, size_a, hdr_a, nullptr, 0, nullptr, views, num_views, options, densify, device, ctx,
+                    h_out_bytes, h_history, h_before, h_after, h_skipped, h_ms, h_bad_view,
+                    DensifyReport{h_num_points, h_rounds, rounds_capacity, h_num_rounds, h_origin}, &targets);
+}
+
 int spz_amd_refine_images_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
                                const spz_amd_render_params *views, int num_views, const float *const *d_targets,
                                int channels, const float *const *d_weights, const spz_amd_refine_options *options,
@@ -722,15 +829,21 @@ int spz_amd_refine_images_open(const uint8_t *d_stream_a, size_t size_a, const s
                     DensifyReport{h_num_points, h_rounds, rounds_capacity, h_num_rounds, h_origin}, &targets);
 }
 
-int spz_amd_refine_images_host_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
-                                    const spz_amd_render_params *views, int num_views, const float *const *h_targets,
-                                    int channels, const float *const *h_weights, const spz_amd_refine_options *options,
-                                    const spz_amd_photo_options *photo, const spz_amd_densify_options *densify,
-                                    int device, void **ctx, uint64_t *h_out_bytes, double *h_history,
-                                    spz_amd_image_metrics *h_before, spz_amd_image_metrics *h_after, uint64_t *h_skipped,
-                                    float *h_ms, int32_t *h_bad_view, uint64_t *h_num_points,
-                                    spz_amd_densify_round *h_rounds, int rounds_capacity, int *h_num_rounds,
-                                    uint32_t *h_origin, double *h_exposures) {
+}  // extern "C"
+
+namespace {
+
+// refine_images_host_open (depth_entry false: h_depths and depth are NULL) and refine_images_depth_host_open: the
+// images, weight maps and depth maps uploaded, then the device form.
+int images_host_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
+                     const spz_amd_render_params *views, int num_views, const float *const *h_targets, int channels,
+                     const float *const *h_weights, const float *const *h_depths, const spz_amd_depth_options *depth,
+                     bool depth_entry, const spz_amd_refine_options *options, const spz_amd_photo_options *photo,
+                     const spz_amd_densify_options *densify, int device, void **ctx, uint64_t *h_out_bytes,
+                     double *h_history, spz_amd_image_metrics *h_before, spz_amd_image_metrics *h_after,
+                     uint64_t *h_skipped, float *h_ms, int32_t *h_bad_view, uint64_t *h_num_points,
+                     spz_amd_densify_round *h_rounds, int rounds_capacity, int *h_num_rounds, uint32_t *h_origin,
+                     double *h_exposures, double *h_depth_history, double *h_depth_error) {
   if (h_bad_view) *h_bad_view = -1;
   if (ctx) *ctx = nullptr;
   if (h_out_bytes) *h_out_bytes = 0;
@@ -738,14 +851,14 @@ int spz_amd_refine_images_host_open(const uint8_t *d_stream_a, size_t size_a, co
   if (rc != SPZ_AMD_OK) return rc;
   if (h_targets == nullptr || (channels != 3 && channels != 4)) return SPZ_AMD_ERR_INVALID_ARG;
   if (spz_amd_refine_check(options) != SPZ_AMD_OK || spz_amd_photo_check(photo) != SPZ_AMD_OK || rounds_capacity < 0 ||
-      (rounds_capacity > 0 && h_rounds == nullptr)) {
+      (rounds_capacity > 0 && h_rounds == nullptr) || (depth_entry && spz_amd_depth_check(depth) != SPZ_AMD_OK)) {
     return SPZ_AMD_ERR_INVALID_ARG;  // before anything is uploaded
   }
   spz_amd_layout lay_a;
   rc = check_packed_stream(d_stream_a, size_a, hdr_a, &lay_a);
   if (rc != SPZ_AMD_OK) return rc;
   WorkspaceOffsets o;
-  std::vector<uint64_t> t_off((size_t)num_views), w_off((size_t)num_views);
+  std::vector<uint64_t> t_off((size_t)num_views), w_off((size_t)num_views), z_off((size_t)num_views);
   for (int v = 0; v < num_views; ++v) {
     if (h_targets[v] == nullptr) {
       if (h_bad_view) *h_bad_view = v;
@@ -754,6 +867,7 @@ int spz_amd_refine_images_host_open(const uint8_t *d_stream_a, size_t size_a, co
     const uint64_t px = (uint64_t)views[v].width * views[v].height;
     t_off[(size_t)v] = o.put(4u * (uint64_t)channels * px);
     w_off[(size_t)v] = o.put(h_weights && h_weights[v] ? 4u * px : 0u);
+    z_off[(size_t)v] = o.put(h_depths && h_depths[v] ? 4u * px : 0u);
   }
   DeviceGuard guard;
   rc = guard.enter(device);
@@ -765,7 +879,8 @@ int spz_amd_refine_images_host_open(const uint8_t *d_stream_a, size_t size_a, co
     }
   } block;
   SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&block.p), o.off ? o.off : 256u));
-  std::vector<const float *> d_targets((size_t)num_views), d_weights((size_t)num_views, nullptr);
+  std::vector<const float *> d_targets((size_t)num_views), d_weights((size_t)num_views, nullptr),
+      d_depths((size_t)num_views, nullptr);
   for (int v = 0; v < num_views; ++v) {
     const uint64_t px = (uint64_t)views[v].width * views[v].height;
     d_targets[(size_t)v] = reinterpret_cast<const float *>(block.p + t_off[(size_t)v]);
@@ -774,12 +889,59 @@ int spz_amd_refine_images_host_open(const uint8_t *d_stream_a, size_t size_a, co
       d_weights[(size_t)v] = reinterpret_cast<const float *>(block.p + w_off[(size_t)v]);
       SPZ_HIP_TRY(hipMemcpy(block.p + w_off[(size_t)v], h_weights[v], 4u * px, hipMemcpyHostToDevice));
     }
+    if (h_depths && h_depths[v]) {
+      d_depths[(size_t)v] = reinterpret_cast<const float *>(block.p + z_off[(size_t)v]);
+      SPZ_HIP_TRY(hipMemcpy(block.p + z_off[(size_t)v], h_depths[v], 4u * px, hipMemcpyHostToDevice));
+    }
   }
   // (the loop blocks, so the images outlive it)
+  if (depth_entry) {
+    return spz_amd_refine_images_depth_open(d_stream_a, size_a, hdr_a, views, num_views, d_targets.data(), channels,
+                                            h_weights ? d_weights.data() : nullptr, h_depths ? d_depths.data() : nullptr,
+                                            depth, options, photo, densify, device, ctx, h_out_bytes, h_history, h_before,
+                                            h_after, h_skipped, h_ms, h_bad_view, h_num_points, h_rounds, rounds_capacity,
+                                            h_num_rounds, h_origin, h_exposures, h_depth_history, h_depth_error);
+  }
   return spz_amd_refine_images_open(d_stream_a, size_a, hdr_a, views, num_views, d_targets.data(), channels,
                                     h_weights ? d_weights.data() : nullptr, options, photo, densify, device, ctx,
                                     h_out_bytes, h_history, h_before, h_after, h_skipped, h_ms, h_bad_view, h_num_points,
                                     h_rounds, rounds_capacity, h_num_rounds, h_origin, h_exposures);
+}
+
+}  // namespace
+
+extern "C" {
+
+int spz_amd_refine_images_host_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
+                                    const spz_amd_render_params *views, int num_views, const float *const *h_targets,
+                                    int channels, const float *const *h_weights, const spz_amd_refine_options *options,
+                                    const spz_amd_photo_options *photo, const spz_amd_densify_options *densify,
+                                    int device, void **ctx, uint64_t *h_out_bytes, double *h_history,
+                                    spz_amd_image_metrics *h_before, spz_amd_image_metrics *h_after, uint64_t *h_skipped,
+                                    float *h_ms, int32_t *h_bad_view, uint64_t *h_num_points,
+                                    spz_amd_densify_round *h_rounds, int rounds_capacity, int *h_num_rounds,
+                                    uint32_t *h_origin, double *h_exposures) {
+  return images_host_open(d_stream_a, size_a, hdr_a, views, num_views, h_targets, channels, h_weights, nullptr, nullptr,
+                          false, options, photo, densify, device, ctx, h_out_bytes, h_history, h_before, h_after,
+                          h_skipped, h_ms, h_bad_view, h_num_points, h_rounds, rounds_capacity, h_num_rounds, h_origin,
+                          h_exposures, nullptr, nullptr);
+}
+
+int spz_amd_refine_images_depth_host_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
+                                          const spz_amd_render_params *views, int num_views,
+                                          const float *const *h_targets, int channels, const float *const *h_weights,
+                                          const float *const *h_depth_targets, const spz_amd_depth_options *depth,
+                                          const spz_amd_refine_options *options, const spz_amd_photo_options *photo,
+                                          const spz_amd_densify_options *densify, int device, void **ctx,
+                                          uint64_t *h_out_bytes, double *h_history, spz_amd_image_metrics *h_before,
+                                          spz_amd_image_metrics *h_after, uint64_t *h_skipped, float *h_ms,
+                                          int32_t *h_bad_view, uint64_t *h_num_points, spz_amd_densify_round *h_rounds,
+                                          int rounds_capacity, int *h_num_rounds, uint32_t *h_origin,
+                                          double *h_exposures, double *h_depth_history, double *h_depth_error) {
+  return images_host_open(d_stream_a, size_a, hdr_a, views, num_views, h_targets, channels, h_weights, h_depth_targets,
+                          depth, true, options, photo, densify, device, ctx, h_out_bytes, h_history, h_before, h_after,
+                          h_skipped, h_ms, h_bad_view, h_num_points, h_rounds, rounds_capacity, h_num_rounds, h_origin,
+                          h_exposures, h_depth_history, h_depth_error);
 }
 
 int spz_amd_refine_fetch(void *ctx, uint8_t *h_out) { return packed_result_fetch(ctx, h_out); }

@@ -10,11 +10,18 @@
 //                                          summed over the wave by DPP, one lane per wave adds them into the batch's
 //                                          LDS slots, and each non-zero slot value goes to the n x 9 record gradients
 //                                          by one global f32 atomic.
+//   spz_render_depth_blend_backward_kernel the same kernel with the depth sum of spz_render_depth_kernel in it ("render
+//                                          depth backward"; DESIGN §8 "Depth fit"): the record's depth z rides in the
+//                                          .w of the staged rgb, D is blended beside the colour, and a tenth value per
+//                                          used pair, dL/dz, goes to an array of its own (n floats), so the n x 9
+//                                          layout stays what the chain and the view backward read.
 //   spz_render_preprocess_backward_kernel  one lane per Gaussian, f64 like the forward preprocess: the forward's
 //                                          intermediates again from the floats and the camera, then the chain from the
 //                                          nine record gradients to positions, log scales, raw quaternion, alpha,
 //                                          colour and sh.  Writes every output element once (zeros for an invisible
-//                                          Gaussian and for sh above the used degree); no atomics.
+//                                          Gaussian and for sh above the used degree); no atomics.  With the depth
+//                                          gradients given, dL/dp += R[2, :] dL/dz (z is the record's depth,
+//                                          rounded to f32 straight through); without them every bit is as before.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -30,18 +37,6 @@ namespace spz_amd_detail {
 namespace {
 
 constexpr uint32_t kRecGrads = 9;  // mean 2, conic 3, opacity 1, rgb 3: the record's first nine floats
-
-// The sum of an f32 over the 64 lanes of a wave (every lane active): within each row of 16 by DPP (quad xor 1, quad
-// xor 2, half-row mirror, row mirror), then the four rows' values by readlane.  The result is wave-uniform.
-__device__ __forceinline__ float wave_sum_f32(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xb1, 0xf, 0xf, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4e, 0xf, 0xf, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xf, 0xf, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xf, 0xf, false));
-  const int b = __float_as_int(v);
-  return (__int_as_float(__builtin_amdgcn_readlane(b, 0)) + __int_as_float(__builtin_amdgcn_readlane(b, 16))) +
-         (__int_as_float(__builtin_amdgcn_readlane(b, 32)) + __int_as_float(__builtin_amdgcn_readlane(b, 48)));
-}
 
 }  // namespace
 
@@ -208,6 +203,176 @@ __global__ __launch_bounds__(kBlendThreads) void spz_render_blend_backward_kerne
   }
 }
 
+constexpr uint32_t kDepthRecGrads = kRecGrads + 1;  // and the record's depth z
+
+struct DepthBlendBackwardParams {
+  BlendBackwardParams b;    // b.grad_image may be null: all zero
+  const float *grad_depth;  // height x width: the gradient to channel 0 of the depth map
+  float *depth_grad;        // n, zeroed; added into
+};
+
+// spz_render_blend_backward_kernel with the depth sum of spz_render_depth_kernel in it ("render depth backward"):
+// s_rgb[k].w carries the record's depth z, D += (T a) z beside the colour sums, and a tenth value per used pair.  With
+// g_D the pixel's gradient to D, D_i the prefix that includes pair i and D_final the pixel's sum:
+//   dL/dz_i = w g_D
+//   dL/da_i = T (g_rgb . rgb_i + g_D z_i) - (g_rgb . (C_final - C_i) + g_D (D_final - D_i) + tail) / (1 - a)
+// Everything else is that kernel's; the tenth sum goes to an array of its own, so the n x 9 layout stays.
+__global__ __launch_bounds__(kBlendThreads) void spz_render_depth_blend_backward_kernel(const DepthBlendBackwardParams pp) {
+  __shared__ float2 s_xy[kBlendThreads];
+  __shared__ float4 s_co[kBlendThreads];   // conic A, B, C, opacity
+  __shared__ float4 s_rgb[kBlendThreads];  // rgb, depth
+  __shared__ float s_grad[kDepthRecGrads][kBlendThreads];
+  const BlendBackwardParams &p = pp.b;
+  const unsigned long long total = *p.total;
+  if (total > p.max_entries) return;
+  const uint32_t t = threadIdx.x;
+  const uint32_t u = blockIdx.x * kTile + (t % kTile), v = blockIdx.y * kTile + (t / kTile);
+  const bool inside = u < p.width && v < p.height;
+  uint32_t begin = 0, end = 0;
+  if (total != 0ull) {
+    const uint2 r = p.ranges[blockIdx.y * p.tiles_x + blockIdx.x];
+    begin = r.x;
+    end = r.y;
+  }
+  if (begin >= end) return;  // workgroup-uniform: nothing blends here
+  const float fu = (float)u, fv = (float)v;
+  // the forward blend, for the pixel's final colour sum, depth sum and T
+  float T = 1.0f, c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, D = 0.0f;
+  bool done = !inside;
+  for (uint32_t base = begin; base < end; base += kBlendThreads) {
+    // also the barrier between the previous batch's reads and this batch's writes
+    if (__syncthreads_count(done ? 1 : 0) == (int)kBlendThreads) break;
+    const uint32_t j = base + t;
+    if (j < end) {
+      const spz_amd_render_record &q = p.rec[p.sorted_gid[j]];
+      s_xy[t] = make_float2(q.mean[0], q.mean[1]);
+      s_co[t] = make_float4(q.conic[0], q.conic[1], q.conic[2], q.opacity);
+      s_rgb[t] = make_float4(q.rgb[0], q.rgb[1], q.rgb[2], q.depth);
+    }
+    __syncthreads();
+    const uint32_t cnt = (end - base) < kBlendThreads ? end - base : kBlendThreads;
+    for (uint32_t k = 0; k < cnt && !done; ++k) {
+      const float2 xy = s_xy[k];
+      const float4 co = s_co[k];
+      const float dx = fu - xy.x, dy = fv - xy.y;
+      const float power = -0.5f * (co.x * dx * dx + co.z * dy * dy) - co.y * dx * dy;
+      if (power > 0.0f) continue;
+      const float a = fminf(0.99f, co.w * expf(power));
+      if (a < 1.0f / 255.0f) continue;
+      const float Tn = T * (1.0f - a);
+      if (Tn < 1e-4f) {
+        done = true;
+        break;
+      }
+      const float4 rgbz = s_rgb[k];
+      const float w = T * a;
+      c0 = c0 + w * rgbz.x;
+      c1 = c1 + w * rgbz.y;
+      c2 = c2 + w * rgbz.z;
+      D = D + w * rgbz.w;
+      T = Tn;
+    }
+  }
+  const float f0 = c0, f1 = c1, f2 = c2, fD = D;
+  float g0 = 0.0f, g1 = 0.0f, g2 = 0.0f, g3 = 0.0f, gD = 0.0f;
+  if (inside) {
+    const unsigned long long at = (unsigned long long)v * p.width + u;
+    if (p.grad_image) {
+      const float *g = p.grad_image + at * 4u;
+      g0 = g[0];
+      g1 = g[1];
+      g2 = g[2];
+      g3 = g[3];
+    }
+    gD = pp.grad_depth[at];
+  }
+  const float tail = T * ((g0 * p.bg[0] + g1 * p.bg[1] + g2 * p.bg[2]) - g3);  // the background and the alpha channel
+  // the same walk again, in step across the wave (a stopped lane takes no more pairs)
+  T = 1.0f;
+  c0 = 0.0f;
+  c1 = 0.0f;
+  c2 = 0.0f;
+  D = 0.0f;
+  done = !inside;
+  for (uint32_t base = begin; base < end; base += kBlendThreads) {
+    // also the barrier between the previous batch's reads and this batch's writes
+    if (__syncthreads_count(done ? 1 : 0) == (int)kBlendThreads) break;
+    const uint32_t j = base + t;
+    uint32_t gid = 0;
+    if (j < end) {
+      gid = p.sorted_gid[j];
+      const spz_amd_render_record &q = p.rec[gid];
+      s_xy[t] = make_float2(q.mean[0], q.mean[1]);
+      s_co[t] = make_float4(q.conic[0], q.conic[1], q.conic[2], q.opacity);
+      s_rgb[t] = make_float4(q.rgb[0], q.rgb[1], q.rgb[2], q.depth);
+    }
+#pragma unroll
+    for (uint32_t e = 0; e < kDepthRecGrads; ++e) s_grad[e][t] = 0.0f;
+    __syncthreads();
+    const uint32_t cnt = (end - base) < kBlendThreads ? end - base : kBlendThreads;
+    for (uint32_t k = 0; k < cnt; ++k) {
+      if (__ballot(!done) == 0ull) break;  // wave-uniform: every lane of the wave has stopped
+      const float2 xy = s_xy[k];
+      const float4 co = s_co[k];
+      const float dx = fu - xy.x, dy = fv - xy.y;
+      const float power = -0.5f * (co.x * dx * dx + co.z * dy * dy) - co.y * dx * dy;
+      const float ex = expf(power);
+      const float raw = co.w * ex;
+      const float a = fminf(0.99f, raw);
+      const float Tn = T * (1.0f - a);
+      bool use = !done && !(power > 0.0f) && !(a < 1.0f / 255.0f);
+      if (use && Tn < 1e-4f) {
+        done = true;
+        use = false;
+      }
+      if (__ballot(use) == 0ull) continue;  // wave-uniform
+      float d[kDepthRecGrads] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+      if (use) {
+        const float4 rgbz = s_rgb[k];
+        const float w = T * a;
+        c0 = c0 + w * rgbz.x;
+        c1 = c1 + w * rgbz.y;
+        c2 = c2 + w * rgbz.z;
+        D = D + w * rgbz.w;
+        const float front = (g0 * rgbz.x + g1 * rgbz.y + g2 * rgbz.z) + gD * rgbz.w;
+        const float behind = ((g0 * (f0 - c0) + g1 * (f1 - c1) + g2 * (f2 - c2)) + gD * (fD - D)) + tail;
+        const float da = T * front - behind / (1.0f - a);
+        d[6] = w * g0;
+        d[7] = w * g1;
+        d[8] = w * g2;
+        d[9] = w * gD;
+        if (!(raw > 0.99f)) {  // a is opacity e^power
+          const float dp = da * raw;
+          d[0] = dp * (co.x * dx + co.y * dy);
+          d[1] = dp * (co.z * dy + co.y * dx);
+          d[2] = dp * (-0.5f * dx * dx);
+          d[3] = dp * (-(dx * dy));
+          d[4] = dp * (-0.5f * dy * dy);
+          d[5] = da * ex;
+        }
+        T = Tn;
+      }
+#pragma unroll
+      for (uint32_t e = 0; e < kDepthRecGrads; ++e) d[e] = wave_sum_f32(d[e]);
+      if ((t & 63u) == 0u) {
+#pragma unroll
+        for (uint32_t e = 0; e < kDepthRecGrads; ++e) atomicAdd(&s_grad[e][k], d[e]);
+      }
+    }
+    __syncthreads();
+    if (j < end) {
+      float *o = p.rec_grad + (unsigned long long)gid * kRecGrads;
+#pragma unroll
+      for (uint32_t e = 0; e < kRecGrads; ++e) {
+        const float s = s_grad[e][t];
+        if (s != 0.0f) atomicAdd(o + e, s);
+      }
+      const float s = s_grad[kRecGrads][t];
+      if (s != 0.0f) atomicAdd(pp.depth_grad + gid, s);
+    }
+  }
+}
+
 struct PreprocessBackwardParams {
   FloatSrc src;
   RenderCam cam;
@@ -219,6 +384,8 @@ struct PreprocessBackwardParams {
   float *rec_grad_out;  // may be null: n x 9
   uint32_t *status;
   uint32_t n;
+  const float *depth_grad;  // may be null: n, the gradients to the records' depth z ("render depth backward")
+  float *depth_grad_out;    // may be null: n
 };
 
 // The forward's symbols (spz_render_preprocess_kernel): p_c = (x, y, z), R_q, s = exp(log scale), M = R_q diag(s),
@@ -236,6 +403,7 @@ __host__ __device__ inline void preprocess_backward_one(const PreprocessBackward
 #pragma unroll
     for (uint32_t e = 0; e < kRecGrads; ++e) p.rec_grad_out[(unsigned long long)i * kRecGrads + e] = rg[e];
   }
+  if (p.depth_grad_out) p.depth_grad_out[i] = p.depth_grad ? p.depth_grad[i] : 0.0f;
   const spz_amd_render_record q = p.rec[i];
   if (!(q.depth < __builtin_huge_valf())) {  // invisible: the forward's own decision
 #pragma unroll
@@ -389,6 +557,11 @@ __host__ __device__ inline void preprocess_backward_one(const PreprocessBackward
   double gp[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) gp[k] = R[k] * g_x + R[3 + k] * g_y + R[6 + k] * g_z;
+  if (p.depth_grad) {  // the record's depth is z itself, rounded to f32 (straight through)
+    const double g_depth = p.depth_grad[i];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) gp[k] = gp[k] + R[6 + k] * g_depth;
+  }
   // ---- rgb -> colour, sh and the view direction
   double gr[3];
 #pragma unroll
@@ -464,26 +637,24 @@ __global__ __launch_bounds__(kPreBlock) void spz_render_preprocess_backward_kern
 
 using namespace spz_amd_detail;
 
-extern "C" {
+namespace {
 
-uint64_t spz_amd_render_backward_workspace_bytes(uint64_t num_points) {
-  return al(num_points * kRecGrads * sizeof(float)) + 256u;  // room to align a caller's pointer up to 256
-}
-
-int spz_amd_render_backward_device(const spz_amd_cloud_in *d_cloud, uint64_t num_points, int sh_degree, int antialiased,
-                                   const spz_amd_render_params *params, uint64_t max_entries, const float *d_image,
-                                   const float *d_grad_image, const spz_amd_cloud_grads *d_grads, float *d_record_grads,
-                                   uint32_t *d_status, const void *d_render_workspace, void *d_backward_workspace,
-                                   void *hip_stream) {
-  (void)d_image;  // the blend runs again instead: see the contract
+// render_backward_device (d_grad_depth null: the colour blend backward, d_grad_image required) and
+// render_depth_backward_device (d_grad_depth given: the depth blend backward, d_grad_image may be null) are one
+// sequence: clear the record gradients, the blend backward, the per-Gaussian chain.
+int backward_impl(const spz_amd_cloud_in *d_cloud, uint64_t num_points, int sh_degree, int antialiased,
+                  const spz_amd_render_params *params, uint64_t max_entries, const float *d_grad_image,
+                  const float *d_grad_depth, bool depth, const spz_amd_cloud_grads *d_grads, float *d_record_grads,
+                  float *d_depth_grads, uint32_t *d_status, const void *d_render_workspace, void *d_backward_workspace,
+                  void *hip_stream) {
   int rc = check_params(params);
   if (rc != SPZ_AMD_OK) return rc;
   FloatSrc src;
   rc = cloud_source(d_cloud, num_points, sh_degree, &src);
   if (rc != SPZ_AMD_OK) return rc;
   if (max_entries > kMaxEntries) return SPZ_AMD_ERR_INVALID_ARG;
-  if (d_grad_image == nullptr || d_grads == nullptr || d_status == nullptr || d_render_workspace == nullptr ||
-      d_backward_workspace == nullptr) {
+  if ((depth ? d_grad_depth : d_grad_image) == nullptr || d_grads == nullptr || d_status == nullptr ||
+      d_render_workspace == nullptr || d_backward_workspace == nullptr) {
     return SPZ_AMD_ERR_INVALID_ARG;
   }
   if (num_points && (!d_grads->positions || !d_grads->scales || !d_grads->rotations || !d_grads->alphas ||
@@ -499,8 +670,12 @@ int spz_amd_render_backward_device(const spz_amd_cloud_in *d_cloud, uint64_t num
   const RenderLayout wl = render_layout(num_points, max_entries);
   const uint8_t *base = align_ws(const_cast<void *>(d_render_workspace));
   const uint8_t *ent = base + wl.prefix;
-  float *rec_grad = reinterpret_cast<float *>(align_ws(d_backward_workspace));
+  uint8_t *bws = align_ws(d_backward_workspace);
+  float *rec_grad = reinterpret_cast<float *>(bws);
+  // the n depth gradients follow the n x 9 record gradients
+  float *depth_grad = depth ? reinterpret_cast<float *>(bws + al(num_points * kRecGrads * sizeof(float))) : nullptr;
   SPZ_HIP_TRY(hipMemsetAsync(rec_grad, 0, num_points * kRecGrads * sizeof(float), st));
+  if (depth) SPZ_HIP_TRY(hipMemsetAsync(depth_grad, 0, num_points * sizeof(float), st));
   BlendBackwardParams b = {};
   b.rec = reinterpret_cast<const spz_amd_render_record *>(base + wl.rec);
   b.sorted_gid = max_entries ? reinterpret_cast<const uint32_t *>(ent + wl.sorted_gid) : nullptr;
@@ -514,7 +689,15 @@ int spz_amd_render_backward_device(const spz_amd_cloud_in *d_cloud, uint64_t num
   b.tiles_x = (params->width + kTile - 1) / kTile;
   for (int k = 0; k < 3; ++k) b.bg[k] = params->background[k];
   const dim3 grid(b.tiles_x, (params->height + kTile - 1) / kTile);
-  hipLaunchKernelGGL(spz_render_blend_backward_kernel, grid, dim3(kBlendThreads), 0, st, b);
+  if (depth) {
+    DepthBlendBackwardParams db = {};
+    db.b = b;
+    db.grad_depth = d_grad_depth;
+    db.depth_grad = depth_grad;
+    hipLaunchKernelGGL(spz_render_depth_blend_backward_kernel, grid, dim3(kBlendThreads), 0, st, db);
+  } else {
+    hipLaunchKernelGGL(spz_render_blend_backward_kernel, grid, dim3(kBlendThreads), 0, st, b);
+  }
   SPZ_HIP_TRY(hipGetLastError());
   PreprocessBackwardParams q = {};
   q.src = src;
@@ -532,10 +715,46 @@ int spz_amd_render_backward_device(const spz_amd_cloud_in *d_cloud, uint64_t num
   q.rec_grad_out = d_record_grads;
   q.status = d_status;
   q.n = (uint32_t)num_points;
+  q.depth_grad = depth_grad;
+  q.depth_grad_out = depth ? d_depth_grads : nullptr;
   hipLaunchKernelGGL(spz_render_preprocess_backward_kernel, dim3((unsigned)((num_points + kPreBlock - 1) / kPreBlock)),
                      dim3(kPreBlock), 0, st, q);
   SPZ_HIP_TRY(hipGetLastError());
   return SPZ_AMD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t spz_amd_render_backward_workspace_bytes(uint64_t num_points) {
+  return al(num_points * kRecGrads * sizeof(float)) + 256u;  // room to align a caller's pointer up to 256
+}
+
+int spz_amd_render_backward_device(const spz_amd_cloud_in *d_cloud, uint64_t num_points, int sh_degree, int antialiased,
+                                   const spz_amd_render_params *params, uint64_t max_entries, const float *d_image,
+                                   const float *d_grad_image, const spz_amd_cloud_grads *d_grads, float *d_record_grads,
+                                   uint32_t *d_status, const void *d_render_workspace, void *d_backward_workspace,
+                                   void *hip_stream) {
+  (void)d_image;  // the blend runs again instead: see the contract
+  return backward_impl(d_cloud, num_points, sh_degree, antialiased, params, max_entries, d_grad_image, nullptr, false,
+                       d_grads, d_record_grads, nullptr, d_status, d_render_workspace, d_backward_workspace, hip_stream);
+}
+
+uint64_t spz_amd_render_depth_backward_workspace_bytes(uint64_t num_points) {
+  // the n x 9 record gradients, the n depth gradients, and room to align a caller's pointer up to 256
+  return al(num_points * kRecGrads * sizeof(float)) + al(num_points * sizeof(float)) + 256u;
+}
+
+int spz_amd_render_depth_backward_device(const spz_amd_cloud_in *d_cloud, uint64_t num_points, int sh_degree,
+                                         int antialiased, const spz_amd_render_params *params, uint64_t max_entries,
+                                         const float *d_grad_image, const float *d_grad_depth,
+                                         const spz_amd_cloud_grads *d_grads, float *d_record_grads, float *d_depth_grads,
+                                         uint32_t *d_status, const void *d_render_workspace, void *d_backward_workspace,
+                                         void *hip_stream) {
+  return backward_impl(d_cloud, num_points, sh_degree, antialiased, params, max_entries, d_grad_image, d_grad_depth, true,
+                       d_grads, d_record_grads, d_depth_grads, d_status, d_render_workspace, d_backward_workspace,
+                       hip_stream);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // spz_render_internal.hpp — what the translation units of the rasteriser share (spz_render.hip: the forward and its
 // scoring and depth blends; spz_render_backward.hip: the gradients): the tile geometry, the f64 camera, the float
-// cloud's loader, 3DGS's sh constants, the workspace layout of the prepare and entries parts, and the host-side
-// argument checks.
+// cloud's loader, 3DGS's sh constants, the wave sum of the blend backwards, the workspace layout of the prepare and
+// entries parts, and the host-side argument checks.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -71,6 +71,18 @@ constexpr double kC3[7] = {-0.5900435899266435, 2.890611442640554, -0.4570457994
                            -0.4570457994644658, 1.445305721320277, -0.5900435899266435};
 
 __device__ __forceinline__ double clampd(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// The sum of an f32 over the 64 lanes of a wave (every lane active): within each row of 16 by DPP (quad xor 1, quad
+// xor 2, half-row mirror, row mirror), then the four rows' values by readlane.  The result is wave-uniform.
+__device__ __forceinline__ float wave_sum_f32(float v) {
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xb1, 0xf, 0xf, false));
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4e, 0xf, 0xf, false));
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xf, 0xf, false));
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xf, 0xf, false));
+  const int b = __float_as_int(v);
+  return (__int_as_float(__builtin_amdgcn_readlane(b, 0)) + __int_as_float(__builtin_amdgcn_readlane(b, 16))) +
+         (__int_as_float(__builtin_amdgcn_readlane(b, 32)) + __int_as_float(__builtin_amdgcn_readlane(b, 48)));
+}
 
 inline uint64_t al(uint64_t b) { return Workspace::aligned(b); }
 

@@ -1066,6 +1066,129 @@ class _RenderFunction(torch.autograd.Function):
         return (None,) * 5 + out
 
 
+def _depth_rendered_workspace(L, source, n, params, dev, max_entries, st):
+    """_rendered_workspace with render_depth_device for the finish: (image, depth, workspace, m)."""
+    h, w = params.height, params.width
+    image = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
+    depth = torch.empty((h, w, 2), dtype=torch.float32, device=dev)
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws, m = _prepared_workspace(L, source, n, params, dev, max_entries, total, st)
+    rc = L.spz_amd_render_depth_device(n, C.byref(params), m, image.data_ptr(), depth.data_ptr(), None,
+                                       status.data_ptr(), ws.data_ptr(), C.c_void_p(st.cuda_stream))
+    abi.check(rc, "spz_amd_render_depth_device")
+    if max_entries is not None and int(status.cpu()[0]) != 0:  # on st: waits for the depth blend
+        raise RuntimeError(f"{int(total.cpu()[0])} tile entries is above max_entries = {max_entries}")
+    return image, depth, ws, m
+
+
+def _render_depth_backward(L, ptrs, n, sh_degree, antialiased, params, m, grad_image, grad_depth, ws, dev, want_records,
+                           st):
+    """Enqueue spz_amd_render_depth_backward_device on st over the workspace ws of a finished or depth render:
+    (grads, record_grads, depth_grads)."""
+    grads = alloc_cloud(n, sh_degree, dev)
+    gp = abi.CloudPtrs(*[grads[k].data_ptr() if grads[k].numel() else None for k in FIELDS])
+    rec = torch.empty((n, 9), dtype=torch.float32, device=dev) if want_records else None
+    dz = torch.empty(n, dtype=torch.float32, device=dev) if want_records else None
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    bws = torch.empty(int(L.spz_amd_render_depth_backward_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+    rc = L.spz_amd_render_depth_backward_device(C.byref(ptrs), n, sh_degree, 1 if antialiased else 0, C.byref(params), m,
+                                                grad_image.data_ptr() if grad_image is not None else None,
+                                                grad_depth.data_ptr(), C.byref(gp),
+                                                rec.data_ptr() if rec is not None and n else None,
+                                                dz.data_ptr() if dz is not None and n else None, status.data_ptr(),
+                                                ws.data_ptr(), bws.data_ptr(), C.c_void_p(st.cuda_stream))
+    abi.check(rc, "spz_amd_render_depth_backward_device")
+    return grads, rec, dz
+
+
+def _check_grad_depth(grad_depth, params, dev):
+    shape = (params.height, params.width)
+    if (not isinstance(grad_depth, torch.Tensor) or grad_depth.dtype != torch.float32 or grad_depth.device != dev
+            or tuple(grad_depth.shape) != shape):
+        raise ValueError(f"grad_depth must be a float32 tensor of shape {shape} on {dev}")
+    return grad_depth.contiguous()
+
+
+def render_depth_backward(cloud, num_points, sh_degree, params, grad_image, grad_depth, *, antialiased=False,
+                          max_entries=None, return_record_grads=False, stream=None):
+    """render_backward() with the accumulated depth in it (include/spz_amd.h "render depth backward"): the gradients of
+    a scalar loss to a float cloud, given grad_image = its gradient to the image (or None: all zero) and grad_depth =
+    its gradient to render_depth()[..., 0], a (height, width) float32 CUDA tensor.  Renders (prepare + finish), then
+    spz_amd_render_depth_backward_device over the same workspace.  With return_record_grads also "records", (n, 9), and
+    "depth", (n,): the gradient to each Gaussian's record depth z.  Otherwise as render_backward()."""
+    ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
+    L = abi.load_library()
+    _check_render_args(L, params, max_entries)
+    if grad_image is not None:
+        grad_image = _check_grad_image(grad_image, params, dev)
+    grad_depth = _check_grad_depth(grad_depth, params, dev)
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        with torch.cuda.stream(st):
+            source = ("cloud", ptrs, num_points, int(sh_degree), antialiased)
+            _, ws, m = _rendered_workspace(L, source, num_points, params, dev, max_entries, st)
+            grads, rec, dz = _render_depth_backward(L, ptrs, num_points, int(sh_degree), antialiased, params, m,
+                                                    grad_image, grad_depth, ws, dev, return_record_grads, st)
+    if return_record_grads:
+        grads["records"] = rec
+        grads["depth"] = dz
+    return grads
+
+
+class _RenderDepthFunction(torch.autograd.Function):
+    """_RenderFunction with two outputs, the image and channel 0 of the depth map: the forward is render_depth_device
+    (its image is render()'s, bit for bit), the backward spz_amd_render_depth_backward_device over the kept workspace."""
+
+    @staticmethod
+    def forward(ctx, num_points, sh_degree, params, antialiased, max_entries, *arrays):
+        cloud = dict(zip(FIELDS, (a.detach() for a in arrays)))
+        ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
+        L = abi.load_library()
+        _check_render_args(L, params, max_entries)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev)
+            source = ("cloud", ptrs, num_points, int(sh_degree), antialiased)
+            image, depth, ws, m = _depth_rendered_workspace(L, source, num_points, params, dev, max_entries, st)
+        ctx.save_for_backward(ws, *arrays)
+        ctx.args = (num_points, int(sh_degree), params, bool(antialiased), m)
+        return image, depth[..., 0].contiguous()
+
+    @staticmethod
+    def backward(ctx, grad_image, grad_depth):
+        ws = ctx.saved_tensors[0]
+        arrays = ctx.saved_tensors[1:]
+        num_points, sh_degree, params, antialiased, m = ctx.args
+        cloud = dict(zip(FIELDS, (a.detach() for a in arrays)))
+        ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
+        L = abi.load_library()
+        if grad_image is not None:
+            grad_image = _check_grad_image(grad_image, params, dev)
+        if grad_depth is None:
+            grad_depth = torch.zeros((params.height, params.width), dtype=torch.float32, device=dev)
+        grad_depth = _check_grad_depth(grad_depth, params, dev)
+        with torch.cuda.device(dev):
+            grads, _, _ = _render_depth_backward(L, ptrs, num_points, sh_degree, antialiased, params, m, grad_image,
+                                                 grad_depth, ws, dev, False, torch.cuda.current_stream(dev))
+        out = tuple(grads[k].view_as(a) if need else None
+                    for k, a, need in zip(FIELDS, arrays, ctx.needs_input_grad[5:]))
+        return (None,) * 5 + out
+
+
+def render_depth_autograd(cloud, num_points, sh_degree, params, antialiased=False, max_entries=None):
+    """render() and the accumulated depth as one differentiable torch operation: (image, depth0), image bit-identical
+    to render()'s and depth0 (height, width) bit-identical to render_depth()[..., 0]; backward() gives the six arrays of
+    cloud their gradients through both (include/spz_amd.h "render depth backward").  The median depth and the index
+    carry no gradient and are not returned.  Otherwise as render_autograd()."""
+    arrays = []
+    for k in FIELDS:
+        t = cloud.get(k)
+        if t is None:
+            t = torch.empty(0, dtype=torch.float32, device=cloud["positions"].device)
+        arrays.append(t)
+    return _RenderDepthFunction.apply(num_points, sh_degree, params, antialiased, max_entries, *arrays)
+
+
 def _records_backward(L, n, params, m, grad_image, ws, dev, st):
     """Enqueue spz_amd_render_records_backward_device on st over the workspace ws of a finished render: (n, 9)."""
     rec = torch.empty((n, 9), dtype=torch.float32, device=dev)
@@ -1461,6 +1584,58 @@ def photo_loss(a_t, b_t, lambda_dssim, weight=None, exposure=None, grad=None, st
     return loss, grad, egrad
 
 
+DEPTH_KINDS = {"l1": abi.DEPTH_L1, "inverse": abi.DEPTH_INVERSE_L1}
+
+
+def depth_loss(depth_t, image_t, target_t, *, weight=None, kind="l1", min_alpha=0.5, scale=1.0, grad_image=None,
+               stream=None):
+    """The loss of a depth render against a measured depth map and its gradient to the render
+    (spz_amd_depth_loss_device; the contract is in include/spz_amd.h "depth loss"): (loss_t, grad_depth_t).
+    depth_t: render_depth()'s (height, width, 2) float32 CUDA tensor (channel 0 is read); image_t: its (height, width,
+    4) image (alpha is read); target_t: (height, width) float32, metric z, not finite or <= 0 where there is no
+    measurement.  weight: as photo_loss().  kind: "l1" (|D / alpha - t|) or "inverse" (|alpha / D - 1 / t|).  A pixel
+    counts where its weight is > 0, the target is valid, alpha >= min_alpha and D > 0.  scale multiplies the gradients,
+    not the loss.  loss_t: a float64 tensor [L, W_v] on the device, not synchronised.  grad_depth_t: (height, width)
+    float32, render_depth_backward()'s grad_depth.  grad_image: None, or a contiguous (height, width, 4) float32 tensor
+    whose alpha channel the loss's gradient to alpha is added into (photo_loss()'s grad).  stream: as render()."""
+    L = abi.load_library()
+    if not isinstance(image_t, torch.Tensor) or not image_t.is_cuda:
+        raise ValueError("image must be a contiguous float32 CUDA tensor of shape (height, width, 4)")
+    dev = image_t.device
+    if image_t.dtype != torch.float32 or not image_t.is_contiguous() or image_t.dim() != 3 or image_t.shape[2] != 4:
+        raise ValueError("image must be a contiguous float32 CUDA tensor of shape (height, width, 4)")
+    h, w = int(image_t.shape[0]), int(image_t.shape[1])
+    abi.check(L.spz_amd_image_metrics_check(w, h, 4, 4), "spz_amd_image_metrics_check")
+    for name, t, shape in (("depth", depth_t, (h, w, 2)), ("target", target_t, (h, w))):
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous()
+                or tuple(t.shape) != shape):
+            raise ValueError(f"{name} must be a contiguous float32 tensor of shape {shape} on {dev}")
+    if weight is not None and (not isinstance(weight, torch.Tensor) or weight.dtype != torch.float32
+                               or weight.device != dev or not weight.is_contiguous() or tuple(weight.shape) != (h, w)):
+        raise ValueError(f"weight must be a contiguous float32 tensor of shape ({h}, {w}) on {dev}")
+    if kind not in DEPTH_KINDS:
+        raise ValueError(f"kind must be 'l1' or 'inverse', got {kind!r}")
+    min_alpha, scale = float(min_alpha), float(scale)
+    if not 0.0 < min_alpha <= 1.0:
+        raise ValueError(f"min_alpha must be in (0, 1], got {min_alpha!r}")
+    if not 0.0 <= scale < float("inf"):
+        raise ValueError(f"scale must be finite and >= 0, got {scale!r}")
+    _check_out("grad_image", grad_image, (h, w, 4), torch.float32, dev)
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        with torch.cuda.stream(st):
+            loss = torch.empty(2, dtype=torch.float64, device=dev)
+            grad = torch.empty((h, w), dtype=torch.float32, device=dev)
+            ws = torch.empty(int(L.spz_amd_depth_loss_workspace_bytes(w, h)), dtype=torch.uint8, device=dev)
+            rc = L.spz_amd_depth_loss_device(depth_t.data_ptr(), image_t.data_ptr(), target_t.data_ptr(),
+                                             weight.data_ptr() if weight is not None else None, w, h, DEPTH_KINDS[kind],
+                                             min_alpha, scale, loss.data_ptr(), grad.data_ptr(),
+                                             grad_image.data_ptr() if grad_image is not None else None, ws.data_ptr(),
+                                             C.c_void_p(st.cuda_stream))
+    abi.check(rc, "spz_amd_depth_loss_device")
+    return loss, grad
+
+
 def image_exposure(image_t, exposure, out=None, stream=None):
     """out = M a + o over the rgb channels of a (height, width, 3 or 4) float32 CUDA image, unclamped, in f32
     (spz_amd_image_exposure_device): exposure a (3, 4) array-like [M | o]; a fourth channel is copied.  out: None (a
@@ -1752,13 +1927,19 @@ def refine_packed(stream_a, header_a, stream_b, header_b, views, iterations, *, 
 
 def refine_packed_images(stream_a, header_a, views, images, iterations, *, weights=None, fit_exposure=False,
                          lr_exposure=None, lambda_dssim=None, lrs=None, beta1=None, beta2=None, eps=None, train=None,
-                         densify=None):
+                         densify=None, depths=None, depth_weight=None, depth_kind=None, depth_min_alpha=None):
     """refine_packed() against photographs: spz_amd_refine_images_open (include/spz_amd.h "refine images").  images: one
     contiguous (height, width, C) float32 CUDA tensor per view, of the view's size, C in {3, 4} and the same for all;
     they are used in place.  weights: None, or one entry per view, each None or a contiguous (height, width) float32
     CUDA tensor.  fit_exposure: fit a 3 x 4 exposure per view beside the cloud, at rate lr_exposure (None: 0.01).
     densify: as refine_packed(), but max_points must be given.  Returns a RefineResult whose report also has
-    `exposures`, a float64 numpy array (views, 3, 4): the identity without fit_exposure."""
+    `exposures`, a float64 numpy array (views, 3, 4): the identity without fit_exposure.
+    depths: None, or one entry per view, each None or a contiguous (height, width) float32 CUDA tensor of metric depth
+    along the camera's z (not finite or <= 0: no measurement): spz_amd_refine_images_depth_open (include/spz_amd.h
+    "refine images with depth") adds depth_weight (None: 1.0) times the depth loss of kind depth_kind ("l1", the
+    default, or "inverse") over the pixels of alpha >= depth_min_alpha (None: 0.5).  The report then also has
+    `depth_history` (the depth loss before each step, 0 for a view without a map) and `depth_error`, a float64 numpy
+    array (views, 2): the depth loss of A and of the output against the map, -1 for a view without one."""
     import numpy as np
     L = abi.load_library()
     _check_stream_tensor(stream_a)
@@ -1791,6 +1972,22 @@ def refine_packed_images(stream_a, header_a, views, images, iterations, *, weigh
     popts = abi.photo_options(fit_exposure, lr_exposure)
     dopts = abi.densify_options(densify) if densify is not None else None
     nv = len(views)
+    if depths is None:
+        if depth_weight is not None or depth_kind is not None or depth_min_alpha is not None:
+            raise ValueError("depth_weight, depth_kind and depth_min_alpha need depths")
+    else:
+        depths = list(depths)
+        if len(depths) != nv:
+            raise ValueError(f"depths must have one entry per view: {len(depths)} depths, {nv} views")
+        for k, (p, dm) in enumerate(zip(views, depths)):
+            shape = (int(p.height), int(p.width))
+            if dm is not None and (not isinstance(dm, torch.Tensor) or dm.dtype != torch.float32 or dm.device != dev
+                                   or not dm.is_contiguous() or tuple(dm.shape) != shape):
+                raise ValueError(f"depths[{k}] must be a contiguous float32 tensor of shape {shape} on {dev}")
+        zopts = abi.depth_options(depth_weight, depth_kind, depth_min_alpha)
+        zptrs = (C.c_void_p * nv)(*[dm.data_ptr() if dm is not None else None for dm in depths])
+        depth_history = (C.c_double * max(1, opts.iterations))()
+        depth_error = np.zeros((nv, 2), dtype=np.float64)
     arr = (abi.RenderParams * nv)(*views)
     targets = (C.c_void_p * nv)(*[img.data_ptr() for img in images])
     wptrs = (C.c_void_p * nv)(*[wt.data_ptr() if wt is not None else None for wt in weights])
@@ -1806,14 +2003,20 @@ def refine_packed_images(stream_a, header_a, views, images, iterations, *, weigh
     exposures = np.zeros((nv, 3, 4), dtype=np.float64)
     torch.cuda.current_stream(dev).synchronize()  # the stream's and the images' producers
     device_index = dev.index if dev.index is not None else torch.cuda.current_device()
-    rc = L.spz_amd_refine_images_open(stream_a.data_ptr(), stream_a.numel(), C.byref(header_a), arr, nv, targets,
-                                      channels, wptrs if any(wt is not None for wt in weights) else None,
-                                      C.byref(opts), C.byref(popts), C.byref(dopts) if dopts is not None else None,
-                                      device_index, C.byref(ctx), C.byref(out_bytes), history, before, after,
-                                      C.byref(skipped), ms, C.byref(bad), C.byref(n_out), h_rounds, room,
-                                      C.byref(n_rounds), origin.ctypes.data, exposures.ctypes.data)
+    head = (stream_a.data_ptr(), stream_a.numel(), C.byref(header_a), arr, nv, targets, channels,
+            wptrs if any(wt is not None for wt in weights) else None)
+    tail = (C.byref(opts), C.byref(popts), C.byref(dopts) if dopts is not None else None, device_index, C.byref(ctx),
+            C.byref(out_bytes), history, before, after, C.byref(skipped), ms, C.byref(bad), C.byref(n_out), h_rounds,
+            room, C.byref(n_rounds), origin.ctypes.data, exposures.ctypes.data)
+    if depths is None:
+        entry = "spz_amd_refine_images_open"
+        rc = L.spz_amd_refine_images_open(*head, *tail)
+    else:
+        entry = "spz_amd_refine_images_depth_open"
+        rc = L.spz_amd_refine_images_depth_open(*head, zptrs if any(dm is not None for dm in depths) else None,
+                                                C.byref(zopts), *tail, depth_history, depth_error.ctypes.data)
     if rc != abi.OK:
-        err = abi.SpzAmdError(rc, "spz_amd_refine_images_open" + (f" (view {bad.value})" if bad.value >= 0 else ""))
+        err = abi.SpzAmdError(rc, entry + (f" (view {bad.value})" if bad.value >= 0 else ""))
         err.view = bad.value
         raise err
     num_points = int(n_out.value)
@@ -1825,6 +2028,9 @@ def refine_packed_images(stream_a, header_a, views, images, iterations, *, weigh
                                                           "num_points")} for r in h_rounds[:min(room, n_rounds.value)]]}
     if dopts is not None:
         report["origin"] = origin[:num_points].copy()
+    if depths is not None:
+        report["depth_history"] = [depth_history[i] for i in range(max(0, opts.iterations))]
+        report["depth_error"] = depth_error
     return RefineResult(ctx, out_bytes.value, dev, report)
 
 
