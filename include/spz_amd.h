@@ -1033,6 +1033,90 @@ int spz_amd_mesh_open(const uint8_t *d_stream, size_t size, const spz_amd_header
 int spz_amd_mesh_fetch(void *ctx, float *h_positions, float *h_colors, uint32_t *h_triangles);
 void spz_amd_mesh_close(void *ctx);
 
+/* ---- seed: Gaussians from posed RGB-D views (spz_seed.hip; DESIGN §8 "Seed").  The reference has no counterpart.
+ *      Each view's valid depth samples that the cloud built so far does not already explain are lifted to Gaussians
+ *      and appended to a float cloud, view after view in the order given.
+ *
+ *      Inputs per view.  params: a pinhole view as "render" defines it, in its coord frame (background and
+ *      max_sh_degree are not read).  image: height x width x channels f32, channels 3 or 4, rows top to bottom.  depth:
+ *      height x width f32, metric z in scene units; a value that is not finite or not > near_plane is no measurement.
+ *      weights (may be NULL): height x width f32; a sample counts when its weight is > 0.5.
+ *      Options (seed_default_options; seed_check, host only, refuses anything else with SPZ_AMD_ERR_INVALID_ARG):
+ *      stride 1..64 (1); scale_factor > 0, finite (1); alpha, the pre-sigmoid opacity, finite (0: opacity 0.5; the
+ *      layers above take opacity in (0, 1) and convert once); cover_alpha in [0, 1] (0.5); cover_tolerance >= 0,
+ *      finite, relative (0.05); cover 0 or 1 (1); sh_degree 0..3 (0).
+ *
+ *      Lattice.  The samples are the pixels u = stride i + stride / 2, v = stride j + stride / 2 (integer division) for
+ *      all i, j >= 0 with u < width and v < height, in row-major (j, i) order; seed_samples (host only) counts them (0
+ *      for a size or stride out of range).  A sample is valid when its depth is a measurement, its weight (if given)
+ *      counts and its three colour values are finite; the tests run in that order and a plane is not read after a
+ *      test before it failed.
+ *      Cover test: only with cover set, num_points > 0 and the two maps given.  d_cover_image (height x width x 4) and
+ *      d_cover_depth (height x width x 2) are render_depth_device's image and depth of the cloud so far for this view,
+ *      prepared with antialiased = 0, max_sh_degree = sh_degree and background 0.  A valid sample is covered when
+ *      A = image alpha >= cover_alpha and |e - d| <= cover_tolerance d, e = depth[..][0] / A in f32 (expected_depth's
+ *      division), the difference, the product and the comparison in f64 from the f32 values.
+ *      Selection: the valid, uncovered samples in lattice order.  The first capacity - num_points of them are
+ *      appended, at num_points + rank; the rest are counted as refused.
+ *      Each appended Gaussian, in f64 from the f32 inputs, operations in the order written, no contraction, each
+ *      result rounded to f32 once: z = d; q = (((u + 0.5 - cx) / fx) z - t_x, ((v + 0.5 - cy) / fy) z - t_y, z - t_z);
+ *      position_k = (q_x R[0][k] + q_y R[1][k]) + q_z R[2][k], which is R^T (z ray - t); the three log scales =
+ *      log((((scale_factor stride) z) 0.5) (1 / fx + 1 / fy)), the lattice's world-space spacing at that depth;
+ *      rotation (0, 0, 0, 1); alpha = the option; colour = (rgb - 0.5) / C0 with the render's C0; sh zeros.
+ *      No atomics: a scan of per-block counts fixes the order, and a run repeats its bytes.
+ *
+ *      seed_workspace_bytes (host only; 0 for a size or stride out of range): a flag byte per sample and the block
+ *      counts.  seed_view_device: d_cloud's six arrays hold num_points Gaussians and have room for capacity (<= 2^31 -
+ *      1; sh may be NULL iff sh_degree == 0); sh_degree must equal the options'.  d_counts (device memory, 3 uint64):
+ *      valid, appended, refused.  Arguments are checked on the host before any launch (a bad one:
+ *      SPZ_AMD_ERR_INVALID_ARG; no device: SPZ_AMD_ERR_NO_DEVICE).  It enqueues on hip_stream and does not synchronise;
+ *      the caller renders, so a cloud that is being trained can be seeded in place.
+ *
+ *      The host form (seed_open / _fetch / _device_data / _close, shaped like decimate's).  views: 1..
+ *      SPZ_AMD_SEED_MAX_VIEWS, each passing render_check_params, all with one coord.  h_images, channels, h_depths:
+ *      one per view, host memory; h_weights: NULL, or one pointer per view, each of which may be NULL.  base_hdr NULL:
+ *      the cloud starts empty.  Otherwise d_base / base_size / base_hdr is a stream already in device memory whose
+ *      degree equals sh_degree (else SPZ_AMD_ERR_SH_DEGREE); it is decoded to coord as the start of the cloud and is
+ *      used for the cover test only.  max_points: the most new points (0: the sum of the views' sample counts, at most
+ *      SPZ_AMD_REFERENCE_MAX_POINTS; above that: SPZ_AMD_ERR_TOO_MANY_POINTS).  Per view: with cover set and a
+ *      non-empty cloud, prepare (the entry total read back once, the workspace grown), render_depth_device; then the
+ *      upload and seed_view_device.  The output is the NEW points alone, encoded from coord under a fresh version 3
+ *      header (12 fractional bits, not antialiased); spz_amd_merge_* joins it to the base without requantising.
+ *      h_counts (may be NULL): 3 uint64 per view; *h_num_points (may be NULL): the points written; h_ms (may be NULL):
+ *      [0] wall-clock milliseconds of the cover renders, [1] of the uploads, selects and emits, [2] of the encode;
+ *      *h_bad_view (may be NULL): the view a failure concerns, else -1.  An entry total above 2^31 - 1:
+ *      SPZ_AMD_ERR_CAPACITY.  It runs on `device` on a stream of its own and blocks. */
+enum { SPZ_AMD_SEED_MAX_VIEWS = 1024 };
+typedef struct {
+  uint32_t stride;
+  float scale_factor;
+  float alpha;
+  float cover_alpha;
+  float cover_tolerance;
+  int32_t cover;
+  int32_t sh_degree;
+  int32_t reserved;
+} spz_amd_seed_options;
+
+int spz_amd_seed_default_options(spz_amd_seed_options *options);
+int spz_amd_seed_check(const spz_amd_seed_options *options);
+uint64_t spz_amd_seed_samples(uint32_t width, uint32_t height, uint32_t stride);
+uint64_t spz_amd_seed_workspace_bytes(uint32_t width, uint32_t height, uint32_t stride);
+int spz_amd_seed_view_device(const spz_amd_cloud_out *d_cloud, uint64_t num_points, uint64_t capacity, int sh_degree,
+                             const spz_amd_render_params *params, const spz_amd_seed_options *options,
+                             const float *d_image, int channels, const float *d_depth, const float *d_weights,
+                             const float *d_cover_image, const float *d_cover_depth, uint64_t *d_counts,
+                             void *d_workspace, void *hip_stream);
+int spz_amd_seed_open(const spz_amd_render_params *views, int num_views, const spz_amd_seed_options *options,
+                      const float *const *h_images, const int32_t *channels, const float *const *h_depths,
+                      const float *const *h_weights, const uint8_t *d_base, size_t base_size,
+                      const spz_amd_header *base_hdr, uint64_t max_points, int device, void **ctx,
+                      uint64_t *h_out_bytes, uint64_t *h_counts, uint64_t *h_num_points, float *h_ms,
+                      int32_t *h_bad_view);
+int spz_amd_seed_fetch(void *ctx, uint8_t *h_out);
+const uint8_t *spz_amd_seed_device_data(void *ctx);
+void spz_amd_seed_close(void *ctx);
+
 /* ---- image metrics: PSNR, MSE, L1, max error and SSIM of two images (spz_metrics.hip; DESIGN §8 "Compare").  The
  *      reference has no counterpart.  The convention of the 3DGS evaluation code (Kerbl et al. 2023, loss_utils.ssim and
  *      image_utils.psnr), so the numbers compare with published tables.

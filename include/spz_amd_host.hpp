@@ -738,6 +738,47 @@ struct TriangleMesh {
 };
 bool meshSpz(const uint8_t *data, int32_t size, const MeshOptions &options, TriangleMesh *mesh);
 bool meshSpz(const std::string &filename, const MeshOptions &options, TriangleMesh *mesh);
+// Seed (DESIGN §8 "Seed"): a file from posed photographs with depth maps (include/spz_amd.h "seed" states the contract):
+// the first link of seedSpz -> refineSpzToImages with depths and densify -> cleanSpz -> tileSpz.  views: 1..1024 pinhole
+// cameras in the `coord` frame; images: one per view, of the view's size, each with pixels (channels 3 or 4), depth
+// (metric z; not finite or not > nearPlane: no measurement) and optionally weights (a sample counts above 0.5).  Every
+// `stride`-th pixel with a measurement that the cloud built so far does not explain (its rendered alpha below coverAlpha,
+// or its expected depth off by more than coverTolerance times the measurement) becomes an isotropic Gaussian of the
+// lattice's spacing at that depth times scaleFactor, with the pixel's colour and `opacity`.  cover = false lifts every
+// sample.  maxPoints 0: the sum of the views' sample counts, at most 10 M.  base / baseData: an existing file (its name,
+// or its bytes when base is unset and baseData is not empty) of the same shDegree, decoded as the start of the cloud
+// and used for the cover test only: the output holds the NEW points alone, under a version 3 header in `coord`, and
+// mergeSpz joins it to the base without requantising.  A run repeats its bytes.  false + one "[SPZ ERROR] seedSpz: …"
+// line on a bad argument (lastDeviceStatus() = SPZ_AMD_ERR_INVALID_ARG; a bad view is named by its index; an image
+// whose size is not its view's names the view and both sizes; an image without depth names the view), a base that does
+// not load, or a device failure.  SPZ_AMD_SEED_TIMING=1 prints the stages' times.
+struct SeedOptions {
+  std::vector<PruneOptions::View> views;
+  CoordinateSystem coord = CoordinateSystem::UNSPECIFIED;
+  float nearPlane = 0.2f;
+  int stride = 1;
+  double scaleFactor = 1.0;
+  double opacity = 0.5;
+  bool cover = true;
+  float coverAlpha = 0.5f;
+  float coverTolerance = 0.05f;
+  int shDegree = 0;
+  uint64_t maxPoints = 0;
+  std::optional<std::string> base;
+  std::vector<uint8_t> baseData;
+};
+struct SeedReport {
+  struct View {
+    uint64_t valid = 0, appended = 0, refused = 0;
+  };
+  std::vector<View> views;
+  uint64_t numPoints = 0;            // of the output: the sum of the views' appended counts
+  float ms[3] = {0.0f, 0.0f, 0.0f};  // cover renders, uploads + selects + emits, encode
+};
+bool seedSpz(const SeedOptions &options, const std::vector<PhotoImage> &images, std::vector<uint8_t> *out,
+             SeedReport *report = nullptr);
+bool seedSpz(const SeedOptions &options, const std::vector<PhotoImage> &images, const std::string &outputFilename,
+             SeedReport *report = nullptr);
 // A binary little-endian PLY: vertex properties x y z (float) and red green blue (uchar, rint(255 clamp(c, 0, 1)), NaN as
 // 0), faces as "list uchar uint vertex_indices".  false + one "[SPZ ERROR] saveMeshPly: …" line when the arrays' sizes
 // do not match (3 numVertices floats each, 3 numTriangles indices, every index below numVertices) or the file cannot be

@@ -110,6 +110,9 @@ EXPORTS = (
     "spz_amd_mesh_tet_table", "spz_amd_mesh_workspace_bytes", "spz_amd_mesh_count_device", "spz_amd_mesh_emit_device",
     "spz_amd_mesh_default_options", "spz_amd_mesh_check", "spz_amd_mesh_open", "spz_amd_mesh_fetch",
     "spz_amd_mesh_close",
+    "spz_amd_seed_default_options", "spz_amd_seed_check", "spz_amd_seed_samples", "spz_amd_seed_workspace_bytes",
+    "spz_amd_seed_view_device", "spz_amd_seed_open", "spz_amd_seed_fetch", "spz_amd_seed_device_data",
+    "spz_amd_seed_close",
 )
 
 RCCL_UNIQUE_ID_BYTES = 128
@@ -251,6 +254,16 @@ class MeshOptions(C.Structure):
     _fields_ = [("box", C.c_double * 6), ("voxel_size", C.c_double), ("truncation", C.c_double),
                 ("has_box", C.c_int32), ("resolution", C.c_int32), ("depth_kind", C.c_int32),
                 ("min_alpha", C.c_float), ("min_weight", C.c_float), ("reserved", C.c_int32)]
+
+
+SEED_MAX_VIEWS = 1024
+
+
+class SeedOptions(C.Structure):
+    """spz_amd_seed_options (include/spz_amd.h "seed"); spz_amd_seed_default_options fills the defaults.  alpha is the
+    pre-sigmoid opacity."""
+    _fields_ = [("stride", C.c_uint32), ("scale_factor", C.c_float), ("alpha", C.c_float), ("cover_alpha", C.c_float),
+                ("cover_tolerance", C.c_float), ("cover", C.c_int32), ("sh_degree", C.c_int32), ("reserved", C.c_int32)]
 
 
 class DensifyOptions(C.Structure):
@@ -832,6 +845,28 @@ def bind(L):
     L.spz_amd_mesh_fetch.argtypes = [vp, vp, vp, vp]
     L.spz_amd_mesh_close.restype = None
     L.spz_amd_mesh_close.argtypes = [vp]
+    L.spz_amd_seed_default_options.restype = i32
+    L.spz_amd_seed_default_options.argtypes = [C.POINTER(SeedOptions)]
+    L.spz_amd_seed_check.restype = i32
+    L.spz_amd_seed_check.argtypes = [C.POINTER(SeedOptions)]
+    L.spz_amd_seed_samples.restype = u64
+    L.spz_amd_seed_samples.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+    L.spz_amd_seed_workspace_bytes.restype = u64
+    L.spz_amd_seed_workspace_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+    L.spz_amd_seed_view_device.restype = i32
+    L.spz_amd_seed_view_device.argtypes = [C.POINTER(CloudPtrs), u64, u64, i32, C.POINTER(RenderParams),
+                                           C.POINTER(SeedOptions), vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.spz_amd_seed_open.restype = i32
+    L.spz_amd_seed_open.argtypes = [C.POINTER(RenderParams), i32, C.POINTER(SeedOptions), C.POINTER(vp),
+                                    C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(vp), vp, sz, C.POINTER(Header), u64,
+                                    i32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp,
+                                    C.POINTER(C.c_int32)]
+    L.spz_amd_seed_fetch.restype = i32
+    L.spz_amd_seed_fetch.argtypes = [vp, vp]
+    L.spz_amd_seed_device_data.restype = vp
+    L.spz_amd_seed_device_data.argtypes = [vp]
+    L.spz_amd_seed_close.restype = None
+    L.spz_amd_seed_close.argtypes = [vp]
     return L
 
 
@@ -1138,6 +1173,53 @@ def mesh_options(**fields):
         raise ValueError("mesh: refused options (box hi > lo and finite, voxel_size > 0 or resolution 1..2046, "
                          "truncation > 0, min_alpha in [0, 1], min_weight > 0)")
     return o
+
+
+SEED_FIELDS = ("stride", "scale_factor", "opacity", "cover", "cover_alpha", "cover_tolerance", "sh_degree")
+
+
+def seed_alpha(opacity):
+    """The pre-sigmoid alpha of an opacity in (0, 1): log(o / (1 - o)) in f64, rounded to f32 by the options struct; 0.5
+    gives exactly 0.  ValueError outside (0, 1)."""
+    import math
+    o = float(opacity)
+    if not 0.0 < o < 1.0:
+        raise ValueError(f"seed: opacity must be in (0, 1), got {opacity!r}")
+    return math.log(o / (1.0 - o))
+
+
+def seed_options(**fields):
+    """spz_amd_seed_default_options with the given fields (SEED_FIELDS) replaced, checked by spz_amd_seed_check:
+    ValueError on an unknown field or a refused value.  opacity in (0, 1) becomes the struct's pre-sigmoid alpha."""
+    L = load_library()
+    o = SeedOptions()
+    check(L.spz_amd_seed_default_options(C.byref(o)), "spz_amd_seed_default_options")
+    for k in fields:
+        if k not in SEED_FIELDS:
+            raise ValueError(f"seed: unknown option {k!r} (one of {', '.join(SEED_FIELDS)})")
+    f = {k: x for k, x in fields.items() if x is not None}
+    for k in ("stride", "sh_degree"):
+        if k in f:
+            x = f[k]
+            if isinstance(x, bool) or not isinstance(x, int) or not 0 <= x <= 2**31 - 1:
+                raise ValueError(f"seed: {k} must be a non-negative int, got {x!r}")
+            setattr(o, k, x)
+    if "opacity" in f:
+        o.alpha = seed_alpha(f["opacity"])
+    if "cover" in f:
+        o.cover = 1 if f["cover"] else 0
+    for k in ("scale_factor", "cover_alpha", "cover_tolerance"):
+        if k in f:
+            setattr(o, k, float(f[k]))
+    if L.spz_amd_seed_check(C.byref(o)) != OK:
+        raise ValueError("seed: refused options (stride 1..64, scale_factor > 0, opacity in (0, 1), cover_alpha in "
+                         "[0, 1], cover_tolerance >= 0, sh_degree 0..3)")
+    return o
+
+
+def seed_samples(width, height, stride=1):
+    """The number of lattice samples of a width x height view at `stride` (spz_amd_seed_samples, host only)."""
+    return int(load_library().spz_amd_seed_samples(int(width), int(height), int(stride)))
 
 
 def densify_options(options=None, **fields):

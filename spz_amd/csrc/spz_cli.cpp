@@ -1108,6 +1108,98 @@ int spzMesh(int argc, char **argv) {
   return 0;
 }
 
+const char *kSeedUsage =
+    "Usage: spz_seed <out.spz> --views FILE --images a.ppm|a.pfm [b ...] --depths d0.pfm [d1 ...] "
+    "[--masks m.ppm|m.pfm [n ...]] [--onto base.spz] [--stride S] [--scale-factor F] [--opacity O] [--no-cover] "
+    "[--cover-alpha A] [--cover-tolerance T] [--sh-degree D] [--max-points N] [--near Z] [--coord " SPZ_COORD_NAMES "]";
+
+// A file from posed photographs with depth maps (spz::seedSpz): image i, depth map i (a PFM as spz_render --depth writes
+// it) and mask i (its first channel above 0.5: the sample counts) belong to view i of the views file.  With --onto only
+// the points the base does not explain are written; spz_merge joins the two.  Prints one line per view and the total.
+int spzSeed(int argc, char **argv) {
+  Args a(argc, argv, kSeedUsage);
+  if (!a.files(1)) return a.usage();
+  spz::SeedOptions o;
+  ViewArgs va;
+  std::vector<std::string> images, masks, depths;
+  std::string onto;
+  std::vector<std::string> *list = nullptr;  // the list a bare argument continues
+  while (a.next()) {
+    if (list != nullptr && a.arg()[0] != '-') {
+      list->push_back(a.arg());
+      continue;
+    }
+    list = nullptr;
+    bool good = false;
+    if (va.take(a, &good)) {}
+    else if (a.is("--images")) good = a.text(&images.emplace_back()) && (list = &images) != nullptr;
+    else if (a.is("--depths")) good = a.text(&depths.emplace_back()) && (list = &depths) != nullptr;
+    else if (a.is("--masks")) good = a.text(&masks.emplace_back()) && (list = &masks) != nullptr;
+    else if (a.is("--onto")) good = a.text(&onto);
+    else if (a.is("--stride")) good = a.integer(&o.stride, 1, 64);
+    else if (a.is("--scale-factor")) good = a.real(&o.scaleFactor) && std::isfinite(o.scaleFactor) && o.scaleFactor > 0.0;
+    else if (a.is("--opacity")) good = a.real(&o.opacity);  // its range is seedSpz's to refuse
+    else if (a.is("--no-cover")) good = !(o.cover = false);
+    else if (a.is("--cover-alpha")) good = a.real(&o.coverAlpha) && o.coverAlpha >= 0.0f && o.coverAlpha <= 1.0f;
+    else if (a.is("--cover-tolerance")) good = a.real(&o.coverTolerance) && std::isfinite(o.coverTolerance) && o.coverTolerance >= 0.0f;
+    else if (a.is("--sh-degree")) good = a.integer(&o.shDegree, 0, 3);
+    else if (a.is("--max-points")) good = a.integer(&o.maxPoints, 0, 10000000);
+    else if (a.is("--near")) good = a.real(&o.nearPlane) && std::isfinite(o.nearPlane) && o.nearPlane > 0.0f;
+    else if (a.is("--coord")) good = a.coord(&o.coord);
+    if (!good) return a.usage();
+  }
+  if (!a.given("--views") || !va.consistent(a) || !a.given("--images") || !a.given("--depths")) return a.usage();
+  if (depths.size() != images.size() || (!masks.empty() && masks.size() != images.size())) {
+    std::cerr << "[SPZ ERROR] spz_seed: " << images.size() << " images but " << depths.size() << " depths"
+              << (masks.empty() ? std::string() : " and " + std::to_string(masks.size()) + " masks") << std::endl;
+    return a.usage();
+  }
+  const int vr = va.resolve(a, "spz_seed", argv[1], o.coord, &o.views);
+  if (vr != 0) return vr == 2 ? a.usage() : 1;
+  if (!onto.empty()) o.base = onto;
+  // every file at its own size: seedSpz compares an image with its view, an image's depth and mask are compared here
+  std::vector<std::vector<float>> pixels(images.size()), zmaps(images.size()), weights(masks.size());
+  std::vector<spz::PhotoImage> photos;
+  for (size_t v = 0; v < images.size(); ++v) {
+    int w = 0, h = 0;
+    try {
+      spz::loadImageFile(images[v], &pixels[v], &w, &h);
+      photos.push_back(spz::PhotoImage{pixels[v].data(), w, h, 3, nullptr, nullptr});
+      for (int kind = 0; kind < (masks.empty() ? 1 : 2); ++kind) {
+        const std::string &file = kind == 0 ? depths[v] : masks[v];
+        int fw = 0, fh = 0;
+        std::vector<float> rgb;
+        if (kind == 0) spz::loadDepthFile(file, &zmaps[v], &fw, &fh);
+        else spz::loadImageFile(file, &rgb, &fw, &fh);
+        if (fw != w || fh != h) {
+          std::cerr << "[SPZ ERROR] spz_seed: " << images[v] << " is " << w << " x " << h << " but " << file << " is " << fw
+                    << " x " << fh << std::endl;
+          return 1;
+        }
+        if (kind == 0) {
+          photos.back().depth = zmaps[v].data();
+        } else {  // the first channel
+          weights[v].resize(static_cast<size_t>(w) * static_cast<size_t>(h));
+          for (size_t k = 0; k < weights[v].size(); ++k) weights[v][k] = rgb[3 * k];
+          photos.back().weights = weights[v].data();
+        }
+      }
+    } catch (const std::invalid_argument &e) {
+      std::cerr << "[SPZ ERROR] spz_seed: " << e.what() << std::endl;
+      return 1;
+    }
+  }
+  spz::SeedReport r;
+  if (!spz::seedSpz(o, photos, std::string(argv[1]), &r)) return 1;
+  for (size_t v = 0; v < r.views.size(); ++v) {
+    std::printf("view %zu valid %llu appended %llu refused %llu\n", v, static_cast<unsigned long long>(r.views[v].valid),
+                static_cast<unsigned long long>(r.views[v].appended), static_cast<unsigned long long>(r.views[v].refused));
+  }
+  std::printf("points %llu\n", static_cast<unsigned long long>(r.numPoints));
+  std::fflush(stdout);
+  return 0;
+}
+
 const struct {
   const char *name;
   int (*run)(int, char **);
@@ -1116,7 +1208,8 @@ const struct {
               {"spz_sort", spzSort},        {"spz_decimate", spzDecimate},    {"spz_clean", spzClean},
               {"spz_render", spzRender},    {"spz_mesh", spzMesh},            {"spz_prune", spzPrune},
               {"spz_compare", spzCompare},  {"spz_tile", spzTile},            {"spz_align", spzAlign},
-              {"spz_refine", spzRefine},    {"spz_fit", spzFit},              {"spz_locate", spzLocate}};
+              {"spz_refine", spzRefine},    {"spz_fit", spzFit},              {"spz_seed", spzSeed},
+              {"spz_locate", spzLocate}};
 
 int dispatch(const std::string &tool, int argc, char **argv) {
   for (const auto &t : kTools) {

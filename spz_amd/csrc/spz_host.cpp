@@ -3537,6 +3537,126 @@ bool meshSpz(const std::string &filename, const MeshOptions &o, TriangleMesh *me
   return meshSpz(data.data(), static_cast<int32_t>(data.size()), o, mesh);
 }
 
+// ---- seed --------------------------------------------------------------------------------------------------------
+namespace {
+// Everything that needs no device: the options, the views, and the images against the views.
+bool seedOptionsOk(const SeedOptions &o, const std::vector<PhotoImage> &images, spz_amd_seed_options *c,
+                   std::vector<spz_amd_render_params> *params) {
+  const char *who = "seedSpz";
+  const int invalid = SPZ_AMD_ERR_INVALID_ARG;
+  spz_amd_seed_default_options(c);
+  if (o.stride < 1 || o.stride > 64) return opRejected(who, invalid, "stride %d is outside 1..64", o.stride);
+  if (!(o.opacity > 0.0 && o.opacity < 1.0)) return opRejected(who, invalid, "opacity must be in (0, 1)");
+  if (o.shDegree < 0 || o.shDegree > 3) return opRejected(who, invalid, "shDegree %d is outside 0..3", o.shDegree);
+  if (o.maxPoints > SPZ_AMD_REFERENCE_MAX_POINTS) {
+    return opRejected(who, invalid, "maxPoints %llu: the reference reads at most %u points",
+                      static_cast<unsigned long long>(o.maxPoints), SPZ_AMD_REFERENCE_MAX_POINTS);
+  }
+  c->stride = static_cast<uint32_t>(o.stride);
+  c->scale_factor = static_cast<float>(o.scaleFactor);
+  c->alpha = static_cast<float>(std::log(o.opacity / (1.0 - o.opacity)));
+  c->cover_alpha = o.coverAlpha;
+  c->cover_tolerance = o.coverTolerance;
+  c->cover = o.cover ? 1 : 0;
+  c->sh_degree = o.shDegree;
+  if (spz_amd_seed_check(c) != SPZ_AMD_OK) {
+    return opRejected(who, invalid, "bad options: scaleFactor finite and > 0, coverAlpha in [0, 1], coverTolerance "
+                                    "finite and >= 0");
+  }
+  if (!viewListParams(who, o.views, SPZ_AMD_SEED_MAX_VIEWS, {o.nearPlane, o.coord, nullptr, o.shDegree, ", coord valid"},
+                      params)) {
+    return false;
+  }
+  if (images.size() != o.views.size()) {
+    return opRejected(who, invalid, "%zu views but %zu images", o.views.size(), images.size());
+  }
+  for (size_t v = 0; v < images.size(); ++v) {
+    const PhotoImage &im = images[v];
+    if (im.pixels == nullptr) return opRejected(who, invalid, "image %zu has no pixels", v);
+    if (im.channels != 3 && im.channels != 4) return opRejected(who, invalid, "image %zu has %d channels: 3 or 4", v, im.channels);
+    if (im.depth == nullptr) return opRejected(who, invalid, "image %zu has no depth", v);
+    if (im.width != o.views[v].width || im.height != o.views[v].height) {
+      return opRejected(who, invalid, "view %zu is %d x %d but its image is %d x %d", v, o.views[v].width,
+                        o.views[v].height, im.width, im.height);
+    }
+  }
+  return true;
+}
+}  // namespace
+
+bool seedSpz(const SeedOptions &o, const std::vector<PhotoImage> &images, std::vector<uint8_t> *out, SeedReport *report) {
+  const char *who = "seedSpz";
+  g_last_status = SPZ_AMD_OK;
+  if (out == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no output vector");
+  spz_amd_seed_options c;
+  std::vector<spz_amd_render_params> params;
+  if (!seedOptionsOk(o, images, &c, &params)) return false;
+  Laps laps(who, "SPZ_AMD_SEED_TIMING");
+  DevicePackedGaussians d;
+  std::vector<uint8_t> baseFile;
+  const bool onto = o.base.has_value() || !o.baseData.empty();
+  if (onto) {
+    const std::vector<uint8_t> *file = &o.baseData;
+    if (o.base) {
+      if (!readInput(who, *o.base, &baseFile)) return false;
+      file = &baseFile;
+    }
+    if (file->size() > static_cast<size_t>(INT32_MAX)) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "the base is larger than 2 GiB");
+    if (!loadInput(who, file->data(), static_cast<int32_t>(file->size()), &d)) return false;
+    laps.lap("inflate");
+    if (d.shDegree != o.shDegree) {
+      return opRejected(who, SPZ_AMD_ERR_SH_DEGREE, "the base has shDegree %d and the seed %d: they must be equal (filterSpz "
+                                                    "lowers a file's)", d.shDegree, o.shDegree);
+    }
+  }
+  const spz_amd_header hdr = onto ? headerOf(d) : spz_amd_header{};
+  const size_t nv = images.size();
+  std::vector<const float *> pix(nv), dep(nv), wts(nv);
+  std::vector<int32_t> ch(nv);
+  for (size_t v = 0; v < nv; ++v) {
+    pix[v] = images[v].pixels;
+    dep[v] = images[v].depth;
+    wts[v] = images[v].weights;
+    ch[v] = images[v].channels;
+  }
+  std::vector<uint64_t> counts(3u * nv, 0);
+  OpenResult r(spz_amd_seed_fetch, spz_amd_seed_device_data, spz_amd_seed_close);
+  uint64_t bytes = 0, added = 0;
+  float ms[3] = {0.0f, 0.0f, 0.0f};
+  int32_t bad = -1;
+  const int rc = spz_amd_seed_open(params.data(), static_cast<int>(nv), &c, pix.data(), ch.data(), dep.data(), wts.data(),
+                                   onto ? d.stream : nullptr, onto ? d.streamBytes : 0, onto ? &hdr : nullptr, o.maxPoints,
+                                   onto ? d.device : deviceIndex(), &r.ctx, &bytes, counts.data(), &added, ms, &bad);
+  if (viewsFailed(who, rc, bad)) return false;
+  laps.stage("cover", ms[0], (" (" + std::to_string(nv) + " views)").c_str());
+  laps.stage("seed", ms[1]);
+  laps.stage("encode", ms[2]);
+  if (onto) d.release();
+  if (!r.finish(who, bytes, &laps, out)) return false;
+  if (report) {
+    SeedReport rep;
+    rep.views.resize(nv);
+    for (size_t v = 0; v < nv; ++v) rep.views[v] = {counts[3u * v], counts[3u * v + 1u], counts[3u * v + 2u]};
+    rep.numPoints = added;
+    for (int k = 0; k < 3; ++k) rep.ms[k] = ms[k];
+    *report = std::move(rep);
+  }
+  return true;
+}
+
+bool seedSpz(const SeedOptions &o, const std::vector<PhotoImage> &images, const std::string &outputFilename,
+             SeedReport *report) {
+  const char *who = "seedSpz";
+  std::vector<uint8_t> file;
+  SeedReport rep;
+  if (!seedSpz(o, images, &file, &rep)) return false;
+  Laps laps(who, "SPZ_AMD_SEED_TIMING");
+  if (!writeOutput(who, outputFilename, file)) return false;
+  laps.lap("write");
+  if (report) *report = std::move(rep);
+  return true;
+}
+
 bool saveMeshPly(const std::string &filename, const float *vertices, const float *colors, size_t numVertices,
                  const uint32_t *triangles, size_t numTriangles) {
   const char *who = "saveMeshPly";

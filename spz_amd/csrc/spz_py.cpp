@@ -618,6 +618,43 @@ PYBIND11_MODULE(spz, m) {
         "(include/spz_amd.h \"depth loss\"), depth_kind \"l1\" or \"inverse\", over the pixels of alpha >= "
         "depth_min_alpha; the dict then also has \"depth_history\" and \"depth_error\", a (views, 2) float64 array: "
         "the depth loss of the input and of the written stream against each map, -1 for a view without one.");
+  m.def("seed_spz",
+        [](const py::object &views, const py::object &images, const py::object &depths, const py::object &masks,
+           const py::object &out, const py::object &base, const py::object &stride, double scale_factor, double opacity,
+           const py::object &cover, double cover_alpha, double cover_tolerance, const py::object &sh_degree,
+           const py::object &max_points, spz::CoordinateSystem coord, float near_plane) {
+          const spz::SeedOptions o = seedOptions(views, base, stride, scale_factor, opacity, cover, cover_alpha,
+                                                 cover_tolerance, sh_degree, max_points, coord, near_plane);
+          std::vector<FloatArray> keep;
+          spz::PhotoOptions p = photoOptions(images, masks, py::bool_(false), 0.0, o.views, &keep);
+          if (depths.is_none()) throw py::value_error("depths must be a sequence of numpy arrays, one per view");
+          depthOptionsInto(p, depths, 1.0, py::str("l1"), 0.5, o.views, &keep);
+          const std::string path = out.is_none() ? std::string() : py::str(out).cast<std::string>();
+          spz::SeedReport rep;
+          std::vector<uint8_t> data;
+          const bool toBytes = out.is_none();
+          if (!unlocked([&] { return toBytes ? spz::seedSpz(o, p.images, &data, &rep) : spz::seedSpz(o, p.images, path, &rep); })) {
+            raiseFailure("seed_spz");
+          }
+          return seedDict(rep, toBytes ? &data : nullptr);
+        },
+        py::arg("views"), py::arg("images"), py::arg("depths"), py::kw_only(), py::arg("masks") = py::none(),
+        py::arg("out") = py::none(), py::arg("base") = py::none(), py::arg("stride") = 1, py::arg("scale_factor") = 1.0,
+        py::arg("opacity") = 0.5, py::arg("cover") = true, py::arg("cover_alpha") = 0.5, py::arg("cover_tolerance") = 0.05,
+        py::arg("sh_degree") = 0, py::arg("max_points") = 0, py::arg("coord") = spz::CoordinateSystem::UNSPECIFIED,
+        py::arg("near_plane") = 0.2f,
+        "A .spz file from posed photographs with depth maps (spz::seedSpz; the contract is in include/spz_amd.h \"seed\"): "
+        "`images`, one (height, width, 3 or 4) float32 array per view of `views` (dicts as orbit_views returns them, in the "
+        "frame `coord`), and `depths`, one (height, width) float32 array of metric depth along the camera's z per view "
+        "(load_depth; not finite or not > near_plane: no measurement).  masks: None, or one entry per view, each None or a "
+        "(height, width) float32 array: a sample counts above 0.5.  Every stride-th pixel with a measurement that the "
+        "cloud built so far does not explain (rendered alpha under cover_alpha, or expected depth off by more than "
+        "cover_tolerance times the measurement) becomes an isotropic Gaussian of the lattice's spacing at that depth "
+        "times scale_factor, with the pixel's colour and `opacity`; cover False lifts every sample.  max_points 0: the "
+        "sum of the views' sample counts.  base: a .spz file (a path or its bytes) of the same sh_degree to seed onto: "
+        "it is used for the cover test only, the NEW points alone are written, and merge_spz joins the two.  Returns a "
+        "dict: views (valid, appended and refused per view), num_points, ms (cover renders, seeds, encode) and, with out "
+        "None, data, the file's bytes; with out a path the file is written there.");
   m.def("locate_spz",
         [](const py::object &input, const py::object &view, const py::object &image, int iterations, int levels,
            spz::CoordinateSystem coord, const py::object &background, int max_sh_degree, float near_plane,

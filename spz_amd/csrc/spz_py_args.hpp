@@ -1085,6 +1085,55 @@ void depthOptionsInto(spz::PhotoOptions &p, const py::object &depths, double dep
   }
 }
 
+// seed_spz's keyword arguments as spz::SeedOptions (the views first: an image is checked against its view).
+spz::SeedOptions seedOptions(const py::object &views, const py::object &base, const py::object &stride, double scale_factor,
+                             double opacity, const py::object &cover, double cover_alpha, double cover_tolerance,
+                             const py::object &sh_degree, const py::object &max_points, spz::CoordinateSystem coord,
+                             float near_plane) {
+  spz::SeedOptions o;
+  finite(near_plane, Bound::Positive, "near_plane must be > 0");
+  o.coord = coord;
+  o.nearPlane = near_plane;
+  o.stride = intIn<int>(stride, 1, 64, "stride must be an int in 1..64");
+  o.scaleFactor = finite(scale_factor, Bound::Positive, "scale_factor must be finite and > 0");
+  if (!(opacity > 0.0 && opacity < 1.0)) throw py::value_error("opacity must be in (0, 1)");
+  o.opacity = opacity;
+  o.cover = flag(cover, "cover");
+  if (!(cover_alpha >= 0.0 && cover_alpha <= 1.0)) throw py::value_error("cover_alpha must be in [0, 1]");
+  o.coverAlpha = static_cast<float>(cover_alpha);
+  o.coverTolerance = static_cast<float>(finite(cover_tolerance, Bound::NonNegative, "cover_tolerance must be finite and >= 0"));
+  o.shDegree = intIn<int>(sh_degree, 0, 3, "sh_degree must be an int in 0..3");
+  o.maxPoints = intIn<uint64_t>(max_points, 0, SPZ_AMD_REFERENCE_MAX_POINTS, "max_points must be an int in 0..10000000");
+  if (!base.is_none()) {
+    const Input in(base);
+    if (in.bytes) {
+      o.baseData.assign(in.bytes->p, in.bytes->p + in.bytes->n);
+      if (o.baseData.empty()) throw py::value_error("base must be a path or the bytes of a .spz file");
+    } else {
+      o.base = in.path;
+    }
+  }
+  o.views = viewList(views, SPZ_AMD_SEED_MAX_VIEWS, coord, near_plane);
+  return o;
+}
+
+py::dict seedDict(const spz::SeedReport &rep, const std::vector<uint8_t> *data) {
+  py::dict d;
+  py::list views;
+  for (const spz::SeedReport::View &v : rep.views) {
+    py::dict x;
+    x["valid"] = v.valid;
+    x["appended"] = v.appended;
+    x["refused"] = v.refused;
+    views.append(x);
+  }
+  d["views"] = views;
+  d["num_points"] = rep.numPoints;
+  d["ms"] = py::make_tuple(rep.ms[0], rep.ms[1], rep.ms[2]);
+  if (data) d["data"] = py::bytes(reinterpret_cast<const char *>(data->data()), data->size());
+  return d;
+}
+
 // locate_spz's arguments as spz::LocateOptions.
 spz::LocateOptions locateOptions(int iterations, int levels, spz::CoordinateSystem coord, const py::object &background,
                                  int max_sh_degree, float near_plane, double lambda_dssim, double lr_rotation,

@@ -2220,6 +2220,122 @@ def mesh_packed(stream_t, header, views, **options):
     return {"vertices": vertices, "colors": colors, "triangles": triangles, "volume": volume_dict(vol), "ms": tuple(ms)}
 
 
+def _seed_capacity_ptrs(cloud, capacity, sh_degree, dev):
+    p = abi.CloudPtrs()
+    for k in FIELDS:
+        need = capacity * floats_per_point(k, sh_degree)
+        t = cloud.get(k)
+        if need == 0:
+            setattr(p, k, None)
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() \
+                or t.numel() < need:
+            raise ValueError(f"cloud[{k!r}] must be a contiguous float32 tensor of at least {need} elements on {dev}")
+        setattr(p, k, t.data_ptr())
+    return p
+
+
+def _check_map(name, t, shape, dev):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() \
+            or tuple(t.shape) != shape:
+        raise ValueError(f"{name} must be a contiguous float32 tensor of shape {shape} on {dev}")
+
+
+def seed_view(cloud, num_points, capacity, sh_degree, params, image, depth, *, weights=None, cover=True, stride=1,
+              scale_factor=1.0, opacity=0.5, cover_alpha=0.5, cover_tolerance=0.05, max_entries=None, stream=None):
+    """Seed one posed RGB-D view into a float cloud in place (the cover render of the first num_points Gaussians, then
+    spz_amd_seed_view_device; the contract is in include/spz_amd.h "seed").  cloud: device tensors keyed like the
+    GaussianCloud fields, each with room for `capacity` Gaussians, in the frame of the camera `params`
+    (abi.render_params).  image (height, width, 3 or 4), depth (height, width) and weights (height, width, or None):
+    float32 CUDA tensors.  With cover set and num_points > 0 the cloud so far is rendered (render_depth, not
+    antialiased, max_sh_degree = sh_degree, background 0) and samples it explains are skipped.  max_entries: as render();
+    a cover render whose entry total is above it raises RuntimeError before anything is appended.  Returns
+    (new_num_points, counts): counts = (valid, appended, refused), read back once."""
+    L = abi.load_library()
+    _check_render_args(L, params, max_entries)
+    opts = abi.seed_options(stride=stride, scale_factor=scale_factor, opacity=opacity, cover=cover,
+                            cover_alpha=cover_alpha, cover_tolerance=cover_tolerance, sh_degree=sh_degree)
+    for name, x in (("num_points", num_points), ("capacity", capacity)):
+        if isinstance(x, bool) or not isinstance(x, int) or x < 0:
+            raise ValueError(f"{name} must be a non-negative int, got {x!r}")
+    if num_points > capacity:
+        raise ValueError(f"num_points {num_points} is above capacity {capacity}")
+    dev = depth.device if isinstance(depth, torch.Tensor) else None
+    h, w = params.height, params.width
+    _check_map("depth", depth, (h, w), dev)
+    if not isinstance(image, torch.Tensor) or image.dim() != 3 or image.shape[2] not in (3, 4):
+        raise ValueError(f"image must be a float32 tensor of shape ({h}, {w}, 3 or 4)")
+    _check_map("image", image, (h, w, int(image.shape[2])), dev)
+    if weights is not None:
+        _check_map("weights", weights, (h, w), dev)
+    ptrs = _seed_capacity_ptrs(cloud, capacity, sh_degree, dev)
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        with torch.cuda.stream(st):
+            cimage = cdepth = None
+            if opts.cover and num_points > 0:
+                view = abi.RenderParams.from_buffer_copy(params)
+                view.max_sh_degree = int(sh_degree)
+                for a in range(3):
+                    view.background[a] = 0.0
+                head = {k: cloud[k][: num_points * floats_per_point(k, sh_degree)] for k in FIELDS
+                        if floats_per_point(k, sh_degree)}
+                cdepth, cimage, total, status = render_depth(head, num_points, sh_degree, view, antialiased=False,
+                                                             max_entries=max_entries, return_image=True,
+                                                             return_index=False, return_info=True, stream=st)
+                # with status 1 the render wrote neither map: nothing may be decided on them
+                if max_entries is not None and int(status.cpu()[0]) != 0:  # on st: waits for the depth blend
+                    raise RuntimeError(f"{int(total.cpu()[0])} tile entries is above max_entries = {max_entries}")
+            ws = torch.empty(int(L.spz_amd_seed_workspace_bytes(w, h, opts.stride)), dtype=torch.uint8, device=dev)
+            counts = torch.empty(3, dtype=torch.int64, device=dev)
+            rc = L.spz_amd_seed_view_device(C.byref(ptrs), num_points, capacity, int(sh_degree), C.byref(params),
+                                            C.byref(opts), image.data_ptr(), int(image.shape[2]), depth.data_ptr(),
+                                            weights.data_ptr() if weights is not None else None,
+                                            cimage.data_ptr() if cimage is not None else None,
+                                            cdepth.data_ptr() if cdepth is not None else None, counts.data_ptr(),
+                                            ws.data_ptr(), C.c_void_p(st.cuda_stream))
+            abi.check(rc, "spz_amd_seed_view_device")
+            got = tuple(int(x) for x in counts.cpu())  # on st: waits for the emit
+    return num_points + got[1], got
+
+
+def seed(views, images, depths, *, weights=None, sh_degree=0, max_points=0, stream=None, **options):
+    """A float cloud from posed RGB-D views on device tensors: seed_view over `views` (a sequence of abi.RenderParams,
+    one coord) in order, into a cloud allocated for max_points Gaussians (0: the sum of the views' sample counts, at
+    most abi.REFERENCE_MAX_POINTS).  images, depths and weights (None, or one tensor or None per view): as seed_view.
+    options: seed_view's keywords.  Returns (cloud, num_points, counts): the cloud trimmed to num_points, and one
+    (valid, appended, refused) per view."""
+    views, images, depths = list(views), list(images), list(depths)
+    if not 1 <= len(views) <= abi.SEED_MAX_VIEWS or not all(isinstance(p, abi.RenderParams) for p in views):
+        raise ValueError(f"views must be 1..{abi.SEED_MAX_VIEWS} abi.RenderParams")
+    if len(images) != len(views) or len(depths) != len(views):
+        raise ValueError(f"{len(views)} views, {len(images)} images and {len(depths)} depths: the counts differ")
+    weights = [None] * len(views) if weights is None else list(weights)
+    if len(weights) != len(views):
+        raise ValueError(f"{len(views)} views and {len(weights)} weights: the counts differ")
+    if any(p.coord != views[0].coord for p in views):
+        raise ValueError("views must share one coord")
+    if isinstance(max_points, bool) or not isinstance(max_points, int) or not 0 <= max_points <= abi.REFERENCE_MAX_POINTS:
+        raise ValueError(f"max_points must be an int in 0..{abi.REFERENCE_MAX_POINTS}, got {max_points!r}")
+    stride = options.get("stride", 1)
+    abi.seed_options(stride=stride, sh_degree=sh_degree)
+    capacity = max_points or min(abi.REFERENCE_MAX_POINTS,
+                                 sum(abi.seed_samples(p.width, p.height, stride) for p in views))
+    if not isinstance(depths[0], torch.Tensor) or not depths[0].is_cuda:
+        raise ValueError("depths must be float32 CUDA tensors")
+    dev = depths[0].device
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        with torch.cuda.stream(st):
+            cloud = alloc_cloud(capacity, sh_degree, dev)
+            n, counts = 0, []
+            for p, image, depth, weight in zip(views, images, depths, weights):
+                n, got = seed_view(cloud, n, capacity, sh_degree, p, image, depth, weights=weight, stream=st, **options)
+                counts.append(got)
+            cloud = {k: cloud[k][: n * floats_per_point(k, sh_degree)] for k in FIELDS}
+    return cloud, n, counts
+
+
 def convert_coordinates(cloud, num_points, sh_degree, from_coord, to_coord, stream=None):
     """In-place GaussianCloud::convertCoordinates on device tensors (positions, rotations, sh)."""
     L = abi.load_library()
@@ -2249,5 +2365,5 @@ __all__ = ["encode", "decode", "encode_shard", "decode_shard", "decode_gather", 
            "alloc_cloud", "image_loss", "adam_step", "refine_packed",
            "densify_accumulate", "densify_plan", "densify_apply", "reset_opacity",
            "render_view_backward", "image_halve", "locate", "locate_packed",
-           "tsdf_alloc", "tsdf_integrate", "tsdf_extract", "mesh_packed",
+           "tsdf_alloc", "tsdf_integrate", "tsdf_extract", "mesh_packed", "seed_view", "seed",
            "make_header", "to_device", "to_numpy", "SH_DIM"]
