@@ -11,7 +11,8 @@
 //                                          LDS slots, and each non-zero slot value goes to the n x 9 record gradients
 //                                          by one global f32 atomic.
 //   spz_render_depth_blend_backward_kernel the same kernel with the depth sum of spz_render_depth_kernel in it ("render
-//                                          depth backward"; DESIGN §8 "Depth fit"): the record's depth z rides in the
+//                                          depth backward"; DESIGN §8 "Depth fit"): the record's depth, less the
+//                                          depth of the tile's first entry, rides in the
 //                                          .w of the staged rgb, D is blended beside the colour, and a tenth value per
 //                                          used pair, dL/dz, goes to an array of its own (n floats), so the n x 9
 //                                          layout stays what the chain and the view backward read.
@@ -216,7 +217,13 @@ struct DepthBlendBackwardParams {
 // g_D the pixel's gradient to D, D_i the prefix that includes pair i and D_final the pixel's sum:
 //   dL/dz_i = w g_D
 //   dL/da_i = T (g_rgb . rgb_i + g_D z_i) - (g_rgb . (C_final - C_i) + g_D (D_final - D_i) + tail) / (1 - a)
-// Everything else is that kernel's; the tenth sum goes to an array of its own, so the n x 9 layout stays.
+// D_final - D_i is a difference of two long f32 sums of w z, and at camera depths far above the depth range of a tile's
+// list it cancels most of their digits.  So both walks sum w (z - z0) instead, z0 the depth of the tile's first (nearest)
+// entry: D = D' + z0 (1 - T_final), which is the same loss with z - z0 for z and g_alpha + g_D z0 for g_alpha:
+//   dL/da_i = T (g_rgb . rgb_i + g_D (z_i - z0)) - (g_rgb . (C_final - C_i) + g_D (D'_final - D'_i) + tail') / (1 - a)
+//   tail'   = T_final (g_rgb . bg - g_alpha - g_D z0)
+// dL/dz_i is unchanged.  Everything else is that kernel's; the tenth sum goes to an array of its own, so the n x 9
+// layout stays.
 __global__ __launch_bounds__(kBlendThreads) void spz_render_depth_blend_backward_kernel(const DepthBlendBackwardParams pp) {
   __shared__ float2 s_xy[kBlendThreads];
   __shared__ float4 s_co[kBlendThreads];   // conic A, B, C, opacity
@@ -236,7 +243,8 @@ __global__ __launch_bounds__(kBlendThreads) void spz_render_depth_blend_backward
   }
   if (begin >= end) return;  // workgroup-uniform: nothing blends here
   const float fu = (float)u, fv = (float)v;
-  // the forward blend, for the pixel's final colour sum, depth sum and T
+  const float z0 = p.rec[p.sorted_gid[begin]].depth;  // workgroup-uniform: the list is in depth order
+  // the forward blend, for the pixel's final colour sum, depth sum (of z - z0) and T
   float T = 1.0f, c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, D = 0.0f;
   bool done = !inside;
   for (uint32_t base = begin; base < end; base += kBlendThreads) {
@@ -247,7 +255,7 @@ __global__ __launch_bounds__(kBlendThreads) void spz_render_depth_blend_backward
       const spz_amd_render_record &q = p.rec[p.sorted_gid[j]];
       s_xy[t] = make_float2(q.mean[0], q.mean[1]);
       s_co[t] = make_float4(q.conic[0], q.conic[1], q.conic[2], q.opacity);
-      s_rgb[t] = make_float4(q.rgb[0], q.rgb[1], q.rgb[2], q.depth);
+      s_rgb[t] = make_float4(q.rgb[0], q.rgb[1], q.rgb[2], q.depth - z0);
     }
     __syncthreads();
     const uint32_t cnt = (end - base) < kBlendThreads ? end - base : kBlendThreads;
@@ -286,7 +294,8 @@ __global__ __launch_bounds__(kBlendThreads) void spz_render_depth_blend_backward
     }
     gD = pp.grad_depth[at];
   }
-  const float tail = T * ((g0 * p.bg[0] + g1 * p.bg[1] + g2 * p.bg[2]) - g3);  // the background and the alpha channel
+  // the background, the alpha channel and z0 (1 - T_final)
+  const float tail = T * (((g0 * p.bg[0] + g1 * p.bg[1] + g2 * p.bg[2]) - g3) - gD * z0);
   // the same walk again, in step across the wave (a stopped lane takes no more pairs)
   T = 1.0f;
   c0 = 0.0f;
@@ -304,7 +313,7 @@ __global__ __launch_bounds__(kBlendThreads) void spz_render_depth_blend_backward
       const spz_amd_render_record &q = p.rec[gid];
       s_xy[t] = make_float2(q.mean[0], q.mean[1]);
       s_co[t] = make_float4(q.conic[0], q.conic[1], q.conic[2], q.opacity);
-      s_rgb[t] = make_float4(q.rgb[0], q.rgb[1], q.rgb[2], q.depth);
+      s_rgb[t] = make_float4(q.rgb[0], q.rgb[1], q.rgb[2], q.depth - z0);
     }
 #pragma unroll
     for (uint32_t e = 0; e < kDepthRecGrads; ++e) s_grad[e][t] = 0.0f;

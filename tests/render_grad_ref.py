@@ -13,19 +13,21 @@ import torch
 
 import render_ref as RR
 
-BAND = 1e-4
+BAND = RR.BAND
 
 
 def _walk(rec, sel, u, v):
     """render_ref._blend over the Gaussians sel at the pixels (u, v), keeping the decisions: take (pixels, len(sel))
-    bool, the used pairs; and the counts (marginal, stopped pixels, clamped-alpha pairs)."""
+    bool, the used pairs; the marginal pairs per pixel (pixels, int); and the counts (stopped pixels, clamped-alpha
+    pairs)."""
     T = np.ones(u.shape)
     live = np.ones(u.shape, dtype=bool)
     mean = rec["mean"].astype(np.float64)
     conic = rec["conic"].astype(np.float64)
     op = rec["opacity"].astype(np.float64)
     take_all = np.zeros(u.shape + (len(sel),), dtype=bool)
-    marginal = clamped = 0
+    marginal = np.zeros(u.shape, dtype=np.int64)
+    clamped = 0
     for k, g in enumerate(sel):
         if not live.any():
             break
@@ -41,7 +43,7 @@ def _walk(rec, sel, u, v):
         m |= neg & (np.abs(255.0 * a - 1.0) < BAND)
         m |= neg & (np.abs(raw / 0.99 - 1.0) < BAND)
         m |= take & (np.abs(Tn / 1e-4 - 1.0) < BAND)
-        marginal += int(m.sum())
+        marginal += m
         stop = take & (Tn < 1e-4)
         live &= ~stop
         take &= ~stop
@@ -51,27 +53,37 @@ def _walk(rec, sel, u, v):
     return take_all, marginal, int((~live).sum()), clamped
 
 
-def decisions(cloud, sh_degree, cam, antialiased=False):
-    """The constants of forward(): visible (n bool), and per tile the Gaussians in blend order, the pixels and the used
-    pairs; plus the scene's counts: entries, used, stopped (pixels), clamped (alpha pairs), marginal."""
+def _walk_vec(rec, sel, u, v):
+    """_walk through render_ref.walk (vectorised over the list as well): the same four results, for long lists."""
+    wk = RR.walk(rec, sel, u, v)
+    return np.ascontiguousarray(wk["take"].T), wk["marginal"], int(wk["stopped"].sum()), wk["clamped"]
+
+
+def decisions(cloud, sh_degree, cam, antialiased=False, vectorised=False):
+    """The constants of forward(): visible (n bool), and per tile the Gaussians in blend order, the pixels, the used
+    pairs and each pixel's number of marginal pairs; plus the scene's counts: entries, used, stopped (pixels), clamped
+    (alpha pairs), marginal (pairs), and marginal_mask (H, W bool): the pixels with a marginal pair.  vectorised: walk
+    each tile with _walk_vec, which gives the same decisions faster on lists of hundreds of entries."""
     rec = RR.preprocess(cloud, sh_degree, cam, antialiased)
     W, H = cam["width"], cam["height"]
     tw, th = RR.tiles(cam)
     order = RR.depth_order(rec)
     r = rec["rect"][order]
     out = {"visible": rec["visible"].copy(), "tiles": [], "entries": RR.entry_count(rec), "used": 0, "stopped": 0,
-           "clamped": 0, "marginal": 0, "rec": rec}
+           "clamped": 0, "marginal": 0, "marginal_mask": np.zeros((H, W), dtype=bool), "rec": rec}
     for ty in range(th):
         for tx in range(tw):
             sel = order[(r[:, 0] <= tx) & (tx < r[:, 2]) & (r[:, 1] <= ty) & (ty < r[:, 3])]
             vv, uu = np.mgrid[ty * RR.TILE:min(H, ty * RR.TILE + RR.TILE), tx * RR.TILE:min(W, tx * RR.TILE + RR.TILE)]
             uu, vv = uu.ravel(), vv.ravel()
-            take, marginal, stopped, clamped = _walk(rec, sel, uu.astype(np.float64), vv.astype(np.float64))
-            out["tiles"].append({"sel": sel, "u": uu, "v": vv, "take": take})
+            take, marginal, stopped, clamped = (_walk_vec if vectorised else _walk)(
+                rec, sel, uu.astype(np.float64), vv.astype(np.float64))
+            out["tiles"].append({"sel": sel, "u": uu, "v": vv, "take": take, "marginal": marginal})
             out["used"] += int(take.sum())
             out["stopped"] += stopped
             out["clamped"] += clamped
-            out["marginal"] += marginal
+            out["marginal"] += int(marginal.sum())
+            out["marginal_mask"][vv, uu] = marginal > 0
     return out
 
 

@@ -2,6 +2,8 @@
 preprocess (3DGS forward pass with a general principal point), the 16x16 tile rectangles, the (depth, index) order and
 the per-pixel blend.  Vectorised over Gaussians for the preprocess and over a tile's pixels for the blend, which loops
 over the tile's entries.  The records are rounded to float32 as the device stores them, and the blend reads them so.
+For long lists and large views: walk() is the same blend vectorised over a tile's list as well (bit for bit _blend's
+values), and render_tiles() renders only the tiles asked for.
 
 A cloud is a dict of the GaussianCloud arrays (float32): positions, scales, rotations (xyzw), alphas, colors, sh
 ([point][coeff][rgb]), already in the camera's frame."""
@@ -174,6 +176,121 @@ def _blend(rec, order, u, v, cam):
         C[take] += (T[take] * a[take])[:, None] * rgb[g][None, :]
         T = np.where(take, Tn, T)
     return C, T
+
+
+BAND = 1e-4  # a pair within this relative distance of a decision threshold is marginal (render_grad_ref)
+
+
+def walk(rec, sel, u, v):
+    """_blend's walk over the Gaussians sel at the pixels (u, v) (flat float arrays), vectorised over the list: the
+    (len(sel), pixels) arrays of power and a, then cumprod along the list.  A pair that is not used multiplies T by
+    exactly 1, so cumprod makes _blend's products in _blend's order and every value below has _blend's bits.  A dict:
+      take      (L, pixels) bool, the used pairs
+      w         (L, pixels) T a of the used pairs, 0 elsewhere
+      T         (pixels) the transmittance left
+      stopped   (pixels) bool: the pixel reached the stop
+      last      (pixels) the list position of the last used pair (-1: none)
+      clamped   the number of used pairs whose alpha was clamped at 0.99
+      marginal  (pixels) the number of considered pairs within a relative BAND of a decision threshold (the rules of
+                render_grad_ref._walk), which a float32 blend might decide the other way"""
+    u, v = np.ascontiguousarray(u, dtype=np.float64).ravel(), np.ascontiguousarray(v, dtype=np.float64).ravel()
+    sel = np.asarray(sel, dtype=np.int64)
+    L, P = sel.size, u.size
+    if L == 0:
+        return {"take": np.zeros((0, P), dtype=bool), "w": np.zeros((0, P)), "T": np.ones(P),
+                "stopped": np.zeros(P, dtype=bool), "last": np.full(P, -1, dtype=np.int64), "clamped": 0,
+                "marginal": np.zeros(P, dtype=np.int64)}
+    mean = rec["mean"][sel].astype(np.float64)
+    conic = rec["conic"][sel].astype(np.float64)
+    op = rec["opacity"][sel].astype(np.float64)[:, None]
+    dx, dy = u[None, :] - mean[:, 0:1], v[None, :] - mean[:, 1:2]
+    A, B, Cc = conic[:, 0:1], conic[:, 1:2], conic[:, 2:3]
+    power = -0.5 * (A * dx * dx + Cc * dy * dy) - B * dx * dy
+    raw = op * np.exp(np.minimum(power, 0.0))
+    a = np.minimum(0.99, raw)
+    neg = power <= 0
+    cand = neg & (a >= 1.0 / 255.0)
+    through = np.cumprod(np.where(cand, 1.0 - a, 1.0), axis=0)  # T after each pair, were there no stop
+    before = np.concatenate([np.ones((1, P)), through[:-1]], axis=0)
+    stops = cand & (through < 1e-4)
+    stopped = stops.any(axis=0)
+    at = np.where(stopped, np.argmax(stops, axis=0), L)  # the list position of the pair that stops the pixel
+    k = np.arange(L)[:, None]
+    live = k <= at[None, :]  # still walking when the pair is considered
+    take = cand & (k < at[None, :])
+    m = live & (np.abs(power) < 1e-6)
+    m |= live & neg & (np.abs(255.0 * a - 1.0) < BAND)
+    m |= live & neg & (np.abs(raw / 0.99 - 1.0) < BAND)
+    m |= live & cand & (np.abs(through / 1e-4 - 1.0) < BAND)
+    T = np.where(stopped, before[np.minimum(at, L - 1), np.arange(P)], through[-1])  # a stop leaves T as it was
+    last = np.where(take.any(axis=0), L - 1 - np.argmax(take[::-1], axis=0), -1)
+    return {"take": take, "w": np.where(take, before * a, 0.0), "T": T, "stopped": stopped, "last": last,
+            "clamped": int((take & (raw > 0.99)).sum()), "marginal": m.sum(axis=0)}
+
+
+def _colours(rec, order, wk, shape):
+    """(rgb, T) of _blend from walk()'s result, bit for bit.  The colours add up along the list with cumsum, one term
+    after the other as _blend adds them; an unused pair adds exactly 0."""
+    C = np.zeros((wk["T"].size, 3))
+    if len(order):
+        rgb = rec["rgb"][np.asarray(order, dtype=np.int64)].astype(np.float64)
+        for c in range(3):
+            C[:, c] = np.cumsum(wk["w"] * rgb[:, c:c + 1], axis=0)[-1]
+    return C.reshape(shape + (3,)), wk["T"].reshape(shape)
+
+
+def _blend_vec(rec, order, u, v, cam=None):
+    """_blend through walk(): the same (rgb, T), bit for bit."""
+    return _colours(rec, order, walk(rec, order, u, v), np.shape(u))
+
+
+def tile_lists(rec, cam, tile_list=None):
+    """{tile id (ty * tiles_x + tx): the Gaussians of its list in blend order} for the tiles of tile_list (None: the
+    touched tiles, those with a list).  From the entries themselves (every visible Gaussian's rectangle), so the cost
+    does not grow with the tile count."""
+    tw, th = tiles(cam)
+    order = depth_order(rec)
+    r = rec["rect"][order]
+    nx, ny = r[:, 2] - r[:, 0], r[:, 3] - r[:, 1]
+    cnt = nx * ny
+    g = np.repeat(np.arange(order.size), cnt)              # position in the depth order, ascending
+    j = np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+    key = (r[g, 1] + j // nx[g]) * tw + r[g, 0] + j % nx[g]
+    by_tile = np.argsort(key, kind="stable")               # stable: the depth order survives within a tile
+    key, g = key[by_tile], order[g[by_tile]]
+    ids, start = np.unique(key, return_index=True)
+    end = np.append(start[1:], key.size)
+    lists = {int(t): g[s:e] for t, s, e in zip(ids, start, end)}
+    if tile_list is None:
+        return lists
+    return {int(t): lists.get(int(t), np.zeros(0, dtype=np.int64)) for t in tile_list}
+
+
+def tile_pixels(cam, t):
+    """(vv, uu): the pixel rows and columns of tile t, as render()'s mgrid."""
+    tw, _ = tiles(cam)
+    ty, tx = divmod(int(t), tw)
+    return np.mgrid[ty * TILE:min(cam["height"], ty * TILE + TILE), tx * TILE:min(cam["width"], tx * TILE + TILE)]
+
+
+def render_tiles(rec, cam, tile_list, blend=None, marginal=None):
+    """render() restricted to the tiles of tile_list: {tile id: (rows, columns, 4) float64}, each equal to render()'s
+    image over that tile's pixels.  A view of millions of pixels costs only the tiles asked for.  blend: _blend, to
+    walk as render() does (default: walk()).  marginal: a dict that receives {tile id: (rows, columns) int}, each
+    pixel's number of marginal pairs."""
+    out = {}
+    bg = cam["background"]
+    for t, sel in tile_lists(rec, cam, tile_list).items():
+        vv, uu = tile_pixels(cam, t)
+        if blend is None:
+            wk = walk(rec, sel, uu, vv)
+            C, T = _colours(rec, sel, wk, uu.shape)
+            if marginal is not None:
+                marginal[t] = wk["marginal"].reshape(uu.shape)
+        else:
+            C, T = blend(rec, sel, uu.astype(np.float64), vv.astype(np.float64), cam)
+        out[t] = np.concatenate([C + T[..., None] * bg, (1.0 - T)[..., None]], axis=2)
+    return out
 
 
 def render(cloud, sh_degree, cam, antialiased=False, rec=None):

@@ -81,6 +81,73 @@ def test_tiled_equals_bruteforce():
         assert np.allclose(t, b, rtol=0, atol=1e-12)
 
 
+def deep_scene():
+    """The first gradient scene of test_gpu_render_grad (300 Gaussians and 4 clamp hits at 40 x 36, degree 3 used to
+    degree 2): lists of up to about 290 entries, a few hundred pixels that stop, alphas that clamp."""
+    import render_grad_ref as GR
+    from test_gpu_render import view_of
+    c = GR.scene(1, 3, clamp_hits=4)
+    m, fx, fy, cx, cy = view_of(c["positions"], width=40, height=36)
+    return c, RR.camera(m, fx, fy, cx, cy, 40, 36, 0.2, (0.1, 0.2, 0.3), 2)
+
+
+@pytest.mark.parametrize("aa", [False, True])
+def test_vectorised_blend_equals_the_loop_bit_for_bit(aa):
+    """render_ref.walk makes _blend's products and sums in _blend's order: render() through _blend_vec and
+    render_tiles() give the bits of render() through _blend, and walk's decisions are render_grad_ref._walk's."""
+    import render_grad_ref as GR
+    c, cam = deep_scene()
+    rec = RR.preprocess(c, 3, cam, aa)
+    want = RR.render(c, 3, cam, aa, rec=rec)
+    tw, th = RR.tiles(cam)
+    lists = RR.tile_lists(rec, cam)
+    assert max(len(s) for s in lists.values()) >= 100 and sum(len(s) for s in lists.values()) == RR.entry_count(rec)
+    some = [0, 4, tw * th - 1, tw + 2]
+    got = RR.render_tiles(rec, cam, some)
+    loop = RR.render_tiles(rec, cam, some, blend=RR._blend)
+    assert sorted(got) == sorted(some)
+    for t in some:
+        vv, uu = RR.tile_pixels(cam, t)
+        assert np.array_equal(got[t], want[vv, uu]) and np.array_equal(loop[t], want[vv, uu]), t
+    everything = RR.render_tiles(rec, cam, range(tw * th))
+    img = np.zeros_like(want)
+    for t, px in everything.items():
+        vv, uu = RR.tile_pixels(cam, t)
+        img[vv, uu] = px
+    assert np.array_equal(img, want)
+    # the decisions: used pairs, marginal pairs per pixel, stopped pixels, clamped alphas
+    dec = GR.decisions(c, 3, cam, aa)
+    vec = GR.decisions(c, 3, cam, aa, vectorised=True)
+    assert dec["stopped"] >= 190 and (aa or dec["clamped"] >= 1) and dec["used"] >= 18000
+    for k in ("entries", "used", "stopped", "clamped", "marginal"):
+        assert dec[k] == vec[k], k
+    assert np.array_equal(dec["marginal_mask"], vec["marginal_mask"])
+    for a, b in zip(dec["tiles"], vec["tiles"]):
+        assert np.array_equal(a["sel"], b["sel"]) and np.array_equal(a["take"], b["take"])
+        assert np.array_equal(a["marginal"], b["marginal"])
+
+
+def test_marginal_mask_sums_to_the_marginal_count():
+    """decisions() keeps the marginal pairs per pixel: they sum to its count, and the mask marks their pixels.  The
+    scene is made to have some: Gaussians whose peak alpha is 1/255 to within 1e-5 relative, each on a pixel centre."""
+    import render_grad_ref as GR
+    cam = cam_at_origin()
+    alpha = float(np.log((1.0 / 255.0) / (1.0 - 1.0 / 255.0)))  # opacity 1/255
+    px = [(10, 7), (40, 30), (41, 30)]
+    c = cat(one([0, 0, 6], 0.0, 2.0, colour_of([0.2, 0.6, 0.4])),
+            *[one([(u - 32) * 5 / 50.0, (v - 24) * 5 / 50.0, 5], -1.0, alpha, colour_of([0.9, 0.1, 0.3])) for u, v in px])
+    for vectorised in (False, True):
+        dec = GR.decisions(c, 0, cam, vectorised=vectorised)
+        per_pixel = np.zeros((cam["height"], cam["width"]), dtype=np.int64)
+        for t in dec["tiles"]:
+            per_pixel[t["v"], t["u"]] = t["marginal"]
+        assert dec["marginal"] == per_pixel.sum() >= len(px)
+        assert np.array_equal(dec["marginal_mask"], per_pixel > 0)
+        for u, v in px:
+            assert dec["marginal_mask"][v, u], (u, v)
+        assert dec["marginal_mask"].sum() < 20
+
+
 def test_look_at_projects_target_to_the_principal_point():
     import spz_amd.spz as spz
     eye, target, up = np.array([1.0, 2.0, -3.0]), np.array([0.5, -1.0, 4.0]), np.array([0.0, 0.0, 1.0])

@@ -43,16 +43,30 @@ def view_gradient(cloud_np, sh_degree, cam, dec, G, antialiased=False, dtype=tor
     return {"view": pack(tc["R"].grad, tc["t"].grad), "records": rg, "image": img.detach().to(torch.float64).numpy()}
 
 
-def chain(cloud_np, sh_degree, cam, dec, record_grads, antialiased=False, dtype=torch.float64):
+def chain(cloud_np, sh_degree, cam, dec, record_grads, antialiased=False, dtype=torch.float64, forward_mode=False):
     """The chain from given record gradients (n, 9) to the camera alone: (n, 3, 4) float64, each Gaussian's 12
-    contributions (zero for the invisible ones).  Their sum over n is the view gradient for those record gradients."""
+    contributions (zero for the invisible ones).  Their sum over n is the view gradient for those record gradients.
+    forward_mode: the same derivatives by 12 forward-mode passes, one per camera entry over all the Gaussians at once,
+    where one backward pass per Gaussian (n of them, each through all n rows) would take too long."""
     cloud = GR.as_tensors(cloud_np, dtype, requires_grad=False)
-    tc = torch_camera(cam, dtype)
     idx = np.nonzero(dec["visible"])[0]
-    rec9 = GR.records(cloud, sh_degree, tc, idx, antialiased)
     w = torch.as_tensor(np.asarray(record_grads, dtype=np.float64)[idx]).to(dtype)
-    per = (rec9 * w).sum(dim=1)
     out = np.zeros((dec["visible"].size, 3, 4))
+    if forward_mode:
+        import torch.autograd.forward_ad as fwd
+        base = torch_camera(cam, dtype, requires_grad=False)
+        for a in range(3):
+            for b in range(4):
+                dR, dt = torch.zeros(3, 3, dtype=dtype), torch.zeros(3, dtype=dtype)
+                (dR[a] if b < 3 else dt)[b if b < 3 else a] = 1.0
+                with fwd.dual_level():
+                    tc = dict(base, R=fwd.make_dual(base["R"], dR), t=fwd.make_dual(base["t"], dt))
+                    tangent = fwd.unpack_dual(GR.records(cloud, sh_degree, tc, idx, antialiased)).tangent
+                    out[idx, a, b] = (tangent * w).sum(dim=1).to(torch.float64).numpy()
+        return out
+    tc = torch_camera(cam, dtype)
+    rec9 = GR.records(cloud, sh_degree, tc, idx, antialiased)
+    per = (rec9 * w).sum(dim=1)
     for k, i in enumerate(idx):
         gR, gt = torch.autograd.grad(per[k], (tc["R"], tc["t"]), retain_graph=True)
         out[i] = pack(gR, gt)
