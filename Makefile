@@ -1,10 +1,10 @@
 # Top-level build: everything is built IN-TREE (the .so files travel to the GPU box with
 # gpurun; they are git-ignored).  `python -c "import __graft_entry__ as g; g.build()"` runs this.
 #
-#   spz_amd/lib/libspz_amd.so    HIP kernels (spz_kernels.hip, spz_ply_kernels.hip, spz_median.hip, spz_filter.hip, spz_transform.hip, spz_merge.hip, spz_sort.hip, spz_decimate.hip, spz_tile.hip, spz_clean.hip, spz_align.hip, spz_render.hip, spz_render_backward.hip, spz_render_view_backward.hip, spz_locate.hip, spz_mesh.hip, spz_prune.hip, spz_metrics.hip, spz_refine.hip, spz_densify.hip, spz_photo.hip, spz_depth_loss.hip, spz_seed.hip) + C ABI (spz_abi.hip, spz_hostpath.hip, spz_exchange.hip)   (hipcc, gfx950)
+#   spz_amd/lib/libspz_amd.so    HIP kernels (spz_kernels.hip, spz_ply_kernels.hip, spz_median.hip, spz_filter.hip, spz_transform.hip, spz_merge.hip, spz_sort.hip, spz_decimate.hip, spz_tile.hip, spz_clean.hip, spz_align.hip, spz_render.hip, spz_render_backward.hip, spz_render_view_backward.hip, spz_locate.hip, spz_mesh.hip, spz_prune.hip, spz_metrics.hip, spz_refine.hip, spz_densify.hip, spz_photo.hip, spz_depth_loss.hip, spz_seed.hip, spz_plane.hip) + C ABI (spz_abi.hip, spz_hostpath.hip, spz_exchange.hip)   (hipcc, gfx950)
 #   spz_amd/lib/libspz_host.so   C++ drop-in layer spz::saveSpz/loadSpz + gzip (g++, zlib)
 #   spz_amd/spz*.so              Python module `spz` (pybind11) over the C++ layer
-#   spz_amd/bin/{ply_to_spz,spz_to_ply,spz_info}   the reference's three CLI tools over the C++ layer (+ spz_filter, spz_transform, spz_merge, spz_sort, spz_decimate, spz_clean, spz_render, spz_prune, spz_compare, spz_tile, spz_align, spz_refine, spz_fit, spz_seed, spz_locate, spz_mesh)
+#   spz_amd/bin/{ply_to_spz,spz_to_ply,spz_info}   the reference's three CLI tools over the C++ layer (+ spz_filter, spz_transform, spz_merge, spz_sort, spz_decimate, spz_clean, spz_render, spz_prune, spz_compare, spz_tile, spz_align, spz_refine, spz_fit, spz_seed, spz_locate, spz_mesh, spz_level)
 #   oracle/liboracle.so, oracle/_ref/libspz_ref.so   CPU checkers (tests only)
 
 ROOT    := $(dir $(abspath $(lastword $(MAKEFILE_LIST))))
@@ -31,7 +31,7 @@ host:   $(LIBDIR)/libspz_host.so
 python: $(ROOT)spz_amd/spz$(PYEXT)
 cli:    $(ROOT)spz_amd/bin/spz_tool $(ROOT)spz_amd/bin/dropin_user_test $(ROOT)spz_amd/bin/host_bench
 
-DEVICE_SRCS := $(CSRC)/spz_kernels.hip $(CSRC)/spz_abi.hip $(CSRC)/spz_hostpath.hip $(CSRC)/spz_ply_kernels.hip $(CSRC)/spz_median.hip $(CSRC)/spz_exchange.hip $(CSRC)/spz_lz77.hip $(CSRC)/spz_inflate_dev.hip $(CSRC)/spz_place.hip $(CSRC)/spz_filter.hip $(CSRC)/spz_transform.hip $(CSRC)/spz_merge.hip $(CSRC)/spz_sort.hip $(CSRC)/spz_decimate.hip $(CSRC)/spz_tile.hip $(CSRC)/spz_clean.hip $(CSRC)/spz_align.hip $(CSRC)/spz_render.hip $(CSRC)/spz_render_backward.hip $(CSRC)/spz_render_view_backward.hip $(CSRC)/spz_locate.hip $(CSRC)/spz_mesh.hip $(CSRC)/spz_prune.hip $(CSRC)/spz_metrics.hip $(CSRC)/spz_refine.hip $(CSRC)/spz_densify.hip $(CSRC)/spz_photo.hip $(CSRC)/spz_depth_loss.hip $(CSRC)/spz_seed.hip
+DEVICE_SRCS := $(CSRC)/spz_kernels.hip $(CSRC)/spz_abi.hip $(CSRC)/spz_hostpath.hip $(CSRC)/spz_ply_kernels.hip $(CSRC)/spz_median.hip $(CSRC)/spz_exchange.hip $(CSRC)/spz_lz77.hip $(CSRC)/spz_inflate_dev.hip $(CSRC)/spz_place.hip $(CSRC)/spz_filter.hip $(CSRC)/spz_transform.hip $(CSRC)/spz_merge.hip $(CSRC)/spz_sort.hip $(CSRC)/spz_decimate.hip $(CSRC)/spz_tile.hip $(CSRC)/spz_clean.hip $(CSRC)/spz_align.hip $(CSRC)/spz_render.hip $(CSRC)/spz_render_backward.hip $(CSRC)/spz_render_view_backward.hip $(CSRC)/spz_locate.hip $(CSRC)/spz_mesh.hip $(CSRC)/spz_prune.hip $(CSRC)/spz_metrics.hip $(CSRC)/spz_refine.hip $(CSRC)/spz_densify.hip $(CSRC)/spz_photo.hip $(CSRC)/spz_depth_loss.hip $(CSRC)/spz_seed.hip $(CSRC)/spz_plane.hip
 $(LIBDIR)/libspz_amd.so: $(DEVICE_SRCS) $(CSRC)/spz_densify_internal.hpp $(CSRC)/spz_photo_internal.hpp $(CSRC)/spz_image_tile.hpp $(CSRC)/spz_common.hpp $(CSRC)/spz_kernel_params.hpp $(CSRC)/spz_quant.hpp $(CSRC)/spz_sort_internal.hpp $(CSRC)/spz_render_internal.hpp $(CSRC)/spz_view_pass.hpp $(CSRC)/spz_view_backward_core.hpp $(CSRC)/spz_morton_walk.hpp $(CSRC)/spz_block_ops.hpp $(CSRC)/spz_xf.hpp $(CSRC)/spz_lz77_core.hpp $(CSRC)/spz_huff_core.hpp $(CSRC)/spz_inflate_core.hpp $(INC)/spz_amd.h
 	mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(DEVICE_SRCS) -ldl
@@ -48,7 +48,7 @@ $(ROOT)spz_amd/bin/spz_tool: $(CSRC)/spz_cli.cpp $(INC)/spz_amd_host.hpp $(LIBDI
 	mkdir -p $(ROOT)spz_amd/bin
 	$(CXX) $(CXXFLAGS) -o $@ $(CSRC)/spz_cli.cpp -L$(LIBDIR) -lspz_host -lspz_amd \
 	    -Wl,-rpath,'$$ORIGIN/../lib' -Wl,-rpath,/opt/rocm/lib
-	for t in ply_to_spz spz_to_ply spz_info spz_filter spz_transform spz_merge spz_sort spz_decimate spz_clean spz_render spz_prune spz_compare spz_tile spz_align spz_refine spz_fit spz_seed spz_locate spz_mesh; do ln -sf spz_tool $(ROOT)spz_amd/bin/$$t; done
+	for t in ply_to_spz spz_to_ply spz_info spz_filter spz_transform spz_merge spz_sort spz_decimate spz_clean spz_render spz_prune spz_compare spz_tile spz_align spz_refine spz_fit spz_seed spz_locate spz_mesh spz_level; do ln -sf spz_tool $(ROOT)spz_amd/bin/$$t; done
 
 # A user program written against the reference's C++ API, built against the compat headers
 # (tests/cpp/dropin_user.cpp; its expected output comes from the same source built against the reference).

@@ -679,6 +679,139 @@ int spz_amd_align_host(const spz_amd_align_cloud *source, const spz_amd_align_cl
                        const spz_amd_align_options *options, int device, spz_amd_align_result *result,
                        spz_amd_align_history *history, uint32_t capacity, float *h_ms);
 
+/* ---- plane: the dominant plane of a packed stream, or up to K of them, by MSAC over seeded hypotheses with an exact
+ *      least-squares refinement, and the placement that levels the scene on it (spz_plane.hip; DESIGN §8 "Level").  The
+ *      reference has no counterpart.  Everything after the hypotheses' normals is integer arithmetic on the stored 24-bit
+ *      positions, so a restatement in Python integers agrees count for count.  v2 or v3 (version 1, float16 positions:
+ *      SPZ_AMD_ERR_UNSUPPORTED), at most SPZ_AMD_REFERENCE_MAX_POINTS (SPZ_AMD_ERR_TOO_MANY_POINTS).  All geometry is in
+ *      the stored RUB frame; plane_host conjugates the options in and the results out with the axis flips of
+ *      spz_amd_transform_params.
+ *
+ *      1. Points.  P_i = the sign-extended stored integers (fractionalBits f).  Point i takes part iff i % stride == 0
+ *         and labels[i] == 0 (labels: uint8 per point, device memory; NULL: all zero).  plane_prepare_device compacts the
+ *         taking-part points, in input order, into the workspace (int32 X, Y, Z and the input index), and blocks until
+ *         their count m is in *h_count, as select_device does.
+ *      2. Plane (a, b, c, e): int32 a, b, c in [-2^16, 2^16], int64 e.  The signed distance of P is the exact integer
+ *         d = a X + b Y + c Z - e, |d| < 2^43.  Threshold T = floor(tau 2^(f+16)) for tau in world units
+ *         (plane_threshold, host only; tau not finite, < 0, or T > 2^36: SPZ_AMD_ERR_INVALID_ARG).  P is an inlier iff
+ *         |d| <= T.  A plane with a = b = c = 0 is invalid.
+ *      3. Score (plane_score_device): for each of H planes (device memory) over the m prepared points, K = the number of
+ *         inliers, S = sum |d| over them (< 2^60), cost = S + T (m - K), the MSAC cost.  An invalid plane: K = S = 0,
+ *         cost = UINT64_MAX.  Integers: a run repeats its bits however it is summed.
+ *      4. Hypotheses (plane_hypotheses; host only, no GPU, f64).  idx(r, h, k) = mix64(seed + (r << 48) + 3 h + k) mod m
+ *         (uint64 arithmetic, wrapping) for round r, hypothesis h, k = 0..2, with splitmix64's finaliser
+ *             mix64(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31.
+ *         h_indices (3 H, may be NULL) receives them; with h_points (3 H x 3 int32: prepared point idx(r, h, k) at row
+ *         3 h + k, what plane_gather_device returns for those indices) h_planes receives the planes:
+ *         N = (P_1 - P_0) x (P_2 - P_0) in exact int64 (components below 2^52); two equal indices or N = 0: invalid
+ *         (a = b = c = e = 0).  Else each component to f64, L = sqrt((Nx Nx + Ny Ny) + Nz Nz), every product and sum
+ *         rounded on its own, (a, b, c) = rint(65536 N / L) (the product first), e = a X_0 + b Y_0 + c Z_0.  With a
+ *         constraint (axis: 3 doubles, stored frame, nonzero, normalised by sqrt((x x + y y) + z z); NULL: none) a plane
+ *         with |(a u_x + b u_y) + c u_z| < 65536 cos(max_tilt pi / 180) is invalid.
+ *      5. Moments (plane_moments_device; one plane by value, one lane per prepared point): K and S as above, the side
+ *         counts above (d > T) and below (d < -T), and over the inliers sum P (3 int64) and sum XX, XY, XZ, YY, YZ, ZZ as
+ *         exact 128-bit integers (hi 2^64 + lo, two's complement).  int64 sums per tile of 2048 points (2048 2^46 <
+ *         2^63), joined with carries: exact, so a run repeats its bits.
+ *      6. Solve (plane_solve; host only, no GPU): M = K sum P P^T - sum P sum P^T in exact 128-bit integers (< 2^96),
+ *         each entry rounded once to f64; a cyclic Jacobi eigen-solve of the symmetric 3 x 3 (sweeps over (0,1), (0,2),
+ *         (1,2) until no rotation is left; a pair is rotated unless |m_pq| <= 1e-17 sqrt(|m_pp|) sqrt(|m_qq|));
+ *         n = the unit eigenvector of the smallest eigenvalue, (a, b, c) = rint(65536 n),
+ *         e = (a sum X + b sum Y + c sum Z) / K rounded to the nearest integer, ties to even, in exact integers.
+ *         *degenerate = 1 (and *out untouched) when K < 3 or the middle eigenvalue is <= 1e-12 of the largest (a line or
+ *         a point), the rule and constant of align_solve.  normal (3 doubles) and eigenvalues (3 doubles, descending;
+ *         both may be NULL) receive n and the eigenvalues of M before the rounding.
+ *      7. The run (plane_host; blocking, on `device`, on a stream of its own; the stream already in device memory).  For
+ *         round r = 0 .. max_planes - 1: prepare (stop if m < 3); the H hypotheses, scored; the best is the smallest cost,
+ *         ties to the smallest h (stop if none is valid); up to `refine` times moments of the current plane, solve, score
+ *         of the solved plane, accepted only when its cost is strictly smaller (the first rejected or degenerate solve
+ *         ends the refinement); stop if the final K < min_inliers; orientation: with has_up_hint negate (a, b, c, e) if
+ *         n . hint < 0, else negate if below > above (the scene lies on the positive side of its floor), and on
+ *         above == below choose b >= 0 (stored +Y is up); plane_mark_device writes r + 1 into labels at the input indices
+ *         of the inliers.  Per plane the result holds the integers, K, S, m, above, below, the winning h, the accepted
+ *         refinements, fitness = K / m, mean_distance = S / K 2^-(f+16), the unit normal n = (a, b, c) / |(a, b, c)| and
+ *         offset d = e / |(a, b, c)| 2^-f (n . p = d, world units) with n stated in coord, and the levelling placement:
+ *         the shortest arc that takes n to the up axis of coord (+-Y by its U / D letter: stored +Y), q = (-n_z, 0, n_x,
+ *         w) normalised with w = 1 + n_y, or (n_x^2 + n_z^2) / (1 - n_y) for n_y < 0, and a half turn about stored X
+ *         when w < 1e-12 (n opposite to up); translation -d up (0 under no_translate); scale 1; stated in coord as
+ *         (x, y, z, w), w >= 0, ready for spz_amd_transform_params.  h_labels (may be NULL): num_points bytes, 0 or the
+ *         1-based plane of each point.  *h_found: the number of planes written (at most `capacity`, which must be >=
+ *         max_planes).  h_ms (may be NULL): [0] wall-clock milliseconds of prepare + gather, [1] of the scoring, [2] of
+ *         moments, solves and marks.
+ *      plane_check (host only, no GPU): hypotheses 1..65536; refine 0..16; max_planes 1..255; stride >= 1; tau finite
+ *      and >= 0; a finite, nonzero axis (when has_axis) and hint (when has_up_hint); max_tilt in [0, 90]; coord 0..8.
+ *      plane_default_options: 4096 hypotheses, refine 3, one plane, stride 1, seed 0, no constraint, min_inliers 0,
+ *      tau = NaN (it has no default and must be given).
+ *
+ *      Device forms (enqueue on hip_stream; only prepare blocks; d_workspace: plane_workspace_bytes(num_points) bytes of
+ *      device memory, any alignment, the same for every call on one stream).  plane_gather_device: d_out[k] (3 int32) =
+ *      prepared point d_indices[k], k < count (an index >= m is clamped to m - 1).  d_scores: 3 H uint64 (K, S, cost per
+ *      plane).  d_moments: one spz_amd_plane_moments.  plane_mark_device: d_labels[index] = value for the inliers.
+ *      plane_placement (host only, no GPU): the plane, normal, offset, rotation, translation and scale of *out for an
+ *      oriented plane at fractional_bits, as plane_host reports them; the other members are untouched.
+ *      plane_sides_host (blocking, on `device`, the stream in device memory): h_side[i] = 0 (|d| <= T), 1 (d > T) or 2
+ *      (d < -T) for every point i of the stream, whatever stride and labels a run used: the masks of a selection.
+ *      A plane whose a, b, c lie outside [-2^16, 2^16] or whose |e| > 2^42 counts as invalid wherever a = b = c = 0 does
+ *      (the forms that take one plane by value return SPZ_AMD_ERR_INVALID_ARG for an invalid one). */
+typedef struct {
+  int32_t a, b, c, reserved;
+  int64_t e;
+} spz_amd_plane;
+typedef struct {
+  double threshold;              /* tau, world units */
+  uint32_t hypotheses, refine, max_planes, stride;
+  uint64_t seed;
+  uint64_t min_inliers;
+  int32_t has_axis;
+  double axis[3];                /* in coord */
+  double max_tilt;               /* degrees */
+  int32_t has_up_hint;
+  double up_hint[3];             /* in coord */
+  int32_t coord;
+  int32_t no_translate;
+} spz_amd_plane_options;
+typedef struct {
+  uint64_t count;                /* K */
+  uint64_t sum_abs;              /* S */
+  uint64_t above, below;
+  uint64_t points;               /* m */
+  int64_t sum_p[3];
+  uint64_t sum_pp_lo[6];         /* XX, XY, XZ, YY, YZ, ZZ */
+  int64_t sum_pp_hi[6];
+} spz_amd_plane_moments;
+typedef struct {
+  spz_amd_plane plane;           /* stored frame, oriented */
+  uint64_t inliers, sum_abs, points, above, below;
+  uint32_t best_hypothesis, refinements;
+  double fitness, mean_distance;
+  double normal[3], offset;      /* in coord, world units */
+  double rotation[4], translation[3], scale;   /* the levelling placement, in coord */
+} spz_amd_plane_result;
+int spz_amd_plane_default_options(spz_amd_plane_options *options);
+int spz_amd_plane_check(const spz_amd_plane_options *options);
+int spz_amd_plane_threshold(double tau, int fractional_bits, uint64_t *threshold);
+uint64_t spz_amd_plane_workspace_bytes(uint64_t num_points);
+int spz_amd_plane_prepare_device(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, uint32_t stride,
+                                 const uint8_t *d_labels, void *d_workspace, uint64_t *h_count, void *hip_stream);
+int spz_amd_plane_gather_device(const void *d_workspace, uint64_t num_points, uint64_t m, const uint32_t *d_indices,
+                                uint64_t count, int32_t *d_out, void *hip_stream);
+int spz_amd_plane_hypotheses(uint64_t seed, uint32_t round, uint32_t hypotheses, uint64_t m, const int32_t *h_points,
+                             const double *axis, double max_tilt, uint32_t *h_indices, spz_amd_plane *h_planes);
+int spz_amd_plane_score_device(void *d_workspace, uint64_t num_points, uint64_t m, const spz_amd_plane *d_planes,
+                               uint32_t hypotheses, uint64_t threshold, uint64_t *d_scores, void *hip_stream);
+int spz_amd_plane_moments_device(void *d_workspace, uint64_t num_points, uint64_t m, const spz_amd_plane *plane,
+                                 uint64_t threshold, spz_amd_plane_moments *d_moments, void *hip_stream);
+int spz_amd_plane_solve(const spz_amd_plane_moments *moments, spz_amd_plane *out, double *normal, double *eigenvalues,
+                        int *degenerate);
+int spz_amd_plane_mark_device(const void *d_workspace, uint64_t num_points, uint64_t m, const spz_amd_plane *plane,
+                              uint64_t threshold, uint8_t value, uint8_t *d_labels, void *hip_stream);
+int spz_amd_plane_placement(const spz_amd_plane *plane, int fractional_bits, int coord, int no_translate,
+                            spz_amd_plane_result *out);
+int spz_amd_plane_sides_host(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr, const spz_amd_plane *plane,
+                             uint64_t threshold, int device, uint8_t *h_side);
+int spz_amd_plane_host(const uint8_t *d_stream, size_t size, const spz_amd_header *hdr,
+                       const spz_amd_plane_options *options, int device, spz_amd_plane_result *results,
+                       uint32_t capacity, uint32_t *h_found, uint8_t *h_labels, float *h_ms);
+
 /* ---- render: a forward 3D Gaussian splat rasteriser (spz_render.hip; DESIGN §8 "Render").  The reference has no
  *      counterpart.  The image of one pinhole view, computed on the device with no display attached.
  *

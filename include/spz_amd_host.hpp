@@ -27,6 +27,7 @@
 #include <array>
 #include <cstdint>
 #include <iosfwd>
+#include <limits>
 #include <optional>
 #include <string>
 #include <vector>
@@ -434,6 +435,61 @@ bool alignSpz(const uint8_t *source, int32_t sourceSize, const uint8_t *target, 
               const AlignOptions &options, AlignResult *result);
 bool alignSpz(const std::string &sourceFilename, const std::string &targetFilename, const AlignOptions &options,
               AlignResult *result);
+// Level (DESIGN §8 "Level"): the dominant plane of a .spz, or up to `planes` of them, by MSAC over seeded hypotheses on
+// the stored integers with an exact least-squares refinement (include/spz_amd.h "plane" states the contract), and the
+// placement that levels the scene on the first plane.  detectPlanes: the member is inflated (loadSpzPackedDevice, or
+// the caller's packed device stream) and the run happens on the device (spz_amd_plane_host); it returns true with no
+// plane when none reaches minInliers.  levelSpz: detectPlanes, then with select == None the file placed by the first
+// plane's rotation and translation (transformSpz at fractionalBits), otherwise the chosen subset of the input without
+// requantising (filterSpz with a mask): Plane is |d| <= T of the first plane over every point, OffPlane the rest, Above
+// d > T, Below d < -T.  No plane found: levelSpz returns true with no plane, an empty *out, and writes no file.
+// threshold (world units) has no default.  The inlier floor is the larger of minInliers and ceil(minInlierFraction *
+// the points taking part in the first round).  axis, upHint and the results' normal, rotation and translation are stated
+// in `coord`.  Version 1 files are refused (SPZ_AMD_ERR_UNSUPPORTED).  false + one "[SPZ ERROR] levelSpz: …" line on a
+// bad argument, an input that does not load, or a device failure.  SPZ_AMD_LEVEL_TIMING=1 prints the stages' times.
+struct LevelOptions {
+  enum class Select { None, Plane, OffPlane, Above, Below };
+  double threshold = std::numeric_limits<double>::quiet_NaN();
+  uint32_t hypotheses = 4096;           // 1 ... 65536
+  uint64_t seed = 0;
+  uint32_t stride = 1;
+  uint32_t refine = 3;                  // 0 ... 16
+  uint32_t planes = 1;                  // 1 ... 255
+  uint64_t minInliers = 0;
+  double minInlierFraction = 0.0;       // 0 ... 1
+  std::optional<std::array<double, 3>> axis;
+  double maxTilt = 90.0;                // degrees, with axis
+  std::optional<std::array<double, 3>> upHint;
+  CoordinateSystem coord = CoordinateSystem::UNSPECIFIED;
+  bool noTranslate = false;
+  Select select = Select::None;         // levelSpz
+  int32_t fractionalBits = 12;          // of the levelled file's positions (levelSpz, select == None)
+};
+struct DetectedPlane {
+  std::array<int32_t, 3> normalInt = {0, 0, 0};   // (a, b, c), stored frame
+  int64_t offsetInt = 0;                           // e
+  uint64_t inliers = 0, sumAbs = 0, points = 0, above = 0, below = 0;
+  uint32_t bestHypothesis = 0, refinements = 0;
+  double fitness = 0.0, meanDistance = 0.0;
+  std::array<double, 3> normal = {0.0, 0.0, 0.0};
+  double offset = 0.0;
+  std::array<double, 4> rotation = {0.0, 0.0, 0.0, 1.0};
+  std::array<double, 3> translation = {0.0, 0.0, 0.0};
+};
+struct LevelResult {
+  std::vector<DetectedPlane> planes;
+  std::vector<uint8_t> labels;          // per input point: 0, or the 1-based plane it is an inlier of
+  uint64_t threshold = 0;               // T
+  double prepareMs = 0.0, scoreMs = 0.0, refineMs = 0.0;
+  int64_t kept = -1;                    // levelSpz with a selection: the points written
+};
+bool detectPlanes(const DevicePackedGaussians &packed, const LevelOptions &options, LevelResult *result);
+bool detectPlanes(const uint8_t *data, int32_t size, const LevelOptions &options, LevelResult *result);
+bool detectPlanes(const std::string &filename, const LevelOptions &options, LevelResult *result);
+bool levelSpz(const uint8_t *data, int32_t size, const LevelOptions &options, std::vector<uint8_t> *out,
+              LevelResult *result);
+bool levelSpz(const std::string &inputFilename, const std::string &outputFilename, const LevelOptions &options,
+              LevelResult *result);
 // Render (DESIGN §8 "Render"): the image of one pinhole view on the device (include/spz_amd.h "render" states the
 // contract).  worldToCamera: [R | t] row-major, OpenCV axes (x right, y down, z forward), in the `coord` frame: the file
 // is rendered as loadSpz(to = coord) returns it (renderCloud: the cloud as it is; coord is ignored).  *rgba: height x

@@ -80,6 +80,10 @@ EXPORTS = (
     "spz_amd_align_default_options", "spz_amd_align_check", "spz_amd_align_workspace_bytes",
     "spz_amd_align_prepare_device", "spz_amd_nearest_device", "spz_amd_align_step_device", "spz_amd_align_solve",
     "spz_amd_align_host",
+    "spz_amd_plane_default_options", "spz_amd_plane_check", "spz_amd_plane_threshold", "spz_amd_plane_workspace_bytes",
+    "spz_amd_plane_prepare_device", "spz_amd_plane_gather_device", "spz_amd_plane_hypotheses",
+    "spz_amd_plane_score_device", "spz_amd_plane_moments_device", "spz_amd_plane_solve", "spz_amd_plane_mark_device",
+    "spz_amd_plane_placement", "spz_amd_plane_sides_host", "spz_amd_plane_host",
     "spz_amd_render_check_params", "spz_amd_render_workspace_bytes", "spz_amd_render_prepare_packed_device",
     "spz_amd_render_prepare_cloud_device", "spz_amd_render_finish_device", "spz_amd_render_host",
     "spz_amd_render_cloud_host", "spz_amd_render_score_device", "spz_amd_prune_keep_count", "spz_amd_prune_open",
@@ -174,6 +178,36 @@ class AlignMoments(C.Structure):
     _fields_ = [("count", C.c_uint64), ("taking_part", C.c_uint64), ("candidates", C.c_uint64),
                 ("sum_d2_lo", C.c_uint64), ("sum_d2_hi", C.c_uint64), ("sum_a", C.c_double * 3),
                 ("sum_b", C.c_double * 3), ("sum_ab", C.c_double * 9), ("sum_aa", C.c_double), ("sum_bb", C.c_double)]
+
+
+class Plane(C.Structure):
+    """spz_amd_plane: d = a X + b Y + c Z - e on the stored integers (include/spz_amd.h "plane")."""
+    _fields_ = [("a", C.c_int32), ("b", C.c_int32), ("c", C.c_int32), ("reserved", C.c_int32), ("e", C.c_int64)]
+
+
+class PlaneOptions(C.Structure):
+    """spz_amd_plane_options; spz_amd_plane_default_options fills the defaults (threshold has none)."""
+    _fields_ = [("threshold", C.c_double), ("hypotheses", C.c_uint32), ("refine", C.c_uint32),
+                ("max_planes", C.c_uint32), ("stride", C.c_uint32), ("seed", C.c_uint64), ("min_inliers", C.c_uint64),
+                ("has_axis", C.c_int32), ("axis", C.c_double * 3), ("max_tilt", C.c_double),
+                ("has_up_hint", C.c_int32), ("up_hint", C.c_double * 3), ("coord", C.c_int32),
+                ("no_translate", C.c_int32)]
+
+
+class PlaneMoments(C.Structure):
+    """spz_amd_plane_moments: the exact sums of one plane over its inliers (sum_pp = hi 2^64 + lo, two's complement)."""
+    _fields_ = [("count", C.c_uint64), ("sum_abs", C.c_uint64), ("above", C.c_uint64), ("below", C.c_uint64),
+                ("points", C.c_uint64), ("sum_p", C.c_int64 * 3), ("sum_pp_lo", C.c_uint64 * 6),
+                ("sum_pp_hi", C.c_int64 * 6)]
+
+
+class PlaneResult(C.Structure):
+    """spz_amd_plane_result: one plane of a run with its levelling placement."""
+    _fields_ = [("plane", Plane), ("inliers", C.c_uint64), ("sum_abs", C.c_uint64), ("points", C.c_uint64),
+                ("above", C.c_uint64), ("below", C.c_uint64), ("best_hypothesis", C.c_uint32),
+                ("refinements", C.c_uint32), ("fitness", C.c_double), ("mean_distance", C.c_double),
+                ("normal", C.c_double * 3), ("offset", C.c_double), ("rotation", C.c_double * 4),
+                ("translation", C.c_double * 3), ("scale", C.c_double)]
 
 
 class AlignHistory(C.Structure):
@@ -639,6 +673,36 @@ def bind(L):
     L.spz_amd_align_host.restype = i32
     L.spz_amd_align_host.argtypes = [ac, ac, C.POINTER(AlignOptions), i32, C.POINTER(AlignResult),
                                      C.POINTER(AlignHistory), u32, C.POINTER(C.c_float)]
+    pp, dp = C.POINTER(Plane), C.POINTER(C.c_double)
+    L.spz_amd_plane_default_options.restype = i32
+    L.spz_amd_plane_default_options.argtypes = [C.POINTER(PlaneOptions)]
+    L.spz_amd_plane_check.restype = i32
+    L.spz_amd_plane_check.argtypes = [C.POINTER(PlaneOptions)]
+    L.spz_amd_plane_threshold.restype = i32
+    L.spz_amd_plane_threshold.argtypes = [C.c_double, i32, C.POINTER(u64)]
+    L.spz_amd_plane_workspace_bytes.restype = u64
+    L.spz_amd_plane_workspace_bytes.argtypes = [u64]
+    L.spz_amd_plane_prepare_device.restype = i32
+    L.spz_amd_plane_prepare_device.argtypes = [vp, C.c_size_t, C.POINTER(Header), u32, vp, vp, C.POINTER(u64), vp]
+    L.spz_amd_plane_gather_device.restype = i32
+    L.spz_amd_plane_gather_device.argtypes = [vp, u64, u64, vp, u64, vp, vp]
+    L.spz_amd_plane_hypotheses.restype = i32
+    L.spz_amd_plane_hypotheses.argtypes = [u64, u32, u32, u64, vp, dp, C.c_double, vp, pp]
+    L.spz_amd_plane_score_device.restype = i32
+    L.spz_amd_plane_score_device.argtypes = [vp, u64, u64, vp, u32, u64, vp, vp]
+    L.spz_amd_plane_moments_device.restype = i32
+    L.spz_amd_plane_moments_device.argtypes = [vp, u64, u64, pp, u64, vp, vp]
+    L.spz_amd_plane_solve.restype = i32
+    L.spz_amd_plane_solve.argtypes = [C.POINTER(PlaneMoments), pp, dp, dp, C.POINTER(i32)]
+    L.spz_amd_plane_mark_device.restype = i32
+    L.spz_amd_plane_mark_device.argtypes = [vp, u64, u64, pp, u64, C.c_uint8, vp, vp]
+    L.spz_amd_plane_placement.restype = i32
+    L.spz_amd_plane_placement.argtypes = [pp, i32, i32, i32, C.POINTER(PlaneResult)]
+    L.spz_amd_plane_sides_host.restype = i32
+    L.spz_amd_plane_sides_host.argtypes = [vp, C.c_size_t, C.POINTER(Header), pp, u64, i32, vp]
+    L.spz_amd_plane_host.restype = i32
+    L.spz_amd_plane_host.argtypes = [vp, C.c_size_t, C.POINTER(Header), C.POINTER(PlaneOptions), i32,
+                                     C.POINTER(PlaneResult), u32, C.POINTER(u32), vp, C.POINTER(C.c_float)]
     L.spz_amd_render_check_params.restype = i32
     L.spz_amd_render_check_params.argtypes = [C.POINTER(RenderParams)]
     L.spz_amd_render_workspace_bytes.restype = u64

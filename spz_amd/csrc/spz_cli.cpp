@@ -2,7 +2,8 @@
 // MI355X drop-in layer: ply_to_spz, spz_to_ply, spz_info; and spz_filter (spz::filterSpz),
 // spz_transform (spz::transformSpz), spz_merge (spz::mergeSpz), spz_sort (spz::sortSpz), spz_decimate
 // (spz::decimateSpz), spz_tile (spz::tileSpz), spz_clean (spz::cleanSpz), spz_render (spz::renderSpz), spz_prune
-// (spz::pruneSpz), spz_compare (spz::compareSpz), spz_align (spz::alignSpz), spz_refine (spz::refineSpz),
+// (spz::pruneSpz), spz_compare (spz::compareSpz), spz_align (spz::alignSpz), spz_level (spz::levelSpz),
+// spz_refine (spz::refineSpz),
 // spz_locate (spz::locateSpz) and spz_mesh (spz::meshSpz), which have no counterpart in the reference.  One binary,
 // dispatched on argv[0] (the Makefile installs it under the seventeen names) or on a first argument naming the tool.
 // spz_refine, spz_locate and spz_mesh exit 0 on success and 1 on a failure.
@@ -20,6 +21,7 @@
 #include <algorithm>
 #include <stdexcept>
 #include <array>
+#include <cerrno>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -973,6 +975,84 @@ int spzAlign(int argc, char **argv) {
   return 0;
 }
 
+const char *kLevelUsage =
+    "Usage: spz_level <in.spz> [out.spz] --threshold TAU [--hypotheses H] [--seed S] [--stride K] [--refine R] "
+    "[--planes K] [--min-inliers N|FRACTION] [--axis X Y Z --max-tilt DEG] [--up-hint X Y Z] "
+    "[--coord " SPZ_COORD_NAMES "] [--no-translate] [--select plane|off-plane|above|below] [--fractional-bits n]";
+
+// Prints each plane, then the first plane's placement in spz_transform's own spelling.  With out.spz: the levelled file,
+// or with --select that subset of the input.  Exit 2 when no plane reaches --min-inliers.
+int spzLevel(int argc, char **argv) {
+  Args a(argc, argv, kLevelUsage);
+  const bool hasOut = argc > 2 && argv[2][0] != '-';
+  if (!a.files(hasOut ? 2 : 1)) return a.usage();
+  spz::LevelOptions o;
+  while (a.next()) {
+    bool good = false;
+    if (a.is("--threshold")) good = a.real(&o.threshold) && !std::isnan(o.threshold);
+    else if (a.is("--hypotheses")) good = a.integer(&o.hypotheses, 1, 65536);
+    else if (a.is("--seed")) good = a.integer(&o.seed, 0, UINT64_MAX);
+    else if (a.is("--stride")) good = a.integer(&o.stride, 1, UINT32_MAX);
+    else if (a.is("--refine")) good = a.integer(&o.refine, 0, 16);
+    else if (a.is("--planes")) good = a.integer(&o.planes, 1, 255);
+    else if (a.is("--min-inliers")) {
+      std::string v;
+      good = a.text(&v) && !v.empty();
+      if (good && v.find_first_not_of("0123456789") == std::string::npos) {  // a count
+        char *end = nullptr;
+        errno = 0;
+        o.minInliers = std::strtoull(v.c_str(), &end, 10);
+        good = errno == 0;
+      } else if (good) {  // a fraction of the points taking part
+        char *end = nullptr;
+        o.minInlierFraction = std::strtod(v.c_str(), &end);
+        good = end != v.c_str() && *end == '\0' && o.minInlierFraction >= 0.0 && o.minInlierFraction <= 1.0;
+      }
+    } else if (a.is("--axis")) good = a.real(o.axis.emplace().data(), 3);
+    else if (a.is("--max-tilt")) good = a.real(&o.maxTilt);
+    else if (a.is("--up-hint")) good = a.real(o.upHint.emplace().data(), 3);
+    else if (a.is("--coord")) good = a.coord(&o.coord);
+    else if (a.is("--no-translate")) good = o.noTranslate = true;
+    else if (a.is("--fractional-bits")) good = a.integer(&o.fractionalBits, 0, 24);
+    else if (a.is("--select")) {
+      std::string v;
+      good = a.text(&v);
+      if (v == "plane") o.select = spz::LevelOptions::Select::Plane;
+      else if (v == "off-plane") o.select = spz::LevelOptions::Select::OffPlane;
+      else if (v == "above") o.select = spz::LevelOptions::Select::Above;
+      else if (v == "below") o.select = spz::LevelOptions::Select::Below;
+      else good = false;
+    }
+    if (!good) return a.usage();
+  }
+  if (!a.given("--threshold") || a.given("--max-tilt") != a.given("--axis") || (a.given("--select") && !hasOut)) {
+    return a.usage();
+  }
+  spz::LevelResult r;
+  const bool ok = hasOut ? spz::levelSpz(std::string(argv[1]), std::string(argv[2]), o, &r)
+                         : spz::detectPlanes(std::string(argv[1]), o, &r);
+  if (!ok) return 1;
+  for (size_t k = 0; k < r.planes.size(); ++k) {
+    const spz::DetectedPlane &p = r.planes[k];
+    std::printf("plane %zu normal %.17g %.17g %.17g offset %.17g inliers %llu of %llu fitness %.17g mean-distance %.17g "
+                "integers %d %d %d %lld\n", k + 1, p.normal[0], p.normal[1], p.normal[2], p.offset,
+                static_cast<unsigned long long>(p.inliers), static_cast<unsigned long long>(p.points), p.fitness,
+                p.meanDistance, p.normalInt[0], p.normalInt[1], p.normalInt[2], static_cast<long long>(p.offsetInt));
+  }
+  if (r.planes.empty()) {
+    std::fflush(stdout);
+    std::cerr << "spz_level: no plane reaches --min-inliers" << std::endl;
+    return 2;
+  }
+  const spz::DetectedPlane &f = r.planes[0];
+  std::printf("--rotate %.17g %.17g %.17g %.17g --translate %.17g %.17g %.17g --scale 1 --coord %s\n", f.rotation[0],
+              f.rotation[1], f.rotation[2], f.rotation[3], f.translation[0], f.translation[1], f.translation[2],
+              kCoordNames[static_cast<int>(o.coord)]);
+  if (r.kept >= 0) std::printf("kept %lld\n", static_cast<long long>(r.kept));
+  std::fflush(stdout);
+  return 0;
+}
+
 const char *kLocateUsage =
     "Usage: spz_locate <scene.spz> --views FILE --images a.pfm|a.ppm [b ...] [--out FILE] [--iterations N] "
     "[--lr-rotation R] [--lr-translation T] [--lambda L] [--levels K] [--coord " SPZ_COORD_NAMES "] "
@@ -1207,7 +1287,7 @@ const struct {
               {"spz_filter", spzFilter},    {"spz_transform", spzTransform},  {"spz_merge", spzMerge},
               {"spz_sort", spzSort},        {"spz_decimate", spzDecimate},    {"spz_clean", spzClean},
               {"spz_render", spzRender},    {"spz_mesh", spzMesh},            {"spz_prune", spzPrune},
-              {"spz_compare", spzCompare},  {"spz_tile", spzTile},            {"spz_align", spzAlign},
+              {"spz_compare", spzCompare},  {"spz_tile", spzTile},            {"spz_align", spzAlign},           {"spz_level", spzLevel},
               {"spz_refine", spzRefine},    {"spz_fit", spzFit},              {"spz_seed", spzSeed},
               {"spz_locate", spzLocate}};
 

@@ -3782,6 +3782,186 @@ bool alignSpz(const std::string &sourceFilename, const std::string &targetFilena
   return alignSpz(a.data(), static_cast<int32_t>(a.size()), b.data(), static_cast<int32_t>(b.size()), o, result);
 }
 
+// ---- level -------------------------------------------------------------------------------------------------------
+namespace {
+bool levelOptionsOk(const LevelOptions &o, spz_amd_plane_options *c) {
+  const char *who = "levelSpz";
+  spz_amd_plane_default_options(c);
+  c->threshold = o.threshold;
+  c->hypotheses = o.hypotheses;
+  c->refine = o.refine;
+  c->max_planes = o.planes;
+  c->stride = o.stride;
+  c->seed = o.seed;
+  c->min_inliers = o.minInliers;
+  c->has_axis = o.axis ? 1 : 0;
+  c->has_up_hint = o.upHint ? 1 : 0;
+  for (int k = 0; k < 3; ++k) {
+    c->axis[k] = o.axis ? (*o.axis)[k] : 0.0;
+    c->up_hint[k] = o.upHint ? (*o.upHint)[k] : 0.0;
+  }
+  c->max_tilt = o.maxTilt;
+  c->coord = static_cast<int32_t>(o.coord);
+  c->no_translate = o.noTranslate ? 1 : 0;
+  if (std::isnan(o.threshold)) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "a threshold (world units) is required");
+  if (!(o.minInlierFraction >= 0.0) || !(o.minInlierFraction <= 1.0)) {
+    return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "minInlierFraction %g is outside 0 ... 1", o.minInlierFraction);
+  }
+  if (o.fractionalBits < 0 || o.fractionalBits > 24) {
+    return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "fractionalBits %d is outside 0 ... 24", o.fractionalBits);
+  }
+  if (spz_amd_plane_check(c) == SPZ_AMD_OK) return true;
+  return opRejected(who, SPZ_AMD_ERR_INVALID_ARG,
+                    "bad options: threshold >= 0, hypotheses 1..65536, refine 0..16, planes 1..255, stride >= 1, a nonzero "
+                    "axis and upHint, maxTilt 0..90, coord valid, all finite");
+}
+}  // namespace
+
+bool detectPlanes(const DevicePackedGaussians &d, const LevelOptions &o, LevelResult *result) {
+  const char *who = "levelSpz";
+  g_last_status = SPZ_AMD_OK;
+  if (result == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no result");
+  *result = LevelResult{};
+  spz_amd_plane_options c;
+  if (!levelOptionsOk(o, &c)) return false;
+  if (!d.valid()) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "the packed stream is empty");
+  const spz_amd_header hdr = headerOf(d);
+  if (hdr.version == 1) {
+    return opRejected(who, SPZ_AMD_ERR_UNSUPPORTED, "a version 1 file has float16 positions (transformSpz with the identity writes a v3 copy)");
+  }
+  if (spz_amd_plane_threshold(o.threshold, static_cast<int>(hdr.fractional_bits), &result->threshold) != SPZ_AMD_OK) {
+    return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "the threshold %g is too large at %u fractional bits", o.threshold,
+                      static_cast<unsigned>(hdr.fractional_bits));
+  }
+  const uint64_t taking = (static_cast<uint64_t>(hdr.num_points) + o.stride - 1) / o.stride;
+  const uint64_t floorCount = static_cast<uint64_t>(std::ceil(o.minInlierFraction * static_cast<double>(taking)));
+  if (floorCount > c.min_inliers) c.min_inliers = floorCount;
+  Laps laps(who, "SPZ_AMD_LEVEL_TIMING");
+  std::vector<spz_amd_plane_result> found(c.max_planes);
+  result->labels.assign(hdr.num_points, 0);
+  uint32_t count = 0;
+  float ms[3] = {0.0f, 0.0f, 0.0f};
+  const int rc = spz_amd_plane_host(d.stream, d.streamBytes, &hdr, &c, d.device, found.data(), c.max_planes, &count,
+                                    result->labels.data(), ms);
+  if (deviceFailed(rc, who)) return false;
+  laps.stage("prepare", ms[0]);
+  laps.stage("score", ms[1]);
+  laps.stage("refine", ms[2]);
+  laps.lap("planes");
+  result->prepareMs = ms[0];
+  result->scoreMs = ms[1];
+  result->refineMs = ms[2];
+  for (uint32_t k = 0; k < count; ++k) {
+    const spz_amd_plane_result &r = found[k];
+    DetectedPlane p;
+    p.normalInt = {r.plane.a, r.plane.b, r.plane.c};
+    p.offsetInt = r.plane.e;
+    p.inliers = r.inliers;
+    p.sumAbs = r.sum_abs;
+    p.points = r.points;
+    p.above = r.above;
+    p.below = r.below;
+    p.bestHypothesis = r.best_hypothesis;
+    p.refinements = r.refinements;
+    p.fitness = r.fitness;
+    p.meanDistance = r.mean_distance;
+    p.offset = r.offset;
+    for (int a = 0; a < 3; ++a) {
+      p.normal[a] = r.normal[a];
+      p.translation[a] = r.translation[a];
+    }
+    for (int a = 0; a < 4; ++a) p.rotation[a] = r.rotation[a];
+    result->planes.push_back(p);
+  }
+  return true;
+}
+
+bool detectPlanes(const uint8_t *data, int32_t size, const LevelOptions &o, LevelResult *result) {
+  const char *who = "levelSpz";
+  g_last_status = SPZ_AMD_OK;
+  if (result == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no result");
+  *result = LevelResult{};
+  spz_amd_plane_options c;
+  if (!levelOptionsOk(o, &c)) return false;
+  DevicePackedGaussians d;
+  if (!loadInput(who, data, size, &d)) return false;
+  return detectPlanes(d, o, result);
+}
+
+bool detectPlanes(const std::string &filename, const LevelOptions &o, LevelResult *result) {
+  const char *who = "levelSpz";
+  g_last_status = SPZ_AMD_OK;
+  if (result == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no result");
+  *result = LevelResult{};
+  spz_amd_plane_options c;
+  if (!levelOptionsOk(o, &c)) return false;
+  std::vector<uint8_t> data;
+  if (!readInput(who, filename, &data)) return false;
+  return detectPlanes(data.data(), static_cast<int32_t>(data.size()), o, result);
+}
+
+bool levelSpz(const uint8_t *data, int32_t size, const LevelOptions &o, std::vector<uint8_t> *out, LevelResult *result) {
+  const char *who = "levelSpz";
+  g_last_status = SPZ_AMD_OK;
+  if (result == nullptr || out == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no result or no output vector");
+  *result = LevelResult{};
+  spz_amd_plane_options c;
+  if (!levelOptionsOk(o, &c)) return false;
+  DevicePackedGaussians d;
+  if (!loadInput(who, data, size, &d)) return false;
+  if (!detectPlanes(d, o, result)) return false;
+  out->clear();
+  if (result->planes.empty()) return true;  // no plane reaches the floor: no output
+  const DetectedPlane &first = result->planes[0];
+  if (o.select == LevelOptions::Select::None) {
+    d.release();
+    TransformOptions t;
+    t.rotation = first.rotation;
+    t.translation = first.translation;
+    t.coord = o.coord;
+    t.fractionalBits = o.fractionalBits;
+    return transformSpz(data, size, t, out);
+  }
+  const spz_amd_header hdr = headerOf(d);
+  const spz_amd_plane plane = {first.normalInt[0], first.normalInt[1], first.normalInt[2], 0, first.offsetInt};
+  std::vector<uint8_t> side(hdr.num_points);
+  const int rc = spz_amd_plane_sides_host(d.stream, d.streamBytes, &hdr, &plane, result->threshold, d.device, side.data());
+  if (deviceFailed(rc, who)) return false;
+  d.release();
+  FilterOptions f;
+  f.mask.emplace(side.size());
+  for (size_t i = 0; i < side.size(); ++i) {
+    bool keep = false;
+    switch (o.select) {
+      case LevelOptions::Select::Plane: keep = side[i] == 0; break;
+      case LevelOptions::Select::OffPlane: keep = side[i] != 0; break;
+      case LevelOptions::Select::Above: keep = side[i] == 1; break;
+      case LevelOptions::Select::Below: keep = side[i] == 2; break;
+      case LevelOptions::Select::None: break;
+    }
+    (*f.mask)[i] = keep ? 1 : 0;
+  }
+  int64_t kept = 0;
+  if (!filterSpz(data, size, f, out, &kept)) return false;
+  result->kept = kept;
+  return true;
+}
+
+bool levelSpz(const std::string &inputFilename, const std::string &outputFilename, const LevelOptions &o,
+              LevelResult *result) {
+  g_last_status = SPZ_AMD_OK;
+  if (result == nullptr) return opRejected("levelSpz", SPZ_AMD_ERR_INVALID_ARG, "no result");
+  *result = LevelResult{};
+  spz_amd_plane_options c;
+  if (!levelOptionsOk(o, &c)) return false;
+  const char *who = "levelSpz";
+  std::vector<uint8_t> data, file;
+  if (!readInput(who, inputFilename, &data)) return false;
+  if (!levelSpz(data.data(), static_cast<int32_t>(data.size()), o, &file, result)) return false;
+  if (result->planes.empty()) return true;  // nothing is written
+  return writeOutput(who, outputFilename, file);
+}
+
 bool compareImages(const float *a, int channelsA, const float *b, int channelsB, int width, int height,
                    ImageMetrics *metrics, std::vector<float> *ssimMap) {
   const char *who = "compareImages";

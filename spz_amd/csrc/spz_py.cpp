@@ -484,6 +484,42 @@ PYBIND11_MODULE(spz, m) {
         "Returns a dict: rotation, translation, scale (in `coord`, ready for transform_spz or a merge placement), "
         "fitness, inlier_rmse, inliers, iterations, converged, degenerate and history, a list of (fitness, "
         "inlier_rmse, inliers) per step.");
+  m.def("level_spz",
+        [](const py::object &input, const py::object &output, const py::object &threshold, const py::object &hypotheses,
+           const py::object &seed, const py::object &stride, const py::object &refine, const py::object &planes,
+           const py::object &min_inliers, const py::object &axis, const py::object &max_tilt, const py::object &up_hint,
+           spz::CoordinateSystem coord, bool no_translate, const py::object &select, const py::object &fractional_bits) {
+          const spz::LevelOptions o = levelOptions(threshold, hypotheses, seed, stride, refine, planes, min_inliers, axis,
+                                                   max_tilt, up_hint, coord, no_translate, select, fractional_bits);
+          if (output.is_none() && !select.is_none()) throw py::value_error("select needs an output file");
+          const Input in(input);
+          spz::LevelResult r;
+          bool ok;
+          if (output.is_none()) {
+            ok = callOn(in, [&](auto... file) { return spz::detectPlanes(file..., o, &r); });
+          } else {
+            if (in.bytes) throw py::value_error("with an output file the input must be a path");
+            const std::string out = py::str(output).cast<std::string>();
+            ok = unlocked([&] { return spz::levelSpz(in.path, out, o, &r); });
+          }
+          if (!ok) raiseFailure("level_spz", "", "", /*unsupportedRefused=*/true);
+          return levelDict(r);
+        },
+        py::arg("input"), py::arg("output") = py::none(), py::kw_only(), py::arg("threshold"),
+        py::arg("hypotheses") = 4096, py::arg("seed") = 0, py::arg("stride") = 1, py::arg("refine") = 3,
+        py::arg("planes") = 1, py::arg("min_inliers") = 0, py::arg("axis") = py::none(),
+        py::arg("max_tilt") = py::none(), py::arg("up_hint") = py::none(),
+        py::arg("coord") = spz::CoordinateSystem::UNSPECIFIED, py::arg("no_translate") = false,
+        py::arg("select") = py::none(), py::arg("fractional_bits") = 12,
+        "The dominant plane of a v2/v3 .spz (a path, or the file's bytes), or up to `planes` of them, by MSAC over seeded "
+        "hypotheses on the stored integers with an exact least-squares refinement on the device (spz::detectPlanes / "
+        "spz::levelSpz; the contract is in include/spz_amd.h \"plane\").  threshold is the inlier distance in world "
+        "units; min_inliers an int count or a float fraction of the points taking part.  With output and no select the "
+        "file is written levelled on the first plane (transform_spz); with select ('plane', 'off-plane', 'above', "
+        "'below') that subset of the input is written without requantising.  Returns a dict: planes (a list of dicts: "
+        "integers (a, b, c, e), normal, offset, inliers, points, fitness, mean_distance, rotation, translation, ...), "
+        "rotation, translation and scale of the first plane's placement in `coord` (None without a plane; nothing is "
+        "written then), threshold (T), labels (uint8 per point), kept, and ms (prepare, score, refine).");
   m.def("compare_spz",
         [](const py::object &a, const py::object &b, const py::object &views, spz::CoordinateSystem coord,
            const py::object &background, int max_sh_degree, float near_plane, const py::object &return_maps) {

@@ -446,6 +446,44 @@ py::dict alignDict(const spz::AlignResult &r) {
   return d;
 }
 
+// level_spz's result: the planes, the first plane's placement, the labels and the stages' times.
+py::dict levelDict(const spz::LevelResult &r) {
+  py::dict d;
+  py::list planes;
+  for (const spz::DetectedPlane &p : r.planes) {
+    py::dict q;
+    q["integers"] = py::make_tuple(p.normalInt[0], p.normalInt[1], p.normalInt[2], p.offsetInt);
+    q["normal"] = py::make_tuple(p.normal[0], p.normal[1], p.normal[2]);
+    q["offset"] = p.offset;
+    q["inliers"] = p.inliers;
+    q["sum_abs"] = p.sumAbs;
+    q["points"] = p.points;
+    q["above"] = p.above;
+    q["below"] = p.below;
+    q["best_hypothesis"] = p.bestHypothesis;
+    q["refinements"] = p.refinements;
+    q["fitness"] = p.fitness;
+    q["mean_distance"] = p.meanDistance;
+    q["rotation"] = py::make_tuple(p.rotation[0], p.rotation[1], p.rotation[2], p.rotation[3]);
+    q["translation"] = py::make_tuple(p.translation[0], p.translation[1], p.translation[2]);
+    planes.append(q);
+  }
+  d["planes"] = planes;
+  if (r.planes.empty()) {
+    d["rotation"] = py::none();
+    d["translation"] = py::none();
+  } else {
+    d["rotation"] = planes[0]["rotation"];
+    d["translation"] = planes[0]["translation"];
+  }
+  d["scale"] = 1.0;
+  d["threshold"] = r.threshold;
+  d["labels"] = toArray(r.labels);
+  d["kept"] = r.kept < 0 ? py::object(py::none()) : py::object(py::int_(r.kept));
+  d["ms"] = py::make_tuple(r.prepareMs, r.scoreMs, r.refineMs);
+  return d;
+}
+
 // refine_spz's report; `data` is the written file where the inputs were bytes.
 py::dict refineDict(const spz::RefineReport &rep, const std::vector<uint8_t> *data) {
   py::dict d;
@@ -813,6 +851,54 @@ spz::AlignOptions alignOptions(const py::object &rotation, const py::object &tra
     o.maxDistance = finite(max_distance.cast<double>(), Bound::Positive, "max_distance must be None or a finite number > 0");
   }
   o.scale = finite(scale, Bound::Positive, "scale must be a finite number > 0");
+  return o;
+}
+
+// A direction argument of level_spz: None, or three numbers.
+std::optional<std::array<double, 3>> levelVector(const py::object &v, const char *name) {
+  if (v.is_none()) return std::nullopt;
+  py::array_t<double, py::array::c_style | py::array::forcecast> a(v);
+  if (a.size() != 3) throw py::value_error(std::string(name) + " must be None or (x, y, z)");
+  return std::array<double, 3>{a.data()[0], a.data()[1], a.data()[2]};
+}
+// level_spz's arguments as spz::LevelOptions.
+spz::LevelOptions levelOptions(const py::object &threshold, const py::object &hypotheses, const py::object &seed,
+                               const py::object &stride, const py::object &refine, const py::object &planes,
+                               const py::object &min_inliers, const py::object &axis, const py::object &max_tilt,
+                               const py::object &up_hint, spz::CoordinateSystem coord, bool no_translate,
+                               const py::object &select, const py::object &fractional_bits) {
+  spz::LevelOptions o;
+  o.threshold = finiteReal(threshold, Bound::NonNegative, "threshold must be a finite number >= 0 (world units)");
+  o.hypotheses = intIn<uint32_t>(hypotheses, 1, 65536, "hypotheses must be an int in 1..65536");
+  o.seed = intIn<uint64_t>(seed, 0, UINT64_MAX, "seed must be an int in 0..2^64 - 1");
+  o.stride = intIn<uint32_t>(stride, 1, 0xffffffffu, "stride must be an int >= 1");
+  o.refine = intIn<uint32_t>(refine, 0, 16, "refine must be an int in 0..16");
+  o.planes = intIn<uint32_t>(planes, 1, 255, "planes must be an int in 1..255");
+  const char *floorText = "min_inliers must be an int >= 0 (a count) or a float in [0, 1] (a fraction)";
+  if (isInt(min_inliers)) {
+    o.minInliers = intIn<uint64_t>(min_inliers, 0, UINT64_MAX, floorText);
+  } else {
+    o.minInlierFraction = finiteReal(min_inliers, Bound::NonNegative, floorText);
+    if (o.minInlierFraction > 1.0) throw py::value_error(floorText);
+  }
+  o.axis = levelVector(axis, "axis");
+  o.upHint = levelVector(up_hint, "up_hint");
+  if (o.axis.has_value() != !max_tilt.is_none()) throw py::value_error("give axis and max_tilt together");
+  if (!max_tilt.is_none()) {
+    o.maxTilt = finiteReal(max_tilt, Bound::NonNegative, "max_tilt must be a number in [0, 90] (degrees)");
+    if (o.maxTilt > 90.0) throw py::value_error("max_tilt must be a number in [0, 90] (degrees)");
+  }
+  o.coord = coord;
+  o.noTranslate = no_translate;
+  if (!select.is_none()) {
+    const std::string v = py::isinstance<py::str>(select) ? select.cast<std::string>() : "";
+    if (v == "plane") o.select = spz::LevelOptions::Select::Plane;
+    else if (v == "off-plane") o.select = spz::LevelOptions::Select::OffPlane;
+    else if (v == "above") o.select = spz::LevelOptions::Select::Above;
+    else if (v == "below") o.select = spz::LevelOptions::Select::Below;
+    else throw py::value_error("select must be None, 'plane', 'off-plane', 'above' or 'below'");
+  }
+  o.fractionalBits = intInBrackets(fractional_bits, 0, 24, "fractional_bits", false);
   return o;
 }
 

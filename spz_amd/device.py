@@ -815,6 +815,208 @@ def align_packed(source_t, source_hdr, target_t, target_hdr, *, rotation=None, t
                 ms=tuple(ms))
 
 
+def plane_threshold(threshold, fractional_bits):
+    """T = floor(threshold 2^(f+16)) of a threshold in world units (spz_amd_plane_threshold); ValueError outside
+    [0, 2^36]."""
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)):
+        raise ValueError(f"threshold must be a finite number >= 0, got {threshold!r}")
+    T = C.c_uint64(0)
+    if abi.load_library().spz_amd_plane_threshold(float(threshold), int(fractional_bits), C.byref(T)) != abi.OK:
+        raise ValueError(f"threshold must be a finite number >= 0 with floor(threshold 2^(f+16)) <= 2^36, got {threshold!r}")
+    return T.value
+
+
+def _plane_T(header, threshold, T):
+    if (threshold is None) == (T is None):
+        raise ValueError("give exactly one of threshold (world units) and T (the integer threshold)")
+    if T is None:
+        return plane_threshold(threshold, header.fractional_bits)
+    if isinstance(T, bool) or not isinstance(T, int) or not 0 <= T <= 1 << 36:
+        raise ValueError(f"T must be an int in 0..2^36, got {T!r}")
+    return T
+
+
+def _plane_struct(plane):
+    p = [int(v) for v in plane]
+    if len(p) != 4 or any(abs(v) > 65536 for v in p[:3]) or abs(p[3]) > 1 << 42 or not any(p[:3]):
+        raise ValueError("plane must be (a, b, c, e): a, b, c in [-2^16, 2^16] and not all zero, |e| <= 2^42")
+    return abi.Plane(p[0], p[1], p[2], 0, p[3])
+
+
+def plane_prepare(stream_t, header, stride=1, labels=None, stream=None):
+    """The taking-part points of a packed v2/v3 device stream (include/spz_amd.h "plane", step 1: i % stride == 0 and
+    labels[i] == 0; labels: None or a uint8 CUDA tensor of num_points), compacted into a workspace: (workspace, m).
+    Blocks until the count m is known.  The workspace serves plane_gather and the prepared= argument of plane_score,
+    plane_moments and plane_mark."""
+    L = abi.load_library()
+    _check_clean_stream(stream_t, header)
+    stride = _align_stride(stride)
+    n, dev = header.num_points, stream_t.device
+    if labels is not None and (labels.dtype != torch.uint8 or labels.numel() != n or labels.device != dev
+                               or not labels.is_contiguous()):
+        raise ValueError("labels must be a contiguous uint8 tensor of num_points on the stream's device")
+    ws = torch.empty(int(L.spz_amd_plane_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+    m = C.c_uint64(0)
+    with torch.cuda.device(dev):
+        rc = L.spz_amd_plane_prepare_device(stream_t.data_ptr(), stream_t.numel(), C.byref(header), stride,
+                                            labels.data_ptr() if labels is not None else None, ws.data_ptr(),
+                                            C.byref(m), _stream_handle(stream))
+    abi.check(rc, "spz_amd_plane_prepare_device")
+    if stream is not None:
+        ws.record_stream(stream)
+    return ws, int(m.value)
+
+
+def plane_gather(prepared, header, indices, stream=None):
+    """Prepared points by their place among the prepared ones: an int32 (k, 3) CUDA tensor of the stored integers."""
+    L = abi.load_library()
+    ws, m = prepared
+    idx = torch.as_tensor(indices, dtype=torch.int64, device=ws.device).reshape(-1)
+    if m == 0 or (idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= m)):
+        raise ValueError("an index is out of range for the prepared points")
+    idx32 = idx.to(torch.int32)   # m < 2^31
+    out = torch.empty((idx.numel(), 3), dtype=torch.int32, device=ws.device)
+    with torch.cuda.device(ws.device):
+        rc = L.spz_amd_plane_gather_device(ws.data_ptr(), header.num_points, m, idx32.data_ptr(), idx.numel(),
+                                           out.data_ptr(), _stream_handle(stream))
+    abi.check(rc, "spz_amd_plane_gather_device")
+    return out
+
+
+def plane_score(stream_t, header, planes, threshold=None, T=None, stride=1, labels=None, prepared=None, stream=None):
+    """The MSAC score of H planes over the taking-part points (include/spz_amd.h "plane", step 3).  planes: an (H, 4)
+    integer array of (a, b, c, e); a plane with a = b = c = 0, or out of range, is invalid.  Returns (K, S, cost), int64
+    CUDA tensors of H; an invalid plane has K = S = 0 and cost -1 (UINT64_MAX)."""
+    L = abi.load_library()
+    T = _plane_T(header, threshold, T)
+    ws, m = prepared if prepared is not None else plane_prepare(stream_t, header, stride, labels, stream)
+    import numpy as np
+    p = np.asarray(planes, dtype=np.int64).reshape(-1, 4)
+    H = p.shape[0]
+    if not 1 <= H <= 65536:
+        raise ValueError("between 1 and 65536 planes")
+    if np.any(np.abs(p[:, :3]) >= 1 << 31):
+        raise ValueError("a, b, c must fit 32 bits")
+    rec = np.zeros(H, dtype=[("a", "<i4"), ("b", "<i4"), ("c", "<i4"), ("r", "<i4"), ("e", "<i8")])
+    rec["a"], rec["b"], rec["c"], rec["e"] = p[:, 0], p[:, 1], p[:, 2], p[:, 3]
+    dev = ws.device
+    planes_t = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
+    scores = torch.empty((H, 3), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.spz_amd_plane_score_device(ws.data_ptr(), header.num_points, m, planes_t.data_ptr(), H, T,
+                                          scores.data_ptr(), _stream_handle(stream))
+    abi.check(rc, "spz_amd_plane_score_device")
+    if stream is not None:
+        planes_t.record_stream(stream)
+    return scores[:, 0].contiguous(), scores[:, 1].contiguous(), scores[:, 2].contiguous()
+
+
+def plane_moments(stream_t, header, plane, threshold=None, T=None, stride=1, labels=None, prepared=None, stream=None):
+    """The exact moments of one plane (a, b, c, e) over the taking-part points (include/spz_amd.h "plane", step 5): a
+    dict of Python ints: count, sum_abs, above, below, points, sum_p (3) and sum_pp (6: XX, XY, XZ, YY, YZ, ZZ), and
+    `struct`, the abi.PlaneMoments for spz_amd_plane_solve.  Synchronises to read them."""
+    L = abi.load_library()
+    T = _plane_T(header, threshold, T)
+    q = _plane_struct(plane)
+    ws, m = prepared if prepared is not None else plane_prepare(stream_t, header, stride, labels, stream)
+    dev = ws.device
+    mom_t = torch.empty(C.sizeof(abi.PlaneMoments), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.spz_amd_plane_moments_device(ws.data_ptr(), header.num_points, m, C.byref(q), T, mom_t.data_ptr(),
+                                            _stream_handle(stream))
+        abi.check(rc, "spz_amd_plane_moments_device")
+        (stream or torch.cuda.current_stream(dev)).synchronize()
+    mo = abi.PlaneMoments.from_buffer_copy(mom_t.cpu().numpy().tobytes())
+    return dict(count=int(mo.count), sum_abs=int(mo.sum_abs), above=int(mo.above), below=int(mo.below),
+                points=int(mo.points), sum_p=[int(v) for v in mo.sum_p],
+                sum_pp=[(int(h) << 64) + int(l) for l, h in zip(mo.sum_pp_lo, mo.sum_pp_hi)], struct=mo)
+
+
+def plane_mark(stream_t, header, plane, value, labels_out, threshold=None, T=None, stride=1, labels=None,
+               prepared=None, stream=None):
+    """labels_out[i] = value (1..255) for the inliers of one plane among the taking-part points, in place
+    (spz_amd_plane_mark_device); every other entry keeps its value.  Returns labels_out."""
+    L = abi.load_library()
+    T = _plane_T(header, threshold, T)
+    q = _plane_struct(plane)
+    if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value <= 255:
+        raise ValueError(f"value must be an int in 0..255, got {value!r}")
+    ws, m = prepared if prepared is not None else plane_prepare(stream_t, header, stride, labels, stream)
+    if labels_out.dtype != torch.uint8 or labels_out.numel() != header.num_points or labels_out.device != ws.device \
+            or not labels_out.is_contiguous():
+        raise ValueError("labels_out must be a contiguous uint8 tensor of num_points on the stream's device")
+    with torch.cuda.device(ws.device):
+        rc = L.spz_amd_plane_mark_device(ws.data_ptr(), header.num_points, m, C.byref(q), T, value,
+                                         labels_out.data_ptr(), _stream_handle(stream))
+    abi.check(rc, "spz_amd_plane_mark_device")
+    return labels_out
+
+
+def detect_planes_packed(stream_t, header, *, threshold, hypotheses=4096, seed=0, stride=1, refine=3, planes=1,
+                         min_inliers=0, axis=None, max_tilt=None, up_hint=None, coord=0, no_translate=False):
+    """The dominant planes of a packed v2/v3 device stream (spz_amd_plane_host; include/spz_amd.h "plane"): a dict with
+    planes (a list of dicts: integers (a, b, c, e), inliers, sum_abs, points, above, below, best_hypothesis,
+    refinements, fitness, mean_distance, normal, offset, rotation (x, y, z, w), translation, scale: the levelling
+    placement in `coord`), labels (a uint8 CUDA tensor: 0 or the 1-based plane of each point), threshold (T) and ms
+    (prepare, score, refine).  min_inliers: an int count, or a float fraction of the points taking part.  Blocking; runs
+    on a stream of its own."""
+    L = abi.load_library()
+    _check_clean_stream(stream_t, header)
+    o = abi.PlaneOptions()
+    abi.check(L.spz_amd_plane_default_options(C.byref(o)), "spz_amd_plane_default_options")
+    for name, v in (("hypotheses", hypotheses), ("stride", stride), ("refine", refine), ("planes", planes)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 2 ** 32:
+            raise ValueError(f"{name} must be a non-negative int, got {v!r}")
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"seed must be an int in 0..2^64 - 1, got {seed!r}")
+    T = plane_threshold(threshold, header.fractional_bits)
+    o.threshold = float(threshold)
+    o.hypotheses, o.stride, o.refine, o.max_planes, o.seed = hypotheses, stride, refine, planes, seed
+    if isinstance(min_inliers, bool) or not isinstance(min_inliers, (int, float)) or min_inliers < 0:
+        raise ValueError("min_inliers must be an int >= 0 (a count) or a float in [0, 1] (a fraction)")
+    if isinstance(min_inliers, float):
+        if not min_inliers <= 1.0:
+            raise ValueError("min_inliers must be an int >= 0 (a count) or a float in [0, 1] (a fraction)")
+        taking = (header.num_points + max(stride, 1) - 1) // max(stride, 1)
+        o.min_inliers = math.ceil(min_inliers * float(taking))
+    else:
+        o.min_inliers = min_inliers
+    if (axis is None) != (max_tilt is None):
+        raise ValueError("give axis and max_tilt together")
+    for name, v, has in (("axis", axis, "has_axis"), ("up_hint", up_hint, "has_up_hint")):
+        if v is not None:
+            v = [float(t) for t in v]
+            if len(v) != 3:
+                raise ValueError(f"{name} must be (x, y, z)")
+            getattr(o, name)[:] = v
+            setattr(o, has, 1)
+    if max_tilt is not None:
+        o.max_tilt = float(max_tilt)
+    o.coord = int(coord)
+    o.no_translate = 1 if no_translate else 0
+    if L.spz_amd_plane_check(C.byref(o)) != abi.OK:
+        raise ValueError("invalid plane options: threshold >= 0, hypotheses 1..65536, refine 0..16, planes 1..255, "
+                         "stride >= 1, a nonzero axis and up_hint, max_tilt 0..90, coord 0..8, all finite")
+    import numpy as np
+    res = (abi.PlaneResult * planes)()
+    found = C.c_uint32(0)
+    ms = (C.c_float * 3)()
+    labels = np.zeros(header.num_points, np.uint8)
+    dev = stream_t.device
+    torch.cuda.current_stream(dev).synchronize()   # the stream's producers: the run uses a stream of its own
+    rc = L.spz_amd_plane_host(stream_t.data_ptr(), stream_t.numel(), C.byref(header), C.byref(o), dev.index or 0, res,
+                              planes, C.byref(found), labels.ctypes.data, ms)
+    abi.check(rc, "spz_amd_plane_host")
+    out = []
+    for r in res[:found.value]:
+        out.append(dict(integers=(r.plane.a, r.plane.b, r.plane.c, r.plane.e), inliers=int(r.inliers),
+                        sum_abs=int(r.sum_abs), points=int(r.points), above=int(r.above), below=int(r.below),
+                        best_hypothesis=int(r.best_hypothesis), refinements=int(r.refinements), fitness=r.fitness,
+                        mean_distance=r.mean_distance, normal=tuple(r.normal), offset=r.offset,
+                        rotation=tuple(r.rotation), translation=tuple(r.translation), scale=r.scale))
+    return dict(planes=out, labels=torch.from_numpy(labels).to(dev), threshold=T, ms=tuple(ms))
+
+
 def _cloud_render_args(cloud, num_points, sh_degree):
     if int(sh_degree) not in SH_DIM:
         raise ValueError(f"sh_degree must be 0..3, got {sh_degree}")
