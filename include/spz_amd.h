@@ -1373,7 +1373,9 @@ int spz_amd_compare_host(const uint8_t *d_stream_a, size_t size_a, const spz_amd
  *      num_views results each; *h_skipped (may be NULL): the non-finite elements the steps left alone, summed over the
  *      steps; h_ms (may be NULL): [0] wall-clock milliseconds of the targets and "before" metrics, [1] of the
  *      iterations and the encode, [2] of the "after" metrics; *h_bad_view (may be NULL): the view a failure concerns,
- *      else -1. */
+ *      else -1.  Every refusal of every open entry of this family (refine, densify, images, images with depth, and
+ *      their host forms) leaves *ctx NULL, *h_out_bytes 0, *h_bad_view -1 unless a view is at fault, and, where the
+ *      entry has them, *h_num_points 0 and *h_num_rounds 0. */
 enum {
   SPZ_AMD_REFINE_MAX_VIEWS = 1024,
   SPZ_AMD_TRAIN_POSITIONS = 1,
@@ -1594,8 +1596,8 @@ int spz_amd_refine_densify_open(const uint8_t *d_stream_a, size_t size_a, const 
  *      be NULL): 12 doubles per view, exactly the identity without fit_exposure.  The other outputs are
  *      refine_densify_open's; the result is fetched and closed with refine_fetch, refine_device_data, refine_close.
  *      refine_images_host_open: the same with the images and weight maps in host memory (h_targets, h_weights, shaped
- *      as above): views, options and photo are checked first, then the images are copied to `device` and kept there
- *      until the call returns. */
+ *      as above): every argument is checked first, as refine_images_open checks it (but a host map may lie at any
+ *      address), then the images are copied to `device` and kept there until the call returns. */
 typedef struct {
   int32_t fit_exposure; /* 0 or 1 */
   int32_t reserved;

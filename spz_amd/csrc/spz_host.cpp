@@ -2941,86 +2941,87 @@ bool refineOptionsOk(const RefineOptions &o, std::vector<spz_amd_render_params> 
   return viewListParams(who, o.views, SPZ_AMD_REFINE_MAX_VIEWS,
                         {o.nearPlane, o.coord, &o.background, o.maxShDegree, ", maxShDegree 0..3, coord valid"}, params);
 }
-}  // namespace
 
-bool refineSpz(const uint8_t *data, int32_t size, const uint8_t *target, int32_t targetSize, const RefineOptions &o,
-               std::vector<uint8_t> *out, RefineReport *report) {
-  const char *who = "refineSpz";
-  g_last_status = SPZ_AMD_OK;
-  if (report) *report = RefineReport{};
-  if (out == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no output vector");
+// What refineSpz and refineSpzToImages do around their open entries: the options as the C ABI's, the position rate
+// from the scene's extent, the densify pre-check, the host-side result arrays, and after the entry the messages, the
+// stage laps and the RefineReport.
+struct RefineCall {
+  const char *who;
+  const RefineOptions &o;
   std::vector<spz_amd_render_params> params;
   spz_amd_refine_options c;
   spz_amd_densify_options d;
-  if (!refineOptionsOk(o, &params, &c, &d)) return false;
-  Laps laps(who, "SPZ_AMD_REFINE_TIMING");
-  DevicePackedGaussians da, db;
-  if (!loadInput(who, data, size, &da) || !loadInput(who, target, targetSize, &db)) return false;
-  laps.lap("inflate");
-  if (da.device != db.device) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "the inputs were loaded on different devices");
-  if (!o.positionLr) {  // 3DGS scales the position rate by the scene's extent
+  std::vector<spz_amd_image_metrics> before, after;
+  std::vector<double> history;
+  std::vector<spz_amd_densify_round> rounds;
+  OpenResult r{spz_amd_refine_fetch, spz_amd_refine_device_data, spz_amd_refine_close};
+  uint64_t bytes = 0, skipped = 0, numPoints = 0;
+  float ms[3] = {0.0f, 0.0f, 0.0f};
+  int32_t bad = -1;
+  int numRounds = 0;
+
+  RefineCall(const char *name, const RefineOptions &options) : who(name), o(options) {}
+  bool densify() const { return d.interval > 0; }
+  int views() const { return static_cast<int>(params.size()); }
+
+  // 3DGS scales the position rate by the scene's extent.
+  void positionRate(const DevicePackedGaussians &scene, Laps *laps) {
+    if (o.positionLr) return;
     UnpackOptions u;
     u.to = o.coord;
-    const GaussianCloud t = db.unpack(u);
+    const GaussianCloud t = scene.unpack(u);
     std::array<float, 3> centre;
     float radius = 1.0f;
     if (!boundingSphere(t.positions, &centre, &radius)) radius = 1.0f;
     c.lr[0] = 1.6e-4 * static_cast<double>(radius);
-    laps.lap("extent");
+    laps->lap("extent");
   }
-  const spz_amd_header ha = headerOf(da), hb = headerOf(db);
-  const size_t nv = params.size();
-  std::vector<spz_amd_image_metrics> before(nv), after(nv);
-  std::vector<double> history(static_cast<size_t>(o.iterations) + 1);
-  OpenResult r(spz_amd_refine_fetch, spz_amd_refine_device_data, spz_amd_refine_close);
-  uint64_t bytes = 0, skipped = 0;
-  float ms[3] = {0.0f, 0.0f, 0.0f};
-  int32_t bad = -1;
-  const bool densify = d.interval > 0;
-  if (densify) {
+
+  // With densify: the views give an extent, and the cloud may grow to `cap` points, not below the input's.
+  bool densifyFits(const spz_amd_header &ha, uint64_t cap) const {
+    if (!densify()) return true;
     spz_amd_densify_limits lim;
-    if (spz_amd_densify_thresholds(&d, params.data(), static_cast<int>(nv), &lim) != SPZ_AMD_OK) {
+    if (spz_amd_densify_thresholds(&d, params.data(), views(), &lim) != SPZ_AMD_OK) {
       return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "densify: the views' camera centres coincide, so they give no "
                         "extent: set densify.extent");
     }
-    const uint64_t cap = d.max_points ? d.max_points : hb.num_points;
     if (cap < ha.num_points) {
       return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "densify: maxPoints %llu is below the input's %u points",
                         static_cast<unsigned long long>(cap), ha.num_points);
     }
+    return true;
   }
-  uint64_t numPoints = ha.num_points;
-  int numRounds = 0;
-  std::vector<spz_amd_densify_round> rounds(densify ? static_cast<size_t>(o.iterations / d.interval) + 1 : 0);
-  const int rc = densify
-      ? spz_amd_refine_densify_open(da.stream, da.streamBytes, &ha, db.stream, db.streamBytes, &hb, params.data(),
-                                    static_cast<int>(nv), &c, &d, da.device, &r.ctx, &bytes, history.data(),
-                                    before.data(), after.data(), &skipped, ms, &bad, &numPoints, rounds.data(),
-                                    static_cast<int>(rounds.size()), &numRounds, nullptr)
-      : spz_amd_refine_open(da.stream, da.streamBytes, &ha, db.stream, db.streamBytes, &hb, params.data(),
-                            static_cast<int>(nv), &c, da.device, &r.ctx, &bytes, history.data(), before.data(),
-                            after.data(), &skipped, ms, &bad);
-  if (rc == SPZ_AMD_ERR_UNSUPPORTED) {
-    return opRejected(who, rc, "the encoder writes versions 2 and 3 and positions at 12 fractional bits: the input has "
-                      "version %u and %u", ha.version, static_cast<unsigned>(ha.fractional_bits));
+
+  void allocate(const spz_amd_header &ha) {
+    before.resize(params.size());
+    after.resize(params.size());
+    history.resize(static_cast<size_t>(o.iterations) + 1);
+    rounds.resize(densify() ? static_cast<size_t>(o.iterations / d.interval) + 1 : 0);
+    numPoints = ha.num_points;
   }
-  if (viewsFailed(who, rc, bad)) return false;
-  laps.stage("targets", ms[0], (" (" + std::to_string(nv) + " views)").c_str());
-  laps.stage("iterations", ms[1], (" (" + std::to_string(o.iterations) + ")").c_str());
-  laps.stage("after", ms[2]);
-  laps.lap("refine");
-  da.release();
-  db.release();
-  if (!r.finish(who, bytes, &laps, out)) return false;
-  if (report) {
+
+  // What the entry answered: its refusals as messages, then its three stages (the first is `firstStage`).
+  bool opened(int rc, const spz_amd_header &ha, const char *firstStage, Laps *laps) const {
+    if (rc == SPZ_AMD_ERR_UNSUPPORTED) {
+      return opRejected(who, rc, "the encoder writes versions 2 and 3 and positions at 12 fractional bits: the input has "
+                        "version %u and %u", ha.version, static_cast<unsigned>(ha.fractional_bits));
+    }
+    if (viewsFailed(who, rc, bad)) return false;
+    laps->stage(firstStage, ms[0], (" (" + std::to_string(params.size()) + " views)").c_str());
+    laps->stage("iterations", ms[1], (" (" + std::to_string(o.iterations) + ")").c_str());
+    laps->stage("after", ms[2]);
+    laps->lap("refine");
+    return true;
+  }
+
+  // The output file's image, and the report.  The caller has released the inputs' device memory.
+  bool finish(Laps *laps, std::vector<uint8_t> *out, RefineReport *report) {
+    if (!r.finish(who, bytes, laps, out)) return false;
+    if (report == nullptr) return true;
     history.resize(static_cast<size_t>(o.iterations));
     report->history.swap(history);
-    report->before.resize(nv);
-    report->after.resize(nv);
-    for (size_t v = 0; v < nv; ++v) {
-      report->before[v] = toMetrics(before[v]);
-      report->after[v] = toMetrics(after[v]);
-    }
+    for (const spz_amd_image_metrics &m : before) report->before.push_back(toMetrics(m));
+    for (const spz_amd_image_metrics &m : after) report->after.push_back(toMetrics(m));
     report->skipped = skipped;
     report->positionLr = c.lr[0];
     for (int k = 0; k < 3; ++k) report->ms[k] = ms[k];
@@ -3029,9 +3030,43 @@ bool refineSpz(const uint8_t *data, int32_t size, const uint8_t *target, int32_t
       const spz_amd_densify_round &x = rounds[static_cast<size_t>(k)];
       report->rounds.push_back(DensifyRound{x.iteration, x.cloned, x.split, x.culled, x.refused, x.num_points});
     }
+    return true;
   }
-  return true;
+};
+}  // namespace
+
+bool refineSpz(const uint8_t *data, int32_t size, const uint8_t *target, int32_t targetSize, const RefineOptions &o,
+               std::vector<uint8_t> *out, RefineReport *report) {
+  const char *who = "refineSpz";
+  g_last_status = SPZ_AMD_OK;
+  if (report) *report = RefineReport{};
+  if (out == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no output vector");
+  RefineCall call(who, o);
+  if (!refineOptionsOk(o, &call.params, &call.c, &call.d)) return false;
+  Laps laps(who, "SPZ_AMD_REFINE_TIMING");
+  DevicePackedGaussians da, db;
+  if (!loadInput(who, data, size, &da) || !loadInput(who, target, targetSize, &db)) return false;
+  laps.lap("inflate");
+  if (da.device != db.device) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "the inputs were loaded on different devices");
+  call.positionRate(db, &laps);
+  const spz_amd_header ha = headerOf(da), hb = headerOf(db);
+  if (!call.densifyFits(ha, call.d.max_points ? call.d.max_points : hb.num_points)) return false;
+  call.allocate(ha);
+  const int rc = call.densify()
+      ? spz_amd_refine_densify_open(da.stream, da.streamBytes, &ha, db.stream, db.streamBytes, &hb, call.params.data(),
+                                    call.views(), &call.c, &call.d, da.device, &call.r.ctx, &call.bytes,
+                                    call.history.data(), call.before.data(), call.after.data(), &call.skipped, call.ms,
+                                    &call.bad, &call.numPoints, call.rounds.data(),
+                                    static_cast<int>(call.rounds.size()), &call.numRounds, nullptr)
+      : spz_amd_refine_open(da.stream, da.streamBytes, &ha, db.stream, db.streamBytes, &hb, call.params.data(),
+                            call.views(), &call.c, da.device, &call.r.ctx, &call.bytes, call.history.data(),
+                            call.before.data(), call.after.data(), &call.skipped, call.ms, &call.bad);
+  if (!call.opened(rc, ha, "targets", &laps)) return false;
+  da.release();
+  db.release();
+  return call.finish(&laps, out, report);
 }
+
 
 bool refineSpz(const std::vector<uint8_t> &data, const std::vector<uint8_t> &target, const RefineOptions &o,
                std::vector<uint8_t> *out, RefineReport *report) {
@@ -3109,43 +3144,21 @@ bool refineSpzToImages(const uint8_t *data, int32_t size, const RefineOptions &o
   g_last_status = SPZ_AMD_OK;
   if (report) *report = PhotoReport{};
   if (out == nullptr) return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "no output vector");
-  std::vector<spz_amd_render_params> params;
-  spz_amd_refine_options c;
-  spz_amd_densify_options d;
+  RefineCall call(who, o);
   spz_amd_photo_options pc;
   spz_amd_depth_options zc;
-  if (!refineOptionsOk(o, &params, &c, &d, who) || !photoOptionsOk(who, o, p, &pc, &zc)) return false;
-  const bool densify = d.interval > 0;
-  if (densify && d.max_points == 0) {
+  if (!refineOptionsOk(o, &call.params, &call.c, &call.d, who) || !photoOptionsOk(who, o, p, &pc, &zc)) return false;
+  if (call.densify() && call.d.max_points == 0) {
     return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "densify: there is no target to take a count from: set densify.maxPoints");
   }
   Laps laps(who, "SPZ_AMD_REFINE_TIMING");
   DevicePackedGaussians da;
   if (!loadInput(who, data, size, &da)) return false;
   laps.lap("inflate");
-  if (!o.positionLr) {  // 3DGS scales the position rate by the scene's extent
-    UnpackOptions u;
-    u.to = o.coord;
-    const GaussianCloud t = da.unpack(u);
-    std::array<float, 3> centre;
-    float radius = 1.0f;
-    if (!boundingSphere(t.positions, &centre, &radius)) radius = 1.0f;
-    c.lr[0] = 1.6e-4 * static_cast<double>(radius);
-    laps.lap("extent");
-  }
+  call.positionRate(da, &laps);
   const spz_amd_header ha = headerOf(da);
-  const size_t nv = params.size();
-  if (densify) {
-    spz_amd_densify_limits lim;
-    if (spz_amd_densify_thresholds(&d, params.data(), static_cast<int>(nv), &lim) != SPZ_AMD_OK) {
-      return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "densify: the views' camera centres coincide, so they give no "
-                        "extent: set densify.extent");
-    }
-    if (d.max_points < ha.num_points) {
-      return opRejected(who, SPZ_AMD_ERR_INVALID_ARG, "densify: maxPoints %llu is below the input's %u points",
-                        static_cast<unsigned long long>(d.max_points), ha.num_points);
-    }
-  }
+  if (!call.densifyFits(ha, call.d.max_points)) return false;
+  const size_t nv = call.params.size();
   std::vector<const float *> targets(nv), weights(nv), depths(nv);
   bool anyWeights = false, anyDepth = false;
   for (size_t v = 0; v < nv; ++v) {
@@ -3156,56 +3169,30 @@ bool refineSpzToImages(const uint8_t *data, int32_t size, const RefineOptions &o
     anyDepth = anyDepth || depths[v] != nullptr;
   }
   std::vector<double> depthHistory(anyDepth ? static_cast<size_t>(o.iterations) + 1 : 0), depthError(anyDepth ? 2 * nv : 0);
-  std::vector<spz_amd_image_metrics> before(nv), after(nv);
-  std::vector<double> history(static_cast<size_t>(o.iterations) + 1), exposures(12 * nv);
-  OpenResult r(spz_amd_refine_fetch, spz_amd_refine_device_data, spz_amd_refine_close);
-  uint64_t bytes = 0, skipped = 0, numPoints = ha.num_points;
-  float ms[3] = {0.0f, 0.0f, 0.0f};
-  int32_t bad = -1;
-  int numRounds = 0;
-  std::vector<spz_amd_densify_round> rounds(densify ? static_cast<size_t>(o.iterations / d.interval) + 1 : 0);
+  std::vector<double> exposures(12 * nv);
+  call.allocate(ha);
+  const spz_amd_densify_options *dn = call.densify() ? &call.d : nullptr;
+  const int nr = static_cast<int>(call.rounds.size());
   const int rc =
       anyDepth ? spz_amd_refine_images_depth_host_open(
-                     da.stream, da.streamBytes, &ha, params.data(), static_cast<int>(nv), targets.data(),
-                     p.images[0].channels, anyWeights ? weights.data() : nullptr, depths.data(), &zc, &c, &pc,
-                     densify ? &d : nullptr, da.device, &r.ctx, &bytes, history.data(), before.data(), after.data(),
-                     &skipped, ms, &bad, &numPoints, rounds.data(), static_cast<int>(rounds.size()), &numRounds, nullptr,
+                     da.stream, da.streamBytes, &ha, call.params.data(), call.views(), targets.data(),
+                     p.images[0].channels, anyWeights ? weights.data() : nullptr, depths.data(), &zc, &call.c, &pc, dn,
+                     da.device, &call.r.ctx, &call.bytes, call.history.data(), call.before.data(), call.after.data(),
+                     &call.skipped, call.ms, &call.bad, &call.numPoints, call.rounds.data(), nr, &call.numRounds, nullptr,
                      exposures.data(), depthHistory.data(), depthError.data())
                : spz_amd_refine_images_host_open(
-                     da.stream, da.streamBytes, &ha, params.data(), static_cast<int>(nv), targets.data(),
-                     p.images[0].channels, anyWeights ? weights.data() : nullptr, &c, &pc, densify ? &d : nullptr,
-                     da.device, &r.ctx, &bytes, history.data(), before.data(), after.data(), &skipped, ms, &bad,
-                     &numPoints, rounds.data(), static_cast<int>(rounds.size()), &numRounds, nullptr, exposures.data());
-  if (rc == SPZ_AMD_ERR_UNSUPPORTED) {
-    return opRejected(who, rc, "the encoder writes versions 2 and 3 and positions at 12 fractional bits: the input has "
-                      "version %u and %u", ha.version, static_cast<unsigned>(ha.fractional_bits));
-  }
-  if (viewsFailed(who, rc, bad)) return false;
-  laps.stage("before", ms[0], (" (" + std::to_string(nv) + " views)").c_str());
-  laps.stage("iterations", ms[1], (" (" + std::to_string(o.iterations) + ")").c_str());
-  laps.stage("after", ms[2]);
-  laps.lap("refine");
+                     da.stream, da.streamBytes, &ha, call.params.data(), call.views(), targets.data(),
+                     p.images[0].channels, anyWeights ? weights.data() : nullptr, &call.c, &pc, dn, da.device,
+                     &call.r.ctx, &call.bytes, call.history.data(), call.before.data(), call.after.data(), &call.skipped,
+                     call.ms, &call.bad, &call.numPoints, call.rounds.data(), nr, &call.numRounds, nullptr,
+                     exposures.data());
+  if (!call.opened(rc, ha, "before", &laps)) return false;
   da.release();
-  if (!r.finish(who, bytes, &laps, out)) return false;
-  if (report) {
-    RefineReport &rr = report->refine;
-    history.resize(static_cast<size_t>(o.iterations));
-    rr.history.swap(history);
-    rr.before.resize(nv);
-    rr.after.resize(nv);
+  if (!call.finish(&laps, out, report ? &report->refine : nullptr)) return false;
+  if (report) {  // on top of the RefineReport: the exposures and, with a depth map, the depth losses
     report->exposures.resize(nv);
     for (size_t v = 0; v < nv; ++v) {
-      rr.before[v] = toMetrics(before[v]);
-      rr.after[v] = toMetrics(after[v]);
       std::copy(exposures.begin() + 12 * v, exposures.begin() + 12 * (v + 1), report->exposures[v].begin());
-    }
-    rr.skipped = skipped;
-    rr.positionLr = c.lr[0];
-    for (int k = 0; k < 3; ++k) rr.ms[k] = ms[k];
-    rr.numPoints = numPoints;
-    for (int k = 0; k < numRounds && static_cast<size_t>(k) < rounds.size(); ++k) {
-      const spz_amd_densify_round &x = rounds[static_cast<size_t>(k)];
-      rr.rounds.push_back(DensifyRound{x.iteration, x.cloned, x.split, x.culled, x.refused, x.num_points});
     }
     if (anyDepth) {
       depthHistory.resize(static_cast<size_t>(o.iterations));

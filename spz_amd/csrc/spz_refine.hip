@@ -20,6 +20,10 @@
 //   refine images with depth       (DESIGN §8 "Depth fit") a view with a depth map: spz_amd_render_depth_device for the
 //                                  finish, the photo loss, spz_amd_depth_loss_device adding into its gradient, and
 //                                  spz_amd_render_depth_backward_device; the depth error of A and of the output.
+//
+// The six open entries share one path: an entry fills a RefineRequest and a RefineOutputs; reset() and plan() refuse on
+// the host, before any HIP call, and derive every fact once; layout() cuts the one allocation into typed RefineBuffers;
+// RefineRun is the loop as small functions over that state.  The host forms upload and join at refine_run.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -209,14 +213,8 @@ int adam_check_args(const spz_amd_cloud_grads *d_params, const spz_amd_cloud_gra
 
 // The float cloud, its gradients and moments: four times the six arrays, each array 256-aligned in one allocation.
 struct CloudSet {
-  spz_amd_cloud_grads p, g, m, v;
-  uint64_t moments_off = 0, moments_bytes = 0;  // m and v are contiguous: one memset
+  spz_amd_cloud_grads p = {}, g = {}, m = {}, v = {};
 };
-
-spz_amd_cloud_grads cloud_at(uint8_t *base, const uint64_t off[6], const uint64_t count[6]) {
-  auto f = [&](int k) { return count[k] ? reinterpret_cast<float *>(base + off[k]) : nullptr; };
-  return spz_amd_cloud_grads{f(0), f(1), f(2), f(3), f(4), f(5)};
-}
 
 }  // namespace
 }  // namespace spz_amd_detail
@@ -288,464 +286,683 @@ int spz_amd_refine_check(const spz_amd_refine_options *o) {
 
 namespace {
 
-// What the densify entry reports beside refine_open's results.
-struct DensifyReport {
-  uint64_t *h_num_points;
-  spz_amd_densify_round *h_rounds;
-  int rounds_capacity;
-  int *h_num_rounds;
-  uint32_t *h_origin;
+// What the caller of one of the six open entries gives.  An entry fills this and a RefineOutputs; nothing below the
+// entries reads an argument list.
+struct RefineRequest {
+  const uint8_t *d_stream_a;
+  size_t size_a;
+  const spz_amd_header *hdr_a;
+  const uint8_t *d_stream_b;  // the stream the targets are rendered from: not read when they are given
+  size_t size_b;
+  const spz_amd_header *hdr_b;
+  const spz_amd_render_params *views;
+  int num_views;
+  const spz_amd_refine_options *options;
+  const spz_amd_densify_options *densify;  // NULL or interval 0: off
+  int device;
+  bool given = false;  // "refine images": the targets are the caller's num_views images of `channels` floats a pixel
+  const spz_amd_photo_options *photo = nullptr;
+  const float *const *targets = nullptr;
+  int channels = 4;
+  const float *const *weights = nullptr;  // NULL, or num_views weight maps, any of them NULL
+  bool depth_entry = false;               // "refine images with depth": depth is required
+  const spz_amd_depth_options *depth = nullptr;
+  const float *const *depths = nullptr;  // NULL, or num_views depth maps, any of them NULL
+  bool on_host = false;  // the host forms before their upload: targets, weights and depths point to host memory
 };
 
-// The targets of spz_amd_refine_images_open: given, not rendered.  Every pointer is the caller's.
-struct PhotoTargets {
-  const float *const *d_targets;  // num_views images of `channels` floats per pixel
-  const float *const *d_weights;  // NULL, or num_views weight maps, any of them NULL
-  int channels;
-  const spz_amd_photo_options *options;
-  double *h_exposures;            // may be NULL: 12 doubles per view out
-  // "refine images with depth": all NULL for spz_amd_refine_images_open
-  const float *const *d_depths = nullptr;        // NULL, or num_views depth maps, any of them NULL
-  const spz_amd_depth_options *depth = nullptr;  // required with the depth entries
-  double *h_depth_history = nullptr;             // may be NULL: iterations doubles out
-  double *h_depth_error = nullptr;               // may be NULL: 2 doubles per view out
+// Every place a result goes, in the order of the entries' arguments.  All but ctx and h_out_bytes may be NULL.
+struct RefineOutputs {
+  void **ctx;
+  uint64_t *h_out_bytes;
+  double *h_history;
+  spz_amd_image_metrics *h_before, *h_after;
+  uint64_t *h_skipped;
+  float *h_ms;
+  int32_t *h_bad_view;
+  uint64_t *h_num_points = nullptr;  // densify's report
+  spz_amd_densify_round *h_rounds = nullptr;
+  int rounds_capacity = 0;
+  int *h_num_rounds = nullptr;
+  uint32_t *h_origin = nullptr;
+  double *h_exposures = nullptr, *h_depth_history = nullptr, *h_depth_error = nullptr;  // 12 V, iterations, 2 V doubles
 };
 
-// The loop of the three entries: spz_amd_refine_open (densify == nullptr), spz_amd_refine_densify_open, and
-// spz_amd_refine_images_open (photo != nullptr: there is no stream B, the targets are the caller's images).
-int refine_run(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a, const uint8_t *d_stream_b,
-               size_t size_b, const spz_amd_header *hdr_b, const spz_amd_render_params *views, int num_views,
-               const spz_amd_refine_options *options, const spz_amd_densify_options *densify, int device, void **ctx,
-               uint64_t *h_out_bytes, double *h_history, spz_amd_image_metrics *h_before, spz_amd_image_metrics *h_after,
-               uint64_t *h_skipped, float *h_ms, int32_t *h_bad_view, const DensifyReport &rep,
-               const PhotoTargets *photo = nullptr) {
-  if (h_bad_view) *h_bad_view = -1;
-  if (rep.h_num_points) *rep.h_num_points = 0;
-  if (rep.h_num_rounds) *rep.h_num_rounds = 0;
-  if (ctx == nullptr || h_out_bytes == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
-  *ctx = nullptr;
-  *h_out_bytes = 0;
-  int rc = spz_amd_refine_check(options);
-  if (rc != SPZ_AMD_OK) return rc;
-  if (options->iterations > 0 && h_history == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
-  rc = check_views(views, num_views, SPZ_AMD_REFINE_MAX_VIEWS, h_bad_view);
-  if (rc != SPZ_AMD_OK) return rc;
-  spz_amd_layout lay_a, lay_b;
-  rc = check_packed_stream(d_stream_a, size_a, hdr_a, &lay_a);
-  if (rc != SPZ_AMD_OK) return rc;
-  const int tch = photo ? photo->channels : 4;  // the targets' channels
-  bool fit = false;
+// What every entry does first: no refusal leaves an output as the caller had it.
+void reset(const RefineOutputs &o) {
+  if (o.ctx) *o.ctx = nullptr;
+  if (o.h_out_bytes) *o.h_out_bytes = 0;
+  if (o.h_bad_view) *o.h_bad_view = -1;
+  if (o.h_num_points) *o.h_num_points = 0;
+  if (o.h_num_rounds) *o.h_num_rounds = 0;
+}
+
+// What follows from a request, derived once.
+struct RefinePlan {
+  spz_amd_layout lay_a;
+  // A's points; those of the stream the targets are rendered from (A's when they are given); the most the cloud may
+  // grow to (n unless rounds run)
+  uint64_t n = 0, n_target = 0, cap_n = 0;
+  int deg = 0, aa = 0, coord = 0, iters = 0;
+  int tch = 4;             // the targets' channels
+  unsigned mask = 0;       // the trained arrays (without sh at degree 0: nothing to train there)
+  bool fit = false;        // an exposure per view is fitted
   bool any_depth = false;  // some view has a depth map
-  if (photo != nullptr) {
-    rc = spz_amd_photo_check(photo->options);
+  bool densify = false;    // densify rounds run
+  spz_amd_densify_limits lim = {};
+  uint64_t max_px = 0, loss_ws = 0, metrics_ws = 0, depth_ws = 0;  // the largest view's pixels and workspaces
+};
+
+// The given targets: the photo and depth options, then per view the image, its weight map and its depth map.
+int plan_given(const RefineRequest &rq, const RefineOutputs &out, RefinePlan *pl) {
+  int rc = spz_amd_photo_check(rq.photo);
+  if (rc != SPZ_AMD_OK) return rc;
+  if (rq.depth_entry) {
+    rc = spz_amd_depth_check(rq.depth);
     if (rc != SPZ_AMD_OK) return rc;
-    if (photo->depth != nullptr) {
-      rc = spz_amd_depth_check(photo->depth);
-      if (rc != SPZ_AMD_OK) return rc;
-    } else if (photo->d_depths != nullptr) {
+  }
+  if (rq.targets == nullptr || (rq.channels != 3 && rq.channels != 4)) return SPZ_AMD_ERR_INVALID_ARG;
+  for (int v = 0; v < rq.num_views; ++v) {
+    const float *w = rq.weights ? rq.weights[v] : nullptr;
+    const float *dm = rq.depths ? rq.depths[v] : nullptr;
+    pl->any_depth = pl->any_depth || dm != nullptr;
+    // (device memory is read as floats; the host forms copy from theirs)
+    const bool readable = rq.on_host || (aligned4(rq.targets[v]) && aligned4(w) && aligned4(dm));
+    if (rq.targets[v] == nullptr || !readable ||
+        spz_amd_image_metrics_check((int)rq.views[v].width, (int)rq.views[v].height, 4, rq.channels) != SPZ_AMD_OK) {
+      if (out.h_bad_view) *out.h_bad_view = v;
       return SPZ_AMD_ERR_INVALID_ARG;
     }
-    if (photo->d_targets == nullptr || (tch != 3 && tch != 4)) return SPZ_AMD_ERR_INVALID_ARG;
-    for (int v = 0; v < num_views; ++v) {
-      const float *w = photo->d_weights ? photo->d_weights[v] : nullptr;
-      const float *dm = photo->d_depths ? photo->d_depths[v] : nullptr;
-      any_depth = any_depth || dm != nullptr;
-      if (photo->d_targets[v] == nullptr || (reinterpret_cast<uintptr_t>(photo->d_targets[v]) & 3u) != 0 ||
-          (reinterpret_cast<uintptr_t>(w) & 3u) != 0 || (reinterpret_cast<uintptr_t>(dm) & 3u) != 0 ||
-          spz_amd_image_metrics_check((int)views[v].width, (int)views[v].height, 4, tch) != SPZ_AMD_OK) {
-        if (h_bad_view) *h_bad_view = v;
-        return SPZ_AMD_ERR_INVALID_ARG;
-      }
-    }
-    fit = photo->options->fit_exposure != 0 && options->iterations > 0;
-    hdr_b = hdr_a;  // (only its count is read below)
-  } else {
-    rc = check_packed_stream(d_stream_b, size_b, hdr_b, &lay_b);
-    if (rc != SPZ_AMD_OK) return rc;
   }
-  if (hdr_a->num_points > kMaxEntries || hdr_b->num_points > kMaxEntries) return SPZ_AMD_ERR_TOO_MANY_POINTS;
-  const uint64_t n = hdr_a->num_points;
-  const int deg = hdr_a->sh_degree, aa = hdr_a->flags & 1, coord = views[0].coord;
-  const int iters = options->iterations;
-  unsigned mask = options->train_mask;
-  if (deg == 0) mask &= ~32u;  // nothing to train there
-  // what the encode kernel writes: versions 2 and 3, positions at 12 fractional bits
-  if (iters > 0 && (hdr_a->version == 1 || ((mask & 1u) && hdr_a->fractional_bits != 12))) return SPZ_AMD_ERR_UNSUPPORTED;
-  // densify: the thresholds once, every buffer at the capacity the cloud may grow to
-  spz_amd_densify_limits lim = {};
-  uint64_t cap_n = n;
-  bool dn = false;
-  if (densify != nullptr) {
-    rc = spz_amd_densify_check(densify);
-    if (rc != SPZ_AMD_OK) return rc;
-    if (densify->interval > 0) {
-      rc = spz_amd_densify_thresholds(densify, views, num_views, &lim);
-      if (rc != SPZ_AMD_OK) return rc;
-      if ((mask & 3u) != 3u || (densify->opacity_reset_interval > 0 && (mask & 8u) == 0u)) return SPZ_AMD_ERR_INVALID_ARG;
-      if (photo != nullptr && densify->max_points == 0) return SPZ_AMD_ERR_INVALID_ARG;  // no target count to take
-      const uint64_t mp = densify->max_points ? densify->max_points : hdr_b->num_points;
-      if (mp > kMaxEntries) return SPZ_AMD_ERR_TOO_MANY_POINTS;
-      if (mp < n) return SPZ_AMD_ERR_INVALID_ARG;
-      dn = iters > 0;
-      if (dn) cap_n = mp;
-    }
-  }
-  DeviceGuard guard;
-  rc = guard.enter(device);
-  if (rc != SPZ_AMD_OK) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
-  PackedResultPtr c;
-  rc = packed_result_open(device, &c);
-  if (rc != SPZ_AMD_OK) return rc;
+  pl->fit = rq.photo->fit_exposure != 0 && rq.options->iterations > 0;
+  return SPZ_AMD_OK;
+}
 
-  // the block: four clouds, the targets, the image and its gradient, the two small workspaces, the results
-  uint64_t count[6];
-  cloud_counts(cap_n, deg, count);
-  uint64_t max_px = 0, loss_ws = 0, metrics_ws = 0, depth_ws = 0;
-  std::vector<uint64_t> target_off((size_t)num_views);
-  for (int v = 0; v < num_views; ++v) {
-    const uint64_t px = (uint64_t)views[v].width * views[v].height;
-    max_px = px > max_px ? px : max_px;
-    const uint64_t lw = photo ? spz_amd_photo_loss_workspace_bytes((int)views[v].width, (int)views[v].height)
-                              : spz_amd_image_loss_workspace_bytes((int)views[v].width, (int)views[v].height);
-    const uint64_t mw = spz_amd_image_metrics_workspace_bytes((int)views[v].width, (int)views[v].height);
-    const uint64_t dw = any_depth ? spz_amd_depth_loss_workspace_bytes((int)views[v].width, (int)views[v].height) : 0u;
-    loss_ws = lw > loss_ws ? lw : loss_ws;
-    metrics_ws = mw > metrics_ws ? mw : metrics_ws;
-    depth_ws = dw > depth_ws ? dw : depth_ws;
+// Densify: the thresholds once, and the capacity every buffer gets.
+int plan_densify(const RefineRequest &rq, RefinePlan *pl) {
+  const spz_amd_densify_options *d = rq.densify;
+  pl->cap_n = pl->n;
+  if (d == nullptr) return SPZ_AMD_OK;
+  int rc = spz_amd_densify_check(d);
+  if (rc != SPZ_AMD_OK || d->interval <= 0) return rc;
+  rc = spz_amd_densify_thresholds(d, rq.views, rq.num_views, &pl->lim);
+  if (rc != SPZ_AMD_OK) return rc;
+  if ((pl->mask & 3u) != 3u || (d->opacity_reset_interval > 0 && (pl->mask & 8u) == 0u)) return SPZ_AMD_ERR_INVALID_ARG;
+  if (rq.given && d->max_points == 0) return SPZ_AMD_ERR_INVALID_ARG;  // no target count to take
+  const uint64_t mp = d->max_points ? d->max_points : pl->n_target;
+  if (mp > kMaxEntries) return SPZ_AMD_ERR_TOO_MANY_POINTS;
+  if (mp < pl->n) return SPZ_AMD_ERR_INVALID_ARG;
+  pl->densify = pl->iters > 0;
+  if (pl->densify) pl->cap_n = mp;
+  return SPZ_AMD_OK;
+}
+
+// Every refusal that needs no device, in one order for the six entries, and the plan.  No HIP call.
+int plan(const RefineRequest &rq, const RefineOutputs &out, RefinePlan *pl) {
+  int rc = spz_amd_refine_check(rq.options);
+  if (rc != SPZ_AMD_OK) return rc;
+  if (rq.options->iterations > 0 && out.h_history == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
+  rc = check_views(rq.views, rq.num_views, SPZ_AMD_REFINE_MAX_VIEWS, out.h_bad_view);
+  if (rc != SPZ_AMD_OK) return rc;
+  rc = check_packed_stream(rq.d_stream_a, rq.size_a, rq.hdr_a, &pl->lay_a);
+  if (rc != SPZ_AMD_OK) return rc;
+  if (rq.given) {
+    rc = plan_given(rq, out, pl);
+    pl->tch = rq.channels;
+  } else {
+    spz_amd_layout lay_b;
+    rc = check_packed_stream(rq.d_stream_b, rq.size_b, rq.hdr_b, &lay_b);
   }
-  WorkspaceOffsets o;
-  uint64_t off[4][6];
-  for (int s = 0; s < 4; ++s) {
-    for (int k = 0; k < 6; ++k) off[s][k] = o.put(count[k] * 4u);
+  if (rc != SPZ_AMD_OK) return rc;
+  pl->n = rq.hdr_a->num_points;
+  pl->n_target = rq.given ? pl->n : rq.hdr_b->num_points;
+  if (pl->n > kMaxEntries || pl->n_target > kMaxEntries) return SPZ_AMD_ERR_TOO_MANY_POINTS;
+  pl->deg = rq.hdr_a->sh_degree;
+  pl->aa = rq.hdr_a->flags & 1;
+  pl->coord = rq.views[0].coord;
+  pl->iters = rq.options->iterations;
+  pl->mask = rq.options->train_mask & (pl->deg == 0 ? ~32u : ~0u);
+  // what the encode kernel writes: versions 2 and 3, positions at 12 fractional bits
+  if (pl->iters > 0 && (rq.hdr_a->version == 1 || ((pl->mask & 1u) && rq.hdr_a->fractional_bits != 12))) {
+    return SPZ_AMD_ERR_UNSUPPORTED;
   }
-  for (int v = 0; v < num_views; ++v) {  // (given targets are used in place)
-    target_off[(size_t)v] = o.put(photo ? 0u : 16u * (uint64_t)views[v].width * views[v].height);
+  rc = plan_densify(rq, pl);
+  if (rc != SPZ_AMD_OK) return rc;
+  auto raise = [](uint64_t *most, uint64_t x) { *most = x > *most ? x : *most; };
+  for (int v = 0; v < rq.num_views; ++v) {
+    const int w = (int)rq.views[v].width, h = (int)rq.views[v].height;
+    raise(&pl->max_px, (uint64_t)rq.views[v].width * rq.views[v].height);
+    raise(&pl->loss_ws, rq.given ? spz_amd_photo_loss_workspace_bytes(w, h) : spz_amd_image_loss_workspace_bytes(w, h));
+    raise(&pl->metrics_ws, spz_amd_image_metrics_workspace_bytes(w, h));
+    raise(&pl->depth_ws, pl->any_depth ? spz_amd_depth_loss_workspace_bytes(w, h) : 0u);
   }
-  // a fitted exposure per view: 12 values and their two moments, each kind contiguous; then one gradient
-  const uint64_t o_exposure = o.put(fit ? 3u * 96u * (uint64_t)num_views + 96u : 0u);
-  const uint64_t o_image = o.put(16u * max_px), o_grad = o.put(16u * max_px), o_lws = o.put(iters ? loss_ws : 0u),
-                 o_mws = o.put(metrics_ws), o_small = o.put(16u), o_loss = o.put(24u * (uint64_t)iters),
-                 o_metrics = o.put(2u * (uint64_t)num_views * sizeof(spz_amd_image_metrics)),
-                 o_bws = o.put(!iters       ? 0u
-                               : any_depth ? spz_amd_render_depth_backward_workspace_bytes(cap_n)
-                                           : spz_amd_render_backward_workspace_bytes(cap_n));
+  return SPZ_AMD_OK;
+}
+
+// The sections of the loop's one allocation as typed pointers.  Whether a section is needed is decided in layout()
+// and nowhere else.
+struct RefineBuffers {
+  uint64_t bytes = 0;  // the allocation
+  uint64_t count[6];   // the elements of the six arrays at capacity
+  CloudSet cs;         // the float cloud, its gradients and its two moments
+  uint8_t *moments;    // m and v are contiguous: one memset of moments_bytes
+  uint64_t moments_bytes;
+  std::vector<float *> rendered;  // per view the target rendered from B (given targets are used in place)
+  // a fitted exposure per view: view v's 12 values at exposure + 12 v, its moments 12 V and 24 V doubles on, and after
+  // them all one gradient
+  double *exposure, *exposure_grad;
+  float *image, *grad;  // the render and the loss's gradient to it
+  uint8_t *loss_ws, *metrics_ws, *backward_ws;
+  uint64_t *total;
+  uint32_t *status, *skipped;
+  double *loss;                      // L, l1 and ssim per iteration
+  spz_amd_image_metrics *metrics;    // "before" per view, then "after" per view
   // with depth maps: the depth render, the gradient to its channel 0, the depth loss's workspace, L_depth and W_v per
   // iteration, and per view the two depth errors (each L and W_v)
-  const uint64_t o_depth = o.put(any_depth ? 8u * max_px : 0u), o_gdepth = o.put(any_depth ? 4u * max_px : 0u),
-                 o_dws = o.put(depth_ws), o_dloss = o.put(any_depth ? 16u * (uint64_t)iters : 0u),
-                 o_derr = o.put(any_depth ? 32u * (uint64_t)num_views : 0u);
-  uint64_t off_alt[3][6] = {};
-  for (int s = 0; s < 3; ++s) {
-    for (int k = 0; k < 6; ++k) off_alt[s][k] = o.put(dn ? count[k] * 4u : 0u);
+  float *depth, *gdepth;
+  uint8_t *depth_ws;
+  double *dloss, *derr;
+  // with densify: the apply's destinations (parameters and both moments), the statistics (accum and denom contiguous:
+  // one memset of stats_bytes), the plan's outputs, the two origin maps, the record gradients
+  CloudSet alt;
+  float *accum, *rg;
+  uint32_t *denom, *parent, *origin[2];
+  uint64_t stats_bytes, *counts;
+  uint8_t *action, *child, *plan_ws;
+};
+
+// Sections one after the other, each 256-aligned from the allocation's base; without a base (raw NULL) only the sizes.
+struct Carver {
+  uint8_t *raw;
+  WorkspaceOffsets o;
+  template <class T = uint8_t>
+  T *take(uint64_t bytes) {
+    const uint64_t at = o.put(bytes);
+    return raw ? reinterpret_cast<T *>(raw + at) : nullptr;
   }
-  const uint64_t o_accum = o.put(dn ? cap_n * 4u : 0u), o_denom = o.put(dn ? cap_n * 4u : 0u),
-                 o_action = o.put(dn ? cap_n : 0u), o_parent = o.put(dn ? cap_n * 4u : 0u),
-                 o_child = o.put(dn ? cap_n : 0u), o_origin0 = o.put(dn ? cap_n * 4u : 0u),
-                 o_origin1 = o.put(dn ? cap_n * 4u : 0u), o_rg = o.put(dn ? cap_n * 36u : 0u),
-                 o_counts = o.put(dn ? 64u : 0u), o_pws = o.put(dn ? spz_amd_densify_plan_workspace_bytes(cap_n) : 0u);
-  SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->block), o.off));
-  uint8_t *raw = c->block;  // every section is 256-aligned from hipMalloc's base
-  CloudSet cs;
-  cs.p = cloud_at(raw, off[0], count);
-  cs.g = cloud_at(raw, off[1], count);
-  cs.m = cloud_at(raw, off[2], count);
-  cs.v = cloud_at(raw, off[3], count);
-  cs.moments_off = off[2][0];
-  cs.moments_bytes = target_off[0] - off[2][0];
-  CloudSet alt;  // the apply's destinations: parameters and both moments
-  if (dn) {
-    alt.p = cloud_at(raw, off_alt[0], count);
-    alt.m = cloud_at(raw, off_alt[1], count);
-    alt.v = cloud_at(raw, off_alt[2], count);
+  spz_amd_cloud_grads cloud(const uint64_t count[6], bool on = true) {  // the six arrays; NULL for an empty one
+    float *f[6];
+    for (int k = 0; k < 6; ++k) {
+      float *p = take<float>(on ? count[k] * 4u : 0u);
+      f[k] = on && count[k] ? p : nullptr;
+    }
+    return spz_amd_cloud_grads{f[0], f[1], f[2], f[3], f[4], f[5]};
   }
-  auto *d_accum = reinterpret_cast<float *>(raw + o_accum);
-  auto *d_denom = reinterpret_cast<uint32_t *>(raw + o_denom);
-  auto *d_parent = reinterpret_cast<uint32_t *>(raw + o_parent);
-  uint32_t *d_origin[2] = {reinterpret_cast<uint32_t *>(raw + o_origin0), reinterpret_cast<uint32_t *>(raw + o_origin1)};
-  const uint32_t *origin_cur = nullptr;  // nullptr: no round yet, the identity
-  auto *d_rg = reinterpret_cast<float *>(raw + o_rg);
-  auto *d_counts = reinterpret_cast<uint64_t *>(raw + o_counts);
-  uint64_t n_cur = n;
+};
+
+// layout(rq, pl, NULL).bytes is the allocation; layout(rq, pl, its base) binds the pointers.
+RefineBuffers layout(const RefineRequest &rq, const RefinePlan &pl, uint8_t *raw) {
+  RefineBuffers b;
+  Carver c{raw, {}};
+  const uint64_t nv = (uint64_t)rq.num_views, iters = (uint64_t)pl.iters, cap = pl.densify ? pl.cap_n : 0u;
+  const uint64_t depth_px = pl.any_depth ? pl.max_px : 0u;
+  cloud_counts(pl.cap_n, pl.deg, b.count);
+  b.cs.p = c.cloud(b.count);
+  b.cs.g = c.cloud(b.count);
+  const uint64_t moments_at = c.o.off;
+  b.moments = c.take(0u);
+  b.cs.m = c.cloud(b.count);
+  b.cs.v = c.cloud(b.count);
+  b.moments_bytes = c.o.off - moments_at;
+  b.rendered.resize((size_t)nv);
+  for (uint64_t v = 0; v < nv; ++v) {
+    b.rendered[(size_t)v] = c.take<float>(rq.given ? 0u : 16u * (uint64_t)rq.views[v].width * rq.views[v].height);
+  }
+  b.exposure = c.take<double>(pl.fit ? 3u * 96u * nv + 96u : 0u);
+  b.exposure_grad = b.exposure ? b.exposure + 36u * nv : nullptr;
+  b.image = c.take<float>(16u * pl.max_px);
+  b.grad = c.take<float>(16u * pl.max_px);
+  b.loss_ws = c.take(iters ? pl.loss_ws : 0u);
+  b.metrics_ws = c.take(pl.metrics_ws);
+  uint8_t *small = c.take(16u);
+  b.total = reinterpret_cast<uint64_t *>(small);
+  b.status = small ? reinterpret_cast<uint32_t *>(small + 8u) : nullptr;
+  b.skipped = small ? reinterpret_cast<uint32_t *>(small + 12u) : nullptr;
+  b.loss = c.take<double>(24u * iters);
+  b.metrics = c.take<spz_amd_image_metrics>(2u * nv * sizeof(spz_amd_image_metrics));
+  b.backward_ws = c.take(!iters          ? 0u
+                         : pl.any_depth ? spz_amd_render_depth_backward_workspace_bytes(pl.cap_n)
+                                        : spz_amd_render_backward_workspace_bytes(pl.cap_n));
+  b.depth = c.take<float>(8u * depth_px);
+  b.gdepth = c.take<float>(4u * depth_px);
+  b.depth_ws = c.take(pl.depth_ws);
+  b.dloss = c.take<double>(pl.any_depth ? 16u * iters : 0u);
+  b.derr = c.take<double>(pl.any_depth ? 32u * nv : 0u);
+  b.alt.p = c.cloud(b.count, pl.densify);
+  b.alt.m = c.cloud(b.count, pl.densify);
+  b.alt.v = c.cloud(b.count, pl.densify);
+  const uint64_t stats_at = c.o.off;
+  b.accum = c.take<float>(cap * 4u);
+  b.denom = c.take<uint32_t>(cap * 4u);
+  b.stats_bytes = c.o.off - stats_at;
+  b.action = c.take(cap);
+  b.parent = c.take<uint32_t>(cap * 4u);
+  b.child = c.take(cap);
+  b.origin[0] = c.take<uint32_t>(cap * 4u);
+  b.origin[1] = c.take<uint32_t>(cap * 4u);
+  b.rg = c.take<float>(cap * 36u);
+  b.counts = c.take<uint64_t>(pl.densify ? 64u : 0u);
+  b.plan_ws = c.take(pl.densify ? spz_amd_densify_plan_workspace_bytes(pl.cap_n) : 0u);
+  b.bytes = c.o.off;
+  return b;
+}
+
+spz_amd_cloud_in as_input(const spz_amd_cloud_grads &c) {
+  return spz_amd_cloud_in{c.positions, c.scales, c.rotations, c.alphas, c.colors, c.sh};
+}
+
+// One run of the loop (DESIGN §8 "Refine", "Densify", "Fit", "Depth fit"): the result, the buffers, and what changes
+// from step to step.  Every function enqueues on the result's stream; the four that wait for it say so.
+struct RefineRun {
+  const RefineRequest &rq;
+  const RefinePlan &pl;
+  const RefineOutputs &out;
+  PackedResult *c;
+  RefineBuffers b;
+  uint64_t ws_cap = 0, total = 0;  // the render workspace's size and the last prepared view's pair count
+  uint64_t n_cur = 0;              // the cloud's count now
+  spz_amd_cloud_in cloud = {};     // b.cs.p, as the render reads it
+  const uint32_t *origin_cur = nullptr;  // NULL: no round yet, the identity
   std::vector<spz_amd_densify_round> rounds;
-  auto *d_image = reinterpret_cast<float *>(raw + o_image);
-  auto *d_grad = reinterpret_cast<float *>(raw + o_grad);
-  auto *d_total = reinterpret_cast<uint64_t *>(raw + o_small);
-  auto *d_status = reinterpret_cast<uint32_t *>(raw + o_small + 8u);
-  auto *d_skipped = reinterpret_cast<uint32_t *>(raw + o_small + 12u);
-  auto *d_loss = reinterpret_cast<double *>(raw + o_loss);
-  auto *d_metrics = reinterpret_cast<spz_amd_image_metrics *>(raw + o_metrics);
-  auto target = [&](int v) {
-    return photo ? photo->d_targets[v] : reinterpret_cast<const float *>(raw + target_off[(size_t)v]);
-  };
-  auto weight = [&](int v) { return photo && photo->d_weights ? photo->d_weights[v] : nullptr; };
-  auto depth_map = [&](int v) { return any_depth ? photo->d_depths[v] : nullptr; };
-  auto *d_depth = reinterpret_cast<float *>(raw + o_depth);
-  auto *d_gdepth = reinterpret_cast<float *>(raw + o_gdepth);
-  auto *d_dloss = reinterpret_cast<double *>(raw + o_dloss);
-  auto *d_derr = reinterpret_cast<double *>(raw + o_derr);
-  // view v's exposure at d_exposure + 12 v, its moments 12 V and 24 V doubles on, the gradient after them all
-  auto *d_exposure = reinterpret_cast<double *>(raw + o_exposure);
-  double *d_exposure_grad = d_exposure + 36u * (size_t)num_views;
-  std::vector<double> exposures(12u * (size_t)num_views, 0.0);
-  for (int v = 0; v < num_views; ++v) exposures[12u * (size_t)v] = exposures[12u * (size_t)v + 5u] = exposures[12u * (size_t)v + 10u] = 1.0;
-  std::vector<int> visits((size_t)num_views, 0);
-  auto fail = [&](int v, int r) {
-    if (h_bad_view) *h_bad_view = v;
-    return r;
-  };
-  SPZ_HIP_TRY(hipMemsetAsync(d_skipped, 0, 4, c->st));
+  std::vector<double> exposures;  // the host's copy: the identity until the loop has fitted them
+  std::vector<int> visits;        // the exposure steps a view has had
 
-  // the output begins as A's bytes
-  SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->out_block), lay_a.total_bytes));
-  SPZ_HIP_TRY(hipMemcpyAsync(c->out_block, d_stream_a, lay_a.total_bytes, hipMemcpyDeviceToDevice, c->st));
-  c->out = c->out_block;
-  c->out_bytes = lay_a.total_bytes;
-
-  // targets and the "before" metrics
-  uint64_t cap = 0, total = 0;
-  const RenderSource src_a = packed_render_source(d_stream_a, size_a, hdr_a);
-  auto render = [&](const RenderSource &src, const spz_amd_render_params *p, float *d_out) {
-    return render_view(&c->scratch, &cap, src, p, d_total, d_status, d_out, c->st, &total);
-  };
-  // render_view with the depth blend for the second stage: the same image, and d_depth
-  auto render_with_depth = [&](const RenderSource &src, const spz_amd_render_params *p, float *d_out) {
-    const int r = prepare_view(&c->scratch, &cap, src, p, d_total, c->st, &total);
-    if (r != SPZ_AMD_OK) return r;
-    return spz_amd_render_depth_device(src.n, p, total, d_out, d_depth, nullptr, d_status, c->scratch, c->st);
-  };
-  // view v's depth error (L and W_v, scale 1) of the depth render in d_image and d_depth, into slot `which` (0: A, 1:
-  // the output stream)
-  auto depth_error = [&](int v, int which) {
-    const spz_amd_render_params &p = views[v];
-    return spz_amd_depth_loss_device(d_depth, d_image, depth_map(v), weight(v), (int)p.width, (int)p.height,
-                                     photo->depth->kind, photo->depth->min_alpha, 1.0,
-                                     d_derr + 2u * (2u * (size_t)v + (size_t)which), d_gdepth, nullptr, raw + o_dws,
-                                     c->st);
-  };
-  for (int v = 0; v < num_views; ++v) {
-    const spz_amd_render_params &p = views[v];
-    if (photo == nullptr) {
-      const RenderSource src_b = packed_render_source(d_stream_b, size_b, hdr_b);
-      rc = render(src_b, &p, reinterpret_cast<float *>(raw + target_off[(size_t)v]));
-      if (rc != SPZ_AMD_OK) return fail(v, rc);
-    }
-    rc = depth_map(v) ? render_with_depth(src_a, &p, d_image) : render(src_a, &p, d_image);
-    if (rc != SPZ_AMD_OK) return fail(v, rc);
-    rc = spz_amd_image_metrics_device(d_image, 4, target(v), tch, (int)p.width, (int)p.height, d_metrics + v, nullptr,
-                                      raw + o_mws, c->st);
-    if (rc != SPZ_AMD_OK) return fail(v, rc);
-    if (depth_map(v)) {
-      rc = depth_error(v, 0);
-      if (rc != SPZ_AMD_OK) return fail(v, rc);
+  RefineRun(const RefineRequest &rq_, const RefinePlan &pl_, const RefineOutputs &out_, PackedResult *c_)
+      : rq(rq_), pl(pl_), out(out_), c(c_), n_cur(pl_.n), exposures(12u * (size_t)rq_.num_views, 0.0),
+        visits((size_t)rq_.num_views, 0) {
+    for (size_t v = 0; v < (size_t)rq.num_views; ++v) {
+      exposures[12u * v] = exposures[12u * v + 5u] = exposures[12u * v + 10u] = 1.0;
     }
   }
-  if (fit) {
-    SPZ_HIP_TRY(hipMemsetAsync(d_exposure, 0, 3u * 96u * (size_t)num_views + 96u, c->st));
-    SPZ_HIP_TRY(hipMemcpyAsync(d_exposure, exposures.data(), 96u * (size_t)num_views, hipMemcpyHostToDevice, c->st));
-  }
-  SPZ_HIP_TRY(hipStreamSynchronize(c->st));
-  const double before_ms = ms_since(t0);
 
-  // the iterations
-  if (iters > 0) {
-    const spz_amd_cloud_out dec = {cs.p.positions, cs.p.scales, cs.p.rotations, cs.p.alphas, cs.p.colors, cs.p.sh};
-    rc = spz_amd_decode_device(d_stream_a, size_a, hdr_a, coord, &dec, c->st);
+  const spz_amd_render_params &view(int v) const { return rq.views[v]; }
+  const float *target(int v) const { return rq.given ? rq.targets[v] : b.rendered[(size_t)v]; }
+  const float *weight(int v) const { return rq.given && rq.weights ? rq.weights[v] : nullptr; }
+  const float *depth_map(int v) const { return pl.any_depth ? rq.depths[v] : nullptr; }
+  int fail(int v, int rc) const {
+    if (out.h_bad_view) *out.h_bad_view = v;
+    return rc;
+  }
+
+  // The block and, as A's bytes to begin with, the output.
+  int allocate() {
+    SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->block), layout(rq, pl, nullptr).bytes));
+    b = layout(rq, pl, c->block);
+    SPZ_HIP_TRY(hipMemsetAsync(b.skipped, 0, 4, c->st));
+    SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->out_block), pl.lay_a.total_bytes));
+    SPZ_HIP_TRY(hipMemcpyAsync(c->out_block, rq.d_stream_a, pl.lay_a.total_bytes, hipMemcpyDeviceToDevice, c->st));
+    c->out = c->out_block;
+    c->out_bytes = pl.lay_a.total_bytes;
+    return SPZ_AMD_OK;
+  }
+
+  // View v of `src` into d_out; with_depth: the depth blend for the second stage: the same image, and b.depth.
+  int render(const RenderSource &src, int v, bool with_depth, float *d_out) {
+    if (!with_depth) return render_view(&c->scratch, &ws_cap, src, &view(v), b.total, b.status, d_out, c->st, &total);
+    const int rc = prepare_view(&c->scratch, &ws_cap, src, &view(v), b.total, c->st, &total);
     if (rc != SPZ_AMD_OK) return rc;
-    if (cs.moments_bytes) SPZ_HIP_TRY(hipMemsetAsync(raw + cs.moments_off, 0, cs.moments_bytes, c->st));
-    spz_amd_cloud_in cloud = {cs.p.positions, cs.p.scales, cs.p.rotations, cs.p.alphas, cs.p.colors, cs.p.sh};
-    if (dn && cap_n) SPZ_HIP_TRY(hipMemsetAsync(raw + o_accum, 0, o_action - o_accum, c->st));  // accum and denom
-    RenderSource src_f;
-    src_f.cloud = &cloud;
-    src_f.n = n;
-    src_f.sh_degree = deg;
-    src_f.antialiased = aa;
-    for (int i = 0; i < iters; ++i) {
-      const int v = i % num_views;
-      const spz_amd_render_params &p = views[v];
-      const bool with_depth = depth_map(v) != nullptr && photo->depth->weight > 0.0;
-      rc = with_depth ? render_with_depth(src_f, &p, d_image) : render(src_f, &p, d_image);
-      if (rc != SPZ_AMD_OK) return fail(v, rc);
-      if (photo != nullptr) {
-        rc = photo_loss_enqueue(d_image, 4, target(v), tch, weight(v), fit ? d_exposure + 12u * (size_t)v : nullptr,
-                                (int)p.width, (int)p.height, options->lambda_dssim, d_loss + 3 * (size_t)i, d_grad,
-                                fit ? d_exposure_grad : nullptr, raw + o_lws, c->st);
-      } else {
-        rc = spz_amd_image_loss_device(d_image, 4, target(v), 4, (int)p.width, (int)p.height, options->lambda_dssim,
-                                       d_loss + 3 * (size_t)i, d_grad, raw + o_lws, c->st);
-      }
-      if (rc != SPZ_AMD_OK) return fail(v, rc);
-      if (fit) {  // the exposure's own step: the image gradient above was formed with the values before it
-        double *e = d_exposure + 12u * (size_t)v;
-        rc = photo_exposure_adam_enqueue(e, d_exposure_grad, e + 12u * (size_t)num_views, e + 24u * (size_t)num_views,
-                                         ++visits[(size_t)v], photo->options->lr_exposure, options->beta1,
-                                         options->beta2, options->eps, c->st);
-        if (rc != SPZ_AMD_OK) return rc;
-      }
-      const bool gather_stats = dn && i >= densify->from_iter && i < densify->until_iter;
-      if (with_depth) {  // the depth term: its gradient to alpha joins the photo loss's d_grad
-        rc = spz_amd_depth_loss_device(d_depth, d_image, depth_map(v), weight(v), (int)p.width, (int)p.height,
-                                       photo->depth->kind, photo->depth->min_alpha, photo->depth->weight,
-                                       d_dloss + 2 * (size_t)i, d_gdepth, d_grad, raw + o_dws, c->st);
-        if (rc != SPZ_AMD_OK) return fail(v, rc);
-        rc = spz_amd_render_depth_backward_device(&cloud, n_cur, deg, aa, &p, total, d_grad, d_gdepth, &cs.g,
-                                                  gather_stats && n_cur ? d_rg : nullptr, nullptr, d_status, c->scratch,
-                                                  raw + o_bws, c->st);
-      } else {
-        rc = spz_amd_render_backward_device(&cloud, n_cur, deg, aa, &p, total, d_image, d_grad, &cs.g,
-                                            gather_stats && n_cur ? d_rg : nullptr, d_status, c->scratch, raw + o_bws,
-                                            c->st);
-      }
-      if (rc != SPZ_AMD_OK) return fail(v, rc);
-      if (gather_stats && n_cur) {  // the records are the front of the render workspace
-        rc = spz_amd_densify_accumulate_device(reinterpret_cast<const spz_amd_render_record *>(align_ws(c->scratch)),
-                                               d_rg, n_cur, p.width, p.height, d_accum, d_denom, c->st);
-        if (rc != SPZ_AMD_OK) return rc;
-      }
-      if (n_cur) {
-        spz_amd_adam_scalars sc;
-        rc = spz_amd_adam_scalars_of(i + 1, options->lr, options->beta1, options->beta2, options->eps, &sc);
-        if (rc != SPZ_AMD_OK) return rc;
-        rc = adam_enqueue(&cs.p, &cs.g, &cs.m, &cs.v, n_cur, deg, mask, sc, d_skipped, c->st);
-        if (rc != SPZ_AMD_OK) return rc;
-      }
-      if (gather_stats && (i + 1) % densify->interval == 0) {
-        uint64_t counts[5] = {};
-        rc = spz_amd_densify_plan_host(d_accum, d_denom, cs.p.scales, cs.p.alphas, n_cur, &lim, cap_n, cap_n,
-                                       raw + o_action, d_parent, raw + o_child, d_counts, raw + o_pws, counts, c->st);
-        if (rc != SPZ_AMD_OK) return rc;
-        const uint64_t n_new = counts[0];
-        if (n_new > cap_n) return SPZ_AMD_ERR_CAPACITY;  // (the plan's bound says it cannot be)
-        rc = spz_amd_densify_apply_device(&cs.p, &cs.m, &cs.v, &alt.p, &alt.m, &alt.v, d_parent, raw + o_child, n_cur,
-                                          n_new, cap_n, deg, densify->seed, (uint32_t)rounds.size(), c->st);
-        if (rc != SPZ_AMD_OK) return rc;
-        uint32_t *origin_next = d_origin[origin_cur == d_origin[0] ? 1 : 0];
-        rc = densify_gather_u32(origin_cur, d_parent, n_cur, n_new, origin_next, c->st);
-        if (rc != SPZ_AMD_OK) return rc;
-        origin_cur = origin_next;
-        std::swap(cs.p, alt.p);
-        std::swap(cs.m, alt.m);
-        std::swap(cs.v, alt.v);
-        cloud = spz_amd_cloud_in{cs.p.positions, cs.p.scales, cs.p.rotations, cs.p.alphas, cs.p.colors, cs.p.sh};
-        if (cap_n) SPZ_HIP_TRY(hipMemsetAsync(raw + o_accum, 0, o_action - o_accum, c->st));
-        rounds.push_back(spz_amd_densify_round{i, 0, counts[1], counts[2], counts[3], counts[4], n_new});
-        n_cur = n_new;
-        src_f.n = n_cur;
-      }
-      if (dn && densify->opacity_reset_interval > 0 && (i + 1) % densify->opacity_reset_interval == 0) {
-        rc = spz_amd_densify_reset_opacity_device(cs.p.alphas, cs.m.alphas, cs.v.alphas, n_cur, c->st);
-        if (rc != SPZ_AMD_OK) return rc;
-      }
+    return spz_amd_render_depth_device(src.n, &view(v), total, d_out, b.depth, nullptr, b.status, c->scratch, c->st);
+  }
+
+  // Depth: view v's depth loss of the depth render in b.image and b.depth against its map (L and W_v into d_out), its
+  // gradient to the depth channel into b.gdepth and, times `scale`, to alpha added into d_grad_image (may be NULL).
+  int depth_loss(int v, double scale, double *d_out, float *d_grad_image) {
+    return spz_amd_depth_loss_device(b.depth, b.image, depth_map(v), weight(v), (int)view(v).width, (int)view(v).height,
+                                     rq.depth->kind, rq.depth->min_alpha, scale, d_out, b.gdepth, d_grad_image,
+                                     b.depth_ws, c->st);
+  }
+  // The depth term of iteration i, joining the photo loss's gradient; the depth error of A (slot 0) or the output (1).
+  int depth_term(int i, int v) { return depth_loss(v, rq.depth->weight, b.dloss + 2 * (size_t)i, b.grad); }
+  int depth_error(int v, int slot) { return depth_loss(v, 1.0, b.derr + 4u * (size_t)v + 2u * (size_t)slot, nullptr); }
+
+  // "before" (slot 0: src is A) and "after" (slot 1: src is the output stream, judged through the exposure fitted for
+  // the photograph): view v's metrics and, with a depth map, its depth error.  The depth error of the output goes in
+  // front of the exposure, which rewrites the image in place; A's has nothing to wait for and follows the metrics.
+  int measure(int v, const RenderSource &src, int slot) {
+    const bool z = depth_map(v) != nullptr;
+    const int w = (int)view(v).width, h = (int)view(v).height;
+    int rc = render(src, v, z, b.image);
+    if (rc == SPZ_AMD_OK && z && slot == 1) rc = depth_error(v, 1);
+    if (rc == SPZ_AMD_OK && pl.fit && slot == 1) {
+      rc = spz_amd_image_exposure_device(b.image, 4, exposures.data() + 12u * (size_t)v, w, h, b.image, c->st);
     }
-    if (dn) {
-      // the output at the new count: A's bytes gathered through the origin map, the header's count replaced
+    if (rc == SPZ_AMD_OK) {
+      spz_amd_image_metrics *d_out = b.metrics + (size_t)slot * (size_t)rq.num_views + v;
+      rc = spz_amd_image_metrics_device(b.image, 4, target(v), pl.tch, w, h, d_out, nullptr, b.metrics_ws, c->st);
+    }
+    if (rc == SPZ_AMD_OK && z && slot == 0) rc = depth_error(v, 0);
+    return rc;
+  }
+
+  // The targets where they are rendered, "before", and the exposures at the identity with zero moments.  Waits.
+  int before() {
+    const RenderSource src_a = packed_render_source(rq.d_stream_a, rq.size_a, rq.hdr_a);
+    for (int v = 0; v < rq.num_views; ++v) {
+      int rc = SPZ_AMD_OK;
+      if (!rq.given) {
+        const RenderSource src_b = packed_render_source(rq.d_stream_b, rq.size_b, rq.hdr_b);
+        rc = render(src_b, v, false, b.rendered[(size_t)v]);
+      }
+      if (rc == SPZ_AMD_OK) rc = measure(v, src_a, 0);
+      if (rc != SPZ_AMD_OK) return fail(v, rc);
+    }
+    if (pl.fit) {
+      const size_t nv = (size_t)rq.num_views;
+      SPZ_HIP_TRY(hipMemsetAsync(b.exposure, 0, 3u * 96u * nv + 96u, c->st));
+      SPZ_HIP_TRY(hipMemcpyAsync(b.exposure, exposures.data(), 96u * nv, hipMemcpyHostToDevice, c->st));
+    }
+    SPZ_HIP_TRY(hipStreamSynchronize(c->st));
+    return SPZ_AMD_OK;
+  }
+
+  // A decoded into the float cloud in the views' frame; zero moments and statistics.
+  int decode() {
+    const spz_amd_cloud_grads &p = b.cs.p;
+    const spz_amd_cloud_out dec = {p.positions, p.scales, p.rotations, p.alphas, p.colors, p.sh};
+    const int rc = spz_amd_decode_device(rq.d_stream_a, rq.size_a, rq.hdr_a, pl.coord, &dec, c->st);
+    if (rc != SPZ_AMD_OK) return rc;
+    if (b.moments_bytes) SPZ_HIP_TRY(hipMemsetAsync(b.moments, 0, b.moments_bytes, c->st));
+    cloud = as_input(b.cs.p);
+    if (pl.densify && pl.cap_n) SPZ_HIP_TRY(hipMemsetAsync(b.accum, 0, b.stats_bytes, c->st));
+    return SPZ_AMD_OK;
+  }
+
+  int forward(int v, bool with_depth) {
+    RenderSource src;
+    src.cloud = &cloud;
+    src.n = n_cur;
+    src.sh_degree = pl.deg;
+    src.antialiased = pl.aa;
+    return render(src, v, with_depth, b.image);
+  }
+
+  // Iteration i's loss of the render against view v's target (L, l1, ssim into b.loss) and its gradient into b.grad.
+  // Photo: given targets take the photo loss of spz_photo.hip, with the view's weights and, when they are fitted, its
+  // exposure read from device memory and that exposure's gradient.
+  int loss(int i, int v) {
+    const int w = (int)view(v).width, h = (int)view(v).height;
+    double *d_loss = b.loss + 3 * (size_t)i;
+    if (!rq.given) {
+      return spz_amd_image_loss_device(b.image, 4, target(v), 4, w, h, rq.options->lambda_dssim, d_loss, b.grad,
+                                       b.loss_ws, c->st);
+    }
+    return photo_loss_enqueue(b.image, 4, target(v), pl.tch, weight(v), pl.fit ? b.exposure + 12u * (size_t)v : nullptr,
+                              w, h, rq.options->lambda_dssim, d_loss, b.grad, pl.fit ? b.exposure_grad : nullptr,
+                              b.loss_ws, c->st);
+  }
+
+  // Exposure: view v's own Adam step on the device.  The image gradient was formed with the values before it.
+  int exposure_step(int v) {
+    const size_t nv = (size_t)rq.num_views;
+    double *e = b.exposure + 12u * (size_t)v;
+    return photo_exposure_adam_enqueue(e, b.exposure_grad, e + 12u * nv, e + 24u * nv, ++visits[(size_t)v],
+                                       rq.photo->lr_exposure, rq.options->beta1, rq.options->beta2, rq.options->eps,
+                                       c->st);
+  }
+
+  // The gradients of the cloud from b.grad (and b.gdepth); with_stats: also the record gradients densify accumulates.
+  int backward(int v, bool with_depth, bool with_stats) {
+    float *d_rg = with_stats ? b.rg : nullptr;
+    if (with_depth) {
+      return spz_amd_render_depth_backward_device(&cloud, n_cur, pl.deg, pl.aa, &view(v), total, b.grad, b.gdepth, &b.cs.g,
+                                                  d_rg, nullptr, b.status, c->scratch, b.backward_ws, c->st);
+    }
+    return spz_amd_render_backward_device(&cloud, n_cur, pl.deg, pl.aa, &view(v), total, b.image, b.grad, &b.cs.g, d_rg,
+                                          b.status, c->scratch, b.backward_ws, c->st);
+  }
+
+  // Densify's statistics of view v.  The records are the front of the render workspace.
+  int accumulate(int v) {
+    return spz_amd_densify_accumulate_device(reinterpret_cast<const spz_amd_render_record *>(align_ws(c->scratch)), b.rg,
+                                             n_cur, view(v).width, view(v).height, b.accum, b.denom, c->st);
+  }
+
+  int adam(int i) {
+    spz_amd_adam_scalars sc;
+    const spz_amd_refine_options &o = *rq.options;
+    const int rc = spz_amd_adam_scalars_of(i + 1, o.lr, o.beta1, o.beta2, o.eps, &sc);
+    if (rc != SPZ_AMD_OK) return rc;
+    return adam_enqueue(&b.cs.p, &b.cs.g, &b.cs.m, &b.cs.v, n_cur, pl.deg, pl.mask, sc, b.skipped, c->st);
+  }
+
+  // Densify: one round after iteration i.  The plan (which waits for its counts), the apply into the other set of
+  // parameters and moments, the origin map through the plan's parents, fresh statistics.
+  int densify_round(int i) {
+    uint64_t counts[5] = {};
+    int rc = spz_amd_densify_plan_host(b.accum, b.denom, b.cs.p.scales, b.cs.p.alphas, n_cur, &pl.lim, pl.cap_n, pl.cap_n,
+                                       b.action, b.parent, b.child, b.counts, b.plan_ws, counts, c->st);
+    if (rc != SPZ_AMD_OK) return rc;
+    const uint64_t n_new = counts[0];
+    if (n_new > pl.cap_n) return SPZ_AMD_ERR_CAPACITY;  // (the plan's bound says it cannot be)
+    rc = spz_amd_densify_apply_device(&b.cs.p, &b.cs.m, &b.cs.v, &b.alt.p, &b.alt.m, &b.alt.v, b.parent, b.child, n_cur,
+                                      n_new, pl.cap_n, pl.deg, rq.densify->seed, (uint32_t)rounds.size(), c->st);
+    if (rc != SPZ_AMD_OK) return rc;
+    uint32_t *origin_next = b.origin[origin_cur == b.origin[0] ? 1 : 0];
+    rc = densify_gather_u32(origin_cur, b.parent, n_cur, n_new, origin_next, c->st);
+    if (rc != SPZ_AMD_OK) return rc;
+    origin_cur = origin_next;
+    std::swap(b.cs.p, b.alt.p);
+    std::swap(b.cs.m, b.alt.m);
+    std::swap(b.cs.v, b.alt.v);
+    cloud = as_input(b.cs.p);
+    if (pl.cap_n) SPZ_HIP_TRY(hipMemsetAsync(b.accum, 0, b.stats_bytes, c->st));
+    rounds.push_back(spz_amd_densify_round{i, 0, counts[1], counts[2], counts[3], counts[4], n_new});
+    n_cur = n_new;
+    return SPZ_AMD_OK;
+  }
+
+  int reset_opacity() {
+    return spz_amd_densify_reset_opacity_device(b.cs.p.alphas, b.cs.m.alphas, b.cs.v.alphas, n_cur, c->st);
+  }
+
+  // Iteration i, as DESIGN §8 has it.
+  int iterate(int i) {
+    const int v = i % rq.num_views;
+    const spz_amd_densify_options *d = rq.densify;
+    const bool with_depth = depth_map(v) != nullptr && rq.depth->weight > 0.0;
+    const bool gather = pl.densify && i >= d->from_iter && i < d->until_iter;
+    int rc = forward(v, with_depth);
+    if (rc == SPZ_AMD_OK) rc = loss(i, v);
+    if (rc != SPZ_AMD_OK) return fail(v, rc);
+    if (pl.fit) rc = exposure_step(v);
+    if (rc != SPZ_AMD_OK) return rc;
+    if (with_depth) rc = depth_term(i, v);
+    if (rc == SPZ_AMD_OK) rc = backward(v, with_depth, gather && n_cur);
+    if (rc != SPZ_AMD_OK) return fail(v, rc);
+    if (gather && n_cur) rc = accumulate(v);
+    if (rc == SPZ_AMD_OK && n_cur) rc = adam(i);
+    if (rc == SPZ_AMD_OK && gather && (i + 1) % d->interval == 0) rc = densify_round(i);
+    if (rc == SPZ_AMD_OK && pl.densify && d->opacity_reset_interval > 0 && (i + 1) % d->opacity_reset_interval == 0) {
+      rc = reset_opacity();
+    }
+    return rc;
+  }
+
+  // The output stream: after a round A's bytes gathered through the origin map at the new count (waits, to free the
+  // copy of A), then the trained sections encoded over it, from the views' frame back to the file's.
+  int write_output() {
+    if (origin_cur != nullptr) {
       spz_amd_layout lay_o;
-      rc = spz_amd_stream_layout(n_cur, deg, (int)hdr_a->version, &lay_o);
+      int rc = spz_amd_stream_layout(n_cur, pl.deg, (int)rq.hdr_a->version, &lay_o);
       if (rc != SPZ_AMD_OK) return rc;
-      if (origin_cur != nullptr) {
-        SPZ_HIP_TRY(hipStreamSynchronize(c->st));
-        SPZ_HIP_TRY(hipFree(c->out_block));
-        c->out_block = nullptr;
-        c->out = nullptr;
-        SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->out_block), lay_o.total_bytes));
-        c->out = c->out_block;
-        c->out_bytes = lay_o.total_bytes;
-        rc = spz_amd_subset_device(d_stream_a, size_a, hdr_a, origin_cur, n_cur, -1, c->out_block, lay_o.total_bytes,
-                                   c->st);
-        if (rc != SPZ_AMD_OK) return rc;
-      }
+      SPZ_HIP_TRY(hipStreamSynchronize(c->st));
+      SPZ_HIP_TRY(hipFree(c->out_block));
+      c->out_block = nullptr;
+      c->out = nullptr;
+      SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->out_block), lay_o.total_bytes));
+      c->out = c->out_block;
+      c->out_bytes = lay_o.total_bytes;
+      rc = spz_amd_subset_device(rq.d_stream_a, rq.size_a, rq.hdr_a, origin_cur, n_cur, -1, c->out_block,
+                                 lay_o.total_bytes, c->st);
+      if (rc != SPZ_AMD_OK) return rc;
     }
-    // the trained sections over the copy of A's bytes, from the views' frame back to the file's
     const unsigned sec_of[6] = {1u << SPZ_AMD_SEC_POSITIONS, 1u << SPZ_AMD_SEC_SCALES, 1u << SPZ_AMD_SEC_ROTATIONS,
                                 1u << SPZ_AMD_SEC_ALPHAS,    1u << SPZ_AMD_SEC_COLORS, 1u << SPZ_AMD_SEC_SH};
     unsigned sections = 0;
-    for (int k = 0; k < 6; ++k) sections |= ((mask >> k) & 1u) ? sec_of[k] : 0u;
-    if (n_cur && sections) {
-      rc = spz_amd_encode_shard_sections_device(&cloud, 0, n_cur, n_cur, deg, aa, coord, (int)hdr_a->version, 0, sections,
-                                                c->out_block, c->out_bytes, c->st);
-      if (rc != SPZ_AMD_OK) return rc;
-    }
+    for (int k = 0; k < 6; ++k) sections |= ((pl.mask >> k) & 1u) ? sec_of[k] : 0u;
+    if (n_cur == 0 || sections == 0) return SPZ_AMD_OK;
+    return spz_amd_encode_shard_sections_device(&cloud, 0, n_cur, n_cur, pl.deg, pl.aa, pl.coord, (int)rq.hdr_a->version,
+                                                0, sections, c->out_block, c->out_bytes, c->st);
   }
-  if (fit) {
-    SPZ_HIP_TRY(hipMemcpyAsync(exposures.data(), d_exposure, 96u * (size_t)num_views, hipMemcpyDeviceToHost, c->st));
-  }
-  SPZ_HIP_TRY(hipStreamSynchronize(c->st));
-  const double loop_ms = ms_since(t0) - before_ms;
 
-  // the "after" metrics: of the output stream
-  spz_amd_header hdr_o = *hdr_a;
-  hdr_o.num_points = (uint32_t)n_cur;
-  RenderSource src_o = packed_render_source(c->out_block, c->out_bytes, &hdr_o);
-  for (int v = 0; v < num_views; ++v) {
-    const spz_amd_render_params &p = views[v];
-    if (iters == 0) break;
-    rc = depth_map(v) ? render_with_depth(src_o, &p, d_image) : render(src_o, &p, d_image);
-    if (rc != SPZ_AMD_OK) return fail(v, rc);
-    if (depth_map(v)) {
-      rc = depth_error(v, 1);
+  // The iterations and the output, and the fitted exposures to the host.  Waits.
+  int loop() {
+    int rc = pl.iters > 0 ? decode() : SPZ_AMD_OK;
+    for (int i = 0; rc == SPZ_AMD_OK && i < pl.iters; ++i) rc = iterate(i);
+    if (rc == SPZ_AMD_OK && pl.iters > 0) rc = write_output();
+    if (rc != SPZ_AMD_OK) return rc;
+    if (pl.fit) {
+      SPZ_HIP_TRY(hipMemcpyAsync(exposures.data(), b.exposure, 96u * (size_t)rq.num_views, hipMemcpyDeviceToHost, c->st));
+    }
+    SPZ_HIP_TRY(hipStreamSynchronize(c->st));
+    return SPZ_AMD_OK;
+  }
+
+  // "after": of the output stream.  Without an iteration it is "before".
+  int after() {
+    spz_amd_header hdr_o = *rq.hdr_a;
+    hdr_o.num_points = (uint32_t)n_cur;
+    const RenderSource src_o = packed_render_source(c->out_block, c->out_bytes, &hdr_o);
+    for (int v = 0; pl.iters > 0 && v < rq.num_views; ++v) {
+      const int rc = measure(v, src_o, 1);
       if (rc != SPZ_AMD_OK) return fail(v, rc);
     }
-    if (fit) {  // the file is judged through the exposure fitted for this photograph
-      rc = spz_amd_image_exposure_device(d_image, 4, exposures.data() + 12u * (size_t)v, (int)p.width, (int)p.height,
-                                         d_image, c->st);
-      if (rc != SPZ_AMD_OK) return fail(v, rc);
+    return SPZ_AMD_OK;
+  }
+
+  // Every result to where the caller wants it (all but the three laps and ctx).  Waits.
+  int report() {
+    const size_t nv = (size_t)rq.num_views, iters = (size_t)pl.iters;
+    if (out.h_exposures) std::memcpy(out.h_exposures, exposures.data(), 96u * nv);
+    const size_t mbytes = nv * sizeof(spz_amd_image_metrics);
+    if (out.h_before) SPZ_HIP_TRY(hipMemcpyAsync(out.h_before, b.metrics, mbytes, hipMemcpyDeviceToHost, c->st));
+    if (out.h_after) {
+      SPZ_HIP_TRY(hipMemcpyAsync(out.h_after, iters ? b.metrics + nv : b.metrics, mbytes, hipMemcpyDeviceToHost, c->st));
     }
-    rc = spz_amd_image_metrics_device(d_image, 4, target(v), tch, (int)p.width, (int)p.height,
-                                      d_metrics + num_views + v, nullptr, raw + o_mws, c->st);
-    if (rc != SPZ_AMD_OK) return fail(v, rc);
+    std::vector<double> loss3(3u * iters);
+    if (iters) SPZ_HIP_TRY(hipMemcpyAsync(loss3.data(), b.loss, 24u * iters, hipMemcpyDeviceToHost, c->st));
+    std::vector<double> dloss2(pl.any_depth ? 2u * iters : 0u), derr4(pl.any_depth ? 4u * nv : 0u);
+    if (pl.any_depth) {
+      if (iters) SPZ_HIP_TRY(hipMemcpyAsync(dloss2.data(), b.dloss, 16u * iters, hipMemcpyDeviceToHost, c->st));
+      SPZ_HIP_TRY(hipMemcpyAsync(derr4.data(), b.derr, 32u * nv, hipMemcpyDeviceToHost, c->st));
+    }
+    uint32_t skipped = 0;
+    SPZ_HIP_TRY(hipMemcpyAsync(&skipped, b.skipped, 4, hipMemcpyDeviceToHost, c->st));
+    if (out.h_origin && origin_cur && n_cur) {
+      SPZ_HIP_TRY(hipMemcpyAsync(out.h_origin, origin_cur, 4u * n_cur, hipMemcpyDeviceToHost, c->st));
+    }
+    SPZ_HIP_TRY(hipStreamSynchronize(c->st));
+    for (uint64_t k = 0; out.h_origin && !origin_cur && k < n_cur; ++k) out.h_origin[k] = (uint32_t)k;
+    if (out.h_num_points) *out.h_num_points = n_cur;
+    if (out.h_num_rounds) *out.h_num_rounds = (int)rounds.size();
+    for (size_t k = 0; out.h_rounds && k < rounds.size() && (int)k < out.rounds_capacity; ++k) out.h_rounds[k] = rounds[k];
+    for (size_t i = 0; i < iters; ++i) {  // the history is the loss that was minimised: with the depth term where it was
+      const bool with_depth = depth_map((int)(i % nv)) != nullptr && rq.depth->weight > 0.0;
+      const double l_depth = with_depth ? dloss2[2u * i] : 0.0;
+      out.h_history[i] = with_depth ? loss3[3u * i] + rq.depth->weight * l_depth : loss3[3u * i];
+      if (out.h_depth_history) out.h_depth_history[i] = l_depth;
+    }
+    for (size_t v = 0; out.h_depth_error && v < nv; ++v) {
+      const bool has = depth_map((int)v) != nullptr;
+      out.h_depth_error[2 * v] = has ? derr4[4u * v] : -1.0;
+      out.h_depth_error[2 * v + 1] = has ? derr4[4u * v + (iters ? 2u : 0u)] : -1.0;
+    }
+    if (out.h_skipped) *out.h_skipped = skipped;
+    return SPZ_AMD_OK;
   }
-  if (photo != nullptr && photo->h_exposures != nullptr) {
-    std::memcpy(photo->h_exposures, exposures.data(), 96u * (size_t)num_views);
+};
+
+// A planned request on its device: the three laps of h_ms are "before", the loop, and "after" with the report.
+int refine_run(const RefineRequest &rq, const RefinePlan &pl, const RefineOutputs &out) {
+  DeviceGuard guard;
+  int rc = guard.enter(rq.device);
+  if (rc != SPZ_AMD_OK) return rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  PackedResultPtr c;
+  rc = packed_result_open(rq.device, &c);
+  if (rc != SPZ_AMD_OK) return rc;
+  RefineRun run(rq, pl, out, c.get());
+  rc = run.allocate();
+  if (rc == SPZ_AMD_OK) rc = run.before();
+  if (rc != SPZ_AMD_OK) return rc;
+  const double before_ms = ms_since(t0);
+  rc = run.loop();
+  if (rc != SPZ_AMD_OK) return rc;
+  const double loop_ms = ms_since(t0) - before_ms;
+  rc = run.after();
+  if (rc == SPZ_AMD_OK) rc = run.report();
+  if (rc != SPZ_AMD_OK) return rc;
+  if (out.h_ms) {
+    out.h_ms[0] = (float)before_ms;
+    out.h_ms[1] = (float)loop_ms;
+    out.h_ms[2] = (float)(ms_since(t0) - before_ms - loop_ms);
   }
-  const size_t mbytes = (size_t)num_views * sizeof(spz_amd_image_metrics);
-  if (h_before) SPZ_HIP_TRY(hipMemcpyAsync(h_before, d_metrics, mbytes, hipMemcpyDeviceToHost, c->st));
-  if (h_after) {
-    SPZ_HIP_TRY(hipMemcpyAsync(h_after, iters ? d_metrics + num_views : d_metrics, mbytes, hipMemcpyDeviceToHost, c->st));
-  }
-  std::vector<double> loss3(3u * (size_t)iters);
-  if (iters) SPZ_HIP_TRY(hipMemcpyAsync(loss3.data(), d_loss, 24u * (size_t)iters, hipMemcpyDeviceToHost, c->st));
-  std::vector<double> dloss2(any_depth ? 2u * (size_t)iters : 0u), derr4(any_depth ? 4u * (size_t)num_views : 0u);
-  if (any_depth) {
-    if (iters) SPZ_HIP_TRY(hipMemcpyAsync(dloss2.data(), d_dloss, 16u * (size_t)iters, hipMemcpyDeviceToHost, c->st));
-    SPZ_HIP_TRY(hipMemcpyAsync(derr4.data(), d_derr, 32u * (size_t)num_views, hipMemcpyDeviceToHost, c->st));
-  }
-  uint32_t skipped = 0;
-  SPZ_HIP_TRY(hipMemcpyAsync(&skipped, d_skipped, 4, hipMemcpyDeviceToHost, c->st));
-  if (rep.h_origin && origin_cur && n_cur) {
-    SPZ_HIP_TRY(hipMemcpyAsync(rep.h_origin, origin_cur, 4u * n_cur, hipMemcpyDeviceToHost, c->st));
-  }
-  SPZ_HIP_TRY(hipStreamSynchronize(c->st));
-  if (rep.h_origin && !origin_cur) {
-    for (uint64_t k = 0; k < n_cur; ++k) rep.h_origin[k] = (uint32_t)k;
-  }
-  if (rep.h_num_points) *rep.h_num_points = n_cur;
-  if (rep.h_num_rounds) *rep.h_num_rounds = (int)rounds.size();
-  for (size_t k = 0; rep.h_rounds && k < rounds.size() && (int)k < rep.rounds_capacity; ++k) rep.h_rounds[k] = rounds[k];
-  for (int i = 0; i < iters; ++i) {
-    const bool with_depth = depth_map(i % num_views) != nullptr && photo->depth->weight > 0.0;
-    const double l_depth = with_depth ? dloss2[2u * (size_t)i] : 0.0;
-    h_history[i] = with_depth ? loss3[3u * (size_t)i] + photo->depth->weight * l_depth : loss3[3u * (size_t)i];
-    if (photo && photo->h_depth_history) photo->h_depth_history[i] = l_depth;
-  }
-  for (int v = 0; photo && photo->h_depth_error && v < num_views; ++v) {
-    const bool has = depth_map(v) != nullptr;
-    photo->h_depth_error[2 * v] = has ? derr4[4u * (size_t)v] : -1.0;
-    photo->h_depth_error[2 * v + 1] = has ? derr4[4u * (size_t)v + (iters ? 2u : 0u)] : -1.0;
-  }
-  if (h_skipped) *h_skipped = skipped;
-  if (h_ms) {
-    h_ms[0] = (float)before_ms;
-    h_ms[1] = (float)loop_ms;
-    h_ms[2] = (float)(ms_since(t0) - before_ms - loop_ms);
-  }
-  *h_out_bytes = c->out_bytes;
   // fetch needs the output alone
   SPZ_HIP_TRY(hipFree(c->scratch));
   c->scratch = nullptr;
   SPZ_HIP_TRY(hipFree(c->block));
   c->block = nullptr;
-  *ctx = c.release();
+  *out.h_out_bytes = c->out_bytes;
+  *out.ctx = c.release();
   return SPZ_AMD_OK;
+}
+
+// Every entry's beginning: the outputs reset, the one check of the outputs themselves, the plan.
+int refine_begin(const RefineRequest &rq, const RefineOutputs &out, RefinePlan *pl) {
+  reset(out);
+  if (out.ctx == nullptr || out.h_out_bytes == nullptr) return SPZ_AMD_ERR_INVALID_ARG;
+  if (out.rounds_capacity < 0 || (out.rounds_capacity > 0 && out.h_rounds == nullptr)) return SPZ_AMD_ERR_INVALID_ARG;
+  return plan(rq, out, pl);
+}
+
+int refine_open(const RefineRequest &rq, const RefineOutputs &out) {
+  RefinePlan pl;
+  const int rc = refine_begin(rq, out, &pl);
+  return rc != SPZ_AMD_OK ? rc : refine_run(rq, pl, out);
+}
+
+// The host forms: planned (and refused) before anything is uploaded; then the images, weight maps and depth maps in one
+// block of device memory, and the same run.  The run blocks, so the block outlives it.
+int refine_host_open(RefineRequest rq, const RefineOutputs &out) {
+  RefinePlan pl;
+  rq.on_host = true;
+  int rc = refine_begin(rq, out, &pl);
+  if (rc != SPZ_AMD_OK) return rc;
+  const size_t nv = (size_t)rq.num_views;
+  const float *const *host[3] = {rq.targets, rq.weights, rq.depths};
+  std::vector<const float *> dev[3];
+  std::vector<uint64_t> at(3u * nv), bytes(3u * nv);
+  WorkspaceOffsets o;
+  for (size_t v = 0; v < nv; ++v) {
+    const uint64_t px = (uint64_t)rq.views[v].width * rq.views[v].height;
+    for (size_t k = 0; k < 3; ++k) {
+      bytes[3u * v + k] = host[k] && host[k][v] ? 4u * px * (k == 0 ? (uint64_t)rq.channels : 1u) : 0u;
+      at[3u * v + k] = o.put(bytes[3u * v + k]);
+    }
+  }
+  DeviceGuard guard;
+  rc = guard.enter(rq.device);
+  if (rc != SPZ_AMD_OK) return rc;
+  struct Block {
+    uint8_t *p = nullptr;
+    ~Block() {
+      if (p) (void)hipFree(p);
+    }
+  } block;
+  SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&block.p), o.off ? o.off : 256u));
+  for (size_t k = 0; k < 3; ++k) dev[k].assign(nv, nullptr);
+  for (size_t v = 0; v < nv; ++v) {
+    for (size_t k = 0; k < 3; ++k) {
+      if (bytes[3u * v + k] == 0) continue;
+      dev[k][v] = reinterpret_cast<const float *>(block.p + at[3u * v + k]);
+      SPZ_HIP_TRY(hipMemcpy(block.p + at[3u * v + k], host[k][v], bytes[3u * v + k], hipMemcpyHostToDevice));
+    }
+  }
+  rq.targets = dev[0].data();
+  rq.weights = rq.weights ? dev[1].data() : nullptr;
+  rq.depths = rq.depths ? dev[2].data() : nullptr;
+  rq.on_host = false;
+  return refine_run(rq, pl, out);
 }
 
 }  // namespace
@@ -758,9 +975,8 @@ int spz_amd_refine_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_
                         int device, void **ctx, uint64_t *h_out_bytes, double *h_history,
                         spz_amd_image_metrics *h_before, spz_amd_image_metrics *h_after, uint64_t *h_skipped, float *h_ms,
                         int32_t *h_bad_view) {
-  return refine_run(d_stream_a, size_a, hdr_a, d_stream_b, size_b, hdr_b, views, num_views, options, nullptr, device,
-                    ctx, h_out_bytes, h_history, h_before, h_after, h_skipped, h_ms, h_bad_view,
-                    DensifyReport{nullptr, nullptr, 0, nullptr, nullptr});
+  const RefineRequest rq = {d_stream_a, size_a, hdr_a, d_stream_b, size_b, hdr_b, views, num_views, options, nullptr, device};
+  return refine_open(rq, RefineOutputs{ctx, h_out_bytes, h_history, h_before, h_after, h_skipped, h_ms, h_bad_view});
 }
 
 int spz_amd_refine_densify_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
@@ -771,15 +987,23 @@ int spz_amd_refine_densify_open(const uint8_t *d_stream_a, size_t size_a, const 
                                 uint64_t *h_skipped, float *h_ms, int32_t *h_bad_view, uint64_t *h_num_points,
                                 spz_amd_densify_round *h_rounds, int rounds_capacity, int *h_num_rounds,
                                 uint32_t *h_origin) {
-  if (rounds_capacity < 0 || (rounds_capacity > 0 && h_rounds == nullptr)) {
-    if (h_bad_view) *h_bad_view = -1;
-    if (ctx) *ctx = nullptr;
-    if (h_out_bytes) *h_out_bytes = 0;
-    return SPZ_AMD_ERR_INVALID_ARG;
-  }
-  return refine_run(d_stream_a, size_a, hdr_a, d_stream_b, size_b, hdr_b, views, num_views, options, densify, device,
-                    ctx, h_out_bytes, h_history, h_before, h_after, h_skipped, h_ms, h_bad_view,
-                    DensifyReport{h_num_points, h_rounds, rounds_capacity, h_num_rounds, h_origin});
+  const RefineRequest rq = {d_stream_a, size_a, hdr_a, d_stream_b, size_b, hdr_b, views, num_views, options, densify, device};
+  return refine_open(rq, RefineOutputs{ctx, h_out_bytes, h_history, h_before, h_after, h_skipped, h_ms, h_bad_view,
+                                       h_num_points, h_rounds, rounds_capacity, h_num_rounds, h_origin});
+}
+
+int spz_amd_refine_images_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
+                               const spz_amd_render_params *views, int num_views, const float *const *d_targets,
+                               int channels, const float *const *d_weights, const spz_amd_refine_options *options,
+                               const spz_amd_photo_options *photo, const spz_amd_densify_options *densify, int device,
+                               void **ctx, uint64_t *h_out_bytes, double *h_history, spz_amd_image_metrics *h_before,
+                               spz_amd_image_metrics *h_after, uint64_t *h_skipped, float *h_ms, int32_t *h_bad_view,
+                               uint64_t *h_num_points, spz_amd_densify_round *h_rounds, int rounds_capacity,
+                               int *h_num_rounds, uint32_t *h_origin, double *h_exposures) {
+  const RefineRequest rq = {d_stream_a, size_a, hdr_a, nullptr, 0, nullptr, views, num_views, options, densify, device,
+                            true, photo, d_targets, channels, d_weights};
+  return refine_open(rq, RefineOutputs{ctx, h_out_bytes, h_history, h_before, h_after, h_skipped, h_ms, h_bad_view,
+                                       h_num_points, h_rounds, rounds_capacity, h_num_rounds, h_origin, h_exposures});
 }
 
 int spz_amd_refine_images_depth_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
@@ -793,124 +1017,12 @@ int spz_amd_refine_images_depth_open(const uint8_t *d_stream_a, size_t size_a, c
                                      spz_amd_densify_round *h_rounds, int rounds_capacity, int *h_num_rounds,
                                      uint32_t *h_origin, double *h_exposures, double *h_depth_history,
                                      double *h_depth_error) {
-  if (rounds_capacity < 0 || (rounds_capacity > 0 && h_rounds == nullptr) || depth == nullptr) {
-    if (h_bad_view) *h_bad_view = -1;
-    if (ctx) *ctx = nullptr;
-    if (h_out_bytes) *h_out_bytes = 0;
-    return SPZ_AMD_ERR_INVALID_ARG;
-  }
-  PhotoTargets targets = {d_targets, d_weights, channels, photo, h_exposures};
-  targets.d_depths = d_depth_targets;
-  targets.depth = depth;
-  targets.h_depth_history = h_depth_history;
-  targets.h_depth_error = h_depth_error;
-  return refine_run(d_stream_a, size_a, hdr_a, nullptr, 0, nullptr, views, num_views, options, densify, device, ctx,
-                    h_out_bytes, h_history, h_before, h_after, h_skipped, h_ms, h_bad_view,
-                    DensifyReport{h_num_points, h_rounds, rounds_capacity, h_num_rounds, h_origin}, &targets);
+  const RefineRequest rq = {d_stream_a, size_a, hdr_a, nullptr, 0, nullptr, views, num_views, options, densify, device,
+                            true, photo, d_targets, channels, d_weights, true, depth, d_depth_targets};
+  return refine_open(rq, RefineOutputs{ctx, h_out_bytes, h_history, h_before, h_after, h_skipped, h_ms, h_bad_view,
+                                       h_num_points, h_rounds, rounds_capacity, h_num_rounds, h_origin, h_exposures,
+                                       h_depth_history, h_depth_error});
 }
-
-int spz_amd_refine_images_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
-                               const spz_amd_render_params *views, int num_views, const float *const *d_targets,
-                               int channels, const float *const *d_weights, const spz_amd_refine_options *options,
-                               const spz_amd_photo_options *photo, const spz_amd_densify_options *densify, int device,
-                               void **ctx, uint64_t *h_out_bytes, double *h_history, spz_amd_image_metrics *h_before,
-                               spz_amd_image_metrics *h_after, uint64_t *h_skipped, float *h_ms, int32_t *h_bad_view,
-                               uint64_t *h_num_points, spz_amd_densify_round *h_rounds, int rounds_capacity,
-                               int *h_num_rounds, uint32_t *h_origin, double *h_exposures) {
-  if (rounds_capacity < 0 || (rounds_capacity > 0 && h_rounds == nullptr)) {
-    if (h_bad_view) *h_bad_view = -1;
-    if (ctx) *ctx = nullptr;
-    if (h_out_bytes) *h_out_bytes = 0;
-    return SPZ_AMD_ERR_INVALID_ARG;
-  }
-  const PhotoTargets targets = {d_targets, d_weights, channels, photo, h_exposures};
-  return refine_run(d_stream_a, size_a, hdr_a, nullptr, 0, nullptr, views, num_views, options, densify, device, ctx,
-                    h_out_bytes, h_history, h_before, h_after, h_skipped, h_ms, h_bad_view,
-                    DensifyReport{h_num_points, h_rounds, rounds_capacity, h_num_rounds, h_origin}, &targets);
-}
-
-}  // extern "C"
-
-namespace {
-
-// refine_images_host_open (depth_entry false: h_depths and depth are NULL) and refine_images_depth_host_open: the
-// images, weight maps and depth maps uploaded, then the device form.
-int images_host_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
-                     const spz_amd_render_params *views, int num_views, const float *const *h_targets, int channels,
-                     const float *const *h_weights, const float *const *h_depths, const spz_amd_depth_options *depth,
-                     bool depth_entry, const spz_amd_refine_options *options, const spz_amd_photo_options *photo,
-                     const spz_amd_densify_options *densify, int device, void **ctx, uint64_t *h_out_bytes,
-                     double *h_history, spz_amd_image_metrics *h_before, spz_amd_image_metrics *h_after,
-                     uint64_t *h_skipped, float *h_ms, int32_t *h_bad_view, uint64_t *h_num_points,
-                     spz_amd_densify_round *h_rounds, int rounds_capacity, int *h_num_rounds, uint32_t *h_origin,
-                     double *h_exposures, double *h_depth_history, double *h_depth_error) {
-  if (h_bad_view) *h_bad_view = -1;
-  if (ctx) *ctx = nullptr;
-  if (h_out_bytes) *h_out_bytes = 0;
-  int rc = check_views(views, num_views, SPZ_AMD_REFINE_MAX_VIEWS, h_bad_view);
-  if (rc != SPZ_AMD_OK) return rc;
-  if (h_targets == nullptr || (channels != 3 && channels != 4)) return SPZ_AMD_ERR_INVALID_ARG;
-  if (spz_amd_refine_check(options) != SPZ_AMD_OK || spz_amd_photo_check(photo) != SPZ_AMD_OK || rounds_capacity < 0 ||
-      (rounds_capacity > 0 && h_rounds == nullptr) || (depth_entry && spz_amd_depth_check(depth) != SPZ_AMD_OK)) {
-    return SPZ_AMD_ERR_INVALID_ARG;  // before anything is uploaded
-  }
-  spz_amd_layout lay_a;
-  rc = check_packed_stream(d_stream_a, size_a, hdr_a, &lay_a);
-  if (rc != SPZ_AMD_OK) return rc;
-  WorkspaceOffsets o;
-  std::vector<uint64_t> t_off((size_t)num_views), w_off((size_t)num_views), z_off((size_t)num_views);
-  for (int v = 0; v < num_views; ++v) {
-    if (h_targets[v] == nullptr) {
-      if (h_bad_view) *h_bad_view = v;
-      return SPZ_AMD_ERR_INVALID_ARG;
-    }
-    const uint64_t px = (uint64_t)views[v].width * views[v].height;
-    t_off[(size_t)v] = o.put(4u * (uint64_t)channels * px);
-    w_off[(size_t)v] = o.put(h_weights && h_weights[v] ? 4u * px : 0u);
-    z_off[(size_t)v] = o.put(h_depths && h_depths[v] ? 4u * px : 0u);
-  }
-  DeviceGuard guard;
-  rc = guard.enter(device);
-  if (rc != SPZ_AMD_OK) return rc;
-  struct Block {
-    uint8_t *p = nullptr;
-    ~Block() {
-      if (p) (void)hipFree(p);
-    }
-  } block;
-  SPZ_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&block.p), o.off ? o.off : 256u));
-  std::vector<const float *> d_targets((size_t)num_views), d_weights((size_t)num_views, nullptr),
-      d_depths((size_t)num_views, nullptr);
-  for (int v = 0; v < num_views; ++v) {
-    const uint64_t px = (uint64_t)views[v].width * views[v].height;
-    d_targets[(size_t)v] = reinterpret_cast<const float *>(block.p + t_off[(size_t)v]);
-    SPZ_HIP_TRY(hipMemcpy(block.p + t_off[(size_t)v], h_targets[v], 4u * (uint64_t)channels * px, hipMemcpyHostToDevice));
-    if (h_weights && h_weights[v]) {
-      d_weights[(size_t)v] = reinterpret_cast<const float *>(block.p + w_off[(size_t)v]);
-      SPZ_HIP_TRY(hipMemcpy(block.p + w_off[(size_t)v], h_weights[v], 4u * px, hipMemcpyHostToDevice));
-    }
-    if (h_depths && h_depths[v]) {
-      d_depths[(size_t)v] = reinterpret_cast<const float *>(block.p + z_off[(size_t)v]);
-      SPZ_HIP_TRY(hipMemcpy(block.p + z_off[(size_t)v], h_depths[v], 4u * px, hipMemcpyHostToDevice));
-    }
-  }
-  // (the loop blocks, so the images outlive it)
-  if (depth_entry) {
-    return spz_amd_refine_images_depth_open(d_stream_a, size_a, hdr_a, views, num_views, d_targets.data(), channels,
-                                            h_weights ? d_weights.data() : nullptr, h_depths ? d_depths.data() : nullptr,
-                                            depth, options, photo, densify, device, ctx, h_out_bytes, h_history, h_before,
-                                            h_after, h_skipped, h_ms, h_bad_view, h_num_points, h_rounds, rounds_capacity,
-                                            h_num_rounds, h_origin, h_exposures, h_depth_history, h_depth_error);
-  }
-  return spz_amd_refine_images_open(d_stream_a, size_a, hdr_a, views, num_views, d_targets.data(), channels,
-                                    h_weights ? d_weights.data() : nullptr, options, photo, densify, device, ctx,
-                                    h_out_bytes, h_history, h_before, h_after, h_skipped, h_ms, h_bad_view, h_num_points,
-                                    h_rounds, rounds_capacity, h_num_rounds, h_origin, h_exposures);
-}
-
-}  // namespace
-
-extern "C" {
 
 int spz_amd_refine_images_host_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
                                     const spz_amd_render_params *views, int num_views, const float *const *h_targets,
@@ -921,10 +1033,10 @@ int spz_amd_refine_images_host_open(const uint8_t *d_stream_a, size_t size_a, co
                                     float *h_ms, int32_t *h_bad_view, uint64_t *h_num_points,
                                     spz_amd_densify_round *h_rounds, int rounds_capacity, int *h_num_rounds,
                                     uint32_t *h_origin, double *h_exposures) {
-  return images_host_open(d_stream_a, size_a, hdr_a, views, num_views, h_targets, channels, h_weights, nullptr, nullptr,
-                          false, options, photo, densify, device, ctx, h_out_bytes, h_history, h_before, h_after,
-                          h_skipped, h_ms, h_bad_view, h_num_points, h_rounds, rounds_capacity, h_num_rounds, h_origin,
-                          h_exposures, nullptr, nullptr);
+  const RefineRequest rq = {d_stream_a, size_a, hdr_a, nullptr, 0, nullptr, views, num_views, options, densify, device,
+                            true, photo, h_targets, channels, h_weights};
+  return refine_host_open(rq, RefineOutputs{ctx, h_out_bytes, h_history, h_before, h_after, h_skipped, h_ms, h_bad_view,
+                                            h_num_points, h_rounds, rounds_capacity, h_num_rounds, h_origin, h_exposures});
 }
 
 int spz_amd_refine_images_depth_host_open(const uint8_t *d_stream_a, size_t size_a, const spz_amd_header *hdr_a,
@@ -938,10 +1050,11 @@ int spz_amd_refine_images_depth_host_open(const uint8_t *d_stream_a, size_t size
                                           int32_t *h_bad_view, uint64_t *h_num_points, spz_amd_densify_round *h_rounds,
                                           int rounds_capacity, int *h_num_rounds, uint32_t *h_origin,
                                           double *h_exposures, double *h_depth_history, double *h_depth_error) {
-  return images_host_open(d_stream_a, size_a, hdr_a, views, num_views, h_targets, channels, h_weights, h_depth_targets,
-                          depth, true, options, photo, densify, device, ctx, h_out_bytes, h_history, h_before, h_after,
-                          h_skipped, h_ms, h_bad_view, h_num_points, h_rounds, rounds_capacity, h_num_rounds, h_origin,
-                          h_exposures, h_depth_history, h_depth_error);
+  const RefineRequest rq = {d_stream_a, size_a, hdr_a, nullptr, 0, nullptr, views, num_views, options, densify, device,
+                            true, photo, h_targets, channels, h_weights, true, depth, h_depth_targets};
+  return refine_host_open(rq, RefineOutputs{ctx, h_out_bytes, h_history, h_before, h_after, h_skipped, h_ms, h_bad_view,
+                                            h_num_points, h_rounds, rounds_capacity, h_num_rounds, h_origin, h_exposures,
+                                            h_depth_history, h_depth_error});
 }
 
 int spz_amd_refine_fetch(void *ctx, uint8_t *h_out) { return packed_result_fetch(ctx, h_out); }
@@ -951,3 +1064,4 @@ const uint8_t *spz_amd_refine_device_data(void *ctx) { return packed_result_devi
 void spz_amd_refine_close(void *ctx) { packed_result_close(ctx); }
 
 }  // extern "C"
+

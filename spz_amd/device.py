@@ -2059,6 +2059,42 @@ def reset_opacity(alphas, m=None, v=None, stream=None):
     abi.check(rc, "spz_amd_densify_reset_opacity_device")
 
 
+def _refine_open(entry, head, opts, mid, dev, nv, room=None, origin_room=0, extra=()):
+    """What the refine forms share: the outputs every open entry has, the call entry(*head, &opts, *mid, device, the
+    shared outputs[, densify's outputs], *extra), SpzAmdError with `.view` on a refusal, and the common part of the
+    report.  room: None for spz_amd_refine_open, which has no densify outputs; otherwise the rounds the caller has room
+    for, and origin_room the points.  Returns (ctx, report, origin); the report has num_points and rounds, and origin is
+    the output's origin map, only with room."""
+    import numpy as np
+    ctx, out_bytes, skipped, bad = C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_int32(-1)
+    history = (C.c_double * max(1, opts.iterations))()
+    before, after = (abi.ImageMetrics * nv)(), (abi.ImageMetrics * nv)()
+    ms = (C.c_float * 3)()
+    densify_out = ()
+    if room is not None:
+        h_rounds, n_rounds, n_out = (abi.DensifyRound * max(1, room))(), C.c_int32(), C.c_uint64()
+        origin = np.empty(origin_room, dtype=np.uint32)
+        densify_out = (C.byref(n_out), h_rounds, room, C.byref(n_rounds), origin.ctypes.data)
+    torch.cuda.current_stream(dev).synchronize()  # the producers of the streams and the images
+    device_index = dev.index if dev.index is not None else torch.cuda.current_device()
+    rc = getattr(abi.load_library(), entry)(*head, C.byref(opts), *mid, device_index, C.byref(ctx), C.byref(out_bytes),
+                                            history, before, after, C.byref(skipped), ms, C.byref(bad), *densify_out,
+                                            *extra)
+    if rc != abi.OK:
+        err = abi.SpzAmdError(rc, entry + (f" (view {bad.value})" if bad.value >= 0 else ""))
+        err.view = bad.value
+        raise err
+    report = {"history": [history[i] for i in range(max(0, opts.iterations))],
+              "before": [_metrics_dict(x) for x in before], "after": [_metrics_dict(x) for x in after],
+              "skipped": int(skipped.value), "ms": tuple(ms), "out_bytes": int(out_bytes.value)}
+    if room is None:
+        return ctx, report, None
+    report["num_points"] = int(n_out.value)
+    report["rounds"] = [{k: int(getattr(r, k)) for k in ("iteration", "cloned", "split", "culled", "refused",
+                                                         "num_points")} for r in h_rounds[:min(room, n_rounds.value)]]
+    return ctx, report, origin[:report["num_points"]].copy()
+
+
 def refine_packed(stream_a, header_a, stream_b, header_b, views, iterations, *, lambda_dssim=None, lrs=None, beta1=None,
                   beta2=None, eps=None, train=None, densify=None):
     """Fit the resident packed stream A to the target B over `views` (a sequence of abi.RenderParams, one coord):
@@ -2070,7 +2106,6 @@ def refine_packed(stream_a, header_a, stream_b, header_b, views, iterations, *, 
     cloned, split and culled while fitting, up to max_points (0: B's count).  The report's num_points is the output's
     count, rounds one dict per round (iteration, cloned, split, culled, refused, num_points), and origin the index in A
     of every output point (a numpy uint32 array)."""
-    L = abi.load_library()
     _check_stream_tensor(stream_a)
     _check_stream_tensor(stream_b)
     dev = stream_a.device
@@ -2081,50 +2116,19 @@ def refine_packed(stream_a, header_a, stream_b, header_b, views, iterations, *, 
         raise ValueError(f"views must be 1..{abi.REFINE_MAX_VIEWS} abi.RenderParams")
     opts = abi.refine_options(iterations, lambda_dssim=lambda_dssim, lrs=lrs, beta1=beta1, beta2=beta2, eps=eps,
                               train=train)
-    arr = (abi.RenderParams * len(views))(*views)
-    ctx, out_bytes, skipped, bad = C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_int32(-1)
-    history = (C.c_double * max(1, opts.iterations))()
-    before = (abi.ImageMetrics * len(views))()
-    after = (abi.ImageMetrics * len(views))()
-    ms = (C.c_float * 3)()
-    dopts = abi.densify_options(densify) if densify is not None else None
-    torch.cuda.current_stream(dev).synchronize()  # the streams' producers
-    device_index = dev.index if dev.index is not None else torch.cuda.current_device()
-    num_points, rounds, origin = int(header_a.num_points), [], None
-    if dopts is None:
-        entry = "spz_amd_refine_open"
-        rc = L.spz_amd_refine_open(stream_a.data_ptr(), stream_a.numel(), C.byref(header_a), stream_b.data_ptr(),
-                                   stream_b.numel(), C.byref(header_b), arr, len(views), C.byref(opts), device_index,
-                                   C.byref(ctx), C.byref(out_bytes), history, before, after, C.byref(skipped), ms,
-                                   C.byref(bad))
+    head = (stream_a.data_ptr(), stream_a.numel(), C.byref(header_a), stream_b.data_ptr(), stream_b.numel(),
+            C.byref(header_b), (abi.RenderParams * len(views))(*views), len(views))
+    if densify is None:
+        ctx, report, _ = _refine_open("spz_amd_refine_open", head, opts, (), dev, len(views))
+        report.update(num_points=int(header_a.num_points), rounds=[])
     else:
-        import numpy as np
-        entry = "spz_amd_refine_densify_open"
-        room = max(1, opts.iterations // max(1, dopts.interval))
-        h_rounds, n_rounds, n_out = (abi.DensifyRound * room)(), C.c_int32(), C.c_uint64()
-        cap = max(int(dopts.max_points) or int(header_b.num_points), int(header_a.num_points), 1)
-        origin = np.empty(cap, dtype=np.uint32)
-        rc = L.spz_amd_refine_densify_open(stream_a.data_ptr(), stream_a.numel(), C.byref(header_a), stream_b.data_ptr(),
-                                           stream_b.numel(), C.byref(header_b), arr, len(views), C.byref(opts),
-                                           C.byref(dopts), device_index, C.byref(ctx), C.byref(out_bytes), history,
-                                           before, after, C.byref(skipped), ms, C.byref(bad), C.byref(n_out), h_rounds,
-                                           room, C.byref(n_rounds), origin.ctypes.data)
-        if rc == abi.OK:
-            num_points = int(n_out.value)
-            origin = origin[:num_points].copy()
-            rounds = [{k: int(getattr(r, k)) for k in ("iteration", "cloned", "split", "culled", "refused", "num_points")}
-                      for r in h_rounds[:min(room, n_rounds.value)]]
-    if rc != abi.OK:
-        err = abi.SpzAmdError(rc, entry + (f" (view {bad.value})" if bad.value >= 0 else ""))
-        err.view = bad.value
-        raise err
-    report = {"history": [history[i] for i in range(max(0, opts.iterations))],
-              "before": [_metrics_dict(x) for x in before], "after": [_metrics_dict(x) for x in after],
-              "skipped": int(skipped.value), "ms": tuple(ms), "out_bytes": int(out_bytes.value),
-              "num_points": num_points, "rounds": rounds}
-    if origin is not None:
+        dopts = abi.densify_options(densify)
+        ctx, report, origin = _refine_open(
+            "spz_amd_refine_densify_open", head, opts, (C.byref(dopts),), dev, len(views),
+            room=max(1, opts.iterations // max(1, dopts.interval)),
+            origin_room=max(int(dopts.max_points) or int(header_b.num_points), int(header_a.num_points), 1))
         report["origin"] = origin
-    return RefineResult(ctx, out_bytes.value, dev, report)
+    return RefineResult(ctx, report["out_bytes"], dev, report)
 
 
 def refine_packed_images(stream_a, header_a, views, images, iterations, *, weights=None, fit_exposure=False,
@@ -2143,7 +2147,6 @@ def refine_packed_images(stream_a, header_a, views, images, iterations, *, weigh
     `depth_history` (the depth loss before each step, 0 for a view without a map) and `depth_error`, a float64 numpy
     array (views, 2): the depth loss of A and of the output against the map, -1 for a view without one."""
     import numpy as np
-    L = abi.load_library()
     _check_stream_tensor(stream_a)
     dev = stream_a.device
     views = list(views)
@@ -2190,50 +2193,26 @@ def refine_packed_images(stream_a, header_a, views, images, iterations, *, weigh
         zptrs = (C.c_void_p * nv)(*[dm.data_ptr() if dm is not None else None for dm in depths])
         depth_history = (C.c_double * max(1, opts.iterations))()
         depth_error = np.zeros((nv, 2), dtype=np.float64)
-    arr = (abi.RenderParams * nv)(*views)
-    targets = (C.c_void_p * nv)(*[img.data_ptr() for img in images])
-    wptrs = (C.c_void_p * nv)(*[wt.data_ptr() if wt is not None else None for wt in weights])
-    ctx, out_bytes, skipped, bad = C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_int32(-1)
-    history = (C.c_double * max(1, opts.iterations))()
-    before = (abi.ImageMetrics * nv)()
-    after = (abi.ImageMetrics * nv)()
-    ms = (C.c_float * 3)()
-    room = max(1, opts.iterations // max(1, dopts.interval)) if dopts is not None else 0
-    h_rounds = (abi.DensifyRound * max(1, room))()
-    n_rounds, n_out = C.c_int32(), C.c_uint64()
-    origin = np.empty(max(int(dopts.max_points) if dopts is not None else 0, int(header_a.num_points), 1), dtype=np.uint32)
+    head = (stream_a.data_ptr(), stream_a.numel(), C.byref(header_a), (abi.RenderParams * nv)(*views), nv,
+            (C.c_void_p * nv)(*[img.data_ptr() for img in images]), channels,
+            (C.c_void_p * nv)(*[wt.data_ptr() if wt is not None else None for wt in weights])
+            if any(wt is not None for wt in weights) else None)
     exposures = np.zeros((nv, 3, 4), dtype=np.float64)
-    torch.cuda.current_stream(dev).synchronize()  # the stream's and the images' producers
-    device_index = dev.index if dev.index is not None else torch.cuda.current_device()
-    head = (stream_a.data_ptr(), stream_a.numel(), C.byref(header_a), arr, nv, targets, channels,
-            wptrs if any(wt is not None for wt in weights) else None)
-    tail = (C.byref(opts), C.byref(popts), C.byref(dopts) if dopts is not None else None, device_index, C.byref(ctx),
-            C.byref(out_bytes), history, before, after, C.byref(skipped), ms, C.byref(bad), C.byref(n_out), h_rounds,
-            room, C.byref(n_rounds), origin.ctypes.data, exposures.ctypes.data)
-    if depths is None:
-        entry = "spz_amd_refine_images_open"
-        rc = L.spz_amd_refine_images_open(*head, *tail)
-    else:
-        entry = "spz_amd_refine_images_depth_open"
-        rc = L.spz_amd_refine_images_depth_open(*head, zptrs if any(dm is not None for dm in depths) else None,
-                                                C.byref(zopts), *tail, depth_history, depth_error.ctypes.data)
-    if rc != abi.OK:
-        err = abi.SpzAmdError(rc, entry + (f" (view {bad.value})" if bad.value >= 0 else ""))
-        err.view = bad.value
-        raise err
-    num_points = int(n_out.value)
-    report = {"history": [history[i] for i in range(max(0, opts.iterations))],
-              "before": [_metrics_dict(x) for x in before], "after": [_metrics_dict(x) for x in after],
-              "skipped": int(skipped.value), "ms": tuple(ms), "out_bytes": int(out_bytes.value),
-              "num_points": num_points, "exposures": exposures,
-              "rounds": [{k: int(getattr(r, k)) for k in ("iteration", "cloned", "split", "culled", "refused",
-                                                          "num_points")} for r in h_rounds[:min(room, n_rounds.value)]]}
+    entry, extra = "spz_amd_refine_images_open", (exposures.ctypes.data,)
+    if depths is not None:
+        entry, extra = "spz_amd_refine_images_depth_open", extra + (depth_history, depth_error.ctypes.data)
+        head += (zptrs if any(dm is not None for dm in depths) else None, C.byref(zopts))
+    ctx, report, origin = _refine_open(
+        entry, head, opts, (C.byref(popts), C.byref(dopts) if dopts is not None else None), dev, nv,
+        room=max(1, opts.iterations // max(1, dopts.interval)) if dopts is not None else 0,
+        origin_room=max(int(dopts.max_points) if dopts is not None else 0, int(header_a.num_points), 1), extra=extra)
+    report["exposures"] = exposures
     if dopts is not None:
-        report["origin"] = origin[:num_points].copy()
+        report["origin"] = origin
     if depths is not None:
         report["depth_history"] = [depth_history[i] for i in range(max(0, opts.iterations))]
         report["depth_error"] = depth_error
-    return RefineResult(ctx, out_bytes.value, dev, report)
+    return RefineResult(ctx, report["out_bytes"], dev, report)
 
 
 def image_halve(image_t, stream=None):

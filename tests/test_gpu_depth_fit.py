@@ -74,6 +74,70 @@ def test_no_depth_is_the_path_of_refine_images(cuda):
     assert zero["depth_history"] == [0.0] and (zero["depth_error"] > 0).all()
 
 
+def run_every_option(cuda, iterations, densify):
+    """Photo loss with a weight map, a fitted exposure, a depth map on view 0 alone, every array trained and, when given,
+    densify with the opacity reset: (report, output stream, A's header, views, images, weight map, depth map)."""
+    from spz_amd import abi, device as D
+    s, e = scene(), expected()
+    a_t = torch.as_tensor(s["a"]).to(cuda)
+    rc, ha = abi.peek_header(s["a"].tobytes())
+    assert rc == 0
+    views = [view_params(v, DG.FIT_COORD) for v in s["views"]]
+    images = [torch.as_tensor(x).to(cuda) for x in s["images"]]
+    weight = torch.zeros((DG.FIT_H, DG.FIT_W), dtype=torch.float32, device=cuda)
+    weight[:, DG.FIT_W // 2:] = 1.0
+    depth = torch.as_tensor(s["depths"][0]).to(cuda)
+    with D.refine_packed_images(a_t, ha, views, images, iterations, weights=[weight, None], fit_exposure=True,
+                                lrs={"positions": e["lr_positions"]}, densify=densify, depths=[depth, None]) as res:
+        return res.report, res.tensor().clone(), ha, views, images, weight, depth
+
+
+def test_every_option_at_once(cuda):
+    """Weights, exposure, depth, densify and the opacity reset in one call of 12 iterations: what the forward makes
+    repeatable (everything before the first step carries the bits of the one-iteration call without densify; "after" and
+    the depth error of the output are those of the output stream rendered again) and the structure of the report.
+    Neither growth nor a smaller loss is asserted: nothing on the CPU has shown either for this configuration."""
+    from spz_amd import abi, device as D
+    dn = {"interval": 4, "from_iter": 0, "until_iter": 12, "opacity_reset_interval": 6, "max_points": 400}
+    first = run_every_option(cuda, 1, None)[0]
+    rep, out, ha, views, images, weight, depth = run_every_option(cuda, 12, dn)
+    bits = lambda x: np.float64(x).tobytes()  # noqa: E731
+    assert len(rep["history"]) == len(rep["depth_history"]) == 12
+    assert bits(rep["history"][0]) == bits(first["history"][0])
+    assert bits(rep["depth_history"][0]) == bits(first["depth_history"][0])
+    assert bits(rep["depth_error"][:, 0]) == bits(first["depth_error"][:, 0])
+    for a, b in zip(rep["before"], first["before"]):
+        assert a.keys() == b.keys() and all(bits(a[k]) == bits(b[k]) for k in a)
+    assert all(rep["depth_history"][i] == 0.0 for i in range(1, 12, 2))  # view 1 has no map
+    assert rep["depth_error"][1].tolist() == [-1.0, -1.0]
+    # the rounds
+    n_a = int(ha.num_points)
+    assert [r["iteration"] for r in rep["rounds"]] == [3, 7, 11]
+    count = n_a
+    for r in rep["rounds"]:
+        assert r["num_points"] == count - r["culled"] + r["cloned"] + r["split"], r
+        count = r["num_points"]
+    n = rep["num_points"]
+    print(f"rounds {rep['rounds']}; {n_a} -> {n} points; history {rep['history'][0]!r} -> {rep['history'][-1]!r}")
+    assert n == count and n <= 400
+    origin = rep["origin"]
+    assert origin.shape == (n,) and (origin < n_a).all() and (np.diff(origin.astype(np.int64)) >= 0).all()
+    # the output stream
+    assert out.numel() == rep["out_bytes"] == abi.stream_layout(n, 0, 3).total_bytes
+    ho = abi.Header.from_buffer_copy(ha)
+    ho.num_points = n
+    rc, got = abi.peek_header(out.cpu().numpy().tobytes())
+    assert rc == 0 and bytes(got) == bytes(ho), "the output's header is A's except for the count"
+    assert np.isfinite(rep["exposures"]).all() and rep["exposures"].shape == (2, 3, 4)
+    for v, p in enumerate(views):
+        shown = D.image_exposure(D.render_packed(out, ho, p), rep["exposures"][v])
+        m = D.image_metrics(shown, images[v]).cpu().numpy()
+        assert rep["after"][v] == dict(zip(("mse", "psnr", "ssim", "l1", "max_abs"), m.tolist())), v
+    z, image = D.render_depth_packed(out, ho, views[0], return_image=True, return_index=False)
+    loss, _ = D.depth_loss(z, image, depth, weight=weight, kind="l1", min_alpha=0.5, scale=1.0)
+    assert bits(rep["depth_error"][0, 1]) == bits(loss.cpu().numpy()[0])
+
+
 @functools.lru_cache(maxsize=None)
 def fitted(cuda_index):
     """The run with the depth term, shared by the tests below (nothing changes it)."""

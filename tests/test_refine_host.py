@@ -278,6 +278,90 @@ def test_refine_open_refuses_bad_arguments_and_no_device_is_an_error():
         assert call([good], iterations=0, hist=None)[0] == abi.ERR_NO_DEVICE
 
 
+OPEN_ENTRIES = ("spz_amd_refine_open", "spz_amd_refine_densify_open", "spz_amd_refine_images_open",
+                "spz_amd_refine_images_depth_open", "spz_amd_refine_images_host_open",
+                "spz_amd_refine_images_depth_host_open")
+
+
+def open_with_one_bad_argument(entry, kind):
+    """One call of `entry` with everything in order but `kind`: (status, bad_view, ctx, bytes, num_points, num_rounds),
+    every output filled with 7 before the call (the last two None for spz_amd_refine_open, which has neither).  The
+    device forms are given addresses that are never followed; the host forms real images, which they may upload."""
+    from spz_amd import abi
+    L = abi.load_library()
+    images, depth_entry, host = "images" in entry, "depth" in entry, "host" in entry
+    hdr = abi.Header(1 if kind == "version 1" else 3, 4, 0, 12, 0, 0)
+    stream = np.zeros(4096, np.uint8)
+    eye = np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 5]], np.float64)
+    good = abi.render_params(eye, 30.0, 30.0, 8.0, 6.0, 16, 12, 0.2, (0.0, 0.0, 0.0), 3, abi.RDF)
+    worse = abi.RenderParams.from_buffer_copy(good)
+    worse.fx = -1.0
+    views = (abi.RenderParams * 3)(good, worse if kind == "bad view" else good, good)
+    keep = [np.zeros((12, 16, 3), np.float32), np.zeros((12, 16), np.float32)]   # what a host form would upload
+    p, z = (keep[0].ctypes.data, keep[1].ctypes.data) if host else (0x1000, 0x1000)
+    targets = (C.c_void_p * 3)(p, None if kind == "NULL target" else p, p)
+    weights = (C.c_void_p * 3)(None, 0x1001, None) if kind == "odd weight" else None
+    depths = (C.c_void_p * 3)(z, 0x1002 if kind == "odd depth" else z, None)
+    opts, photo, depth = abi.refine_options(2), abi.photo_options(), abi.depth_options()
+    ctx, nbytes, bad, n_out, n_rounds = C.c_void_p(7), C.c_uint64(7), C.c_int32(7), C.c_uint64(7), C.c_int32(7)
+    rounds, hist, dhist, derr = (abi.DensifyRound * 2)(), (C.c_double * 2)(), (C.c_double * 2)(), (C.c_double * 6)()
+    args = [stream.ctypes.data, 50 if kind == "short stream" else stream.size, C.byref(hdr)]
+    if not images:
+        args += [stream.ctypes.data, stream.size, C.byref(abi.Header(3, 4, 0, 12, 0, 0))]
+    args += [views, 0 if kind == "zero views" else 3]
+    if images:
+        args += [targets, 3, weights]
+    if depth_entry:
+        args += [depths, None if kind == "NULL depth options" else C.byref(depth)]
+    args += [None if kind == "NULL options" else C.byref(opts)]
+    if images:
+        args += [None if kind == "NULL photo options" else C.byref(photo)]
+    if entry != "spz_amd_refine_open":
+        args += [None]                                                        # densify: off
+    args += [0, C.byref(ctx), C.byref(nbytes), hist, None, None, None, None, C.byref(bad)]
+    if entry != "spz_amd_refine_open":
+        args += [C.byref(n_out), None if kind == "NULL rounds" else rounds, -1 if kind == "rounds_capacity -1" else 2,
+                 C.byref(n_rounds), None]
+    if images:
+        args += [None]                                                        # exposures
+    if depth_entry:
+        args += [dhist, derr]
+    rc = getattr(L, entry)(*args)
+    counted = entry != "spz_amd_refine_open"
+    return rc, bad.value, ctx.value, nbytes.value, n_out.value if counted else None, n_rounds.value if counted else None
+
+
+@pytest.mark.parametrize("entry", OPEN_ENTRIES)
+def test_every_open_entry_refuses_one_bad_argument_and_resets_every_output(entry):
+    """The six open entries over one table: the status and bad_view of every single bad argument the entry accepts, and
+    after each refusal ctx NULL, the byte count 0 and, where the entry reports them, num_points 0 and num_rounds 0.
+    A weight or depth map at an odd address is refused by the device forms alone: the host forms copy from theirs.
+    Before the entries shared one reset, num_points and num_rounds kept the caller's 7 on the refusals the entries made
+    themselves: rounds_capacity -1 and NULL rounds in all five entries that have them, NULL depth options in the two
+    depth entries, and every row of the two host forms (which also uploaded the images before they looked at the
+    stream's version, so that without a device version 1 was answered with ERR_NO_DEVICE)."""
+    from spz_amd import abi
+    invalid = abi.ERR_INVALID_ARG
+    table = [("NULL options", invalid, -1), ("zero views", invalid, -1), ("bad view", invalid, 1),
+             ("short stream", abi.ERR_SHORT_STREAM, -1), ("version 1", abi.ERR_UNSUPPORTED, -1)]
+    if entry != "spz_amd_refine_open":
+        table += [("rounds_capacity -1", invalid, -1), ("NULL rounds", invalid, -1)]
+    if "images" in entry:
+        table += [("NULL photo options", invalid, -1), ("NULL target", invalid, 1)]
+    if "depth" in entry:
+        table += [("NULL depth options", invalid, -1)]
+    if "images" in entry and "host" not in entry:
+        table += [("odd weight", invalid, 1)]
+    if entry == "spz_amd_refine_images_depth_open":
+        table += [("odd depth", invalid, 1)]
+    for kind, status, view in table:
+        rc, bad, ctx, nbytes, num_points, num_rounds = open_with_one_bad_argument(entry, kind)
+        assert (rc, bad) == (status, view), kind
+        assert ctx is None and nbytes == 0, kind
+        if entry != "spz_amd_refine_open":
+            assert (num_points, num_rounds) == (0, 0), kind
+
+
 def test_refine_defaults_are_the_published_arguments():
     from spz_amd import abi
     o = abi.refine_options(0)
