@@ -497,7 +497,7 @@ __global__ __launch_bounds__(kDecBlock) void spz_dec_flags_kernel(const uint8_t 
     if (i >= n) break;
     v += (cell_start(pos, i, level) ? 1ull : 0ull) + (alpha[i] ? (1ull << 32) : 0ull);
   }
-  const unsigned long long e = block_exclusive_scan64(v, s);
+  const unsigned long long e = block_exclusive_scan(v, s);
   if (threadIdx.x == kDecBlock - 1u) tile_sums[blockIdx.x] = e + v;
 }
 
@@ -507,21 +507,11 @@ __global__ __launch_bounds__(kDecBlock) void spz_dec_scan_kernel(unsigned long l
                                                                  uint32_t sh_degree, uint32_t sh_dim, uint32_t fb,
                                                                  uint32_t flags) {
   __shared__ unsigned long long s[kDecBlock];
-  const uint32_t t = threadIdx.x;
-  const uint32_t per = (tiles + kDecBlock - 1u) / kDecBlock;
-  const unsigned long long b64 = (unsigned long long)t * per;
-  const uint32_t b = b64 < tiles ? (uint32_t)b64 : tiles;
-  const uint32_t e = (tiles - b) < per ? tiles : b + per;
-  unsigned long long sum = 0;
-  for (uint32_t k = b; k < e; ++k) sum += tile_sums[k];
-  unsigned long long run = block_exclusive_scan64(sum, s);
-  for (uint32_t k = b; k < e; ++k) {
-    const unsigned long long c = tile_sums[k];
-    tile_sums[k] = run;
-    run += c;
-  }
-  if (t == kDecBlock - 1u) {
-    const uint32_t m = (uint32_t)run;
+  const unsigned long long sum = block_scan_owned_runs(
+      tiles, s, [&](uint32_t k) { return tile_sums[k]; },
+      [&](uint32_t k, unsigned long long before) { tile_sums[k] = before; });
+  if (threadIdx.x == 0) {
+    const uint32_t m = (uint32_t)sum;
     const bool ok = out_layout(m, sh_dim).total <= capacity;
     plan->m = m;
     plan->ok = ok ? 1u : 0u;
@@ -549,7 +539,7 @@ __global__ __launch_bounds__(kDecBlock) void spz_dec_apply_kernel(const uint8_t 
     bits |= (z ? 1u : 0u) << (8 + r);
     v += (f ? 1ull : 0ull) + (z ? (1ull << 32) : 0ull);
   }
-  unsigned long long run = tile_sums[blockIdx.x] + block_exclusive_scan64(v, s);
+  unsigned long long run = tile_sums[blockIdx.x] + block_exclusive_scan(v, s);
   for (uint32_t r = 0; r < kDecItems; ++r) {
     const unsigned long long i = first + r;
     if (i >= n) break;

@@ -31,7 +31,7 @@
 namespace spz_amd_detail {
 namespace {
 
-constexpr uint32_t kDnBlock = kOpsBlock;  // 256: block_sum and block_exclusive_scan64 are written for it
+constexpr uint32_t kDnBlock = kOpsBlock;  // 256: block_sum is written for it
 constexpr uint32_t kDnScanBlock = 1024;
 
 __device__ __forceinline__ bool finite_bits(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
@@ -162,28 +162,10 @@ __global__ __launch_bounds__(kDnBlock) void spz_densify_tile_count_kernel(const 
 __global__ __launch_bounds__(kDnScanBlock) void spz_densify_tile_scan_kernel(unsigned long long *counts, uint32_t tiles,
                                                                              unsigned long long *total) {
   __shared__ unsigned long long part[kDnScanBlock];
-  const uint32_t t = threadIdx.x;
-  const uint32_t per = (tiles + kDnScanBlock - 1u) / kDnScanBlock;
-  const unsigned long long b64 = (unsigned long long)t * per;
-  const uint32_t b = b64 < tiles ? (uint32_t)b64 : tiles;
-  const uint32_t e = (tiles - b) < per ? tiles : b + per;
-  unsigned long long s = 0;
-  for (uint32_t k = b; k < e; ++k) s += counts[k];
-  part[t] = s;
-  __syncthreads();
-  for (uint32_t off = 1; off < kDnScanBlock; off <<= 1) {
-    const unsigned long long v = t >= off ? part[t - off] : 0ull;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  unsigned long long run = part[t] - s;
-  for (uint32_t k = b; k < e; ++k) {
-    const unsigned long long c = counts[k];
-    counts[k] = run;
-    run += c;
-  }
-  if (t == kDnScanBlock - 1u) *total = part[t];
+  const unsigned long long sum = block_scan_owned_runs<unsigned long long, kDnScanBlock>(
+      tiles, part, [&](uint32_t k) { return counts[k]; },
+      [&](uint32_t k, unsigned long long before) { counts[k] = before; });
+  if (threadIdx.x == 0) *total = sum;
 }
 
 __global__ __launch_bounds__(kDnBlock) void spz_densify_emit_kernel(const PlanParams p) {
@@ -191,7 +173,7 @@ __global__ __launch_bounds__(kDnBlock) void spz_densify_emit_kernel(const PlanPa
   const unsigned long long i = (unsigned long long)blockIdx.x * kDnBlock + threadIdx.x;
   const uint32_t a = i < p.n ? p.action[i] : 3u;
   const uint32_t c = outputs_of(a);
-  const unsigned long long at = p.tile_counts[blockIdx.x] + block_exclusive_scan64(c, s);
+  const unsigned long long at = p.tile_counts[blockIdx.x] + block_exclusive_scan<unsigned long long>(c, s);
   if (c >= 1u && at < p.list_capacity) {
     p.parent[at] = (uint32_t)i;
     p.child[at] = (uint8_t)(a == 2u ? 2u : 0u);

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "spz_amd.h"
+#include "spz_block_ops.hpp"
 #include "spz_common.hpp"
 #include "spz_kernel_params.hpp"
 
@@ -112,28 +113,9 @@ __global__ __launch_bounds__(kSelBlock) void spz_select_kernel(const SelectParam
 __global__ __launch_bounds__(kScanBlock) void spz_select_scan_kernel(uint32_t *counts, uint32_t tiles,
                                                                      unsigned long long *total) {
   __shared__ uint32_t part[kScanBlock];
-  const uint32_t t = threadIdx.x;
-  const uint32_t per = (tiles + kScanBlock - 1u) / kScanBlock;
-  const unsigned long long b64 = (unsigned long long)t * per;
-  const uint32_t b = b64 < tiles ? (uint32_t)b64 : tiles;
-  const uint32_t e = (tiles - b) < per ? tiles : b + per;
-  uint32_t s = 0;
-  for (uint32_t k = b; k < e; ++k) s += counts[k];
-  part[t] = s;
-  __syncthreads();
-  for (uint32_t off = 1; off < kScanBlock; off <<= 1) {  // inclusive scan of the runs' sums
-    const uint32_t v = t >= off ? part[t - off] : 0u;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  uint32_t run = part[t] - s;
-  for (uint32_t k = b; k < e; ++k) {
-    const uint32_t c = counts[k];
-    counts[k] = run;
-    run += c;
-  }
-  if (t == kScanBlock - 1u) *total = part[t];
+  const uint32_t sum = block_scan_owned_runs<uint32_t, kScanBlock>(
+      tiles, part, [&](uint32_t k) { return counts[k]; }, [&](uint32_t k, uint32_t before) { counts[k] = before; });
+  if (threadIdx.x == 0) *total = sum;
 }
 
 __global__ __launch_bounds__(kSelBlock) void spz_compact_kernel(const CompactParams p) {

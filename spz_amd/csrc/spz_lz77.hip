@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "spz_amd.h"
+#include "spz_block_ops.hpp"
 #include "spz_common.hpp"
 #include "spz_huff_core.hpp"
 #include "spz_lz77_core.hpp"
@@ -847,16 +848,9 @@ __global__ __launch_bounds__(256) void lz_encode_kernel(const uint16_t *__restri
     bits += n0 + n1;
   });
   // exclusive scan of the runs' bit counts (a block's symbols take at most 32768 * 48 bits)
-  s_scan[tid] = bits;
-  __syncthreads();
-  for (uint32_t off = 1; off < kEncodeThreads; off <<= 1) {
-    const uint32_t v = tid >= off ? s_scan[tid - off] : 0u;
-    __syncthreads();
-    s_scan[tid] += v;
-    __syncthreads();
-  }
-  const uint32_t before = s_scan[tid] - bits;
-  if (tid == kEncodeThreads - 1) symbol_bits[b] = s_scan[tid];
+  uint32_t block_bits;
+  const uint32_t before = block_exclusive_scan<uint32_t, kEncodeThreads>(bits, s_scan, &block_bits);
+  if (tid == 0) symbol_bits[b] = block_bits;
   if (i0 >= i1) return;
   const unsigned long long at = blk.bit_start + blk.header_bits + before;
   BitSink sink = {body, at >> 5, 0ull, (uint32_t)(at & 31ull), true};

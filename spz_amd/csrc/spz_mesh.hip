@@ -290,7 +290,7 @@ __global__ __launch_bounds__(kMeshBlock) void spz_mesh_scan_sums_kernel(const ui
   for (uint32_t base = 0; base < blocks; base += kMeshBlock) {
     const uint32_t at = base + threadIdx.x;
     const unsigned long long v = at < blocks ? sums[at] : 0ull;
-    const unsigned long long pre = block_exclusive_scan64(v, s);
+    const unsigned long long pre = block_exclusive_scan(v, s);
     if (at < blocks) offsets[at] = carry + pre;
     carry += block_sum(v, s);
   }
@@ -311,7 +311,7 @@ __global__ __launch_bounds__(kMeshBlock) void spz_mesh_scan_apply_kernel(uint32_
     v[e] = base + e < n ? a[base + e] : 0u;
     sum += v[e];
   }
-  unsigned long long pre = block_exclusive_scan64(sum, s);
+  unsigned long long pre = block_exclusive_scan(sum, s);
   if (to_vertex) pre += offsets[blockIdx.x];
 #pragma unroll
   for (uint32_t e = 0; e < kScanPer; ++e) {

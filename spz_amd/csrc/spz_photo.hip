@@ -17,6 +17,7 @@
 #include <cstring>
 
 #include "spz_amd.h"
+#include "spz_block_ops.hpp"
 #include "spz_common.hpp"
 #include "spz_image_tile.hpp"
 #include "spz_photo_internal.hpp"
@@ -73,18 +74,13 @@ __global__ __launch_bounds__(kMtRedThreads) void spz_photo_exposure_reduce_kerne
                                                                                   uint32_t tiles,
                                                                                   double *__restrict__ out) {
   __shared__ double r[kMtRedThreads];
+  static_assert(kMtRedThreads == kOpsBlock, "block_sum is over 256 threads");
   const uint32_t tid = threadIdx.x;
   for (uint32_t k = 0; k < 12u; ++k) {
     double t = 0.0;
     for (uint32_t i = tid; i < tiles; i += kMtRedThreads) t += eslab[k * tiles + i];
-    r[tid] = t;
-    __syncthreads();
-    for (uint32_t s = kMtRedThreads / 2; s > 0; s >>= 1) {
-      if (tid < s) r[tid] += r[tid + s];
-      __syncthreads();
-    }
-    if (tid == 0) out[k] = r[0];
-    __syncthreads();  // the next value overwrites r
+    t = block_sum(t, r);
+    if (tid == 0) out[k] = t;
   }
 }
 

@@ -29,6 +29,7 @@
 #include <cstring>
 
 #include "spz_amd.h"
+#include "spz_block_ops.hpp"
 #include "spz_common.hpp"
 #include "spz_kernel_params.hpp"
 #include "spz_quant.hpp"
@@ -219,27 +220,7 @@ __global__ __launch_bounds__(kPreBlock) void spz_render_preprocess_kernel(const 
   tile_count[i] = count;
 }
 
-namespace {
-
-// Exclusive scan of v over the kScanBlock threads through s; returns this thread's prefix, *sum = the block total.
-__device__ __forceinline__ unsigned long long block_scan_u64(unsigned long long v, unsigned long long *s,
-                                                             unsigned long long *sum) {
-  const uint32_t t = threadIdx.x;
-  s[t] = v;
-  __syncthreads();
-  for (uint32_t off = 1; off < kScanBlock; off <<= 1) {
-    const unsigned long long u = t >= off ? s[t - off] : 0ull;
-    __syncthreads();
-    s[t] += u;
-    __syncthreads();
-  }
-  const unsigned long long r = s[t] - v;
-  *sum = s[kScanBlock - 1];
-  __syncthreads();
-  return r;
-}
-
-}  // namespace
+static_assert(kScanBlock == kOpsBlock, "the scans below run at the default block size");
 
 __global__ __launch_bounds__(kScanBlock) void spz_render_block_sums_kernel(const uint32_t *order, const uint32_t *tile_count,
                                                                            uint32_t n, unsigned long long *run_sums) {
@@ -251,7 +232,7 @@ __global__ __launch_bounds__(kScanBlock) void spz_render_block_sums_kernel(const
     if (k0 + r < n) v += tile_count[order[k0 + r]];
   }
   unsigned long long sum;
-  (void)block_scan_u64(v, s, &sum);
+  (void)block_exclusive_scan(v, s, &sum);
   if (threadIdx.x == 0) run_sums[blockIdx.x] = sum;
 }
 
@@ -260,21 +241,10 @@ __global__ __launch_bounds__(kScanBlock) void spz_render_scan_sums_kernel(unsign
                                                                           unsigned long long *total,
                                                                           unsigned long long *d_total) {
   __shared__ unsigned long long s[kScanBlock];
-  const uint32_t t = threadIdx.x;
-  const uint32_t per = (runs + kScanBlock - 1u) / kScanBlock;
-  const unsigned long long b64 = (unsigned long long)t * per;
-  const uint32_t b = b64 < runs ? (uint32_t)b64 : runs;
-  const uint32_t e = (runs - b) < per ? runs : b + per;
-  unsigned long long v = 0;
-  for (uint32_t k = b; k < e; ++k) v += run_sums[k];
-  unsigned long long sum;
-  unsigned long long run = block_scan_u64(v, s, &sum);
-  for (uint32_t k = b; k < e; ++k) {
-    const unsigned long long c = run_sums[k];
-    run_sums[k] = run;
-    run += c;
-  }
-  if (t == 0) {
+  const unsigned long long sum = block_scan_owned_runs(
+      runs, s, [&](uint32_t k) { return run_sums[k]; },
+      [&](uint32_t k, unsigned long long before) { run_sums[k] = before; });
+  if (threadIdx.x == 0) {
     *total = sum;
     *d_total = sum;
   }
@@ -308,8 +278,7 @@ __global__ __launch_bounds__(kScanBlock) void spz_render_emit_kernel(const EmitP
     c[r] = ok ? p.tile_count[g[r]] : 0u;
     v += c[r];
   }
-  unsigned long long sum;
-  unsigned long long off = p.run_offsets[blockIdx.x] + block_scan_u64(v, s, &sum);
+  unsigned long long off = p.run_offsets[blockIdx.x] + block_exclusive_scan(v, s);
 #pragma unroll
   for (uint32_t r = 0; r < kScanPer; ++r) {
     if (c[r] == 0u) continue;

@@ -5,9 +5,8 @@
 //                             depth, weight and colour tests first, then (when covering) the two rendered maps.  A flag
 //                             byte per sample (bit 0 valid, bit 1 selected) and the block's two counts.  A pure
 //                             streaming read: at stride 1 every plane is read coalesced, once.
-//   spz_seed_offsets_kernel   one block: the exclusive scan of the blocks' selected counts (a run of blocks per lane, the
-//                             runs placed by spz_block_ops.hpp's scan), the three totals (valid, appended, refused)
-//                             into d_counts.
+//   spz_seed_offsets_kernel   one block: the exclusive scan of the blocks' selected counts (spz_block_ops.hpp's owned-run
+//                             scan), the three totals (valid, appended, refused) into d_counts.
 //   spz_seed_emit_kernel      the same blocks again: a selected sample's rank is its block's offset plus the block scan
 //                             of the flags; rank < room writes the Gaussian at n + rank, the rest are the refused.  The
 //                             block's ranks are consecutive, so its sh rows are zeroed by all lanes together.  No
@@ -124,30 +123,22 @@ __global__ __launch_bounds__(kSeedBlock) void spz_seed_select_kernel(SeedLattice
   }
 }
 
-// One block.  Each lane owns a run of consecutive blocks: it sums its run, one block scan places the runs, and the lane
-// walks its run again with the running prefix.  d_counts: valid, appended = min(selected, room), refused = selected -
-// appended.
+// One block: the owned-run scan of the blocks' selected counts, whose total is the selected; each lane sums its run's
+// valid counts on the storing walk.  d_counts: valid, appended = min(selected, room), refused = selected - appended.
 __global__ __launch_bounds__(kSeedBlock) void spz_seed_offsets_kernel(const uint32_t *__restrict__ block_sel,
                                                                       const uint32_t *__restrict__ block_valid,
                                                                       uint32_t blocks, unsigned long long room,
                                                                       unsigned long long *__restrict__ offsets,
                                                                       unsigned long long *__restrict__ counts) {
   __shared__ unsigned long long s[kSeedBlock];
-  const uint32_t per = (blocks + kSeedBlock - 1u) / kSeedBlock;
-  const uint32_t lo = threadIdx.x * per < blocks ? threadIdx.x * per : blocks;
-  const uint32_t hi = lo + per < blocks ? lo + per : blocks;
-  unsigned long long sel = 0ull, valid = 0ull;
-  for (uint32_t b = lo; b < hi; ++b) {
-    sel += block_sel[b];
-    valid += block_valid[b];
-  }
-  unsigned long long pre = block_exclusive_scan64(sel, s);
-  const unsigned long long total = block_sum(sel, s);
+  unsigned long long valid = 0ull;
+  const unsigned long long total = block_scan_owned_runs(
+      blocks, s, [&](uint32_t b) { return (unsigned long long)block_sel[b]; },
+      [&](uint32_t b, unsigned long long before) {
+        offsets[b] = before;
+        valid += block_valid[b];
+      });
   valid = block_sum(valid, s);
-  for (uint32_t b = lo; b < hi; ++b) {
-    offsets[b] = pre;
-    pre += block_sel[b];
-  }
   if (threadIdx.x == 0u) {
     const unsigned long long appended = total < room ? total : room;
     counts[0] = valid;
@@ -172,7 +163,7 @@ __global__ __launch_bounds__(kSeedBlock) void spz_seed_emit_kernel(SeedLattice l
   if (count == 0u || first >= room) return;  // block-uniform
   const uint32_t sample = blockIdx.x * kSeedBlock + threadIdx.x;
   const bool selected = sample < l.samples && (flags[sample] & kSeedSelected) != 0u;
-  const unsigned long long rank = first + block_exclusive_scan64(selected ? 1ull : 0ull, s);
+  const unsigned long long rank = first + block_exclusive_scan(selected ? 1ull : 0ull, s);
   if (a.sh3) {  // the block's rows n + first .. n + min(first + count, room), zeroed together
     const unsigned long long last = first + count < room ? first + count : room;
     float *row = sh + (n + first) * a.sh3;

@@ -21,6 +21,7 @@
 #include <cstring>
 
 #include "spz_amd.h"
+#include "spz_block_ops.hpp"
 #include "spz_common.hpp"
 #include "spz_morton_walk.hpp"
 #include "spz_sort_internal.hpp"
@@ -28,7 +29,7 @@
 namespace spz_amd_detail {
 namespace {
 
-constexpr uint32_t kSortBlock = 256;
+constexpr uint32_t kSortBlock = kOpsBlock;                // 256
 constexpr uint32_t kSortWaves = kSortBlock / 64u;
 constexpr uint32_t kSortItems = 8;                        // points per thread and tile
 constexpr uint32_t kSortTile = kSortBlock * kSortItems;   // 2048 points per tile
@@ -70,22 +71,6 @@ __device__ __forceinline__ unsigned long long spread3_21(unsigned long long x) {
   x = (x | x << 4) & 0x10c30c30c30c30c3ull;
   x = (x | x << 2) & 0x1249249249249249ull;
   return x;
-}
-
-// Exclusive scan of v over the 256 threads of the block through s (256 entries); returns this thread's prefix.
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t *s) {
-  const uint32_t t = threadIdx.x;
-  s[t] = v;
-  __syncthreads();
-  for (uint32_t off = 1; off < kSortBlock; off <<= 1) {
-    const uint32_t u = t >= off ? s[t - off] : 0u;
-    __syncthreads();
-    s[t] += u;
-    __syncthreads();
-  }
-  const uint32_t r = s[t] - v;
-  __syncthreads();
-  return r;
 }
 
 }  // namespace
@@ -174,20 +159,9 @@ __global__ __launch_bounds__(kSortBlock) void spz_radix_hist_kernel(const uint32
 __global__ __launch_bounds__(kSortBlock) void spz_radix_scan_kernel(uint32_t *counts, uint32_t tiles, uint32_t *totals) {
   __shared__ uint32_t s[kSortBlock];
   uint32_t *row = counts + (unsigned long long)blockIdx.x * tiles;
-  const uint32_t t = threadIdx.x;
-  const uint32_t per = (tiles + kSortBlock - 1u) / kSortBlock;
-  const unsigned long long b64 = (unsigned long long)t * per;
-  const uint32_t b = b64 < tiles ? (uint32_t)b64 : tiles;
-  const uint32_t e = (tiles - b) < per ? tiles : b + per;
-  uint32_t sum = 0;
-  for (uint32_t k = b; k < e; ++k) sum += row[k];
-  uint32_t run = block_exclusive_scan(sum, s);
-  for (uint32_t k = b; k < e; ++k) {
-    const uint32_t c = row[k];
-    row[k] = run;
-    run += c;
-  }
-  if (t == kSortBlock - 1u) totals[blockIdx.x] = run;
+  const uint32_t sum = block_scan_owned_runs(
+      tiles, s, [&](uint32_t k) { return row[k]; }, [&](uint32_t k, uint32_t before) { row[k] = before; });
+  if (threadIdx.x == 0) totals[blockIdx.x] = sum;
 }
 
 __global__ __launch_bounds__(kSortBlock) void spz_radix_scatter_kernel(const PassParams p) {

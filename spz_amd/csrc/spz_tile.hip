@@ -133,21 +133,6 @@ __device__ __forceinline__ uint32_t root_level(const Pyramid &p) {
   return m;
 }
 
-__device__ __forceinline__ uint32_t block_exclusive_scan32(uint32_t v, uint32_t *s) {
-  const uint32_t t = threadIdx.x;
-  s[t] = v;
-  __syncthreads();
-  for (uint32_t off = 1; off < kBlock; off <<= 1) {
-    const uint32_t u = t >= off ? s[t - off] : 0u;
-    __syncthreads();
-    s[t] += u;
-    __syncthreads();
-  }
-  const uint32_t r = s[t] - v;
-  __syncthreads();
-  return r;
-}
-
 // Per-point bytes of the six sections of a stream of `version` with dim sh coefficients per channel.
 __device__ __host__ __forceinline__ void section_bytes(uint32_t version, uint32_t dim, uint32_t bpp[6]) {
   bpp[0] = 9;
@@ -242,7 +227,7 @@ __global__ __launch_bounds__(kBlock) void spz_tile_scan_reduce_kernel(const uint
   for (uint32_t r = 0; r < kScanItems; ++r) {
     if (first + r < n) v += (uint32_t)__popc(mask[first + r]);
   }
-  const uint32_t e = block_exclusive_scan32(v, sh);
+  const uint32_t e = block_exclusive_scan(v, sh);
   if (threadIdx.x == kBlock - 1u) sums[blockIdx.x] = e + v;
 }
 
@@ -250,23 +235,13 @@ __global__ __launch_bounds__(kBlock) void spz_tile_scan_reduce_kernel(const uint
 __global__ __launch_bounds__(kBlock) void spz_tile_scan_sums_kernel(uint32_t *sums, uint32_t count, uint32_t max_tiles,
                                                                     const Pyramid p, spz_amd_tile_summary *summary) {
   __shared__ unsigned long long sh[kBlock];
-  const uint32_t t = threadIdx.x;
-  const uint32_t per = (count + kBlock - 1u) / kBlock;
-  const unsigned long long b64 = (unsigned long long)t * per;
-  const uint32_t b = b64 < count ? (uint32_t)b64 : count;
-  const uint32_t e = (count - b) < per ? count : b + per;
-  unsigned long long sum = 0;
-  for (uint32_t k = b; k < e; ++k) sum += sums[k];
-  unsigned long long run = block_exclusive_scan64(sum, sh);
-  for (uint32_t k = b; k < e; ++k) {
-    const uint32_t c = sums[k];
-    sums[k] = (uint32_t)run;
-    run += c;
-  }
-  if (t == kBlock - 1u) {
-    summary->num_tiles = run;
+  const unsigned long long num_tiles = block_scan_owned_runs(
+      count, sh, [&](uint32_t k) { return (unsigned long long)sums[k]; },
+      [&](uint32_t k, unsigned long long before) { sums[k] = (uint32_t)before; });
+  if (threadIdx.x == 0) {
+    summary->num_tiles = num_tiles;
     summary->arena_bytes = 0;
-    summary->ok = run <= max_tiles ? 1u : 0u;
+    summary->ok = num_tiles <= max_tiles ? 1u : 0u;
     summary->root_level = root_level(p);
   }
 }
@@ -279,7 +254,7 @@ __global__ __launch_bounds__(kBlock) void spz_tile_scan_apply_kernel(const uint3
   for (uint32_t r = 0; r < kScanItems; ++r) {
     if (first + r < n) v += (uint32_t)__popc(mask[first + r]);
   }
-  uint32_t run = sums[blockIdx.x] + block_exclusive_scan32(v, sh);
+  uint32_t run = sums[blockIdx.x] + block_exclusive_scan(v, sh);
   for (uint32_t r = 0; r < kScanItems; ++r) {
     if (first + r >= n) break;
     toff[first + r] = run;
@@ -437,25 +412,16 @@ __global__ __launch_bounds__(kBlock) void spz_tile_offsets_kernel(uint32_t versi
                                                                   spz_amd_tile_summary *summary, spz_amd_tile_info *table) {
   __shared__ unsigned long long sh[kBlock];
   if (!summary->ok) return;
-  const uint32_t count = (uint32_t)summary->num_tiles;
-  const uint32_t t = threadIdx.x;
-  const uint32_t per = (count + kBlock - 1u) / kBlock;
-  const unsigned long long b64 = (unsigned long long)t * per;
-  const uint32_t b = b64 < count ? (uint32_t)b64 : count;
-  const uint32_t e = (count - b) < per ? count : b + per;
-  unsigned long long sum = 0;
-  for (uint32_t k = b; k < e; ++k) {
-    const unsigned long long bytes =
-        16ull + (unsigned long long)table[k].num_points * point_bytes(table[k].content_level < 0 ? version : 3u, dim);
-    table[k].bytes = bytes;
-    sum += (bytes + 15ull) & ~15ull;
-  }
-  unsigned long long run = block_exclusive_scan64(sum, sh);
-  for (uint32_t k = b; k < e; ++k) {
-    table[k].offset = run;
-    run += (table[k].bytes + 15ull) & ~15ull;
-  }
-  if (t == kBlock - 1u) summary->arena_bytes = run;
+  auto bytes_of = [&](uint32_t k) {
+    return 16ull + (unsigned long long)table[k].num_points * point_bytes(table[k].content_level < 0 ? version : 3u, dim);
+  };
+  const unsigned long long arena_bytes = block_scan_owned_runs(
+      (uint32_t)summary->num_tiles, sh, [&](uint32_t k) { return (bytes_of(k) + 15ull) & ~15ull; },
+      [&](uint32_t k, unsigned long long before) {
+        table[k].bytes = bytes_of(k);
+        table[k].offset = before;
+      });
+  if (threadIdx.x == 0) summary->arena_bytes = arena_bytes;
 }
 
 // The n == 0 tree: one empty leaf.
@@ -487,31 +453,24 @@ __global__ __launch_bounds__(kBlock) void spz_tile_worklist_kernel(spz_amd_tile_
                                                                    int level, uint32_t *prefix) {
   __shared__ uint32_t sh[kBlock];
   count = rows_of(summary, count);
-  const uint32_t t = threadIdx.x;
-  const uint32_t per = (count + kBlock - 1u) / kBlock;
-  const unsigned long long b64 = (unsigned long long)t * per;
-  const uint32_t b = b64 < count ? (uint32_t)b64 : count;
-  const uint32_t e = (count - b) < per ? count : b + per;
-  uint32_t sum = 0;
-  for (uint32_t k = b; k < e; ++k) {
-    if (table[k].content_level != level) continue;
-    const uint32_t c = (table[k].num_points + kChunk - 1u) / kChunk;
-    sum += c ? c : 1u;
-    int32_t *lo = reinterpret_cast<int32_t *>(table[k].box_min), *hi = reinterpret_cast<int32_t *>(table[k].box_max);
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = 0x7fffffff;
-      hi[a] = (int32_t)0x80000000;
-    }
-    *reinterpret_cast<uint32_t *>(&table[k].max_radius) = 0u;
-  }
-  uint32_t run = block_exclusive_scan32(sum, sh);
-  for (uint32_t k = b; k < e; ++k) {
-    prefix[k] = run;
-    if (table[k].content_level != level) continue;
-    const uint32_t c = (table[k].num_points + kChunk - 1u) / kChunk;
-    run += c ? c : 1u;
-  }
-  if (t == kBlock - 1u) prefix[count] = run;
+  const uint32_t items = block_scan_owned_runs(
+      count, sh,
+      [&](uint32_t k) {
+        if (table[k].content_level != level) return 0u;
+        const uint32_t c = (table[k].num_points + kChunk - 1u) / kChunk;
+        return c ? c : 1u;
+      },
+      [&](uint32_t k, uint32_t before) {
+        prefix[k] = before;
+        if (table[k].content_level != level) return;
+        int32_t *lo = reinterpret_cast<int32_t *>(table[k].box_min), *hi = reinterpret_cast<int32_t *>(table[k].box_max);
+        for (int a = 0; a < 3; ++a) {
+          lo[a] = 0x7fffffff;
+          hi[a] = (int32_t)0x80000000;
+        }
+        *reinterpret_cast<uint32_t *>(&table[k].max_radius) = 0u;
+      });
+  if (threadIdx.x == 0) prefix[count] = items;
 }
 
 namespace {

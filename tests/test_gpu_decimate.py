@@ -184,6 +184,18 @@ def test_edge_sizes_and_flags(spz, oracle, tmp_path):
                 check(oracle, raw, level, got, parents)
 
 
+def test_odd_tile_count_past_one_block(spz, oracle, tmp_path):
+    """257 tiles of 2048 points for the 256 threads of spz_dec_scan_kernel: runs of two tile sums, the last owning thread
+    holds one, half the block holds none."""
+    n = 524_289
+    tiles = -(-n // 2048)
+    assert tiles % 2 == 1 and 256 < tiles < 2 * 256
+    raw = cloud_stream(oracle, n, 0, n + 1)
+    (lv, pts, parents), got = run_file(spz, tmp_path, raw, level=12)
+    assert lv == 12 and pts == level_counts(raw)[12]
+    check(oracle, raw, 12, got, parents)
+
+
 def test_cells_crossing_wave_and_tile_edges(spz, oracle, tmp_path):
     """Runs of equal and of nearby positions whose cells begin and end on every side of 64- and 2048-point edges."""
     raw = cloud_stream(oracle, 6000, 1, 12)

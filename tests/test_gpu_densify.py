@@ -153,8 +153,15 @@ def planted_mix(n, seed, ref_lim):
     return accum, denom, scales, alphas, ties
 
 
-@pytest.mark.parametrize("n", [257, 70001, 300001])
+ODD_RUNS_N = 262_145   # 1025 tiles of 256 Gaussians for the 1024 threads of the second level: runs of two sums, the last
+                       # owning thread holds one, half the block holds none
+
+
+@pytest.mark.parametrize("n", [257, 70001, ODD_RUNS_N, 300001])
 def test_plan_of_a_planted_mix(cuda, n):
+    if n == ODD_RUNS_N:
+        tiles = -(-n // 256)
+        assert tiles % 2 == 1 and 1024 < tiles < 2 * 1024
     _, ref = limits(percent_dense=0.05)
     accum, denom, scales, alphas, ties = planted_mix(n, n, ref)
     action, counts = run_plan(cuda, accum, denom, scales, alphas, 2 * n, percent_dense=0.05)   # every candidate granted

@@ -134,10 +134,17 @@ def test_box_and_min_alpha_equal_the_predicate_on_the_decoded_floats(spz, tmp_pa
         assert {1, 2} <= set(D.select(st, hdr, min_alpha=np.inf).cpu().numpy())    # byte 255 decodes to +inf
 
 
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 1023, 1024, 1025, 4097])
+ODD_RUNS_N = 1_048_577   # 1025 select tiles of 1024 points for the 1024 threads of the offset scan: runs of two counts,
+                         # the last owning thread holds one, half the block holds none
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 1023, 1024, 1025, 4097, ODD_RUNS_N])
 def test_sizes_around_the_wave_and_the_tile(spz, tmp_path, oracle, n):
     from spz_amd.synth import make_cloud_numpy
-    deg = 3 if n % 2 else 2
+    deg = 0 if n == ODD_RUNS_N else 3 if n % 2 else 2
+    if n == ODD_RUNS_N:
+        tiles = -(-n // 1024)
+        assert tiles % 2 == 1 and 1024 < tiles < 2 * 1024
     raw = oracle.pack(make_cloud_numpy(n, deg, 100 + n), n, deg, True, 6).tobytes()
     rng = np.random.default_rng(n)
     mask = (rng.random(n) < 0.5).astype(np.uint8) * rng.integers(1, 255, n).astype(np.uint8)

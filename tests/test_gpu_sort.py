@@ -130,10 +130,17 @@ def test_idempotent_and_filter_undoes_it(spz, tmp_path, oracle):
     assert zlib.decompress(back.read_bytes(), 31) == raw
 
 
-@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, TILE - 1, TILE, TILE + 1, (1 << 20) + 3, 10_000_000])
+ODD_RUNS_N = 256 * TILE + 1   # 257 tiles for the 256 threads of the row scan: runs of two counts, the last owning thread
+                              # holds one, half the block holds none
+
+
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, TILE - 1, TILE, TILE + 1, ODD_RUNS_N, (1 << 20) + 3, 10_000_000])
 def test_device_argsort_equals_numpy(cuda, n):
     import torch
     from spz_amd import device as D
+    if n == ODD_RUNS_N:
+        tiles = -(-n // TILE)
+        assert n == 524_289 and tiles % 2 == 1 and 256 < tiles < 2 * 256
     rng = np.random.default_rng(n)
     special = np.array([0.0, -0.0, np.inf, -np.inf, np.nan, -np.nan, 1.0, -1.0], np.float32)
     cases = {"random": rng.standard_normal(n).astype(np.float32),
