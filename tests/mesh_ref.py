@@ -113,9 +113,11 @@ def integrate(grid, vol, view, depth, image, kind=MEDIAN, min_alpha=0.5):
     return ok
 
 
-def extract(grid, vol, min_weight=1.0):
+def extract(grid, vol, min_weight=1.0, return_ids=False):
     """(vertices (n_v, 3) float32, colors (n_v, 3) float32, triangles (n_t, 3) uint32) of grid ((5, nz, ny, nx)
-    float32) in the contract's order: vertices by ascending edge id, triangles by cube, tet, case."""
+    float32) in the contract's order: vertices by ascending edge id, triangles by cube, tet, case.  With return_ids
+    two more: the edge id 7 lin(a) + code - 1 of every vertex (n_v, int64) and the linear index of the cube of every
+    triangle (n_t, int64), which say where in the device's two scans a vertex and a triangle come from."""
     nx, ny, nz = vol["dims"]
     corners, ntri, edges = tet_table()
     W = grid[0].reshape(-1)
@@ -133,7 +135,7 @@ def extract(grid, vol, min_weight=1.0):
         cm |= inside[sl].astype(np.int64) << c
     active = valid & (cm != 0) & (cm != 255)
     off = lambda c: (c & 1) + ((c >> 1) & 1) * nx + ((c >> 2) & 1) * nx * ny
-    tri_edges = []
+    tri_edges, tri_cubes = [], []
     for k, j, i in zip(*np.nonzero(active)):   # ascending cube linear index
         lin = (int(k) * ny + int(j)) * nx + int(i)
         m8 = int(cm[k, j, i])
@@ -146,6 +148,7 @@ def extract(grid, vol, min_weight=1.0):
                     ca, cb = int(corners[t][va]), int(corners[t][vb])
                     ids.append(7 * (lin + off(ca)) + (cb - ca) - 1)
                 tri_edges.append(ids)
+                tri_cubes.append(lin)
     tri_edges = np.array(tri_edges, dtype=np.int64).reshape(-1, 3)
     used = np.unique(tri_edges)
     triangles = np.searchsorted(used, tri_edges).astype(np.uint32)
@@ -161,7 +164,8 @@ def extract(grid, vol, min_weight=1.0):
     vertices = (lo[None, :] + (idx + t[:, None] * delta) * s).astype(np.float32)
     colors = np.stack([(col[c][a].astype(np.float64) + t * (col[c][b].astype(np.float64) - col[c][a].astype(np.float64)))
                        for c in range(3)], axis=1).astype(np.float32)
-    return vertices.reshape(-1, 3), colors.reshape(-1, 3), triangles.reshape(-1, 3)
+    mesh = vertices.reshape(-1, 3), colors.reshape(-1, 3), triangles.reshape(-1, 3)
+    return mesh + (used, np.array(tri_cubes, dtype=np.int64)) if return_ids else mesh
 
 
 def grid_from_field(f, valid=None, color=None):
@@ -184,6 +188,35 @@ def edge_counts(triangles):
             k = (min(e), max(e))
             und[k] = und.get(k, 0) + 1
     return und, dire
+
+
+def edge_multiplicity(triangles):
+    """edge_counts for a large mesh, without the dicts: (edges (m, 2) int64 with a < b, the number of triangles on each
+    of them (m), the number of triangles on each directed edge (one entry per distinct directed edge))."""
+    t = np.asarray(triangles, np.int64).reshape(-1, 3)
+    a = np.concatenate([t[:, 0], t[:, 1], t[:, 2]])
+    b = np.concatenate([t[:, 1], t[:, 2], t[:, 0]])
+    n = int(t.max()) + 1 if t.size else 1
+    _, directed = np.unique(a * n + b, return_counts=True)
+    key, undirected = np.unique(np.minimum(a, b) * n + np.maximum(a, b), return_counts=True)
+    return np.stack([key // n, key % n], axis=1), undirected, directed
+
+
+# ---- where in the device's scans an id lies (spz_mesh.hip: blocks of kScanTile values, their sums 256 at a time) ------
+SCAN_TILE, SCAN_CHUNK = 2048, 256
+
+
+def scan_blocks(count):
+    """The blocks of a scan over `count` values."""
+    return -(-int(count) // SCAN_TILE)
+
+
+def scan_chunk_counts(ids, count):
+    """How many of `ids` (positions in a scan over `count` values) fall into each chunk of 256 blocks: one entry per
+    chunk the scan walks."""
+    ids = np.asarray(ids, np.int64)
+    assert ids.size == 0 or (ids.min() >= 0 and ids.max() < count)
+    return np.bincount(ids // SCAN_TILE // SCAN_CHUNK, minlength=-(-scan_blocks(count) // SCAN_CHUNK))
 
 
 def euler_characteristic(num_vertices, triangles):
@@ -224,9 +257,9 @@ def plane_field():
     return x - 7.0
 
 
-def field_color():
-    x, y, z = field_coords()
-    return np.stack([x / 20.0, y / 18.0, z / 22.0]).astype(np.float32)
+def field_color(dims=FIELD_DIMS):
+    x, y, z = field_coords(dims)
+    return np.stack([x / float(dims[0]), y / float(dims[1]), z / float(dims[2])]).astype(np.float32)
 
 
 def analytic_grids():

@@ -73,12 +73,14 @@ def assert_mesh_equal(got, want, what=""):
 
 
 # ---- the fuse --------------------------------------------------------------------------------------------------------
-def hand_made_views():
-    """Three views of the lattice with depth and image arrays that reach every branch of the fuse."""
+def hand_made_views(ms=None):
+    """Three views of the lattice (or the poses `ms`, the second one with the farther near plane) with depth and image
+    arrays that reach every branch of the fuse."""
     rng = np.random.default_rng(23)
-    ms = [RR.look_at([0.1, -0.05, -3.0], [0, 0, 0], [0, 1, 0]),        # outside: the lattice overflows the image
-          RR.look_at([0.2, 0.1, -0.5], [0.1, 0.3, 1.0], [0, 1, 0]),    # inside the lattice: points behind `near`
-          RR.look_at([3.1, 0.4, 0.3], [0, 0, 0], [0, 0, 1])]           # from +x, z up
+    if ms is None:
+        ms = [RR.look_at([0.1, -0.05, -3.0], [0, 0, 0], [0, 1, 0]),        # outside: the lattice overflows the image
+              RR.look_at([0.2, 0.1, -0.5], [0.1, 0.3, 1.0], [0, 1, 0]),    # inside the lattice: points behind `near`
+              RR.look_at([3.1, 0.4, 0.3], [0, 0, 0], [0, 0, 1])]           # from +x, z up
     out = []
     for k, m in enumerate(ms):
         p = params(m, near=0.2 if k != 1 else 0.35)
@@ -97,39 +99,44 @@ def hand_made_views():
     return out
 
 
-@pytest.mark.parametrize("kind", ["median", "expected"])
-def test_integrate_equals_the_reference_bit_for_bit(cuda, D, kind):
+def fuse_views_and_compare(cuda, D, grid, want, vol, rvol, views, kind):
+    """Fuses `views` into the device's `grid` and the reference's `want`, comparing after every view.  Returns what the
+    views reach, from the reference's own intermediate values, and the lattice points some view updated."""
     import torch
-    vol, rvol = volumes()
-    grid = D.tsdf_alloc(vol, cuda)
-    assert tuple(grid.shape) == (5, DIMS[2], DIMS[1], DIMS[0]) and not grid.any()
-    want = np.zeros((5, DIMS[2], DIMS[1], DIMS[0]), np.float32)
     rk = MR.MEDIAN if kind == "median" else MR.EXPECTED
     reached = {"near": False, "off_image": False, "behind": False, "front": False, "updated": False}
-    for p, depth, image in hand_made_views():
+    touched = np.zeros(want.shape[1:], bool)
+    for p, depth, image in views:
         D.tsdf_integrate(grid, vol, p, torch.from_numpy(depth).to(cuda), torch.from_numpy(image).to(cuda), depth_kind=kind,
                          min_alpha=0.5)
         before = want.copy()
         ok = MR.integrate(want, rvol, ref_view(p), depth, image, rk, 0.5)
         assert_grid_equal(grid, want)
-        # what the hand-made arrays reach, from the reference's own intermediate values
         pts = MR.lattice_points(rvol)
         M = ref_view(p)["world_to_camera"].astype(np.float64)
         z = pts @ M[2, :3] + M[2, 3]
         reached["near"] |= bool((z <= p.near_plane).any())
         u = np.floor(p.fx * ((pts @ M[0, :3] + M[0, 3]) / z) + p.cx)
-        reached["off_image"] |= bool(((z > p.near_plane) & ((u < 0) | (u >= W))).any())
+        reached["off_image"] |= bool(((z > p.near_plane) & ((u < 0) | (u >= p.width))).any())
         d = (want[1] - before[1])[ok]
         reached["front"] |= bool((d == 1.0).any())                     # sdf > truncation: clamped to 1
         reached["behind"] |= bool((~ok).any())
         reached["updated"] |= bool(ok.any())
+        touched |= ok
+    return reached, touched
+
+
+@pytest.mark.parametrize("kind", ["median", "expected"])
+def test_integrate_equals_the_reference_bit_for_bit(cuda, D, kind):
+    vol, rvol = volumes()
+    grid = D.tsdf_alloc(vol, cuda)
+    assert tuple(grid.shape) == (5, DIMS[2], DIMS[1], DIMS[0]) and not grid.any()
+    want = np.zeros((5, DIMS[2], DIMS[1], DIMS[0]), np.float32)
+    reached, _ = fuse_views_and_compare(cuda, D, grid, want, vol, rvol, hand_made_views(), kind)
     assert all(reached.values()), reached
     assert want[0].max() == 3.0 and (want[0] == 0).any()
     # a second pass over the same views accumulates
-    for p, depth, image in hand_made_views():
-        D.tsdf_integrate(grid, vol, p, torch.from_numpy(depth).to(cuda), torch.from_numpy(image).to(cuda), depth_kind=kind)
-        MR.integrate(want, rvol, ref_view(p), depth, image, rk, 0.5)
-    assert_grid_equal(grid, want)
+    fuse_views_and_compare(cuda, D, grid, want, vol, rvol, hand_made_views(), kind)
     assert want[0].max() == 6.0
 
 
@@ -223,11 +230,17 @@ def test_extract_min_weight_and_no_crossing(cuda, D):
 
 
 def test_emit_capacity_one_short_writes_nothing(cuda, D):
+    g, vol, want = analytic("sphere")
+    check_capacity_one_short(cuda, g, vol, want)
+
+
+def check_capacity_one_short(cuda, g, vol, want):
+    """The count / emit pair of the C ABI on grid `g`: the counts are those of the mesh `want`, an emit whose capacity is
+    one short of either is refused and writes nothing, and the emit after it gives `want`."""
     import ctypes as C
     import torch
     from spz_amd import abi
     L = abi.load_library()
-    g, vol, want = analytic("sphere")
     nv, nt = len(want[0]), len(want[2])
     grid = torch.from_numpy(g).to(cuda)
     ws = torch.empty(int(L.spz_amd_mesh_workspace_bytes(C.byref(vol))), dtype=torch.uint8, device=cuda)

@@ -488,6 +488,69 @@ def test_ref_plane_through_lattice_points(analytic):
     assert MR.euler_characteristic(len(v), t) == 1
 
 
+@pytest.mark.parametrize("name", ["sphere", "torus", "half_sphere", "plane"])
+def test_ref_extract_ids_reproduce_the_mesh(analytic, name):
+    v, c, t, g, vol = analytic[name]
+    got = MR.extract(g, vol, return_ids=True)
+    assert len(got) == 5 and all(np.array_equal(a, b) for a, b in zip(got[:3], (v, c, t))), "the mesh itself is unchanged"
+    used, cubes = got[3], got[4]
+    nx, ny, nz = vol["dims"]
+    # a vertex per edge id, ascending; the vertex from the id alone: a = id // 7, the direction id % 7 + 1
+    assert used.shape == (len(v),) and (np.diff(used) > 0).all() and used.min() >= 0 and used.max() < 7 * nx * ny * nz
+    a, code = used // 7, used % 7 + 1
+    delta = np.stack([code & 1, (code >> 1) & 1, (code >> 2) & 1], axis=1)
+    b = a + delta[:, 0] + delta[:, 1] * nx + delta[:, 2] * nx * ny
+    with np.errstate(all="ignore"):
+        f = (g[1].reshape(-1) / g[0].reshape(-1)).astype(np.float32).astype(np.float64)
+    assert ((f[a] < 0) != (f[b] < 0)).all(), "an edge of the list does not cross the surface"
+    s = f[a] / (f[a] - f[b])
+    at = np.stack([a % nx, (a // nx) % ny, a // (nx * ny)], axis=1)
+    assert np.array_equal(v, (at + s[:, None] * delta).astype(np.float32))          # lo = 0, unit spacing
+    # a cube per triangle, ascending; its three edges join corners of that cube
+    assert cubes.shape == (len(t),) and (np.diff(cubes) >= 0).all()
+    corner = lambda p: np.stack([p % nx, (p // nx) % ny, p // (nx * ny)], axis=-1)   # noqa: E731
+    for end in (a, b):
+        off = corner(end[t.astype(np.int64)]) - corner(cubes)[:, None, :]
+        assert ((off == 0) | (off == 1)).all()
+    inside = f.reshape(nz, ny, nx) < 0
+    ok = (g[0] >= 1).reshape(nz, ny, nx)
+    some, every, valid = (np.zeros((nz - 1, ny - 1, nx - 1), bool), np.ones((nz - 1, ny - 1, nx - 1), bool),
+                          np.ones((nz - 1, ny - 1, nx - 1), bool))
+    for dz, dy, dx in itertools.product(range(2), repeat=3):
+        sl = (slice(dz, nz - 1 + dz), slice(dy, ny - 1 + dy), slice(dx, nx - 1 + dx))
+        some, every, valid = some | inside[sl], every & inside[sl], valid & ok[sl]
+    k, j, i = np.nonzero(valid & some & ~every)
+    assert np.array_equal(np.unique(cubes), (k * ny + j) * nx + i), "the cubes the surface crosses, each with a triangle"
+
+
+@pytest.mark.parametrize("name", ["sphere", "torus", "half_sphere", "plane"])
+def test_ref_edge_multiplicity_equals_edge_counts(analytic, name):
+    _, _, t, _, _ = analytic[name]
+    und, dire = MR.edge_counts(t)
+    edges, per_edge, per_directed = MR.edge_multiplicity(t)
+    assert {(int(a), int(b)): int(k) for (a, b), k in zip(edges, per_edge)} == und
+    assert sorted(per_directed.tolist()) == sorted(dire.values())
+    assert len(edges) == len(t) + (t.max() + 1) - MR.euler_characteristic(t.max() + 1, t)
+    e, u, d = MR.edge_multiplicity(np.zeros((0, 3), np.uint32))
+    assert e.shape == (0, 2) and len(u) == 0 and len(d) == 0
+
+
+def test_ref_scan_chunks_and_field_color():
+    assert (MR.SCAN_TILE, MR.SCAN_CHUNK) == (2048, 256)
+    assert [MR.scan_blocks(n) for n in (1, 2048, 2049, 524288, 524289, 7 * 524288, 638685, 7 * 638685)] == \
+        [1, 1, 2, 256, 257, 1792, 312, 2184]
+    assert MR.scan_chunk_counts([0, 524287, 524288, 638684], 638685).tolist() == [2, 2]
+    assert MR.scan_chunk_counts([524287], 524288).tolist() == [1]
+    assert MR.scan_chunk_counts([], 7 * 638685).tolist() == [0] * 9
+    assert MR.scan_chunk_counts([8 * 524288], 7 * 638685).tolist() == [0] * 8 + [1]
+    for bad in ([-1], [524288]):
+        with pytest.raises(AssertionError):
+            MR.scan_chunk_counts(bad, 524288)
+    x, y, z = MR.field_coords()
+    assert np.array_equal(MR.field_color(), np.stack([x / 20.0, y / 18.0, z / 22.0]).astype(np.float32))
+    assert MR.field_color((5, 3, 2)).shape == (3, 2, 3, 5) and MR.field_color((5, 3, 2)).max() == np.float32(0.8)
+
+
 def test_ref_integrate_on_a_wall():
     """One view looking down +z at a wall at depth 2: W counts the views, S / W is the truncated signed distance along
     z, and occluded, out-of-frustum and near-clipped points are not written."""
