@@ -712,17 +712,8 @@ int blend_impl(uint64_t n, const spz_amd_render_params *params, uint64_t m, floa
                hipStream_t st) {
   const RenderLayout wl = render_layout(n, m);
   BlendParams b = {};
-  b.rec = reinterpret_cast<const spz_amd_render_record *>(base + wl.rec);
-  b.sorted_gid = m ? reinterpret_cast<const uint32_t *>(ent + wl.sorted_gid) : nullptr;
-  b.ranges = m ? reinterpret_cast<const uint2 *>(ent + wl.ranges) : nullptr;  // read only when the total is > 0
-  b.total = reinterpret_cast<const unsigned long long *>(base + wl.total);
+  const dim3 grid = fill_blend_params(b, wl, base, ent, params, m);
   b.image = d_image;
-  b.max_entries = m;
-  b.width = params->width;
-  b.height = params->height;
-  b.tiles_x = (params->width + kTile - 1) / kTile;
-  for (int k = 0; k < 3; ++k) b.bg[k] = params->background[k];
-  const dim3 grid(b.tiles_x, (params->height + kTile - 1) / kTile);
   hipLaunchKernelGGL(spz_render_blend_kernel, grid, dim3(kBlendThreads), 0, st, b);
   SPZ_HIP_TRY(hipGetLastError());
   return SPZ_AMD_OK;
@@ -732,19 +723,10 @@ int score_impl(uint64_t n, const spz_amd_render_params *params, uint64_t m, floa
                float *d_weight_max, uint8_t *base, uint8_t *ent, hipStream_t st) {
   const RenderLayout wl = render_layout(n, m);
   ScoreParams b = {};
-  b.rec = reinterpret_cast<const spz_amd_render_record *>(base + wl.rec);
-  b.sorted_gid = m ? reinterpret_cast<const uint32_t *>(ent + wl.sorted_gid) : nullptr;
-  b.ranges = m ? reinterpret_cast<const uint2 *>(ent + wl.ranges) : nullptr;  // read only when the total is > 0
-  b.total = reinterpret_cast<const unsigned long long *>(base + wl.total);
+  const dim3 grid = fill_blend_params(b, wl, base, ent, params, m);
   b.image = d_image;
   b.weight_sum = reinterpret_cast<unsigned long long *>(d_weight_sum);
   b.weight_max = reinterpret_cast<uint32_t *>(d_weight_max);
-  b.max_entries = m;
-  b.width = params->width;
-  b.height = params->height;
-  b.tiles_x = (params->width + kTile - 1) / kTile;
-  for (int k = 0; k < 3; ++k) b.bg[k] = params->background[k];
-  const dim3 grid(b.tiles_x, (params->height + kTile - 1) / kTile);
   hipLaunchKernelGGL(spz_render_score_kernel, grid, dim3(kBlendThreads), 0, st, b);
   SPZ_HIP_TRY(hipGetLastError());
   return SPZ_AMD_OK;
@@ -754,19 +736,10 @@ int depth_impl(uint64_t n, const spz_amd_render_params *params, uint64_t m, floa
                uint32_t *d_index, uint8_t *base, uint8_t *ent, hipStream_t st) {
   const RenderLayout wl = render_layout(n, m);
   DepthParams b = {};
-  b.rec = reinterpret_cast<const spz_amd_render_record *>(base + wl.rec);
-  b.sorted_gid = m ? reinterpret_cast<const uint32_t *>(ent + wl.sorted_gid) : nullptr;
-  b.ranges = m ? reinterpret_cast<const uint2 *>(ent + wl.ranges) : nullptr;  // read only when the total is > 0
-  b.total = reinterpret_cast<const unsigned long long *>(base + wl.total);
+  const dim3 grid = fill_blend_params(b, wl, base, ent, params, m);
   b.image = d_image;
   b.depth = d_depth;
   b.index = d_index;
-  b.max_entries = m;
-  b.width = params->width;
-  b.height = params->height;
-  b.tiles_x = (params->width + kTile - 1) / kTile;
-  for (int k = 0; k < 3; ++k) b.bg[k] = params->background[k];
-  const dim3 grid(b.tiles_x, (params->height + kTile - 1) / kTile);
   hipLaunchKernelGGL(spz_render_depth_kernel, grid, dim3(kBlendThreads), 0, st, b);
   SPZ_HIP_TRY(hipGetLastError());
   return SPZ_AMD_OK;

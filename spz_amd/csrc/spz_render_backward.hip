@@ -10,12 +10,13 @@
 //                                          summed over the wave by DPP, one lane per wave adds them into the batch's
 //                                          LDS slots, and each non-zero slot value goes to the n x 9 record gradients
 //                                          by one global f32 atomic.
-//   spz_render_depth_blend_backward_kernel the same kernel with the depth sum of spz_render_depth_kernel in it ("render
-//                                          depth backward"; DESIGN §8 "Depth fit"): the record's depth, less the
-//                                          depth of the tile's first entry, rides in the
-//                                          .w of the staged rgb, D is blended beside the colour, and a tenth value per
-//                                          used pair, dL/dz, goes to an array of its own (n floats), so the n x 9
-//                                          layout stays what the chain and the view backward read.
+//   spz_render_depth_blend_backward_kernel the same body (blend_backward_body, which both kernels instantiate) with the
+//                                          depth sum of spz_render_depth_kernel in it ("render depth backward"; DESIGN
+//                                          §8 "Depth fit"): the record's depth, less the depth of the tile's first
+//                                          entry, rides in the .w of the staged rgb, D is blended beside the colour,
+//                                          and a tenth value per used pair, dL/dz, goes to an array of its own (n
+//                                          floats), so the n x 9 layout stays what the chain and the view backward
+//                                          read.
 //   spz_render_preprocess_backward_kernel  one lane per Gaussian, f64 like the forward preprocess: the forward's
 //                                          intermediates again from the floats and the camera, then the chain from the
 //                                          nine record gradients to positions, log scales, raw quaternion, alpha,
@@ -53,168 +54,25 @@ struct BlendBackwardParams {
   float bg[3];
 };
 
-// power, a, T' and the three tests are the expressions of spz_render_blend_kernel, so both passes use the pairs the
-// image used.  With I = C + T_final bg and alpha = 1 - T_final, g the pixel's gradient, and for a used pair i
-// (T before it, w = T a, C_i the prefix that includes it):
-//   dL/drgb_i = w g_rgb
-//   dL/da_i   = T (g_rgb . rgb_i) - (g_rgb . (C_final - C_i) + T_final (g_rgb . bg - g_alpha)) / (1 - a)
-// a = min(0.99, opacity e^power) hands dL/da to opacity and power only where it does not clamp.
-__global__ __launch_bounds__(kBlendThreads) void spz_render_blend_backward_kernel(const BlendBackwardParams p) {
-  __shared__ float2 s_xy[kBlendThreads];
-  __shared__ float4 s_co[kBlendThreads];   // conic A, B, C, opacity
-  __shared__ float4 s_rgb[kBlendThreads];
-  __shared__ float s_grad[kRecGrads][kBlendThreads];
-  const unsigned long long total = *p.total;
-  if (total > p.max_entries) return;
-  const uint32_t t = threadIdx.x;
-  const uint32_t u = blockIdx.x * kTile + (t % kTile), v = blockIdx.y * kTile + (t / kTile);
-  const bool inside = u < p.width && v < p.height;
-  uint32_t begin = 0, end = 0;
-  if (total != 0ull) {
-    const uint2 r = p.ranges[blockIdx.y * p.tiles_x + blockIdx.x];
-    begin = r.x;
-    end = r.y;
-  }
-  if (begin >= end) return;  // workgroup-uniform: nothing blends here
-  const float fu = (float)u, fv = (float)v;
-  // the forward blend, for the pixel's final colour sum and T
-  float T = 1.0f, c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
-  bool done = !inside;
-  for (uint32_t base = begin; base < end; base += kBlendThreads) {
-    // also the barrier between the previous batch's reads and this batch's writes
-    if (__syncthreads_count(done ? 1 : 0) == (int)kBlendThreads) break;
-    const uint32_t j = base + t;
-    if (j < end) {
-      const spz_amd_render_record &q = p.rec[p.sorted_gid[j]];
-      s_xy[t] = make_float2(q.mean[0], q.mean[1]);
-      s_co[t] = make_float4(q.conic[0], q.conic[1], q.conic[2], q.opacity);
-      s_rgb[t] = make_float4(q.rgb[0], q.rgb[1], q.rgb[2], 0.0f);
-    }
-    __syncthreads();
-    const uint32_t cnt = (end - base) < kBlendThreads ? end - base : kBlendThreads;
-    for (uint32_t k = 0; k < cnt && !done; ++k) {
-      const float2 xy = s_xy[k];
-      const float4 co = s_co[k];
-      const float dx = fu - xy.x, dy = fv - xy.y;
-      const float power = -0.5f * (co.x * dx * dx + co.z * dy * dy) - co.y * dx * dy;
-      if (power > 0.0f) continue;
-      const float a = fminf(0.99f, co.w * expf(power));
-      if (a < 1.0f / 255.0f) continue;
-      const float Tn = T * (1.0f - a);
-      if (Tn < 1e-4f) {
-        done = true;
-        break;
-      }
-      const float4 rgb = s_rgb[k];
-      const float w = T * a;
-      c0 = c0 + w * rgb.x;
-      c1 = c1 + w * rgb.y;
-      c2 = c2 + w * rgb.z;
-      T = Tn;
-    }
-  }
-  const float f0 = c0, f1 = c1, f2 = c2;
-  float g0 = 0.0f, g1 = 0.0f, g2 = 0.0f, g3 = 0.0f;
-  if (inside) {
-    const float *g = p.grad_image + ((unsigned long long)v * p.width + u) * 4u;
-    g0 = g[0];
-    g1 = g[1];
-    g2 = g[2];
-    g3 = g[3];
-  }
-  const float tail = T * ((g0 * p.bg[0] + g1 * p.bg[1] + g2 * p.bg[2]) - g3);  // the background and the alpha channel
-  // the same walk again, in step across the wave (a stopped lane takes no more pairs)
-  T = 1.0f;
-  c0 = 0.0f;
-  c1 = 0.0f;
-  c2 = 0.0f;
-  done = !inside;
-  for (uint32_t base = begin; base < end; base += kBlendThreads) {
-    // also the barrier between the previous batch's reads and this batch's writes
-    if (__syncthreads_count(done ? 1 : 0) == (int)kBlendThreads) break;
-    const uint32_t j = base + t;
-    uint32_t gid = 0;
-    if (j < end) {
-      gid = p.sorted_gid[j];
-      const spz_amd_render_record &q = p.rec[gid];
-      s_xy[t] = make_float2(q.mean[0], q.mean[1]);
-      s_co[t] = make_float4(q.conic[0], q.conic[1], q.conic[2], q.opacity);
-      s_rgb[t] = make_float4(q.rgb[0], q.rgb[1], q.rgb[2], 0.0f);
-    }
-#pragma unroll
-    for (uint32_t e = 0; e < kRecGrads; ++e) s_grad[e][t] = 0.0f;
-    __syncthreads();
-    const uint32_t cnt = (end - base) < kBlendThreads ? end - base : kBlendThreads;
-    for (uint32_t k = 0; k < cnt; ++k) {
-      if (__ballot(!done) == 0ull) break;  // wave-uniform: every lane of the wave has stopped
-      const float2 xy = s_xy[k];
-      const float4 co = s_co[k];
-      const float dx = fu - xy.x, dy = fv - xy.y;
-      const float power = -0.5f * (co.x * dx * dx + co.z * dy * dy) - co.y * dx * dy;
-      const float ex = expf(power);
-      const float raw = co.w * ex;
-      const float a = fminf(0.99f, raw);
-      const float Tn = T * (1.0f - a);
-      bool use = !done && !(power > 0.0f) && !(a < 1.0f / 255.0f);
-      if (use && Tn < 1e-4f) {
-        done = true;
-        use = false;
-      }
-      if (__ballot(use) == 0ull) continue;  // wave-uniform
-      float d[kRecGrads] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-      if (use) {
-        const float4 rgb = s_rgb[k];
-        const float w = T * a;
-        c0 = c0 + w * rgb.x;
-        c1 = c1 + w * rgb.y;
-        c2 = c2 + w * rgb.z;
-        const float front = g0 * rgb.x + g1 * rgb.y + g2 * rgb.z;
-        const float behind = (g0 * (f0 - c0) + g1 * (f1 - c1) + g2 * (f2 - c2)) + tail;
-        const float da = T * front - behind / (1.0f - a);
-        d[6] = w * g0;
-        d[7] = w * g1;
-        d[8] = w * g2;
-        if (!(raw > 0.99f)) {  // a is opacity e^power
-          const float dp = da * raw;
-          d[0] = dp * (co.x * dx + co.y * dy);
-          d[1] = dp * (co.z * dy + co.y * dx);
-          d[2] = dp * (-0.5f * dx * dx);
-          d[3] = dp * (-(dx * dy));
-          d[4] = dp * (-0.5f * dy * dy);
-          d[5] = da * ex;
-        }
-        T = Tn;
-      }
-#pragma unroll
-      for (uint32_t e = 0; e < kRecGrads; ++e) d[e] = wave_sum_f32(d[e]);
-      if ((t & 63u) == 0u) {
-#pragma unroll
-        for (uint32_t e = 0; e < kRecGrads; ++e) atomicAdd(&s_grad[e][k], d[e]);
-      }
-    }
-    __syncthreads();
-    if (j < end) {
-      float *o = p.rec_grad + (unsigned long long)gid * kRecGrads;
-#pragma unroll
-      for (uint32_t e = 0; e < kRecGrads; ++e) {
-        const float s = s_grad[e][t];
-        if (s != 0.0f) atomicAdd(o + e, s);
-      }
-    }
-  }
-}
-
-constexpr uint32_t kDepthRecGrads = kRecGrads + 1;  // and the record's depth z
-
 struct DepthBlendBackwardParams {
   BlendBackwardParams b;    // b.grad_image may be null: all zero
   const float *grad_depth;  // height x width: the gradient to channel 0 of the depth map
   float *depth_grad;        // n, zeroed; added into
 };
 
-// spz_render_blend_backward_kernel with the depth sum of spz_render_depth_kernel in it ("render depth backward"):
-// s_rgb[k].w carries the record's depth z, D += (T a) z beside the colour sums, and a tenth value per used pair.  With
-// g_D the pixel's gradient to D, D_i the prefix that includes pair i and D_final the pixel's sum:
+// The body of both blend backward kernels: the colour one (kDepth false) and the one with the depth sum of
+// spz_render_depth_kernel in it (kDepth true: "render depth backward").
+//
+// Colour.  power, a, T' and the three tests are the expressions of spz_render_blend_kernel, so both passes use the
+// pairs the image used.  With I = C + T_final bg and alpha = 1 - T_final, g the pixel's gradient, and for a used pair i
+// (T before it, w = T a, C_i the prefix that includes it):
+//   dL/drgb_i = w g_rgb
+//   dL/da_i   = T (g_rgb . rgb_i) - (g_rgb . (C_final - C_i) + tail) / (1 - a)
+//   tail      = T_final (g_rgb . bg - g_alpha)
+// a = min(0.99, opacity e^power) hands dL/da to opacity and power only where it does not clamp.
+//
+// Depth.  s_rgb[k].w carries the record's depth z, D += (T a) z beside the colour sums, and a tenth value per used
+// pair.  With g_D the pixel's gradient to D, D_i the prefix that includes pair i and D_final the pixel's sum:
 //   dL/dz_i = w g_D
 //   dL/da_i = T (g_rgb . rgb_i + g_D z_i) - (g_rgb . (C_final - C_i) + g_D (D_final - D_i) + tail) / (1 - a)
 // D_final - D_i is a difference of two long f32 sums of w z, and at camera depths far above the depth range of a tile's
@@ -222,14 +80,18 @@ struct DepthBlendBackwardParams {
 // entry: D = D' + z0 (1 - T_final), which is the same loss with z - z0 for z and g_alpha + g_D z0 for g_alpha:
 //   dL/da_i = T (g_rgb . rgb_i + g_D (z_i - z0)) - (g_rgb . (C_final - C_i) + g_D (D'_final - D'_i) + tail') / (1 - a)
 //   tail'   = T_final (g_rgb . bg - g_alpha - g_D z0)
-// dL/dz_i is unchanged.  Everything else is that kernel's; the tenth sum goes to an array of its own, so the n x 9
-// layout stays.
-__global__ __launch_bounds__(kBlendThreads) void spz_render_depth_blend_backward_kernel(const DepthBlendBackwardParams pp) {
+// dL/dz_i is unchanged.  The tenth sum goes to an array of its own, so the n x 9 layout stays.
+//
+// The colour instance stages 0 in s_rgb[k].w, reads no depth, no z0 and no grad_depth, and reads grad_image without a
+// null check; every depth term is added after the colour terms of its sum, so each instance rounds as its formula reads.
+template <bool kDepth>
+__device__ __forceinline__ void blend_backward_body(const BlendBackwardParams &p, const float *grad_depth,
+                                                    float *depth_grad) {
+  constexpr uint32_t kGrads = kDepth ? kRecGrads + 1 : kRecGrads;  // and the record's depth z
   __shared__ float2 s_xy[kBlendThreads];
   __shared__ float4 s_co[kBlendThreads];   // conic A, B, C, opacity
-  __shared__ float4 s_rgb[kBlendThreads];  // rgb, depth
-  __shared__ float s_grad[kDepthRecGrads][kBlendThreads];
-  const BlendBackwardParams &p = pp.b;
+  __shared__ float4 s_rgb[kBlendThreads];  // rgb, z - z0 (0 without the depth)
+  __shared__ float s_grad[kGrads][kBlendThreads];
   const unsigned long long total = *p.total;
   if (total > p.max_entries) return;
   const uint32_t t = threadIdx.x;
@@ -243,7 +105,8 @@ __global__ __launch_bounds__(kBlendThreads) void spz_render_depth_blend_backward
   }
   if (begin >= end) return;  // workgroup-uniform: nothing blends here
   const float fu = (float)u, fv = (float)v;
-  const float z0 = p.rec[p.sorted_gid[begin]].depth;  // workgroup-uniform: the list is in depth order
+  float z0 = 0.0f;
+  if constexpr (kDepth) z0 = p.rec[p.sorted_gid[begin]].depth;  // workgroup-uniform: the list is in depth order
   // the forward blend, for the pixel's final colour sum, depth sum (of z - z0) and T
   float T = 1.0f, c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, D = 0.0f;
   bool done = !inside;
@@ -255,7 +118,7 @@ __global__ __launch_bounds__(kBlendThreads) void spz_render_depth_blend_backward
       const spz_amd_render_record &q = p.rec[p.sorted_gid[j]];
       s_xy[t] = make_float2(q.mean[0], q.mean[1]);
       s_co[t] = make_float4(q.conic[0], q.conic[1], q.conic[2], q.opacity);
-      s_rgb[t] = make_float4(q.rgb[0], q.rgb[1], q.rgb[2], q.depth - z0);
+      s_rgb[t] = make_float4(q.rgb[0], q.rgb[1], q.rgb[2], kDepth ? q.depth - z0 : 0.0f);
     }
     __syncthreads();
     const uint32_t cnt = (end - base) < kBlendThreads ? end - base : kBlendThreads;
@@ -277,7 +140,7 @@ __global__ __launch_bounds__(kBlendThreads) void spz_render_depth_blend_backward
       c0 = c0 + w * rgbz.x;
       c1 = c1 + w * rgbz.y;
       c2 = c2 + w * rgbz.z;
-      D = D + w * rgbz.w;
+      if constexpr (kDepth) D = D + w * rgbz.w;
       T = Tn;
     }
   }
@@ -285,17 +148,19 @@ __global__ __launch_bounds__(kBlendThreads) void spz_render_depth_blend_backward
   float g0 = 0.0f, g1 = 0.0f, g2 = 0.0f, g3 = 0.0f, gD = 0.0f;
   if (inside) {
     const unsigned long long at = (unsigned long long)v * p.width + u;
-    if (p.grad_image) {
+    if (!kDepth || p.grad_image) {  // only the depth kernel's may be null
       const float *g = p.grad_image + at * 4u;
       g0 = g[0];
       g1 = g[1];
       g2 = g[2];
       g3 = g[3];
     }
-    gD = pp.grad_depth[at];
+    if constexpr (kDepth) gD = grad_depth[at];
   }
-  // the background, the alpha channel and z0 (1 - T_final)
-  const float tail = T * (((g0 * p.bg[0] + g1 * p.bg[1] + g2 * p.bg[2]) - g3) - gD * z0);
+  // the background and the alpha channel, and with the depth z0 (1 - T_final)
+  float tail = (g0 * p.bg[0] + g1 * p.bg[1] + g2 * p.bg[2]) - g3;
+  if constexpr (kDepth) tail = tail - gD * z0;
+  tail = T * tail;
   // the same walk again, in step across the wave (a stopped lane takes no more pairs)
   T = 1.0f;
   c0 = 0.0f;
@@ -313,10 +178,10 @@ __global__ __launch_bounds__(kBlendThreads) void spz_render_depth_blend_backward
       const spz_amd_render_record &q = p.rec[gid];
       s_xy[t] = make_float2(q.mean[0], q.mean[1]);
       s_co[t] = make_float4(q.conic[0], q.conic[1], q.conic[2], q.opacity);
-      s_rgb[t] = make_float4(q.rgb[0], q.rgb[1], q.rgb[2], q.depth - z0);
+      s_rgb[t] = make_float4(q.rgb[0], q.rgb[1], q.rgb[2], kDepth ? q.depth - z0 : 0.0f);
     }
 #pragma unroll
-    for (uint32_t e = 0; e < kDepthRecGrads; ++e) s_grad[e][t] = 0.0f;
+    for (uint32_t e = 0; e < kGrads; ++e) s_grad[e][t] = 0.0f;
     __syncthreads();
     const uint32_t cnt = (end - base) < kBlendThreads ? end - base : kBlendThreads;
     for (uint32_t k = 0; k < cnt; ++k) {
@@ -335,21 +200,26 @@ __global__ __launch_bounds__(kBlendThreads) void spz_render_depth_blend_backward
         use = false;
       }
       if (__ballot(use) == 0ull) continue;  // wave-uniform
-      float d[kDepthRecGrads] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+      float d[kGrads] = {};
       if (use) {
         const float4 rgbz = s_rgb[k];
         const float w = T * a;
         c0 = c0 + w * rgbz.x;
         c1 = c1 + w * rgbz.y;
         c2 = c2 + w * rgbz.z;
-        D = D + w * rgbz.w;
-        const float front = (g0 * rgbz.x + g1 * rgbz.y + g2 * rgbz.z) + gD * rgbz.w;
-        const float behind = ((g0 * (f0 - c0) + g1 * (f1 - c1) + g2 * (f2 - c2)) + gD * (fD - D)) + tail;
+        float front = g0 * rgbz.x + g1 * rgbz.y + g2 * rgbz.z;
+        float behind = g0 * (f0 - c0) + g1 * (f1 - c1) + g2 * (f2 - c2);
+        if constexpr (kDepth) {
+          D = D + w * rgbz.w;
+          front = front + gD * rgbz.w;
+          behind = behind + gD * (fD - D);
+          d[kRecGrads] = w * gD;
+        }
+        behind = behind + tail;
         const float da = T * front - behind / (1.0f - a);
         d[6] = w * g0;
         d[7] = w * g1;
         d[8] = w * g2;
-        d[9] = w * gD;
         if (!(raw > 0.99f)) {  // a is opacity e^power
           const float dp = da * raw;
           d[0] = dp * (co.x * dx + co.y * dy);
@@ -362,10 +232,10 @@ __global__ __launch_bounds__(kBlendThreads) void spz_render_depth_blend_backward
         T = Tn;
       }
 #pragma unroll
-      for (uint32_t e = 0; e < kDepthRecGrads; ++e) d[e] = wave_sum_f32(d[e]);
+      for (uint32_t e = 0; e < kGrads; ++e) d[e] = wave_sum_f32(d[e]);
       if ((t & 63u) == 0u) {
 #pragma unroll
-        for (uint32_t e = 0; e < kDepthRecGrads; ++e) atomicAdd(&s_grad[e][k], d[e]);
+        for (uint32_t e = 0; e < kGrads; ++e) atomicAdd(&s_grad[e][k], d[e]);
       }
     }
     __syncthreads();
@@ -376,10 +246,21 @@ __global__ __launch_bounds__(kBlendThreads) void spz_render_depth_blend_backward
         const float s = s_grad[e][t];
         if (s != 0.0f) atomicAdd(o + e, s);
       }
-      const float s = s_grad[kRecGrads][t];
-      if (s != 0.0f) atomicAdd(pp.depth_grad + gid, s);
+      if constexpr (kDepth) {
+        const float s = s_grad[kRecGrads][t];
+        if (s != 0.0f) atomicAdd(depth_grad + gid, s);
+      }
     }
   }
+}
+
+// The two entries keep their names and parameter blocks (the tools and the recorded profiles find them by name).
+__global__ __launch_bounds__(kBlendThreads) void spz_render_blend_backward_kernel(const BlendBackwardParams p) {
+  blend_backward_body<false>(p, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(kBlendThreads) void spz_render_depth_blend_backward_kernel(const DepthBlendBackwardParams pp) {
+  blend_backward_body<true>(pp.b, pp.grad_depth, pp.depth_grad);
 }
 
 struct PreprocessBackwardParams {
@@ -678,7 +559,6 @@ int backward_impl(const spz_amd_cloud_in *d_cloud, uint64_t num_points, int sh_d
   if (num_points == 0) return SPZ_AMD_OK;  // the total is 0 and there is nothing to write
   const RenderLayout wl = render_layout(num_points, max_entries);
   const uint8_t *base = align_ws(const_cast<void *>(d_render_workspace));
-  const uint8_t *ent = base + wl.prefix;
   uint8_t *bws = align_ws(d_backward_workspace);
   float *rec_grad = reinterpret_cast<float *>(bws);
   // the n depth gradients follow the n x 9 record gradients
@@ -686,18 +566,9 @@ int backward_impl(const spz_amd_cloud_in *d_cloud, uint64_t num_points, int sh_d
   SPZ_HIP_TRY(hipMemsetAsync(rec_grad, 0, num_points * kRecGrads * sizeof(float), st));
   if (depth) SPZ_HIP_TRY(hipMemsetAsync(depth_grad, 0, num_points * sizeof(float), st));
   BlendBackwardParams b = {};
-  b.rec = reinterpret_cast<const spz_amd_render_record *>(base + wl.rec);
-  b.sorted_gid = max_entries ? reinterpret_cast<const uint32_t *>(ent + wl.sorted_gid) : nullptr;
-  b.ranges = max_entries ? reinterpret_cast<const uint2 *>(ent + wl.ranges) : nullptr;  // read only when the total is > 0
-  b.total = reinterpret_cast<const unsigned long long *>(base + wl.total);
+  const dim3 grid = fill_blend_params(b, wl, base, base + wl.prefix, params, max_entries);
   b.grad_image = d_grad_image;
   b.rec_grad = rec_grad;
-  b.max_entries = max_entries;
-  b.width = params->width;
-  b.height = params->height;
-  b.tiles_x = (params->width + kTile - 1) / kTile;
-  for (int k = 0; k < 3; ++k) b.bg[k] = params->background[k];
-  const dim3 grid(b.tiles_x, (params->height + kTile - 1) / kTile);
   if (depth) {
     DepthBlendBackwardParams db = {};
     db.b = b;
@@ -809,24 +680,14 @@ int spz_amd_render_records_backward_device(uint64_t num_points, const spz_amd_re
   if (num_points == 0) return SPZ_AMD_OK;  // the total is 0 and there is nothing to write
   const RenderLayout wl = render_layout(num_points, max_entries);
   const uint8_t *base = align_ws(const_cast<void *>(d_render_workspace));
-  const uint8_t *ent = base + wl.prefix;
   BlendBackwardParams b = {};
-  b.rec = reinterpret_cast<const spz_amd_render_record *>(base + wl.rec);
-  b.sorted_gid = max_entries ? reinterpret_cast<const uint32_t *>(ent + wl.sorted_gid) : nullptr;
-  b.ranges = max_entries ? reinterpret_cast<const uint2 *>(ent + wl.ranges) : nullptr;  // read only when the total is > 0
-  b.total = reinterpret_cast<const unsigned long long *>(base + wl.total);
+  const dim3 grid = fill_blend_params(b, wl, base, base + wl.prefix, params, max_entries);
   b.grad_image = d_grad_image;
   b.rec_grad = d_record_grads;
-  b.max_entries = max_entries;
-  b.width = params->width;
-  b.height = params->height;
-  b.tiles_x = (params->width + kTile - 1) / kTile;
-  for (int k = 0; k < 3; ++k) b.bg[k] = params->background[k];
   const unsigned long long count = (unsigned long long)num_points * kRecGrads;
   hipLaunchKernelGGL(spz_render_records_clear_kernel, dim3((unsigned)((count + kPreBlock - 1) / kPreBlock)),
                      dim3(kPreBlock), 0, st, d_record_grads, count, b.total, max_entries, d_status);
   SPZ_HIP_TRY(hipGetLastError());
-  const dim3 grid(b.tiles_x, (params->height + kTile - 1) / kTile);
   hipLaunchKernelGGL(spz_render_blend_backward_kernel, grid, dim3(kBlendThreads), 0, st, b);
   SPZ_HIP_TRY(hipGetLastError());
   return SPZ_AMD_OK;

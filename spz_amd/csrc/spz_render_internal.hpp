@@ -1,7 +1,7 @@
 // spz_render_internal.hpp — what the translation units of the rasteriser share (spz_render.hip: the forward and its
 // scoring and depth blends; spz_render_backward.hip: the gradients): the tile geometry, the f64 camera, the float
 // cloud's loader, 3DGS's sh constants, the wave sum of the blend backwards, the workspace layout of the prepare and
-// entries parts, and the host-side argument checks.
+// entries parts, the fill of a blend kernel's common parameters, and the host-side argument checks.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -132,6 +132,24 @@ inline RenderLayout render_layout(uint64_t n, uint64_t m) {
   w.entries = e;
   w.bytes = w.prefix + w.entries + 256u;  // room to align a caller's pointer up to 256
   return w;
+}
+
+// What the parameter blocks of the blend kernels have in common (BlendParams, ScoreParams, DepthParams,
+// BlendBackwardParams): the records, the tile lists and the total from the workspace (base: the prepare part; ent: the
+// entries part), the image's size and the background.  Returns the launch grid, one workgroup per tile.
+template <class P>
+inline dim3 fill_blend_params(P &b, const RenderLayout &wl, const uint8_t *base, const uint8_t *ent,
+                              const spz_amd_render_params *params, uint64_t max_entries) {
+  b.rec = reinterpret_cast<const spz_amd_render_record *>(base + wl.rec);
+  b.sorted_gid = max_entries ? reinterpret_cast<const uint32_t *>(ent + wl.sorted_gid) : nullptr;
+  b.ranges = max_entries ? reinterpret_cast<const uint2 *>(ent + wl.ranges) : nullptr;  // read only when the total is > 0
+  b.total = reinterpret_cast<const unsigned long long *>(base + wl.total);
+  b.max_entries = max_entries;
+  b.width = params->width;
+  b.height = params->height;
+  b.tiles_x = (params->width + kTile - 1) / kTile;
+  for (int k = 0; k < 3; ++k) b.bg[k] = params->background[k];
+  return dim3(b.tiles_x, (params->height + kTile - 1) / kTile);
 }
 
 inline bool finite3(const float *v, int k) {

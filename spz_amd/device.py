@@ -1024,6 +1024,12 @@ def _cloud_render_args(cloud, num_points, sh_degree):
     return _ptrs(cloud, sh_degree, num_points, dev), dev
 
 
+def _cloud_source(cloud, num_points, sh_degree, antialiased):
+    """The float source of _render_prepare for a cloud, with its pointers and its device: (source, ptrs, dev)."""
+    ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
+    return ("cloud", ptrs, num_points, int(sh_degree), antialiased), ptrs, dev
+
+
 def _render_prepare(L, source, params, total, records, ws, st):
     """Enqueue the prepare step of a packed ("packed", stream_t, header) or float ("cloud", ptrs, n, sh_degree,
     antialiased) source into ws on the torch stream st."""
@@ -1093,6 +1099,25 @@ def _check_out(name, t, shape, dtype, dev):
         raise ValueError(f"{name} must be a contiguous {str(dtype).split('.')[-1]} tensor of shape {shape} on {dev}")
 
 
+def _prepare_finish(L, source, n, params, dev, max_entries, st, image, depth=None, index=None):
+    """Prepare + finish on st into the given tensors, keeping the workspace: (total, status, workspace, m).  With a
+    depth map the finish step is spz_amd_render_depth_device (image and index may then be None), without one
+    spz_amd_render_finish_device."""
+    # the prepare step always writes the total, the finish step always writes the status
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws, m = _prepared_workspace(L, source, n, params, dev, max_entries, total, st)
+    tail = (status.data_ptr(), ws.data_ptr(), C.c_void_p(st.cuda_stream))
+    if depth is None:
+        rc = L.spz_amd_render_finish_device(n, C.byref(params), m, image.data_ptr(), *tail)
+        abi.check(rc, "spz_amd_render_finish_device")
+    else:
+        rc = L.spz_amd_render_depth_device(n, C.byref(params), m, image.data_ptr() if image is not None else None,
+                                           depth.data_ptr(), index.data_ptr() if index is not None else None, *tail)
+        abi.check(rc, "spz_amd_render_depth_device")
+    return total, status, ws, m
+
+
 def _render(source, n, params, dev, max_entries, out, return_info, stream):
     L = abi.load_library()
     _check_render_args(L, params, max_entries)
@@ -1105,13 +1130,7 @@ def _render(source, n, params, dev, max_entries, out, return_info, stream):
         with torch.cuda.stream(st):
             if out is None:
                 out = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
-            # the prepare step always writes the total, the finish step always writes the status
-            total = torch.empty(1, dtype=torch.int64, device=dev)
-            status = torch.empty(1, dtype=torch.int32, device=dev)
-            ws, m = _prepared_workspace(L, source, n, params, dev, max_entries, total, st)
-            rc = L.spz_amd_render_finish_device(n, C.byref(params), m, out.data_ptr(), status.data_ptr(), ws.data_ptr(),
-                                                C.c_void_p(st.cuda_stream))
-    abi.check(rc, "spz_amd_render_finish_device")
+            total, status, _, _ = _prepare_finish(L, source, n, params, dev, max_entries, st, out)
     return (out, total, status) if return_info else out
 
 
@@ -1137,13 +1156,7 @@ def _render_depth(source, n, params, dev, max_entries, return_image, return_inde
             image = out.get("image")
             if image is None and return_image:
                 image = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
-            total = torch.empty(1, dtype=torch.int64, device=dev)
-            status = torch.empty(1, dtype=torch.int32, device=dev)
-            ws, m = _prepared_workspace(L, source, n, params, dev, max_entries, total, st)
-            rc = L.spz_amd_render_depth_device(n, C.byref(params), m, image.data_ptr() if image is not None else None,
-                                               depth.data_ptr(), index.data_ptr() if index is not None else None,
-                                               status.data_ptr(), ws.data_ptr(), C.c_void_p(st.cuda_stream))
-    abi.check(rc, "spz_amd_render_depth_device")
+            total, status, _, _ = _prepare_finish(L, source, n, params, dev, max_entries, st, image, depth, index)
     res = (depth,)
     if index is not None:
         res += (index,)
@@ -1164,48 +1177,89 @@ def render(cloud, num_points, sh_degree, params, antialiased=False, max_entries=
     return_info: (image, total (int64 tensor [1]), status (int32 tensor [1])).  stream: a torch stream that first waits
     for the current one, then takes every allocation, copy, launch and read-back of the render; the results belong to it
     (synchronise with it before using them on another stream)."""
-    ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
-    return _render(("cloud", ptrs, num_points, int(sh_degree), antialiased), num_points, params, dev, max_entries, out,
-                   return_info, stream)
+    source, _, dev = _cloud_source(cloud, num_points, sh_degree, antialiased)
+    return _render(source, num_points, params, dev, max_entries, out, return_info, stream)
 
 
-def _rendered_workspace(L, source, n, params, dev, max_entries, st):
-    """Prepare + finish on st, keeping the workspace: (image, workspace, m).  Raises when the total is above
-    max_entries (one word is read back)."""
+def _rendered_workspace(L, source, n, params, dev, max_entries, st, depth=False):
+    """Prepare + finish on st, keeping the workspace: (image, workspace, m), or with depth, where the finish step is
+    spz_amd_render_depth_device, (image, depth, workspace, m).  Raises when the total is above max_entries (one word is
+    read back)."""
     h, w = params.height, params.width
-    image = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
-    total = torch.empty(1, dtype=torch.int64, device=dev)
-    status = torch.empty(1, dtype=torch.int32, device=dev)
-    ws, m = _prepared_workspace(L, source, n, params, dev, max_entries, total, st)
-    rc = L.spz_amd_render_finish_device(n, C.byref(params), m, image.data_ptr(), status.data_ptr(), ws.data_ptr(),
-                                        C.c_void_p(st.cuda_stream))
-    abi.check(rc, "spz_amd_render_finish_device")
+    maps = [torch.empty((h, w, 4), dtype=torch.float32, device=dev)]
+    if depth:
+        maps.append(torch.empty((h, w, 2), dtype=torch.float32, device=dev))
+    total, status, ws, m = _prepare_finish(L, source, n, params, dev, max_entries, st, *maps)
     if max_entries is not None and int(status.cpu()[0]) != 0:  # on st: waits for the finish step
         raise RuntimeError(f"{int(total.cpu()[0])} tile entries is above max_entries = {max_entries}")
-    return image, ws, m
+    return (*maps, ws, m)
 
 
-def _render_backward(L, ptrs, n, sh_degree, antialiased, params, m, image, grad_image, ws, dev, want_records, st):
-    """Enqueue spz_amd_render_backward_device on st over the workspace ws of a finished render: (grads, record_grads)."""
+def _render_backward(L, ptrs, n, sh_degree, antialiased, params, m, image, grad_image, grad_depth, ws, dev,
+                     want_records, st):
+    """Enqueue the backward on st over the workspace ws of a finished or depth render: (grads, record_grads,
+    depth_grads).  With grad_depth it is spz_amd_render_depth_backward_device (grad_image may then be None, and image
+    is not read), and depth_grads is (n,) when the records are wanted; without, spz_amd_render_backward_device, and
+    depth_grads is None."""
+    depth = grad_depth is not None
     grads = alloc_cloud(n, sh_degree, dev)
     gp = abi.CloudPtrs(*[grads[k].data_ptr() if grads[k].numel() else None for k in FIELDS])
     rec = torch.empty((n, 9), dtype=torch.float32, device=dev) if want_records else None
+    dz = torch.empty(n, dtype=torch.float32, device=dev) if want_records and depth else None
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    bws = torch.empty(int(L.spz_amd_render_backward_workspace_bytes(n)), dtype=torch.uint8, device=dev)
-    rc = L.spz_amd_render_backward_device(C.byref(ptrs), n, sh_degree, 1 if antialiased else 0, C.byref(params), m,
-                                          image.data_ptr(), grad_image.data_ptr(), C.byref(gp),
-                                          rec.data_ptr() if rec is not None and n else None, status.data_ptr(),
-                                          ws.data_ptr(), bws.data_ptr(), C.c_void_p(st.cuda_stream))
-    abi.check(rc, "spz_amd_render_backward_device")
-    return grads, rec
+    ws_bytes = L.spz_amd_render_depth_backward_workspace_bytes if depth else L.spz_amd_render_backward_workspace_bytes
+    bws = torch.empty(int(ws_bytes(n)), dtype=torch.uint8, device=dev)
+    head = (C.byref(ptrs), n, sh_degree, 1 if antialiased else 0, C.byref(params), m)
+    rec_ptr = rec.data_ptr() if rec is not None and n else None
+    tail = (status.data_ptr(), ws.data_ptr(), bws.data_ptr(), C.c_void_p(st.cuda_stream))
+    if depth:
+        rc = L.spz_amd_render_depth_backward_device(*head, grad_image.data_ptr() if grad_image is not None else None,
+                                                    grad_depth.data_ptr(), C.byref(gp), rec_ptr,
+                                                    dz.data_ptr() if dz is not None and n else None, *tail)
+        abi.check(rc, "spz_amd_render_depth_backward_device")
+    else:
+        rc = L.spz_amd_render_backward_device(*head, image.data_ptr(), grad_image.data_ptr(), C.byref(gp), rec_ptr,
+                                              *tail)
+        abi.check(rc, "spz_amd_render_backward_device")
+    return grads, rec, dz
+
+
+def _check_grad(name, t, shape, dev):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != shape:
+        raise ValueError(f"{name} must be a float32 tensor of shape {shape} on {dev}")
+    return t.contiguous()
 
 
 def _check_grad_image(grad_image, params, dev):
-    shape = (params.height, params.width, 4)
-    if (not isinstance(grad_image, torch.Tensor) or grad_image.dtype != torch.float32 or grad_image.device != dev
-            or tuple(grad_image.shape) != shape):
-        raise ValueError(f"grad_image must be a float32 tensor of shape {shape} on {dev}")
-    return grad_image.contiguous()
+    return _check_grad("grad_image", grad_image, (params.height, params.width, 4), dev)
+
+
+def _check_grad_depth(grad_depth, params, dev):
+    return _check_grad("grad_depth", grad_depth, (params.height, params.width), dev)
+
+
+def _render_then_backward(cloud, num_points, sh_degree, params, grad_image, grad_depth, depth, antialiased, max_entries,
+                          return_record_grads, stream):
+    """render_backward() (depth False) and render_depth_backward() (depth True: grad_depth is required and grad_image may
+    be None): check, render keeping the workspace, and the backward over it, all on the stream."""
+    source, ptrs, dev = _cloud_source(cloud, num_points, sh_degree, antialiased)
+    L = abi.load_library()
+    _check_render_args(L, params, max_entries)
+    if grad_image is not None or not depth:
+        grad_image = _check_grad_image(grad_image, params, dev)
+    if depth:
+        grad_depth = _check_grad_depth(grad_depth, params, dev)
+    with torch.cuda.device(dev):
+        st = _on_stream(dev, stream)
+        with torch.cuda.stream(st):
+            image, ws, m = _rendered_workspace(L, source, num_points, params, dev, max_entries, st)
+            grads, rec, dz = _render_backward(L, ptrs, num_points, int(sh_degree), antialiased, params, m, image,
+                                              grad_image, grad_depth, ws, dev, return_record_grads, st)
+    if return_record_grads:
+        grads["records"] = rec
+        if depth:
+            grads["depth"] = dz
+    return grads
 
 
 def render_backward(cloud, num_points, sh_degree, params, grad_image, *, antialiased=False, max_entries=None,
@@ -1216,100 +1270,8 @@ def render_backward(cloud, num_points, sh_degree, params, grad_image, *, antiali
     shaped like the cloud; with return_record_grads also "records", (n, 9): the gradients to each Gaussian's mean 2,
     conic 3, opacity 1 and rgb 3.  Sums with f32 atomic adds: two runs may differ in the last bits.  max_entries: as
     render(), but a total above it raises RuntimeError.  stream: as render()."""
-    ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
-    L = abi.load_library()
-    _check_render_args(L, params, max_entries)
-    grad_image = _check_grad_image(grad_image, params, dev)
-    with torch.cuda.device(dev):
-        st = _on_stream(dev, stream)
-        with torch.cuda.stream(st):
-            source = ("cloud", ptrs, num_points, int(sh_degree), antialiased)
-            image, ws, m = _rendered_workspace(L, source, num_points, params, dev, max_entries, st)
-            grads, rec = _render_backward(L, ptrs, num_points, int(sh_degree), antialiased, params, m, image, grad_image,
-                                          ws, dev, return_record_grads, st)
-    if return_record_grads:
-        grads["records"] = rec
-    return grads
-
-
-class _RenderFunction(torch.autograd.Function):
-    """render() with a backward: the forward keeps its workspace (a tensor of this call alone, never reused), the
-    backward runs spz_amd_render_backward_device over it on the current stream.  The six arrays are saved with
-    save_for_backward, so changing one in place before the backward raises torch's usual error."""
-
-    @staticmethod
-    def forward(ctx, num_points, sh_degree, params, antialiased, max_entries, *arrays):
-        cloud = dict(zip(FIELDS, (a.detach() for a in arrays)))
-        ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
-        L = abi.load_library()
-        _check_render_args(L, params, max_entries)
-        with torch.cuda.device(dev):
-            st = torch.cuda.current_stream(dev)
-            source = ("cloud", ptrs, num_points, int(sh_degree), antialiased)
-            image, ws, m = _rendered_workspace(L, source, num_points, params, dev, max_entries, st)
-        ctx.save_for_backward(image, ws, *arrays)
-        ctx.args = (num_points, int(sh_degree), params, bool(antialiased), m)
-        return image
-
-    @staticmethod
-    def backward(ctx, grad_image):
-        image, ws = ctx.saved_tensors[:2]
-        arrays = ctx.saved_tensors[2:]
-        num_points, sh_degree, params, antialiased, m = ctx.args
-        cloud = dict(zip(FIELDS, (a.detach() for a in arrays)))
-        ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
-        L = abi.load_library()
-        grad_image = _check_grad_image(grad_image, params, dev)
-        with torch.cuda.device(dev):
-            grads, _ = _render_backward(L, ptrs, num_points, sh_degree, antialiased, params, m, image, grad_image, ws,
-                                        dev, False, torch.cuda.current_stream(dev))
-        out = tuple(grads[k].view_as(a) if need else None
-                    for k, a, need in zip(FIELDS, arrays, ctx.needs_input_grad[5:]))
-        return (None,) * 5 + out
-
-
-def _depth_rendered_workspace(L, source, n, params, dev, max_entries, st):
-    """_rendered_workspace with render_depth_device for the finish: (image, depth, workspace, m)."""
-    h, w = params.height, params.width
-    image = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
-    depth = torch.empty((h, w, 2), dtype=torch.float32, device=dev)
-    total = torch.empty(1, dtype=torch.int64, device=dev)
-    status = torch.empty(1, dtype=torch.int32, device=dev)
-    ws, m = _prepared_workspace(L, source, n, params, dev, max_entries, total, st)
-    rc = L.spz_amd_render_depth_device(n, C.byref(params), m, image.data_ptr(), depth.data_ptr(), None,
-                                       status.data_ptr(), ws.data_ptr(), C.c_void_p(st.cuda_stream))
-    abi.check(rc, "spz_amd_render_depth_device")
-    if max_entries is not None and int(status.cpu()[0]) != 0:  # on st: waits for the depth blend
-        raise RuntimeError(f"{int(total.cpu()[0])} tile entries is above max_entries = {max_entries}")
-    return image, depth, ws, m
-
-
-def _render_depth_backward(L, ptrs, n, sh_degree, antialiased, params, m, grad_image, grad_depth, ws, dev, want_records,
-                           st):
-    """Enqueue spz_amd_render_depth_backward_device on st over the workspace ws of a finished or depth render:
-    (grads, record_grads, depth_grads)."""
-    grads = alloc_cloud(n, sh_degree, dev)
-    gp = abi.CloudPtrs(*[grads[k].data_ptr() if grads[k].numel() else None for k in FIELDS])
-    rec = torch.empty((n, 9), dtype=torch.float32, device=dev) if want_records else None
-    dz = torch.empty(n, dtype=torch.float32, device=dev) if want_records else None
-    status = torch.empty(1, dtype=torch.int32, device=dev)
-    bws = torch.empty(int(L.spz_amd_render_depth_backward_workspace_bytes(n)), dtype=torch.uint8, device=dev)
-    rc = L.spz_amd_render_depth_backward_device(C.byref(ptrs), n, sh_degree, 1 if antialiased else 0, C.byref(params), m,
-                                                grad_image.data_ptr() if grad_image is not None else None,
-                                                grad_depth.data_ptr(), C.byref(gp),
-                                                rec.data_ptr() if rec is not None and n else None,
-                                                dz.data_ptr() if dz is not None and n else None, status.data_ptr(),
-                                                ws.data_ptr(), bws.data_ptr(), C.c_void_p(st.cuda_stream))
-    abi.check(rc, "spz_amd_render_depth_backward_device")
-    return grads, rec, dz
-
-
-def _check_grad_depth(grad_depth, params, dev):
-    shape = (params.height, params.width)
-    if (not isinstance(grad_depth, torch.Tensor) or grad_depth.dtype != torch.float32 or grad_depth.device != dev
-            or tuple(grad_depth.shape) != shape):
-        raise ValueError(f"grad_depth must be a float32 tensor of shape {shape} on {dev}")
-    return grad_depth.contiguous()
+    return _render_then_backward(cloud, num_points, sh_degree, params, grad_image, None, False, antialiased, max_entries,
+                                 return_record_grads, stream)
 
 
 def render_depth_backward(cloud, num_points, sh_degree, params, grad_image, grad_depth, *, antialiased=False,
@@ -1319,76 +1281,8 @@ def render_depth_backward(cloud, num_points, sh_degree, params, grad_image, grad
     its gradient to render_depth()[..., 0], a (height, width) float32 CUDA tensor.  Renders (prepare + finish), then
     spz_amd_render_depth_backward_device over the same workspace.  With return_record_grads also "records", (n, 9), and
     "depth", (n,): the gradient to each Gaussian's record depth z.  Otherwise as render_backward()."""
-    ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
-    L = abi.load_library()
-    _check_render_args(L, params, max_entries)
-    if grad_image is not None:
-        grad_image = _check_grad_image(grad_image, params, dev)
-    grad_depth = _check_grad_depth(grad_depth, params, dev)
-    with torch.cuda.device(dev):
-        st = _on_stream(dev, stream)
-        with torch.cuda.stream(st):
-            source = ("cloud", ptrs, num_points, int(sh_degree), antialiased)
-            _, ws, m = _rendered_workspace(L, source, num_points, params, dev, max_entries, st)
-            grads, rec, dz = _render_depth_backward(L, ptrs, num_points, int(sh_degree), antialiased, params, m,
-                                                    grad_image, grad_depth, ws, dev, return_record_grads, st)
-    if return_record_grads:
-        grads["records"] = rec
-        grads["depth"] = dz
-    return grads
-
-
-class _RenderDepthFunction(torch.autograd.Function):
-    """_RenderFunction with two outputs, the image and channel 0 of the depth map: the forward is render_depth_device
-    (its image is render()'s, bit for bit), the backward spz_amd_render_depth_backward_device over the kept workspace."""
-
-    @staticmethod
-    def forward(ctx, num_points, sh_degree, params, antialiased, max_entries, *arrays):
-        cloud = dict(zip(FIELDS, (a.detach() for a in arrays)))
-        ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
-        L = abi.load_library()
-        _check_render_args(L, params, max_entries)
-        with torch.cuda.device(dev):
-            st = torch.cuda.current_stream(dev)
-            source = ("cloud", ptrs, num_points, int(sh_degree), antialiased)
-            image, depth, ws, m = _depth_rendered_workspace(L, source, num_points, params, dev, max_entries, st)
-        ctx.save_for_backward(ws, *arrays)
-        ctx.args = (num_points, int(sh_degree), params, bool(antialiased), m)
-        return image, depth[..., 0].contiguous()
-
-    @staticmethod
-    def backward(ctx, grad_image, grad_depth):
-        ws = ctx.saved_tensors[0]
-        arrays = ctx.saved_tensors[1:]
-        num_points, sh_degree, params, antialiased, m = ctx.args
-        cloud = dict(zip(FIELDS, (a.detach() for a in arrays)))
-        ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
-        L = abi.load_library()
-        if grad_image is not None:
-            grad_image = _check_grad_image(grad_image, params, dev)
-        if grad_depth is None:
-            grad_depth = torch.zeros((params.height, params.width), dtype=torch.float32, device=dev)
-        grad_depth = _check_grad_depth(grad_depth, params, dev)
-        with torch.cuda.device(dev):
-            grads, _, _ = _render_depth_backward(L, ptrs, num_points, sh_degree, antialiased, params, m, grad_image,
-                                                 grad_depth, ws, dev, False, torch.cuda.current_stream(dev))
-        out = tuple(grads[k].view_as(a) if need else None
-                    for k, a, need in zip(FIELDS, arrays, ctx.needs_input_grad[5:]))
-        return (None,) * 5 + out
-
-
-def render_depth_autograd(cloud, num_points, sh_degree, params, antialiased=False, max_entries=None):
-    """render() and the accumulated depth as one differentiable torch operation: (image, depth0), image bit-identical
-    to render()'s and depth0 (height, width) bit-identical to render_depth()[..., 0]; backward() gives the six arrays of
-    cloud their gradients through both (include/spz_amd.h "render depth backward").  The median depth and the index
-    carry no gradient and are not returned.  Otherwise as render_autograd()."""
-    arrays = []
-    for k in FIELDS:
-        t = cloud.get(k)
-        if t is None:
-            t = torch.empty(0, dtype=torch.float32, device=cloud["positions"].device)
-        arrays.append(t)
-    return _RenderDepthFunction.apply(num_points, sh_degree, params, antialiased, max_entries, *arrays)
+    return _render_then_backward(cloud, num_points, sh_degree, params, grad_image, grad_depth, True, antialiased,
+                                 max_entries, return_record_grads, stream)
 
 
 def _records_backward(L, n, params, m, grad_image, ws, dev, st):
@@ -1423,7 +1317,7 @@ def render_view_backward(cloud, num_points, sh_degree, params, grad_image, *, an
     record_grads: an (n, 9) float32 CUDA tensor to use instead of the blend half's (grad_image may then be None): the
     sum over the Gaussians uses no atomics, so the same record gradients give the same bits.  return_record_grads:
     (view_grad, record_grads).  max_entries and stream: as render_backward()."""
-    ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
+    source, ptrs, dev = _cloud_source(cloud, num_points, sh_degree, antialiased)
     L = abi.load_library()
     _check_render_args(L, params, max_entries)
     if record_grads is None:
@@ -1434,7 +1328,6 @@ def render_view_backward(cloud, num_points, sh_degree, params, grad_image, *, an
     with torch.cuda.device(dev):
         st = _on_stream(dev, stream)
         with torch.cuda.stream(st):
-            source = ("cloud", ptrs, num_points, int(sh_degree), antialiased)
             image, ws, m = _rendered_workspace(L, source, num_points, params, dev, max_entries, st)
             if record_grads is None:
                 rec = _records_backward(L, num_points, params, m, grad_image, ws, dev, st)
@@ -1455,6 +1348,87 @@ def _params_with_pose(params, world_to_camera):
     return p
 
 
+def _autograd_forward(ctx, num_points, sh_degree, params, antialiased, max_entries, arrays, depth=False):
+    """The forward of the three render Functions: check, render on the current stream keeping the workspace (a tensor of
+    this call alone, never reused), and leave in ctx.args what the backward needs beside the saved tensors.  Returns
+    _rendered_workspace's maps and the workspace: (image, workspace) or, with depth, (image, depth, workspace)."""
+    cloud = dict(zip(FIELDS, (a.detach() for a in arrays)))
+    source, _, dev = _cloud_source(cloud, num_points, sh_degree, antialiased)
+    L = abi.load_library()
+    _check_render_args(L, params, max_entries)
+    with torch.cuda.device(dev):
+        *maps, ws, m = _rendered_workspace(L, source, num_points, params, dev, max_entries,
+                                           torch.cuda.current_stream(dev), depth)
+    ctx.args = (num_points, int(sh_degree), params, bool(antialiased), m)
+    return (*maps, ws)
+
+
+def _autograd_backward(ctx, mode, image, ws, arrays, grad_image, grad_depth, need, need_pose=False):
+    """The backward of the three render Functions on the current stream, over the workspace the forward kept:
+    (array_grads, pose_grad).  array_grads: the gradients to the six saved arrays, None where need says so.  mode
+    "image": spz_amd_render_backward_device.  mode "depth": spz_amd_render_depth_backward_device, where a grad_image
+    of None is all zero, as is a grad_depth of None.  mode "pose": as "image", and with need_pose also the (3, 4)
+    float64 gradient to [R | t] from spz_amd_render_view_backward_device (from the blend half alone when no array
+    needs a gradient); pose_grad is None otherwise."""
+    num_points, sh_degree, params, antialiased, m = ctx.args
+    cloud = dict(zip(FIELDS, (a.detach() for a in arrays)))
+    ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
+    L = abi.load_library()
+    if grad_image is not None or mode != "depth":
+        grad_image = _check_grad_image(grad_image, params, dev)
+    if mode == "depth":
+        if grad_depth is None:
+            grad_depth = torch.zeros((params.height, params.width), dtype=torch.float32, device=dev)
+        grad_depth = _check_grad_depth(grad_depth, params, dev)
+    need_pose = need_pose and mode == "pose"
+    grads, rec, pose = None, None, None
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev)
+        if any(need) or mode != "pose":
+            grads, rec, _ = _render_backward(L, ptrs, num_points, sh_degree, antialiased, params, m, image, grad_image,
+                                             grad_depth, ws, dev, need_pose, st)
+        elif need_pose:
+            rec = _records_backward(L, num_points, params, m, grad_image, ws, dev, st)
+        if need_pose:
+            pose = _view_backward(L, ptrs, num_points, sh_degree, antialiased, params, m, rec, ws, dev, st)
+    return tuple(grads[k].view_as(a) if n else None for k, a, n in zip(FIELDS, arrays, need)), pose
+
+
+class _RenderFunction(torch.autograd.Function):
+    """render() with a backward: the forward keeps its workspace (a tensor of this call alone, never reused), the
+    backward runs spz_amd_render_backward_device over it on the current stream.  The six arrays are saved with
+    save_for_backward, so changing one in place before the backward raises torch's usual error."""
+
+    @staticmethod
+    def forward(ctx, num_points, sh_degree, params, antialiased, max_entries, *arrays):
+        image, ws = _autograd_forward(ctx, num_points, sh_degree, params, antialiased, max_entries, arrays)
+        ctx.save_for_backward(image, ws, *arrays)
+        return image
+
+    @staticmethod
+    def backward(ctx, grad_image):
+        image, ws, *arrays = ctx.saved_tensors
+        out, _ = _autograd_backward(ctx, "image", image, ws, arrays, grad_image, None, ctx.needs_input_grad[5:])
+        return (None,) * 5 + out
+
+
+class _RenderDepthFunction(torch.autograd.Function):
+    """_RenderFunction with two outputs, the image and channel 0 of the depth map: the forward is render_depth_device
+    (its image is render()'s, bit for bit), the backward spz_amd_render_depth_backward_device over the kept workspace."""
+
+    @staticmethod
+    def forward(ctx, num_points, sh_degree, params, antialiased, max_entries, *arrays):
+        image, depth, ws = _autograd_forward(ctx, num_points, sh_degree, params, antialiased, max_entries, arrays, True)
+        ctx.save_for_backward(ws, *arrays)
+        return image, depth[..., 0].contiguous()
+
+    @staticmethod
+    def backward(ctx, grad_image, grad_depth):
+        ws, *arrays = ctx.saved_tensors
+        out, _ = _autograd_backward(ctx, "depth", None, ws, arrays, grad_image, grad_depth, ctx.needs_input_grad[5:])
+        return (None,) * 5 + out
+
+
 class _RenderPoseFunction(torch.autograd.Function):
     """_RenderFunction with the camera's [R | t] as one more differentiable input: the forward renders params with the
     matrix replaced, the backward also runs spz_amd_render_view_backward_device over the kept workspace."""
@@ -1462,41 +1436,32 @@ class _RenderPoseFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, num_points, sh_degree, params, antialiased, max_entries, world_to_camera, *arrays):
         params = _params_with_pose(params, world_to_camera)
-        cloud = dict(zip(FIELDS, (a.detach() for a in arrays)))
-        ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
-        L = abi.load_library()
-        _check_render_args(L, params, max_entries)
-        with torch.cuda.device(dev):
-            st = torch.cuda.current_stream(dev)
-            source = ("cloud", ptrs, num_points, int(sh_degree), antialiased)
-            image, ws, m = _rendered_workspace(L, source, num_points, params, dev, max_entries, st)
+        image, ws = _autograd_forward(ctx, num_points, sh_degree, params, antialiased, max_entries, arrays)
         ctx.save_for_backward(image, ws, world_to_camera, *arrays)
-        ctx.args = (num_points, int(sh_degree), params, bool(antialiased), m)
         return image
 
     @staticmethod
     def backward(ctx, grad_image):
-        image, ws, world_to_camera = ctx.saved_tensors[:3]
-        arrays = ctx.saved_tensors[3:]
-        num_points, sh_degree, params, antialiased, m = ctx.args
-        cloud = dict(zip(FIELDS, (a.detach() for a in arrays)))
-        ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
-        L = abi.load_library()
-        grad_image = _check_grad_image(grad_image, params, dev)
-        need_pose, need = ctx.needs_input_grad[5], ctx.needs_input_grad[6:]
-        grads, rec, pose = None, None, None
-        with torch.cuda.device(dev):
-            st = torch.cuda.current_stream(dev)
-            if any(need):
-                grads, rec = _render_backward(L, ptrs, num_points, sh_degree, antialiased, params, m, image, grad_image,
-                                              ws, dev, need_pose, st)
-            elif need_pose:
-                rec = _records_backward(L, num_points, params, m, grad_image, ws, dev, st)
-            if need_pose:
-                pose = _view_backward(L, ptrs, num_points, sh_degree, antialiased, params, m, rec, ws, dev, st)
-                pose = pose.to(device=world_to_camera.device, dtype=world_to_camera.dtype)
-        out = tuple(grads[k].view_as(a) if n else None for k, a, n in zip(FIELDS, arrays, need))
+        image, ws, world_to_camera, *arrays = ctx.saved_tensors
+        out, pose = _autograd_backward(ctx, "pose", image, ws, arrays, grad_image, None, ctx.needs_input_grad[6:],
+                                       ctx.needs_input_grad[5])
+        if pose is not None:
+            pose = pose.to(device=world_to_camera.device, dtype=world_to_camera.dtype)
         return (None,) * 5 + (pose,) + out
+
+
+def _six_arrays(cloud):
+    """The six arrays of cloud in FIELDS order, with an empty sh for a cloud (of degree 0) that leaves it out."""
+    return [t if t is not None else torch.empty(0, dtype=torch.float32, device=cloud["positions"].device)
+            for t in map(cloud.get, FIELDS)]
+
+
+def render_depth_autograd(cloud, num_points, sh_degree, params, antialiased=False, max_entries=None):
+    """render() and the accumulated depth as one differentiable torch operation: (image, depth0), image bit-identical
+    to render()'s and depth0 (height, width) bit-identical to render_depth()[..., 0]; backward() gives the six arrays of
+    cloud their gradients through both (include/spz_amd.h "render depth backward").  The median depth and the index
+    carry no gradient and are not returned.  Otherwise as render_autograd()."""
+    return _RenderDepthFunction.apply(num_points, sh_degree, params, antialiased, max_entries, *_six_arrays(cloud))
 
 
 def render_autograd(cloud, num_points, sh_degree, params, antialiased=False, max_entries=None, world_to_camera=None):
@@ -1508,12 +1473,7 @@ def render_autograd(cloud, num_points, sh_degree, params, antialiased=False, max
     world_to_camera: a (3, 4) floating-point tensor that replaces the matrix of params (rounded to float32; it must
     still pass the render's checks) and, when it requires grad, receives the gradient to its 12 entries taken as
     independent (include/spz_amd.h "render view backward").  None: params as they are."""
-    arrays = []
-    for k in FIELDS:
-        t = cloud.get(k)
-        if t is None:
-            t = torch.empty(0, dtype=torch.float32, device=cloud["positions"].device)
-        arrays.append(t)
+    arrays = _six_arrays(cloud)
     if world_to_camera is not None:
         return _RenderPoseFunction.apply(num_points, sh_degree, params, antialiased, max_entries, world_to_camera,
                                          *arrays)
@@ -1538,9 +1498,9 @@ def render_depth(cloud, num_points, sh_degree, params, antialiased=False, max_en
     render(), bit for bit.  expected_depth() normalises channel 0.  out: a dict of tensors to write into (depth, index,
     image; a given one is also returned).  cloud, max_entries, return_info (appends total and status) and stream: as
     render(); with status 1 no output is written."""
-    ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
-    return _render_depth(("cloud", ptrs, num_points, int(sh_degree), antialiased), num_points, params, dev, max_entries,
-                         return_image, return_index, out, return_info, stream)
+    source, _, dev = _cloud_source(cloud, num_points, sh_degree, antialiased)
+    return _render_depth(source, num_points, params, dev, max_entries, return_image, return_index, out, return_info,
+                         stream)
 
 
 def render_depth_packed(stream_t, header, params, max_entries=None, return_image=False, return_index=True, out=None,
@@ -1628,8 +1588,8 @@ def score(cloud, num_points, sh_degree, views, antialiased=False, max_entries=No
     workspace is sized for it, and a view whose total is above it adds nothing and gets status 1.  images: also the
     list of the views' images (bit-identical to render()).  return_status: also the int32 status word of every view.
     stream: as render()."""
-    ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
-    return _score(("cloud", ptrs, num_points, int(sh_degree), antialiased), num_points, views, dev, max_entries, images,
+    source, _, dev = _cloud_source(cloud, num_points, sh_degree, antialiased)
+    return _score(source, num_points, views, dev, max_entries, images,
                   return_status, stream)
 
 
@@ -1668,8 +1628,8 @@ def _preprocess(source, n, params, dev, stream):
 def preprocess(cloud, num_points, sh_degree, params, antialiased=False, stream=None):
     """The per-Gaussian records of render() (input order) as CUDA tensors: mean (n, 2), conic (n, 3: A, B, C), opacity,
     rgb (n, 3), depth (+inf: invisible), rect (n, 4 int32: tile x0, y0, x1, y1); and total (the entry count)."""
-    ptrs, dev = _cloud_render_args(cloud, num_points, sh_degree)
-    return _preprocess(("cloud", ptrs, num_points, int(sh_degree), antialiased), num_points, params, dev, stream)
+    source, _, dev = _cloud_source(cloud, num_points, sh_degree, antialiased)
+    return _preprocess(source, num_points, params, dev, stream)
 
 
 def preprocess_packed(stream_t, header, params, stream=None):

@@ -245,6 +245,33 @@ def test_autograd_forward_is_render_and_render_depth(cuda, name):
     check_gradients({k: cloud[k].grad for k in ("positions", "alphas")}, ref, "autograd", ("positions", "alphas"))
 
 
+def autograd_gradients(ref, cuda, loss):
+    """The six arrays' gradients of loss(image, depth0) through render_depth_autograd."""
+    from spz_amd import device as D
+    cloud = {k: v.requires_grad_(True) for k, v in D.to_device(ref["cloud"], cuda).items()}
+    img, d0 = D.render_depth_autograd(cloud, ref["n"], ref["deg"], ref["params"], antialiased=ref["aa"])
+    loss(img, d0).backward()
+    return {k: cloud[k].grad for k in ARRAYS}
+
+
+def test_autograd_with_the_image_alone_in_the_loss(cuda):
+    """Only the image reaches the loss: the six arrays are within the rule of the colour reference (its bound, 8 max|ref32
+    - ref64|; check_gradients here is test_gpu_render_grad's rule over the keys given, autograd returns no records)."""
+    base = TG.reference("sh3")
+    G = torch.as_tensor(base["G"]).to(cuda)
+    got = autograd_gradients(base, cuda, lambda img, d0: (img * G).sum())
+    check_gradients(got, base, "image alone", ARRAYS)
+
+
+def test_autograd_with_the_depth_alone_in_the_loss(cuda):
+    """Only depth0 reaches the loss: colours and sh get exactly 0, the rest is within the rule of the depth reference."""
+    ref = reference("sh3", "depth")
+    GD = torch.as_tensor(ref["GD"]).to(cuda)
+    got = autograd_gradients(ref, cuda, lambda img, d0: (d0 * GD).sum())
+    assert not got["colors"].any() and not got["sh"].any()
+    check_gradients(got, ref, "depth alone", ARRAYS)
+
+
 def test_an_input_changed_in_place_before_the_backward_raises(cuda):
     from spz_amd import device as D
     ref = reference("sh0")
