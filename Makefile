@@ -29,10 +29,10 @@ all: device host python cli oracle
 device: $(LIBDIR)/libspz_amd.so
 host:   $(LIBDIR)/libspz_host.so
 python: $(ROOT)spz_amd/spz$(PYEXT)
-cli:    $(ROOT)spz_amd/bin/spz_tool $(ROOT)spz_amd/bin/dropin_user_test $(ROOT)spz_amd/bin/host_bench
+cli:    $(ROOT)spz_amd/bin/spz_tool $(ROOT)spz_amd/bin/dropin_user_test $(ROOT)spz_amd/bin/host_bench $(ROOT)spz_amd/bin/render_chain_host
 
 DEVICE_SRCS := $(CSRC)/spz_kernels.hip $(CSRC)/spz_abi.hip $(CSRC)/spz_hostpath.hip $(CSRC)/spz_ply_kernels.hip $(CSRC)/spz_median.hip $(CSRC)/spz_exchange.hip $(CSRC)/spz_lz77.hip $(CSRC)/spz_inflate_dev.hip $(CSRC)/spz_place.hip $(CSRC)/spz_filter.hip $(CSRC)/spz_transform.hip $(CSRC)/spz_merge.hip $(CSRC)/spz_sort.hip $(CSRC)/spz_decimate.hip $(CSRC)/spz_tile.hip $(CSRC)/spz_clean.hip $(CSRC)/spz_align.hip $(CSRC)/spz_render.hip $(CSRC)/spz_render_backward.hip $(CSRC)/spz_render_view_backward.hip $(CSRC)/spz_locate.hip $(CSRC)/spz_mesh.hip $(CSRC)/spz_prune.hip $(CSRC)/spz_metrics.hip $(CSRC)/spz_refine.hip $(CSRC)/spz_densify.hip $(CSRC)/spz_photo.hip $(CSRC)/spz_depth_loss.hip $(CSRC)/spz_seed.hip $(CSRC)/spz_plane.hip
-$(LIBDIR)/libspz_amd.so: $(DEVICE_SRCS) $(CSRC)/spz_densify_internal.hpp $(CSRC)/spz_photo_internal.hpp $(CSRC)/spz_image_tile.hpp $(CSRC)/spz_common.hpp $(CSRC)/spz_kernel_params.hpp $(CSRC)/spz_quant.hpp $(CSRC)/spz_sort_internal.hpp $(CSRC)/spz_render_internal.hpp $(CSRC)/spz_view_pass.hpp $(CSRC)/spz_view_backward_core.hpp $(CSRC)/spz_morton_walk.hpp $(CSRC)/spz_block_ops.hpp $(CSRC)/spz_xf.hpp $(CSRC)/spz_lz77_core.hpp $(CSRC)/spz_huff_core.hpp $(CSRC)/spz_inflate_core.hpp $(INC)/spz_amd.h
+$(LIBDIR)/libspz_amd.so: $(DEVICE_SRCS) $(CSRC)/spz_densify_internal.hpp $(CSRC)/spz_photo_internal.hpp $(CSRC)/spz_image_tile.hpp $(CSRC)/spz_common.hpp $(CSRC)/spz_kernel_params.hpp $(CSRC)/spz_quant.hpp $(CSRC)/spz_sort_internal.hpp $(CSRC)/spz_render_internal.hpp $(CSRC)/spz_view_pass.hpp $(CSRC)/spz_view_backward_core.hpp $(CSRC)/spz_preprocess_backward_core.hpp $(CSRC)/spz_morton_walk.hpp $(CSRC)/spz_block_ops.hpp $(CSRC)/spz_xf.hpp $(CSRC)/spz_lz77_core.hpp $(CSRC)/spz_huff_core.hpp $(CSRC)/spz_inflate_core.hpp $(INC)/spz_amd.h
 	mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(DEVICE_SRCS) -ldl
 
@@ -62,6 +62,13 @@ $(ROOT)spz_amd/bin/host_bench: $(ROOT)tools/host_bench.cpp $(INC)/spz_amd_host.h
 	mkdir -p $(ROOT)spz_amd/bin
 	$(CXX) $(CXXFLAGS) -o $@ $(ROOT)tools/host_bench.cpp -L$(LIBDIR) -lspz_host -lspz_amd -lpthread \
 	    -Wl,-rpath,'$$ORIGIN/../lib' -Wl,-rpath,/opt/rocm/lib
+
+# The render backward's two per-Gaussian chains (preprocess_backward_one, view_backward_one: host-and-device functions)
+# built for the host, a stand-alone program that tests/test_render_frustum_host.py runs over its scenes (CPU only).
+$(ROOT)spz_amd/bin/render_chain_host: $(ROOT)tests/cpp/render_chain_host.cpp $(CSRC)/spz_preprocess_backward_core.hpp $(CSRC)/spz_view_backward_core.hpp $(CSRC)/spz_render_internal.hpp $(CSRC)/spz_common.hpp $(INC)/spz_amd.h
+	mkdir -p $(ROOT)spz_amd/bin
+	$(HIPCC) --cuda-host-only -x hip -O2 -std=c++17 -ffp-contract=off -Wall -Wno-unused-function -I$(INC) -o $@ \
+	    $(ROOT)tests/cpp/render_chain_host.cpp
 
 oracle:
 	$(MAKE) -C $(ROOT)oracle

@@ -834,8 +834,8 @@ int spz_amd_plane_host(const uint8_t *d_stream, size_t size, const spz_amd_heade
  *      det)))), mid = (a + c) / 2.  Tiles are 16x16: rect x0 = clamp(floor((m_x - radius) / 16), 0, tiles_x), x1 =
  *      clamp(floor((m_x + radius + 15) / 16), 0, tiles_x), likewise y; empty: invisible.  rgb = max(0, C0 colour + the
  *      higher sh bands of 3DGS (constants and band order) at normalize(p - c), c = -R^T t, + 0.5).  opacity =
- *      sigmoid(alpha).  A non-finite mean, conic or radius: invisible.  An invisible Gaussian's record is all zero
- *      but for depth = +inf.
+ *      sigmoid(alpha).  A non-finite mean, conic, radius or opacity (a NaN alpha): invisible.  An invisible
+ *      Gaussian's record is all zero but for depth = +inf.
  *      Order: within a tile, ascending (f32 depth z, input index).  Blend per pixel (u, v), d = (u - m_x, v - m_y),
  *      T = 1, C = 0, in that order: power = -0.5 (A dx^2 + C dy^2) - B dx dy, skip if power > 0; a = min(0.99,
  *      opacity exp(power)), skip if a < 1/255; T' = T (1 - a), stop if T' < 1e-4; C += T a rgb; T = T'.

@@ -182,7 +182,9 @@ __global__ __launch_bounds__(kPreBlock) void spz_render_preprocess_kernel(const 
       const double disc = mid * mid - det;
       const double lam = mid + sqrt(disc > 0.1 ? disc : 0.1);
       const double radius = ceil(3.0 * sqrt(lam));
-      visible = isfinite(mx) && isfinite(my) && isfinite(radius) && isfinite(ca) && isfinite(cb) && isfinite(cc);
+      // the opacity too: fminf(0.99f, NaN) is 0.99f, so a NaN alpha would blend as an opaque Gaussian
+      visible = isfinite(mx) && isfinite(my) && isfinite(radius) && isfinite(ca) && isfinite(cb) && isfinite(cc) &&
+                isfinite(opacity);
       if (visible) {
         const double tw = (double)cam.tiles_x, th = (double)cam.tiles_y;
         const double x0 = clampd(floor((mx - radius) / 16.0), 0.0, tw), x1 = clampd(floor((mx + radius + 15.0) / 16.0), 0.0, tw);

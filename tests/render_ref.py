@@ -47,7 +47,8 @@ def tiles(cam):
 
 def preprocess(cloud, sh_degree, cam, antialiased=False):
     """The records (input order): mean (n, 2), conic (n, 3), opacity, rgb (n, 3), depth (+inf: invisible), rect (n, 4)
-    as float32 / int64, plus visible (bool) and r3 = 3 sqrt(lambda) before the ceil (f64)."""
+    as float32 / int64, plus visible (bool), r3 = 3 sqrt(lambda) before the ceil, camera_xyz = R p + t, det0 and a0c0
+    (all f64)."""
     n = cloud["alphas"].size
     P = cloud["positions"].reshape(n, 3).astype(np.float64)
     R, t = cam["R"], cam["t"]
@@ -96,6 +97,7 @@ def preprocess(cloud, sh_degree, cam, antialiased=False):
         r3 = 3.0 * np.sqrt(lam)
         radius = np.ceil(r3)
         vis &= np.isfinite(mx) & np.isfinite(my) & np.isfinite(radius) & np.isfinite(conic).all(axis=1)
+        vis &= np.isfinite(op)  # a NaN alpha: min(0.99, NaN) has no one reading, so the Gaussian is not blended at all
         tw, th = tiles(cam)
         x0 = np.clip(np.floor((mx - radius) / 16.0), 0, tw)
         x1 = np.clip(np.floor((mx + radius + 15.0) / 16.0), 0, tw)
@@ -115,6 +117,9 @@ def preprocess(cloud, sh_degree, cam, antialiased=False):
         "rect": np.where(vis[:, None], np.stack([x0, y0, x1, y1], axis=1), 0).astype(np.int64),
         "visible": vis,
         "r3": r3,
+        "camera_xyz": np.stack([x, y, z], axis=1),  # p_c = R p + t, for tests that sort Gaussians by where they lie
+        "det0": det0,                               # of the 2D covariance before the 0.3, and the product it is cut from
+        "a0c0": (a - 0.3) * (c - 0.3),
     }
     return rec
 
